@@ -19,12 +19,18 @@ total work is fixed => "strong".  The N = 1 point of THAT job is the extra key `
 480-frame morph on one GPU, set-up and writer inside), so an N-sweep is read against it and not against the chained headline; every
 N > 1 line carries its own measured serial part (`amdahl`: set-up, broadcast, frames).
 
-One JSON line on rank 0 (driver contract) with
+A plain run at N = 1 does only what `value` needs: the inputs, the pool, the warm-up, the --steps timed steps, --dump-outputs when given
+(dump_outputs), and the result line (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, the pool selection, the configuration).
+Everything else below, and every extra key of the line (`value_unselected`, `value_step_synchronous`, `pairs_in_one_call`, `step_ms`, `roofline`, `sequential_fps`,
+`resident_pair_fps*`, `pair_setup_ms`, `scaling_baseline*`, `value_photo`, `value_from_host_images`, `h2d`, `kernels`, `cpu_baseline`, `parity_check`,
+`content_sensitivity`, `odd_width`, `ceilings`, `cfg3_4k`), is measured with --full only; --full --headline-only stops before the extras.
+
+One JSON line on rank 0 (driver contract); with --full also
   roofline      (`isolated` inside it: the same kernel's launches with nothing else on the GPU, measured after the timed region)
                 the dominant kernel (fused create_map + remap of both sources): algorithmic bytes per launch = 16 B/px (SURVEY.md
                 8d, faithful path: id 4 + src 3 + 3 in, warped 3 + 3 out) x pixels, / the kernel's average launch duration
-                measured live with HIP events attached to the dispatch on the library's stream (one launch in seven of the timed
-                region).  The kernel moves about what the contract counts: no id map (the raster reaches it as one id byte per pixel
+                measured live with HIP events attached to the dispatch on the library's stream (one launch in seven of the headline's
+                steps, timed once more after `value`'s timed region, which carries no events).  The kernel moves about what the contract counts: no id map (the raster reaches it as one id byte per pixel
                 + 2.5 KB of record slots per tile, ~3.6 B/px) and no blend mask (the level-0 blend kernels derive it from m2) — 12 B/px of images; `moved_*` states
                 that.  Only when the mask rider is on (POPPY_HIP_LBMASK_RIDER) `frac_with_rider` adds its 8 B/px;
   cpu_baseline  oracle/ (CPU restatement, "port"): 20 chained 1080p frames of pair 0 from the GPU's own pair state on 1 thread (`value`),
@@ -456,6 +462,46 @@ def run_cfg3_4k(capi, torch, dev, steps, check=True):
     return out
 
 
+DUMP_BUDGET = 64 << 20         # bytes, every file of --dump-outputs together
+DUMP_SEED = 20240601           # the sampled pixel positions of frame_samples.npy
+
+
+def dump_outputs(path, pool, ptrs):
+    """--dump-outputs PATH: what the timed path hands its caller in its last step — every frame of every pair of the step, (H, W, 3) u8 each, through the
+    writer — as .npy files in float32 / float64, under DUMP_BUDGET in all.  Every timed step renders the same pairs from the same resident images, so the
+    last step's frames are those of one more such step on the same pool through the same entry point (poppy_hip_pool_submit_pairs), made after the timed
+    region with a writer that keeps them instead of the one that only counts them; the timed steps themselves are untouched.
+      frame_sums.npy     float64 (pairs, frames): the sum of every byte of each frame
+      frame_samples.npy  float32 (pairs, frames, K, 3): K pixels of each frame at fixed positions (a seeded draw without replacement, the same for every frame)
+      last_frame.npy     float32: the step's last frame (last pair, last frame) in full — every s-th row and column when a full frame would not fit"""
+    npairs = len(ptrs)
+    k = max(1, min(4096, W * H, (DUMP_BUDGET * 3 // 8) // (npairs * FRAMES * 3 * 4)))
+    s = 1
+    while -(-H // s) * -(-W // s) * 3 * 4 > DUMP_BUDGET // 2:
+        s += 1
+    pos = np.sort(np.random.default_rng(DUMP_SEED).choice(W * H, size=k, replace=False))
+    rows, cols = pos // W, pos % W
+    sums = np.zeros((npairs, FRAMES), np.float64)
+    samples = np.zeros((npairs, FRAMES, k, 3), np.float32)
+    seen = np.zeros((npairs, FRAMES), np.int64)
+    last = [None]
+
+    def keep(p, j, f):            # called on the pool's threads; f is valid only during the call
+        sums[p, j] = float(f.sum(dtype=np.uint64))
+        samples[p, j] = f[rows, cols]
+        if (p, j) == (npairs - 1, FRAMES - 1):
+            last[0] = f[::s, ::s].astype(np.float32)
+        seen[p, j] += 1
+    pool.submit_pairs(ptrs, keep, phase=-1.0, inputs_on_device=True, w=W, h=H)
+    pool.wait()
+    assert (seen == 1).all() and last[0] is not None, "the dumped step did not hand every frame to the writer exactly once"
+    arrays = {"frame_sums": sums, "frame_samples": samples, "last_frame": last[0]}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -463,7 +509,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-4k", action="store_true", help="skip the configs[2] (3840x2160 x 120) object")
-    ap.add_argument("--headline-only", action="store_true", help="only the timed region (the command the rocprofv3 summaries under profiles/ are taken from)")
+    ap.add_argument("--full", action="store_true", help="N = 1: everything beyond the headline as well — the unselected pool, the step-synchronous form, the roofline's own timed "
+                    "region, the extras (sequential, resident, set-up, scaling, photographs, host images, kernel groups, CPU baseline and parity checks, content, odd widths, ceilings, "
+                    "configs[2] at 4K).  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: only the headline's timed regions, none of the extras (the command the rocprofv3 summaries under profiles/ are taken from)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="N = 1: after the timed steps, write the frames the timed path hands its writer in its last step as .npy files "
+                    "(float32 / float64, a fixed sample, under 64 MB in all) into DIR: see dump_outputs")
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--frames", type=int, default=None, help="frames per sequence (default 60)")
@@ -476,6 +527,8 @@ def main():
     ap.add_argument("--no-cpu-end-to-end", action="store_true", help="skip the 512x512x30 whole-morph CPU figure (~40 s of oracle time)")
     ap.add_argument("--contexts", type=int, default=0, help="contexts (host threads) a rank's pairs are spread over; default 6 = one per pair of a step (round 5, ms per step of 6 pairs on one box, ten pools each: 3 contexts 59.2 - 60.4 with the chains of a set-up one after the other — side by side one pool in four ran at 75 -, 4: 57.2 - 59.3, 5: 57.1 - 60.5, 6: 55.9 - 59.4; profiles/r05_notes.md section 6)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global W, H, FRAMES, PAIRS
     if args.width and args.height:
         W, H = args.width, args.height
@@ -510,6 +563,10 @@ def main():
     if selftest:
         os.environ.setdefault("POPPY_HIP_SHARD_WORLD1", "1")
         args.shard_setup = True
+    if args.dump_outputs and (world > 1 or selftest):
+        if rank == 0:
+            print("bench.py: --dump-outputs is written by the --gpus 1 line only", file=sys.stderr)
+        sys.exit(2)
     if world > 1 or selftest:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29531")
@@ -534,7 +591,6 @@ def bench_single(args, torch, capi, dev, local):
     pairs_host = [synth_pair(W, H, k) for k in range(PAIRS)]
     pairs_dev = [(torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)) for a, b in pairs_host]
     torch.cuda.synchronize()
-    ctx = capi.Context(local, number_of_frames=FRAMES)
     # The step's pairs are independent (the CLI's pairs loop, src/poppy.cpp:266-328, has no cross-pair state): the library's pool
     # renders them on CONTEXTS contexts of this GPU, one host thread each, so that one pair's set-up runs beside another's frames.
     ptrs = [(ta.data_ptr(), tb.data_ptr()) for ta, tb in pairs_dev]
@@ -565,44 +621,21 @@ def bench_single(args, torch, capi, dev, local):
         torch.cuda.synchronize()
         return n_, time.perf_counter() - t0_, per_step
 
-    plain = capi.Pool([local], contexts_per_device=args.contexts, number_of_frames=FRAMES)
-    plain.morph_pairs_device_counted(ptrs, W, H, -1.0)                    # allocates
-    n_plain, dt_plain, _ = timed_region(plain, False)
-    # the same pairs handed to the pool in ONE call (informational, not `value`): the contexts take pairs off a shared counter and run out of step — one pair's set-up
-    # beside other pairs' frames — where the bench's steps start six set-ups together and then render together
-    torch.cuda.synchronize()
-    t1c = time.perf_counter()
-    n_one = plain.morph_pairs_device_counted(ptrs * args.steps, W, H, -1.0)
-    torch.cuda.synchronize()
-    dt_one = time.perf_counter() - t1c
-    plain.close()
+    # the headline: the pool, the warm-up, the timed steps — all a plain run does besides --dump-outputs and the result line
     pool = capi.Pool([local], contexts_per_device=args.contexts, tuned_for=(W, H), number_of_frames=FRAMES)
     pool_selection = {"candidates_ms_per_batch": [round(x, 2) for x in pool.candidates_ms], "kept": pool.kept, "made_by": "poppy_hip_pool_create_tuned",
                       "what": "pools the library made at start-up and timed on its built-in calibration batch (two pairs per context, twice); the fastest is the pool"}
-    written, dt, _ = timed_region(pool, True)
-    warp_ms, warp_n = next(((ms, c) for nm, ms, c in pool.timing_summary() if nm == "warp"), (0.0, 0))
-    pool.set_timing(0)
-    n_sync, dt_sync, step_ms = timed_region(pool, False, queued=False)
+    written, dt, _ = timed_region(pool, False)
     assert written == args.steps * PAIRS * FRAMES, (written, args.steps * PAIRS * FRAMES)
     fps = written / dt
-    roof = roofline_of(pool, warp_ms, warp_n, W, H)
-    pool.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pool, ptrs)
 
     out = {
         "metric": "morph frames/sec at 1080p, 60-frame sequence; Mpix/s warped" if (W, H, FRAMES) == (1920, 1080, 60) else f"morph frames/sec at {W}x{H}, {FRAMES}-frame sequence; Mpix/s warped",
         "value": round(fps, 2), "unit": "frames/s", "mpix_per_s": round(fps * P / 1e6, 1),
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "value_unselected": round(n_plain / dt_plain, 2),
-        "value_step_synchronous": {"fps": round(n_sync / dt_sync, 2), "ms_per_step": round(dt_sync / args.steps * 1e3, 3),
-                                   "what": "the same pool, the same steps, but every step waits for its own last frame before the next batch is handed in "
-                                           "(poppy_hip_pool_morph_pairs per step): `value`'s definition up to round 5 — the contexts then start every step with a round of "
-                                           "set-ups together; `value` queues the steps (poppy_hip_pool_submit_pairs) and waits once, at the end of the timed region"},
-        "pairs_in_one_call": {"fps": round(n_one / dt_one, 2), "pairs": len(ptrs) * args.steps,
-                              "what": "the timed region's pairs (steps x pairs per step) handed to the unselected pool in ONE poppy_hip_pool_morph_pairs call instead of one call per step: "
-                                      "informational — the pool without any step structure; not `value`"},
         "pool_selection": pool_selection,
-        "step_ms": {"min": round(min(step_ms), 3), "median": round(sorted(step_ms)[len(step_ms) // 2], 3), "max": round(max(step_ms), 3),
-                    "what": "the steps of `value_step_synchronous` one by one (diagnostic; the queued steps of `value` have no ends of their own)"},
         "timed_region_s": round(dt, 3),
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "scaling_note": "the --gpus N lines shard ONE fixed 480-frame 1080p morph by frame range (total work fixed: strong); the N = 1 point of that series is "
@@ -617,11 +650,47 @@ def bench_single(args, torch, capi, dev, local):
                                "(pair set-up from the raw images + 60 chained frames handed to a writer through pinned host memory), pyramid_levels 64",
                    "pairs_per_step": PAIRS, "steps_queued": True, "contexts": args.contexts, "frames_per_pair": FRAMES, "mode": "chain", "includes": ["pair set-up", "frame loop", "writer hand-off (D2H)"],
                    "parallelism": "1 GPU"},
-        "roofline": roof,
     }
-    if args.headline_only:
-        ctx.close()
+    if not args.full:
+        pool.close()
         return out
+
+    # ---- --full: the headline's other forms, each a timed region of its own after `value`'s --------------------------
+    # the roofline: the same steps on the same pool with HIP events on the roofline kernel's own dispatch, one launch in seven, on the stream it is launched on
+    n_roof, _, _ = timed_region(pool, True)
+    assert n_roof == args.steps * PAIRS * FRAMES, (n_roof, args.steps * PAIRS * FRAMES)
+    warp_ms, warp_n = next(((ms, c) for nm, ms, c in pool.timing_summary() if nm == "warp"), (0.0, 0))
+    pool.set_timing(0)
+    out["roofline"] = roofline_of(pool, warp_ms, warp_n, W, H)
+    n_sync, dt_sync, step_ms = timed_region(pool, False, queued=False)
+    pool.close()
+    plain = capi.Pool([local], contexts_per_device=args.contexts, number_of_frames=FRAMES)
+    plain.morph_pairs_device_counted(ptrs, W, H, -1.0)                    # allocates
+    n_plain, dt_plain, _ = timed_region(plain, False)
+    # the same pairs handed to the pool in ONE call (informational, not `value`): the contexts take pairs off a shared counter and run out of step — one pair's set-up
+    # beside other pairs' frames — where the bench's steps start six set-ups together and then render together
+    torch.cuda.synchronize()
+    t1c = time.perf_counter()
+    n_one = plain.morph_pairs_device_counted(ptrs * args.steps, W, H, -1.0)
+    torch.cuda.synchronize()
+    dt_one = time.perf_counter() - t1c
+    plain.close()
+    out.update({
+        "value_unselected": round(n_plain / dt_plain, 2),
+        "value_step_synchronous": {"fps": round(n_sync / dt_sync, 2), "ms_per_step": round(dt_sync / args.steps * 1e3, 3),
+                                   "what": "the same pool, the same steps, but every step waits for its own last frame before the next batch is handed in "
+                                           "(poppy_hip_pool_morph_pairs per step): `value`'s definition up to round 5 — the contexts then start every step with a round of "
+                                           "set-ups together; `value` queues the steps (poppy_hip_pool_submit_pairs) and waits once, at the end of the timed region"},
+        "pairs_in_one_call": {"fps": round(n_one / dt_one, 2), "pairs": len(ptrs) * args.steps,
+                              "what": "the timed region's pairs (steps x pairs per step) handed to the unselected pool in ONE poppy_hip_pool_morph_pairs call instead of one call per step: "
+                                      "informational — the pool without any step structure; not `value`"},
+        "step_ms": {"min": round(min(step_ms), 3), "median": round(sorted(step_ms)[len(step_ms) // 2], 3), "max": round(max(step_ms), 3),
+                    "what": "the steps of `value_step_synchronous` one by one (diagnostic; the queued steps of `value` have no ends of their own)"},
+    })
+    if args.headline_only:
+        return out
+
+    ctx = capi.Context(local, number_of_frames=FRAMES)
 
     # ---- extras, all outside the timed region -------------------------------------------------------------------------
     ta, tb = pairs_dev[0]

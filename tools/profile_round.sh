@@ -21,7 +21,7 @@ done
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/${tag}_setup_trace -o t -- python3 $R/tools/experiments/pair_begin_time.py > $O/${tag}_setup.log 2>&1
 cd "$R"
 bash tools/make_profile_docs.sh ${tag} > gpurun_out/${tag}_docs.log 2>&1          # (on the box: bench.py below reads what this writes)
-python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
+python3 bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 cp gpurun_out/${tag}_bench.json profiles/${tag}_bench.json
 mkdir -p gpurun_out/${tag}_profiles
 cp profiles/${tag}_* profiles/${tag%%_*}_warp_pmc.json profiles/${tag%%_*}_warp_facts.json gpurun_out/${tag}_profiles/ 2>/dev/null
