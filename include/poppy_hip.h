@@ -244,6 +244,18 @@ int poppy_hip_pair_begin(poppy_hip_ctx* ctx, const uint8_t* bgr1, size_t stride1
 /* poppy_hip_pair_begin with the two raw images already in this GPU's memory (tight rows, width*3 bytes each): the throughput
  * path of a caller whose decoder or previous stage left the images in HBM, and what bench.py times.                      */
 int poppy_hip_pair_begin_device(poppy_hip_ctx* ctx, const void* d_bgr1, const void* d_bgr2, int width, int height);
+/* The set-up of the NEXT pair of the CLI's loop (src/poppy.cpp:326: img1 = corrected2.clone()): image 1 = the resident pair's second image as
+ * poppy::morph hands it back (corrected2, what poppy_hip_pair_corrected2 returns; the ALIGNED image under auto-align), image 2 = bgr.  The same
+ * result in every bit as poppy_hip_pair_begin(ctx, corrected2, bgr).  Image 1's filter chain (foreground, dft_detail2, ORB input, the detector's
+ * pyramid and FAST candidates, src/extractor.cpp:33-83,136-229) is not run again when it is the image the resident pair's own set-up ran it on:
+ * after poppy_hip_pair_begin / _device / _next without auto-align, with no other call in between that filters, detects or replaces the resident
+ * images (poppy_hip_render*, _morph_frames, _pair_reset and the frame accessors keep it).  Only nfeatures depends on the pair (quotas, retainBest,
+ * Harris, angles: src/extractor.cpp:40-45).  POPPY_E_STATE without a resident pair; POPPY_E_ARG when the size differs from the resident pair's.
+ * _device: image 2 in this GPU's memory, tight rows. */
+int poppy_hip_pair_begin_next(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height);
+int poppy_hip_pair_begin_next_device(poppy_hip_ctx* ctx, const void* d_bgr, int width, int height);
+/* image chains run and reused by the set-ups of this context since it was created (diagnostic; either pointer may be NULL) */
+int poppy_hip_chain_counts(poppy_hip_ctx* ctx, unsigned long long* chains_run, unsigned long long* chains_reused);
 /* A poppy_write_cb that only counts: ++*(long long*)user.  For callers (and the benchmark) that want the frame hand-off —
  * every frame downloaded into pinned host memory and presented to the writer — without a consumer of their own.           */
 void poppy_count_frames_cb(void* user, const uint8_t* bgr, int width, int height, size_t stride);
@@ -389,6 +401,27 @@ int poppy_hip_pool_timing_summary(poppy_hip_pool* pool, const char** names, floa
 int poppy_hip_pool_warp_counts(poppy_hip_pool* pool, unsigned long long* fused, unsigned long long* tiled, unsigned long long* general);
 /* poppy_hip_mask_rider of the pool's contexts (they share settings and geometry) */
 int poppy_hip_pool_mask_rider(poppy_hip_pool* pool);
+/* The CLI's loop over an image list (src/poppy.cpp:266-328) on ONE context: pair k = (image k, image k + 1), where image k of pair k > 0 is
+ * the corrected2 that pair k - 1 handed back (:326; the aligned image under auto-align).  The same result in every bit as
+ *     for k: poppy_hip_morph(ctx, img1, img_{k+1}, .., phase, 0, ..); img1 = corrected2 (poppy_hip_pair_corrected2 when auto-align is on)
+ * with pair 0 set up by poppy_hip_pair_begin and every later pair by poppy_hip_pair_begin_next: each image's filter chain runs once
+ * (poppy_hip_chain_counts: n_images chains, n_images - 2 of them reused, with auto-align off).
+ *   source          called on the calling thread, once per image, in index order: *bgr, *stride, *width, *height of image `image_index`;
+ *                   return 0.  The pointer must stay valid until source is called for image index + 2, or until this call returns.
+ *                   inputs_on_device != 0: device pointers of this context's GPU, tight rows (*stride is ignored).
+ *   canvas          canvas_width = canvas_height = 0: every image must have image 0's size (poppy::morph takes one size,
+ *                   src/poppy.cpp:313-316), else POPPY_E_ARG.  Otherwise every image (at most the canvas in each side) is placed into
+ *                   the canvas by blur_margin's rule on the device, the bytes poppy_hip_blur_margin(img, canvas) returns (src/util.cpp:574-602).
+ *   phase           < 0: default chained mode; 0 < phase < 1: one phase-mode frame per pair.  0 or 1 with more than two images:
+ *                   POPPY_E_UNSUPPORTED (poppy::morph returns before it sets corrected2, :54-70); with two images as poppy_hip_morph.
+ *   write           (pair, frame) in order, on the calling thread; NULL keeps the frames on the device.
+ *   morph_distances the printed morph distance of every pair (n_images - 1 doubles, may be NULL).
+ * The first pair that is not POPPY_OK ends the call with its status, after writing what poppy_hip_morph writes (the linear-blend frames of
+ * POPPY_E_NOMATCH); *pairs_done (may be NULL) = the pairs that returned POPPY_OK.  No --distance mode.                                   */
+typedef int (*poppy_image_source_cb)(void* user, int image_index, const uint8_t** bgr, size_t* stride, int* width, int* height);
+int poppy_hip_morph_list(poppy_hip_ctx* ctx, int n_images, int canvas_width, int canvas_height, double phase, int inputs_on_device,
+                         poppy_image_source_cb source, poppy_write_pair_cb write, void* user,
+                         double* morph_distances, int* pairs_done);
 /* a poppy_write_pair_cb that only counts, atomically: ++*(long long*)user */
 void poppy_count_pair_frames_cb(void* user, int pair_index, int frame_index, const uint8_t* bgr, int width, int height, size_t stride);
 int poppy_hip_morph_sharded(const int* devices, int n_devices, const poppy_settings* settings,

@@ -37,6 +37,7 @@ SYMBOLS = [
     "poppy_hip_pair_begin_sharded", "poppy_hip_sharded_setups", "poppy_hip_pair_begin_sharded_local", "poppy_hip_pair_state_bytes", "poppy_hip_pair_export_device", "poppy_hip_pair_import_device", "poppy_hip_morph_sharded", "poppy_hip_morph_pairs",
     "poppy_dft_plan", "poppy_hip_pair_begin_device", "poppy_count_frames_cb", "poppy_hip_morph", "poppy_hip_pair_distance", "poppy_printed_morph_distance", "poppy_hypotf_selfcheck",
     "poppy_hip_orb_detect", "poppy_hip_foreground", "poppy_hip_median_blur", "poppy_match_points", "poppy_hip_pair_begin_prefiltered", "poppy_hip_pair_begin", "poppy_hip_pair_begin_info", "poppy_hip_orb_input", "poppy_hip_gabor_field", "poppy_hip_set_gabor_direct", "poppy_hip_set_setup_chains", "poppy_hip_gabor_doubt", "poppy_radial_gradient", "poppy_radial_mask", "poppy_gabor_tables", "poppy_pyr_tail_plan", "poppy_hip_blur_margin", "poppy_hip_pair_points",
+    "poppy_hip_pair_begin_next", "poppy_hip_pair_begin_next_device", "poppy_hip_chain_counts", "poppy_hip_morph_list",
 ]
 
 
@@ -142,6 +143,10 @@ def lib():
         L.poppy_hip_morph_sharded.argtypes = [vp, i, vp, vp, sz, vp, sz, i, i, i, vp, vp, vp, sz]
         L.poppy_hip_morph_pairs.argtypes = [vp, i, i, vp, i, i, i, d, vp, vp, vp, vp, sz]
         L.poppy_hip_pair_begin_device.argtypes = [vp, vp, vp, i, i]
+        L.poppy_hip_pair_begin_next.argtypes = [vp, vp, sz, i, i]
+        L.poppy_hip_pair_begin_next_device.argtypes = [vp, vp, i, i]
+        L.poppy_hip_chain_counts.argtypes = [vp, vp, vp]
+        L.poppy_hip_morph_list.argtypes = [vp, i, i, i, d, i, vp, vp, vp, vp, vp]
         L.poppy_hip_pair_begin_sharded.argtypes = [vp, vp, vp, i, i, i]
         L.poppy_hip_pair_begin_sharded_local.argtypes = [C.POINTER(vp), i, vp, vp, i, i, i]
         L.poppy_hip_morph.argtypes = [vp, vp, sz, vp, sz, i, i, d, i, vp, vp, vp]
@@ -273,6 +278,7 @@ def radial_mask(w, h):
 WRITE_INDEXED_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_size_t)
 PAIR_SOURCE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 WRITE_PAIR_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_size_t)
+IMAGE_SOURCE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int))
 
 
 def comm_id():
@@ -669,6 +675,69 @@ class Context:
         """Raw BGR pair already in this GPU's memory (device pointers, tight rows)."""
         self._chk(lib().poppy_hip_pair_begin_device(self.h, d1, d2, w, h), "pair_begin_device")
         self.w, self.h_ = w, h
+
+    def pair_begin_next(self, bgr):
+        """The next pair of the CLI's loop: image 1 = the resident pair's corrected2, image 2 = bgr (image 1's filter chain is reused when it can be)."""
+        b = np.ascontiguousarray(bgr, np.uint8)
+        h, w = b.shape[:2]
+        self._chk(lib().poppy_hip_pair_begin_next(self.h, _p(b), w * 3, w, h), "pair_begin_next")
+        self.w, self.h_ = w, h
+
+    def pair_begin_next_device(self, d_bgr, w, h):
+        """pair_begin_next with image 2 already in this GPU's memory (device pointer, tight rows)."""
+        self._chk(lib().poppy_hip_pair_begin_next_device(self.h, d_bgr, w, h), "pair_begin_next_device")
+        self.w, self.h_ = w, h
+
+    def chain_counts(self):
+        """(image chains run, image chains reused) by this context's pair set-ups since it was created."""
+        run, reused = C.c_ulonglong(0), C.c_ulonglong(0)
+        self._chk(lib().poppy_hip_chain_counts(self.h, C.byref(run), C.byref(reused)), "chain_counts")
+        return run.value, reused.value
+
+    def morph_list(self, images, phase=-1.0, canvas=None, collect=True, counted=False, on_device=False, write=None):
+        """The CLI's loop over an image list in one call (poppy_hip_morph_list): returns (status, frames per pair, printed distance per pair,
+        pairs done).  status is POPPY_OK (0) or POPPY_E_NOMATCH (-5, the failing pair's fallback frames written); anything else raises.
+        images: HxWx3 uint8 arrays, or with on_device=True (device pointer, w, h) tuples.  canvas: (width, height) to pad every image into by
+        blur_margin's rule, None = one size for all.  counted: frames go to the library's counting writer; frames per pair is then [total].
+        write: optional callable(pair, frame, view) instead of collecting (the view of the pinned host copy is valid during the call)."""
+        imgs = list(images) if on_device else [np.ascontiguousarray(a, np.uint8) for a in images]
+        n = len(imgs)
+
+        def src(user, k, pp, ps, pw, ph):
+            if on_device:
+                ptr, w, h = imgs[k]
+                pp[0], ps[0], pw[0], ph[0] = ptr, w * 3, w, h
+            else:
+                a = imgs[k]
+                pp[0], ps[0], pw[0], ph[0] = a.ctypes.data, a.shape[1] * 3, a.shape[1], a.shape[0]
+            return 0
+        frames = [[] for _ in range(max(n - 1, 0))]
+
+        def wr(user, k, j, ptr, ww, hh, stride):
+            view = np.ctypeslib.as_array(ptr, shape=(hh, stride))[:, :ww * 3].reshape(hh, ww, 3)
+            if write is not None:
+                write(k, j, view)
+            else:
+                frames[k].append(view.copy())
+        fs = IMAGE_SOURCE_CB(src)
+        count = C.c_longlong(0)
+        if counted:
+            wcb, user = C.cast(lib().poppy_count_pair_frames_cb, C.c_void_p), C.cast(C.byref(count), C.c_void_p)
+        else:
+            fw = WRITE_PAIR_CB(wr) if (collect or write is not None) else None
+            wcb, user = (C.cast(fw, C.c_void_p) if fw else None), None
+        dist = np.full(max(n - 1, 1), np.nan)
+        done = C.c_int(0)
+        cw, ch = canvas if canvas is not None else (0, 0)
+        rc = lib().poppy_hip_morph_list(self.h, n, int(cw), int(ch), float(phase), int(on_device), C.cast(fs, C.c_void_p), wcb, user,
+                                        _p(dist), C.byref(done))
+        if rc not in (0, -5):
+            self._chk(rc, "morph_list")
+        if canvas is not None:
+            self.w, self.h_ = int(cw), int(ch)
+        elif n:
+            self.w, self.h_ = (imgs[0][1], imgs[0][2]) if on_device else (imgs[0].shape[1], imgs[0].shape[0])
+        return rc, ([count.value] if counted else frames), [float(x) for x in dist[:max(n - 1, 0)]], done.value
 
     def morph_frames_counted(self, phase=-1.0):
         """The frame loop with every frame handed to the library's counting writer (pinned host hand-off, no Python per frame)."""

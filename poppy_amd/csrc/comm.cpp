@@ -153,6 +153,7 @@ int poppy_hip_pair_broadcast(poppy_hip_ctx* c, int root, int W, int H) {
     if (!c->comm.load()) return fail(c, POPPY_E_STATE, c->comm_aborted.load() ? "the communicator was aborted" : "no communicator (poppy_hip_comm_init)");
     if (root < 0 || root >= c->comm_world || W <= 0 || H <= 0) return fail(c, POPPY_E_ARG, "bad root / geometry");   // the same on every rank
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     int rc;
     if (c->comm_rank == root) {
         if (!c->pair_ready || c->W != W || c->H != H) rc = fail(c, POPPY_E_STATE, "the root has no resident pair of this geometry");
@@ -218,6 +219,7 @@ int poppy_hip_pair_import_device(poppy_hip_ctx* c, const void* d_src, size_t byt
     if (!c || !d_src || W <= 0 || H <= 0) return POPPY_E_ARG;
     if (bytes < pair_state_bytes(W, H)) return fail(c, POPPY_E_ARG, "buffer smaller than poppy_hip_pair_state_bytes");
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     int rc = alloc_pair(c, W, H); if (rc) return rc;
     c->pair_ready = false;
     HIPCHK(c, hipMemcpyAsync(c->arena, d_src, c->arena_bytes, hipMemcpyDeviceToDevice, c->stream));
@@ -280,6 +282,7 @@ std::atomic<unsigned long long> g_sharded_setups{0};     // protocol runs in thi
 
 int setup_sharded(poppy_hip_ctx* c, Transport& T, const void* d1, const void* d2, int W, int H, int root) {
     g_sharded_setups.fetch_add(1);
+    chain_touch(c);
     if (c->cfg.enable_auto_align) return fail(c, POPPY_E_UNSUPPORTED, "the sharded set-up does not take auto-align (image 2 changes after the match)");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t P = (size_t)W * H;

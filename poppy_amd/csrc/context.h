@@ -104,6 +104,17 @@ struct poppy_hip_ctx {
     bool writer_attached = false;                   // a multi-frame call with a writer is in progress
     double wait_ms[4] = {0, 0, 0, 0};               // host waits inside submit_frame since the context was made (POPPY_SEQ_TIMING prints the per-sequence share)
     ForegroundFilter foreground, foreground_b;      // two instances: the images of a pair are filtered side by side
+    // The two chain slots (slot 0 = foreground + orb, slot 1 = foreground_b + orb_b; chain_fg / chain_orb below).  After a set-up from raw images the slot
+    // chain_b holds the SECOND image's chain state (its detail, its detector's atlas and fetched candidates): poppy_hip_pair_begin_next takes it over in
+    // the role of image 1 instead of filtering that image again when kept_gen == chain_gen.  chain_gen moves in every entry point that uses a slot or
+    // replaces the resident images (chain_touch), so a state is only reused while nothing else can have changed it.
+    int chain_b = 1;
+    unsigned long long chain_gen = 1, kept_gen = 0;
+    double kept_detail = 0;                         // dft_detail2 of the kept image
+    unsigned long long chains_run = 0, chains_reused = 0;      // poppy_hip_chain_counts
+    // poppy_hip_morph_list: canvas scratch of the device-side blur_margin (canvas, 32-bit row sums, taps) and the two padded images
+    uint8_t* bm_canvas = nullptr; uint32_t* bm_tmp = nullptr; int* bm_taps = nullptr; size_t bm_bytes = 0;
+    uint8_t* list_img[2] = {nullptr, nullptr}; size_t list_img_bytes = 0;
     hipStream_t aux_stream = nullptr;
     hipEvent_t setup_ev = nullptr;                  // "the second image's medians are through" (pair set-up: gabor2 starts there)
     hipEvent_t c2_up_ev = nullptr;                  // "the second host image is in c2" (recorded on aux_stream by the second chain's thread; gabor2 on copy_stream waits for it)
@@ -175,3 +186,13 @@ int alloc_pair(poppy_hip_ctx* c, int W, int H);                                 
 int upload_image(poppy_hip_ctx* c, uint8_t* dst, const uint8_t* src, size_t stride, int W, int H);
 int set_points(poppy_hip_ctx* c, const float* p1, const float* p2, int n);
 int finish_pair_load(poppy_hip_ctx* c);                                           // m2 from gabor2, chain state reset, pair_ready
+
+// blur_margin (pair_setup.cpp): the taps, the image's place in the canvas, and canvas -> padded image on the device
+constexpr int kBlurMarginTaps = 127;
+std::vector<int> blur_margin_taps();
+void blur_margin_origin(int W, int H, int UW, int UH, int* x0, int* y0);
+hipError_t blur_margin_strips(const uint8_t* canvas, uint8_t* out, uint32_t* tmp, const int* d_taps, int W, int H, int UW, int UH, hipStream_t s);
+
+inline ForegroundFilter& chain_fg(poppy_hip_ctx* c, int slot) { return slot ? c->foreground_b : c->foreground; }
+inline OrbDetector& chain_orb(poppy_hip_ctx* c, int slot) { return slot ? c->orb_b : c->orb; }
+inline void chain_touch(poppy_hip_ctx* c) { ++c->chain_gen; }                     // no kept chain state survives this call

@@ -6,11 +6,42 @@
 #include <chrono>
 #include "dft_exact.h"
 
+// blur_margin's two halves (src/util.cpp:574-602), shared by poppy_hip_blur_margin and poppy_hip_morph_list's device-side padding.
+// taps: exp(-x^2 / 2 sigma^2) / sum in double, to 8 fractional bits with error diffusion, centre = 256 - rest (smooth.dispatch.cpp:224-258)
+std::vector<int> blur_margin_taps() {
+    const int n = kBlurMarginTaps; const double sigma = 6;
+    std::vector<double> v(n); double sum = 0;
+    for (int i = 0; i < n; ++i) { const double x = i - (n - 1) * 0.5; v[i] = std::exp(-(x * x) / (2 * sigma * sigma)); sum += v[i]; }
+    std::vector<int> taps(n, 0);
+    { double err = 0; int tot = 0;
+      for (int i = 0; i < n / 2; ++i) { const double adj = v[i] / sum * 256 + err; const int v0 = (int)std::nearbyint(adj); err = adj - v0; taps[i] = taps[n - 1 - i] = v0; tot += v0; }
+      taps[n / 2] = 256 - 2 * tot; }
+    return taps;
+}
+// where a W x H image goes in the UW x UH canvas (its top-left pixel)
+void blur_margin_origin(int W, int H, int UW, int UH, int* x0, int* y0) {
+    *x0 = (int)(std::fabs((double)(W - UW)) / 2.0);
+    *y0 = (int)(std::fabs((double)(H - UH)) / 2.0);
+}
+// canvas (the image already placed, zeros around it) -> out: the canvas, then the four margin strips blurred from it
+hipError_t blur_margin_strips(const uint8_t* canvas, uint8_t* out, uint32_t* tmp, const int* d_taps, int W, int H, int UW, int UH, hipStream_t s) {
+    hipError_t e = hipMemcpyAsync(out, canvas, (size_t)UW * UH * 3, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return e;
+    const double margin = (W + H) / 100.0;
+    double dx = std::fabs((double)(W - UW)) / 2.0, dy = std::fabs((double)(H - UH)) / 2.0;
+    dx = (dx == 0 ? 1.3 : dx + margin);
+    dy = (dy == 0 ? 1.3 : dy + margin);
+    const int rects[4][4] = {{0, 0, (int)dx, UH}, {(int)(UW - dx), 0, (int)dx, UH}, {0, 0, UW, (int)dy}, {0, (int)(UH - dy), UW, (int)dy}};
+    for (const auto& r : rects) launch_strip_blur(canvas, out, UW, tmp, d_taps, kBlurMarginTaps, r[0], r[1], r[2], r[3], s);   // left, right, top, bottom: later strips win
+    return hipGetLastError();
+}
+
 extern "C" {
 
 int poppy_hip_orb_detect(poppy_hip_ctx* c, const uint8_t* gray, size_t stride, int W, int H, int nfeatures, float* kps7, int max_kps, int* n_kps) {
     if (!c || !gray || !n_kps || W <= 0 || H <= 0 || stride < (size_t)W || nfeatures < 0) return POPPY_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     std::vector<OrbKeyPoint> kps;
     int n = c->orb.detect(gray, stride, W, H, nfeatures, c->stream, kps);
     if (n < 0) { c->err = "orb_detect: " + c->orb.err; return n == -2 ? POPPY_E_DEVICE : POPPY_E_ARG; }
@@ -27,6 +58,7 @@ int poppy_hip_orb_detect(poppy_hip_ctx* c, const uint8_t* gray, size_t stride, i
 int poppy_hip_orb_describe(poppy_hip_ctx* c, const uint8_t* gray, size_t stride, int W, int H, const float* kps7, int n, uint8_t* desc) {
     if (!c || !gray || W <= 0 || H <= 0 || stride < (size_t)W || n < 0 || (n && (!kps7 || !desc))) return POPPY_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     int rc = c->orb.describe(gray, stride, W, H, kps7, n, c->stream, desc);
     if (rc < 0) { c->err = "orb_describe: " + c->orb.err; return rc == -2 ? POPPY_E_DEVICE : POPPY_E_ARG; }
     return POPPY_OK;
@@ -35,6 +67,7 @@ int poppy_hip_orb_describe(poppy_hip_ctx* c, const uint8_t* gray, size_t stride,
 int poppy_hip_hamming_match(poppy_hip_ctx* c, const uint8_t* query, int nq, const uint8_t* train, int nt, int* out3, int* n_matches) {
     if (!c || nq < 0 || nt < 0 || !n_matches || (nq && !query) || (nt && !train) || (nq && nt && !out3)) return POPPY_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     int rc = c->orb.hamming(query, nq, train, nt, c->stream, out3);
     if (rc < 0) { c->err = "hamming_match: " + c->orb.err; return POPPY_E_DEVICE; }
     *n_matches = rc;
@@ -44,6 +77,7 @@ int poppy_hip_hamming_match(poppy_hip_ctx* c, const uint8_t* query, int nq, cons
 int poppy_hip_hamming_knn2(poppy_hip_ctx* c, const uint8_t* query, int nq, const uint8_t* train, int nt, int* out4) {
     if (!c || nq < 0 || nt < 0 || (nq && !query) || (nt && !train) || (nq && !out4)) return POPPY_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     if (c->orb.hamming_knn2(query, nq, train, nt, c->stream, out4) < 0) { c->err = "hamming_knn2: " + c->orb.err; return POPPY_E_DEVICE; }
     return POPPY_OK;
 }
@@ -89,6 +123,7 @@ static int align_host_entry(poppy_hip_ctx* c, int which, uint8_t* img, size_t st
     if (!c) return POPPY_E_ARG;
     if (!img || !p1 || !p2 || n < 4 || W <= 0 || H <= 0 || stride < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad align arguments (at least 4 point pairs)");
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     int rc = align_stage(c, img, stride, W, H); if (rc) return rc;
     std::vector<P2f> a(n), b(n);
     memcpy(a.data(), p1, (size_t)n * 8); memcpy(b.data(), p2, (size_t)n * 8);
@@ -146,6 +181,7 @@ int poppy_hip_pair_begin_prefiltered(poppy_hip_ctx* c, const uint8_t* bgr1, size
                                      const uint8_t* g1, const uint8_t* g2, const float* gabor2, int W, int H, int nfeatures) {
     if (!c || !bgr1 || !bgr2 || !g1 || !g2 || !gabor2) return POPPY_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     std::vector<OrbKeyPoint> k1, k2;
     if (c->orb.detect(g1, W, W, H, nfeatures, c->stream, k1) < 0 || c->orb.detect(g2, W, W, H, nfeatures, c->stream, k2) < 0) {
         c->err = "orb_detect: " + c->orb.err;
@@ -164,6 +200,7 @@ int poppy_hip_foreground(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, in
     if (!c) return POPPY_E_ARG;
     if (!bgr || !out || W <= 0 || H <= 0 || stride < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad image arguments");
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     ForegroundDebugOut d;
     if (dbg) { d.grey = dbg->grey; d.stages = dbg->stages; d.floats = dbg->floats; d.masked = dbg->masked; }
     const int rc = c->foreground.run(bgr, stride, W, H, c->stream, out, dbg ? &d : nullptr);
@@ -174,17 +211,29 @@ int poppy_hip_foreground(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, in
 int poppy_hip_median_blur(poppy_hip_ctx* c, const uint8_t* src, int W, int H, int ksize, int form, uint8_t* dst) {
     if (!c) return POPPY_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     const int rc = c->foreground.median(src, W, H, ksize, form, c->stream, dst);
     if (rc) { c->err = "median: " + c->foreground.err; return rc == -1 ? POPPY_E_ARG : POPPY_E_DEVICE; }
     return POPPY_OK;
 }
 
 // Pair set-up from the raw images: the pre-ORB filter chain on the GPU, then the same steps as pair_begin_prefiltered.
+// next: the set-up of the next pair of the CLI's loop (src/poppy.cpp:326) — image 1 is the resident pair's c2 (bgr1 unused); when the chain slot
+// chain_b still holds that image's chain state (kept_gen == chain_gen), image 1's chain is not run again.
 static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint8_t* bgr2, size_t s2, int W, int H, float ratio,
-                           bool on_device = false) {
+                           bool on_device = false, bool next = false) {
     if (!c) return POPPY_E_ARG;
+    if (next) {
+        if (!c->pair_ready) return fail(c, POPPY_E_STATE, "pair_begin_next: no resident pair");
+        if (W != c->W || H != c->H) return fail(c, POPPY_E_ARG, "pair_begin_next: the image's size differs from the resident pair's");
+        bgr1 = c->c2; s1 = (size_t)W * 3;
+    }
     if (!bgr1 || !bgr2 || W <= 0 || H <= 0 || s1 < (size_t)W * 3 || s2 < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad image arguments");
     HIPCHK(c, hipSetDevice(c->device));
+    // image 1's chain state is the one the resident pair's set-up left in slot chain_b (never under auto-align: c2 is then the ALIGNED image)
+    const bool reuse = next && ratio < 0.f && c->kept_gen == c->chain_gen;
+    const int sa = reuse ? c->chain_b : 0, sb = 1 - sa;          // the chain slots of image 1 and image 2
+    chain_touch(c);                                               // from here on, nothing is kept until this set-up succeeds
     struct SetupHook {                                            // a pool lets one context per device set a pair up at a time (comm.cpp: the set-up gate)
         poppy_hip_ctx* c;
         explicit SetupHook(poppy_hip_ctx* c_) : c(c_) { if (c->setup_hook) c->setup_hook(c->setup_hook_user, c, 1); }
@@ -203,12 +252,17 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
     const bool serial_chains = serial_env || c->setup_serial;
     // gabor2 (the second raw image only) at the very start of the set-up, beside the first image's chain: with the chains one after the other the context has one chain in flight
     // and room beside it (a pool step of six pairs 56.7 -> 56.0 ms); with two chains side by side it tripled the first medians' time (round 3) and waits for them
-    const bool gabor2_first = gabor2_first_env || (serial_chains && getenv("POPPY_GABOR2_LATE") == nullptr);
+    // (with image 1's chain reused there is one chain in flight, as with the serial order: gabor2 beside it from the start)
+    const bool gabor2_first = gabor2_first_env || reuse || (serial_chains && getenv("POPPY_GABOR2_LATE") == nullptr);
     // Host images: the second image is uploaded by its own chain's thread on that chain's stream, so the first image's chain — stream-ordered behind its
     // own upload — has the GPU to itself for the length of a copy instead of both waiting for both (POPPY_SETUP_UPLOAD_BOTH=1: the order before round 5)
     static const bool upload_both = getenv("POPPY_SETUP_UPLOAD_BOTH") != nullptr;
-    const bool staged = !on_device && !upload_both && !gabor2_first && !serial_chains;
-    if (on_device) {
+    const bool staged = !on_device && !upload_both && !gabor2_first && !serial_chains && !next;
+    if (next) {                                                   // image 1 = the resident c2 (ordered before c2 is overwritten on the same stream)
+        HIPCHK(c, hipMemcpyAsync(c->c1, c->c2, P * 3, hipMemcpyDeviceToDevice, c->stream));
+        if (on_device) HIPCHK(c, hipMemcpyAsync(c->c2, bgr2, P * 3, hipMemcpyDeviceToDevice, c->stream));
+        else { rc = upload_image(c, c->c2, bgr2, s2, W, H); if (rc) return rc; }
+    } else if (on_device) {
         HIPCHK(c, hipMemcpyAsync(c->c1, bgr1, P * 3, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->c2, bgr2, P * 3, hipMemcpyDeviceToDevice, c->stream));
     } else {
@@ -241,8 +295,9 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
     // (errors go to the CALLING thread's string: with gabor2_late the first image's thread queues this while the second image's thread is inside foreground_b)
     auto gabor2_on_side_stream = [&](std::string& e, bool other_thread_in_fg_b) -> bool {
         std::string ge;
-        const float* gab = c->foreground_b.gabor_field(c->c2, W, H, c->copy_stream, other_thread_in_fg_b ? &ge : nullptr);
-        if (!gab) { e = "gabor_field: " + (other_thread_in_fg_b ? ge : c->foreground_b.err); return false; }
+        ForegroundFilter& fg_b = chain_fg(c, sb);
+        const float* gab = fg_b.gabor_field(c->c2, W, H, c->copy_stream, other_thread_in_fg_b ? &ge : nullptr);
+        if (!gab) { e = "gabor_field: " + (other_thread_in_fg_b ? ge : fg_b.err); return false; }
         if (hipMemcpyAsync(c->gabor2, gab, P * 12, hipMemcpyDeviceToDevice, c->copy_stream) != hipSuccess) { e = "gabor2 copy failed"; return false; }
         return true;
     };
@@ -253,8 +308,8 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
     // image's thread): the first image's chain is through earlier than the second's, gabor2 then fills the GPU beside the second chain's tail of small launches
     static const int gabor2_at = getenv("POPPY_GABOR2_AT") ? atoi(getenv("POPPY_GABOR2_AT")) : 2;      // (1080p 3.03 -> 2.96 ms, 4K 8.5 -> 8.1: tools/experiments/gabor2_at_ab.sh)
     const int gabor2_late = (!align_first && !gabor2_first && !serial_chains) ? gabor2_at : 0;
-    if (gabor2_late && (c->foreground_b.prepare(W, H) || c->foreground_b.prepare2(W, H))) return fail(c, POPPY_E_DEVICE, "foreground buffers");
-    c->foreground_b.medians_done = (!align_first && !gabor2_first && !gabor2_late) ? c->setup_ev : nullptr;
+    if (gabor2_late && (chain_fg(c, sb).prepare(W, H) || chain_fg(c, sb).prepare2(W, H))) return fail(c, POPPY_E_DEVICE, "foreground buffers");
+    chain_fg(c, sb).medians_done = (!align_first && !gabor2_first && !gabor2_late) ? c->setup_ev : nullptr;
     // Each image's thread goes on to the detector's second half by itself as soon as BOTH details are known (nfeatures, src/extractor.cpp:40-45):
     // the other image's detail is ready long before its own candidates are, so nobody waits for a whole chain.  `details` counts the images
     // whose detail is published (or whose chain failed before it).
@@ -276,8 +331,8 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
         ~Publish() { now(); }
     };
     if (!on_device) {                                                    // which median kernel each image's chain takes: from a sample of the host pixels
-        c->foreground.median_cols_hint = median_cols_hint_from_host(bgr1, s1, W, H);
-        c->foreground_b.median_cols_hint = median_cols_hint_from_host(bgr2, s2, W, H);
+        if (!next) chain_fg(c, sa).median_cols_hint = median_cols_hint_from_host(bgr1, s1, W, H);
+        chain_fg(c, sb).median_cols_hint = median_cols_hint_from_host(bgr2, s2, W, H);
     }
     auto chain_of = [&](int i) {
         Publish publish{details};
@@ -286,49 +341,53 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
             ~UploadKnown() { if (mine && state.load() == 0) { state = -1; d.add(); } }
         } upload_known{c2_uploaded, c2_upload_state, i == 1 && staged};
         if (hipSetDevice(c->device) != hipSuccess) { errs[i] = "hipSetDevice failed"; rcs[i] = POPPY_E_DEVICE; return; }
-        ForegroundFilter& fg = i ? c->foreground_b : c->foreground;
+        ForegroundFilter& fg = chain_fg(c, i ? sb : sa);
+        OrbDetector& orb = chain_orb(c, i ? sb : sa);
         hipStream_t st = i ? c->aux_stream : c->stream;
-        if (i == 1 && staged) {
-            const bool ok = copy_rows_async(c->c2, (size_t)W * 3, bgr2, s2, (size_t)W * 3, H, hipMemcpyHostToDevice, st) == hipSuccess &&
-                            hipEventRecord(c->c2_up_ev, st) == hipSuccess;
-            c2_upload_state = ok ? 1 : -1;
-            c2_uploaded.add();
-            if (!ok) { errs[i] = "pair_begin: upload of the second image failed"; rcs[i] = POPPY_E_DEVICE; return; }
-        }
-        const uint8_t* gf = fg.run_device(i ? c->c2 : c->c1, (size_t)W * 3, W, H, st, nullptr);
-        if (!gf) { errs[i] = "foreground: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
-        if (i == 1 && fg.medians_done) {                          // gabor2 starts when the second image's medians are through (queued now, long before)
-            if (hipStreamWaitEvent(c->copy_stream, fg.medians_done, 0) != hipSuccess) { errs[i] = "gabor2: stream wait failed"; rcs[i] = POPPY_E_DEVICE; return; }
-            if (!gabor2_on_side_stream(errs[i], false)) { rcs[i] = POPPY_E_DEVICE; return; }
-        }
-        // dft_detail2 and the ORB input both read goodFeatures: the ORB input's kernels are queued behind dft_detail2's before the host waits for the detail value
-        // (until round 4 the chain's stream ran dry twice in mid-chain, at the two read-backs of dft_detail2)
-        if (fg.detail_begin(gf, W, H, st)) { errs[i] = "dft_detail2: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
-        const uint8_t* gi = fg.orb_input(gf, W, H, 0, st);
-        if (!gi) { errs[i] = "orb_input: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
-        if (fg.detail_end(&d[i])) { errs[i] = "dft_detail2: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
-        publish.now();
-        g_dev[i] = gi;                                            // the detector reads it where it lies; only ORB::compute wants a host copy
-        auto gabor2_behind_this_chain = [&]() {
-            if (staged) {                                         // c2 is written on the other chain's stream: order copy_stream behind that copy
-                c2_uploaded.wait_for(1);
-                if (c2_upload_state.load() < 0) return false;     // (the other chain reports the error)
-                if (hipStreamWaitEvent(c->copy_stream, c->c2_up_ev, 0) != hipSuccess) { errs[i] = "gabor2: stream wait failed"; rcs[i] = POPPY_E_DEVICE; return false; }
+        const bool kept = i == 0 && reuse;                        // image 1's chain ran in the previous set-up: its detail and its detector's first half are in place
+        if (kept) { d[0] = c->kept_detail; publish.now(); }
+        if (!kept) {
+            if (i == 1 && staged) {
+                const bool ok = copy_rows_async(c->c2, (size_t)W * 3, bgr2, s2, (size_t)W * 3, H, hipMemcpyHostToDevice, st) == hipSuccess &&
+                                hipEventRecord(c->c2_up_ev, st) == hipSuccess;
+                c2_upload_state = ok ? 1 : -1;
+                c2_uploaded.add();
+                if (!ok) { errs[i] = "pair_begin: upload of the second image failed"; rcs[i] = POPPY_E_DEVICE; return; }
             }
-            if (hipEventRecord(c->setup_ev, st) != hipSuccess || hipStreamWaitEvent(c->copy_stream, c->setup_ev, 0) != hipSuccess) {
-                errs[i] = "gabor2: stream wait failed"; rcs[i] = POPPY_E_DEVICE; return false;
+            const uint8_t* gf = fg.run_device(i ? c->c2 : c->c1, (size_t)W * 3, W, H, st, nullptr);
+            if (!gf) { errs[i] = "foreground: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
+            if (i == 1 && fg.medians_done) {                          // gabor2 starts when the second image's medians are through (queued now, long before)
+                if (hipStreamWaitEvent(c->copy_stream, fg.medians_done, 0) != hipSuccess) { errs[i] = "gabor2: stream wait failed"; rcs[i] = POPPY_E_DEVICE; return; }
+                if (!gabor2_on_side_stream(errs[i], false)) { rcs[i] = POPPY_E_DEVICE; return; }
             }
-            if (!gabor2_on_side_stream(errs[i], true)) { rcs[i] = POPPY_E_DEVICE; return false; }
-            return true;
-        };
-        if (i == 0 && gabor2_late == 1 && !gabor2_behind_this_chain()) return;
-        hipError_t e = ratio >= 0.f ? hipMemcpyAsync(g[i].data(), gi, P, hipMemcpyDeviceToHost, st) : hipSuccess;
-        if (e != hipSuccess) { errs[i] = std::string("pair_begin: ") + hipGetErrorString(e); rcs[i] = POPPY_E_DEVICE; return; }
-        // the detector's first half needs no nfeatures (which takes BOTH images' detail, src/extractor.cpp:40-45): it follows the chain at once,
-        // so the image that is through first does not wait for the other with the GPU half idle
-        OrbDetector& orb = i ? c->orb_b : c->orb;
-        if (orb.detect_begin(gi, W, W, H, st, true) < 0) { errs[i] = "orb_detect: " + orb.err; rcs[i] = POPPY_E_DEVICE; return; }
-        if (i == 0 && gabor2_late == 2 && !gabor2_behind_this_chain()) return;
+            // dft_detail2 and the ORB input both read goodFeatures: the ORB input's kernels are queued behind dft_detail2's before the host waits for the detail value
+            // (until round 4 the chain's stream ran dry twice in mid-chain, at the two read-backs of dft_detail2)
+            if (fg.detail_begin(gf, W, H, st)) { errs[i] = "dft_detail2: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
+            const uint8_t* gi = fg.orb_input(gf, W, H, 0, st);
+            if (!gi) { errs[i] = "orb_input: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
+            if (fg.detail_end(&d[i])) { errs[i] = "dft_detail2: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
+            publish.now();
+            g_dev[i] = gi;                                            // the detector reads it where it lies; only ORB::compute wants a host copy
+            auto gabor2_behind_this_chain = [&]() {
+                if (staged) {                                         // c2 is written on the other chain's stream: order copy_stream behind that copy
+                    c2_uploaded.wait_for(1);
+                    if (c2_upload_state.load() < 0) return false;     // (the other chain reports the error)
+                    if (hipStreamWaitEvent(c->copy_stream, c->c2_up_ev, 0) != hipSuccess) { errs[i] = "gabor2: stream wait failed"; rcs[i] = POPPY_E_DEVICE; return false; }
+                }
+                if (hipEventRecord(c->setup_ev, st) != hipSuccess || hipStreamWaitEvent(c->copy_stream, c->setup_ev, 0) != hipSuccess) {
+                    errs[i] = "gabor2: stream wait failed"; rcs[i] = POPPY_E_DEVICE; return false;
+                }
+                if (!gabor2_on_side_stream(errs[i], true)) { rcs[i] = POPPY_E_DEVICE; return false; }
+                return true;
+            };
+            if (i == 0 && gabor2_late == 1 && !gabor2_behind_this_chain()) return;
+            hipError_t e = ratio >= 0.f ? hipMemcpyAsync(g[i].data(), gi, P, hipMemcpyDeviceToHost, st) : hipSuccess;
+            if (e != hipSuccess) { errs[i] = std::string("pair_begin: ") + hipGetErrorString(e); rcs[i] = POPPY_E_DEVICE; return; }
+            // the detector's first half needs no nfeatures (which takes BOTH images' detail, src/extractor.cpp:40-45): it follows the chain at once,
+            // so the image that is through first does not wait for the other with the GPU half idle
+            if (orb.detect_begin(gi, W, W, H, st, true) < 0) { errs[i] = "orb_detect: " + orb.err; rcs[i] = POPPY_E_DEVICE; return; }
+            if (i == 0 && gabor2_late == 2 && !gabor2_behind_this_chain()) return;
+        }
         if (serial_chains) return;                                // (one chain after the other: the second half follows below)
         details.wait_for(2);
         if (rcs[i ^ 1]) return;                                   // the other chain failed (its error is reported)
@@ -347,10 +406,12 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
         chain_of(0);
         if (!c->setup_worker.wait()) { c->err = "pair set-up helper thread: " + c->setup_worker.error(); return POPPY_E_DEVICE; }
     }
-    c->foreground_b.medians_done = nullptr;
+    chain_fg(c, sb).medians_done = nullptr;
     ms_joined = since(t_begin);
     if (!align_first) HIPCHK(c, hipStreamSynchronize(c->copy_stream));                // gabor2 is in place
     for (int i = 0; i < 2; ++i) if (rcs[i].load()) { c->err = errs[i]; return rcs[i].load(); }
+    c->chains_run += reuse ? 1 : 2;
+    c->chains_reused += reuse ? 1 : 0;
     ms_chains = since(t_begin);
     const double detail = 255.0 / std::max(d[0], d[1]);                 // src/extractor.cpp:40-45
     c->last_detail[0] = d[0]; c->last_detail[1] = d[1];
@@ -358,10 +419,11 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
     c->last_nfeatures = nfeatures;
     if (serial_chains) {
         int r1 = 0, r2 = 0;
-        c->setup_worker.run([&]() { r2 = hipSetDevice(c->device) == hipSuccess ? c->orb_b.detect_finish(nfeatures, c->aux_stream, k2) : -2; });
-        r1 = c->orb.detect_finish(nfeatures, c->stream, k1);
+        OrbDetector &orb1 = chain_orb(c, sa), &orb2 = chain_orb(c, sb);
+        c->setup_worker.run([&]() { r2 = hipSetDevice(c->device) == hipSuccess ? orb2.detect_finish(nfeatures, c->aux_stream, k2) : -2; });
+        r1 = orb1.detect_finish(nfeatures, c->stream, k1);
         if (!c->setup_worker.wait()) { c->err = "pair set-up helper thread: " + c->setup_worker.error(); return POPPY_E_DEVICE; }
-        if (r1 < 0 || r2 < 0) { c->err = "orb_detect: " + (r1 < 0 ? c->orb.err : c->orb_b.err); return POPPY_E_DEVICE; }
+        if (r1 < 0 || r2 < 0) { c->err = "orb_detect: " + (r1 < 0 ? orb1.err : orb2.err); return POPPY_E_DEVICE; }
     }
     ms_detect = since(t_begin);
     if (ratio >= 0.f) {
@@ -416,8 +478,8 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
             c->c2_raw_valid = true;
             if (c->aligner.run(c->c2, W, H, a, b, c->stream, nullptr)) return fail(c, POPPY_E_DEVICE, c->aligner.err.c_str());
             memcpy(p2.data(), b.data(), n * 8);
-            const float* gab = c->foreground_b.gabor_field(c->c2, W, H, c->stream);
-            if (!gab) { c->err = "gabor_field: " + c->foreground_b.err; return POPPY_E_DEVICE; }
+            const float* gab = chain_fg(c, sb).gabor_field(c->c2, W, H, c->stream);
+            if (!gab) { c->err = "gabor_field: " + chain_fg(c, sb).err; return POPPY_E_DEVICE; }
             HIPCHK(c, hipMemcpyAsync(c->gabor2, gab, P * 12, hipMemcpyDeviceToDevice, c->stream));
         }
         int m = 0;
@@ -431,6 +493,11 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
     ms_match = since(t_begin);
     rc = finish_pair_load(c); if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (ratio < 0.f && !align_first) {                                   // image 2's chain state stays for the next pair's image 1 (c2 is that image, unaligned)
+        c->chain_b = sb;
+        c->kept_detail = d[1];
+        c->kept_gen = c->chain_gen;
+    }
     if (stage_times) fprintf(stderr, "  chains: image 1 through %.3f, image 2 through %.3f, both joined %.3f, gabor2 in place %.3f ms\n", ms_chain_end[0], ms_chain_end[1], ms_joined, ms_chains);
     if (stage_times)
         fprintf(stderr, "pair set-up %dx%d: upload %.3f, chains %.3f, detect %.3f, match %.3f, finish %.3f ms (cumulative); before them (drain + queueing the raw pair's copies) %.3f ms\n", W, H, ms_upload, ms_chains,
@@ -443,6 +510,18 @@ int poppy_hip_pair_begin(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const
 }
 int poppy_hip_pair_begin_device(poppy_hip_ctx* c, const void* d1, const void* d2, int W, int H) {
     return pair_begin_impl(c, (const uint8_t*)d1, (size_t)W * 3, (const uint8_t*)d2, (size_t)W * 3, W, H, -1.f, true);
+}
+int poppy_hip_pair_begin_next(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H) {
+    return pair_begin_impl(c, nullptr, 0, bgr, stride, W, H, -1.f, false, true);
+}
+int poppy_hip_pair_begin_next_device(poppy_hip_ctx* c, const void* d_bgr, int W, int H) {
+    return pair_begin_impl(c, nullptr, 0, (const uint8_t*)d_bgr, (size_t)W * 3, W, H, -1.f, true, true);
+}
+int poppy_hip_chain_counts(poppy_hip_ctx* c, unsigned long long* run, unsigned long long* reused) {
+    if (!c) return POPPY_E_ARG;
+    if (run) *run = c->chains_run;
+    if (reused) *reused = c->chains_reused;
+    return POPPY_OK;
 }
 void poppy_count_frames_cb(void* user, const uint8_t*, int, int, size_t) { if (user) ++*(long long*)user; }
 int poppy_hip_pair_begin_descriptors(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint8_t* bgr2, size_t s2, int W, int H, float ratio) {
@@ -472,6 +551,7 @@ int poppy_hip_pair_begin_info(poppy_hip_ctx* c, int* nfeatures, double* detail2)
 int poppy_hip_orb_input(poppy_hip_ctx* c, const uint8_t* good_features, int W, int H, uint8_t* g, float* us, float* gb, double* detail) {
     if (!c || !good_features || W <= 0 || H <= 0) return POPPY_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     ForegroundFilter& fg = c->foreground;
     if (fg.prepare(W, H)) { c->err = "foreground: " + fg.err; return POPPY_E_DEVICE; }
     uint8_t* d_gf = fg.bgr_staging();                                   // any w*h device bytes will do as the staging area
@@ -488,6 +568,7 @@ int poppy_hip_orb_input(poppy_hip_ctx* c, const uint8_t* good_features, int W, i
 int poppy_hip_set_gabor_direct(poppy_hip_ctx* c, int on) {
     if (!c) return POPPY_E_ARG;
     c->foreground.gabor_direct = c->foreground_b.gabor_direct = on != 0;
+    chain_touch(c);
     return POPPY_OK;
 }
 
@@ -503,6 +584,7 @@ int poppy_hip_gabor_doubt(unsigned long long out[3]) { return out && gabor_fft_d
 int poppy_hip_gabor_field(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, float* out) {
     if (!c || !bgr || !out || W <= 0 || H <= 0 || stride < (size_t)W * 3) return POPPY_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     ForegroundFilter& fg = c->foreground;
     if (fg.prepare(W, H)) { c->err = "foreground: " + fg.err; return POPPY_E_DEVICE; }
     HIPCHK(c, copy_rows_async(fg.bgr_staging(), (size_t)W * 3, bgr, stride, (size_t)W * 3, H, hipMemcpyHostToDevice, c->stream));
@@ -522,30 +604,19 @@ int poppy_hip_blur_margin(poppy_hip_ctx* c, const uint8_t* src, size_t stride, i
     const size_t UB = (size_t)UW * UH * 3;
     uint8_t *canvas = nullptr, *out = nullptr; uint32_t* tmp = nullptr; int* d_taps = nullptr;
     auto cleanup = [&]() { for (void* p : {(void*)canvas, (void*)out, (void*)tmp, (void*)d_taps}) if (p) (void)hipFree(p); };
-    // taps: exp(-x^2 / 2 sigma^2) / sum in double, to 8 fractional bits with error diffusion, centre = 256 - rest (smooth.dispatch.cpp:224-258)
-    const int n = 127; const double sigma = 6;
-    std::vector<double> v(n); double sum = 0;
-    for (int i = 0; i < n; ++i) { const double x = i - (n - 1) * 0.5; v[i] = std::exp(-(x * x) / (2 * sigma * sigma)); sum += v[i]; }
-    std::vector<int> taps(n, 0);
-    { double err = 0; int tot = 0;
-      for (int i = 0; i < n / 2; ++i) { const double adj = v[i] / sum * 256 + err; const int v0 = (int)std::nearbyint(adj); err = adj - v0; taps[i] = taps[n - 1 - i] = v0; tot += v0; }
-      taps[n / 2] = 256 - 2 * tot; }
+    const int n = kBlurMarginTaps;
+    const std::vector<int> taps = blur_margin_taps();
     hipError_t e = hipMalloc((void**)&canvas, UB);
     if (e == hipSuccess) e = hipMalloc((void**)&out, UB);
     if (e == hipSuccess) e = hipMalloc((void**)&tmp, UB * 4);
     if (e == hipSuccess) e = hipMalloc((void**)&d_taps, n * 4);
     if (e == hipSuccess) e = hipMemcpyAsync(d_taps, taps.data(), n * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(canvas, 0, UB, c->stream);
-    const double margin = (W + H) / 100.0;
-    double dx = std::fabs((double)(W - UW)) / 2.0, dy = std::fabs((double)(H - UH)) / 2.0;
-    const int rx = (int)dx, ry = (int)dy;
+    int rx = 0, ry = 0;
+    blur_margin_origin(W, H, UW, UH, &rx, &ry);
     if (e == hipSuccess) e = copy_rows_async(canvas + ((size_t)ry * UW + rx) * 3, (size_t)UW * 3, src, stride, (size_t)W * 3, H, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, canvas, UB, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = blur_margin_strips(canvas, out, tmp, d_taps, W, H, UW, UH, c->stream);
     if (e != hipSuccess) { cleanup(); c->err = std::string("blur_margin: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
-    dx = (dx == 0 ? 1.3 : dx + margin);
-    dy = (dy == 0 ? 1.3 : dy + margin);
-    const int rects[4][4] = {{0, 0, (int)dx, UH}, {(int)(UW - dx), 0, (int)dx, UH}, {0, 0, UW, (int)dy}, {0, (int)(UH - dy), UW, (int)dy}};
-    for (const auto& r : rects) launch_strip_blur(canvas, out, UW, tmp, d_taps, n, r[0], r[1], r[2], r[3], c->stream);   // left, right, top, bottom: later strips win
     e = copy_rows_async(dst, dst_stride, out, (size_t)UW * 3, (size_t)UW * 3, UH, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     cleanup();

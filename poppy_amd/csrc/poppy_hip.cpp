@@ -133,6 +133,7 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
     for (auto& m : c->marks) (void)hipEventDestroy(m.ev);
     (void)hipStreamSynchronize(c->copy_stream);
     if (c->d_align) (void)hipFree(c->d_align);
+    for (void* p : {(void*)c->bm_canvas, (void*)c->bm_tmp, (void*)c->bm_taps, (void*)c->list_img[0], (void*)c->list_img[1]}) if (p) (void)hipFree(p);
     if (c->d_comm_scratch) (void)hipFree(c->d_comm_scratch);
     c->aligner.release();
     (void)hipStreamDestroy(c->copy_stream);
@@ -983,6 +984,7 @@ int poppy_hip_pair_load(poppy_hip_ctx* c, const uint8_t* c1, size_t s1, const ui
     if (!c) return POPPY_E_ARG;
     if (!c1 || !c2 || !gabor2 || W <= 0 || H <= 0 || s1 < (size_t)W * 3 || s2 < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad image arguments");
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     int rc = alloc_pair(c, W, H); if (rc) return rc;
     c->c2_raw_valid = false;
     rc = set_points(c, p1, p2, n); if (rc) return rc;
@@ -999,6 +1001,7 @@ int poppy_hip_pair_load_device(poppy_hip_ctx* c, const void* d1, const void* d2,
     if (!c) return POPPY_E_ARG;
     if (!d1 || !d2 || !dg || W <= 0 || H <= 0) return fail(c, POPPY_E_ARG, "bad image arguments");
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     int rc = alloc_pair(c, W, H); if (rc) return rc;
     c->c2_raw_valid = false;
     rc = set_points(c, p1, p2, n); if (rc) return rc;
@@ -1171,6 +1174,7 @@ int poppy_hip_dissolve(poppy_hip_ctx* c, const uint8_t* img1, size_t s1, const u
     if (!c) return POPPY_E_ARG;
     if (!img1 || !img2 || !dst || W <= 0 || H <= 0) return fail(c, POPPY_E_ARG, "bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
     int rc = alloc_pair(c, W, H); if (rc) return rc;
     rc = upload_image(c, c->c1, img1, s1, W, H); if (rc) return rc;
     rc = upload_image(c, c->c2, img2, s2, W, H); if (rc) return rc;
