@@ -238,7 +238,10 @@ int poppy_hip_pair_begin_prefiltered(poppy_hip_ctx* ctx,
  * grey, 31x31 Gabor bank, radial gradient, equalizeHist -> ORB x2 -> matcher -> gabor_filter(image2 / 255) -> resident pair.
  * Parity: bit-exact with the reference end to end (tests/test_gpu_prefilter2.py reproduces the point pairs and frames of
  * the real poppy::morph).  dft_detail2 restates cv::dft operation for operation; the Gabor banks produce the once-rounded
- * exact sums that OpenCV's double-precision DFT correlation yields (DESIGN.md section 7 has the fine print).          */
+ * exact sums that OpenCV's double-precision DFT correlation yields (DESIGN.md section 7 has the fine print).
+ * Frames one pixel wide or high: POPPY_E_UNSUPPORTED before any launch (dft_detail2 keeps an even number of spectrum rows and
+ * columns: none of a 1-point DFT, so the reference's detail is 0 / 0 and its nfeatures undefined); the same for poppy_hip_morph,
+ * the sharded set-ups and poppy_hip_orb_input's detail.                                                                       */
 int poppy_hip_pair_begin(poppy_hip_ctx* ctx, const uint8_t* bgr1, size_t stride1, const uint8_t* bgr2, size_t stride2,
                          int width, int height);
 /* poppy_hip_pair_begin with the two raw images already in this GPU's memory (tight rows, width*3 bytes each): the throughput
@@ -462,6 +465,22 @@ int poppy_hip_set_debug(poppy_hip_ctx* ctx, int on);
  * POPPY_HIP_IDMAP, or a plan whose per-tile lists outgrew the blob), 0 = the general kernel (degenerate matrices or odd
  * geometry).  Same output bits in all three; exported so that the parity tests can tell which one they exercised.           */
 int poppy_hip_last_warp_kind(poppy_hip_ctx* ctx);
+/* The pyramid launches of the last frame rendered in debug mode, in launch order, as (kind, level, arg) triples in out[3 * k ..]:
+ * at most `cap` triples are written; returns how many the frame had (POPPY_E_STATE when no debug frame was rendered since the pair's
+ * geometry was set).  The launch sequence depends on the pair's geometry, pyramid_levels and the POPPY_HIP_NOCONE / POPPY_HIP_NOFUSE /
+ * POPPY_TAIL_PX switches only, so it also describes the same pair's frames outside debug mode.  Kinds (POPPY_PYR_*):
+ *   DOWN    level i -> i + 1 (arg 1: level 0 reads the blend mask from the pair's m2, "lazy", else 0)
+ *   DOWN2   levels i -> i + 2 in one launch (k_pyrdown2)
+ *   TAIL    k_pyr_tail from level `level` (arg: its multi-pixel steps, n_wide); always followed by
+ *   TAIL_NL level = pyramid_levels, arg: the tail's single-pixel reductions (nl; -1 when the pyramid stops above 1 x 1)
+ *   MIX_TOP the coarsest level's mix from global memory (the tail does not fit)
+ *   CONE    k_collapse_cone<arg> writes level `level` from level + arg
+ *   UP2     k_collapse2 writes level `level` from level + 2
+ *   UP      level i from i + 1 (arg as for DOWN)
+ *   UNSHARP level 0; arg 1: the separable path of frames under 2 pixels wide or high, 0: the 2-D kernels              */
+enum { POPPY_PYR_DOWN = 1, POPPY_PYR_DOWN2 = 2, POPPY_PYR_TAIL = 3, POPPY_PYR_TAIL_NL = 4, POPPY_PYR_MIX_TOP = 5, POPPY_PYR_CONE = 6,
+       POPPY_PYR_UP2 = 7, POPPY_PYR_UP = 8, POPPY_PYR_UNSHARP = 9 };
+int poppy_hip_last_pyramid_forms(poppy_hip_ctx* ctx, int* out, int cap);
 /* frames rendered by each of the three since the context was created */
 int poppy_hip_warp_counts(poppy_hip_ctx* ctx, unsigned long long* fused, unsigned long long* tiled, unsigned long long* general);
 /* Measurement aid: relaunches the last frame's fused raster + warp kernel (create_map + remap, src/algo.cpp:146-176,230-238) `reps`

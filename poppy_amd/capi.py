@@ -21,6 +21,8 @@ class PoppySettings(C.Structure):
 
 
 WARP_KERNELS = ("k_warp_bin", "k_warp_tile", "k_warp4")        # order of poppy_hip_warp_counts
+# kinds 1.. of poppy_hip_last_pyramid_forms (POPPY_PYR_*)
+PYRAMID_FORMS = ("down", "down2", "tail", "tail_nl", "mix_top", "cone", "up2", "up", "unsharp")
 WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_size_t)
 
 # every symbol include/poppy_hip.h declares (tests check the library exports all of them)
@@ -38,6 +40,7 @@ SYMBOLS = [
     "poppy_dft_plan", "poppy_hip_pair_begin_device", "poppy_count_frames_cb", "poppy_hip_morph", "poppy_hip_pair_distance", "poppy_printed_morph_distance", "poppy_hypotf_selfcheck",
     "poppy_hip_orb_detect", "poppy_hip_foreground", "poppy_hip_median_blur", "poppy_match_points", "poppy_hip_pair_begin_prefiltered", "poppy_hip_pair_begin", "poppy_hip_pair_begin_info", "poppy_hip_orb_input", "poppy_hip_gabor_field", "poppy_hip_set_gabor_direct", "poppy_hip_set_setup_chains", "poppy_hip_gabor_doubt", "poppy_radial_gradient", "poppy_radial_mask", "poppy_gabor_tables", "poppy_pyr_tail_plan", "poppy_hip_blur_margin", "poppy_hip_pair_points",
     "poppy_hip_pair_begin_next", "poppy_hip_pair_begin_next_device", "poppy_hip_chain_counts", "poppy_hip_morph_list",
+    "poppy_hip_last_pyramid_forms",
 ]
 
 
@@ -74,6 +77,7 @@ def lib():
         L.poppy_hip_dissolve.argtypes = [vp, vp, sz, vp, sz, i, i, d, vp, sz]
         L.poppy_hip_set_debug.argtypes = [vp, i]
         L.poppy_hip_last_warp_kind.argtypes = [vp]
+        L.poppy_hip_last_pyramid_forms.argtypes = [vp, vp, i]
         L.poppy_hip_set_timing.argtypes = [vp, i]
         L.poppy_hip_debug_fetch.argtypes = [vp, C.c_char_p, vp, sz]
         L.poppy_hip_debug_triangles.argtypes = [vp, vp, vp, vp, vp, i]
@@ -942,6 +946,14 @@ class Context:
 
     def last_warp_kind(self):
         return int(lib().poppy_hip_last_warp_kind(self.h))
+
+    def last_pyramid_forms(self):
+        """[(kind, level, arg)] of the last debug-mode frame's pyramid launches in launch order (include/poppy_hip.h: poppy_hip_last_pyramid_forms)."""
+        n = lib().poppy_hip_last_pyramid_forms(self.h, None, 0)
+        self._chk(min(n, 0), "last_pyramid_forms")
+        out = np.zeros((max(n, 1), 3), np.int32)
+        lib().poppy_hip_last_pyramid_forms(self.h, _p(out), n)
+        return [(PYRAMID_FORMS[k - 1], int(lv), int(arg)) for k, lv, arg in out[:n]]
 
     def set_debug(self, on=True):
         lib().poppy_hip_set_debug(self.h, int(on))

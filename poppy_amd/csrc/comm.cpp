@@ -284,6 +284,7 @@ int setup_sharded(poppy_hip_ctx* c, Transport& T, const void* d1, const void* d2
     g_sharded_setups.fetch_add(1);
     chain_touch(c);
     if (c->cfg.enable_auto_align) return fail(c, POPPY_E_UNSUPPORTED, "the sharded set-up does not take auto-align (image 2 changes after the match)");
+    if (!setup_size_ok(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kSetupSizeMsg);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t P = (size_t)W * H;
     const int rA = root, rB = T.world >= 2 ? (root + 1) % T.world : root, rC = T.world >= 3 ? (root + 2) % T.world : rB;

@@ -139,6 +139,7 @@ struct poppy_hip_ctx {
     // diagnostics
     bool debug = false;
     bool lazy_mask = false;                     // the level-0 blend kernels compute lbmask from m2; the warp kernel does not write it
+    std::vector<int> pyr_forms;                 // the pyramid launches of the last debug-mode frame, (kind, level, arg) triples (poppy_hip_last_pyramid_forms)
     int timing = 0;                      // 0 off, 1 every kernel group (direct launches), 2 the warp kernel only
     struct Mark { const char* name; hipEvent_t ev; };   // name == nullptr opens a frame
     std::vector<Mark> marks; size_t marks_used = 0;
@@ -180,6 +181,10 @@ int adopt_pair_state(poppy_hip_ctx* c);            // arena head -> points, chai
     } while (0)
 
 inline int fail(poppy_hip_ctx* c, int code, const char* msg) { c->err = msg; return code; }
+// the pair set-up's dft_detail2 keeps an even number of spectrum rows and columns (include/poppy_hip.h: poppy_hip_pair_begin):
+// a frame one pixel wide or high has none, its detail is 0 / 0 — refused before any launch
+inline bool setup_size_ok(int W, int H) { return W >= 2 && H >= 2; }
+constexpr const char* kSetupSizeMsg = "the pair set-up needs a frame at least 2 x 2 pixels (dft_detail2 of a one-pixel row or column is 0 / 0)";
 
 // shared between the translation units (defined in poppy_hip.cpp)
 int alloc_pair(poppy_hip_ctx* c, int W, int H);                                   // resident buffers + frame slots for a W x H pair

@@ -497,18 +497,20 @@ void launch_mix_top(const float* l, const float* r, const float* m, float* out, 
 __constant__ float c_gauss9[9] = {0x1.18a9c4p-13f, 0x1.22724cp-8f, 0x1.ba4b9ap-5f, 0x1.ef8ebap-3f, 0x1.9884a4p-2f,
                                   0x1.ef8ebap-3f, 0x1.ba4b9ap-5f, 0x1.22724cp-8f, 0x1.18a9c4p-13f};
 
-__global__ void __launch_bounds__(256) k_gauss_row(const float* __restrict__ src, float* __restrict__ dst, int W, int H) {
+// (sp: pixels per row of src, the blended level 0 — padded for one-pixel-wide frames from 150 001 pixels up, kernels.h: level_pitch;
+// the scratch images and the outputs are tight)
+__global__ void __launch_bounds__(256) k_gauss_row(const float* __restrict__ src, float* __restrict__ dst, int W, int H, int sp) {
     const int xe = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (xe >= W * 3) return;
     const int px = xe / 3, c = xe - px * 3;
-    const float* row = src + (size_t)y * W * 3;
+    const float* row = src + (size_t)y * sp * 3;
     float acc = row[reflect101(px - 4, W) * 3 + c] * c_gauss9[0];
 #pragma unroll
     for (int k = 1; k < 9; ++k) acc = row[reflect101(px - 4 + k, W) * 3 + c] * c_gauss9[k] + acc;
     dst[(size_t)y * W * 3 + xe] = acc;
 }
 
-__global__ void __launch_bounds__(256) k_gauss_col_diff(const float* __restrict__ src, const float* __restrict__ tmp, float* __restrict__ diff, int W, int H) {
+__global__ void __launch_bounds__(256) k_gauss_col_diff(const float* __restrict__ src, const float* __restrict__ tmp, float* __restrict__ diff, int W, int H, int sp) {
     const int xe = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (xe >= W * 3) return;
     const size_t stride = (size_t)W * 3;
@@ -516,7 +518,7 @@ __global__ void __launch_bounds__(256) k_gauss_col_diff(const float* __restrict_
 #pragma unroll
     for (int k = 1; k <= 4; ++k)
         acc = c_gauss9[4 + k] * (tmp[reflect101(y + k, H) * stride + xe] + tmp[reflect101(y - k, H) * stride + xe]) + acc;
-    diff[y * stride + xe] = src[y * stride + xe] - acc;
+    diff[y * stride + xe] = src[(size_t)y * sp * 3 + xe] - acc;
 }
 
 __device__ __forceinline__ void mnmx(float& a, float& b) {
@@ -548,13 +550,13 @@ __device__ __forceinline__ float median9(const float* __restrict__ d, int W, int
 }
 
 __global__ void __launch_bounds__(256) k_median_apply(const float* __restrict__ src, const float* __restrict__ diff, uint8_t* __restrict__ out,
-                                                      float* __restrict__ outF, int W, int H, float amount, float threshold) {
+                                                      float* __restrict__ outF, int W, int H, float amount, float threshold, int sp) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= W) return;
     float d0 = median9(diff, W, H, x, y, 0), d1 = median9(diff, W, H, x, y, 1), d2 = median9(diff, W, H, x, y, 2);
     double s = (double)d0 * (double)d0 + (double)d1 * (double)d1 + (double)d2 * (double)d2;
-    const size_t p = ((size_t)y * W + x) * 3;
-    float v0 = src[p], v1 = src[p + 1], v2 = src[p + 2];
+    const size_t p = ((size_t)y * W + x) * 3, q = ((size_t)y * sp + x) * 3;
+    float v0 = src[q], v1 = src[q + 1], v2 = src[q + 2];
     if (sqrt(s) >= (double)threshold) {
         v0 = v0 + amount * d0; v1 = v1 + amount * d1; v2 = v2 + amount * d2;
     }
@@ -807,9 +809,9 @@ void launch_unsharp(const float* src, float* tmpRow, float* diff, uint8_t* out_u
         return;
     }
     dim3 ge((w * 3 + 255) / 256, h), gp((w + 255) / 256, h);
-    hipLaunchKernelGGL(k_gauss_row, ge, dim3(256), 0, s, src, tmpRow, w, h);
-    hipLaunchKernelGGL(k_gauss_col_diff, ge, dim3(256), 0, s, src, tmpRow, diff, w, h);
-    hipLaunchKernelGGL(k_median_apply, gp, dim3(256), 0, s, src, diff, out_u8, out_f32_or_null, w, h, amount, threshold);
+    hipLaunchKernelGGL(k_gauss_row, ge, dim3(256), 0, s, src, tmpRow, w, h, src_pitch);
+    hipLaunchKernelGGL(k_gauss_col_diff, ge, dim3(256), 0, s, src, tmpRow, diff, w, h, src_pitch);
+    hipLaunchKernelGGL(k_median_apply, gp, dim3(256), 0, s, src, diff, out_u8, out_f32_or_null, w, h, amount, threshold, src_pitch);
     if (done) (void)hipEventRecord(done, s);
 }
 

@@ -229,6 +229,7 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
         bgr1 = c->c2; s1 = (size_t)W * 3;
     }
     if (!bgr1 || !bgr2 || W <= 0 || H <= 0 || s1 < (size_t)W * 3 || s2 < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad image arguments");
+    if (!setup_size_ok(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kSetupSizeMsg);
     HIPCHK(c, hipSetDevice(c->device));
     // image 1's chain state is the one the resident pair's set-up left in slot chain_b (never under auto-align: c2 is then the ALIGNED image)
     const bool reuse = next && ratio < 0.f && c->kept_gen == c->chain_gen;
@@ -550,6 +551,7 @@ int poppy_hip_pair_begin_info(poppy_hip_ctx* c, int* nfeatures, double* detail2)
 // Extractor::keypoints' image chain for one goodFeatures image (host in / out): us = grey(unsharp), gb = Gabor mean, g = ORB input
 int poppy_hip_orb_input(poppy_hip_ctx* c, const uint8_t* good_features, int W, int H, uint8_t* g, float* us, float* gb, double* detail) {
     if (!c || !good_features || W <= 0 || H <= 0) return POPPY_E_ARG;
+    if (detail && !setup_size_ok(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kSetupSizeMsg);
     HIPCHK(c, hipSetDevice(c->device));
     chain_touch(c);
     ForegroundFilter& fg = c->foreground;

@@ -146,6 +146,13 @@ int poppy_warp_records(const float* inv1, const float* inv2, int n_tris, int wid
     return pack_warp_records(inv1, inv2, n_tris, width, height, records) ? 1 : 0;
 }
 int poppy_hip_last_warp_kind(poppy_hip_ctx* c) { return c ? (c->last_warp_bin ? 2 : c->last_warp_fast ? 1 : 0) : POPPY_E_ARG; }
+int poppy_hip_last_pyramid_forms(poppy_hip_ctx* c, int* out, int cap) {
+    if (!c || cap < 0 || (cap > 0 && !out)) return POPPY_E_ARG;
+    if (c->pyr_forms.empty()) return POPPY_E_STATE;
+    const int n = (int)c->pyr_forms.size() / 3;
+    if (cap > 0) memcpy(out, c->pyr_forms.data(), (size_t)std::min(n, cap) * 3 * sizeof(int));
+    return n;
+}
 int poppy_hip_warp_counts(poppy_hip_ctx* c, unsigned long long* fused, unsigned long long* tiled, unsigned long long* general) {
     if (!c) return POPPY_E_ARG;
     if (fused) *fused = c->n_warp_bin;
@@ -220,6 +227,7 @@ int alloc_pair(poppy_hip_ctx* c, int W, int H) {
     { int rc = drain_frames(c); if (rc) return rc; }              // every pair loader comes through here: no frame still reads the old pair
     if (c->W == W && c->H == H && c->c1) return POPPY_OK;
     free_pair(c);
+    c->pyr_forms.clear();
     if (c->cfg.pyramid_levels < 1 || c->cfg.pyramid_levels > 256) return fail(c, POPPY_E_UNSUPPORTED, "pyramid_levels must be in [1,256]");
     const size_t P = (size_t)W * H;
     const int L = c->cfg.pyramid_levels;
@@ -621,12 +629,16 @@ static void enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* t
     const int W = c->W, H = c->H, L = c->cfg.pyramid_levels;
     const int ft = c->first_tail < L ? c->first_tail : L;
     static const bool fuse = getenv("POPPY_HIP_NOFUSE") == nullptr;
+    // debug frames only (issued by the calling thread, never captured): the launch list for poppy_hip_last_pyramid_forms
+    if (debug) c->pyr_forms.clear();
+    auto rec = [&](int kind, int level, int arg) { if (debug) c->pyr_forms.insert(c->pyr_forms.end(), {kind, level, arg}); };
     for (int i = 0; i < ft;) {
         const PyrLevel &a = c->levels[i], &b = c->levels[i + 1];
         if (fuse && i >= 1 && i + 2 <= ft && b.pitch == b.w && c->levels[i + 2].pitch == c->levels[i + 2].w && pyrdown2_eligible(a.w, a.h)) {     // two small levels in one launch (the two it writes are tight)
             const PyrLevel& d = c->levels[i + 2];
             launch_pyrdown2(f.pyrL + a.off3, f.pyrR + a.off3, f.pyrM + a.off1, f.pyrL + b.off3, f.pyrR + b.off3, f.pyrM + b.off1,
                             f.pyrL + d.off3, f.pyrR + d.off3, f.pyrM + d.off1, a.w, a.h, s, a.pitch);
+            rec(POPPY_PYR_DOWN2, i, 0);
             i += 2;
             continue;
         }
@@ -635,12 +647,15 @@ static void enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* t
         const bool lazy = i == 0 && c->lazy_mask;      // level 0 reads the mask through m2 (kernels.h: launch_pyrdown)
         launch_pyrdown(sl, sr, lazy ? c->m2 : f.pyrM + a.off1, i == 0, f.pyrL + b.off3, f.pyrR + b.off3, f.pyrM + b.off1, a.w, a.h, s,
                        lazy ? (const double*)(f.d_blob + kBlobMaskAB) : nullptr, a.pitch, lazy ? a.w : a.pitch, b.pitch);
+        rec(POPPY_PYR_DOWN, i, lazy);
         ++i;
     }
     if (tm) tm->mark("pyrdown");
     if (c->use_tail) launch_pyr_tail(f.pyrL, f.pyrR, f.pyrM, f.pyrB, c->d_levels, c->tail.args, c->tail.lds_bytes, s);
     else launch_mix_top(f.pyrL + c->levels[L].off3, f.pyrR + c->levels[L].off3, f.pyrM + c->levels[L].off1, f.pyrB + c->levels[L].off3,
-                        c->levels[L].w * c->levels[L].h, s);
+                        c->levels[L].pitch * c->levels[L].h, s);      // element-wise: a padded level's rows are mixed with their padding
+    if (c->use_tail) { rec(POPPY_PYR_TAIL, ft, c->tail.args.n_wide); rec(POPPY_PYR_TAIL_NL, L, c->tail.args.nl); }
+    else rec(POPPY_PYR_MIX_TOP, L, 0);
     if (tm) tm->mark("pyr_tail");
     // The way up: the small levels in ONE launch (round 6, kernels_pyramid_cone.hip): from the tail's level to the largest level of at most kConeMaxPixels
     // (level 1 at 1080p, level 2 at 4K).  POPPY_HIP_NOCONE: the launches of round 5 (k_collapse2 pairs + one k_collapse_level per remaining level).
@@ -652,6 +667,7 @@ static void enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* t
         if (ft - k > kConeMaxLevels) k = ft - kConeMaxLevels;
         if (ft - k >= 2 && collapse_cone_eligible(&c->levels[k], ft - k)) {
             launch_collapse_cone(f.pyrL, f.pyrR, f.pyrM, f.pyrB, &c->levels[k], ft - k, s);
+            rec(POPPY_PYR_CONE, k, ft - k);
             j_top = k;
         }
     }
@@ -661,6 +677,7 @@ static void enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* t
             if (a.pitch == a.w && m.pitch == m.w && collapse2_eligible(a.w, a.h, m.w, m.h, n.w, n.h)) {
                 launch_collapse2(f.pyrL + a.off3, f.pyrR + a.off3, f.pyrM + a.off1, f.pyrL + m.off3, f.pyrR + m.off3, f.pyrM + m.off1,
                                  f.pyrL + n.off3, f.pyrR + n.off3, f.pyrB + n.off3, f.pyrB + a.off3, a.w, a.h, m.w, m.h, n.w, n.h, s);
+                rec(POPPY_PYR_UP2, j - 2, 0);
                 j -= 2;
                 continue;
             }
@@ -672,10 +689,12 @@ static void enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* t
         const bool lazy = i == 0 && c->lazy_mask;
         launch_collapse(gl, gr, i == 0, lazy ? c->m2 : f.pyrM + a.off1, f.pyrL + b.off3, f.pyrR + b.off3, f.pyrB + b.off3, f.pyrB + a.off3,
                         a.w, a.h, b.w, b.h, s, lazy ? (const double*)(f.d_blob + kBlobMaskAB) : nullptr, a.pitch, lazy ? a.w : a.pitch, b.pitch);
+        rec(POPPY_PYR_UP, i, lazy);
         --j;
     }
     if (tm) tm->mark("collapse");
     launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s, done, c->levels[0].pitch);
+    rec(POPPY_PYR_UNSHARP, 0, W < 2 || H < 2);
     if (tm) tm->mark("unsharp");
 }
 
