@@ -126,6 +126,24 @@ double poppy_frame_ratio(int j, int number_of_frames, double phase);
  * only during the call.  write may be NULL (frames stay on the device: benchmark mode).              */
 typedef void (*poppy_write_cb)(void* user, const uint8_t* bgr, int width, int height, size_t stride);
 int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb write, void* user);
+/* The format of the frames handed to a writer.  POPPY_FRAME_BGR (the default): u8x3 rows, stride >= 3 * width.  POPPY_FRAME_I420: planar
+ * YUV 4:2:0 as video encoders and Y4M C420jpeg take it, full-range BT.601 with centred chroma, converted on the GPU before the copy to the
+ * host (half the bytes of BGR on the link).  Layout of a width x height frame, tight, back to back: Y (width * height bytes), then U,
+ * then V (cw * ch bytes each, cw = (width + 1) / 2, ch = (height + 1) / 2).  Y = the Y4M C444 sink's; U, V of each 2 x 2 block, clipped at
+ * the right and bottom edges to n = 1, 2 or 4 pixels, k = log2 n, from its channel sums:
+ *     U = clamp(((-11059 * sum R - 21709 * sum G + 32768 * sum B + (32768 << k)) >> (16 + k)) + 128, 0, 255)
+ *     V = clamp((( 32768 * sum R - 27439 * sum G -  5329 * sum B + (32768 << k)) >> (16 + k)) + 128, 0, 255)   (>> arithmetic)
+ * poppy_bgr_to_i420 is the host statement of the format, poppy_frame_bytes its size (0 for an unknown format or an empty frame).
+ * poppy_hip_set_frame_format drains the context's frames and applies to every frame handed to a writer by poppy_hip_morph,
+ * poppy_hip_morph_frames, poppy_hip_render_many, poppy_hip_render_phases and poppy_hip_morph_list — the phase == 0 / 1 and t == 0 / 1
+ * copies and the POPPY_E_NOMATCH linear-blend frames included; under I420 the writer gets (frame, width, height, stride = width).
+ * Any other format: POPPY_E_ARG.  These stay BGR whatever the setting: poppy_hip_render / poppy_hip_dissolve into an explicit dst,
+ * poppy_hip_frame_device, frames kept on the device (write == NULL), poppy_hip_morph_sharded and poppy_hip_morph_pairs (their contexts
+ * are made from poppy_settings), and include/poppy_hip_shim.hpp.  poppy_hip_pool_set_frame_format sets every context of a pool.  */
+enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1 };
+int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
+size_t poppy_frame_bytes(int format, int width, int height);
+int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 /* phase == 0 / phase == 1 follow the reference's short-circuit (src/poppy.hpp:54-70): number_of_frames copies of image 1 /
  * image 2 as they were handed to the pair set-up (with auto-align: the UNALIGNED image 2), no frame is rendered.            */
 
@@ -402,6 +420,9 @@ int poppy_hip_pool_wait(poppy_hip_pool* pool, char* err, size_t err_len);
 int poppy_hip_pool_set_timing(poppy_hip_pool* pool, int on);
 int poppy_hip_pool_timing_summary(poppy_hip_pool* pool, const char** names, float* total_ms, int* launches, int max);
 int poppy_hip_pool_warp_counts(poppy_hip_pool* pool, unsigned long long* fused, unsigned long long* tiled, unsigned long long* general);
+/* poppy_hip_set_frame_format on every context of the pool; POPPY_E_STATE while batches submitted with poppy_hip_pool_submit_pairs have not been
+ * waited for (poppy_hip_pool_wait). */
+int poppy_hip_pool_set_frame_format(poppy_hip_pool* pool, int format);
 /* poppy_hip_mask_rider of the pool's contexts (they share settings and geometry) */
 int poppy_hip_pool_mask_rider(poppy_hip_pool* pool);
 /* The CLI's loop over an image list (src/poppy.cpp:266-328) on ONE context: pair k = (image k, image k + 1), where image k of pair k > 0 is
@@ -438,9 +459,11 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * (user = the sink), so  poppy_hip_morph(ctx, .., poppy_sink_write, sink, ..)  writes the sequence to disk.  RAW: one file, BGR rows back
  * to back; PPM: one P6 file per frame, `path` holds exactly one %d, %<width>d or %0<width>d for the frame index (the library substitutes
  * it itself; any other conversion, or none, makes poppy_sink_open return NULL); Y4M: one YUV4MPEG2 file, C444, full-range BT.601.
+ * Y4M420: one YUV4MPEG2 file, C420jpeg XCOLORRANGE=FULL, written from POPPY_FRAME_I420 frames as they come (stride must be the width).
+ * The BGR sinks take frames with stride >= 3 * width, the I420 sink frames with stride == width: a frame of the other format fails the sink.
  * poppy_sink_close returns the number of frames written, or a negative status if a write failed or a frame had another geometry.   */
 typedef struct poppy_sink poppy_sink;
-enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2 };
+enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3 };
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den);
 void poppy_sink_write(void* sink, const uint8_t* bgr, int width, int height, size_t stride);
 int poppy_sink_close(poppy_sink* sink);

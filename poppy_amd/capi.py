@@ -24,6 +24,9 @@ WARP_KERNELS = ("k_warp_bin", "k_warp_tile", "k_warp4")        # order of poppy_
 # kinds 1.. of poppy_hip_last_pyramid_forms (POPPY_PYR_*)
 PYRAMID_FORMS = ("down", "down2", "tail", "tail_nl", "mix_top", "cone", "up2", "up", "unsharp")
 WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_size_t)
+# formats of the frames handed to writers (poppy_hip_set_frame_format) and the file sinks (poppy_sink_open)
+FRAME_BGR, FRAME_I420 = 0, 1
+SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420 = 0, 1, 2, 3
 
 # every symbol include/poppy_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -41,6 +44,7 @@ SYMBOLS = [
     "poppy_hip_orb_detect", "poppy_hip_foreground", "poppy_hip_median_blur", "poppy_match_points", "poppy_hip_pair_begin_prefiltered", "poppy_hip_pair_begin", "poppy_hip_pair_begin_info", "poppy_hip_orb_input", "poppy_hip_gabor_field", "poppy_hip_set_gabor_direct", "poppy_hip_set_setup_chains", "poppy_hip_gabor_doubt", "poppy_radial_gradient", "poppy_radial_mask", "poppy_gabor_tables", "poppy_pyr_tail_plan", "poppy_hip_blur_margin", "poppy_hip_pair_points",
     "poppy_hip_pair_begin_next", "poppy_hip_pair_begin_next_device", "poppy_hip_chain_counts", "poppy_hip_morph_list",
     "poppy_hip_last_pyramid_forms",
+    "poppy_hip_set_frame_format", "poppy_hip_pool_set_frame_format", "poppy_frame_bytes", "poppy_bgr_to_i420",
 ]
 
 
@@ -156,6 +160,11 @@ def lib():
         L.poppy_hip_morph.argtypes = [vp, vp, sz, vp, sz, i, i, d, i, vp, vp, vp]
         L.poppy_hip_pair_distance.argtypes = [vp, vp]
         L.poppy_printed_morph_distance.argtypes = [vp, vp, i, i, i, vp]
+        L.poppy_hip_set_frame_format.argtypes = [vp, i]
+        L.poppy_hip_pool_set_frame_format.argtypes = [vp, i]
+        L.poppy_frame_bytes.restype = sz
+        L.poppy_frame_bytes.argtypes = [i, i, i]
+        L.poppy_bgr_to_i420.argtypes = [vp, sz, i, i, vp]
         L.poppy_hypotf_selfcheck.restype = C.c_long
         L.poppy_hypotf_selfcheck.argtypes = [C.c_long, C.c_uint64]
         _lib = L
@@ -164,6 +173,29 @@ def lib():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def frame_bytes(fmt, w, h):
+    """Host-only: bytes of a w x h frame in format fmt (FRAME_BGR / FRAME_I420; 0 for anything else)."""
+    return int(lib().poppy_frame_bytes(int(fmt), int(w), int(h)))
+
+
+def bgr_to_i420(bgr):
+    """Host-only: the library's I420 of an HxWx3 BGR frame (poppy_bgr_to_i420), as a flat uint8 array of frame_bytes(FRAME_I420, W, H)."""
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    out = np.empty(frame_bytes(FRAME_I420, w, h), np.uint8)
+    rc = lib().poppy_bgr_to_i420(_p(a), w * 3, w, h, _p(out))
+    if rc:
+        raise PoppyError(f"poppy_bgr_to_i420: {rc}")
+    return out
+
+
+def _frame_view(ptr, w, h, stride, fmt):
+    """A writer's frame as numpy: HxWx3 for BGR, the flat I420 bytes (frame_bytes long) for I420.  A view: valid during the callback."""
+    if fmt == FRAME_I420:
+        return np.ctypeslib.as_array(ptr, shape=(frame_bytes(FRAME_I420, w, h),))
+    return np.ctypeslib.as_array(ptr, shape=(h, stride))[:, :w * 3].reshape(h, w, 3)
 
 
 class PoppyError(RuntimeError):
@@ -402,6 +434,15 @@ class Pool:
             self.candidates_ms, self.kept = [float(ms[k]) for k in range(n.value)], kept.value
         if not self.h:
             raise PoppyError("poppy_hip_pool_create: " + err.value.decode())
+        self.frame_format = FRAME_BGR
+
+    def set_frame_format(self, fmt):
+        """FRAME_BGR or FRAME_I420 for every context of the pool (poppy_hip_pool_set_frame_format); PoppyError with the status while submitted
+        batches have not been waited for."""
+        rc = lib().poppy_hip_pool_set_frame_format(self.h, int(fmt))
+        if rc:
+            raise PoppyError(f"poppy_hip_pool_set_frame_format: {rc}")
+        self.frame_format = int(fmt)
 
     def close(self):
         if self.h:
@@ -473,8 +514,10 @@ class Pool:
             pa[0] = pairs[p][0] if inputs_on_device else pairs[p][0].ctypes.data; sa[0] = w * 3
             pb[0] = pairs[p][1] if inputs_on_device else pairs[p][1].ctypes.data; sb[0] = w * 3
             return 0
+        fmt = self.frame_format
+
         def wr(user, p, j, ptr, ww, hh, stride):
-            write(p, j, np.ctypeslib.as_array(ptr, shape=(hh, stride))[:, :ww * 3].reshape(hh, ww, 3))
+            write(p, j, _frame_view(ptr, ww, hh, stride, fmt))
         fs, fw = PAIR_SOURCE_CB(src), WRITE_PAIR_CB(wr)
         if not hasattr(self, "_pending"):
             self._pending, self._count = [], C.c_longlong(0)
@@ -539,6 +582,13 @@ class Context:
         if not self.h:
             raise PoppyError("poppy_hip_create failed: " + L.poppy_hip_create_error().decode())
         self.w = self.h_ = 0
+        self.frame_format = FRAME_BGR
+
+    def set_frame_format(self, fmt):
+        """FRAME_BGR (default) or FRAME_I420: the format of every frame handed to a writer (poppy_hip_set_frame_format).  Under I420 the collecting
+        wrappers return flat uint8 arrays of frame_bytes(FRAME_I420, W, H)."""
+        self._chk(lib().poppy_hip_set_frame_format(self.h, int(fmt)), "set_frame_format")
+        self.frame_format = int(fmt)
 
     def close(self):
         if self.h:
@@ -717,8 +767,10 @@ class Context:
             return 0
         frames = [[] for _ in range(max(n - 1, 0))]
 
+        fmt = self.frame_format
+
         def wr(user, k, j, ptr, ww, hh, stride):
-            view = np.ctypeslib.as_array(ptr, shape=(hh, stride))[:, :ww * 3].reshape(hh, ww, 3)
+            view = _frame_view(ptr, ww, hh, stride, fmt)
             if write is not None:
                 write(k, j, view)
             else:
@@ -760,8 +812,10 @@ class Context:
             return n.value
         fn = None
         if write is not None:
+            fmt = self.frame_format
+
             def cb(user, ptr, w, h, stride):
-                write(np.ctypeslib.as_array(ptr, shape=(h, stride))[:, :w * 3].reshape(h, w, 3))
+                write(_frame_view(ptr, w, h, stride, fmt))
             fn = WRITE_CB(cb)
         self._chk(lib().poppy_hip_render_phases(self.h, _p(t), len(t), C.cast(fn, C.c_void_p) if fn else None, None), "render_phases")
 
@@ -892,9 +946,10 @@ class Context:
                 padded.append(buf)
             a, b = padded
         frames = []
+        fmt = self.frame_format
 
         def cb(user, ptr, ww, hh, stride):
-            frames.append(np.ctypeslib.as_array(ptr, shape=(hh, stride))[:, :ww * 3].reshape(hh, ww, 3).copy())
+            frames.append(_frame_view(ptr, ww, hh, stride, fmt).copy())
         fn = WRITE_CB(cb) if collect else None
         d = C.c_double(float("nan"))
         rc = lib().poppy_hip_morph(self.h, _p(a), strides[0], _p(b), strides[1], w, h, phase, int(distance),
@@ -917,9 +972,10 @@ class Context:
 
     def morph_frames(self, phase=-1.0, collect=True):
         frames = []
+        fmt = self.frame_format
 
         def cb(user, ptr, w, h, stride):
-            frames.append(np.ctypeslib.as_array(ptr, shape=(h, stride))[:, :w * 3].reshape(h, w, 3).copy())
+            frames.append(_frame_view(ptr, w, h, stride, fmt).copy())
         fn = WRITE_CB(cb) if collect else None
         self._chk(lib().poppy_hip_morph_frames(self.h, phase, C.cast(fn, C.c_void_p) if fn else None, None), "morph_frames")
         return frames
@@ -994,8 +1050,10 @@ class Context:
         mk = sh if masks is None else np.ascontiguousarray(masks, np.float64)
         fn = None
         if write is not None:
+            fmt = self.frame_format
+
             def cb(user, ptr, w, h, stride):
-                write(np.ctypeslib.as_array(ptr, shape=(h, stride))[:, :w * 3].reshape(h, w, 3))
+                write(_frame_view(ptr, w, h, stride, fmt))
             fn = WRITE_CB(cb)
         self._chk(lib().poppy_hip_render_many(self.h, _p(sh), _p(mk), len(sh), int(chain), C.cast(fn, C.c_void_p) if fn else None, None), "render_many")
 

@@ -637,6 +637,7 @@ struct poppy_hip_pool {
     std::condition_variable q_cv, q_idle;
     std::deque<std::shared_ptr<Batch>> queue;    // batches with pairs nobody has taken yet
     long long outstanding = 0;                   // pairs submitted and not finished
+    bool unwaited = false;                       // a batch was submitted since the last poppy_hip_pool_wait
     int async_rc = POPPY_OK;                     // the first failure since the last poppy_hip_pool_wait (the pairs behind it are dropped)
     std::string async_err;
     std::vector<std::thread> feeders;
@@ -808,6 +809,7 @@ int poppy_hip_pool_submit_pairs(poppy_hip_pool* p, int n_pairs, int W, int H, do
         if (p->feeders.empty())
             for (int k = 0; k < (int)p->ctx.size(); ++k) p->feeders.emplace_back(pool_feeder, p, k);
         p->outstanding += n_pairs;
+        p->unwaited = true;
         p->queue.push_back(std::move(b));
     }
     p->q_cv.notify_all();
@@ -819,6 +821,7 @@ int poppy_hip_pool_wait(poppy_hip_pool* p, char* err, size_t err_len) {
     std::unique_lock<std::mutex> lk(p->q_mu);
     p->q_idle.wait(lk, [&] { return p->outstanding == 0; });
     const int rc = p->async_rc;
+    p->unwaited = false;
     if (rc != POPPY_OK) set_err(err, err_len, p->async_err);
     p->async_rc = POPPY_OK;
     p->async_err.clear();
@@ -920,6 +923,16 @@ int poppy_hip_pool_warp_counts(poppy_hip_pool* p, unsigned long long* fused, uns
     if (fused) *fused = f;
     if (tiled) *tiled = a;
     if (general) *general = b;
+    return POPPY_OK;
+}
+
+int poppy_hip_pool_set_frame_format(poppy_hip_pool* p, int format) {
+    if (!p || (format != POPPY_FRAME_BGR && format != POPPY_FRAME_I420)) return POPPY_E_ARG;
+    {
+        std::lock_guard<std::mutex> lk(p->q_mu);
+        if (p->unwaited || p->outstanding) return POPPY_E_STATE;                 // the feeders' contexts may be rendering
+    }
+    for (poppy_hip_ctx* c : p->ctx) { const int rc = poppy_hip_set_frame_format(c, format); if (rc) return rc; }
     return POPPY_OK;
 }
 

@@ -5,6 +5,8 @@
 //   POPPY_SINK_PPM   one binary PPM (P6, RGB) per frame; the path holds exactly one %d / %<width>d / %0<width>d (frame index from 0)
 //   POPPY_SINK_Y4M   one YUV4MPEG2 file, C444, full-range BT.601 in 8-bit integer arithmetic (lossless containers downstream can
 //                    re-encode it; the conversion is this file's, not the reference's)
+//   POPPY_SINK_Y4M420  one YUV4MPEG2 file, C420jpeg, that takes I420 frames as they are (poppy_hip_set_frame_format)
+// and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "../../include/poppy_hip.h"
 #include <cstdio>
 #include <string>
@@ -22,8 +24,44 @@ struct poppy_sink {
 
 extern "C" {
 
+size_t poppy_frame_bytes(int format, int width, int height) {
+    if (width <= 0 || height <= 0) return 0;
+    const size_t w = (size_t)width, h = (size_t)height;
+    if (format == POPPY_FRAME_BGR) return w * h * 3;
+    if (format == POPPY_FRAME_I420) return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2);
+    return 0;
+}
+
+// Y: the C444 branch of poppy_sink_write.  U, V of each 2 x 2 block (n = 1, 2 or 4 pixels at the right and bottom edges, k = log2 n) from
+// the block's channel sums with the same coefficients: ((c_r * sum R + c_g * sum G + c_b * sum B + (32768 << k)) >> (16 + k)) + 128, clamped.
+int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst) {
+    if (!bgr || !dst || width <= 0 || height <= 0 || stride < (size_t)width * 3) return POPPY_E_ARG;
+    const int cw = (width + 1) / 2, ch = (height + 1) / 2;
+    auto clamp = [](int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); };
+    for (int y = 0; y < height; ++y) {
+        const uint8_t* p = bgr + (size_t)y * stride;
+        uint8_t* o = dst + (size_t)y * width;
+        for (int x = 0; x < width; ++x) o[x] = clamp((19595 * p[3 * x + 2] + 38470 * p[3 * x + 1] + 7471 * p[3 * x] + 32768) >> 16);
+    }
+    uint8_t* u = dst + (size_t)width * height;
+    uint8_t* v = u + (size_t)cw * ch;
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const int nx = 2 * cx + 1 < width ? 2 : 1, ny = 2 * cy + 1 < height ? 2 : 1, k = (nx >> 1) + (ny >> 1);
+            int sb = 0, sg = 0, sr = 0;
+            for (int r = 0; r < ny; ++r)
+                for (int q = 0; q < nx; ++q) {
+                    const uint8_t* px = bgr + (size_t)(2 * cy + r) * stride + (size_t)(2 * cx + q) * 3;
+                    sb += px[0]; sg += px[1]; sr += px[2];
+                }
+            u[(size_t)cy * cw + cx] = clamp(((-11059 * sr - 21709 * sg + 32768 * sb + (32768 << k)) >> (16 + k)) + 128);
+            v[(size_t)cy * cw + cx] = clamp(((32768 * sr - 27439 * sg - 5329 * sb + (32768 << k)) >> (16 + k)) + 128);
+        }
+    return POPPY_OK;
+}
+
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den) {
-    if (!path || width <= 0 || height <= 0 || format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M) return nullptr;
+    if (!path || width <= 0 || height <= 0 || format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420) return nullptr;
     poppy_sink* s = new poppy_sink();
     s->format = format; s->w = width; s->h = height; s->path = path;
     if (format == POPPY_SINK_PPM) {
@@ -52,6 +90,8 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
         if (!s->f) { delete s; return nullptr; }
         if (format == POPPY_SINK_Y4M)
             fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C444 XCOLORRANGE=FULL\n", width, height, fps_num > 0 ? fps_num : 30, fps_den > 0 ? fps_den : 1);
+        else if (format == POPPY_SINK_Y4M420)
+            fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=FULL\n", width, height, fps_num > 0 ? fps_num : 30, fps_den > 0 ? fps_den : 1);
     }
     s->row.resize((size_t)width * 3);
     return s;
@@ -60,8 +100,15 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
 void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, size_t stride) {
     poppy_sink* s = (poppy_sink*)user;
     if (!s || s->failed) return;
-    if (!bgr || width != s->w || height != s->h || stride < (size_t)width * 3) { s->failed = true; return; }
+    // (an I420 frame comes with stride == width: the BGR sinks refuse it, and the I420 sink refuses anything else)
+    const bool i420 = s->format == POPPY_SINK_Y4M420;
+    if (!bgr || width != s->w || height != s->h || (i420 ? stride != (size_t)width : stride < (size_t)width * 3)) { s->failed = true; return; }
     FILE* f = s->f;
+    if (i420) {
+        const size_t n = poppy_frame_bytes(POPPY_FRAME_I420, width, height);
+        if (fputs("FRAME\n", f) < 0 || fwrite(bgr, 1, n, f) != n) s->failed = true; else ++s->frames;
+        return;
+    }
     if (s->format == POPPY_SINK_PPM) {
         std::string num = std::to_string(s->frames);
         if ((int)num.size() < s->pad) num.insert(0, (size_t)s->pad - num.size(), s->zero ? '0' : ' ');

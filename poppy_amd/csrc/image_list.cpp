@@ -93,7 +93,15 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
     int rc = fetch(0, a); if (rc) return rc;
     rc = fetch(1, b); if (rc) return rc;
     if (phase == 0 || phase == 1) {                            // two images: poppy_hip_morph's short-circuit, before any feature work
-        if (write) {
+        if (write && c->frame_format == POPPY_FRAME_I420) {     // (the writer's format: converted on the device, or on the host for host images as poppy_hip_morph does)
+            const ListImage& img = phase == 0 ? a : b;
+            std::vector<uint8_t> host; size_t stride = 0;
+            const uint8_t* frame = nullptr;
+            if (img.dev) { rc = download_frame(c, img.p, W, H, host, &stride); if (rc) return rc; frame = host.data(); }
+            else frame = host_frame(c, img.p, img.stride, W, H, host, &stride);
+            PairWriter pw{write, user, 0, 0};
+            for (int j = 0; j < N; ++j) pair_writer_cb(&pw, frame, W, H, stride);
+        } else if (write) {
             const ListImage& img = phase == 0 ? a : b;
             std::vector<uint8_t> host;
             if (img.dev) { rc = list_download(c, img.p, W, H, host); if (rc) return rc; }
@@ -114,9 +122,12 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
                 launch_dissolve(raw2, c->c1, c->slots[0].out, (size_t)W * H * 3, (float)phase, (float)(1.0 - phase), c->stream);
                 HIPCHK(c, hipGetLastError());
                 std::vector<uint8_t> blend;
-                rc = list_download(c, c->slots[0].out, W, H, blend); if (rc) return rc;
+                size_t stride = (size_t)W * 3;
+                if (c->frame_format == POPPY_FRAME_I420) rc = download_frame(c, c->slots[0].out, W, H, blend, &stride);
+                else rc = list_download(c, c->slots[0].out, W, H, blend);
+                if (rc) return rc;
                 PairWriter pw{write, user, k, 0};
-                for (int j = 0; j < N; ++j) pair_writer_cb(&pw, blend.data(), W, H, (size_t)W * 3);
+                for (int j = 0; j < N; ++j) pair_writer_cb(&pw, blend.data(), W, H, stride);
                 chain_touch(c);                                // as after poppy_hip_dissolve
                 c->pair_ready = false;
             }

@@ -200,4 +200,7 @@ void launch_unsharp_stream(const float* src, uint8_t* out_u8, float* out_f32_or_
 // u8 cross-dissolve fallback (src/poppy.hpp:129)
 void launch_dissolve(const uint8_t* a, const uint8_t* b, uint8_t* dst, size_t n, float wa, float wb, hipStream_t s);
 
+// tight u8x3 BGR -> I420 (kernels_frame_format.hip; the format: include/poppy_hip.h, POPPY_FRAME_I420).  `done` (optional) rides on the last dispatch.
+void launch_bgr_to_i420(const uint8_t* src, uint8_t* dst, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
+
 }  // namespace poppy_hip

@@ -94,6 +94,8 @@ static void free_pair(poppy_hip_ctx* c) {
         void* fb[] = {f.tr1, f.tr2, f.out, f.pyrL, f.pyrR, f.pyrM, f.pyrB, f.tmp, f.diff, f.unsharpF, f.triMap};
         for (void* b : fb) if (b) (void)hipFree(b);
         f.tr1 = f.tr2 = f.out = nullptr; f.pyrL = f.pyrR = f.pyrM = f.pyrB = f.tmp = f.diff = f.unsharpF = nullptr; f.triMap = nullptr;
+        if (f.i420) (void)hipFree(f.i420);
+        f.i420 = nullptr;
     }
     for (FrameSlot& f : c->slots) {
         if (f.body) { (void)hipGraphExecDestroy(f.body); f.body = nullptr; }
@@ -135,6 +137,7 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
     if (c->d_align) (void)hipFree(c->d_align);
     for (void* p : {(void*)c->bm_canvas, (void*)c->bm_tmp, (void*)c->bm_taps, (void*)c->list_img[0], (void*)c->list_img[1]}) if (p) (void)hipFree(p);
     if (c->d_comm_scratch) (void)hipFree(c->d_comm_scratch);
+    if (c->i420_scratch) (void)hipFree(c->i420_scratch);
     c->aligner.release();
     (void)hipStreamDestroy(c->copy_stream);
     (void)hipStreamDestroy(c->stream);
@@ -223,6 +226,13 @@ static int ensure_ring(poppy_hip_ctx* c, int n_points) {
     return POPPY_OK;
 }
 
+// every slot's I420 buffer for the pair's geometry (while the context's frame format is I420)
+static int alloc_slot_i420(poppy_hip_ctx* c) {
+    const size_t bytes = poppy_frame_bytes(POPPY_FRAME_I420, c->W, c->H);
+    for (FrameSlot& f : c->slots) if (!f.i420) HIPCHK(c, hipMalloc((void**)&f.i420, bytes + 16));
+    return POPPY_OK;
+}
+
 int alloc_pair(poppy_hip_ctx* c, int W, int H) {
     { int rc = drain_frames(c); if (rc) return rc; }              // every pair loader comes through here: no frame still reads the old pair
     if (c->W == W && c->H == H && c->c1) return POPPY_OK;
@@ -277,7 +287,7 @@ int alloc_pair(poppy_hip_ctx* c, int W, int H) {
         if (!c->tail.desc.empty()) HIPCHK(c, hipMemcpy(c->d_levels, c->tail.desc.data(), c->tail.desc.size() * 4, hipMemcpyHostToDevice));
     }
     c->W = W; c->H = H;
-    return POPPY_OK;
+    return c->frame_format == POPPY_FRAME_I420 ? alloc_slot_i420(c) : POPPY_OK;
 }
 
 int set_points(poppy_hip_ctx* c, const float* p1, const float* p2, int n) {
@@ -500,7 +510,9 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
     std::vector<std::atomic<int>>& ready = sp->ready;
     std::atomic<int>& next = sp->next;
     int rc = POPPY_OK;
-    const size_t row = (size_t)W * 3, frame_bytes = row * H;
+    // the writer's format (poppy_hip_set_frame_format): I420 frames are converted by the frame body into the slot's i420 buffer (enqueue_body)
+    const bool i420 = write && c->frame_format == POPPY_FRAME_I420;
+    const size_t row = i420 ? (size_t)W : (size_t)W * 3, frame_bytes = i420 ? poppy_frame_bytes(POPPY_FRAME_I420, W, H) : row * H;
     static const int ring_pref = getenv("POPPY_HIP_RING") ? std::max(1, atoi(getenv("POPPY_HIP_RING"))) : 3;
     const int R = std::min({poppy_hip_ctx::kStageRing, ring_pref, (int)c->slots.size()});
     const size_t slot_bytes = (frame_bytes + 255) & ~(size_t)255;     // ring slots start on 256-byte boundaries
@@ -538,7 +550,7 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
         ms_done += lap(t0);
         if (dl_streams) {
             if (e == hipSuccess && !c->dl_ring[r]) e = hipStreamCreateWithFlags(&c->dl_ring[r], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, f.out, frame_bytes, hipMemcpyDeviceToHost, c->dl_ring[r]);
+            if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, i420 ? f.i420 : f.out, frame_bytes, hipMemcpyDeviceToHost, c->dl_ring[r]);
             f.dl_pending = true; f.dl_ring_idx = r;
             if (e != hipSuccess) { c->err = std::string("frame download: ") + hipGetErrorString(e); rc = POPPY_E_DEVICE; return false; }
             return true;
@@ -548,7 +560,7 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
         static const bool skip_copy = getenv("POPPY_DL_SKIP_COPY") != nullptr;      // timing experiment: every wait and event of the writer path, no bytes moved (wrong frames)
         if (!skip_copy)
 #endif
-        if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, f.out, frame_bytes, hipMemcpyDeviceToHost, c->dl_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, i420 ? f.i420 : f.out, frame_bytes, hipMemcpyDeviceToHost, c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(c->dl_done[r], c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(f.downloaded, c->dl_stream);          // the slot's own: ring events are re-recorded every R frames
         f.dl_pending = true;
@@ -623,6 +635,9 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
 
 static_assert(kPlanRasterRows == kRasterChunkRows, "the plan's work list and k_raster must agree on the chunk height");
 
+// the frames being submitted go to a writer that takes I420 (their slots' bodies end with the conversion)
+static bool frame_wants_i420(const poppy_hip_ctx* c) { return c->writer_attached && c->frame_format == POPPY_FRAME_I420; }
+
 // pyrdown .. unsharp of one slot.  Every argument is fixed for the life of the pair (the per-frame unsharp amount is
 // read from the slot's plan blob), which is what lets the whole sequence be captured into one graph launch.
 static void enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm, float amount, bool debug, hipEvent_t done = nullptr) {
@@ -693,15 +708,23 @@ static void enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* t
         --j;
     }
     if (tm) tm->mark("collapse");
-    launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s, done, c->levels[0].pitch);
+    // A frame for a writer that takes I420 is converted right behind its unsharp, on the same stream, and the frame's completion event rides on the
+    // conversion: the host waits for that event, then issues the copy of the slot's I420 buffer (render_sequence), which depends on nothing
+    const bool i420 = frame_wants_i420(c);
+    launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s, i420 ? nullptr : done, c->levels[0].pitch);
     rec(POPPY_PYR_UNSHARP, 0, W < 2 || H < 2);
     if (tm) tm->mark("unsharp");
+    if (i420) {
+        launch_bgr_to_i420(f.out, f.i420, W, H, s, done);
+        if (tm) tm->mark("frame_format");
+    }
 }
 
 static int capture_body(poppy_hip_ctx* c, FrameSlot& f) {
     hipGraph_t g = nullptr;
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     enqueue_body(c, f, c->stream, nullptr, 0.f, false);
+    f.body_i420 = frame_wants_i420(c);
     HIPCHK(c, hipStreamEndCapture(c->stream, &g));
     hipError_t e = hipGraphInstantiate(&f.body, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
@@ -851,6 +874,10 @@ static int prepare_slot(poppy_hip_ctx* c, const FramePlan& plan, double mask, bo
     // bottleneck.  On the chained critical path a graph launch leaves the GPU idle ~8 us longer than the same kernels
     // launched one by one (4600 vs 4785 frames/s, profiles/r01_e_streams.md), and the host keeps up easily.
     const bool use_graph = !no_graph && !chained && !c->debug && !all_marks && W > 1 && H > 1;
+    if (use_graph && f.body && f.body_i420 != frame_wants_i420(c)) {          // the body has (not) the conversion the frame needs: captured again
+        HIPCHK(c, hipEventSynchronize(f.done));                                // (the slot's last frame may still run it)
+        (void)hipGraphExecDestroy(f.body); f.body = nullptr;
+    }
     if (use_graph && !f.body) { int rc = capture_body(c, f); if (rc) return rc; }
 
     pr.T = T; pr.n_work = n_work; pr.tile_w = plan.tile_w; pr.bin_warp = bin_warp; pr.fast_warp = fast_warp; pr.chained = chained; pr.use_graph = use_graph;
@@ -990,6 +1017,39 @@ static int prepare_ahead(poppy_hip_ctx* c, const FramePlan& plan, double mask) {
     return rc;
 }
 
+int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride) {
+    if (c->frame_format != POPPY_FRAME_I420) {
+        host.resize((size_t)W * H * 3);
+        *stride = (size_t)W * 3;
+        HIPCHK(c, hipMemcpyAsync(host.data(), d_bgr, host.size(), hipMemcpyDeviceToHost, c->stream));
+    } else {
+        const size_t bytes = poppy_frame_bytes(POPPY_FRAME_I420, W, H);
+        if (bytes + 16 > c->i420_scratch_bytes) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (c->i420_scratch) (void)hipFree(c->i420_scratch);
+            c->i420_scratch = nullptr; c->i420_scratch_bytes = 0;
+            HIPCHK(c, hipMalloc((void**)&c->i420_scratch, bytes + 16));
+            c->i420_scratch_bytes = bytes + 16;
+        }
+        host.resize(bytes);
+        *stride = (size_t)W;
+        launch_bgr_to_i420(d_bgr, c->i420_scratch, W, H, c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(host.data(), c->i420_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return POPPY_OK;
+}
+
+const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride) {
+    *out_stride = stride;
+    if (c->frame_format != POPPY_FRAME_I420) return bgr;
+    tmp.resize(poppy_frame_bytes(POPPY_FRAME_I420, W, H));
+    (void)poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
+    *out_stride = (size_t)W;
+    return tmp.data();
+}
+
 int upload_image(poppy_hip_ctx* c, uint8_t* dst, const uint8_t* src, size_t stride, int W, int H) {
     // (tight rows go as one linear copy: kernels.h copy_rows_async; only images that really have padded rows — ROIs — pay the 2-D copy's slow path at odd widths)
     HIPCHK(c, copy_rows_async(dst, (size_t)W * 3, src, stride, (size_t)W * 3, H, hipMemcpyHostToDevice, c->stream));
@@ -1103,6 +1163,12 @@ int poppy_hip_morph_frames(poppy_hip_ctx* c, double phase, poppy_write_cb write,
     if (phase == 0 || phase == 1) {                            // src/poppy.hpp:54-70: N copies of image 1 / image 2, nothing rendered
         if (!write) return POPPY_OK;
         const uint8_t* img = phase == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2);
+        if (c->frame_format == POPPY_FRAME_I420) {
+            std::vector<uint8_t> host; size_t stride = 0;
+            int rc = download_frame(c, img, c->W, c->H, host, &stride); if (rc) return rc;
+            for (int j = 0; j < N; ++j) write(user, host.data(), c->W, c->H, stride);
+            return POPPY_OK;
+        }
         const size_t row = (size_t)c->W * 3;
         HIPCHK(c, hipMemcpyAsync(c->h_stage, img, row * c->H, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1122,7 +1188,11 @@ int poppy_hip_render_phases(poppy_hip_ctx* c, const double* t, int n, poppy_writ
     const size_t row = (size_t)c->W * 3;
     for (int i = 0; i < n;) {
         if (t[i] == 0 || t[i] == 1) {                             // a plain copy of image 1 / image 2
-            if (write) {
+            if (write && c->frame_format == POPPY_FRAME_I420) {
+                std::vector<uint8_t> host; size_t stride = 0;
+                int rc = download_frame(c, t[i] == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2), c->W, c->H, host, &stride); if (rc) return rc;
+                write(user, host.data(), c->W, c->H, stride);
+            } else if (write) {
                 int rc = stage_host(c, row * c->H); if (rc) return rc;
                 const uint8_t* img = t[i] == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2);
                 HIPCHK(c, hipMemcpyAsync(c->h_stage, img, row * c->H, hipMemcpyDeviceToHost, c->stream));
@@ -1166,8 +1236,11 @@ int poppy_hip_morph(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint
     if (!c) return POPPY_E_ARG;
     if (!bgr1 || !bgr2 || W <= 0 || H <= 0 || s1 < (size_t)W * 3 || s2 < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad image arguments");
     const int N = c->cfg.number_of_frames;
-    if (phase == 0 || phase == 1) {                            // src/poppy.hpp:54-70, before any feature work
-        for (int j = 0; j < N && write; ++j) write(user, phase == 0 ? bgr1 : bgr2, W, H, phase == 0 ? s1 : s2);
+    if (phase == 0 || phase == 1) {                            // src/poppy.hpp:54-70, before any feature work (I420: converted on the host, no GPU touched)
+        std::vector<uint8_t> tmp;
+        size_t stride = phase == 0 ? s1 : s2;
+        const uint8_t* img = (write && N > 0) ? host_frame(c, phase == 0 ? bgr1 : bgr2, stride, W, H, tmp, &stride) : nullptr;
+        for (int j = 0; j < N && write; ++j) write(user, img, W, H, stride);
         return POPPY_OK;
     }
     int rc = poppy_hip_pair_begin(c, bgr1, s1, bgr2, s2, W, H); if (rc) return rc;
@@ -1175,7 +1248,9 @@ int poppy_hip_morph(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint
         if (!distance && write) {
             std::vector<uint8_t> blend((size_t)W * 3 * H);
             rc = poppy_hip_dissolve(c, bgr1, s1, bgr2, s2, W, H, phase, blend.data(), (size_t)W * 3); if (rc) return rc;
-            for (int j = 0; j < N; ++j) write(user, blend.data(), W, H, (size_t)W * 3);
+            size_t stride = (size_t)W * 3;
+            if (c->frame_format == POPPY_FRAME_I420) { rc = download_frame(c, c->slots[0].out, W, H, blend, &stride); if (rc) return rc; }      // the blend, still in slot 0
+            for (int j = 0; j < N; ++j) write(user, blend.data(), W, H, stride);
         }
         return fail(c, POPPY_E_NOMATCH, "no point pairs: linear-blend fallback frames written (src/poppy.hpp:125-134)");
     }
@@ -1299,6 +1374,15 @@ int poppy_hip_timing_summary(poppy_hip_ctx* c, const char** names, float* total_
     }
     c->marks_used = 0;
     return n;
+}
+
+int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
+    if (!c) return POPPY_E_ARG;
+    if (format != POPPY_FRAME_BGR && format != POPPY_FRAME_I420) return fail(c, POPPY_E_ARG, "unknown frame format");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = drain_frames(c); if (rc) return rc; }
+    c->frame_format = format;
+    return (format == POPPY_FRAME_I420 && c->c1) ? alloc_slot_i420(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
 }
 
 int poppy_hip_render_many(poppy_hip_ctx* c, const double* shape, const double* mask, int n, int chain, poppy_write_cb write, void* user) {

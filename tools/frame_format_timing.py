@@ -1,0 +1,144 @@
+"""BGR against I420 frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run times
+each row once per format, one format right after the other, and the rows report min / median / max over --runs runs.
+
+  pool_1080p    bench.py's `value` set-up: a pool of --contexts contexts, --steps queued batches of six 1080p pairs from device images, 60 chained
+                frames per pair to the library's counting writer (pinned host copies)
+  pool_4k       the same at 3840 x 2160 (--steps-4k batches)
+  job480        ONE 480-frame 1080p phase-mode job on one context: pair set-up from device images + poppy_hip_render_phases to the counting writer
+  chained       one context, pair after pair: pair set-up + 60 chained frames to the counting writer
+  chained_frame one context, the 60 chained frames of a resident pair to the counting writer (what the extra launch costs a chained frame)
+  d2h_ceiling   pinned device-to-host copies of one frame's bytes, back to back on one stream (BGR and I420 sizes at 1080p and 4K)
+
+    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6]
+One JSON line at the end.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from poppy_amd import capi, synth  # noqa: E402
+
+FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420))
+
+
+def pair_images(torch, dev, w, h, n):
+    out = []
+    for k in range(n):
+        a = np.ascontiguousarray(synth.gen(w, h, 1234 + k, 0, 0)); b = np.ascontiguousarray(synth.gen(w, h, 1234 + k, w // 60 + k, h // 90))
+        out.append((torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)))
+    torch.cuda.synchronize()
+    return out
+
+
+def pool_row(pool, ptrs, w, h, steps, torch):
+    pool.morph_pairs_device_counted(ptrs, w, h, -1.0)              # warm (and the first pairs of this format's buffers)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        pool.submit_pairs_device_counted(ptrs, w, h, -1.0)
+    n = pool.wait()
+    torch.cuda.synchronize()
+    return n / (time.perf_counter() - t0)
+
+
+def d2h(torch, dev, nbytes, reps=200):
+    d = torch.empty(nbytes, dtype=torch.uint8, device=dev); d.fill_(7)
+    hbuf = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+    hbuf.copy_(d, non_blocking=True); torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        hbuf.copy_(d, non_blocking=True)
+    e1.record(); torch.cuda.synchronize()
+    s = e0.elapsed_time(e1) / 1e3
+    return {"GBps": round(nbytes * reps / s / 1e9, 2), "frames_per_s_cap": round(reps / s, 1)}
+
+
+def summary(xs):
+    return {"min": round(min(xs), 1), "median": round(statistics.median(xs), 1), "max": round(max(xs), 1), "runs": [round(x, 1) for x in xs]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--steps-4k", type=int, default=3)
+    ap.add_argument("--contexts", type=int, default=6)
+    ap.add_argument("--rows", default="pool_1080p,pool_4k,job480,chained,chained_frame,d2h_ceiling")
+    a = ap.parse_args()
+    rows = a.rows.split(",")
+    import torch
+    dev = torch.device("cuda", 0)
+    res = {r: {f: [] for f, _ in FMTS} for r in rows if r != "d2h_ceiling"}
+    W, H = 1920, 1080
+    p1080 = pair_images(torch, dev, W, H, 6)
+    ptrs = [(x.data_ptr(), y.data_ptr()) for x, y in p1080]
+    pool = capi.Pool([0], contexts_per_device=a.contexts, number_of_frames=60) if "pool_1080p" in rows else None
+    p4k = pair_images(torch, dev, 3840, 2160, 6) if "pool_4k" in rows else None
+    pool4 = capi.Pool([0], contexts_per_device=a.contexts, number_of_frames=60) if p4k else None
+    ctx = capi.Context(0, number_of_frames=60)
+    ta, tb = p1080[0]
+    ph480 = np.arange(480) / 480.0
+    shapes = np.array([capi.lib().poppy_frame_ratio(j, 60, -1.0) for j in range(60)])
+    for run in range(a.runs):
+        for name, fmt in FMTS:
+            if pool:
+                pool.set_frame_format(fmt)
+                res["pool_1080p"][name].append(pool_row(pool, ptrs, W, H, a.steps, torch))
+            if pool4:
+                pool4.set_frame_format(fmt)
+                res["pool_4k"][name].append(pool_row(pool4, [(x.data_ptr(), y.data_ptr()) for x, y in p4k], 3840, 2160, a.steps_4k, torch))
+            ctx.set_frame_format(fmt)
+            if "job480" in rows:
+                ctx.pair_begin_device(ta.data_ptr(), tb.data_ptr(), W, H); ctx.render_phases(ph480, counted=True); ctx.sync()
+                t0 = time.perf_counter()
+                for _ in range(3):
+                    ctx.pair_begin_device(ta.data_ptr(), tb.data_ptr(), W, H)
+                    n = ctx.render_phases(ph480, counted=True)
+                ctx.sync()
+                res["job480"][name].append(3 * n / (time.perf_counter() - t0))
+            if "chained" in rows:
+                t0 = time.perf_counter(); n = 0
+                for x, y in p1080:
+                    ctx.pair_begin_device(x.data_ptr(), y.data_ptr(), W, H)
+                    n += ctx.morph_frames_counted(-1.0)
+                ctx.sync()
+                res["chained"][name].append(n / (time.perf_counter() - t0))
+            if "chained_frame" in rows:
+                ctx.pair_begin_device(ta.data_ptr(), tb.data_ptr(), W, H)
+                ctx.reset(); ctx.render_many_counted(shapes, chain=True); ctx.sync()
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    ctx.reset(); ctx.render_many_counted(shapes, chain=True)
+                ctx.sync()
+                res["chained_frame"][name].append(600 / (time.perf_counter() - t0))
+        print(f"run {run}: " + ", ".join(f"{r} {f} {v[f][-1]:.0f}" for r, v in res.items() for f in v), flush=True)
+    out = {"unit": "frames/s", "rows": {r: {f: summary(v) for f, v in fv.items()} for r, fv in res.items()}}
+    for r, fv in res.items():
+        out["rows"][r]["i420_over_bgr_median"] = round(statistics.median(fv["i420"]) / statistics.median(fv["bgr"]), 3)
+    if "d2h_ceiling" in rows:
+        out["d2h_ceiling"] = {f"{w}x{h}_{f}": d2h(torch, dev, capi.frame_bytes(fmt, w, h)) for w, h in ((1920, 1080), (3840, 2160)) for f, fmt in FMTS}
+    # the conversion kernel in timing mode 1 (events around it; a chained frame): per-launch time
+    ctx.set_frame_format(capi.FRAME_I420)
+    ctx.pair_begin_device(ta.data_ptr(), tb.data_ptr(), W, H)
+    ctx.set_timing(1)
+    ctx.reset(); ctx.render_many_counted(shapes, chain=True)
+    t = {n: (ms, k) for n, ms, k in ctx.timing_summary()}
+    ctx.set_timing(0)
+    if "frame_format" in t:
+        out["timing_mode1_us"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items()}
+    for p in (pool, pool4):
+        if p:
+            p.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
