@@ -169,7 +169,9 @@ int poppy_printed_morph_distance(const float* points1, const float* points2, int
 /* ---- once-per-pair stage (outer boundary: poppy::morph, src/poppy.hpp:46-157) -------------------
  * ORB::create(nfeatures)->detect(gray, keypoints)  (src/extractor.cpp:45,77-78).  gray is an 8-bit single
  * channel host image.  kps7 receives max_kps x 7 floats per keypoint in cv::KeyPoint field order
- * (x, y, size, angle, response, octave, class_id); the ORDER equals the reference's.                   */
+ * (x, y, size, angle, response, octave, class_id); the ORDER equals the reference's.  retainBest keeps every tie with the
+ * n-th response, so the count has no bound in nfeatures: *n_kps is written also when it exceeds max_kps (POPPY_E_ARG, nothing
+ * copied), and a second call with that size succeeds.                                                   */
 int poppy_hip_orb_detect(poppy_hip_ctx* ctx, const uint8_t* gray, size_t stride, int width, int height,
                          int nfeatures, float* kps7, int max_kps, int* n_kps);
 
@@ -292,6 +294,11 @@ int poppy_hip_pair_begin_descriptors(poppy_hip_ctx* ctx, const uint8_t* bgr1, si
  * corrected2 that poppy::morph hands back to its caller (src/poppy.hpp:46-47; src/poppy.cpp:326 chains it into the next pair). */
 int poppy_hip_pair_corrected2(poppy_hip_ctx* ctx, uint8_t* dst, size_t dst_stride);
 
+/* nfeatures = int(max_keypoints * 255 / max(detail2[0], detail2[1])) (src/extractor.cpp:40-45).  Where that quotient is no int (both details 0: two
+ * featureless images, whose foregrounds are constant), nfeatures is INT_MIN (-2147483648): what the reference's x86-64 build gets from the conversion
+ * (cvttsd2si), written out here.  The detector then keeps every candidate (OCV/features2d/src/keypoint.cpp:69-90 skips retainBest for n < 0);
+ * a flat image's ORB input is constant (all 256 grey levels), without any, so such a pair has no point pairs (poppy_hip_morph: POPPY_E_NOMATCH
+ * and the dissolve frames).  poppy_hip_orb_detect itself refuses nfeatures < 0.                                                          */
 int poppy_hip_pair_begin_info(poppy_hip_ctx* ctx, int* nfeatures, double* detail2);
 /* Pieces of the chain, host in / host out, for tests and for callers that cache intermediates:
  * poppy_hip_orb_input: goodFeatures (w*h) -> g = the ORB input image; optional us (grey of the unsharp-masked image), gb (Gabor

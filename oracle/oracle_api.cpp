@@ -102,10 +102,12 @@ int orc_morph_images(const uint8_t* c1, const uint8_t* c2, const float* gabor2, 
     return 0;
 }
 
+// The keypoint count, or MINUS the count when it exceeds maxKps (nothing copied): retainBest keeps ties, so the count has no bound in nfeatures
+// and a caller sizes its buffer from the refusal.  (Negative as before for every overflow: callers that only test < 0 are unaffected.)
 int orc_orb_detect(const uint8_t* img, int w, int h, int nfeatures, float* kps7, int maxKps, float* fast3, int maxFast, int* nFast) {
     std::vector<float> k, f;
     int n = orb_detect(wrap_u8(img, w, h, 1), nfeatures, k, &f);
-    if (n > maxKps) return -1;
+    if (n > maxKps) return -n;
     put(kps7, k);
     if (nFast) *nFast = (int)f.size() / 3;
     if (fast3 && (int)f.size() / 3 <= maxFast) put(fast3, f);

@@ -641,7 +641,12 @@ class Context:
         cap = max(2 * nfeatures + 64, 64)
         kp = np.zeros((cap, 7), np.float32)
         n = C.c_int(0)
-        self._chk(lib().poppy_hip_orb_detect(self.h, _p(g), w, w, h, nfeatures, _p(kp), cap, C.byref(n)), "orb_detect")
+        rc = lib().poppy_hip_orb_detect(self.h, _p(g), w, w, h, nfeatures, _p(kp), cap, C.byref(n))
+        if rc == -1 and n.value > cap:      # POPPY_E_ARG, count reported: retainBest kept more ties with the n-th response than the guess holds
+            cap = n.value
+            kp = np.zeros((cap, 7), np.float32)
+            rc = lib().poppy_hip_orb_detect(self.h, _p(g), w, w, h, nfeatures, _p(kp), cap, C.byref(n))
+        self._chk(rc, "orb_detect")
         return kp[:n.value].copy()
 
     def median_blur(self, img, ksize, form=0):

@@ -331,9 +331,8 @@ int setup_sharded(poppy_hip_ctx* c, Transport& T, const void* d1, const void* d2
     v[0] = d[0]; v[1] = d[1]; v[2] = rc == POPPY_OK ? 0.0 : 1.0;
     { const int ra = T.allmax(c, v, 3); if (ra) return ra; }
     if (v[2] != 0.0) return rc != POPPY_OK ? rc : fail(c, POPPY_E_STATE, "another rank failed in its part of the set-up");
-    const double detail = 255.0 / std::max(v[0], v[1]);                 // src/extractor.cpp:40-45
     c->last_detail[0] = v[0]; c->last_detail[1] = v[1];
-    const int nfeatures = (int)(c->cfg.max_keypoints * detail);
+    const int nfeatures = nfeatures_of(c->cfg.max_keypoints, v[0], v[1]);   // src/extractor.cpp:40-45
     c->last_nfeatures = nfeatures;
     // 3. ORB::detect where the ORB inputs lie
     std::vector<OrbKeyPoint> k1, k2;

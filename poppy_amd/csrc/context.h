@@ -166,6 +166,14 @@ struct PairStateHeader {
 };
 static_assert(sizeof(PairStateHeader) <= kPairHeadBytes, "header area too small");
 constexpr uint32_t kPairMagic = 0x50505931u;        // "PPY1"
+// nfeatures = int(max_keypoints * 255 / max(d1, d2)) (src/extractor.cpp:40-45).  Where the quotient is no int — both details 0 (two featureless images:
+// +inf) or 2^31 and more — C++ leaves the conversion undefined; the reference's x86-64 build converts with cvttsd2si, which gives INT_MIN for every such
+// value, and so does this, written out.  The detector's quotas stay in range with it (every quota <= 0: retainBest keeps every candidate).
+inline int nfeatures_of(int max_keypoints, double d1, double d2) {
+    const double m = std::max(d1, d2);
+    const double v = m > 0.0 ? max_keypoints * (255.0 / m) : HUGE_VAL;
+    return v >= -2147483648.0 && v < 2147483648.0 ? (int)v : INT32_MIN;
+}
 inline size_t pair_align(size_t v) { return (v + 255) & ~(size_t)255; }
 inline size_t pair_state_bytes(int W, int H) {
     const size_t P = (size_t)W * H;

@@ -392,7 +392,7 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
         if (serial_chains) return;                                // (one chain after the other: the second half follows below)
         details.wait_for(2);
         if (rcs[i ^ 1]) return;                                   // the other chain failed (its error is reported)
-        const int nf = (int)(c->cfg.max_keypoints * (255.0 / std::max(d[0], d[1])));
+        const int nf = nfeatures_of(c->cfg.max_keypoints, d[0], d[1]);
         if (orb.detect_finish(nf, st, i ? k2 : k1) < 0) { errs[i] = "orb_detect: " + orb.err; rcs[i] = POPPY_E_DEVICE; }
         ms_chain_end[i] = since(t_begin);
     };
@@ -414,9 +414,8 @@ static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, con
     c->chains_run += reuse ? 1 : 2;
     c->chains_reused += reuse ? 1 : 0;
     ms_chains = since(t_begin);
-    const double detail = 255.0 / std::max(d[0], d[1]);                 // src/extractor.cpp:40-45
     c->last_detail[0] = d[0]; c->last_detail[1] = d[1];
-    nfeatures = (int)(c->cfg.max_keypoints * detail);
+    nfeatures = nfeatures_of(c->cfg.max_keypoints, d[0], d[1]);          // src/extractor.cpp:40-45
     c->last_nfeatures = nfeatures;
     if (serial_chains) {
         int r1 = 0, r2 = 0;

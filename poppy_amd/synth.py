@@ -170,3 +170,96 @@ def fnv1a64(buf):
     for b in data.tobytes():
         hsh = ((hsh ^ b) * prime) & _M64
     return hsh
+
+
+# ---- content that reaches the set-up's content-dependent branches on purpose (flat, saturated, two-tone, tie-heavy) ------------------
+def as_bgr(gray):
+    """A grey image as BGR with three equal channels: cvtColor(BGR2GRAY) gives the grey image back (the weights sum to 1 << 14)."""
+    return np.ascontiguousarray(np.repeat(np.asarray(gray, np.uint8)[..., None], 3, axis=2))
+
+
+def flat_bgr(w, h, value):
+    """One colour everywhere: value is a grey level or a (b, g, r) triple.  Foreground and dft_detail2 of it are constant / 0."""
+    img = np.empty((h, w, 3), np.uint8)
+    img[...] = value
+    return img
+
+
+def checker(w, h, period, lo=0, hi=255, phase=0):
+    """Checkerboard of square cells `period` pixels wide, shifted by `phase` pixels along both axes; cell (0, 0) is lo.  Its FAST corners
+    come in families of exactly equal scores (the ties retainBest keeps, OCV/features2d/src/keypoint.cpp:69-90)."""
+    c = max(int(period), 1)
+    yy, xx = np.mgrid[0:h, 0:w]
+    odd = (((xx + phase) // c) + ((yy + phase) // c)) & 1
+    return np.where(odd == 1, hi, lo).astype(np.uint8)
+
+
+def checker_bgr(w, h, period, lo=0, hi=255, phase=0):
+    return as_bgr(checker(w, h, period, lo, hi, phase))
+
+
+def plateau(w, h, base, contrast):
+    """Flat `base` with four axis-aligned rectangles of exactly base + contrast (clipped to 0..255): every FAST ring difference is 0 or
+    +-contrast, so the corner test sits on its threshold (20, strict > in fast.cpp's threshold table) when contrast is 20 or 21."""
+    img = np.full((h, w), base, np.uint8)
+    v = int(np.clip(base + contrast, 0, 255))
+    for fx0, fy0, fx1, fy1 in ((0.2, 0.25, 0.4, 0.5), (0.55, 0.2, 0.8, 0.45), (0.25, 0.6, 0.45, 0.8), (0.6, 0.58, 0.75, 0.82)):
+        img[int(fy0 * h):int(fy1 * h), int(fx0 * w):int(fx1 * w)] = v
+    return img
+
+
+def dot_positions(w, h):
+    """Positions 0..16 px from each border (0, 1, 6 and 15: the 13 and 31 tap Gabor banks' radii and their window edges; 16 one further)
+    plus a few inside, all distinct."""
+    out = []
+    for d in (0, 1, 6, 15, 16):
+        out += [(d, h // 2), (w - 1 - d, h // 3), (w // 3, d), (2 * w // 3, h - 1 - d)]
+    out += [(w // 2, h // 2), (w // 4, h // 4), (3 * w // 4, 3 * h // 4)]
+    return sorted(set(out))
+
+
+def dots(w, h, positions=None, value=255, size=1):
+    """Black image with single pixels (size 1) or size x size squares (centred; clipped at the border) of `value` at `positions`."""
+    img = np.zeros((h, w), np.uint8)
+    r = size // 2
+    for x, y in (dot_positions(w, h) if positions is None else positions):
+        img[max(y - r, 0):y + r + 1, max(x - r, 0):x + r + 1] = value
+    return img
+
+
+def rings(w, h, radii=(6, 12, 20, 30, 44), lo=0, hi=255):
+    """Concentric bands about the image centre, symmetric about both image axes: the intensity-centroid moments (ICAngles,
+    OCV/features2d/src/orb.cpp:181-215) of every point on an axis vanish.  Band k is hi for even k, lo for odd k; r is measured in half pixels."""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.int64)
+    r2 = (2 * xx - (w - 1)) ** 2 + (2 * yy - (h - 1)) ** 2           # (2 r)^2: exact for even and odd sizes
+    band = np.zeros((h, w), np.int64)
+    for rr in radii:
+        band += r2 > (2 * rr) ** 2
+    return np.where(band % 2 == 0, hi, lo).astype(np.uint8)
+
+
+def near_flat(w, h, value=77, x=None, y=None, delta=1):
+    """Flat `value` with one pixel off by `delta` (at the centre unless given)."""
+    img = np.full((h, w), value, np.uint8)
+    x = w // 2 if x is None else x
+    y = h // 2 if y is None else y
+    img[y, x] = np.uint8(int(np.clip(value + delta, 0, 255)))
+    return img
+
+
+def uniform_noise(w, h, seed=3, channels=1):
+    """Independent uniform bytes from the hash (no block structure): FAST fires nearly everywhere."""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.int64)
+    planes = [(_hash32(xx, yy, seed + 7 * c) & np.uint64(0xFF)).astype(np.uint8) for c in range(channels)]
+    return planes[0] if channels == 1 else np.ascontiguousarray(np.stack(planes, axis=2))
+
+
+def channel_stripes(w, h, period=6):
+    """Vertical stripes of pure blue, green and red (255 in one channel, 0 in the others) between black ones, each period // 2 wide:
+    the grey conversion's rounding on single-channel input."""
+    img = np.zeros((h, w, 3), np.uint8)
+    c = max(period // 2, 1)
+    k = np.arange(w) // c
+    for ch in range(3):
+        img[:, k % 6 == 2 * ch, ch] = 255
+    return img

@@ -235,13 +235,17 @@ def morph_images(c1, c2, gabor2, p1, p2, shape, mask, levels=64, debug=False):
 def orb_detect(img, nfeatures, with_fast=False):
     g = np.ascontiguousarray(img, np.uint8)
     h, w = g.shape
-    kp = np.zeros((nfeatures * 2 + 64, 7), np.float32)
     mf = w * h // 4 + 16
     fast = np.zeros((mf, 3), np.float32)
     nf = C.c_int(0)
+    cap = max(nfeatures * 2 + 64, 64)
+    kp = np.zeros((cap, 7), np.float32)
     n = lib().orc_orb_detect(_vp(g), w, h, nfeatures, _vp(kp), len(kp), _vp(fast), mf, C.byref(nf))
-    if n < 0:
-        raise ValueError("orb_detect overflow")
+    if n < 0:                                        # retainBest kept more ties than the guess holds: the refusal is minus the exact count
+        kp = np.zeros((-n, 7), np.float32)
+        n = lib().orc_orb_detect(_vp(g), w, h, nfeatures, _vp(kp), len(kp), _vp(fast), mf, C.byref(nf))
+        if n < 0:
+            raise ValueError("orb_detect: %d keypoints do not fit %d" % (-n, len(kp)))
     return (kp[:n].copy(), fast[:nf.value].copy()) if with_fast else kp[:n].copy()
 
 
@@ -498,19 +502,33 @@ def frame_ratio(j, n, phase):
     return min(shape, 1.0)
 
 
-def pair_setup(img1, img2, max_keypoints=300, tolerance=1.0):
+INT_MIN = -(1 << 31)
+
+
+def nfeatures_of(max_keypoints, d1, d2):
+    """int(max_keypoints * 255 / max(d1, d2)) (src/extractor.cpp:40-45), INT_MIN where that is no int: both details 0 (two featureless images, +inf)
+    or a quotient of 2^31 and more.  The reference's double -> int conversion is cvttsd2si on x86-64, which gives INT_MIN for every such value."""
+    if d1 != d1 or d2 != d2:          # 0 / 0: an image one pixel wide or high has no spectrum rows or columns to keep; the library refuses such pairs
+        raise ValueError("dft_detail2 is NaN: no detail, no nfeatures")
+    m = max(d1, d2)
+    v = max_keypoints * (255.0 / m) if m > 0 else float("inf")
+    return int(v) if -2147483648.0 <= v < 2147483648.0 else INT_MIN
+
+
+def pair_setup(img1, img2, max_keypoints=300, tolerance=1.0, foregrounds=None, orb_inputs=None, with_gabor2=True):
     """poppy::morph up to its frame loop (src/poppy.hpp:46-160, no face detection, no auto-align) from the raw BGR pair:
-    dict(nfeatures, detail, g1, g2, kp1, kp2, points1, points2, gabor2, distance)."""
+    dict(nfeatures, detail, g1, g2, kp1, kp2, points1, points2, gabor2, distance).  foregrounds / orb_inputs: the two images' goodFeatures /
+    ORB inputs where the caller has them already (the slow part at large sizes); with_gabor2=False leaves gabor2 out (None)."""
     img1 = np.ascontiguousarray(img1, np.uint8); img2 = np.ascontiguousarray(img2, np.uint8)
     h, w = img1.shape[:2]
-    gf1, gf2 = foreground(img1)["foreground"], foreground(img2)["foreground"]
+    gf1, gf2 = foregrounds or (foreground(img1)["foreground"], foreground(img2)["foreground"])
     d1, d2 = dft_detail2(gf1), dft_detail2(gf2)
-    nfeatures = int(max_keypoints * (255.0 / max(d1, d2)))
-    g1, g2 = orb_input(gf1), orb_input(gf2)
+    nfeatures = nfeatures_of(max_keypoints, d1, d2)
+    g1, g2 = orb_inputs or (orb_input(gf1), orb_input(gf2))
     kp1, kp2 = orb_detect(g1, nfeatures), orb_detect(g2, nfeatures)
     n = min(len(kp1), len(kp2))
     f1, f2 = filter_invalid(kp1[:n, :2].copy(), kp2[:n, :2].copy(), w, h)
-    out = dict(nfeatures=nfeatures, detail=(d1, d2), g1=g1, g2=g2, kp1=kp1, kp2=kp2, gabor2=gabor_field(img2),
+    out = dict(nfeatures=nfeatures, detail=(d1, d2), g1=g1, g2=g2, kp1=kp1, kp2=kp2, gabor2=gabor_field(img2) if with_gabor2 else None,
                points1=f1[:0], points2=f2[:0], distance=None)
     if len(f1):
         md = morph_distance(f1, f2, w, h)
