@@ -136,14 +136,37 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * poppy_bgr_to_i420 is the host statement of the format, poppy_frame_bytes its size (0 for an unknown format or an empty frame).
  * poppy_hip_set_frame_format drains the context's frames and applies to every frame handed to a writer by poppy_hip_morph,
  * poppy_hip_morph_frames, poppy_hip_render_many, poppy_hip_render_phases and poppy_hip_morph_list — the phase == 0 / 1 and t == 0 / 1
- * copies and the POPPY_E_NOMATCH linear-blend frames included; under I420 the writer gets (frame, width, height, stride = width).
+ * copies and the POPPY_E_NOMATCH linear-blend frames included; under I420 and PAL8 the writer gets (frame, width, height, stride = width).
  * Any other format: POPPY_E_ARG.  These stay BGR whatever the setting: poppy_hip_render / poppy_hip_dissolve into an explicit dst,
  * poppy_hip_frame_device, frames kept on the device (write == NULL), poppy_hip_morph_sharded and poppy_hip_morph_pairs (their contexts
- * are made from poppy_settings), and include/poppy_hip_shim.hpp.  poppy_hip_pool_set_frame_format sets every context of a pool.  */
-enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1 };
+ * are made from poppy_settings), and include/poppy_hip_shim.hpp.  poppy_hip_pool_set_frame_format sets every context of a pool.
+ *
+ * POPPY_FRAME_PAL8: the frame quantised to 256 colours on the GPU before the copy, for GIF and other palette writers (a third of BGR's
+ * bytes on the link).  Layout of a width x height frame: width * height index bytes (tight rows, stride = width), then a 768-byte palette,
+ * 256 entries of R, G, B (GIF's order); poppy_frame_bytes = width * height + 768, and the writer gets (frame, width, height, stride =
+ * width) with the palette at frame + width * height.  Its value is 8 and POPPY_SINK_GIF is 8 because the values 2 (frame format) and 4
+ * (sink) are documented and tested as "unknown format" and stay so; both enums continue from 8.
+ * The palette is built per frame, nothing is carried between frames, and there is no dithering.  Integer arithmetic throughout:
+ *   1. Histogram.  Cell of a pixel = (R >> 3, G >> 3, B >> 3), 32^3 cells; per cell the pixel count and the sums of the full 8-bit R, G, B.
+ *      The sums are 32-bit: a frame of more than POPPY_PAL8_MAX_PIXELS = 2^24 pixels (2^24 * 255 < 2^32) is refused with
+ *      POPPY_E_UNSUPPORTED, by poppy_bgr_to_pal8 and by every call that would hand such a frame to a writer under this format.
+ *   2. Median cut over the cells.  A box is a cell range [lo, hi] per axis, always shrunk to the bounding box of its occupied cells.  Start
+ *      with one box around all occupied cells.  Until there are 256 boxes or no box spans more than one cell: take the box with the largest
+ *      count * (longest side in cells) among the boxes that span more than one cell (64-bit product; ties: the lowest box index); cut it
+ *      along its longest side (ties: G, then R, then B) at the smallest position k for which the pixels at coordinates <= k are at least
+ *      (count + 1) / 2, clamped to k < hi so that both halves are non-empty; the lower half keeps the box's index, the upper half takes
+ *      the next free index; both are shrunk.
+ *   3. Colours.  Entry i = per channel (sum + count / 2) / count over box i; entries without a box are 0.
+ *   4. Indices.  A pixel's index is the box that holds its cell (a table look-up, NOT a nearest-colour search), so every channel of
+ *      palette[index] is within 8 * (the box's side) of the pixel, and a frame with at most 256 occupied cells and one colour per cell
+ *      comes back exactly.
+ * poppy_bgr_to_pal8 is the host statement of all this (dst: poppy_frame_bytes(POPPY_FRAME_PAL8, width, height) bytes).  */
+#define POPPY_PAL8_MAX_PIXELS (1 << 24)
+enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_bgr_to_pal8(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 /* phase == 0 / phase == 1 follow the reference's short-circuit (src/poppy.hpp:54-70): number_of_frames copies of image 1 /
  * image 2 as they were handed to the pair set-up (with auto-align: the UNALIGNED image 2), no frame is rendered.            */
 
@@ -467,10 +490,15 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * to back; PPM: one P6 file per frame, `path` holds exactly one %d, %<width>d or %0<width>d for the frame index (the library substitutes
  * it itself; any other conversion, or none, makes poppy_sink_open return NULL); Y4M: one YUV4MPEG2 file, C444, full-range BT.601.
  * Y4M420: one YUV4MPEG2 file, C420jpeg XCOLORRANGE=FULL, written from POPPY_FRAME_I420 frames as they come (stride must be the width).
- * The BGR sinks take frames with stride >= 3 * width, the I420 sink frames with stride == width: a frame of the other format fails the sink.
+ * GIF: one GIF89a file written from POPPY_FRAME_PAL8 frames as they come (stride must be the width; width, height <= 65535): no global colour
+ * table, a NETSCAPE2.0 block that loops forever, and per frame a graphic control extension (delay = fps_den * 100 / fps_num rounded to the
+ * nearest centisecond, at least 1), an image descriptor with the frame's palette as a 256-entry local colour table and LZW data (minimum
+ * code size 8).  No frame differencing, no transparency.
+ * The BGR sinks take frames with stride >= 3 * width, the I420 and GIF sinks frames with stride == width: a frame of another format fails the
+ * sink where its stride tells (a BGR frame at the I420 or GIF sink, an I420 or PAL8 frame at a BGR sink); a writer must match the context's format.
  * poppy_sink_close returns the number of frames written, or a negative status if a write failed or a frame had another geometry.   */
 typedef struct poppy_sink poppy_sink;
-enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3 };
+enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8 };
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den);
 void poppy_sink_write(void* sink, const uint8_t* bgr, int width, int height, size_t stride);
 int poppy_sink_close(poppy_sink* sink);

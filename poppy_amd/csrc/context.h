@@ -43,8 +43,12 @@ struct FrameSlot {
     void* h_blob_dev = nullptr;                     // device-side address of the pinned copy
     hipEvent_t uploaded = nullptr;                  // the device copy is complete
     hipGraphExec_t body = nullptr;                  // pyrdown .. unsharp of this slot, captured once per pair geometry
-    bool body_i420 = false;                         // ... with the I420 conversion behind the unsharp (re-captured when that changes)
-    uint8_t* i420 = nullptr;                        // the frame as I420 for the writer (allocated while the context's frame format is I420)
+    int body_format = POPPY_FRAME_BGR;              // ... with this format's conversion behind the unsharp (re-captured when that changes)
+    uint8_t* i420 = nullptr;                        // the frame as I420 for the writer (allocated when the format is I420 and a pair is there; kept until the pair's buffers go)
+    uint8_t* pal8 = nullptr;                        // the frame as PAL8 for the writer, and the conversion's tables (kernels.h: kPal8TableBytes) — the slot's own,
+    uint8_t* pal8_tables = nullptr;                 // because the conversions of frames in flight run beside each other (allocated like i420; the stream and event live as long as the context)
+    hipStream_t fmt_stream = nullptr;               // chained PAL8 frames: the conversion's side stream (the chain goes on from the unsharp: enqueue_body)
+    hipEvent_t bgr_done = nullptr;                  // ... and the event that rides on that unsharp
     hipEvent_t downloaded = nullptr;                // completes when the last download of this slot's `out` towards the writer has read it
     bool dl_pending = false;                        // ... and whether such a download was issued since the slot was last rendered into
     int dl_ring_idx = -1;                           // POPPY_HIP_DL_STREAMS: the ring stream that carries that download
@@ -105,7 +109,8 @@ struct poppy_hip_ctx {
     Team planners;                                  // the frame planners of multi-frame calls
     bool writer_attached = false;                   // a multi-frame call with a writer is in progress
     int frame_format = POPPY_FRAME_BGR;             // of the frames handed to writers (poppy_hip_set_frame_format)
-    uint8_t* i420_scratch = nullptr; size_t i420_scratch_bytes = 0;      // I420 of the copies and fallback frames that no slot renders (download_frame)
+    uint8_t* i420_scratch = nullptr; size_t i420_scratch_bytes = 0;      // I420 / PAL8 of the copies and fallback frames that no slot renders (download_frame)
+    uint8_t* pal8_scratch_tables = nullptr;         // ... and the PAL8 conversion's tables for them
     double wait_ms[4] = {0, 0, 0, 0};               // host waits inside submit_frame since the context was made (POPPY_SEQ_TIMING prints the per-sequence share)
     ForegroundFilter foreground, foreground_b;      // two instances: the images of a pair are filtered side by side
     // The two chain slots (slot 0 = foreground + orb, slot 1 = foreground_b + orb_b; chain_fg / chain_orb below).  After a set-up from raw images the slot
@@ -206,8 +211,8 @@ int finish_pair_load(poppy_hip_ctx* c);                                         
 // the frame hand-off's format (poppy_hip_set_frame_format): a device frame (tight u8x3, W x H) in the writer's format in `host`, queued on
 // c->stream and waited for; *stride = what the writer is told
 int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride);
-// a host frame in the writer's format: `bgr` itself (BGR) or its I420 in `tmp`
-const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride);
+// a host frame in the writer's format: `bgr` itself (BGR) or its I420 / PAL8 in `tmp`; nullptr, *status and c->err set, when the format refuses the frame
+const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status);
 
 // blur_margin (pair_setup.cpp): the taps, the image's place in the canvas, and canvas -> padded image on the device
 constexpr int kBlurMarginTaps = 127;

@@ -6,8 +6,11 @@
 //   POPPY_SINK_Y4M   one YUV4MPEG2 file, C444, full-range BT.601 in 8-bit integer arithmetic (lossless containers downstream can
 //                    re-encode it; the conversion is this file's, not the reference's)
 //   POPPY_SINK_Y4M420  one YUV4MPEG2 file, C420jpeg, that takes I420 frames as they are (poppy_hip_set_frame_format)
+//   POPPY_SINK_GIF   one animated GIF89a file that takes PAL8 frames as they are: a local colour table and one LZW image per frame
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "../../include/poppy_hip.h"
+#include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -20,7 +23,71 @@ struct poppy_sink {
     int pad = 0; bool zero = false;    // PPM: width and zero flag of the conversion (%d, %5d, %05d)
     FILE* f = nullptr;
     std::vector<uint8_t> row;
+    int delay_cs = 3;                  // GIF: the frames' delay in centiseconds
 };
+
+namespace {
+
+// GIF's variable-width LZW (minimum code size 8): codes 0..255 the bytes, 256 clear, 257 end, strings from 258; the width grows from 9 to 12 bits
+// when the entry just added is the first that needs the next width (what decoders mirror one entry behind), and a clear code restarts the table
+// when it is full.  The packed bits go out in sub-blocks of at most 255 bytes.
+struct GifLzw {
+    FILE* f;
+    bool ok = true;
+    uint32_t acc = 0; int n_acc = 0;
+    uint8_t block[255]; int n_block = 0;
+    static constexpr int kHash = 8192;                      // open addressing over (prefix << 8 | byte); at most 3838 strings live
+    std::vector<uint32_t> key; std::vector<uint16_t> val;
+    explicit GifLzw(FILE* file) : f(file), key(kHash), val(kHash) {}
+    void flush_block() {
+        if (!n_block) return;
+        const uint8_t len = (uint8_t)n_block;
+        if (fwrite(&len, 1, 1, f) != 1 || fwrite(block, 1, (size_t)n_block, f) != (size_t)n_block) ok = false;
+        n_block = 0;
+    }
+    void put(int code, int width) {
+        acc |= (uint32_t)code << n_acc; n_acc += width;
+        while (n_acc >= 8) { block[n_block++] = (uint8_t)acc; acc >>= 8; n_acc -= 8; if (n_block == 255) flush_block(); }
+    }
+    void reset() { std::fill(key.begin(), key.end(), 0xffffffffu); }
+    void encode(const uint8_t* px, size_t n) {
+        const int kClear = 256, kEnd = 257;
+        int width = 9, next = 258;
+        reset();
+        put(kClear, width);
+        int prefix = px[0];
+        for (size_t i = 1; i < n; ++i) {
+            const uint32_t k = ((uint32_t)prefix << 8) | px[i];
+            uint32_t h = (k * 2654435761u) >> 19;            // 13 bits
+            while (key[h] != 0xffffffffu && key[h] != k) h = (h + 1) & (kHash - 1);
+            if (key[h] == k) { prefix = val[h]; continue; }
+            put(prefix, width);
+            if (next == 4096) { put(kClear, width); reset(); width = 9; next = 258; }
+            else { key[h] = k; val[h] = (uint16_t)next; if (next == (1 << width)) ++width; ++next; }
+            prefix = px[i];
+        }
+        put(prefix, width);
+        put(kEnd, width);
+        if (n_acc) { block[n_block++] = (uint8_t)acc; acc = 0; n_acc = 0; if (n_block == 255) flush_block(); }
+        flush_block();
+        const uint8_t zero = 0;
+        if (fwrite(&zero, 1, 1, f) != 1) ok = false;         // the block terminator
+    }
+};
+
+bool gif_frame(poppy_sink* s, const uint8_t* pal8) {
+    const int w = s->w, h = s->h;
+    const size_t n = (size_t)w * h;
+    const uint8_t gce[8] = {0x21, 0xF9, 4, 0, (uint8_t)(s->delay_cs & 255), (uint8_t)(s->delay_cs >> 8), 0, 0};
+    const uint8_t desc[10] = {0x2C, 0, 0, 0, 0, (uint8_t)(w & 255), (uint8_t)(w >> 8), (uint8_t)(h & 255), (uint8_t)(h >> 8), 0x87};      // local table, 256 entries
+    const uint8_t min_code = 8;
+    if (fwrite(gce, 1, 8, s->f) != 8 || fwrite(desc, 1, 10, s->f) != 10 || fwrite(pal8 + n, 1, 768, s->f) != 768 || fwrite(&min_code, 1, 1, s->f) != 1) return false;
+    GifLzw z(s->f);
+    z.encode(pal8, n);
+    return z.ok;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -29,6 +96,7 @@ size_t poppy_frame_bytes(int format, int width, int height) {
     const size_t w = (size_t)width, h = (size_t)height;
     if (format == POPPY_FRAME_BGR) return w * h * 3;
     if (format == POPPY_FRAME_I420) return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2);
+    if (format == POPPY_FRAME_PAL8) return w * h + 768;
     return 0;
 }
 
@@ -61,7 +129,7 @@ int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, 
 }
 
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den) {
-    if (!path || width <= 0 || height <= 0 || format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420) return nullptr;
+    if (!path || width <= 0 || height <= 0 || (format != POPPY_SINK_GIF && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
     poppy_sink* s = new poppy_sink();
     s->format = format; s->w = width; s->h = height; s->path = path;
     if (format == POPPY_SINK_PPM) {
@@ -85,6 +153,7 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
         if (bad || !seen) { delete s; return nullptr; }
         s->path = head; s->tail = tail;
     }
+    if (format == POPPY_SINK_GIF && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen: every write fails, close says so
     if (format != POPPY_SINK_PPM) {
         s->f = fopen(path, "wb");
         if (!s->f) { delete s; return nullptr; }
@@ -92,6 +161,15 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
             fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C444 XCOLORRANGE=FULL\n", width, height, fps_num > 0 ? fps_num : 30, fps_den > 0 ? fps_den : 1);
         else if (format == POPPY_SINK_Y4M420)
             fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=FULL\n", width, height, fps_num > 0 ? fps_num : 30, fps_den > 0 ? fps_den : 1);
+        else if (format == POPPY_SINK_GIF) {
+            const long long num = fps_num > 0 ? fps_num : 30, den = fps_den > 0 ? fps_den : 1;
+            const long long cs = (den * 100 + num / 2) / num;
+            s->delay_cs = (int)(cs < 1 ? 1 : cs > 65535 ? 65535 : cs);
+            // header, logical screen without a global colour table, the NETSCAPE2.0 application block: loop for ever
+            const uint8_t head[13] = {'G', 'I', 'F', '8', '9', 'a', (uint8_t)(width & 255), (uint8_t)(width >> 8), (uint8_t)(height & 255), (uint8_t)(height >> 8), 0x70, 0, 0};
+            const uint8_t loop[19] = {0x21, 0xFF, 11, 'N', 'E', 'T', 'S', 'C', 'A', 'P', 'E', '2', '.', '0', 3, 1, 0, 0, 0};
+            if (fwrite(head, 1, 13, s->f) != 13 || fwrite(loop, 1, 19, s->f) != 19) s->failed = true;
+        }
     }
     s->row.resize((size_t)width * 3);
     return s;
@@ -101,9 +179,13 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
     poppy_sink* s = (poppy_sink*)user;
     if (!s || s->failed) return;
     // (an I420 frame comes with stride == width: the BGR sinks refuse it, and the I420 sink refuses anything else)
-    const bool i420 = s->format == POPPY_SINK_Y4M420;
-    if (!bgr || width != s->w || height != s->h || (i420 ? stride != (size_t)width : stride < (size_t)width * 3)) { s->failed = true; return; }
+    const bool i420 = s->format == POPPY_SINK_Y4M420, pal8 = s->format == POPPY_SINK_GIF;
+    if (!bgr || width != s->w || height != s->h || ((i420 || pal8) ? stride != (size_t)width : stride < (size_t)width * 3)) { s->failed = true; return; }
     FILE* f = s->f;
+    if (pal8) {
+        if (!gif_frame(s, bgr)) s->failed = true; else ++s->frames;
+        return;
+    }
     if (i420) {
         const size_t n = poppy_frame_bytes(POPPY_FRAME_I420, width, height);
         if (fputs("FRAME\n", f) < 0 || fwrite(bgr, 1, n, f) != n) s->failed = true; else ++s->frames;
@@ -150,6 +232,7 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
 
 int poppy_sink_close(poppy_sink* s) {
     if (!s) return POPPY_E_ARG;
+    if (s->f && s->format == POPPY_SINK_GIF && !s->failed && fputc(0x3B, s->f) == EOF) s->failed = true;      // the trailer
     const int n = s->failed ? POPPY_E_DEVICE : s->frames;
     if (s->f) fclose(s->f);
     delete s;

@@ -93,12 +93,12 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
     int rc = fetch(0, a); if (rc) return rc;
     rc = fetch(1, b); if (rc) return rc;
     if (phase == 0 || phase == 1) {                            // two images: poppy_hip_morph's short-circuit, before any feature work
-        if (write && c->frame_format == POPPY_FRAME_I420) {     // (the writer's format: converted on the device, or on the host for host images as poppy_hip_morph does)
+        if (write && c->frame_format != POPPY_FRAME_BGR) {      // (the writer's format: converted on the device, or on the host for host images as poppy_hip_morph does)
             const ListImage& img = phase == 0 ? a : b;
             std::vector<uint8_t> host; size_t stride = 0;
             const uint8_t* frame = nullptr;
             if (img.dev) { rc = download_frame(c, img.p, W, H, host, &stride); if (rc) return rc; frame = host.data(); }
-            else frame = host_frame(c, img.p, img.stride, W, H, host, &stride);
+            else { frame = host_frame(c, img.p, img.stride, W, H, host, &stride, &rc); if (!frame) return rc; }
             PairWriter pw{write, user, 0, 0};
             for (int j = 0; j < N; ++j) pair_writer_cb(&pw, frame, W, H, stride);
         } else if (write) {
@@ -123,7 +123,7 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
                 HIPCHK(c, hipGetLastError());
                 std::vector<uint8_t> blend;
                 size_t stride = (size_t)W * 3;
-                if (c->frame_format == POPPY_FRAME_I420) rc = download_frame(c, c->slots[0].out, W, H, blend, &stride);
+                if (c->frame_format != POPPY_FRAME_BGR) rc = download_frame(c, c->slots[0].out, W, H, blend, &stride);
                 else rc = list_download(c, c->slots[0].out, W, H, blend);
                 if (rc) return rc;
                 PairWriter pw{write, user, k, 0};

@@ -203,4 +203,15 @@ void launch_dissolve(const uint8_t* a, const uint8_t* b, uint8_t* dst, size_t n,
 // tight u8x3 BGR -> I420 (kernels_frame_format.hip; the format: include/poppy_hip.h, POPPY_FRAME_I420).  `done` (optional) rides on the last dispatch.
 void launch_bgr_to_i420(const uint8_t* src, uint8_t* dst, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
 
+// tight u8x3 BGR -> PAL8 (kernels_frame_pal8.hip; the format: include/poppy_hip.h, POPPY_FRAME_PAL8), three dispatches on one stream: the cells' histogram,
+// the palette build (one workgroup; writes the palette behind dst's index plane), the index plane.  `tables`: kPal8TableBytes of device memory that is all
+// zero before the first frame (the build leaves the histogram zero again) and that no other frame uses meanwhile: two 64-bit words per cell, then the
+// cell -> index table.  `done` (optional) rides on the last dispatch.  prepare_pal8: raises the build's dynamic-LDS limit on the CURRENT device (kept per device; cheap when
+// already done); call it with the context's device current and outside stream capture before that context's first launch.
+constexpr size_t kPal8TableOffset = (size_t)32768 * 16, kPal8TableBytes = kPal8TableOffset + 32768;
+bool prepare_pal8();
+void launch_pal8_hist(const uint8_t* src, uint8_t* tables, int w, int h, hipStream_t s);
+void launch_pal8_build(uint8_t* tables, uint8_t* dst, int w, int h, hipStream_t s);
+void launch_pal8_remap(const uint8_t* src, const uint8_t* tables, uint8_t* dst, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
+
 }  // namespace poppy_hip

@@ -94,8 +94,8 @@ static void free_pair(poppy_hip_ctx* c) {
         void* fb[] = {f.tr1, f.tr2, f.out, f.pyrL, f.pyrR, f.pyrM, f.pyrB, f.tmp, f.diff, f.unsharpF, f.triMap};
         for (void* b : fb) if (b) (void)hipFree(b);
         f.tr1 = f.tr2 = f.out = nullptr; f.pyrL = f.pyrR = f.pyrM = f.pyrB = f.tmp = f.diff = f.unsharpF = nullptr; f.triMap = nullptr;
-        if (f.i420) (void)hipFree(f.i420);
-        f.i420 = nullptr;
+        for (uint8_t* b : {f.i420, f.pal8, f.pal8_tables}) if (b) (void)hipFree(b);
+        f.i420 = f.pal8 = f.pal8_tables = nullptr;
     }
     for (FrameSlot& f : c->slots) {
         if (f.body) { (void)hipGraphExecDestroy(f.body); f.body = nullptr; }
@@ -113,7 +113,8 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     (void)poppy_hip_comm_free(c);
-    for (FrameSlot& f : c->slots) { if (f.stream) (void)hipStreamSynchronize(f.stream); if (f.own_stream) (void)hipStreamSynchronize(f.own_stream); }
+    for (FrameSlot& f : c->slots)
+        for (hipStream_t st : {f.stream, f.own_stream, f.fmt_stream}) if (st) (void)hipStreamSynchronize(st);
     free_pair(c);
     for (FrameSlot& f : c->slots) {
         if (f.done) (void)hipEventDestroy(f.done);
@@ -121,6 +122,8 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
         if (f.downloaded) (void)hipEventDestroy(f.downloaded);
         if (f.uploaded) (void)hipEventDestroy(f.uploaded);
         if (f.own_stream) (void)hipStreamDestroy(f.own_stream);
+        if (f.fmt_stream) (void)hipStreamDestroy(f.fmt_stream);
+        if (f.bgr_done) (void)hipEventDestroy(f.bgr_done);
     }
     if (c->inputs_ready) (void)hipEventDestroy(c->inputs_ready);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -138,6 +141,7 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
     for (void* p : {(void*)c->bm_canvas, (void*)c->bm_tmp, (void*)c->bm_taps, (void*)c->list_img[0], (void*)c->list_img[1]}) if (p) (void)hipFree(p);
     if (c->d_comm_scratch) (void)hipFree(c->d_comm_scratch);
     if (c->i420_scratch) (void)hipFree(c->i420_scratch);
+    if (c->pal8_scratch_tables) (void)hipFree(c->pal8_scratch_tables);
     c->aligner.release();
     (void)hipStreamDestroy(c->copy_stream);
     (void)hipStreamDestroy(c->stream);
@@ -233,9 +237,46 @@ static int alloc_slot_i420(poppy_hip_ctx* c) {
     return POPPY_OK;
 }
 
+// the PAL8 conversion's tables: zero before the first frame (the palette build leaves them zero again)
+static int alloc_pal8_tables(poppy_hip_ctx* c, uint8_t** tables) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!prepare_pal8()) return fail(c, POPPY_E_DEVICE, "could not raise the palette build's LDS limit");      // (per device: kernels.h)
+    HIPCHK(c, hipMalloc((void**)tables, kPal8TableBytes));
+    HIPCHK(c, hipMemset(*tables, 0, kPal8TableBytes));
+    return POPPY_OK;
+}
+
+static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H <= (unsigned long long)POPPY_PAL8_MAX_PIXELS; }
+
+// every slot's PAL8 buffer, tables, side stream and event for the pair's geometry (while the context's frame format is PAL8)
+static int alloc_slot_pal8(poppy_hip_ctx* c) {
+    if (!pal8_fits(c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8 takes frames of at most 2^24 pixels");
+    const size_t bytes = poppy_frame_bytes(POPPY_FRAME_PAL8, c->W, c->H);
+    for (FrameSlot& f : c->slots) {
+        if (!f.pal8) HIPCHK(c, hipMalloc((void**)&f.pal8, bytes + 16));
+        if (!f.pal8_tables) { int rc = alloc_pal8_tables(c, &f.pal8_tables); if (rc) return rc; }
+        // The side streams are created at the LOWEST stream priority.  The runtime keeps its hardware queues per priority, so they never share a queue with the
+        // chain's stream or the plan upload's (normal priority): a dispatch waits for the one before it in its hardware queue whatever its stream, and a
+        // 350 us palette build in the chain's queue held the next frame's warp back for its whole length (kernel trace).
+        if (!f.fmt_stream) {
+            int least = 0, greatest = 0;
+            HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+            HIPCHK(c, hipStreamCreateWithPriority(&f.fmt_stream, hipStreamNonBlocking, least));
+        }
+        if (!f.bgr_done) HIPCHK(c, hipEventCreateWithFlags(&f.bgr_done, hipEventDisableTiming));
+    }
+    return POPPY_OK;
+}
+
+static int alloc_slot_format(poppy_hip_ctx* c) {
+    return c->frame_format == POPPY_FRAME_I420 ? alloc_slot_i420(c) : c->frame_format == POPPY_FRAME_PAL8 ? alloc_slot_pal8(c) : POPPY_OK;
+}
+
 int alloc_pair(poppy_hip_ctx* c, int W, int H) {
     { int rc = drain_frames(c); if (rc) return rc; }              // every pair loader comes through here: no frame still reads the old pair
-    if (c->W == W && c->H == H && c->c1) return POPPY_OK;
+    // PAL8 takes frames of at most 2^24 pixels: refused before anything is allocated or any state changes, so the context keeps the pair it had
+    if (c->frame_format == POPPY_FRAME_PAL8 && !pal8_fits(W, H)) return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8 takes frames of at most 2^24 pixels");
+    if (c->W == W && c->H == H && c->c1) return alloc_slot_format(c);      // (allocates only what is missing: nothing, unless an earlier attempt failed half-way)
     free_pair(c);
     c->pyr_forms.clear();
     if (c->cfg.pyramid_levels < 1 || c->cfg.pyramid_levels > 256) return fail(c, POPPY_E_UNSUPPORTED, "pyramid_levels must be in [1,256]");
@@ -287,7 +328,7 @@ int alloc_pair(poppy_hip_ctx* c, int W, int H) {
         if (!c->tail.desc.empty()) HIPCHK(c, hipMemcpy(c->d_levels, c->tail.desc.data(), c->tail.desc.size() * 4, hipMemcpyHostToDevice));
     }
     c->W = W; c->H = H;
-    return c->frame_format == POPPY_FRAME_I420 ? alloc_slot_i420(c) : POPPY_OK;
+    return alloc_slot_format(c);
 }
 
 int set_points(poppy_hip_ctx* c, const float* p1, const float* p2, int n) {
@@ -315,6 +356,7 @@ int drain_frames(poppy_hip_ctx* c) {
     for (FrameSlot& f : c->slots) {
         if (f.stream) HIPCHK(c, hipStreamSynchronize(f.stream));
         if (f.own_stream && f.own_stream != f.stream) HIPCHK(c, hipStreamSynchronize(f.own_stream));
+        if (f.fmt_stream) HIPCHK(c, hipStreamSynchronize(f.fmt_stream));
     }
     return POPPY_OK;
 }
@@ -510,9 +552,14 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
     std::vector<std::atomic<int>>& ready = sp->ready;
     std::atomic<int>& next = sp->next;
     int rc = POPPY_OK;
-    // the writer's format (poppy_hip_set_frame_format): I420 frames are converted by the frame body into the slot's i420 buffer (enqueue_body)
-    const bool i420 = write && c->frame_format == POPPY_FRAME_I420;
-    const size_t row = i420 ? (size_t)W : (size_t)W * 3, frame_bytes = i420 ? poppy_frame_bytes(POPPY_FRAME_I420, W, H) : row * H;
+    // the writer's format (poppy_hip_set_frame_format): I420 and PAL8 frames are converted by the frame body into the slot's i420 / pal8 buffer (enqueue_body)
+    const int fmt = write ? c->frame_format : POPPY_FRAME_BGR;
+    // (every way to this format with a pair allocates the slots' buffers — alloc_pair, poppy_hip_set_frame_format — or refuses: a frame is never converted into nothing)
+    for (const FrameSlot& f : c->slots)
+        if ((fmt == POPPY_FRAME_I420 && !f.i420) || (fmt == POPPY_FRAME_PAL8 && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)))
+            return fail(c, POPPY_E_STATE, "the frame format's buffers are not allocated for this pair");
+    const size_t row = fmt != POPPY_FRAME_BGR ? (size_t)W : (size_t)W * 3, frame_bytes = poppy_frame_bytes(fmt, W, H);
+    auto frame_of = [fmt](const FrameSlot& f) -> const uint8_t* { return fmt == POPPY_FRAME_I420 ? f.i420 : fmt == POPPY_FRAME_PAL8 ? f.pal8 : f.out; };
     static const int ring_pref = getenv("POPPY_HIP_RING") ? std::max(1, atoi(getenv("POPPY_HIP_RING"))) : 3;
     const int R = std::min({poppy_hip_ctx::kStageRing, ring_pref, (int)c->slots.size()});
     const size_t slot_bytes = (frame_bytes + 255) & ~(size_t)255;     // ring slots start on 256-byte boundaries
@@ -535,6 +582,7 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
     const double w0[4] = {c->wait_ms[0], c->wait_ms[1], c->wait_ms[2], c->wait_ms[3]};
     auto lap = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
     std::vector<int> slot_of(n, -1);
+    const int pal8_lag = fmt == POPPY_FRAME_PAL8 ? std::max(0, (int)c->slots.size() - 2) : 0;
     int issued = 0;                                               // downloads queued so far (frames 0 .. issued-1)
     // Round 6: a frame copy goes to the stream of its pinned ring buffer, which carries nothing else, and NO event is recorded behind it — whoever needs the copy
     // finished synchronises that stream.  An event record behind a copy is a marker packet that waits, in one of the process's four hardware queues, for the copy's
@@ -550,7 +598,7 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
         ms_done += lap(t0);
         if (dl_streams) {
             if (e == hipSuccess && !c->dl_ring[r]) e = hipStreamCreateWithFlags(&c->dl_ring[r], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, i420 ? f.i420 : f.out, frame_bytes, hipMemcpyDeviceToHost, c->dl_ring[r]);
+            if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, frame_of(f), frame_bytes, hipMemcpyDeviceToHost, c->dl_ring[r]);
             f.dl_pending = true; f.dl_ring_idx = r;
             if (e != hipSuccess) { c->err = std::string("frame download: ") + hipGetErrorString(e); rc = POPPY_E_DEVICE; return false; }
             return true;
@@ -560,7 +608,7 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
         static const bool skip_copy = getenv("POPPY_DL_SKIP_COPY") != nullptr;      // timing experiment: every wait and event of the writer path, no bytes moved (wrong frames)
         if (!skip_copy)
 #endif
-        if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, i420 ? f.i420 : f.out, frame_bytes, hipMemcpyDeviceToHost, c->dl_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, frame_of(f), frame_bytes, hipMemcpyDeviceToHost, c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(c->dl_done[r], c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(f.downloaded, c->dl_stream);          // the slot's own: ring events are re-recorded every R frames
         f.dl_pending = true;
@@ -606,7 +654,10 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
         if (rc != POPPY_OK) break;
         slot_of[j] = c->last_slot;
         if (write) {
-            const int upto = dev_wait ? j + 1 : j;                // frames whose download can be issued now
+            // frames whose download can be issued now.  A PAL8 frame is complete one palette build (several frame times) behind its BGR: waiting for frame
+            // j - 1 here would hold back frame j + 1 for that long, so under PAL8 the downloads trail as far as the slots allow (the loop above the
+            // submit sends what a slot's reuse forces out) and the conversions of that many frames run beside each other.
+            const int upto = (dev_wait ? j + 1 : j) - pal8_lag;
             while (issued < upto && rc == POPPY_OK) {
                 while (issued - written >= R && rc == POPPY_OK) deliver(written);
                 if (rc == POPPY_OK && issue_download(issued)) ++issued;
@@ -635,12 +686,12 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
 
 static_assert(kPlanRasterRows == kRasterChunkRows, "the plan's work list and k_raster must agree on the chunk height");
 
-// the frames being submitted go to a writer that takes I420 (their slots' bodies end with the conversion)
-static bool frame_wants_i420(const poppy_hip_ctx* c) { return c->writer_attached && c->frame_format == POPPY_FRAME_I420; }
+// the format the frames being submitted are converted to for their writer (their slots' bodies end with the conversion); BGR: none
+static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached ? c->frame_format : POPPY_FRAME_BGR; }
 
 // pyrdown .. unsharp of one slot.  Every argument is fixed for the life of the pair (the per-frame unsharp amount is
 // read from the slot's plan blob), which is what lets the whole sequence be captured into one graph launch.
-static void enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm, float amount, bool debug, hipEvent_t done = nullptr) {
+static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm, float amount, bool debug, hipEvent_t done = nullptr, bool chained = false) {
     const int W = c->W, H = c->H, L = c->cfg.pyramid_levels;
     const int ft = c->first_tail < L ? c->first_tail : L;
     static const bool fuse = getenv("POPPY_HIP_NOFUSE") == nullptr;
@@ -710,21 +761,37 @@ static void enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* t
     if (tm) tm->mark("collapse");
     // A frame for a writer that takes I420 is converted right behind its unsharp, on the same stream, and the frame's completion event rides on the
     // conversion: the host waits for that event, then issues the copy of the slot's I420 buffer (render_sequence), which depends on nothing
-    const bool i420 = frame_wants_i420(c);
-    launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s, i420 ? nullptr : done, c->levels[0].pitch);
+    // PAL8 is three dispatches, and the palette build in the middle is one workgroup's serial work (about as long as the rest of the frame).  The next chained
+    // frame needs this frame's BGR, not its palette form: on the chain (`chained` with a completion event riding, i.e. kernels launched one by one) the
+    // conversion goes to the slot's side stream behind an event that rides on the unsharp, the chain's stream goes on with the next frame, and `done` —
+    // which the download, the slot's reuse and drain_frames wait for — rides on the conversion's last dispatch.
+    const int fmt = frame_wants_format(c);
+    const bool side = fmt == POPPY_FRAME_PAL8 && chained && done && !tm;
+    launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s,
+                   side ? f.bgr_done : fmt != POPPY_FRAME_BGR ? nullptr : done, c->levels[0].pitch);
     rec(POPPY_PYR_UNSHARP, 0, W < 2 || H < 2);
     if (tm) tm->mark("unsharp");
-    if (i420) {
+    if (fmt == POPPY_FRAME_I420) {
         launch_bgr_to_i420(f.out, f.i420, W, H, s, done);
         if (tm) tm->mark("frame_format");
+    } else if (fmt == POPPY_FRAME_PAL8) {
+        hipStream_t fs = side ? f.fmt_stream : s;
+        if (side) HIPCHK(c, hipStreamWaitEvent(fs, f.bgr_done, 0));
+        launch_pal8_hist(f.out, f.pal8_tables, W, H, fs);
+        if (tm) tm->mark("pal8_hist");
+        launch_pal8_build(f.pal8_tables, f.pal8, W, H, fs);
+        if (tm) tm->mark("pal8_build");
+        launch_pal8_remap(f.out, f.pal8_tables, f.pal8, W, H, fs, done);
+        if (tm) tm->mark("frame_format");                      // (under PAL8: the index plane alone)
     }
+    return POPPY_OK;
 }
 
 static int capture_body(poppy_hip_ctx* c, FrameSlot& f) {
     hipGraph_t g = nullptr;
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    enqueue_body(c, f, c->stream, nullptr, 0.f, false);
-    f.body_i420 = frame_wants_i420(c);
+    (void)enqueue_body(c, f, c->stream, nullptr, 0.f, false);
+    f.body_format = frame_wants_format(c);
     HIPCHK(c, hipStreamEndCapture(c->stream, &g));
     hipError_t e = hipGraphInstantiate(&f.body, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
@@ -874,7 +941,7 @@ static int prepare_slot(poppy_hip_ctx* c, const FramePlan& plan, double mask, bo
     // bottleneck.  On the chained critical path a graph launch leaves the GPU idle ~8 us longer than the same kernels
     // launched one by one (4600 vs 4785 frames/s, profiles/r01_e_streams.md), and the host keeps up easily.
     const bool use_graph = !no_graph && !chained && !c->debug && !all_marks && W > 1 && H > 1;
-    if (use_graph && f.body && f.body_i420 != frame_wants_i420(c)) {          // the body has (not) the conversion the frame needs: captured again
+    if (use_graph && f.body && f.body_format != frame_wants_format(c)) {          // the body has (not) the conversion the frame needs: captured again
         HIPCHK(c, hipEventSynchronize(f.done));                                // (the slot's last frame may still run it)
         (void)hipGraphExecDestroy(f.body); f.body = nullptr;
     }
@@ -981,7 +1048,7 @@ static int render_slot(poppy_hip_ctx* c, int fi, bool chain) {
     static const bool done_packet = getenv("POPPY_HIP_DONE_PACKET") != nullptr;
     const bool done_rides = !use_graph && !all_marks && !done_packet;
     if (use_graph) HIPCHK(c, hipGraphLaunch(f.body, s));
-    else enqueue_body(c, f, s, all_marks ? &tm : nullptr, (float)(1.0 - amount), c->debug, done_rides ? f.done : nullptr);
+    else { int rc = enqueue_body(c, f, s, all_marks ? &tm : nullptr, (float)(1.0 - amount), c->debug, done_rides ? f.done : nullptr, chained); if (rc) return rc; }
     HIPCHK(c, hipGetLastError());
     if (!done_rides) HIPCHK(c, hipEventRecord(f.done, s));
     c->last_slot = fi;
@@ -1018,12 +1085,15 @@ static int prepare_ahead(poppy_hip_ctx* c, const FramePlan& plan, double mask) {
 }
 
 int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride) {
-    if (c->frame_format != POPPY_FRAME_I420) {
+    if (c->frame_format == POPPY_FRAME_BGR) {
         host.resize((size_t)W * H * 3);
         *stride = (size_t)W * 3;
         HIPCHK(c, hipMemcpyAsync(host.data(), d_bgr, host.size(), hipMemcpyDeviceToHost, c->stream));
     } else {
-        const size_t bytes = poppy_frame_bytes(POPPY_FRAME_I420, W, H);
+        const bool pal8 = c->frame_format == POPPY_FRAME_PAL8;
+        if (pal8 && !pal8_fits(W, H)) return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8 takes frames of at most 2^24 pixels");
+        if (pal8 && !c->pal8_scratch_tables) { int rc = alloc_pal8_tables(c, &c->pal8_scratch_tables); if (rc) return rc; }
+        const size_t bytes = poppy_frame_bytes(c->frame_format, W, H);
         if (bytes + 16 > c->i420_scratch_bytes) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (c->i420_scratch) (void)hipFree(c->i420_scratch);
@@ -1033,7 +1103,11 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::ve
         }
         host.resize(bytes);
         *stride = (size_t)W;
-        launch_bgr_to_i420(d_bgr, c->i420_scratch, W, H, c->stream);
+        if (pal8) {
+            launch_pal8_hist(d_bgr, c->pal8_scratch_tables, W, H, c->stream);
+            launch_pal8_build(c->pal8_scratch_tables, c->i420_scratch, W, H, c->stream);
+            launch_pal8_remap(d_bgr, c->pal8_scratch_tables, c->i420_scratch, W, H, c->stream);
+        } else launch_bgr_to_i420(d_bgr, c->i420_scratch, W, H, c->stream);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(host.data(), c->i420_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
     }
@@ -1041,11 +1115,13 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::ve
     return POPPY_OK;
 }
 
-const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride) {
+const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status) {
     *out_stride = stride;
-    if (c->frame_format != POPPY_FRAME_I420) return bgr;
-    tmp.resize(poppy_frame_bytes(POPPY_FRAME_I420, W, H));
-    (void)poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
+    *status = POPPY_OK;
+    if (c->frame_format == POPPY_FRAME_BGR) return bgr;
+    tmp.resize(poppy_frame_bytes(c->frame_format, W, H));
+    const int rc = c->frame_format == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
+    if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
     *out_stride = (size_t)W;
     return tmp.data();
 }
@@ -1163,7 +1239,7 @@ int poppy_hip_morph_frames(poppy_hip_ctx* c, double phase, poppy_write_cb write,
     if (phase == 0 || phase == 1) {                            // src/poppy.hpp:54-70: N copies of image 1 / image 2, nothing rendered
         if (!write) return POPPY_OK;
         const uint8_t* img = phase == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2);
-        if (c->frame_format == POPPY_FRAME_I420) {
+        if (c->frame_format != POPPY_FRAME_BGR) {
             std::vector<uint8_t> host; size_t stride = 0;
             int rc = download_frame(c, img, c->W, c->H, host, &stride); if (rc) return rc;
             for (int j = 0; j < N; ++j) write(user, host.data(), c->W, c->H, stride);
@@ -1188,7 +1264,7 @@ int poppy_hip_render_phases(poppy_hip_ctx* c, const double* t, int n, poppy_writ
     const size_t row = (size_t)c->W * 3;
     for (int i = 0; i < n;) {
         if (t[i] == 0 || t[i] == 1) {                             // a plain copy of image 1 / image 2
-            if (write && c->frame_format == POPPY_FRAME_I420) {
+            if (write && c->frame_format != POPPY_FRAME_BGR) {
                 std::vector<uint8_t> host; size_t stride = 0;
                 int rc = download_frame(c, t[i] == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2), c->W, c->H, host, &stride); if (rc) return rc;
                 write(user, host.data(), c->W, c->H, stride);
@@ -1239,7 +1315,9 @@ int poppy_hip_morph(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint
     if (phase == 0 || phase == 1) {                            // src/poppy.hpp:54-70, before any feature work (I420: converted on the host, no GPU touched)
         std::vector<uint8_t> tmp;
         size_t stride = phase == 0 ? s1 : s2;
-        const uint8_t* img = (write && N > 0) ? host_frame(c, phase == 0 ? bgr1 : bgr2, stride, W, H, tmp, &stride) : nullptr;
+        int frame_rc = POPPY_OK;
+        const uint8_t* img = (write && N > 0) ? host_frame(c, phase == 0 ? bgr1 : bgr2, stride, W, H, tmp, &stride, &frame_rc) : nullptr;
+        if (write && N > 0 && !img) return frame_rc;
         for (int j = 0; j < N && write; ++j) write(user, img, W, H, stride);
         return POPPY_OK;
     }
@@ -1249,7 +1327,7 @@ int poppy_hip_morph(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint
             std::vector<uint8_t> blend((size_t)W * 3 * H);
             rc = poppy_hip_dissolve(c, bgr1, s1, bgr2, s2, W, H, phase, blend.data(), (size_t)W * 3); if (rc) return rc;
             size_t stride = (size_t)W * 3;
-            if (c->frame_format == POPPY_FRAME_I420) { rc = download_frame(c, c->slots[0].out, W, H, blend, &stride); if (rc) return rc; }      // the blend, still in slot 0
+            if (c->frame_format != POPPY_FRAME_BGR) { rc = download_frame(c, c->slots[0].out, W, H, blend, &stride); if (rc) return rc; }      // the blend, still in slot 0
             for (int j = 0; j < N; ++j) write(user, blend.data(), W, H, stride);
         }
         return fail(c, POPPY_E_NOMATCH, "no point pairs: linear-blend fallback frames written (src/poppy.hpp:125-134)");
@@ -1378,11 +1456,12 @@ int poppy_hip_timing_summary(poppy_hip_ctx* c, const char** names, float* total_
 
 int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
     if (!c) return POPPY_E_ARG;
-    if (format != POPPY_FRAME_BGR && format != POPPY_FRAME_I420) return fail(c, POPPY_E_ARG, "unknown frame format");
+    if (format != POPPY_FRAME_BGR && format != POPPY_FRAME_I420 && format != POPPY_FRAME_PAL8) return fail(c, POPPY_E_ARG, "unknown frame format");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = drain_frames(c); if (rc) return rc; }
+    if (format == POPPY_FRAME_PAL8 && c->c1 && !pal8_fits(c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8 takes frames of at most 2^24 pixels");
     c->frame_format = format;
-    return (format == POPPY_FRAME_I420 && c->c1) ? alloc_slot_i420(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
+    return c->c1 ? alloc_slot_format(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
 }
 
 int poppy_hip_render_many(poppy_hip_ctx* c, const double* shape, const double* mask, int n, int chain, poppy_write_cb write, void* user) {

@@ -1,5 +1,5 @@
-"""BGR against I420 frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run times
-each row once per format, one format right after the other, and the rows report min / median / max over --runs runs.
+"""BGR against I420 against PAL8 frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run
+times each row once per format, one format right after the other, and the rows report min / median / max over --runs runs.
 
   pool_1080p    bench.py's `value` set-up: a pool of --contexts contexts, --steps queued batches of six 1080p pairs from device images, 60 chained
                 frames per pair to the library's counting writer (pinned host copies)
@@ -7,7 +7,8 @@ each row once per format, one format right after the other, and the rows report 
   job480        ONE 480-frame 1080p phase-mode job on one context: pair set-up from device images + poppy_hip_render_phases to the counting writer
   chained       one context, pair after pair: pair set-up + 60 chained frames to the counting writer
   chained_frame one context, the 60 chained frames of a resident pair to the counting writer (what the extra launch costs a chained frame)
-  d2h_ceiling   pinned device-to-host copies of one frame's bytes, back to back on one stream (BGR and I420 sizes at 1080p and 4K)
+  d2h_ceiling   pinned device-to-host copies of one frame's bytes, back to back on one stream (BGR, I420 and PAL8 sizes at 1080p and 4K)
+and, at the end, the conversion kernels' own times in timing mode 1 at 1080p and 4K (I420: frame_format; PAL8: pal8_hist, pal8_build, frame_format = the index plane).
 
     python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6]
 One JSON line at the end.
@@ -24,7 +25,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poppy_amd import capi, synth  # noqa: E402
 
-FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420))
+FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420), ("pal8", capi.FRAME_PAL8))
 
 
 def pair_images(torch, dev, w, h, n):
@@ -121,18 +122,21 @@ def main():
         print(f"run {run}: " + ", ".join(f"{r} {f} {v[f][-1]:.0f}" for r, v in res.items() for f in v), flush=True)
     out = {"unit": "frames/s", "rows": {r: {f: summary(v) for f, v in fv.items()} for r, fv in res.items()}}
     for r, fv in res.items():
-        out["rows"][r]["i420_over_bgr_median"] = round(statistics.median(fv["i420"]) / statistics.median(fv["bgr"]), 3)
+        for f in ("i420", "pal8"):
+            out["rows"][r][f + "_over_bgr_median"] = round(statistics.median(fv[f]) / statistics.median(fv["bgr"]), 3)
     if "d2h_ceiling" in rows:
         out["d2h_ceiling"] = {f"{w}x{h}_{f}": d2h(torch, dev, capi.frame_bytes(fmt, w, h)) for w, h in ((1920, 1080), (3840, 2160)) for f, fmt in FMTS}
-    # the conversion kernel in timing mode 1 (events around it; a chained frame): per-launch time
-    ctx.set_frame_format(capi.FRAME_I420)
-    ctx.pair_begin_device(ta.data_ptr(), tb.data_ptr(), W, H)
-    ctx.set_timing(1)
-    ctx.reset(); ctx.render_many_counted(shapes, chain=True)
-    t = {n: (ms, k) for n, ms, k in ctx.timing_summary()}
-    ctx.set_timing(0)
-    if "frame_format" in t:
-        out["timing_mode1_us"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items()}
+    # the conversion kernels in timing mode 1 (events around every kernel of a chained frame): time per launch
+    out["timing_mode1_us"] = {}
+    for (w, h), (x, y) in (((W, H), (ta, tb)),) + ((((3840, 2160), p4k[0]),) if p4k else ()):
+        for name, fmt in FMTS[1:]:
+            ctx.set_frame_format(fmt)
+            ctx.pair_begin_device(x.data_ptr(), y.data_ptr(), w, h)
+            ctx.set_timing(1)
+            ctx.reset(); ctx.render_many_counted(shapes, chain=True)
+            t = {n: (ms, k) for n, ms, k in ctx.timing_summary()}
+            ctx.set_timing(0)
+            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_format", "pal8_hist", "pal8_build")}
     for p in (pool, pool4):
         if p:
             p.close()
