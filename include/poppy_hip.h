@@ -160,13 +160,40 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  *   4. Indices.  A pixel's index is the box that holds its cell (a table look-up, NOT a nearest-colour search), so every channel of
  *      palette[index] is within 8 * (the box's side) of the pixel, and a frame with at most 256 occupied cells and one colour per cell
  *      comes back exactly.
- * poppy_bgr_to_pal8 is the host statement of all this (dst: poppy_frame_bytes(POPPY_FRAME_PAL8, width, height) bytes).  */
+ * poppy_bgr_to_pal8 is the host statement of all this (dst: poppy_frame_bytes(POPPY_FRAME_PAL8, width, height) bytes).
+ *
+ * POPPY_FRAME_PAL8_SEQ: PAL8 frames with ONE palette for the whole sequence, so that flat regions of an animation do not shimmer from frame
+ * to frame and a GIF can carry a single global colour table (POPPY_SINK_GIF_GLOBAL).  Its value is 16, and POPPY_SINK_GIF_GLOBAL is 16, for
+ * the reason PAL8 is 8: 2, 4, 7 and 9 are tested as unknown frame formats and 4 - 7 and 9 as unknown sinks, so both enums go on with 16.
+ * A frame has PAL8's layout and size (width * height index bytes, then 768 palette bytes; the writer gets stride = width), every PAL8
+ * writer takes it unchanged, and all frames of one sequence carry the same 768 palette bytes.
+ *   The rule is steps 1 - 4 above with one change: step 1's histogram is taken over all pixels of ALL frames of the sequence.  Counts and
+ *      sums are 64-bit; cuts, tie rules, the (count + 1) / 2 position, shrinking, colours and the table look-up are word for word the
+ *      same.  A sequence of one frame therefore gives exactly that frame's PAL8 bytes, and a sequence of n frames gives what PAL8 gives for
+ *      the n frames stacked into one width x (n * height) image, cut into n pieces again.
+ *   A sequence is the set of frames that one call hands to its writer: one call of poppy_hip_morph (its phase 0 / 1 copies and its
+ *      POPPY_E_NOMATCH blend frames included), poppy_hip_morph_frames, poppy_hip_render_many or poppy_hip_render_phases; in
+ *      poppy_hip_morph_list, poppy_hip_pool_morph_pairs and poppy_hip_pool_submit_pairs EACH PAIR is one sequence.  The format applies
+ *      wherever PAL8 applies and stays BGR wherever PAL8 stays BGR.
+ *   Hand-over: the palette is known only after the last frame, so the writer is first called when every frame of the sequence has been
+ *      rendered, and then for every frame in order.  Until then the frames wait in device memory, 3 * width * height bytes each, in a buffer
+ *      that the context keeps between sequences and grows when needed (an allocation failure is POPPY_E_DEVICE).  If a frame fails to
+ *      render, NOTHING of that sequence is written and the call returns the status.
+ *   Limits, checked before a frame is rendered or any state changes: a frame has at most POPPY_PAL8_MAX_PIXELS pixels, as under PAL8, and
+ *      a sequence has fewer than POPPY_PAL8_SEQ_MAX_PIXELS = 2^32 pixels in all (n_frames * width * height: 2071 frames at 1080p, 517 at
+ *      4K), because the device's 3-D prefix sums of the counts are 32-bit words (33^3 of them fill 140 KiB of a compute unit's 160 KiB of
+ *      LDS; 64-bit words would not fit).  Both refusals are POPPY_E_UNSUPPORTED.
+ * poppy_bgr_frames_to_pal8 is the host statement: n_frames BGR frames, frame k at bgr + k * frame_stride with rows `stride` bytes apart,
+ * become n_frames PAL8_SEQ frames back to back in dst (n_frames * poppy_frame_bytes(POPPY_FRAME_PAL8_SEQ, width, height) bytes).  Its
+ * refusals are poppy_bgr_to_pal8's, plus n_frames < 1 (POPPY_E_ARG) and the sequence limit; nothing is read or written before them.  */
 #define POPPY_PAL8_MAX_PIXELS (1 << 24)
-enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8 };
+#define POPPY_PAL8_SEQ_MAX_PIXELS (1ull << 32)
+enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 int poppy_bgr_to_pal8(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_bgr_frames_to_pal8(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst);
 /* phase == 0 / phase == 1 follow the reference's short-circuit (src/poppy.hpp:54-70): number_of_frames copies of image 1 /
  * image 2 as they were handed to the pair set-up (with auto-align: the UNALIGNED image 2), no frame is rendered.            */
 
@@ -494,11 +521,15 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * table, a NETSCAPE2.0 block that loops forever, and per frame a graphic control extension (delay = fps_den * 100 / fps_num rounded to the
  * nearest centisecond, at least 1), an image descriptor with the frame's palette as a 256-entry local colour table and LZW data (minimum
  * code size 8).  No frame differencing, no transparency.
+ * GIF_GLOBAL: as GIF, for POPPY_FRAME_PAL8_SEQ frames: the first frame's palette is written as a 256-entry GLOBAL colour table (logical
+ * screen flags 0xF7), a frame whose palette equals it gets an image descriptor without a local table (flags 0x00), and a frame whose
+ * palette differs gets its own local table as under GIF (0x87) — so PAL8 frames and the frames of several pairs are taken too and decode
+ * to the pixels the GIF sink's file decodes to.  The header goes out with the first frame, which names the table.
  * The BGR sinks take frames with stride >= 3 * width, the I420 and GIF sinks frames with stride == width: a frame of another format fails the
  * sink where its stride tells (a BGR frame at the I420 or GIF sink, an I420 or PAL8 frame at a BGR sink); a writer must match the context's format.
  * poppy_sink_close returns the number of frames written, or a negative status if a write failed or a frame had another geometry.   */
 typedef struct poppy_sink poppy_sink;
-enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8 };
+enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8, POPPY_SINK_GIF_GLOBAL = 16 };
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den);
 void poppy_sink_write(void* sink, const uint8_t* bgr, int width, int height, size_t stride);
 int poppy_sink_close(poppy_sink* sink);

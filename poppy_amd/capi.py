@@ -25,8 +25,8 @@ WARP_KERNELS = ("k_warp_bin", "k_warp_tile", "k_warp4")        # order of poppy_
 PYRAMID_FORMS = ("down", "down2", "tail", "tail_nl", "mix_top", "cone", "up2", "up", "unsharp")
 WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_size_t)
 # formats of the frames handed to writers (poppy_hip_set_frame_format) and the file sinks (poppy_sink_open)
-FRAME_BGR, FRAME_I420, FRAME_PAL8 = 0, 1, 8
-SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF = 0, 1, 2, 3, 8
+FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ = 0, 1, 8, 16
+SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL = 0, 1, 2, 3, 8, 16
 
 # every symbol include/poppy_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -44,7 +44,7 @@ SYMBOLS = [
     "poppy_hip_orb_detect", "poppy_hip_foreground", "poppy_hip_median_blur", "poppy_match_points", "poppy_hip_pair_begin_prefiltered", "poppy_hip_pair_begin", "poppy_hip_pair_begin_info", "poppy_hip_orb_input", "poppy_hip_gabor_field", "poppy_hip_set_gabor_direct", "poppy_hip_set_setup_chains", "poppy_hip_gabor_doubt", "poppy_radial_gradient", "poppy_radial_mask", "poppy_gabor_tables", "poppy_pyr_tail_plan", "poppy_hip_blur_margin", "poppy_hip_pair_points",
     "poppy_hip_pair_begin_next", "poppy_hip_pair_begin_next_device", "poppy_hip_chain_counts", "poppy_hip_morph_list",
     "poppy_hip_last_pyramid_forms",
-    "poppy_hip_set_frame_format", "poppy_hip_pool_set_frame_format", "poppy_frame_bytes", "poppy_bgr_to_i420", "poppy_bgr_to_pal8",
+    "poppy_hip_set_frame_format", "poppy_hip_pool_set_frame_format", "poppy_frame_bytes", "poppy_bgr_to_i420", "poppy_bgr_to_pal8", "poppy_bgr_frames_to_pal8",
 ]
 
 
@@ -166,6 +166,7 @@ def lib():
         L.poppy_frame_bytes.argtypes = [i, i, i]
         L.poppy_bgr_to_i420.argtypes = [vp, sz, i, i, vp]
         L.poppy_bgr_to_pal8.argtypes = [vp, sz, i, i, vp]
+        L.poppy_bgr_frames_to_pal8.argtypes = [vp, sz, sz, i, i, i, vp]
         L.poppy_hypotf_selfcheck.restype = C.c_long
         L.poppy_hypotf_selfcheck.argtypes = [C.c_long, C.c_uint64]
         _lib = L
@@ -177,7 +178,7 @@ def _p(a):
 
 
 def frame_bytes(fmt, w, h):
-    """Host-only: bytes of a w x h frame in format fmt (FRAME_BGR / FRAME_I420 / FRAME_PAL8; 0 for anything else)."""
+    """Host-only: bytes of a w x h frame in format fmt (FRAME_BGR / FRAME_I420 / FRAME_PAL8 / FRAME_PAL8_SEQ; 0 for anything else)."""
     return int(lib().poppy_frame_bytes(int(fmt), int(w), int(h)))
 
 
@@ -209,6 +210,25 @@ def bgr_to_pal8(bgr, row_pad=0):
     return out
 
 
+def bgr_frames_to_pal8(frames, row_pad=0, frame_pad=0):
+    """Host-only: the library's PAL8_SEQ frames of a sequence of n HxWx3 BGR frames (poppy_bgr_frames_to_pal8): an n x frame_bytes(FRAME_PAL8_SEQ, W, H)
+    uint8 array, every row W * H index bytes and the sequence's one palette.  row_pad / frame_pad: the frames are handed over with that many extra
+    bytes per row / between frames."""
+    a = np.ascontiguousarray(frames, np.uint8)
+    n, h, w = a.shape[:3]
+    stride = w * 3 + int(row_pad)
+    frame_stride = stride * h + int(frame_pad)
+    if row_pad or frame_pad:
+        buf = np.full((n, frame_stride), 0xA5, np.uint8)
+        buf[:, :stride * h].reshape(n, h, stride)[:, :, :w * 3] = a.reshape(n, h, w * 3)
+        a = buf
+    out = np.empty((n, frame_bytes(FRAME_PAL8_SEQ, w, h)), np.uint8)
+    rc = lib().poppy_bgr_frames_to_pal8(_p(a), stride, frame_stride, n, w, h, _p(out))
+    if rc:
+        raise PoppyError(f"poppy_bgr_frames_to_pal8: {rc}")
+    return out
+
+
 def pal8_to_bgr(frame, w, h):
     """palette[index] of a flat PAL8 frame, as an HxWx3 BGR array (what a viewer of the frame sees)."""
     f = np.asarray(frame, np.uint8)
@@ -216,8 +236,8 @@ def pal8_to_bgr(frame, w, h):
 
 
 def _frame_view(ptr, w, h, stride, fmt):
-    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420 and PAL8.  A view: valid during the callback."""
-    if fmt in (FRAME_I420, FRAME_PAL8):
+    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ.  A view: valid during the callback."""
+    if fmt in (FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ):
         return np.ctypeslib.as_array(ptr, shape=(frame_bytes(fmt, w, h),))
     return np.ctypeslib.as_array(ptr, shape=(h, stride))[:, :w * 3].reshape(h, w, 3)
 
@@ -461,7 +481,7 @@ class Pool:
         self.frame_format = FRAME_BGR
 
     def set_frame_format(self, fmt):
-        """FRAME_BGR, FRAME_I420 or FRAME_PAL8 for every context of the pool (poppy_hip_pool_set_frame_format); PoppyError with the status while submitted
+        """FRAME_BGR, FRAME_I420, FRAME_PAL8 or FRAME_PAL8_SEQ (one palette per pair) for every context of the pool (poppy_hip_pool_set_frame_format); PoppyError with the status while submitted
         batches have not been waited for."""
         rc = lib().poppy_hip_pool_set_frame_format(self.h, int(fmt))
         if rc:
@@ -609,8 +629,8 @@ class Context:
         self.frame_format = FRAME_BGR
 
     def set_frame_format(self, fmt):
-        """FRAME_BGR (default), FRAME_I420 or FRAME_PAL8: the format of every frame handed to a writer (poppy_hip_set_frame_format).  Under I420 and
-        PAL8 the collecting wrappers return flat uint8 arrays of frame_bytes(format, W, H)."""
+        """FRAME_BGR (default), FRAME_I420, FRAME_PAL8 or FRAME_PAL8_SEQ (one palette for all frames of a call, which are handed over when the last
+        one is rendered): the format of every frame handed to a writer (poppy_hip_set_frame_format).  Under I420 and both PAL8 formats the collecting wrappers return flat uint8 arrays of frame_bytes(format, W, H)."""
         self._chk(lib().poppy_hip_set_frame_format(self.h, int(fmt)), "set_frame_format")
         self.frame_format = int(fmt)
 

@@ -7,11 +7,13 @@
 //                    re-encode it; the conversion is this file's, not the reference's)
 //   POPPY_SINK_Y4M420  one YUV4MPEG2 file, C420jpeg, that takes I420 frames as they are (poppy_hip_set_frame_format)
 //   POPPY_SINK_GIF   one animated GIF89a file that takes PAL8 frames as they are: a local colour table and one LZW image per frame
+//   POPPY_SINK_GIF_GLOBAL  the same for PAL8_SEQ frames: the first frame's palette as the global colour table, local tables only where a frame's palette differs
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "../../include/poppy_hip.h"
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -24,6 +26,8 @@ struct poppy_sink {
     FILE* f = nullptr;
     std::vector<uint8_t> row;
     int delay_cs = 3;                  // GIF: the frames' delay in centiseconds
+    bool head_written = false;         // GIF_GLOBAL: the header waits for the first frame's palette
+    uint8_t global_pal[768];           // ... which is the global colour table
 };
 
 namespace {
@@ -75,13 +79,27 @@ struct GifLzw {
     }
 };
 
+// header, logical screen (with `global` as its 256-entry colour table, or without one), the NETSCAPE2.0 application block: loop for ever
+bool gif_head(poppy_sink* s, const uint8_t* global) {
+    const int width = s->w, height = s->h;
+    const uint8_t head[13] = {'G', 'I', 'F', '8', '9', 'a', (uint8_t)(width & 255), (uint8_t)(width >> 8), (uint8_t)(height & 255), (uint8_t)(height >> 8), (uint8_t)(global ? 0xF7 : 0x70), 0, 0};
+    const uint8_t loop[19] = {0x21, 0xFF, 11, 'N', 'E', 'T', 'S', 'C', 'A', 'P', 'E', '2', '.', '0', 3, 1, 0, 0, 0};
+    s->head_written = true;
+    return fwrite(head, 1, 13, s->f) == 13 && (!global || fwrite(global, 1, 768, s->f) == 768) && fwrite(loop, 1, 19, s->f) == 19;
+}
+
 bool gif_frame(poppy_sink* s, const uint8_t* pal8) {
     const int w = s->w, h = s->h;
     const size_t n = (size_t)w * h;
+    bool local = true;
+    if (s->format == POPPY_SINK_GIF_GLOBAL) {
+        if (!s->head_written) { memcpy(s->global_pal, pal8 + n, 768); if (!gif_head(s, s->global_pal)) return false; }
+        local = memcmp(s->global_pal, pal8 + n, 768) != 0;
+    }
     const uint8_t gce[8] = {0x21, 0xF9, 4, 0, (uint8_t)(s->delay_cs & 255), (uint8_t)(s->delay_cs >> 8), 0, 0};
-    const uint8_t desc[10] = {0x2C, 0, 0, 0, 0, (uint8_t)(w & 255), (uint8_t)(w >> 8), (uint8_t)(h & 255), (uint8_t)(h >> 8), 0x87};      // local table, 256 entries
+    const uint8_t desc[10] = {0x2C, 0, 0, 0, 0, (uint8_t)(w & 255), (uint8_t)(w >> 8), (uint8_t)(h & 255), (uint8_t)(h >> 8), (uint8_t)(local ? 0x87 : 0x00)};      // local table, 256 entries, or none
     const uint8_t min_code = 8;
-    if (fwrite(gce, 1, 8, s->f) != 8 || fwrite(desc, 1, 10, s->f) != 10 || fwrite(pal8 + n, 1, 768, s->f) != 768 || fwrite(&min_code, 1, 1, s->f) != 1) return false;
+    if (fwrite(gce, 1, 8, s->f) != 8 || fwrite(desc, 1, 10, s->f) != 10 || (local && fwrite(pal8 + n, 1, 768, s->f) != 768) || fwrite(&min_code, 1, 1, s->f) != 1) return false;
     GifLzw z(s->f);
     z.encode(pal8, n);
     return z.ok;
@@ -96,7 +114,7 @@ size_t poppy_frame_bytes(int format, int width, int height) {
     const size_t w = (size_t)width, h = (size_t)height;
     if (format == POPPY_FRAME_BGR) return w * h * 3;
     if (format == POPPY_FRAME_I420) return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2);
-    if (format == POPPY_FRAME_PAL8) return w * h + 768;
+    if (format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ) return w * h + 768;
     return 0;
 }
 
@@ -129,7 +147,7 @@ int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, 
 }
 
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den) {
-    if (!path || width <= 0 || height <= 0 || (format != POPPY_SINK_GIF && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
+    if (!path || width <= 0 || height <= 0 || (format != POPPY_SINK_GIF && format != POPPY_SINK_GIF_GLOBAL && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
     poppy_sink* s = new poppy_sink();
     s->format = format; s->w = width; s->h = height; s->path = path;
     if (format == POPPY_SINK_PPM) {
@@ -153,7 +171,7 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
         if (bad || !seen) { delete s; return nullptr; }
         s->path = head; s->tail = tail;
     }
-    if (format == POPPY_SINK_GIF && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen: every write fails, close says so
+    if ((format == POPPY_SINK_GIF || format == POPPY_SINK_GIF_GLOBAL) && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen: every write fails, close says so
     if (format != POPPY_SINK_PPM) {
         s->f = fopen(path, "wb");
         if (!s->f) { delete s; return nullptr; }
@@ -161,14 +179,11 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
             fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C444 XCOLORRANGE=FULL\n", width, height, fps_num > 0 ? fps_num : 30, fps_den > 0 ? fps_den : 1);
         else if (format == POPPY_SINK_Y4M420)
             fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=FULL\n", width, height, fps_num > 0 ? fps_num : 30, fps_den > 0 ? fps_den : 1);
-        else if (format == POPPY_SINK_GIF) {
+        else if (format == POPPY_SINK_GIF || format == POPPY_SINK_GIF_GLOBAL) {
             const long long num = fps_num > 0 ? fps_num : 30, den = fps_den > 0 ? fps_den : 1;
             const long long cs = (den * 100 + num / 2) / num;
             s->delay_cs = (int)(cs < 1 ? 1 : cs > 65535 ? 65535 : cs);
-            // header, logical screen without a global colour table, the NETSCAPE2.0 application block: loop for ever
-            const uint8_t head[13] = {'G', 'I', 'F', '8', '9', 'a', (uint8_t)(width & 255), (uint8_t)(width >> 8), (uint8_t)(height & 255), (uint8_t)(height >> 8), 0x70, 0, 0};
-            const uint8_t loop[19] = {0x21, 0xFF, 11, 'N', 'E', 'T', 'S', 'C', 'A', 'P', 'E', '2', '.', '0', 3, 1, 0, 0, 0};
-            if (fwrite(head, 1, 13, s->f) != 13 || fwrite(loop, 1, 19, s->f) != 19) s->failed = true;
+            if (format == POPPY_SINK_GIF && !gif_head(s, nullptr)) s->failed = true;      // (GIF_GLOBAL: with the first frame)
         }
     }
     s->row.resize((size_t)width * 3);
@@ -179,7 +194,7 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
     poppy_sink* s = (poppy_sink*)user;
     if (!s || s->failed) return;
     // (an I420 frame comes with stride == width: the BGR sinks refuse it, and the I420 sink refuses anything else)
-    const bool i420 = s->format == POPPY_SINK_Y4M420, pal8 = s->format == POPPY_SINK_GIF;
+    const bool i420 = s->format == POPPY_SINK_Y4M420, pal8 = s->format == POPPY_SINK_GIF || s->format == POPPY_SINK_GIF_GLOBAL;
     if (!bgr || width != s->w || height != s->h || ((i420 || pal8) ? stride != (size_t)width : stride < (size_t)width * 3)) { s->failed = true; return; }
     FILE* f = s->f;
     if (pal8) {
@@ -232,7 +247,8 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
 
 int poppy_sink_close(poppy_sink* s) {
     if (!s) return POPPY_E_ARG;
-    if (s->f && s->format == POPPY_SINK_GIF && !s->failed && fputc(0x3B, s->f) == EOF) s->failed = true;      // the trailer
+    if (s->f && s->format == POPPY_SINK_GIF_GLOBAL && !s->failed && !s->head_written && !gif_head(s, nullptr)) s->failed = true;      // no frame came: GIF's empty file
+    if (s->f && (s->format == POPPY_SINK_GIF || s->format == POPPY_SINK_GIF_GLOBAL) && !s->failed && fputc(0x3B, s->f) == EOF) s->failed = true;      // the trailer
     const int n = s->failed ? POPPY_E_DEVICE : s->frames;
     if (s->f) fclose(s->f);
     delete s;

@@ -97,8 +97,8 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
             const ListImage& img = phase == 0 ? a : b;
             std::vector<uint8_t> host; size_t stride = 0;
             const uint8_t* frame = nullptr;
-            if (img.dev) { rc = download_frame(c, img.p, W, H, host, &stride); if (rc) return rc; frame = host.data(); }
-            else { frame = host_frame(c, img.p, img.stride, W, H, host, &stride, &rc); if (!frame) return rc; }
+            if (img.dev) { rc = download_frame(c, img.p, W, H, host, &stride, N); if (rc) return rc; frame = host.data(); }
+            else { frame = host_frame(c, img.p, img.stride, W, H, host, &stride, &rc, N); if (!frame) return rc; }
             PairWriter pw{write, user, 0, 0};
             for (int j = 0; j < N; ++j) pair_writer_cb(&pw, frame, W, H, stride);
         } else if (write) {
@@ -123,7 +123,7 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
                 HIPCHK(c, hipGetLastError());
                 std::vector<uint8_t> blend;
                 size_t stride = (size_t)W * 3;
-                if (c->frame_format != POPPY_FRAME_BGR) rc = download_frame(c, c->slots[0].out, W, H, blend, &stride);
+                if (c->frame_format != POPPY_FRAME_BGR) rc = download_frame(c, c->slots[0].out, W, H, blend, &stride, N);
                 else rc = list_download(c, c->slots[0].out, W, H, blend);
                 if (rc) return rc;
                 PairWriter pw{write, user, k, 0};

@@ -213,5 +213,13 @@ bool prepare_pal8();
 void launch_pal8_hist(const uint8_t* src, uint8_t* tables, int w, int h, hipStream_t s);
 void launch_pal8_build(uint8_t* tables, uint8_t* dst, int w, int h, hipStream_t s);
 void launch_pal8_remap(const uint8_t* src, const uint8_t* tables, uint8_t* dst, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
+// POPPY_FRAME_PAL8_SEQ: one palette per sequence.  `seq_tables`: kPal8SeqTableBytes, zero before a sequence's first frame (the build leaves the sums zero again): four
+// tables of 64-bit words per cell (count, sum R, sum G, sum B), the cell -> index table, the 768 palette bytes.  The pass adds one frame to the sums (any number of
+// passes may run beside each other) and stores it on to `store` (null: no copy); `done` (optional) rides on it.  The build (prepare_pal8 first) runs once, behind the
+// last pass; the remap writes a frame's w * h index bytes.
+constexpr size_t kPal8SeqTableOffset = (size_t)32768 * 32, kPal8SeqPaletteOffset = kPal8SeqTableOffset + 32768, kPal8SeqTableBytes = kPal8SeqPaletteOffset + 768;
+void launch_pal8_seq_pass(const uint8_t* src, uint8_t* store, uint8_t* seq_tables, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
+void launch_pal8_seq_build(uint8_t* seq_tables, hipStream_t s);
+void launch_pal8_seq_remap(const uint8_t* src, const uint8_t* seq_tables, uint8_t* dst, int w, int h, hipStream_t s);
 
 }  // namespace poppy_hip

@@ -15,10 +15,20 @@
 //                 wave reduction of the score and a ballot for its lowest index.  Then all 16 waves, a box each: the cell -> index table, the box's colour
 //                 sums and its palette entry.  The cells read are cleared on the way, so the tables are zero again for the slot's next frame.
 //   k_pal8_remap  index = table[cell], four pixels per thread, one 4-byte store.
+//
+// POPPY_FRAME_PAL8_SEQ (one palette for all frames of a sequence; poppy_bgr_frames_to_pal8 is its host statement) uses the same pieces around tables that live for a
+// whole sequence:
+//   k_pal8_seq_pass   per frame: k_pal8_hist's read and LDS stage (the packed words are safe inside one workgroup), but every occupied entry is flushed UNPACKED into
+//                     four 64-bit tables (count, sum R, sum G, sum B: packed fields would carry into each other when summed over frames), and the pixels just read
+//                     are stored on into the frame's place in the sequence store — the pass is the frame's only conversion work before the last frame.
+//   k_pal8_seq_build  once per sequence: k_pal8_build's code (pal8_build<true>) on those tables; counts go into the 32-bit prefix array (a sequence has fewer
+//                     than 2^32 pixels), scores (count * side, up to 2^37) and colour sums are 64-bit.
+//   k_pal8_remap      per frame, from the store.
 #include "kernels.h"
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 
 namespace poppy_hip {
 
@@ -86,6 +96,55 @@ __global__ void __launch_bounds__(256) k_pal8_hist(const uint8_t* __restrict__ s
     }
 }
 
+// tab: four tables of kCells 64-bit words (count, sum R, sum G, sum B).  store (may be null): where the frame's bytes go, as they are.
+__global__ void __launch_bounds__(256) k_pal8_seq_pass(const uint8_t* __restrict__ src, uint8_t* __restrict__ store, unsigned long long* __restrict__ tab, size_t n_px, int aligned) {
+    __shared__ int keys[kHistSlots];
+    __shared__ unsigned long long va[kHistSlots], vb[kHistSlots];
+    for (int i = threadIdx.x; i < kHistSlots; i += 256) { keys[i] = -1; va[i] = 0; vb[i] = 0; }
+    __syncthreads();
+    auto flush = [&](int cell, unsigned long long a, unsigned long long b) {
+        atomicAdd(&tab[cell], a >> 32); atomicAdd(&tab[kCells + cell], a & 0xffffffffull);
+        atomicAdd(&tab[2 * kCells + cell], b & 0xffffffffull); atomicAdd(&tab[3 * kCells + cell], b >> 32);
+    };
+    auto add = [&](int cell, unsigned long long a, unsigned long long b) {
+        unsigned h = ((unsigned)cell * 2654435761u) >> 21;           // 11 bits
+        for (int p = 0; p < kHistProbes; ++p) {
+            const int prev = atomicCAS(&keys[h], -1, cell);
+            if (prev == -1 || prev == cell) { atomicAdd(&va[h], a); atomicAdd(&vb[h], b); return; }
+            h = (h + 1) & (kHistSlots - 1);
+        }
+        flush(cell, a, b);
+    };
+    const size_t n_quads = (n_px + 3) / 4;
+    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < n_quads; q += (size_t)gridDim.x * 256) {
+        const int n = n_px - q * 4 >= 4 ? 4 : (int)(n_px - q * 4);
+        uint32_t w[3];
+        load_quad(src, q, n, aligned != 0, w);
+        if (store) {
+            if (aligned && n == 4) { uint32_t* o = (uint32_t*)(store + q * 12); o[0] = w[0]; o[1] = w[1]; o[2] = w[2]; }
+            else for (int i = 0; i < 3 * n; ++i) store[q * 12 + i] = (uint8_t)quad_byte(w, i);
+        }
+        int cur = -1;
+        unsigned long long a = 0, b = 0;
+        #pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < n) {
+                const int pb = quad_byte(w, 3 * k), pg = quad_byte(w, 3 * k + 1), pr = quad_byte(w, 3 * k + 2);
+                const int cell = cell_of(pb, pg, pr);
+                if (cell != cur) { if (cur >= 0) add(cur, a, b); cur = cell; a = 0; b = 0; }
+                a += (1ull << 32) | (unsigned long long)pr;
+                b += ((unsigned long long)pb << 32) | (unsigned long long)pg;
+            }
+        }
+        if (cur >= 0) add(cur, a, b);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kHistSlots; i += 256) {
+        const int cell = keys[i];
+        if (cell >= 0) flush(cell, va[i], vb[i]);
+    }
+}
+
 namespace {
 
 // The counts' inclusive prefix sums live in a 33^3 array whose planes r = -1, g = -1 and b = -1 are zero, so that a box's count is eight plain look-ups:
@@ -110,11 +169,12 @@ __device__ __forceinline__ Box3 unpack_box(uint32_t v) {
     x.r0 = v & 31; x.g0 = (v >> 5) & 31; x.b0 = (v >> 10) & 31; x.r1 = (v >> 15) & 31; x.g1 = (v >> 20) & 31; x.b1 = (v >> 25) & 31;
     return x;
 }
-// count * (longest side in cells), 0 for a box of one cell; at most 2^24 * 32
-__device__ __forceinline__ uint32_t box_score(uint32_t lh, uint32_t count) {
+// count * (longest side in cells), 0 for a box of one cell; at most 2^24 * 32 for a frame (Score = uint32_t), below 2^32 * 32 for a sequence (64-bit)
+template <typename Score>
+__device__ __forceinline__ Score box_score(uint32_t lh, uint32_t count) {
     const Box3 x = unpack_box(lh);
     const int side = max(max(x.r1 - x.r0, x.g1 - x.g0), x.b1 - x.b0) + 1;
-    return side < 2 ? 0u : count * (uint32_t)side;
+    return side < 2 ? (Score)0 : (Score)count * (Score)side;
 }
 
 // Wave 0, all 64 lanes.  Two boxes at once, lanes 0..31 on a and 32..63 on b, holding ca > 0 and cb > 0 pixels: both shrunk to the bounding boxes of
@@ -143,8 +203,14 @@ __device__ __forceinline__ void shrink_pair(const uint32_t* P, Box3& a, Box3& b,
 
 }  // namespace
 
-__global__ void __launch_bounds__(1024) k_pal8_build(unsigned long long* __restrict__ hist_a, unsigned long long* __restrict__ hist_b, uint8_t* __restrict__ table,
-                                                     uint8_t* __restrict__ palette) {
+// The palette build, for one frame (kSeq = false: hist_a / hist_b are k_pal8_hist's packed words) and for a sequence (kSeq = true: hist_a is k_pal8_seq_pass's four
+// unpacked tables, hist_b is not used).  The two differ in where a cell's count and sums are read and in the width of the scores and colour sums, nowhere else.
+namespace {
+template <bool kSeq>
+__device__ __forceinline__ void pal8_build(unsigned long long* __restrict__ hist_a, unsigned long long* __restrict__ hist_b, uint8_t* __restrict__ table,
+                                           uint8_t* __restrict__ palette) {
+    using Score = typename std::conditional<kSeq, unsigned long long, uint32_t>::type;
+    using Sum = Score;
     extern __shared__ uint32_t P[];                       // kPrefWords
     __shared__ uint32_t box_lh[256], box_cnt[256];
     __shared__ int n_boxes_s;
@@ -154,7 +220,7 @@ __global__ void __launch_bounds__(1024) k_pal8_build(unsigned long long* __restr
     // along B: 32 consecutive cells are one (r, g) row and one half of a wave
     for (int it = 0; it < 32; ++it) {
         const int cell = it * 1024 + t;
-        uint32_t v = (uint32_t)(hist_a[cell] >> 32);
+        uint32_t v = kSeq ? (uint32_t)hist_a[cell] : (uint32_t)(hist_a[cell] >> 32);
         #pragma unroll
         for (int d = 1; d < 32; d <<= 1) { const uint32_t u = __shfl_up(v, d, 32); if ((lane & 31) >= d) v += u; }
         P[((cell >> 10) + 1) * kPrefR + (((cell >> 5) & 31) + 1) * kPrefG + (cell & 31) + 1] = v;
@@ -175,10 +241,10 @@ __global__ void __launch_bounds__(1024) k_pal8_build(unsigned long long* __restr
         }
         while (n < 256) {
             // the best score at the lowest index (boxes that do not exist score 0)
-            const uint32_t s0 = box_score(lh0, cn0), s1 = box_score(lh1, cn1), s2 = box_score(lh2, cn2), s3 = box_score(lh3, cn3);
-            uint32_t m = max(max(s0, s1), max(s2, s3));
+            const Score s0 = box_score<Score>(lh0, cn0), s1 = box_score<Score>(lh1, cn1), s2 = box_score<Score>(lh2, cn2), s3 = box_score<Score>(lh3, cn3);
+            Score m = max(max(s0, s1), max(s2, s3));
             #pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor(m, d, 64));
+            for (int d = 32; d >= 1; d >>= 1) m = max(m, (Score)__shfl_xor(m, d, 64));
             if (m == 0) break;                                      // no box spans more than one cell
             int best;
             unsigned long long w;
@@ -197,7 +263,7 @@ __global__ void __launch_bounds__(1024) k_pal8_build(unsigned long long* __restr
             const int la = axis == 0 ? x.r0 : axis == 1 ? x.g0 : x.b0;
             const int pos = la + min(lane, ea);
             const uint32_t cum = box_count(P, x.r0, x.g0, x.b0, axis == 0 ? pos : x.r1, axis == 1 ? pos : x.g1, axis == 2 ? pos : x.b1);
-            const uint32_t half = (bcnt + 1) / 2;
+            const uint32_t half = (uint32_t)(((unsigned long long)bcnt + 1) / 2);      // (a sequence's count may be 2^32 - 1)
             const unsigned long long reach = __ballot(lane <= ea && cum >= half);      // never empty: the last position holds them all
             const int k = min(__ffsll(reach) - 1, ea - 1);
             const uint32_t cnt_lo = __shfl(cum, k, 64), cnt_hi = bcnt - cnt_lo;
@@ -223,16 +289,21 @@ __global__ void __launch_bounds__(1024) k_pal8_build(unsigned long long* __restr
     for (int i = t >> 6; i < n; i += 16) {
         const Box3 x = unpack_box(box_lh[i]);
         const int dg = x.g1 - x.g0 + 1, db = x.b1 - x.b0 + 1, vol = (x.r1 - x.r0 + 1) * dg * db;
-        uint32_t s0 = 0, s1 = 0, s2 = 0;
+        Sum s0 = 0, s1 = 0, s2 = 0;
         for (int v = lane; v < vol; v += 64) {
             const int b = v % db, g = (v / db) % dg, r = v / (db * dg);
             const int cell = ((x.r0 + r) << 10) | ((x.g0 + g) << 5) | (x.b0 + b);
             table[cell] = (uint8_t)i;
             const unsigned long long a = hist_a[cell];
             if (a) {
-                const unsigned long long gb = hist_b[cell];
-                s0 += (uint32_t)a; s1 += (uint32_t)gb; s2 += (uint32_t)(gb >> 32);
-                hist_a[cell] = 0; hist_b[cell] = 0;
+                if (kSeq) {
+                    s0 += (Sum)hist_a[kCells + cell]; s1 += (Sum)hist_a[2 * kCells + cell]; s2 += (Sum)hist_a[3 * kCells + cell];
+                    hist_a[cell] = 0; hist_a[kCells + cell] = 0; hist_a[2 * kCells + cell] = 0; hist_a[3 * kCells + cell] = 0;
+                } else {
+                    const unsigned long long gb = hist_b[cell];
+                    s0 += (uint32_t)a; s1 += (uint32_t)gb; s2 += (uint32_t)(gb >> 32);
+                    hist_a[cell] = 0; hist_b[cell] = 0;
+                }
             }
         }
         #pragma unroll
@@ -245,6 +316,16 @@ __global__ void __launch_bounds__(1024) k_pal8_build(unsigned long long* __restr
         }
     }
     for (int i = n * 3 + t; i < 768; i += 1024) palette[i] = 0;
+}
+}  // namespace
+
+__global__ void __launch_bounds__(1024) k_pal8_build(unsigned long long* __restrict__ hist_a, unsigned long long* __restrict__ hist_b, uint8_t* __restrict__ table,
+                                                     uint8_t* __restrict__ palette) {
+    pal8_build<false>(hist_a, hist_b, table, palette);
+}
+
+__global__ void __launch_bounds__(1024) k_pal8_seq_build(unsigned long long* __restrict__ tab, uint8_t* __restrict__ table, uint8_t* __restrict__ palette) {
+    pal8_build<true>(tab, nullptr, table, palette);
 }
 
 __global__ void __launch_bounds__(256) k_pal8_remap(const uint8_t* __restrict__ src, const uint8_t* __restrict__ table, uint8_t* __restrict__ dst, size_t n_px, int aligned) {
@@ -271,6 +352,7 @@ bool prepare_pal8() {
     std::lock_guard<std::mutex> lock(mu);
     if (granted[dev]) return true;
     if (hipFuncSetAttribute((const void*)k_pal8_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLds) != hipSuccess) return false;
+    if (hipFuncSetAttribute((const void*)k_pal8_seq_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLds) != hipSuccess) return false;
     granted[dev] = true;
     return true;
 }
@@ -291,6 +373,23 @@ void launch_pal8_remap(const uint8_t* src, const uint8_t* tables, uint8_t* dst, 
     const size_t n_px = (size_t)w * h, n_quads = (n_px + 3) / 4;
     const int aligned = (((uintptr_t)src | (uintptr_t)dst) & 3) == 0;
     hipExtLaunchKernelGGL(k_pal8_remap, dim3((unsigned)((n_quads + 255) / 256)), dim3(256), 0, s, nullptr, done, 0, src, tables + kPal8TableOffset, dst, n_px, aligned);
+}
+
+void launch_pal8_seq_pass(const uint8_t* src, uint8_t* store, uint8_t* seq_tables, int w, int h, hipStream_t s, hipEvent_t done) {
+    const size_t n_px = (size_t)w * h, n_quads = (n_px + 3) / 4;
+    const int blocks = (int)std::min<size_t>((n_quads + 255) / 256, 512);
+    const int aligned = (((uintptr_t)src | (uintptr_t)store) & 3) == 0;
+    hipExtLaunchKernelGGL(k_pal8_seq_pass, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, src, store, (unsigned long long*)seq_tables, n_px, aligned);
+}
+
+void launch_pal8_seq_build(uint8_t* seq_tables, hipStream_t s) {
+    hipLaunchKernelGGL(k_pal8_seq_build, dim3(1), dim3(1024), kBuildLds, s, (unsigned long long*)seq_tables, seq_tables + kPal8SeqTableOffset, seq_tables + kPal8SeqPaletteOffset);
+}
+
+void launch_pal8_seq_remap(const uint8_t* src, const uint8_t* seq_tables, uint8_t* dst, int w, int h, hipStream_t s) {
+    const size_t n_px = (size_t)w * h, n_quads = (n_px + 3) / 4;
+    const int aligned = (((uintptr_t)src | (uintptr_t)dst) & 3) == 0;
+    hipLaunchKernelGGL(k_pal8_remap, dim3((unsigned)((n_quads + 255) / 256)), dim3(256), 0, s, src, seq_tables + kPal8SeqTableOffset, dst, n_px, aligned);
 }
 
 }  // namespace poppy_hip

@@ -142,6 +142,7 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
     if (c->d_comm_scratch) (void)hipFree(c->d_comm_scratch);
     if (c->i420_scratch) (void)hipFree(c->i420_scratch);
     if (c->pal8_scratch_tables) (void)hipFree(c->pal8_scratch_tables);
+    for (uint8_t* b : {c->seq_tables, c->seq_store, c->seq_idx}) if (b) (void)hipFree(b);
     c->aligner.release();
     (void)hipStreamDestroy(c->copy_stream);
     (void)hipStreamDestroy(c->stream);
@@ -247,35 +248,58 @@ static int alloc_pal8_tables(poppy_hip_ctx* c, uint8_t** tables) {
 }
 
 static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H <= (unsigned long long)POPPY_PAL8_MAX_PIXELS; }
+static bool is_pal8(int format) { return format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ; }
+constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8 and POPPY_FRAME_PAL8_SEQ take frames of at most 2^24 pixels";
+
+// a slot's conversion side stream and the event that rides on its unsharp (PAL8 and PAL8_SEQ; they live as long as the context)
+static int alloc_slot_side(poppy_hip_ctx* c, FrameSlot& f) {
+    // The side streams are created at the LOWEST stream priority.  The runtime keeps its hardware queues per priority, so they never share a queue with the
+    // chain's stream or the plan upload's (normal priority): a dispatch waits for the one before it in its hardware queue whatever its stream, and a
+    // 350 us palette build in the chain's queue held the next frame's warp back for its whole length (kernel trace).
+    if (!f.fmt_stream) {
+        int least = 0, greatest = 0;
+        HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCHK(c, hipStreamCreateWithPriority(&f.fmt_stream, hipStreamNonBlocking, least));
+    }
+    if (!f.bgr_done) HIPCHK(c, hipEventCreateWithFlags(&f.bgr_done, hipEventDisableTiming));
+    return POPPY_OK;
+}
 
 // every slot's PAL8 buffer, tables, side stream and event for the pair's geometry (while the context's frame format is PAL8)
 static int alloc_slot_pal8(poppy_hip_ctx* c) {
-    if (!pal8_fits(c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8 takes frames of at most 2^24 pixels");
+    if (!pal8_fits(c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
     const size_t bytes = poppy_frame_bytes(POPPY_FRAME_PAL8, c->W, c->H);
     for (FrameSlot& f : c->slots) {
         if (!f.pal8) HIPCHK(c, hipMalloc((void**)&f.pal8, bytes + 16));
         if (!f.pal8_tables) { int rc = alloc_pal8_tables(c, &f.pal8_tables); if (rc) return rc; }
-        // The side streams are created at the LOWEST stream priority.  The runtime keeps its hardware queues per priority, so they never share a queue with the
-        // chain's stream or the plan upload's (normal priority): a dispatch waits for the one before it in its hardware queue whatever its stream, and a
-        // 350 us palette build in the chain's queue held the next frame's warp back for its whole length (kernel trace).
-        if (!f.fmt_stream) {
-            int least = 0, greatest = 0;
-            HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIPCHK(c, hipStreamCreateWithPriority(&f.fmt_stream, hipStreamNonBlocking, least));
-        }
-        if (!f.bgr_done) HIPCHK(c, hipEventCreateWithFlags(&f.bgr_done, hipEventDisableTiming));
+        int rc = alloc_slot_side(c, f); if (rc) return rc;
+    }
+    return POPPY_OK;
+}
+
+// PAL8_SEQ: the slots' side streams and the context's sequence tables, zero before the first sequence (the build leaves the sums zero again).  The store and the
+// index ring depend on the sequence's length: seq_begin, seq_finish.
+static int alloc_slot_pal8_seq(poppy_hip_ctx* c) {
+    if (!pal8_fits(c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
+    for (FrameSlot& f : c->slots) { int rc = alloc_slot_side(c, f); if (rc) return rc; }
+    if (!c->seq_tables) {
+        HIPCHK(c, hipSetDevice(c->device));
+        if (!prepare_pal8()) return fail(c, POPPY_E_DEVICE, "could not raise the palette build's LDS limit");
+        HIPCHK(c, hipMalloc((void**)&c->seq_tables, kPal8SeqTableBytes));
+        HIPCHK(c, hipMemset(c->seq_tables, 0, kPal8SeqTableBytes));
     }
     return POPPY_OK;
 }
 
 static int alloc_slot_format(poppy_hip_ctx* c) {
-    return c->frame_format == POPPY_FRAME_I420 ? alloc_slot_i420(c) : c->frame_format == POPPY_FRAME_PAL8 ? alloc_slot_pal8(c) : POPPY_OK;
+    return c->frame_format == POPPY_FRAME_I420 ? alloc_slot_i420(c) : c->frame_format == POPPY_FRAME_PAL8 ? alloc_slot_pal8(c) :
+           c->frame_format == POPPY_FRAME_PAL8_SEQ ? alloc_slot_pal8_seq(c) : POPPY_OK;
 }
 
 int alloc_pair(poppy_hip_ctx* c, int W, int H) {
     { int rc = drain_frames(c); if (rc) return rc; }              // every pair loader comes through here: no frame still reads the old pair
     // PAL8 takes frames of at most 2^24 pixels: refused before anything is allocated or any state changes, so the context keeps the pair it had
-    if (c->frame_format == POPPY_FRAME_PAL8 && !pal8_fits(W, H)) return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8 takes frames of at most 2^24 pixels");
+    if (is_pal8(c->frame_format) && !pal8_fits(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
     if (c->W == W && c->H == H && c->c1) return alloc_slot_format(c);      // (allocates only what is missing: nothing, unless an earlier attempt failed half-way)
     free_pair(c);
     c->pyr_forms.clear();
@@ -533,11 +557,139 @@ void start_default_seq_plans(poppy_hip_ctx* c) {
     start_seq_plans(c, ratio.data(), N, true);
 }
 
-static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* mask, int n, bool chain, poppy_write_cb write, void* user) {
+// ---- POPPY_FRAME_PAL8_SEQ: one palette for all the frames a call hands to its writer ---------------------------------------------------------------------
+// seq_begin opens a sequence of n frames (limits, tables, store), every frame for the writer then goes through seq_pass (render_slot, seq_add_image) instead of
+// a download, and seq_finish builds the palette and hands every frame to the writer; seq_abort ends a sequence of which a frame failed, nothing written.
+static int seq_abort(poppy_hip_ctx* c);
+static int seq_begin(poppy_hip_ctx* c, int n) {
+    const int W = c->W, H = c->H;
+    if (c->seq_open) { int rc = seq_abort(c); if (rc) return rc; }      // (a sequence that a device error left open: its frames and sums are dropped, not mixed into this one)
+    if (!pal8_fits(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
+    if ((unsigned long long)n * (unsigned long long)W * (unsigned long long)H >= POPPY_PAL8_SEQ_MAX_PIXELS)
+        return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8_SEQ takes sequences of fewer than 2^32 pixels in all");
+    { int rc = alloc_slot_pal8_seq(c); if (rc) return rc; }
+    const size_t stride = ((size_t)W * H * 3 + 15) & ~(size_t)15, need = stride * (size_t)n;      // (every frame's place begins on a 16-byte boundary)
+    if (need > c->seq_store_bytes) {
+        if (c->seq_store) (void)hipFree(c->seq_store);
+        c->seq_store = nullptr; c->seq_store_bytes = 0;
+        if (hipMalloc((void**)&c->seq_store, need) != hipSuccess) { (void)hipGetLastError(); return fail(c, POPPY_E_DEVICE, "no device memory for the sequence's frames (3 * width * height bytes each)"); }
+        c->seq_store_bytes = need;
+    }
+    c->seq_stride = stride; c->seq_n = n; c->seq_count = 0; c->seq_open = true;
+    return POPPY_OK;
+}
+
+// frames submitted now go into the open sequence
+static bool seq_wanted(const poppy_hip_ctx* c) { return c->seq_open && c->writer_attached && c->frame_format == POPPY_FRAME_PAL8_SEQ; }
+
+// the pass of one frame: into the sequence's sums and on to `dst` in the store, one kernel
+static int seq_pass(poppy_hip_ctx* c, const uint8_t* d_bgr, uint8_t* dst, hipStream_t s, hipEvent_t done) {
+    launch_pal8_seq_pass(d_bgr, dst, c->seq_tables, c->W, c->H, s, done);
+    HIPCHK(c, hipGetLastError());
+    return POPPY_OK;
+}
+
+static uint8_t* seq_next_place(poppy_hip_ctx* c) { return c->seq_count < c->seq_n ? c->seq_store + (size_t)c->seq_count++ * c->seq_stride : nullptr; }
+
+// a frame that no slot renders (the t == 0 / 1 copies of poppy_hip_render_phases), on the context's stream
+static int seq_add_image(poppy_hip_ctx* c, const uint8_t* d_bgr) {
+    uint8_t* dst = seq_next_place(c);
+    if (!dst) return fail(c, POPPY_E_STATE, "more frames than the sequence was opened for");
+    Timer tm(c, c->stream);
+    if (c->timing == 1) tm.mark(nullptr);
+    { int rc = seq_pass(c, d_bgr, dst, c->stream, nullptr); if (rc) return rc; }
+    if (c->timing == 1) tm.mark("pal8_seq_hist");
+    HIPCHK(c, hipGetLastError());
+    return POPPY_OK;
+}
+
+static int seq_abort(poppy_hip_ctx* c) {
+    c->seq_open = false;
+    int rc = drain_frames(c);
+    if (c->seq_tables && hipMemset(c->seq_tables, 0, kPal8SeqTableOffset) != hipSuccess && rc == POPPY_OK) rc = fail(c, POPPY_E_DEVICE, "could not clear the sequence tables");
+    return rc;
+}
+
+static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user);
+// the open sequence is complete: palette, then every frame to the writer.  Whatever fails in there, the sequence is closed and the tables are zero afterwards.
+static int seq_finish(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
+    if (c->seq_count != c->seq_n) { (void)seq_abort(c); return fail(c, POPPY_E_STATE, "fewer frames than the sequence was opened for"); }
+    const int rc = seq_hand_over(c, write, user);
+    if (rc) { const std::string why = c->err; (void)seq_abort(c); c->err = why; }
+    return rc;
+}
+
+static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
+    const int n = c->seq_count, W = c->W, H = c->H;
+    c->seq_open = false;
+    { int rc = drain_frames(c); if (rc) return rc; }              // every pass has added its frame (they ran on the slots' streams)
+    const bool marks = c->timing == 1;
+    {
+        Timer tm(c, c->stream);
+        if (marks) tm.mark(nullptr);
+        launch_pal8_seq_build(c->seq_tables, c->stream);
+        if (marks) tm.mark("pal8_seq_build");
+    }
+    HIPCHK(c, hipGetLastError());
+    uint8_t pal[768];
+    HIPCHK(c, hipMemcpyAsync(pal, c->seq_tables + kPal8SeqPaletteOffset, 768, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // Every frame: the index plane from the store through a ring of R device planes and R pinned buffers, remap and copy in order on the ring buffer's own stream
+    // (render_sequence: no event behind a copy), the palette behind the indices on the host.
+    static const int ring_pref = getenv("POPPY_HIP_RING") ? std::max(1, atoi(getenv("POPPY_HIP_RING"))) : 3;
+    const int R = std::min(poppy_hip_ctx::kStageRing, ring_pref);
+    const size_t n_px = (size_t)W * H, slot_bytes = (n_px + 768 + 255) & ~(size_t)255, plane = (n_px + 255) & ~(size_t)255;
+    { int rc = stage_host(c, slot_bytes * R); if (rc) return rc; }
+    if (plane * R > c->seq_idx_bytes) {
+        if (c->seq_idx) (void)hipFree(c->seq_idx);
+        c->seq_idx = nullptr; c->seq_idx_bytes = 0;
+        HIPCHK(c, hipMalloc((void**)&c->seq_idx, plane * R));
+        c->seq_idx_bytes = plane * R;
+    }
+    auto deliver = [&](int k) -> int {
+        const int r = k % R;
+        HIPCHK(c, hipStreamSynchronize(c->dl_ring[r]));
+        uint8_t* frame = c->h_stage + (size_t)r * slot_bytes;
+        memcpy(frame + n_px, pal, 768);
+        write(user, frame, W, H, (size_t)W);
+        return POPPY_OK;
+    };
+    int written = 0;
+    for (int k = 0; k < n; ++k) {
+        const int r = k % R;
+        if (k >= R) { int rc = deliver(written); if (rc) return rc; ++written; }
+        if (!c->dl_ring[r]) HIPCHK(c, hipStreamCreateWithFlags(&c->dl_ring[r], hipStreamNonBlocking));
+        Timer tm(c, c->dl_ring[r]);
+        if (marks) tm.mark(nullptr);
+        launch_pal8_seq_remap(c->seq_store + (size_t)k * c->seq_stride, c->seq_tables, c->seq_idx + (size_t)r * plane, W, H, c->dl_ring[r]);
+        if (marks) tm.mark("frame_format");
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, c->seq_idx + (size_t)r * plane, n_px, hipMemcpyDeviceToHost, c->dl_ring[r]));
+    }
+    for (; written < n; ++written) { int rc = deliver(written); if (rc) return rc; }
+    return POPPY_OK;
+}
+
+static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const double* mask, int n, bool chain, poppy_write_cb write, void* user);
+
+// PAL8_SEQ: the frames go through the pass into the sequence store and to the writer when all are there — of this call's own sequence, or of the one its caller
+// opened and ends (in_open_seq: poppy_hip_render_phases).  Opened first: its limits refuse before anything is rendered.  Every way out of the frames' loop
+// comes back here, so a sequence this call opened is finished or aborted, never left open.
+static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* mask, int n, bool chain, poppy_write_cb write, void* user, bool in_open_seq = false) {
     if (!c->pair_ready) return fail(c, POPPY_E_STATE, "no pair loaded");
     if (c->pts1.empty()) return fail(c, POPPY_E_NOMATCH, "no point pairs (use poppy_hip_dissolve)");
     if (n <= 0) return POPPY_OK;
+    const bool own_seq = write && c->frame_format == POPPY_FRAME_PAL8_SEQ && !in_open_seq;
+    if (own_seq) { int rc = seq_begin(c, n); if (rc) return rc; }
+    int rc = render_sequence_frames(c, shape, mask, n, chain, write, user);
+    c->writer_attached = false;
+    if (own_seq) { if (rc == POPPY_OK) rc = seq_finish(c, write, user); else { const std::string why = c->err; (void)seq_abort(c); c->err = why; } }
+    return rc;
+}
+
+static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const double* mask, int n, bool chain, poppy_write_cb write, void* user) {
     const int W = c->W, H = c->H;
+    const bool seq = write && c->frame_format == POPPY_FRAME_PAL8_SEQ;
     if (n >= 2) c->plan_ahead_credit = true;                       // a caller of sequences: the next pair loader plans ahead again (start_default_seq_plans)
     // the plans a pair loader started for exactly these frames on exactly these points, or new ones
     SeqPlans* sp = static_cast<SeqPlans*>(c->seq_plans);
@@ -556,7 +708,8 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
     const int fmt = write ? c->frame_format : POPPY_FRAME_BGR;
     // (every way to this format with a pair allocates the slots' buffers — alloc_pair, poppy_hip_set_frame_format — or refuses: a frame is never converted into nothing)
     for (const FrameSlot& f : c->slots)
-        if ((fmt == POPPY_FRAME_I420 && !f.i420) || (fmt == POPPY_FRAME_PAL8 && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)))
+        if ((fmt == POPPY_FRAME_I420 && !f.i420) || (fmt == POPPY_FRAME_PAL8 && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) ||
+            (seq && !(c->seq_open && c->seq_tables && f.fmt_stream && f.bgr_done)))
             return fail(c, POPPY_E_STATE, "the frame format's buffers are not allocated for this pair");
     const size_t row = fmt != POPPY_FRAME_BGR ? (size_t)W : (size_t)W * 3, frame_bytes = poppy_frame_bytes(fmt, W, H);
     auto frame_of = [fmt](const FrameSlot& f) -> const uint8_t* { return fmt == POPPY_FRAME_I420 ? f.i420 : fmt == POPPY_FRAME_PAL8 ? f.pal8 : f.out; };
@@ -564,7 +717,8 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
     const int R = std::min({poppy_hip_ctx::kStageRing, ring_pref, (int)c->slots.size()});
     const size_t slot_bytes = (frame_bytes + 255) & ~(size_t)255;     // ring slots start on 256-byte boundaries
     int written = 0;
-    if (write) rc = stage_host(c, slot_bytes * R);
+    if (write && !seq) rc = stage_host(c, slot_bytes * R);
+    const bool dl = write && !seq;                                // frames are downloaded and handed over as they finish
     c->writer_attached = write != nullptr;                        // (phase-mode frames pick their streams by it: submit_frame)
     // Frame hand-off.  The download of a frame runs on its own stream into a ring of R pinned buffers while the GPU renders the
     // frames behind it, and the writer gets frames in order, R - 1 downloads behind.  A copy whose start depends on an event of
@@ -632,7 +786,7 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
         if (rcs[j]) { rc = fail(c, POPPY_E_RANGE, "point outside the image rectangle (Subdiv2D::insert would throw)"); break; }
         c->plan = std::move(plans[j]);
         if (chain) c->pts1 = src1[j];
-        if (write) {
+        if (dl) {
             // The slot frame j renders into may still hold a frame whose download has not been issued (few slots, or every frame
             // landing in the one slot that does not hold corrected1): that copy goes out first; submit_frame then waits for it.
             int ps = c->next_slot;
@@ -653,7 +807,7 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
         ms_submit += lap(t_sub);
         if (rc != POPPY_OK) break;
         slot_of[j] = c->last_slot;
-        if (write) {
+        if (dl) {
             // frames whose download can be issued now.  A PAL8 frame is complete one palette build (several frame times) behind its BGR: waiting for frame
             // j - 1 here would hold back frame j + 1 for that long, so under PAL8 the downloads trail as far as the slots allow (the loop above the
             // submit sends what a slot's reuse forces out) and the conversions of that many frames run beside each other.
@@ -664,7 +818,7 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
             }
         }
     }
-    if (write && rc == POPPY_OK) {
+    if (dl && rc == POPPY_OK) {
         while (issued < n && rc == POPPY_OK) {                    // the last frame(s), then drain the ring
             while (issued - written >= R && rc == POPPY_OK) deliver(written);
             if (rc == POPPY_OK && issue_download(issued)) ++issued;
@@ -687,11 +841,13 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
 static_assert(kPlanRasterRows == kRasterChunkRows, "the plan's work list and k_raster must agree on the chunk height");
 
 // the format the frames being submitted are converted to for their writer (their slots' bodies end with the conversion); BGR: none
-static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached ? c->frame_format : POPPY_FRAME_BGR; }
+// (PAL8_SEQ: none either — the sequence pass is launched behind the body, its destination differs from frame to frame: render_slot)
+static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached && c->frame_format != POPPY_FRAME_PAL8_SEQ ? c->frame_format : POPPY_FRAME_BGR; }
 
 // pyrdown .. unsharp of one slot.  Every argument is fixed for the life of the pair (the per-frame unsharp amount is
 // read from the slot's plan blob), which is what lets the whole sequence be captured into one graph launch.
-static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm, float amount, bool debug, hipEvent_t done = nullptr, bool chained = false) {
+static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm, float amount, bool debug, hipEvent_t done = nullptr, bool chained = false,
+                        uint8_t* seq_dst = nullptr) {
     const int W = c->W, H = c->H, L = c->cfg.pyramid_levels;
     const int ft = c->first_tail < L ? c->first_tail : L;
     static const bool fuse = getenv("POPPY_HIP_NOFUSE") == nullptr;
@@ -765,10 +921,12 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     // frame needs this frame's BGR, not its palette form: on the chain (`chained` with a completion event riding, i.e. kernels launched one by one) the
     // conversion goes to the slot's side stream behind an event that rides on the unsharp, the chain's stream goes on with the next frame, and `done` —
     // which the download, the slot's reuse and drain_frames wait for — rides on the conversion's last dispatch.
+    // PAL8_SEQ (seq_dst: the frame's place in the sequence store, never set in a captured body): the pass takes PAL8's place, on the side stream too — it is short,
+    // but the chain needs nothing of it.
     const int fmt = frame_wants_format(c);
-    const bool side = fmt == POPPY_FRAME_PAL8 && chained && done && !tm;
+    const bool side = (fmt == POPPY_FRAME_PAL8 || seq_dst) && chained && done && !tm;
     launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s,
-                   side ? f.bgr_done : fmt != POPPY_FRAME_BGR ? nullptr : done, c->levels[0].pitch);
+                   side ? f.bgr_done : (fmt != POPPY_FRAME_BGR || seq_dst) ? nullptr : done, c->levels[0].pitch);
     rec(POPPY_PYR_UNSHARP, 0, W < 2 || H < 2);
     if (tm) tm->mark("unsharp");
     if (fmt == POPPY_FRAME_I420) {
@@ -783,6 +941,11 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
         if (tm) tm->mark("pal8_build");
         launch_pal8_remap(f.out, f.pal8_tables, f.pal8, W, H, fs, done);
         if (tm) tm->mark("frame_format");                      // (under PAL8: the index plane alone)
+    } else if (seq_dst) {
+        hipStream_t fs = side ? f.fmt_stream : s;
+        if (side) HIPCHK(c, hipStreamWaitEvent(fs, f.bgr_done, 0));
+        { int rc = seq_pass(c, f.out, seq_dst, fs, done); if (rc) return rc; }
+        if (tm) tm->mark("pal8_seq_hist");
     }
     return POPPY_OK;
 }
@@ -1047,8 +1210,11 @@ static int render_slot(poppy_hip_ctx* c, int fi, bool chain) {
     // its own behind the last kernel leaves the stream idle for ~6 us before the next frame's first kernel.
     static const bool done_packet = getenv("POPPY_HIP_DONE_PACKET") != nullptr;
     const bool done_rides = !use_graph && !all_marks && !done_packet;
-    if (use_graph) HIPCHK(c, hipGraphLaunch(f.body, s));
-    else { int rc = enqueue_body(c, f, s, all_marks ? &tm : nullptr, (float)(1.0 - amount), c->debug, done_rides ? f.done : nullptr, chained); if (rc) return rc; }
+    // PAL8_SEQ: the frame's pass — behind the captured body on the same stream (the body stays BGR: the store address differs per frame), or as the body's last launch
+    uint8_t* seq_dst = nullptr;
+    if (seq_wanted(c) && !(seq_dst = seq_next_place(c))) return fail(c, POPPY_E_STATE, "more frames than the sequence was opened for");
+    if (use_graph) { HIPCHK(c, hipGraphLaunch(f.body, s)); if (seq_dst) { int rc = seq_pass(c, f.out, seq_dst, s, nullptr); if (rc) return rc; } }
+    else { int rc = enqueue_body(c, f, s, all_marks ? &tm : nullptr, (float)(1.0 - amount), c->debug, done_rides ? f.done : nullptr, chained, seq_dst); if (rc) return rc; }
     HIPCHK(c, hipGetLastError());
     if (!done_rides) HIPCHK(c, hipEventRecord(f.done, s));
     c->last_slot = fi;
@@ -1084,14 +1250,22 @@ static int prepare_ahead(poppy_hip_ctx* c, const FramePlan& plan, double mask) {
     return rc;
 }
 
-int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride) {
+int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride, int n_copies) {
+    if (c->frame_format == POPPY_FRAME_PAL8_SEQ) {                 // the copies are the sequence: the host statement on the BGR frame
+        std::vector<uint8_t> bgr((size_t)W * H * 3);
+        HIPCHK(c, hipMemcpyAsync(bgr.data(), d_bgr, bgr.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        int rc = POPPY_OK;
+        const uint8_t* frame = host_frame(c, bgr.data(), (size_t)W * 3, W, H, host, stride, &rc, n_copies);
+        return frame ? POPPY_OK : rc;
+    }
     if (c->frame_format == POPPY_FRAME_BGR) {
         host.resize((size_t)W * H * 3);
         *stride = (size_t)W * 3;
         HIPCHK(c, hipMemcpyAsync(host.data(), d_bgr, host.size(), hipMemcpyDeviceToHost, c->stream));
     } else {
         const bool pal8 = c->frame_format == POPPY_FRAME_PAL8;
-        if (pal8 && !pal8_fits(W, H)) return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8 takes frames of at most 2^24 pixels");
+        if (pal8 && !pal8_fits(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
         if (pal8 && !c->pal8_scratch_tables) { int rc = alloc_pal8_tables(c, &c->pal8_scratch_tables); if (rc) return rc; }
         const size_t bytes = poppy_frame_bytes(c->frame_format, W, H);
         if (bytes + 16 > c->i420_scratch_bytes) {
@@ -1115,12 +1289,13 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::ve
     return POPPY_OK;
 }
 
-const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status) {
+const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status, int n_copies) {
     *out_stride = stride;
     *status = POPPY_OK;
     if (c->frame_format == POPPY_FRAME_BGR) return bgr;
     tmp.resize(poppy_frame_bytes(c->frame_format, W, H));
-    const int rc = c->frame_format == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
+    const int rc = c->frame_format == POPPY_FRAME_PAL8_SEQ ? pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, tmp.data()) :
+                   c->frame_format == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
     if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
     *out_stride = (size_t)W;
     return tmp.data();
@@ -1241,7 +1416,7 @@ int poppy_hip_morph_frames(poppy_hip_ctx* c, double phase, poppy_write_cb write,
         const uint8_t* img = phase == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2);
         if (c->frame_format != POPPY_FRAME_BGR) {
             std::vector<uint8_t> host; size_t stride = 0;
-            int rc = download_frame(c, img, c->W, c->H, host, &stride); if (rc) return rc;
+            int rc = download_frame(c, img, c->W, c->H, host, &stride, N); if (rc) return rc;
             for (int j = 0; j < N; ++j) write(user, host.data(), c->W, c->H, stride);
             return POPPY_OK;
         }
@@ -1262,9 +1437,15 @@ int poppy_hip_render_phases(poppy_hip_ctx* c, const double* t, int n, poppy_writ
     if (!c->pair_ready) return fail(c, POPPY_E_STATE, "no pair loaded");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t row = (size_t)c->W * 3;
+    // PAL8_SEQ: the call's frames, copies included, are one sequence: collected on the device, handed over at the end
+    const bool seq = write && n > 0 && c->frame_format == POPPY_FRAME_PAL8_SEQ;
+    if (seq) { int rc = seq_begin(c, n); if (rc) return rc; }
     for (int i = 0; i < n;) {
         if (t[i] == 0 || t[i] == 1) {                             // a plain copy of image 1 / image 2
-            if (write && c->frame_format != POPPY_FRAME_BGR) {
+            if (seq) {
+                int rc = seq_add_image(c, t[i] == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2));
+                if (rc) { const std::string why = c->err; (void)seq_abort(c); c->err = why; return rc; }
+            } else if (write && c->frame_format != POPPY_FRAME_BGR) {
                 std::vector<uint8_t> host; size_t stride = 0;
                 int rc = download_frame(c, t[i] == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2), c->W, c->H, host, &stride); if (rc) return rc;
                 write(user, host.data(), c->W, c->H, stride);
@@ -1280,11 +1461,12 @@ int poppy_hip_render_phases(poppy_hip_ctx* c, const double* t, int n, poppy_writ
         }
         int j = i;
         while (j < n && t[j] != 0 && t[j] != 1) ++j;
-        { int rc = poppy_hip_pair_reset(c); if (rc) return rc; }
-        int rc = render_sequence(c, t + i, t + i, j - i, false, write, user); if (rc) return rc;
+        int rc = poppy_hip_pair_reset(c);
+        if (rc == POPPY_OK) rc = render_sequence(c, t + i, t + i, j - i, false, write, user, seq);
+        if (rc) { if (seq) { const std::string why = c->err; (void)seq_abort(c); c->err = why; } return rc; }
         i = j;
     }
-    return POPPY_OK;
+    return seq ? seq_finish(c, write, user) : POPPY_OK;
 }
 
 int poppy_printed_morph_distance(const float* p1, const float* p2, int n, int W, int H, double* out) {
@@ -1316,7 +1498,7 @@ int poppy_hip_morph(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint
         std::vector<uint8_t> tmp;
         size_t stride = phase == 0 ? s1 : s2;
         int frame_rc = POPPY_OK;
-        const uint8_t* img = (write && N > 0) ? host_frame(c, phase == 0 ? bgr1 : bgr2, stride, W, H, tmp, &stride, &frame_rc) : nullptr;
+        const uint8_t* img = (write && N > 0) ? host_frame(c, phase == 0 ? bgr1 : bgr2, stride, W, H, tmp, &stride, &frame_rc, N) : nullptr;
         if (write && N > 0 && !img) return frame_rc;
         for (int j = 0; j < N && write; ++j) write(user, img, W, H, stride);
         return POPPY_OK;
@@ -1327,7 +1509,7 @@ int poppy_hip_morph(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint
             std::vector<uint8_t> blend((size_t)W * 3 * H);
             rc = poppy_hip_dissolve(c, bgr1, s1, bgr2, s2, W, H, phase, blend.data(), (size_t)W * 3); if (rc) return rc;
             size_t stride = (size_t)W * 3;
-            if (c->frame_format != POPPY_FRAME_BGR) { rc = download_frame(c, c->slots[0].out, W, H, blend, &stride); if (rc) return rc; }      // the blend, still in slot 0
+            if (c->frame_format != POPPY_FRAME_BGR) { rc = download_frame(c, c->slots[0].out, W, H, blend, &stride, N); if (rc) return rc; }      // the blend, still in slot 0
             for (int j = 0; j < N; ++j) write(user, blend.data(), W, H, stride);
         }
         return fail(c, POPPY_E_NOMATCH, "no point pairs: linear-blend fallback frames written (src/poppy.hpp:125-134)");
@@ -1456,10 +1638,10 @@ int poppy_hip_timing_summary(poppy_hip_ctx* c, const char** names, float* total_
 
 int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
     if (!c) return POPPY_E_ARG;
-    if (format != POPPY_FRAME_BGR && format != POPPY_FRAME_I420 && format != POPPY_FRAME_PAL8) return fail(c, POPPY_E_ARG, "unknown frame format");
+    if (format != POPPY_FRAME_BGR && format != POPPY_FRAME_I420 && !is_pal8(format)) return fail(c, POPPY_E_ARG, "unknown frame format");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = drain_frames(c); if (rc) return rc; }
-    if (format == POPPY_FRAME_PAL8 && c->c1 && !pal8_fits(c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8 takes frames of at most 2^24 pixels");
+    if (is_pal8(format) && c->c1 && !pal8_fits(c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
     c->frame_format = format;
     return c->c1 ? alloc_slot_format(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
 }

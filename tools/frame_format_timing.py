@@ -1,4 +1,4 @@
-"""BGR against I420 against PAL8 frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run
+"""BGR against I420 against PAL8 against PAL8_SEQ frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run
 times each row once per format, one format right after the other, and the rows report min / median / max over --runs runs.
 
   pool_1080p    bench.py's `value` set-up: a pool of --contexts contexts, --steps queued batches of six 1080p pairs from device images, 60 chained
@@ -8,10 +8,12 @@ times each row once per format, one format right after the other, and the rows r
   chained       one context, pair after pair: pair set-up + 60 chained frames to the counting writer
   chained_frame one context, the 60 chained frames of a resident pair to the counting writer (what the extra launch costs a chained frame)
   d2h_ceiling   pinned device-to-host copies of one frame's bytes, back to back on one stream (BGR, I420 and PAL8 sizes at 1080p and 4K)
-and, at the end, the conversion kernels' own times in timing mode 1 at 1080p and 4K (I420: frame_format; PAL8: pal8_hist, pal8_build, frame_format = the index plane).
+and, at the end, the conversion kernels' own times in timing mode 1 at 1080p and 4K (I420: frame_format; PAL8: pal8_hist, pal8_build, frame_format = the index plane;
+PAL8_SEQ: pal8_seq_hist per frame, pal8_seq_build per sequence, frame_format = the index plane).  Under PAL8_SEQ a pair's (a call's) frames are handed over after its last
+frame.
 
-    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6]
-One JSON line at the end.
+    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq]
+--formats leaves formats out (a library older than PAL8_SEQ: bgr,i420,pal8).  One JSON line at the end.
 """
 import argparse
 import json
@@ -25,7 +27,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poppy_amd import capi, synth  # noqa: E402
 
-FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420), ("pal8", capi.FRAME_PAL8))
+ALL_FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420), ("pal8", capi.FRAME_PAL8), ("pal8_seq", capi.FRAME_PAL8_SEQ))
 
 
 def pair_images(torch, dev, w, h, n):
@@ -72,8 +74,10 @@ def main():
     ap.add_argument("--steps-4k", type=int, default=3)
     ap.add_argument("--contexts", type=int, default=6)
     ap.add_argument("--rows", default="pool_1080p,pool_4k,job480,chained,chained_frame,d2h_ceiling")
+    ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq")
     a = ap.parse_args()
     rows = a.rows.split(",")
+    FMTS = tuple((f, v) for f, v in ALL_FMTS if f in a.formats.split(","))
     import torch
     dev = torch.device("cuda", 0)
     res = {r: {f: [] for f, _ in FMTS} for r in rows if r != "d2h_ceiling"}
@@ -122,7 +126,7 @@ def main():
         print(f"run {run}: " + ", ".join(f"{r} {f} {v[f][-1]:.0f}" for r, v in res.items() for f in v), flush=True)
     out = {"unit": "frames/s", "rows": {r: {f: summary(v) for f, v in fv.items()} for r, fv in res.items()}}
     for r, fv in res.items():
-        for f in ("i420", "pal8"):
+        for f in (f for f, _ in FMTS if f != "bgr"):
             out["rows"][r][f + "_over_bgr_median"] = round(statistics.median(fv[f]) / statistics.median(fv["bgr"]), 3)
     if "d2h_ceiling" in rows:
         out["d2h_ceiling"] = {f"{w}x{h}_{f}": d2h(torch, dev, capi.frame_bytes(fmt, w, h)) for w, h in ((1920, 1080), (3840, 2160)) for f, fmt in FMTS}
@@ -136,7 +140,7 @@ def main():
             ctx.reset(); ctx.render_many_counted(shapes, chain=True)
             t = {n: (ms, k) for n, ms, k in ctx.timing_summary()}
             ctx.set_timing(0)
-            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_format", "pal8_hist", "pal8_build")}
+            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build")}
     for p in (pool, pool4):
         if p:
             p.close()
