@@ -87,6 +87,9 @@ void dft_make_plan(int n, DftPlanHost& p) {
     } else {
         s1 = std::sin(-M_PI * 2 / n);
         c1 = std::sqrt(1. - s1 * s1);
+        // the positive root is the cosine only while 2 pi / n <= pi / 2: n == 3 is the one length where it is not.  The reference builds no table at
+        // all for n <= 5 and no pass of a length-3 line reads one (j == 0 only), so this changes no transform — only what poppy_dft_plan reports
+        if (n < 4) c1 = -c1;
     }
     p.wave.assign((size_t)n * 2, 0.f);
     auto put = [&](int k, double re, double im) { p.wave[2 * (size_t)k] = (float)re; p.wave[2 * (size_t)k + 1] = (float)im; };

@@ -207,6 +207,35 @@ def test_dft_plan_tables():
     assert np.abs(wave[:, 0] - np.cos(2 * np.pi * k / 1080)).max() < 1e-6 and np.abs(wave[:, 1] + np.sin(2 * np.pi * k / 1080)).max() < 1e-6
 
 
+def test_dft_plan_of_every_smooth_length():
+    """The plan of every length the padding can ask for up to 8640 (all 167 lengths 2^a 3^b 5^c: getOptimalDFTSize restated here): a permutation, the
+    factors in pass order (the whole power of two, the 5s, the 3s), the twiddles on the unit circle where they belong, and no more factors than
+    DftPlanDev::factors holds (16) — tests/test_gpu_dft_lengths.py runs every one of these lengths through the kernels."""
+    def smooth(n):
+        for f in (2, 3, 5):
+            while n % f == 0:
+                n //= f
+        return n == 1
+    S = [n for n in range(2, 8641) if smooth(n)]
+    assert len(S) == 167
+    for n in S:
+        f, itab, wave = capi.dft_plan(n)
+        f = f.tolist()
+        assert sorted(itab.tolist()) == list(range(n)), n
+        assert int(np.prod(np.asarray(f, np.int64))) == n, (n, f)
+        two = n & -n
+        want = ([two] if two > 1 else [])
+        rest = n // two
+        for p in (5, 3):
+            while rest % p == 0:
+                want.append(p); rest //= p
+        assert f == want, (n, f, want)
+        assert len(f) <= 16, (n, f)
+        k = np.arange(n)
+        err = max(np.abs(wave[:, 0] - np.cos(2 * np.pi * k / n)).max(), np.abs(wave[:, 1] + np.sin(2 * np.pi * k / n)).max())
+        assert err < 1e-6, (n, err)
+
+
 def test_matcher_hypot_is_libm_hypotf():
     """point_match.cpp evaluates hypotf by glibc's own closed form; compare with the linked libm on 2e6 inputs."""
     L = capi.lib()
