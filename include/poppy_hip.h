@@ -136,7 +136,7 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * poppy_bgr_to_i420 is the host statement of the format, poppy_frame_bytes its size (0 for an unknown format or an empty frame).
  * poppy_hip_set_frame_format drains the context's frames and applies to every frame handed to a writer by poppy_hip_morph,
  * poppy_hip_morph_frames, poppy_hip_render_many, poppy_hip_render_phases and poppy_hip_morph_list — the phase == 0 / 1 and t == 0 / 1
- * copies and the POPPY_E_NOMATCH linear-blend frames included; under I420 and PAL8 the writer gets (frame, width, height, stride = width).
+ * copies and the POPPY_E_NOMATCH linear-blend frames included; under I420 and PAL8 the writer gets (frame, width, height, stride = width), under GIF stride = 0.
  * Any other format: POPPY_E_ARG.  These stay BGR whatever the setting: poppy_hip_render / poppy_hip_dissolve into an explicit dst,
  * poppy_hip_frame_device, frames kept on the device (write == NULL), poppy_hip_morph_sharded and poppy_hip_morph_pairs (their contexts
  * are made from poppy_settings), and include/poppy_hip_shim.hpp.  poppy_hip_pool_set_frame_format sets every context of a pool.
@@ -185,15 +185,47 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  *      LDS; 64-bit words would not fit).  Both refusals are POPPY_E_UNSUPPORTED.
  * poppy_bgr_frames_to_pal8 is the host statement: n_frames BGR frames, frame k at bgr + k * frame_stride with rows `stride` bytes apart,
  * become n_frames PAL8_SEQ frames back to back in dst (n_frames * poppy_frame_bytes(POPPY_FRAME_PAL8_SEQ, width, height) bytes).  Its
- * refusals are poppy_bgr_to_pal8's, plus n_frames < 1 (POPPY_E_ARG) and the sequence limit; nothing is read or written before them.  */
+ * refusals are poppy_bgr_to_pal8's, plus n_frames < 1 (POPPY_E_ARG) and the sequence limit; nothing is read or written before them.
+ *
+ * POPPY_FRAME_GIF: PAL8's per-frame palette and indices with the indices LZW-coded on the GPU and framed as GIF image data, ready to be written behind an
+ * image descriptor (POPPY_SINK_GIF_CODED): the LZW coding, 40 ms of one host core per textured 1080p frame in POPPY_SINK_GIF, is off the host.  Its value is 64,
+ * and POPPY_SINK_GIF_CODED is 64, because 32 and the values below it are taken or tested as unknown.  Layout of a frame, little-endian:
+ *     bytes 0..3     total: the whole frame's length in bytes, these four included (poppy_gif_frame_bytes reads it)
+ *     bytes 4..771   the 768-byte palette, exactly PAL8's for this frame
+ *     bytes 772..    GIF image data: the minimum-code-size byte 8, the payload in sub-blocks of 255 bytes (a length byte in front of each; the last one
+ *                    shorter, none of length 0), then the terminator byte 0
+ * The writer gets (frame, width, height, stride = 0): a stride of 0 is how sinks and callers tell a coded frame from a raster, and only `total` bytes are valid.
+ *   The payload.  The index plane is one linear run of n = width * height bytes, cut into segments of POPPY_GIF_SEGMENT_PIXELS pixels, the last one shorter.
+ *      Every segment is coded by exactly the rule of POPPY_SINK_GIF's coder (codes 0..255 the bytes, 256 clear, 257 end, strings from 258; the width grows
+ *      from 9 to 12 bits when the entry just added is the first that needs the next width; a full table is restarted by a clear code): it begins with a clear
+ *      code at 9 bits and does not end with an end code but with one clear code at the current width, then the fewest further clear codes at 9 bits (0 to 7;
+ *      9 = 1 mod 8) that bring it to a byte boundary.  The segment behind it begins with its own clear code, so clear codes double there.  The last segment
+ *      ends with the end code at the current width, padded with zero bits to a byte.  Segments are whole bytes and are concatenated bytewise; repeated clear
+ *      codes are ordinary GIF, every decoder takes them.  The segments are independent, which is what lets the GPU code one per wave.
+ *   POPPY_GIF_SEGMENT_PIXELS is a constant of the FORMAT: it decides the bytes ("GIF hand-off", has the measurements behind its value).
+ *   Capacity.  poppy_frame_bytes(POPPY_FRAME_GIF, w, h) is an upper bound for any content, and the size of the buffers a frame is built in.  A segment of
+ *      s <= POPPY_GIF_SEGMENT_PIXELS <= 4096 pixels is: one clear code (9 bits); at most s string codes of at most 12 bits; at most ONE restart clear code
+ *      (12 bits: a table fills after 3838 codes, and 2 * 3838 > 4096); the closing clear or end code (at most 12 bits); at most seven padding clear codes
+ *      (63 bits) or seven zero bits.  So a segment has at most POPPY_GIF_SEGMENT_BYTES = ceil((9 + 12 * (S + 2) + 63) / 8) bytes, the payload at most P = that
+ *      times ceil(n / S), and the frame at most 772 + 1 + P + ceil(P / 255) + 1 bytes.
+ *   Limits, refused with POPPY_E_UNSUPPORTED before any state changes: PAL8's 2^24 pixels, and a width or height above 65535 (GIF's 16-bit descriptor).
+ * poppy_pal8_to_gif_frame is the host statement (pal8: a PAL8 frame of poppy_frame_bytes(POPPY_FRAME_PAL8, ..) bytes; dst: the capacity), poppy_bgr_to_gif_frame
+ * is poppy_bgr_to_pal8 followed by it.  poppy_hip_pal8_to_gif_frame codes a host PAL8 frame on the context's GPU (upload, the two kernels, download of `total`
+ * bytes): the same bytes.  The format applies wherever PAL8 applies and stays BGR wherever PAL8 stays BGR.  */
 #define POPPY_PAL8_MAX_PIXELS (1 << 24)
 #define POPPY_PAL8_SEQ_MAX_PIXELS (1ull << 32)
-enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16 };
+#define POPPY_GIF_SEGMENT_PIXELS 2048
+#define POPPY_GIF_SEGMENT_BYTES ((9 + 12 * (POPPY_GIF_SEGMENT_PIXELS + 2) + 63 + 7) / 8)
+enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 int poppy_bgr_to_pal8(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 int poppy_bgr_frames_to_pal8(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst);
+size_t poppy_gif_frame_bytes(const uint8_t* frame);
+int poppy_pal8_to_gif_frame(const uint8_t* pal8, int width, int height, uint8_t* dst);
+int poppy_bgr_to_gif_frame(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* ctx, const uint8_t* pal8, int width, int height, uint8_t* dst);
 /* phase == 0 / phase == 1 follow the reference's short-circuit (src/poppy.hpp:54-70): number_of_frames copies of image 1 /
  * image 2 as they were handed to the pair set-up (with auto-align: the UNALIGNED image 2), no frame is rendered.            */
 
@@ -525,11 +557,14 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * screen flags 0xF7), a frame whose palette equals it gets an image descriptor without a local table (flags 0x00), and a frame whose
  * palette differs gets its own local table as under GIF (0x87) — so PAL8 frames and the frames of several pairs are taken too and decode
  * to the pixels the GIF sink's file decodes to.  The header goes out with the first frame, which names the table.
+ * GIF_CODED: POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames (stride must be 0): header, NETSCAPE2.0 block, and per frame the graphic control extension, the
+ * descriptor with a local table, the frame's palette, then the frame's bytes 772 .. total as they are.  Decodes to the pixels the GIF sink's file decodes to; its
+ * length is 0.99 - 1.16 times that file's on the measured inputs (every segment of the coded form starts a new table).  A frame of any other format fails this sink, and a coded frame fails every other sink.
  * The BGR sinks take frames with stride >= 3 * width, the I420 and GIF sinks frames with stride == width: a frame of another format fails the
  * sink where its stride tells (a BGR frame at the I420 or GIF sink, an I420 or PAL8 frame at a BGR sink); a writer must match the context's format.
  * poppy_sink_close returns the number of frames written, or a negative status if a write failed or a frame had another geometry.   */
 typedef struct poppy_sink poppy_sink;
-enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8, POPPY_SINK_GIF_GLOBAL = 16 };
+enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8, POPPY_SINK_GIF_GLOBAL = 16, POPPY_SINK_GIF_CODED = 64 };
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den);
 void poppy_sink_write(void* sink, const uint8_t* bgr, int width, int height, size_t stride);
 int poppy_sink_close(poppy_sink* sink);

@@ -25,8 +25,8 @@ WARP_KERNELS = ("k_warp_bin", "k_warp_tile", "k_warp4")        # order of poppy_
 PYRAMID_FORMS = ("down", "down2", "tail", "tail_nl", "mix_top", "cone", "up2", "up", "unsharp")
 WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_size_t)
 # formats of the frames handed to writers (poppy_hip_set_frame_format) and the file sinks (poppy_sink_open)
-FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ = 0, 1, 8, 16
-SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL = 0, 1, 2, 3, 8, 16
+FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF = 0, 1, 8, 16, 64
+SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED = 0, 1, 2, 3, 8, 16, 64
 
 # every symbol include/poppy_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -45,6 +45,7 @@ SYMBOLS = [
     "poppy_hip_pair_begin_next", "poppy_hip_pair_begin_next_device", "poppy_hip_chain_counts", "poppy_hip_morph_list",
     "poppy_hip_last_pyramid_forms",
     "poppy_hip_set_frame_format", "poppy_hip_pool_set_frame_format", "poppy_frame_bytes", "poppy_bgr_to_i420", "poppy_bgr_to_pal8", "poppy_bgr_frames_to_pal8",
+    "poppy_gif_frame_bytes", "poppy_pal8_to_gif_frame", "poppy_bgr_to_gif_frame", "poppy_hip_pal8_to_gif_frame",
 ]
 
 
@@ -167,6 +168,11 @@ def lib():
         L.poppy_bgr_to_i420.argtypes = [vp, sz, i, i, vp]
         L.poppy_bgr_to_pal8.argtypes = [vp, sz, i, i, vp]
         L.poppy_bgr_frames_to_pal8.argtypes = [vp, sz, sz, i, i, i, vp]
+        L.poppy_gif_frame_bytes.restype = sz
+        L.poppy_gif_frame_bytes.argtypes = [vp]
+        L.poppy_pal8_to_gif_frame.argtypes = [vp, i, i, vp]
+        L.poppy_bgr_to_gif_frame.argtypes = [vp, sz, i, i, vp]
+        L.poppy_hip_pal8_to_gif_frame.argtypes = [vp, vp, i, i, vp]
         L.poppy_hypotf_selfcheck.restype = C.c_long
         L.poppy_hypotf_selfcheck.argtypes = [C.c_long, C.c_uint64]
         _lib = L
@@ -178,7 +184,8 @@ def _p(a):
 
 
 def frame_bytes(fmt, w, h):
-    """Host-only: bytes of a w x h frame in format fmt (FRAME_BGR / FRAME_I420 / FRAME_PAL8 / FRAME_PAL8_SEQ; 0 for anything else)."""
+    """Host-only: bytes of a w x h frame in format fmt (FRAME_BGR / FRAME_I420 / FRAME_PAL8 / FRAME_PAL8_SEQ; FRAME_GIF: the capacity, an upper bound for any
+    content — a frame's own length is gif_frame_bytes; 0 for anything else)."""
     return int(lib().poppy_frame_bytes(int(fmt), int(w), int(h)))
 
 
@@ -229,6 +236,38 @@ def bgr_frames_to_pal8(frames, row_pad=0, frame_pad=0):
     return out
 
 
+def gif_frame_bytes(frame):
+    """Host-only: `total` of a FRAME_GIF frame, its length in bytes (poppy_gif_frame_bytes: the first four bytes, little-endian)."""
+    f = np.ascontiguousarray(frame, np.uint8)
+    if f.size < 4:
+        raise PoppyError("gif_frame_bytes: a coded frame has at least four bytes")
+    return int(lib().poppy_gif_frame_bytes(_p(f)))
+
+
+def _gif_frame(call, name, w, h):
+    out = np.empty(max(frame_bytes(FRAME_GIF, w, h), 4), np.uint8)
+    rc = call(out)
+    if rc:
+        raise PoppyError(f"{name}: {rc}")
+    return out[:gif_frame_bytes(out)].copy()
+
+
+def pal8_to_gif_frame(pal8, w, h):
+    """Host-only: the FRAME_GIF frame of a flat PAL8 frame (poppy_pal8_to_gif_frame): `total`, the palette, the LZW-coded indices as GIF image data; a flat
+    uint8 array of exactly `total` bytes."""
+    a = np.ascontiguousarray(pal8, np.uint8)
+    if a.size != w * h + 768:
+        raise PoppyError("pal8_to_gif_frame: a PAL8 frame has w * h + 768 bytes")
+    return _gif_frame(lambda out: lib().poppy_pal8_to_gif_frame(_p(a), int(w), int(h), _p(out)), "poppy_pal8_to_gif_frame", w, h)
+
+
+def bgr_to_gif_frame(bgr):
+    """Host-only: the FRAME_GIF frame of an HxWx3 BGR frame (poppy_bgr_to_gif_frame = bgr_to_pal8, then pal8_to_gif_frame)."""
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    return _gif_frame(lambda out: lib().poppy_bgr_to_gif_frame(_p(a), w * 3, w, h, _p(out)), "poppy_bgr_to_gif_frame", w, h)
+
+
 def pal8_to_bgr(frame, w, h):
     """palette[index] of a flat PAL8 frame, as an HxWx3 BGR array (what a viewer of the frame sees)."""
     f = np.asarray(frame, np.uint8)
@@ -236,7 +275,9 @@ def pal8_to_bgr(frame, w, h):
 
 
 def _frame_view(ptr, w, h, stride, fmt):
-    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ.  A view: valid during the callback."""
+    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF.  A view: valid during the callback."""
+    if fmt == FRAME_GIF:                                        # a coded frame: its own length, not the capacity
+        return np.ctypeslib.as_array(ptr, shape=(int(lib().poppy_gif_frame_bytes(ptr)),))
     if fmt in (FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ):
         return np.ctypeslib.as_array(ptr, shape=(frame_bytes(fmt, w, h),))
     return np.ctypeslib.as_array(ptr, shape=(h, stride))[:, :w * 3].reshape(h, w, 3)
@@ -481,7 +522,7 @@ class Pool:
         self.frame_format = FRAME_BGR
 
     def set_frame_format(self, fmt):
-        """FRAME_BGR, FRAME_I420, FRAME_PAL8 or FRAME_PAL8_SEQ (one palette per pair) for every context of the pool (poppy_hip_pool_set_frame_format); PoppyError with the status while submitted
+        """FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ (one palette per pair) or FRAME_GIF for every context of the pool (poppy_hip_pool_set_frame_format); PoppyError with the status while submitted
         batches have not been waited for."""
         rc = lib().poppy_hip_pool_set_frame_format(self.h, int(fmt))
         if rc:
@@ -630,9 +671,20 @@ class Context:
 
     def set_frame_format(self, fmt):
         """FRAME_BGR (default), FRAME_I420, FRAME_PAL8 or FRAME_PAL8_SEQ (one palette for all frames of a call, which are handed over when the last
-        one is rendered): the format of every frame handed to a writer (poppy_hip_set_frame_format).  Under I420 and both PAL8 formats the collecting wrappers return flat uint8 arrays of frame_bytes(format, W, H)."""
+        one is rendered): the format of every frame handed to a writer (poppy_hip_set_frame_format).  Under I420 and both PAL8 formats the collecting wrappers return flat uint8 arrays of frame_bytes(format, W, H).
+        FRAME_GIF: PAL8 frames with the indices LZW-coded on the GPU; the wrappers return flat arrays of each frame's own length (gif_frame_bytes)."""
         self._chk(lib().poppy_hip_set_frame_format(self.h, int(fmt)), "set_frame_format")
         self.frame_format = int(fmt)
+
+    def pal8_to_gif_frame(self, pal8, w, h):
+        """The FRAME_GIF frame of a flat PAL8 frame, coded on this context's GPU (poppy_hip_pal8_to_gif_frame: upload, the two kernels, download): the bytes of
+        the host's pal8_to_gif_frame."""
+        a = np.ascontiguousarray(pal8, np.uint8)
+        if a.size != w * h + 768:
+            raise PoppyError("pal8_to_gif_frame: a PAL8 frame has w * h + 768 bytes")
+        out = np.empty(max(frame_bytes(FRAME_GIF, w, h), 4), np.uint8)
+        self._chk(lib().poppy_hip_pal8_to_gif_frame(self.h, _p(a), int(w), int(h), _p(out)), "pal8_to_gif_frame")
+        return out[:gif_frame_bytes(out)].copy()
 
     def close(self):
         if self.h:

@@ -47,6 +47,10 @@ struct FrameSlot {
     uint8_t* i420 = nullptr;                        // the frame as I420 for the writer (allocated when the format is I420 and a pair is there; kept until the pair's buffers go)
     uint8_t* pal8 = nullptr;                        // the frame as PAL8 for the writer, and the conversion's tables (kernels.h: kPal8TableBytes) — the slot's own,
     uint8_t* pal8_tables = nullptr;                 // because the conversions of frames in flight run beside each other (allocated like i420; the stream and event live as long as the context)
+    uint8_t* gif = nullptr;                         // POPPY_FRAME_GIF: the coded frame for the writer (its capacity: poppy_frame_bytes), the coder's scratch (kernels.h: gif_scratch_bytes)
+    uint8_t* gif_scratch = nullptr;                 // ... and a word of mapped pinned memory that k_gif_pack stores the frame's length into: the host reads it when `done`
+    uint32_t* gif_total = nullptr;                  // has fired and copies that many bytes (the PAL8 frame the coder reads is the slot's pal8)
+    void* gif_total_dev = nullptr;
     hipStream_t fmt_stream = nullptr;               // chained PAL8 / PAL8_SEQ frames: the conversion's side stream (the chain goes on from the unsharp: enqueue_body)
     hipEvent_t bgr_done = nullptr;                  // ... and the event that rides on that unsharp
     hipEvent_t downloaded = nullptr;                // completes when the last download of this slot's `out` towards the writer has read it

@@ -8,8 +8,10 @@
 //   POPPY_SINK_Y4M420  one YUV4MPEG2 file, C420jpeg, that takes I420 frames as they are (poppy_hip_set_frame_format)
 //   POPPY_SINK_GIF   one animated GIF89a file that takes PAL8 frames as they are: a local colour table and one LZW image per frame
 //   POPPY_SINK_GIF_GLOBAL  the same for PAL8_SEQ frames: the first frame's palette as the global colour table, local tables only where a frame's palette differs
+//   POPPY_SINK_GIF_CODED   POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames, whose image data arrives coded (frame_gif.cpp, kernels_frame_gif.hip): nothing is coded here
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "../../include/poppy_hip.h"
+#include "gif_lzw.h"
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -32,47 +34,25 @@ struct poppy_sink {
 
 namespace {
 
-// GIF's variable-width LZW (minimum code size 8): codes 0..255 the bytes, 256 clear, 257 end, strings from 258; the width grows from 9 to 12 bits
-// when the entry just added is the first that needs the next width (what decoders mirror one entry behind), and a clear code restarts the table
-// when it is full.  The packed bits go out in sub-blocks of at most 255 bytes.
+// One image's LZW data: the coder of gif_lzw.h (codes, width growth and the restart of a full table are stated there), closed by the end code; the packed bits go
+// out in sub-blocks of at most 255 bytes, then the block terminator.
 struct GifLzw {
     FILE* f;
     bool ok = true;
-    uint32_t acc = 0; int n_acc = 0;
     uint8_t block[255]; int n_block = 0;
-    static constexpr int kHash = 8192;                      // open addressing over (prefix << 8 | byte); at most 3838 strings live
-    std::vector<uint32_t> key; std::vector<uint16_t> val;
-    explicit GifLzw(FILE* file) : f(file), key(kHash), val(kHash) {}
+    poppy_hip::GifLzwCoder coder;
+    explicit GifLzw(FILE* file) : f(file) {}
     void flush_block() {
         if (!n_block) return;
         const uint8_t len = (uint8_t)n_block;
         if (fwrite(&len, 1, 1, f) != 1 || fwrite(block, 1, (size_t)n_block, f) != (size_t)n_block) ok = false;
         n_block = 0;
     }
-    void put(int code, int width) {
-        acc |= (uint32_t)code << n_acc; n_acc += width;
-        while (n_acc >= 8) { block[n_block++] = (uint8_t)acc; acc >>= 8; n_acc -= 8; if (n_block == 255) flush_block(); }
-    }
-    void reset() { std::fill(key.begin(), key.end(), 0xffffffffu); }
+    void operator()(uint8_t byte) { block[n_block++] = byte; if (n_block == 255) flush_block(); }
     void encode(const uint8_t* px, size_t n) {
-        const int kClear = 256, kEnd = 257;
-        int width = 9, next = 258;
-        reset();
-        put(kClear, width);
-        int prefix = px[0];
-        for (size_t i = 1; i < n; ++i) {
-            const uint32_t k = ((uint32_t)prefix << 8) | px[i];
-            uint32_t h = (k * 2654435761u) >> 19;            // 13 bits
-            while (key[h] != 0xffffffffu && key[h] != k) h = (h + 1) & (kHash - 1);
-            if (key[h] == k) { prefix = val[h]; continue; }
-            put(prefix, width);
-            if (next == 4096) { put(kClear, width); reset(); width = 9; next = 258; }
-            else { key[h] = k; val[h] = (uint16_t)next; if (next == (1 << width)) ++width; ++next; }
-            prefix = px[i];
-        }
-        put(prefix, width);
-        put(kEnd, width);
-        if (n_acc) { block[n_block++] = (uint8_t)acc; acc = 0; n_acc = 0; if (n_block == 255) flush_block(); }
+        const int width = coder.run(px, n, *this);
+        coder.put(poppy_hip::GifLzwCoder::kEnd, width, *this);
+        coder.flush(*this);
         flush_block();
         const uint8_t zero = 0;
         if (fwrite(&zero, 1, 1, f) != 1) ok = false;         // the block terminator
@@ -105,6 +85,16 @@ bool gif_frame(poppy_sink* s, const uint8_t* pal8) {
     return z.ok;
 }
 
+// a POPPY_FRAME_GIF frame: the palette as the local table, then the frame's image data as it is
+bool gif_coded_frame(poppy_sink* s, const uint8_t* frame) {
+    const int w = s->w, h = s->h;
+    const size_t total = poppy_gif_frame_bytes(frame);
+    if (total < 772 + 3 || total > poppy_frame_bytes(POPPY_FRAME_GIF, w, h) || frame[772] != 8 || frame[total - 1] != 0) return false;
+    const uint8_t gce[8] = {0x21, 0xF9, 4, 0, (uint8_t)(s->delay_cs & 255), (uint8_t)(s->delay_cs >> 8), 0, 0};
+    const uint8_t desc[10] = {0x2C, 0, 0, 0, 0, (uint8_t)(w & 255), (uint8_t)(w >> 8), (uint8_t)(h & 255), (uint8_t)(h >> 8), 0x87};
+    return fwrite(gce, 1, 8, s->f) == 8 && fwrite(desc, 1, 10, s->f) == 10 && fwrite(frame + 4, 1, total - 4, s->f) == total - 4;
+}
+
 }  // namespace
 
 extern "C" {
@@ -115,6 +105,10 @@ size_t poppy_frame_bytes(int format, int width, int height) {
     if (format == POPPY_FRAME_BGR) return w * h * 3;
     if (format == POPPY_FRAME_I420) return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2);
     if (format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ) return w * h + 768;
+    if (format == POPPY_FRAME_GIF) {                        // the capacity (include/poppy_hip.h has the derivation): every segment at its bound, framed
+        const size_t segments = (w * h + POPPY_GIF_SEGMENT_PIXELS - 1) / POPPY_GIF_SEGMENT_PIXELS, payload = segments * POPPY_GIF_SEGMENT_BYTES;
+        return 772 + 1 + payload + (payload + 254) / 255 + 1;
+    }
     return 0;
 }
 
@@ -147,7 +141,7 @@ int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, 
 }
 
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den) {
-    if (!path || width <= 0 || height <= 0 || (format != POPPY_SINK_GIF && format != POPPY_SINK_GIF_GLOBAL && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
+    if (!path || width <= 0 || height <= 0 || (format != POPPY_SINK_GIF && format != POPPY_SINK_GIF_GLOBAL && format != POPPY_SINK_GIF_CODED && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
     poppy_sink* s = new poppy_sink();
     s->format = format; s->w = width; s->h = height; s->path = path;
     if (format == POPPY_SINK_PPM) {
@@ -171,7 +165,7 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
         if (bad || !seen) { delete s; return nullptr; }
         s->path = head; s->tail = tail;
     }
-    if ((format == POPPY_SINK_GIF || format == POPPY_SINK_GIF_GLOBAL) && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen: every write fails, close says so
+    if ((format == POPPY_SINK_GIF || format == POPPY_SINK_GIF_GLOBAL || format == POPPY_SINK_GIF_CODED) && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen: every write fails, close says so
     if (format != POPPY_SINK_PPM) {
         s->f = fopen(path, "wb");
         if (!s->f) { delete s; return nullptr; }
@@ -179,11 +173,11 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
             fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C444 XCOLORRANGE=FULL\n", width, height, fps_num > 0 ? fps_num : 30, fps_den > 0 ? fps_den : 1);
         else if (format == POPPY_SINK_Y4M420)
             fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=FULL\n", width, height, fps_num > 0 ? fps_num : 30, fps_den > 0 ? fps_den : 1);
-        else if (format == POPPY_SINK_GIF || format == POPPY_SINK_GIF_GLOBAL) {
+        else if (format == POPPY_SINK_GIF || format == POPPY_SINK_GIF_GLOBAL || format == POPPY_SINK_GIF_CODED) {
             const long long num = fps_num > 0 ? fps_num : 30, den = fps_den > 0 ? fps_den : 1;
             const long long cs = (den * 100 + num / 2) / num;
             s->delay_cs = (int)(cs < 1 ? 1 : cs > 65535 ? 65535 : cs);
-            if (format == POPPY_SINK_GIF && !gif_head(s, nullptr)) s->failed = true;      // (GIF_GLOBAL: with the first frame)
+            if (format != POPPY_SINK_GIF_GLOBAL && !gif_head(s, nullptr)) s->failed = true;      // (GIF_GLOBAL: with the first frame)
         }
     }
     s->row.resize((size_t)width * 3);
@@ -194,6 +188,11 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
     poppy_sink* s = (poppy_sink*)user;
     if (!s || s->failed) return;
     // (an I420 frame comes with stride == width: the BGR sinks refuse it, and the I420 sink refuses anything else)
+    // (a coded frame comes with stride == 0: every other sink refuses it below, and the coded sink refuses anything else)
+    if (s->format == POPPY_SINK_GIF_CODED) {
+        if (!bgr || width != s->w || height != s->h || stride != 0 || !gif_coded_frame(s, bgr)) s->failed = true; else ++s->frames;
+        return;
+    }
     const bool i420 = s->format == POPPY_SINK_Y4M420, pal8 = s->format == POPPY_SINK_GIF || s->format == POPPY_SINK_GIF_GLOBAL;
     if (!bgr || width != s->w || height != s->h || ((i420 || pal8) ? stride != (size_t)width : stride < (size_t)width * 3)) { s->failed = true; return; }
     FILE* f = s->f;
@@ -248,7 +247,7 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
 int poppy_sink_close(poppy_sink* s) {
     if (!s) return POPPY_E_ARG;
     if (s->f && s->format == POPPY_SINK_GIF_GLOBAL && !s->failed && !s->head_written && !gif_head(s, nullptr)) s->failed = true;      // no frame came: GIF's empty file
-    if (s->f && (s->format == POPPY_SINK_GIF || s->format == POPPY_SINK_GIF_GLOBAL) && !s->failed && fputc(0x3B, s->f) == EOF) s->failed = true;      // the trailer
+    if (s->f && (s->format == POPPY_SINK_GIF || s->format == POPPY_SINK_GIF_GLOBAL || s->format == POPPY_SINK_GIF_CODED) && !s->failed && fputc(0x3B, s->f) == EOF) s->failed = true;      // the trailer
     const int n = s->failed ? POPPY_E_DEVICE : s->frames;
     if (s->f) fclose(s->f);
     delete s;

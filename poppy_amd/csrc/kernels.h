@@ -1,5 +1,6 @@
 // kernels.h — launchers of the HIP kernels behind libpoppy_hip.so (gfx950 only).
 #pragma once
+#include "../../include/poppy_hip.h"
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
@@ -221,5 +222,14 @@ constexpr size_t kPal8SeqTableOffset = (size_t)32768 * 32, kPal8SeqPaletteOffset
 void launch_pal8_seq_pass(const uint8_t* src, uint8_t* store, uint8_t* seq_tables, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
 void launch_pal8_seq_build(uint8_t* seq_tables, hipStream_t s);
 void launch_pal8_seq_remap(const uint8_t* src, const uint8_t* seq_tables, uint8_t* dst, int w, int h, hipStream_t s);
+
+// a PAL8 frame on the device (w * h index bytes, 4-byte aligned, then the palette) -> POPPY_FRAME_GIF (kernels_frame_gif.hip; the format: include/poppy_hip.h), two
+// dispatches on one stream: the LZW coding, a segment per wave, into `scratch` (gif_scratch_bytes: a slot of kGifSlotBytes per segment, then the segments' byte
+// lengths), and the gather into `frame` (poppy_frame_bytes(POPPY_FRAME_GIF, w, h) bytes) with the sub-block framing, the palette and `total`; total_host (optional):
+// a word of mapped pinned host memory that receives `total` too.  `done` (optional) rides on the second dispatch.
+constexpr size_t kGifSlotBytes = ((size_t)POPPY_GIF_SEGMENT_BYTES + 3) & ~(size_t)3;
+size_t gif_scratch_bytes(int w, int h);
+void launch_gif_lzw(const uint8_t* pal8, uint8_t* scratch, int w, int h, hipStream_t s);
+void launch_gif_pack(const uint8_t* pal8, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
 
 }  // namespace poppy_hip

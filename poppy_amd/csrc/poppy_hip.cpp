@@ -94,8 +94,10 @@ static void free_pair(poppy_hip_ctx* c) {
         void* fb[] = {f.tr1, f.tr2, f.out, f.pyrL, f.pyrR, f.pyrM, f.pyrB, f.tmp, f.diff, f.unsharpF, f.triMap};
         for (void* b : fb) if (b) (void)hipFree(b);
         f.tr1 = f.tr2 = f.out = nullptr; f.pyrL = f.pyrR = f.pyrM = f.pyrB = f.tmp = f.diff = f.unsharpF = nullptr; f.triMap = nullptr;
-        for (uint8_t* b : {f.i420, f.pal8, f.pal8_tables}) if (b) (void)hipFree(b);
-        f.i420 = f.pal8 = f.pal8_tables = nullptr;
+        for (uint8_t* b : {f.i420, f.pal8, f.pal8_tables, f.gif, f.gif_scratch}) if (b) (void)hipFree(b);
+        f.i420 = f.pal8 = f.pal8_tables = f.gif = f.gif_scratch = nullptr;
+        if (f.gif_total) (void)hipHostFree(f.gif_total);
+        f.gif_total = nullptr; f.gif_total_dev = nullptr;
     }
     for (FrameSlot& f : c->slots) {
         if (f.body) { (void)hipGraphExecDestroy(f.body); f.body = nullptr; }
@@ -249,7 +251,14 @@ static int alloc_pal8_tables(poppy_hip_ctx* c, uint8_t** tables) {
 
 static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H <= (unsigned long long)POPPY_PAL8_MAX_PIXELS; }
 static bool is_pal8(int format) { return format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ; }
-constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8 and POPPY_FRAME_PAL8_SEQ take frames of at most 2^24 pixels";
+constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF take frames of at most 2^24 pixels";
+constexpr const char* kGifSizeMsg = "POPPY_FRAME_GIF takes frames of at most 65535 pixels in width and height";
+// why `format` refuses a W x H frame, or null: checked on the arguments alone, before anything is allocated or any state changes
+static const char* format_refuses(int format, int W, int H) {
+    if ((is_pal8(format) || format == POPPY_FRAME_GIF) && !pal8_fits(W, H)) return kPal8SizeMsg;
+    if (format == POPPY_FRAME_GIF && (W > 65535 || H > 65535)) return kGifSizeMsg;
+    return nullptr;
+}
 
 // a slot's conversion side stream and the event that rides on its unsharp (PAL8 and PAL8_SEQ; they live as long as the context)
 static int alloc_slot_side(poppy_hip_ctx* c, FrameSlot& f) {
@@ -291,7 +300,24 @@ static int alloc_slot_pal8_seq(poppy_hip_ctx* c) {
     return POPPY_OK;
 }
 
+// GIF: PAL8's buffers (the coder reads the slot's PAL8 frame) and the coded frame, the coder's scratch and the pinned length word
+static int alloc_slot_gif(poppy_hip_ctx* c) {
+    if (const char* why = format_refuses(POPPY_FRAME_GIF, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    { int rc = alloc_slot_pal8(c); if (rc) return rc; }
+    for (FrameSlot& f : c->slots) {
+        if (!f.gif) HIPCHK(c, hipMalloc((void**)&f.gif, poppy_frame_bytes(POPPY_FRAME_GIF, c->W, c->H) + 16));
+        if (!f.gif_scratch) HIPCHK(c, hipMalloc((void**)&f.gif_scratch, gif_scratch_bytes(c->W, c->H)));
+        if (!f.gif_total) {
+            HIPCHK(c, hipHostMalloc((void**)&f.gif_total, 64, hipHostMallocMapped));
+            HIPCHK(c, hipHostGetDevicePointer(&f.gif_total_dev, f.gif_total, 0));
+            *f.gif_total = 0;
+        }
+    }
+    return POPPY_OK;
+}
+
 static int alloc_slot_format(poppy_hip_ctx* c) {
+    if (c->frame_format == POPPY_FRAME_GIF) return alloc_slot_gif(c);
     return c->frame_format == POPPY_FRAME_I420 ? alloc_slot_i420(c) : c->frame_format == POPPY_FRAME_PAL8 ? alloc_slot_pal8(c) :
            c->frame_format == POPPY_FRAME_PAL8_SEQ ? alloc_slot_pal8_seq(c) : POPPY_OK;
 }
@@ -299,7 +325,7 @@ static int alloc_slot_format(poppy_hip_ctx* c) {
 int alloc_pair(poppy_hip_ctx* c, int W, int H) {
     { int rc = drain_frames(c); if (rc) return rc; }              // every pair loader comes through here: no frame still reads the old pair
     // PAL8 takes frames of at most 2^24 pixels: refused before anything is allocated or any state changes, so the context keeps the pair it had
-    if (is_pal8(c->frame_format) && !pal8_fits(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
+    if (const char* why = format_refuses(c->frame_format, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     if (c->W == W && c->H == H && c->c1) return alloc_slot_format(c);      // (allocates only what is missing: nothing, unless an earlier attempt failed half-way)
     free_pair(c);
     c->pyr_forms.clear();
@@ -708,11 +734,13 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
     const int fmt = write ? c->frame_format : POPPY_FRAME_BGR;
     // (every way to this format with a pair allocates the slots' buffers — alloc_pair, poppy_hip_set_frame_format — or refuses: a frame is never converted into nothing)
     for (const FrameSlot& f : c->slots)
-        if ((fmt == POPPY_FRAME_I420 && !f.i420) || (fmt == POPPY_FRAME_PAL8 && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) ||
+        if ((fmt == POPPY_FRAME_I420 && !f.i420) || ((fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF) && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) ||
+            (fmt == POPPY_FRAME_GIF && !(f.gif && f.gif_scratch && f.gif_total)) ||
             (seq && !(c->seq_open && c->seq_tables && f.fmt_stream && f.bgr_done)))
             return fail(c, POPPY_E_STATE, "the frame format's buffers are not allocated for this pair");
-    const size_t row = fmt != POPPY_FRAME_BGR ? (size_t)W : (size_t)W * 3, frame_bytes = poppy_frame_bytes(fmt, W, H);
-    auto frame_of = [fmt](const FrameSlot& f) -> const uint8_t* { return fmt == POPPY_FRAME_I420 ? f.i420 : fmt == POPPY_FRAME_PAL8 ? f.pal8 : f.out; };
+    // (GIF: a coded frame goes to the writer with stride 0; frame_bytes is its capacity, which sizes the pinned ring — a frame's copy moves its own length)
+    const size_t row = fmt == POPPY_FRAME_GIF ? 0 : fmt != POPPY_FRAME_BGR ? (size_t)W : (size_t)W * 3, frame_bytes = poppy_frame_bytes(fmt, W, H);
+    auto frame_of = [fmt](const FrameSlot& f) -> const uint8_t* { return fmt == POPPY_FRAME_I420 ? f.i420 : fmt == POPPY_FRAME_PAL8 ? f.pal8 : fmt == POPPY_FRAME_GIF ? f.gif : f.out; };
     static const int ring_pref = getenv("POPPY_HIP_RING") ? std::max(1, atoi(getenv("POPPY_HIP_RING"))) : 3;
     const int R = std::min({poppy_hip_ctx::kStageRing, ring_pref, (int)c->slots.size()});
     const size_t slot_bytes = (frame_bytes + 255) & ~(size_t)255;     // ring slots start on 256-byte boundaries
@@ -736,7 +764,7 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
     const double w0[4] = {c->wait_ms[0], c->wait_ms[1], c->wait_ms[2], c->wait_ms[3]};
     auto lap = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
     std::vector<int> slot_of(n, -1);
-    const int pal8_lag = fmt == POPPY_FRAME_PAL8 ? std::max(0, (int)c->slots.size() - 2) : 0;
+    const int pal8_lag = fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF ? std::max(0, (int)c->slots.size() - 2) : 0;
     int issued = 0;                                               // downloads queued so far (frames 0 .. issued-1)
     // Round 6: a frame copy goes to the stream of its pinned ring buffer, which carries nothing else, and NO event is recorded behind it — whoever needs the copy
     // finished synchronises that stream.  An event record behind a copy is a marker packet that waits, in one of the process's four hardware queues, for the copy's
@@ -748,11 +776,17 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
         FrameSlot& f = c->slots[slot_of[k]];
         const int r = k % R;
         const auto t0 = clk::now();
-        hipError_t e = dev_wait ? hipStreamWaitEvent(c->dl_stream, f.done, 0) : hipEventSynchronize(f.done);
+        // (GIF: the host waits in every form: k_gif_pack has stored the frame's length into the slot's pinned word by then, and the copy moves that many bytes)
+        hipError_t e = dev_wait && fmt != POPPY_FRAME_GIF ? hipStreamWaitEvent(c->dl_stream, f.done, 0) : hipEventSynchronize(f.done);
         ms_done += lap(t0);
+        size_t copy_bytes = frame_bytes;
+        if (fmt == POPPY_FRAME_GIF && e == hipSuccess) {
+            copy_bytes = *(volatile uint32_t*)f.gif_total;
+            if (copy_bytes < 776 || copy_bytes > frame_bytes) { c->err = "the coded frame's length is outside its bounds"; rc = POPPY_E_DEVICE; return false; }
+        }
         if (dl_streams) {
             if (e == hipSuccess && !c->dl_ring[r]) e = hipStreamCreateWithFlags(&c->dl_ring[r], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, frame_of(f), frame_bytes, hipMemcpyDeviceToHost, c->dl_ring[r]);
+            if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, frame_of(f), copy_bytes, hipMemcpyDeviceToHost, c->dl_ring[r]);
             f.dl_pending = true; f.dl_ring_idx = r;
             if (e != hipSuccess) { c->err = std::string("frame download: ") + hipGetErrorString(e); rc = POPPY_E_DEVICE; return false; }
             return true;
@@ -762,7 +796,7 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
         static const bool skip_copy = getenv("POPPY_DL_SKIP_COPY") != nullptr;      // timing experiment: every wait and event of the writer path, no bytes moved (wrong frames)
         if (!skip_copy)
 #endif
-        if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, frame_of(f), frame_bytes, hipMemcpyDeviceToHost, c->dl_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, frame_of(f), copy_bytes, hipMemcpyDeviceToHost, c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(c->dl_done[r], c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(f.downloaded, c->dl_stream);          // the slot's own: ring events are re-recorded every R frames
         f.dl_pending = true;
@@ -924,7 +958,9 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     // PAL8_SEQ (seq_dst: the frame's place in the sequence store, never set in a captured body): the pass takes PAL8's place, on the side stream too — it is short,
     // but the chain needs nothing of it.
     const int fmt = frame_wants_format(c);
-    const bool side = (fmt == POPPY_FRAME_PAL8 || seq_dst) && chained && done && !tm;
+    // GIF is PAL8 with the two coding dispatches behind the index plane, wherever PAL8's run; `done` rides on the second.
+    const bool pal8_like = fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF;
+    const bool side = (pal8_like || seq_dst) && chained && done && !tm;
     launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s,
                    side ? f.bgr_done : (fmt != POPPY_FRAME_BGR || seq_dst) ? nullptr : done, c->levels[0].pitch);
     rec(POPPY_PYR_UNSHARP, 0, W < 2 || H < 2);
@@ -932,15 +968,22 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     if (fmt == POPPY_FRAME_I420) {
         launch_bgr_to_i420(f.out, f.i420, W, H, s, done);
         if (tm) tm->mark("frame_format");
-    } else if (fmt == POPPY_FRAME_PAL8) {
+    } else if (pal8_like) {
+        const bool gif = fmt == POPPY_FRAME_GIF;
         hipStream_t fs = side ? f.fmt_stream : s;
         if (side) HIPCHK(c, hipStreamWaitEvent(fs, f.bgr_done, 0));
         launch_pal8_hist(f.out, f.pal8_tables, W, H, fs);
         if (tm) tm->mark("pal8_hist");
         launch_pal8_build(f.pal8_tables, f.pal8, W, H, fs);
         if (tm) tm->mark("pal8_build");
-        launch_pal8_remap(f.out, f.pal8_tables, f.pal8, W, H, fs, done);
-        if (tm) tm->mark("frame_format");                      // (under PAL8: the index plane alone)
+        launch_pal8_remap(f.out, f.pal8_tables, f.pal8, W, H, fs, gif ? nullptr : done);
+        if (tm) tm->mark("frame_format");                      // (under PAL8 and GIF: the index plane alone)
+        if (gif) {
+            launch_gif_lzw(f.pal8, f.gif_scratch, W, H, fs);
+            if (tm) tm->mark("gif_lzw");
+            launch_gif_pack(f.pal8, f.gif_scratch, f.gif, (uint32_t*)f.gif_total_dev, W, H, fs, done);
+            if (tm) tm->mark("gif_pack");
+        }
     } else if (seq_dst) {
         hipStream_t fs = side ? f.fmt_stream : s;
         if (side) HIPCHK(c, hipStreamWaitEvent(fs, f.bgr_done, 0));
@@ -1250,6 +1293,29 @@ static int prepare_ahead(poppy_hip_ctx* c, const FramePlan& plan, double mask) {
     return rc;
 }
 
+// a PAL8 frame in device memory -> its POPPY_FRAME_GIF frame in `host` (exactly `total` bytes), on the context's stream and waited for: the frames that no slot renders,
+// and poppy_hip_pal8_to_gif_frame.  The buffers live for the call.
+static int gif_from_device_pal8(poppy_hip_ctx* c, const uint8_t* d_pal8, int W, int H, std::vector<uint8_t>& host) {
+    const size_t cap = poppy_frame_bytes(POPPY_FRAME_GIF, W, H);
+    uint8_t *work = nullptr, *frame = nullptr;
+    hipError_t e = hipMalloc((void**)&work, gif_scratch_bytes(W, H));
+    if (e == hipSuccess) e = hipMalloc((void**)&frame, cap + 16);
+    uint32_t total = 0;
+    if (e == hipSuccess) {
+        launch_gif_lzw(d_pal8, work, W, H, c->stream);
+        launch_gif_pack(d_pal8, work, frame, nullptr, W, H, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && (total < 776 || total > cap)) { (void)hipFree(work); (void)hipFree(frame); return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds"); }
+    if (e == hipSuccess) { host.resize(total); e = hipMemcpy(host.data(), frame, total, hipMemcpyDeviceToHost); }
+    if (work) (void)hipFree(work);
+    if (frame) (void)hipFree(frame);
+    if (e != hipSuccess) { c->err = std::string("GIF frame coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    return POPPY_OK;
+}
+
 int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride, int n_copies) {
     if (c->frame_format == POPPY_FRAME_PAL8_SEQ) {                 // the copies are the sequence: the host statement on the BGR frame
         std::vector<uint8_t> bgr((size_t)W * H * 3);
@@ -1264,10 +1330,10 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::ve
         *stride = (size_t)W * 3;
         HIPCHK(c, hipMemcpyAsync(host.data(), d_bgr, host.size(), hipMemcpyDeviceToHost, c->stream));
     } else {
-        const bool pal8 = c->frame_format == POPPY_FRAME_PAL8;
-        if (pal8 && !pal8_fits(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
+        const bool gif = c->frame_format == POPPY_FRAME_GIF, pal8 = c->frame_format == POPPY_FRAME_PAL8 || gif;
+        if (const char* why = format_refuses(c->frame_format, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
         if (pal8 && !c->pal8_scratch_tables) { int rc = alloc_pal8_tables(c, &c->pal8_scratch_tables); if (rc) return rc; }
-        const size_t bytes = poppy_frame_bytes(c->frame_format, W, H);
+        const size_t bytes = poppy_frame_bytes(gif ? POPPY_FRAME_PAL8 : c->frame_format, W, H);
         if (bytes + 16 > c->i420_scratch_bytes) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (c->i420_scratch) (void)hipFree(c->i420_scratch);
@@ -1283,6 +1349,7 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::ve
             launch_pal8_remap(d_bgr, c->pal8_scratch_tables, c->i420_scratch, W, H, c->stream);
         } else launch_bgr_to_i420(d_bgr, c->i420_scratch, W, H, c->stream);
         HIPCHK(c, hipGetLastError());
+        if (gif) { *stride = 0; return gif_from_device_pal8(c, c->i420_scratch, W, H, host); }
         HIPCHK(c, hipMemcpyAsync(host.data(), c->i420_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1293,11 +1360,13 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
     *out_stride = stride;
     *status = POPPY_OK;
     if (c->frame_format == POPPY_FRAME_BGR) return bgr;
+    if (const char* why = format_refuses(c->frame_format, W, H)) { *status = fail(c, POPPY_E_UNSUPPORTED, why); return nullptr; }
     tmp.resize(poppy_frame_bytes(c->frame_format, W, H));
     const int rc = c->frame_format == POPPY_FRAME_PAL8_SEQ ? pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, tmp.data()) :
+                   c->frame_format == POPPY_FRAME_GIF ? poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data()) :
                    c->frame_format == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
     if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
-    *out_stride = (size_t)W;
+    *out_stride = c->frame_format == POPPY_FRAME_GIF ? 0 : (size_t)W;
     return tmp.data();
 }
 
@@ -1638,12 +1707,29 @@ int poppy_hip_timing_summary(poppy_hip_ctx* c, const char** names, float* total_
 
 int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
     if (!c) return POPPY_E_ARG;
-    if (format != POPPY_FRAME_BGR && format != POPPY_FRAME_I420 && !is_pal8(format)) return fail(c, POPPY_E_ARG, "unknown frame format");
+    if (format != POPPY_FRAME_BGR && format != POPPY_FRAME_I420 && !is_pal8(format) && format != POPPY_FRAME_GIF) return fail(c, POPPY_E_ARG, "unknown frame format");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = drain_frames(c); if (rc) return rc; }
-    if (is_pal8(format) && c->c1 && !pal8_fits(c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
+    if (c->c1) if (const char* why = format_refuses(format, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     c->frame_format = format;
     return c->c1 ? alloc_slot_format(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
+}
+
+int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* c, const uint8_t* pal8, int W, int H, uint8_t* dst) {
+    if (!c) return POPPY_E_ARG;
+    if (!pal8 || !dst || W <= 0 || H <= 0) return fail(c, POPPY_E_ARG, "bad arguments");
+    if (const char* why = format_refuses(POPPY_FRAME_GIF, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = poppy_frame_bytes(POPPY_FRAME_PAL8, W, H);
+    uint8_t* d_pal8 = nullptr;
+    HIPCHK(c, hipMalloc((void**)&d_pal8, bytes + 16));
+    std::vector<uint8_t> host;
+    int rc = POPPY_OK;
+    if (hipMemcpy(d_pal8, pal8, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, POPPY_E_DEVICE, "upload of the PAL8 frame failed");
+    if (rc == POPPY_OK) rc = gif_from_device_pal8(c, d_pal8, W, H, host);
+    (void)hipFree(d_pal8);
+    if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
+    return rc;
 }
 
 int poppy_hip_render_many(poppy_hip_ctx* c, const double* shape, const double* mask, int n, int chain, poppy_write_cb write, void* user) {

@@ -1,4 +1,4 @@
-"""BGR against I420 against PAL8 against PAL8_SEQ frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run
+"""BGR against I420 against PAL8 against PAL8_SEQ against GIF frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run
 times each row once per format, one format right after the other, and the rows report min / median / max over --runs runs.
 
   pool_1080p    bench.py's `value` set-up: a pool of --contexts contexts, --steps queued batches of six 1080p pairs from device images, 60 chained
@@ -9,11 +9,12 @@ times each row once per format, one format right after the other, and the rows r
   chained_frame one context, the 60 chained frames of a resident pair to the counting writer (what the extra launch costs a chained frame)
   d2h_ceiling   pinned device-to-host copies of one frame's bytes, back to back on one stream (BGR, I420 and PAL8 sizes at 1080p and 4K)
 and, at the end, the conversion kernels' own times in timing mode 1 at 1080p and 4K (I420: frame_format; PAL8: pal8_hist, pal8_build, frame_format = the index plane;
-PAL8_SEQ: pal8_seq_hist per frame, pal8_seq_build per sequence, frame_format = the index plane).  Under PAL8_SEQ a pair's (a call's) frames are handed over after its last
+PAL8_SEQ: pal8_seq_hist per frame, pal8_seq_build per sequence, frame_format = the index plane; GIF: PAL8's three, then gif_lzw and gif_pack).  Under PAL8_SEQ a pair's (a call's) frames are handed over after its last
 frame.
 
-    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq]
---formats leaves formats out (a library older than PAL8_SEQ: bgr,i420,pal8).  One JSON line at the end.
+    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif]
+--formats leaves formats out (a library older than GIF: bgr,i420,pal8,pal8_seq).  GIF's d2h_ceiling entry is its CAPACITY (poppy_frame_bytes); a frame's copy moves its own
+length, which depends on the content.  One JSON line at the end.
 """
 import argparse
 import json
@@ -27,7 +28,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poppy_amd import capi, synth  # noqa: E402
 
-ALL_FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420), ("pal8", capi.FRAME_PAL8), ("pal8_seq", capi.FRAME_PAL8_SEQ))
+ALL_FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420), ("pal8", capi.FRAME_PAL8), ("pal8_seq", capi.FRAME_PAL8_SEQ), ("gif", capi.FRAME_GIF))
 
 
 def pair_images(torch, dev, w, h, n):
@@ -74,7 +75,7 @@ def main():
     ap.add_argument("--steps-4k", type=int, default=3)
     ap.add_argument("--contexts", type=int, default=6)
     ap.add_argument("--rows", default="pool_1080p,pool_4k,job480,chained,chained_frame,d2h_ceiling")
-    ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq")
+    ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq,gif")
     a = ap.parse_args()
     rows = a.rows.split(",")
     FMTS = tuple((f, v) for f, v in ALL_FMTS if f in a.formats.split(","))
@@ -140,7 +141,7 @@ def main():
             ctx.reset(); ctx.render_many_counted(shapes, chain=True)
             t = {n: (ms, k) for n, ms, k in ctx.timing_summary()}
             ctx.set_timing(0)
-            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build")}
+            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build", "gif_lzw", "gif_pack")}
     for p in (pool, pool4):
         if p:
             p.close()
