@@ -1,9 +1,12 @@
 // context.h — the library's context (one per GPU) and the helpers shared by its translation units:
-//   poppy_hip.cpp   context life cycle, HBM layout, the per-frame path and the resident-pair API
-//   pair_setup.cpp  everything that happens once per pair: pre-ORB chain, ORB, matching, auto-align, margins
+//   poppy_hip.cpp     context life cycle, HBM layout, the per-frame path and the resident-pair API
+//   frame_format.cpp  everything that depends on the writer's frame format (frame_format.h): slot buffers, conversion launches, the palette sequence, the writer ring
+//   pair_setup.cpp    everything that happens once per pair: pre-ORB chain, ORB, matching, auto-align, margins
+//   image_list.cpp    poppy_hip_morph_list;  comm.cpp: pools and RCCL
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "foreground.h"
+#include "frame_format.h"
 #include "frame_plan.h"
 #include "kernels.h"
 #include "kernels_prefilter.h"
@@ -44,15 +47,7 @@ struct FrameSlot {
     hipEvent_t uploaded = nullptr;                  // the device copy is complete
     hipGraphExec_t body = nullptr;                  // pyrdown .. unsharp of this slot, captured once per pair geometry
     int body_format = POPPY_FRAME_BGR;              // ... with this format's conversion behind the unsharp (re-captured when that changes)
-    uint8_t* i420 = nullptr;                        // the frame as I420 for the writer (allocated when the format is I420 and a pair is there; kept until the pair's buffers go)
-    uint8_t* pal8 = nullptr;                        // the frame as PAL8 for the writer, and the conversion's tables (kernels.h: kPal8TableBytes) — the slot's own,
-    uint8_t* pal8_tables = nullptr;                 // because the conversions of frames in flight run beside each other (allocated like i420; the stream and event live as long as the context)
-    uint8_t* gif = nullptr;                         // POPPY_FRAME_GIF: the coded frame for the writer (its capacity: poppy_frame_bytes), the coder's scratch (kernels.h: gif_scratch_bytes)
-    uint8_t* gif_scratch = nullptr;                 // ... and a word of mapped pinned memory that k_gif_pack stores the frame's length into: the host reads it when `done`
-    uint32_t* gif_total = nullptr;                  // has fired and copies that many bytes (the PAL8 frame the coder reads is the slot's pal8)
-    void* gif_total_dev = nullptr;
-    hipStream_t fmt_stream = nullptr;               // chained PAL8 / PAL8_SEQ frames: the conversion's side stream (the chain goes on from the unsharp: enqueue_body)
-    hipEvent_t bgr_done = nullptr;                  // ... and the event that rides on that unsharp
+    SlotFormat fmt;                                 // the frame in the writer's format: buffers, side stream and event (frame_format.h)
     hipEvent_t downloaded = nullptr;                // completes when the last download of this slot's `out` towards the writer has read it
     bool dl_pending = false;                        // ... and whether such a download was issued since the slot was last rendered into
     int dl_ring_idx = -1;                           // POPPY_HIP_DL_STREAMS: the ring stream that carries that download
@@ -113,15 +108,9 @@ struct poppy_hip_ctx {
     Team planners;                                  // the frame planners of multi-frame calls
     bool writer_attached = false;                   // a multi-frame call with a writer is in progress
     int frame_format = POPPY_FRAME_BGR;             // of the frames handed to writers (poppy_hip_set_frame_format)
-    uint8_t* i420_scratch = nullptr; size_t i420_scratch_bytes = 0;      // I420 / PAL8 of the copies and fallback frames that no slot renders (download_frame)
-    uint8_t* pal8_scratch_tables = nullptr;         // ... and the PAL8 conversion's tables for them
-    // POPPY_FRAME_PAL8_SEQ (poppy_hip.cpp: seq_begin .. seq_finish): the sequence's tables (kernels.h: kPal8SeqTableBytes; zero between sequences), the frames held back
-    // until the palette is known (seq_stride bytes apart, kept between sequences, grown when needed), and a ring of index planes on their way to the writer
-    uint8_t* seq_tables = nullptr;
-    uint8_t* seq_store = nullptr; size_t seq_store_bytes = 0, seq_stride = 0;
-    uint8_t* seq_idx = nullptr; size_t seq_idx_bytes = 0;
-    bool seq_open = false;                          // a sequence is being collected: frames for the writer go through the pass into the store
-    int seq_n = 0, seq_count = 0;                   // its frames, and how many of them have been queued
+    uint8_t* fmt_scratch = nullptr; size_t fmt_scratch_bytes = 0;      // I420 / PAL8 of the copies and fallback frames that no slot renders (download_frame)
+    uint8_t* fmt_scratch_tables = nullptr;          // ... and the PAL8 conversion's tables for them
+    PaletteSeq seq;                                 // POPPY_FRAME_PAL8_SEQ: the sequence being collected (frame_format.h: seq_begin .. seq_finish)
     double wait_ms[4] = {0, 0, 0, 0};               // host waits inside submit_frame since the context was made (POPPY_SEQ_TIMING prints the per-sequence share)
     ForegroundFilter foreground, foreground_b;      // two instances: the images of a pair are filtered side by side
     // The two chain slots (slot 0 = foreground + orb, slot 1 = foreground_b + orb_b; chain_fg / chain_orb below).  After a set-up from raw images the slot
@@ -219,14 +208,23 @@ int alloc_pair(poppy_hip_ctx* c, int W, int H);                                 
 int upload_image(poppy_hip_ctx* c, uint8_t* dst, const uint8_t* src, size_t stride, int W, int H);
 int set_points(poppy_hip_ctx* c, const float* p1, const float* p2, int n);
 int finish_pair_load(poppy_hip_ctx* c);                                           // m2 from gabor2, chain state reset, pair_ready
-// the frame hand-off's format (poppy_hip_set_frame_format): a device frame (tight u8x3, W x H) in the writer's format in `host`, queued on
-// c->stream and waited for; *stride = what the writer is told
-// n_copies: how often the writer gets this frame — under POPPY_FRAME_PAL8_SEQ these copies are the whole sequence, and the frame is converted on the host
-int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride, int n_copies = 1);
-// a host frame in the writer's format: `bgr` itself (BGR) or its I420 / PAL8 in `tmp`; nullptr, *status and c->err set, when the format refuses the frame
-const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status, int n_copies = 1);
-// frame_pal8.cpp: the POPPY_FRAME_PAL8_SEQ frame of a sequence that is n_copies times the same BGR frame (poppy_bgr_frames_to_pal8 with frame_stride 0, one frame out)
-int pal8_seq_of_copies(const uint8_t* bgr, size_t stride, int n_copies, int width, int height, uint8_t* dst);
+
+// Per-kernel timing: events are only RECORDED while frames are queued (no host sync); they are resolved
+// in poppy_hip_timing_summary() after the caller has drained the stream.
+struct Timer {
+    poppy_hip_ctx* c;
+    Timer(poppy_hip_ctx* c_, hipStream_t s_) : c(c_), s(s_) {}
+    hipStream_t s = nullptr;
+    hipEvent_t take(const char* name) {           // next event of the pool, labelled, not recorded
+        if (c->marks_used >= c->marks.size()) { hipEvent_t e; (void)hipEventCreate(&e); c->marks.push_back({nullptr, e}); }
+        c->marks[c->marks_used].name = name;
+        return c->marks[c->marks_used++].ev;
+    }
+    void mark(const char* name) {
+        if (!c->timing) return;
+        (void)hipEventRecord(take(name), s);
+    }
+};
 
 // blur_margin (pair_setup.cpp): the taps, the image's place in the canvas, and canvas -> padded image on the device
 constexpr int kBlurMarginTaps = 127;

@@ -47,14 +47,6 @@ int list_pad(poppy_hip_ctx* c, const ListImage& img, int UW, int UH, uint8_t* ou
     return POPPY_OK;
 }
 
-// a device image -> host bytes (the short-circuit and fallback frames go to the writer from the host)
-int list_download(poppy_hip_ctx* c, const uint8_t* d, int W, int H, std::vector<uint8_t>& host) {
-    host.resize((size_t)W * H * 3);
-    HIPCHK(c, hipMemcpyAsync(host.data(), d, host.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return POPPY_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -93,20 +85,11 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
     int rc = fetch(0, a); if (rc) return rc;
     rc = fetch(1, b); if (rc) return rc;
     if (phase == 0 || phase == 1) {                            // two images: poppy_hip_morph's short-circuit, before any feature work
-        if (write && c->frame_format != POPPY_FRAME_BGR) {      // (the writer's format: converted on the device, or on the host for host images as poppy_hip_morph does)
+        if (write) {                                           // (in the writer's format: converted on the device, or on the host for host images as poppy_hip_morph does)
             const ListImage& img = phase == 0 ? a : b;
-            std::vector<uint8_t> host; size_t stride = 0;
-            const uint8_t* frame = nullptr;
-            if (img.dev) { rc = download_frame(c, img.p, W, H, host, &stride, N); if (rc) return rc; frame = host.data(); }
-            else { frame = host_frame(c, img.p, img.stride, W, H, host, &stride, &rc, N); if (!frame) return rc; }
             PairWriter pw{write, user, 0, 0};
-            for (int j = 0; j < N; ++j) pair_writer_cb(&pw, frame, W, H, stride);
-        } else if (write) {
-            const ListImage& img = phase == 0 ? a : b;
-            std::vector<uint8_t> host;
-            if (img.dev) { rc = list_download(c, img.p, W, H, host); if (rc) return rc; }
-            PairWriter pw{write, user, 0, 0};
-            for (int j = 0; j < N; ++j) pair_writer_cb(&pw, img.dev ? host.data() : img.p, W, H, img.dev ? (size_t)W * 3 : img.stride);
+            rc = img.dev ? write_device_image(c, img.p, W, H, N, pair_writer_cb, &pw) : write_host_image(c, img.p, img.stride, W, H, N, pair_writer_cb, &pw);
+            if (rc) return rc;
         }
         if (pairs_done) *pairs_done = 1;
         return POPPY_OK;
@@ -121,13 +104,8 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
                 const uint8_t* raw2 = c->c2_raw_valid ? c->c2_raw : c->c2;          // the image as it came in (auto-align may have replaced c2)
                 launch_dissolve(raw2, c->c1, c->slots[0].out, (size_t)W * H * 3, (float)phase, (float)(1.0 - phase), c->stream);
                 HIPCHK(c, hipGetLastError());
-                std::vector<uint8_t> blend;
-                size_t stride = (size_t)W * 3;
-                if (c->frame_format != POPPY_FRAME_BGR) rc = download_frame(c, c->slots[0].out, W, H, blend, &stride, N);
-                else rc = list_download(c, c->slots[0].out, W, H, blend);
-                if (rc) return rc;
                 PairWriter pw{write, user, k, 0};
-                for (int j = 0; j < N; ++j) pair_writer_cb(&pw, blend.data(), W, H, stride);
+                rc = write_device_image(c, c->slots[0].out, W, H, N, pair_writer_cb, &pw); if (rc) return rc;
                 chain_touch(c);                                // as after poppy_hip_dissolve
                 c->pair_ready = false;
             }

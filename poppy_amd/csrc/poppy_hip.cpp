@@ -94,10 +94,7 @@ static void free_pair(poppy_hip_ctx* c) {
         void* fb[] = {f.tr1, f.tr2, f.out, f.pyrL, f.pyrR, f.pyrM, f.pyrB, f.tmp, f.diff, f.unsharpF, f.triMap};
         for (void* b : fb) if (b) (void)hipFree(b);
         f.tr1 = f.tr2 = f.out = nullptr; f.pyrL = f.pyrR = f.pyrM = f.pyrB = f.tmp = f.diff = f.unsharpF = nullptr; f.triMap = nullptr;
-        for (uint8_t* b : {f.i420, f.pal8, f.pal8_tables, f.gif, f.gif_scratch}) if (b) (void)hipFree(b);
-        f.i420 = f.pal8 = f.pal8_tables = f.gif = f.gif_scratch = nullptr;
-        if (f.gif_total) (void)hipHostFree(f.gif_total);
-        f.gif_total = nullptr; f.gif_total_dev = nullptr;
+        free_slot_format_pair(f.fmt);
     }
     for (FrameSlot& f : c->slots) {
         if (f.body) { (void)hipGraphExecDestroy(f.body); f.body = nullptr; }
@@ -116,7 +113,7 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     (void)poppy_hip_comm_free(c);
     for (FrameSlot& f : c->slots)
-        for (hipStream_t st : {f.stream, f.own_stream, f.fmt_stream}) if (st) (void)hipStreamSynchronize(st);
+        for (hipStream_t st : {f.stream, f.own_stream, f.fmt.fmt_stream}) if (st) (void)hipStreamSynchronize(st);
     free_pair(c);
     for (FrameSlot& f : c->slots) {
         if (f.done) (void)hipEventDestroy(f.done);
@@ -124,8 +121,7 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
         if (f.downloaded) (void)hipEventDestroy(f.downloaded);
         if (f.uploaded) (void)hipEventDestroy(f.uploaded);
         if (f.own_stream) (void)hipStreamDestroy(f.own_stream);
-        if (f.fmt_stream) (void)hipStreamDestroy(f.fmt_stream);
-        if (f.bgr_done) (void)hipEventDestroy(f.bgr_done);
+        free_slot_format_ctx(f.fmt);
     }
     if (c->inputs_ready) (void)hipEventDestroy(c->inputs_ready);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -142,9 +138,7 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
     if (c->d_align) (void)hipFree(c->d_align);
     for (void* p : {(void*)c->bm_canvas, (void*)c->bm_tmp, (void*)c->bm_taps, (void*)c->list_img[0], (void*)c->list_img[1]}) if (p) (void)hipFree(p);
     if (c->d_comm_scratch) (void)hipFree(c->d_comm_scratch);
-    if (c->i420_scratch) (void)hipFree(c->i420_scratch);
-    if (c->pal8_scratch_tables) (void)hipFree(c->pal8_scratch_tables);
-    for (uint8_t* b : {c->seq_tables, c->seq_store, c->seq_idx}) if (b) (void)hipFree(b);
+    free_context_format(c);
     c->aligner.release();
     (void)hipStreamDestroy(c->copy_stream);
     (void)hipStreamDestroy(c->stream);
@@ -233,95 +227,6 @@ static int ensure_ring(poppy_hip_ctx* c, int n_points) {
     return POPPY_OK;
 }
 
-// every slot's I420 buffer for the pair's geometry (while the context's frame format is I420)
-static int alloc_slot_i420(poppy_hip_ctx* c) {
-    const size_t bytes = poppy_frame_bytes(POPPY_FRAME_I420, c->W, c->H);
-    for (FrameSlot& f : c->slots) if (!f.i420) HIPCHK(c, hipMalloc((void**)&f.i420, bytes + 16));
-    return POPPY_OK;
-}
-
-// the PAL8 conversion's tables: zero before the first frame (the palette build leaves them zero again)
-static int alloc_pal8_tables(poppy_hip_ctx* c, uint8_t** tables) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!prepare_pal8()) return fail(c, POPPY_E_DEVICE, "could not raise the palette build's LDS limit");      // (per device: kernels.h)
-    HIPCHK(c, hipMalloc((void**)tables, kPal8TableBytes));
-    HIPCHK(c, hipMemset(*tables, 0, kPal8TableBytes));
-    return POPPY_OK;
-}
-
-static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H <= (unsigned long long)POPPY_PAL8_MAX_PIXELS; }
-static bool is_pal8(int format) { return format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ; }
-constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF take frames of at most 2^24 pixels";
-constexpr const char* kGifSizeMsg = "POPPY_FRAME_GIF takes frames of at most 65535 pixels in width and height";
-// why `format` refuses a W x H frame, or null: checked on the arguments alone, before anything is allocated or any state changes
-static const char* format_refuses(int format, int W, int H) {
-    if ((is_pal8(format) || format == POPPY_FRAME_GIF) && !pal8_fits(W, H)) return kPal8SizeMsg;
-    if (format == POPPY_FRAME_GIF && (W > 65535 || H > 65535)) return kGifSizeMsg;
-    return nullptr;
-}
-
-// a slot's conversion side stream and the event that rides on its unsharp (PAL8 and PAL8_SEQ; they live as long as the context)
-static int alloc_slot_side(poppy_hip_ctx* c, FrameSlot& f) {
-    // The side streams are created at the LOWEST stream priority.  The runtime keeps its hardware queues per priority, so they never share a queue with the
-    // chain's stream or the plan upload's (normal priority): a dispatch waits for the one before it in its hardware queue whatever its stream, and a
-    // 350 us palette build in the chain's queue held the next frame's warp back for its whole length (kernel trace).
-    if (!f.fmt_stream) {
-        int least = 0, greatest = 0;
-        HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(c, hipStreamCreateWithPriority(&f.fmt_stream, hipStreamNonBlocking, least));
-    }
-    if (!f.bgr_done) HIPCHK(c, hipEventCreateWithFlags(&f.bgr_done, hipEventDisableTiming));
-    return POPPY_OK;
-}
-
-// every slot's PAL8 buffer, tables, side stream and event for the pair's geometry (while the context's frame format is PAL8)
-static int alloc_slot_pal8(poppy_hip_ctx* c) {
-    if (!pal8_fits(c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
-    const size_t bytes = poppy_frame_bytes(POPPY_FRAME_PAL8, c->W, c->H);
-    for (FrameSlot& f : c->slots) {
-        if (!f.pal8) HIPCHK(c, hipMalloc((void**)&f.pal8, bytes + 16));
-        if (!f.pal8_tables) { int rc = alloc_pal8_tables(c, &f.pal8_tables); if (rc) return rc; }
-        int rc = alloc_slot_side(c, f); if (rc) return rc;
-    }
-    return POPPY_OK;
-}
-
-// PAL8_SEQ: the slots' side streams and the context's sequence tables, zero before the first sequence (the build leaves the sums zero again).  The store and the
-// index ring depend on the sequence's length: seq_begin, seq_finish.
-static int alloc_slot_pal8_seq(poppy_hip_ctx* c) {
-    if (!pal8_fits(c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
-    for (FrameSlot& f : c->slots) { int rc = alloc_slot_side(c, f); if (rc) return rc; }
-    if (!c->seq_tables) {
-        HIPCHK(c, hipSetDevice(c->device));
-        if (!prepare_pal8()) return fail(c, POPPY_E_DEVICE, "could not raise the palette build's LDS limit");
-        HIPCHK(c, hipMalloc((void**)&c->seq_tables, kPal8SeqTableBytes));
-        HIPCHK(c, hipMemset(c->seq_tables, 0, kPal8SeqTableBytes));
-    }
-    return POPPY_OK;
-}
-
-// GIF: PAL8's buffers (the coder reads the slot's PAL8 frame) and the coded frame, the coder's scratch and the pinned length word
-static int alloc_slot_gif(poppy_hip_ctx* c) {
-    if (const char* why = format_refuses(POPPY_FRAME_GIF, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
-    { int rc = alloc_slot_pal8(c); if (rc) return rc; }
-    for (FrameSlot& f : c->slots) {
-        if (!f.gif) HIPCHK(c, hipMalloc((void**)&f.gif, poppy_frame_bytes(POPPY_FRAME_GIF, c->W, c->H) + 16));
-        if (!f.gif_scratch) HIPCHK(c, hipMalloc((void**)&f.gif_scratch, gif_scratch_bytes(c->W, c->H)));
-        if (!f.gif_total) {
-            HIPCHK(c, hipHostMalloc((void**)&f.gif_total, 64, hipHostMallocMapped));
-            HIPCHK(c, hipHostGetDevicePointer(&f.gif_total_dev, f.gif_total, 0));
-            *f.gif_total = 0;
-        }
-    }
-    return POPPY_OK;
-}
-
-static int alloc_slot_format(poppy_hip_ctx* c) {
-    if (c->frame_format == POPPY_FRAME_GIF) return alloc_slot_gif(c);
-    return c->frame_format == POPPY_FRAME_I420 ? alloc_slot_i420(c) : c->frame_format == POPPY_FRAME_PAL8 ? alloc_slot_pal8(c) :
-           c->frame_format == POPPY_FRAME_PAL8_SEQ ? alloc_slot_pal8_seq(c) : POPPY_OK;
-}
-
 int alloc_pair(poppy_hip_ctx* c, int W, int H) {
     { int rc = drain_frames(c); if (rc) return rc; }              // every pair loader comes through here: no frame still reads the old pair
     // PAL8 takes frames of at most 2^24 pixels: refused before anything is allocated or any state changes, so the context keeps the pair it had
@@ -406,7 +311,7 @@ int drain_frames(poppy_hip_ctx* c) {
     for (FrameSlot& f : c->slots) {
         if (f.stream) HIPCHK(c, hipStreamSynchronize(f.stream));
         if (f.own_stream && f.own_stream != f.stream) HIPCHK(c, hipStreamSynchronize(f.own_stream));
-        if (f.fmt_stream) HIPCHK(c, hipStreamSynchronize(f.fmt_stream));
+        if (f.fmt.fmt_stream) HIPCHK(c, hipStreamSynchronize(f.fmt.fmt_stream));
     }
     return POPPY_OK;
 }
@@ -447,33 +352,6 @@ int adopt_pair_state(poppy_hip_ctx* c) {
     c->cur1 = c->c1; c->cur1_ready = nullptr; c->last_slot = -1; c->pair_ready = true;
     return POPPY_OK;
 }
-
-static int stage_host(poppy_hip_ctx* c, size_t bytes) {
-    if (bytes <= c->h_stage_bytes) return POPPY_OK;
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    c->h_stage = nullptr; c->h_stage_bytes = 0;
-    HIPCHK(c, hipHostMalloc((void**)&c->h_stage, bytes, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer(&c->h_stage_dev, c->h_stage, 0));
-    c->h_stage_bytes = bytes;
-    return POPPY_OK;
-}
-
-// Per-kernel timing: events are only RECORDED while frames are queued (no host sync); they are resolved
-// in poppy_hip_timing_summary() after the caller has drained the stream.
-struct Timer {
-    poppy_hip_ctx* c;
-    Timer(poppy_hip_ctx* c_, hipStream_t s_) : c(c_), s(s_) {}
-    hipStream_t s = nullptr;
-    hipEvent_t take(const char* name) {           // next event of the pool, labelled, not recorded
-        if (c->marks_used >= c->marks.size()) { hipEvent_t e; (void)hipEventCreate(&e); c->marks.push_back({nullptr, e}); }
-        c->marks[c->marks_used].name = name;
-        return c->marks[c->marks_used++].ev;
-    }
-    void mark(const char* name) {
-        if (!c->timing) return;
-        (void)hipEventRecord(take(name), s);
-    }
-};
 
 static int submit_frame(poppy_hip_ctx* c, double mask, bool chain);
 static int prepare_ahead(poppy_hip_ctx* c, const FramePlan& plan, double mask);
@@ -583,119 +461,6 @@ void start_default_seq_plans(poppy_hip_ctx* c) {
     start_seq_plans(c, ratio.data(), N, true);
 }
 
-// ---- POPPY_FRAME_PAL8_SEQ: one palette for all the frames a call hands to its writer ---------------------------------------------------------------------
-// seq_begin opens a sequence of n frames (limits, tables, store), every frame for the writer then goes through seq_pass (render_slot, seq_add_image) instead of
-// a download, and seq_finish builds the palette and hands every frame to the writer; seq_abort ends a sequence of which a frame failed, nothing written.
-static int seq_abort(poppy_hip_ctx* c);
-static int seq_begin(poppy_hip_ctx* c, int n) {
-    const int W = c->W, H = c->H;
-    if (c->seq_open) { int rc = seq_abort(c); if (rc) return rc; }      // (a sequence that a device error left open: its frames and sums are dropped, not mixed into this one)
-    if (!pal8_fits(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kPal8SizeMsg);
-    if ((unsigned long long)n * (unsigned long long)W * (unsigned long long)H >= POPPY_PAL8_SEQ_MAX_PIXELS)
-        return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8_SEQ takes sequences of fewer than 2^32 pixels in all");
-    { int rc = alloc_slot_pal8_seq(c); if (rc) return rc; }
-    const size_t stride = ((size_t)W * H * 3 + 15) & ~(size_t)15, need = stride * (size_t)n;      // (every frame's place begins on a 16-byte boundary)
-    if (need > c->seq_store_bytes) {
-        if (c->seq_store) (void)hipFree(c->seq_store);
-        c->seq_store = nullptr; c->seq_store_bytes = 0;
-        if (hipMalloc((void**)&c->seq_store, need) != hipSuccess) { (void)hipGetLastError(); return fail(c, POPPY_E_DEVICE, "no device memory for the sequence's frames (3 * width * height bytes each)"); }
-        c->seq_store_bytes = need;
-    }
-    c->seq_stride = stride; c->seq_n = n; c->seq_count = 0; c->seq_open = true;
-    return POPPY_OK;
-}
-
-// frames submitted now go into the open sequence
-static bool seq_wanted(const poppy_hip_ctx* c) { return c->seq_open && c->writer_attached && c->frame_format == POPPY_FRAME_PAL8_SEQ; }
-
-// the pass of one frame: into the sequence's sums and on to `dst` in the store, one kernel
-static int seq_pass(poppy_hip_ctx* c, const uint8_t* d_bgr, uint8_t* dst, hipStream_t s, hipEvent_t done) {
-    launch_pal8_seq_pass(d_bgr, dst, c->seq_tables, c->W, c->H, s, done);
-    HIPCHK(c, hipGetLastError());
-    return POPPY_OK;
-}
-
-static uint8_t* seq_next_place(poppy_hip_ctx* c) { return c->seq_count < c->seq_n ? c->seq_store + (size_t)c->seq_count++ * c->seq_stride : nullptr; }
-
-// a frame that no slot renders (the t == 0 / 1 copies of poppy_hip_render_phases), on the context's stream
-static int seq_add_image(poppy_hip_ctx* c, const uint8_t* d_bgr) {
-    uint8_t* dst = seq_next_place(c);
-    if (!dst) return fail(c, POPPY_E_STATE, "more frames than the sequence was opened for");
-    Timer tm(c, c->stream);
-    if (c->timing == 1) tm.mark(nullptr);
-    { int rc = seq_pass(c, d_bgr, dst, c->stream, nullptr); if (rc) return rc; }
-    if (c->timing == 1) tm.mark("pal8_seq_hist");
-    HIPCHK(c, hipGetLastError());
-    return POPPY_OK;
-}
-
-static int seq_abort(poppy_hip_ctx* c) {
-    c->seq_open = false;
-    int rc = drain_frames(c);
-    if (c->seq_tables && hipMemset(c->seq_tables, 0, kPal8SeqTableOffset) != hipSuccess && rc == POPPY_OK) rc = fail(c, POPPY_E_DEVICE, "could not clear the sequence tables");
-    return rc;
-}
-
-static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user);
-// the open sequence is complete: palette, then every frame to the writer.  Whatever fails in there, the sequence is closed and the tables are zero afterwards.
-static int seq_finish(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
-    if (c->seq_count != c->seq_n) { (void)seq_abort(c); return fail(c, POPPY_E_STATE, "fewer frames than the sequence was opened for"); }
-    const int rc = seq_hand_over(c, write, user);
-    if (rc) { const std::string why = c->err; (void)seq_abort(c); c->err = why; }
-    return rc;
-}
-
-static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
-    const int n = c->seq_count, W = c->W, H = c->H;
-    c->seq_open = false;
-    { int rc = drain_frames(c); if (rc) return rc; }              // every pass has added its frame (they ran on the slots' streams)
-    const bool marks = c->timing == 1;
-    {
-        Timer tm(c, c->stream);
-        if (marks) tm.mark(nullptr);
-        launch_pal8_seq_build(c->seq_tables, c->stream);
-        if (marks) tm.mark("pal8_seq_build");
-    }
-    HIPCHK(c, hipGetLastError());
-    uint8_t pal[768];
-    HIPCHK(c, hipMemcpyAsync(pal, c->seq_tables + kPal8SeqPaletteOffset, 768, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    // Every frame: the index plane from the store through a ring of R device planes and R pinned buffers, remap and copy in order on the ring buffer's own stream
-    // (render_sequence: no event behind a copy), the palette behind the indices on the host.
-    static const int ring_pref = getenv("POPPY_HIP_RING") ? std::max(1, atoi(getenv("POPPY_HIP_RING"))) : 3;
-    const int R = std::min(poppy_hip_ctx::kStageRing, ring_pref);
-    const size_t n_px = (size_t)W * H, slot_bytes = (n_px + 768 + 255) & ~(size_t)255, plane = (n_px + 255) & ~(size_t)255;
-    { int rc = stage_host(c, slot_bytes * R); if (rc) return rc; }
-    if (plane * R > c->seq_idx_bytes) {
-        if (c->seq_idx) (void)hipFree(c->seq_idx);
-        c->seq_idx = nullptr; c->seq_idx_bytes = 0;
-        HIPCHK(c, hipMalloc((void**)&c->seq_idx, plane * R));
-        c->seq_idx_bytes = plane * R;
-    }
-    auto deliver = [&](int k) -> int {
-        const int r = k % R;
-        HIPCHK(c, hipStreamSynchronize(c->dl_ring[r]));
-        uint8_t* frame = c->h_stage + (size_t)r * slot_bytes;
-        memcpy(frame + n_px, pal, 768);
-        write(user, frame, W, H, (size_t)W);
-        return POPPY_OK;
-    };
-    int written = 0;
-    for (int k = 0; k < n; ++k) {
-        const int r = k % R;
-        if (k >= R) { int rc = deliver(written); if (rc) return rc; ++written; }
-        if (!c->dl_ring[r]) HIPCHK(c, hipStreamCreateWithFlags(&c->dl_ring[r], hipStreamNonBlocking));
-        Timer tm(c, c->dl_ring[r]);
-        if (marks) tm.mark(nullptr);
-        launch_pal8_seq_remap(c->seq_store + (size_t)k * c->seq_stride, c->seq_tables, c->seq_idx + (size_t)r * plane, W, H, c->dl_ring[r]);
-        if (marks) tm.mark("frame_format");
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, c->seq_idx + (size_t)r * plane, n_px, hipMemcpyDeviceToHost, c->dl_ring[r]));
-    }
-    for (; written < n; ++written) { int rc = deliver(written); if (rc) return rc; }
-    return POPPY_OK;
-}
-
 static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const double* mask, int n, bool chain, poppy_write_cb write, void* user);
 
 // PAL8_SEQ: the frames go through the pass into the sequence store and to the writer when all are there — of this call's own sequence, or of the one its caller
@@ -705,17 +470,17 @@ static int render_sequence(poppy_hip_ctx* c, const double* shape, const double* 
     if (!c->pair_ready) return fail(c, POPPY_E_STATE, "no pair loaded");
     if (c->pts1.empty()) return fail(c, POPPY_E_NOMATCH, "no point pairs (use poppy_hip_dissolve)");
     if (n <= 0) return POPPY_OK;
-    const bool own_seq = write && c->frame_format == POPPY_FRAME_PAL8_SEQ && !in_open_seq;
+    const bool own_seq = writer_wants_sequence(c, write != nullptr) && !in_open_seq;
     if (own_seq) { int rc = seq_begin(c, n); if (rc) return rc; }
     int rc = render_sequence_frames(c, shape, mask, n, chain, write, user);
     c->writer_attached = false;
-    if (own_seq) { if (rc == POPPY_OK) rc = seq_finish(c, write, user); else { const std::string why = c->err; (void)seq_abort(c); c->err = why; } }
+    if (own_seq) { if (rc == POPPY_OK) rc = seq_finish(c, write, user); else seq_abort_keep_error(c); }
     return rc;
 }
 
 static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const double* mask, int n, bool chain, poppy_write_cb write, void* user) {
     const int W = c->W, H = c->H;
-    const bool seq = write && c->frame_format == POPPY_FRAME_PAL8_SEQ;
+    const bool seq = writer_wants_sequence(c, write != nullptr);
     if (n >= 2) c->plan_ahead_credit = true;                       // a caller of sequences: the next pair loader plans ahead again (start_default_seq_plans)
     // the plans a pair loader started for exactly these frames on exactly these points, or new ones
     SeqPlans* sp = static_cast<SeqPlans*>(c->seq_plans);
@@ -730,23 +495,15 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
     std::vector<std::atomic<int>>& ready = sp->ready;
     std::atomic<int>& next = sp->next;
     int rc = POPPY_OK;
-    // the writer's format (poppy_hip_set_frame_format): I420 and PAL8 frames are converted by the frame body into the slot's i420 / pal8 buffer (enqueue_body)
-    const int fmt = write ? c->frame_format : POPPY_FRAME_BGR;
-    // (every way to this format with a pair allocates the slots' buffers — alloc_pair, poppy_hip_set_frame_format — or refuses: a frame is never converted into nothing)
+    // the writer's format (poppy_hip_set_frame_format): the frame body converts the frame into the slot's buffer of that format (enqueue_body)
+    const int fmt = writer_format(c, write != nullptr);
     for (const FrameSlot& f : c->slots)
-        if ((fmt == POPPY_FRAME_I420 && !f.i420) || ((fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF) && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) ||
-            (fmt == POPPY_FRAME_GIF && !(f.gif && f.gif_scratch && f.gif_total)) ||
-            (seq && !(c->seq_open && c->seq_tables && f.fmt_stream && f.bgr_done)))
-            return fail(c, POPPY_E_STATE, "the frame format's buffers are not allocated for this pair");
+        if (!slot_format_ready(c, f, fmt)) return fail(c, POPPY_E_STATE, "the frame format's buffers are not allocated for this pair");
     // (GIF: a coded frame goes to the writer with stride 0; frame_bytes is its capacity, which sizes the pinned ring — a frame's copy moves its own length)
-    const size_t row = fmt == POPPY_FRAME_GIF ? 0 : fmt != POPPY_FRAME_BGR ? (size_t)W : (size_t)W * 3, frame_bytes = poppy_frame_bytes(fmt, W, H);
-    auto frame_of = [fmt](const FrameSlot& f) -> const uint8_t* { return fmt == POPPY_FRAME_I420 ? f.i420 : fmt == POPPY_FRAME_PAL8 ? f.pal8 : fmt == POPPY_FRAME_GIF ? f.gif : f.out; };
-    static const int ring_pref = getenv("POPPY_HIP_RING") ? std::max(1, atoi(getenv("POPPY_HIP_RING"))) : 3;
-    const int R = std::min({poppy_hip_ctx::kStageRing, ring_pref, (int)c->slots.size()});
-    const size_t slot_bytes = (frame_bytes + 255) & ~(size_t)255;     // ring slots start on 256-byte boundaries
-    int written = 0;
-    if (write && !seq) rc = stage_host(c, slot_bytes * R);
+    const size_t row = writer_stride(fmt, W), frame_bytes = poppy_frame_bytes(fmt, W, H);
     const bool dl = write && !seq;                                // frames are downloaded and handed over as they finish
+    WriterRing ring;                                              // (frames 0 .. ring.issued - 1: their downloads are queued)
+    if (dl) rc = ring.open(c, frame_bytes, true);
     c->writer_attached = write != nullptr;                        // (phase-mode frames pick their streams by it: submit_frame)
     // Frame hand-off.  The download of a frame runs on its own stream into a ring of R pinned buffers while the GPU renders the
     // frames behind it, and the writer gets frames in order, R - 1 downloads behind.  A copy whose start depends on an event of
@@ -764,8 +521,7 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
     const double w0[4] = {c->wait_ms[0], c->wait_ms[1], c->wait_ms[2], c->wait_ms[3]};
     auto lap = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
     std::vector<int> slot_of(n, -1);
-    const int pal8_lag = fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF ? std::max(0, (int)c->slots.size() - 2) : 0;
-    int issued = 0;                                               // downloads queued so far (frames 0 .. issued-1)
+    const int pal8_lag = format_builds_palette(fmt) ? std::max(0, (int)c->slots.size() - 2) : 0;
     // Round 6: a frame copy goes to the stream of its pinned ring buffer, which carries nothing else, and NO event is recorded behind it — whoever needs the copy
     // finished synchronises that stream.  An event record behind a copy is a marker packet that waits, in one of the process's four hardware queues, for the copy's
     // signal, and every kernel of every stream mapped to that queue waits with it for the length of a frame copy (~120 us): a pool of six with the writer 6.2 -> 6.6-6.9k
@@ -774,19 +530,17 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
     static const bool dl_streams = getenv("POPPY_HIP_DL_EVENTS") == nullptr && !dev_wait;
     auto issue_download = [&](int k) -> bool {
         FrameSlot& f = c->slots[slot_of[k]];
-        const int r = k % R;
+        const int r = k % ring.R;
         const auto t0 = clk::now();
         // (GIF: the host waits in every form: k_gif_pack has stored the frame's length into the slot's pinned word by then, and the copy moves that many bytes)
-        hipError_t e = dev_wait && fmt != POPPY_FRAME_GIF ? hipStreamWaitEvent(c->dl_stream, f.done, 0) : hipEventSynchronize(f.done);
+        hipError_t e = dev_wait && !format_is_coded(fmt) ? hipStreamWaitEvent(c->dl_stream, f.done, 0) : hipEventSynchronize(f.done);
         ms_done += lap(t0);
         size_t copy_bytes = frame_bytes;
-        if (fmt == POPPY_FRAME_GIF && e == hipSuccess) {
-            copy_bytes = *(volatile uint32_t*)f.gif_total;
-            if (copy_bytes < 776 || copy_bytes > frame_bytes) { c->err = "the coded frame's length is outside its bounds"; rc = POPPY_E_DEVICE; return false; }
-        }
+        if (e == hipSuccess && !slot_frame_length(f, fmt, frame_bytes, &copy_bytes)) { c->err = "the coded frame's length is outside its bounds"; rc = POPPY_E_DEVICE; return false; }
         if (dl_streams) {
-            if (e == hipSuccess && !c->dl_ring[r]) e = hipStreamCreateWithFlags(&c->dl_ring[r], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, frame_of(f), copy_bytes, hipMemcpyDeviceToHost, c->dl_ring[r]);
+            hipStream_t ds = nullptr;
+            if (e == hipSuccess) e = ring.stream(c, k, &ds);
+            if (e == hipSuccess) e = hipMemcpyAsync(ring.buffer(k), slot_frame(f, fmt), copy_bytes, hipMemcpyDeviceToHost, ds);
             f.dl_pending = true; f.dl_ring_idx = r;
             if (e != hipSuccess) { c->err = std::string("frame download: ") + hipGetErrorString(e); rc = POPPY_E_DEVICE; return false; }
             return true;
@@ -796,21 +550,26 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
         static const bool skip_copy = getenv("POPPY_DL_SKIP_COPY") != nullptr;      // timing experiment: every wait and event of the writer path, no bytes moved (wrong frames)
         if (!skip_copy)
 #endif
-        if (e == hipSuccess) e = hipMemcpyAsync(c->h_stage + (size_t)r * slot_bytes, frame_of(f), copy_bytes, hipMemcpyDeviceToHost, c->dl_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ring.buffer(k), slot_frame(f, fmt), copy_bytes, hipMemcpyDeviceToHost, c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(c->dl_done[r], c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(f.downloaded, c->dl_stream);          // the slot's own: ring events are re-recorded every R frames
         f.dl_pending = true;
         if (e != hipSuccess) { c->err = std::string("frame download: ") + hipGetErrorString(e); rc = POPPY_E_DEVICE; return false; }
         return true;
     };
-    auto deliver = [&](int k) -> bool {
-        const int rr = k % R;
+    auto deliver = [&]() {
         const auto t0 = clk::now();
-        if ((dl_streams ? hipStreamSynchronize(c->dl_ring[rr]) : hipEventSynchronize(c->dl_done[rr])) != hipSuccess) { c->err = "frame download failed"; rc = POPPY_E_DEVICE; return false; }
+        uint8_t* frame = nullptr;
+        if (ring.deliver_next(c, !dl_streams, &frame) != hipSuccess) { c->err = "frame download failed"; rc = POPPY_E_DEVICE; return; }
         ms_deliver += lap(t0);
-        write(user, c->h_stage + (size_t)rr * slot_bytes, W, H, row);
-        ++written;
-        return true;
+        write(user, frame, W, H, row);
+    };
+    // the downloads of the frames before `upto` are queued, each behind the delivery that frees its ring buffer
+    auto pump = [&](int upto) {
+        while (ring.issued < upto && rc == POPPY_OK) {
+            while (ring.issued - ring.written >= ring.R && rc == POPPY_OK) deliver();
+            if (rc == POPPY_OK && issue_download(ring.issued)) ++ring.issued;
+        }
     };
     for (int j = 0; j < n && rc == POPPY_OK; ++j) {
         const auto t_plan = clk::now();
@@ -826,11 +585,8 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
             int ps = c->next_slot;
             if (c->slots[ps].out == c->cur1) ps = (ps + 1) % (int)c->slots.size();
             int last_user = -1;
-            for (int k = issued; k < j; ++k) if (slot_of[k] == ps) last_user = k;
-            while (issued <= last_user && rc == POPPY_OK) {
-                while (issued - written >= R && rc == POPPY_OK) deliver(written);
-                if (rc == POPPY_OK && issue_download(issued)) ++issued;
-            }
+            for (int k = ring.issued; k < j; ++k) if (slot_of[k] == ps) last_user = k;
+            pump(last_user + 1);
             if (rc != POPPY_OK) break;
         }
         const auto t_sub = clk::now();
@@ -845,19 +601,12 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
             // frames whose download can be issued now.  A PAL8 frame is complete one palette build (several frame times) behind its BGR: waiting for frame
             // j - 1 here would hold back frame j + 1 for that long, so under PAL8 the downloads trail as far as the slots allow (the loop above the
             // submit sends what a slot's reuse forces out) and the conversions of that many frames run beside each other.
-            const int upto = (dev_wait ? j + 1 : j) - pal8_lag;
-            while (issued < upto && rc == POPPY_OK) {
-                while (issued - written >= R && rc == POPPY_OK) deliver(written);
-                if (rc == POPPY_OK && issue_download(issued)) ++issued;
-            }
+            pump((dev_wait ? j + 1 : j) - pal8_lag);
         }
     }
     if (dl && rc == POPPY_OK) {
-        while (issued < n && rc == POPPY_OK) {                    // the last frame(s), then drain the ring
-            while (issued - written >= R && rc == POPPY_OK) deliver(written);
-            if (rc == POPPY_OK && issue_download(issued)) ++issued;
-        }
-        while (written < n && rc == POPPY_OK) deliver(written);
+        pump(n);                                                  // the last frame(s), then drain the ring
+        while (ring.written < n && rc == POPPY_OK) deliver();
     }
     c->writer_attached = false;
     drop_slot_preps(c);                    // (a frame prepared ahead and never rendered — an error exit — must not meet a later call)
@@ -950,46 +699,27 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     }
     if (tm) tm->mark("collapse");
     // A frame for a writer that takes I420 is converted right behind its unsharp, on the same stream, and the frame's completion event rides on the
-    // conversion: the host waits for that event, then issues the copy of the slot's I420 buffer (render_sequence), which depends on nothing
+    // conversion: the host waits for that event, then issues the copy of the slot's I420 buffer (render_sequence_frames), which depends on nothing.
     // PAL8 is three dispatches, and the palette build in the middle is one workgroup's serial work (about as long as the rest of the frame).  The next chained
     // frame needs this frame's BGR, not its palette form: on the chain (`chained` with a completion event riding, i.e. kernels launched one by one) the
     // conversion goes to the slot's side stream behind an event that rides on the unsharp, the chain's stream goes on with the next frame, and `done` —
-    // which the download, the slot's reuse and drain_frames wait for — rides on the conversion's last dispatch.
+    // which the download, the slot's reuse and drain_frames wait for — rides on the conversion's last dispatch (frame_format.cpp: enqueue_conversion).
+    // GIF is PAL8 with the two coding dispatches behind the index plane, wherever PAL8's run; `done` rides on the second.
     // PAL8_SEQ (seq_dst: the frame's place in the sequence store, never set in a captured body): the pass takes PAL8's place, on the side stream too — it is short,
     // but the chain needs nothing of it.
     const int fmt = frame_wants_format(c);
-    // GIF is PAL8 with the two coding dispatches behind the index plane, wherever PAL8's run; `done` rides on the second.
-    const bool pal8_like = fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF;
-    const bool side = (pal8_like || seq_dst) && chained && done && !tm;
+    const bool side = (fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF || seq_dst) && chained && done && !tm;
+    const bool converts = fmt != POPPY_FRAME_BGR || seq_dst;
     launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s,
-                   side ? f.bgr_done : (fmt != POPPY_FRAME_BGR || seq_dst) ? nullptr : done, c->levels[0].pitch);
+                   side ? f.fmt.bgr_done : converts ? nullptr : done, c->levels[0].pitch);
     rec(POPPY_PYR_UNSHARP, 0, W < 2 || H < 2);
     if (tm) tm->mark("unsharp");
-    if (fmt == POPPY_FRAME_I420) {
-        launch_bgr_to_i420(f.out, f.i420, W, H, s, done);
-        if (tm) tm->mark("frame_format");
-    } else if (pal8_like) {
-        const bool gif = fmt == POPPY_FRAME_GIF;
-        hipStream_t fs = side ? f.fmt_stream : s;
-        if (side) HIPCHK(c, hipStreamWaitEvent(fs, f.bgr_done, 0));
-        launch_pal8_hist(f.out, f.pal8_tables, W, H, fs);
-        if (tm) tm->mark("pal8_hist");
-        launch_pal8_build(f.pal8_tables, f.pal8, W, H, fs);
-        if (tm) tm->mark("pal8_build");
-        launch_pal8_remap(f.out, f.pal8_tables, f.pal8, W, H, fs, gif ? nullptr : done);
-        if (tm) tm->mark("frame_format");                      // (under PAL8 and GIF: the index plane alone)
-        if (gif) {
-            launch_gif_lzw(f.pal8, f.gif_scratch, W, H, fs);
-            if (tm) tm->mark("gif_lzw");
-            launch_gif_pack(f.pal8, f.gif_scratch, f.gif, (uint32_t*)f.gif_total_dev, W, H, fs, done);
-            if (tm) tm->mark("gif_pack");
-        }
-    } else if (seq_dst) {
-        hipStream_t fs = side ? f.fmt_stream : s;
-        if (side) HIPCHK(c, hipStreamWaitEvent(fs, f.bgr_done, 0));
-        { int rc = seq_pass(c, f.out, seq_dst, fs, done); if (rc) return rc; }
-        if (tm) tm->mark("pal8_seq_hist");
-    }
+    if (!converts) return POPPY_OK;
+    hipStream_t fs = side ? f.fmt.fmt_stream : s;
+    if (side) HIPCHK(c, hipStreamWaitEvent(fs, f.fmt.bgr_done, 0));
+    if (!seq_dst) { enqueue_conversion(fmt, f.out, W, H, f.fmt, fs, done, tm); return POPPY_OK; }
+    { int rc = seq_pass(c, f.out, seq_dst, fs, done); if (rc) return rc; }
+    if (tm) tm->mark("pal8_seq_hist");
     return POPPY_OK;
 }
 
@@ -1293,83 +1023,6 @@ static int prepare_ahead(poppy_hip_ctx* c, const FramePlan& plan, double mask) {
     return rc;
 }
 
-// a PAL8 frame in device memory -> its POPPY_FRAME_GIF frame in `host` (exactly `total` bytes), on the context's stream and waited for: the frames that no slot renders,
-// and poppy_hip_pal8_to_gif_frame.  The buffers live for the call.
-static int gif_from_device_pal8(poppy_hip_ctx* c, const uint8_t* d_pal8, int W, int H, std::vector<uint8_t>& host) {
-    const size_t cap = poppy_frame_bytes(POPPY_FRAME_GIF, W, H);
-    uint8_t *work = nullptr, *frame = nullptr;
-    hipError_t e = hipMalloc((void**)&work, gif_scratch_bytes(W, H));
-    if (e == hipSuccess) e = hipMalloc((void**)&frame, cap + 16);
-    uint32_t total = 0;
-    if (e == hipSuccess) {
-        launch_gif_lzw(d_pal8, work, W, H, c->stream);
-        launch_gif_pack(d_pal8, work, frame, nullptr, W, H, c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && (total < 776 || total > cap)) { (void)hipFree(work); (void)hipFree(frame); return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds"); }
-    if (e == hipSuccess) { host.resize(total); e = hipMemcpy(host.data(), frame, total, hipMemcpyDeviceToHost); }
-    if (work) (void)hipFree(work);
-    if (frame) (void)hipFree(frame);
-    if (e != hipSuccess) { c->err = std::string("GIF frame coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
-    return POPPY_OK;
-}
-
-int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride, int n_copies) {
-    if (c->frame_format == POPPY_FRAME_PAL8_SEQ) {                 // the copies are the sequence: the host statement on the BGR frame
-        std::vector<uint8_t> bgr((size_t)W * H * 3);
-        HIPCHK(c, hipMemcpyAsync(bgr.data(), d_bgr, bgr.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        int rc = POPPY_OK;
-        const uint8_t* frame = host_frame(c, bgr.data(), (size_t)W * 3, W, H, host, stride, &rc, n_copies);
-        return frame ? POPPY_OK : rc;
-    }
-    if (c->frame_format == POPPY_FRAME_BGR) {
-        host.resize((size_t)W * H * 3);
-        *stride = (size_t)W * 3;
-        HIPCHK(c, hipMemcpyAsync(host.data(), d_bgr, host.size(), hipMemcpyDeviceToHost, c->stream));
-    } else {
-        const bool gif = c->frame_format == POPPY_FRAME_GIF, pal8 = c->frame_format == POPPY_FRAME_PAL8 || gif;
-        if (const char* why = format_refuses(c->frame_format, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
-        if (pal8 && !c->pal8_scratch_tables) { int rc = alloc_pal8_tables(c, &c->pal8_scratch_tables); if (rc) return rc; }
-        const size_t bytes = poppy_frame_bytes(gif ? POPPY_FRAME_PAL8 : c->frame_format, W, H);
-        if (bytes + 16 > c->i420_scratch_bytes) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->i420_scratch) (void)hipFree(c->i420_scratch);
-            c->i420_scratch = nullptr; c->i420_scratch_bytes = 0;
-            HIPCHK(c, hipMalloc((void**)&c->i420_scratch, bytes + 16));
-            c->i420_scratch_bytes = bytes + 16;
-        }
-        host.resize(bytes);
-        *stride = (size_t)W;
-        if (pal8) {
-            launch_pal8_hist(d_bgr, c->pal8_scratch_tables, W, H, c->stream);
-            launch_pal8_build(c->pal8_scratch_tables, c->i420_scratch, W, H, c->stream);
-            launch_pal8_remap(d_bgr, c->pal8_scratch_tables, c->i420_scratch, W, H, c->stream);
-        } else launch_bgr_to_i420(d_bgr, c->i420_scratch, W, H, c->stream);
-        HIPCHK(c, hipGetLastError());
-        if (gif) { *stride = 0; return gif_from_device_pal8(c, c->i420_scratch, W, H, host); }
-        HIPCHK(c, hipMemcpyAsync(host.data(), c->i420_scratch, bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return POPPY_OK;
-}
-
-const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status, int n_copies) {
-    *out_stride = stride;
-    *status = POPPY_OK;
-    if (c->frame_format == POPPY_FRAME_BGR) return bgr;
-    if (const char* why = format_refuses(c->frame_format, W, H)) { *status = fail(c, POPPY_E_UNSUPPORTED, why); return nullptr; }
-    tmp.resize(poppy_frame_bytes(c->frame_format, W, H));
-    const int rc = c->frame_format == POPPY_FRAME_PAL8_SEQ ? pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, tmp.data()) :
-                   c->frame_format == POPPY_FRAME_GIF ? poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data()) :
-                   c->frame_format == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
-    if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
-    *out_stride = c->frame_format == POPPY_FRAME_GIF ? 0 : (size_t)W;
-    return tmp.data();
-}
-
 int upload_image(poppy_hip_ctx* c, uint8_t* dst, const uint8_t* src, size_t stride, int W, int H) {
     // (tight rows go as one linear copy: kernels.h copy_rows_async; only images that really have padded rows — ROIs — pay the 2-D copy's slow path at odd widths)
     HIPCHK(c, copy_rows_async(dst, (size_t)W * 3, src, stride, (size_t)W * 3, H, hipMemcpyHostToDevice, c->stream));
@@ -1479,21 +1132,9 @@ int poppy_hip_morph_frames(poppy_hip_ctx* c, double phase, poppy_write_cb write,
     if (!c->pair_ready) return fail(c, POPPY_E_STATE, "no pair loaded");
     HIPCHK(c, hipSetDevice(c->device));
     const int N = c->cfg.number_of_frames;
-    if (write) { int rc = stage_host(c, (size_t)c->W * 3 * c->H); if (rc) return rc; }
     if (phase == 0 || phase == 1) {                            // src/poppy.hpp:54-70: N copies of image 1 / image 2, nothing rendered
         if (!write) return POPPY_OK;
-        const uint8_t* img = phase == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2);
-        if (c->frame_format != POPPY_FRAME_BGR) {
-            std::vector<uint8_t> host; size_t stride = 0;
-            int rc = download_frame(c, img, c->W, c->H, host, &stride, N); if (rc) return rc;
-            for (int j = 0; j < N; ++j) write(user, host.data(), c->W, c->H, stride);
-            return POPPY_OK;
-        }
-        const size_t row = (size_t)c->W * 3;
-        HIPCHK(c, hipMemcpyAsync(c->h_stage, img, row * c->H, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int j = 0; j < N; ++j) write(user, c->h_stage, c->W, c->H, row);
-        return POPPY_OK;
+        return write_device_image(c, phase == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2), c->W, c->H, N, write, user);
     }
     const int n = phase >= 0 ? 1 : N;                          // phase mode: exactly one frame (src/poppy.hpp:234-235)
     std::vector<double> ratio(n);
@@ -1505,34 +1146,21 @@ int poppy_hip_render_phases(poppy_hip_ctx* c, const double* t, int n, poppy_writ
     if (!c || (n > 0 && !t) || n < 0) return POPPY_E_ARG;
     if (!c->pair_ready) return fail(c, POPPY_E_STATE, "no pair loaded");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t row = (size_t)c->W * 3;
     // PAL8_SEQ: the call's frames, copies included, are one sequence: collected on the device, handed over at the end
-    const bool seq = write && n > 0 && c->frame_format == POPPY_FRAME_PAL8_SEQ;
+    const bool seq = n > 0 && writer_wants_sequence(c, write != nullptr);
     if (seq) { int rc = seq_begin(c, n); if (rc) return rc; }
     for (int i = 0; i < n;) {
+        int rc = POPPY_OK, j = i + 1;
         if (t[i] == 0 || t[i] == 1) {                             // a plain copy of image 1 / image 2
-            if (seq) {
-                int rc = seq_add_image(c, t[i] == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2));
-                if (rc) { const std::string why = c->err; (void)seq_abort(c); c->err = why; return rc; }
-            } else if (write && c->frame_format != POPPY_FRAME_BGR) {
-                std::vector<uint8_t> host; size_t stride = 0;
-                int rc = download_frame(c, t[i] == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2), c->W, c->H, host, &stride); if (rc) return rc;
-                write(user, host.data(), c->W, c->H, stride);
-            } else if (write) {
-                int rc = stage_host(c, row * c->H); if (rc) return rc;
-                const uint8_t* img = t[i] == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2);
-                HIPCHK(c, hipMemcpyAsync(c->h_stage, img, row * c->H, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                write(user, c->h_stage, c->W, c->H, row);
-            }
-            ++i;
-            continue;
+            const uint8_t* img = t[i] == 0 ? c->c1 : (c->c2_raw_valid ? c->c2_raw : c->c2);
+            if (seq) rc = seq_add_image(c, img);
+            else if (write) rc = write_device_image(c, img, c->W, c->H, 1, write, user);
+        } else {
+            while (j < n && t[j] != 0 && t[j] != 1) ++j;
+            rc = poppy_hip_pair_reset(c);
+            if (rc == POPPY_OK) rc = render_sequence(c, t + i, t + i, j - i, false, write, user, seq);
         }
-        int j = i;
-        while (j < n && t[j] != 0 && t[j] != 1) ++j;
-        int rc = poppy_hip_pair_reset(c);
-        if (rc == POPPY_OK) rc = render_sequence(c, t + i, t + i, j - i, false, write, user, seq);
-        if (rc) { if (seq) { const std::string why = c->err; (void)seq_abort(c); c->err = why; } return rc; }
+        if (rc) { if (seq) seq_abort_keep_error(c); return rc; }
         i = j;
     }
     return seq ? seq_finish(c, write, user) : POPPY_OK;
@@ -1563,23 +1191,14 @@ int poppy_hip_morph(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint
     if (!c) return POPPY_E_ARG;
     if (!bgr1 || !bgr2 || W <= 0 || H <= 0 || s1 < (size_t)W * 3 || s2 < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad image arguments");
     const int N = c->cfg.number_of_frames;
-    if (phase == 0 || phase == 1) {                            // src/poppy.hpp:54-70, before any feature work (I420: converted on the host, no GPU touched)
-        std::vector<uint8_t> tmp;
-        size_t stride = phase == 0 ? s1 : s2;
-        int frame_rc = POPPY_OK;
-        const uint8_t* img = (write && N > 0) ? host_frame(c, phase == 0 ? bgr1 : bgr2, stride, W, H, tmp, &stride, &frame_rc, N) : nullptr;
-        if (write && N > 0 && !img) return frame_rc;
-        for (int j = 0; j < N && write; ++j) write(user, img, W, H, stride);
-        return POPPY_OK;
-    }
+    if (phase == 0 || phase == 1)                              // src/poppy.hpp:54-70, before any feature work (converted on the host, no GPU touched)
+        return write && N > 0 ? write_host_image(c, phase == 0 ? bgr1 : bgr2, phase == 0 ? s1 : s2, W, H, N, write, user) : POPPY_OK;
     int rc = poppy_hip_pair_begin(c, bgr1, s1, bgr2, s2, W, H); if (rc) return rc;
     if (c->pts1_0.empty()) {                                   // :125-134 (see the header: the reference throws before reaching it)
         if (!distance && write) {
             std::vector<uint8_t> blend((size_t)W * 3 * H);
             rc = poppy_hip_dissolve(c, bgr1, s1, bgr2, s2, W, H, phase, blend.data(), (size_t)W * 3); if (rc) return rc;
-            size_t stride = (size_t)W * 3;
-            if (c->frame_format != POPPY_FRAME_BGR) { rc = download_frame(c, c->slots[0].out, W, H, blend, &stride, N); if (rc) return rc; }      // the blend, still in slot 0
-            for (int j = 0; j < N; ++j) write(user, blend.data(), W, H, stride);
+            rc = write_device_image(c, c->slots[0].out, W, H, N, write, user); if (rc) return rc;      // the blend, still in slot 0
         }
         return fail(c, POPPY_E_NOMATCH, "no point pairs: linear-blend fallback frames written (src/poppy.hpp:125-134)");
     }
@@ -1705,38 +1324,10 @@ int poppy_hip_timing_summary(poppy_hip_ctx* c, const char** names, float* total_
     return n;
 }
 
-int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
-    if (!c) return POPPY_E_ARG;
-    if (format != POPPY_FRAME_BGR && format != POPPY_FRAME_I420 && !is_pal8(format) && format != POPPY_FRAME_GIF) return fail(c, POPPY_E_ARG, "unknown frame format");
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc = drain_frames(c); if (rc) return rc; }
-    if (c->c1) if (const char* why = format_refuses(format, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
-    c->frame_format = format;
-    return c->c1 ? alloc_slot_format(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
-}
-
-int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* c, const uint8_t* pal8, int W, int H, uint8_t* dst) {
-    if (!c) return POPPY_E_ARG;
-    if (!pal8 || !dst || W <= 0 || H <= 0) return fail(c, POPPY_E_ARG, "bad arguments");
-    if (const char* why = format_refuses(POPPY_FRAME_GIF, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t bytes = poppy_frame_bytes(POPPY_FRAME_PAL8, W, H);
-    uint8_t* d_pal8 = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d_pal8, bytes + 16));
-    std::vector<uint8_t> host;
-    int rc = POPPY_OK;
-    if (hipMemcpy(d_pal8, pal8, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, POPPY_E_DEVICE, "upload of the PAL8 frame failed");
-    if (rc == POPPY_OK) rc = gif_from_device_pal8(c, d_pal8, W, H, host);
-    (void)hipFree(d_pal8);
-    if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
-    return rc;
-}
-
 int poppy_hip_render_many(poppy_hip_ctx* c, const double* shape, const double* mask, int n, int chain, poppy_write_cb write, void* user) {
     if (!c || !shape || !mask || n < 0) return POPPY_E_ARG;
     if (!c->pair_ready) return fail(c, POPPY_E_STATE, "no pair loaded");
     HIPCHK(c, hipSetDevice(c->device));
-    if (write) { int rc = stage_host(c, (size_t)c->W * 3 * c->H); if (rc) return rc; }
     return render_sequence(c, shape, mask, n, chain != 0, write, user);
 }
 
