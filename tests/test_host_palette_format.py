@@ -7,72 +7,14 @@ import os
 import numpy as np
 import pytest
 
-from palette_util import gif_decode, pal8_reference
+from palette_util import GOLDEN, frames, gif_decode, pal8_reference, photo
 from poppy_amd import capi, synth
 
-GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 E_ARG, E_UNSUPPORTED = -1, -6
-
-
-def cells_frame(cells, w, h, seed, one_colour=True):
-    """A w x h frame whose pixels occupy exactly the given cells (every cell at least once); one colour per cell, or any colour of the cell."""
-    rng = np.random.default_rng(seed)
-    cells = np.asarray(cells)
-    assert len(cells) <= w * h
-    pick = np.concatenate([np.arange(len(cells)), rng.integers(0, len(cells), w * h - len(cells))])
-    rng.shuffle(pick)
-    low = rng.integers(0, 8, (len(cells), 3)) if one_colour else None
-    c = cells[pick]
-    rgb = np.stack([(c >> 10) & 31, (c >> 5) & 31, c & 31], 1) * 8 + (low[pick] if one_colour else rng.integers(0, 8, (w * h, 3)))
-    return np.ascontiguousarray(rgb[:, ::-1].reshape(h, w, 3).astype(np.uint8))
-
-
-def photo(name):
-    return np.load(os.path.join(GOLDEN, "photo_pair_720x405.npz"))[name]
 
 
 def cars():
     return np.load(os.path.join(GOLDEN, "a_749x480_cars.npz"))["frame0"]
-
-
-def tie_frames():
-    out = {}
-    # two boxes of equal score: four colours, two pairs of equal count, each pair one cell apart on another axis
-    f = np.zeros((8, 8, 3), np.uint8)
-    f[:2, :] = (0, 0, 0); f[2:4, :] = (0, 0, 8); f[4:6, :] = (200, 200, 200); f[6:, :] = (200, 208, 200)
-    out["equal_scores"] = f
-    # sides of equal length: the corners of a cube of cells, equal counts -> the first cut is along G, then R, then B
-    f = np.zeros((8, 16, 3), np.uint8)
-    for k in range(8):
-        f[k, :] = (40 + 80 * (k & 1), 40 + 80 * ((k >> 1) & 1), 40 + 80 * ((k >> 2) & 1))
-    out["equal_sides"] = f
-    # equal sides on R and B only (G flat), and a median that falls on the last position (clamped to k < hi)
-    f = np.zeros((4, 10, 3), np.uint8)
-    f[:, :9] = (16, 100, 16); f[:, 9] = (48, 100, 48)
-    out["rb_tie_clamped"] = f
-    rng = np.random.default_rng(5)
-    g = rng.integers(0, 4, (40, 40, 3)) * 64                                         # 64 colours on a lattice: many equal extents and counts
-    out["lattice"] = g.astype(np.uint8)
-    return out
-
-
-def frames():
-    rng = np.random.default_rng(11)
-    out = {"random_97x61": rng.integers(0, 256, (61, 97, 3), dtype=np.uint8),
-           "random_256x256": rng.integers(0, 256, (256, 256, 3), dtype=np.uint8),
-           "textured_640x360": synth.textured_bgr(640, 360, 3),
-           "photo_a": photo("a"), "photo_b": photo("b"),
-           "flat": np.full((30, 50, 3), (12, 200, 99), np.uint8),
-           "cells_256": cells_frame(rng.choice(32768, 256, replace=False), 64, 40, 1),
-           "cells_257": cells_frame(rng.choice(32768, 257, replace=False), 64, 40, 2),
-           "cells_257_any_colour": cells_frame(rng.choice(32768, 257, replace=False), 64, 40, 3, one_colour=False),
-           "1x1": rng.integers(0, 256, (1, 1, 3), dtype=np.uint8), "1x7": rng.integers(0, 256, (7, 1, 3), dtype=np.uint8),
-           "5x3": rng.integers(0, 256, (3, 5, 3), dtype=np.uint8), "odd_749x31": synth.textured_bgr(749, 31, 9)}
-    two = np.zeros((20, 33, 3), np.uint8)
-    two[:, :11] = (250, 3, 77); two[:, 11:] = (4, 180, 90)
-    out["two_tone"] = two
-    out.update(tie_frames())
-    return out
 
 
 FRAMES = frames()
