@@ -211,12 +211,29 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  *   Limits, refused with POPPY_E_UNSUPPORTED before any state changes: PAL8's 2^24 pixels, and a width or height above 65535 (GIF's 16-bit descriptor).
  * poppy_pal8_to_gif_frame is the host statement (pal8: a PAL8 frame of poppy_frame_bytes(POPPY_FRAME_PAL8, ..) bytes; dst: the capacity), poppy_bgr_to_gif_frame
  * is poppy_bgr_to_pal8 followed by it.  poppy_hip_pal8_to_gif_frame codes a host PAL8 frame on the context's GPU (upload, the two kernels, download of `total`
- * bytes): the same bytes.  The format applies wherever PAL8 applies and stays BGR wherever PAL8 stays BGR.  */
+ * bytes): the same bytes.  The format applies wherever PAL8 applies and stays BGR wherever PAL8 stays BGR.
+ *
+ * POPPY_FRAME_GIF_SEQ: the coded form of POPPY_FRAME_PAL8_SEQ — ONE palette for the whole sequence and every frame's indices LZW-coded on the GPU, so that a GIF
+ * with a single global colour table (POPPY_SINK_GIF_GLOBAL_CODED) is written without any coding on the host.  Its value is 128, and POPPY_SINK_GIF_GLOBAL_CODED is
+ * 128: 32, 63 and 65 are tested as unknown formats, 127 and 129 stay unknown.  A frame has POPPY_FRAME_GIF's layout, capacity and limits (poppy_frame_bytes gives
+ * the same value for both, poppy_gif_frame_bytes reads both, the writer gets stride = 0).
+ *   The rule is the composition of the two above: frame k of a sequence is poppy_pal8_to_gif_frame of frame k of poppy_bgr_frames_to_pal8 over the same frames.
+ *      All frames of a sequence therefore carry the same 768 palette bytes, and a sequence of one frame is byte for byte that frame's POPPY_FRAME_GIF.  There is
+ *      no delta coding and no transparency: every frame is coded whole.
+ *   A sequence and its hand-over are PAL8_SEQ's: one call's frames, each pair in lists and pools; the writer is first called after the last frame has been rendered,
+ *      then once per frame in order; nothing is written if a frame fails.  On the device the coder reads each frame's BGR where it waits for the palette, through
+ *      the sequence's cell -> index table: the index plane is never stored.
+ *   Limits, POPPY_E_UNSUPPORTED before any state changes: PAL8_SEQ's (2^24 pixels per frame, fewer than 2^32 per sequence) and GIF's 65535 per side.
+ * poppy_bgr_frames_to_gif_frames is the host statement (poppy_bgr_frames_to_pal8's arguments): frame k goes to dst + k * poppy_frame_bytes(POPPY_FRAME_GIF_SEQ,
+ * width, height).  Its refusals are poppy_bgr_frames_to_pal8's plus the 65535 limit; nothing is read or written before them.
+ * poppy_hip_bgr_frames_to_gif_frames does the same on the context's GPU (upload into a store that lives for the call, the sequence pass per frame, the palette
+ * build, the coder and the gather per frame, download of each frame's `total` bytes): the same bytes.  It needs no resident pair and disturbs none; while the
+ * context has a sequence open it returns POPPY_E_STATE.  The format applies wherever PAL8_SEQ applies and stays BGR wherever PAL8_SEQ stays BGR.  */
 #define POPPY_PAL8_MAX_PIXELS (1 << 24)
 #define POPPY_PAL8_SEQ_MAX_PIXELS (1ull << 32)
 #define POPPY_GIF_SEGMENT_PIXELS 2048
 #define POPPY_GIF_SEGMENT_BYTES ((9 + 12 * (POPPY_GIF_SEGMENT_PIXELS + 2) + 63 + 7) / 8)
-enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64 };
+enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
@@ -226,6 +243,8 @@ size_t poppy_gif_frame_bytes(const uint8_t* frame);
 int poppy_pal8_to_gif_frame(const uint8_t* pal8, int width, int height, uint8_t* dst);
 int poppy_bgr_to_gif_frame(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* ctx, const uint8_t* pal8, int width, int height, uint8_t* dst);
+int poppy_bgr_frames_to_gif_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst);
+int poppy_hip_bgr_frames_to_gif_frames(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst);
 /* phase == 0 / phase == 1 follow the reference's short-circuit (src/poppy.hpp:54-70): number_of_frames copies of image 1 /
  * image 2 as they were handed to the pair set-up (with auto-align: the UNALIGNED image 2), no frame is rendered.            */
 
@@ -560,11 +579,15 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * GIF_CODED: POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames (stride must be 0): header, NETSCAPE2.0 block, and per frame the graphic control extension, the
  * descriptor with a local table, the frame's palette, then the frame's bytes 772 .. total as they are.  Decodes to the pixels the GIF sink's file decodes to; its
  * length is 0.99 - 1.16 times that file's on the measured inputs (every segment of the coded form starts a new table).  A frame of any other format fails this sink, and a coded frame fails every other sink.
+ * GIF_GLOBAL_CODED: POPPY_SINK_GIF_GLOBAL's file from coded frames (POPPY_FRAME_GIF_SEQ; stride must be 0): the header waits for the first frame, whose palette becomes the
+ * 256-entry global table (flags 0xF7); a frame whose palette equals it gets a descriptor with flags 0x00 and no local table, then its bytes 772 .. total as they
+ * are; a frame whose palette differs gets a local table (0x87), so POPPY_FRAME_GIF frames and the frames of several pairs are taken too.  A raster frame fails this
+ * sink; no frame at all gives GIF's empty file.
  * The BGR sinks take frames with stride >= 3 * width, the I420 and GIF sinks frames with stride == width: a frame of another format fails the
  * sink where its stride tells (a BGR frame at the I420 or GIF sink, an I420 or PAL8 frame at a BGR sink); a writer must match the context's format.
  * poppy_sink_close returns the number of frames written, or a negative status if a write failed or a frame had another geometry.   */
 typedef struct poppy_sink poppy_sink;
-enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8, POPPY_SINK_GIF_GLOBAL = 16, POPPY_SINK_GIF_CODED = 64 };
+enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8, POPPY_SINK_GIF_GLOBAL = 16, POPPY_SINK_GIF_CODED = 64, POPPY_SINK_GIF_GLOBAL_CODED = 128 };
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den);
 void poppy_sink_write(void* sink, const uint8_t* bgr, int width, int height, size_t stride);
 int poppy_sink_close(poppy_sink* sink);

@@ -25,8 +25,8 @@ WARP_KERNELS = ("k_warp_bin", "k_warp_tile", "k_warp4")        # order of poppy_
 PYRAMID_FORMS = ("down", "down2", "tail", "tail_nl", "mix_top", "cone", "up2", "up", "unsharp")
 WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_size_t)
 # formats of the frames handed to writers (poppy_hip_set_frame_format) and the file sinks (poppy_sink_open)
-FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF = 0, 1, 8, 16, 64
-SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED = 0, 1, 2, 3, 8, 16, 64
+FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF, FRAME_GIF_SEQ = 0, 1, 8, 16, 64, 128
+SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED, SINK_GIF_GLOBAL_CODED = 0, 1, 2, 3, 8, 16, 64, 128
 
 # every symbol include/poppy_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -46,6 +46,7 @@ SYMBOLS = [
     "poppy_hip_last_pyramid_forms",
     "poppy_hip_set_frame_format", "poppy_hip_pool_set_frame_format", "poppy_frame_bytes", "poppy_bgr_to_i420", "poppy_bgr_to_pal8", "poppy_bgr_frames_to_pal8",
     "poppy_gif_frame_bytes", "poppy_pal8_to_gif_frame", "poppy_bgr_to_gif_frame", "poppy_hip_pal8_to_gif_frame",
+    "poppy_bgr_frames_to_gif_frames", "poppy_hip_bgr_frames_to_gif_frames",
 ]
 
 
@@ -173,6 +174,8 @@ def lib():
         L.poppy_pal8_to_gif_frame.argtypes = [vp, i, i, vp]
         L.poppy_bgr_to_gif_frame.argtypes = [vp, sz, i, i, vp]
         L.poppy_hip_pal8_to_gif_frame.argtypes = [vp, vp, i, i, vp]
+        L.poppy_bgr_frames_to_gif_frames.argtypes = [vp, sz, sz, i, i, i, vp]
+        L.poppy_hip_bgr_frames_to_gif_frames.argtypes = [vp, vp, sz, sz, i, i, i, vp]
         L.poppy_hypotf_selfcheck.restype = C.c_long
         L.poppy_hypotf_selfcheck.argtypes = [C.c_long, C.c_uint64]
         _lib = L
@@ -184,7 +187,7 @@ def _p(a):
 
 
 def frame_bytes(fmt, w, h):
-    """Host-only: bytes of a w x h frame in format fmt (FRAME_BGR / FRAME_I420 / FRAME_PAL8 / FRAME_PAL8_SEQ; FRAME_GIF: the capacity, an upper bound for any
+    """Host-only: bytes of a w x h frame in format fmt (FRAME_BGR / FRAME_I420 / FRAME_PAL8 / FRAME_PAL8_SEQ; FRAME_GIF and FRAME_GIF_SEQ: the capacity, an upper bound for any
     content — a frame's own length is gif_frame_bytes; 0 for anything else)."""
     return int(lib().poppy_frame_bytes(int(fmt), int(w), int(h)))
 
@@ -268,6 +271,29 @@ def bgr_to_gif_frame(bgr):
     return _gif_frame(lambda out: lib().poppy_bgr_to_gif_frame(_p(a), w * 3, w, h, _p(out)), "poppy_bgr_to_gif_frame", w, h)
 
 
+def _gif_frames(call, chk, frames, row_pad, frame_pad):
+    a = np.ascontiguousarray(frames, np.uint8)
+    n, h, w = a.shape[:3]
+    stride = w * 3 + int(row_pad)
+    frame_stride = stride * h + int(frame_pad)
+    if row_pad or frame_pad:
+        buf = np.full((n, frame_stride), 0xA5, np.uint8)
+        buf[:, :stride * h].reshape(n, h, stride)[:, :, :w * 3] = a.reshape(n, h, w * 3)
+        a = buf
+    out = np.empty((n, max(frame_bytes(FRAME_GIF_SEQ, w, h), 4)), np.uint8)
+    chk(call(_p(a), stride, frame_stride, n, w, h, _p(out)))
+    return [f[:gif_frame_bytes(f)].copy() for f in out]
+
+
+def bgr_frames_to_gif_frames(frames, row_pad=0, frame_pad=0):
+    """Host-only: the library's GIF_SEQ frames of a sequence of n HxWx3 BGR frames (poppy_bgr_frames_to_gif_frames = bgr_frames_to_pal8, then pal8_to_gif_frame
+    of every frame): a list of n flat uint8 arrays, each cut to its `total`.  row_pad / frame_pad: as in bgr_frames_to_pal8."""
+    def chk(rc):
+        if rc:
+            raise PoppyError(f"poppy_bgr_frames_to_gif_frames: {rc}")
+    return _gif_frames(lib().poppy_bgr_frames_to_gif_frames, chk, frames, row_pad, frame_pad)
+
+
 def pal8_to_bgr(frame, w, h):
     """palette[index] of a flat PAL8 frame, as an HxWx3 BGR array (what a viewer of the frame sees)."""
     f = np.asarray(frame, np.uint8)
@@ -275,8 +301,8 @@ def pal8_to_bgr(frame, w, h):
 
 
 def _frame_view(ptr, w, h, stride, fmt):
-    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF.  A view: valid during the callback."""
-    if fmt == FRAME_GIF:                                        # a coded frame: its own length, not the capacity
+    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF and GIF_SEQ.  A view: valid during the callback."""
+    if fmt in (FRAME_GIF, FRAME_GIF_SEQ):                                        # a coded frame: its own length, not the capacity
         return np.ctypeslib.as_array(ptr, shape=(int(lib().poppy_gif_frame_bytes(ptr)),))
     if fmt in (FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ):
         return np.ctypeslib.as_array(ptr, shape=(frame_bytes(fmt, w, h),))
@@ -522,7 +548,7 @@ class Pool:
         self.frame_format = FRAME_BGR
 
     def set_frame_format(self, fmt):
-        """FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ (one palette per pair) or FRAME_GIF for every context of the pool (poppy_hip_pool_set_frame_format); PoppyError with the status while submitted
+        """FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ (one palette per pair) FRAME_GIF or FRAME_GIF_SEQ (FRAME_PAL8_SEQ coded) for every context of the pool (poppy_hip_pool_set_frame_format); PoppyError with the status while submitted
         batches have not been waited for."""
         rc = lib().poppy_hip_pool_set_frame_format(self.h, int(fmt))
         if rc:
@@ -672,7 +698,8 @@ class Context:
     def set_frame_format(self, fmt):
         """FRAME_BGR (default), FRAME_I420, FRAME_PAL8 or FRAME_PAL8_SEQ (one palette for all frames of a call, which are handed over when the last
         one is rendered): the format of every frame handed to a writer (poppy_hip_set_frame_format).  Under I420 and both PAL8 formats the collecting wrappers return flat uint8 arrays of frame_bytes(format, W, H).
-        FRAME_GIF: PAL8 frames with the indices LZW-coded on the GPU; the wrappers return flat arrays of each frame's own length (gif_frame_bytes)."""
+        FRAME_GIF: PAL8 frames with the indices LZW-coded on the GPU; the wrappers return flat arrays of each frame's own length (gif_frame_bytes).
+        FRAME_GIF_SEQ: FRAME_PAL8_SEQ's sequences with every frame coded like FRAME_GIF's, one palette in all frames of a call."""
         self._chk(lib().poppy_hip_set_frame_format(self.h, int(fmt)), "set_frame_format")
         self.frame_format = int(fmt)
 
@@ -685,6 +712,11 @@ class Context:
         out = np.empty(max(frame_bytes(FRAME_GIF, w, h), 4), np.uint8)
         self._chk(lib().poppy_hip_pal8_to_gif_frame(self.h, _p(a), int(w), int(h), _p(out)), "pal8_to_gif_frame")
         return out[:gif_frame_bytes(out)].copy()
+
+    def bgr_frames_to_gif_frames(self, frames, row_pad=0, frame_pad=0):
+        """The FRAME_GIF_SEQ frames of a sequence of n HxWx3 BGR frames, palette and coding on this context's GPU (poppy_hip_bgr_frames_to_gif_frames: upload, the
+        sequence pass per frame, the palette build, the coder and the gather per frame, download): the bytes of the host's bgr_frames_to_gif_frames, as its list."""
+        return _gif_frames(lambda *args: lib().poppy_hip_bgr_frames_to_gif_frames(self.h, *args), lambda rc: self._chk(rc, "bgr_frames_to_gif_frames"), frames, row_pad, frame_pad)
 
     def close(self):
         if self.h:

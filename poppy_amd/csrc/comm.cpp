@@ -926,7 +926,7 @@ int poppy_hip_pool_warp_counts(poppy_hip_pool* p, unsigned long long* fused, uns
 }
 
 int poppy_hip_pool_set_frame_format(poppy_hip_pool* p, int format) {
-    if (!p || (format != POPPY_FRAME_BGR && format != POPPY_FRAME_I420 && format != POPPY_FRAME_PAL8 && format != POPPY_FRAME_PAL8_SEQ && format != POPPY_FRAME_GIF)) return POPPY_E_ARG;
+    if (!p || !format_known(format)) return POPPY_E_ARG;
     {
         std::lock_guard<std::mutex> lk(p->q_mu);
         if (p->unwaited || p->outstanding) return POPPY_E_STATE;                 // the feeders' contexts may be rendering

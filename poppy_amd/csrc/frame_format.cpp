@@ -3,20 +3,25 @@
 #include "context.h"
 
 static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H <= (unsigned long long)POPPY_PAL8_MAX_PIXELS; }
-constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF take frames of at most 2^24 pixels";
-constexpr const char* kGifSizeMsg = "POPPY_FRAME_GIF takes frames of at most 65535 pixels in width and height";
+constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 2^24 pixels";
+constexpr const char* kGifSizeMsg = "POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 65535 pixels in width and height";
+constexpr const char* kSeqSizeMsg = "POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ take sequences of fewer than 2^32 pixels in all";
 
 bool format_known(int fmt) {
-    return fmt == POPPY_FRAME_BGR || fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF;
+    return fmt == POPPY_FRAME_BGR || fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ;
 }
 const char* format_refuses(int fmt, int W, int H) {
-    if ((format_builds_palette(fmt) || fmt == POPPY_FRAME_PAL8_SEQ) && !pal8_fits(W, H)) return kPal8SizeMsg;
-    if (fmt == POPPY_FRAME_GIF && (W > 65535 || H > 65535)) return kGifSizeMsg;
+    if ((format_builds_palette(fmt) || format_is_sequence(fmt)) && !pal8_fits(W, H)) return kPal8SizeMsg;
+    if (format_is_coded(fmt) && (W > 65535 || H > 65535)) return kGifSizeMsg;
     return nullptr;
+}
+static const char* sequence_refuses(int fmt, int n, int W, int H) {
+    if (const char* why = format_refuses(fmt, W, H)) return why;
+    return (unsigned long long)n * (unsigned long long)W * (unsigned long long)H >= POPPY_PAL8_SEQ_MAX_PIXELS ? kSeqSizeMsg : nullptr;
 }
 size_t writer_stride(int fmt, int W) { return format_is_coded(fmt) ? 0 : fmt == POPPY_FRAME_BGR ? (size_t)W * 3 : (size_t)W; }
 int writer_format(const poppy_hip_ctx* c, bool has_writer) { return has_writer ? c->frame_format : POPPY_FRAME_BGR; }
-bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer) { return has_writer && c->frame_format == POPPY_FRAME_PAL8_SEQ; }
+bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer) { return has_writer && format_is_sequence(c->frame_format); }
 
 // conversion tables, zero before the first frame (the palette builds leave them zero again): PAL8's per slot and for the scratch, the sequence's per context
 static int alloc_zeroed_tables(poppy_hip_ctx* c, uint8_t** tables, size_t bytes) {
@@ -28,7 +33,7 @@ static int alloc_zeroed_tables(poppy_hip_ctx* c, uint8_t** tables, size_t bytes)
     return POPPY_OK;
 }
 
-// a slot's conversion side stream and the event that rides on its unsharp (PAL8, PAL8_SEQ and GIF; they live as long as the context)
+// a slot's conversion side stream and the event that rides on its unsharp (the palette formats; they live as long as the context)
 static int alloc_slot_side(poppy_hip_ctx* c, SlotFormat& f) {
     // The side streams are created at the LOWEST stream priority.  The runtime keeps its hardware queues per priority, so they never share a queue with the
     // chain's stream or the plan upload's (normal priority): a dispatch waits for the one before it in its hardware queue whatever its stream, and a
@@ -43,8 +48,8 @@ static int alloc_slot_side(poppy_hip_ctx* c, SlotFormat& f) {
 }
 
 // I420: the slot's I420 buffer.  PAL8: its PAL8 buffer, tables, side stream and event.  GIF: PAL8's (the coder reads the slot's PAL8 frame) and the coded frame, the
-// coder's scratch and the pinned length word.  PAL8_SEQ: the slots' side streams and the context's sequence tables — the store and the index ring depend on the
-// sequence's length: seq_begin, seq_finish.
+// coder's scratch and the pinned length word.  PAL8_SEQ and GIF_SEQ: the slots' side streams and the context's sequence tables — the store and the index ring depend on the
+// sequence's length and, under GIF_SEQ, the ring of coded frames: seq_begin, seq_finish.
 int alloc_slot_format(poppy_hip_ctx* c) {
     const int fmt = c->frame_format, W = c->W, H = c->H;
     if (const char* why = format_refuses(fmt, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
@@ -55,8 +60,8 @@ int alloc_slot_format(poppy_hip_ctx* c) {
             if (!f.pal8) HIPCHK(c, hipMalloc((void**)&f.pal8, poppy_frame_bytes(POPPY_FRAME_PAL8, W, H) + 16));
             int rc = alloc_zeroed_tables(c, &f.pal8_tables, kPal8TableBytes); if (rc) return rc;
         }
-        if (format_builds_palette(fmt) || fmt == POPPY_FRAME_PAL8_SEQ) { int rc = alloc_slot_side(c, f); if (rc) return rc; }
-        if (fmt != POPPY_FRAME_GIF) continue;
+        if (format_builds_palette(fmt) || format_is_sequence(fmt)) { int rc = alloc_slot_side(c, f); if (rc) return rc; }
+        if (fmt != POPPY_FRAME_GIF) continue;                       // (the slot's coded frame: GIF_SEQ codes from the store into the sequence's ring)
         if (!f.gif) HIPCHK(c, hipMalloc((void**)&f.gif, poppy_frame_bytes(fmt, W, H) + 16));
         if (!f.gif_scratch) HIPCHK(c, hipMalloc((void**)&f.gif_scratch, gif_scratch_bytes(W, H)));
         if (!f.gif_total) {
@@ -65,7 +70,7 @@ int alloc_slot_format(poppy_hip_ctx* c) {
             *f.gif_total = 0;
         }
     }
-    return fmt == POPPY_FRAME_PAL8_SEQ ? alloc_zeroed_tables(c, &c->seq.tables, kPal8SeqTableBytes) : POPPY_OK;
+    return format_is_sequence(fmt) ? alloc_zeroed_tables(c, &c->seq.tables, kPal8SeqTableBytes) : POPPY_OK;
 }
 
 void free_slot_format_pair(SlotFormat& f) {
@@ -79,7 +84,8 @@ void free_slot_format_ctx(SlotFormat& f) {
     if (f.bgr_done) (void)hipEventDestroy(f.bgr_done);
 }
 void free_context_format(poppy_hip_ctx* c) {
-    for (uint8_t* b : {c->fmt_scratch, c->fmt_scratch_tables, c->seq.tables, c->seq.store, c->seq.idx}) if (b) (void)hipFree(b);
+    for (uint8_t* b : {c->fmt_scratch, c->fmt_scratch_tables, c->seq.tables, c->seq.store, c->seq.idx, c->seq.gif}) if (b) (void)hipFree(b);
+    if (c->seq.gif_total) (void)hipHostFree(c->seq.gif_total);
     c->fmt_scratch = c->fmt_scratch_tables = nullptr; c->fmt_scratch_bytes = 0;
     c->seq = PaletteSeq();
 }
@@ -87,7 +93,7 @@ void free_context_format(poppy_hip_ctx* c) {
 bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt) {
     const SlotFormat& f = slot.fmt;
     if (fmt == POPPY_FRAME_I420) return f.i420 != nullptr;
-    if (fmt == POPPY_FRAME_PAL8_SEQ) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
+    if (format_is_sequence(fmt)) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
     if (format_builds_palette(fmt) && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) return false;
     return fmt != POPPY_FRAME_GIF || (f.gif && f.gif_scratch && f.gif_total);
 }
@@ -128,9 +134,7 @@ int seq_begin(poppy_hip_ctx* c, int n) {
     const int W = c->W, H = c->H;
     PaletteSeq& q = c->seq;
     if (q.open) { int rc = seq_abort(c); if (rc) return rc; }      // (a sequence that a device error left open: its frames and sums are dropped, not mixed into this one)
-    if (const char* why = format_refuses(POPPY_FRAME_PAL8_SEQ, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
-    if ((unsigned long long)n * (unsigned long long)W * (unsigned long long)H >= POPPY_PAL8_SEQ_MAX_PIXELS)
-        return fail(c, POPPY_E_UNSUPPORTED, "POPPY_FRAME_PAL8_SEQ takes sequences of fewer than 2^32 pixels in all");
+    if (const char* why = sequence_refuses(c->frame_format, n, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);      // (a sequence format: writer_wants_sequence)
     { int rc = alloc_slot_format(c); if (rc) return rc; }
     const size_t stride = ((size_t)W * H * 3 + 15) & ~(size_t)15, need = stride * (size_t)n;      // (every frame's place begins on a 16-byte boundary)
     if (need > q.store_bytes) {
@@ -169,24 +173,15 @@ int seq_abort(poppy_hip_ctx* c) {
 }
 void seq_abort_keep_error(poppy_hip_ctx* c) { const std::string why = c->err; (void)seq_abort(c); c->err = why; }
 
-static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
+// Every frame as PAL8_SEQ: the index plane from the store through a ring of R device planes and R pinned buffers, remap and copy in order on the ring buffer's own
+// stream (render_sequence_frames: no event behind a copy), the palette behind the indices on the host.
+static int seq_hand_over_indices(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
     PaletteSeq& q = c->seq;
     const int n = q.count, W = c->W, H = c->H;
-    q.open = false;
-    { int rc = drain_frames(c); if (rc) return rc; }              // every pass has added its frame (they ran on the slots' streams)
     const bool marks = c->timing == 1;
-    {
-        Timer tm(c, c->stream);
-        if (marks) tm.mark(nullptr);
-        launch_pal8_seq_build(q.tables, c->stream);
-        if (marks) tm.mark("pal8_seq_build");
-    }
-    HIPCHK(c, hipGetLastError());
     uint8_t pal[768];
     HIPCHK(c, hipMemcpyAsync(pal, q.tables + kPal8SeqPaletteOffset, 768, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    // Every frame: the index plane from the store through a ring of R device planes and R pinned buffers, remap and copy in order on the ring buffer's own stream
-    // (render_sequence_frames: no event behind a copy), the palette behind the indices on the host.
     const size_t n_px = (size_t)W * H, plane = (n_px + 255) & ~(size_t)255;
     WriterRing ring;
     { int rc = ring.open(c, n_px + 768, false); if (rc) return rc; }
@@ -218,6 +213,121 @@ static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
     }
     while (ring.written < n) { int rc = deliver(); if (rc) return rc; }
     return POPPY_OK;
+}
+
+// the coding pair of one frame of a sequence: from its BGR (its place in a sequence store) through seq_tables, into `frame`; the length also into total_dev (null: none)
+static void enqueue_seq_gif_coding(const uint8_t* bgr, const uint8_t* seq_tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, Timer* tm) {
+    launch_gif_lzw_bgr(bgr, seq_tables, scratch, W, H, s);
+    if (tm) tm->mark("gif_lzw");
+    launch_gif_pack_seq(seq_tables, scratch, frame, (uint32_t*)total_dev, W, H, s);
+    if (tm) tm->mark("gif_pack");
+}
+
+// Every frame as GIF_SEQ: coded from its place in the store (k_gif_lzw_bgr: no index plane) into one of R device buffers, each followed by the coder's scratch, on the
+// ring buffer's own stream; k_gif_pack stores the frame's length into the ring buffer's pinned word.  The host waits for that stream, reads the word, bounds-checks it
+// as slot_frame_length does and queues the copy of exactly that many bytes on the same stream — no event behind a copy.  Frame k + 1 is being coded (on the next ring
+// buffer's stream) while the host waits for frame k's length, its copy runs and the writer has the frames before it; the writer gets the frames in order.
+static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
+    PaletteSeq& q = c->seq;
+    const int n = q.count, W = c->W, H = c->H;
+    const bool marks = c->timing == 1;
+    const size_t capacity = poppy_frame_bytes(POPPY_FRAME_GIF_SEQ, W, H), frame_part = (capacity + 16 + 255) & ~(size_t)255;
+    const size_t each = frame_part + ((gif_scratch_bytes(W, H) + 255) & ~(size_t)255);
+    WriterRing ring;
+    { int rc = ring.open(c, capacity, false); if (rc) return rc; }
+    if (each * ring.R > q.gif_bytes) {
+        if (q.gif) (void)hipFree(q.gif);
+        q.gif = nullptr; q.gif_bytes = 0;
+        HIPCHK(c, hipMalloc((void**)&q.gif, each * ring.R));
+        q.gif_bytes = each * ring.R;
+    }
+    if (!q.gif_total) {
+        HIPCHK(c, hipHostMalloc((void**)&q.gif_total, 64 * poppy_hip_ctx::kStageRing, hipHostMallocMapped));
+        HIPCHK(c, hipHostGetDevicePointer((void**)&q.gif_total_dev, q.gif_total, 0));
+    }
+    auto d_frame = [&](int k) { return q.gif + (size_t)(k % ring.R) * each; };
+    auto total_word = [&](int k) { return (volatile uint32_t*)((uint8_t*)q.gif_total + 64 * (size_t)(k % ring.R)); };
+#ifdef POPPY_EXPERIMENTS
+    const bool two_dispatch = getenv("POPPY_GIF_SEQ_TWO_DISPATCH") != nullptr;      // timing experiment, read per sequence so that one process alternates: the index plane through HBM (k_pal8_remap, then k_gif_lzw); the same bytes
+#endif
+    int coded = 0;                                                 // frames 0 .. coded - 1: their coding is queued; ring.issued: their copies are
+    auto code_next = [&]() -> int {
+        const int k = coded;
+        hipStream_t s = nullptr;
+        HIPCHK(c, ring.stream(c, k, &s));
+        *total_word(k) = 0;                                        // (the buffer's last frame has been handed over: nothing writes the word now)
+        Timer tm(c, s);
+        if (marks) tm.mark(nullptr);
+#ifdef POPPY_EXPERIMENTS
+        if (two_dispatch) {
+            uint8_t* d_idx = q.idx + (size_t)(k % ring.R) * (((size_t)W * H + 255) & ~(size_t)255);
+            launch_pal8_seq_remap(q.store + (size_t)k * q.stride, q.tables, d_idx, W, H, s);
+            if (marks) tm.mark("frame_format");
+            launch_gif_lzw(d_idx, d_frame(k) + frame_part, W, H, s);
+            if (marks) tm.mark("gif_lzw");
+            launch_gif_pack_seq(q.tables, d_frame(k) + frame_part, d_frame(k), (uint32_t*)(q.gif_total_dev + 64 * (size_t)(k % ring.R)), W, H, s);
+            if (marks) tm.mark("gif_pack");
+        } else
+#endif
+        enqueue_seq_gif_coding(q.store + (size_t)k * q.stride, q.tables, d_frame(k) + frame_part, d_frame(k), q.gif_total_dev + 64 * (size_t)(k % ring.R), W, H, s, marks ? &tm : nullptr);
+        HIPCHK(c, hipGetLastError());
+        ++coded;
+        return POPPY_OK;
+    };
+    auto copy_next = [&]() -> int {
+        const int k = ring.issued;
+        hipStream_t s = nullptr;
+        HIPCHK(c, ring.stream(c, k, &s));
+        HIPCHK(c, hipStreamSynchronize(s));                        // the frame is coded, its length is in the pinned word
+        const size_t total = *total_word(k);
+        if (total < 776 || total > capacity) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+        HIPCHK(c, hipMemcpyAsync(ring.buffer(k), d_frame(k), total, hipMemcpyDeviceToHost, s));
+        ++ring.issued;
+        return POPPY_OK;
+    };
+    auto deliver = [&]() -> int {
+        if (ring.issued == ring.written) { int rc = copy_next(); if (rc) return rc; }
+        uint8_t* frame = nullptr;
+        HIPCHK(c, ring.deliver_next(c, false, &frame));
+        write(user, frame, W, H, writer_stride(POPPY_FRAME_GIF_SEQ, W));
+        return POPPY_OK;
+    };
+#ifdef POPPY_EXPERIMENTS
+    {
+        const size_t plane = ((size_t)W * H + 255) & ~(size_t)255;
+        if (plane * ring.R > q.idx_bytes) {
+            if (q.idx) (void)hipFree(q.idx);
+            q.idx = nullptr; q.idx_bytes = 0;
+            HIPCHK(c, hipMalloc((void**)&q.idx, plane * ring.R));
+            q.idx_bytes = plane * ring.R;
+        }
+    }
+#endif
+    int rc = POPPY_OK;
+    while (coded < n && rc == POPPY_OK) {
+        if (coded >= ring.R) rc = deliver();                       // frame coded - R has left its ring buffer, device and pinned
+        if (rc == POPPY_OK) rc = code_next();
+        if (rc == POPPY_OK && ring.issued < coded - 1) rc = copy_next();      // the frame before it, while this one is coded
+    }
+    while (ring.written < n && rc == POPPY_OK) rc = deliver();
+    if (rc) for (int r = 0; r < ring.R; ++r) if (c->dl_ring[r]) (void)hipStreamSynchronize(c->dl_ring[r]);      // nothing writes the ring's buffers or words behind a failure
+    return rc;
+}
+
+static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
+    PaletteSeq& q = c->seq;
+    q.open = false;
+    { int rc = drain_frames(c); if (rc) return rc; }              // every pass has added its frame (they ran on the slots' streams)
+    {
+        Timer tm(c, c->stream);
+        if (c->timing == 1) tm.mark(nullptr);
+        launch_pal8_seq_build(q.tables, c->stream);
+        if (c->timing == 1) tm.mark("pal8_seq_build");
+    }
+    HIPCHK(c, hipGetLastError());
+    if (!format_is_coded(c->frame_format)) return seq_hand_over_indices(c, write, user);
+    HIPCHK(c, hipStreamSynchronize(c->stream));                   // the ring's streams read the tables
+    return seq_hand_over_coded(c, write, user);
 }
 
 int seq_finish(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
@@ -279,7 +389,7 @@ static int gif_from_device_pal8(poppy_hip_ctx* c, const uint8_t* d_pal8, int W, 
 
 int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride, int n_copies) {
     const int fmt = c->frame_format;
-    if (fmt == POPPY_FRAME_PAL8_SEQ) {                             // the copies are the sequence: the host statement on the BGR frame
+    if (format_is_sequence(fmt)) {                                 // the copies are the sequence: the host statement on the BGR frame
         std::vector<uint8_t> bgr((size_t)W * H * 3);
         HIPCHK(c, hipMemcpyAsync(bgr.data(), d_bgr, bgr.size(), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -321,9 +431,11 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
     if (fmt == POPPY_FRAME_BGR) return bgr;
     if (const char* why = format_refuses(fmt, W, H)) { *status = fail(c, POPPY_E_UNSUPPORTED, why); return nullptr; }
     tmp.resize(poppy_frame_bytes(fmt, W, H));
-    const int rc = fmt == POPPY_FRAME_PAL8_SEQ ? pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, tmp.data()) :
+    std::vector<uint8_t> pal8(format_is_sequence(fmt) && format_is_coded(fmt) ? poppy_frame_bytes(POPPY_FRAME_PAL8_SEQ, W, H) : 0);      // (GIF_SEQ: PAL8_SEQ's frame, then the host coder)
+    int rc = format_is_sequence(fmt) ? pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, pal8.empty() ? tmp.data() : pal8.data()) :
                    fmt == POPPY_FRAME_GIF ? poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data()) :
                    fmt == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
+    if (rc == POPPY_OK && !pal8.empty()) rc = poppy_pal8_to_gif_frame(pal8.data(), W, H, tmp.data());
     if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
     *out_stride = writer_stride(fmt, W);
     return tmp.data();
@@ -369,6 +481,42 @@ int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* c, const uint8_t* pal8, int W, in
     if (rc == POPPY_OK) rc = gif_from_device_pal8(c, d_pal8, W, H, host);
     (void)hipFree(d_pal8);
     if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
+    return rc;
+}
+
+int poppy_hip_bgr_frames_to_gif_frames(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int W, int H, uint8_t* dst) {
+    if (!c) return POPPY_E_ARG;
+    if (!bgr || !dst || W <= 0 || H <= 0 || stride < (size_t)W * 3 || n_frames < 1) return fail(c, POPPY_E_ARG, "bad arguments");
+    if (const char* why = sequence_refuses(POPPY_FRAME_GIF_SEQ, n_frames, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    if (c->seq.open) return fail(c, POPPY_E_STATE, "a sequence is open on this context");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!prepare_pal8()) return fail(c, POPPY_E_DEVICE, "could not raise the palette build's LDS limit");
+    // everything lives for the call: the context's own sequence tables, store and rings are not touched
+    const size_t row = (size_t)W * 3, place = (row * H + 15) & ~(size_t)15, capacity = poppy_frame_bytes(POPPY_FRAME_GIF_SEQ, W, H);
+    uint8_t *store = nullptr, *tables = nullptr, *work = nullptr, *frame = nullptr;
+    hipError_t e = hipMalloc((void**)&store, place * (size_t)n_frames);
+    if (e == hipSuccess) e = hipMalloc((void**)&tables, kPal8SeqTableBytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&work, gif_scratch_bytes(W, H));
+    if (e == hipSuccess) e = hipMalloc((void**)&frame, capacity + 16);
+    if (e == hipSuccess) e = hipMemsetAsync(tables, 0, kPal8SeqTableBytes, c->stream);
+    for (int k = 0; k < n_frames && e == hipSuccess; ++k) {
+        e = hipMemcpy2D(store + (size_t)k * place, row, bgr + (size_t)k * frame_stride, stride, row, (size_t)H, hipMemcpyHostToDevice);
+        if (e == hipSuccess) { launch_pal8_seq_pass(store + (size_t)k * place, nullptr, tables, W, H, c->stream); e = hipGetLastError(); }
+    }
+    if (e == hipSuccess) { launch_pal8_seq_build(tables, c->stream); e = hipGetLastError(); }
+    int rc = POPPY_OK;
+    for (int k = 0; k < n_frames && e == hipSuccess && rc == POPPY_OK; ++k) {
+        uint32_t total = 0;
+        enqueue_seq_gif_coding(store + (size_t)k * place, tables, work, frame, nullptr, W, H, c->stream, nullptr);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess && (total < 776 || total > capacity)) rc = fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+        else if (e == hipSuccess) e = hipMemcpy(dst + (size_t)k * capacity, frame, total, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);   // nothing of the call is in flight when its buffers go
+    for (uint8_t* b : {store, tables, work, frame}) if (b) (void)hipFree(b);
+    if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("GIF sequence coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
     return rc;
 }
 

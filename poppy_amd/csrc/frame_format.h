@@ -1,5 +1,5 @@
 // frame_format.h — what depends on the format a writer gets its frames in (poppy_hip_set_frame_format): the formats' facts, a slot's conversion buffers,
-// the conversion launches, the POPPY_FRAME_PAL8_SEQ sequence, the pinned ring towards the writer and the frames that no slot renders.  frame_format.cpp.
+// the conversion launches, the POPPY_FRAME_PAL8_SEQ / POPPY_FRAME_GIF_SEQ sequence, the pinned ring towards the writer and the frames that no slot renders.  frame_format.cpp.
 #pragma once
 #include "../../include/poppy_hip.h"
 #include <hip/hip_runtime.h>
@@ -13,7 +13,10 @@ size_t writer_stride(int fmt, int W);      // what the writer is told: 0 for a c
 // a palette per frame: the PAL8 triple (histogram, build, index plane) converts it — GIF is PAL8 with the two coding dispatches behind the index plane
 inline bool format_builds_palette(int fmt) { return fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF; }
 // a frame whose length its bytes decide: poppy_frame_bytes is its capacity, the slot's pinned word holds its length (slot_frame_length)
-inline bool format_is_coded(int fmt) { return fmt == POPPY_FRAME_GIF; }
+// (GIF_SEQ: the pinned word is the sequence ring buffer's, seq_finish)
+inline bool format_is_coded(int fmt) { return fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ; }
+// one palette for all the frames a call hands to its writer: they wait in the sequence store until the last is rendered (PaletteSeq); GIF_SEQ is PAL8_SEQ coded
+inline bool format_is_sequence(int fmt) { return fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF_SEQ; }
 int writer_format(const poppy_hip_ctx* c, bool has_writer);      // the format of the frames a call hands to its writer (none: they stay BGR in HBM), and whether they are collected into one palette sequence first
 bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer);
 
@@ -31,7 +34,7 @@ struct SlotFormat {
 int alloc_slot_format(poppy_hip_ctx* c);          // every slot's buffers for the context's format and the pair's geometry: allocates what is missing
 void free_slot_format_pair(SlotFormat& f);        // what goes with the pair's buffers
 void free_slot_format_ctx(SlotFormat& f);         // the side stream and its event: they live as long as the context
-void free_context_format(poppy_hip_ctx* c);       // the context's own: scratch of the frames that no slot renders, the sequence's tables, store and index ring
+void free_context_format(poppy_hip_ctx* c);       // the context's own: scratch of the frames that no slot renders, the sequence's tables, store and rings
 bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& f, int fmt);      // (every way to a format with a pair allocates the slots' buffers — alloc_pair, poppy_hip_set_frame_format — or refuses: a frame is never converted into nothing)
 const uint8_t* slot_frame(const FrameSlot& f, int fmt);       // the slot's frame as the writer gets it
 bool slot_frame_length(const FrameSlot& f, int fmt, size_t capacity, size_t* bytes);      // the bytes of that frame, once its `done` has fired: `capacity`, or a coded frame's own length from the slot's pinned word; false when that is out of bounds
@@ -40,15 +43,18 @@ bool slot_frame_length(const FrameSlot& f, int fmt, size_t capacity, size_t* byt
 // last dispatch; tm (timing mode 1) gets the marks frame_format, pal8_hist, pal8_build, gif_lzw, gif_pack.
 void enqueue_conversion(int fmt, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm);
 
-// POPPY_FRAME_PAL8_SEQ: one palette for all the frames a call hands to its writer.
+// POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ: one palette for all the frames a call hands to its writer.
 // seq_begin opens a sequence of n frames (limits, tables, store), every frame for the writer then goes through seq_pass (render_slot, seq_add_image) instead of
 // a download, and seq_finish builds the palette and hands every frame to the writer; seq_abort ends a sequence of which a frame failed, nothing written.
 // The sequence's tables (kernels.h: kPal8SeqTableBytes; zero between sequences), the frames held back until the palette is known (`stride` bytes apart, kept between
-// sequences, grown when needed), and a ring of index planes on their way to the writer.
+// sequences, grown when needed), and a ring of index planes on their way to the writer.  GIF_SEQ: a ring of coded frames instead (`gif`: per ring buffer the frame's
+// capacity, then the coder's scratch, `gif_each` bytes apart) and a word of mapped pinned memory per ring buffer that k_gif_pack stores the frame's length into.
 struct PaletteSeq {
     uint8_t* tables = nullptr;
     uint8_t* store = nullptr; size_t store_bytes = 0, stride = 0;
     uint8_t* idx = nullptr; size_t idx_bytes = 0;
+    uint8_t* gif = nullptr; size_t gif_bytes = 0;
+    uint32_t* gif_total = nullptr; uint8_t* gif_total_dev = nullptr;      // kStageRing words, 64 bytes apart
     bool open = false;                    // a sequence is being collected: frames for the writer go through the pass into the store
     int n = 0, count = 0;                 // its frames, and how many of them have been queued
 };
@@ -74,9 +80,9 @@ struct WriterRing {
 };
 
 // a device frame (tight u8x3, W x H) in the writer's format in `host`, queued on c->stream and waited for; *stride = what the writer is told
-// n_copies: how often the writer gets this frame — under POPPY_FRAME_PAL8_SEQ these copies are the whole sequence, and the frame is converted on the host
+// n_copies: how often the writer gets this frame — under the sequence formats these copies are the whole sequence, and the frame is converted on the host
 int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride, int n_copies = 1);
-const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status, int n_copies = 1);      // a host frame in the writer's format: `bgr` itself (BGR) or its I420 / PAL8 in `tmp`; nullptr, *status and c->err set, when the format refuses the frame
+const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status, int n_copies = 1);      // a host frame in the writer's format: `bgr` itself (BGR) or its I420 / PAL8 / coded form in `tmp`; nullptr, *status and c->err set, when the format refuses the frame
 int write_device_image(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, int n_copies, poppy_write_cb write, void* user);      // a device image / a host image to the writer, n_copies times, in the writer's format (the phase 0 / 1 and t = 0 / 1 copies, the linear-blend fallback frames)
 int write_host_image(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, int n_copies, poppy_write_cb write, void* user);
 int pal8_seq_of_copies(const uint8_t* bgr, size_t stride, int n_copies, int width, int height, uint8_t* dst);      // frame_pal8.cpp: the POPPY_FRAME_PAL8_SEQ frame of a sequence that is n_copies times the same BGR frame (poppy_bgr_frames_to_pal8 with frame_stride 0, one frame out)

@@ -1,4 +1,4 @@
-// frame_gif.cpp — the library's definition of the POPPY_FRAME_GIF hand-off format in plain C++ (include/poppy_hip.h): a PAL8 frame whose index plane is LZW-coded in
+// frame_gif.cpp — the library's definition of the POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ hand-off formats in plain C++ (include/poppy_hip.h): a PAL8 frame whose index plane is LZW-coded in
 // independent segments of POPPY_GIF_SEGMENT_PIXELS pixels and framed as GIF image data.  The coder is the GIF sinks' (gif_lzw.h); kernels_frame_gif.hip computes the
 // same bytes on the device, tests/test_host_gif_coded.py pins these to a plain-Python restatement of the rule.
 #include "../../include/poppy_hip.h"
@@ -67,6 +67,19 @@ int poppy_bgr_to_gif_frame(const uint8_t* bgr, size_t stride, int width, int hei
     std::vector<uint8_t> pal8(poppy_frame_bytes(POPPY_FRAME_PAL8, width, height));
     const int rc = poppy_bgr_to_pal8(bgr, stride, width, height, pal8.data());
     return rc ? rc : poppy_pal8_to_gif_frame(pal8.data(), width, height, dst);
+}
+
+// POPPY_FRAME_GIF_SEQ: the composition of the two statements — the sequence's PAL8_SEQ frames, each coded.  The limits are checked here, on the arguments alone,
+// so that nothing is read or written when either statement would refuse.
+int poppy_bgr_frames_to_gif_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst) {
+    if (!bgr || !dst || width <= 0 || height <= 0 || stride < (size_t)width * 3 || n_frames < 1) return POPPY_E_ARG;
+    if (!gif_fits(width, height)) return POPPY_E_UNSUPPORTED;
+    if ((unsigned long long)n_frames * (unsigned long long)width * (unsigned long long)height >= POPPY_PAL8_SEQ_MAX_PIXELS) return POPPY_E_UNSUPPORTED;
+    const size_t pal8_bytes = poppy_frame_bytes(POPPY_FRAME_PAL8_SEQ, width, height), capacity = poppy_frame_bytes(POPPY_FRAME_GIF_SEQ, width, height);
+    std::vector<uint8_t> pal8(pal8_bytes * (size_t)n_frames);
+    int rc = poppy_bgr_frames_to_pal8(bgr, stride, frame_stride, n_frames, width, height, pal8.data());
+    for (int k = 0; k < n_frames && rc == POPPY_OK; ++k) rc = poppy_pal8_to_gif_frame(pal8.data() + (size_t)k * pal8_bytes, width, height, dst + (size_t)k * capacity);
+    return rc;
 }
 
 }  // extern "C"

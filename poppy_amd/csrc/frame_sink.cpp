@@ -9,6 +9,7 @@
 //   POPPY_SINK_GIF   one animated GIF89a file that takes PAL8 frames as they are: a local colour table and one LZW image per frame
 //   POPPY_SINK_GIF_GLOBAL  the same for PAL8_SEQ frames: the first frame's palette as the global colour table, local tables only where a frame's palette differs
 //   POPPY_SINK_GIF_CODED   POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames, whose image data arrives coded (frame_gif.cpp, kernels_frame_gif.hip): nothing is coded here
+//   POPPY_SINK_GIF_GLOBAL_CODED  POPPY_SINK_GIF_GLOBAL's file from coded frames (POPPY_FRAME_GIF_SEQ): the first frame's palette as the global table, local tables only where a palette differs
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "../../include/poppy_hip.h"
 #include "gif_lzw.h"
@@ -85,14 +86,26 @@ bool gif_frame(poppy_sink* s, const uint8_t* pal8) {
     return z.ok;
 }
 
-// a POPPY_FRAME_GIF frame: the palette as the local table, then the frame's image data as it is
+// whether the sink writes GIF89a, and whether its frames arrive coded (stride 0)
+bool sink_is_gif(int format) { return format == POPPY_SINK_GIF || format == POPPY_SINK_GIF_GLOBAL || format == POPPY_SINK_GIF_CODED || format == POPPY_SINK_GIF_GLOBAL_CODED; }
+bool sink_takes_coded(int format) { return format == POPPY_SINK_GIF_CODED || format == POPPY_SINK_GIF_GLOBAL_CODED; }
+bool sink_has_global_table(int format) { return format == POPPY_SINK_GIF_GLOBAL || format == POPPY_SINK_GIF_GLOBAL_CODED; }
+
+// a coded frame (POPPY_FRAME_GIF, POPPY_FRAME_GIF_SEQ): the palette as the local table — GIF_GLOBAL_CODED: only where it differs from the global table, which is
+// the first frame's —, then the frame's image data as it is
 bool gif_coded_frame(poppy_sink* s, const uint8_t* frame) {
     const int w = s->w, h = s->h;
     const size_t total = poppy_gif_frame_bytes(frame);
     if (total < 772 + 3 || total > poppy_frame_bytes(POPPY_FRAME_GIF, w, h) || frame[772] != 8 || frame[total - 1] != 0) return false;
+    bool local = true;
+    if (sink_has_global_table(s->format)) {
+        if (!s->head_written) { memcpy(s->global_pal, frame + 4, 768); if (!gif_head(s, s->global_pal)) return false; }
+        local = memcmp(s->global_pal, frame + 4, 768) != 0;
+    }
     const uint8_t gce[8] = {0x21, 0xF9, 4, 0, (uint8_t)(s->delay_cs & 255), (uint8_t)(s->delay_cs >> 8), 0, 0};
-    const uint8_t desc[10] = {0x2C, 0, 0, 0, 0, (uint8_t)(w & 255), (uint8_t)(w >> 8), (uint8_t)(h & 255), (uint8_t)(h >> 8), 0x87};
-    return fwrite(gce, 1, 8, s->f) == 8 && fwrite(desc, 1, 10, s->f) == 10 && fwrite(frame + 4, 1, total - 4, s->f) == total - 4;
+    const uint8_t desc[10] = {0x2C, 0, 0, 0, 0, (uint8_t)(w & 255), (uint8_t)(w >> 8), (uint8_t)(h & 255), (uint8_t)(h >> 8), (uint8_t)(local ? 0x87 : 0x00)};
+    const size_t from = local ? 4 : 772;
+    return fwrite(gce, 1, 8, s->f) == 8 && fwrite(desc, 1, 10, s->f) == 10 && fwrite(frame + from, 1, total - from, s->f) == total - from;
 }
 
 }  // namespace
@@ -105,7 +118,7 @@ size_t poppy_frame_bytes(int format, int width, int height) {
     if (format == POPPY_FRAME_BGR) return w * h * 3;
     if (format == POPPY_FRAME_I420) return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2);
     if (format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ) return w * h + 768;
-    if (format == POPPY_FRAME_GIF) {                        // the capacity (include/poppy_hip.h has the derivation): every segment at its bound, framed
+    if (format == POPPY_FRAME_GIF || format == POPPY_FRAME_GIF_SEQ) {      // the capacity (include/poppy_hip.h has the derivation): every segment at its bound, framed
         const size_t segments = (w * h + POPPY_GIF_SEGMENT_PIXELS - 1) / POPPY_GIF_SEGMENT_PIXELS, payload = segments * POPPY_GIF_SEGMENT_BYTES;
         return 772 + 1 + payload + (payload + 254) / 255 + 1;
     }
@@ -141,7 +154,7 @@ int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, 
 }
 
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den) {
-    if (!path || width <= 0 || height <= 0 || (format != POPPY_SINK_GIF && format != POPPY_SINK_GIF_GLOBAL && format != POPPY_SINK_GIF_CODED && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
+    if (!path || width <= 0 || height <= 0 || (!sink_is_gif(format) && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
     poppy_sink* s = new poppy_sink();
     s->format = format; s->w = width; s->h = height; s->path = path;
     if (format == POPPY_SINK_PPM) {
@@ -165,7 +178,7 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
         if (bad || !seen) { delete s; return nullptr; }
         s->path = head; s->tail = tail;
     }
-    if ((format == POPPY_SINK_GIF || format == POPPY_SINK_GIF_GLOBAL || format == POPPY_SINK_GIF_CODED) && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen: every write fails, close says so
+    if (sink_is_gif(format) && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen: every write fails, close says so
     if (format != POPPY_SINK_PPM) {
         s->f = fopen(path, "wb");
         if (!s->f) { delete s; return nullptr; }
@@ -173,11 +186,11 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
             fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C444 XCOLORRANGE=FULL\n", width, height, fps_num > 0 ? fps_num : 30, fps_den > 0 ? fps_den : 1);
         else if (format == POPPY_SINK_Y4M420)
             fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=FULL\n", width, height, fps_num > 0 ? fps_num : 30, fps_den > 0 ? fps_den : 1);
-        else if (format == POPPY_SINK_GIF || format == POPPY_SINK_GIF_GLOBAL || format == POPPY_SINK_GIF_CODED) {
+        else if (sink_is_gif(format)) {
             const long long num = fps_num > 0 ? fps_num : 30, den = fps_den > 0 ? fps_den : 1;
             const long long cs = (den * 100 + num / 2) / num;
             s->delay_cs = (int)(cs < 1 ? 1 : cs > 65535 ? 65535 : cs);
-            if (format != POPPY_SINK_GIF_GLOBAL && !gif_head(s, nullptr)) s->failed = true;      // (GIF_GLOBAL: with the first frame)
+            if (!sink_has_global_table(format) && !gif_head(s, nullptr)) s->failed = true;      // (a global table: with the first frame)
         }
     }
     s->row.resize((size_t)width * 3);
@@ -188,8 +201,8 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
     poppy_sink* s = (poppy_sink*)user;
     if (!s || s->failed) return;
     // (an I420 frame comes with stride == width: the BGR sinks refuse it, and the I420 sink refuses anything else)
-    // (a coded frame comes with stride == 0: every other sink refuses it below, and the coded sink refuses anything else)
-    if (s->format == POPPY_SINK_GIF_CODED) {
+    // (a coded frame comes with stride == 0: every other sink refuses it below, and the coded sinks refuse anything else)
+    if (sink_takes_coded(s->format)) {
         if (!bgr || width != s->w || height != s->h || stride != 0 || !gif_coded_frame(s, bgr)) s->failed = true; else ++s->frames;
         return;
     }
@@ -246,8 +259,8 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
 
 int poppy_sink_close(poppy_sink* s) {
     if (!s) return POPPY_E_ARG;
-    if (s->f && s->format == POPPY_SINK_GIF_GLOBAL && !s->failed && !s->head_written && !gif_head(s, nullptr)) s->failed = true;      // no frame came: GIF's empty file
-    if (s->f && (s->format == POPPY_SINK_GIF || s->format == POPPY_SINK_GIF_GLOBAL || s->format == POPPY_SINK_GIF_CODED) && !s->failed && fputc(0x3B, s->f) == EOF) s->failed = true;      // the trailer
+    if (s->f && sink_has_global_table(s->format) && !s->failed && !s->head_written && !gif_head(s, nullptr)) s->failed = true;      // no frame came: GIF's empty file
+    if (s->f && sink_is_gif(s->format) && !s->failed && fputc(0x3B, s->f) == EOF) s->failed = true;      // the trailer
     const int n = s->failed ? POPPY_E_DEVICE : s->frames;
     if (s->f) fclose(s->f);
     delete s;

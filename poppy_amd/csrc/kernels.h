@@ -231,5 +231,9 @@ constexpr size_t kGifSlotBytes = ((size_t)POPPY_GIF_SEGMENT_BYTES + 3) & ~(size_
 size_t gif_scratch_bytes(int w, int h);
 void launch_gif_lzw(const uint8_t* pal8, uint8_t* scratch, int w, int h, hipStream_t s);
 void launch_gif_pack(const uint8_t* pal8, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
+// POPPY_FRAME_GIF_SEQ: the same two dispatches from a frame's place in the sequence store (tight u8x3 BGR, 16-byte aligned) and the sequence's tables behind the
+// build (seq_tables: the cell -> index table and the palette are read); no index plane is stored.
+void launch_gif_lzw_bgr(const uint8_t* bgr, const uint8_t* seq_tables, uint8_t* scratch, int w, int h, hipStream_t s);
+void launch_gif_pack_seq(const uint8_t* seq_tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
 
 }  // namespace poppy_hip

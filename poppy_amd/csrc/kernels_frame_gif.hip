@@ -17,7 +17,15 @@
 //                773 + i + i / 255 + 1, the thread that stores the first byte of a sub-block also stores the length byte in front of it.  Workgroup 0 writes the
 //                minimum-code-size byte, the terminator, the palette and `total` — into the frame and into a word of mapped pinned host memory, so that the host knows
 //                how many bytes to copy when the frame's completion event has fired, without a copy packet of its own in the stream.
+//
+// POPPY_FRAME_GIF_SEQ (one palette per sequence, poppy_bgr_frames_to_gif_frames is its host statement) codes from the sequence store instead:
+//   k_gif_lzw_bgr  k_gif_lzw with another staging (gif_lzw_segment is the code of both): the lanes read the segment's BGR from the frame's place in the store, look every
+//                pixel's cell up in the sequence's 32 KiB cell -> index table in global memory and write the index bytes into the wave's s_px, so k_pal8_remap's
+//                dispatch and the index plane in HBM fall away.  The table is not copied to LDS: 32 KiB more per workgroup would leave one workgroup per compute
+//                unit where three run now.
+//   k_gif_pack   as it is, with the palette read from the sequence's tables.
 #include "kernels.h"
+#include "pal8_cells.h"
 #include <hip/hip_ext.h>
 
 namespace poppy_hip {
@@ -49,7 +57,47 @@ struct BitOut {
 
 }  // namespace
 
-__global__ void __launch_bounds__(64 * kLzwWaves) k_gif_lzw(const uint8_t* __restrict__ idx, uint32_t* __restrict__ scratch, uint32_t* __restrict__ lengths, int n_px, int n_seg) {
+namespace {
+
+// The segment's index bytes into the wave's s_px, all lanes; the two stagings are the only difference between k_gif_lzw and k_gif_lzw_bgr.
+// From a PAL8 index plane: coalesced; the plane's start is 4-byte aligned (a hipMalloc'd buffer) and kSeg is a multiple of 4, so whole words are read up to the
+// plane's last, partial one.
+struct StageIndices {
+    const uint8_t* __restrict__ idx;
+    __device__ __forceinline__ void operator()(uint32_t* px, int at, int len, int lane) const {
+        for (int w = lane; w * 4 < len; w += 64) {
+            uint32_t v;
+            if (w * 4 + 4 <= len) v = *(const uint32_t*)(idx + at + w * 4);
+            else { v = 0; for (int k = 0; w * 4 + k < len; ++k) v |= (uint32_t)idx[at + w * 4 + k] << (8 * k); }
+            px[w] = v;
+        }
+    }
+};
+// From the frame's BGR in the sequence store, through the sequence's cell -> index table (k_pal8_remap's indexing): four pixels = three words per lane and step.  The
+// frame's place begins on a 16-byte boundary and a segment on a multiple of kSeg * 3 bytes behind it, so the words are aligned; the frame's last quad, of 1 to 3
+// pixels, is read bytewise and never past its last pixel (the place's padding ends before a whole quad would).  The table is read from global memory: 32 KiB that
+// every wave of the device touches stay in L2.
+struct StageBgr {
+    const uint8_t* __restrict__ bgr;
+    const uint8_t* __restrict__ table;
+    __device__ __forceinline__ void operator()(uint32_t* px, int at, int len, int lane) const {
+        const uint8_t* src = bgr + (size_t)at * 3;
+        for (int w = lane; w * 4 < len; w += 64) {
+            const int n = min(4, len - w * 4);
+            uint32_t q[3];
+            load_quad(src, (size_t)w, n, true, q);
+            uint32_t v = 0;
+            #pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) v |= (uint32_t)table[cell_of(quad_byte(q, 3 * k), quad_byte(q, 3 * k + 1), quad_byte(q, 3 * k + 2))] << (8 * k);
+            px[w] = v;
+        }
+    }
+};
+
+// One wave's segment: staged by `stage`, coded by lane 0, stored by all lanes (the header comment has the arrangement).
+template <typename Stage>
+__device__ __forceinline__ void gif_lzw_segment(const Stage stage, uint32_t* __restrict__ scratch, uint32_t* __restrict__ lengths, int n_px, int n_seg) {
     __shared__ uint32_t s_px[kLzwWaves][kSeg / 4];
     __shared__ uint32_t s_tab[kLzwWaves][kTable];
     __shared__ uint32_t s_out[kLzwWaves][kOutWords];
@@ -61,13 +109,7 @@ __global__ void __launch_bounds__(64 * kLzwWaves) k_gif_lzw(const uint8_t* __res
     uint32_t* px = s_px[wv];
     uint32_t* tab = s_tab[wv];
     uint32_t* out = s_out[wv];
-    // the segment's bytes, coalesced; the plane's start is 4-byte aligned (a hipMalloc'd buffer) and kSeg is a multiple of 4, so whole words are read up to the plane's last, partial one
-    for (int w = lane; w * 4 < len; w += 64) {
-        uint32_t v;
-        if (w * 4 + 4 <= len) v = *(const uint32_t*)(idx + at + w * 4);
-        else { v = 0; for (int k = 0; w * 4 + k < len; ++k) v |= (uint32_t)idx[at + w * 4 + k] << (8 * k); }
-        px[w] = v;
-    }
+    stage(px, at, len, lane);
     for (int i = lane; i < kTable; i += 64) tab[i] = 0xffffffffu;
     wave_sync();
     // lane 0's state lives in its registers across the table restarts
@@ -120,6 +162,18 @@ __global__ void __launch_bounds__(64 * kLzwWaves) k_gif_lzw(const uint8_t* __res
     for (int w = lane; w * 4 < n_bytes && w < kOutWords; w += 64) dst[w] = out[w];
 }
 
+}  // namespace
+
+__global__ void __launch_bounds__(64 * kLzwWaves) k_gif_lzw(const uint8_t* __restrict__ idx, uint32_t* __restrict__ scratch, uint32_t* __restrict__ lengths, int n_px, int n_seg) {
+    gif_lzw_segment(StageIndices{idx}, scratch, lengths, n_px, n_seg);
+}
+
+// bgr: the frame's place in the sequence store (16-byte aligned, tight u8x3); table: the sequence's cell -> index table (32768 bytes)
+__global__ void __launch_bounds__(64 * kLzwWaves) k_gif_lzw_bgr(const uint8_t* __restrict__ bgr, const uint8_t* __restrict__ table, uint32_t* __restrict__ scratch,
+                                                               uint32_t* __restrict__ lengths, int n_px, int n_seg) {
+    gif_lzw_segment(StageBgr{bgr, table}, scratch, lengths, n_px, n_seg);
+}
+
 namespace {
 constexpr int kPackGroup = 8;                               // segments per workgroup
 constexpr size_t kGifData = 773;                            // the frame's offset of the first sub-block's length byte
@@ -165,18 +219,32 @@ __global__ void __launch_bounds__(256) k_gif_pack(const uint8_t* __restrict__ sc
     }
 }
 
+namespace {
+int gif_segments(int w, int h) { return (int)(((size_t)w * h + kSeg - 1) / kSeg); }
+uint32_t* gif_lengths(uint8_t* scratch, int n_seg) { return (uint32_t*)(scratch + (size_t)n_seg * kGifSlotBytes); }
+void gif_pack(const uint8_t* palette, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int n_seg, hipStream_t s, hipEvent_t done) {
+    hipExtLaunchKernelGGL(k_gif_pack, dim3((unsigned)((n_seg + kPackGroup - 1) / kPackGroup)), dim3(256), 0, s, nullptr, done, 0, scratch,
+                          gif_lengths(const_cast<uint8_t*>(scratch), n_seg), palette, n_seg, frame, total_host);
+}
+}  // namespace
+
 void launch_gif_lzw(const uint8_t* pal8, uint8_t* scratch, int w, int h, hipStream_t s) {
-    const size_t n_px = (size_t)w * h;
-    const int n_seg = (int)((n_px + kSeg - 1) / kSeg);
-    uint32_t* lengths = (uint32_t*)(scratch + (size_t)n_seg * kGifSlotBytes);
-    hipLaunchKernelGGL(k_gif_lzw, dim3((unsigned)((n_seg + kLzwWaves - 1) / kLzwWaves)), dim3(64 * kLzwWaves), 0, s, pal8, (uint32_t*)scratch, lengths, (int)n_px, n_seg);
+    const int n_seg = gif_segments(w, h);
+    hipLaunchKernelGGL(k_gif_lzw, dim3((unsigned)((n_seg + kLzwWaves - 1) / kLzwWaves)), dim3(64 * kLzwWaves), 0, s, pal8, (uint32_t*)scratch, gif_lengths(scratch, n_seg), (int)((size_t)w * h), n_seg);
 }
 
 void launch_gif_pack(const uint8_t* pal8, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done) {
-    const size_t n_px = (size_t)w * h;
-    const int n_seg = (int)((n_px + kSeg - 1) / kSeg);
-    const uint32_t* lengths = (const uint32_t*)(scratch + (size_t)n_seg * kGifSlotBytes);
-    hipExtLaunchKernelGGL(k_gif_pack, dim3((unsigned)((n_seg + kPackGroup - 1) / kPackGroup)), dim3(256), 0, s, nullptr, done, 0, scratch, lengths, pal8 + n_px, n_seg, frame, total_host);
+    gif_pack(pal8 + (size_t)w * h, scratch, frame, total_host, gif_segments(w, h), s, done);
+}
+
+void launch_gif_lzw_bgr(const uint8_t* bgr, const uint8_t* seq_tables, uint8_t* scratch, int w, int h, hipStream_t s) {
+    const int n_seg = gif_segments(w, h);
+    hipLaunchKernelGGL(k_gif_lzw_bgr, dim3((unsigned)((n_seg + kLzwWaves - 1) / kLzwWaves)), dim3(64 * kLzwWaves), 0, s, bgr, seq_tables + kPal8SeqTableOffset, (uint32_t*)scratch,
+                       gif_lengths(scratch, n_seg), (int)((size_t)w * h), n_seg);
+}
+
+void launch_gif_pack_seq(const uint8_t* seq_tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done) {
+    gif_pack(seq_tables + kPal8SeqPaletteOffset, scratch, frame, total_host, gif_segments(w, h), s, done);
 }
 
 size_t gif_scratch_bytes(int w, int h) {

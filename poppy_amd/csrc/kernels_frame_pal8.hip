@@ -25,6 +25,7 @@
 //                     than 2^32 pixels), scores (count * side, up to 2^37) and colour sums are 64-bit.
 //   k_pal8_remap      per frame, from the store.
 #include "kernels.h"
+#include "pal8_cells.h"
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <mutex>
@@ -37,21 +38,6 @@ namespace {
 constexpr int kCells = 32768;
 constexpr int kHistSlots = 2048;                 // per workgroup: 8 KiB of keys + 2 x 16 KiB of sums
 constexpr int kHistProbes = 8;
-
-__device__ __forceinline__ int cell_of(int b, int g, int r) { return ((r >> 3) << 10) | ((g >> 3) << 5) | (b >> 3); }
-
-// the (up to) four pixels of quad q as 12 bytes in three words; n = how many of them exist
-__device__ __forceinline__ void load_quad(const uint8_t* __restrict__ src, size_t q, int n, bool aligned, uint32_t w[3]) {
-    if (aligned && n == 4) {
-        const uint32_t* p = (const uint32_t*)(src + q * 12);
-        w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
-    } else {
-        w[0] = w[1] = w[2] = 0;
-        #pragma unroll
-        for (int i = 0; i < 12; ++i) if (i < 3 * n) w[i >> 2] |= (uint32_t)src[q * 12 + i] << (8 * (i & 3));
-    }
-}
-__device__ __forceinline__ int quad_byte(const uint32_t w[3], int o) { return (int)((w[o >> 2] >> (8 * (o & 3))) & 0xffu); }
 
 }  // namespace
 

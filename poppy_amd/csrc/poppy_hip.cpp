@@ -624,8 +624,8 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
 static_assert(kPlanRasterRows == kRasterChunkRows, "the plan's work list and k_raster must agree on the chunk height");
 
 // the format the frames being submitted are converted to for their writer (their slots' bodies end with the conversion); BGR: none
-// (PAL8_SEQ: none either — the sequence pass is launched behind the body, its destination differs from frame to frame: render_slot)
-static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached && c->frame_format != POPPY_FRAME_PAL8_SEQ ? c->frame_format : POPPY_FRAME_BGR; }
+// (PAL8_SEQ, GIF_SEQ: none either — the sequence pass is launched behind the body, its destination differs from frame to frame: render_slot)
+static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached && !format_is_sequence(c->frame_format) ? c->frame_format : POPPY_FRAME_BGR; }
 
 // pyrdown .. unsharp of one slot.  Every argument is fixed for the life of the pair (the per-frame unsharp amount is
 // read from the slot's plan blob), which is what lets the whole sequence be captured into one graph launch.
