@@ -647,6 +647,19 @@ int poppy_plan_frame(int width, int height, const float* src_points1, const floa
                      double shape_ratio, int max_tris, int* n_tris, int* idx3, int* tri_xy,
                      float* M1, float* M2, float* inv1, float* inv2, float* morphed_pts);
 
+/* Host-only: the lengths of the per-tile triangle lists the fused warp kernels (k_tile_expand, k_warp_bin) would be handed for this
+ * frame, in tiles tile_width (64 or 128) pixels wide and 1024 / tile_width high, row-major: the planner's own mesh and binning, with
+ * the room for list entries a context keeps for n_points point pairs.  *bins_ok = 0 when the lists outgrow that room (such a frame
+ * takes the id-map path); counts[] and *total then hold what the lists would have been.  counts (capacity `cap` tiles), total and
+ * bins_ok may be NULL; POPPY_E_ARG when counts is given and *n_tiles > cap.  Used by the CPU test suite.                                            */
+int poppy_plan_tile_counts(int width, int height, const float* src_points1, const float* src_points2, int n_points,
+                           double shape_ratio, int tile_width, int* counts, int cap, int* n_tiles, long long* total, int* bins_ok);
+/* Host-only: the lists themselves, tile after tile in the order of poppy_plan_tile_counts: tris[] (capacity `cap` entries; may be NULL) receives the
+ * *total triangle numbers (indices into poppy_plan_frame's triangles), ascending inside a tile, which is painter's order: entry e of a tile's list
+ * is what the fused kernels number e + 1 in that tile.  POPPY_E_ARG when *total > cap.  Used by the CPU test suite.                              */
+int poppy_plan_tile_tris(int width, int height, const float* src_points1, const float* src_points2, int n_points,
+                         double shape_ratio, int tile_width, int* tris, long long cap, long long* total);
+
 /* Host-only: packs T pairs of inverse matrices (as poppy_plan_frame returns them) into the (T+1) x 20 float records the
  * tiled warp kernel reads (record 0 = identity; layout in poppy_amd/csrc/frame_plan.h) and returns 1 when every matrix is
  * inside the range for which that kernel's arithmetic is proven identical to the general one, 0 when the frame must take

@@ -35,7 +35,7 @@ SYMBOLS = [
     "poppy_hip_frame_device", "poppy_hip_frame_wait", "poppy_hip_frame_stream", "poppy_hip_sync", "poppy_hip_stream", "poppy_frame_ratio", "poppy_hip_morph_frames",
     "poppy_hip_dissolve", "poppy_hip_set_debug", "poppy_hip_last_warp_kind", "poppy_warp_records", "poppy_hip_hamming_knn2", "poppy_ratio_symmetry",
     "poppy_hip_pair_begin_descriptors", "poppy_hip_warp_affine", "poppy_hip_auto_align", "poppy_hip_align_step",
-    "poppy_procrustes", "poppy_perspective_from4", "poppy_hip_pair_corrected2", "poppy_hip_debug_fetch", "poppy_hip_debug_triangles", "poppy_plan_frame",
+    "poppy_procrustes", "poppy_perspective_from4", "poppy_hip_pair_corrected2", "poppy_hip_debug_fetch", "poppy_hip_debug_triangles", "poppy_plan_frame", "poppy_plan_tile_counts", "poppy_plan_tile_tris",
     "poppy_hip_timing_summary", "poppy_hip_set_timing", "poppy_hip_render_many",
     "poppy_hip_orb_describe", "poppy_hip_hamming_match",
     "poppy_sink_open", "poppy_sink_write", "poppy_sink_close", "poppy_hip_render_phases", "poppy_hip_pool_set_timing", "poppy_hip_pool_timing_summary", "poppy_hip_pool_warp_counts", "poppy_hip_pool_create", "poppy_hip_pool_create_tuned", "poppy_hip_pool_destroy", "poppy_hip_pool_morph_pairs", "poppy_hip_pool_submit_pairs", "poppy_hip_pool_wait", "poppy_count_pair_frames_cb", "poppy_hip_warp_counts", "poppy_hip_time_last_warp", "poppy_hip_mask_rider", "poppy_hip_pool_mask_rider", "poppy_hip_comm_id", "poppy_hip_comm_init", "poppy_hip_comm_free", "poppy_hip_comm_info", "poppy_hip_pair_broadcast", "poppy_hip_comm_max",
@@ -88,6 +88,8 @@ def lib():
         L.poppy_hip_debug_fetch.argtypes = [vp, C.c_char_p, vp, sz]
         L.poppy_hip_debug_triangles.argtypes = [vp, vp, vp, vp, vp, i]
         L.poppy_plan_frame.argtypes = [i, i, vp, vp, i, d, i, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.poppy_plan_tile_counts.argtypes = [i, i, vp, vp, i, d, i, vp, i, vp, vp, vp]
+        L.poppy_plan_tile_tris.argtypes = [i, i, vp, vp, i, d, i, vp, C.c_longlong, vp]
         L.poppy_warp_records.argtypes = [vp, vp, i, i, i, vp]
         L.poppy_hip_hamming_knn2.argtypes = [vp, vp, i, vp, i, vp]
         L.poppy_hip_warp_affine.argtypes = [vp, vp, C.c_size_t, i, i, vp, vp, C.c_size_t]
@@ -328,6 +330,34 @@ def plan_frame(w, h, p1, p2, shape):
         raise PoppyError(f"poppy_plan_frame: {rc}")
     t = nt.value
     return dict(idx3=idx3[:t], tri_xy=tri[:t], M1=M1[:t], M2=M2[:t], inv1=i1[:t], inv2=i2[:t], morphed=mp)
+
+
+def plan_tile_counts(w, h, p1, p2, shape, tile_w):
+    """Host-only: what the planner hands the fused warp kernels for this frame in tiles tile_w wide — (list length of every tile, row-major
+    (tiles_y, tiles_x) int32, their sum, whether the lists fit the room a context keeps for len(p1) point pairs)."""
+    p1 = np.ascontiguousarray(p1, np.float32)
+    p2 = np.ascontiguousarray(p2, np.float32)
+    th = 1024 // tile_w
+    ty, tx = (h + th - 1) // th, (w + tile_w - 1) // tile_w
+    counts = np.zeros((ty, tx), np.int32)
+    nt, total, ok = C.c_int(0), C.c_longlong(0), C.c_int(0)
+    rc = lib().poppy_plan_tile_counts(w, h, _p(p1), _p(p2), len(p1), shape, tile_w, _p(counts), counts.size, C.byref(nt), C.byref(total), C.byref(ok))
+    if rc or nt.value != counts.size:
+        raise PoppyError(f"poppy_plan_tile_counts: {rc} ({nt.value} tiles)")
+    return counts, int(total.value), bool(ok.value)
+
+
+def plan_tile_tris(w, h, p1, p2, shape, tile_w):
+    """Host-only: the tile lists themselves, as a list (tile after tile, row-major) of int32 arrays of triangle numbers in painter's order."""
+    counts, total, _ = plan_tile_counts(w, h, p1, p2, shape, tile_w)
+    p1 = np.ascontiguousarray(p1, np.float32)
+    p2 = np.ascontiguousarray(p2, np.float32)
+    tris = np.zeros(max(total, 1), np.int32)
+    tot = C.c_longlong(0)
+    rc = lib().poppy_plan_tile_tris(w, h, _p(p1), _p(p2), len(p1), shape, tile_w, _p(tris), total, C.byref(tot))
+    if rc or tot.value != total:
+        raise PoppyError(f"poppy_plan_tile_tris: {rc}")
+    return np.split(tris[:total], np.cumsum(counts.ravel())[:-1])
 
 
 def warp_records(inv1, inv2, w, h):

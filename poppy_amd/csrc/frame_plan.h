@@ -49,6 +49,11 @@ struct FramePlan {
 // Returns false when a triangle index does not fit 16 bits or the list outgrows max_entries (the caller then takes the
 // id-map path).
 bool build_tile_bins(FramePlan& plan, int w, int h, int tile_w, int tile_h, size_t max_entries);
+// What a context sizes its plan blobs for with n_points point pairs: the triangles (a planar triangulation of n points has < 2n),
+// and the per-tile list entries of a w x h image in tiles tile_w wide (1024 pixels each) — the max_entries it bins with.
+inline int plan_triangle_budget(int n_points) { return 2 * n_points + 16; }
+inline size_t tile_count(int w, int h, int tile_w) { const int th = 1024 / tile_w; return (size_t)((w + tile_w - 1) / tile_w) * ((h + th - 1) / th); }
+inline size_t tile_bins_capacity(int n_points, int w, int h, int tile_w) { return 64 * (size_t)plan_triangle_budget(n_points) + 16 * tile_count(w, h, tile_w); }
 constexpr int kPlanRasterRows = 16;  // rows of one triangle per raster work item
 
 // Returns 0, or -3 (POPPY_E_RANGE) when a point is outside [0,w)x[0,h) where Subdiv2D::insert throws.

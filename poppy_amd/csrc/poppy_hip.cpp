@@ -197,16 +197,16 @@ int poppy_hip_sync(poppy_hip_ctx* c) { if (!c) return POPPY_E_ARG; HIPCHK(c, hip
 
 // ---------------------------------------------------------------------------------------------
 static int ensure_ring(poppy_hip_ctx* c, int n_points) {
-    int need = 2 * n_points + 16;            // a planar triangulation of n points has < 2n triangles
+    int need = plan_triangle_budget(n_points);
     if (need <= c->max_tris) return POPPY_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     c->last_warp.valid = false;                     // the plan blobs and tile entries it points into are reallocated below
     // worst case every triangle spans the whole image height
     const size_t items = (size_t)need * ((size_t)c->H / kRasterChunkRows + 3);
-    const int tw = warp_bin_tile_width(c->W, c->H), th = 1024 / tw;
-    const size_t ntiles = (size_t)((c->W + tw - 1) / tw) * ((c->H + th - 1) / th);
-    c->bins_cap = 64 * (size_t)need + 16 * ntiles;
+    const int tw = warp_bin_tile_width(c->W, c->H);
+    const size_t ntiles = tile_count(c->W, c->H, tw);
+    c->bins_cap = tile_bins_capacity(n_points, c->W, c->H, tw);
     c->tile_bytes = warp_bin_data_bytes(ntiles, c->bins_cap);
     const size_t bytes = ((kBlobHeader + (size_t)(need + 1) * kWarpRecordFloats * 4 +
                           (size_t)need * (6 * 4 + 18 * 4 + sizeof(RasterTri)) + items * 8 +
@@ -1293,6 +1293,46 @@ int poppy_plan_frame(int W, int H, const float* p1, const float* p2, int n, doub
     if (inv1 && T) memcpy(inv1, plan.inv1.data(), (size_t)T * 36);
     if (inv2 && T) memcpy(inv2, plan.inv2.data(), (size_t)T * 36);
     if (morphed && n) memcpy(morphed, plan.morphed.data(), (size_t)n * 8);
+    return POPPY_OK;
+}
+
+// the frame's plan binned as a context would bin it for n point pairs; *ok = the lists fit its room (they are built in full either way)
+static int plan_tile_bins(int W, int H, const float* p1, const float* p2, int n, double shape, int tile_w, FramePlan& plan, bool* ok) {
+    if (W <= 0 || H <= 0 || n < 0 || (n > 0 && (!p1 || !p2)) || (tile_w != 64 && tile_w != 128)) return POPPY_E_ARG;
+    std::vector<P2f> a(n), b(n);
+    if (n) { memcpy(a.data(), p1, (size_t)n * 8); memcpy(b.data(), p2, (size_t)n * 8); }
+    if (plan_frame(W, H, a, b, shape, plan)) return POPPY_E_RANGE;
+    *ok = build_tile_bins(plan, W, H, tile_w, 1024 / tile_w, tile_bins_capacity(n, W, H, tile_w));
+    if (!*ok && !build_tile_bins(plan, W, H, tile_w, 1024 / tile_w, SIZE_MAX)) return POPPY_E_UNSUPPORTED;     // the lists a context would have needed room for
+    return POPPY_OK;
+}
+
+int poppy_plan_tile_counts(int W, int H, const float* p1, const float* p2, int n, double shape, int tile_w,
+                           int* counts, int cap, int* n_tiles, long long* total, int* bins_ok) {
+    if (!n_tiles) return POPPY_E_ARG;
+    FramePlan plan;
+    bool ok = false;
+    if (int rc = plan_tile_bins(W, H, p1, p2, n, shape, tile_w, plan, &ok)) return rc;
+    const int nt = (int)plan.tile_off.size() - 1;
+    *n_tiles = nt;
+    if (total) *total = (long long)plan.tile_tris.size();
+    if (bins_ok) *bins_ok = ok;
+    if (!counts) return POPPY_OK;
+    if (nt > cap) return POPPY_E_ARG;
+    for (int i = 0; i < nt; ++i) counts[i] = plan.tile_off[i + 1] - plan.tile_off[i];
+    return POPPY_OK;
+}
+
+int poppy_plan_tile_tris(int W, int H, const float* p1, const float* p2, int n, double shape, int tile_w,
+                         int* tris, long long cap, long long* total) {
+    if (!total) return POPPY_E_ARG;
+    FramePlan plan;
+    bool ok = false;
+    if (int rc = plan_tile_bins(W, H, p1, p2, n, shape, tile_w, plan, &ok)) return rc;
+    *total = (long long)plan.tile_tris.size();
+    if (!tris) return POPPY_OK;
+    if (*total > cap) return POPPY_E_ARG;
+    for (size_t i = 0; i < plan.tile_tris.size(); ++i) tris[i] = plan.tile_tris[i];
     return POPPY_OK;
 }
 
