@@ -660,6 +660,14 @@ int poppy_plan_tile_counts(int width, int height, const float* src_points1, cons
 int poppy_plan_tile_tris(int width, int height, const float* src_points1, const float* src_points2, int n_points,
                          double shape_ratio, int tile_width, int* tris, long long cap, long long* total);
 
+/* Host-only: where the groups of a frame's plan lie in a slot's plan blob (poppy_amd/csrc/plan_blob.h), for n_tris triangles, n_work work items of the
+ * id-map raster, n_toff tile offsets and n_ttri tile-list entries, on the fused path (fused != 0) or the id-map path: out[0..8] = rec_bytes, o_edges,
+ * o_outl, o_toff, o_ttri, o_tri, o_inv, o_work, used, in bytes (the offsets of the group the path does not upload are 0).
+ * With capacity != 0 the four counts are instead n_points, width, height and the tile width (64, 128, or 0: what a context picks for that size), and
+ * out[0..4] = the bytes a context allocates for a slot's blob with that many point pairs, its triangle budget, its tile count, the tile-list entries it
+ * keeps room for, and the tile width; out[5..8] = 0.  Used by the CPU test suite; the library does not call it.                               */
+int poppy_plan_blob_layout(int capacity, int n_tris, long long n_work, long long n_toff, long long n_ttri, int fused, unsigned long long* out);
+
 /* Host-only: packs T pairs of inverse matrices (as poppy_plan_frame returns them) into the (T+1) x 20 float records the
  * tiled warp kernel reads (record 0 = identity; layout in poppy_amd/csrc/frame_plan.h) and returns 1 when every matrix is
  * inside the range for which that kernel's arithmetic is proven identical to the general one, 0 when the frame must take

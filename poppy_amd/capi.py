@@ -35,7 +35,7 @@ SYMBOLS = [
     "poppy_hip_frame_device", "poppy_hip_frame_wait", "poppy_hip_frame_stream", "poppy_hip_sync", "poppy_hip_stream", "poppy_frame_ratio", "poppy_hip_morph_frames",
     "poppy_hip_dissolve", "poppy_hip_set_debug", "poppy_hip_last_warp_kind", "poppy_warp_records", "poppy_hip_hamming_knn2", "poppy_ratio_symmetry",
     "poppy_hip_pair_begin_descriptors", "poppy_hip_warp_affine", "poppy_hip_auto_align", "poppy_hip_align_step",
-    "poppy_procrustes", "poppy_perspective_from4", "poppy_hip_pair_corrected2", "poppy_hip_debug_fetch", "poppy_hip_debug_triangles", "poppy_plan_frame", "poppy_plan_tile_counts", "poppy_plan_tile_tris",
+    "poppy_procrustes", "poppy_perspective_from4", "poppy_hip_pair_corrected2", "poppy_hip_debug_fetch", "poppy_hip_debug_triangles", "poppy_plan_frame", "poppy_plan_tile_counts", "poppy_plan_tile_tris", "poppy_plan_blob_layout",
     "poppy_hip_timing_summary", "poppy_hip_set_timing", "poppy_hip_render_many",
     "poppy_hip_orb_describe", "poppy_hip_hamming_match",
     "poppy_sink_open", "poppy_sink_write", "poppy_sink_close", "poppy_hip_render_phases", "poppy_hip_pool_set_timing", "poppy_hip_pool_timing_summary", "poppy_hip_pool_warp_counts", "poppy_hip_pool_create", "poppy_hip_pool_create_tuned", "poppy_hip_pool_destroy", "poppy_hip_pool_morph_pairs", "poppy_hip_pool_submit_pairs", "poppy_hip_pool_wait", "poppy_count_pair_frames_cb", "poppy_hip_warp_counts", "poppy_hip_time_last_warp", "poppy_hip_mask_rider", "poppy_hip_pool_mask_rider", "poppy_hip_comm_id", "poppy_hip_comm_init", "poppy_hip_comm_free", "poppy_hip_comm_info", "poppy_hip_pair_broadcast", "poppy_hip_comm_max",
@@ -90,6 +90,7 @@ def lib():
         L.poppy_plan_frame.argtypes = [i, i, vp, vp, i, d, i, vp, vp, vp, vp, vp, vp, vp, vp]
         L.poppy_plan_tile_counts.argtypes = [i, i, vp, vp, i, d, i, vp, i, vp, vp, vp]
         L.poppy_plan_tile_tris.argtypes = [i, i, vp, vp, i, d, i, vp, C.c_longlong, vp]
+        L.poppy_plan_blob_layout.argtypes = [i, i, C.c_longlong, C.c_longlong, C.c_longlong, i, vp]
         L.poppy_warp_records.argtypes = [vp, vp, i, i, i, vp]
         L.poppy_hip_hamming_knn2.argtypes = [vp, vp, i, vp, i, vp]
         L.poppy_hip_warp_affine.argtypes = [vp, vp, C.c_size_t, i, i, vp, vp, C.c_size_t]
@@ -358,6 +359,27 @@ def plan_tile_tris(w, h, p1, p2, shape, tile_w):
     if rc or tot.value != total:
         raise PoppyError(f"poppy_plan_tile_tris: {rc}")
     return np.split(tris[:total], np.cumsum(counts.ravel())[:-1])
+
+
+BLOB_FIELDS = ("rec_bytes", "o_edges", "o_outl", "o_toff", "o_ttri", "o_tri", "o_inv", "o_work", "used")
+
+
+def plan_blob_layout(n_tris, n_work, n_toff, n_ttri, fused):
+    """Host-only: the byte offsets of a frame's plan groups in a slot's plan blob (csrc/plan_blob.h), as a dict over BLOB_FIELDS."""
+    out = (C.c_ulonglong * 9)()
+    rc = lib().poppy_plan_blob_layout(0, n_tris, n_work, n_toff, n_ttri, int(bool(fused)), out)
+    if rc:
+        raise PoppyError(f"poppy_plan_blob_layout: {rc}")
+    return dict(zip(BLOB_FIELDS, (int(v) for v in out)))
+
+
+def plan_blob_capacity(n_points, w, h, tile_w=0):
+    """Host-only: what a context allocates for a slot's plan blob — dict(capacity, max_tris, n_tiles, bins_cap, tile_w); tile_w 0: the context's choice."""
+    out = (C.c_ulonglong * 9)()
+    rc = lib().poppy_plan_blob_layout(1, n_points, w, h, tile_w, 0, out)
+    if rc:
+        raise PoppyError(f"poppy_plan_blob_layout: {rc}")
+    return dict(zip(("capacity", "max_tris", "n_tiles", "bins_cap", "tile_w"), (int(v) for v in out)))
 
 
 def warp_records(inv1, inv2, w, h):

@@ -1,13 +1,18 @@
 // context.h — the library's context (one per GPU) and the helpers shared by its translation units:
-//   poppy_hip.cpp     context life cycle, HBM layout, the per-frame path and the resident-pair API
+//   poppy_hip.cpp     context life cycle, HBM layout, plan blob allocation (plan_blob.h), the pair loaders and the C entry points of the resident-pair API
+//   frame_render.cpp  one frame (frame_render.h): the frame body and the two halves of a frame, prepare_slot and render_slot
+//   frame_sequence.cpp  the multi-frame driver (frame_sequence.h): the planner team's SeqPlans, render_frame, render_sequence and its download pump
 //   frame_format.cpp  everything that depends on the writer's frame format (frame_format.h): slot buffers, conversion launches, the palette sequence, the writer ring
 //   pair_setup.cpp    everything that happens once per pair: pre-ORB chain, ORB, matching, auto-align, margins
 //   image_list.cpp    poppy_hip_morph_list;  comm.cpp: pools and RCCL
+//   frame_plan.cpp    host-side planning of a frame;  frame_pal8.cpp, frame_gif.cpp, frame_sink.cpp: the host side of the writer formats and the file sinks
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "foreground.h"
 #include "frame_format.h"
 #include "frame_plan.h"
+#include "frame_render.h"
+#include "frame_sequence.h"
 #include "kernels.h"
 #include "kernels_prefilter.h"
 #include "orb_detect.h"
@@ -19,6 +24,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -34,7 +40,6 @@ struct FrameSlot {
     hipStream_t own_stream = nullptr;    // the slot's own (created at its first frame that stays in HBM)
     hipStream_t last_stream = nullptr;   // the stream the frame last rendered here ran on (the context's for chained frames, `stream` otherwise)
     hipEvent_t done = nullptr;           // end of the frame last rendered here
-    hipEvent_t prepared = nullptr;       // id map and mask of the frame being rendered here are written
     uint8_t *tr1 = nullptr, *tr2 = nullptr, *out = nullptr;
     float *pyrL = nullptr, *pyrR = nullptr, *pyrM = nullptr, *pyrB = nullptr;
     float *tmp = nullptr, *diff = nullptr;      // only for 1-pixel-wide / -high images (separate unsharp passes)
@@ -50,10 +55,8 @@ struct FrameSlot {
     SlotFormat fmt;                                 // the frame in the writer's format: buffers, side stream and event (frame_format.h)
     hipEvent_t downloaded = nullptr;                // completes when the last download of this slot's `out` towards the writer has read it
     bool dl_pending = false;                        // ... and whether such a download was issued since the slot was last rendered into
-    int dl_ring_idx = -1;                           // POPPY_HIP_DL_STREAMS: the ring stream that carries that download
+    int dl_ring_idx = -1;                           // unless POPPY_HIP_DL_EVENTS is set: the ring stream that carries that download
 };
-constexpr size_t kBlobHeader = 64;            // [0] float: unsharp amount; [16], [24] double: the frame's mask (alpha, beta)
-constexpr size_t kBlobMaskAB = 16;
 
 struct poppy_hip_ctx {
     int device = 0;
@@ -72,9 +75,9 @@ struct poppy_hip_ctx {
     bool c2_raw_valid = false;           // ... and whether it belongs to the resident pair
     float *gabor2 = nullptr, *m2 = nullptr;
     std::vector<FrameSlot> slots;        // per-frame working sets, used round-robin
-    void* slot_prep_store = nullptr;     // per slot: the frame prepared there (poppy_hip.cpp: SlotPrep)
+    std::vector<SlotPrep> slot_preps;    // per slot: the frame prepared there (frame_render.h; sized with `slots`)
     unsigned long long frame_seq = 0;    // submit_frame calls so far (a slot prepared ahead names the call it is for)
-    void* seq_plans = nullptr;           // the plans of a multi-frame call in the making (poppy_hip.cpp: SeqPlans), possibly started ahead by a pair loader
+    std::unique_ptr<SeqPlans> seq_plans; // the plans of a multi-frame call in the making (frame_sequence.h), possibly started ahead by a pair loader; ended by end_seq_plans alone
     // called at the beginning (1) and at the end (0) of every pair set-up from raw images (pair_setup.cpp: pair_begin_impl): a pool's set-up gate (comm.cpp)
     void (*setup_hook)(void* user, poppy_hip_ctx* c, int begin) = nullptr;
     void* setup_hook_user = nullptr;
@@ -97,8 +100,6 @@ struct poppy_hip_ctx {
     std::vector<P2f> pts1_0, pts1, pts2;
     // per-frame plan blobs (pinned host + device) live in the frame slots, so the host can plan ahead of the GPU
     int max_tris = 0;
-    // blob layout: [header 64 B: f32 unsharp amount][warp records (T+1)*20 f32][tri_xy T*6 i32][inv1 T*9 f32][inv2 T*9 f32]
-    //              [RasterTri T][work 2*n i32]
     size_t blob_bytes = 0; size_t bins_cap = 0;       // bins_cap: most per-tile triangle-list entries a plan blob has room for
     size_t tile_bytes = 0;                            // size of every slot's tile_data (kernels.h: warp_bin_data_bytes)
     hipStream_t copy_stream = nullptr;
@@ -158,7 +159,7 @@ struct poppy_hip_ctx {
     hipStream_t dl_stream = nullptr;
     bool setup_serial = false;                  // pair set-up: the two images' chains one after the other (set by pools of >= 3 contexts per device and by poppy_hip_set_setup_chains)
     hipEvent_t dl_done[kStageRing] = {};
-    hipStream_t dl_ring[kStageRing] = {};     // POPPY_HIP_DL_STREAMS: a stream per pinned ring buffer, carrying nothing but that buffer's copies (no event is recorded behind a copy)
+    hipStream_t dl_ring[kStageRing] = {};     // unless POPPY_HIP_DL_EVENTS is set: a stream per pinned ring buffer, carrying nothing but that buffer's copies (no event is recorded behind a copy)
 };
 
 // ---- packed pair state (see poppy_hip_ctx::arena) -------------------------------------------------------------------------

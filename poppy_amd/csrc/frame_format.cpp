@@ -1,5 +1,5 @@
 // frame_format.cpp — everything that depends on the format a writer gets its frames in (frame_format.h).  The frame path itself — which stream a frame's
-// conversion runs on, what its completion event rides on, when its copy is issued — is poppy_hip.cpp's (enqueue_body, render_slot, render_sequence_frames).
+// conversion runs on, what its completion event rides on, when its copy is issued — is frame_render.cpp's and frame_sequence.cpp's (enqueue_body, render_slot, render_sequence_frames).
 #include "context.h"
 
 static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H <= (unsigned long long)POPPY_PAL8_MAX_PIXELS; }

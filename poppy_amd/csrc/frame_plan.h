@@ -3,6 +3,7 @@
 // reference's triangle ORDER, integer triangle corners and the two inverse affine matrices per
 // triangle.  The per-pixel work that consumes this plan runs in the HIP kernels.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
