@@ -14,7 +14,7 @@
 //                        run one host thread and one context per device and create their communicators with ncclCommInitAll.
 // librccl is loaded on first use (dlopen): single-GPU callers never touch it, and all entry points come from ONE handle, so a
 // second copy of RCCL in the process (PyTorch ships its own) cannot be mixed in by symbol interposition.
-#include "context.h"
+#include "pair_begin.h"
 #include <dlfcn.h>
 #include <atomic>
 #include <condition_variable>
@@ -259,16 +259,12 @@ int chain_image(poppy_hip_ctx* c, int i, bool with_gabor, double* detail, const 
     const int W = c->W, H = c->H;
     const size_t P = (size_t)W * H;
     if (hipSetDevice(c->device) != hipSuccess) { *err = "hipSetDevice failed"; return POPPY_E_DEVICE; }
-    ForegroundFilter& fg = i ? c->foreground_b : c->foreground;
     hipStream_t st = i ? c->aux_stream : c->stream;
-    const uint8_t* gf = fg.run_device(i ? c->c2 : c->c1, (size_t)W * 3, W, H, st, nullptr);
-    if (!gf) { *err = "foreground: " + fg.err; return POPPY_E_DEVICE; }
-    if (fg.detail(gf, W, H, st, detail)) { *err = "dft_detail2: " + fg.err; return POPPY_E_DEVICE; }
-    const uint8_t* gi = fg.orb_input(gf, W, H, 0, st);
-    if (!gi) { *err = "orb_input: " + fg.err; return POPPY_E_DEVICE; }
-    *g_dev = gi;
+    SetupStatus s;
+    if (!chain_filter(c, i, i ? c->c2 : c->c1, st, detail, g_dev, s)) { *err = s.msg; return s.rc; }
     hipError_t e = hipSuccess;
     if (with_gabor) {
+        ForegroundFilter& fg = chain_fg(c, i);
         const float* gab = fg.gabor_field(c->c2, W, H, st);
         if (!gab) { *err = "gabor_field: " + fg.err; return POPPY_E_DEVICE; }
         e = hipMemcpyAsync(c->gabor2, gab, P * 12, hipMemcpyDeviceToDevice, st);
@@ -381,17 +377,13 @@ int setup_sharded(poppy_hip_ctx* c, Transport& T, const void* d1, const void* d2
             if (n2 > kPairMaxPoints - 1) n2 = -1;
             if (valid && n2 >= 0) p2v.assign(buf.begin() + 2, buf.begin() + 2 + 2 * (size_t)n2);
         } else {
-            if (r2 < 0) n2 = -1;
-            for (int i = 0; i < n2; ++i) { p2v.push_back(k2[i].x); p2v.push_back(k2[i].y); }
+            if (r2 < 0) n2 = -1; else p2v = keypoint_xy(k2);
         }
         if (r1 < 0 || n2 < 0) { valid = false; root_err = r1 < 0 ? "orb_detect (image 1): " + c->orb.err : std::string("image 2's rank reported a failed detection or too many keypoints"); }
         if (valid) {
-            const size_t n = std::min(k1.size(), (size_t)n2);                   // Extractor::points (extractor.cpp:96-99)
-            std::vector<float> p1(n * 2), p2(n * 2), o1((n + 4) * 2), o2((n + 4) * 2);
-            for (size_t i = 0; i < n; ++i) { p1[2 * i] = k1[i].x; p1[2 * i + 1] = k1[i].y; p2[2 * i] = p2v[2 * i]; p2[2 * i + 1] = p2v[2 * i + 1]; }
-            int m = 0;
-            int mr = poppy_match_points(p1.data(), p2.data(), (int)n, W, H, c->cfg.match_tolerance, o1.data(), o2.data(), &m, &c->initial_morph_dist);
-            if (mr == POPPY_OK) mr = set_points(c, o1.data(), o2.data(), m);
+            PointLists pts = extractor_points(k1, p2v.data(), (size_t)n2);
+            int mr = prepare_points(c, pts, W, H, nullptr);
+            if (mr == POPPY_OK) mr = set_points(c, pts.p1.data(), pts.p2.data(), (int)pts.p1.size() / 2);
             if (mr == POPPY_OK) mr = stage_pair_state(c);
             if (mr != POPPY_OK) { valid = false; root_err = "matcher / pair state: " + c->err; }
         }
@@ -660,7 +652,7 @@ poppy_hip_pool* poppy_hip_pool_create(const int* devices, int n_devices, int con
         for (int k = 0; k < contexts_per_device; ++k) {
             poppy_hip_ctx* c = poppy_hip_create(devices[d], settings);
             if (!c) { set_err(err, err_len, std::string("poppy_hip_create: ") + poppy_hip_create_error()); poppy_hip_pool_destroy(p); return nullptr; }
-            // (pair_setup.cpp: from three contexts on the chains of a pair run one after the other — six chains on four hardware queues were a lottery, profiles/r05_notes.md
+            // (pair_begin.cpp: from three contexts on the chains of a pair run one after the other — six chains on four hardware queues were a lottery, profiles/r05_notes.md
             // section 6; still the better form behind the set-up gate: profiles/r06_gate.txt; POPPY_POOL_CHAINS=0 / 1 forces side by side / serial)
             static const int chains_env = getenv("POPPY_POOL_CHAINS") ? atoi(getenv("POPPY_POOL_CHAINS")) : -1;
             c->setup_serial = chains_env >= 0 ? chains_env != 0 : contexts_per_device >= 3;
@@ -686,7 +678,7 @@ void poppy_hip_pool_destroy(poppy_hip_pool* p) {
 }
 
 // The set-up gate: every pair set-up of a pool's contexts — from host images (poppy_hip_morph) or from resident ones (poppy_hip_pair_begin_device) — passes through here
-// (context.h: setup_hook, called by pair_setup.cpp at the set-up's beginning and end)
+// (context.h: setup_hook, called by pair_begin.cpp at the set-up's beginning and end)
 static void pool_setup_hook(void* user, poppy_hip_ctx* c, int begin) {
     poppy_hip_pool* p = static_cast<poppy_hip_pool*>(user);
     const int dev = c->device;

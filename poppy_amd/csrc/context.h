@@ -3,7 +3,8 @@
 //   frame_render.cpp  one frame (frame_render.h): the frame body and the two halves of a frame, prepare_slot and render_slot
 //   frame_sequence.cpp  the multi-frame driver (frame_sequence.h): the planner team's SeqPlans, render_frame, render_sequence and its download pump
 //   frame_format.cpp  everything that depends on the writer's frame format (frame_format.h): slot buffers, conversion launches, the palette sequence, the writer ring
-//   pair_setup.cpp    everything that happens once per pair: pre-ORB chain, ORB, matching, auto-align, margins
+//   pair_begin.cpp    the pair set-up from raw images (pair_begin.h): its schedule and stages, the chain threads (setup_latch.h), the pair_begin entry points
+//   pair_setup.cpp    the stage-by-stage entry points of the once-per-pair half: pre-ORB chain, ORB, matching, auto-align, tables, margins
 //   image_list.cpp    poppy_hip_morph_list;  comm.cpp: pools and RCCL
 //   frame_plan.cpp    host-side planning of a frame;  frame_pal8.cpp, frame_gif.cpp, frame_sink.cpp: the host side of the writer formats and the file sinks
 #pragma once
@@ -78,7 +79,7 @@ struct poppy_hip_ctx {
     std::vector<SlotPrep> slot_preps;    // per slot: the frame prepared there (frame_render.h; sized with `slots`)
     unsigned long long frame_seq = 0;    // submit_frame calls so far (a slot prepared ahead names the call it is for)
     std::unique_ptr<SeqPlans> seq_plans; // the plans of a multi-frame call in the making (frame_sequence.h), possibly started ahead by a pair loader; ended by end_seq_plans alone
-    // called at the beginning (1) and at the end (0) of every pair set-up from raw images (pair_setup.cpp: pair_begin_impl): a pool's set-up gate (comm.cpp)
+    // called at the beginning (1) and at the end (0) of every pair set-up from raw images (pair_begin.cpp: pair_begin_impl): a pool's set-up gate (comm.cpp)
     void (*setup_hook)(void* user, poppy_hip_ctx* c, int begin) = nullptr;
     void* setup_hook_user = nullptr;
     bool plan_ahead_credit = true;       // pair loaders start the default sequence's plans (false after a pair whose plans nobody took, until a multi-frame call comes again)
@@ -126,7 +127,7 @@ struct poppy_hip_ctx {
     uint8_t* bm_canvas = nullptr; uint32_t* bm_tmp = nullptr; int* bm_taps = nullptr; size_t bm_bytes = 0;
     uint8_t* list_img[2] = {nullptr, nullptr}; size_t list_img_bytes = 0;
     hipStream_t aux_stream = nullptr;
-    hipEvent_t setup_ev = nullptr;                  // "the second image's medians are through" (pair set-up: gabor2 starts there)
+    hipEvent_t setup_ev = nullptr;                  // "the first image's chain has queued its detector's first half" (recorded on `stream` by the first chain's thread when the chains run side by side: gabor2 on copy_stream starts there)
     hipEvent_t c2_up_ev = nullptr;                  // "the second host image is in c2" (recorded on aux_stream by the second chain's thread; gabor2 on copy_stream waits for it)
     double initial_morph_dist = 0;
     int last_nfeatures = 0;

@@ -45,7 +45,6 @@ public:
     int prepare2(int w, int h) { return ensure2(w, h); }      // the buffers of part 2 (a caller that uses the object from two threads allocates first)
     std::string err;
 
-    hipEvent_t medians_done = nullptr;   // when set, run_device records it on its stream behind the last median (the pair set-up starts gabor2 there)
     // Which kernel the chain's medians take from median_cols_min_ksize() on: 1 = column histograms (images of few values per neighbourhood), 0 = a lane per
     // column, -1 = ask the device (a presence pass over the grey image and a 4-byte read-back).  Set per image by the caller that holds host pixels
     // (median_cols_hint_from_host); reset to -1 by run_device.  POPPY_MED_COLS_FORCE = 0 / 1 overrides.  Every choice gives the same bytes.

@@ -260,3 +260,6 @@ int render_sequence(poppy_hip_ctx* c, const double* shape, const double* mask, i
     return rc;
 }
 
+// a writer that only counts the frames it is handed (user: a long long, or null)
+extern "C" void poppy_count_frames_cb(void* user, const uint8_t*, int, int, size_t) { if (user) ++*(long long*)user; }
+

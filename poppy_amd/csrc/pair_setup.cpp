@@ -1,9 +1,7 @@
-// pair_setup.cpp — the once-per-pair half of the C ABI (include/poppy_hip.h): ORB / descriptor / matching entry points, the
-// pre-ORB filter chain (Extractor::foreground, dft_detail2, unsharp + Gabor banks), pair set-up from raw images
-// (poppy::morph up to its frame loop, src/poppy.hpp:46-160, incl. Matcher::find / prepare and the auto-align), blur_margin.
-// The per-frame path and the context itself live in poppy_hip.cpp; both share context.h.
-#include "context.h"
-#include <chrono>
+// pair_setup.cpp — the stage-by-stage entry points of the once-per-pair half of the C ABI (include/poppy_hip.h): ORB / descriptor / Hamming
+// matching, the auto-align steps, the matcher, the stages of the pre-ORB filter chain (Extractor::foreground, medians, ORB input, gabor_filter),
+// the host-side tables, blur_margin.  The set-up that runs them all from a raw pair is pair_begin.cpp; both share context.h.
+#include "pair_begin.h"
 #include "dft_exact.h"
 
 // blur_margin's two halves (src/util.cpp:574-602), shared by poppy_hip_blur_margin and poppy_hip_morph_list's device-side padding.
@@ -47,11 +45,7 @@ int poppy_hip_orb_detect(poppy_hip_ctx* c, const uint8_t* gray, size_t stride, i
     if (n < 0) { c->err = "orb_detect: " + c->orb.err; return n == -2 ? POPPY_E_DEVICE : POPPY_E_ARG; }
     *n_kps = n;
     if (n > max_kps) return fail(c, POPPY_E_ARG, "max_kps too small");
-    for (int i = 0; i < n && kps7; ++i) {
-        float* o = kps7 + (size_t)i * 7;
-        o[0] = kps[i].x; o[1] = kps[i].y; o[2] = kps[i].size; o[3] = kps[i].angle; o[4] = kps[i].response;
-        o[5] = (float)kps[i].octave; o[6] = (float)kps[i].class_id;
-    }
+    if (kps7) keypoint_rows7(kps, kps7);
     return POPPY_OK;
 }
 
@@ -158,42 +152,8 @@ int poppy_perspective_from4(const float* s4, const float* d4, double* m) {
     return POPPY_OK;
 }
 
-static int match_points_with(Worker* helper, const float* p1, const float* p2, int n, int W, int H, double tol, float* o1, float* o2, int* n_out, double* imd) {
-    if (n < 0 || W <= 0 || H <= 0 || !n_out || (n && (!p1 || !p2))) return POPPY_E_ARG;
-    std::vector<P2f> a(n), b(n);
-    if (n) { memcpy(a.data(), p1, (size_t)n * 8); memcpy(b.data(), p2, (size_t)n * 8); }
-    drop_out_of_image(a, b, W, H);
-    if (a.empty()) { *n_out = 0; if (imd) *imd = 0; return POPPY_OK; }     // caller falls back to the dissolve (poppy.hpp:125)
-    std::vector<PointPair> pairs;
-    const double d = morph_distance_pairs(a, b, W, H, pairs, helper);
-    if (imd) *imd = d;
-    match_and_prepare_from(pairs, a, b, W, H, tol, d);
-    *n_out = (int)a.size();
-    if (o1) memcpy(o1, a.data(), a.size() * 8);
-    if (o2) memcpy(o2, b.data(), b.size() * 8);
-    return POPPY_OK;
-}
 int poppy_match_points(const float* p1, const float* p2, int n, int W, int H, double tol, float* o1, float* o2, int* n_out, double* imd) {
     return match_points_with(nullptr, p1, p2, n, W, H, tol, o1, o2, n_out, imd);
-}
-
-int poppy_hip_pair_begin_prefiltered(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint8_t* bgr2, size_t s2,
-                                     const uint8_t* g1, const uint8_t* g2, const float* gabor2, int W, int H, int nfeatures) {
-    if (!c || !bgr1 || !bgr2 || !g1 || !g2 || !gabor2) return POPPY_E_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    chain_touch(c);
-    std::vector<OrbKeyPoint> k1, k2;
-    if (c->orb.detect(g1, W, W, H, nfeatures, c->stream, k1) < 0 || c->orb.detect(g2, W, W, H, nfeatures, c->stream, k2) < 0) {
-        c->err = "orb_detect: " + c->orb.err;
-        return POPPY_E_DEVICE;
-    }
-    const size_t n = std::min(k1.size(), k2.size());                    // Extractor::points (extractor.cpp:96-99)
-    std::vector<float> p1(n * 2), p2(n * 2), o1((n + 4) * 2), o2((n + 4) * 2);
-    for (size_t i = 0; i < n; ++i) { p1[2 * i] = k1[i].x; p1[2 * i + 1] = k1[i].y; p2[2 * i] = k2[i].x; p2[2 * i + 1] = k2[i].y; }
-    int m = 0;
-    int rc = poppy_match_points(p1.data(), p2.data(), (int)n, W, H, c->cfg.match_tolerance, o1.data(), o2.data(), &m, &c->initial_morph_dist);
-    if (rc) return fail(c, rc, "poppy_match_points failed");
-    return poppy_hip_pair_load(c, bgr1, s1, bgr2, s2, gabor2, W, H, o1.data(), o2.data(), m);
 }
 
 int poppy_hip_foreground(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* out, const poppy_foreground_debug* dbg) {
@@ -215,318 +175,6 @@ int poppy_hip_median_blur(poppy_hip_ctx* c, const uint8_t* src, int W, int H, in
     const int rc = c->foreground.median(src, W, H, ksize, form, c->stream, dst);
     if (rc) { c->err = "median: " + c->foreground.err; return rc == -1 ? POPPY_E_ARG : POPPY_E_DEVICE; }
     return POPPY_OK;
-}
-
-// Pair set-up from the raw images: the pre-ORB filter chain on the GPU, then the same steps as pair_begin_prefiltered.
-// next: the set-up of the next pair of the CLI's loop (src/poppy.cpp:326) — image 1 is the resident pair's c2 (bgr1 unused); when the chain slot
-// chain_b still holds that image's chain state (kept_gen == chain_gen), image 1's chain is not run again.
-static int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint8_t* bgr2, size_t s2, int W, int H, float ratio,
-                           bool on_device = false, bool next = false) {
-    if (!c) return POPPY_E_ARG;
-    if (next) {
-        if (!c->pair_ready) return fail(c, POPPY_E_STATE, "pair_begin_next: no resident pair");
-        if (W != c->W || H != c->H) return fail(c, POPPY_E_ARG, "pair_begin_next: the image's size differs from the resident pair's");
-        bgr1 = c->c2; s1 = (size_t)W * 3;
-    }
-    if (!bgr1 || !bgr2 || W <= 0 || H <= 0 || s1 < (size_t)W * 3 || s2 < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad image arguments");
-    if (!setup_size_ok(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kSetupSizeMsg);
-    HIPCHK(c, hipSetDevice(c->device));
-    // image 1's chain state is the one the resident pair's set-up left in slot chain_b (never under auto-align: c2 is then the ALIGNED image)
-    const bool reuse = next && ratio < 0.f && c->kept_gen == c->chain_gen;
-    const int sa = reuse ? c->chain_b : 0, sb = 1 - sa;          // the chain slots of image 1 and image 2
-    chain_touch(c);                                               // from here on, nothing is kept until this set-up succeeds
-    struct SetupHook {                                            // a pool lets one context per device set a pair up at a time (comm.cpp: the set-up gate)
-        poppy_hip_ctx* c;
-        explicit SetupHook(poppy_hip_ctx* c_) : c(c_) { if (c->setup_hook) c->setup_hook(c->setup_hook_user, c, 1); }
-        ~SetupHook() { if (c->setup_hook) c->setup_hook(c->setup_hook_user, c, 0); }
-    } setup_hook(c);
-    const auto t_enter = std::chrono::steady_clock::now();
-    int rc = alloc_pair(c, W, H); if (rc) return rc;
-    c->pair_ready = false;
-    c->c2_raw_valid = false;
-    const size_t P = (size_t)W * H;
-    static const bool gabor2_first_env = getenv("POPPY_GABOR2_FIRST") != nullptr;
-    // One image's chain after the other on the GPU: a context of a pool of three or more (three set-ups side by side fill the GPU; two chains each would only put
-    // six chains on the process's four hardware queues — which layout a pool of three got was a lottery with a 25 % slower outcome in one pool of four, profiles/r05_notes.md
-    // section 6), a caller's choice (poppy_hip_set_setup_chains), or POPPY_SETUP_SERIAL
-    static const bool serial_env = getenv("POPPY_SETUP_SERIAL") != nullptr;
-    const bool serial_chains = serial_env || c->setup_serial;
-    // gabor2 (the second raw image only) at the very start of the set-up, beside the first image's chain: with the chains one after the other the context has one chain in flight
-    // and room beside it (a pool step of six pairs 56.7 -> 56.0 ms); with two chains side by side it tripled the first medians' time (round 3) and waits for them
-    // (with image 1's chain reused there is one chain in flight, as with the serial order: gabor2 beside it from the start)
-    const bool gabor2_first = gabor2_first_env || reuse || (serial_chains && getenv("POPPY_GABOR2_LATE") == nullptr);
-    // Host images: the second image is uploaded by its own chain's thread on that chain's stream, so the first image's chain — stream-ordered behind its
-    // own upload — has the GPU to itself for the length of a copy instead of both waiting for both (POPPY_SETUP_UPLOAD_BOTH=1: the order before round 5)
-    static const bool upload_both = getenv("POPPY_SETUP_UPLOAD_BOTH") != nullptr;
-    const bool staged = !on_device && !upload_both && !gabor2_first && !serial_chains && !next;
-    if (next) {                                                   // image 1 = the resident c2 (ordered before c2 is overwritten on the same stream)
-        HIPCHK(c, hipMemcpyAsync(c->c1, c->c2, P * 3, hipMemcpyDeviceToDevice, c->stream));
-        if (on_device) HIPCHK(c, hipMemcpyAsync(c->c2, bgr2, P * 3, hipMemcpyDeviceToDevice, c->stream));
-        else { rc = upload_image(c, c->c2, bgr2, s2, W, H); if (rc) return rc; }
-    } else if (on_device) {
-        HIPCHK(c, hipMemcpyAsync(c->c1, bgr1, P * 3, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->c2, bgr2, P * 3, hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        rc = upload_image(c, c->c1, bgr1, s1, W, H); if (rc) return rc;
-        if (!staged) { rc = upload_image(c, c->c2, bgr2, s2, W, H); if (rc) return rc; }
-    }
-    // POPPY_SETUP_TIMING: host wall time of the set-up's stages on stderr (chains = foreground + detail + ORB input (+ gabor2) of both
-    // images side by side; detect = the two ORB detections; match = the host matcher; finish = m2 + the pair state)
-    static const bool stage_times = getenv("POPPY_SETUP_TIMING") != nullptr;
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    double ms_upload = 0, ms_chains = 0, ms_detect = 0, ms_match = 0, ms_chain_end[2] = {0, 0}, ms_joined = 0;
-    std::vector<uint8_t> g[2];
-    if (ratio >= 0.f) { g[0].resize(P); g[1].resize(P); }
-    const uint8_t* g_dev[2] = {nullptr, nullptr};
-    double d[2] = {0, 0};
-    if (!c->aux_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-    if (!staged) HIPCHK(c, hipStreamSynchronize(c->stream));            // the uploads above
-    ms_upload = since(t_begin);
-    // The two images go through the chain independently (Extractor::foreground -> dft_detail2 -> the ORB input of
-    // Extractor::keypoints; image 2 also through gabor_filter(corrected2 / 255), src/poppy.hpp:119-122): one host thread and
-    // one stream each, so that the medians of one image run beside the Gabor bank of the other.
-    std::string errs[2];
-    std::atomic<int> rcs[2] = {{POPPY_OK}, {POPPY_OK}};          // (each written by its own thread, read by the other once)
-    // with auto-align, gabor2 belongs to the ALIGNED second image (src/poppy.hpp:116-122 runs after Matcher::find): computed further down
-    const bool align_first = c->cfg.enable_auto_align != 0 && ratio < 0.f;
-    // gabor2 depends on the second image alone, not on its chain (and has its own buffers): it goes to the plan-upload stream — idle during a
-    // set-up — and starts when the second image's medians are through, beside the strings of small dependent launches that follow them (at
-    // the very start it ran beside the first medians, one wave per histogram set, and tripled their time; POPPY_GABOR2_FIRST: that order)
-    // (errors go to the CALLING thread's string: with gabor2_late the first image's thread queues this while the second image's thread is inside foreground_b)
-    auto gabor2_on_side_stream = [&](std::string& e, bool other_thread_in_fg_b) -> bool {
-        std::string ge;
-        ForegroundFilter& fg_b = chain_fg(c, sb);
-        const float* gab = fg_b.gabor_field(c->c2, W, H, c->copy_stream, other_thread_in_fg_b ? &ge : nullptr);
-        if (!gab) { e = "gabor_field: " + (other_thread_in_fg_b ? ge : fg_b.err); return false; }
-        if (hipMemcpyAsync(c->gabor2, gab, P * 12, hipMemcpyDeviceToDevice, c->copy_stream) != hipSuccess) { e = "gabor2 copy failed"; return false; }
-        return true;
-    };
-    if (!align_first && gabor2_first && !gabor2_on_side_stream(c->err, false)) return POPPY_E_DEVICE;
-    if (!c->setup_ev) HIPCHK(c, hipEventCreateWithFlags(&c->setup_ev, hipEventDisableTiming));
-    if (!c->c2_up_ev) HIPCHK(c, hipEventCreateWithFlags(&c->c2_up_ev, hipEventDisableTiming));
-    // POPPY_GABOR2_AT: where gabor2 starts — 0 behind the second image's medians, 1 / 2 behind the FIRST image's ORB input / FAST kernels (queued by that
-    // image's thread): the first image's chain is through earlier than the second's, gabor2 then fills the GPU beside the second chain's tail of small launches
-    static const int gabor2_at = getenv("POPPY_GABOR2_AT") ? atoi(getenv("POPPY_GABOR2_AT")) : 2;      // (1080p 3.03 -> 2.96 ms, 4K 8.5 -> 8.1: tools/experiments/gabor2_at_ab.sh)
-    const int gabor2_late = (!align_first && !gabor2_first && !serial_chains) ? gabor2_at : 0;
-    if (gabor2_late && (chain_fg(c, sb).prepare(W, H) || chain_fg(c, sb).prepare2(W, H))) return fail(c, POPPY_E_DEVICE, "foreground buffers");
-    chain_fg(c, sb).medians_done = (!align_first && !gabor2_first && !gabor2_late) ? c->setup_ev : nullptr;
-    // Each image's thread goes on to the detector's second half by itself as soon as BOTH details are known (nfeatures, src/extractor.cpp:40-45):
-    // the other image's detail is ready long before its own candidates are, so nobody waits for a whole chain.  `details` counts the images
-    // whose detail is published (or whose chain failed before it).
-    struct Details {                                                      // a counter two threads wait on (no spinning: the wait can be a chain's length)
-        std::mutex m; std::condition_variable cv; int n = 0;
-        void add() { { std::lock_guard<std::mutex> g(m); ++n; } cv.notify_all(); }
-        void wait_for(int k) { std::unique_lock<std::mutex> g(m); cv.wait(g, [&] { return n >= k; }); }
-    } details;
-    // The staged upload of the second image happens on the second chain's thread and stream; gabor2 reads c2 on copy_stream, queued by the FIRST chain's
-    // thread: that thread waits (host) until the upload has been QUEUED and its event recorded, then makes copy_stream wait for the event (device).
-    // 0 = not yet, 1 = event recorded, -1 = the upload failed (round 5 had no such edge: gabor2 could read a half-written c2 when the helper thread was late)
-    Details c2_uploaded;
-    std::atomic<int> c2_upload_state{staged ? 0 : 1};
-    std::vector<OrbKeyPoint> k1, k2;
-    int nfeatures = 0;
-    struct Publish {                                                      // counts once, at the detail or at whichever exit comes before it
-        Details& d; bool done = false;
-        void now() { if (!done) { done = true; d.add(); } }
-        ~Publish() { now(); }
-    };
-    if (!on_device) {                                                    // which median kernel each image's chain takes: from a sample of the host pixels
-        if (!next) chain_fg(c, sa).median_cols_hint = median_cols_hint_from_host(bgr1, s1, W, H);
-        chain_fg(c, sb).median_cols_hint = median_cols_hint_from_host(bgr2, s2, W, H);
-    }
-    auto chain_of = [&](int i) {
-        Publish publish{details};
-        struct UploadKnown {                                      // whichever way the second chain leaves, the first is not left waiting for its upload
-            Details& d; std::atomic<int>& state; bool mine;
-            ~UploadKnown() { if (mine && state.load() == 0) { state = -1; d.add(); } }
-        } upload_known{c2_uploaded, c2_upload_state, i == 1 && staged};
-        if (hipSetDevice(c->device) != hipSuccess) { errs[i] = "hipSetDevice failed"; rcs[i] = POPPY_E_DEVICE; return; }
-        ForegroundFilter& fg = chain_fg(c, i ? sb : sa);
-        OrbDetector& orb = chain_orb(c, i ? sb : sa);
-        hipStream_t st = i ? c->aux_stream : c->stream;
-        const bool kept = i == 0 && reuse;                        // image 1's chain ran in the previous set-up: its detail and its detector's first half are in place
-        if (kept) { d[0] = c->kept_detail; publish.now(); }
-        if (!kept) {
-            if (i == 1 && staged) {
-                const bool ok = copy_rows_async(c->c2, (size_t)W * 3, bgr2, s2, (size_t)W * 3, H, hipMemcpyHostToDevice, st) == hipSuccess &&
-                                hipEventRecord(c->c2_up_ev, st) == hipSuccess;
-                c2_upload_state = ok ? 1 : -1;
-                c2_uploaded.add();
-                if (!ok) { errs[i] = "pair_begin: upload of the second image failed"; rcs[i] = POPPY_E_DEVICE; return; }
-            }
-            const uint8_t* gf = fg.run_device(i ? c->c2 : c->c1, (size_t)W * 3, W, H, st, nullptr);
-            if (!gf) { errs[i] = "foreground: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
-            if (i == 1 && fg.medians_done) {                          // gabor2 starts when the second image's medians are through (queued now, long before)
-                if (hipStreamWaitEvent(c->copy_stream, fg.medians_done, 0) != hipSuccess) { errs[i] = "gabor2: stream wait failed"; rcs[i] = POPPY_E_DEVICE; return; }
-                if (!gabor2_on_side_stream(errs[i], false)) { rcs[i] = POPPY_E_DEVICE; return; }
-            }
-            // dft_detail2 and the ORB input both read goodFeatures: the ORB input's kernels are queued behind dft_detail2's before the host waits for the detail value
-            // (until round 4 the chain's stream ran dry twice in mid-chain, at the two read-backs of dft_detail2)
-            if (fg.detail_begin(gf, W, H, st)) { errs[i] = "dft_detail2: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
-            const uint8_t* gi = fg.orb_input(gf, W, H, 0, st);
-            if (!gi) { errs[i] = "orb_input: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
-            if (fg.detail_end(&d[i])) { errs[i] = "dft_detail2: " + fg.err; rcs[i] = POPPY_E_DEVICE; return; }
-            publish.now();
-            g_dev[i] = gi;                                            // the detector reads it where it lies; only ORB::compute wants a host copy
-            auto gabor2_behind_this_chain = [&]() {
-                if (staged) {                                         // c2 is written on the other chain's stream: order copy_stream behind that copy
-                    c2_uploaded.wait_for(1);
-                    if (c2_upload_state.load() < 0) return false;     // (the other chain reports the error)
-                    if (hipStreamWaitEvent(c->copy_stream, c->c2_up_ev, 0) != hipSuccess) { errs[i] = "gabor2: stream wait failed"; rcs[i] = POPPY_E_DEVICE; return false; }
-                }
-                if (hipEventRecord(c->setup_ev, st) != hipSuccess || hipStreamWaitEvent(c->copy_stream, c->setup_ev, 0) != hipSuccess) {
-                    errs[i] = "gabor2: stream wait failed"; rcs[i] = POPPY_E_DEVICE; return false;
-                }
-                if (!gabor2_on_side_stream(errs[i], true)) { rcs[i] = POPPY_E_DEVICE; return false; }
-                return true;
-            };
-            if (i == 0 && gabor2_late == 1 && !gabor2_behind_this_chain()) return;
-            hipError_t e = ratio >= 0.f ? hipMemcpyAsync(g[i].data(), gi, P, hipMemcpyDeviceToHost, st) : hipSuccess;
-            if (e != hipSuccess) { errs[i] = std::string("pair_begin: ") + hipGetErrorString(e); rcs[i] = POPPY_E_DEVICE; return; }
-            // the detector's first half needs no nfeatures (which takes BOTH images' detail, src/extractor.cpp:40-45): it follows the chain at once,
-            // so the image that is through first does not wait for the other with the GPU half idle
-            if (orb.detect_begin(gi, W, W, H, st, true) < 0) { errs[i] = "orb_detect: " + orb.err; rcs[i] = POPPY_E_DEVICE; return; }
-            if (i == 0 && gabor2_late == 2 && !gabor2_behind_this_chain()) return;
-        }
-        if (serial_chains) return;                                // (one chain after the other: the second half follows below)
-        details.wait_for(2);
-        if (rcs[i ^ 1]) return;                                   // the other chain failed (its error is reported)
-        const int nf = nfeatures_of(c->cfg.max_keypoints, d[0], d[1]);
-        if (orb.detect_finish(nf, st, i ? k2 : k1) < 0) { errs[i] = "orb_detect: " + orb.err; rcs[i] = POPPY_E_DEVICE; }
-        ms_chain_end[i] = since(t_begin);
-    };
-    if (serial_chains) {
-        const double t0 = since(t_begin);
-        chain_of(0);
-        const double t1 = since(t_begin);
-        chain_of(1);
-        if (stage_times) fprintf(stderr, "  chains one after the other: image 1 %.3f ms, image 2 (+ gabor2) %.3f ms\n", t1 - t0, since(t_begin) - t1);
-    } else {
-        c->setup_worker.run([&]() { chain_of(1); });
-        chain_of(0);
-        if (!c->setup_worker.wait()) { c->err = "pair set-up helper thread: " + c->setup_worker.error(); return POPPY_E_DEVICE; }
-    }
-    chain_fg(c, sb).medians_done = nullptr;
-    ms_joined = since(t_begin);
-    if (!align_first) HIPCHK(c, hipStreamSynchronize(c->copy_stream));                // gabor2 is in place
-    for (int i = 0; i < 2; ++i) if (rcs[i].load()) { c->err = errs[i]; return rcs[i].load(); }
-    c->chains_run += reuse ? 1 : 2;
-    c->chains_reused += reuse ? 1 : 0;
-    ms_chains = since(t_begin);
-    c->last_detail[0] = d[0]; c->last_detail[1] = d[1];
-    nfeatures = nfeatures_of(c->cfg.max_keypoints, d[0], d[1]);          // src/extractor.cpp:40-45
-    c->last_nfeatures = nfeatures;
-    if (serial_chains) {
-        int r1 = 0, r2 = 0;
-        OrbDetector &orb1 = chain_orb(c, sa), &orb2 = chain_orb(c, sb);
-        c->setup_worker.run([&]() { r2 = hipSetDevice(c->device) == hipSuccess ? orb2.detect_finish(nfeatures, c->aux_stream, k2) : -2; });
-        r1 = orb1.detect_finish(nfeatures, c->stream, k1);
-        if (!c->setup_worker.wait()) { c->err = "pair set-up helper thread: " + c->setup_worker.error(); return POPPY_E_DEVICE; }
-        if (r1 < 0 || r2 < 0) { c->err = "orb_detect: " + (r1 < 0 ? orb1.err : orb2.err); return POPPY_E_DEVICE; }
-    }
-    ms_detect = since(t_begin);
-    if (ratio >= 0.f) {
-        // Opt-in descriptor mode (the reference only sketched it, src/experiments.hpp:14-144): ORB::compute on both
-        // keypoint sets, 2-NN Hamming both ways, ratio test, symmetry test; the surviving pairs, in query order, become the
-        // point sets (out-of-image pairs dropped, the four corners appended).  No positional re-pairing, no threshold.
-        std::vector<uint8_t> d1(k1.size() * 32), d2(k2.size() * 32);
-        auto rows7 = [](const std::vector<OrbKeyPoint>& k) {            // cv::KeyPoint field order, all as float
-            std::vector<float> r(k.size() * 7);
-            for (size_t i = 0; i < k.size(); ++i) {
-                float* o = &r[i * 7];
-                o[0] = k[i].x; o[1] = k[i].y; o[2] = k[i].size; o[3] = k[i].angle; o[4] = k[i].response; o[5] = (float)k[i].octave; o[6] = (float)k[i].class_id;
-            }
-            return r;
-        };
-        const std::vector<float> r1v = rows7(k1), r2v = rows7(k2);
-        {
-            int r1 = 0, r2 = 0;
-            std::thread other([&]() { r2 = hipSetDevice(c->device) == hipSuccess ? c->orb_b.describe(g[1].data(), W, W, H, r2v.data(), (int)k2.size(), c->aux_stream, d2.data()) : -2; });
-            r1 = c->orb.describe(g[0].data(), W, W, H, r1v.data(), (int)k1.size(), c->stream, d1.data());
-            other.join();
-            if (r1 < 0 || r2 < 0) { c->err = "orb_describe: " + (r1 < 0 ? c->orb.err : c->orb_b.err); return POPPY_E_DEVICE; }
-        }
-        std::vector<int> k12(k1.size() * 4), k21(k2.size() * 4), sym;
-        if (c->orb.hamming_knn2(d1.data(), (int)k1.size(), d2.data(), (int)k2.size(), c->stream, k12.data()) < 0 ||
-            c->orb.hamming_knn2(d2.data(), (int)k2.size(), d1.data(), (int)k1.size(), c->stream, k21.data()) < 0) {
-            c->err = "hamming_knn2: " + c->orb.err;
-            return POPPY_E_DEVICE;
-        }
-        ratio_symmetry(k12.data(), (int)k1.size(), k21.data(), (int)k2.size(), ratio, sym);
-        std::vector<P2f> a, b;
-        for (size_t i = 0; i + 3 <= sym.size(); i += 3) {
-            a.push_back(P2f{k1[sym[i]].x, k1[sym[i]].y});
-            b.push_back(P2f{k2[sym[i + 1]].x, k2[sym[i + 1]].y});
-        }
-        drop_out_of_image(a, b, W, H);
-        c->last_descriptor_matches = (int)a.size();
-        if (a.empty()) return fail(c, POPPY_E_NOMATCH, "no symmetric descriptor matches");
-        c->initial_morph_dist = morph_distance_ref(a, b, W, H);
-        add_image_corners(a, b, W, H);
-        rc = set_points(c, (const float*)a.data(), (const float*)b.data(), (int)a.size()); if (rc) return rc;
-    } else {
-        const size_t n = std::min(k1.size(), k2.size());                    // Extractor::points (extractor.cpp:96-99)
-        std::vector<float> p1(n * 2), p2(n * 2), o1((n + 4) * 2), o2((n + 4) * 2);
-        for (size_t i = 0; i < n; ++i) { p1[2 * i] = k1[i].x; p1[2 * i + 1] = k1[i].y; p2[2 * i] = k2[i].x; p2[2 * i + 1] = k2[i].y; }
-        if (align_first) {                                                  // Matcher::find, src/matcher.cpp:29-32
-            if (n < 4) return fail(c, POPPY_E_UNSUPPORTED, "auto-align needs at least 4 keypoint pairs (the reference reads 4 unconditionally)");
-            std::vector<P2f> a(n), b(n);
-            memcpy(a.data(), p1.data(), n * 8); memcpy(b.data(), p2.data(), n * 8);
-            if (!c->c2_raw) HIPCHK(c, hipMalloc((void**)&c->c2_raw, P * 3 + 16));       // phase == 1 writes the image as it came in
-            HIPCHK(c, hipMemcpyAsync(c->c2_raw, c->c2, P * 3, hipMemcpyDeviceToDevice, c->stream));
-            c->c2_raw_valid = true;
-            if (c->aligner.run(c->c2, W, H, a, b, c->stream, nullptr)) return fail(c, POPPY_E_DEVICE, c->aligner.err.c_str());
-            memcpy(p2.data(), b.data(), n * 8);
-            const float* gab = chain_fg(c, sb).gabor_field(c->c2, W, H, c->stream);
-            if (!gab) { c->err = "gabor_field: " + chain_fg(c, sb).err; return POPPY_E_DEVICE; }
-            HIPCHK(c, hipMemcpyAsync(c->gabor2, gab, P * 12, hipMemcpyDeviceToDevice, c->stream));
-        }
-        int m = 0;
-        const double ms_m0 = since(t_begin);
-        rc = match_points_with(&c->setup_worker, p1.data(), p2.data(), (int)n, W, H, c->cfg.match_tolerance, o1.data(), o2.data(), &m, &c->initial_morph_dist);
-        if (rc) return fail(c, rc, "poppy_match_points failed");
-        const double ms_m1 = since(t_begin);
-        rc = set_points(c, o1.data(), o2.data(), m); if (rc) return rc;
-        if (stage_times) fprintf(stderr, "  match stage: points out of the keypoints %.3f, matcher %.3f, set_points %.3f ms (cumulative)\n", ms_m0, ms_m1, since(t_begin));
-    }
-    ms_match = since(t_begin);
-    rc = finish_pair_load(c); if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (ratio < 0.f && !align_first) {                                   // image 2's chain state stays for the next pair's image 1 (c2 is that image, unaligned)
-        c->chain_b = sb;
-        c->kept_detail = d[1];
-        c->kept_gen = c->chain_gen;
-    }
-    if (stage_times) fprintf(stderr, "  chains: image 1 through %.3f, image 2 through %.3f, both joined %.3f, gabor2 in place %.3f ms\n", ms_chain_end[0], ms_chain_end[1], ms_joined, ms_chains);
-    if (stage_times)
-        fprintf(stderr, "pair set-up %dx%d: upload %.3f, chains %.3f, detect %.3f, match %.3f, finish %.3f ms (cumulative); before them (drain + queueing the raw pair's copies) %.3f ms\n", W, H, ms_upload, ms_chains,
-                ms_detect, ms_match, since(t_begin), std::chrono::duration<double, std::milli>(t_begin - t_enter).count());
-    return POPPY_OK;
-}
-
-int poppy_hip_pair_begin(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint8_t* bgr2, size_t s2, int W, int H) {
-    return pair_begin_impl(c, bgr1, s1, bgr2, s2, W, H, -1.f);
-}
-int poppy_hip_pair_begin_device(poppy_hip_ctx* c, const void* d1, const void* d2, int W, int H) {
-    return pair_begin_impl(c, (const uint8_t*)d1, (size_t)W * 3, (const uint8_t*)d2, (size_t)W * 3, W, H, -1.f, true);
-}
-int poppy_hip_pair_begin_next(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H) {
-    return pair_begin_impl(c, nullptr, 0, bgr, stride, W, H, -1.f, false, true);
-}
-int poppy_hip_pair_begin_next_device(poppy_hip_ctx* c, const void* d_bgr, int W, int H) {
-    return pair_begin_impl(c, nullptr, 0, (const uint8_t*)d_bgr, (size_t)W * 3, W, H, -1.f, true, true);
-}
-int poppy_hip_chain_counts(poppy_hip_ctx* c, unsigned long long* run, unsigned long long* reused) {
-    if (!c) return POPPY_E_ARG;
-    if (run) *run = c->chains_run;
-    if (reused) *reused = c->chains_reused;
-    return POPPY_OK;
-}
-void poppy_count_frames_cb(void* user, const uint8_t*, int, int, size_t) { if (user) ++*(long long*)user; }
-int poppy_hip_pair_begin_descriptors(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint8_t* bgr2, size_t s2, int W, int H, float ratio) {
-    if (!(ratio >= 0.f)) return c ? fail(c, POPPY_E_ARG, "ratio must be >= 0") : POPPY_E_ARG;
-    return pair_begin_impl(c, bgr1, s1, bgr2, s2, W, H, ratio);
 }
 
 int poppy_hip_pair_corrected2(poppy_hip_ctx* c, uint8_t* dst, size_t ds) {

@@ -108,7 +108,7 @@ def test_setup_alternative_forms_stay_exact():
     POPPY_ORB_CAP=50 (candidate lists far too short for any image: the detector re-allocates them for the counted candidates and runs FAST again —
     what noise-like content does to the default lists: round 4, found by timing the set-up on textured images), POPPY_ORB_KPCAP=64 (the
     same for the keypoint buffers behind the first retainBest, whose ties are unbounded),
-    POPPY_GABOR2_FIRST (gabor2 beside the first medians instead of behind the second image's)."""
+    POPPY_GABOR2_FIRST (gabor2 beside the first medians instead of behind the first image's detector)."""
     import subprocess
     import sys
     forms = [{"POPPY_ACC_STEPS": "0"}, {"POPPY_ACC_STEPS": "1"}, {"POPPY_ACC_STEPS": "2"}, {"POPPY_ACC_STEPS": "4"}, {"POPPY_ACC_STEPS": "6"},
