@@ -447,7 +447,7 @@ int poppy_hip_pair_points(poppy_hip_ctx* ctx, float* points1, float* points2, in
 int poppy_hip_render_many(poppy_hip_ctx* ctx, const double* shape_ratio, const double* mask_ratio, int n, int chain,
                           poppy_write_cb write, void* user);
 
-/* ---- multi-GPU (implementation notes in poppy_amd/csrc/comm.cpp) ----------------------------------------------
+/* ---- multi-GPU (implementation notes in poppy_amd/csrc/rccl_comm.cpp) ----------------------------------------------
  * The path shards by FRAMES of one pair in phase mode (each frame = morph(.., phase = t_j) with number_of_frames = 1,
  * src/poppy.hpp:186-200,234-235) and by PAIRS (the pairs loop of the CLI, src/poppy.cpp:266-328).  The only exchange is the pair
  * state — both images, the mask field's grey complement, the point sets: one contiguous allocation — from the GPU that ran the
@@ -495,7 +495,8 @@ int poppy_hip_pair_import_device(poppy_hip_ctx* ctx, const void* d_src, size_t b
  *                  taken off a shared counter by contexts_per_device host threads per GPU (2-3 fill a GPU: a chained sequence is
  *                  a latency chain, and one pair's set-up runs beside another pair's frames).  `source` hands out pair p's two
  *                  images for the device that will render it (pointers must stay valid until the pair's last frame was written;
- *                  return 0); `write` gets (pair, frame) and is called concurrently.  No communication.
+ *                  return 0); `write` gets (pair, frame) and is called concurrently.  Both are called from the pool's own threads, never
+ *                  from the calling thread.  No communication.
  *   pool_*         the same with contexts (and their HBM) kept between batches; inputs_on_device != 0: `source` returns device
  *                  pointers (tight rows) in the memory of the device it is asked for.
  * err (may be NULL) receives the message of the first failure.                                                              */

@@ -5,7 +5,10 @@
 //   frame_format.cpp  everything that depends on the writer's frame format (frame_format.h): slot buffers, conversion launches, the palette sequence, the writer ring
 //   pair_begin.cpp    the pair set-up from raw images (pair_begin.h): its schedule and stages, the chain threads (setup_latch.h), the pair_begin entry points
 //   pair_setup.cpp    the stage-by-stage entry points of the once-per-pair half: pre-ORB chain, ORB, matching, auto-align, tables, margins
-//   image_list.cpp    poppy_hip_morph_list;  comm.cpp: pools and RCCL
+//   image_list.cpp    poppy_hip_morph_list
+//   rccl_comm.cpp     the RCCL loader and a context's communicator (rccl_comm.h, comm_guard.h): the two collectives, the abort, the pair state's broadcast, export and import
+//   sharded_setup.cpp the pair set-up spread over ranks, as named stages (shard_protocol.h: roles and the keypoint hand-off; local_hub.h: the in-process transport)
+//   morph_sharded.cpp one job over N devices;  pool.cpp: pools of contexts, the set-up gate, batches of pairs
 //   frame_plan.cpp    host-side planning of a frame;  frame_pal8.cpp, frame_gif.cpp, frame_sink.cpp: the host side of the writer formats and the file sinks
 #pragma once
 #include "../../include/poppy_hip.h"
@@ -19,6 +22,8 @@
 #include "orb_detect.h"
 #include "point_match.h"
 #include "auto_align.h"
+#include "comm_guard.h"
+#include "pair_state_limits.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -69,7 +74,7 @@ struct poppy_hip_ctx {
     bool pair_ready = false;
     // resident buffers
     // c1, c2 and m2 live in ONE allocation behind a small header + point area (PairStateHeader): the "pair state" that a
-    // frame needs.  Being contiguous, it travels to other GPUs as a single ncclBroadcast / a single device copy (comm.cpp).
+    // frame needs.  Being contiguous, it travels to other GPUs as a single ncclBroadcast / a single device copy (rccl_comm.cpp).
     uint8_t* arena = nullptr; size_t arena_bytes = 0;
     uint8_t *c1 = nullptr, *c2 = nullptr;
     uint8_t* c2_raw = nullptr;           // image 2 before auto-align (only allocated when auto-align ran): what phase == 1 writes
@@ -79,7 +84,7 @@ struct poppy_hip_ctx {
     std::vector<SlotPrep> slot_preps;    // per slot: the frame prepared there (frame_render.h; sized with `slots`)
     unsigned long long frame_seq = 0;    // submit_frame calls so far (a slot prepared ahead names the call it is for)
     std::unique_ptr<SeqPlans> seq_plans; // the plans of a multi-frame call in the making (frame_sequence.h), possibly started ahead by a pair loader; ended by end_seq_plans alone
-    // called at the beginning (1) and at the end (0) of every pair set-up from raw images (pair_begin.cpp: pair_begin_impl): a pool's set-up gate (comm.cpp)
+    // called at the beginning (1) and at the end (0) of every pair set-up from raw images (pair_begin.cpp: pair_begin_impl): a pool's set-up gate (pool.cpp)
     void (*setup_hook)(void* user, poppy_hip_ctx* c, int begin) = nullptr;
     void* setup_hook_user = nullptr;
     bool plan_ahead_credit = true;       // pair loaders start the default sequence's plans (false after a pair whose plans nobody took, until a multi-frame call comes again)
@@ -138,11 +143,13 @@ struct poppy_hip_ctx {
     struct LastWarp { const float* rec = nullptr; const void* tile_data = nullptr; size_t tile_bytes = 0; const int* toff = nullptr; int tile_w = 0;
                       const uint8_t* c1 = nullptr; const uint8_t* c2 = nullptr; uint8_t* tr1 = nullptr; uint8_t* tr2 = nullptr; WarpExtras ex; bool valid = false; } last_warp;
     int last_descriptor_matches = 0;               // symmetric matches kept by the last pair_begin_descriptors
-    // RCCL communicator of this context (comm.cpp), or null.  Atomic: morph_sharded's abort path takes the pointer AWAY (exchange to null) before
-    // ncclCommAbort frees the communicator, and every collective wrapper loads it once — a late entrant finds null (POPPY_E_STATE), never a freed handle
-    std::atomic<void*> comm{nullptr}; int comm_rank = 0, comm_world = 1;
-    std::atomic<bool> comm_aborted{false};                          // the communicator was aborted under this context: its collectives fail with POPPY_E_STATE until poppy_hip_comm_free
-    double* d_comm_scratch = nullptr;                               // 8 doubles for the small reductions (comm.cpp), allocated on first use
+    // RCCL communicator of this context, or none.  Only rccl_comm.cpp touches it, and hands it to RCCL only inside a CommUse bracket (comm_guard.h) that spans
+    // the enqueue call and never the stream synchronise behind it.  morph_sharded's abort path takes the pointer away and waits for the brackets that are open
+    // before ncclCommAbort frees the communicator: a late entrant finds none (POPPY_E_STATE), and no thread is inside RCCL with a freed handle — unless a
+    // bracket outlasts kCommAbortBoundMs, after which the abort goes ahead regardless and says so in the job's error.  Aborted, the context takes no new
+    // communicator until poppy_hip_comm_free.
+    CommHandle comm; int comm_rank = 0, comm_world = 1;
+    double* d_comm_scratch = nullptr;                               // 8 doubles for the small reductions (rccl_comm.cpp: comm_max_n), allocated with the communicator
     unsigned warp_seq = 0;                      // warp launches issued in timing mode 2 (every kWarpStampStride-th is stamped)
     bool last_warp_fast = false;                   // which warp kernel the last submitted frame used
     bool last_warp_bin = false;
@@ -165,7 +172,7 @@ struct poppy_hip_ctx {
 
 // ---- packed pair state (see poppy_hip_ctx::arena) -------------------------------------------------------------------------
 constexpr size_t kPairHeadBytes = 4096;
-constexpr int kPairMaxPoints = 16384;              // point pairs the packed state has room for
+// (kPairMaxPoints, the point pairs the packed state has room for: pair_state_limits.h)
 struct PairStateHeader {
     uint32_t magic, version;
     int32_t W, H, n_points, nfeatures;
@@ -200,6 +207,7 @@ int adopt_pair_state(poppy_hip_ctx* c);            // arena head -> points, chai
     } while (0)
 
 inline int fail(poppy_hip_ctx* c, int code, const char* msg) { c->err = msg; return code; }
+inline void set_err(char* err, size_t n, const std::string& s) { if (err && n) snprintf(err, n, "%s", s.c_str()); }      // a caller's error buffer (entry points without a context)
 // the pair set-up's dft_detail2 keeps an even number of spectrum rows and columns (include/poppy_hip.h: poppy_hip_pair_begin):
 // a frame one pixel wide or high has none, its detail is 0 / 0 — refused before any launch
 inline bool setup_size_ok(int W, int H) { return W >= 2 && H >= 2; }

@@ -72,7 +72,7 @@ struct PairSetup {                       // one call's state, shared by its two 
     SetupTimes t;
 };
 
-struct SetupHook {                       // a pool lets one context per device set a pair up at a time (comm.cpp: the set-up gate)
+struct SetupHook {                       // a pool lets one context per device set a pair up at a time (pool.cpp: the set-up gate)
     poppy_hip_ctx* c;
     explicit SetupHook(poppy_hip_ctx* c_) : c(c_) { if (c->setup_hook) c->setup_hook(c->setup_hook_user, c, 1); }
     ~SetupHook() { if (c->setup_hook) c->setup_hook(c->setup_hook_user, c, 0); }
@@ -96,12 +96,12 @@ bool queue_gabor2(PairSetup& p, Gabor2At at, SetupStatus& s) {
     if (at != p.sch.gabor2) return true;
     poppy_hip_ctx* c = p.c;
     hipStream_t st = c->copy_stream;
-    std::string other_err, *other = nullptr;
+    bool concurrent = false;
     switch (at) {
     case Gabor2At::kAfterAlign: st = c->stream; break;                    // behind the aligner's warp of c2
     case Gabor2At::kAtStart: break;                                        // (the raw pair's copies have been waited for)
-    case Gabor2At::kBehindFirstDetect:                                     // on the first chain's thread, while the second's is inside the same ForegroundFilter:
-        other = &other_err;                                                // errors go to a string of the caller's, the buffers were prepared before the threads started
+    case Gabor2At::kBehindFirstDetect:                                     // on the first chain's thread, while the second's is inside the same ForegroundFilter
+        concurrent = true;
         if (p.sch.staged) {                                                // c2 is written on the other chain's stream: order copy_stream behind that copy
             if (!p.c2_upload.wait()) return false;                         // (the other chain reports the error)
             if (hipStreamWaitEvent(st, c->c2_up_ev, 0) != hipSuccess) return s.fail("gabor2: stream wait failed");
@@ -110,11 +110,7 @@ bool queue_gabor2(PairSetup& p, Gabor2At at, SetupStatus& s) {
         break;
     }
     ++p.gabor2_queued;
-    ForegroundFilter& fg = chain_fg(c, p.sb);
-    const float* gab = fg.gabor_field(c->c2, p.W, p.H, st, other);
-    if (!gab) return s.fail("gabor_field: " + (other ? other_err : fg.err));
-    if (hipMemcpyAsync(c->gabor2, gab, (size_t)p.W * p.H * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) return s.fail("gabor2 copy failed");
-    return true;
+    return gabor2_into_state(c, chain_fg(c, p.sb), st, s, concurrent);
 }
 
 // Front half of image i's chain, on its own thread and stream: (staged upload ->) filter chain -> its detail published -> the detector's first half (-> gabor2)
@@ -319,6 +315,14 @@ bool chain_filter(poppy_hip_ctx* c, int slot, const uint8_t* d_bgr, hipStream_t 
     *orb_in = fg.orb_input(gf, W, H, 0, st);
     if (!*orb_in) return s.fail("orb_input: " + fg.err);
     if (fg.detail_end(detail)) return s.fail("dft_detail2: " + fg.err);
+    return true;
+}
+
+bool gabor2_into_state(poppy_hip_ctx* c, ForegroundFilter& fg, hipStream_t st, SetupStatus& s, bool concurrent) {
+    std::string own_err;
+    const float* gab = fg.gabor_field(c->c2, c->W, c->H, st, concurrent ? &own_err : nullptr);
+    if (!gab) return s.fail("gabor_field: " + (concurrent ? own_err : fg.err));
+    if (hipMemcpyAsync(c->gabor2, gab, (size_t)c->W * c->H * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) return s.fail("gabor2 copy failed");
     return true;
 }
 

@@ -1,5 +1,5 @@
 // pair_begin.h — the pair set-up from raw images (pair_begin.cpp: poppy::morph up to its frame loop, src/poppy.hpp:46-160) and those of its
-// stages that other units run too: comm.cpp's sharded set-up (one image's filter chain, the matcher's points) and pair_setup.cpp's ORB entry.
+// stages that other units run too: sharded_setup.cpp (one image's filter chain, gabor2, the matcher's points) and pair_setup.cpp's ORB entry.
 #pragma once
 #include "context.h"
 
@@ -12,6 +12,10 @@ struct SetupStatus {
 // One image's filter chain on stream st with chain slot `slot`: Extractor::foreground -> dft_detail2 -> the ORB input of Extractor::keypoints.
 // true: *orb_in is the ORB input where it lies on the device (queued on st) and *detail is known; false: s says why.
 bool chain_filter(poppy_hip_ctx* c, int slot, const uint8_t* d_bgr, hipStream_t st, double* detail, const uint8_t** orb_in, SetupStatus& s);
+
+// gabor2 = gabor_filter(second image / 255) (src/poppy.hpp:119-122) into the pair state: fg's gabor_field of c->c2 and its copy into c->gabor2, both queued on st.
+// concurrent: another thread is inside fg — its buffers were prepared beforehand and the error goes to s alone, not to fg.err.  false: s says why.
+bool gabor2_into_state(poppy_hip_ctx* c, ForegroundFilter& fg, hipStream_t st, SetupStatus& s, bool concurrent = false);
 
 // The matcher's points in two steps, so that the set-up from raw images can align the second image in between (Matcher::find):
 // Extractor::points (extractor.cpp:96-99) — image 1's keypoints and image 2's positions (n2 x, y pairs), both cut to the shorter list's length —

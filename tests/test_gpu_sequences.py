@@ -509,7 +509,7 @@ def test_frame_wait_orders_a_caller_stream_behind_a_phase_mode_frame():
 
 @pytest.mark.parametrize("n_ctx,root", [(2, 0), (3, 0), (3, 1), (4, 2)])
 def test_sharded_pair_setup_between_contexts_equals_the_one_gpu_setup(n_ctx, root):
-    """The pair set-up spread over ranks (comm.cpp: setup_sharded — image 1 on rank root, image 2 on root + 1, the mask field on root + 2,
+    """The pair set-up spread over ranks (sharded_setup.cpp: setup_sharded — image 1 on rank root, image 2 on root + 1, the mask field on root + 2,
     five small exchanges) run between contexts of this process on one GPU: every context ends up with the pair state of the one-GPU set-up —
     same point sets, same nfeatures, and the reference's frames."""
     import ctypes as C
