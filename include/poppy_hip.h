@@ -245,6 +245,37 @@ int poppy_bgr_to_gif_frame(const uint8_t* bgr, size_t stride, int width, int hei
 int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* ctx, const uint8_t* pal8, int width, int height, uint8_t* dst);
 int poppy_bgr_frames_to_gif_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst);
 int poppy_hip_bgr_frames_to_gif_frames(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst);
+/* Scaled hand-off: frames rendered at the pair's resolution and handed to the writer scaled down by a whole factor, on the GPU, in front of the format
+ * conversion.  The pair's resolution decides the keypoints, the mesh and the morph; the scale only decides what crosses the link and what the writer gets.
+ *   The rule.  A factor s is a whole number from 1 to POPPY_FRAME_SCALE_MAX = 8; 1, the default, is the identity.  A width x height BGR frame becomes
+ *      ow x oh, ow = (width + s - 1) / s, oh = (height + s - 1) / s (poppy_frame_scaled_size).  Output pixel (x, y) covers source columns
+ *      [s x, min(s x + s, width)) and rows [s y, min(s y + s, height)), n = 1 .. 64 pixels: blocks are clipped at the right and bottom edges, as I420's chroma
+ *      blocks are, and no pixel is dropped.  Per channel out = (sum + n / 2) / n in integer arithmetic; there is no gamma handling.
+ *   poppy_bgr_downscale is the host statement (dst: oh rows of 3 * ow bytes, dst_stride >= 3 * ow apart).  POPPY_E_ARG, before anything is read or written,
+ *      for a null pointer, an empty frame, a factor outside 1..8, stride < 3 * width or dst_stride < 3 * ow.  poppy_hip_bgr_downscale does the same on the
+ *      context's GPU (upload, the kernel, download): the same bytes.  It needs no resident pair and disturbs none.  The device copy of the source is tight and
+ *      begins (stride - 3 * width) mod 16 bytes behind a 256-byte boundary, so that a caller (a test) reaches every alignment the kernel's launcher tells apart.
+ *   A writer's frame under scale s and format F is F's host statement at the scaled geometry, applied to poppy_bgr_downscale of the BGR frame that a
+ *      context with s = 1 hands out: poppy_bgr_to_i420, poppy_bgr_to_pal8, poppy_bgr_frames_to_pal8, poppy_bgr_to_gif_frame, poppy_bgr_frames_to_gif_frames.
+ *      Under the sequence formats the palette is taken over the SCALED frames.  The writer is told ow, oh and the format's stride for ow (3 * ow, ow or 0);
+ *      a caller opens its sink with poppy_frame_scaled_size.
+ *   Limits are the format's, checked on the scaled geometry and the scaled sequence before any state changes (2^24 pixels per frame, 65535 per side, fewer than
+ *      2^32 per sequence): a pair that a format refuses at s = 1 can be admissible at s = 2.
+ *   Where it applies: exactly where the frame format applies — every frame handed to a writer by poppy_hip_morph, poppy_hip_morph_frames,
+ *      poppy_hip_render_many, poppy_hip_render_phases, poppy_hip_morph_list and the calls of a pool (poppy_hip_pool_set_frame_scale), the phase 0 / 1 and
+ *      t == 0 / 1 copies and the POPPY_E_NOMATCH blend frames included.  Host images among these are scaled by the host statement.
+ *   Where it does not: everything that stays BGR under a format stays full size — poppy_hip_render / poppy_hip_dissolve into an explicit dst,
+ *      poppy_hip_frame_device, poppy_hip_debug_fetch, frames kept on the device (write == NULL), poppy_hip_morph_sharded, poppy_hip_morph_pairs and
+ *      include/poppy_hip_shim.hpp.  The chain is untouched: corrected1 <- frame is the full-size frame, so the BGR frames of a chained sequence under s > 1
+ *      are the scaled frames of the same sequence under s = 1.
+ * poppy_hip_set_frame_scale drains the context's frames, as poppy_hip_set_frame_format does; POPPY_E_ARG outside 1..8, POPPY_E_STATE while a sequence is
+ * open, POPPY_E_UNSUPPORTED (nothing changed) when the resident pair's scaled frame is refused by the context's format.  It takes effect with or without a
+ * resident pair, before or after the format is set. */
+#define POPPY_FRAME_SCALE_MAX 8
+int poppy_hip_set_frame_scale(poppy_hip_ctx* ctx, int factor);
+int poppy_frame_scaled_size(int width, int height, int factor, int* ow, int* oh);
+int poppy_bgr_downscale(const uint8_t* bgr, size_t stride, int width, int height, int factor, uint8_t* dst, size_t dst_stride);
+int poppy_hip_bgr_downscale(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, int factor, uint8_t* dst, size_t dst_stride);
 /* phase == 0 / phase == 1 follow the reference's short-circuit (src/poppy.hpp:54-70): number_of_frames copies of image 1 /
  * image 2 as they were handed to the pair set-up (with auto-align: the UNALIGNED image 2), no frame is rendered.            */
 
@@ -532,6 +563,8 @@ int poppy_hip_pool_warp_counts(poppy_hip_pool* pool, unsigned long long* fused, 
 /* poppy_hip_set_frame_format on every context of the pool; POPPY_E_STATE while batches submitted with poppy_hip_pool_submit_pairs have not been
  * waited for (poppy_hip_pool_wait). */
 int poppy_hip_pool_set_frame_format(poppy_hip_pool* pool, int format);
+/* poppy_hip_set_frame_scale on every context of the pool; POPPY_E_ARG outside 1..POPPY_FRAME_SCALE_MAX, POPPY_E_STATE as for the format. */
+int poppy_hip_pool_set_frame_scale(poppy_hip_pool* pool, int factor);
 /* poppy_hip_mask_rider of the pool's contexts (they share settings and geometry) */
 int poppy_hip_pool_mask_rider(poppy_hip_pool* pool);
 /* The CLI's loop over an image list (src/poppy.cpp:266-328) on ONE context: pair k = (image k, image k + 1), where image k of pair k > 0 is

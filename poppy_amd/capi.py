@@ -47,6 +47,7 @@ SYMBOLS = [
     "poppy_hip_set_frame_format", "poppy_hip_pool_set_frame_format", "poppy_frame_bytes", "poppy_bgr_to_i420", "poppy_bgr_to_pal8", "poppy_bgr_frames_to_pal8",
     "poppy_gif_frame_bytes", "poppy_pal8_to_gif_frame", "poppy_bgr_to_gif_frame", "poppy_hip_pal8_to_gif_frame",
     "poppy_bgr_frames_to_gif_frames", "poppy_hip_bgr_frames_to_gif_frames",
+    "poppy_hip_set_frame_scale", "poppy_hip_pool_set_frame_scale", "poppy_frame_scaled_size", "poppy_bgr_downscale", "poppy_hip_bgr_downscale",
 ]
 
 
@@ -179,6 +180,11 @@ def lib():
         L.poppy_hip_pal8_to_gif_frame.argtypes = [vp, vp, i, i, vp]
         L.poppy_bgr_frames_to_gif_frames.argtypes = [vp, sz, sz, i, i, i, vp]
         L.poppy_hip_bgr_frames_to_gif_frames.argtypes = [vp, vp, sz, sz, i, i, i, vp]
+        L.poppy_hip_set_frame_scale.argtypes = [vp, i]
+        L.poppy_hip_pool_set_frame_scale.argtypes = [vp, i]
+        L.poppy_frame_scaled_size.argtypes = [i, i, i, vp, vp]
+        L.poppy_bgr_downscale.argtypes = [vp, sz, i, i, i, vp, sz]
+        L.poppy_hip_bgr_downscale.argtypes = [vp, vp, sz, i, i, i, vp, sz]
         L.poppy_hypotf_selfcheck.restype = C.c_long
         L.poppy_hypotf_selfcheck.argtypes = [C.c_long, C.c_uint64]
         _lib = L
@@ -295,6 +301,41 @@ def bgr_frames_to_gif_frames(frames, row_pad=0, frame_pad=0):
         if rc:
             raise PoppyError(f"poppy_bgr_frames_to_gif_frames: {rc}")
     return _gif_frames(lib().poppy_bgr_frames_to_gif_frames, chk, frames, row_pad, frame_pad)
+
+
+def frame_scaled_size(w, h, factor):
+    """Host-only: (ow, oh) of a w x h frame scaled down by the whole factor 1..8 (poppy_frame_scaled_size): what a writer under Context.set_frame_scale is
+    told, and what its sink is opened with."""
+    ow, oh = C.c_int(0), C.c_int(0)
+    rc = lib().poppy_frame_scaled_size(int(w), int(h), int(factor), C.byref(ow), C.byref(oh))
+    if rc:
+        raise PoppyError(f"poppy_frame_scaled_size: {rc}")
+    return ow.value, oh.value
+
+
+def _downscale(call, chk, bgr, factor, row_pad, dst_pad):
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    ow, oh = frame_scaled_size(w, h, factor)
+    stride = w * 3 + int(row_pad)
+    if row_pad:
+        buf = np.full((h, stride), 0xA5, np.uint8)
+        buf[:, :w * 3] = a.reshape(h, w * 3)
+        a = buf
+    out = np.full((oh, ow * 3 + int(dst_pad)), 0xA5, np.uint8)
+    chk(call(_p(a), stride, w, h, int(factor), _p(out), ow * 3 + int(dst_pad)))
+    if dst_pad and not (out[:, ow * 3:] == 0xA5).all():
+        raise PoppyError("bgr_downscale wrote into the padding of dst")
+    return out[:, :ow * 3].reshape(oh, ow, 3).copy()
+
+
+def bgr_downscale(bgr, factor, row_pad=0, dst_pad=0):
+    """Host-only: an HxWx3 BGR frame scaled down by the whole factor 1..8 (poppy_bgr_downscale, the host statement of Context.set_frame_scale's rule), as an
+    oh x ow x 3 array.  row_pad / dst_pad: the frame is handed over / taken back with that many extra bytes per row."""
+    def chk(rc):
+        if rc:
+            raise PoppyError(f"poppy_bgr_downscale: {rc}")
+    return _downscale(lib().poppy_bgr_downscale, chk, bgr, factor, row_pad, dst_pad)
 
 
 def pal8_to_bgr(frame, w, h):
@@ -598,6 +639,15 @@ class Pool:
         if not self.h:
             raise PoppyError("poppy_hip_pool_create: " + err.value.decode())
         self.frame_format = FRAME_BGR
+        self.frame_scale = 1
+
+    def set_frame_scale(self, factor):
+        """The whole factor 1..8 every frame handed to a writer is scaled down by, for every context of the pool (poppy_hip_pool_set_frame_scale); PoppyError with the
+        status while submitted batches have not been waited for."""
+        rc = lib().poppy_hip_pool_set_frame_scale(self.h, int(factor))
+        if rc:
+            raise PoppyError(f"poppy_hip_pool_set_frame_scale: {rc}")
+        self.frame_scale = int(factor)
 
     def set_frame_format(self, fmt):
         """FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ (one palette per pair) FRAME_GIF or FRAME_GIF_SEQ (FRAME_PAL8_SEQ coded) for every context of the pool (poppy_hip_pool_set_frame_format); PoppyError with the status while submitted
@@ -746,6 +796,19 @@ class Context:
             raise PoppyError("poppy_hip_create failed: " + L.poppy_hip_create_error().decode())
         self.w = self.h_ = 0
         self.frame_format = FRAME_BGR
+        self.frame_scale = 1
+
+    def set_frame_scale(self, factor):
+        """The whole factor 1..8 (default 1) every frame handed to a writer is scaled down by on the GPU, in front of the format conversion
+        (poppy_hip_set_frame_scale): writers get frames of frame_scaled_size(W, H, factor) in the context's format.  Frames fetched with render(), frames kept
+        on the device and the chain itself stay full size."""
+        self._chk(lib().poppy_hip_set_frame_scale(self.h, int(factor)), "set_frame_scale")
+        self.frame_scale = int(factor)
+
+    def bgr_downscale(self, bgr, factor, row_pad=0, dst_pad=0):
+        """An HxWx3 BGR frame scaled down on this context's GPU (poppy_hip_bgr_downscale: upload, the kernel, download): the bytes of the host's bgr_downscale.
+        The low four bits of row_pad place the device copy of the source that many bytes behind a 256-byte boundary."""
+        return _downscale(lambda *args: lib().poppy_hip_bgr_downscale(self.h, *args), lambda rc: self._chk(rc, "bgr_downscale"), bgr, factor, row_pad, dst_pad)
 
     def set_frame_format(self, fmt):
         """FRAME_BGR (default), FRAME_I420, FRAME_PAL8 or FRAME_PAL8_SEQ (one palette for all frames of a call, which are handed over when the last

@@ -20,6 +20,8 @@ static const char* sequence_refuses(int fmt, int n, int W, int H) {
     return (unsigned long long)n * (unsigned long long)W * (unsigned long long)H >= POPPY_PAL8_SEQ_MAX_PIXELS ? kSeqSizeMsg : nullptr;
 }
 size_t writer_stride(int fmt, int W) { return format_is_coded(fmt) ? 0 : fmt == POPPY_FRAME_BGR ? (size_t)W * 3 : (size_t)W; }
+WriterGeom scaled_geom(int W, int H, int scale) { return WriterGeom{(W + scale - 1) / scale, (H + scale - 1) / scale, scale}; }
+WriterGeom writer_geom(const poppy_hip_ctx* c, bool has_writer) { return scaled_geom(c->W, c->H, has_writer ? c->frame_scale : 1); }
 int writer_format(const poppy_hip_ctx* c, bool has_writer) { return has_writer ? c->frame_format : POPPY_FRAME_BGR; }
 bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer) { return has_writer && format_is_sequence(c->frame_format); }
 
@@ -49,12 +51,14 @@ static int alloc_slot_side(poppy_hip_ctx* c, SlotFormat& f) {
 
 // I420: the slot's I420 buffer.  PAL8: its PAL8 buffer, tables, side stream and event.  GIF: PAL8's (the coder reads the slot's PAL8 frame) and the coded frame, the
 // coder's scratch and the pinned length word.  PAL8_SEQ and GIF_SEQ: the slots' side streams and the context's sequence tables — the store and the index ring depend on the
-// sequence's length and, under GIF_SEQ, the ring of coded frames: seq_begin, seq_finish.
+// sequence's length and, under GIF_SEQ, the ring of coded frames: seq_begin, seq_finish.  All of it in the writer's geometry; with a scale above 1 the scaled BGR frame too.
 int alloc_slot_format(poppy_hip_ctx* c) {
-    const int fmt = c->frame_format, W = c->W, H = c->H;
+    const WriterGeom g = writer_geom(c);
+    const int fmt = c->frame_format, W = g.w, H = g.h;
     if (const char* why = format_refuses(fmt, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     for (FrameSlot& slot : c->slots) {
         SlotFormat& f = slot.fmt;
+        if (g.scaled() && !f.scaled) HIPCHK(c, hipMalloc((void**)&f.scaled, poppy_frame_bytes(POPPY_FRAME_BGR, W, H) + 16));
         if (fmt == POPPY_FRAME_I420 && !f.i420) HIPCHK(c, hipMalloc((void**)&f.i420, poppy_frame_bytes(fmt, W, H) + 16));
         if (format_builds_palette(fmt)) {
             if (!f.pal8) HIPCHK(c, hipMalloc((void**)&f.pal8, poppy_frame_bytes(POPPY_FRAME_PAL8, W, H) + 16));
@@ -74,8 +78,8 @@ int alloc_slot_format(poppy_hip_ctx* c) {
 }
 
 void free_slot_format_pair(SlotFormat& f) {
-    for (uint8_t* b : {f.i420, f.pal8, f.pal8_tables, f.gif, f.gif_scratch}) if (b) (void)hipFree(b);
-    f.i420 = f.pal8 = f.pal8_tables = f.gif = f.gif_scratch = nullptr;
+    for (uint8_t* b : {f.scaled, f.i420, f.pal8, f.pal8_tables, f.gif, f.gif_scratch}) if (b) (void)hipFree(b);
+    f.scaled = f.i420 = f.pal8 = f.pal8_tables = f.gif = f.gif_scratch = nullptr;
     if (f.gif_total) (void)hipHostFree(f.gif_total);
     f.gif_total = nullptr; f.gif_total_dev = nullptr;
 }
@@ -84,21 +88,23 @@ void free_slot_format_ctx(SlotFormat& f) {
     if (f.bgr_done) (void)hipEventDestroy(f.bgr_done);
 }
 void free_context_format(poppy_hip_ctx* c) {
-    for (uint8_t* b : {c->fmt_scratch, c->fmt_scratch_tables, c->seq.tables, c->seq.store, c->seq.idx, c->seq.gif}) if (b) (void)hipFree(b);
+    for (uint8_t* b : {c->scale_scratch, c->fmt_scratch, c->fmt_scratch_tables, c->seq.tables, c->seq.store, c->seq.idx, c->seq.gif}) if (b) (void)hipFree(b);
     if (c->seq.gif_total) (void)hipHostFree(c->seq.gif_total);
-    c->fmt_scratch = c->fmt_scratch_tables = nullptr; c->fmt_scratch_bytes = 0;
+    c->scale_scratch = c->fmt_scratch = c->fmt_scratch_tables = nullptr; c->scale_scratch_bytes = c->fmt_scratch_bytes = 0;
     c->seq = PaletteSeq();
 }
 
-bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt) {
+bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt, int scale) {
     const SlotFormat& f = slot.fmt;
+    if (scale > 1 && !f.scaled) return false;
     if (fmt == POPPY_FRAME_I420) return f.i420 != nullptr;
     if (format_is_sequence(fmt)) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
     if (format_builds_palette(fmt) && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) return false;
     return fmt != POPPY_FRAME_GIF || (f.gif && f.gif_scratch && f.gif_total);
 }
-const uint8_t* slot_frame(const FrameSlot& f, int fmt) {
-    return fmt == POPPY_FRAME_I420 ? f.fmt.i420 : fmt == POPPY_FRAME_PAL8 ? f.fmt.pal8 : fmt == POPPY_FRAME_GIF ? f.fmt.gif : f.out;
+const uint8_t* slot_bgr(const FrameSlot& f, int scale) { return scale > 1 ? f.fmt.scaled : f.out; }
+const uint8_t* slot_frame(const FrameSlot& f, int fmt, int scale) {
+    return fmt == POPPY_FRAME_I420 ? f.fmt.i420 : fmt == POPPY_FRAME_PAL8 ? f.fmt.pal8 : fmt == POPPY_FRAME_GIF ? f.fmt.gif : slot_bgr(f, scale);
 }
 bool slot_frame_length(const FrameSlot& f, int fmt, size_t capacity, size_t* bytes) {
     *bytes = format_is_coded(fmt) ? *(volatile uint32_t*)f.fmt.gif_total : capacity;
@@ -113,7 +119,13 @@ static void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* f
     if (tm) tm->mark("gif_pack");
 }
 
-void enqueue_conversion(int fmt, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm) {
+void enqueue_conversion(int fmt, int scale, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm) {
+    if (scale > 1) {                                               // the conversion's first dispatch; what follows reads the scaled frame
+        launch_bgr_downscale(src_bgr, b.scaled, W, H, scale, s, fmt == POPPY_FRAME_BGR ? done : nullptr);
+        if (tm) tm->mark("frame_scale");
+        const WriterGeom g = scaled_geom(W, H, scale);
+        src_bgr = b.scaled; W = g.w; H = g.h;
+    }
     if (fmt == POPPY_FRAME_I420) {
         launch_bgr_to_i420(src_bgr, b.i420, W, H, s, done);
         if (tm) tm->mark("frame_format");
@@ -131,7 +143,8 @@ void enqueue_conversion(int fmt, const uint8_t* src_bgr, int W, int H, const Slo
 }
 
 int seq_begin(poppy_hip_ctx* c, int n) {
-    const int W = c->W, H = c->H;
+    const WriterGeom g = writer_geom(c);
+    const int W = g.w, H = g.h;
     PaletteSeq& q = c->seq;
     if (q.open) { int rc = seq_abort(c); if (rc) return rc; }      // (a sequence that a device error left open: its frames and sums are dropped, not mixed into this one)
     if (const char* why = sequence_refuses(c->frame_format, n, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);      // (a sequence format: writer_wants_sequence)
@@ -149,17 +162,40 @@ int seq_begin(poppy_hip_ctx* c, int n) {
 
 bool seq_wanted(const poppy_hip_ctx* c) { return c->seq.open && writer_wants_sequence(c, c->writer_attached); }
 int seq_pass(poppy_hip_ctx* c, const uint8_t* d_bgr, uint8_t* dst, hipStream_t s, hipEvent_t done) {
-    launch_pal8_seq_pass(d_bgr, dst, c->seq.tables, c->W, c->H, s, done);
+    const WriterGeom g = writer_geom(c);
+    launch_pal8_seq_pass(d_bgr, dst, c->seq.tables, g.w, g.h, s, done);
     HIPCHK(c, hipGetLastError());
     return POPPY_OK;
 }
 uint8_t* seq_next_place(poppy_hip_ctx* c) { return c->seq.count < c->seq.n ? c->seq.store + (size_t)c->seq.count++ * c->seq.stride : nullptr; }
+
+// a full-size device frame scaled down into the context's scale scratch on c->stream (grown when needed: the stream's order keeps the readers of one frame
+// in front of the next frame's downscale)
+static int scale_into_scratch(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const WriterGeom& g) {
+    const size_t bytes = poppy_frame_bytes(POPPY_FRAME_BGR, g.w, g.h) + 16;
+    if (bytes > c->scale_scratch_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->scale_scratch) (void)hipFree(c->scale_scratch);
+        c->scale_scratch = nullptr; c->scale_scratch_bytes = 0;
+        HIPCHK(c, hipMalloc((void**)&c->scale_scratch, bytes));
+        c->scale_scratch_bytes = bytes;
+    }
+    launch_bgr_downscale(d_bgr, c->scale_scratch, W, H, g.scale, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return POPPY_OK;
+}
 
 int seq_add_image(poppy_hip_ctx* c, const uint8_t* d_bgr) {
     uint8_t* dst = seq_next_place(c);
     if (!dst) return fail(c, POPPY_E_STATE, "more frames than the sequence was opened for");
     Timer tm(c, c->stream);
     if (c->timing == 1) tm.mark(nullptr);
+    const WriterGeom g = writer_geom(c);
+    if (g.scaled()) {
+        int rc = scale_into_scratch(c, d_bgr, c->W, c->H, g); if (rc) return rc;
+        if (c->timing == 1) tm.mark("frame_scale");
+        d_bgr = c->scale_scratch;
+    }
     { int rc = seq_pass(c, d_bgr, dst, c->stream, nullptr); if (rc) return rc; }
     if (c->timing == 1) tm.mark("pal8_seq_hist");
     return POPPY_OK;
@@ -177,7 +213,8 @@ void seq_abort_keep_error(poppy_hip_ctx* c) { const std::string why = c->err; (v
 // stream (render_sequence_frames: no event behind a copy), the palette behind the indices on the host.
 static int seq_hand_over_indices(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
     PaletteSeq& q = c->seq;
-    const int n = q.count, W = c->W, H = c->H;
+    const WriterGeom g = writer_geom(c);
+    const int n = q.count, W = g.w, H = g.h;
     const bool marks = c->timing == 1;
     uint8_t pal[768];
     HIPCHK(c, hipMemcpyAsync(pal, q.tables + kPal8SeqPaletteOffset, 768, hipMemcpyDeviceToHost, c->stream));
@@ -229,7 +266,8 @@ static void enqueue_seq_gif_coding(const uint8_t* bgr, const uint8_t* seq_tables
 // buffer's stream) while the host waits for frame k's length, its copy runs and the writer has the frames before it; the writer gets the frames in order.
 static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
     PaletteSeq& q = c->seq;
-    const int n = q.count, W = c->W, H = c->H;
+    const WriterGeom g = writer_geom(c);
+    const int n = q.count, W = g.w, H = g.h;
     const bool marks = c->timing == 1;
     const size_t capacity = poppy_frame_bytes(POPPY_FRAME_GIF_SEQ, W, H), frame_part = (capacity + 16 + 255) & ~(size_t)255;
     const size_t each = frame_part + ((gif_scratch_bytes(W, H) + 255) & ~(size_t)255);
@@ -387,8 +425,13 @@ static int gif_from_device_pal8(poppy_hip_ctx* c, const uint8_t* d_pal8, int W, 
     return POPPY_OK;
 }
 
-int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host, size_t* stride, int n_copies) {
+int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const WriterGeom& g, std::vector<uint8_t>& host, size_t* stride, int n_copies) {
     const int fmt = c->frame_format;
+    if (const char* why = format_refuses(fmt, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    if (g.scaled()) {                                              // scaled first, on the device; everything below is in the writer's geometry
+        int rc = scale_into_scratch(c, d_bgr, W, H, g); if (rc) return rc;
+        d_bgr = c->scale_scratch; W = g.w; H = g.h;
+    }
     if (format_is_sequence(fmt)) {                                 // the copies are the sequence: the host statement on the BGR frame
         std::vector<uint8_t> bgr((size_t)W * H * 3);
         HIPCHK(c, hipMemcpyAsync(bgr.data(), d_bgr, bgr.size(), hipMemcpyDeviceToHost, c->stream));
@@ -401,7 +444,6 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::ve
     const uint8_t* d_frame = d_bgr;
     if (fmt != POPPY_FRAME_BGR) {                                  // converted into the context's scratch: the slots' launches on other buffers
         const bool gif = fmt == POPPY_FRAME_GIF;
-        if (const char* why = format_refuses(fmt, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
         if (format_builds_palette(fmt)) { int rc = alloc_zeroed_tables(c, &c->fmt_scratch_tables, kPal8TableBytes); if (rc) return rc; }
         const size_t bytes = poppy_frame_bytes(gif ? POPPY_FRAME_PAL8 : fmt, W, H);
         if (bytes + 16 > c->fmt_scratch_bytes) {
@@ -413,7 +455,7 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::ve
         }
         SlotFormat scratch;
         scratch.i420 = scratch.pal8 = c->fmt_scratch; scratch.pal8_tables = c->fmt_scratch_tables;
-        enqueue_conversion(gif ? POPPY_FRAME_PAL8 : fmt, d_bgr, W, H, scratch, c->stream, nullptr, nullptr);
+        enqueue_conversion(gif ? POPPY_FRAME_PAL8 : fmt, 1, d_bgr, W, H, scratch, c->stream, nullptr, nullptr);
         HIPCHK(c, hipGetLastError());
         if (gif) return gif_from_device_pal8(c, c->fmt_scratch, W, H, host);
         d_frame = c->fmt_scratch;
@@ -442,16 +484,25 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
 }
 
 int write_device_image(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, int n_copies, poppy_write_cb write, void* user) {
+    const WriterGeom g = scaled_geom(W, H, c->frame_scale);
     std::vector<uint8_t> host; size_t stride = 0;
-    int rc = download_frame(c, d_bgr, W, H, host, &stride, n_copies); if (rc) return rc;
-    for (int j = 0; j < n_copies; ++j) write(user, host.data(), W, H, stride);
+    int rc = download_frame(c, d_bgr, W, H, g, host, &stride, n_copies); if (rc) return rc;
+    for (int j = 0; j < n_copies; ++j) write(user, host.data(), g.w, g.h, stride);
     return POPPY_OK;
 }
 int write_host_image(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, int n_copies, poppy_write_cb write, void* user) {
-    std::vector<uint8_t> tmp; int rc = POPPY_OK;
-    const uint8_t* frame = host_frame(c, bgr, stride, W, H, tmp, &stride, &rc, n_copies);
+    const WriterGeom g = scaled_geom(W, H, c->frame_scale);
+    if (const char* why = format_refuses(c->frame_format, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    std::vector<uint8_t> small, tmp; int rc = POPPY_OK;
+    if (g.scaled()) {                                              // the host statement, then the format's as for any host image
+        small.resize(poppy_frame_bytes(POPPY_FRAME_BGR, g.w, g.h));
+        rc = poppy_bgr_downscale(bgr, stride, W, H, g.scale, small.data(), (size_t)g.w * 3);
+        if (rc) return fail(c, rc, "the frame could not be scaled");
+        bgr = small.data(); stride = (size_t)g.w * 3;
+    }
+    const uint8_t* frame = host_frame(c, bgr, stride, g.w, g.h, tmp, &stride, &rc, n_copies);
     if (!frame) return rc;
-    for (int j = 0; j < n_copies; ++j) write(user, frame, W, H, stride);
+    for (int j = 0; j < n_copies; ++j) write(user, frame, g.w, g.h, stride);
     return POPPY_OK;
 }
 
@@ -462,9 +513,51 @@ int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
     if (!format_known(format)) return fail(c, POPPY_E_ARG, "unknown frame format");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = drain_frames(c); if (rc) return rc; }
-    if (c->c1) if (const char* why = format_refuses(format, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    if (c->c1) if (const char* why = format_refuses(format, writer_geom(c).w, writer_geom(c).h)) return fail(c, POPPY_E_UNSUPPORTED, why);
     c->frame_format = format;
     return c->c1 ? alloc_slot_format(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
+}
+
+// A new scale resizes every buffer of the writer's geometry: the slots' are freed and allocated again, and the captured bodies, which hold their addresses, go.
+int poppy_hip_set_frame_scale(poppy_hip_ctx* c, int factor) {
+    if (!c) return POPPY_E_ARG;
+    if (factor < 1 || factor > POPPY_FRAME_SCALE_MAX) return fail(c, POPPY_E_ARG, "the frame scale is a whole factor from 1 to 8");
+    if (c->seq.open) return fail(c, POPPY_E_STATE, "a sequence is open on this context");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = drain_frames(c); if (rc) return rc; }
+    if (factor == c->frame_scale) return POPPY_OK;
+    if (c->c1) {
+        const WriterGeom g = scaled_geom(c->W, c->H, factor);
+        if (const char* why = format_refuses(c->frame_format, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    }
+    c->frame_scale = factor;
+    if (!c->c1) return POPPY_OK;                                   // (a pair allocated later gets its buffers in alloc_pair)
+    for (FrameSlot& f : c->slots) {
+        if (f.body) { (void)hipGraphExecDestroy(f.body); f.body = nullptr; }
+        free_slot_format_pair(f.fmt);
+    }
+    return alloc_slot_format(c);
+}
+
+int poppy_hip_bgr_downscale(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, int factor, uint8_t* dst, size_t dst_stride) {
+    if (!c) return POPPY_E_ARG;
+    int ow = 0, oh = 0;
+    if (!bgr || !dst || poppy_frame_scaled_size(W, H, factor, &ow, &oh) != POPPY_OK || stride < (size_t)W * 3 || dst_stride < (size_t)ow * 3)
+        return fail(c, POPPY_E_ARG, "bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    // everything lives for the call; the source's place behind a 256-byte boundary is the row pad's low bits (include/poppy_hip.h)
+    const size_t row = (size_t)W * 3, shift = (stride - row) % 16, out_row = (size_t)ow * 3;
+    uint8_t *d_src = nullptr, *d_dst = nullptr;
+    hipError_t e = hipMalloc((void**)&d_src, row * H + shift + 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_dst, out_row * oh + 16);
+    if (e == hipSuccess) e = copy_rows_async(d_src + shift, row, bgr, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { launch_bgr_downscale(d_src + shift, d_dst, W, H, factor, c->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = copy_rows_async(dst, dst_stride, d_dst, out_row, out_row, (size_t)oh, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go
+    if (e == hipSuccess) e = e_sync;
+    for (uint8_t* b : {d_src, d_dst}) if (b) (void)hipFree(b);
+    if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("BGR downscale: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    return POPPY_OK;
 }
 
 int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* c, const uint8_t* pal8, int W, int H, uint8_t* dst) {

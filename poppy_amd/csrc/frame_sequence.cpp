@@ -119,6 +119,7 @@ struct FramePump {
     poppy_hip_ctx* c;
     poppy_write_cb write; void* user;
     int fmt;                               // the writer's format: the frame body converts the frame into the slot's buffer of that format (enqueue_body)
+    WriterGeom geom;                       // the writer's geometry: what it is told, and what sizes row and frame_bytes
     size_t row, frame_bytes;               // (GIF: a coded frame goes to the writer with stride 0; frame_bytes is its capacity, which sizes the pinned ring — a frame's copy moves its own length)
     bool dev_wait, dl_streams;
     WriterRing ring;                       // (frames 0 .. ring.issued - 1: their downloads are queued)
@@ -138,7 +139,7 @@ struct FramePump {
         if (dl_streams) {
             hipStream_t ds = nullptr;
             if (e == hipSuccess) e = ring.stream(c, k, &ds);
-            if (e == hipSuccess) e = hipMemcpyAsync(ring.buffer(k), slot_frame(f, fmt), copy_bytes, hipMemcpyDeviceToHost, ds);
+            if (e == hipSuccess) e = hipMemcpyAsync(ring.buffer(k), slot_frame(f, fmt, geom.scale), copy_bytes, hipMemcpyDeviceToHost, ds);
             f.dl_pending = true; f.dl_ring_idx = r;
             if (e != hipSuccess) { c->err = std::string("frame download: ") + hipGetErrorString(e); rc = POPPY_E_DEVICE; return false; }
             return true;
@@ -148,7 +149,7 @@ struct FramePump {
         static const bool skip_copy = getenv("POPPY_DL_SKIP_COPY") != nullptr;      // timing experiment: every wait and event of the writer path, no bytes moved (wrong frames)
         if (!skip_copy)
 #endif
-        if (e == hipSuccess) e = hipMemcpyAsync(ring.buffer(k), slot_frame(f, fmt), copy_bytes, hipMemcpyDeviceToHost, c->dl_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ring.buffer(k), slot_frame(f, fmt, geom.scale), copy_bytes, hipMemcpyDeviceToHost, c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(c->dl_done[r], c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(f.downloaded, c->dl_stream);          // the slot's own: ring events are re-recorded every R frames
         f.dl_pending = true;
@@ -160,7 +161,7 @@ struct FramePump {
         uint8_t* frame = nullptr;
         if (ring.deliver_next(c, !dl_streams, &frame) != hipSuccess) { c->err = "frame download failed"; rc = POPPY_E_DEVICE; return; }
         ms_deliver += lap(t0);
-        write(user, frame, c->W, c->H, row);
+        write(user, frame, geom.w, geom.h, row);
     }
     // the downloads of the frames before `upto` are queued, each behind the delivery that frees its ring buffer
     void pump(int upto) {
@@ -198,9 +199,10 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
     static const bool dev_wait = getenv("POPPY_HIP_DL_DEVWAIT") != nullptr;
     static const bool dl_streams = getenv("POPPY_HIP_DL_EVENTS") == nullptr && !dev_wait;
     const int fmt = writer_format(c, write != nullptr);
+    const WriterGeom geom = writer_geom(c, write != nullptr);
     for (const FrameSlot& f : c->slots)
-        if (!slot_format_ready(c, f, fmt)) return fail(c, POPPY_E_STATE, "the frame format's buffers are not allocated for this pair");
-    FramePump dlp{c, write, user, fmt, writer_stride(fmt, W), poppy_frame_bytes(fmt, W, H), dev_wait, dl_streams};
+        if (!slot_format_ready(c, f, fmt, geom.scale)) return fail(c, POPPY_E_STATE, "the frame format's buffers are not allocated for this pair");
+    FramePump dlp{c, write, user, fmt, geom, writer_stride(fmt, geom.w), poppy_frame_bytes(fmt, geom.w, geom.h), dev_wait, dl_streams};
     dlp.slot_of.assign(n, -1);
     const bool dl = write && !seq;                                // frames are downloaded and handed over as they finish
     int rc = POPPY_OK;

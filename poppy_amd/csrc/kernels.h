@@ -204,6 +204,12 @@ void launch_dissolve(const uint8_t* a, const uint8_t* b, uint8_t* dst, size_t n,
 // tight u8x3 BGR -> I420 (kernels_frame_format.hip; the format: include/poppy_hip.h, POPPY_FRAME_I420).  `done` (optional) rides on the last dispatch.
 void launch_bgr_to_i420(const uint8_t* src, uint8_t* dst, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
 
+// tight u8x3 BGR, w x h -> the frame scaled down by the whole factor s (1..8), tight, ((w + s - 1) / s) x ((h + s - 1) / s) (kernels_frame_scale.hip; the rule:
+// include/poppy_hip.h, poppy_hip_set_frame_scale).  `done` (optional) rides on the last dispatch.  bgr_downscale_wide: whether the launcher takes the wide
+// form for these arguments (s = 2, 4, 8; w % 8 == 0; h >= s; an 8-byte aligned src, dst aligned to 8 / s bytes) — decided by them alone.
+void launch_bgr_downscale(const uint8_t* src, uint8_t* dst, int w, int h, int s, hipStream_t stream, hipEvent_t done = nullptr);
+bool bgr_downscale_wide(const uint8_t* src, const uint8_t* dst, int w, int h, int s);
+
 // tight u8x3 BGR -> PAL8 (kernels_frame_pal8.hip; the format: include/poppy_hip.h, POPPY_FRAME_PAL8), three dispatches on one stream: the cells' histogram,
 // the palette build (one workgroup; writes the palette behind dst's index plane), the index plane.  `tables`: kPal8TableBytes of device memory that is all
 // zero before the first frame (the build leaves the histogram zero again) and that no other frame uses meanwhile: two 64-bit words per cell, then the

@@ -12,8 +12,10 @@ and, at the end, the conversion kernels' own times in timing mode 1 at 1080p and
 PAL8_SEQ: pal8_seq_hist per frame, pal8_seq_build per sequence, frame_format = the index plane; GIF: PAL8's three, then gif_lzw and gif_pack).  Under PAL8_SEQ a pair's (a call's) frames are handed over after its last
 frame.
 
-    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif]
---formats leaves formats out (a library older than GIF: bgr,i420,pal8,pal8_seq).  GIF's d2h_ceiling entry is its CAPACITY (poppy_frame_bytes); a frame's copy moves its own
+    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif --scales 1,2 --kernel-scales 2,4]
+--formats leaves formats out (a library older than GIF: bgr,i420,pal8,pal8_seq).  --scales adds every format again per scale above 1 (poppy_hip_set_frame_scale: the
+column "gif@2" is GIF at scale 2), alternated with the others in the same process; --kernel-scales adds k_bgr_downscale's own time (timing mode 1: frame_scale) under BGR
+at 1080p and 4K for those factors.  GIF's d2h_ceiling entry is its CAPACITY (poppy_frame_bytes); a frame's copy moves its own
 length, which depends on the content.  One JSON line at the end.
 """
 import argparse
@@ -76,9 +78,19 @@ def main():
     ap.add_argument("--contexts", type=int, default=6)
     ap.add_argument("--rows", default="pool_1080p,pool_4k,job480,chained,chained_frame,d2h_ceiling")
     ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq,gif")
+    ap.add_argument("--scales", default="1")
+    ap.add_argument("--kernel-scales", default="")
     a = ap.parse_args()
     rows = a.rows.split(",")
-    FMTS = tuple((f, v) for f, v in ALL_FMTS if f in a.formats.split(","))
+    scales = [int(x) for x in a.scales.split(",")]
+    # a column is a format at a scale; scale 1 keeps the format's plain name and never calls the scale setter
+    FMTS = tuple((f if sc == 1 else f"{f}@{sc}", (v, sc)) for f, v in ALL_FMTS if f in a.formats.split(",") for sc in scales)
+
+    def set_column(target, col):
+        fmt, sc = col
+        target.set_frame_format(fmt)
+        if scales != [1]:
+            target.set_frame_scale(sc)
     import torch
     dev = torch.device("cuda", 0)
     res = {r: {f: [] for f, _ in FMTS} for r in rows if r != "d2h_ceiling"}
@@ -95,12 +107,12 @@ def main():
     for run in range(a.runs):
         for name, fmt in FMTS:
             if pool:
-                pool.set_frame_format(fmt)
+                set_column(pool, fmt)
                 res["pool_1080p"][name].append(pool_row(pool, ptrs, W, H, a.steps, torch))
             if pool4:
-                pool4.set_frame_format(fmt)
+                set_column(pool4, fmt)
                 res["pool_4k"][name].append(pool_row(pool4, [(x.data_ptr(), y.data_ptr()) for x, y in p4k], 3840, 2160, a.steps_4k, torch))
-            ctx.set_frame_format(fmt)
+            set_column(ctx, fmt)
             if "job480" in rows:
                 ctx.pair_begin_device(ta.data_ptr(), tb.data_ptr(), W, H); ctx.render_phases(ph480, counted=True); ctx.sync()
                 t0 = time.perf_counter()
@@ -127,21 +139,24 @@ def main():
         print(f"run {run}: " + ", ".join(f"{r} {f} {v[f][-1]:.0f}" for r, v in res.items() for f in v), flush=True)
     out = {"unit": "frames/s", "rows": {r: {f: summary(v) for f, v in fv.items()} for r, fv in res.items()}}
     for r, fv in res.items():
-        for f in (f for f, _ in FMTS if f != "bgr"):
+        for f in (f for f, _ in FMTS if f != "bgr" and "bgr" in fv):
             out["rows"][r][f + "_over_bgr_median"] = round(statistics.median(fv[f]) / statistics.median(fv["bgr"]), 3)
     if "d2h_ceiling" in rows:
-        out["d2h_ceiling"] = {f"{w}x{h}_{f}": d2h(torch, dev, capi.frame_bytes(fmt, w, h)) for w, h in ((1920, 1080), (3840, 2160)) for f, fmt in FMTS}
+        out["d2h_ceiling"] = {f"{w}x{h}_{f}": d2h(torch, dev, capi.frame_bytes(fmt, -(-w // sc), -(-h // sc))) for w, h in ((1920, 1080), (3840, 2160)) for f, (fmt, sc) in FMTS}
     # the conversion kernels in timing mode 1 (events around every kernel of a chained frame): time per launch
     out["timing_mode1_us"] = {}
     for (w, h), (x, y) in (((W, H), (ta, tb)),) + ((((3840, 2160), p4k[0]),) if p4k else ()):
-        for name, fmt in FMTS[1:]:
-            ctx.set_frame_format(fmt)
+        kernel_cols = tuple((f"bgr@{k}", (capi.FRAME_BGR, int(k))) for k in a.kernel_scales.split(",") if k)
+        for name, fmt in tuple(c for c in FMTS if c[1] != (capi.FRAME_BGR, 1)) + kernel_cols:
+            ctx.set_frame_format(fmt[0])
+            if fmt[1] != 1 or scales != [1]:
+                ctx.set_frame_scale(fmt[1])
             ctx.pair_begin_device(x.data_ptr(), y.data_ptr(), w, h)
             ctx.set_timing(1)
             ctx.reset(); ctx.render_many_counted(shapes, chain=True)
             t = {n: (ms, k) for n, ms, k in ctx.timing_summary()}
             ctx.set_timing(0)
-            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build", "gif_lzw", "gif_pack")}
+            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_scale", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build", "gif_lzw", "gif_pack")}
     for p in (pool, pool4):
         if p:
             p.close()
