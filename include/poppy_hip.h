@@ -270,12 +270,58 @@ int poppy_hip_bgr_frames_to_gif_frames(poppy_hip_ctx* ctx, const uint8_t* bgr, s
  *      are the scaled frames of the same sequence under s = 1.
  * poppy_hip_set_frame_scale drains the context's frames, as poppy_hip_set_frame_format does; POPPY_E_ARG outside 1..8, POPPY_E_STATE while a sequence is
  * open, POPPY_E_UNSUPPORTED (nothing changed) when the resident pair's scaled frame is refused by the context's format.  It takes effect with or without a
- * resident pair, before or after the format is set. */
+ * resident pair, before or after the format is set.  A factor above 1 returns POPPY_E_STATE while a size is set (poppy_hip_set_frame_size). */
 #define POPPY_FRAME_SCALE_MAX 8
 int poppy_hip_set_frame_scale(poppy_hip_ctx* ctx, int factor);
 int poppy_frame_scaled_size(int width, int height, int factor, int* ow, int* oh);
 int poppy_bgr_downscale(const uint8_t* bgr, size_t stride, int width, int height, int factor, uint8_t* dst, size_t dst_stride);
 int poppy_hip_bgr_downscale(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, int factor, uint8_t* dst, size_t dst_stride);
+/* Resized hand-off: the scaled hand-off with a free size instead of a whole factor — frames rendered at the pair's resolution and handed to the writer as
+ * ow x oh frames, resampled on the GPU in front of the format conversion.  A context has a scale above 1 or a size, never both.
+ *   The rule: exact area resampling in integer arithmetic.  A width x height BGR frame becomes ow x oh, where 1 <= ow <= width, 1 <= oh <= height,
+ *      width <= POPPY_FRAME_SCALE_MAX * ow and height <= POPPY_FRAME_SCALE_MAX * oh: downscale only, by at most 8 per axis; the aspect ratio need not be kept.
+ *      Columns are measured in units of 1 / ow of a source pixel: output column x covers [x * width, (x + 1) * width), source column i covers
+ *      [i * ow, (i + 1) * ow), and wx(x, i) is the length of their overlap, a whole number 0..ow.  It is non-zero for i from (x * width) / ow to
+ *      ((x + 1) * width - 1) / ow; over i it sums to width, over x to ow.  wy(y, r) is the same with height and oh.  Per channel
+ *         out(x, y) = (sum over r, i of wy(y, r) * wx(x, i) * src(i, r) + (width * height) / 2) / (width * height)
+ *      with integer divisions and the numerator formed in 64 bits; there is no gamma handling.  The numerator is at most 255.5 * width * height, which fits
+ *      an unsigned 32-bit word exactly when width * height <= 2^24: the device forms 32-bit sums up to that size and 64-bit sums above it.
+ *   Properties.  Identity: ow = width and oh = height returns the frame.  A constant frame stays constant.  Where width = s * ow and height = s * oh the
+ *      bytes are exactly those of the whole-factor rule at factor s (every weight is ow resp. oh; DESIGN.md section 4 has the derivation).  Where the
+ *      whole-factor rule clips its edge blocks (width % s != 0 or height % s != 0) the two rules differ by design: this one stretches every output pixel
+ *      over the same share of the frame, that one clips.
+ *   poppy_bgr_resize_area is the host statement (dst: oh rows of 3 * ow bytes, dst_stride >= 3 * ow apart).  POPPY_E_ARG, before anything is read or
+ *      written, for a null pointer, an empty frame, an inadmissible size, stride < 3 * width or dst_stride < 3 * ow.  poppy_hip_bgr_resize_area does the
+ *      same on the context's GPU (upload, the kernel, download): the same bytes.  It needs no resident pair and disturbs none.  The device copy of the source
+ *      is tight and begins (stride - 3 * width) mod 16 bytes behind a 256-byte boundary, so that a caller (a test) reaches every alignment of the source.
+ *   poppy_frame_fit_size gives the largest size inside a max_width x max_height box that keeps the aspect ratio: (width, height) itself when the frame fits;
+ *      else, when width * max_height >= height * max_width, ow = max_width and oh = max(1, (height * max_width + width / 2) / width), otherwise oh = max_height
+ *      and ow = max(1, (width * max_height + height / 2) / height), all products in 64 bits.  POPPY_E_ARG for non-positive arguments or null pointers (the
+ *      outputs untouched), POPPY_E_UNSUPPORTED when the result would need more than a factor of 8 on an axis.
+ *   A writer's frame under size (ow, oh) and format F is F's host statement at ow x oh, applied to poppy_bgr_resize_area of the BGR frame that a plain
+ *      context hands out.  Under the sequence formats the palette is taken over the RESIZED frames.  The writer is told ow, oh and the format's stride for ow.
+ *   Limits are the format's, checked on ow x oh and the resized sequence before any state changes.
+ *   Where it applies: exactly where the frame format applies — every frame handed to a writer by poppy_hip_morph, poppy_hip_morph_frames,
+ *      poppy_hip_render_many, poppy_hip_render_phases, poppy_hip_morph_list and the calls of a pool (poppy_hip_pool_set_frame_size), the phase 0 / 1 and
+ *      t == 0 / 1 copies and the POPPY_E_NOMATCH blend frames included.  Host images among these are resized by the host statement.
+ *   Where it does not: everything that stays BGR under a format stays full size — poppy_hip_render / poppy_hip_dissolve into an explicit dst,
+ *      poppy_hip_frame_device, poppy_hip_debug_fetch, frames kept on the device (write == NULL), poppy_hip_morph_sharded, poppy_hip_morph_pairs and
+ *      include/poppy_hip_shim.hpp.  The chain is untouched: corrected1 <- frame is the full-size frame.
+ * poppy_hip_set_frame_size: (0, 0), the default, switches the size off.  It drains the context's frames, as poppy_hip_set_frame_scale does.  POPPY_E_ARG for
+ * a negative value or when exactly one of the two is 0; POPPY_E_STATE while a sequence is open or while the context's scale is above 1 (symmetrically,
+ * poppy_hip_set_frame_scale with a factor above 1 returns POPPY_E_STATE while a size is set; each is switched off to get to the other);
+ * POPPY_E_UNSUPPORTED (nothing changed) when the resident pair's geometry does not admit the size or the context's format refuses ow x oh.  It takes effect
+ * with or without a resident pair, before or after the format is set.  A pair whose geometry does not admit the set size is refused with
+ * POPPY_E_UNSUPPORTED by the call that brings it, before any state changes, as a pair that the format refuses is; a host image that is handed to a writer
+ * without a pair (the phase 0 / 1 copies) is refused by that call. */
+int poppy_hip_set_frame_size(poppy_hip_ctx* ctx, int ow, int oh);
+int poppy_frame_fit_size(int width, int height, int max_width, int max_height, int* ow, int* oh);
+int poppy_bgr_resize_area(const uint8_t* bgr, size_t stride, int width, int height, int ow, int oh, uint8_t* dst, size_t dst_stride);
+int poppy_hip_bgr_resize_area(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, int ow, int oh, uint8_t* dst, size_t dst_stride);
+/* which width of arithmetic the device takes for these sizes: 2 for 32-bit sums and 32-bit indices (width * height <= 2^24, both sides <= 32768), 1 for 32-bit
+ * sums and 64-bit indices (width * height <= 2^24, a longer side), 0 for 64-bit sums and indices (above 2^24 pixels); POPPY_E_ARG for an inadmissible size.
+ * The sizes alone decide: every alignment of the source is taken. */
+int poppy_hip_bgr_resize_area_form(int width, int height, int ow, int oh);
 /* phase == 0 / phase == 1 follow the reference's short-circuit (src/poppy.hpp:54-70): number_of_frames copies of image 1 /
  * image 2 as they were handed to the pair set-up (with auto-align: the UNALIGNED image 2), no frame is rendered.            */
 
@@ -565,6 +611,8 @@ int poppy_hip_pool_warp_counts(poppy_hip_pool* pool, unsigned long long* fused, 
 int poppy_hip_pool_set_frame_format(poppy_hip_pool* pool, int format);
 /* poppy_hip_set_frame_scale on every context of the pool; POPPY_E_ARG outside 1..POPPY_FRAME_SCALE_MAX, POPPY_E_STATE as for the format. */
 int poppy_hip_pool_set_frame_scale(poppy_hip_pool* pool, int factor);
+/* poppy_hip_set_frame_size on every context of the pool; POPPY_E_ARG as there, POPPY_E_STATE as for the format. */
+int poppy_hip_pool_set_frame_size(poppy_hip_pool* pool, int ow, int oh);
 /* poppy_hip_mask_rider of the pool's contexts (they share settings and geometry) */
 int poppy_hip_pool_mask_rider(poppy_hip_pool* pool);
 /* The CLI's loop over an image list (src/poppy.cpp:266-328) on ONE context: pair k = (image k, image k + 1), where image k of pair k > 0 is

@@ -48,6 +48,8 @@ SYMBOLS = [
     "poppy_gif_frame_bytes", "poppy_pal8_to_gif_frame", "poppy_bgr_to_gif_frame", "poppy_hip_pal8_to_gif_frame",
     "poppy_bgr_frames_to_gif_frames", "poppy_hip_bgr_frames_to_gif_frames",
     "poppy_hip_set_frame_scale", "poppy_hip_pool_set_frame_scale", "poppy_frame_scaled_size", "poppy_bgr_downscale", "poppy_hip_bgr_downscale",
+    "poppy_hip_set_frame_size", "poppy_hip_pool_set_frame_size", "poppy_frame_fit_size", "poppy_bgr_resize_area", "poppy_hip_bgr_resize_area",
+    "poppy_hip_bgr_resize_area_form",
 ]
 
 
@@ -185,6 +187,12 @@ def lib():
         L.poppy_frame_scaled_size.argtypes = [i, i, i, vp, vp]
         L.poppy_bgr_downscale.argtypes = [vp, sz, i, i, i, vp, sz]
         L.poppy_hip_bgr_downscale.argtypes = [vp, vp, sz, i, i, i, vp, sz]
+        L.poppy_hip_set_frame_size.argtypes = [vp, i, i]
+        L.poppy_hip_pool_set_frame_size.argtypes = [vp, i, i]
+        L.poppy_frame_fit_size.argtypes = [i, i, i, i, vp, vp]
+        L.poppy_bgr_resize_area.argtypes = [vp, sz, i, i, i, i, vp, sz]
+        L.poppy_hip_bgr_resize_area.argtypes = [vp, vp, sz, i, i, i, i, vp, sz]
+        L.poppy_hip_bgr_resize_area_form.argtypes = [i, i, i, i]
         L.poppy_hypotf_selfcheck.restype = C.c_long
         L.poppy_hypotf_selfcheck.argtypes = [C.c_long, C.c_uint64]
         _lib = L
@@ -336,6 +344,50 @@ def bgr_downscale(bgr, factor, row_pad=0, dst_pad=0):
         if rc:
             raise PoppyError(f"poppy_bgr_downscale: {rc}")
     return _downscale(lib().poppy_bgr_downscale, chk, bgr, factor, row_pad, dst_pad)
+
+
+def frame_fit_size(w, h, max_w, max_h):
+    """Host-only: the largest (ow, oh) inside a max_w x max_h box that keeps the aspect ratio of a w x h frame (poppy_frame_fit_size); (w, h) when the frame
+    fits.  PoppyError with the status when the result would need more than a factor of 8 on an axis."""
+    ow, oh = C.c_int(0), C.c_int(0)
+    rc = lib().poppy_frame_fit_size(int(w), int(h), int(max_w), int(max_h), C.byref(ow), C.byref(oh))
+    if rc:
+        raise PoppyError(f"poppy_frame_fit_size: {rc}")
+    return ow.value, oh.value
+
+
+def _resize_area(call, chk, bgr, ow, oh, row_pad, dst_pad):
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    ow, oh = int(ow), int(oh)
+    stride = w * 3 + int(row_pad)
+    if row_pad:
+        buf = np.full((h, stride), 0xA5, np.uint8)
+        buf[:, :w * 3] = a.reshape(h, w * 3)
+        a = buf
+    out = np.full((max(oh, 1), max(ow, 1) * 3 + int(dst_pad)), 0xA5, np.uint8)
+    chk(call(_p(a), stride, w, h, ow, oh, _p(out), ow * 3 + int(dst_pad)))
+    if dst_pad and not (out[:, ow * 3:] == 0xA5).all():
+        raise PoppyError("bgr_resize_area wrote into the padding of dst")
+    return out[:, :ow * 3].reshape(oh, ow, 3).copy()
+
+
+def bgr_resize_area(bgr, ow, oh, row_pad=0, dst_pad=0):
+    """Host-only: an HxWx3 BGR frame resampled to ow x oh by exact area weights (poppy_bgr_resize_area, the host statement of Context.set_frame_size's rule),
+    as an oh x ow x 3 array.  row_pad / dst_pad: the frame is handed over / taken back with that many extra bytes per row."""
+    def chk(rc):
+        if rc:
+            raise PoppyError(f"poppy_bgr_resize_area: {rc}")
+    return _resize_area(lib().poppy_bgr_resize_area, chk, bgr, ow, oh, row_pad, dst_pad)
+
+
+def bgr_resize_area_form(w, h, ow, oh):
+    """Host-only: the width of arithmetic the device takes for a w x h -> ow x oh resize (poppy_hip_bgr_resize_area_form): 2 for 32-bit sums and indices, 1 for
+    32-bit sums and 64-bit indices (a side above 32768), 0 for 64-bit sums (above 2^24 pixels)."""
+    rc = lib().poppy_hip_bgr_resize_area_form(int(w), int(h), int(ow), int(oh))
+    if rc < 0:
+        raise PoppyError(f"poppy_hip_bgr_resize_area_form: {rc}")
+    return rc
 
 
 def pal8_to_bgr(frame, w, h):
@@ -640,6 +692,15 @@ class Pool:
             raise PoppyError("poppy_hip_pool_create: " + err.value.decode())
         self.frame_format = FRAME_BGR
         self.frame_scale = 1
+        self.frame_size = (0, 0)
+
+    def set_frame_size(self, ow, oh):
+        """The size every frame handed to a writer is resized to, for every context of the pool (poppy_hip_pool_set_frame_size); (0, 0): none.  PoppyError with
+        the status while submitted batches have not been waited for."""
+        rc = lib().poppy_hip_pool_set_frame_size(self.h, int(ow), int(oh))
+        if rc:
+            raise PoppyError(f"poppy_hip_pool_set_frame_size: {rc}")
+        self.frame_size = (int(ow), int(oh))
 
     def set_frame_scale(self, factor):
         """The whole factor 1..8 every frame handed to a writer is scaled down by, for every context of the pool (poppy_hip_pool_set_frame_scale); PoppyError with the
@@ -797,6 +858,19 @@ class Context:
         self.w = self.h_ = 0
         self.frame_format = FRAME_BGR
         self.frame_scale = 1
+        self.frame_size = (0, 0)
+
+    def set_frame_size(self, ow, oh):
+        """The size (default (0, 0): none) every frame handed to a writer is resized to on the GPU by exact area weights, in front of the format conversion
+        (poppy_hip_set_frame_size): writers get ow x oh frames in the context's format.  An alternative to set_frame_scale: downscale only, by at most 8 per
+        axis.  Frames fetched with render(), frames kept on the device and the chain itself stay full size."""
+        self._chk(lib().poppy_hip_set_frame_size(self.h, int(ow), int(oh)), "set_frame_size")
+        self.frame_size = (int(ow), int(oh))
+
+    def bgr_resize_area(self, bgr, ow, oh, row_pad=0, dst_pad=0):
+        """An HxWx3 BGR frame resized on this context's GPU (poppy_hip_bgr_resize_area: upload, the kernel, download): the bytes of the host's bgr_resize_area.
+        The low four bits of row_pad place the device copy of the source that many bytes behind a 256-byte boundary."""
+        return _resize_area(lambda *args: lib().poppy_hip_bgr_resize_area(self.h, *args), lambda rc: self._chk(rc, "bgr_resize_area"), bgr, ow, oh, row_pad, dst_pad)
 
     def set_frame_scale(self, factor):
         """The whole factor 1..8 (default 1) every frame handed to a writer is scaled down by on the GPU, in front of the format conversion

@@ -9,7 +9,7 @@
 //   rccl_comm.cpp     the RCCL loader and a context's communicator (rccl_comm.h, comm_guard.h): the two collectives, the abort, the pair state's broadcast, export and import
 //   sharded_setup.cpp the pair set-up spread over ranks, as named stages (shard_protocol.h: roles and the keypoint hand-off; local_hub.h: the in-process transport)
 //   morph_sharded.cpp one job over N devices;  pool.cpp: pools of contexts, the set-up gate, batches of pairs
-//   frame_plan.cpp    host-side planning of a frame;  frame_pal8.cpp, frame_gif.cpp, frame_scale.cpp, frame_sink.cpp: the host side of the writer formats, the scaled hand-off and the file sinks
+//   frame_plan.cpp    host-side planning of a frame;  frame_pal8.cpp, frame_gif.cpp, frame_scale.cpp, frame_resize.cpp, frame_sink.cpp: the host side of the writer formats, the scaled and resized hand-off and the file sinks
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "foreground.h"
@@ -58,7 +58,7 @@ struct FrameSlot {
     hipEvent_t uploaded = nullptr;                  // the device copy is complete
     hipGraphExec_t body = nullptr;                  // pyrdown .. unsharp of this slot, captured once per pair geometry
     int body_format = POPPY_FRAME_BGR;              // ... with this format's conversion behind the unsharp (re-captured when that changes)
-    int body_scale = 1;                             // ... and this scale's downscale in front of it (frame_format.h: WriterGeom)
+    WriterGeom body_geom;                           // ... and this geometry's downscale or resize in front of it (frame_format.h: WriterGeom)
     SlotFormat fmt;                                 // the frame in the writer's format: buffers, side stream and event (frame_format.h)
     hipEvent_t downloaded = nullptr;                // completes when the last download of this slot's `out` towards the writer has read it
     bool dl_pending = false;                        // ... and whether such a download was issued since the slot was last rendered into
@@ -117,6 +117,7 @@ struct poppy_hip_ctx {
     bool writer_attached = false;                   // a multi-frame call with a writer is in progress
     int frame_format = POPPY_FRAME_BGR;             // of the frames handed to writers (poppy_hip_set_frame_format)
     int frame_scale = 1;                            // ... and the whole factor they are scaled down by first (poppy_hip_set_frame_scale; frame_format.h: writer_geom)
+    int frame_ow = 0, frame_oh = 0;                 // ... or the size they are resized to (poppy_hip_set_frame_size; 0, 0: none; never beside a scale above 1)
     uint8_t* scale_scratch = nullptr; size_t scale_scratch_bytes = 0;  // the scaled BGR of the copies and fallback frames that no slot renders
     uint8_t* fmt_scratch = nullptr; size_t fmt_scratch_bytes = 0;      // I420 / PAL8 of the copies and fallback frames that no slot renders (download_frame)
     uint8_t* fmt_scratch_tables = nullptr;          // ... and the PAL8 conversion's tables for them

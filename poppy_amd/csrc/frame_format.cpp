@@ -20,8 +20,26 @@ static const char* sequence_refuses(int fmt, int n, int W, int H) {
     return (unsigned long long)n * (unsigned long long)W * (unsigned long long)H >= POPPY_PAL8_SEQ_MAX_PIXELS ? kSeqSizeMsg : nullptr;
 }
 size_t writer_stride(int fmt, int W) { return format_is_coded(fmt) ? 0 : fmt == POPPY_FRAME_BGR ? (size_t)W * 3 : (size_t)W; }
-WriterGeom scaled_geom(int W, int H, int scale) { return WriterGeom{(W + scale - 1) / scale, (H + scale - 1) / scale, scale}; }
-WriterGeom writer_geom(const poppy_hip_ctx* c, bool has_writer) { return scaled_geom(c->W, c->H, has_writer ? c->frame_scale : 1); }
+constexpr const char* kSizeMsg = "the frame size set with poppy_hip_set_frame_size takes frames at least as large and at most 8 times as large per side";
+WriterGeom scaled_geom(int W, int H, int scale) { return WriterGeom{(W + scale - 1) / scale, (H + scale - 1) / scale, scale, scale > 1 ? kScaleFactor : kScaleNone}; }
+WriterGeom sized_geom(int ow, int oh) { return WriterGeom{ow, oh, 1, kScaleSize}; }
+bool size_admits(int W, int H, int ow, int oh) {
+    return ow >= 1 && oh >= 1 && ow <= W && oh <= H && (long long)W <= (long long)POPPY_FRAME_SCALE_MAX * ow && (long long)H <= (long long)POPPY_FRAME_SCALE_MAX * oh;
+}
+WriterGeom context_geom(const poppy_hip_ctx* c, int W, int H, bool has_writer) {
+    return has_writer && c->frame_ow ? sized_geom(c->frame_ow, c->frame_oh) : scaled_geom(W, H, has_writer ? c->frame_scale : 1);
+}
+WriterGeom writer_geom(const poppy_hip_ctx* c, bool has_writer) { return context_geom(c, c->W, c->H, has_writer); }
+const char* writer_refuses(const poppy_hip_ctx* c, int fmt, int W, int H) {
+    if (c->frame_ow && !size_admits(W, H, c->frame_ow, c->frame_oh)) return kSizeMsg;
+    const WriterGeom g = context_geom(c, W, H);
+    return format_refuses(fmt, g.w, g.h);
+}
+void launch_writer_scaling(const WriterGeom& g, const uint8_t* src, uint8_t* dst, int W, int H, hipStream_t s, hipEvent_t done) {
+    if (g.kind == kScaleSize) launch_bgr_resize_area(src, dst, W, H, g.w, g.h, s, done);
+    else launch_bgr_downscale(src, dst, W, H, g.scale, s, done);
+}
+const char* scaling_mark(const WriterGeom& g) { return g.kind == kScaleSize ? "frame_resize" : "frame_scale"; }
 int writer_format(const poppy_hip_ctx* c, bool has_writer) { return has_writer ? c->frame_format : POPPY_FRAME_BGR; }
 bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer) { return has_writer && format_is_sequence(c->frame_format); }
 
@@ -51,11 +69,11 @@ static int alloc_slot_side(poppy_hip_ctx* c, SlotFormat& f) {
 
 // I420: the slot's I420 buffer.  PAL8: its PAL8 buffer, tables, side stream and event.  GIF: PAL8's (the coder reads the slot's PAL8 frame) and the coded frame, the
 // coder's scratch and the pinned length word.  PAL8_SEQ and GIF_SEQ: the slots' side streams and the context's sequence tables — the store and the index ring depend on the
-// sequence's length and, under GIF_SEQ, the ring of coded frames: seq_begin, seq_finish.  All of it in the writer's geometry; with a scale above 1 the scaled BGR frame too.
+// sequence's length and, under GIF_SEQ, the ring of coded frames: seq_begin, seq_finish.  All of it in the writer's geometry; with a scale above 1 or a size the scaled BGR frame too.
 int alloc_slot_format(poppy_hip_ctx* c) {
     const WriterGeom g = writer_geom(c);
     const int fmt = c->frame_format, W = g.w, H = g.h;
-    if (const char* why = format_refuses(fmt, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    if (const char* why = writer_refuses(c, fmt, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     for (FrameSlot& slot : c->slots) {
         SlotFormat& f = slot.fmt;
         if (g.scaled() && !f.scaled) HIPCHK(c, hipMalloc((void**)&f.scaled, poppy_frame_bytes(POPPY_FRAME_BGR, W, H) + 16));
@@ -94,17 +112,17 @@ void free_context_format(poppy_hip_ctx* c) {
     c->seq = PaletteSeq();
 }
 
-bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt, int scale) {
+bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt, const WriterGeom& g) {
     const SlotFormat& f = slot.fmt;
-    if (scale > 1 && !f.scaled) return false;
+    if (g.scaled() && !f.scaled) return false;
     if (fmt == POPPY_FRAME_I420) return f.i420 != nullptr;
     if (format_is_sequence(fmt)) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
     if (format_builds_palette(fmt) && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) return false;
     return fmt != POPPY_FRAME_GIF || (f.gif && f.gif_scratch && f.gif_total);
 }
-const uint8_t* slot_bgr(const FrameSlot& f, int scale) { return scale > 1 ? f.fmt.scaled : f.out; }
-const uint8_t* slot_frame(const FrameSlot& f, int fmt, int scale) {
-    return fmt == POPPY_FRAME_I420 ? f.fmt.i420 : fmt == POPPY_FRAME_PAL8 ? f.fmt.pal8 : fmt == POPPY_FRAME_GIF ? f.fmt.gif : slot_bgr(f, scale);
+const uint8_t* slot_bgr(const FrameSlot& f, const WriterGeom& g) { return g.scaled() ? f.fmt.scaled : f.out; }
+const uint8_t* slot_frame(const FrameSlot& f, int fmt, const WriterGeom& g) {
+    return fmt == POPPY_FRAME_I420 ? f.fmt.i420 : fmt == POPPY_FRAME_PAL8 ? f.fmt.pal8 : fmt == POPPY_FRAME_GIF ? f.fmt.gif : slot_bgr(f, g);
 }
 bool slot_frame_length(const FrameSlot& f, int fmt, size_t capacity, size_t* bytes) {
     *bytes = format_is_coded(fmt) ? *(volatile uint32_t*)f.fmt.gif_total : capacity;
@@ -119,11 +137,10 @@ static void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* f
     if (tm) tm->mark("gif_pack");
 }
 
-void enqueue_conversion(int fmt, int scale, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm) {
-    if (scale > 1) {                                               // the conversion's first dispatch; what follows reads the scaled frame
-        launch_bgr_downscale(src_bgr, b.scaled, W, H, scale, s, fmt == POPPY_FRAME_BGR ? done : nullptr);
-        if (tm) tm->mark("frame_scale");
-        const WriterGeom g = scaled_geom(W, H, scale);
+void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm) {
+    if (g.scaled()) {                                              // the conversion's first dispatch; what follows reads the scaled frame
+        launch_writer_scaling(g, src_bgr, b.scaled, W, H, s, fmt == POPPY_FRAME_BGR ? done : nullptr);
+        if (tm) tm->mark(scaling_mark(g));
         src_bgr = b.scaled; W = g.w; H = g.h;
     }
     if (fmt == POPPY_FRAME_I420) {
@@ -180,7 +197,7 @@ static int scale_into_scratch(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int
         HIPCHK(c, hipMalloc((void**)&c->scale_scratch, bytes));
         c->scale_scratch_bytes = bytes;
     }
-    launch_bgr_downscale(d_bgr, c->scale_scratch, W, H, g.scale, c->stream);
+    launch_writer_scaling(g, d_bgr, c->scale_scratch, W, H, c->stream);
     HIPCHK(c, hipGetLastError());
     return POPPY_OK;
 }
@@ -193,7 +210,7 @@ int seq_add_image(poppy_hip_ctx* c, const uint8_t* d_bgr) {
     const WriterGeom g = writer_geom(c);
     if (g.scaled()) {
         int rc = scale_into_scratch(c, d_bgr, c->W, c->H, g); if (rc) return rc;
-        if (c->timing == 1) tm.mark("frame_scale");
+        if (c->timing == 1) tm.mark(scaling_mark(g));
         d_bgr = c->scale_scratch;
     }
     { int rc = seq_pass(c, d_bgr, dst, c->stream, nullptr); if (rc) return rc; }
@@ -455,7 +472,7 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
         }
         SlotFormat scratch;
         scratch.i420 = scratch.pal8 = c->fmt_scratch; scratch.pal8_tables = c->fmt_scratch_tables;
-        enqueue_conversion(gif ? POPPY_FRAME_PAL8 : fmt, 1, d_bgr, W, H, scratch, c->stream, nullptr, nullptr);
+        enqueue_conversion(gif ? POPPY_FRAME_PAL8 : fmt, WriterGeom{W, H}, d_bgr, W, H, scratch, c->stream, nullptr, nullptr);
         HIPCHK(c, hipGetLastError());
         if (gif) return gif_from_device_pal8(c, c->fmt_scratch, W, H, host);
         d_frame = c->fmt_scratch;
@@ -484,19 +501,21 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
 }
 
 int write_device_image(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, int n_copies, poppy_write_cb write, void* user) {
-    const WriterGeom g = scaled_geom(W, H, c->frame_scale);
+    if (const char* why = writer_refuses(c, c->frame_format, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    const WriterGeom g = context_geom(c, W, H);
     std::vector<uint8_t> host; size_t stride = 0;
     int rc = download_frame(c, d_bgr, W, H, g, host, &stride, n_copies); if (rc) return rc;
     for (int j = 0; j < n_copies; ++j) write(user, host.data(), g.w, g.h, stride);
     return POPPY_OK;
 }
 int write_host_image(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, int n_copies, poppy_write_cb write, void* user) {
-    const WriterGeom g = scaled_geom(W, H, c->frame_scale);
-    if (const char* why = format_refuses(c->frame_format, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    if (const char* why = writer_refuses(c, c->frame_format, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    const WriterGeom g = context_geom(c, W, H);
     std::vector<uint8_t> small, tmp; int rc = POPPY_OK;
     if (g.scaled()) {                                              // the host statement, then the format's as for any host image
         small.resize(poppy_frame_bytes(POPPY_FRAME_BGR, g.w, g.h));
-        rc = poppy_bgr_downscale(bgr, stride, W, H, g.scale, small.data(), (size_t)g.w * 3);
+        rc = g.kind == kScaleSize ? poppy_bgr_resize_area(bgr, stride, W, H, g.w, g.h, small.data(), (size_t)g.w * 3)
+                                  : poppy_bgr_downscale(bgr, stride, W, H, g.scale, small.data(), (size_t)g.w * 3);
         if (rc) return fail(c, rc, "the frame could not be scaled");
         bgr = small.data(); stride = (size_t)g.w * 3;
     }
@@ -513,30 +532,77 @@ int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
     if (!format_known(format)) return fail(c, POPPY_E_ARG, "unknown frame format");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = drain_frames(c); if (rc) return rc; }
-    if (c->c1) if (const char* why = format_refuses(format, writer_geom(c).w, writer_geom(c).h)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    if (c->c1) if (const char* why = writer_refuses(c, format, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     c->frame_format = format;
     return c->c1 ? alloc_slot_format(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
 }
 
-// A new scale resizes every buffer of the writer's geometry: the slots' are freed and allocated again, and the captured bodies, which hold their addresses, go.
-int poppy_hip_set_frame_scale(poppy_hip_ctx* c, int factor) {
-    if (!c) return POPPY_E_ARG;
-    if (factor < 1 || factor > POPPY_FRAME_SCALE_MAX) return fail(c, POPPY_E_ARG, "the frame scale is a whole factor from 1 to 8");
-    if (c->seq.open) return fail(c, POPPY_E_STATE, "a sequence is open on this context");
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc = drain_frames(c); if (rc) return rc; }
-    if (factor == c->frame_scale) return POPPY_OK;
-    if (c->c1) {
-        const WriterGeom g = scaled_geom(c->W, c->H, factor);
-        if (const char* why = format_refuses(c->frame_format, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
-    }
-    c->frame_scale = factor;
+// A new writer's geometry resizes every buffer of it: the slots' are freed and allocated again, and the captured bodies, which hold their addresses, go.
+static int writer_geometry_changed(poppy_hip_ctx* c) {
     if (!c->c1) return POPPY_OK;                                   // (a pair allocated later gets its buffers in alloc_pair)
     for (FrameSlot& f : c->slots) {
         if (f.body) { (void)hipGraphExecDestroy(f.body); f.body = nullptr; }
         free_slot_format_pair(f.fmt);
     }
     return alloc_slot_format(c);
+}
+
+int poppy_hip_set_frame_scale(poppy_hip_ctx* c, int factor) {
+    if (!c) return POPPY_E_ARG;
+    if (factor < 1 || factor > POPPY_FRAME_SCALE_MAX) return fail(c, POPPY_E_ARG, "the frame scale is a whole factor from 1 to 8");
+    if (c->seq.open) return fail(c, POPPY_E_STATE, "a sequence is open on this context");
+    if (factor > 1 && c->frame_ow) return fail(c, POPPY_E_STATE, "a frame size is set on this context: poppy_hip_set_frame_size(ctx, 0, 0) first");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = drain_frames(c); if (rc) return rc; }
+    if (factor == c->frame_scale) return POPPY_OK;
+    if (c->c1 && !c->frame_ow) {
+        const WriterGeom g = scaled_geom(c->W, c->H, factor);
+        if (const char* why = format_refuses(c->frame_format, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    }
+    c->frame_scale = factor;
+    return writer_geometry_changed(c);
+}
+
+int poppy_hip_set_frame_size(poppy_hip_ctx* c, int ow, int oh) {
+    if (!c) return POPPY_E_ARG;
+    if (ow < 0 || oh < 0 || (ow == 0) != (oh == 0)) return fail(c, POPPY_E_ARG, "the frame size is two positive numbers, or 0, 0 for none");
+    if (c->seq.open) return fail(c, POPPY_E_STATE, "a sequence is open on this context");
+    if (ow && c->frame_scale > 1) return fail(c, POPPY_E_STATE, "a frame scale is set on this context: poppy_hip_set_frame_scale(ctx, 1) first");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = drain_frames(c); if (rc) return rc; }
+    if (ow == c->frame_ow && oh == c->frame_oh) return POPPY_OK;
+    if (c->c1) {
+        if (ow && !size_admits(c->W, c->H, ow, oh)) return fail(c, POPPY_E_UNSUPPORTED, kSizeMsg);
+        const WriterGeom g = ow ? sized_geom(ow, oh) : scaled_geom(c->W, c->H, c->frame_scale);
+        if (const char* why = format_refuses(c->frame_format, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    }
+    c->frame_ow = ow; c->frame_oh = oh;
+    return writer_geometry_changed(c);
+}
+
+int poppy_hip_bgr_resize_area_form(int W, int H, int ow, int oh) {
+    if (W <= 0 || H <= 0 || !size_admits(W, H, ow, oh)) return POPPY_E_ARG;
+    return bgr_resize_area_form(W, H, ow, oh);
+}
+
+int poppy_hip_bgr_resize_area(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, int ow, int oh, uint8_t* dst, size_t dst_stride) {
+    if (!c) return POPPY_E_ARG;
+    if (!bgr || !dst || W <= 0 || H <= 0 || !size_admits(W, H, ow, oh) || stride < (size_t)W * 3 || dst_stride < (size_t)ow * 3)
+        return fail(c, POPPY_E_ARG, "bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    // everything lives for the call; the source's place behind a 256-byte boundary is the row pad's low bits (include/poppy_hip.h)
+    const size_t row = (size_t)W * 3, shift = (stride - row) % 16, out_row = (size_t)ow * 3;
+    uint8_t *d_src = nullptr, *d_dst = nullptr;
+    hipError_t e = hipMalloc((void**)&d_src, row * H + shift + 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_dst, out_row * oh + 16);
+    if (e == hipSuccess) e = copy_rows_async(d_src + shift, row, bgr, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { launch_bgr_resize_area(d_src + shift, d_dst, W, H, ow, oh, c->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = copy_rows_async(dst, dst_stride, d_dst, out_row, out_row, (size_t)oh, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go
+    if (e == hipSuccess) e = e_sync;
+    for (uint8_t* b : {d_src, d_dst}) if (b) (void)hipFree(b);
+    if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("BGR resize: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    return POPPY_OK;
 }
 
 int poppy_hip_bgr_downscale(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, int factor, uint8_t* dst, size_t dst_stride) {

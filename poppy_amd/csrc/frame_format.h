@@ -17,20 +17,31 @@ inline bool format_builds_palette(int fmt) { return fmt == POPPY_FRAME_PAL8 || f
 inline bool format_is_coded(int fmt) { return fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ; }
 // one palette for all the frames a call hands to its writer: they wait in the sequence store until the last is rendered (PaletteSeq); GIF_SEQ is PAL8_SEQ coded
 inline bool format_is_sequence(int fmt) { return fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF_SEQ; }
-// The writer's geometry: what a W x H frame is for the writer of a context whose scale is s (poppy_hip_set_frame_scale) — ow x oh, ow = (W + s - 1) / s,
-// oh = (H + s - 1) / s.  Everything the writer sees is sized by it: strides, frame bytes, the pinned ring, the conversion buffers, the formats' limits, the
-// sequence store.  Frames kept on the device (no writer) have scale 1: the pair's own geometry.
+// The writer's geometry: what a W x H frame is for the writer of a context — ow x oh.  Under a scale s (poppy_hip_set_frame_scale) ow = (W + s - 1) / s,
+// oh = (H + s - 1) / s (kScaleFactor); under a size (poppy_hip_set_frame_size) ow x oh is that size (kScaleSize); a context has at most one of the two.
+// Everything the writer sees is sized by it: strides, frame bytes, the pinned ring, the conversion buffers, the formats' limits, the sequence store.
+// Frames kept on the device (no writer) have kScaleNone: the pair's own geometry.
+enum ScaleKind { kScaleNone = 0, kScaleFactor = 1, kScaleSize = 2 };
 struct WriterGeom {
     int w = 0, h = 0, scale = 1;
-    bool scaled() const { return scale > 1; }
+    int kind = kScaleNone;
+    bool scaled() const { return kind != kScaleNone; }
+    bool operator==(const WriterGeom& o) const { return w == o.w && h == o.h && scale == o.scale && kind == o.kind; }
+    bool operator!=(const WriterGeom& o) const { return !(*this == o); }
 };
 WriterGeom scaled_geom(int W, int H, int scale);
+WriterGeom sized_geom(int ow, int oh);
+bool size_admits(int W, int H, int ow, int oh);      // the rule's admissible sizes (include/poppy_hip.h)
+WriterGeom context_geom(const poppy_hip_ctx* c, int W, int H, bool has_writer = true);      // of a W x H frame under the context's scale or size (which W x H admits: writer_refuses)
 WriterGeom writer_geom(const poppy_hip_ctx* c, bool has_writer = true);      // of the resident pair's frames
+const char* writer_refuses(const poppy_hip_ctx* c, int fmt, int W, int H);      // why a W x H frame cannot go to a writer under the context's scale or size in format `fmt`, or null: the size's admission, then format_refuses on the writer's geometry
+void launch_writer_scaling(const WriterGeom& g, const uint8_t* src, uint8_t* dst, int W, int H, hipStream_t s, hipEvent_t done = nullptr);      // W x H -> g on the device (g.scaled()): the whole-factor downscale or the area resize
+const char* scaling_mark(const WriterGeom& g);      // its name in timing mode 1: frame_scale or frame_resize
 int writer_format(const poppy_hip_ctx* c, bool has_writer);      // the format of the frames a call hands to its writer (none: they stay BGR in HBM), and whether they are collected into one palette sequence first
 bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer);
 
 struct SlotFormat {
-    uint8_t* scaled = nullptr;            // scale > 1: the frame scaled down, tight BGR, ow x oh — what the conversion reads and, under BGR, what the writer gets
+    uint8_t* scaled = nullptr;            // a scale above 1 or a size: the frame scaled down, tight BGR, ow x oh — what the conversion reads and, under BGR, what the writer gets
     uint8_t* i420 = nullptr;              // the frame as I420 for the writer (allocated when the format is I420 and a pair is there; kept until the pair's buffers go)
     uint8_t* pal8 = nullptr;              // the frame as PAL8 for the writer, and the conversion's tables (kernels.h: kPal8TableBytes) — the slot's own,
     uint8_t* pal8_tables = nullptr;       // because the conversions of frames in flight run beside each other (allocated like i420; the stream and event live as long as the context)
@@ -45,15 +56,15 @@ int alloc_slot_format(poppy_hip_ctx* c);          // every slot's buffers for th
 void free_slot_format_pair(SlotFormat& f);        // what goes with the pair's buffers
 void free_slot_format_ctx(SlotFormat& f);         // the side stream and its event: they live as long as the context
 void free_context_format(poppy_hip_ctx* c);       // the context's own: scratch of the frames that no slot renders, the sequence's tables, store and rings
-bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& f, int fmt, int scale);      // (every way to a format with a pair allocates the slots' buffers — alloc_pair, poppy_hip_set_frame_format — or refuses: a frame is never converted into nothing)
-const uint8_t* slot_frame(const FrameSlot& f, int fmt, int scale);       // the slot's frame as the writer gets it
-const uint8_t* slot_bgr(const FrameSlot& f, int scale);       // ... and as BGR in the writer's geometry: the frame itself, or the scaled frame
+bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& f, int fmt, const WriterGeom& g);      // (every way to a format with a pair allocates the slots' buffers — alloc_pair, poppy_hip_set_frame_format — or refuses: a frame is never converted into nothing)
+const uint8_t* slot_frame(const FrameSlot& f, int fmt, const WriterGeom& g);       // the slot's frame as the writer gets it
+const uint8_t* slot_bgr(const FrameSlot& f, const WriterGeom& g);       // ... and as BGR in the writer's geometry: the frame itself, or the scaled frame
 bool slot_frame_length(const FrameSlot& f, int fmt, size_t capacity, size_t* bytes);      // the bytes of that frame, once its `done` has fired: `capacity`, or a coded frame's own length from the slot's pinned word; false when that is out of bounds
 
-// src_bgr (W x H) scaled down by `scale` into b.scaled (scale > 1: the first dispatch) and in format `fmt` into b's buffers on stream s: the I420 kernel, or the PAL8
-// triple and, for GIF, the coding pair behind it.  `done` (optional) rides on the last dispatch; tm (timing mode 1) gets the marks frame_scale, frame_format, pal8_hist,
-// pal8_build, gif_lzw, gif_pack.
-void enqueue_conversion(int fmt, int scale, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm);
+// src_bgr (W x H) scaled down to g into b.scaled (g.scaled(): the first dispatch) and in format `fmt` into b's buffers on stream s: the I420 kernel, or the PAL8
+// triple and, for GIF, the coding pair behind it.  `done` (optional) rides on the last dispatch; tm (timing mode 1) gets the marks frame_scale or frame_resize,
+// frame_format, pal8_hist, pal8_build, gif_lzw, gif_pack.
+void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm);
 
 // POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ: one palette for all the frames a call hands to its writer.
 // seq_begin opens a sequence of n frames (limits, tables, store), every frame for the writer then goes through seq_pass (render_slot, seq_add_image) instead of
@@ -91,7 +102,7 @@ struct WriterRing {
     hipError_t deliver_next(poppy_hip_ctx* c, bool by_event, uint8_t** frame);      // waits for the copy of frame `written` — its buffer's stream, or with by_event the ring event recorded behind it — and counts it as handed over
 };
 
-// a device frame (tight u8x3, W x H) in the writer's geometry g = scaled_geom(W, H, the context's scale) and format in `host`, queued on c->stream and waited for;
+// a device frame (tight u8x3, W x H) in the writer's geometry g = context_geom(c, W, H) and format in `host`, queued on c->stream and waited for;
 // *stride = what the writer is told
 // n_copies: how often the writer gets this frame — under the sequence formats these copies are the whole sequence, and the frame is converted on the host
 int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const WriterGeom& g, std::vector<uint8_t>& host, size_t* stride, int n_copies = 1);

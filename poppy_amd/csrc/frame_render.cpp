@@ -9,8 +9,8 @@ static_assert(kPlanRasterRows == kRasterChunkRows, "the plan's work list and k_r
 // the format the frames being submitted are converted to for their writer (their slots' bodies end with the conversion); BGR: none
 // (PAL8_SEQ, GIF_SEQ: none either — the sequence pass is launched behind the body, its destination differs from frame to frame: render_slot)
 static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached && !format_is_sequence(c->frame_format) ? c->frame_format : POPPY_FRAME_BGR; }
-// ... and the factor they are scaled down by in front of it, under every format (the sequence formats' pass reads the scaled frame); 1: not at all
-static int frame_wants_scale(const poppy_hip_ctx* c) { return c->writer_attached ? c->frame_scale : 1; }
+// ... and the geometry they are scaled down or resized to in front of it, under every format (the sequence formats' pass reads the scaled frame)
+static WriterGeom frame_wants_geom(const poppy_hip_ctx* c) { return writer_geom(c, c->writer_attached); }
 
 // pyrdown .. unsharp of one slot.  Every argument is fixed for the life of the pair (the per-frame unsharp amount is
 // read from the slot's plan blob), which is what lets the whole sequence be captured into one graph launch.
@@ -92,11 +92,12 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     // GIF is PAL8 with the two coding dispatches behind the index plane, wherever PAL8's run; `done` rides on the second.
     // PAL8_SEQ (seq_dst: the frame's place in the sequence store, never set in a captured body): the pass takes PAL8's place, on the side stream too — it is short,
     // but the chain needs nothing of it.
-    // A scale above 1: the downscale is the conversion's first dispatch wherever that runs, and a conversion of its own under BGR (the writer gets the slot's
+    // A scale above 1 or a size: the downscale (the resize) is the conversion's first dispatch wherever that runs, and a conversion of its own under BGR (the writer gets the slot's
     // scaled frame); the chain goes on from the full-size frame.
-    const int fmt = frame_wants_format(c), scale = frame_wants_scale(c);
+    const int fmt = frame_wants_format(c);
+    const WriterGeom geom = frame_wants_geom(c);
     const bool side = (fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF || seq_dst) && chained && done && !tm;
-    const bool converts = fmt != POPPY_FRAME_BGR || seq_dst || scale > 1;
+    const bool converts = fmt != POPPY_FRAME_BGR || seq_dst || geom.scaled();
     launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s,
                    side ? f.fmt.bgr_done : converts ? nullptr : done, c->levels[0].pitch);
     rec(POPPY_PYR_UNSHARP, 0, W < 2 || H < 2);
@@ -104,9 +105,9 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     if (!converts) return POPPY_OK;
     hipStream_t fs = side ? f.fmt.fmt_stream : s;
     if (side) HIPCHK(c, hipStreamWaitEvent(fs, f.fmt.bgr_done, 0));
-    if (!seq_dst) { enqueue_conversion(fmt, scale, f.out, W, H, f.fmt, fs, done, tm); return POPPY_OK; }
-    if (scale > 1) enqueue_conversion(POPPY_FRAME_BGR, scale, f.out, W, H, f.fmt, fs, nullptr, tm);
-    { int rc = seq_pass(c, slot_bgr(f, scale), seq_dst, fs, done); if (rc) return rc; }
+    if (!seq_dst) { enqueue_conversion(fmt, geom, f.out, W, H, f.fmt, fs, done, tm); return POPPY_OK; }
+    if (geom.scaled()) enqueue_conversion(POPPY_FRAME_BGR, geom, f.out, W, H, f.fmt, fs, nullptr, tm);
+    { int rc = seq_pass(c, slot_bgr(f, geom), seq_dst, fs, done); if (rc) return rc; }
     if (tm) tm->mark("pal8_seq_hist");
     return POPPY_OK;
 }
@@ -115,7 +116,7 @@ static int capture_body(poppy_hip_ctx* c, FrameSlot& f) {
     hipGraph_t g = nullptr;
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     (void)enqueue_body(c, f, c->stream, nullptr, 0.f, false);
-    f.body_format = frame_wants_format(c); f.body_scale = frame_wants_scale(c);
+    f.body_format = frame_wants_format(c); f.body_geom = frame_wants_geom(c);
     HIPCHK(c, hipStreamEndCapture(c->stream, &g));
     hipError_t e = hipGraphInstantiate(&f.body, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
@@ -235,7 +236,7 @@ static int prepare_slot(poppy_hip_ctx* c, const FramePlan& plan, double mask, bo
     // bottleneck.  On the chained critical path a graph launch leaves the GPU idle ~8 us longer than the same kernels
     // launched one by one (4600 vs 4785 frames/s, profiles/r01_e_streams.md), and the host keeps up easily.
     const bool use_graph = !no_graph && !chained && !c->debug && !all_marks && W > 1 && H > 1;
-    if (use_graph && f.body && (f.body_format != frame_wants_format(c) || f.body_scale != frame_wants_scale(c))) {      // the body has (not) the downscale and conversion the frame needs: captured again
+    if (use_graph && f.body && (f.body_format != frame_wants_format(c) || f.body_geom != frame_wants_geom(c))) {      // the body has (not) the downscale and conversion the frame needs: captured again
         HIPCHK(c, hipEventSynchronize(f.done));                                // (the slot's last frame may still run it)
         (void)hipGraphExecDestroy(f.body); f.body = nullptr;
     }
@@ -339,7 +340,7 @@ static int render_slot(poppy_hip_ctx* c, int fi, bool chain) {
     // PAL8_SEQ: the frame's pass — behind the captured body on the same stream (the body stays BGR: the store address differs per frame), or as the body's last launch
     uint8_t* seq_dst = nullptr;
     if (seq_wanted(c) && !(seq_dst = seq_next_place(c))) return fail(c, POPPY_E_STATE, "more frames than the sequence was opened for");
-    if (use_graph) { HIPCHK(c, hipGraphLaunch(f.body, s)); if (seq_dst) { int rc = seq_pass(c, slot_bgr(f, frame_wants_scale(c)), seq_dst, s, nullptr); if (rc) return rc; } }
+    if (use_graph) { HIPCHK(c, hipGraphLaunch(f.body, s)); if (seq_dst) { int rc = seq_pass(c, slot_bgr(f, frame_wants_geom(c)), seq_dst, s, nullptr); if (rc) return rc; } }
     else { int rc = enqueue_body(c, f, s, all_marks ? &tm : nullptr, (float)(1.0 - amount), c->debug, done_rides ? f.done : nullptr, chained, seq_dst); if (rc) return rc; }
     HIPCHK(c, hipGetLastError());
     if (!done_rides) HIPCHK(c, hipEventRecord(f.done, s));

@@ -139,7 +139,7 @@ struct FramePump {
         if (dl_streams) {
             hipStream_t ds = nullptr;
             if (e == hipSuccess) e = ring.stream(c, k, &ds);
-            if (e == hipSuccess) e = hipMemcpyAsync(ring.buffer(k), slot_frame(f, fmt, geom.scale), copy_bytes, hipMemcpyDeviceToHost, ds);
+            if (e == hipSuccess) e = hipMemcpyAsync(ring.buffer(k), slot_frame(f, fmt, geom), copy_bytes, hipMemcpyDeviceToHost, ds);
             f.dl_pending = true; f.dl_ring_idx = r;
             if (e != hipSuccess) { c->err = std::string("frame download: ") + hipGetErrorString(e); rc = POPPY_E_DEVICE; return false; }
             return true;
@@ -149,7 +149,7 @@ struct FramePump {
         static const bool skip_copy = getenv("POPPY_DL_SKIP_COPY") != nullptr;      // timing experiment: every wait and event of the writer path, no bytes moved (wrong frames)
         if (!skip_copy)
 #endif
-        if (e == hipSuccess) e = hipMemcpyAsync(ring.buffer(k), slot_frame(f, fmt, geom.scale), copy_bytes, hipMemcpyDeviceToHost, c->dl_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ring.buffer(k), slot_frame(f, fmt, geom), copy_bytes, hipMemcpyDeviceToHost, c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(c->dl_done[r], c->dl_stream);
         if (e == hipSuccess) e = hipEventRecord(f.downloaded, c->dl_stream);          // the slot's own: ring events are re-recorded every R frames
         f.dl_pending = true;
@@ -201,7 +201,7 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
     const int fmt = writer_format(c, write != nullptr);
     const WriterGeom geom = writer_geom(c, write != nullptr);
     for (const FrameSlot& f : c->slots)
-        if (!slot_format_ready(c, f, fmt, geom.scale)) return fail(c, POPPY_E_STATE, "the frame format's buffers are not allocated for this pair");
+        if (!slot_format_ready(c, f, fmt, geom)) return fail(c, POPPY_E_STATE, "the frame format's buffers are not allocated for this pair");
     FramePump dlp{c, write, user, fmt, geom, writer_stride(fmt, geom.w), poppy_frame_bytes(fmt, geom.w, geom.h), dev_wait, dl_streams};
     dlp.slot_of.assign(n, -1);
     const bool dl = write && !seq;                                // frames are downloaded and handed over as they finish

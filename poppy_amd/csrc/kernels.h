@@ -210,6 +210,13 @@ void launch_bgr_to_i420(const uint8_t* src, uint8_t* dst, int w, int h, hipStrea
 void launch_bgr_downscale(const uint8_t* src, uint8_t* dst, int w, int h, int s, hipStream_t stream, hipEvent_t done = nullptr);
 bool bgr_downscale_wide(const uint8_t* src, const uint8_t* dst, int w, int h, int s);
 
+// tight u8x3 BGR, w x h -> the frame resampled to ow x oh by exact area weights, tight (kernels_frame_resize.hip; the rule and the admissible sizes:
+// include/poppy_hip.h, poppy_hip_set_frame_size — the caller has checked them).  `done` (optional) rides on the last dispatch.  bgr_resize_area_form: the width
+// of arithmetic the launcher takes for these arguments, decided by them alone — 2: 32-bit sums and indices (w * h <= 2^24, w and h <= 32768), 1: 32-bit sums and
+// 64-bit indices (w * h <= 2^24), 0: 64-bit sums and indices.  Any alignment is taken.
+void launch_bgr_resize_area(const uint8_t* src, uint8_t* dst, int w, int h, int ow, int oh, hipStream_t stream, hipEvent_t done = nullptr);
+int bgr_resize_area_form(int w, int h, int ow, int oh);
+
 // tight u8x3 BGR -> PAL8 (kernels_frame_pal8.hip; the format: include/poppy_hip.h, POPPY_FRAME_PAL8), three dispatches on one stream: the cells' histogram,
 // the palette build (one workgroup; writes the palette behind dst's index plane), the index plane.  `tables`: kPal8TableBytes of device memory that is all
 // zero before the first frame (the build leaves the histogram zero again) and that no other frame uses meanwhile: two 64-bit words per cell, then the

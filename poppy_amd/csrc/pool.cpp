@@ -321,6 +321,16 @@ int poppy_hip_pool_set_frame_scale(poppy_hip_pool* p, int factor) {
     return POPPY_OK;
 }
 
+int poppy_hip_pool_set_frame_size(poppy_hip_pool* p, int ow, int oh) {
+    if (!p || ow < 0 || oh < 0 || (ow == 0) != (oh == 0)) return POPPY_E_ARG;
+    {
+        std::lock_guard<std::mutex> lk(p->q_mu);
+        if (p->unwaited || p->outstanding) return POPPY_E_STATE;                 // the feeders' contexts may be rendering
+    }
+    for (poppy_hip_ctx* c : p->ctx) { const int rc = poppy_hip_set_frame_size(c, ow, oh); if (rc) return rc; }
+    return POPPY_OK;
+}
+
 int poppy_hip_pool_mask_rider(poppy_hip_pool* p) {
     if (!p || p->ctx.empty()) return POPPY_E_ARG;
     return poppy_hip_mask_rider(p->ctx[0]);

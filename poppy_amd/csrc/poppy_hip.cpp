@@ -220,7 +220,8 @@ static int ensure_ring(poppy_hip_ctx* c, int n_points) {
 int alloc_pair(poppy_hip_ctx* c, int W, int H) {
     { int rc = drain_frames(c); if (rc) return rc; }              // every pair loader comes through here: no frame still reads the old pair
     // PAL8 takes frames of at most 2^24 pixels (in the writer's geometry): refused before anything is allocated or any state changes, so the context keeps the pair it had
-    { const WriterGeom g = scaled_geom(W, H, c->frame_scale); if (const char* why = format_refuses(c->frame_format, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why); }
+    // ... and a pair whose geometry does not admit the size set with poppy_hip_set_frame_size likewise
+    if (const char* why = writer_refuses(c, c->frame_format, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     if (c->W == W && c->H == H && c->c1) return alloc_slot_format(c);      // (allocates only what is missing: nothing, unless an earlier attempt failed half-way)
     free_pair(c);
     c->pyr_forms.clear();

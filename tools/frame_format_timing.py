@@ -6,16 +6,19 @@ times each row once per format, one format right after the other, and the rows r
   pool_4k       the same at 3840 x 2160 (--steps-4k batches)
   job480        ONE 480-frame 1080p phase-mode job on one context: pair set-up from device images + poppy_hip_render_phases to the counting writer
   chained       one context, pair after pair: pair set-up + 60 chained frames to the counting writer
+  chained_4k    the same at 3840 x 2160 on a context of its own (not among the default --rows)
   chained_frame one context, the 60 chained frames of a resident pair to the counting writer (what the extra launch costs a chained frame)
   d2h_ceiling   pinned device-to-host copies of one frame's bytes, back to back on one stream (BGR, I420 and PAL8 sizes at 1080p and 4K)
 and, at the end, the conversion kernels' own times in timing mode 1 at 1080p and 4K (I420: frame_format; PAL8: pal8_hist, pal8_build, frame_format = the index plane;
 PAL8_SEQ: pal8_seq_hist per frame, pal8_seq_build per sequence, frame_format = the index plane; GIF: PAL8's three, then gif_lzw and gif_pack).  Under PAL8_SEQ a pair's (a call's) frames are handed over after its last
 frame.
 
-    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif --scales 1,2 --kernel-scales 2,4]
+    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif --scales 1,2 --kernel-scales 2,4
+                                         --size 1280x720 --size-4k 1920x1080]
 --formats leaves formats out (a library older than GIF: bgr,i420,pal8,pal8_seq).  --scales adds every format again per scale above 1 (poppy_hip_set_frame_scale: the
 column "gif@2" is GIF at scale 2), alternated with the others in the same process; --kernel-scales adds k_bgr_downscale's own time (timing mode 1: frame_scale) under BGR
-at 1080p and 4K for those factors.  GIF's d2h_ceiling entry is its CAPACITY (poppy_frame_bytes); a frame's copy moves its own
+at 1080p and 4K for those factors.  --size OWxOH adds every format again at that size (poppy_hip_set_frame_size: the column "i420@1280x720"); the 4K rows of such a
+column use --size-4k (default: --size), and its timing mode 1 entry has the resize kernel's time (frame_resize).  GIF's d2h_ceiling entry is its CAPACITY (poppy_frame_bytes); a frame's copy moves its own
 length, which depends on the content.  One JSON line at the end.
 """
 import argparse
@@ -80,17 +83,34 @@ def main():
     ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq,gif")
     ap.add_argument("--scales", default="1")
     ap.add_argument("--kernel-scales", default="")
+    ap.add_argument("--size", default="")
+    ap.add_argument("--size-4k", default="")
     a = ap.parse_args()
     rows = a.rows.split(",")
     scales = [int(x) for x in a.scales.split(",")]
     # a column is a format at a scale; scale 1 keeps the format's plain name and never calls the scale setter
-    FMTS = tuple((f if sc == 1 else f"{f}@{sc}", (v, sc)) for f, v in ALL_FMTS if f in a.formats.split(",") for sc in scales)
+    # ... and a size column is a format at (the size of the 1080p rows, the size of the 4K rows): a tuple where the others have their scale
+    size = tuple(int(x) for x in a.size.split("x")) if a.size else None
+    size4k = tuple(int(x) for x in a.size_4k.split("x")) if a.size_4k else size
+    FMTS = tuple((f if sc == 1 else f"{f}@{sc}" if isinstance(sc, int) else f"{f}@{a.size}", (v, sc)) for f, v in ALL_FMTS if f in a.formats.split(",")
+                 for sc in scales + ([(size, size4k)] if size else []))
 
-    def set_column(target, col):
+    def set_scaling(target, sc, four_k=False):
+        sized = not isinstance(sc, int)
+        if size and not sized:
+            target.set_frame_size(0, 0)                            # size and scale are alternatives: the one off before the other goes on
+        if scales != [1] or sized:
+            target.set_frame_scale(1 if sized else sc)
+        if sized:
+            target.set_frame_size(*sc[1 if four_k else 0])
+
+    def set_column(target, col, four_k=False):
         fmt, sc = col
         target.set_frame_format(fmt)
-        if scales != [1]:
-            target.set_frame_scale(sc)
+        set_scaling(target, sc, four_k)
+
+    def writer_size(w, h, sc):
+        return (-(-w // sc), -(-h // sc)) if isinstance(sc, int) else sc[1 if w > W else 0]
     import torch
     dev = torch.device("cuda", 0)
     res = {r: {f: [] for f, _ in FMTS} for r in rows if r != "d2h_ceiling"}
@@ -98,8 +118,9 @@ def main():
     p1080 = pair_images(torch, dev, W, H, 6)
     ptrs = [(x.data_ptr(), y.data_ptr()) for x, y in p1080]
     pool = capi.Pool([0], contexts_per_device=a.contexts, number_of_frames=60) if "pool_1080p" in rows else None
-    p4k = pair_images(torch, dev, 3840, 2160, 6) if "pool_4k" in rows else None
-    pool4 = capi.Pool([0], contexts_per_device=a.contexts, number_of_frames=60) if p4k else None
+    p4k = pair_images(torch, dev, 3840, 2160, 6) if "pool_4k" in rows or "chained_4k" in rows else None
+    pool4 = capi.Pool([0], contexts_per_device=a.contexts, number_of_frames=60) if "pool_4k" in rows else None
+    ctx4 = capi.Context(0, number_of_frames=60) if "chained_4k" in rows else None
     ctx = capi.Context(0, number_of_frames=60)
     ta, tb = p1080[0]
     ph480 = np.arange(480) / 480.0
@@ -110,7 +131,7 @@ def main():
                 set_column(pool, fmt)
                 res["pool_1080p"][name].append(pool_row(pool, ptrs, W, H, a.steps, torch))
             if pool4:
-                set_column(pool4, fmt)
+                set_column(pool4, fmt, four_k=True)
                 res["pool_4k"][name].append(pool_row(pool4, [(x.data_ptr(), y.data_ptr()) for x, y in p4k], 3840, 2160, a.steps_4k, torch))
             set_column(ctx, fmt)
             if "job480" in rows:
@@ -128,6 +149,14 @@ def main():
                     n += ctx.morph_frames_counted(-1.0)
                 ctx.sync()
                 res["chained"][name].append(n / (time.perf_counter() - t0))
+            if ctx4:
+                set_column(ctx4, fmt, four_k=True)
+                t0 = time.perf_counter(); n = 0
+                for x, y in p4k[:3]:
+                    ctx4.pair_begin_device(x.data_ptr(), y.data_ptr(), 3840, 2160)
+                    n += ctx4.morph_frames_counted(-1.0)
+                ctx4.sync()
+                res["chained_4k"][name].append(n / (time.perf_counter() - t0))
             if "chained_frame" in rows:
                 ctx.pair_begin_device(ta.data_ptr(), tb.data_ptr(), W, H)
                 ctx.reset(); ctx.render_many_counted(shapes, chain=True); ctx.sync()
@@ -142,22 +171,26 @@ def main():
         for f in (f for f, _ in FMTS if f != "bgr" and "bgr" in fv):
             out["rows"][r][f + "_over_bgr_median"] = round(statistics.median(fv[f]) / statistics.median(fv["bgr"]), 3)
     if "d2h_ceiling" in rows:
-        out["d2h_ceiling"] = {f"{w}x{h}_{f}": d2h(torch, dev, capi.frame_bytes(fmt, -(-w // sc), -(-h // sc))) for w, h in ((1920, 1080), (3840, 2160)) for f, (fmt, sc) in FMTS}
+        out["d2h_ceiling"] = {f"{w}x{h}_{f}": d2h(torch, dev, capi.frame_bytes(fmt, *writer_size(w, h, sc))) for w, h in ((1920, 1080), (3840, 2160)) for f, (fmt, sc) in FMTS}
     # the conversion kernels in timing mode 1 (events around every kernel of a chained frame): time per launch
     out["timing_mode1_us"] = {}
-    for (w, h), (x, y) in (((W, H), (ta, tb)),) + ((((3840, 2160), p4k[0]),) if p4k else ()):
+    for (w, h), (x, y) in (((W, H), (ta, tb)),) + ((((3840, 2160), p4k[0]),) if p4k else ()):      # (the 1080p context takes the 4K pair here)
         kernel_cols = tuple((f"bgr@{k}", (capi.FRAME_BGR, int(k))) for k in a.kernel_scales.split(",") if k)
         for name, fmt in tuple(c for c in FMTS if c[1] != (capi.FRAME_BGR, 1)) + kernel_cols:
             ctx.set_frame_format(fmt[0])
+            if size:
+                ctx.set_frame_size(0, 0)                           # (the pair first: the size of the other geometry's rows may not be admissible for it)
             if fmt[1] != 1 or scales != [1]:
-                ctx.set_frame_scale(fmt[1])
+                ctx.set_frame_scale(fmt[1] if isinstance(fmt[1], int) else 1)
             ctx.pair_begin_device(x.data_ptr(), y.data_ptr(), w, h)
+            if not isinstance(fmt[1], int):
+                ctx.set_frame_size(*fmt[1][1 if w > W else 0])
             ctx.set_timing(1)
             ctx.reset(); ctx.render_many_counted(shapes, chain=True)
             t = {n: (ms, k) for n, ms, k in ctx.timing_summary()}
             ctx.set_timing(0)
-            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_scale", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build", "gif_lzw", "gif_pack")}
-    for p in (pool, pool4):
+            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_scale", "frame_resize", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build", "gif_lzw", "gif_pack")}
+    for p in (pool, pool4, ctx4):
         if p:
             p.close()
     ctx.close()
