@@ -321,29 +321,40 @@ def frame_scaled_size(w, h, factor):
     return ow.value, oh.value
 
 
-def _downscale(call, chk, bgr, factor, row_pad, dst_pad):
+def _scaled_frame(call, what, bgr, size, args, row_pad, dst_pad, chk=None):
+    """An HxWx3 BGR frame through one of the four scaling calls, `what` by name: size(w, h) is the result's (ow, oh), args what the call takes between the source's
+    size and dst.  chk(rc): the context's check; without one a status raises as poppy_<what>'s."""
     a = np.ascontiguousarray(bgr, np.uint8)
     h, w = a.shape[:2]
-    ow, oh = frame_scaled_size(w, h, factor)
+    ow, oh = size(w, h)
     stride = w * 3 + int(row_pad)
     if row_pad:
         buf = np.full((h, stride), 0xA5, np.uint8)
         buf[:, :w * 3] = a.reshape(h, w * 3)
         a = buf
-    out = np.full((oh, ow * 3 + int(dst_pad)), 0xA5, np.uint8)
-    chk(call(_p(a), stride, w, h, int(factor), _p(out), ow * 3 + int(dst_pad)))
+    out = np.full((max(oh, 1), max(ow, 1) * 3 + int(dst_pad)), 0xA5, np.uint8)
+    rc = call(_p(a), stride, w, h, *args, _p(out), ow * 3 + int(dst_pad))
+    if chk:
+        chk(rc, what)
+    elif rc:
+        raise PoppyError(f"poppy_{what}: {rc}")
     if dst_pad and not (out[:, ow * 3:] == 0xA5).all():
-        raise PoppyError("bgr_downscale wrote into the padding of dst")
+        raise PoppyError(f"{what} wrote into the padding of dst")
     return out[:, :ow * 3].reshape(oh, ow, 3).copy()
+
+
+def _downscale(call, bgr, factor, row_pad, dst_pad, chk=None):
+    return _scaled_frame(call, "bgr_downscale", bgr, lambda w, h: frame_scaled_size(w, h, factor), (int(factor),), row_pad, dst_pad, chk)
+
+
+def _resize_area(call, bgr, ow, oh, row_pad, dst_pad, chk=None):
+    return _scaled_frame(call, "bgr_resize_area", bgr, lambda w, h: (int(ow), int(oh)), (int(ow), int(oh)), row_pad, dst_pad, chk)
 
 
 def bgr_downscale(bgr, factor, row_pad=0, dst_pad=0):
     """Host-only: an HxWx3 BGR frame scaled down by the whole factor 1..8 (poppy_bgr_downscale, the host statement of Context.set_frame_scale's rule), as an
     oh x ow x 3 array.  row_pad / dst_pad: the frame is handed over / taken back with that many extra bytes per row."""
-    def chk(rc):
-        if rc:
-            raise PoppyError(f"poppy_bgr_downscale: {rc}")
-    return _downscale(lib().poppy_bgr_downscale, chk, bgr, factor, row_pad, dst_pad)
+    return _downscale(lib().poppy_bgr_downscale, bgr, factor, row_pad, dst_pad)
 
 
 def frame_fit_size(w, h, max_w, max_h):
@@ -356,29 +367,10 @@ def frame_fit_size(w, h, max_w, max_h):
     return ow.value, oh.value
 
 
-def _resize_area(call, chk, bgr, ow, oh, row_pad, dst_pad):
-    a = np.ascontiguousarray(bgr, np.uint8)
-    h, w = a.shape[:2]
-    ow, oh = int(ow), int(oh)
-    stride = w * 3 + int(row_pad)
-    if row_pad:
-        buf = np.full((h, stride), 0xA5, np.uint8)
-        buf[:, :w * 3] = a.reshape(h, w * 3)
-        a = buf
-    out = np.full((max(oh, 1), max(ow, 1) * 3 + int(dst_pad)), 0xA5, np.uint8)
-    chk(call(_p(a), stride, w, h, ow, oh, _p(out), ow * 3 + int(dst_pad)))
-    if dst_pad and not (out[:, ow * 3:] == 0xA5).all():
-        raise PoppyError("bgr_resize_area wrote into the padding of dst")
-    return out[:, :ow * 3].reshape(oh, ow, 3).copy()
-
-
 def bgr_resize_area(bgr, ow, oh, row_pad=0, dst_pad=0):
     """Host-only: an HxWx3 BGR frame resampled to ow x oh by exact area weights (poppy_bgr_resize_area, the host statement of Context.set_frame_size's rule),
     as an oh x ow x 3 array.  row_pad / dst_pad: the frame is handed over / taken back with that many extra bytes per row."""
-    def chk(rc):
-        if rc:
-            raise PoppyError(f"poppy_bgr_resize_area: {rc}")
-    return _resize_area(lib().poppy_bgr_resize_area, chk, bgr, ow, oh, row_pad, dst_pad)
+    return _resize_area(lib().poppy_bgr_resize_area, bgr, ow, oh, row_pad, dst_pad)
 
 
 def bgr_resize_area_form(w, h, ow, oh):
@@ -870,7 +862,7 @@ class Context:
     def bgr_resize_area(self, bgr, ow, oh, row_pad=0, dst_pad=0):
         """An HxWx3 BGR frame resized on this context's GPU (poppy_hip_bgr_resize_area: upload, the kernel, download): the bytes of the host's bgr_resize_area.
         The low four bits of row_pad place the device copy of the source that many bytes behind a 256-byte boundary."""
-        return _resize_area(lambda *args: lib().poppy_hip_bgr_resize_area(self.h, *args), lambda rc: self._chk(rc, "bgr_resize_area"), bgr, ow, oh, row_pad, dst_pad)
+        return _resize_area(lambda *args: lib().poppy_hip_bgr_resize_area(self.h, *args), bgr, ow, oh, row_pad, dst_pad, self._chk)
 
     def set_frame_scale(self, factor):
         """The whole factor 1..8 (default 1) every frame handed to a writer is scaled down by on the GPU, in front of the format conversion
@@ -882,7 +874,7 @@ class Context:
     def bgr_downscale(self, bgr, factor, row_pad=0, dst_pad=0):
         """An HxWx3 BGR frame scaled down on this context's GPU (poppy_hip_bgr_downscale: upload, the kernel, download): the bytes of the host's bgr_downscale.
         The low four bits of row_pad place the device copy of the source that many bytes behind a 256-byte boundary."""
-        return _downscale(lambda *args: lib().poppy_hip_bgr_downscale(self.h, *args), lambda rc: self._chk(rc, "bgr_downscale"), bgr, factor, row_pad, dst_pad)
+        return _downscale(lambda *args: lib().poppy_hip_bgr_downscale(self.h, *args), bgr, factor, row_pad, dst_pad, self._chk)
 
     def set_frame_format(self, fmt):
         """FRAME_BGR (default), FRAME_I420, FRAME_PAL8 or FRAME_PAL8_SEQ (one palette for all frames of a call, which are handed over when the last

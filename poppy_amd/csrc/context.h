@@ -2,7 +2,9 @@
 //   poppy_hip.cpp     context life cycle, HBM layout, plan blob allocation (plan_blob.h), the pair loaders and the C entry points of the resident-pair API
 //   frame_render.cpp  one frame (frame_render.h): the frame body and the two halves of a frame, prepare_slot and render_slot
 //   frame_sequence.cpp  the multi-frame driver (frame_sequence.h): the planner team's SeqPlans, render_frame, render_sequence and its download pump
-//   frame_format.cpp  everything that depends on the writer's frame format (frame_format.h): slot buffers, conversion launches, the palette sequence, the writer ring
+//   frame_format.cpp  the writer's formats and geometry (frame_format.h; frame_limits.h: the bounds shared with the host statements): their facts, slot buffers, conversion launches, the setters
+//   palette_seq.cpp   the PAL8_SEQ / GIF_SEQ sequence (palette_seq.h): store, palette, the two hand-over loops;  writer_ring.cpp: the pinned ring towards the writer (writer_ring.h)
+//   writer_image.cpp  the frames that no slot renders and the stand-alone conversion entry points (writer_image.h);  writer_buffers.h: the grow-only device buffer and the call-scoped holder
 //   pair_begin.cpp    the pair set-up from raw images (pair_begin.h): its schedule and stages, the chain threads (setup_latch.h), the pair_begin entry points
 //   pair_setup.cpp    the stage-by-stage entry points of the once-per-pair half: pre-ORB chain, ORB, matching, auto-align, tables, margins
 //   image_list.cpp    poppy_hip_morph_list
@@ -14,6 +16,9 @@
 #include "../../include/poppy_hip.h"
 #include "foreground.h"
 #include "frame_format.h"
+#include "palette_seq.h"
+#include "writer_image.h"
+#include "writer_ring.h"
 #include "frame_plan.h"
 #include "frame_render.h"
 #include "frame_sequence.h"
@@ -118,10 +123,10 @@ struct poppy_hip_ctx {
     int frame_format = POPPY_FRAME_BGR;             // of the frames handed to writers (poppy_hip_set_frame_format)
     int frame_scale = 1;                            // ... and the whole factor they are scaled down by first (poppy_hip_set_frame_scale; frame_format.h: writer_geom)
     int frame_ow = 0, frame_oh = 0;                 // ... or the size they are resized to (poppy_hip_set_frame_size; 0, 0: none; never beside a scale above 1)
-    uint8_t* scale_scratch = nullptr; size_t scale_scratch_bytes = 0;  // the scaled BGR of the copies and fallback frames that no slot renders
-    uint8_t* fmt_scratch = nullptr; size_t fmt_scratch_bytes = 0;      // I420 / PAL8 of the copies and fallback frames that no slot renders (download_frame)
+    DeviceBuffer scale_scratch;                     // the scaled BGR of the copies and fallback frames that no slot renders (writer_image.h: scale_into_scratch)
+    DeviceBuffer fmt_scratch;                       // I420 / PAL8 of the copies and fallback frames that no slot renders (download_frame)
     uint8_t* fmt_scratch_tables = nullptr;          // ... and the PAL8 conversion's tables for them
-    PaletteSeq seq;                                 // POPPY_FRAME_PAL8_SEQ: the sequence being collected (frame_format.h: seq_begin .. seq_finish)
+    PaletteSeq seq;                                 // POPPY_FRAME_PAL8_SEQ: the sequence being collected (palette_seq.h: seq_begin .. seq_finish)
     double wait_ms[4] = {0, 0, 0, 0};               // host waits inside submit_frame since the context was made (POPPY_SEQ_TIMING prints the per-sequence share)
     ForegroundFilter foreground, foreground_b;      // two instances: the images of a pair are filtered side by side
     // The two chain slots (slot 0 = foreground + orb, slot 1 = foreground_b + orb_b; chain_fg / chain_orb below).  After a set-up from raw images the slot

@@ -1,9 +1,10 @@
-// frame_format.h — what depends on the format a writer gets its frames in (poppy_hip_set_frame_format): the formats' facts, a slot's conversion buffers,
-// the conversion launches, the POPPY_FRAME_PAL8_SEQ / POPPY_FRAME_GIF_SEQ sequence, the pinned ring towards the writer and the frames that no slot renders.  frame_format.cpp.
+// frame_format.h — what depends on the format a writer gets its frames in (poppy_hip_set_frame_format) and on the writer's geometry (poppy_hip_set_frame_scale,
+// poppy_hip_set_frame_size): the formats' facts, WriterGeom, a slot's conversion buffers and the conversion launches.  frame_format.cpp.  The palette sequence is
+// palette_seq.h's, the pinned ring towards the writer writer_ring.h's, the frames that no slot renders writer_image.h's.
 #pragma once
 #include "../../include/poppy_hip.h"
 #include <hip/hip_runtime.h>
-#include <vector>
+#include "frame_limits.h"
 
 struct poppy_hip_ctx; struct FrameSlot; struct Timer;
 
@@ -31,7 +32,6 @@ struct WriterGeom {
 };
 WriterGeom scaled_geom(int W, int H, int scale);
 WriterGeom sized_geom(int ow, int oh);
-bool size_admits(int W, int H, int ow, int oh);      // the rule's admissible sizes (include/poppy_hip.h)
 WriterGeom context_geom(const poppy_hip_ctx* c, int W, int H, bool has_writer = true);      // of a W x H frame under the context's scale or size (which W x H admits: writer_refuses)
 WriterGeom writer_geom(const poppy_hip_ctx* c, bool has_writer = true);      // of the resident pair's frames
 const char* writer_refuses(const poppy_hip_ctx* c, int fmt, int W, int H);      // why a W x H frame cannot go to a writer under the context's scale or size in format `fmt`, or null: the size's admission, then format_refuses on the writer's geometry
@@ -39,6 +39,7 @@ void launch_writer_scaling(const WriterGeom& g, const uint8_t* src, uint8_t* dst
 const char* scaling_mark(const WriterGeom& g);      // its name in timing mode 1: frame_scale or frame_resize
 int writer_format(const poppy_hip_ctx* c, bool has_writer);      // the format of the frames a call hands to its writer (none: they stay BGR in HBM), and whether they are collected into one palette sequence first
 bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer);
+const char* sequence_refuses(int fmt, int n, int W, int H);      // ... and why a sequence of n such frames is refused, or null
 
 struct SlotFormat {
     uint8_t* scaled = nullptr;            // a scale above 1 or a size: the frame scaled down, tight BGR, ow x oh — what the conversion reads and, under BGR, what the writer gets
@@ -65,48 +66,7 @@ bool slot_frame_length(const FrameSlot& f, int fmt, size_t capacity, size_t* byt
 // triple and, for GIF, the coding pair behind it.  `done` (optional) rides on the last dispatch; tm (timing mode 1) gets the marks frame_scale or frame_resize,
 // frame_format, pal8_hist, pal8_build, gif_lzw, gif_pack.
 void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm);
-
-// POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ: one palette for all the frames a call hands to its writer.
-// seq_begin opens a sequence of n frames (limits, tables, store), every frame for the writer then goes through seq_pass (render_slot, seq_add_image) instead of
-// a download, and seq_finish builds the palette and hands every frame to the writer; seq_abort ends a sequence of which a frame failed, nothing written.
-// The sequence's tables (kernels.h: kPal8SeqTableBytes; zero between sequences), the frames held back until the palette is known (`stride` bytes apart, kept between
-// sequences, grown when needed), and a ring of index planes on their way to the writer.  GIF_SEQ: a ring of coded frames instead (`gif`: per ring buffer the frame's
-// capacity, then the coder's scratch, `gif_each` bytes apart) and a word of mapped pinned memory per ring buffer that k_gif_pack stores the frame's length into.
-struct PaletteSeq {
-    uint8_t* tables = nullptr;
-    uint8_t* store = nullptr; size_t store_bytes = 0, stride = 0;
-    uint8_t* idx = nullptr; size_t idx_bytes = 0;
-    uint8_t* gif = nullptr; size_t gif_bytes = 0;
-    uint32_t* gif_total = nullptr; uint8_t* gif_total_dev = nullptr;      // kStageRing words, 64 bytes apart
-    bool open = false;                    // a sequence is being collected: frames for the writer go through the pass into the store
-    int n = 0, count = 0;                 // its frames, and how many of them have been queued
-};
-int seq_begin(poppy_hip_ctx* c, int n);
-bool seq_wanted(const poppy_hip_ctx* c);          // frames submitted now go into the open sequence
-uint8_t* seq_next_place(poppy_hip_ctx* c);        // the next frame's place in the store; null: the sequence is full
-int seq_pass(poppy_hip_ctx* c, const uint8_t* d_bgr, uint8_t* dst, hipStream_t s, hipEvent_t done);      // the pass of one frame (in the writer's geometry): into the sequence's sums and on to `dst` in the store, one kernel
-int seq_add_image(poppy_hip_ctx* c, const uint8_t* d_bgr);      // a full-size frame that no slot renders (the t == 0 / 1 copies of poppy_hip_render_phases), on the context's stream
-int seq_abort(poppy_hip_ctx* c);
-void seq_abort_keep_error(poppy_hip_ctx* c);      // ... behind a failure whose message the caller gets
-int seq_finish(poppy_hip_ctx* c, poppy_write_cb write, void* user);      // the open sequence is complete: palette, then every frame to the writer.  Whatever fails in there, the sequence is closed and the tables are zero afterwards.
-
-// R pinned buffers, frame k in buffer k mod R: the copy of frame `issued` is the next to be queued, frame `written` the next the writer gets.
-struct WriterRing {
-    int R = 1;
-    size_t slot_bytes = 0;                // ring slots start on 256-byte boundaries
-    int issued = 0, written = 0;
-    uint8_t* base = nullptr;
-    int open(poppy_hip_ctx* c, size_t frame_bytes, bool cap_by_slots);      // POPPY_HIP_RING buffers (default 3; at most kStageRing and, where the frames come from the slots, the slot count) of frame_bytes in the context's pinned stage
-    uint8_t* buffer(int k) const { return base + (size_t)(k % R) * slot_bytes; }
-    hipError_t stream(poppy_hip_ctx* c, int k, hipStream_t* s) const;      // the stream of frame k's buffer, which carries nothing but that buffer's copies (created at first use)
-    hipError_t deliver_next(poppy_hip_ctx* c, bool by_event, uint8_t** frame);      // waits for the copy of frame `written` — its buffer's stream, or with by_event the ring event recorded behind it — and counts it as handed over
-};
-
-// a device frame (tight u8x3, W x H) in the writer's geometry g = context_geom(c, W, H) and format in `host`, queued on c->stream and waited for;
-// *stride = what the writer is told
-// n_copies: how often the writer gets this frame — under the sequence formats these copies are the whole sequence, and the frame is converted on the host
-int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const WriterGeom& g, std::vector<uint8_t>& host, size_t* stride, int n_copies = 1);
-const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status, int n_copies = 1);      // a host frame (already in the writer's geometry) in the writer's format: `bgr` itself (BGR) or its I420 / PAL8 / coded form in `tmp`; nullptr, *status and c->err set, when the format refuses the frame
-int write_device_image(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, int n_copies, poppy_write_cb write, void* user);      // a device image / a host image to the writer, n_copies times, in the writer's format (the phase 0 / 1 and t = 0 / 1 copies, the linear-blend fallback frames)
-int write_host_image(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, int n_copies, poppy_write_cb write, void* user);
-int pal8_seq_of_copies(const uint8_t* bgr, size_t stride, int n_copies, int width, int height, uint8_t* dst);      // frame_pal8.cpp: the POPPY_FRAME_PAL8_SEQ frame of a sequence that is n_copies times the same BGR frame (poppy_bgr_frames_to_pal8 with frame_stride 0, one frame out)
+// the GIF half: the PAL8 frame coded into `frame`, its length also into the pinned word behind total_dev (null: none); `done` rides on the second dispatch
+void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm);
+// conversion tables, zero before the first frame (the palette builds leave them zero again): PAL8's per slot and for the scratch, the sequence's per context
+int alloc_zeroed_tables(poppy_hip_ctx* c, uint8_t** tables, size_t bytes);

@@ -1,0 +1,17 @@
+// frame_limits.h — the bounds of a writer's frame that the host statements (frame_resize.cpp, frame_sink.cpp) and the device path (frame_format.cpp, palette_seq.cpp,
+// writer_image.cpp) both check, each stated once.  Host only, nothing of HIP.
+#pragma once
+#include "../../include/poppy_hip.h"
+
+// poppy_hip_set_frame_size's rule (include/poppy_hip.h): ow x oh is no larger than W x H and at most POPPY_FRAME_SCALE_MAX times smaller per side (so W, H >= 1 too)
+inline bool size_admits(int W, int H, int ow, int oh) {
+    return ow >= 1 && oh >= 1 && ow <= W && oh <= H && (long long)W <= (long long)POPPY_FRAME_SCALE_MAX * ow && (long long)H <= (long long)POPPY_FRAME_SCALE_MAX * oh;
+}
+// A coded frame (POPPY_FRAME_GIF, POPPY_FRAME_GIF_SEQ) of w x h pixels.  Its capacity (include/poppy_hip.h has the derivation): `total` and the palette, the
+// minimum-code-size byte, every segment's payload at its bound in sub-blocks of 255 bytes behind a length byte each, the terminator ...
+inline size_t gif_frame_capacity(size_t w, size_t h) {
+    const size_t segments = (w * h + POPPY_GIF_SEGMENT_PIXELS - 1) / POPPY_GIF_SEGMENT_PIXELS, payload = segments * POPPY_GIF_SEGMENT_BYTES;
+    return 772 + 1 + payload + (payload + 254) / 255 + 1;
+}
+constexpr size_t kGifFrameMinBytes = 776;      // ... and the smallest there is, the same with one byte of payload in one sub-block: 772 + 1 + (1 + 1) + 1
+inline bool coded_length_ok(size_t total, size_t capacity) { return total >= kGifFrameMinBytes && total <= capacity; }      // a coder's `total`, before that many bytes are copied or read

@@ -1,12 +1,7 @@
 // frame_resize.cpp — the host side of the resized hand-off (include/poppy_hip.h: poppy_hip_set_frame_size): the size that fits a box and poppy_bgr_resize_area,
 // the library's definition of a frame resampled to a smaller size by exact area weights (kernels_frame_resize.hip computes the same bytes on the device).
-#include "../../include/poppy_hip.h"
+#include "frame_limits.h"
 #include <algorithm>
-
-static bool size_admissible(int width, int height, int ow, int oh) {
-    return width > 0 && height > 0 && ow >= 1 && oh >= 1 && ow <= width && oh <= height &&
-           (long long)width <= (long long)POPPY_FRAME_SCALE_MAX * ow && (long long)height <= (long long)POPPY_FRAME_SCALE_MAX * oh;
-}
 
 extern "C" {
 
@@ -20,7 +15,7 @@ int poppy_frame_fit_size(int width, int height, int max_width, int max_height, i
             fh = max_height; fw = std::max(1LL, ((long long)width * max_height + height / 2) / height);
         }
     }
-    if (!size_admissible(width, height, (int)fw, (int)fh)) return POPPY_E_UNSUPPORTED;
+    if (!size_admits(width, height, (int)fw, (int)fh)) return POPPY_E_UNSUPPORTED;
     *ow = (int)fw; *oh = (int)fh;
     return POPPY_OK;
 }
@@ -28,7 +23,7 @@ int poppy_frame_fit_size(int width, int height, int max_width, int max_height, i
 // output pixel (x, y): per channel (sum of wy(y, r) wx(x, i) src(i, r) + width height / 2) / (width height); wx(x, i) = the overlap of [x width, (x + 1) width)
 // and [i ow, (i + 1) ow), wy likewise with height and oh
 int poppy_bgr_resize_area(const uint8_t* bgr, size_t stride, int width, int height, int ow, int oh, uint8_t* dst, size_t dst_stride) {
-    if (!bgr || !dst || !size_admissible(width, height, ow, oh)) return POPPY_E_ARG;
+    if (!bgr || !dst || !size_admits(width, height, ow, oh)) return POPPY_E_ARG;
     if (stride < (size_t)width * 3 || dst_stride < (size_t)ow * 3) return POPPY_E_ARG;
     const long long W = width, H = height, area = W * H;
     for (long long y = 0; y < oh; ++y) {

@@ -11,7 +11,7 @@
 //   POPPY_SINK_GIF_CODED   POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames, whose image data arrives coded (frame_gif.cpp, kernels_frame_gif.hip): nothing is coded here
 //   POPPY_SINK_GIF_GLOBAL_CODED  POPPY_SINK_GIF_GLOBAL's file from coded frames (POPPY_FRAME_GIF_SEQ): the first frame's palette as the global table, local tables only where a palette differs
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
-#include "../../include/poppy_hip.h"
+#include "frame_limits.h"
 #include "gif_lzw.h"
 #include <algorithm>
 #include <cstdint>
@@ -96,6 +96,8 @@ bool sink_has_global_table(int format) { return format == POPPY_SINK_GIF_GLOBAL 
 bool gif_coded_frame(poppy_sink* s, const uint8_t* frame) {
     const int w = s->w, h = s->h;
     const size_t total = poppy_gif_frame_bytes(frame);
+    // (772 + 3 is not coded_length_ok's bound, the smallest frame a coder gives, but one byte less: what keeps the two reads here, frame[772] and frame[total - 1],
+    // apart and inside the frame.  The sink has always taken such a frame from a caller; it goes on doing so.)
     if (total < 772 + 3 || total > poppy_frame_bytes(POPPY_FRAME_GIF, w, h) || frame[772] != 8 || frame[total - 1] != 0) return false;
     bool local = true;
     if (sink_has_global_table(s->format)) {
@@ -118,10 +120,7 @@ size_t poppy_frame_bytes(int format, int width, int height) {
     if (format == POPPY_FRAME_BGR) return w * h * 3;
     if (format == POPPY_FRAME_I420) return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2);
     if (format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ) return w * h + 768;
-    if (format == POPPY_FRAME_GIF || format == POPPY_FRAME_GIF_SEQ) {      // the capacity (include/poppy_hip.h has the derivation): every segment at its bound, framed
-        const size_t segments = (w * h + POPPY_GIF_SEGMENT_PIXELS - 1) / POPPY_GIF_SEGMENT_PIXELS, payload = segments * POPPY_GIF_SEGMENT_BYTES;
-        return 772 + 1 + payload + (payload + 254) / 255 + 1;
-    }
+    if (format == POPPY_FRAME_GIF || format == POPPY_FRAME_GIF_SEQ) return gif_frame_capacity(w, h);      // (frame_limits.h, beside the smallest coded frame)
     return 0;
 }
 
