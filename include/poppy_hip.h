@@ -424,6 +424,19 @@ int poppy_hip_foreground(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, 
  * the same bytes.                                                                                                                     */
 int poppy_hip_median_blur(poppy_hip_ctx* ctx, const uint8_t* src, int width, int height, int ksize, int form, uint8_t* dst);
 
+/* The last stage of every frame on its own: unsharp_mask(src, 1, amount, 0.3) + convertTo(CV_8U, 255) (src/util.cpp:113-148,
+ * src/algo.cpp:263-265) on a host float image of width x height BGR pixels, `pitch` pixels per row (>= width; the padding pixels are
+ * uploaded with the rows and must not influence the result).  dst: tight 8-bit BGR; dst_f32_or_null: the float image before the 8-bit
+ * conversion, tight (what the debug fetch "unsharp" returns for a frame).  The launcher, the threshold and the bound of the decision are
+ * the frame path's own.  form selects the kernel (diagnostics, tests): 0 = what a frame of this geometry takes (the POPPY_UNSHARP_STREAM /
+ * POPPY_UNSHARP_TILE switches apply), 1 = the tile kernel (k_unsharp_tile; POPPY_E_UNSUPPORTED under 2 pixels wide or high), 2 = the
+ * streaming kernel (k_unsharp_stream; POPPY_E_UNSUPPORTED under 64 x 16), 3 = the three separable kernels frames under 2 pixels wide or
+ * high take (any geometry).  amount_on_device: 0 = the amount is the kernel's argument, 1 = the kernel reads it from a 4-byte device
+ * buffer as the frames of a captured body do (the separable kernels have no such form and take the argument).  All forms return the same
+ * bits.  Bad arguments: POPPY_E_ARG, nothing written.                                                                                  */
+int poppy_hip_unsharp_frame(poppy_hip_ctx* ctx, const float* src, int width, int height, int pitch, float amount, int form,
+                            int amount_on_device, uint8_t* dst, float* dst_f32_or_null);
+
 /* Pair set-up from the two ORB input images g1/g2 (what Extractor::keypoints feeds the detector,
  * src/extractor.cpp:50-78) and gabor2 (src/poppy.hpp:119-122): ORB x2 -> truncate to the shorter list
  * (extractor.cpp:96-99) -> poppy_match_points -> resident pair.  nfeatures = int(max_keypoints * detail).  */

@@ -50,6 +50,7 @@ SYMBOLS = [
     "poppy_hip_set_frame_scale", "poppy_hip_pool_set_frame_scale", "poppy_frame_scaled_size", "poppy_bgr_downscale", "poppy_hip_bgr_downscale",
     "poppy_hip_set_frame_size", "poppy_hip_pool_set_frame_size", "poppy_frame_fit_size", "poppy_bgr_resize_area", "poppy_hip_bgr_resize_area",
     "poppy_hip_bgr_resize_area_form",
+    "poppy_hip_unsharp_frame",
 ]
 
 
@@ -109,6 +110,7 @@ def lib():
         L.poppy_hip_orb_detect.argtypes = [vp, vp, sz, i, i, i, vp, i, vp]
         L.poppy_hip_foreground.argtypes = [vp, vp, sz, i, i, vp, vp]
         L.poppy_hip_median_blur.argtypes = [vp, vp, i, i, i, i, vp]
+        L.poppy_hip_unsharp_frame.argtypes = [vp, vp, i, i, i, C.c_float, i, i, vp, vp]
         L.poppy_hip_comm_info.argtypes = [vp, vp, vp, vp, vp]
         L.poppy_hip_pair_begin.argtypes = [vp, vp, sz, vp, sz, i, i]
         L.poppy_hip_pair_begin_info.argtypes = [vp, vp, vp]
@@ -966,6 +968,28 @@ class Context:
         out = np.zeros((h, w), np.uint8)
         self._chk(lib().poppy_hip_median_blur(self.h, _p(a), w, h, int(ksize), int(form), _p(out)), "median_blur")
         return out
+
+    def unsharp_frame(self, src, amount, form=0, pitch=None, amount_on_device=False, want_float=False):
+        """The frame path's last stage on a float image (h, w, 3): unsharp_mask(src, 1, amount, 0.3) + convertTo(CV_8U, 255) -> u8 (h, w, 3), with
+        want_float=True (u8, the float image before the conversion).  form: 0 what a frame of this geometry takes, 1 tile kernel, 2 streaming kernel,
+        3 separable kernels (include/poppy_hip.h).  pitch: pixels per row of the array `src` is cut from — `src` is then the `[:, :w]` view of a
+        C-contiguous (h, pitch, 3) array, whose padding pixels go to the device with the rows.  amount_on_device: the kernel reads the amount from
+        device memory, as a captured frame body's does."""
+        v = np.asarray(src)
+        if v.dtype != np.float32 or v.ndim != 3 or v.shape[2] != 3:
+            raise ValueError("unsharp_frame takes a float32 (h, w, 3) image")
+        h, w = v.shape[:2]
+        if pitch is None:
+            a = np.ascontiguousarray(v); pitch = w
+        else:                                   # `src` is the first w columns of a C-contiguous (h, pitch, 3) array: handed over with its padding
+            if pitch < w or v.strides != (pitch * 12, 12, 4):
+                raise ValueError("with a pitch, src must be the [:, :w] view of a C-contiguous (h, pitch, 3) array")
+            a = v
+        out = np.zeros((h, w, 3), np.uint8)
+        outf = np.zeros((h, w, 3), np.float32) if want_float else None
+        self._chk(lib().poppy_hip_unsharp_frame(self.h, a.ctypes.data, w, h, int(pitch), float(amount), int(form), int(bool(amount_on_device)),
+                                                _p(out), _p(outf) if want_float else None), "unsharp_frame")
+        return (out, outf) if want_float else out
 
     def foreground(self, bgr, debug=False):
         """Extractor::foreground for one BGR image -> goodFeatures (u8); with debug=True a dict with every intermediate."""

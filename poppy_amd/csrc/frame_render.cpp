@@ -375,3 +375,42 @@ int prepare_ahead(poppy_hip_ctx* c, const FramePlan& plan, double mask) {
     if (rc == POPPY_OK) c->slot_preps[fi].seq = c->frame_seq + 1;
     return rc;
 }
+
+// The frame body's last stage on a caller's float image (include/poppy_hip.h): the same launcher, threshold and bound as enqueue_body's call, the kernel named by
+// `form`.  Buffers of the call's own: no pair needs to be resident and none is disturbed beyond the kept chain state.
+int poppy_hip_unsharp_frame(poppy_hip_ctx* c, const float* src, int W, int H, int pitch, float amount, int form, int amount_on_device,
+                            uint8_t* dst, float* dst_f32_or_null) {
+    if (!c) return POPPY_E_ARG;
+    if (!src || !dst || W <= 0 || H <= 0 || pitch < W || form < kUnsharpAuto || form > kUnsharpSeparable || (amount_on_device != 0 && amount_on_device != 1))
+        return fail(c, POPPY_E_ARG, "bad unsharp_frame arguments");
+    if (form == kUnsharpStream && !unsharp_stream_takes(W, H)) return fail(c, POPPY_E_UNSUPPORTED, "the streaming unsharp kernel takes frames from 64 x 16 pixels up");
+    if (form == kUnsharpTile && (W < 2 || H < 2)) return fail(c, POPPY_E_UNSUPPORTED, "the tile unsharp kernel takes frames from 2 x 2 pixels up");
+    HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
+    const size_t n_src = (size_t)pitch * H * 3, n_out = (size_t)W * H * 3;
+    const bool separable = form == kUnsharpSeparable || W < 2 || H < 2;
+    float *d_src = nullptr, *d_tmp = nullptr, *d_diff = nullptr, *d_outF = nullptr, *d_amount = nullptr;
+    uint8_t* d_out = nullptr;
+    hipError_t e = hipMalloc((void**)&d_src, n_src * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, n_out);
+    if (e == hipSuccess && separable) e = hipMalloc((void**)&d_tmp, n_out * 4);
+    if (e == hipSuccess && separable) e = hipMalloc((void**)&d_diff, n_out * 4);
+    if (e == hipSuccess && dst_f32_or_null) e = hipMalloc((void**)&d_outF, n_out * 4);
+    if (e == hipSuccess && amount_on_device) e = hipMalloc((void**)&d_amount, 4);
+    // the source goes up with its pitch: the padding pixels are on the device, where a kernel that read them would show it
+    if (e == hipSuccess) e = hipMemcpyAsync(d_src, src, n_src * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && d_amount) e = hipMemcpyAsync(d_amount, &amount, 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        // amount_on_device: as in a captured body, the argument is 0 and the value is the buffer's (the separable kernels take the argument: kernels.h)
+        launch_unsharp(d_src, d_tmp, d_diff, d_out, d_outF, W, H, d_amount && !separable ? 0.f : amount, d_amount, (float)0.3, c->stream, nullptr, pitch, form);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, d_out, n_out, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && d_outF) e = hipMemcpyAsync(dst_f32_or_null, d_outF, n_out * 4, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // also on failure: `amount` and the host images are read until the copies have run
+    if (e == hipSuccess) e = es;
+    void* bufs[] = {d_src, d_out, d_tmp, d_diff, d_outF, d_amount};
+    for (void* b : bufs) if (b) (void)hipFree(b);
+    if (e != hipSuccess) { c->err = std::string("unsharp_frame: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    return POPPY_OK;
+}

@@ -187,8 +187,16 @@ void launch_pyr_tail(const float* pyrL, const float* pyrR, const float* pyrM, fl
 // `done` (optional): an event that completes with the launch's last kernel; for the tile kernel it rides on the dispatch
 // itself instead of being a packet of its own behind it.
 // src_pitch: pixels per row of src (0 = w; the outputs are tight).
+// form: which of the three forms runs.  kUnsharpAuto is the frame path's: the separable kernels for frames under 2 pixels wide or high, else the streaming
+// kernel where unsharp_stream_eligible, else the tile kernel.  The others (poppy_hip_unsharp_frame: diagnostics, tests) name one; a frame under 2 pixels wide or
+// high runs the separable kernels whatever is named (they alone take it), kUnsharpStream is the caller's to refuse where !unsharp_stream_takes.  The separable
+// kernels have no pointer form of the amount (no captured body holds them): they take the argument.
+enum { kUnsharpAuto = 0, kUnsharpTile = 1, kUnsharpStream = 2, kUnsharpSeparable = 3 };
 void launch_unsharp(const float* src, float* tmpRow, float* diff, uint8_t* out_u8, float* out_f32_or_null,
-                    int w, int h, float amount, const float* d_amount, float threshold, hipStream_t s, hipEvent_t done = nullptr, int src_pitch = 0);
+                    int w, int h, float amount, const float* d_amount, float threshold, hipStream_t s, hipEvent_t done = nullptr, int src_pitch = 0,
+                    int form = kUnsharpAuto);
+// the bound the tile and streaming kernels compare the double sum of squares with: the smallest double whose square root reaches the threshold
+double unsharp_norm2_min(float threshold);
 
 // The streaming form (kernels_unsharp_stream.hip: a wave per 60-pixel column strip, rows kept in registers); launch_unsharp uses it
 // for frames of 4 Mpx and more among the geometries it takes (w >= 64, h >= 16; any width and source pitch since round 6) unless POPPY_UNSHARP_TILE is set;

@@ -789,21 +789,27 @@ int stagger_flag(int bit) {
     return (POPPY_STAGGER >> bit) & 1;
 }
 
+// norm(d) >= threshold with norm = correctly rounded sqrt of a double: equivalent to |d|^2 >= x*, where x* is the
+// smallest double whose square root rounds to >= threshold (found here with the host's IEEE sqrt).
+double unsharp_norm2_min(float threshold) {
+    const double t = (double)threshold;
+    double x = t <= 0 ? 0.0 : t * t;
+    if (t > 0) {
+        while (x > 0 && std::sqrt(std::nextafter(x, 0.0)) >= t) x = std::nextafter(x, 0.0);
+        while (std::sqrt(x) < t) x = std::nextafter(x, INFINITY);
+    }
+    return x;
+}
+
 void launch_unsharp(const float* src, float* tmpRow, float* diff, uint8_t* out_u8, float* out_f32_or_null,
-                    int w, int h, float amount, const float* d_amount, float threshold, hipStream_t s, hipEvent_t done, int src_pitch) {
+                    int w, int h, float amount, const float* d_amount, float threshold, hipStream_t s, hipEvent_t done, int src_pitch, int form) {
     if (src_pitch <= 0) src_pitch = w;
-    if (w > 1 && h > 1) {
-        // norm(d) >= threshold with norm = correctly rounded sqrt of a double: equivalent to |d|^2 >= x*, where x* is the
-        // smallest double whose square root rounds to >= threshold (found here with the host's IEEE sqrt).
-        const double t = (double)threshold;
-        double x = t <= 0 ? 0.0 : t * t;
-        if (t > 0) {
-            while (x > 0 && std::sqrt(std::nextafter(x, 0.0)) >= t) x = std::nextafter(x, 0.0);
-            while (std::sqrt(x) < t) x = std::nextafter(x, INFINITY);
-        }
+    if (w > 1 && h > 1 && form != kUnsharpSeparable) {
+        const double x = unsharp_norm2_min(threshold);
         static const bool tile_only = getenv("POPPY_UNSHARP_TILE") != nullptr;
         static const int unsharp_dbg = poppy_experiment_env_i("POPPY_UNSHARP_SKIP");
-        if (!tile_only && unsharp_stream_eligible(w, h)) { launch_unsharp_stream(src, out_u8, out_f32_or_null, w, h, amount, d_amount, x, s, done, src_pitch); return; }
+        const bool stream = form == kUnsharpAuto ? !tile_only && unsharp_stream_eligible(w, h) : form == kUnsharpStream;
+        if (stream) { launch_unsharp_stream(src, out_u8, out_f32_or_null, w, h, amount, d_amount, x, s, done, src_pitch); return; }
         dim3 grid(((w + kUTx - 1) / kUTx) * ((h + kUTy - 1) / kUTy));
         hipExtLaunchKernelGGL(k_unsharp_tile, grid, dim3(256), 0, s, nullptr, done, 0, src, out_u8, out_f32_or_null, w, h, amount, d_amount, x, src_pitch, stagger_flag(1), unsharp_dbg);
         return;
