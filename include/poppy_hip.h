@@ -379,6 +379,13 @@ int poppy_ratio_symmetry(const int* knn12, int n1, const int* knn21, int n2, flo
  *               replaced by their aligned versions; *distance = morph distance afterwards.
  * align_step  : one Transformer step on the same arguments — 0 retranslate, 1 reprocrustes, 2 rerotate
  *               (src/transformer.cpp:99-217,260-269); *distance = the value the step returns.
+ * align_scores: (diagnostics, tests) what the searches of those steps rank their candidates by — morph_distance(points1, set k)
+ *               in a width x height image for n_candidates versions of the second point list (sets: n_candidates x n_points
+ *               float pairs), scored in one launch.  distances receives the value per candidate; totals, n_pairs and
+ *               inner_sums the scoring kernel's three outputs behind it: the float sum of the greedy pairs' distances, the
+ *               number of pairs (a set point at exactly (-1, -1) is the reference's "claimed" marker and pairs with nothing)
+ *               and the raw float sum of the set's offsets from points1.  Each output may be NULL.
+ * The three take 4 .. 4096 point pairs (POPPY_E_ARG otherwise).
  * procrustes / perspective_from4 (host only): Procrustes(true,false)::procrustes (src/procrustes.cpp:52-114; rotation 2x2,
  *               scale_error[2], yprime n x 2) and cv::getPerspectiveTransform of four point pairs (3x3 doubles).
  * poppy_hip_pair_begin runs auto_align itself when settings.enable_auto_align is set.                              */
@@ -388,6 +395,8 @@ int poppy_hip_auto_align(poppy_hip_ctx* ctx, uint8_t* image2, size_t stride, int
                          const float* points1, float* points2, int n_points, double* distance);
 int poppy_hip_align_step(poppy_hip_ctx* ctx, int which, uint8_t* image2, size_t stride, int width, int height,
                          const float* points1, float* points2, int n_points, double* distance);
+int poppy_hip_align_scores(poppy_hip_ctx* ctx, const float* points1, const float* sets, int n_points, int n_candidates, int width, int height,
+                           double* distances, float* totals, int* n_pairs, float* inner_sums);
 int poppy_procrustes(const float* x, const float* y, int n_points, float* rotation4, float* scale_error2, float* yprime);
 int poppy_perspective_from4(const float* src4, const float* dst4, double* m3x3);
 

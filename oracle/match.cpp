@@ -243,10 +243,24 @@ double contour_area(const std::vector<Pt>& c) {
 
 void convex_hull_points(const std::vector<Pt>& pts, std::vector<Pt>& hull) { convex_hull(pts, hull); }
 
-double morph_distance(const std::vector<Pt>& p1, const std::vector<Pt>& p2, int w, int h) {
-    const long double width = w, height = h;
+// The O(N^2) parts of morph_distance: the float sum of the greedy pairs' distances in map order, the number of pairs, and the
+// raw float sum of the second set's offsets before it is normalised.
+void morph_distance_parts(const std::vector<Pt>& p1, const std::vector<Pt>& p2, float* total_out, size_t* n_pairs, float* inner2_sum) {
     std::vector<DistPair> dm;
     make_distance_map(p1, p2, dm);
+    float inner2 = 0;
+    for (size_t i = 0; i < p2.size(); ++i)
+        for (size_t j = 0; j < p2.size(); ++j) { float vx = p2[i].x - p1[j].x, vy = p2[i].y - p1[j].y; inner2 += vx + vy; }   // sic: srcPoints1[j]
+    float total = 0;
+    for (const DistPair& e : dm) total += hypotf(e.b.x - e.a.x, e.b.y - e.a.y);    // float += float
+    *total_out = total; *n_pairs = dm.size(); *inner2_sum = inner2;
+}
+
+double morph_distance(const std::vector<Pt>& p1, const std::vector<Pt>& p2, int w, int h) {
+    const long double width = w, height = h;
+    float total, inner2;
+    size_t n_pairs;
+    morph_distance_parts(p1, p2, &total, &n_pairs, &inner2);
     std::vector<Pt> hull1, hull2, c1, c2;
     convex_hull(p1, hull1); convex_hull(p2, hull2);
     approx_poly_closed(hull1, 0.001, c1); approx_poly_closed(hull2, 0.001, c2);
@@ -256,14 +270,9 @@ double morph_distance(const std::vector<Pt>& p1, const std::vector<Pt>& p2, int 
     for (size_t i = 0; i < p1.size(); ++i)
         for (size_t j = 0; j < p1.size(); ++j) { float vx = p1[i].x - p1[j].x, vy = p1[i].y - p1[j].y; inner1 += vx + vy; }
     inner1 = (float)((inner1 / (p1.size() * p1.size())) / (width + height));
-    float inner2 = 0;
-    for (size_t i = 0; i < p2.size(); ++i)
-        for (size_t j = 0; j < p2.size(); ++j) { float vx = p2[i].x - p1[j].x, vy = p2[i].y - p1[j].y; inner2 += vx + vy; }   // sic: srcPoints1[j]
     inner2 = (float)((inner2 / (p2.size() * p2.size())) / (width + height));
 
-    float total = 0;
-    for (const DistPair& e : dm) total += hypotf(e.b.x - e.a.x, e.b.y - e.a.y);    // float += float
-    long double ret = ((total / (dm.size())) / hypotl(width, height)) + fabs(inner1 - inner2)
+    long double ret = ((total / (n_pairs)) / hypotl(width, height)) + fabs(inner1 - inner2)
                       + (fabs(area1 - area2) / (width * height)) / 3.0;
     return (double)ret;
 }

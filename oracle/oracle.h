@@ -111,6 +111,8 @@ struct DistPair { double d; Pt a, b; };
 void make_distance_map(const std::vector<Pt>& p1, const std::vector<Pt>& p2, std::vector<DistPair>& out);   // ascending, stable
 void filter_invalid_points(std::vector<Pt>& p1, std::vector<Pt>& p2, int cols, int rows);
 double morph_distance(const std::vector<Pt>& p1, const std::vector<Pt>& p2, int w, int h);
+// its O(N^2) parts: float sum of the pairs' distances, number of pairs, raw float offset sum of p2 against p1
+void morph_distance_parts(const std::vector<Pt>& p1, const std::vector<Pt>& p2, float* total, size_t* n_pairs, float* inner2_sum);
 void match_prepare(std::vector<Pt>& s1, std::vector<Pt>& s2, int w, int h, double tolerance, double initialMorphDist);
 
 // ---- align.cpp: auto-align (src/matcher.cpp:133-244, src/transformer.cpp, src/procrustes.cpp) -------------------

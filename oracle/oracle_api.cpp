@@ -144,6 +144,9 @@ int orc_filter_invalid(float* p1, float* p2, int n, int cols, int rows) {
     put((Pt*)p1, a); put((Pt*)p2, b); return (int)a.size();
 }
 double orc_morph_distance(const float* p1, const float* p2, int n, int w, int h) { return morph_distance(wrap_pts(p1, n), wrap_pts(p2, n), w, h); }
+void orc_morph_distance_parts(const float* p1, const float* p2, int n, float* total, int* n_pairs, float* inner2_sum) {
+    size_t np = 0; morph_distance_parts(wrap_pts(p1, n), wrap_pts(p2, n), total, &np, inner2_sum); *n_pairs = (int)np;
+}
 int orc_match_prepare(const float* p1, const float* p2, int n, int w, int h, double tol, double imd, float* o1, float* o2) {
     auto a = wrap_pts(p1, n), b = wrap_pts(p2, n); match_prepare(a, b, w, h, tol, imd); put((Pt*)o1, a); put((Pt*)o2, b); return (int)a.size();
 }

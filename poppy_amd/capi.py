@@ -50,7 +50,7 @@ SYMBOLS = [
     "poppy_hip_set_frame_scale", "poppy_hip_pool_set_frame_scale", "poppy_frame_scaled_size", "poppy_bgr_downscale", "poppy_hip_bgr_downscale",
     "poppy_hip_set_frame_size", "poppy_hip_pool_set_frame_size", "poppy_frame_fit_size", "poppy_bgr_resize_area", "poppy_hip_bgr_resize_area",
     "poppy_hip_bgr_resize_area_form",
-    "poppy_hip_unsharp_frame",
+    "poppy_hip_unsharp_frame", "poppy_hip_align_scores",
 ]
 
 
@@ -100,6 +100,7 @@ def lib():
         L.poppy_hip_warp_affine.argtypes = [vp, vp, C.c_size_t, i, i, vp, vp, C.c_size_t]
         L.poppy_hip_auto_align.argtypes = [vp, vp, C.c_size_t, i, i, vp, vp, i, vp]
         L.poppy_hip_align_step.argtypes = [vp, i, vp, C.c_size_t, i, i, vp, vp, i, vp]
+        L.poppy_hip_align_scores.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp, vp]
         L.poppy_procrustes.argtypes = [vp, vp, i, vp, vp, vp]
         L.poppy_hip_pair_corrected2.argtypes = [vp, vp, C.c_size_t]
         L.poppy_perspective_from4.argtypes = [vp, vp, vp]
@@ -1239,6 +1240,16 @@ class Context:
             code = {"retranslate": 0, "reprocrustes": 1, "rerotate": 2}[which]
             self._chk(lib().poppy_hip_align_step(self.h, code, _p(im), w * 3, w, h, _p(a), _p(b), len(a), C.byref(d)), "align_step")
         return im, b, d.value
+
+    def align_scores(self, p1, sets, w, h):
+        """What the align searches rank by, for candidate versions of the second point list (sets: n_cand x n x 2):
+        (morph distances f64, totals f32, pair counts i32, raw offset sums f32), one entry per candidate."""
+        a = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        s = np.ascontiguousarray(sets, np.float32).reshape(-1, len(a), 2)
+        k = len(s)
+        d = np.zeros(k, np.float64); total = np.zeros(k, np.float32); n_pairs = np.zeros(k, np.int32); inner = np.zeros(k, np.float32)
+        self._chk(lib().poppy_hip_align_scores(self.h, _p(a), _p(s), len(a), k, int(w), int(h), _p(d), _p(total), _p(n_pairs), _p(inner)), "align_scores")
+        return d, total, n_pairs, inner
 
     def hamming_knn2(self, query, train):
         q = np.ascontiguousarray(query, np.uint8).reshape(-1, 32); t = np.ascontiguousarray(train, np.uint8).reshape(-1, 32)

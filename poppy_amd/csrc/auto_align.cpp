@@ -250,7 +250,7 @@ bool AutoAligner::warp_in_place(uint8_t* d_img, const double M[6], hipStream_t s
 }
 
 // morph_distance(p1, set_k) for n_cand candidate sets
-bool AutoAligner::score_sets(const std::vector<P2f>& p1, const std::vector<P2f>& sets, int n_cand, hipStream_t s, std::vector<double>& out) {
+bool AutoAligner::score_sets(const std::vector<P2f>& p1, const std::vector<P2f>& sets, int n_cand, hipStream_t s, std::vector<double>& out, ScoreParts* parts) {
     const int n = (int)p1.size();
     const size_t pts = (size_t)n * 8, all = pts * n_cand, res = (size_t)n_cand * 4;
     const size_t need = pts + all + 3 * res + 64;
@@ -271,6 +271,12 @@ bool AutoAligner::score_sets(const std::vector<P2f>& p1, const std::vector<P2f>&
               hipMemcpyAsync(d_sets, sets.data(), all, hipMemcpyHostToDevice, s) == hipSuccess;
     if (ok) {
         launch_candidate_scores(d_p1, d_sets, n, n_cand, d_total, d_np, d_inner, s);
+        const hipError_t launched = hipGetLastError();          // a refused launch wrote nothing: its results are not read back
+        if (launched != hipSuccess) {
+            (void)hipStreamSynchronize(s);                      // the uploads read p1 and sets
+            failed = true; err = std::string("auto_align: candidate scoring failed: ") + hipGetErrorString(launched);
+            return false;
+        }
         ok = hipMemcpyAsync(total.data(), d_total, res, hipMemcpyDeviceToHost, s) == hipSuccess &&
              hipMemcpyAsync(inner.data(), d_inner, res, hipMemcpyDeviceToHost, s) == hipSuccess &&
              hipMemcpyAsync(npairs.data(), d_np, res, hipMemcpyDeviceToHost, s) == hipSuccess;
@@ -296,6 +302,7 @@ bool AutoAligner::score_sets(const std::vector<P2f>& p1, const std::vector<P2f>&
     out.resize(n_cand);
     for (int k = 0; k < n_cand; ++k)
         out[k] = morph_distance_combine(total[k], (size_t)npairs[k], inner1, inner[k], p1.size(), p1.size(), area1, area2[k], W, H);
+    if (parts) { parts->total.swap(total); parts->inner.swap(inner); parts->n_pairs.swap(npairs); }
     return true;
 }
 
@@ -426,7 +433,7 @@ double AutoAligner::reprocrustes(uint8_t* d_img, const std::vector<P2f>& p1, std
 }
 
 int AutoAligner::step(int which, uint8_t* d_img, int w, int h, const std::vector<P2f>& p1, std::vector<P2f>& p2, hipStream_t s, double* dist) {
-    if (p1.size() != p2.size() || p1.size() < 4 || p1.size() > (size_t)kAlignMaxPoints) { err = "auto_align: needs 4 .. 4096 point pairs"; return -1; }
+    if (p1.size() != p2.size() || p1.size() < 4 || p1.size() > (size_t)kAlignMaxPoints) { err = kAlignCountError; return -1; }
     if (int rc = ensure(w, h)) return rc;
     failed = false;
     const double d = which == 0 ? retranslate(d_img, p1, p2, s) : which == 1 ? reprocrustes(d_img, p1, p2, s) : rerotate(d_img, p1, p2, s);
@@ -435,8 +442,17 @@ int AutoAligner::step(int which, uint8_t* d_img, int w, int h, const std::vector
     return 0;
 }
 
+int AutoAligner::scores(const std::vector<P2f>& p1, const std::vector<P2f>& sets, int n_cand, int w, int h, hipStream_t s, std::vector<double>& dist, ScoreParts& parts) {
+    if (p1.size() < 4 || p1.size() > (size_t)kAlignMaxPoints) { err = kAlignCountError; return -1; }
+    if (n_cand < 1 || sets.size() != p1.size() * (size_t)n_cand) { err = "auto_align: the candidate sets need n_cand x n points"; return -1; }
+    if (int rc = ensure(w, h)) return rc;
+    failed = false; err.clear();
+    if (!score_sets(p1, sets, n_cand, s, dist, &parts) || hipStreamSynchronize(s) != hipSuccess) { if (err.empty()) err = "auto_align: device error"; return -2; }
+    return 0;
+}
+
 int AutoAligner::run(uint8_t* d_img, int w, int h, const std::vector<P2f>& p1, std::vector<P2f>& p2, hipStream_t s, double* final_distance) {
-    if (p1.size() != p2.size() || p1.size() < 4 || p1.size() > (size_t)kAlignMaxPoints) { err = "auto_align: needs 4 .. 4096 point pairs"; return -1; }
+    if (p1.size() != p2.size() || p1.size() < 4 || p1.size() > (size_t)kAlignMaxPoints) { err = kAlignCountError; return -1; }
     if (int rc = ensure(w, h)) return rc;
     failed = false;
     const size_t bytes = (size_t)w * h * 3;

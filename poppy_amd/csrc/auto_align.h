@@ -23,6 +23,7 @@ bool warp_affine_device(const uint8_t* d_src, uint8_t* d_dst, int w, int h, cons
 // Candidate scoring (kernels_align.hip): for n_cand versions of the second point set (n_cand x n points, device), per
 // candidate the float sum of the greedy pairs' distances, the number of pairs and the raw inner offset sum.
 constexpr int kAlignMaxPoints = 4096;             // the pairing kernel keeps 16 bytes per point in LDS
+constexpr const char* kAlignCountError = "auto_align: needs 4 .. 4096 point pairs (at least 4 point pairs)";      // every align entry's answer
 void launch_candidate_scores(const float* d_p1, const float* d_sets, int n, int n_cand, float* d_total, int* d_npairs, float* d_inner, hipStream_t s);
 void rotation_matrix_2d(float cx, float cy, double angle_deg, double scale, double M[6]);      // getRotationMatrix2D
 
@@ -38,6 +39,10 @@ public:
     int run(uint8_t* d_img, int w, int h, const std::vector<P2f>& p1, std::vector<P2f>& p2, hipStream_t s, double* final_distance);
     // single steps (tests): 0 retranslate, 1 reprocrustes, 2 rerotate; returns the step's distance through *dist
     int step(int which, uint8_t* d_img, int w, int h, const std::vector<P2f>& p1, std::vector<P2f>& p2, hipStream_t s, double* dist);
+    // score_sets alone (tests): morph_distance(p1, set_k) in a w x h image for n_cand candidate sets, and the kernel's three
+    // per-candidate outputs behind it (float total of the pairs' distances, number of pairs, raw float offset sum)
+    struct ScoreParts { std::vector<float> total, inner; std::vector<int> n_pairs; };
+    int scores(const std::vector<P2f>& p1, const std::vector<P2f>& sets, int n_cand, int w, int h, hipStream_t s, std::vector<double>& dist, ScoreParts& parts);
     void release();
     std::string err;
 private:
@@ -51,7 +56,7 @@ private:
     unsigned char* d_score = nullptr;              // first set, candidate sets and per-candidate results of a search
     size_t d_score_bytes = 0;
     // morph_distance(p1, set) for every candidate set (n_cand x n points, contiguous): O(N^2) parts on the GPU, hull areas on host threads
-    bool score_sets(const std::vector<P2f>& p1, const std::vector<P2f>& sets, int n_cand, hipStream_t s, std::vector<double>& out);
+    bool score_sets(const std::vector<P2f>& p1, const std::vector<P2f>& sets, int n_cand, hipStream_t s, std::vector<double>& out, ScoreParts* parts = nullptr);
     int W = 0, H = 0;
     bool failed = false;
 };

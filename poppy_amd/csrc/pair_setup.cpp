@@ -115,7 +115,8 @@ int poppy_hip_warp_affine(poppy_hip_ctx* c, const uint8_t* src, size_t ss, int W
 
 static int align_host_entry(poppy_hip_ctx* c, int which, uint8_t* img, size_t stride, int W, int H, const float* p1, float* p2, int n, double* dist) {
     if (!c) return POPPY_E_ARG;
-    if (!img || !p1 || !p2 || n < 4 || W <= 0 || H <= 0 || stride < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad align arguments (at least 4 point pairs)");
+    if (!img || !p1 || !p2 || W <= 0 || H <= 0 || stride < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad align arguments");
+    if (n < 4 || n > kAlignMaxPoints) return fail(c, POPPY_E_ARG, kAlignCountError);
     HIPCHK(c, hipSetDevice(c->device));
     chain_touch(c);
     int rc = align_stage(c, img, stride, W, H); if (rc) return rc;
@@ -134,6 +135,25 @@ int poppy_hip_auto_align(poppy_hip_ctx* c, uint8_t* img, size_t stride, int W, i
 int poppy_hip_align_step(poppy_hip_ctx* c, int which, uint8_t* img, size_t stride, int W, int H, const float* p1, float* p2, int n, double* dist) {
     if (which < 0 || which > 2) return c ? fail(c, POPPY_E_ARG, "align_step: which must be 0, 1 or 2") : POPPY_E_ARG;
     return align_host_entry(c, which, img, stride, W, H, p1, p2, n, dist);
+}
+int poppy_hip_align_scores(poppy_hip_ctx* c, const float* p1, const float* sets, int n, int n_cand, int W, int H, double* distances, float* totals,
+                           int* n_pairs, float* inner_sums) {
+    if (!c) return POPPY_E_ARG;
+    if (!p1 || !sets || n_cand < 1 || W <= 0 || H <= 0) return fail(c, POPPY_E_ARG, "bad align arguments");
+    if (n < 4 || n > kAlignMaxPoints) return fail(c, POPPY_E_ARG, kAlignCountError);
+    HIPCHK(c, hipSetDevice(c->device));
+    chain_touch(c);
+    std::vector<P2f> a(n), b((size_t)n * n_cand);
+    memcpy(a.data(), p1, (size_t)n * 8); memcpy(b.data(), sets, (size_t)n * n_cand * 8);
+    std::vector<double> d;
+    AutoAligner::ScoreParts parts;
+    const int rc = c->aligner.scores(a, b, n_cand, W, H, c->stream, d, parts);
+    if (rc) return fail(c, rc == -1 ? POPPY_E_ARG : POPPY_E_DEVICE, c->aligner.err.c_str());
+    if (distances) memcpy(distances, d.data(), (size_t)n_cand * 8);
+    if (totals) memcpy(totals, parts.total.data(), (size_t)n_cand * 4);
+    if (n_pairs) memcpy(n_pairs, parts.n_pairs.data(), (size_t)n_cand * 4);
+    if (inner_sums) memcpy(inner_sums, parts.inner.data(), (size_t)n_cand * 4);
+    return POPPY_OK;
 }
 int poppy_procrustes(const float* x, const float* y, int n, float* rot4, float* se2, float* yprime) {
     if (!x || !y || n < 1) return POPPY_E_ARG;

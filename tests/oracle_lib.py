@@ -292,6 +292,14 @@ def morph_distance(p1, p2, w, h):
     return lib().orc_morph_distance(_vp(p1), _vp(p2), len(p1), w, h)
 
 
+def morph_distance_parts(p1, p2):
+    """The O(N^2) parts of morph_distance: (float total of the pairs' distances, number of pairs, raw float offset sum of p2 against p1)."""
+    p1, p2 = _f(p1), _f(p2)
+    total = np.zeros(1, np.float32); inner = np.zeros(1, np.float32); n_pairs = np.zeros(1, np.int32)
+    lib().orc_morph_distance_parts(_vp(p1), _vp(p2), len(p1), _vp(total), _vp(n_pairs), _vp(inner))
+    return total[0], int(n_pairs[0]), inner[0]
+
+
 def match_prepare(p1, p2, w, h, tol, imd):
     p1, p2 = _f(p1), _f(p2)
     o1 = np.zeros((len(p1) + 4, 2), np.float32); o2 = np.zeros((len(p1) + 4, 2), np.float32)
