@@ -136,7 +136,7 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * poppy_bgr_to_i420 is the host statement of the format, poppy_frame_bytes its size (0 for an unknown format or an empty frame).
  * poppy_hip_set_frame_format drains the context's frames and applies to every frame handed to a writer by poppy_hip_morph,
  * poppy_hip_morph_frames, poppy_hip_render_many, poppy_hip_render_phases and poppy_hip_morph_list — the phase == 0 / 1 and t == 0 / 1
- * copies and the POPPY_E_NOMATCH linear-blend frames included; under I420 and PAL8 the writer gets (frame, width, height, stride = width), under GIF stride = 0.
+ * copies and the POPPY_E_NOMATCH linear-blend frames included; under I420 and PAL8 the writer gets (frame, width, height, stride = width), under GIF and JPEG stride = 0.
  * Any other format: POPPY_E_ARG.  These stay BGR whatever the setting: poppy_hip_render / poppy_hip_dissolve into an explicit dst,
  * poppy_hip_frame_device, frames kept on the device (write == NULL), poppy_hip_morph_sharded and poppy_hip_morph_pairs (their contexts
  * are made from poppy_settings), and include/poppy_hip_shim.hpp.  poppy_hip_pool_set_frame_format sets every context of a pool.
@@ -228,12 +228,66 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * width, height).  Its refusals are poppy_bgr_frames_to_pal8's plus the 65535 limit; nothing is read or written before them.
  * poppy_hip_bgr_frames_to_gif_frames does the same on the context's GPU (upload into a store that lives for the call, the sequence pass per frame, the palette
  * build, the coder and the gather per frame, download of each frame's `total` bytes): the same bytes.  It needs no resident pair and disturbs none; while the
- * context has a sequence open it returns POPPY_E_STATE.  The format applies wherever PAL8_SEQ applies and stays BGR wherever PAL8_SEQ stays BGR.  */
+ * context has a sequence open it returns POPPY_E_STATE.  The format applies wherever PAL8_SEQ applies and stays BGR wherever PAL8_SEQ stays BGR.
+ *
+ * POPPY_FRAME_JPEG: the frame coded on the GPU as one baseline JPEG (JFIF) file, ready to be written into a Motion-JPEG AVI (POPPY_SINK_MJPEG) or to disk as it
+ * is: 24-bit colour, and a fraction of I420's bytes on the link.  Its value is 256, and POPPY_SINK_MJPEG is 256; 255 and 257 stay unknown.  Layout, little-endian:
+ *     bytes 0..3     total: the whole frame's length in bytes, these four included (poppy_jpeg_frame_bytes reads it)
+ *     bytes 4..      one complete JFIF file, FF D8 .. FF D9
+ * The writer gets (frame, width, height, stride = 0), as under GIF, and only `total` bytes are valid.  The rule is integer arithmetic throughout, 32-bit, all
+ * shifts arithmetic, all divisions of non-negative numbers; two implementations agree byte for byte.
+ *   Planes.  The frame's I420 planes exactly as poppy_bgr_to_i420 gives them: Y is w x h, U (Cb) and V (Cr) are cw x ch.
+ *   MCUs.  One MCU is 16 x 16 luma samples, six 8 x 8 blocks in the order Y00, Y01 (right), Y10 (below), Y11, Cb, Cr; ceil(w / 16) x ceil(h / 16) MCUs in raster
+ *      order.  MCU (mx, my)'s luma blocks begin at sample (16 mx + 8 i, 16 my + 8 j), its chroma blocks at (8 mx, 8 my) of their planes.  A sample outside its
+ *      plane is the nearest one inside: x clamped to the plane's width - 1, y to its height - 1.
+ *   FDCT.  s(x, y) = sample - 128.  K = {8192, 8035, 7568, 6811, 5793, 4551, 3135, 1598}, K[k] = round(8192 cos(k pi / 16)).  The 8 x 8 table T has
+ *      T[0][x] = 5793 and, for u > 0, T[u][x] = +-K[..] = round(8192 cos((2 x + 1) u pi / 16)) (so T[u][x] = round(2^14 a(u) cos(..)) for the orthonormal
+ *      DCT's a(0) = sqrt(1 / 8), a(u) = 1 / 2).  Two passes, rows first:
+ *         t(y, u) = (sum over x of T[u][x] * s(x, y) + 1024) >> 11
+ *         F(v, u) = (sum over y of T[v][y] * t(y, u) + 8192) >> 14
+ *      F is 8 times the orthonormal DCT coefficient (three fractional bits, as libjpeg's integer transforms leave them).  |sum| stays below 2^28 in both passes.
+ *   Quantisation.  The Annex K base tables of ITU-T T.81 (K.1 for Y, K.2 for Cb and Cr), scaled by libjpeg's rule: for a quality q from 1 to 100,
+ *      scale = 5000 / q below 50 and 200 - 2 q from 50 up, Q = clamp((base * scale + 50) / 100, 1, 255).  The divisor takes in the transform's factor 8, and the
+ *      division rounds half away from zero: m = (|F| + 4 Q) / (8 Q), the quantised coefficient is m with F's sign.  It is within 1 of a double-precision DCT's
+ *      coefficient quantised by the same Q (ITU-T T.83's bar).  A DC coefficient lies in -1024 .. 1016, an AC coefficient's magnitude below 1024.
+ *   Huffman coding.  Baseline sequential, the four "typical" tables of Annex K.3 (K.3 and K.5 for Y, K.4 and K.6 for Cb and Cr), never optimised.  Per block: the
+ *      DC difference to the previous block of the same component in the segment (the first: to 0) as its category's code and the category's low bits (a negative
+ *      value v as v - 1); then the AC coefficients in zig-zag order as run / category symbols, ZRL (F0) for every 16 zeros in front of a non-zero coefficient,
+ *      EOB (00) when the block ends in zeros, nothing when coefficient 63 is non-zero.  Bits are packed most significant first.
+ *   Restart intervals.  The MCU sequence is cut into segments of POPPY_JPEG_RESTART_MCUS MCUs, whatever the row; the last may be shorter.  Every segment begins
+ *      with DC predictors of 0, is padded with 1-bits to a byte boundary and byte-stuffed (FF -> FF 00).  Segment k, unless it is the last, is followed by
+ *      RST(k mod 8) = FF D0 + (k mod 8); EOI follows the last.  Segments are whole bytes and independent, which is what lets the GPU code one per wave.
+ *      POPPY_JPEG_RESTART_MCUS is a constant of the FORMAT: it decides the bytes ("JPEG hand-off", has what stands behind its value).
+ *   Header.  613 bytes, so the entropy-coded data begins at frame offset 617: SOI; APP0 "JFIF" 1.01, units 0, density 1 : 1, no thumbnail; ONE DQT with table 0
+ *      and table 1 (8-bit entries, zig-zag order); SOF0 with 8-bit precision, the true height and width, components 1 (2 x 2, table 0), 2 and 3 (1 x 1, table 1);
+ *      ONE DHT with DC 0, AC 0, DC 1, AC 1; DRI with the interval (always present); SOS with components 1 (tables 0 / 0), 2 and 3 (1 / 1), Ss 0, Se 63, Ah / Al 0.
+ *   Capacity.  poppy_frame_bytes(POPPY_FRAME_JPEG, w, h) is an upper bound for any content at any quality, and the size of the buffers a frame is built in.  A block
+ *      is at most a DC code of 11 bits (table K.4's longest; K.3's is 9) with 11 value bits (the differences' range is 2040 < 2^11) and 63 AC codes of 16 bits with 10 value bits: 1660 bits.  A
+ *      coefficient in front of which ZRL symbols stand costs less than that many coefficients coded singly (a ZRL is 11 or 10 bits for 16 coefficients), and EOB
+ *      only ever replaces coefficients.  A segment of R = POPPY_JPEG_RESTART_MCUS MCUs is at most ceil(6 * 1660 * R / 8) bytes with its padding, twice that when
+ *      every byte is stuffed, and 2 bytes of marker: POPPY_JPEG_SEGMENT_BYTES.  The frame is at most 617 + ceil(MCUs / R) * POPPY_JPEG_SEGMENT_BYTES bytes (about
+ *      9.7 bytes per pixel: the price of a bound that holds for noise at quality 100 with every byte FF).
+ *   Limits, refused with POPPY_E_UNSUPPORTED before any state changes: a width or height above 65535 (SOF0's 16 bits), and a capacity of 2^32 bytes or more
+ *      (`total` is 32 bits; about 440 million pixels).
+ * poppy_i420_to_jpeg_frame is the host statement (i420: poppy_frame_bytes(POPPY_FRAME_I420, ..) bytes; dst: the capacity; POPPY_E_ARG for a null pointer, an empty
+ * frame or a quality outside 1..100), poppy_bgr_to_jpeg_frame is poppy_bgr_to_i420 followed by it.  poppy_hip_i420_to_jpeg_frame codes a host I420 frame on the
+ * context's GPU at the given quality (upload, the two kernels, download of `total` bytes): the same bytes; it needs no resident pair and disturbs none.
+ * poppy_hip_set_jpeg_quality sets the quality of the frames a context hands to its writers (POPPY_JPEG_QUALITY_DEFAULT = 90 until then): POPPY_E_ARG outside
+ * 1..100, POPPY_E_STATE while a sequence is open; it drains the context's frames, as poppy_hip_set_frame_format does, and takes effect whatever the format is at
+ * the time.  poppy_hip_pool_set_jpeg_quality sets every context of a pool (POPPY_E_STATE with work submitted).
+ * The format applies wherever GIF applies — poppy_hip_morph, poppy_hip_morph_frames, poppy_hip_render_many, poppy_hip_render_phases, poppy_hip_morph_list and
+ * pools, the phase 0 / 1 and t == 0 / 1 copies and the POPPY_E_NOMATCH frames included, under poppy_hip_set_frame_scale and poppy_hip_set_frame_size the host
+ * statement at the writer's geometry — and stays BGR wherever GIF stays BGR.  There is no 4:4:4 or 4:2:2 sampling, no progressive mode and no sequence form. */
 #define POPPY_PAL8_MAX_PIXELS (1 << 24)
 #define POPPY_PAL8_SEQ_MAX_PIXELS (1ull << 32)
 #define POPPY_GIF_SEGMENT_PIXELS 2048
 #define POPPY_GIF_SEGMENT_BYTES ((9 + 12 * (POPPY_GIF_SEGMENT_PIXELS + 2) + 63 + 7) / 8)
-enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128 };
+#ifndef POPPY_JPEG_RESTART_MCUS      /* (a build with another value codes ANOTHER format: only for measuring what the choice costs) */
+#define POPPY_JPEG_RESTART_MCUS 8
+#endif
+#define POPPY_JPEG_SEGMENT_BYTES (2 * ((6 * 1660 * POPPY_JPEG_RESTART_MCUS + 7) / 8) + 2)
+#define POPPY_JPEG_QUALITY_DEFAULT 90
+enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128, POPPY_FRAME_JPEG = 256 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
@@ -245,6 +299,11 @@ int poppy_bgr_to_gif_frame(const uint8_t* bgr, size_t stride, int width, int hei
 int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* ctx, const uint8_t* pal8, int width, int height, uint8_t* dst);
 int poppy_bgr_frames_to_gif_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst);
 int poppy_hip_bgr_frames_to_gif_frames(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst);
+size_t poppy_jpeg_frame_bytes(const uint8_t* frame);
+int poppy_i420_to_jpeg_frame(const uint8_t* i420, int width, int height, int quality, uint8_t* dst);
+int poppy_bgr_to_jpeg_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst);
+int poppy_hip_i420_to_jpeg_frame(poppy_hip_ctx* ctx, const uint8_t* i420, int width, int height, int quality, uint8_t* dst);
+int poppy_hip_set_jpeg_quality(poppy_hip_ctx* ctx, int quality);
 /* Scaled hand-off: frames rendered at the pair's resolution and handed to the writer scaled down by a whole factor, on the GPU, in front of the format
  * conversion.  The pair's resolution decides the keypoints, the mesh and the morph; the scale only decides what crosses the link and what the writer gets.
  *   The rule.  A factor s is a whole number from 1 to POPPY_FRAME_SCALE_MAX = 8; 1, the default, is the identity.  A width x height BGR frame becomes
@@ -635,6 +694,8 @@ int poppy_hip_pool_set_frame_format(poppy_hip_pool* pool, int format);
 int poppy_hip_pool_set_frame_scale(poppy_hip_pool* pool, int factor);
 /* poppy_hip_set_frame_size on every context of the pool; POPPY_E_ARG as there, POPPY_E_STATE as for the format. */
 int poppy_hip_pool_set_frame_size(poppy_hip_pool* pool, int ow, int oh);
+/* poppy_hip_set_jpeg_quality on every context of the pool; POPPY_E_ARG outside 1..100, POPPY_E_STATE as for the format. */
+int poppy_hip_pool_set_jpeg_quality(poppy_hip_pool* pool, int quality);
 /* poppy_hip_mask_rider of the pool's contexts (they share settings and geometry) */
 int poppy_hip_pool_mask_rider(poppy_hip_pool* pool);
 /* The CLI's loop over an image list (src/poppy.cpp:266-328) on ONE context: pair k = (image k, image k + 1), where image k of pair k > 0 is
@@ -687,11 +748,18 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * 256-entry global table (flags 0xF7); a frame whose palette equals it gets a descriptor with flags 0x00 and no local table, then its bytes 772 .. total as they
  * are; a frame whose palette differs gets a local table (0x87), so POPPY_FRAME_GIF frames and the frames of several pairs are taken too.  A raster frame fails this
  * sink; no frame at all gives GIF's empty file.
+ * MJPEG: one RIFF AVI file written from POPPY_FRAME_JPEG frames as they come (stride must be 0, bytes 4 and 5 FF D8, `total` inside the format's capacity, and the
+ * frame's SOF0 must name the sink's width and height): a `hdrl` list with the `avih` main header (dwMicroSecPerFrame = 1000000 * fps_den / fps_num rounded,
+ * AVIF_HASINDEX, one stream) and one `strl` list — `strh` with fccType `vids`, fccHandler `MJPG`, dwScale = fps_den, dwRate = fps_num, and `strf`, a 40-byte
+ * BITMAPINFOHEADER with 24 bits and compression `MJPG` —, a `movi` list with one `00dc` chunk per frame holding the frame's bytes 4 .. total as they are, padded
+ * with a zero byte to even length, and an `idx1` index (AVIIF_KEYFRAME, offsets counted from the `movi` fourcc, the unpadded length).  The RIFF, `movi` and index
+ * lengths, the frame counts and the largest chunk's size are patched in at close; no frame at all gives a valid file of no frames.  A frame that would take the
+ * file past 4 GiB fails the sink (a plain AVI has 32-bit lengths).  A frame of any other format fails this sink, and a JPEG frame fails every other sink.
  * The BGR sinks take frames with stride >= 3 * width, the I420 and GIF sinks frames with stride == width: a frame of another format fails the
  * sink where its stride tells (a BGR frame at the I420 or GIF sink, an I420 or PAL8 frame at a BGR sink); a writer must match the context's format.
  * poppy_sink_close returns the number of frames written, or a negative status if a write failed or a frame had another geometry.   */
 typedef struct poppy_sink poppy_sink;
-enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8, POPPY_SINK_GIF_GLOBAL = 16, POPPY_SINK_GIF_CODED = 64, POPPY_SINK_GIF_GLOBAL_CODED = 128 };
+enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8, POPPY_SINK_GIF_GLOBAL = 16, POPPY_SINK_GIF_CODED = 64, POPPY_SINK_GIF_GLOBAL_CODED = 128, POPPY_SINK_MJPEG = 256 };
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den);
 void poppy_sink_write(void* sink, const uint8_t* bgr, int width, int height, size_t stride);
 int poppy_sink_close(poppy_sink* sink);

@@ -25,8 +25,10 @@ WARP_KERNELS = ("k_warp_bin", "k_warp_tile", "k_warp4")        # order of poppy_
 PYRAMID_FORMS = ("down", "down2", "tail", "tail_nl", "mix_top", "cone", "up2", "up", "unsharp")
 WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_size_t)
 # formats of the frames handed to writers (poppy_hip_set_frame_format) and the file sinks (poppy_sink_open)
-FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF, FRAME_GIF_SEQ = 0, 1, 8, 16, 64, 128
-SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED, SINK_GIF_GLOBAL_CODED = 0, 1, 2, 3, 8, 16, 64, 128
+FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG = 0, 1, 8, 16, 64, 128, 256
+FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG)      # a frame whose length its first four bytes hold
+JPEG_QUALITY_DEFAULT = 90
+SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED, SINK_GIF_GLOBAL_CODED, SINK_MJPEG = 0, 1, 2, 3, 8, 16, 64, 128, 256
 
 # every symbol include/poppy_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -47,6 +49,7 @@ SYMBOLS = [
     "poppy_hip_set_frame_format", "poppy_hip_pool_set_frame_format", "poppy_frame_bytes", "poppy_bgr_to_i420", "poppy_bgr_to_pal8", "poppy_bgr_frames_to_pal8",
     "poppy_gif_frame_bytes", "poppy_pal8_to_gif_frame", "poppy_bgr_to_gif_frame", "poppy_hip_pal8_to_gif_frame",
     "poppy_bgr_frames_to_gif_frames", "poppy_hip_bgr_frames_to_gif_frames",
+    "poppy_jpeg_frame_bytes", "poppy_i420_to_jpeg_frame", "poppy_bgr_to_jpeg_frame", "poppy_hip_i420_to_jpeg_frame", "poppy_hip_set_jpeg_quality", "poppy_hip_pool_set_jpeg_quality",
     "poppy_hip_set_frame_scale", "poppy_hip_pool_set_frame_scale", "poppy_frame_scaled_size", "poppy_bgr_downscale", "poppy_hip_bgr_downscale",
     "poppy_hip_set_frame_size", "poppy_hip_pool_set_frame_size", "poppy_frame_fit_size", "poppy_bgr_resize_area", "poppy_hip_bgr_resize_area",
     "poppy_hip_bgr_resize_area_form",
@@ -185,6 +188,13 @@ def lib():
         L.poppy_hip_pal8_to_gif_frame.argtypes = [vp, vp, i, i, vp]
         L.poppy_bgr_frames_to_gif_frames.argtypes = [vp, sz, sz, i, i, i, vp]
         L.poppy_hip_bgr_frames_to_gif_frames.argtypes = [vp, vp, sz, sz, i, i, i, vp]
+        L.poppy_jpeg_frame_bytes.restype = sz
+        L.poppy_jpeg_frame_bytes.argtypes = [vp]
+        L.poppy_i420_to_jpeg_frame.argtypes = [vp, i, i, i, vp]
+        L.poppy_bgr_to_jpeg_frame.argtypes = [vp, sz, i, i, i, vp]
+        L.poppy_hip_i420_to_jpeg_frame.argtypes = [vp, vp, i, i, i, vp]
+        L.poppy_hip_set_jpeg_quality.argtypes = [vp, i]
+        L.poppy_hip_pool_set_jpeg_quality.argtypes = [vp, i]
         L.poppy_hip_set_frame_scale.argtypes = [vp, i]
         L.poppy_hip_pool_set_frame_scale.argtypes = [vp, i]
         L.poppy_frame_scaled_size.argtypes = [i, i, i, vp, vp]
@@ -208,7 +218,7 @@ def _p(a):
 
 def frame_bytes(fmt, w, h):
     """Host-only: bytes of a w x h frame in format fmt (FRAME_BGR / FRAME_I420 / FRAME_PAL8 / FRAME_PAL8_SEQ; FRAME_GIF and FRAME_GIF_SEQ: the capacity, an upper bound for any
-    content — a frame's own length is gif_frame_bytes; 0 for anything else)."""
+    content — a frame's own length is gif_frame_bytes; FRAME_JPEG: the capacity too, a frame's own length is jpeg_frame_bytes; 0 for anything else)."""
     return int(lib().poppy_frame_bytes(int(fmt), int(w), int(h)))
 
 
@@ -289,6 +299,37 @@ def bgr_to_gif_frame(bgr):
     a = np.ascontiguousarray(bgr, np.uint8)
     h, w = a.shape[:2]
     return _gif_frame(lambda out: lib().poppy_bgr_to_gif_frame(_p(a), w * 3, w, h, _p(out)), "poppy_bgr_to_gif_frame", w, h)
+
+
+def jpeg_frame_bytes(frame):
+    """Host-only: `total` of a FRAME_JPEG frame, its length in bytes (poppy_jpeg_frame_bytes: the first four bytes, little-endian)."""
+    f = np.ascontiguousarray(frame, np.uint8)
+    if f.size < 4:
+        raise PoppyError("jpeg_frame_bytes: a coded frame has at least four bytes")
+    return int(lib().poppy_jpeg_frame_bytes(_p(f)))
+
+
+def _jpeg_frame(call, name, w, h):
+    out = np.empty(max(frame_bytes(FRAME_JPEG, w, h), 4), np.uint8)
+    rc = call(out)
+    if rc:
+        raise PoppyError(f"{name}: {rc}")
+    return out[:jpeg_frame_bytes(out)].copy()
+
+
+def i420_to_jpeg_frame(i420, w, h, quality=JPEG_QUALITY_DEFAULT):
+    """Host-only: the FRAME_JPEG frame of a flat I420 frame (poppy_i420_to_jpeg_frame): `total`, then one baseline JFIF file; a flat uint8 array of its own length."""
+    a = np.ascontiguousarray(i420, np.uint8).ravel()
+    if w > 0 and h > 0 and a.size != frame_bytes(FRAME_I420, w, h):
+        raise PoppyError("i420_to_jpeg_frame: an I420 frame has w * h + 2 * cw * ch bytes")
+    return _jpeg_frame(lambda out: lib().poppy_i420_to_jpeg_frame(_p(a), int(w), int(h), int(quality), _p(out)), "poppy_i420_to_jpeg_frame", w, h)
+
+
+def bgr_to_jpeg_frame(bgr, quality=JPEG_QUALITY_DEFAULT):
+    """Host-only: the FRAME_JPEG frame of an HxWx3 BGR frame (poppy_bgr_to_jpeg_frame = bgr_to_i420, then i420_to_jpeg_frame)."""
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    return _jpeg_frame(lambda out: lib().poppy_bgr_to_jpeg_frame(_p(a), w * 3, w, h, int(quality), _p(out)), "poppy_bgr_to_jpeg_frame", w, h)
 
 
 def _gif_frames(call, chk, frames, row_pad, frame_pad):
@@ -392,8 +433,8 @@ def pal8_to_bgr(frame, w, h):
 
 
 def _frame_view(ptr, w, h, stride, fmt):
-    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF and GIF_SEQ.  A view: valid during the callback."""
-    if fmt in (FRAME_GIF, FRAME_GIF_SEQ):                                        # a coded frame: its own length, not the capacity
+    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF, GIF_SEQ and JPEG.  A view: valid during the callback."""
+    if fmt in FRAMES_CODED:                                                      # a coded frame: its own length, not the capacity (every coded format keeps it in its first four bytes)
         return np.ctypeslib.as_array(ptr, shape=(int(lib().poppy_gif_frame_bytes(ptr)),))
     if fmt in (FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ):
         return np.ctypeslib.as_array(ptr, shape=(frame_bytes(fmt, w, h),))
@@ -713,6 +754,13 @@ class Pool:
             raise PoppyError(f"poppy_hip_pool_set_frame_format: {rc}")
         self.frame_format = int(fmt)
 
+    def set_jpeg_quality(self, quality):
+        """The quality, 1..100, of the FRAME_JPEG frames of every context of the pool (poppy_hip_pool_set_jpeg_quality); PoppyError with the status outside
+        that range or while submitted batches have not been waited for."""
+        rc = lib().poppy_hip_pool_set_jpeg_quality(self.h, int(quality))
+        if rc:
+            raise PoppyError(f"poppy_hip_pool_set_jpeg_quality: {rc}")
+
     def close(self):
         if self.h:
             lib().poppy_hip_pool_destroy(self.h)
@@ -883,9 +931,24 @@ class Context:
         """FRAME_BGR (default), FRAME_I420, FRAME_PAL8 or FRAME_PAL8_SEQ (one palette for all frames of a call, which are handed over when the last
         one is rendered): the format of every frame handed to a writer (poppy_hip_set_frame_format).  Under I420 and both PAL8 formats the collecting wrappers return flat uint8 arrays of frame_bytes(format, W, H).
         FRAME_GIF: PAL8 frames with the indices LZW-coded on the GPU; the wrappers return flat arrays of each frame's own length (gif_frame_bytes).
-        FRAME_GIF_SEQ: FRAME_PAL8_SEQ's sequences with every frame coded like FRAME_GIF's, one palette in all frames of a call."""
+        FRAME_GIF_SEQ: FRAME_PAL8_SEQ's sequences with every frame coded like FRAME_GIF's, one palette in all frames of a call.
+        FRAME_JPEG: every frame one baseline JPEG file, coded on the GPU at set_jpeg_quality's quality; flat arrays of each frame's own length (jpeg_frame_bytes)."""
         self._chk(lib().poppy_hip_set_frame_format(self.h, int(fmt)), "set_frame_format")
         self.frame_format = int(fmt)
+
+    def set_jpeg_quality(self, quality):
+        """The quality, 1..100 (default JPEG_QUALITY_DEFAULT), of the FRAME_JPEG frames this context hands to writers (poppy_hip_set_jpeg_quality)."""
+        self._chk(lib().poppy_hip_set_jpeg_quality(self.h, int(quality)), "set_jpeg_quality")
+
+    def i420_to_jpeg_frame(self, i420, w, h, quality=JPEG_QUALITY_DEFAULT):
+        """The FRAME_JPEG frame of a flat I420 frame, coded on this context's GPU (poppy_hip_i420_to_jpeg_frame: upload, the two kernels, download): the bytes
+        of the host's i420_to_jpeg_frame."""
+        a = np.ascontiguousarray(i420, np.uint8).ravel()
+        if w > 0 and h > 0 and a.size != frame_bytes(FRAME_I420, w, h):
+            raise PoppyError("i420_to_jpeg_frame: an I420 frame has w * h + 2 * cw * ch bytes")
+        out = np.empty(max(frame_bytes(FRAME_JPEG, w, h), 4), np.uint8)
+        self._chk(lib().poppy_hip_i420_to_jpeg_frame(self.h, _p(a), int(w), int(h), int(quality), _p(out)), "i420_to_jpeg_frame")
+        return out[:jpeg_frame_bytes(out)].copy()
 
     def pal8_to_gif_frame(self, pal8, w, h):
         """The FRAME_GIF frame of a flat PAL8 frame, coded on this context's GPU (poppy_hip_pal8_to_gif_frame: upload, the two kernels, download): the bytes of

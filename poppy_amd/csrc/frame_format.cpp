@@ -6,13 +6,16 @@
 static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H <= (unsigned long long)POPPY_PAL8_MAX_PIXELS; }
 constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 2^24 pixels";
 constexpr const char* kGifSizeMsg = "POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 65535 pixels in width and height";
+constexpr const char* kJpegSizeMsg = "POPPY_FRAME_JPEG takes frames of at most 65535 pixels in width and height whose capacity stays below 2^32 bytes";
 constexpr const char* kSeqSizeMsg = "POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ take sequences of fewer than 2^32 pixels in all";
 
 bool format_known(int fmt) {
-    return fmt == POPPY_FRAME_BGR || fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ;
+    return fmt == POPPY_FRAME_BGR || fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ || fmt == POPPY_FRAME_JPEG;
 }
+size_t coded_frame_least(int fmt) { return fmt == POPPY_FRAME_JPEG ? kJpegFrameMinBytes : kGifFrameMinBytes; }
 const char* format_refuses(int fmt, int W, int H) {
     if ((format_builds_palette(fmt) || format_is_sequence(fmt)) && !pal8_fits(W, H)) return kPal8SizeMsg;
+    if (fmt == POPPY_FRAME_JPEG) return jpeg_fits(W, H) ? nullptr : kJpegSizeMsg;
     if (format_is_coded(fmt) && (W > 65535 || H > 65535)) return kGifSizeMsg;
     return nullptr;
 }
@@ -64,7 +67,26 @@ static int alloc_slot_side(poppy_hip_ctx* c, SlotFormat& f) {
     return POPPY_OK;
 }
 
-// I420: the slot's I420 buffer.  PAL8: its PAL8 buffer, tables, side stream and event.  GIF: PAL8's (the coder reads the slot's PAL8 frame) and the coded frame, the
+int ensure_jpeg_tables(poppy_hip_ctx* c) {
+    if (c->jpeg_tables) return POPPY_OK;
+    jpeg::QualityTables t;
+    jpeg::fill_quality_tables(c->jpeg_quality, &t);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMalloc((void**)&c->jpeg_tables, kJpegTableBytes));
+    HIPCHK(c, hipMemcpy(c->jpeg_tables, &t, sizeof t, hipMemcpyHostToDevice));
+    return POPPY_OK;
+}
+
+// the coded frame, the coder's scratch and the pinned length word of a slot: gone (the format they were sized for is another, or the pair's buffers go)
+static void free_slot_coded(SlotFormat& f) {
+    for (uint8_t* b : {f.coded, f.coded_scratch}) if (b) (void)hipFree(b);
+    f.coded = f.coded_scratch = nullptr;
+    if (f.coded_total) (void)hipHostFree(f.coded_total);
+    f.coded_total = nullptr; f.coded_total_dev = nullptr;
+    f.coded_for = POPPY_FRAME_BGR;
+}
+
+// I420: the slot's I420 buffer.  JPEG: that, the coded frame, the coder's scratch, the pinned length word and the context's tables.  PAL8: its PAL8 buffer, tables, side stream and event.  GIF: PAL8's (the coder reads the slot's PAL8 frame) and the coded frame, the
 // coder's scratch and the pinned length word.  PAL8_SEQ and GIF_SEQ: the slots' side streams and the context's sequence tables — the store and the index ring depend on the
 // sequence's length and, under GIF_SEQ, the ring of coded frames: palette_seq.cpp's seq_begin, seq_finish.  All of it in the writer's geometry; with a scale above 1 or a size the scaled BGR frame too.
 int alloc_slot_format(poppy_hip_ctx* c) {
@@ -74,29 +96,31 @@ int alloc_slot_format(poppy_hip_ctx* c) {
     for (FrameSlot& slot : c->slots) {
         SlotFormat& f = slot.fmt;
         if (g.scaled() && !f.scaled) HIPCHK(c, hipMalloc((void**)&f.scaled, poppy_frame_bytes(POPPY_FRAME_BGR, W, H) + 16));
-        if (fmt == POPPY_FRAME_I420 && !f.i420) HIPCHK(c, hipMalloc((void**)&f.i420, poppy_frame_bytes(fmt, W, H) + 16));
+        if (format_converts_to_i420(fmt) && !f.i420) HIPCHK(c, hipMalloc((void**)&f.i420, poppy_frame_bytes(POPPY_FRAME_I420, W, H) + 16));
         if (format_builds_palette(fmt)) {
             if (!f.pal8) HIPCHK(c, hipMalloc((void**)&f.pal8, poppy_frame_bytes(POPPY_FRAME_PAL8, W, H) + 16));
             int rc = alloc_zeroed_tables(c, &f.pal8_tables, kPal8TableBytes); if (rc) return rc;
         }
         if (format_builds_palette(fmt) || format_is_sequence(fmt)) { int rc = alloc_slot_side(c, f); if (rc) return rc; }
-        if (fmt != POPPY_FRAME_GIF) continue;                       // (the slot's coded frame: GIF_SEQ codes from the store into the sequence's ring)
-        if (!f.gif) HIPCHK(c, hipMalloc((void**)&f.gif, poppy_frame_bytes(fmt, W, H) + 16));
-        if (!f.gif_scratch) HIPCHK(c, hipMalloc((void**)&f.gif_scratch, gif_scratch_bytes(W, H)));
-        if (!f.gif_total) {
-            HIPCHK(c, hipHostMalloc((void**)&f.gif_total, 64, hipHostMallocMapped));
-            HIPCHK(c, hipHostGetDevicePointer(&f.gif_total_dev, f.gif_total, 0));
-            *f.gif_total = 0;
+        if (!format_codes_per_frame(fmt)) continue;                 // (the slot's coded frame: GIF_SEQ codes from the store into the sequence's ring)
+        if (fmt == POPPY_FRAME_JPEG) { int rc = ensure_jpeg_tables(c); if (rc) return rc; f.jpeg_tables = c->jpeg_tables; }
+        if (f.coded_for != fmt) free_slot_coded(f);                 // (sized for the other coded format; the frames are drained and the bodies of that format are captured again)
+        f.coded_for = fmt;
+        if (!f.coded) HIPCHK(c, hipMalloc((void**)&f.coded, poppy_frame_bytes(fmt, W, H) + 16));
+        if (!f.coded_scratch) HIPCHK(c, hipMalloc((void**)&f.coded_scratch, fmt == POPPY_FRAME_JPEG ? jpeg_scratch_bytes(W, H) : gif_scratch_bytes(W, H)));
+        if (!f.coded_total) {
+            HIPCHK(c, hipHostMalloc((void**)&f.coded_total, 64, hipHostMallocMapped));
+            HIPCHK(c, hipHostGetDevicePointer(&f.coded_total_dev, f.coded_total, 0));
+            *f.coded_total = 0;
         }
     }
     return format_is_sequence(fmt) ? alloc_zeroed_tables(c, &c->seq.tables, kPal8SeqTableBytes) : POPPY_OK;
 }
 
 void free_slot_format_pair(SlotFormat& f) {
-    for (uint8_t* b : {f.scaled, f.i420, f.pal8, f.pal8_tables, f.gif, f.gif_scratch}) if (b) (void)hipFree(b);
-    f.scaled = f.i420 = f.pal8 = f.pal8_tables = f.gif = f.gif_scratch = nullptr;
-    if (f.gif_total) (void)hipHostFree(f.gif_total);
-    f.gif_total = nullptr; f.gif_total_dev = nullptr;
+    for (uint8_t* b : {f.scaled, f.i420, f.pal8, f.pal8_tables}) if (b) (void)hipFree(b);
+    f.scaled = f.i420 = f.pal8 = f.pal8_tables = nullptr;
+    free_slot_coded(f);
 }
 void free_slot_format_ctx(SlotFormat& f) {
     if (f.fmt_stream) (void)hipStreamDestroy(f.fmt_stream);
@@ -104,7 +128,8 @@ void free_slot_format_ctx(SlotFormat& f) {
 }
 void free_context_format(poppy_hip_ctx* c) {
     for (DeviceBuffer* b : {&c->scale_scratch, &c->fmt_scratch, &c->seq.store, &c->seq.idx, &c->seq.gif}) b->release();
-    for (uint8_t* b : {c->fmt_scratch_tables, c->seq.tables}) if (b) (void)hipFree(b);
+    for (uint8_t* b : {c->fmt_scratch_tables, c->seq.tables, c->jpeg_tables}) if (b) (void)hipFree(b);
+    c->jpeg_tables = nullptr;
     if (c->seq.gif_total) (void)hipHostFree(c->seq.gif_total);
     c->fmt_scratch_tables = nullptr;
     c->seq = PaletteSeq();
@@ -114,17 +139,18 @@ bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt, c
     const SlotFormat& f = slot.fmt;
     if (g.scaled() && !f.scaled) return false;
     if (fmt == POPPY_FRAME_I420) return f.i420 != nullptr;
+    if (fmt == POPPY_FRAME_JPEG) return f.i420 && f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt && f.jpeg_tables;
     if (format_is_sequence(fmt)) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
     if (format_builds_palette(fmt) && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) return false;
-    return fmt != POPPY_FRAME_GIF || (f.gif && f.gif_scratch && f.gif_total);
+    return fmt != POPPY_FRAME_GIF || (f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt);
 }
 const uint8_t* slot_bgr(const FrameSlot& f, const WriterGeom& g) { return g.scaled() ? f.fmt.scaled : f.out; }
 const uint8_t* slot_frame(const FrameSlot& f, int fmt, const WriterGeom& g) {
-    return fmt == POPPY_FRAME_I420 ? f.fmt.i420 : fmt == POPPY_FRAME_PAL8 ? f.fmt.pal8 : fmt == POPPY_FRAME_GIF ? f.fmt.gif : slot_bgr(f, g);
+    return fmt == POPPY_FRAME_I420 ? f.fmt.i420 : fmt == POPPY_FRAME_PAL8 ? f.fmt.pal8 : format_codes_per_frame(fmt) ? f.fmt.coded : slot_bgr(f, g);
 }
 bool slot_frame_length(const FrameSlot& f, int fmt, size_t capacity, size_t* bytes) {
-    *bytes = format_is_coded(fmt) ? *(volatile uint32_t*)f.fmt.gif_total : capacity;
-    return !format_is_coded(fmt) || coded_length_ok(*bytes, capacity);
+    *bytes = format_is_coded(fmt) ? *(volatile uint32_t*)f.fmt.coded_total : capacity;
+    return !format_is_coded(fmt) || coded_length_ok(*bytes, capacity, coded_frame_least(fmt));
 }
 
 void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
@@ -134,15 +160,24 @@ void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* frame, v
     if (tm) tm->mark("gif_pack");
 }
 
+void enqueue_jpeg_coding(const uint8_t* i420, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
+    launch_jpeg_code(i420, tables, scratch, W, H, s);
+    if (tm) tm->mark("jpeg_code");
+    launch_jpeg_pack(tables, scratch, frame, (uint32_t*)total_dev, W, H, s, done);
+    if (tm) tm->mark("jpeg_pack");
+}
+
 void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm) {
     if (g.scaled()) {                                              // the conversion's first dispatch; what follows reads the scaled frame
         launch_writer_scaling(g, src_bgr, b.scaled, W, H, s, fmt == POPPY_FRAME_BGR ? done : nullptr);
         if (tm) tm->mark(scaling_mark(g));
         src_bgr = b.scaled; W = g.w; H = g.h;
     }
-    if (fmt == POPPY_FRAME_I420) {
-        launch_bgr_to_i420(src_bgr, b.i420, W, H, s, done);
+    if (format_converts_to_i420(fmt)) {
+        const bool jpeg = fmt == POPPY_FRAME_JPEG;
+        launch_bgr_to_i420(src_bgr, b.i420, W, H, s, jpeg ? nullptr : done);
         if (tm) tm->mark("frame_format");
+        if (jpeg) enqueue_jpeg_coding(b.i420, b.jpeg_tables, b.coded_scratch, b.coded, b.coded_total_dev, W, H, s, done, tm);
     } else if (format_builds_palette(fmt)) {
         // PAL8 is three dispatches, and the palette build in the middle is one workgroup's serial work (about as long as the rest of the frame)
         const bool gif = fmt == POPPY_FRAME_GIF;
@@ -152,7 +187,7 @@ void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, in
         if (tm) tm->mark("pal8_build");
         launch_pal8_remap(src_bgr, b.pal8_tables, b.pal8, W, H, s, gif ? nullptr : done);
         if (tm) tm->mark("frame_format");                      // (under PAL8 and GIF: the index plane alone)
-        if (gif) enqueue_gif_coding(b.pal8, b.gif_scratch, b.gif, b.gif_total_dev, W, H, s, done, tm);
+        if (gif) enqueue_gif_coding(b.pal8, b.coded_scratch, b.coded, b.coded_total_dev, W, H, s, done, tm);
     }
 }
 
@@ -166,6 +201,24 @@ int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
     if (c->c1) if (const char* why = writer_refuses(c, format, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     c->frame_format = format;
     return c->c1 ? alloc_slot_format(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
+}
+
+// The quality names the tables that the JPEG kernels read.  They stay where they are — the captured bodies of the slots hold the address — and are rewritten
+// once nothing reads them: the frames are drained first.
+int poppy_hip_set_jpeg_quality(poppy_hip_ctx* c, int quality) {
+    if (!c) return POPPY_E_ARG;
+    if (quality < 1 || quality > 100) return fail(c, POPPY_E_ARG, "the JPEG quality is a whole number from 1 to 100");
+    if (c->seq.open) return fail(c, POPPY_E_STATE, "a sequence is open on this context");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = drain_frames(c); if (rc) return rc; }
+    if (quality == c->jpeg_quality) return POPPY_OK;
+    if (c->jpeg_tables) {
+        jpeg::QualityTables t;
+        jpeg::fill_quality_tables(quality, &t);
+        HIPCHK(c, hipMemcpy(c->jpeg_tables, &t, sizeof t, hipMemcpyHostToDevice));
+    }
+    c->jpeg_quality = quality;
+    return POPPY_OK;
 }
 
 // A new writer's geometry resizes every buffer of it: the slots' are freed and allocated again, and the captured bodies, which hold their addresses, go.

@@ -2,6 +2,7 @@
 // writer_image.cpp) both check, each stated once.  Host only, nothing of HIP.
 #pragma once
 #include "../../include/poppy_hip.h"
+#include "jpeg_tables.h"
 
 // poppy_hip_set_frame_size's rule (include/poppy_hip.h): ow x oh is no larger than W x H and at most POPPY_FRAME_SCALE_MAX times smaller per side (so W, H >= 1 too)
 inline bool size_admits(int W, int H, int ow, int oh) {
@@ -14,4 +15,9 @@ inline size_t gif_frame_capacity(size_t w, size_t h) {
     return 772 + 1 + payload + (payload + 254) / 255 + 1;
 }
 constexpr size_t kGifFrameMinBytes = 776;      // ... and the smallest there is, the same with one byte of payload in one sub-block: 772 + 1 + (1 + 1) + 1
-inline bool coded_length_ok(size_t total, size_t capacity) { return total >= kGifFrameMinBytes && total <= capacity; }      // a coder's `total`, before that many bytes are copied or read
+inline bool coded_length_ok(size_t total, size_t capacity, size_t least = kGifFrameMinBytes) { return total >= least && total <= capacity; }      // a coder's `total`, before that many bytes are copied or read
+// A JPEG-coded frame (POPPY_FRAME_JPEG): `total`, the fixed header, every restart interval at its bound (include/poppy_hip.h has the derivation; jpeg_tables.h) ...
+inline size_t jpeg_frame_capacity(size_t w, size_t h) { return (size_t)poppy_hip::jpeg::frame_capacity(w, h); }
+constexpr size_t kJpegFrameMinBytes = poppy_hip::jpeg::kFrameMinBytes;      // ... and the smallest: the header, a byte of entropy-coded data, EOI
+// what the format takes: SOF0's 16-bit sides, and a capacity that `total`'s 32 bits hold
+inline bool jpeg_fits(int W, int H) { return W <= 65535 && H <= 65535 && poppy_hip::jpeg::frame_capacity((size_t)W, (size_t)H) <= 0xffffffffull; }

@@ -10,6 +10,7 @@
 //   POPPY_SINK_GIF_GLOBAL  the same for PAL8_SEQ frames: the first frame's palette as the global colour table, local tables only where a frame's palette differs
 //   POPPY_SINK_GIF_CODED   POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames, whose image data arrives coded (frame_gif.cpp, kernels_frame_gif.hip): nothing is coded here
 //   POPPY_SINK_GIF_GLOBAL_CODED  POPPY_SINK_GIF_GLOBAL's file from coded frames (POPPY_FRAME_GIF_SEQ): the first frame's palette as the global table, local tables only where a palette differs
+//   POPPY_SINK_MJPEG  one RIFF AVI file, a `vids` / `MJPG` stream, from POPPY_FRAME_JPEG frames, whose bytes arrive coded (frame_jpeg.cpp, kernels_frame_jpeg.hip)
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "frame_limits.h"
 #include "gif_lzw.h"
@@ -31,6 +32,10 @@ struct poppy_sink {
     int delay_cs = 3;                  // GIF: the frames' delay in centiseconds
     bool head_written = false;         // GIF_GLOBAL: the header waits for the first frame's palette
     uint8_t global_pal[768];           // ... which is the global colour table
+    int fps_num = 30, fps_den = 1;     // MJPEG: the stream's rate and scale
+    uint64_t at = 0;                   // MJPEG: the file's length so far
+    uint32_t largest = 0;              // MJPEG: the largest chunk's payload
+    std::vector<uint32_t> index;       // MJPEG: per frame the chunk's offset from the `movi` fourcc and its length
 };
 
 namespace {
@@ -110,6 +115,92 @@ bool gif_coded_frame(poppy_sink* s, const uint8_t* frame) {
     return fwrite(gce, 1, 8, s->f) == 8 && fwrite(desc, 1, 10, s->f) == 10 && fwrite(frame + from, 1, total - from, s->f) == total - from;
 }
 
+// ---- POPPY_SINK_MJPEG: a RIFF AVI with one Motion-JPEG video stream (include/poppy_hip.h names every chunk) ----
+constexpr long kAviMovi = 220;                              // the file offset of the `movi` fourcc; the first chunk follows it
+constexpr long kAviRiffSize = 4, kAviTotalFrames = 48, kAviBuffer = 60, kAviLength = 140, kAviStreamBuffer = 144, kAviMoviSize = 216;
+
+void le32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+
+bool avi_head(poppy_sink* s) {
+    uint8_t h[224];
+    memset(h, 0, sizeof h);
+    auto tag = [&](int at, const char* t) { memcpy(h + at, t, 4); };
+    const uint32_t w = (uint32_t)s->w, ht = (uint32_t)s->h;
+    tag(0, "RIFF"); tag(8, "AVI ");
+    tag(12, "LIST"); le32(h + 16, 192); tag(20, "hdrl");
+    tag(24, "avih"); le32(h + 28, 56);
+    le32(h + 32, (uint32_t)((1000000ll * s->fps_den + s->fps_num / 2) / s->fps_num));      // dwMicroSecPerFrame
+    le32(h + 44, 0x10);                                     // AVIF_HASINDEX
+    le32(h + 56, 1);                                        // dwStreams
+    le32(h + 64, w); le32(h + 68, ht);
+    tag(88, "LIST"); le32(h + 92, 116); tag(96, "strl");
+    tag(100, "strh"); le32(h + 104, 56); tag(108, "vids"); tag(112, "MJPG");
+    le32(h + 128, (uint32_t)s->fps_den); le32(h + 132, (uint32_t)s->fps_num);      // dwScale, dwRate
+    le32(h + 148, 0xffffffffu);                             // dwQuality: the default
+    h[160] = (uint8_t)w; h[161] = (uint8_t)(w >> 8); h[162] = (uint8_t)ht; h[163] = (uint8_t)(ht >> 8);      // rcFrame's right and bottom
+    tag(164, "strf"); le32(h + 168, 40);
+    le32(h + 172, 40); le32(h + 176, w); le32(h + 180, ht); h[184] = 1; h[186] = 24; tag(188, "MJPG"); le32(h + 192, w * ht * 3);
+    tag(212, "LIST"); tag(220, "movi");
+    s->at = sizeof h;
+    return fwrite(h, 1, sizeof h, s->f) == sizeof h;
+}
+
+// the width and height that the file's SOF0 names (a walk over the marker segments in front of SOS, inside n bytes); false when there is none
+bool jpeg_sof0_size(const uint8_t* jfif, size_t n, int* w, int* h) {
+    size_t at = 2;
+    while (at + 4 <= n && jfif[at] == 0xFF) {
+        const int marker = jfif[at + 1];
+        const size_t len = (size_t)jfif[at + 2] << 8 | jfif[at + 3];
+        if (marker == 0xDA || len < 2 || at + 2 + len > n) return false;
+        if (marker == 0xC0) {
+            if (len < 7) return false;
+            *h = jfif[at + 5] << 8 | jfif[at + 6]; *w = jfif[at + 7] << 8 | jfif[at + 8];
+            return true;
+        }
+        at += 2 + len;
+    }
+    return false;
+}
+
+bool mjpeg_frame(poppy_sink* s, const uint8_t* frame) {
+    const size_t total = poppy_jpeg_frame_bytes(frame);
+    if (total < 4 + 4 || total > poppy_frame_bytes(POPPY_FRAME_JPEG, s->w, s->h)) return false;
+    const uint8_t* jfif = frame + 4;
+    const size_t n = total - 4, pad = n & 1;
+    int w = 0, h = 0;
+    if (jfif[0] != 0xFF || jfif[1] != 0xD8 || !jpeg_sof0_size(jfif, n, &w, &h) || w != s->w || h != s->h) return false;
+    // the file with this chunk, the index's chunk header and every index entry stays below 4 GiB
+    if (s->at + 8 + n + pad + 8 + 16 * (uint64_t)(s->index.size() / 2 + 1) > 0xffffffffull) return false;
+    uint8_t head[8] = {'0', '0', 'd', 'c'};
+    le32(head + 4, (uint32_t)n);
+    const uint8_t zero = 0;
+    if (fwrite(head, 1, 8, s->f) != 8 || fwrite(jfif, 1, n, s->f) != n || (pad && fwrite(&zero, 1, 1, s->f) != 1)) return false;
+    s->index.push_back((uint32_t)(s->at - kAviMovi)); s->index.push_back((uint32_t)n);
+    s->at += 8 + n + pad;
+    if (n > s->largest) s->largest = (uint32_t)n;
+    return true;
+}
+
+// the index behind the last chunk, then the lengths and counts that were not known at the head
+bool avi_close(poppy_sink* s) {
+    const uint32_t frames = (uint32_t)(s->index.size() / 2);
+    std::vector<uint8_t> idx(8 + 16 * (size_t)frames);
+    memcpy(idx.data(), "idx1", 4); le32(idx.data() + 4, 16 * frames);
+    for (uint32_t k = 0; k < frames; ++k) {
+        uint8_t* e = idx.data() + 8 + 16 * (size_t)k;
+        memcpy(e, "00dc", 4); le32(e + 4, 0x10); le32(e + 8, s->index[2 * k]); le32(e + 12, s->index[2 * k + 1]);      // AVIIF_KEYFRAME
+    }
+    if (fwrite(idx.data(), 1, idx.size(), s->f) != idx.size()) return false;
+    const uint64_t end = s->at + idx.size();
+    const struct { long at; uint32_t v; } patch[] = {{kAviRiffSize, (uint32_t)(end - 8)}, {kAviTotalFrames, frames}, {kAviBuffer, s->largest}, {kAviLength, frames},
+                                                     {kAviStreamBuffer, s->largest}, {kAviMoviSize, (uint32_t)(s->at - kAviMovi)}};
+    for (const auto& p : patch) {
+        uint8_t v[4]; le32(v, p.v);
+        if (fseek(s->f, p.at, SEEK_SET) != 0 || fwrite(v, 1, 4, s->f) != 4) return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -121,6 +212,7 @@ size_t poppy_frame_bytes(int format, int width, int height) {
     if (format == POPPY_FRAME_I420) return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2);
     if (format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ) return w * h + 768;
     if (format == POPPY_FRAME_GIF || format == POPPY_FRAME_GIF_SEQ) return gif_frame_capacity(w, h);      // (frame_limits.h, beside the smallest coded frame)
+    if (format == POPPY_FRAME_JPEG) return jpeg_frame_capacity(w, h);
     return 0;
 }
 
@@ -153,7 +245,7 @@ int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, 
 }
 
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den) {
-    if (!path || width <= 0 || height <= 0 || (!sink_is_gif(format) && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
+    if (!path || width <= 0 || height <= 0 || (!sink_is_gif(format) && format != POPPY_SINK_MJPEG && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
     poppy_sink* s = new poppy_sink();
     s->format = format; s->w = width; s->h = height; s->path = path;
     if (format == POPPY_SINK_PPM) {
@@ -177,7 +269,7 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
         if (bad || !seen) { delete s; return nullptr; }
         s->path = head; s->tail = tail;
     }
-    if (sink_is_gif(format) && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen: every write fails, close says so
+    if ((sink_is_gif(format) || format == POPPY_SINK_MJPEG) && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen, JPEG's 16-bit SOF0: every write fails, close says so
     if (format != POPPY_SINK_PPM) {
         s->f = fopen(path, "wb");
         if (!s->f) { delete s; return nullptr; }
@@ -190,6 +282,9 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
             const long long cs = (den * 100 + num / 2) / num;
             s->delay_cs = (int)(cs < 1 ? 1 : cs > 65535 ? 65535 : cs);
             if (!sink_has_global_table(format) && !gif_head(s, nullptr)) s->failed = true;      // (a global table: with the first frame)
+        } else if (format == POPPY_SINK_MJPEG) {
+            s->fps_num = fps_num > 0 ? fps_num : 30; s->fps_den = fps_den > 0 ? fps_den : 1;
+            if (!avi_head(s)) s->failed = true;
         }
     }
     s->row.resize((size_t)width * 3);
@@ -201,6 +296,10 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
     if (!s || s->failed) return;
     // (an I420 frame comes with stride == width: the BGR sinks refuse it, and the I420 sink refuses anything else)
     // (a coded frame comes with stride == 0: every other sink refuses it below, and the coded sinks refuse anything else)
+    if (s->format == POPPY_SINK_MJPEG) {
+        if (!bgr || width != s->w || height != s->h || stride != 0 || !mjpeg_frame(s, bgr)) s->failed = true; else ++s->frames;
+        return;
+    }
     if (sink_takes_coded(s->format)) {
         if (!bgr || width != s->w || height != s->h || stride != 0 || !gif_coded_frame(s, bgr)) s->failed = true; else ++s->frames;
         return;
@@ -260,6 +359,7 @@ int poppy_sink_close(poppy_sink* s) {
     if (!s) return POPPY_E_ARG;
     if (s->f && sink_has_global_table(s->format) && !s->failed && !s->head_written && !gif_head(s, nullptr)) s->failed = true;      // no frame came: GIF's empty file
     if (s->f && sink_is_gif(s->format) && !s->failed && fputc(0x3B, s->f) == EOF) s->failed = true;      // the trailer
+    if (s->f && s->format == POPPY_SINK_MJPEG && !s->failed && !avi_close(s)) s->failed = true;
     const int n = s->failed ? POPPY_E_DEVICE : s->frames;
     if (s->f) fclose(s->f);
     delete s;

@@ -1,6 +1,7 @@
 // kernels.h — launchers of the HIP kernels behind libpoppy_hip.so (gfx950 only).
 #pragma once
 #include "../../include/poppy_hip.h"
+#include "jpeg_tables.h"
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
@@ -256,5 +257,16 @@ void launch_gif_pack(const uint8_t* pal8, const uint8_t* scratch, uint8_t* frame
 // build (seq_tables: the cell -> index table and the palette are read); no index plane is stored.
 void launch_gif_lzw_bgr(const uint8_t* bgr, const uint8_t* seq_tables, uint8_t* scratch, int w, int h, hipStream_t s);
 void launch_gif_pack_seq(const uint8_t* seq_tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
+
+// an I420 frame on the device -> POPPY_FRAME_JPEG (kernels_frame_jpeg.hip; the format: include/poppy_hip.h), two dispatches on one stream: the coder, a restart
+// interval per wave, into `scratch` (jpeg_scratch_bytes: a slot of kJpegSlotBytes per segment, then the segments' byte lengths), and the gather into `frame`
+// (poppy_frame_bytes(POPPY_FRAME_JPEG, w, h) bytes) with the header, the restart markers, EOI and `total`; total_host (optional): a word of mapped pinned host
+// memory that receives `total` too.  `tables`: kJpegTableBytes of device memory holding a jpeg::QualityTables (jpeg_tables.h: fill_quality_tables), which names
+// the quality.  `done` (optional) rides on the second dispatch.
+constexpr size_t kJpegSlotBytes = ((size_t)POPPY_JPEG_SEGMENT_BYTES - 2 + 3) & ~(size_t)3;
+constexpr size_t kJpegTableBytes = sizeof(jpeg::QualityTables);
+size_t jpeg_scratch_bytes(int w, int h);
+void launch_jpeg_code(const uint8_t* i420, const void* tables, uint8_t* scratch, int w, int h, hipStream_t s);
+void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
 
 }  // namespace poppy_hip

@@ -311,6 +311,16 @@ int poppy_hip_pool_set_frame_format(poppy_hip_pool* p, int format) {
     return POPPY_OK;
 }
 
+int poppy_hip_pool_set_jpeg_quality(poppy_hip_pool* p, int quality) {
+    if (!p || quality < 1 || quality > 100) return POPPY_E_ARG;
+    {
+        std::lock_guard<std::mutex> lk(p->q_mu);
+        if (p->unwaited || p->outstanding) return POPPY_E_STATE;                 // the feeders' contexts may be rendering
+    }
+    for (poppy_hip_ctx* c : p->ctx) { const int rc = poppy_hip_set_jpeg_quality(c, quality); if (rc) return rc; }
+    return POPPY_OK;
+}
+
 int poppy_hip_pool_set_frame_scale(poppy_hip_pool* p, int factor) {
     if (!p || factor < 1 || factor > POPPY_FRAME_SCALE_MAX) return POPPY_E_ARG;
     {

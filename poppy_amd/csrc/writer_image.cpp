@@ -30,6 +30,28 @@ static int gif_from_device_pal8(poppy_hip_ctx* c, const uint8_t* d_pal8, int W, 
     return POPPY_OK;
 }
 
+// an I420 frame in device memory -> its POPPY_FRAME_JPEG frame in `host` (exactly `total` bytes) at the quality that `d_tables` name, on the context's stream and
+// waited for: the frames that no slot renders, and poppy_hip_i420_to_jpeg_frame.  The buffers live for the call.
+static int jpeg_from_device_i420(poppy_hip_ctx* c, const uint8_t* d_i420, const void* d_tables, int W, int H, std::vector<uint8_t>& host) {
+    const size_t cap = poppy_frame_bytes(POPPY_FRAME_JPEG, W, H);
+    CallBuffers held;
+    uint8_t *work = nullptr, *frame = nullptr;
+    hipError_t e = held.alloc(&work, jpeg_scratch_bytes(W, H));
+    if (e == hipSuccess) e = held.alloc(&frame, cap + 16);
+    uint32_t total = 0;
+    if (e == hipSuccess) {
+        enqueue_jpeg_coding(d_i420, d_tables, work, frame, nullptr, W, H, c->stream, nullptr, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go
+    if (e == hipSuccess) e = e_sync;
+    if (e == hipSuccess && !coded_length_ok(total, cap, kJpegFrameMinBytes)) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+    if (e == hipSuccess) { host.resize(total); e = hipMemcpy(host.data(), frame, total, hipMemcpyDeviceToHost); }
+    if (e != hipSuccess) { c->err = std::string("JPEG frame coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    return POPPY_OK;
+}
+
 int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const WriterGeom& g, std::vector<uint8_t>& host, size_t* stride, int n_copies) {
     const int fmt = c->frame_format;
     if (const char* why = format_refuses(fmt, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
@@ -48,14 +70,18 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
     *stride = writer_stride(fmt, W);
     const uint8_t* d_frame = d_bgr;
     if (fmt != POPPY_FRAME_BGR) {                                  // converted into the context's scratch: the slots' launches on other buffers
-        const bool gif = fmt == POPPY_FRAME_GIF;
+        // (a coded format: its raster form into the scratch — PAL8 for GIF, I420 for JPEG —, then the coder on buffers that live for the call)
+        const bool gif = fmt == POPPY_FRAME_GIF, jpeg = fmt == POPPY_FRAME_JPEG;
+        const int raster = gif ? POPPY_FRAME_PAL8 : jpeg ? POPPY_FRAME_I420 : fmt;
         if (format_builds_palette(fmt)) { int rc = alloc_zeroed_tables(c, &c->fmt_scratch_tables, kPal8TableBytes); if (rc) return rc; }
-        HIPCHK(c, c->fmt_scratch.reserve(poppy_frame_bytes(gif ? POPPY_FRAME_PAL8 : fmt, W, H) + 16, c->stream));
+        if (jpeg) { int rc = ensure_jpeg_tables(c); if (rc) return rc; }
+        HIPCHK(c, c->fmt_scratch.reserve(poppy_frame_bytes(raster, W, H) + 16, c->stream));
         SlotFormat scratch;
         scratch.i420 = scratch.pal8 = c->fmt_scratch.p; scratch.pal8_tables = c->fmt_scratch_tables;
-        enqueue_conversion(gif ? POPPY_FRAME_PAL8 : fmt, WriterGeom{W, H}, d_bgr, W, H, scratch, c->stream, nullptr, nullptr);
+        enqueue_conversion(raster, WriterGeom{W, H}, d_bgr, W, H, scratch, c->stream, nullptr, nullptr);
         HIPCHK(c, hipGetLastError());
         if (gif) return gif_from_device_pal8(c, c->fmt_scratch.p, W, H, host);
+        if (jpeg) return jpeg_from_device_i420(c, c->fmt_scratch.p, c->jpeg_tables, W, H, host);
         d_frame = c->fmt_scratch.p;
     }
     host.resize(poppy_frame_bytes(fmt, W, H));
@@ -74,6 +100,7 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
     std::vector<uint8_t> pal8(format_is_sequence(fmt) && format_is_coded(fmt) ? poppy_frame_bytes(POPPY_FRAME_PAL8_SEQ, W, H) : 0);      // (GIF_SEQ: PAL8_SEQ's frame, then the host coder)
     int rc = format_is_sequence(fmt) ? pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, pal8.empty() ? tmp.data() : pal8.data()) :
                    fmt == POPPY_FRAME_GIF ? poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data()) :
+                   fmt == POPPY_FRAME_JPEG ? poppy_bgr_to_jpeg_frame(bgr, stride, W, H, c->jpeg_quality, tmp.data()) :
                    fmt == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
     if (rc == POPPY_OK && !pal8.empty()) rc = poppy_pal8_to_gif_frame(pal8.data(), W, H, tmp.data());
     if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
@@ -157,6 +184,26 @@ int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* c, const uint8_t* pal8, int W, in
     if (hipMemcpy(d_pal8, pal8, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(c, POPPY_E_DEVICE, "upload of the PAL8 frame failed");
     std::vector<uint8_t> host;
     const int rc = gif_from_device_pal8(c, d_pal8, W, H, host);
+    if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
+    return rc;
+}
+
+int poppy_hip_i420_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i420, int W, int H, int quality, uint8_t* dst) {
+    if (!c) return POPPY_E_ARG;
+    if (!i420 || !dst || W <= 0 || H <= 0 || quality < 1 || quality > 100) return fail(c, POPPY_E_ARG, "bad arguments");
+    if (const char* why = format_refuses(POPPY_FRAME_JPEG, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = poppy_frame_bytes(POPPY_FRAME_I420, W, H);
+    jpeg::QualityTables t;
+    jpeg::fill_quality_tables(quality, &t);
+    CallBuffers held;                                              // (jpeg_from_device_i420 waits for the stream before it returns)
+    uint8_t *d_i420 = nullptr, *d_tables = nullptr;
+    HIPCHK(c, held.alloc(&d_i420, bytes + 16));
+    HIPCHK(c, held.alloc(&d_tables, kJpegTableBytes));
+    if (hipMemcpy(d_i420, i420, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_tables, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, POPPY_E_DEVICE, "upload of the I420 frame failed");
+    std::vector<uint8_t> host;
+    const int rc = jpeg_from_device_i420(c, d_i420, d_tables, W, H, host);
     if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
     return rc;
 }

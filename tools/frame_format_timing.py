@@ -1,4 +1,4 @@
-"""BGR against I420 against PAL8 against PAL8_SEQ against GIF frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run
+"""BGR against I420 against PAL8 against PAL8_SEQ against GIF against JPEG frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run
 times each row once per format, one format right after the other, and the rows report min / median / max over --runs runs.
 
   pool_1080p    bench.py's `value` set-up: a pool of --contexts contexts, --steps queued batches of six 1080p pairs from device images, 60 chained
@@ -10,12 +10,13 @@ times each row once per format, one format right after the other, and the rows r
   chained_frame one context, the 60 chained frames of a resident pair to the counting writer (what the extra launch costs a chained frame)
   d2h_ceiling   pinned device-to-host copies of one frame's bytes, back to back on one stream (BGR, I420 and PAL8 sizes at 1080p and 4K)
 and, at the end, the conversion kernels' own times in timing mode 1 at 1080p and 4K (I420: frame_format; PAL8: pal8_hist, pal8_build, frame_format = the index plane;
-PAL8_SEQ: pal8_seq_hist per frame, pal8_seq_build per sequence, frame_format = the index plane; GIF: PAL8's three, then gif_lzw and gif_pack).  Under PAL8_SEQ a pair's (a call's) frames are handed over after its last
+PAL8_SEQ: pal8_seq_hist per frame, pal8_seq_build per sequence, frame_format = the index plane; GIF: PAL8's three, then gif_lzw and gif_pack; JPEG: I420's frame_format, then
+jpeg_code and jpeg_pack), and for the coded formats the median length of the 60 chained frames of the synthetic and of a textured pair (coded_bytes_median, with the coders' times on those frames; JPEG at --jpeg-quality).  Under PAL8_SEQ a pair's (a call's) frames are handed over after its last
 frame.
 
-    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif --scales 1,2 --kernel-scales 2,4
+    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif,jpeg --scales 1,2 --kernel-scales 2,4
                                          --size 1280x720 --size-4k 1920x1080]
---formats leaves formats out (a library older than GIF: bgr,i420,pal8,pal8_seq).  --scales adds every format again per scale above 1 (poppy_hip_set_frame_scale: the
+--formats leaves formats out (a library older than GIF: bgr,i420,pal8,pal8_seq; older than JPEG: without jpeg).  --scales adds every format again per scale above 1 (poppy_hip_set_frame_scale: the
 column "gif@2" is GIF at scale 2), alternated with the others in the same process; --kernel-scales adds k_bgr_downscale's own time (timing mode 1: frame_scale) under BGR
 at 1080p and 4K for those factors.  --size OWxOH adds every format again at that size (poppy_hip_set_frame_size: the column "i420@1280x720"); the 4K rows of such a
 column use --size-4k (default: --size), and its timing mode 1 entry has the resize kernel's time (frame_resize).  GIF's d2h_ceiling entry is its CAPACITY (poppy_frame_bytes); a frame's copy moves its own
@@ -33,7 +34,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poppy_amd import capi, synth  # noqa: E402
 
-ALL_FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420), ("pal8", capi.FRAME_PAL8), ("pal8_seq", capi.FRAME_PAL8_SEQ), ("gif", capi.FRAME_GIF))
+ALL_FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420), ("pal8", capi.FRAME_PAL8), ("pal8_seq", capi.FRAME_PAL8_SEQ), ("gif", capi.FRAME_GIF), ("jpeg", capi.FRAME_JPEG))
 
 
 def pair_images(torch, dev, w, h, n):
@@ -80,7 +81,8 @@ def main():
     ap.add_argument("--steps-4k", type=int, default=3)
     ap.add_argument("--contexts", type=int, default=6)
     ap.add_argument("--rows", default="pool_1080p,pool_4k,job480,chained,chained_frame,d2h_ceiling")
-    ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq,gif")
+    ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq,gif,jpeg")
+    ap.add_argument("--jpeg-quality", type=int, default=capi.JPEG_QUALITY_DEFAULT)
     ap.add_argument("--scales", default="1")
     ap.add_argument("--kernel-scales", default="")
     ap.add_argument("--size", default="")
@@ -122,6 +124,10 @@ def main():
     pool4 = capi.Pool([0], contexts_per_device=a.contexts, number_of_frames=60) if "pool_4k" in rows else None
     ctx4 = capi.Context(0, number_of_frames=60) if "chained_4k" in rows else None
     ctx = capi.Context(0, number_of_frames=60)
+    if "jpeg" in a.formats.split(","):
+        for target in (pool, pool4, ctx4, ctx):
+            if target:
+                target.set_jpeg_quality(a.jpeg_quality)
     ta, tb = p1080[0]
     ph480 = np.arange(480) / 480.0
     shapes = np.array([capi.lib().poppy_frame_ratio(j, 60, -1.0) for j in range(60)])
@@ -189,7 +195,22 @@ def main():
             ctx.reset(); ctx.render_many_counted(shapes, chain=True)
             t = {n: (ms, k) for n, ms, k in ctx.timing_summary()}
             ctx.set_timing(0)
-            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_scale", "frame_resize", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build", "gif_lzw", "gif_pack")}
+            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_scale", "frame_resize", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build", "gif_lzw", "gif_pack", "jpeg_code", "jpeg_pack")}
+    # the coded formats' frame lengths: the 60 chained frames of the synthetic pair and of a textured pair, collected
+    out["coded_bytes_median"] = {}
+    coded = tuple(c for c in FMTS if c[1][0] in capi.FRAMES_CODED and c[1][1] == 1)
+    for (w, h), (x, y) in ((((W, H), (ta, tb)),) + ((((3840, 2160), p4k[0]),) if p4k else ())) if coded else ():
+        tex = [torch.from_numpy(np.ascontiguousarray(np.tile(synth.textured_bgr(960, 540, sd), (h // 540, w // 960, 1)))).to(dev) for sd in (41, 42)]
+        for name, fmt in coded:
+            set_column(ctx, fmt, four_k=w > W)
+            for pair, (u, v) in (("synthetic", (x, y)), ("textured", tex)):
+                sizes = []
+                ctx.pair_begin_device(u.data_ptr(), v.data_ptr(), w, h)
+                ctx.set_timing(1)
+                ctx.reset(); ctx.render_many(shapes, chain=True, write=lambda f: sizes.append(int(f.size)))
+                t = {n: round(ms / k * 1e3, 2) for n, ms, k in ctx.timing_summary() if n in ("gif_lzw", "gif_pack", "jpeg_code", "jpeg_pack")}
+                ctx.set_timing(0)
+                out["coded_bytes_median"][f"{w}x{h}_{name}_{pair}"] = {"bytes": int(statistics.median(sizes)), "kernels_us": t}
     for p in (pool, pool4, ctx4):
         if p:
             p.close()
