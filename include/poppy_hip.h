@@ -277,7 +277,38 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * the time.  poppy_hip_pool_set_jpeg_quality sets every context of a pool (POPPY_E_STATE with work submitted).
  * The format applies wherever GIF applies — poppy_hip_morph, poppy_hip_morph_frames, poppy_hip_render_many, poppy_hip_render_phases, poppy_hip_morph_list and
  * pools, the phase 0 / 1 and t == 0 / 1 copies and the POPPY_E_NOMATCH frames included, under poppy_hip_set_frame_scale and poppy_hip_set_frame_size the host
- * statement at the writer's geometry — and stays BGR wherever GIF stays BGR.  There is no 4:4:4 or 4:2:2 sampling, no progressive mode and no sequence form. */
+ * statement at the writer's geometry — and stays BGR wherever GIF stays BGR.  There is no 4:2:2 sampling, no progressive mode and no sequence form.
+ *
+ * POPPY_FRAME_JPEG444: POPPY_FRAME_JPEG with full-resolution chroma (4:4:4), for texture and saturated edges, where it is 4:2:0 that costs the quality and not
+ * the quantiser; about 1.3 times JPEG's bytes.  Its value is 512; 511 and 513 stay unknown, and there is no sink value of its own: POPPY_SINK_MJPEG takes its
+ * frames.  The layout is JPEG's (`total`, then one complete JFIF file), the writer gets stride = 0, poppy_jpeg_frame_bytes reads `total`, and the rule is
+ * POPPY_FRAME_JPEG's word for word with these changes only:
+ *   Planes.  The frame's I444 planes exactly as poppy_bgr_to_i444 gives them: three tight w x h planes back to back, Y, then U (Cb), then V (Cr).  Y is I420's Y;
+ *      U and V are I420's formulas with n = 1, k = 0, per pixel and with arithmetic shifts:
+ *         U = clamp(((-11059 R - 21709 G + 32768 B + 32768) >> 16) + 128, 0, 255)
+ *         V = clamp((( 32768 R - 27439 G -  5329 B + 32768) >> 16) + 128, 0, 255)
+ *      (pure blue gives U = 256 before the clamp).  These are the planes POPPY_SINK_Y4M writes.  I444 is a statement and a kernel, not a hand-off format: it
+ *      saves nothing on the link against BGR.
+ *   MCUs.  One MCU is 8 x 8 samples, three 8 x 8 blocks in the order Y, Cb, Cr; ceil(w / 8) x ceil(h / 8) MCUs in raster order.  Every block of MCU (mx, my)
+ *      begins at sample (8 mx, 8 my) of its plane.  A sample outside the plane is the nearest one inside, as under JPEG.
+ *   FDCT, quantisation, Huffman coding.  Unchanged: the same T and shifts, the Annex K tables at the context's quality, m = (|F| + 4 Q) / (8 Q), the typical
+ *      Huffman tables — table 0 for Y, table 1 for Cb and Cr — and one DC predictor per component.
+ *   Restart intervals.  POPPY_JPEG444_RESTART_MCUS = 16 MCUs, a constant of the format: 16 x 3 = 48 blocks, JPEG's 8 x 6, so POPPY_JPEG_SEGMENT_BYTES bounds a
+ *      segment of this format too.
+ *   Header.  613 bytes, the entropy-coded data begins at frame offset 617.  It is JPEG's header for the same size and quality except in exactly two bytes: SOF0
+ *      component 1's sampling byte is 0x11 (1 x 1) instead of 0x22, and DRI's low byte is 16 instead of 8.
+ *   Capacity.  poppy_frame_bytes(POPPY_FRAME_JPEG444, w, h) = 617 + ceil(MCUs / 16) * POPPY_JPEG_SEGMENT_BYTES: about 19.5 bytes per pixel, twice JPEG's, because
+ *      there are twice the blocks.
+ *   Limits, refused with POPPY_E_UNSUPPORTED before any state changes: a width or height above 65535, and a capacity of 2^32 bytes or more (about 220 million
+ *      pixels).
+ * poppy_bgr_to_i444 is the host statement of the planes (dst: 3 * width * height bytes; POPPY_E_ARG for a null pointer, an empty frame or stride < 3 * width),
+ * poppy_hip_bgr_to_i444 does the same on the context's GPU (upload, the kernel, download): the same bytes; it needs no resident pair and disturbs none.  As with
+ * poppy_hip_bgr_downscale, the device copy of the source is tight and begins (stride - 3 * width) mod 16 bytes behind a 256-byte boundary.
+ * poppy_i444_to_jpeg_frame is the host statement of the format (i444: 3 * width * height bytes; dst: the capacity), poppy_bgr_to_jpeg444_frame is
+ * poppy_bgr_to_i444 followed by it; both refuse what poppy_i420_to_jpeg_frame and poppy_bgr_to_jpeg_frame refuse.  poppy_hip_i444_to_jpeg_frame codes a host I444
+ * frame on the context's GPU at the given quality (upload, the two kernels, download of `total` bytes): the same bytes; no resident pair needed, none disturbed.
+ * poppy_hip_set_jpeg_quality and poppy_hip_pool_set_jpeg_quality serve both formats.  The format applies wherever JPEG applies, under poppy_hip_set_frame_scale
+ * and poppy_hip_set_frame_size as the host statement at the writer's geometry, and stays BGR wherever JPEG stays BGR.  */
 #define POPPY_PAL8_MAX_PIXELS (1 << 24)
 #define POPPY_PAL8_SEQ_MAX_PIXELS (1ull << 32)
 #define POPPY_GIF_SEGMENT_PIXELS 2048
@@ -286,8 +317,10 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
 #define POPPY_JPEG_RESTART_MCUS 8
 #endif
 #define POPPY_JPEG_SEGMENT_BYTES (2 * ((6 * 1660 * POPPY_JPEG_RESTART_MCUS + 7) / 8) + 2)
+#define POPPY_JPEG444_RESTART_MCUS 16      /* (3 * 16 blocks = 6 * POPPY_JPEG_RESTART_MCUS: poppy_amd/csrc/jpeg_tables.h asserts it) */
 #define POPPY_JPEG_QUALITY_DEFAULT 90
-enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128, POPPY_FRAME_JPEG = 256 };
+enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128, POPPY_FRAME_JPEG = 256,
+       POPPY_FRAME_JPEG444 = 512 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
@@ -304,6 +337,11 @@ int poppy_i420_to_jpeg_frame(const uint8_t* i420, int width, int height, int qua
 int poppy_bgr_to_jpeg_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst);
 int poppy_hip_i420_to_jpeg_frame(poppy_hip_ctx* ctx, const uint8_t* i420, int width, int height, int quality, uint8_t* dst);
 int poppy_hip_set_jpeg_quality(poppy_hip_ctx* ctx, int quality);
+int poppy_bgr_to_i444(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_hip_bgr_to_i444(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_i444_to_jpeg_frame(const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
+int poppy_bgr_to_jpeg444_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst);
+int poppy_hip_i444_to_jpeg_frame(poppy_hip_ctx* ctx, const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
 /* Scaled hand-off: frames rendered at the pair's resolution and handed to the writer scaled down by a whole factor, on the GPU, in front of the format
  * conversion.  The pair's resolution decides the keypoints, the mesh and the morph; the scale only decides what crosses the link and what the writer gets.
  *   The rule.  A factor s is a whole number from 1 to POPPY_FRAME_SCALE_MAX = 8; 1, the default, is the identity.  A width x height BGR frame becomes
@@ -755,6 +793,8 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * with a zero byte to even length, and an `idx1` index (AVIIF_KEYFRAME, offsets counted from the `movi` fourcc, the unpadded length).  The RIFF, `movi` and index
  * lengths, the frame counts and the largest chunk's size are patched in at close; no frame at all gives a valid file of no frames.  A frame that would take the
  * file past 4 GiB fails the sink (a plain AVI has 32-bit lengths).  A frame of any other format fails this sink, and a JPEG frame fails every other sink.
+ * POPPY_FRAME_JPEG444 frames are taken as well, in any mix with POPPY_FRAME_JPEG frames (the `MJPG` stream does not care): a frame whose SOF0 gives component 1
+ * the sampling byte 0x11 is held to POPPY_FRAME_JPEG444's capacity, any other to POPPY_FRAME_JPEG's; nothing else about the sink differs.
  * The BGR sinks take frames with stride >= 3 * width, the I420 and GIF sinks frames with stride == width: a frame of another format fails the
  * sink where its stride tells (a BGR frame at the I420 or GIF sink, an I420 or PAL8 frame at a BGR sink); a writer must match the context's format.
  * poppy_sink_close returns the number of frames written, or a negative status if a write failed or a frame had another geometry.   */

@@ -25,8 +25,8 @@ WARP_KERNELS = ("k_warp_bin", "k_warp_tile", "k_warp4")        # order of poppy_
 PYRAMID_FORMS = ("down", "down2", "tail", "tail_nl", "mix_top", "cone", "up2", "up", "unsharp")
 WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_size_t)
 # formats of the frames handed to writers (poppy_hip_set_frame_format) and the file sinks (poppy_sink_open)
-FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG = 0, 1, 8, 16, 64, 128, 256
-FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG)      # a frame whose length its first four bytes hold
+FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444 = 0, 1, 8, 16, 64, 128, 256, 512
+FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444)      # a frame whose length its first four bytes hold
 JPEG_QUALITY_DEFAULT = 90
 SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED, SINK_GIF_GLOBAL_CODED, SINK_MJPEG = 0, 1, 2, 3, 8, 16, 64, 128, 256
 
@@ -50,6 +50,7 @@ SYMBOLS = [
     "poppy_gif_frame_bytes", "poppy_pal8_to_gif_frame", "poppy_bgr_to_gif_frame", "poppy_hip_pal8_to_gif_frame",
     "poppy_bgr_frames_to_gif_frames", "poppy_hip_bgr_frames_to_gif_frames",
     "poppy_jpeg_frame_bytes", "poppy_i420_to_jpeg_frame", "poppy_bgr_to_jpeg_frame", "poppy_hip_i420_to_jpeg_frame", "poppy_hip_set_jpeg_quality", "poppy_hip_pool_set_jpeg_quality",
+    "poppy_bgr_to_i444", "poppy_hip_bgr_to_i444", "poppy_i444_to_jpeg_frame", "poppy_bgr_to_jpeg444_frame", "poppy_hip_i444_to_jpeg_frame",
     "poppy_hip_set_frame_scale", "poppy_hip_pool_set_frame_scale", "poppy_frame_scaled_size", "poppy_bgr_downscale", "poppy_hip_bgr_downscale",
     "poppy_hip_set_frame_size", "poppy_hip_pool_set_frame_size", "poppy_frame_fit_size", "poppy_bgr_resize_area", "poppy_hip_bgr_resize_area",
     "poppy_hip_bgr_resize_area_form",
@@ -194,6 +195,11 @@ def lib():
         L.poppy_bgr_to_jpeg_frame.argtypes = [vp, sz, i, i, i, vp]
         L.poppy_hip_i420_to_jpeg_frame.argtypes = [vp, vp, i, i, i, vp]
         L.poppy_hip_set_jpeg_quality.argtypes = [vp, i]
+        L.poppy_bgr_to_i444.argtypes = [vp, sz, i, i, vp]
+        L.poppy_hip_bgr_to_i444.argtypes = [vp, vp, sz, i, i, vp]
+        L.poppy_i444_to_jpeg_frame.argtypes = [vp, i, i, i, vp]
+        L.poppy_bgr_to_jpeg444_frame.argtypes = [vp, sz, i, i, i, vp]
+        L.poppy_hip_i444_to_jpeg_frame.argtypes = [vp, vp, i, i, i, vp]
         L.poppy_hip_pool_set_jpeg_quality.argtypes = [vp, i]
         L.poppy_hip_set_frame_scale.argtypes = [vp, i]
         L.poppy_hip_pool_set_frame_scale.argtypes = [vp, i]
@@ -218,7 +224,7 @@ def _p(a):
 
 def frame_bytes(fmt, w, h):
     """Host-only: bytes of a w x h frame in format fmt (FRAME_BGR / FRAME_I420 / FRAME_PAL8 / FRAME_PAL8_SEQ; FRAME_GIF and FRAME_GIF_SEQ: the capacity, an upper bound for any
-    content — a frame's own length is gif_frame_bytes; FRAME_JPEG: the capacity too, a frame's own length is jpeg_frame_bytes; 0 for anything else)."""
+    content — a frame's own length is gif_frame_bytes; FRAME_JPEG and FRAME_JPEG444: the capacity too, a frame's own length is jpeg_frame_bytes; 0 for anything else)."""
     return int(lib().poppy_frame_bytes(int(fmt), int(w), int(h)))
 
 
@@ -309,8 +315,8 @@ def jpeg_frame_bytes(frame):
     return int(lib().poppy_jpeg_frame_bytes(_p(f)))
 
 
-def _jpeg_frame(call, name, w, h):
-    out = np.empty(max(frame_bytes(FRAME_JPEG, w, h), 4), np.uint8)
+def _jpeg_frame(call, name, w, h, fmt=FRAME_JPEG):
+    out = np.empty(max(frame_bytes(fmt, w, h), 4), np.uint8)
     rc = call(out)
     if rc:
         raise PoppyError(f"{name}: {rc}")
@@ -330,6 +336,45 @@ def bgr_to_jpeg_frame(bgr, quality=JPEG_QUALITY_DEFAULT):
     a = np.ascontiguousarray(bgr, np.uint8)
     h, w = a.shape[:2]
     return _jpeg_frame(lambda out: lib().poppy_bgr_to_jpeg_frame(_p(a), w * 3, w, h, int(quality), _p(out)), "poppy_bgr_to_jpeg_frame", w, h)
+
+
+def _i444(call, what, bgr, row_pad, chk=None):
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    stride = w * 3 + int(row_pad)
+    if row_pad:
+        buf = np.full((h, stride), 0xA5, np.uint8)
+        buf[:, :w * 3] = a.reshape(h, w * 3)
+        a = buf
+    out = np.empty(3 * w * h, np.uint8)
+    rc = call(_p(a), stride, w, h, _p(out))
+    if chk:
+        chk(rc, what)
+    elif rc:
+        raise PoppyError(f"poppy_{what}: {rc}")
+    return out
+
+
+def bgr_to_i444(bgr, row_pad=0):
+    """Host-only: the I444 planes of an HxWx3 BGR frame (poppy_bgr_to_i444), as a flat uint8 array of 3 * W * H: the Y, the U and the V plane, every sample from
+    its own pixel — what FRAME_JPEG444 codes.  row_pad: the frame is handed over with that many extra bytes per row."""
+    return _i444(lib().poppy_bgr_to_i444, "bgr_to_i444", bgr, row_pad)
+
+
+def i444_to_jpeg_frame(i444, w, h, quality=JPEG_QUALITY_DEFAULT):
+    """Host-only: the FRAME_JPEG444 frame of flat I444 planes (poppy_i444_to_jpeg_frame): `total`, then one baseline JFIF file with 4:4:4 sampling; a flat uint8
+    array of its own length."""
+    a = np.ascontiguousarray(i444, np.uint8).ravel()
+    if w > 0 and h > 0 and a.size != 3 * w * h:
+        raise PoppyError("i444_to_jpeg_frame: an I444 frame has 3 * w * h bytes")
+    return _jpeg_frame(lambda out: lib().poppy_i444_to_jpeg_frame(_p(a), int(w), int(h), int(quality), _p(out)), "poppy_i444_to_jpeg_frame", w, h, FRAME_JPEG444)
+
+
+def bgr_to_jpeg444_frame(bgr, quality=JPEG_QUALITY_DEFAULT):
+    """Host-only: the FRAME_JPEG444 frame of an HxWx3 BGR frame (poppy_bgr_to_jpeg444_frame = bgr_to_i444, then i444_to_jpeg_frame)."""
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    return _jpeg_frame(lambda out: lib().poppy_bgr_to_jpeg444_frame(_p(a), w * 3, w, h, int(quality), _p(out)), "poppy_bgr_to_jpeg444_frame", w, h, FRAME_JPEG444)
 
 
 def _gif_frames(call, chk, frames, row_pad, frame_pad):
@@ -433,7 +478,7 @@ def pal8_to_bgr(frame, w, h):
 
 
 def _frame_view(ptr, w, h, stride, fmt):
-    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF, GIF_SEQ and JPEG.  A view: valid during the callback."""
+    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF, GIF_SEQ, JPEG and JPEG444.  A view: valid during the callback."""
     if fmt in FRAMES_CODED:                                                      # a coded frame: its own length, not the capacity (every coded format keeps it in its first four bytes)
         return np.ctypeslib.as_array(ptr, shape=(int(lib().poppy_gif_frame_bytes(ptr)),))
     if fmt in (FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ):
@@ -932,7 +977,8 @@ class Context:
         one is rendered): the format of every frame handed to a writer (poppy_hip_set_frame_format).  Under I420 and both PAL8 formats the collecting wrappers return flat uint8 arrays of frame_bytes(format, W, H).
         FRAME_GIF: PAL8 frames with the indices LZW-coded on the GPU; the wrappers return flat arrays of each frame's own length (gif_frame_bytes).
         FRAME_GIF_SEQ: FRAME_PAL8_SEQ's sequences with every frame coded like FRAME_GIF's, one palette in all frames of a call.
-        FRAME_JPEG: every frame one baseline JPEG file, coded on the GPU at set_jpeg_quality's quality; flat arrays of each frame's own length (jpeg_frame_bytes)."""
+        FRAME_JPEG: every frame one baseline JPEG file, coded on the GPU at set_jpeg_quality's quality; flat arrays of each frame's own length (jpeg_frame_bytes).
+        FRAME_JPEG444: the same with full-resolution chroma (4:4:4), coded from the frame's I444 planes."""
         self._chk(lib().poppy_hip_set_frame_format(self.h, int(fmt)), "set_frame_format")
         self.frame_format = int(fmt)
 
@@ -948,6 +994,21 @@ class Context:
             raise PoppyError("i420_to_jpeg_frame: an I420 frame has w * h + 2 * cw * ch bytes")
         out = np.empty(max(frame_bytes(FRAME_JPEG, w, h), 4), np.uint8)
         self._chk(lib().poppy_hip_i420_to_jpeg_frame(self.h, _p(a), int(w), int(h), int(quality), _p(out)), "i420_to_jpeg_frame")
+        return out[:jpeg_frame_bytes(out)].copy()
+
+    def bgr_to_i444(self, bgr, row_pad=0):
+        """The I444 planes of an HxWx3 BGR frame, converted on this context's GPU (poppy_hip_bgr_to_i444: upload, the kernel, download): the bytes of the host's
+        bgr_to_i444.  The low four bits of row_pad place the device copy of the source that many bytes behind a 256-byte boundary."""
+        return _i444(lambda *args: lib().poppy_hip_bgr_to_i444(self.h, *args), "bgr_to_i444", bgr, row_pad, self._chk)
+
+    def i444_to_jpeg_frame(self, i444, w, h, quality=JPEG_QUALITY_DEFAULT):
+        """The FRAME_JPEG444 frame of flat I444 planes, coded on this context's GPU (poppy_hip_i444_to_jpeg_frame: upload, the two kernels, download): the bytes
+        of the host's i444_to_jpeg_frame."""
+        a = np.ascontiguousarray(i444, np.uint8).ravel()
+        if w > 0 and h > 0 and a.size != 3 * w * h:
+            raise PoppyError("i444_to_jpeg_frame: an I444 frame has 3 * w * h bytes")
+        out = np.empty(max(frame_bytes(FRAME_JPEG444, w, h), 4), np.uint8)
+        self._chk(lib().poppy_hip_i444_to_jpeg_frame(self.h, _p(a), int(w), int(h), int(quality), _p(out)), "i444_to_jpeg_frame")
         return out[:jpeg_frame_bytes(out)].copy()
 
     def pal8_to_gif_frame(self, pal8, w, h):

@@ -11,7 +11,7 @@
 //   rccl_comm.cpp     the RCCL loader and a context's communicator (rccl_comm.h, comm_guard.h): the two collectives, the abort, the pair state's broadcast, export and import
 //   sharded_setup.cpp the pair set-up spread over ranks, as named stages (shard_protocol.h: roles and the keypoint hand-off; local_hub.h: the in-process transport)
 //   morph_sharded.cpp one job over N devices;  pool.cpp: pools of contexts, the set-up gate, batches of pairs
-//   frame_plan.cpp    host-side planning of a frame;  frame_pal8.cpp, frame_gif.cpp, frame_jpeg.cpp (jpeg_tables.h: the tables it shares with kernels_frame_jpeg.hip), frame_scale.cpp, frame_resize.cpp, frame_sink.cpp: the host side of the writer formats, the scaled and resized hand-off and the file sinks
+//   frame_plan.cpp    host-side planning of a frame;  frame_pal8.cpp, frame_gif.cpp, frame_jpeg.cpp (jpeg_tables.h: the tables it shares with kernels_frame_jpeg.hip), frame_i444.cpp, frame_scale.cpp, frame_resize.cpp, frame_sink.cpp: the host side of the writer formats, the scaled and resized hand-off and the file sinks
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "foreground.h"
@@ -122,11 +122,11 @@ struct poppy_hip_ctx {
     bool writer_attached = false;                   // a multi-frame call with a writer is in progress
     int frame_format = POPPY_FRAME_BGR;             // of the frames handed to writers (poppy_hip_set_frame_format)
     int frame_scale = 1;                            // ... and the whole factor they are scaled down by first (poppy_hip_set_frame_scale; frame_format.h: writer_geom)
-    int jpeg_quality = POPPY_JPEG_QUALITY_DEFAULT;  // ... and the quality of POPPY_FRAME_JPEG frames (poppy_hip_set_jpeg_quality)
+    int jpeg_quality = POPPY_JPEG_QUALITY_DEFAULT;  // ... and the quality of POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames (poppy_hip_set_jpeg_quality)
     uint8_t* jpeg_tables = nullptr;                 // ... with its header and quantiser tables on the device (frame_format.h: ensure_jpeg_tables; rewritten in place when the quality changes)
     int frame_ow = 0, frame_oh = 0;                 // ... or the size they are resized to (poppy_hip_set_frame_size; 0, 0: none; never beside a scale above 1)
     DeviceBuffer scale_scratch;                     // the scaled BGR of the copies and fallback frames that no slot renders (writer_image.h: scale_into_scratch)
-    DeviceBuffer fmt_scratch;                       // I420 / PAL8 of the copies and fallback frames that no slot renders (download_frame)
+    DeviceBuffer fmt_scratch;                       // I420 / I444 / PAL8 of the copies and fallback frames that no slot renders (download_frame)
     uint8_t* fmt_scratch_tables = nullptr;          // ... and the PAL8 conversion's tables for them
     PaletteSeq seq;                                 // POPPY_FRAME_PAL8_SEQ: the sequence being collected (palette_seq.h: seq_begin .. seq_finish)
     double wait_ms[4] = {0, 0, 0, 0};               // host waits inside submit_frame since the context was made (POPPY_SEQ_TIMING prints the per-sequence share)

@@ -6,16 +6,16 @@
 static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H <= (unsigned long long)POPPY_PAL8_MAX_PIXELS; }
 constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 2^24 pixels";
 constexpr const char* kGifSizeMsg = "POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 65535 pixels in width and height";
-constexpr const char* kJpegSizeMsg = "POPPY_FRAME_JPEG takes frames of at most 65535 pixels in width and height whose capacity stays below 2^32 bytes";
+constexpr const char* kJpegSizeMsg = "POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 take frames of at most 65535 pixels in width and height whose capacity stays below 2^32 bytes";
 constexpr const char* kSeqSizeMsg = "POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ take sequences of fewer than 2^32 pixels in all";
 
 bool format_known(int fmt) {
-    return fmt == POPPY_FRAME_BGR || fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ || fmt == POPPY_FRAME_JPEG;
+    return fmt == POPPY_FRAME_BGR || fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ || format_is_jpeg(fmt);
 }
-size_t coded_frame_least(int fmt) { return fmt == POPPY_FRAME_JPEG ? kJpegFrameMinBytes : kGifFrameMinBytes; }
+size_t coded_frame_least(int fmt) { return format_is_jpeg(fmt) ? kJpegFrameMinBytes : kGifFrameMinBytes; }
 const char* format_refuses(int fmt, int W, int H) {
     if ((format_builds_palette(fmt) || format_is_sequence(fmt)) && !pal8_fits(W, H)) return kPal8SizeMsg;
-    if (fmt == POPPY_FRAME_JPEG) return jpeg_fits(W, H) ? nullptr : kJpegSizeMsg;
+    if (format_is_jpeg(fmt)) return jpeg_fits(W, H, format_sampling(fmt)) ? nullptr : kJpegSizeMsg;
     if (format_is_coded(fmt) && (W > 65535 || H > 65535)) return kGifSizeMsg;
     return nullptr;
 }
@@ -86,7 +86,7 @@ static void free_slot_coded(SlotFormat& f) {
     f.coded_for = POPPY_FRAME_BGR;
 }
 
-// I420: the slot's I420 buffer.  JPEG: that, the coded frame, the coder's scratch, the pinned length word and the context's tables.  PAL8: its PAL8 buffer, tables, side stream and event.  GIF: PAL8's (the coder reads the slot's PAL8 frame) and the coded frame, the
+// I420: the slot's I420 buffer.  JPEG: that, the coded frame, the coder's scratch, the pinned length word and the context's tables.  JPEG444: the same with the slot's I444 buffer in the I420 buffer's place.  PAL8: its PAL8 buffer, tables, side stream and event.  GIF: PAL8's (the coder reads the slot's PAL8 frame) and the coded frame, the
 // coder's scratch and the pinned length word.  PAL8_SEQ and GIF_SEQ: the slots' side streams and the context's sequence tables — the store and the index ring depend on the
 // sequence's length and, under GIF_SEQ, the ring of coded frames: palette_seq.cpp's seq_begin, seq_finish.  All of it in the writer's geometry; with a scale above 1 or a size the scaled BGR frame too.
 int alloc_slot_format(poppy_hip_ctx* c) {
@@ -97,17 +97,18 @@ int alloc_slot_format(poppy_hip_ctx* c) {
         SlotFormat& f = slot.fmt;
         if (g.scaled() && !f.scaled) HIPCHK(c, hipMalloc((void**)&f.scaled, poppy_frame_bytes(POPPY_FRAME_BGR, W, H) + 16));
         if (format_converts_to_i420(fmt) && !f.i420) HIPCHK(c, hipMalloc((void**)&f.i420, poppy_frame_bytes(POPPY_FRAME_I420, W, H) + 16));
+        if (fmt == POPPY_FRAME_JPEG444 && !f.i444) HIPCHK(c, hipMalloc((void**)&f.i444, (size_t)W * H * 3 + 16));
         if (format_builds_palette(fmt)) {
             if (!f.pal8) HIPCHK(c, hipMalloc((void**)&f.pal8, poppy_frame_bytes(POPPY_FRAME_PAL8, W, H) + 16));
             int rc = alloc_zeroed_tables(c, &f.pal8_tables, kPal8TableBytes); if (rc) return rc;
         }
         if (format_builds_palette(fmt) || format_is_sequence(fmt)) { int rc = alloc_slot_side(c, f); if (rc) return rc; }
         if (!format_codes_per_frame(fmt)) continue;                 // (the slot's coded frame: GIF_SEQ codes from the store into the sequence's ring)
-        if (fmt == POPPY_FRAME_JPEG) { int rc = ensure_jpeg_tables(c); if (rc) return rc; f.jpeg_tables = c->jpeg_tables; }
-        if (f.coded_for != fmt) free_slot_coded(f);                 // (sized for the other coded format; the frames are drained and the bodies of that format are captured again)
+        if (format_is_jpeg(fmt)) { int rc = ensure_jpeg_tables(c); if (rc) return rc; f.jpeg_tables = c->jpeg_tables; }
+        if (f.coded_for != fmt) free_slot_coded(f);                 // (sized for another coded format; the frames are drained and the bodies of that format are captured again)
         f.coded_for = fmt;
         if (!f.coded) HIPCHK(c, hipMalloc((void**)&f.coded, poppy_frame_bytes(fmt, W, H) + 16));
-        if (!f.coded_scratch) HIPCHK(c, hipMalloc((void**)&f.coded_scratch, fmt == POPPY_FRAME_JPEG ? jpeg_scratch_bytes(W, H) : gif_scratch_bytes(W, H)));
+        if (!f.coded_scratch) HIPCHK(c, hipMalloc((void**)&f.coded_scratch, format_is_jpeg(fmt) ? jpeg_scratch_bytes(W, H, format_sampling(fmt)) : gif_scratch_bytes(W, H)));
         if (!f.coded_total) {
             HIPCHK(c, hipHostMalloc((void**)&f.coded_total, 64, hipHostMallocMapped));
             HIPCHK(c, hipHostGetDevicePointer(&f.coded_total_dev, f.coded_total, 0));
@@ -118,8 +119,8 @@ int alloc_slot_format(poppy_hip_ctx* c) {
 }
 
 void free_slot_format_pair(SlotFormat& f) {
-    for (uint8_t* b : {f.scaled, f.i420, f.pal8, f.pal8_tables}) if (b) (void)hipFree(b);
-    f.scaled = f.i420 = f.pal8 = f.pal8_tables = nullptr;
+    for (uint8_t* b : {f.scaled, f.i420, f.i444, f.pal8, f.pal8_tables}) if (b) (void)hipFree(b);
+    f.scaled = f.i420 = f.i444 = f.pal8 = f.pal8_tables = nullptr;
     free_slot_coded(f);
 }
 void free_slot_format_ctx(SlotFormat& f) {
@@ -139,7 +140,7 @@ bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt, c
     const SlotFormat& f = slot.fmt;
     if (g.scaled() && !f.scaled) return false;
     if (fmt == POPPY_FRAME_I420) return f.i420 != nullptr;
-    if (fmt == POPPY_FRAME_JPEG) return f.i420 && f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt && f.jpeg_tables;
+    if (format_is_jpeg(fmt)) return (fmt == POPPY_FRAME_JPEG444 ? f.i444 : f.i420) && f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt && f.jpeg_tables;
     if (format_is_sequence(fmt)) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
     if (format_builds_palette(fmt) && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) return false;
     return fmt != POPPY_FRAME_GIF || (f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt);
@@ -160,10 +161,10 @@ void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* frame, v
     if (tm) tm->mark("gif_pack");
 }
 
-void enqueue_jpeg_coding(const uint8_t* i420, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
-    launch_jpeg_code(i420, tables, scratch, W, H, s);
+void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, jpeg::Sampling sm, hipStream_t s, hipEvent_t done, Timer* tm) {
+    launch_jpeg_code(planes, tables, scratch, W, H, sm, s);
     if (tm) tm->mark("jpeg_code");
-    launch_jpeg_pack(tables, scratch, frame, (uint32_t*)total_dev, W, H, s, done);
+    launch_jpeg_pack(tables, scratch, frame, (uint32_t*)total_dev, W, H, sm, s, done);
     if (tm) tm->mark("jpeg_pack");
 }
 
@@ -177,7 +178,11 @@ void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, in
         const bool jpeg = fmt == POPPY_FRAME_JPEG;
         launch_bgr_to_i420(src_bgr, b.i420, W, H, s, jpeg ? nullptr : done);
         if (tm) tm->mark("frame_format");
-        if (jpeg) enqueue_jpeg_coding(b.i420, b.jpeg_tables, b.coded_scratch, b.coded, b.coded_total_dev, W, H, s, done, tm);
+        if (jpeg) enqueue_jpeg_coding(b.i420, b.jpeg_tables, b.coded_scratch, b.coded, b.coded_total_dev, W, H, jpeg::k420, s, done, tm);
+    } else if (fmt == POPPY_FRAME_JPEG444) {                       // JPEG's chain with the I444 kernel in the I420 kernel's place
+        launch_bgr_to_i444(src_bgr, b.i444, W, H, s);
+        if (tm) tm->mark("frame_format");
+        enqueue_jpeg_coding(b.i444, b.jpeg_tables, b.coded_scratch, b.coded, b.coded_total_dev, W, H, jpeg::k444, s, done, tm);
     } else if (format_builds_palette(fmt)) {
         // PAL8 is three dispatches, and the palette build in the middle is one workgroup's serial work (about as long as the rest of the frame)
         const bool gif = fmt == POPPY_FRAME_GIF;

@@ -1,6 +1,7 @@
-// frame_jpeg.cpp — the library's definition of the POPPY_FRAME_JPEG hand-off format in plain C++ (include/poppy_hip.h has the rule): an I420 frame coded as one
-// baseline JFIF file in independent restart intervals of POPPY_JPEG_RESTART_MCUS MCUs.  kernels_frame_jpeg.hip computes the same bytes on the device,
-// tests/test_host_jpeg.py pins these to a numpy restatement of the rule.  Host only, integer arithmetic only.
+// frame_jpeg.cpp — the library's definition of the POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 hand-off formats in plain C++ (include/poppy_hip.h has the rule): an
+// I420 (an I444) frame coded as one baseline JFIF file in independent restart intervals of POPPY_JPEG_RESTART_MCUS (POPPY_JPEG444_RESTART_MCUS) MCUs.  One coder,
+// the sampling its parameter (jpeg_tables.h: Sampling).  kernels_frame_jpeg.hip computes the same bytes on the device, tests/test_host_jpeg.py and
+// tests/test_host_jpeg444.py pin these to numpy restatements of the rule.  Host only, integer arithmetic only.
 #include "frame_limits.h"
 #include <cstring>
 #include <vector>
@@ -14,7 +15,7 @@ constexpr HuffTables kHuff = make_huff();
 
 void put16(uint8_t* p, int v) { p[0] = (uint8_t)(v >> 8); p[1] = (uint8_t)v; }
 
-// the header with the tables of `quality`; width and height 0 (write_header and the pack kernel fill them in)
+// the header with the tables of `quality`, 4:2:0's; width and height 0 (write_header and the pack kernel fill them in, and the two bytes of the sampling)
 void header_template(int quality, uint8_t* h) {
     static const uint8_t app0[20] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
     memcpy(h, app0, 20);
@@ -119,23 +120,27 @@ void write_header(int quality, int width, int height, uint8_t* dst) {
     put16(dst + kOffSofHeight + 2, width);
 }
 
-// the frame of an I420 frame with restart intervals of `restart_mcus` MCUs (the format's: kRestartMcus; the header's DRI names it); returns `total`
-size_t encode_i420(const uint8_t* i420, int w, int h, int quality, int restart_mcus, uint8_t* dst) {
-    const int cw = (w + 1) / 2, ch = (h + 1) / 2, mw = (w + 15) / 16, mh = (h + 15) / 16, n_mcu = mw * mh;
-    const uint8_t *yp = i420, *up = yp + (size_t)w * h, *vp = up + (size_t)cw * ch;
+namespace {
+
+// the frame of the planes of sampling `s` with restart intervals of `restart` MCUs (the header's DRI names it); returns `total`
+size_t encode(const uint8_t* planes, int w, int h, int quality, Sampling s, int restart, uint8_t* dst) {
+    const int side = mcu_side(s), mw = (w + side - 1) / side, mh = (h + side - 1) / side, n_mcu = mw * mh;
+    const int cw = s == k444 ? w : (w + 1) / 2, ch = s == k444 ? h : (h + 1) / 2;      // the chroma planes
+    const uint8_t *yp = planes, *up = yp + (size_t)w * h, *vp = up + (size_t)cw * ch;
     QualityTables q;
     fill_quality_tables(quality, &q);
     write_header(quality, w, h, dst + 4);
-    put16(dst + 4 + kOffDri + 4, restart_mcus);
+    dst[4 + kOffSofSampling] = sof_sampling(s);
+    put16(dst + 4 + kOffDri + 4, restart);
     size_t at = kFrameData;
     int zz[64];
-    for (int first = 0, seg = 0; first < n_mcu; first += restart_mcus, ++seg) {
+    for (int first = 0, seg = 0; first < n_mcu; first += restart, ++seg) {
         BitString b;
         int pred[3] = {0, 0, 0};
-        for (int m = first; m < n_mcu && m < first + restart_mcus; ++m) {
+        for (int m = first; m < n_mcu && m < first + restart; ++m) {
             const int mx = m % mw, my = m / mw;
-            for (int k = 0; k < 4; ++k) {
-                code_block_coefficients(yp, w, h, 16 * mx + 8 * (k & 1), 16 * my + 8 * (k >> 1), q, 0, zz);
+            for (int k = 0; k < (s == k444 ? 1 : 4); ++k) {       // the luma blocks: 2 x 2 of them in a 16 x 16 MCU, one in an 8 x 8 MCU
+                code_block_coefficients(yp, w, h, side * mx + 8 * (k & 1), side * my + 8 * (k >> 1), q, 0, zz);
                 code_block(b, zz, &pred[0], 0);
             }
             code_block_coefficients(up, cw, ch, 8 * mx, 8 * my, q, 1, zz);
@@ -146,11 +151,16 @@ size_t encode_i420(const uint8_t* i420, int w, int h, int quality, int restart_m
         b.pad();
         for (uint8_t byte : b.bytes) { dst[at++] = byte; if (byte == 0xFF) dst[at++] = 0; }
         dst[at++] = 0xFF;
-        dst[at++] = first + restart_mcus < n_mcu ? (uint8_t)(0xD0 + (seg & 7)) : (uint8_t)0xD9;
+        dst[at++] = first + restart < n_mcu ? (uint8_t)(0xD0 + (seg & 7)) : (uint8_t)0xD9;
     }
     dst[0] = (uint8_t)at; dst[1] = (uint8_t)(at >> 8); dst[2] = (uint8_t)(at >> 16); dst[3] = (uint8_t)(at >> 24);
     return at;
 }
+
+}  // namespace
+
+size_t encode_i420(const uint8_t* i420, int w, int h, int quality, int restart_mcus, uint8_t* dst) { return encode(i420, w, h, quality, k420, restart_mcus, dst); }
+size_t encode_planes(const uint8_t* planes, int w, int h, int quality, Sampling s, uint8_t* dst) { return encode(planes, w, h, quality, s, restart_mcus(s), dst); }
 
 }  // namespace jpeg
 }  // namespace poppy_hip
@@ -164,7 +174,14 @@ size_t poppy_jpeg_frame_bytes(const uint8_t* frame) {
 int poppy_i420_to_jpeg_frame(const uint8_t* i420, int width, int height, int quality, uint8_t* dst) {
     if (!i420 || !dst || width <= 0 || height <= 0 || quality < 1 || quality > 100) return POPPY_E_ARG;
     if (!jpeg_fits(width, height)) return POPPY_E_UNSUPPORTED;
-    poppy_hip::jpeg::encode_i420(i420, width, height, quality, poppy_hip::jpeg::kRestartMcus, dst);
+    poppy_hip::jpeg::encode_planes(i420, width, height, quality, poppy_hip::jpeg::k420, dst);
+    return POPPY_OK;
+}
+
+int poppy_i444_to_jpeg_frame(const uint8_t* i444, int width, int height, int quality, uint8_t* dst) {
+    if (!i444 || !dst || width <= 0 || height <= 0 || quality < 1 || quality > 100) return POPPY_E_ARG;
+    if (!jpeg_fits(width, height, poppy_hip::jpeg::k444)) return POPPY_E_UNSUPPORTED;
+    poppy_hip::jpeg::encode_planes(i444, width, height, quality, poppy_hip::jpeg::k444, dst);
     return POPPY_OK;
 }
 
@@ -174,6 +191,14 @@ int poppy_bgr_to_jpeg_frame(const uint8_t* bgr, size_t stride, int width, int he
     std::vector<uint8_t> i420(poppy_frame_bytes(POPPY_FRAME_I420, width, height));
     const int rc = poppy_bgr_to_i420(bgr, stride, width, height, i420.data());
     return rc ? rc : poppy_i420_to_jpeg_frame(i420.data(), width, height, quality, dst);
+}
+
+int poppy_bgr_to_jpeg444_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst) {
+    if (!bgr || !dst || width <= 0 || height <= 0 || stride < (size_t)width * 3 || quality < 1 || quality > 100) return POPPY_E_ARG;
+    if (!jpeg_fits(width, height, poppy_hip::jpeg::k444)) return POPPY_E_UNSUPPORTED;
+    std::vector<uint8_t> i444((size_t)width * height * 3);
+    const int rc = poppy_bgr_to_i444(bgr, stride, width, height, i444.data());
+    return rc ? rc : poppy_i444_to_jpeg_frame(i444.data(), width, height, quality, dst);
 }
 
 }  // extern "C"

@@ -17,7 +17,10 @@ inline size_t gif_frame_capacity(size_t w, size_t h) {
 constexpr size_t kGifFrameMinBytes = 776;      // ... and the smallest there is, the same with one byte of payload in one sub-block: 772 + 1 + (1 + 1) + 1
 inline bool coded_length_ok(size_t total, size_t capacity, size_t least = kGifFrameMinBytes) { return total >= least && total <= capacity; }      // a coder's `total`, before that many bytes are copied or read
 // A JPEG-coded frame (POPPY_FRAME_JPEG): `total`, the fixed header, every restart interval at its bound (include/poppy_hip.h has the derivation; jpeg_tables.h) ...
-inline size_t jpeg_frame_capacity(size_t w, size_t h) { return (size_t)poppy_hip::jpeg::frame_capacity(w, h); }
+inline size_t jpeg_frame_capacity(size_t w, size_t h, poppy_hip::jpeg::Sampling s = poppy_hip::jpeg::k420) { return (size_t)poppy_hip::jpeg::frame_capacity(w, h, s); }      // (POPPY_FRAME_JPEG444: k444, twice the blocks)
 constexpr size_t kJpegFrameMinBytes = poppy_hip::jpeg::kFrameMinBytes;      // ... and the smallest: the header, a byte of entropy-coded data, EOI
 // what the format takes: SOF0's 16-bit sides, and a capacity that `total`'s 32 bits hold
-inline bool jpeg_fits(int W, int H) { return W <= 65535 && H <= 65535 && poppy_hip::jpeg::frame_capacity((size_t)W, (size_t)H) <= 0xffffffffull; }
+inline bool jpeg_fits(int W, int H, poppy_hip::jpeg::Sampling s = poppy_hip::jpeg::k420) { return W <= 65535 && H <= 65535 && poppy_hip::jpeg::frame_capacity((size_t)W, (size_t)H, s) <= 0xffffffffull; }
+// the two JPEG formats and the sampling each codes
+inline bool format_is_jpeg(int fmt) { return fmt == POPPY_FRAME_JPEG || fmt == POPPY_FRAME_JPEG444; }
+inline poppy_hip::jpeg::Sampling format_sampling(int fmt) { return fmt == POPPY_FRAME_JPEG444 ? poppy_hip::jpeg::k444 : poppy_hip::jpeg::k420; }

@@ -10,7 +10,7 @@
 //   POPPY_SINK_GIF_GLOBAL  the same for PAL8_SEQ frames: the first frame's palette as the global colour table, local tables only where a frame's palette differs
 //   POPPY_SINK_GIF_CODED   POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames, whose image data arrives coded (frame_gif.cpp, kernels_frame_gif.hip): nothing is coded here
 //   POPPY_SINK_GIF_GLOBAL_CODED  POPPY_SINK_GIF_GLOBAL's file from coded frames (POPPY_FRAME_GIF_SEQ): the first frame's palette as the global table, local tables only where a palette differs
-//   POPPY_SINK_MJPEG  one RIFF AVI file, a `vids` / `MJPG` stream, from POPPY_FRAME_JPEG frames, whose bytes arrive coded (frame_jpeg.cpp, kernels_frame_jpeg.hip)
+//   POPPY_SINK_MJPEG  one RIFF AVI file, a `vids` / `MJPG` stream, from POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames, whose bytes arrive coded (frame_jpeg.cpp, kernels_frame_jpeg.hip)
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "frame_limits.h"
 #include "gif_lzw.h"
@@ -145,16 +145,16 @@ bool avi_head(poppy_sink* s) {
     return fwrite(h, 1, sizeof h, s->f) == sizeof h;
 }
 
-// the width and height that the file's SOF0 names (a walk over the marker segments in front of SOS, inside n bytes); false when there is none
-bool jpeg_sof0_size(const uint8_t* jfif, size_t n, int* w, int* h) {
+// the width and height that the file's SOF0 names, and component 1's sampling byte (a walk over the marker segments in front of SOS, inside n bytes); false when there is none
+bool jpeg_sof0_size(const uint8_t* jfif, size_t n, int* w, int* h, int* sampling) {
     size_t at = 2;
     while (at + 4 <= n && jfif[at] == 0xFF) {
         const int marker = jfif[at + 1];
         const size_t len = (size_t)jfif[at + 2] << 8 | jfif[at + 3];
         if (marker == 0xDA || len < 2 || at + 2 + len > n) return false;
         if (marker == 0xC0) {
-            if (len < 7) return false;
-            *h = jfif[at + 5] << 8 | jfif[at + 6]; *w = jfif[at + 7] << 8 | jfif[at + 8];
+            if (len < 10) return false;
+            *h = jfif[at + 5] << 8 | jfif[at + 6]; *w = jfif[at + 7] << 8 | jfif[at + 8]; *sampling = jfif[at + 11];
             return true;
         }
         at += 2 + len;
@@ -164,11 +164,14 @@ bool jpeg_sof0_size(const uint8_t* jfif, size_t n, int* w, int* h) {
 
 bool mjpeg_frame(poppy_sink* s, const uint8_t* frame) {
     const size_t total = poppy_jpeg_frame_bytes(frame);
-    if (total < 4 + 4 || total > poppy_frame_bytes(POPPY_FRAME_JPEG, s->w, s->h)) return false;
+    const size_t cap420 = poppy_frame_bytes(POPPY_FRAME_JPEG, s->w, s->h);
+    if (total < 4 + 4 || total > poppy_frame_bytes(POPPY_FRAME_JPEG444, s->w, s->h)) return false;      // (the larger of the two capacities)
     const uint8_t* jfif = frame + 4;
     const size_t n = total - 4, pad = n & 1;
-    int w = 0, h = 0;
-    if (jfif[0] != 0xFF || jfif[1] != 0xD8 || !jpeg_sof0_size(jfif, n, &w, &h) || w != s->w || h != s->h) return false;
+    int w = 0, h = 0, sampling = 0;
+    // (the header is read inside the smaller capacity, which every frame's buffer has)
+    if (jfif[0] != 0xFF || jfif[1] != 0xD8 || !jpeg_sof0_size(jfif, n < cap420 - 4 ? n : cap420 - 4, &w, &h, &sampling) || w != s->w || h != s->h) return false;
+    if (total > poppy_frame_bytes(sampling == 0x11 ? POPPY_FRAME_JPEG444 : POPPY_FRAME_JPEG, s->w, s->h)) return false;      // a 4:4:4 frame is held to its own capacity
     // the file with this chunk, the index's chunk header and every index entry stays below 4 GiB
     if (s->at + 8 + n + pad + 8 + 16 * (uint64_t)(s->index.size() / 2 + 1) > 0xffffffffull) return false;
     uint8_t head[8] = {'0', '0', 'd', 'c'};
@@ -212,7 +215,7 @@ size_t poppy_frame_bytes(int format, int width, int height) {
     if (format == POPPY_FRAME_I420) return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2);
     if (format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ) return w * h + 768;
     if (format == POPPY_FRAME_GIF || format == POPPY_FRAME_GIF_SEQ) return gif_frame_capacity(w, h);      // (frame_limits.h, beside the smallest coded frame)
-    if (format == POPPY_FRAME_JPEG) return jpeg_frame_capacity(w, h);
+    if (format_is_jpeg(format)) return jpeg_frame_capacity(w, h, format_sampling(format));
     return 0;
 }
 

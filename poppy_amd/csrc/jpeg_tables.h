@@ -90,18 +90,33 @@ struct QualityTables {
 };
 constexpr uint32_t quant_recip(int q) { return (uint32_t)(((1ull << 32) + 8ull * q - 1) / (8ull * q)); }
 void fill_quality_tables(int quality, QualityTables* t);      // frame_jpeg.cpp
-void write_header(int quality, int width, int height, uint8_t* dst);      // kHeaderBytes bytes
+void write_header(int quality, int width, int height, uint8_t* dst);      // kHeaderBytes bytes (POPPY_FRAME_JPEG's: 4:2:0)
 // the host coder with an interval of its caller's choice (the format's is kRestartMcus; another one is for measuring what the choice costs); returns `total`
 size_t encode_i420(const uint8_t* i420, int w, int h, int quality, int restart_mcus, uint8_t* dst);
 
 constexpr int kRestartMcus = POPPY_JPEG_RESTART_MCUS;
+
+// The sampling of a JPEG hand-off format: POPPY_FRAME_JPEG codes the I420 planes (an MCU is 16 x 16 samples, six blocks), POPPY_FRAME_JPEG444 the I444 planes
+// (8 x 8 samples, three blocks).  Everything else of the two rules is one rule; these are the facts that differ.
+enum Sampling { k420 = 0, k444 = 1 };
+constexpr int kRestartMcus444 = POPPY_JPEG444_RESTART_MCUS;
+constexpr int mcu_blocks(Sampling s) { return s == k444 ? 3 : 6; }
+constexpr int mcu_side(Sampling s) { return s == k444 ? 8 : 16; }      // an MCU's side in samples of the frame
+constexpr int restart_mcus(Sampling s) { return s == k444 ? kRestartMcus444 : kRestartMcus; }
+// the two header bytes in which the formats differ: SOF0 component 1's sampling factors, DRI's low byte (the interval)
+constexpr int kOffSofSampling = 154 + 11, kOffDriLow = 593 + 5;
+constexpr uint8_t sof_sampling(Sampling s) { return s == k444 ? 0x11 : 0x22; }
+static_assert(mcu_blocks(k444) * kRestartMcus444 == mcu_blocks(k420) * kRestartMcus,
+              "a 4:4:4 segment has the blocks of a 4:2:0 segment: POPPY_JPEG_SEGMENT_BYTES bounds it, and the coder's lanes, bit buffer and scratch slot serve both");
+// the host coder of either sampling on its planes (I420 or I444) with the format's interval; returns `total`
+size_t encode_planes(const uint8_t* planes, int w, int h, int quality, Sampling s, uint8_t* dst);
 // the bound of a coded block in bits, of a segment in bytes behind stuffing with its marker, and of a frame (include/poppy_hip.h: Capacity)
 constexpr size_t kBlockBitsMax = 11 + 11 + 63 * (16 + 10);
 constexpr size_t kSegmentBytesMax = POPPY_JPEG_SEGMENT_BYTES;
 static_assert(kSegmentBytesMax == 2 * ((6 * kBlockBitsMax * kRestartMcus + 7) / 8) + 2, "POPPY_JPEG_SEGMENT_BYTES is the header's bound");
-inline size_t mcu_count(size_t w, size_t h) { return ((w + 15) / 16) * ((h + 15) / 16); }
-inline size_t segment_count(size_t w, size_t h) { return (mcu_count(w, h) + kRestartMcus - 1) / kRestartMcus; }
-inline unsigned long long frame_capacity(size_t w, size_t h) { return kFrameData + (unsigned long long)segment_count(w, h) * kSegmentBytesMax; }
+inline size_t mcu_count(size_t w, size_t h, Sampling s = k420) { const size_t m = (size_t)mcu_side(s); return ((w + m - 1) / m) * ((h + m - 1) / m); }
+inline size_t segment_count(size_t w, size_t h, Sampling s = k420) { return (mcu_count(w, h, s) + restart_mcus(s) - 1) / restart_mcus(s); }
+inline unsigned long long frame_capacity(size_t w, size_t h, Sampling s = k420) { return kFrameData + (unsigned long long)segment_count(w, h, s) * kSegmentBytesMax; }
 constexpr size_t kFrameMinBytes = kFrameData + 1 + 2;       // the smallest frame: a byte of entropy data and EOI
 
 }  // namespace jpeg

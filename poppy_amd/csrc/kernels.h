@@ -265,8 +265,14 @@ void launch_gif_pack_seq(const uint8_t* seq_tables, const uint8_t* scratch, uint
 // the quality.  `done` (optional) rides on the second dispatch.
 constexpr size_t kJpegSlotBytes = ((size_t)POPPY_JPEG_SEGMENT_BYTES - 2 + 3) & ~(size_t)3;
 constexpr size_t kJpegTableBytes = sizeof(jpeg::QualityTables);
-size_t jpeg_scratch_bytes(int w, int h);
-void launch_jpeg_code(const uint8_t* i420, const void* tables, uint8_t* scratch, int w, int h, hipStream_t s);
-void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
+// `sm` (jpeg_tables.h: Sampling): k420 codes an I420 frame into POPPY_FRAME_JPEG, k444 an I444 frame into POPPY_FRAME_JPEG444; a segment of either is 48 blocks, so
+// the slot is one size, and the pack kernel writes the two header bytes in which the formats differ.
+size_t jpeg_scratch_bytes(int w, int h, jpeg::Sampling sm);
+void launch_jpeg_code(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
+void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, jpeg::Sampling sm, hipStream_t s, hipEvent_t done = nullptr);
+
+// a frame on the device (tight BGR) -> its I444 planes, 3 * w * h bytes (kernels_frame_i444.hip; poppy_bgr_to_i444 is the host statement): any w, h >= 1; `done`
+// (optional) rides on the dispatch
+void launch_bgr_to_i444(const uint8_t* src, uint8_t* dst, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
 
 }  // namespace poppy_hip

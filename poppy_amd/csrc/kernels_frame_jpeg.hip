@@ -1,6 +1,8 @@
 // kernels_frame_jpeg.hip — an I420 frame on the device (kernels_frame_format.hip) -> POPPY_FRAME_JPEG for the writer hand-off (include/poppy_hip.h has the rule):
 // one baseline JFIF file, coded in independent restart intervals of POPPY_JPEG_RESTART_MCUS MCUs.  poppy_i420_to_jpeg_frame (frame_jpeg.cpp) is the host
-// statement; the bytes are equal.
+// statement; the bytes are equal.  The same two kernels code POPPY_FRAME_JPEG444 from the I444 planes (kernels_frame_i444.hip; poppy_i444_to_jpeg_frame): the
+// coder is a template over the sampling (jpeg_tables.h: Sampling), which decides the blocks of an MCU (6 or 3), the MCUs of a segment (8 or 16: 48 lanes
+// either way), each block's plane and origin and which lane holds the previous block of the same component.  Everything behind the DC difference is one code.
 //
 // Two dispatches behind k_bgr_to_i420, no host round trip:
 //   k_jpeg_code  a segment per wave, a workgroup of one wave (no workgroup barrier).  Nothing in a segment is serial but the bit positions, so a LANE takes a BLOCK:
@@ -29,6 +31,7 @@ using namespace jpeg;
 
 constexpr int kSegLanes = 6 * kRestartMcus;                 // blocks of a full segment
 static_assert(kSegLanes <= 64, "a segment's blocks are the lanes of one wave");
+static_assert(mcu_blocks(k444) * kRestartMcus444 == kSegLanes, "... of either sampling: the bit buffer and the scratch slot below are sized for them");
 constexpr int kBitWords = (int)((6 * kBlockBitsMax * kRestartMcus + 31) / 32) + 2;      // the segment's bits at their bound, the word a code may spill into
 static_assert(kJpegSlotBytes >= 2 * ((6 * kBlockBitsMax * kRestartMcus + 7) / 8), "a slot holds a segment with every byte stuffed");
 
@@ -119,24 +122,27 @@ __device__ __forceinline__ uint32_t code_block(CoderLds& L, int lane, int table,
 
 }  // namespace
 
+template <Sampling S>
 __global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i420, const QualityTables* __restrict__ tables, uint8_t* __restrict__ scratch,
                                                   uint32_t* __restrict__ lengths, int w, int h, int mw, int n_mcu) {
+    constexpr int kBlocks = mcu_blocks(S), kMcus = restart_mcus(S);
     __shared__ CoderLds L;
     const int lane = threadIdx.x, seg = blockIdx.x;
     for (int i = lane; i < 512; i += 64) L.ac[i >> 8][i & 255] = c_huff.ac[i >> 8][i & 255];
     if (lane < 32) L.dc[lane >> 4][lane & 15] = c_huff.dc[lane >> 4][lane & 15];
     for (int i = lane; i < 128; i += 64) L.q[i >> 6][i & 63] = make_uint2(tables->bias[i >> 6][i & 63], tables->recip[i >> 6][i & 63]);
     wave_sync();
-    const int first = seg * kRestartMcus, mcus = min(kRestartMcus, n_mcu - first);
-    const int m_in = lane / 6, b = lane - 6 * m_in, table = b >= 4;
+    const int first = seg * kMcus, mcus = min(kMcus, n_mcu - first);
+    const int m_in = lane / kBlocks, b = lane - kBlocks * m_in, table = S == k444 ? b >= 1 : b >= 4;
     const bool active = m_in < mcus;
     int dc = 0;
     if (active) {
         const int m = first + m_in, my = m / mw, mx = m - my * mw;
-        const int cw = (w + 1) / 2, ch = (h + 1) / 2;
+        // the block's plane, that plane's size and the block's origin in it.  4:4:4: (the I444 planes) every plane w x h, every block at (8 mx, 8 my)
+        const int cw = S == k444 ? w : (w + 1) / 2, ch = S == k444 ? h : (h + 1) / 2;
         const int pw = table ? cw : w, ph = table ? ch : h;
-        const int x0 = table ? 8 * mx : 16 * mx + 8 * (b & 1), y0 = table ? 8 * my : 16 * my + 8 * (b >> 1);
-        const uint8_t* plane = i420 + (b < 4 ? (size_t)0 : (size_t)w * h + (b == 5 ? (size_t)cw * ch : (size_t)0));
+        const int x0 = table || S == k444 ? 8 * mx : 16 * mx + 8 * (b & 1), y0 = table || S == k444 ? 8 * my : 16 * my + 8 * (b >> 1);
+        const uint8_t* plane = i420 + (!table ? (size_t)0 : (size_t)w * h + (b == kBlocks - 1 ? (size_t)cw * ch : (size_t)0));
         int f[64];
         #pragma unroll
         for (int y = 0; y < 8; ++y) {
@@ -165,9 +171,10 @@ __global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i4
         dc = quantise_block(L, f, table, lane, std::make_integer_sequence<int, 64>());
     }
     // the previous block of the same component: the luma block before, Y11 of the MCU before for Y00, the same chroma block of the MCU before; the segment's first: 0
-    const int from = b >= 4 ? lane - 6 : b == 0 ? lane - 3 : lane - 1;
+    // (4:4:4: the same block of the MCU before, three lanes down)
+    const int from = S == k444 ? lane - 3 : b >= 4 ? lane - 6 : b == 0 ? lane - 3 : lane - 1;
     const int before = __shfl(dc, max(from, 0), 64);
-    const int diff = dc - ((b == 0 || b >= 4) && m_in == 0 ? 0 : before);
+    const int diff = dc - ((S == k444 || b == 0 || b >= 4) && m_in == 0 ? 0 : before);
     const uint32_t n_bits = active ? code_block<false>(L, lane, table, diff, 0) : 0;
     uint32_t incl = n_bits;
     #pragma unroll
@@ -200,7 +207,7 @@ constexpr int kPackGroup = 8;                               // segments per work
 }
 
 __global__ void __launch_bounds__(256) k_jpeg_pack(const uint8_t* __restrict__ scratch, const uint32_t* __restrict__ lengths, const QualityTables* __restrict__ tables,
-                                                   int n_seg, int w, int h, uint8_t* __restrict__ frame, uint32_t* __restrict__ total_host) {
+                                                   int n_seg, int w, int h, int sof_sampling, int restart, uint8_t* __restrict__ frame, uint32_t* __restrict__ total_host) {
     __shared__ unsigned long long s_part[2][4];
     __shared__ uint32_t s_off[kPackGroup + 1];
     const int t = threadIdx.x, first = blockIdx.x * kPackGroup;
@@ -228,8 +235,9 @@ __global__ void __launch_bounds__(256) k_jpeg_pack(const uint8_t* __restrict__ s
     }
     if (blockIdx.x == 0) {
         for (int i = t; i < kHeaderBytes; i += 256) {
-            const int k = i - kOffSofHeight;                // SOF0's height and width, big-endian
-            frame[4 + i] = k == 0 ? (uint8_t)(h >> 8) : k == 1 ? (uint8_t)h : k == 2 ? (uint8_t)(w >> 8) : k == 3 ? (uint8_t)w : tables->header[i];
+            const int k = i - kOffSofHeight;                // SOF0's height and width, big-endian; the two bytes of the sampling: component 1's factors, DRI's interval
+            frame[4 + i] = k == 0 ? (uint8_t)(h >> 8) : k == 1 ? (uint8_t)h : k == 2 ? (uint8_t)(w >> 8) : k == 3 ? (uint8_t)w :
+                           i == kOffSofSampling ? (uint8_t)sof_sampling : i == kOffDriLow ? (uint8_t)restart : tables->header[i];
         }
         if (t == 0) {
             *(uint32_t*)frame = (uint32_t)total;            // (the frame's buffer comes from hipMalloc: aligned)
@@ -242,18 +250,20 @@ namespace {
 uint32_t* jpeg_lengths(uint8_t* scratch, size_t n_seg) { return (uint32_t*)(scratch + n_seg * kJpegSlotBytes); }
 }
 
-size_t jpeg_scratch_bytes(int w, int h) { return segment_count((size_t)w, (size_t)h) * (kJpegSlotBytes + 4) + 16; }
+size_t jpeg_scratch_bytes(int w, int h, Sampling sm) { return segment_count((size_t)w, (size_t)h, sm) * (kJpegSlotBytes + 4) + 16; }
 
-void launch_jpeg_code(const uint8_t* i420, const void* tables, uint8_t* scratch, int w, int h, hipStream_t s) {
-    const size_t n_seg = segment_count((size_t)w, (size_t)h);
-    hipLaunchKernelGGL(k_jpeg_code, dim3((unsigned)n_seg), dim3(64), 0, s, i420, (const QualityTables*)tables, scratch, jpeg_lengths(scratch, n_seg), w, h, (w + 15) / 16,
-                       (int)mcu_count((size_t)w, (size_t)h));
+void launch_jpeg_code(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
+    const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
+    const int mw = (w + mcu_side(sm) - 1) / mcu_side(sm);
+    hipLaunchKernelGGL(sm == k444 ? k_jpeg_code<k444> : k_jpeg_code<k420>, dim3((unsigned)n_seg), dim3(64), 0, s, planes, (const QualityTables*)tables, scratch,
+                       jpeg_lengths(scratch, n_seg), w, h, mw, (int)mcu_count((size_t)w, (size_t)h, sm));
 }
 
-void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done) {
-    const size_t n_seg = segment_count((size_t)w, (size_t)h);
+void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, hipStream_t s, hipEvent_t done) {
+    const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
     hipExtLaunchKernelGGL(k_jpeg_pack, dim3((unsigned)((n_seg + kPackGroup - 1) / kPackGroup)), dim3(256), 0, s, nullptr, done, 0, scratch,
-                          jpeg_lengths(const_cast<uint8_t*>(scratch), n_seg), (const QualityTables*)tables, (int)n_seg, w, h, frame, total_host);
+                          jpeg_lengths(const_cast<uint8_t*>(scratch), n_seg), (const QualityTables*)tables, (int)n_seg, w, h, (int)sof_sampling(sm), restart_mcus(sm), frame,
+                          total_host);
 }
 
 }  // namespace poppy_hip

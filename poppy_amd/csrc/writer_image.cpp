@@ -31,16 +31,17 @@ static int gif_from_device_pal8(poppy_hip_ctx* c, const uint8_t* d_pal8, int W, 
 }
 
 // an I420 frame in device memory -> its POPPY_FRAME_JPEG frame in `host` (exactly `total` bytes) at the quality that `d_tables` name, on the context's stream and
-// waited for: the frames that no slot renders, and poppy_hip_i420_to_jpeg_frame.  The buffers live for the call.
-static int jpeg_from_device_i420(poppy_hip_ctx* c, const uint8_t* d_i420, const void* d_tables, int W, int H, std::vector<uint8_t>& host) {
-    const size_t cap = poppy_frame_bytes(POPPY_FRAME_JPEG, W, H);
+// waited for: the frames that no slot renders, and poppy_hip_i420_to_jpeg_frame.  The buffers live for the call.  sm == k444: an I444 frame -> its
+// POPPY_FRAME_JPEG444 frame (poppy_hip_i444_to_jpeg_frame).
+static int jpeg_from_device_planes(poppy_hip_ctx* c, const uint8_t* d_i420, const void* d_tables, int W, int H, jpeg::Sampling sm, std::vector<uint8_t>& host) {
+    const size_t cap = jpeg_frame_capacity((size_t)W, (size_t)H, sm);
     CallBuffers held;
     uint8_t *work = nullptr, *frame = nullptr;
-    hipError_t e = held.alloc(&work, jpeg_scratch_bytes(W, H));
+    hipError_t e = held.alloc(&work, jpeg_scratch_bytes(W, H, sm));
     if (e == hipSuccess) e = held.alloc(&frame, cap + 16);
     uint32_t total = 0;
     if (e == hipSuccess) {
-        enqueue_jpeg_coding(d_i420, d_tables, work, frame, nullptr, W, H, c->stream, nullptr, nullptr);
+        enqueue_jpeg_coding(d_i420, d_tables, work, frame, nullptr, W, H, sm, c->stream, nullptr, nullptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
@@ -70,7 +71,14 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
     *stride = writer_stride(fmt, W);
     const uint8_t* d_frame = d_bgr;
     if (fmt != POPPY_FRAME_BGR) {                                  // converted into the context's scratch: the slots' launches on other buffers
-        // (a coded format: its raster form into the scratch — PAL8 for GIF, I420 for JPEG —, then the coder on buffers that live for the call)
+        // (a coded format: its raster form into the scratch — PAL8 for GIF, I420 for JPEG, the I444 planes for JPEG444 —, then the coder on buffers that live for the call)
+        if (fmt == POPPY_FRAME_JPEG444) {                          // (I444 is no format of its own: the kernel is launched here)
+            { int rc = ensure_jpeg_tables(c); if (rc) return rc; }
+            HIPCHK(c, c->fmt_scratch.reserve((size_t)W * H * 3 + 16, c->stream));
+            launch_bgr_to_i444(d_bgr, c->fmt_scratch.p, W, H, c->stream);
+            HIPCHK(c, hipGetLastError());
+            return jpeg_from_device_planes(c, c->fmt_scratch.p, c->jpeg_tables, W, H, jpeg::k444, host);
+        }
         const bool gif = fmt == POPPY_FRAME_GIF, jpeg = fmt == POPPY_FRAME_JPEG;
         const int raster = gif ? POPPY_FRAME_PAL8 : jpeg ? POPPY_FRAME_I420 : fmt;
         if (format_builds_palette(fmt)) { int rc = alloc_zeroed_tables(c, &c->fmt_scratch_tables, kPal8TableBytes); if (rc) return rc; }
@@ -81,7 +89,7 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
         enqueue_conversion(raster, WriterGeom{W, H}, d_bgr, W, H, scratch, c->stream, nullptr, nullptr);
         HIPCHK(c, hipGetLastError());
         if (gif) return gif_from_device_pal8(c, c->fmt_scratch.p, W, H, host);
-        if (jpeg) return jpeg_from_device_i420(c, c->fmt_scratch.p, c->jpeg_tables, W, H, host);
+        if (jpeg) return jpeg_from_device_planes(c, c->fmt_scratch.p, c->jpeg_tables, W, H, jpeg::k420, host);
         d_frame = c->fmt_scratch.p;
     }
     host.resize(poppy_frame_bytes(fmt, W, H));
@@ -101,6 +109,7 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
     int rc = format_is_sequence(fmt) ? pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, pal8.empty() ? tmp.data() : pal8.data()) :
                    fmt == POPPY_FRAME_GIF ? poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data()) :
                    fmt == POPPY_FRAME_JPEG ? poppy_bgr_to_jpeg_frame(bgr, stride, W, H, c->jpeg_quality, tmp.data()) :
+                   fmt == POPPY_FRAME_JPEG444 ? poppy_bgr_to_jpeg444_frame(bgr, stride, W, H, c->jpeg_quality, tmp.data()) :
                    fmt == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
     if (rc == POPPY_OK && !pal8.empty()) rc = poppy_pal8_to_gif_frame(pal8.data(), W, H, tmp.data());
     if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
@@ -188,24 +197,53 @@ int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* c, const uint8_t* pal8, int W, in
     return rc;
 }
 
-int poppy_hip_i420_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i420, int W, int H, int quality, uint8_t* dst) {
+// the body of poppy_hip_i420_to_jpeg_frame and poppy_hip_i444_to_jpeg_frame: the planes of format `fmt`'s sampling up, the two kernels, `total` bytes down
+static int jpeg_code_host_planes(poppy_hip_ctx* c, int fmt, const uint8_t* i420, int W, int H, int quality, uint8_t* dst) {
     if (!c) return POPPY_E_ARG;
     if (!i420 || !dst || W <= 0 || H <= 0 || quality < 1 || quality > 100) return fail(c, POPPY_E_ARG, "bad arguments");
-    if (const char* why = format_refuses(POPPY_FRAME_JPEG, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    if (const char* why = format_refuses(fmt, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bytes = poppy_frame_bytes(POPPY_FRAME_I420, W, H);
+    const size_t bytes = fmt == POPPY_FRAME_JPEG444 ? (size_t)W * H * 3 : poppy_frame_bytes(POPPY_FRAME_I420, W, H);
     jpeg::QualityTables t;
     jpeg::fill_quality_tables(quality, &t);
-    CallBuffers held;                                              // (jpeg_from_device_i420 waits for the stream before it returns)
+    CallBuffers held;                                              // (jpeg_from_device_planes waits for the stream before it returns)
     uint8_t *d_i420 = nullptr, *d_tables = nullptr;
     HIPCHK(c, held.alloc(&d_i420, bytes + 16));
     HIPCHK(c, held.alloc(&d_tables, kJpegTableBytes));
     if (hipMemcpy(d_i420, i420, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_tables, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(c, POPPY_E_DEVICE, "upload of the I420 frame failed");
+        return fail(c, POPPY_E_DEVICE, "upload of the planes failed");
     std::vector<uint8_t> host;
-    const int rc = jpeg_from_device_i420(c, d_i420, d_tables, W, H, host);
+    const int rc = jpeg_from_device_planes(c, d_i420, d_tables, W, H, format_sampling(fmt), host);
     if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
     return rc;
+}
+
+int poppy_hip_i420_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i420, int W, int H, int quality, uint8_t* dst) {
+    return jpeg_code_host_planes(c, POPPY_FRAME_JPEG, i420, W, H, quality, dst);
+}
+
+int poppy_hip_i444_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i444, int W, int H, int quality, uint8_t* dst) {
+    return jpeg_code_host_planes(c, POPPY_FRAME_JPEG444, i444, W, H, quality, dst);
+}
+
+// a host frame up, the I444 kernel, the planes down, on buffers that live for the call; the source's place behind a 256-byte boundary is the row pad's low bits
+// (include/poppy_hip.h), as in scale_host_frame
+int poppy_hip_bgr_to_i444(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* dst) {
+    if (!c) return POPPY_E_ARG;
+    if (!bgr || !dst || W <= 0 || H <= 0 || stride < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t row = (size_t)W * 3, shift = (stride - row) % 16, bytes = row * H;
+    CallBuffers held;
+    uint8_t *d_src = nullptr, *d_dst = nullptr;
+    hipError_t e = held.alloc(&d_src, bytes + shift + 16);
+    if (e == hipSuccess) e = held.alloc(&d_dst, bytes + 16);
+    if (e == hipSuccess) e = copy_rows_async(d_src + shift, row, bgr, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { launch_bgr_to_i444(d_src + shift, d_dst, W, H, c->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, d_dst, bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go (`held`, at the return)
+    if (e == hipSuccess) e = e_sync;
+    if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("BGR to I444: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    return POPPY_OK;
 }
 
 }  // extern "C"
