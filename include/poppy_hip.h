@@ -308,7 +308,42 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * poppy_bgr_to_i444 followed by it; both refuse what poppy_i420_to_jpeg_frame and poppy_bgr_to_jpeg_frame refuse.  poppy_hip_i444_to_jpeg_frame codes a host I444
  * frame on the context's GPU at the given quality (upload, the two kernels, download of `total` bytes): the same bytes; no resident pair needed, none disturbed.
  * poppy_hip_set_jpeg_quality and poppy_hip_pool_set_jpeg_quality serve both formats.  The format applies wherever JPEG applies, under poppy_hip_set_frame_scale
- * and poppy_hip_set_frame_size as the host statement at the writer's geometry, and stays BGR wherever JPEG stays BGR.  */
+ * and poppy_hip_set_frame_size as the host statement at the writer's geometry, and stays BGR wherever JPEG stays BGR.
+ *
+ * POPPY_FRAME_PNG: the frame coded on the GPU as one PNG file, LOSSLESS: the file decodes to exactly the frame's pixels, at 1.5 - 3 times fewer bytes than BGR on
+ * photograph-like frames.  Its value is 1024, and POPPY_SINK_PNG is 1024; 1023 and 1025 stay unknown in both enums.  Layout, little-endian:
+ *     bytes 0..3     total: the whole frame's length in bytes, these four included (poppy_png_frame_bytes reads it)
+ *     bytes 4..      one complete PNG file
+ * The writer gets (frame, width, height, stride = 0).  Integer arithmetic throughout; the host statement and the GPU agree byte for byte.
+ *   File.  The 8-byte signature; IHDR (width, height, bit depth 8, colour type 2 = RGB, compression 0, filter 0, interlace 0); ONE IDAT holding the whole zlib
+ *      stream; IEND.  No ancillary chunks.  Chunk CRCs are the PNG specification's (CRC-32 over type and data).  IDAT's length field is at frame offset 37, the
+ *      zlib stream begins at 45, the deflate bits at 47.
+ *   Filtered stream.  n = h * (1 + 3 w) bytes: every row is its filter-type byte and 3 w filtered bytes of R, G, B (the frame's BGR swapped; bpp = 3).  All five
+ *      filter types of the PNG specification (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth) are evaluated for EVERY row from the original pixels; the row above row 0
+ *      and the pixel left of column 0 are zeros; Average is floor((a + b) / 2); Paeth takes the specification's tie order a, b, c.  A type's score is the sum over
+ *      the row's 3 w filtered bytes v of min(v, 256 - v); the smallest score wins, ties go to the lowest type number.
+ *   Segments.  The filtered stream is one linear run, cut into segments of POPPY_PNG_SEGMENT_BYTES = 8192 bytes whatever the rows; the last may be shorter.  The
+ *      length is a constant of the FORMAT ("PNG hand-off", says what stands behind its value).
+ *   Tables.  POPPY_PNG_TABLES = 8 code-length tables over 257 symbols, literal 0..255 and end-of-block 256; no length or distance symbol is ever emitted: there is
+ *      no LZ77 matching.  The tables are constants of the format, committed in poppy_amd/csrc/png_tables.h (poppy_png_table hands them out): table k is an
+ *      optimal length-limited (15 bits) prefix code over the weights w(v) = max(1, floor(2^40 * theta_k^m)), m = min(v, 256 - v), theta_k = 1/4, 1/2, 3/4, 7/8,
+ *      15/16, 31/32, 63/64, 1, end-of-block weighing 1 (tools/gen_png_tables.py states the construction and its tie rule; the committed header is the
+ *      definition).  Codes are deflate's canonical codes from the lengths.
+ *   Block header.  Each table has a constant header bit string of H_k bits, in the same file: BFINAL (bit 0), BTYPE = 10, HLIT = 0 (257 codes), HDIST = 0 with one
+ *      distance code of length 1, HCLEN, the code-length code's lengths (themselves limited to 7 bits), then the 258 lengths each sent as itself (no run symbols).
+ *   Table choice.  Segment s takes the k that minimises H_k + sum of len_k[v] over its bytes + len_k[256]; ties go to the lowest k.
+ *   Stream.  78 01; then for every segment in order, NOT byte-aligned, packed from the least significant bit as deflate packs (Huffman codes most significant bit
+ *      first, everything else least significant first): the table's header with BFINAL = 1 only in the last segment, the segment's literal codes, end-of-block;
+ *      then zero bits to a byte boundary; then the Adler-32 of the filtered stream, big-endian.
+ *   Capacity.  poppy_frame_bytes(POPPY_FRAME_PNG, w, h) is an upper bound for any content: table 7 is always a candidate, so a segment of s bytes costs at most
+ *      H_7 + L7 * s + len_7[256] bits, L7 <= 9 being table 7's longest literal; summed over the segments and rounded up to bytes, plus 67: `total`, 8 bytes of
+ *      signature, 25 of IHDR, 12 of IDAT's framing, 2 of zlib header, 4 of Adler-32 and 12 of IEND.  About 1.13 bytes per byte of BGR.
+ *   Limits (POPPY_E_UNSUPPORTED, before any state changes): a capacity of 2^31 bytes or more (IDAT's length field and `total`); poppy_frame_bytes gives 0 for such a size.
+ * poppy_bgr_to_png_frame is the host statement (dst: the capacity; POPPY_E_ARG for a null pointer, an empty frame or stride < 3 * width).  poppy_png_table gives
+ * table k's 257 lengths and its header bit string (header_bits: POPPY_PNG_HEADER_BYTES bytes, bit i of the string is bit i mod 8 of byte i / 8; either output
+ * may be null; POPPY_E_ARG for k outside 0..7).  poppy_hip_bgr_to_png_frame codes a host frame on the context's GPU (upload, the kernels, download of `total`
+ * bytes): the same bytes; it needs no resident pair and disturbs none, and places its source as poppy_hip_bgr_downscale does.  The format applies wherever JPEG
+ * applies, under poppy_hip_set_frame_scale and poppy_hip_set_frame_size as the host statement at the writer's geometry, and stays BGR wherever JPEG stays BGR.  */
 #define POPPY_PAL8_MAX_PIXELS (1 << 24)
 #define POPPY_PAL8_SEQ_MAX_PIXELS (1ull << 32)
 #define POPPY_GIF_SEGMENT_PIXELS 2048
@@ -319,8 +354,11 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
 #define POPPY_JPEG_SEGMENT_BYTES (2 * ((6 * 1660 * POPPY_JPEG_RESTART_MCUS + 7) / 8) + 2)
 #define POPPY_JPEG444_RESTART_MCUS 16      /* (3 * 16 blocks = 6 * POPPY_JPEG_RESTART_MCUS: poppy_amd/csrc/jpeg_tables.h asserts it) */
 #define POPPY_JPEG_QUALITY_DEFAULT 90
+#define POPPY_PNG_SEGMENT_BYTES 8192
+#define POPPY_PNG_TABLES 8
+#define POPPY_PNG_HEADER_BYTES 236      /* (any header of the form fits: 17 + 19 * 3 + 258 * 7 bits) */
 enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128, POPPY_FRAME_JPEG = 256,
-       POPPY_FRAME_JPEG444 = 512 };
+       POPPY_FRAME_JPEG444 = 512, POPPY_FRAME_PNG = 1024 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
@@ -342,6 +380,10 @@ int poppy_hip_bgr_to_i444(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride,
 int poppy_i444_to_jpeg_frame(const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
 int poppy_bgr_to_jpeg444_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst);
 int poppy_hip_i444_to_jpeg_frame(poppy_hip_ctx* ctx, const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
+size_t poppy_png_frame_bytes(const uint8_t* frame);
+int poppy_png_table(int k, uint8_t lengths[257], uint8_t* header_bits, int* n_header_bits);
+int poppy_bgr_to_png_frame(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_hip_bgr_to_png_frame(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 /* Scaled hand-off: frames rendered at the pair's resolution and handed to the writer scaled down by a whole factor, on the GPU, in front of the format
  * conversion.  The pair's resolution decides the keypoints, the mesh and the morph; the scale only decides what crosses the link and what the writer gets.
  *   The rule.  A factor s is a whole number from 1 to POPPY_FRAME_SCALE_MAX = 8; 1, the default, is the identity.  A width x height BGR frame becomes
@@ -795,11 +837,14 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * file past 4 GiB fails the sink (a plain AVI has 32-bit lengths).  A frame of any other format fails this sink, and a JPEG frame fails every other sink.
  * POPPY_FRAME_JPEG444 frames are taken as well, in any mix with POPPY_FRAME_JPEG frames (the `MJPG` stream does not care): a frame whose SOF0 gives component 1
  * the sampling byte 0x11 is held to POPPY_FRAME_JPEG444's capacity, any other to POPPY_FRAME_JPEG's; nothing else about the sink differs.
+ * PNG: one PNG file per frame from POPPY_FRAME_PNG frames as they come; `path` follows PPM's %d rule exactly.  The file holds the frame's bytes 4 .. total as they
+ * are.  The stride must be 0, bytes 4..11 the PNG signature, IHDR must name the sink's width and height, and `total` must be inside the format's capacity.  A frame
+ * of any other format fails this sink, and a PNG frame fails every other sink.
  * The BGR sinks take frames with stride >= 3 * width, the I420 and GIF sinks frames with stride == width: a frame of another format fails the
  * sink where its stride tells (a BGR frame at the I420 or GIF sink, an I420 or PAL8 frame at a BGR sink); a writer must match the context's format.
  * poppy_sink_close returns the number of frames written, or a negative status if a write failed or a frame had another geometry.   */
 typedef struct poppy_sink poppy_sink;
-enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8, POPPY_SINK_GIF_GLOBAL = 16, POPPY_SINK_GIF_CODED = 64, POPPY_SINK_GIF_GLOBAL_CODED = 128, POPPY_SINK_MJPEG = 256 };
+enum { POPPY_SINK_RAW = 0, POPPY_SINK_PPM = 1, POPPY_SINK_Y4M = 2, POPPY_SINK_Y4M420 = 3, POPPY_SINK_GIF = 8, POPPY_SINK_GIF_GLOBAL = 16, POPPY_SINK_GIF_CODED = 64, POPPY_SINK_GIF_GLOBAL_CODED = 128, POPPY_SINK_MJPEG = 256, POPPY_SINK_PNG = 1024 };
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den);
 void poppy_sink_write(void* sink, const uint8_t* bgr, int width, int height, size_t stride);
 int poppy_sink_close(poppy_sink* sink);

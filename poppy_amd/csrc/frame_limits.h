@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "jpeg_tables.h"
+#include "png_tables.h"
 
 // poppy_hip_set_frame_size's rule (include/poppy_hip.h): ow x oh is no larger than W x H and at most POPPY_FRAME_SCALE_MAX times smaller per side (so W, H >= 1 too)
 inline bool size_admits(int W, int H, int ow, int oh) {
@@ -24,3 +25,8 @@ inline bool jpeg_fits(int W, int H, poppy_hip::jpeg::Sampling s = poppy_hip::jpe
 // the two JPEG formats and the sampling each codes
 inline bool format_is_jpeg(int fmt) { return fmt == POPPY_FRAME_JPEG || fmt == POPPY_FRAME_JPEG444; }
 inline poppy_hip::jpeg::Sampling format_sampling(int fmt) { return fmt == POPPY_FRAME_JPEG444 ? poppy_hip::jpeg::k444 : poppy_hip::jpeg::k420; }
+// A PNG-coded frame (POPPY_FRAME_PNG): `total`, the file's fixed parts and every segment on table 7 at its longest literal (include/poppy_hip.h has the derivation;
+// png_tables.h); what the format takes is a capacity below 2^31 bytes, which IDAT's length field and `total` hold; the smallest frame has one byte of deflate data
+inline bool png_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
+inline size_t png_frame_capacity(size_t w, size_t h) { return (size_t)poppy_hip::png::frame_capacity(w, h); }
+constexpr size_t kPngFrameMinBytes = poppy_hip::png::kFrameMinBytes;

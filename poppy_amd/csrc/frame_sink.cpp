@@ -11,6 +11,7 @@
 //   POPPY_SINK_GIF_CODED   POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames, whose image data arrives coded (frame_gif.cpp, kernels_frame_gif.hip): nothing is coded here
 //   POPPY_SINK_GIF_GLOBAL_CODED  POPPY_SINK_GIF_GLOBAL's file from coded frames (POPPY_FRAME_GIF_SEQ): the first frame's palette as the global table, local tables only where a palette differs
 //   POPPY_SINK_MJPEG  one RIFF AVI file, a `vids` / `MJPG` stream, from POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames, whose bytes arrive coded (frame_jpeg.cpp, kernels_frame_jpeg.hip)
+//   POPPY_SINK_PNG   one PNG file per frame from POPPY_FRAME_PNG frames, whose bytes arrive coded (frame_png.cpp, kernels_frame_png.hip); the path as under PPM
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "frame_limits.h"
 #include "gif_lzw.h"
@@ -24,9 +25,9 @@
 struct poppy_sink {
     int format = 0, w = 0, h = 0, frames = 0;
     bool failed = false;
-    std::string path;                  // PPM: the text before the pattern's conversion
-    std::string tail;                  // PPM: the text after it
-    int pad = 0; bool zero = false;    // PPM: width and zero flag of the conversion (%d, %5d, %05d)
+    std::string path;                  // PPM, PNG: the text before the pattern's conversion
+    std::string tail;                  // PPM, PNG: the text after it
+    int pad = 0; bool zero = false;    // PPM, PNG: width and zero flag of the conversion (%d, %5d, %05d)
     FILE* f = nullptr;
     std::vector<uint8_t> row;
     int delay_cs = 3;                  // GIF: the frames' delay in centiseconds
@@ -184,6 +185,27 @@ bool mjpeg_frame(poppy_sink* s, const uint8_t* frame) {
     return true;
 }
 
+// the name of the sink's next numbered file (PPM, PNG)
+std::string numbered_name(const poppy_sink* s) {
+    std::string num = std::to_string(s->frames);
+    if ((int)num.size() < s->pad) num.insert(0, (size_t)s->pad - num.size(), s->zero ? '0' : ' ');
+    return s->path + num + s->tail;
+}
+
+// a POPPY_FRAME_PNG frame: its bytes 4 .. total as one file, once the signature, IHDR's size and `total` are what the sink's size allows
+bool png_frame(poppy_sink* s, const uint8_t* frame) {
+    using namespace poppy_hip::png;
+    const size_t total = poppy_png_frame_bytes(frame);
+    if (total < kPngFrameMinBytes || total > poppy_frame_bytes(POPPY_FRAME_PNG, s->w, s->h) || memcmp(frame + kOffSignature, kSignature, 8) != 0) return false;
+    const uint8_t* ihdr = frame + kOffIhdr;
+    const uint32_t w = (uint32_t)ihdr[8] << 24 | (uint32_t)ihdr[9] << 16 | (uint32_t)ihdr[10] << 8 | ihdr[11], h = (uint32_t)ihdr[12] << 24 | (uint32_t)ihdr[13] << 16 | (uint32_t)ihdr[14] << 8 | ihdr[15];
+    if (memcmp(ihdr + 4, "IHDR", 4) != 0 || w != (uint32_t)s->w || h != (uint32_t)s->h) return false;
+    FILE* f = fopen(numbered_name(s).c_str(), "wb");
+    if (!f) return false;
+    const bool ok = fwrite(frame + 4, 1, total - 4, f) == total - 4;
+    return fclose(f) == 0 && ok;
+}
+
 // the index behind the last chunk, then the lengths and counts that were not known at the head
 bool avi_close(poppy_sink* s) {
     const uint32_t frames = (uint32_t)(s->index.size() / 2);
@@ -216,6 +238,7 @@ size_t poppy_frame_bytes(int format, int width, int height) {
     if (format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ) return w * h + 768;
     if (format == POPPY_FRAME_GIF || format == POPPY_FRAME_GIF_SEQ) return gif_frame_capacity(w, h);      // (frame_limits.h, beside the smallest coded frame)
     if (format_is_jpeg(format)) return jpeg_frame_capacity(w, h, format_sampling(format));
+    if (format == POPPY_FRAME_PNG) return png_fits(width, height) ? png_frame_capacity(w, h) : 0;      // (nothing to size where the format refuses)
     return 0;
 }
 
@@ -248,10 +271,10 @@ int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, 
 }
 
 poppy_sink* poppy_sink_open(const char* path, int format, int width, int height, int fps_num, int fps_den) {
-    if (!path || width <= 0 || height <= 0 || (!sink_is_gif(format) && format != POPPY_SINK_MJPEG && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
+    if (!path || width <= 0 || height <= 0 || (!sink_is_gif(format) && format != POPPY_SINK_MJPEG && format != POPPY_SINK_PNG && (format < POPPY_SINK_RAW || format > POPPY_SINK_Y4M420))) return nullptr;
     poppy_sink* s = new poppy_sink();
     s->format = format; s->w = width; s->h = height; s->path = path;
-    if (format == POPPY_SINK_PPM) {
+    if (format == POPPY_SINK_PPM || format == POPPY_SINK_PNG) {
         // The pattern is parsed here, never handed to printf: exactly one conversion of the form %d / %<width>d / %0<width>d ("%%" is a
         // literal percent sign); anything else — %s, %n, a second conversion, no conversion at all (every frame would overwrite the
         // same file) — is refused.
@@ -273,7 +296,8 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
         s->path = head; s->tail = tail;
     }
     if ((sink_is_gif(format) || format == POPPY_SINK_MJPEG) && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen, JPEG's 16-bit SOF0: every write fails, close says so
-    if (format != POPPY_SINK_PPM) {
+    if (format == POPPY_SINK_PNG && !png_fits(width, height)) { s->failed = true; return s; }      // no such frame: every write fails, close says so
+    if (format != POPPY_SINK_PPM && format != POPPY_SINK_PNG) {
         s->f = fopen(path, "wb");
         if (!s->f) { delete s; return nullptr; }
         if (format == POPPY_SINK_Y4M)
@@ -303,6 +327,10 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
         if (!bgr || width != s->w || height != s->h || stride != 0 || !mjpeg_frame(s, bgr)) s->failed = true; else ++s->frames;
         return;
     }
+    if (s->format == POPPY_SINK_PNG) {
+        if (!bgr || width != s->w || height != s->h || stride != 0 || !png_frame(s, bgr)) s->failed = true; else ++s->frames;
+        return;
+    }
     if (sink_takes_coded(s->format)) {
         if (!bgr || width != s->w || height != s->h || stride != 0 || !gif_coded_frame(s, bgr)) s->failed = true; else ++s->frames;
         return;
@@ -320,10 +348,7 @@ void poppy_sink_write(void* user, const uint8_t* bgr, int width, int height, siz
         return;
     }
     if (s->format == POPPY_SINK_PPM) {
-        std::string num = std::to_string(s->frames);
-        if ((int)num.size() < s->pad) num.insert(0, (size_t)s->pad - num.size(), s->zero ? '0' : ' ');
-        const std::string name = s->path + num + s->tail;
-        f = fopen(name.c_str(), "wb");
+        f = fopen(numbered_name(s).c_str(), "wb");
         if (!f) { s->failed = true; return; }
         fprintf(f, "P6\n%d %d\n255\n", width, height);
     } else if (s->format == POPPY_SINK_Y4M) {

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "jpeg_tables.h"
+#include "png_tables.h"
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
@@ -274,5 +275,17 @@ void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame
 // a frame on the device (tight BGR) -> its I444 planes, 3 * w * h bytes (kernels_frame_i444.hip; poppy_bgr_to_i444 is the host statement): any w, h >= 1; `done`
 // (optional) rides on the dispatch
 void launch_bgr_to_i444(const uint8_t* src, uint8_t* dst, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
+
+// a frame on the device (tight BGR, any alignment) -> POPPY_FRAME_PNG (kernels_frame_png.hip, which says what each does; the format: include/poppy_hip.h and
+// png_tables.h), six dispatches on one stream in this order.  `scratch`: png_scratch_bytes of device memory (the filtered stream, then the segments' and the CRC
+// pieces' words); `frame`: poppy_frame_bytes(POPPY_FRAME_PNG, w, h) + 16 bytes, 4-byte aligned; total_host (optional): a word of mapped pinned host memory that
+// receives `total` too.  `done` (optional) rides on the last dispatch.
+size_t png_scratch_bytes(int w, int h);
+void launch_png_filter(const uint8_t* bgr, uint8_t* scratch, int w, int h, hipStream_t s);
+void launch_png_cost(uint8_t* scratch, int w, int h, hipStream_t s);
+void launch_png_scan(uint8_t* scratch, uint8_t* frame, int w, int h, hipStream_t s);
+void launch_png_pack(const uint8_t* scratch, uint8_t* frame, int w, int h, hipStream_t s);
+void launch_png_crc(uint8_t* scratch, const uint8_t* frame, int w, int h, hipStream_t s);
+void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
 
 }  // namespace poppy_hip

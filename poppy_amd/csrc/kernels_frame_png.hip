@@ -1,0 +1,474 @@
+// kernels_frame_png.hip — a BGR frame on the device -> POPPY_FRAME_PNG for the writer hand-off (include/poppy_hip.h has the rule; png_tables.h the constants): one
+// PNG file whose IDAT is a zlib stream of Huffman-only dynamic blocks, a block per POPPY_PNG_SEGMENT_BYTES of the filtered stream.  poppy_bgr_to_png_frame
+// (frame_png.cpp) is the host statement; the bytes are equal.  Nothing in the format is serial but the bit positions and the two checksums, and both combine
+// associatively, so the frame is six dispatches on one stream, no host round trip:
+//   k_png_filter  a workgroup per row, a thread per pixel (strided) — per four pixels from whole dwords where the width is a multiple of 4 and the frame 4-byte
+//                 aligned —: the five filters' scores from the original pixels, a workgroup reduction, the choice (smallest, ties to the lowest type), then
+//                 the chosen filter's bytes into the filtered stream in scratch, R, G, B swapped on the way.
+//   k_png_cost    a workgroup per segment, 32 bytes per thread: the eight tables' lengths of a byte come from one LDS word (a nibble per table: no length is
+//                 above 15), so a segment's eight costs are eight sums; the table (smallest, ties to the lowest), the block's bits, and the segment's Adler
+//                 pair: A = the bytes' sum, B = the sum of (len - i) * byte, which is what the segment adds to Adler's b once a is known.
+//   k_png_scan    one workgroup: the exclusive prefix sum of the blocks' bits, counted from the FRAME's bit 0 (the deflate bits begin at byte 47, on no word
+//                 boundary, and the frame is one bit string), Adler-32 from the pairs (b = n + sum over segments of (bytes behind the segment) * A + B, modulo
+//                 65521), and everything that is known now: `total`, the signature, IHDR, IDAT's length and type, the zlib header, Adler-32 and IEND.  It also
+//                 stores a zero into every word in which a block begins or the stream ends: the words that two writers share.
+//   k_png_pack    a workgroup per segment, the same 32 bytes per thread: a workgroup prefix sum of the threads' code lengths places every thread; a thread
+//                 gathers its codes in a 64-bit accumulator that starts at its bit offset inside a word, so that every flush is one whole-word ds_or_b32 into
+//                 the block's image in LDS, positioned at the block's start bit mod 32.  The image's words go out as plain stores, except the word the block
+//                 begins in and the word it ends in, which its neighbours share: atomicOr on the zeroed word.
+//   k_png_crc     IDAT's CRC-32 in pieces: a thread takes 32 bytes counted from the chunk's END (so every piece's distance to the end is known without the
+//                 length, and the short piece is the first, where leading zeros change nothing), a table-driven raw remainder, one multiplication by
+//                 x^(256 t) modulo the generator, an XOR over the workgroup: a word per 8192 bytes.
+//   k_png_finish  one workgroup: the words multiplied into place and XORed, the initial and final inversions, the CRC's four bytes, `total` into the word of
+//                 mapped pinned host memory.
+// Plain vector stores and atomics only.
+#include "kernels.h"
+#include <hip/hip_ext.h>
+
+namespace poppy_hip {
+
+namespace {
+
+using namespace png;
+
+constexpr int kThreads = 256, kBytesPerThread = (int)kSegment / kThreads;
+static_assert(kBytesPerThread == 32, "a thread takes two 16-byte loads of its segment");
+constexpr int kImageWords = (int)((31 + kSegmentBitsMax + 31) / 32) + 1;      // a block at its bound behind 31 bits of offset, and the word a flush may touch
+constexpr size_t kCrcBlock = 32 * kThreads;                 // bytes of the chunk per workgroup of k_png_crc
+constexpr unsigned long long kFirstBit = 8 * kStreamByte;
+
+struct NibbleTable { uint32_t e[256]; };                    // per literal: table k's length in bits 4 k .. 4 k + 3
+constexpr NibbleTable make_nibbles() {
+    NibbleTable t{};
+    for (int v = 0; v < 256; ++v)
+        for (int k = 0; k < kTables; ++k) t.e[v] |= (uint32_t)kLen[k][v] << (4 * k);
+    return t;
+}
+struct CrcShifts { uint32_t e[kThreads]; };                 // e[t] = x^(8 * 32 * t): what lies behind thread t's piece inside its workgroup
+constexpr CrcShifts make_crc_shifts() {
+    CrcShifts s{};
+    const CrcPowers p = make_crc_powers();
+    for (int t = 0; t < kThreads; ++t) s.e[t] = crc_x_pow_bytes(32ull * t, p);
+    return s;
+}
+// e[t] = x^(8 * kCrcBlock * t), what lies behind word t of k_png_crc's output, and stride = x^(8 * kCrcBlock * 256) for the words 256 further on
+struct CrcBlockPowers { uint32_t e[kThreads], stride; };
+constexpr CrcBlockPowers make_crc_block_powers() {
+    CrcBlockPowers s{};
+    const CrcPowers p = make_crc_powers();
+    for (int t = 0; t < kThreads; ++t) s.e[t] = crc_x_pow_bytes((unsigned long long)kCrcBlock * t, p);
+    s.stride = crc_x_pow_bytes((unsigned long long)kCrcBlock * kThreads, p);
+    return s;
+}
+struct HeaderWords { uint32_t e[kTables][kHeaderWords]; };
+constexpr HeaderWords make_header_words() {
+    HeaderWords h{};
+    for (int k = 0; k < kTables; ++k)
+        for (int i = 0; i < kHeaderWords; ++i) h.e[k][i] = kHeader[k][i];
+    return h;
+}
+struct BlockOver { uint32_t header[kTables], over[kTables]; };      // H_k, and H_k + len_k[end-of-block]
+constexpr BlockOver make_block_over() {
+    BlockOver b{};
+    for (int k = 0; k < kTables; ++k) { b.header[k] = (uint32_t)kHeaderBits[k]; b.over[k] = (uint32_t)kHeaderBits[k] + kLen[k][kEob]; }
+    return b;
+}
+
+struct FixedBytes { uint8_t signature[8], iend[12]; };
+constexpr FixedBytes make_fixed_bytes() {
+    FixedBytes f{};
+    for (int k = 0; k < 8; ++k) f.signature[k] = kSignature[k];
+    for (int k = 0; k < 12; ++k) f.iend[k] = kIend[k];
+    return f;
+}
+
+__constant__ FixedBytes c_fixed = make_fixed_bytes();
+__constant__ NibbleTable c_nibbles = make_nibbles();
+__constant__ Codes c_codes = make_codes();
+__constant__ HeaderWords c_header = make_header_words();
+__constant__ BlockOver c_block = make_block_over();
+__constant__ CrcTable c_crc = make_crc_table();
+__constant__ CrcShifts c_crc_shift = make_crc_shifts();
+__constant__ CrcPowers c_crc_pow = make_crc_powers();
+__constant__ CrcBlockPowers c_crc_block = make_crc_block_powers();
+
+// the words behind the filtered stream in scratch
+struct Scratch {
+    uint8_t* stream;                    // n bytes, padded to whole segments
+    uint4* seg;                         // per segment: table, bits, Adler A, Adler B mod 65521
+    unsigned long long* start;          // per segment: the frame's bit its block begins at
+    uint32_t* crc;                      // per kCrcBlock of the chunk, counted from its end: the raw remainder
+    uint32_t* meta;                     // [0] the frame's byte behind the deflate data (Adler-32's place), [1] whether the frame is inside its capacity
+};
+size_t crc_blocks(int w, int h) { return (size_t)((frame_capacity((size_t)w, (size_t)h) + kCrcBlock - 1) / kCrcBlock); }
+Scratch scratch_of(uint8_t* p, int w, int h) {
+    const size_t n_seg = (size_t)segment_count((size_t)w, (size_t)h);
+    Scratch s;
+    s.stream = p;
+    s.seg = (uint4*)(p + n_seg * kSegment);
+    s.start = (unsigned long long*)(s.seg + n_seg);
+    s.crc = (uint32_t*)(s.start + n_seg);
+    s.meta = s.crc + crc_blocks(w, h);
+    return s;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+    #pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+// the sum of v over the workgroup's 256 threads, in every thread (part: 4 words of LDS, free again behind the call)
+__device__ __forceinline__ unsigned long long group_sum(unsigned long long v, unsigned long long* part) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const unsigned long long all = part[0] + part[1] + part[2] + part[3];
+    __syncthreads();
+    return all;
+}
+// the workgroup's exclusive prefix sum of v, and the sum of all in *all
+__device__ __forceinline__ uint32_t group_scan(uint32_t v, uint32_t* part, uint32_t* all) {
+    const int t = threadIdx.x, lane = t & 63;
+    uint32_t incl = v;
+    #pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up(incl, d, 64); if (lane >= d) incl += u; }
+    if (lane == 63) part[t >> 6] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    for (int k = 0; k < (t >> 6); ++k) before += part[k];
+    *all = part[0] + part[1] + part[2] + part[3];
+    __syncthreads();
+    return before + incl - v;
+}
+
+__device__ __forceinline__ int paeth(int a, int b, int c) {
+    const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+    return pa <= pb && pa <= pc ? a : pb <= pc ? b : c;
+}
+__device__ __forceinline__ uint32_t near_zero(int v) { v &= 255; return (uint32_t)min(v, 256 - v); }
+
+__device__ __forceinline__ uint32_t dev_crc_mul(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    #pragma unroll 4
+    for (uint32_t m = 1u << 31; m; m >>= 1) {
+        if (a & m) p ^= b;
+        b = b & 1u ? (b >> 1) ^ kCrcPoly : b >> 1;
+    }
+    return p;
+}
+// x^(8 n_bytes) in every lane of the wave: lane k holds x^(2^(k + 3)) where bit k of n_bytes is set and 1 elsewhere; the product over the lanes
+__device__ __forceinline__ uint32_t wave_x_pow_bytes(unsigned long long n_bytes) {
+    const int lane = threadIdx.x & 63;
+    uint32_t p = lane <= 60 && (n_bytes >> lane & 1) ? c_crc_pow.e[lane + 3] : 1u << 31;
+    #pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) p = dev_crc_mul(p, __shfl_xor(p, d, 64));
+    return p;
+}
+
+}  // namespace
+
+namespace {
+
+// byte k of four consecutive dwords
+__device__ __forceinline__ int byte_of(const uint32_t (&d)[4], int k) { return (int)((d[k >> 2] >> (8 * (k & 3))) & 255u); }
+
+// f(cur, a, b, c, at) for every byte of row y that the thread takes: the byte, its neighbours left, above and above left (zeros outside the frame) and the byte's
+// place among the row's 3 w filtered bytes (B, G, R -> R, G, B).  WIDE (w a multiple of 4, the frame 4-byte aligned, so every row is): four pixels per trip from
+// three dwords of either row and the dword in front of them, whose upper three bytes are the pixel to the left; else a pixel per trip, bytewise.
+template <bool WIDE, typename F>
+__device__ __forceinline__ void for_each_byte(const uint8_t* __restrict__ row, const uint8_t* __restrict__ above, int w, int y, F&& f) {
+    if (WIDE) {
+        const uint32_t *r32 = (const uint32_t*)row, *a32 = (const uint32_t*)above;
+        for (int q = threadIdx.x; q < w / 4; q += kThreads) {
+            const size_t at = 3 * (size_t)q;
+            const uint32_t cw[4] = {q ? r32[at - 1] : 0u, r32[at], r32[at + 1], r32[at + 2]};
+            const uint32_t aw[4] = {q && y ? a32[at - 1] : 0u, y ? a32[at] : 0u, y ? a32[at + 1] : 0u, y ? a32[at + 2] : 0u};
+            #pragma unroll
+            for (int i = 0; i < 12; ++i) f(byte_of(cw, 4 + i), byte_of(cw, 1 + i), byte_of(aw, 4 + i), byte_of(aw, 1 + i), 4 * at + (size_t)(3 * (i / 3) + 2 - i % 3));
+        }
+    } else {
+        for (int x = threadIdx.x; x < w; x += kThreads) {
+            #pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const size_t at = 3 * (size_t)x + ch;
+                f((int)row[at], x ? (int)row[at - 3] : 0, y ? (int)above[at] : 0, x && y ? (int)above[at - 3] : 0, 3 * (size_t)x + (size_t)(2 - ch));
+            }
+        }
+    }
+}
+
+}  // namespace
+
+template <bool WIDE>
+__global__ void __launch_bounds__(kThreads) k_png_filter(const uint8_t* __restrict__ bgr, uint8_t* __restrict__ stream, int w) {
+    __shared__ unsigned long long s_part[5][4];
+    __shared__ int s_type;
+    const int t = threadIdx.x, y = blockIdx.x;
+    const size_t row_bytes = 3 * (size_t)w;
+    const uint8_t *row = bgr + (size_t)y * row_bytes, *above = row - row_bytes;      // (`above` is read in rows 1.. only)
+    uint32_t score[5] = {0, 0, 0, 0, 0};
+    for_each_byte<WIDE>(row, above, w, y, [&](int cur, int a, int b, int c, size_t) {
+        score[0] += near_zero(cur); score[1] += near_zero(cur - a); score[2] += near_zero(cur - b);
+        score[3] += near_zero(cur - ((a + b) >> 1)); score[4] += near_zero(cur - paeth(a, b, c));
+    });
+    #pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const unsigned long long v = wave_sum(score[k]);
+        if ((t & 63) == 0) s_part[k][t >> 6] = v;
+    }
+    __syncthreads();
+    if (t == 0) {
+        int best = 0; unsigned long long least = 0;
+        for (int k = 0; k < 5; ++k) {
+            const unsigned long long v = s_part[k][0] + s_part[k][1] + s_part[k][2] + s_part[k][3];
+            if (k == 0 || v < least) { best = k; least = v; }
+        }
+        s_type = best;
+    }
+    __syncthreads();
+    const int type = s_type;
+    uint8_t* out = stream + (size_t)y * (1 + row_bytes);
+    if (t == 0) out[0] = (uint8_t)type;
+    for_each_byte<WIDE>(row, above, w, y, [&](int cur, int a, int b, int c, size_t at) {
+        const int pred = type == 0 ? 0 : type == 1 ? a : type == 2 ? b : type == 3 ? (a + b) >> 1 : paeth(a, b, c);
+        out[1 + at] = (uint8_t)(cur - pred);
+    });
+}
+
+__global__ void __launch_bounds__(kThreads) k_png_cost(const uint8_t* __restrict__ stream, uint4* __restrict__ seg_info, unsigned long long n) {
+    __shared__ uint32_t s_nib[256];
+    __shared__ unsigned long long s_part[4];
+    const int t = threadIdx.x;
+    const size_t first = (size_t)blockIdx.x * kSegment;
+    const uint32_t len = (uint32_t)(n - first < kSegment ? n - first : kSegment);
+    s_nib[t] = c_nibbles.e[t];
+    __syncthreads();
+    uint32_t cost[kTables] = {0, 0, 0, 0, 0, 0, 0, 0}, sum = 0, weighted = 0;
+    const uint32_t at = (uint32_t)t * kBytesPerThread;
+    if (at < len) {
+        const uint4* src = (const uint4*)(stream + first + at);
+        const uint4 lo = src[0], hi = src[1];
+        const uint32_t word[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        #pragma unroll
+        for (int i = 0; i < kBytesPerThread; ++i) {
+            if (at + i >= len) break;
+            const uint32_t d = (word[i >> 2] >> (8 * (i & 3))) & 255u, v = s_nib[d];
+            #pragma unroll
+            for (int k = 0; k < kTables; ++k) cost[k] += (v >> (4 * k)) & 15u;
+            sum += d; weighted += (len - (at + i)) * d;      // (at most 32 * 8192 * 255: no overflow)
+        }
+    }
+    unsigned long long total[kTables];
+    #pragma unroll
+    for (int k = 0; k < kTables; ++k) total[k] = group_sum(cost[k], s_part);
+    const unsigned long long a = group_sum(sum, s_part), b = group_sum(weighted % kAdlerMod, s_part);
+    if (t == 0) {
+        int best = 0; unsigned long long least = 0;
+        for (int k = 0; k < kTables; ++k) {
+            const unsigned long long v = total[k] + c_block.over[k];
+            if (k == 0 || v < least) { best = k; least = v; }
+        }
+        seg_info[blockIdx.x] = make_uint4((uint32_t)best, (uint32_t)least, (uint32_t)a, (uint32_t)(b % kAdlerMod));
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_png_scan(const uint4* __restrict__ seg_info, unsigned long long* __restrict__ seg_start, uint32_t* __restrict__ meta,
+                                                       uint32_t* __restrict__ frame32, uint32_t n_seg, unsigned long long n, uint32_t w, uint32_t h,
+                                                       uint32_t ihdr_crc, unsigned long long capacity) {
+    __shared__ uint32_t s_part[4];
+    __shared__ unsigned long long s_sum[4];
+    __shared__ uint32_t s_head[12];
+    const uint32_t t = threadIdx.x;
+    const unsigned long long cap_words = (capacity + 3) / 4;
+    unsigned long long at = kFirstBit, adler_a = 0, adler_b = 0;
+    for (uint32_t base = 0; base < n_seg; base += kThreads) {
+        const uint32_t i = base + t;
+        const bool valid = i < n_seg;
+        const uint4 info = valid ? seg_info[i] : make_uint4(0, 0, 0, 0);
+        uint32_t all = 0;
+        const uint32_t before = group_scan(info.y, s_part, &all);
+        if (valid) {
+            const unsigned long long start = at + before, first = (unsigned long long)i * kSegment, len = n - first < kSegment ? n - first : kSegment;
+            seg_start[i] = start;
+            if (i && (start >> 5) < cap_words) frame32[start >> 5] = 0;      // the word this block shares with the one before it
+            adler_a += info.z;
+            adler_b = (adler_b + ((n - first - len) % kAdlerMod) * (info.z % kAdlerMod) + info.w) % kAdlerMod;
+        }
+        at += all;
+    }
+    adler_a = group_sum(adler_a, s_sum);
+    adler_b = group_sum(adler_b, s_sum);
+    if (t != 0) return;
+    const unsigned long long end = (at + 7) >> 3, total = end + kTailBytes;      // `end`: the frame's byte behind the deflate data
+    const bool ok = total <= capacity && total < (1ull << 31);
+    meta[0] = (uint32_t)end; meta[1] = ok;
+    if (!ok) { frame32[0] = 0; return; }
+    const uint32_t a = (uint32_t)((1 + adler_a) % kAdlerMod), b = (uint32_t)((n % kAdlerMod + adler_b) % kAdlerMod);
+    uint8_t *head = (uint8_t*)s_head, *frame = (uint8_t*)frame32;
+    auto be32 = [](uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; };
+    s_head[0] = (uint32_t)total;
+    for (int k = 0; k < 8; ++k) head[kOffSignature + k] = c_fixed.signature[k];
+    be32(head + kOffIhdr, 13);
+    head[kOffIhdr + 4] = 'I'; head[kOffIhdr + 5] = 'H'; head[kOffIhdr + 6] = 'D'; head[kOffIhdr + 7] = 'R';
+    be32(head + kOffIhdr + 8, w); be32(head + kOffIhdr + 12, h);
+    head[kOffIhdr + 16] = 8; head[kOffIhdr + 17] = 2; head[kOffIhdr + 18] = 0; head[kOffIhdr + 19] = 0; head[kOffIhdr + 20] = 0;
+    be32(head + kOffIhdr + 21, ihdr_crc);
+    be32(head + kOffIdat, (uint32_t)(end + 4 - (kOffIdatType + 4)));
+    head[kOffIdatType] = 'I'; head[kOffIdatType + 1] = 'D'; head[kOffIdatType + 2] = 'A'; head[kOffIdatType + 3] = 'T';
+    head[kOffIdatType + 4] = 0x78; head[kOffIdatType + 5] = 0x01;
+    head[kStreamByte] = 0;                                  // the first block's bits are ORed into this word
+    static_assert(kStreamByte == 47 && sizeof s_head == 48, "the head is twelve whole words");
+    for (int k = 0; k < 12; ++k) frame32[k] = s_head[k];
+    frame32[at >> 5] = 0;                                   // the word the stream ends in: the last block ORs its bits into it, the bytes below follow them
+    be32(frame + end, b << 16 | a);
+    for (int k = 0; k < 12; ++k) frame[end + 8 + k] = c_fixed.iend[k];
+}
+
+__global__ void __launch_bounds__(kThreads) k_png_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const unsigned long long* __restrict__ seg_start,
+                                                       const uint32_t* __restrict__ meta, uint32_t* __restrict__ frame32, uint32_t n_seg, unsigned long long n,
+                                                       unsigned long long capacity) {
+    __shared__ uint32_t s_image[kImageWords];
+    __shared__ uint32_t s_code[kSymbols];
+    __shared__ uint32_t s_part[4];
+    const int t = threadIdx.x;
+    const uint32_t seg = blockIdx.x;
+    const uint4 info = seg_info[seg];
+    const uint32_t table = info.x & (kTables - 1), bits = info.y;
+    if (!meta[1] || bits > kSegmentBitsMax) return;         // (never: the scan found the frame inside its capacity, and table 7 bounds every block)
+    const unsigned long long start = seg_start[seg];
+    const size_t first = (size_t)seg * kSegment;
+    const uint32_t len = (uint32_t)(n - first < kSegment ? n - first : kSegment);
+    const uint32_t off = (uint32_t)start & 31u, n_words = (off + bits + 31) >> 5;
+    for (uint32_t i = t; i < n_words; i += kThreads) s_image[i] = 0;
+    for (int i = t; i < kSymbols; i += kThreads) s_code[i] = c_codes.e[table][i];
+    __syncthreads();
+    const uint32_t header_bits = c_block.header[table];
+    for (uint32_t i = t; 32 * i < header_bits; i += kThreads) {      // the header, a word per thread (the bits behind H_k are zeros in the table)
+        const uint32_t v = c_header.e[table][i] | (i == 0 && seg == n_seg - 1 ? 1u : 0u), p = off + 32 * i;
+        atomicOr(&s_image[p >> 5], v << (p & 31));
+        if ((p & 31) && (v >> (32 - (p & 31)))) atomicOr(&s_image[(p >> 5) + 1], v >> (32 - (p & 31)));
+    }
+    const uint32_t at = (uint32_t)t * kBytesPerThread;
+    uint32_t word[8] = {0, 0, 0, 0, 0, 0, 0, 0}, count = 0;
+    if (at < len) {
+        const uint4* src = (const uint4*)(stream + first + at);
+        const uint4 lo = src[0], hi = src[1];
+        word[0] = lo.x; word[1] = lo.y; word[2] = lo.z; word[3] = lo.w; word[4] = hi.x; word[5] = hi.y; word[6] = hi.z; word[7] = hi.w;
+        #pragma unroll
+        for (int i = 0; i < kBytesPerThread; ++i)
+            if (at + i < len) count += s_code[(word[i >> 2] >> (8 * (i & 3))) & 255u] & 15u;
+    }
+    uint32_t all = 0;
+    const uint32_t before = group_scan(count, s_part, &all);
+    if (at < len) {
+        const uint32_t p = off + header_bits + before;
+        uint32_t at_word = p >> 5;
+        int n_acc = (int)(p & 31);
+        unsigned long long acc = 0;
+        auto put = [&](uint32_t e) {                        // a code of at most 15 bits behind fewer than 32 waiting ones
+            acc |= (unsigned long long)(e >> 4) << n_acc;
+            n_acc += (int)(e & 15u);
+            if (n_acc >= 32) { atomicOr(&s_image[at_word++], (uint32_t)acc); acc >>= 32; n_acc -= 32; }
+        };
+        #pragma unroll
+        for (int i = 0; i < kBytesPerThread; ++i)
+            if (at + i < len) put(s_code[(word[i >> 2] >> (8 * (i & 3))) & 255u]);
+        if (at + kBytesPerThread >= len) put(s_code[kEob]);      // the thread of the segment's last byte: end-of-block
+        if (n_acc) atomicOr(&s_image[at_word], (uint32_t)acc);
+    }
+    __syncthreads();
+    const unsigned long long word0 = start >> 5, word_end = (start + bits) >> 5, cap_words = (capacity + 3) / 4;
+    for (uint32_t i = t; i < n_words; i += kThreads) {
+        const unsigned long long fw = word0 + i;
+        if (fw >= cap_words) continue;
+        if (fw == word0 || fw == word_end) atomicOr(&frame32[fw], s_image[i]); else frame32[fw] = s_image[i];
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_png_crc(const uint8_t* __restrict__ frame, const uint32_t* __restrict__ meta, uint32_t* __restrict__ pieces) {
+    __shared__ uint32_t s_table[256];
+    __shared__ uint32_t s_part[4];
+    const int t = threadIdx.x;
+    if (!meta[1]) return;
+    const long long begin = (long long)kOffIdatType, end = (long long)meta[0] + 4;      // the chunk's type, its data, Adler-32 included
+    if ((long long)blockIdx.x * (long long)kCrcBlock >= end - begin) return;
+    s_table[t] = c_crc.e[t];
+    __syncthreads();
+    const long long hi = end - 32ll * ((long long)blockIdx.x * kThreads + t), lo = hi - 32 > begin ? hi - 32 : begin;
+    uint32_t c = 0;
+    for (long long p = lo; p < hi; ++p) c = s_table[(c ^ frame[p]) & 255u] ^ (c >> 8);
+    c = dev_crc_mul(c_crc_shift.e[t], c);
+    #pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c ^= __shfl_xor(c, d, 64);
+    if ((t & 63) == 0) s_part[t >> 6] = c;
+    __syncthreads();
+    if (t == 0) pieces[blockIdx.x] = s_part[0] ^ s_part[1] ^ s_part[2] ^ s_part[3];
+}
+
+__global__ void __launch_bounds__(kThreads) k_png_finish(const uint32_t* __restrict__ meta, const uint32_t* __restrict__ pieces, uint8_t* __restrict__ frame,
+                                                         uint32_t* __restrict__ total_host) {
+    __shared__ uint32_t s_part[4];
+    const int t = threadIdx.x;
+    const bool ok = meta[1] != 0;
+    const unsigned long long end = meta[0], length = end + 4 - kOffIdatType;
+    const long long n_words = (long long)((length + kCrcBlock - 1) / kCrcBlock);
+    uint32_t c = 0;
+    if (ok && t < n_words) {                                // words t, t + 256, ..: Horner's rule in x^(8 * kCrcBlock * 256) from the furthest, then word t's own place
+        for (long long b = t + (n_words - 1 - t) / kThreads * kThreads; b >= t; b -= kThreads) c = dev_crc_mul(c_crc_block.stride, c) ^ pieces[b];
+        c = dev_crc_mul(c_crc_block.e[t], c);
+    }
+    const uint32_t length_power = wave_x_pow_bytes(length);
+    #pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c ^= __shfl_xor(c, d, 64);
+    if ((t & 63) == 0) s_part[t >> 6] = c;
+    __syncthreads();
+    if (t != 0) return;
+    uint32_t total = 0;
+    if (ok) {
+        const uint32_t crc = s_part[0] ^ s_part[1] ^ s_part[2] ^ s_part[3] ^ dev_crc_mul(length_power, 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
+        uint8_t* p = frame + end + 4;
+        p[0] = (uint8_t)(crc >> 24); p[1] = (uint8_t)(crc >> 16); p[2] = (uint8_t)(crc >> 8); p[3] = (uint8_t)crc;
+        total = (uint32_t)(end + kTailBytes);
+    }
+    if (total_host) { *total_host = total; __threadfence_system(); }
+}
+
+size_t png_scratch_bytes(int w, int h) {
+    const size_t n_seg = (size_t)segment_count((size_t)w, (size_t)h);
+    return n_seg * (kSegment + sizeof(uint4) + 8) + crc_blocks(w, h) * 4 + 16 + 16;
+}
+
+void launch_png_filter(const uint8_t* bgr, uint8_t* scratch, int w, int h, hipStream_t s) {
+    const bool wide = w % 4 == 0 && (uintptr_t)bgr % 4 == 0;
+    hipLaunchKernelGGL(wide ? k_png_filter<true> : k_png_filter<false>, dim3((unsigned)h), dim3(kThreads), 0, s, bgr, scratch_of(scratch, w, h).stream, w);
+}
+void launch_png_cost(uint8_t* scratch, int w, int h, hipStream_t s) {
+    const Scratch m = scratch_of(scratch, w, h);
+    hipLaunchKernelGGL(k_png_cost, dim3((unsigned)segment_count((size_t)w, (size_t)h)), dim3(kThreads), 0, s, (const uint8_t*)m.stream, m.seg, stream_bytes((size_t)w, (size_t)h));
+}
+void launch_png_scan(uint8_t* scratch, uint8_t* frame, int w, int h, hipStream_t s) {
+    const Scratch m = scratch_of(scratch, w, h);
+    constexpr CrcTable table = make_crc_table();
+    const uint8_t ihdr[17] = {'I', 'H', 'D', 'R', (uint8_t)(w >> 24), (uint8_t)(w >> 16), (uint8_t)(w >> 8), (uint8_t)w,
+                              (uint8_t)(h >> 24), (uint8_t)(h >> 16), (uint8_t)(h >> 8), (uint8_t)h, 8, 2, 0, 0, 0};
+    uint32_t c = 0xFFFFFFFFu;
+    for (uint8_t byte : ihdr) c = table.e[(c ^ byte) & 255u] ^ (c >> 8);
+    hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(kThreads), 0, s, (const uint4*)m.seg, m.start, m.meta, (uint32_t*)frame, (uint32_t)segment_count((size_t)w, (size_t)h),
+                       stream_bytes((size_t)w, (size_t)h), (uint32_t)w, (uint32_t)h, c ^ 0xFFFFFFFFu, frame_capacity((size_t)w, (size_t)h));
+}
+void launch_png_pack(const uint8_t* scratch, uint8_t* frame, int w, int h, hipStream_t s) {
+    const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h);
+    const uint32_t n_seg = (uint32_t)segment_count((size_t)w, (size_t)h);
+    hipLaunchKernelGGL(k_png_pack, dim3(n_seg), dim3(kThreads), 0, s, (const uint8_t*)m.stream, (const uint4*)m.seg, (const unsigned long long*)m.start, (const uint32_t*)m.meta,
+                       (uint32_t*)frame, n_seg, stream_bytes((size_t)w, (size_t)h), frame_capacity((size_t)w, (size_t)h));
+}
+void launch_png_crc(uint8_t* scratch, const uint8_t* frame, int w, int h, hipStream_t s) {
+    const Scratch m = scratch_of(scratch, w, h);
+    hipLaunchKernelGGL(k_png_crc, dim3((unsigned)crc_blocks(w, h)), dim3(kThreads), 0, s, frame, (const uint32_t*)m.meta, m.crc);
+}
+void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done) {
+    const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h);
+    hipExtLaunchKernelGGL(k_png_finish, dim3(1), dim3(kThreads), 0, s, nullptr, done, 0, (const uint32_t*)m.meta, (const uint32_t*)m.crc, frame, total_host);
+}
+
+}  // namespace poppy_hip

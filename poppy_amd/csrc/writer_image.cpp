@@ -53,6 +53,28 @@ static int jpeg_from_device_planes(poppy_hip_ctx* c, const uint8_t* d_i420, cons
     return POPPY_OK;
 }
 
+// a tight BGR frame in device memory -> its POPPY_FRAME_PNG frame in `host` (exactly `total` bytes), on the context's stream and waited for: the frames that no slot
+// renders, and poppy_hip_bgr_to_png_frame.  The buffers live for the call.
+static int png_from_device_bgr(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host) {
+    const size_t cap = png_frame_capacity((size_t)W, (size_t)H);
+    CallBuffers held;
+    uint8_t *work = nullptr, *frame = nullptr;
+    hipError_t e = held.alloc(&work, png_scratch_bytes(W, H));
+    if (e == hipSuccess) e = held.alloc(&frame, cap + 16);
+    uint32_t total = 0;
+    if (e == hipSuccess) {
+        enqueue_png_coding(d_bgr, work, frame, nullptr, W, H, c->stream, nullptr, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go
+    if (e == hipSuccess) e = e_sync;
+    if (e == hipSuccess && !coded_length_ok(total, cap, kPngFrameMinBytes)) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+    if (e == hipSuccess) { host.resize(total); e = hipMemcpy(host.data(), frame, total, hipMemcpyDeviceToHost); }
+    if (e != hipSuccess) { c->err = std::string("PNG frame coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    return POPPY_OK;
+}
+
 int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const WriterGeom& g, std::vector<uint8_t>& host, size_t* stride, int n_copies) {
     const int fmt = c->frame_format;
     if (const char* why = format_refuses(fmt, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
@@ -72,6 +94,7 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
     const uint8_t* d_frame = d_bgr;
     if (fmt != POPPY_FRAME_BGR) {                                  // converted into the context's scratch: the slots' launches on other buffers
         // (a coded format: its raster form into the scratch — PAL8 for GIF, I420 for JPEG, the I444 planes for JPEG444 —, then the coder on buffers that live for the call)
+        if (fmt == POPPY_FRAME_PNG) return png_from_device_bgr(c, d_bgr, W, H, host);      // (no raster form: the coder reads the BGR frame)
         if (fmt == POPPY_FRAME_JPEG444) {                          // (I444 is no format of its own: the kernel is launched here)
             { int rc = ensure_jpeg_tables(c); if (rc) return rc; }
             HIPCHK(c, c->fmt_scratch.reserve((size_t)W * H * 3 + 16, c->stream));
@@ -110,6 +133,7 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
                    fmt == POPPY_FRAME_GIF ? poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data()) :
                    fmt == POPPY_FRAME_JPEG ? poppy_bgr_to_jpeg_frame(bgr, stride, W, H, c->jpeg_quality, tmp.data()) :
                    fmt == POPPY_FRAME_JPEG444 ? poppy_bgr_to_jpeg444_frame(bgr, stride, W, H, c->jpeg_quality, tmp.data()) :
+                   fmt == POPPY_FRAME_PNG ? poppy_bgr_to_png_frame(bgr, stride, W, H, tmp.data()) :
                    fmt == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
     if (rc == POPPY_OK && !pal8.empty()) rc = poppy_pal8_to_gif_frame(pal8.data(), W, H, tmp.data());
     if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
@@ -224,6 +248,27 @@ int poppy_hip_i420_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i420, int W, i
 
 int poppy_hip_i444_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i444, int W, int H, int quality, uint8_t* dst) {
     return jpeg_code_host_planes(c, POPPY_FRAME_JPEG444, i444, W, H, quality, dst);
+}
+
+// a host frame up, the six PNG kernels, `total` bytes down, on buffers that live for the call; the source's place behind a 256-byte boundary is the row pad's low
+// bits (include/poppy_hip.h), as in scale_host_frame
+int poppy_hip_bgr_to_png_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* dst) {
+    if (!c) return POPPY_E_ARG;
+    if (!bgr || !dst || W <= 0 || H <= 0 || stride < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad arguments");
+    if (const char* why = format_refuses(POPPY_FRAME_PNG, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t row = (size_t)W * 3, shift = (stride - row) % 16;
+    CallBuffers held;                                              // (png_from_device_bgr waits for the stream before it returns)
+    uint8_t* d_src = nullptr;
+    HIPCHK(c, held.alloc(&d_src, row * H + shift + 16));
+    if (copy_rows_async(d_src + shift, row, bgr, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        return fail(c, POPPY_E_DEVICE, "upload of the BGR frame failed");
+    }
+    std::vector<uint8_t> host;
+    const int rc = png_from_device_bgr(c, d_src + shift, W, H, host);
+    if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
+    return rc;
 }
 
 // a host frame up, the I444 kernel, the planes down, on buffers that live for the call; the source's place behind a 256-byte boundary is the row pad's low bits
