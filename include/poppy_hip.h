@@ -343,7 +343,35 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * table k's 257 lengths and its header bit string (header_bits: POPPY_PNG_HEADER_BYTES bytes, bit i of the string is bit i mod 8 of byte i / 8; either output
  * may be null; POPPY_E_ARG for k outside 0..7).  poppy_hip_bgr_to_png_frame codes a host frame on the context's GPU (upload, the kernels, download of `total`
  * bytes): the same bytes; it needs no resident pair and disturbs none, and places its source as poppy_hip_bgr_downscale does.  The format applies wherever JPEG
- * applies, under poppy_hip_set_frame_scale and poppy_hip_set_frame_size as the host statement at the writer's geometry, and stays BGR wherever JPEG stays BGR.  */
+ * applies, under poppy_hip_set_frame_scale and poppy_hip_set_frame_size as the host statement at the writer's geometry, and stays BGR wherever JPEG stays BGR.
+ *
+ * POPPY_FRAME_PNG_RUNS: POPPY_FRAME_PNG with the runs of equal bytes in the filtered stream coded as deflate matches at distance 1: flat, black and smooth
+ * regions, which are runs of zeros behind the row filter, cost a few bits per 258 bytes where POPPY_FRAME_PNG pays at least a bit per byte.  Its value is 2048;
+ * 2047 and 2049 stay unknown in both enums; there is no sink value of its own: POPPY_SINK_PNG takes both formats.  The format is POPPY_FRAME_PNG word for word —
+ * layout and offsets, File, Filtered stream, Segments, 78 01, blocks that are not byte-aligned, BFINAL in the last, Adler-32 over the filtered stream, one IDAT,
+ * IEND, Limits — with these changes only:
+ *   Tokens.  Within ONE segment, take the maximal runs of equal bytes; a run never extends across a segment cut (so a segment's first byte is always a literal
+ *      and blocks stay independent), and a row's filter-type byte is an ordinary byte of the stream that breaks or joins runs like any other.  Of a run of r
+ *      bytes the first is a literal.  Let m = r - 1.  If m < POPPY_PNG_RUN_MIN = 8, all m bytes are literals.  Otherwise floor(m / 258) matches of length 258
+ *      at distance 1, then for rem = m mod 258: one match of length rem at distance 1 if rem >= 3, rem literals if rem is 1 or 2, nothing if it is 0.  A match
+ *      is deflate's length symbol (257..285, RFC 1951 section 3.2.5; length 258 is symbol 285) under the block's table, its extra bits least significant bit
+ *      first, then distance symbol 0 (distance 1, no extra bits), which is one 0 bit: the distance table has that one code, of length 1.
+ *   Tables.  POPPY_PNG_TABLES = 8 code-length tables over 286 symbols, committed in poppy_amd/csrc/png_runs_tables.h (poppy_png_runs_table hands them out): the
+ *      literals and end-of-block weigh what they weigh in POPPY_FRAME_PNG's table k, length symbol 285 weighs max(1, floor(2^40 * theta_k^3)) and each of
+ *      257..284 max(1, floor(2^40 * theta_k^6)); the same optimal length-limited (15 bits) construction and tie rule (tools/gen_png_tables.py --runs; the committed
+ *      header is the definition).
+ *   Block header.  A constant bit string of H_k bits per table, in the same file: BFINAL (bit 0), BTYPE = 10, HLIT = 29 (286 codes), HDIST = 0, HCLEN, the
+ *      code-length code's lengths (limited to 7 bits), then the 287 lengths (286 and the distance code's 1) as one sequence in which a length that equals the one
+ *      before it and begins r >= 3 equal lengths is sent as symbol 16 with the count min(r, 6); every header fits POPPY_PNG_HEADER_BYTES.
+ *   Table choice.  Segment s takes the k that minimises H_k + the bits of all its tokens (codes, extra bits, a bit per match for the distance) + len_k[256]; ties
+ *      go to the lowest k.
+ *   Capacity.  poppy_frame_bytes(POPPY_FRAME_PNG_RUNS, w, h) is an upper bound for any content: table 7 is always a candidate, a literal costs at most L7r <= 9
+ *      bits under it, a match covers at least 3 bytes and costs at most 3 * L7r bits under it (png_runs_tables.h asserts it for every length symbol), so a
+ *      segment of s bytes costs at most H_7 + L7r * s + len_7[256] bits; the rest as POPPY_FRAME_PNG's, with this format's H_7 and len_7[256].
+ * poppy_bgr_to_png_runs_frame is the host statement (dst: the capacity; the refusals are poppy_bgr_to_png_frame's).  poppy_png_runs_table gives table k's 286
+ * lengths and its header bit string as poppy_png_table does.  poppy_png_frame_bytes reads `total` of either format.  poppy_hip_bgr_to_png_runs_frame codes a host
+ * frame on the context's GPU as poppy_hip_bgr_to_png_frame does: the same bytes as the host statement.  The format applies wherever POPPY_FRAME_PNG applies and
+ * stays BGR wherever that stays BGR.  */
 #define POPPY_PAL8_MAX_PIXELS (1 << 24)
 #define POPPY_PAL8_SEQ_MAX_PIXELS (1ull << 32)
 #define POPPY_GIF_SEGMENT_PIXELS 2048
@@ -357,8 +385,9 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
 #define POPPY_PNG_SEGMENT_BYTES 8192
 #define POPPY_PNG_TABLES 8
 #define POPPY_PNG_HEADER_BYTES 236      /* (any header of the form fits: 17 + 19 * 3 + 258 * 7 bits) */
+#define POPPY_PNG_RUN_MIN 8
 enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128, POPPY_FRAME_JPEG = 256,
-       POPPY_FRAME_JPEG444 = 512, POPPY_FRAME_PNG = 1024 };
+       POPPY_FRAME_JPEG444 = 512, POPPY_FRAME_PNG = 1024, POPPY_FRAME_PNG_RUNS = 2048 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
@@ -384,6 +413,9 @@ size_t poppy_png_frame_bytes(const uint8_t* frame);
 int poppy_png_table(int k, uint8_t lengths[257], uint8_t* header_bits, int* n_header_bits);
 int poppy_bgr_to_png_frame(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 int poppy_hip_bgr_to_png_frame(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_png_runs_table(int k, uint8_t lengths[286], uint8_t* header_bits, int* n_header_bits);
+int poppy_bgr_to_png_runs_frame(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_hip_bgr_to_png_runs_frame(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 /* Scaled hand-off: frames rendered at the pair's resolution and handed to the writer scaled down by a whole factor, on the GPU, in front of the format
  * conversion.  The pair's resolution decides the keypoints, the mesh and the morph; the scale only decides what crosses the link and what the writer gets.
  *   The rule.  A factor s is a whole number from 1 to POPPY_FRAME_SCALE_MAX = 8; 1, the default, is the identity.  A width x height BGR frame becomes
@@ -837,8 +869,9 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * file past 4 GiB fails the sink (a plain AVI has 32-bit lengths).  A frame of any other format fails this sink, and a JPEG frame fails every other sink.
  * POPPY_FRAME_JPEG444 frames are taken as well, in any mix with POPPY_FRAME_JPEG frames (the `MJPG` stream does not care): a frame whose SOF0 gives component 1
  * the sampling byte 0x11 is held to POPPY_FRAME_JPEG444's capacity, any other to POPPY_FRAME_JPEG's; nothing else about the sink differs.
- * PNG: one PNG file per frame from POPPY_FRAME_PNG frames as they come; `path` follows PPM's %d rule exactly.  The file holds the frame's bytes 4 .. total as they
- * are.  The stride must be 0, bytes 4..11 the PNG signature, IHDR must name the sink's width and height, and `total` must be inside the format's capacity.  A frame
+ * PNG: one PNG file per frame from POPPY_FRAME_PNG and POPPY_FRAME_PNG_RUNS frames as they come, in any mix (a PNG file does not say who coded it); `path` follows
+ * PPM's %d rule exactly.  The file holds the frame's bytes 4 .. total as they are.  The stride must be 0, bytes 4..11 the PNG signature, IHDR must name the sink's
+ * width and height, and `total` must be inside the larger of the two formats' capacities.  A frame
  * of any other format fails this sink, and a PNG frame fails every other sink.
  * The BGR sinks take frames with stride >= 3 * width, the I420 and GIF sinks frames with stride == width: a frame of another format fails the
  * sink where its stride tells (a BGR frame at the I420 or GIF sink, an I420 or PAL8 frame at a BGR sink); a writer must match the context's format.

@@ -26,12 +26,13 @@ PYRAMID_FORMS = ("down", "down2", "tail", "tail_nl", "mix_top", "cone", "up2", "
 WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_size_t)
 # formats of the frames handed to writers (poppy_hip_set_frame_format) and the file sinks (poppy_sink_open)
 FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444 = 0, 1, 8, 16, 64, 128, 256, 512
-FRAME_PNG = 1024
-FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444, FRAME_PNG)      # a frame whose length its first four bytes hold
+FRAME_PNG, FRAME_PNG_RUNS = 1024, 2048
+FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444, FRAME_PNG, FRAME_PNG_RUNS)      # a frame whose length its first four bytes hold
 JPEG_QUALITY_DEFAULT = 90
 SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED, SINK_GIF_GLOBAL_CODED, SINK_MJPEG = 0, 1, 2, 3, 8, 16, 64, 128, 256
 SINK_PNG = 1024
 PNG_SEGMENT_BYTES, PNG_TABLES, PNG_HEADER_BYTES = 8192, 8, 236
+PNG_RUN_MIN, PNG_RUNS_SYMBOLS = 8, 286
 
 # every symbol include/poppy_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -55,6 +56,7 @@ SYMBOLS = [
     "poppy_jpeg_frame_bytes", "poppy_i420_to_jpeg_frame", "poppy_bgr_to_jpeg_frame", "poppy_hip_i420_to_jpeg_frame", "poppy_hip_set_jpeg_quality", "poppy_hip_pool_set_jpeg_quality",
     "poppy_bgr_to_i444", "poppy_hip_bgr_to_i444", "poppy_i444_to_jpeg_frame", "poppy_bgr_to_jpeg444_frame", "poppy_hip_i444_to_jpeg_frame",
     "poppy_png_frame_bytes", "poppy_png_table", "poppy_bgr_to_png_frame", "poppy_hip_bgr_to_png_frame",
+    "poppy_png_runs_table", "poppy_bgr_to_png_runs_frame", "poppy_hip_bgr_to_png_runs_frame",
     "poppy_hip_set_frame_scale", "poppy_hip_pool_set_frame_scale", "poppy_frame_scaled_size", "poppy_bgr_downscale", "poppy_hip_bgr_downscale",
     "poppy_hip_set_frame_size", "poppy_hip_pool_set_frame_size", "poppy_frame_fit_size", "poppy_bgr_resize_area", "poppy_hip_bgr_resize_area",
     "poppy_hip_bgr_resize_area_form",
@@ -210,6 +212,9 @@ def lib():
         L.poppy_png_table.argtypes = [i, vp, vp, vp]
         L.poppy_bgr_to_png_frame.argtypes = [vp, sz, i, i, vp]
         L.poppy_hip_bgr_to_png_frame.argtypes = [vp, vp, sz, i, i, vp]
+        L.poppy_png_runs_table.argtypes = [i, vp, vp, vp]
+        L.poppy_bgr_to_png_runs_frame.argtypes = [vp, sz, i, i, vp]
+        L.poppy_hip_bgr_to_png_runs_frame.argtypes = [vp, vp, sz, i, i, vp]
         L.poppy_hip_set_frame_scale.argtypes = [vp, i]
         L.poppy_hip_pool_set_frame_scale.argtypes = [vp, i]
         L.poppy_frame_scaled_size.argtypes = [i, i, i, vp, vp]
@@ -387,7 +392,7 @@ def bgr_to_jpeg444_frame(bgr, quality=JPEG_QUALITY_DEFAULT):
 
 
 def png_frame_bytes(frame):
-    """Host-only: `total` of a FRAME_PNG frame, its length in bytes (poppy_png_frame_bytes: the first four bytes, little-endian)."""
+    """Host-only: `total` of a FRAME_PNG or FRAME_PNG_RUNS frame, its length in bytes (poppy_png_frame_bytes: the first four bytes, little-endian)."""
     f = np.ascontiguousarray(frame, np.uint8)
     if f.size < 4:
         raise PoppyError("png_frame_bytes: a coded frame has at least four bytes")
@@ -406,10 +411,22 @@ def png_table(k):
     return lengths, np.unpackbits(header, bitorder="little")[:n.value].copy()
 
 
+def png_runs_table(k):
+    """Host-only: table k of the FRAME_PNG_RUNS format (poppy_png_runs_table): its 286 code lengths (literal 0..255, end-of-block, the length symbols 257..285) as
+    a uint8 array, and its block header as an array of bits in stream order (bit 0 is BFINAL, left 0)."""
+    lengths = np.zeros(PNG_RUNS_SYMBOLS, np.uint8)
+    header = np.zeros(PNG_HEADER_BYTES, np.uint8)
+    n = C.c_int(0)
+    rc = lib().poppy_png_runs_table(int(k), _p(lengths), _p(header), C.byref(n))
+    if rc:
+        raise PoppyError(f"poppy_png_runs_table: {rc}")
+    return lengths, np.unpackbits(header, bitorder="little")[:n.value].copy()
+
+
 PNG_CANARY = 0xA5
 
 
-def _png_frame(call, what, bgr, row_pad, chk=None, whole=False):
+def _png_frame(call, what, bgr, row_pad, chk=None, whole=False, fmt=FRAME_PNG):
     a = np.ascontiguousarray(bgr, np.uint8)
     h, w = a.shape[:2]
     stride = w * 3 + int(row_pad)
@@ -417,7 +434,7 @@ def _png_frame(call, what, bgr, row_pad, chk=None, whole=False):
         buf = np.full((h, stride), 0xA5, np.uint8)
         buf[:, :w * 3] = a.reshape(h, w * 3)
         a = buf
-    out = np.full(max(frame_bytes(FRAME_PNG, w, h), 4) + 64, PNG_CANARY, np.uint8)
+    out = np.full(max(frame_bytes(fmt, w, h), 4) + 64, PNG_CANARY, np.uint8)
     rc = call(_p(a), stride, w, h, _p(out))
     if chk:
         chk(rc, what)
@@ -431,6 +448,12 @@ def bgr_to_png_frame(bgr, row_pad=0, whole=False):
     uint8 array of its own length.  row_pad: the frame is handed over with that many extra bytes per row.  whole: the whole destination buffer instead — the
     capacity and 64 bytes more, filled with PNG_CANARY before the call."""
     return _png_frame(lib().poppy_bgr_to_png_frame, "bgr_to_png_frame", bgr, row_pad, None, whole)
+
+
+def bgr_to_png_runs_frame(bgr, row_pad=0, whole=False):
+    """Host-only: the FRAME_PNG_RUNS frame of an HxWx3 BGR frame (poppy_bgr_to_png_runs_frame): bgr_to_png_frame's file with runs of equal bytes coded as matches;
+    row_pad and whole as there (the capacity is FRAME_PNG_RUNS's)."""
+    return _png_frame(lib().poppy_bgr_to_png_runs_frame, "bgr_to_png_runs_frame", bgr, row_pad, None, whole, FRAME_PNG_RUNS)
 
 
 def _gif_frames(call, chk, frames, row_pad, frame_pad):
@@ -534,7 +557,7 @@ def pal8_to_bgr(frame, w, h):
 
 
 def _frame_view(ptr, w, h, stride, fmt):
-    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF, GIF_SEQ, JPEG, JPEG444 and PNG.  A view: valid during the callback."""
+    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF, GIF_SEQ, JPEG, JPEG444, PNG and PNG_RUNS.  A view: valid during the callback."""
     if fmt in FRAMES_CODED:                                                      # a coded frame: its own length, not the capacity (every coded format keeps it in its first four bytes)
         return np.ctypeslib.as_array(ptr, shape=(int(lib().poppy_gif_frame_bytes(ptr)),))
     if fmt in (FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ):
@@ -1035,7 +1058,8 @@ class Context:
         FRAME_GIF_SEQ: FRAME_PAL8_SEQ's sequences with every frame coded like FRAME_GIF's, one palette in all frames of a call.
         FRAME_JPEG: every frame one baseline JPEG file, coded on the GPU at set_jpeg_quality's quality; flat arrays of each frame's own length (jpeg_frame_bytes).
         FRAME_JPEG444: the same with full-resolution chroma (4:4:4), coded from the frame's I444 planes.
-        FRAME_PNG: every frame one PNG file, lossless, coded on the GPU; flat arrays of each frame's own length (png_frame_bytes)."""
+        FRAME_PNG: every frame one PNG file, lossless, coded on the GPU; flat arrays of each frame's own length (png_frame_bytes).
+        FRAME_PNG_RUNS: the same with runs of equal bytes coded as matches: several times smaller on frames with flat or smooth regions."""
         self._chk(lib().poppy_hip_set_frame_format(self.h, int(fmt)), "set_frame_format")
         self.frame_format = int(fmt)
 
@@ -1062,6 +1086,11 @@ class Context:
         """The FRAME_PNG frame of an HxWx3 BGR frame, coded on this context's GPU (poppy_hip_bgr_to_png_frame: upload, the six kernels, download of `total` bytes):
         the bytes of the host's bgr_to_png_frame.  The low four bits of row_pad place the device copy of the source that many bytes behind a 256-byte boundary."""
         return _png_frame(lambda *args: lib().poppy_hip_bgr_to_png_frame(self.h, *args), "bgr_to_png_frame", bgr, row_pad, self._chk, whole)
+
+    def bgr_to_png_runs_frame(self, bgr, row_pad=0, whole=False):
+        """The FRAME_PNG_RUNS frame of an HxWx3 BGR frame, coded on this context's GPU (poppy_hip_bgr_to_png_runs_frame): the bytes of the host's
+        bgr_to_png_runs_frame.  row_pad and whole as in bgr_to_png_frame."""
+        return _png_frame(lambda *args: lib().poppy_hip_bgr_to_png_runs_frame(self.h, *args), "bgr_to_png_runs_frame", bgr, row_pad, self._chk, whole, FRAME_PNG_RUNS)
 
     def i444_to_jpeg_frame(self, i444, w, h, quality=JPEG_QUALITY_DEFAULT):
         """The FRAME_JPEG444 frame of flat I444 planes, coded on this context's GPU (poppy_hip_i444_to_jpeg_frame: upload, the two kernels, download): the bytes

@@ -7,17 +7,17 @@ static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned l
 constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 2^24 pixels";
 constexpr const char* kGifSizeMsg = "POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 65535 pixels in width and height";
 constexpr const char* kJpegSizeMsg = "POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 take frames of at most 65535 pixels in width and height whose capacity stays below 2^32 bytes";
-constexpr const char* kPngSizeMsg = "POPPY_FRAME_PNG takes frames whose capacity stays below 2^31 bytes";
+constexpr const char* kPngSizeMsg = "POPPY_FRAME_PNG and POPPY_FRAME_PNG_RUNS take frames whose capacity stays below 2^31 bytes";
 constexpr const char* kSeqSizeMsg = "POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ take sequences of fewer than 2^32 pixels in all";
 
 bool format_known(int fmt) {
-    return fmt == POPPY_FRAME_BGR || fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ || format_is_jpeg(fmt) || fmt == POPPY_FRAME_PNG;
+    return fmt == POPPY_FRAME_BGR || fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ || format_is_jpeg(fmt) || format_is_png(fmt);
 }
-size_t coded_frame_least(int fmt) { return format_is_jpeg(fmt) ? kJpegFrameMinBytes : fmt == POPPY_FRAME_PNG ? kPngFrameMinBytes : kGifFrameMinBytes; }
+size_t coded_frame_least(int fmt) { return format_is_jpeg(fmt) ? kJpegFrameMinBytes : format_is_png(fmt) ? kPngFrameMinBytes : kGifFrameMinBytes; }
 const char* format_refuses(int fmt, int W, int H) {
     if ((format_builds_palette(fmt) || format_is_sequence(fmt)) && !pal8_fits(W, H)) return kPal8SizeMsg;
     if (format_is_jpeg(fmt)) return jpeg_fits(W, H, format_sampling(fmt)) ? nullptr : kJpegSizeMsg;
-    if (fmt == POPPY_FRAME_PNG) return png_fits(W, H) ? nullptr : kPngSizeMsg;
+    if (format_is_png(fmt)) return png_fits(fmt, W, H) ? nullptr : kPngSizeMsg;
     if (format_is_coded(fmt) && (W > 65535 || H > 65535)) return kGifSizeMsg;
     return nullptr;
 }
@@ -88,7 +88,7 @@ static void free_slot_coded(SlotFormat& f) {
     f.coded_for = POPPY_FRAME_BGR;
 }
 
-// PNG: the coded frame, the coder's scratch and the pinned length word.  I420: the slot's I420 buffer.  JPEG: that, the coded frame, the coder's scratch, the pinned length word and the context's tables.  JPEG444: the same with the slot's I444 buffer in the I420 buffer's place.  PAL8: its PAL8 buffer, tables, side stream and event.  GIF: PAL8's (the coder reads the slot's PAL8 frame) and the coded frame, the
+// PNG, PNG_RUNS: the coded frame, the coder's scratch and the pinned length word.  I420: the slot's I420 buffer.  JPEG: that, the coded frame, the coder's scratch, the pinned length word and the context's tables.  JPEG444: the same with the slot's I444 buffer in the I420 buffer's place.  PAL8: its PAL8 buffer, tables, side stream and event.  GIF: PAL8's (the coder reads the slot's PAL8 frame) and the coded frame, the
 // coder's scratch and the pinned length word.  PAL8_SEQ and GIF_SEQ: the slots' side streams and the context's sequence tables — the store and the index ring depend on the
 // sequence's length and, under GIF_SEQ, the ring of coded frames: palette_seq.cpp's seq_begin, seq_finish.  All of it in the writer's geometry; with a scale above 1 or a size the scaled BGR frame too.
 int alloc_slot_format(poppy_hip_ctx* c) {
@@ -110,7 +110,7 @@ int alloc_slot_format(poppy_hip_ctx* c) {
         if (f.coded_for != fmt) free_slot_coded(f);                 // (sized for another coded format; the frames are drained and the bodies of that format are captured again)
         f.coded_for = fmt;
         if (!f.coded) HIPCHK(c, hipMalloc((void**)&f.coded, poppy_frame_bytes(fmt, W, H) + 16));
-        if (!f.coded_scratch) HIPCHK(c, hipMalloc((void**)&f.coded_scratch, format_is_jpeg(fmt) ? jpeg_scratch_bytes(W, H, format_sampling(fmt)) : fmt == POPPY_FRAME_PNG ? png_scratch_bytes(W, H) : gif_scratch_bytes(W, H)));
+        if (!f.coded_scratch) HIPCHK(c, hipMalloc((void**)&f.coded_scratch, format_is_jpeg(fmt) ? jpeg_scratch_bytes(W, H, format_sampling(fmt)) : format_is_png(fmt) ? png_scratch_bytes(W, H, fmt == POPPY_FRAME_PNG_RUNS) : gif_scratch_bytes(W, H)));
         if (!f.coded_total) {
             HIPCHK(c, hipHostMalloc((void**)&f.coded_total, 64, hipHostMallocMapped));
             HIPCHK(c, hipHostGetDevicePointer(&f.coded_total_dev, f.coded_total, 0));
@@ -145,7 +145,7 @@ bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt, c
     if (format_is_jpeg(fmt)) return (fmt == POPPY_FRAME_JPEG444 ? f.i444 : f.i420) && f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt && f.jpeg_tables;
     if (format_is_sequence(fmt)) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
     if (format_builds_palette(fmt) && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) return false;
-    return !format_codes_per_frame(fmt) || (f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt);      // (GIF, PNG)
+    return !format_codes_per_frame(fmt) || (f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt);      // (GIF, PNG, PNG_RUNS)
 }
 const uint8_t* slot_bgr(const FrameSlot& f, const WriterGeom& g) { return g.scaled() ? f.fmt.scaled : f.out; }
 const uint8_t* slot_frame(const FrameSlot& f, int fmt, const WriterGeom& g) {
@@ -170,18 +170,19 @@ void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8_t* scr
     if (tm) tm->mark("jpeg_pack");
 }
 
-void enqueue_png_coding(const uint8_t* bgr, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
-    launch_png_filter(bgr, scratch, W, H, s);
+void enqueue_png_coding(int fmt, const uint8_t* bgr, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
+    const bool runs = fmt == POPPY_FRAME_PNG_RUNS;
+    launch_png_filter(bgr, scratch, W, H, runs, s);
     if (tm) tm->mark("png_filter");
-    launch_png_cost(scratch, W, H, s);
+    launch_png_cost(scratch, W, H, runs, s);
     if (tm) tm->mark("png_cost");
-    launch_png_scan(scratch, frame, W, H, s);
+    launch_png_scan(scratch, frame, W, H, runs, s);
     if (tm) tm->mark("png_scan");
-    launch_png_pack(scratch, frame, W, H, s);
+    launch_png_pack(scratch, frame, W, H, runs, s);
     if (tm) tm->mark("png_pack");
-    launch_png_crc(scratch, frame, W, H, s);
+    launch_png_crc(scratch, frame, W, H, runs, s);
     if (tm) tm->mark("png_crc");
-    launch_png_finish(scratch, frame, (uint32_t*)total_dev, W, H, s, done);
+    launch_png_finish(scratch, frame, (uint32_t*)total_dev, W, H, runs, s, done);
     if (tm) tm->mark("png_finish");
 }
 
@@ -200,8 +201,8 @@ void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, in
         launch_bgr_to_i444(src_bgr, b.i444, W, H, s);
         if (tm) tm->mark("frame_format");
         enqueue_jpeg_coding(b.i444, b.jpeg_tables, b.coded_scratch, b.coded, b.coded_total_dev, W, H, jpeg::k444, s, done, tm);
-    } else if (fmt == POPPY_FRAME_PNG) {                           // straight from the BGR frame
-        enqueue_png_coding(src_bgr, b.coded_scratch, b.coded, b.coded_total_dev, W, H, s, done, tm);
+    } else if (format_is_png(fmt)) {                               // straight from the BGR frame
+        enqueue_png_coding(fmt, src_bgr, b.coded_scratch, b.coded, b.coded_total_dev, W, H, s, done, tm);
     } else if (format_builds_palette(fmt)) {
         // PAL8 is three dispatches, and the palette build in the middle is one workgroup's serial work (about as long as the rest of the frame)
         const bool gif = fmt == POPPY_FRAME_GIF;

@@ -10,15 +10,15 @@ struct poppy_hip_ctx; struct FrameSlot; struct Timer;
 
 bool format_known(int fmt);
 const char* format_refuses(int fmt, int W, int H);      // why `fmt` refuses a W x H frame, or null: checked on the arguments alone, before anything is allocated or any state changes
-size_t writer_stride(int fmt, int W);      // what the writer is told: 0 for a coded frame (GIF, JPEG, JPEG444, PNG), the width for the planar and palette formats, 3 * width for BGR
+size_t writer_stride(int fmt, int W);      // what the writer is told: 0 for a coded frame (GIF, JPEG, JPEG444, PNG, PNG_RUNS), the width for the planar and palette formats, 3 * width for BGR
 // a palette per frame: the PAL8 triple (histogram, build, index plane) converts it — GIF is PAL8 with the two coding dispatches behind the index plane
 inline bool format_builds_palette(int fmt) { return fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF; }
 // a frame whose length its bytes decide: poppy_frame_bytes is its capacity, the slot's pinned word holds its length (slot_frame_length)
 // (GIF_SEQ: the pinned word is the sequence ring buffer's, seq_finish)
-inline bool format_is_coded(int fmt) { return fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ || format_is_jpeg(fmt) || fmt == POPPY_FRAME_PNG; }
+inline bool format_is_coded(int fmt) { return fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ || format_is_jpeg(fmt) || format_is_png(fmt); }
 // a coded frame of the slot's own, built by a coder and a pack dispatch behind the conversion: GIF behind the PAL8 triple, JPEG behind the I420 kernel, JPEG444
-// behind the I444 kernel (format_is_jpeg, format_sampling: frame_limits.h), PNG straight from the BGR frame (six dispatches, no raster form in between)
-inline bool format_codes_per_frame(int fmt) { return fmt == POPPY_FRAME_GIF || format_is_jpeg(fmt) || fmt == POPPY_FRAME_PNG; }
+// behind the I444 kernel (format_is_jpeg, format_sampling: frame_limits.h), PNG and PNG_RUNS straight from the BGR frame (six dispatches, no raster form in between)
+inline bool format_codes_per_frame(int fmt) { return fmt == POPPY_FRAME_GIF || format_is_jpeg(fmt) || format_is_png(fmt); }
 // the frame in the slot's I420 buffer: the writer's frame itself, or what the JPEG coder reads
 inline bool format_converts_to_i420(int fmt) { return fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_JPEG; }
 size_t coded_frame_least(int fmt);      // the smallest `total` a coder of the format gives (coded_length_ok's lower bound)
@@ -53,7 +53,7 @@ struct SlotFormat {
     uint8_t* i444 = nullptr;              // POPPY_FRAME_JPEG444: the frame's I444 planes, 3 * w * h bytes, which its coder reads (allocated and kept like i420)
     uint8_t* pal8 = nullptr;              // the frame as PAL8 for the writer, and the conversion's tables (kernels.h: kPal8TableBytes) — the slot's own,
     uint8_t* pal8_tables = nullptr;       // because the conversions of frames in flight run beside each other (allocated like i420; the stream and event live as long as the context)
-    uint8_t* coded = nullptr;             // POPPY_FRAME_GIF, POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444, POPPY_FRAME_PNG: the coded frame for the writer (its capacity: poppy_frame_bytes), the coder's scratch (kernels.h:
+    uint8_t* coded = nullptr;             // POPPY_FRAME_GIF, POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444, POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS: the coded frame for the writer (its capacity: poppy_frame_bytes), the coder's scratch (kernels.h:
     uint8_t* coded_scratch = nullptr;     // gif_scratch_bytes, jpeg_scratch_bytes, png_scratch_bytes) and a word of mapped pinned memory that the pack kernel stores the frame's length into: the host
     uint32_t* coded_total = nullptr;      // reads it when `done` has fired and copies that many bytes (the GIF coder reads the slot's pal8, the JPEG coder its i420, the JPEG444 coder its i444, the PNG coder the BGR frame itself); the three
     void* coded_total_dev = nullptr;      // are sized by coded_for, the format they were allocated under, and allocated again when the context's coded format is another
@@ -82,8 +82,9 @@ void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* frame, v
 // kernels.h: kJpegTableBytes) name; the rest as for GIF
 void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, poppy_hip::jpeg::Sampling sm, hipStream_t s, hipEvent_t done, Timer* tm);
 // the PNG chain: the BGR frame (tight, any alignment) coded into `frame` by the six dispatches of kernels_frame_png.hip; tm gets the marks png_filter, png_cost,
-// png_scan, png_pack, png_crc, png_finish; the rest as for GIF
-void enqueue_png_coding(const uint8_t* bgr, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm);
+// png_scan, png_pack, png_crc, png_finish; the rest as for GIF.  fmt == POPPY_FRAME_PNG_RUNS: the run-aware cost and pack kernels in the places of the two, the
+// same marks (scratch and frame sized for that format)
+void enqueue_png_coding(int fmt, const uint8_t* bgr, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm);
 // the context's quantisation tables and header for its quality on the device, at an address that stays (captured bodies hold it): allocated and filled when missing
 int ensure_jpeg_tables(poppy_hip_ctx* c);
 // conversion tables, zero before the first frame (the palette builds leave them zero again): PAL8's per slot and for the scratch, the sequence's per context

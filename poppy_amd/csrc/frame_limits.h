@@ -3,7 +3,7 @@
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "jpeg_tables.h"
-#include "png_tables.h"
+#include "png_runs_tables.h"
 
 // poppy_hip_set_frame_size's rule (include/poppy_hip.h): ow x oh is no larger than W x H and at most POPPY_FRAME_SCALE_MAX times smaller per side (so W, H >= 1 too)
 inline bool size_admits(int W, int H, int ow, int oh) {
@@ -30,3 +30,9 @@ inline poppy_hip::jpeg::Sampling format_sampling(int fmt) { return fmt == POPPY_
 inline bool png_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
 inline size_t png_frame_capacity(size_t w, size_t h) { return (size_t)poppy_hip::png::frame_capacity(w, h); }
 constexpr size_t kPngFrameMinBytes = poppy_hip::png::kFrameMinBytes;
+// The two PNG formats: POPPY_FRAME_PNG_RUNS is POPPY_FRAME_PNG with runs coded as matches (png_runs_tables.h), the same limits on its own capacity
+inline bool format_is_png(int fmt) { return fmt == POPPY_FRAME_PNG || fmt == POPPY_FRAME_PNG_RUNS; }
+inline bool png_runs_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png_runs::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
+inline size_t png_runs_frame_capacity(size_t w, size_t h) { return (size_t)poppy_hip::png_runs::frame_capacity(w, h); }
+inline bool png_fits(int fmt, int W, int H) { return fmt == POPPY_FRAME_PNG_RUNS ? png_runs_fits(W, H) : png_fits(W, H); }
+inline size_t png_frame_capacity(int fmt, size_t w, size_t h) { return fmt == POPPY_FRAME_PNG_RUNS ? png_runs_frame_capacity(w, h) : png_frame_capacity(w, h); }

@@ -1,10 +1,10 @@
 // frame_png.cpp — the library's definition of the POPPY_FRAME_PNG hand-off format in plain C++ (include/poppy_hip.h has the rule): a BGR frame as one PNG file
 // whose IDAT is a zlib stream of Huffman-only dynamic blocks, a block per POPPY_PNG_SEGMENT_BYTES of the filtered stream, each on one of the eight tables of
 // png_tables.h.  kernels_frame_png.hip computes the same bytes on the device; tests/test_host_png.py pins these to a numpy restatement of the rule and to
-// zlib's and Pillow's decoders.  Host only, integer arithmetic only.
-#include "frame_limits.h"
+// zlib's and Pillow's decoders.  The filtered stream and the file's fixed parts are functions of their own (frame_png.h): POPPY_FRAME_PNG_RUNS (frame_png_runs.cpp)
+// is the same file around other deflate blocks.  Host only, integer arithmetic only.
+#include "frame_png.h"
 #include <cstring>
-#include <vector>
 
 namespace poppy_hip {
 namespace png {
@@ -35,23 +35,11 @@ inline uint8_t filtered(const uint8_t* row, const uint8_t* above, int j, int typ
     return (uint8_t)(cur - pred);
 }
 
-// the deflate bits, packed from bit 0 of byte 0 up
-struct BitWriter {
-    uint8_t* p;
-    size_t at = 0;
-    unsigned long long acc = 0; int n_acc = 0;
-    void put(uint32_t value, int n) {                       // n <= 32, value's low n bits
-        acc |= (unsigned long long)value << n_acc; n_acc += n;
-        while (n_acc >= 8) { p[at++] = (uint8_t)acc; acc >>= 8; n_acc -= 8; }
-    }
-    void pad() { if (n_acc) put(0, 8 - n_acc); }
-};
-
 }  // namespace
 
-size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst) {
-    const size_t row_bytes = 3 * (size_t)w, n = (size_t)stream_bytes((size_t)w, (size_t)h);
-    std::vector<uint8_t> stream(n);
+std::vector<uint8_t> filter_frame(const uint8_t* bgr, size_t stride, int w, int h) {
+    const size_t row_bytes = 3 * (size_t)w;
+    std::vector<uint8_t> stream((size_t)stream_bytes((size_t)w, (size_t)h));
     for (int y = 0; y < h; ++y) {
         const uint8_t *row = bgr + (size_t)y * stride, *above = y ? row - stride : nullptr;
         int best = 0; unsigned long long best_score = 0;
@@ -64,6 +52,10 @@ size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst)
         out[0] = (uint8_t)best;
         for (size_t j = 0; j < row_bytes; ++j) out[1 + j] = filtered(row, above, (int)j, best);
     }
+    return stream;
+}
+
+void frame_head(uint8_t* dst, int w, int h) {
     memcpy(dst + kOffSignature, kSignature, 8);
     uint8_t* ihdr = dst + kOffIhdr;
     put32(ihdr, 13); memcpy(ihdr + 4, "IHDR", 4); put32(ihdr + 8, (uint32_t)w); put32(ihdr + 12, (uint32_t)h);
@@ -71,6 +63,23 @@ size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst)
     put32(ihdr + 21, crc32_of(ihdr + 4, 17));
     memcpy(dst + kOffIdatType, "IDAT", 4);
     dst[kOffIdatType + 4] = 0x78; dst[kOffIdatType + 5] = 0x01;
+}
+
+size_t frame_tail(uint8_t* dst, size_t deflate_bytes, uint32_t adler) {
+    const size_t end = kStreamByte + deflate_bytes;         // behind the deflate bytes: Adler-32, the chunk's CRC, IEND
+    put32(dst + end, adler);
+    put32(dst + kOffIdat, (uint32_t)(end + 4 - (kOffIdatType + 4)));
+    put32(dst + end + 4, crc32_of(dst + kOffIdatType, end + 4 - kOffIdatType));
+    memcpy(dst + end + 8, kIend, 12);
+    const size_t total = end + kTailBytes;
+    dst[0] = (uint8_t)total; dst[1] = (uint8_t)(total >> 8); dst[2] = (uint8_t)(total >> 16); dst[3] = (uint8_t)(total >> 24);
+    return total;
+}
+
+size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst) {
+    const std::vector<uint8_t> stream = filter_frame(bgr, stride, w, h);
+    const size_t n = stream.size();
+    frame_head(dst, w, h);
     BitWriter bits{dst + kStreamByte};
     uint32_t adler_a = 1, adler_b = 0;
     for (size_t first = 0; first < n; first += kSegment) {
@@ -94,14 +103,7 @@ size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst)
         bits.put(kCodes.e[table][kEob] >> 4, (int)(kCodes.e[table][kEob] & 15u));
     }
     bits.pad();
-    const size_t end = kStreamByte + bits.at;               // behind the deflate bytes: Adler-32, the chunk's CRC, IEND
-    put32(dst + end, adler_b << 16 | adler_a);
-    put32(dst + kOffIdat, (uint32_t)(end + 4 - (kOffIdatType + 4)));
-    put32(dst + end + 4, crc32_of(dst + kOffIdatType, end + 4 - kOffIdatType));
-    memcpy(dst + end + 8, kIend, 12);
-    const size_t total = end + kTailBytes;
-    dst[0] = (uint8_t)total; dst[1] = (uint8_t)(total >> 8); dst[2] = (uint8_t)(total >> 16); dst[3] = (uint8_t)(total >> 24);
-    return total;
+    return frame_tail(dst, bits.at, adler_b << 16 | adler_a);
 }
 
 }  // namespace png

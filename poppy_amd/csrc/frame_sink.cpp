@@ -11,7 +11,7 @@
 //   POPPY_SINK_GIF_CODED   POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames, whose image data arrives coded (frame_gif.cpp, kernels_frame_gif.hip): nothing is coded here
 //   POPPY_SINK_GIF_GLOBAL_CODED  POPPY_SINK_GIF_GLOBAL's file from coded frames (POPPY_FRAME_GIF_SEQ): the first frame's palette as the global table, local tables only where a palette differs
 //   POPPY_SINK_MJPEG  one RIFF AVI file, a `vids` / `MJPG` stream, from POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames, whose bytes arrive coded (frame_jpeg.cpp, kernels_frame_jpeg.hip)
-//   POPPY_SINK_PNG   one PNG file per frame from POPPY_FRAME_PNG frames, whose bytes arrive coded (frame_png.cpp, kernels_frame_png.hip); the path as under PPM
+//   POPPY_SINK_PNG   one PNG file per frame from POPPY_FRAME_PNG and POPPY_FRAME_PNG_RUNS frames, whose bytes arrive coded (frame_png.cpp, frame_png_runs.cpp, kernels_frame_png.hip); the path as under PPM
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "frame_limits.h"
 #include "gif_lzw.h"
@@ -192,11 +192,12 @@ std::string numbered_name(const poppy_sink* s) {
     return s->path + num + s->tail;
 }
 
-// a POPPY_FRAME_PNG frame: its bytes 4 .. total as one file, once the signature, IHDR's size and `total` are what the sink's size allows
+// a POPPY_FRAME_PNG or POPPY_FRAME_PNG_RUNS frame (the file does not say which: `total` is held to the larger capacity): its bytes 4 .. total as one file, once
+// the signature, IHDR's size and `total` are what the sink's size allows
 bool png_frame(poppy_sink* s, const uint8_t* frame) {
     using namespace poppy_hip::png;
     const size_t total = poppy_png_frame_bytes(frame);
-    if (total < kPngFrameMinBytes || total > poppy_frame_bytes(POPPY_FRAME_PNG, s->w, s->h) || memcmp(frame + kOffSignature, kSignature, 8) != 0) return false;
+    if (total < kPngFrameMinBytes || total > std::max(poppy_frame_bytes(POPPY_FRAME_PNG, s->w, s->h), poppy_frame_bytes(POPPY_FRAME_PNG_RUNS, s->w, s->h)) || memcmp(frame + kOffSignature, kSignature, 8) != 0) return false;
     const uint8_t* ihdr = frame + kOffIhdr;
     const uint32_t w = (uint32_t)ihdr[8] << 24 | (uint32_t)ihdr[9] << 16 | (uint32_t)ihdr[10] << 8 | ihdr[11], h = (uint32_t)ihdr[12] << 24 | (uint32_t)ihdr[13] << 16 | (uint32_t)ihdr[14] << 8 | ihdr[15];
     if (memcmp(ihdr + 4, "IHDR", 4) != 0 || w != (uint32_t)s->w || h != (uint32_t)s->h) return false;
@@ -238,7 +239,7 @@ size_t poppy_frame_bytes(int format, int width, int height) {
     if (format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ) return w * h + 768;
     if (format == POPPY_FRAME_GIF || format == POPPY_FRAME_GIF_SEQ) return gif_frame_capacity(w, h);      // (frame_limits.h, beside the smallest coded frame)
     if (format_is_jpeg(format)) return jpeg_frame_capacity(w, h, format_sampling(format));
-    if (format == POPPY_FRAME_PNG) return png_fits(width, height) ? png_frame_capacity(w, h) : 0;      // (nothing to size where the format refuses)
+    if (format_is_png(format)) return png_fits(format, width, height) ? png_frame_capacity(format, w, h) : 0;      // (nothing to size where the format refuses)
     return 0;
 }
 
@@ -296,7 +297,7 @@ poppy_sink* poppy_sink_open(const char* path, int format, int width, int height,
         s->path = head; s->tail = tail;
     }
     if ((sink_is_gif(format) || format == POPPY_SINK_MJPEG) && (width > 65535 || height > 65535)) { s->failed = true; return s; }      // GIF's 16-bit screen, JPEG's 16-bit SOF0: every write fails, close says so
-    if (format == POPPY_SINK_PNG && !png_fits(width, height)) { s->failed = true; return s; }      // no such frame: every write fails, close says so
+    if (format == POPPY_SINK_PNG && !png_fits(width, height) && !png_runs_fits(width, height)) { s->failed = true; return s; }      // no such frame: every write fails, close says so
     if (format != POPPY_SINK_PPM && format != POPPY_SINK_PNG) {
         s->f = fopen(path, "wb");
         if (!s->f) { delete s; return nullptr; }

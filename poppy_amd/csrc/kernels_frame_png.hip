@@ -21,6 +21,17 @@
 //                 x^(256 t) modulo the generator, an XOR over the workgroup: a word per 8192 bytes.
 //   k_png_finish  one workgroup: the words multiplied into place and XORed, the initial and final inversions, the CRC's four bytes, `total` into the word of
 //                 mapped pinned host memory.
+// POPPY_FRAME_PNG_RUNS (png_runs_tables.h; poppy_bgr_to_png_runs_frame in frame_png_runs.cpp is its host statement) is the same six dispatches with two kernels
+// of its own in the places of k_png_cost and k_png_pack; the filter, the scan, the CRC and the finish are the kernels above, on that format's capacity:
+//   k_png_run_cost  the same workgroup per segment and 32 bytes per thread.  A thread marks its breaks (a byte that differs from the one before it, the
+//                 segment's first byte, the segment's end) in one 32-bit mask; a forward max-scan of the threads' last breaks and a backward min-scan of their
+//                 first breaks over the workgroup tell it where the run of its first byte begins and where the run of its last byte ends.  From a run's start and
+//                 length and its own offset every byte decides by itself what it is (png_runs::token_at): a literal, the head of a match, or covered by one.  A
+//                 thread counts the tokens that BEGIN in its bytes: eight sums of nibbles from one LDS word per symbol (286 now), and the matches' extra and
+//                 distance bits, which are the same under every table.  The Adler pair is a function of the bytes, as before.
+//   k_png_run_pack  the same walk again on the chosen table, first for the thread's bit count, then, behind the workgroup's prefix sum, for the bits: a match is
+//                 its length code and one more field of extra bits + 1 (the distance code's 0 bit on top), 15 + 6 bits at the most, so the 64-bit
+//                 accumulator holds as it does for literals.
 // Plain vector stores and atomics only.
 #include "kernels.h"
 #include <hip/hip_ext.h>
@@ -34,6 +45,7 @@ using namespace png;
 constexpr int kThreads = 256, kBytesPerThread = (int)kSegment / kThreads;
 static_assert(kBytesPerThread == 32, "a thread takes two 16-byte loads of its segment");
 constexpr int kImageWords = (int)((31 + kSegmentBitsMax + 31) / 32) + 1;      // a block at its bound behind 31 bits of offset, and the word a flush may touch
+constexpr int kRunImageWords = (int)((31 + png_runs::kSegmentBitsMax + 31) / 32) + 1;
 constexpr size_t kCrcBlock = 32 * kThreads;                 // bytes of the chunk per workgroup of k_png_crc
 constexpr unsigned long long kFirstBit = 8 * kStreamByte;
 
@@ -42,6 +54,13 @@ constexpr NibbleTable make_nibbles() {
     NibbleTable t{};
     for (int v = 0; v < 256; ++v)
         for (int k = 0; k < kTables; ++k) t.e[v] |= (uint32_t)kLen[k][v] << (4 * k);
+    return t;
+}
+struct RunNibbleTable { uint32_t e[png_runs::kSymbols]; };      // the same per symbol of POPPY_FRAME_PNG_RUNS
+constexpr RunNibbleTable make_run_nibbles() {
+    RunNibbleTable t{};
+    for (int v = 0; v < png_runs::kSymbols; ++v)
+        for (int k = 0; k < kTables; ++k) t.e[v] |= (uint32_t)png_runs::kLen[k][v] << (4 * k);
     return t;
 }
 struct CrcShifts { uint32_t e[kThreads]; };                 // e[t] = x^(8 * 32 * t): what lies behind thread t's piece inside its workgroup
@@ -73,6 +92,18 @@ constexpr BlockOver make_block_over() {
     for (int k = 0; k < kTables; ++k) { b.header[k] = (uint32_t)kHeaderBits[k]; b.over[k] = (uint32_t)kHeaderBits[k] + kLen[k][kEob]; }
     return b;
 }
+struct RunHeaderWords { uint32_t e[kTables][png_runs::kHeaderWords]; };
+constexpr RunHeaderWords make_run_header_words() {
+    RunHeaderWords h{};
+    for (int k = 0; k < kTables; ++k)
+        for (int i = 0; i < png_runs::kHeaderWords; ++i) h.e[k][i] = png_runs::kHeader[k][i];
+    return h;
+}
+constexpr BlockOver make_run_block_over() {
+    BlockOver b{};
+    for (int k = 0; k < kTables; ++k) { b.header[k] = (uint32_t)png_runs::kHeaderBits[k]; b.over[k] = (uint32_t)png_runs::kHeaderBits[k] + png_runs::kLen[k][kEob]; }
+    return b;
+}
 
 struct FixedBytes { uint8_t signature[8], iend[12]; };
 constexpr FixedBytes make_fixed_bytes() {
@@ -87,6 +118,10 @@ __constant__ NibbleTable c_nibbles = make_nibbles();
 __constant__ Codes c_codes = make_codes();
 __constant__ HeaderWords c_header = make_header_words();
 __constant__ BlockOver c_block = make_block_over();
+__constant__ RunNibbleTable c_run_nibbles = make_run_nibbles();
+__constant__ png_runs::Codes c_run_codes = png_runs::make_codes();
+__constant__ RunHeaderWords c_run_header = make_run_header_words();
+__constant__ BlockOver c_run_block = make_run_block_over();
 __constant__ CrcTable c_crc = make_crc_table();
 __constant__ CrcShifts c_crc_shift = make_crc_shifts();
 __constant__ CrcPowers c_crc_pow = make_crc_powers();
@@ -100,15 +135,16 @@ struct Scratch {
     uint32_t* crc;                      // per kCrcBlock of the chunk, counted from its end: the raw remainder
     uint32_t* meta;                     // [0] the frame's byte behind the deflate data (Adler-32's place), [1] whether the frame is inside its capacity
 };
-size_t crc_blocks(int w, int h) { return (size_t)((frame_capacity((size_t)w, (size_t)h) + kCrcBlock - 1) / kCrcBlock); }
-Scratch scratch_of(uint8_t* p, int w, int h) {
+unsigned long long capacity_of(int w, int h, bool runs) { return runs ? png_runs::frame_capacity((size_t)w, (size_t)h) : frame_capacity((size_t)w, (size_t)h); }
+size_t crc_blocks(int w, int h, bool runs) { return (size_t)((capacity_of(w, h, runs) + kCrcBlock - 1) / kCrcBlock); }
+Scratch scratch_of(uint8_t* p, int w, int h, bool runs) {
     const size_t n_seg = (size_t)segment_count((size_t)w, (size_t)h);
     Scratch s;
     s.stream = p;
     s.seg = (uint4*)(p + n_seg * kSegment);
     s.start = (unsigned long long*)(s.seg + n_seg);
     s.crc = (uint32_t*)(s.start + n_seg);
-    s.meta = s.crc + crc_blocks(w, h);
+    s.meta = s.crc + crc_blocks(w, h, runs);
     return s;
 }
 
@@ -139,6 +175,85 @@ __device__ __forceinline__ uint32_t group_scan(uint32_t v, uint32_t* part, uint3
     *all = part[0] + part[1] + part[2] + part[3];
     __syncthreads();
     return before + incl - v;
+}
+
+// Where the run that holds a thread's first byte begins and where the run that holds its last byte ends, from the threads' own breaks: `last` is 1 + the position
+// of the thread's last break (0: it has none), `first` the position of its first (0xFFFFFFFF: none).  *begin: the largest `last` of the threads in front of this
+// one (0 in thread 0); *end: the smallest `first` of the threads behind it.  (part: 8 words of LDS, free again behind the call)
+__device__ __forceinline__ void group_run_bounds(uint32_t last, uint32_t first, uint32_t* part, uint32_t* begin, uint32_t* end) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    uint32_t hi = last, lo = first;
+    #pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t u = __shfl_up(hi, d, 64), v = __shfl_down(lo, d, 64);
+        if (lane >= d) hi = max(hi, u);
+        if (lane + d < 64) lo = min(lo, v);
+    }
+    if (lane == 63) part[wave] = hi;
+    if (lane == 0) part[4 + wave] = lo;
+    __syncthreads();
+    uint32_t b = __shfl_up(hi, 1, 64), e = __shfl_down(lo, 1, 64);
+    if (lane == 0) b = 0;
+    if (lane == 63) e = 0xFFFFFFFFu;
+    for (int k = 0; k < 4; ++k) {
+        if (k < wave) b = max(b, part[k]);
+        if (k > wave) e = min(e, part[4 + k]);
+    }
+    __syncthreads();
+    *begin = b; *end = e;
+}
+
+// A thread's 32 bytes of a segment of `len` bytes, at the segment's byte `at` (< len): `valid` of them lie in the segment; bit i of `brk` says that byte i begins
+// a run (it differs from the byte before it, or is the segment's first), and bit `valid`, where there is one, marks the segment's end.
+struct RunBytes { uint32_t word[8], brk; int valid; };
+__device__ __forceinline__ RunBytes load_run_bytes(const uint8_t* __restrict__ seg, uint32_t at, uint32_t len) {
+    RunBytes r;
+    const uint4* src = (const uint4*)(seg + at);
+    const uint4 lo = src[0], hi = src[1];
+    r.word[0] = lo.x; r.word[1] = lo.y; r.word[2] = lo.z; r.word[3] = lo.w; r.word[4] = hi.x; r.word[5] = hi.y; r.word[6] = hi.z; r.word[7] = hi.w;
+    r.valid = (int)(len - at < (uint32_t)kBytesPerThread ? len - at : (uint32_t)kBytesPerThread);
+    uint32_t before = at ? (uint32_t)seg[at - 1] : 256u;    // (the segment's first byte differs from everything)
+    r.brk = 0;
+    #pragma unroll
+    for (int i = 0; i < kBytesPerThread; ++i) {
+        const uint32_t d = (r.word[i >> 2] >> (8 * (i & 3))) & 255u;
+        r.brk |= (uint32_t)(d != before) << i;
+        before = d;
+    }
+    if (r.valid < kBytesPerThread) r.brk = (r.brk & ((1u << r.valid) - 1u)) | 1u << r.valid;
+    return r;
+}
+__device__ __forceinline__ uint32_t last_break(const RunBytes& r, uint32_t at) {
+    const uint32_t m = r.valid < kBytesPerThread ? r.brk & ((1u << r.valid) - 1u) : r.brk;
+    return m ? at + 32u - (uint32_t)__clz(m) : 0u;
+}
+__device__ __forceinline__ uint32_t first_break(const RunBytes& r, uint32_t at) { return r.brk ? at + (uint32_t)__ffs(r.brk) - 1u : 0xFFFFFFFFu; }
+
+// f(symbol, extra_bits, extra) for every token that begins in the thread's bytes, in order: a literal is its byte with no extra bits, a match its length symbol
+// (png_runs::match_of, with the leading bit from a count of zeros).  begin, end: group_run_bounds' of the thread's breaks; the segment's end bounds `end`.
+template <typename F>
+__device__ __forceinline__ void for_each_token(const RunBytes& r, uint32_t at, uint32_t len, uint32_t begin, uint32_t end, F&& f) {
+    const uint32_t run_in = begin - 1u, run_out = end < len ? end : len;      // (begin >= 1 where it is read: thread 0 has its break at byte 0)
+    uint32_t next = at;                                     // the place of the next token: a match moves it past what it covers
+    #pragma unroll
+    for (int i = 0; i < kBytesPerThread; ++i) {
+        const uint32_t p = at + (uint32_t)i;
+        if (i >= r.valid || p < next) continue;
+        const uint32_t lo = r.brk & (0xFFFFFFFFu >> (31 - i)), hi = i < 31 ? r.brk >> (i + 1) : 0u;
+        const uint32_t s = lo ? at + 31u - (uint32_t)__clz(lo) : run_in, e = hi ? p + (uint32_t)__ffs(hi) : run_out;
+        const int token = png_runs::token_at((int)(e - s), (int)(p - s));
+        if (token == 0) {
+            f((r.word[i >> 2] >> (8 * (i & 3))) & 255u, 0u, 0u);
+        } else if (token < 0) {
+            next = p + (uint32_t)-token;                    // covered by a match that began in a thread in front
+        } else {
+            next = p + (uint32_t)token;
+            const uint32_t l = (uint32_t)token - 3u;
+            if (token == 258) f(285u, 0u, 0u);
+            else if (l < 8u) f(257u + l, 0u, 0u);
+            else { const uint32_t eb = 29u - (uint32_t)__clz(l); f(261u + 4u * eb + ((l >> eb) & 3u), eb, l & ((1u << eb) - 1u)); }
+        }
+    }
 }
 
 __device__ __forceinline__ int paeth(int a, int b, int c) {
@@ -385,6 +500,112 @@ __global__ void __launch_bounds__(kThreads) k_png_pack(const uint8_t* __restrict
     }
 }
 
+__global__ void __launch_bounds__(kThreads) k_png_run_cost(const uint8_t* __restrict__ stream, uint4* __restrict__ seg_info, unsigned long long n) {
+    __shared__ uint32_t s_nib[png_runs::kSymbols];
+    __shared__ unsigned long long s_part[4];
+    __shared__ uint32_t s_bound[8];
+    const int t = threadIdx.x;
+    const size_t first = (size_t)blockIdx.x * kSegment;
+    const uint32_t len = (uint32_t)(n - first < kSegment ? n - first : kSegment);
+    for (int i = t; i < png_runs::kSymbols; i += kThreads) s_nib[i] = c_run_nibbles.e[i];
+    uint32_t cost[kTables] = {0, 0, 0, 0, 0, 0, 0, 0}, beside = 0, sum = 0, weighted = 0;
+    const uint32_t at = (uint32_t)t * kBytesPerThread;
+    const bool active = at < len;
+    RunBytes r{};
+    if (active) r = load_run_bytes(stream + first, at, len);
+    uint32_t begin = 0, end = 0;
+    group_run_bounds(active ? last_break(r, at) : 0u, active ? first_break(r, at) : 0xFFFFFFFFu, s_bound, &begin, &end);      // (its barrier stands behind s_nib's stores too)
+    if (active) {
+        for_each_token(r, at, len, begin, end, [&](uint32_t symbol, uint32_t extra_bits, uint32_t) {
+            const uint32_t v = s_nib[symbol];
+            #pragma unroll
+            for (int k = 0; k < kTables; ++k) cost[k] += (v >> (4 * k)) & 15u;
+            if (symbol > (uint32_t)kEob) beside += extra_bits + 1u;      // a match's extra bits and its distance code, whatever the table
+        });
+        #pragma unroll
+        for (int i = 0; i < kBytesPerThread; ++i) {
+            const uint32_t d = i < r.valid ? (r.word[i >> 2] >> (8 * (i & 3))) & 255u : 0u;
+            sum += d; weighted += (len - (at + i)) * d;      // (at most 32 * 8192 * 255: no overflow)
+        }
+    }
+    unsigned long long total[kTables];
+    #pragma unroll
+    for (int k = 0; k < kTables; ++k) total[k] = group_sum(cost[k] + beside, s_part);
+    const unsigned long long a = group_sum(sum, s_part), b = group_sum(weighted % kAdlerMod, s_part);
+    if (t == 0) {
+        int best = 0; unsigned long long least = 0;
+        for (int k = 0; k < kTables; ++k) {
+            const unsigned long long v = total[k] + c_run_block.over[k];
+            if (k == 0 || v < least) { best = k; least = v; }
+        }
+        seg_info[blockIdx.x] = make_uint4((uint32_t)best, (uint32_t)least, (uint32_t)a, (uint32_t)(b % kAdlerMod));
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_png_run_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const unsigned long long* __restrict__ seg_start,
+                                                           const uint32_t* __restrict__ meta, uint32_t* __restrict__ frame32, uint32_t n_seg, unsigned long long n,
+                                                           unsigned long long capacity) {
+    __shared__ uint32_t s_image[kRunImageWords];
+    __shared__ uint32_t s_code[png_runs::kSymbols];
+    __shared__ uint32_t s_part[4];
+    __shared__ uint32_t s_bound[8];
+    const int t = threadIdx.x;
+    const uint32_t seg = blockIdx.x;
+    const uint4 info = seg_info[seg];
+    const uint32_t table = info.x & (kTables - 1), bits = info.y;
+    if (!meta[1] || bits > png_runs::kSegmentBitsMax) return;      // (never: the scan found the frame inside its capacity, and table 7 bounds every block)
+    const unsigned long long start = seg_start[seg];
+    const size_t first = (size_t)seg * kSegment;
+    const uint32_t len = (uint32_t)(n - first < kSegment ? n - first : kSegment);
+    const uint32_t off = (uint32_t)start & 31u, n_words = (off + bits + 31) >> 5;
+    for (uint32_t i = t; i < n_words; i += kThreads) s_image[i] = 0;
+    for (int i = t; i < png_runs::kSymbols; i += kThreads) s_code[i] = c_run_codes.e[table][i];
+    __syncthreads();
+    const uint32_t header_bits = c_run_block.header[table];
+    for (uint32_t i = t; 32 * i < header_bits; i += kThreads) {      // the header, a word per thread (the bits behind H_k are zeros in the table)
+        const uint32_t v = c_run_header.e[table][i] | (i == 0 && seg == n_seg - 1 ? 1u : 0u), p = off + 32 * i;
+        atomicOr(&s_image[p >> 5], v << (p & 31));
+        if ((p & 31) && (v >> (32 - (p & 31)))) atomicOr(&s_image[(p >> 5) + 1], v >> (32 - (p & 31)));
+    }
+    const uint32_t at = (uint32_t)t * kBytesPerThread;
+    const bool active = at < len;
+    RunBytes r{};
+    if (active) r = load_run_bytes(stream + first, at, len);
+    uint32_t begin = 0, end = 0, count = 0;
+    group_run_bounds(active ? last_break(r, at) : 0u, active ? first_break(r, at) : 0xFFFFFFFFu, s_bound, &begin, &end);
+    if (active)
+        for_each_token(r, at, len, begin, end, [&](uint32_t symbol, uint32_t extra_bits, uint32_t) {
+            count += (s_code[symbol] & 15u) + (symbol > (uint32_t)kEob ? extra_bits + 1u : 0u);
+        });
+    uint32_t all = 0;
+    const uint32_t before = group_scan(count, s_part, &all);
+    if (active) {
+        const uint32_t p = off + header_bits + before;
+        uint32_t at_word = p >> 5;
+        int n_acc = (int)(p & 31);
+        unsigned long long acc = 0;
+        auto put = [&](uint32_t value, uint32_t width) {    // at most 15 bits behind fewer than 32 waiting ones
+            acc |= (unsigned long long)value << n_acc;
+            n_acc += (int)width;
+            if (n_acc >= 32) { atomicOr(&s_image[at_word++], (uint32_t)acc); acc >>= 32; n_acc -= 32; }
+        };
+        for_each_token(r, at, len, begin, end, [&](uint32_t symbol, uint32_t extra_bits, uint32_t extra) {
+            const uint32_t e = s_code[symbol];
+            put(e >> 4, e & 15u);
+            if (symbol > (uint32_t)kEob) put(extra, extra_bits + 1u);      // the extra bits, and the distance code's 0 bit on top of them
+        });
+        if (at + kBytesPerThread >= len) put(s_code[kEob] >> 4, s_code[kEob] & 15u);      // the thread of the segment's last byte: end-of-block
+        if (n_acc) atomicOr(&s_image[at_word], (uint32_t)acc);
+    }
+    __syncthreads();
+    const unsigned long long word0 = start >> 5, word_end = (start + bits) >> 5, cap_words = (capacity + 3) / 4;
+    for (uint32_t i = t; i < n_words; i += kThreads) {
+        const unsigned long long fw = word0 + i;
+        if (fw >= cap_words) continue;
+        if (fw == word0 || fw == word_end) atomicOr(&frame32[fw], s_image[i]); else frame32[fw] = s_image[i];
+    }
+}
+
 __global__ void __launch_bounds__(kThreads) k_png_crc(const uint8_t* __restrict__ frame, const uint32_t* __restrict__ meta, uint32_t* __restrict__ pieces) {
     __shared__ uint32_t s_table[256];
     __shared__ uint32_t s_part[4];
@@ -433,41 +654,41 @@ __global__ void __launch_bounds__(kThreads) k_png_finish(const uint32_t* __restr
     if (total_host) { *total_host = total; __threadfence_system(); }
 }
 
-size_t png_scratch_bytes(int w, int h) {
+size_t png_scratch_bytes(int w, int h, bool runs) {
     const size_t n_seg = (size_t)segment_count((size_t)w, (size_t)h);
-    return n_seg * (kSegment + sizeof(uint4) + 8) + crc_blocks(w, h) * 4 + 16 + 16;
+    return n_seg * (kSegment + sizeof(uint4) + 8) + crc_blocks(w, h, runs) * 4 + 16 + 16;
 }
 
-void launch_png_filter(const uint8_t* bgr, uint8_t* scratch, int w, int h, hipStream_t s) {
+void launch_png_filter(const uint8_t* bgr, uint8_t* scratch, int w, int h, bool runs, hipStream_t s) {
     const bool wide = w % 4 == 0 && (uintptr_t)bgr % 4 == 0;
-    hipLaunchKernelGGL(wide ? k_png_filter<true> : k_png_filter<false>, dim3((unsigned)h), dim3(kThreads), 0, s, bgr, scratch_of(scratch, w, h).stream, w);
+    hipLaunchKernelGGL(wide ? k_png_filter<true> : k_png_filter<false>, dim3((unsigned)h), dim3(kThreads), 0, s, bgr, scratch_of(scratch, w, h, runs).stream, w);
 }
-void launch_png_cost(uint8_t* scratch, int w, int h, hipStream_t s) {
-    const Scratch m = scratch_of(scratch, w, h);
-    hipLaunchKernelGGL(k_png_cost, dim3((unsigned)segment_count((size_t)w, (size_t)h)), dim3(kThreads), 0, s, (const uint8_t*)m.stream, m.seg, stream_bytes((size_t)w, (size_t)h));
+void launch_png_cost(uint8_t* scratch, int w, int h, bool runs, hipStream_t s) {
+    const Scratch m = scratch_of(scratch, w, h, runs);
+    hipLaunchKernelGGL(runs ? k_png_run_cost : k_png_cost, dim3((unsigned)segment_count((size_t)w, (size_t)h)), dim3(kThreads), 0, s, (const uint8_t*)m.stream, m.seg, stream_bytes((size_t)w, (size_t)h));
 }
-void launch_png_scan(uint8_t* scratch, uint8_t* frame, int w, int h, hipStream_t s) {
-    const Scratch m = scratch_of(scratch, w, h);
+void launch_png_scan(uint8_t* scratch, uint8_t* frame, int w, int h, bool runs, hipStream_t s) {
+    const Scratch m = scratch_of(scratch, w, h, runs);
     constexpr CrcTable table = make_crc_table();
     const uint8_t ihdr[17] = {'I', 'H', 'D', 'R', (uint8_t)(w >> 24), (uint8_t)(w >> 16), (uint8_t)(w >> 8), (uint8_t)w,
                               (uint8_t)(h >> 24), (uint8_t)(h >> 16), (uint8_t)(h >> 8), (uint8_t)h, 8, 2, 0, 0, 0};
     uint32_t c = 0xFFFFFFFFu;
     for (uint8_t byte : ihdr) c = table.e[(c ^ byte) & 255u] ^ (c >> 8);
     hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(kThreads), 0, s, (const uint4*)m.seg, m.start, m.meta, (uint32_t*)frame, (uint32_t)segment_count((size_t)w, (size_t)h),
-                       stream_bytes((size_t)w, (size_t)h), (uint32_t)w, (uint32_t)h, c ^ 0xFFFFFFFFu, frame_capacity((size_t)w, (size_t)h));
+                       stream_bytes((size_t)w, (size_t)h), (uint32_t)w, (uint32_t)h, c ^ 0xFFFFFFFFu, capacity_of(w, h, runs));
 }
-void launch_png_pack(const uint8_t* scratch, uint8_t* frame, int w, int h, hipStream_t s) {
-    const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h);
+void launch_png_pack(const uint8_t* scratch, uint8_t* frame, int w, int h, bool runs, hipStream_t s) {
+    const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h, runs);
     const uint32_t n_seg = (uint32_t)segment_count((size_t)w, (size_t)h);
-    hipLaunchKernelGGL(k_png_pack, dim3(n_seg), dim3(kThreads), 0, s, (const uint8_t*)m.stream, (const uint4*)m.seg, (const unsigned long long*)m.start, (const uint32_t*)m.meta,
-                       (uint32_t*)frame, n_seg, stream_bytes((size_t)w, (size_t)h), frame_capacity((size_t)w, (size_t)h));
+    hipLaunchKernelGGL(runs ? k_png_run_pack : k_png_pack, dim3(n_seg), dim3(kThreads), 0, s, (const uint8_t*)m.stream, (const uint4*)m.seg, (const unsigned long long*)m.start, (const uint32_t*)m.meta,
+                       (uint32_t*)frame, n_seg, stream_bytes((size_t)w, (size_t)h), capacity_of(w, h, runs));
 }
-void launch_png_crc(uint8_t* scratch, const uint8_t* frame, int w, int h, hipStream_t s) {
-    const Scratch m = scratch_of(scratch, w, h);
-    hipLaunchKernelGGL(k_png_crc, dim3((unsigned)crc_blocks(w, h)), dim3(kThreads), 0, s, frame, (const uint32_t*)m.meta, m.crc);
+void launch_png_crc(uint8_t* scratch, const uint8_t* frame, int w, int h, bool runs, hipStream_t s) {
+    const Scratch m = scratch_of(scratch, w, h, runs);
+    hipLaunchKernelGGL(k_png_crc, dim3((unsigned)crc_blocks(w, h, runs)), dim3(kThreads), 0, s, frame, (const uint32_t*)m.meta, m.crc);
 }
-void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, hipStream_t s, hipEvent_t done) {
-    const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h);
+void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, bool runs, hipStream_t s, hipEvent_t done) {
+    const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h, runs);
     hipExtLaunchKernelGGL(k_png_finish, dim3(1), dim3(kThreads), 0, s, nullptr, done, 0, (const uint32_t*)m.meta, (const uint32_t*)m.crc, frame, total_host);
 }
 

@@ -53,17 +53,17 @@ static int jpeg_from_device_planes(poppy_hip_ctx* c, const uint8_t* d_i420, cons
     return POPPY_OK;
 }
 
-// a tight BGR frame in device memory -> its POPPY_FRAME_PNG frame in `host` (exactly `total` bytes), on the context's stream and waited for: the frames that no slot
-// renders, and poppy_hip_bgr_to_png_frame.  The buffers live for the call.
-static int png_from_device_bgr(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host) {
-    const size_t cap = png_frame_capacity((size_t)W, (size_t)H);
+// a tight BGR frame in device memory -> its POPPY_FRAME_PNG or POPPY_FRAME_PNG_RUNS frame (fmt) in `host` (exactly `total` bytes), on the context's stream and waited
+// for: the frames that no slot renders, and poppy_hip_bgr_to_png_frame, poppy_hip_bgr_to_png_runs_frame.  The buffers live for the call, at fmt's capacity.
+static int png_from_device_bgr(poppy_hip_ctx* c, int fmt, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host) {
+    const size_t cap = png_frame_capacity(fmt, (size_t)W, (size_t)H);
     CallBuffers held;
     uint8_t *work = nullptr, *frame = nullptr;
-    hipError_t e = held.alloc(&work, png_scratch_bytes(W, H));
+    hipError_t e = held.alloc(&work, png_scratch_bytes(W, H, fmt == POPPY_FRAME_PNG_RUNS));
     if (e == hipSuccess) e = held.alloc(&frame, cap + 16);
     uint32_t total = 0;
     if (e == hipSuccess) {
-        enqueue_png_coding(d_bgr, work, frame, nullptr, W, H, c->stream, nullptr, nullptr);
+        enqueue_png_coding(fmt, d_bgr, work, frame, nullptr, W, H, c->stream, nullptr, nullptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
@@ -94,7 +94,7 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
     const uint8_t* d_frame = d_bgr;
     if (fmt != POPPY_FRAME_BGR) {                                  // converted into the context's scratch: the slots' launches on other buffers
         // (a coded format: its raster form into the scratch — PAL8 for GIF, I420 for JPEG, the I444 planes for JPEG444 —, then the coder on buffers that live for the call)
-        if (fmt == POPPY_FRAME_PNG) return png_from_device_bgr(c, d_bgr, W, H, host);      // (no raster form: the coder reads the BGR frame)
+        if (format_is_png(fmt)) return png_from_device_bgr(c, fmt, d_bgr, W, H, host);      // (no raster form: the coder reads the BGR frame)
         if (fmt == POPPY_FRAME_JPEG444) {                          // (I444 is no format of its own: the kernel is launched here)
             { int rc = ensure_jpeg_tables(c); if (rc) return rc; }
             HIPCHK(c, c->fmt_scratch.reserve((size_t)W * H * 3 + 16, c->stream));
@@ -134,6 +134,7 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
                    fmt == POPPY_FRAME_JPEG ? poppy_bgr_to_jpeg_frame(bgr, stride, W, H, c->jpeg_quality, tmp.data()) :
                    fmt == POPPY_FRAME_JPEG444 ? poppy_bgr_to_jpeg444_frame(bgr, stride, W, H, c->jpeg_quality, tmp.data()) :
                    fmt == POPPY_FRAME_PNG ? poppy_bgr_to_png_frame(bgr, stride, W, H, tmp.data()) :
+                   fmt == POPPY_FRAME_PNG_RUNS ? poppy_bgr_to_png_runs_frame(bgr, stride, W, H, tmp.data()) :
                    fmt == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
     if (rc == POPPY_OK && !pal8.empty()) rc = poppy_pal8_to_gif_frame(pal8.data(), W, H, tmp.data());
     if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
@@ -252,10 +253,10 @@ int poppy_hip_i444_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i444, int W, i
 
 // a host frame up, the six PNG kernels, `total` bytes down, on buffers that live for the call; the source's place behind a 256-byte boundary is the row pad's low
 // bits (include/poppy_hip.h), as in scale_host_frame
-int poppy_hip_bgr_to_png_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* dst) {
+static int png_code_host_frame(poppy_hip_ctx* c, int fmt, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* dst) {
     if (!c) return POPPY_E_ARG;
     if (!bgr || !dst || W <= 0 || H <= 0 || stride < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad arguments");
-    if (const char* why = format_refuses(POPPY_FRAME_PNG, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    if (const char* why = format_refuses(fmt, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t row = (size_t)W * 3, shift = (stride - row) % 16;
     CallBuffers held;                                              // (png_from_device_bgr waits for the stream before it returns)
@@ -266,9 +267,15 @@ int poppy_hip_bgr_to_png_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stri
         return fail(c, POPPY_E_DEVICE, "upload of the BGR frame failed");
     }
     std::vector<uint8_t> host;
-    const int rc = png_from_device_bgr(c, d_src + shift, W, H, host);
+    const int rc = png_from_device_bgr(c, fmt, d_src + shift, W, H, host);
     if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
     return rc;
+}
+int poppy_hip_bgr_to_png_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* dst) {
+    return png_code_host_frame(c, POPPY_FRAME_PNG, bgr, stride, W, H, dst);
+}
+int poppy_hip_bgr_to_png_runs_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* dst) {
+    return png_code_host_frame(c, POPPY_FRAME_PNG_RUNS, bgr, stride, W, H, dst);
 }
 
 // a host frame up, the I444 kernel, the planes down, on buffers that live for the call; the source's place behind a 256-byte boundary is the row pad's low bits

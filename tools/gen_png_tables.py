@@ -1,6 +1,8 @@
-"""Generates poppy_amd/csrc/png_tables.h: the eight code-length tables of the POPPY_FRAME_PNG hand-off format and each table's deflate block header.
+"""Generates poppy_amd/csrc/png_tables.h: the eight code-length tables of the POPPY_FRAME_PNG hand-off format and each table's deflate block header,
+and, with --runs, poppy_amd/csrc/png_runs_tables.h: the same for POPPY_FRAME_PNG_RUNS, whose tables have the length symbols too.
 
     python tools/gen_png_tables.py > poppy_amd/csrc/png_tables.h
+    python tools/gen_png_tables.py --runs [--pair a,b] > poppy_amd/csrc/png_runs_tables.h
 
 The committed header is the format's definition (include/poppy_hip.h); this script records how it was made.  Exact integer arithmetic on Python integers only.
 
@@ -9,6 +11,14 @@ w(v) = max(1, floor(2^40 * theta_k^m)), m = min(v, 256 - v), theta_k = 1/4, 1/2,
 Ties: items are ordered by (weight, leaves before packages, symbol number or package position).
 The block header sends HLIT = 0, HDIST = 0, one distance code of length 1, and the 258 lengths each as itself under a code-length code limited to 7 bits
 (package-merge over the lengths' counts, the same tie rule).  Bit 0 of the header's bit string is BFINAL, left 0.
+
+--runs: table k is the same construction over 286 symbols: the literals and end-of-block with the weights above, length symbol 285 with
+max(1, floor(2^40 * theta_k^a)) and the length symbols 257..284 with max(1, floor(2^40 * theta_k^b)) each; (a, b) = RUN_PAIR for all eight tables (DESIGN.md
+section 4, "PNG run hand-off", has the measurement that chose it; --pair writes another candidate's tables for that measurement).
+The block header sends HLIT = 29, HDIST = 0, and the 287 lengths (286 and the one distance code of length 1) as ONE sequence under this greedy rule, from the
+front: where the length equals the one before it and r >= 3 equal lengths stand here, send symbol 16 with the count min(r, 6) (two extra bits, count - 3) and
+go on behind them; else send the length as itself.  (No length is 0, so 17 and 18 never occur.)  The code-length code is package-merge over the counts of the
+symbols so sent, limited to 7 bits, the same tie rule.
 """
 import sys
 
@@ -65,6 +75,53 @@ def table(k):
     return package_merge(weights, 15)
 
 
+RUN_PAIR = (3, 6)
+
+
+def runs_table(k, pair):
+    p, q = THETAS[k]
+    a, b = pair
+
+    def w(e):
+        return max(1, ((1 << 40) * p ** e) // q ** e)
+    weights = [w(min(v, 256 - v)) for v in range(256)] + [1] + [w(b)] * 28 + [w(a)]
+    return package_merge(weights, 15)
+
+
+def runs_header(lengths):
+    sent = lengths + [1]                # the 286 lengths and the one distance code, one sequence
+    items, i = [], 0                    # (code-length symbol, extra value or None)
+    while i < len(sent):
+        r = 1
+        while i + r < len(sent) and sent[i + r] == sent[i]:
+            r += 1
+        if i and sent[i - 1] == sent[i] and r >= 3:
+            items.append((16, min(r, 6) - 3))
+            i += min(r, 6)
+        else:
+            items.append((sent[i], None))
+            i += 1
+    used = sorted(set(s for s, _ in items))
+    cl = [0] * 19
+    for s, l in zip(used, package_merge([sum(1 for t, _ in items if t == s) for s in used], 7)):
+        cl[s] = l
+    cl_codes = canonical(cl)
+    n_cl = max(max(i for i, s in enumerate(CL_ORDER) if cl[s]) + 1, 4)
+    b = Bits()
+    b.put(0, 1)                         # BFINAL: the coder sets it in the last block
+    b.put(2, 2)                         # BTYPE = 10
+    b.put(29, 5)                        # HLIT: 286 codes
+    b.put(0, 5)                         # HDIST: 1 code
+    b.put(n_cl - 4, 4)
+    for s in CL_ORDER[:n_cl]:
+        b.put(cl[s], 3)
+    for s, extra in items:
+        b.put_code(cl_codes[s], cl[s])
+        if extra is not None:
+            b.put(extra, 2)
+    return b
+
+
 def header(lengths):
     sent = lengths + [1]                # the 257 lengths and the one distance code
     used = sorted(set(sent))
@@ -87,7 +144,39 @@ def header(lengths):
     return b
 
 
+def main_runs(pair):
+    tables = [runs_table(k, pair) for k in range(8)]
+    headers = [runs_header(t) for t in tables]
+    for t in tables:
+        assert len(t) == 286 and sum(1 << (15 - l) for l in t) == 1 << 15 and max(t) <= 15 and min(t) >= 1
+    words = max((h.n + 31) // 32 for h in headers)
+    out = [RUNS_LEADER % {"a": pair[0], "b": pair[1], "words": words}]
+    out.append("// kLen[k][v]: the bits of symbol v under table k")
+    out.append("constexpr uint8_t kLen[kTables][kSymbols] = {")
+    for t in tables:
+        rows = [", ".join("%2d" % l for l in t[i:i + 32]) for i in range(0, 286, 32)]
+        out.append("    {" + ",\n     ".join(rows) + "},")
+    out.append("};")
+    out.append("")
+    out.append("// the block header of table k: kHeaderBits[k] bits, least significant bit of word 0 first; bit 0 is BFINAL, 0 here")
+    out.append("constexpr int kHeaderBits[kTables] = {" + ", ".join(str(h.n) for h in headers) + "};")
+    out.append("constexpr uint32_t kHeader[kTables][kHeaderWords] = {")
+    for h in headers:
+        ws = ["0x%08xu" % (h.v >> (32 * i) & 0xffffffff) for i in range(words)]
+        rows = [", ".join(ws[i:i + 8]) for i in range(0, words, 8)]
+        out.append("    {" + ",\n     ".join(rows) + "},")
+    out.append("};")
+    out.append("")
+    out.append(RUNS_TRAILER)
+    sys.stdout.write("\n".join(out))
+
+
 def main():
+    if "--runs" in sys.argv[1:]:
+        pair = RUN_PAIR
+        if "--pair" in sys.argv[1:]:
+            pair = tuple(int(v) for v in sys.argv[sys.argv.index("--pair") + 1].split(","))
+        return main_runs(pair)
     tables = [table(k) for k in range(8)]
     headers = [header(t) for t in tables]
     for t in tables:
@@ -227,6 +316,112 @@ constexpr uint32_t kAdlerMod = 65521;
 size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst);
 
 }  // namespace png
+}  // namespace poppy_hip
+"""
+
+RUNS_LEADER = r"""// png_runs_tables.h — the constants of the POPPY_FRAME_PNG_RUNS hand-off format (include/poppy_hip.h has the rule) that the host statement (frame_png_runs.cpp)
+// and the device coder (kernels_frame_png.hip) share: the eight code-length tables over literal 0..255, end-of-block and the length symbols 257..285, each
+// table's deflate block header, the canonical codes, the tokens of a run, and the capacity.  Everything else of the file is POPPY_FRAME_PNG's: png_tables.h.
+// Host and device, nothing of HIP.
+// Written by tools/gen_png_tables.py --runs, which states the construction; the length symbols' weights are theta_k^%(a)d (285) and theta_k^%(b)d (257..284).
+// This file is the definition: it is never regenerated silently.
+#pragma once
+#include "png_tables.h"
+
+namespace poppy_hip {
+namespace png_runs {
+
+constexpr int kTables = POPPY_PNG_TABLES, kSymbols = 286, kEob = 256, kRunMin = POPPY_PNG_RUN_MIN;
+constexpr int kHeaderWords = %(words)d;      // the longest header in 32-bit words
+"""
+
+RUNS_TRAILER = r"""constexpr bool kraft_is_one(int k) {
+    unsigned sum = 0;
+    for (int v = 0; v < kSymbols; ++v) sum += 1u << (15 - kLen[k][v]);
+    return sum == 1u << 15;
+}
+constexpr int longest_literal(int k) {
+    int m = 0;
+    for (int v = 0; v < 256; ++v) m = kLen[k][v] > m ? kLen[k][v] : m;
+    return m;
+}
+constexpr bool lengths_in_range(int k) {
+    for (int v = 0; v < kSymbols; ++v) if (kLen[k][v] < 1 || kLen[k][v] > 15) return false;
+    return true;
+}
+static_assert(kraft_is_one(0) && kraft_is_one(1) && kraft_is_one(2) && kraft_is_one(3) && kraft_is_one(4) && kraft_is_one(5) && kraft_is_one(6) && kraft_is_one(7),
+              "every table is a complete prefix code: its Kraft sum is exactly 1");
+static_assert(lengths_in_range(0) && lengths_in_range(1) && lengths_in_range(2) && lengths_in_range(3) && lengths_in_range(4) && lengths_in_range(5) &&
+              lengths_in_range(6) && lengths_in_range(7), "deflate's codes have 1 to 15 bits");
+constexpr int kL7 = longest_literal(7);                     // table 7's longest literal: what a byte costs at most as a literal, since table 7 is always a candidate
+static_assert(kL7 <= 9, "the capacity counts 9 bits per byte at most");
+static_assert(kHeaderWords * 4 <= POPPY_PNG_HEADER_BYTES, "a header fits the buffer that poppy_png_runs_table fills");
+
+// A match of `length` bytes (3..258) at distance 1 (RFC 1951, 3.2.5): its length symbol, the number of extra bits and their value.  258 is symbol 285.
+struct Match { int symbol, extra_bits; uint32_t extra; };
+constexpr Match match_of(int length) {
+    if (length == 258) return {285, 0, 0};
+    const int l = length - 3;
+    if (l < 8) return {257 + l, 0, 0};
+    int top = 3;
+    while (l >> (top + 1)) ++top;
+    const int eb = top - 2;
+    return {261 + 4 * eb + ((l >> eb) & 3), eb, (uint32_t)l & ((1u << eb) - 1)};
+}
+constexpr int extra_bits_of_symbol(int s) { return s < 265 || s == 285 ? 0 : (s - 261) / 4; }
+// a match costs no more than the three literals it covers at the least, under table 7: its code, its extra bits and the distance code's one bit
+constexpr bool matches_within_three_literals() {
+    for (int s = 257; s < kSymbols; ++s) if (kLen[7][s] + extra_bits_of_symbol(s) + 1 > 3 * kL7) return false;
+    return true;
+}
+static_assert(matches_within_three_literals(), "the capacity counts a match as the literals it covers");
+static_assert(match_of(3).symbol == 257 && match_of(10).symbol == 264 && match_of(11).symbol == 265 && match_of(12).extra == 1 && match_of(257).symbol == 284 &&
+              match_of(257).extra == 30 && match_of(257).extra_bits == 5 && match_of(227).symbol == 284 && match_of(226).symbol == 283 && match_of(258).symbol == 285 &&
+              match_of(131).symbol == 281 && match_of(130).symbol == 280 && match_of(130).extra == 15, "RFC 1951's length table");
+
+// deflate's canonical code of every symbol, bit-reversed, with its length: entry = reversed code << 4 | length (as png::Codes)
+struct Codes { uint32_t e[kTables][kSymbols]; };
+constexpr Codes make_codes() {
+    Codes c{};
+    for (int k = 0; k < kTables; ++k) {
+        uint32_t code = 0;
+        for (int bits = 1; bits <= 15; ++bits) {
+            for (int v = 0; v < kSymbols; ++v) {
+                if (kLen[k][v] != bits) continue;
+                uint32_t r = 0;
+                for (int i = 0; i < bits; ++i) r |= (code >> i & 1u) << (bits - 1 - i);
+                c.e[k][v] = r << 4 | (uint32_t)bits;
+                ++code;
+            }
+            code <<= 1;
+        }
+    }
+    return c;
+}
+
+// The token that begins at a byte of a run (include/poppy_hip.h: Tokens): the run is `run` bytes, the byte its `offset`-th (0: the run's first).
+// Returns 0 for a literal, the match's length for the head of a match, and -(bytes up to the next token) for a byte that a match covers.
+constexpr int token_at(int run, int offset) {
+    const int m = run - 1;
+    if (offset == 0 || m < kRunMin) return 0;
+    const int j = offset - 1, q = j / 258, r = j - 258 * q, full = m / 258, rem = m - 258 * full;
+    if (q < full) return r == 0 ? 258 : -(258 - r);
+    if (rem < 3) return 0;
+    return r == 0 ? rem : -(rem - r);
+}
+
+using png::kSegment; using png::kStreamByte; using png::kTailBytes; using png::stream_bytes; using png::segment_count;
+// a block of s bytes at its bound in bits, and the frame's capacity (include/poppy_hip.h: Capacity)
+constexpr unsigned long long kBlockBitsOver = (unsigned long long)kHeaderBits[7] + kLen[7][kEob];
+constexpr unsigned long long kSegmentBitsMax = kBlockBitsOver + (unsigned long long)kL7 * kSegment;
+constexpr unsigned long long frame_capacity(unsigned long long w, unsigned long long h) {
+    return kStreamByte + (segment_count(w, h) * kBlockBitsOver + (unsigned long long)kL7 * stream_bytes(w, h) + 7) / 8 + kTailBytes;
+}
+
+// the host coder (frame_png_runs.cpp): a BGR frame with rows `stride` bytes apart into `dst` (the capacity); returns `total`
+size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst);
+
+}  // namespace png_runs
 }  // namespace poppy_hip
 """
 
