@@ -527,7 +527,14 @@ int poppy_hip_orb_detect(poppy_hip_ctx* ctx, const uint8_t* gray, size_t stride,
 /* North-star kernels WITHOUT a call site in Poppy (it never computes descriptors); pinned against
  * OpenCV directly:  ORB::compute (WTA_K 2, 32 bytes/keypoint; OCV/features2d/src/orb.cpp:219-285,1148-1216) and
  * BFMatcher(NORM_HAMMING).match (OCV/features2d/src/matchers.cpp:757, OCV/core/src/batch_distance.cpp:199-262;
- * rows of out3 = queryIdx, trainIdx, distance; lowest train index wins ties).                            */
+ * rows of out3 = queryIdx, trainIdx, distance; lowest train index wins ties).
+ * orb_describe accepts a keypoint (kps7 row: x, y, size, angle, response, octave, class id) whose octave is 0..7 and whose
+ * level position cvRound(pt / scale(octave)) lies in [-9, level width + 9) x [-9, level height + 9): the 31 x 31 steered
+ * patch around it then stays inside the level's 32-pixel border.  Any other keypoint makes the whole call POPPY_E_ARG.
+ * A patch near the border reads that border: the reflect-101 ring around the level, which the reference's in-place
+ * GaussianBlur of the level leaves unblurred, and so does this.  The reference's own ORB::compute never gets that far: it
+ * drops every keypoint closer than 31 px to the border first (runByImageBorder); callers that want its output keep to
+ * keypoints that test would keep, as the detector's are.                                                     */
 int poppy_hip_orb_describe(poppy_hip_ctx* ctx, const uint8_t* gray, size_t stride, int width, int height,
                            const float* kps7, int n_kps, uint8_t* descriptors32);
 int poppy_hip_hamming_match(poppy_hip_ctx* ctx, const uint8_t* query32, int n_query, const uint8_t* train32, int n_train,

@@ -308,7 +308,6 @@ int OrbDetector::describe(const uint8_t* gray, size_t stride, int w, int h, cons
     ORB_CHK(hipMemcpy2DAsync(d_img, w, gray, stride, w, h, hipMemcpyHostToDevice, s));
     launch_orb_pyramid(d_img, w, h, w, d_atlas, Sd, s);
     launch_orb_blur(d_atlas, d_blur, Sd, s);
-    float* cs = h_val;                                   // 2 floats per keypoint: room is kp_cap floats, so stage in halves
     std::vector<float> csv((size_t)n * 2);
     for (int i = 0; i < n; ++i) {
         const float* k = kps7 + (size_t)i * 7;
@@ -323,7 +322,6 @@ int OrbDetector::describe(const uint8_t* gray, size_t stride, int w, int h, cons
             err = "keypoint too close to the border for a 31x31 steered patch"; return -1;
         }
     }
-    (void)cs;
     float* d_cs = nullptr;
     ORB_CHK(hipMalloc((void**)&d_cs, (size_t)n * 2 * sizeof(float)));
     hipError_t e1 = hipMemcpyAsync(d_kp, h_kp, (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, s);
