@@ -545,9 +545,48 @@ int poppy_hip_hamming_match(poppy_hip_ctx* ctx, const uint8_t* query32, int n_qu
  *                    ordered by (distance, train index) (OCV/core/src/batch_distance.cpp:225-248), -1 where there is none;
  *   ratio_symmetry : ratioTest (a query survives with two neighbours and distance0 / distance1 <= ratio) on both
  *                    directions, then symmetryTest; rows of out3 = queryIdx, trainIdx, distance.  Host only.
- * ransacTest (findFundamentalMat) of the same sketch is not provided.                                          */
+ * ransacTest (findFundamentalMat) of the same sketch: poppy_ransac_fundamental below.                            */
 int poppy_hip_hamming_knn2(poppy_hip_ctx* ctx, const uint8_t* query32, int n_query, const uint8_t* train32, int n_train, int* out4);
 int poppy_ratio_symmetry(const int* knn12, int n1, const int* knn21, int n2, float ratio, int* out3, int* n_out);
+
+/* The sketch's third filter, ransacTest: the pairs that agree with a fundamental matrix found by RANSAC.  Not OpenCV's findFundamentalMat (its sampler, its
+ * 7-point solver and its adaptive iteration count are not restated): the filter is DEFINED by the host statement poppy_ransac_fundamental, and
+ * poppy_hip_ransac_fundamental, which scores the hypotheses on the GPU, returns the same bytes.
+ *   The hypothesis count is fixed, so the result does not depend on scheduling: with an inlier share of 0.5 a sample of 8 is all inliers with probability
+ *   0.5^8 = 1 / 256, and 2048 samples hold at least one such sample with probability 1 - (1 - 0.5^8)^2048 = 1 - e^(2048 ln(255 / 256)) = 1 - e^-8.016 = 0.9997.
+ *   All arithmetic is double: + - * / sqrt and comparisons, every sum in a stated order, no fused products, no libm.
+ *   Input: n_points pairs (x1, y1) <-> (x2, y2) of floats, 8 <= n_points <= 65536, widened to double; distance d >= 0 in pixels (the sketch: 3.0).
+ *   Normalisation, per image, over all points: centroid m (sums in index order, / n), r = the mean of sqrt(dx^2 + dy^2) to it (in index order), s = sqrt(2) / r,
+ *     T = [[s, 0, -(s mx)], [0, s, -(s my)], [0, 0, 1]], x^ = s x + T[0][2], y^ = s y + T[1][2].  r = 0 in either image: no model.
+ *   Samples: hypothesis h (0 .. 2047) draws 8 distinct indices; draw k (0 .. 7) is r = mix32(0x9E3779B9 (8 h + k + 1)) mod (n - k) in 32-bit wrap-around
+ *     arithmetic, mapped onto the indices not yet drawn: for each earlier draw in ascending order of value, r += (r >= value).
+ *     mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *   Model: row i of the 8 x 9 system, from draw i, is (x2^ x1^, x2^ y1^, x2^, y2^ x1^, y2^ y1^, y2^, x1^, y1^, 1).  Its null vector by Gaussian elimination with
+ *     complete pivoting: at step k (0 .. 7) the pivot is the largest |A[i][j]| over rows i = k .. 7 and columns j = k .. 8 of the matrix as it stands, scanned row by
+ *     row, ties to the lowest row and then the lowest column; rows k and i swap, columns k and j swap (the unknowns with them); then for i = k + 1 .. 7:
+ *     f = A[i][k] / A[k][k] and for j = k + 1 .. 8: A[i][j] = A[i][j] - f A[k][j].  A first pivot of 0, or any pivot below 1e-10 of the first: the hypothesis is
+ *     INVALID.  The free unknown z[8] = 1; for i = 7 .. 0: s = 0, for j = i + 1 .. 8: s = s + A[i][j] z[j]; z[i] = (-s) / A[i][i]; the column swaps are undone: F^
+ *     (3 x 3, row-major).  No rank-2 step.  F_h = T2^T (F^ T1): G = F^ T1 first, then T2^T G, every entry (a0 b0 + a1 b1) + a2 b2 with all three products.
+ *   Score: a = (F[0][0] x1 + F[0][1] y1) + F[0][2], b and c likewise from rows 1 and 2; e = (a x2 + b y2) + c; a' = (F[0][0] x2 + F[1][0] y2) + F[2][0],
+ *     b' = (F[0][1] x2 + F[1][1] y2) + F[2][1], on the points as given (widened).  Pair i is an inlier of h iff e e <= (d d) (a a + b b) and
+ *     e e <= (d d) (a' a' + b' b').  counts[h] = the number of inliers, -1 for an invalid hypothesis.
+ *   Choice: the largest count, ties to the lowest h.  No valid hypothesis, or a best count below 8: no model.
+ *   Result: inliers[i] = 1 / 0, the best hypothesis's inliers in input order; *n_inliers their number; *best = h.  f3x3 (row-major, x2^T F x1 = 0) is a normalised
+ *     8-point fit over those inliers (host only, also in the GPU form): the normalisation recomputed from them, A^T A (9 x 9) through cyclic Jacobi and the vector of
+ *     its smallest eigenvalue, rank 2 by a 3 x 3 one-sided Jacobi SVD with the smallest singular value zeroed, denormalised, scaled to Frobenius norm 1, signed so
+ *     that its largest-magnitude entry is positive.  The mask is not recomputed from it.  Inliers that allow no such fit (r = 0 among them): no model.
+ *   No model never throws pairs away: inliers all 1, f3x3 nine zeros, *best = -1, *n_inliers = n_points, POPPY_OK.  Identical images and pure shifts are
+ *     planar-degenerate and may end here.
+ *   counts (2048) and models (2048 x 9 doubles, F_h; zeros where invalid) are optional.  POPPY_E_ARG — nothing written — for a null required pointer, n_points
+ *   outside 8 .. 65536, or a distance that is negative or not finite.  NaN and infinite coordinates are not pinned.
+ * poppy_hip_ransac_fundamental needs no resident pair and disturbs none.                                                                                    */
+#define POPPY_RANSAC_HYPOTHESES 2048
+#define POPPY_RANSAC_MIN_POINTS 8
+#define POPPY_RANSAC_MAX_POINTS 65536
+int poppy_ransac_fundamental(const float* points1, const float* points2, int n_points, double distance,
+                             uint8_t* inliers, int* n_inliers, double* f3x3, int* best, int* counts, double* models);
+int poppy_hip_ransac_fundamental(poppy_hip_ctx* ctx, const float* points1, const float* points2, int n_points, double distance,
+                                 uint8_t* inliers, int* n_inliers, double* f3x3, int* best, int* counts, double* models);
 
 /* ---- auto-align (Settings::enable_auto_align) ---------------------------------------------------
  * warp_affine : cv::warpAffine(src, dst, M, src.size()) for 8UC3, INTER_LINEAR, BORDER_CONSTANT 0, M = 2x3 forward map
@@ -667,6 +706,14 @@ void poppy_count_frames_cb(void* user, const uint8_t* bgr, int width, int height
  * POPPY_E_NOMATCH when nothing survives (use poppy_hip_dissolve).  ratio: 0.7 in the reference's sketch.        */
 int poppy_hip_pair_begin_descriptors(poppy_hip_ctx* ctx, const uint8_t* bgr1, size_t stride1, const uint8_t* bgr2, size_t stride2,
                                      int width, int height, float ratio);
+/* The same with the sketch's third filter: the pairs left after the out-of-image drop go through poppy_hip_ransac_fundamental with this distance (the sketch: 3.0)
+ * and only its inliers, still in query order, become the point pairs (then the morph distance and the four corners, as above).  Fewer than 8 pairs: the filter
+ * is skipped.  Nothing left before the filter: POPPY_E_NOMATCH.  poppy_hip_pair_fundamental reports what the filter of the resident pair's set-up found: F (nine
+ * zeros without a model or when the filter was skipped), the pairs that went in, the pairs that came out and the winning hypothesis (-1 likewise); each pointer may be
+ * NULL.  POPPY_E_STATE when the resident pair was set up any other way.                                                                                     */
+int poppy_hip_pair_begin_descriptors_ransac(poppy_hip_ctx* ctx, const uint8_t* bgr1, size_t stride1, const uint8_t* bgr2, size_t stride2,
+                                            int width, int height, float ratio, double distance);
+int poppy_hip_pair_fundamental(poppy_hip_ctx* ctx, double* f3x3, int* n_matches, int* n_inliers, int* best);
 
 /* The second image as the resident pair holds it — after poppy_hip_pair_begin with enable_auto_align this is the ALIGNED
  * corrected2 that poppy::morph hands back to its caller (src/poppy.hpp:46-47; src/poppy.cpp:326 chains it into the next pair). */

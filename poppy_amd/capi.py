@@ -61,6 +61,7 @@ SYMBOLS = [
     "poppy_hip_set_frame_size", "poppy_hip_pool_set_frame_size", "poppy_frame_fit_size", "poppy_bgr_resize_area", "poppy_hip_bgr_resize_area",
     "poppy_hip_bgr_resize_area_form",
     "poppy_hip_unsharp_frame", "poppy_hip_align_scores",
+    "poppy_ransac_fundamental", "poppy_hip_ransac_fundamental", "poppy_hip_pair_begin_descriptors_ransac", "poppy_hip_pair_fundamental",
 ]
 
 
@@ -116,6 +117,10 @@ def lib():
         L.poppy_perspective_from4.argtypes = [vp, vp, vp]
         L.poppy_ratio_symmetry.argtypes = [vp, i, vp, i, C.c_float, vp, vp]
         L.poppy_hip_pair_begin_descriptors.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i, i, C.c_float]
+        L.poppy_hip_pair_begin_descriptors_ransac.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, i, i, C.c_float, d]
+        L.poppy_ransac_fundamental.argtypes = [vp, vp, i, d, vp, vp, vp, vp, vp, vp]
+        L.poppy_hip_ransac_fundamental.argtypes = [vp, vp, vp, i, d, vp, vp, vp, vp, vp, vp]
+        L.poppy_hip_pair_fundamental.argtypes = [vp, vp, vp, vp, vp]
         L.poppy_hip_timing_summary.argtypes = [vp, vp, vp, vp, i]
         L.poppy_hip_render_many.argtypes = [vp, vp, vp, i, i, vp, vp]
         L.poppy_hip_orb_detect.argtypes = [vp, vp, sz, i, i, i, vp, i, vp]
@@ -657,6 +662,32 @@ def ratio_symmetry(knn12, knn21, ratio=0.7):
     if rc:
         raise PoppyError(f"poppy_ratio_symmetry: {rc}")
     return out[:n.value]
+
+
+RANSAC_HYPOTHESES, RANSAC_MIN_POINTS, RANSAC_MAX_POINTS = 2048, 8, 65536
+
+
+def _ransac(call, what, points1, points2, distance, chk=None):
+    a = np.ascontiguousarray(points1, np.float32).reshape(-1, 2); b = np.ascontiguousarray(points2, np.float32).reshape(-1, 2)
+    n = len(a)
+    assert len(b) == n
+    res = {"inliers": np.zeros(max(n, 1), np.uint8), "f": np.zeros((3, 3), np.float64), "counts": np.zeros(RANSAC_HYPOTHESES, np.int32),
+           "models": np.zeros((RANSAC_HYPOTHESES, 3, 3), np.float64)}
+    n_in, best = C.c_int(0), C.c_int(0)
+    rc = call(_p(a), _p(b), n, float(distance), _p(res["inliers"]), C.byref(n_in), _p(res["f"]), C.byref(best), _p(res["counts"]), _p(res["models"]))
+    if chk:
+        chk(rc, what)
+    elif rc:
+        raise PoppyError(f"{what}: {rc}")
+    res["inliers"] = res["inliers"][:n]
+    res["n_inliers"], res["best"] = n_in.value, best.value
+    return res
+
+
+def ransac_fundamental(points1, points2, distance=3.0):
+    """Host statement of the RANSAC fundamental-matrix filter (include/poppy_hip.h: poppy_ransac_fundamental): dict(inliers u8 [n], n_inliers, f 3x3,
+    best, counts i32 [2048], models f64 [2048, 3, 3])."""
+    return _ransac(lib().poppy_ransac_fundamental, "poppy_ransac_fundamental", points1, points2, distance)
 
 
 def procrustes(x, y):
@@ -1480,6 +1511,27 @@ class Context:
         nf = C.c_int(0)
         lib().poppy_hip_pair_begin_info(self.h, C.byref(nf), None)
         return nf.value
+
+    def pair_begin_descriptors_ransac(self, bgr1, bgr2, ratio=0.7, distance=3.0):
+        """The descriptor mode with the RANSAC fundamental-matrix filter behind the symmetry test; returns nfeatures."""
+        a = np.ascontiguousarray(bgr1, np.uint8); b = np.ascontiguousarray(bgr2, np.uint8)
+        h, w = a.shape[:2]
+        self._chk(lib().poppy_hip_pair_begin_descriptors_ransac(self.h, _p(a), w * 3, _p(b), w * 3, w, h, ratio, distance), "pair_begin_descriptors_ransac")
+        self.w, self.h_ = w, h
+        nf = C.c_int(0)
+        lib().poppy_hip_pair_begin_info(self.h, C.byref(nf), None)
+        return nf.value
+
+    def pair_fundamental(self):
+        """What the filter of the last pair_begin_descriptors_ransac found: dict(f 3x3, n_matches, n_inliers, best)."""
+        f = np.zeros((3, 3), np.float64)
+        n_m, n_in, best = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(lib().poppy_hip_pair_fundamental(self.h, _p(f), C.byref(n_m), C.byref(n_in), C.byref(best)), "pair_fundamental")
+        return {"f": f, "n_matches": n_m.value, "n_inliers": n_in.value, "best": best.value}
+
+    def ransac_fundamental(self, points1, points2, distance=3.0):
+        """capi.ransac_fundamental with the 2048 hypotheses on this context's GPU: the same bytes."""
+        return _ransac(lambda *args: lib().poppy_hip_ransac_fundamental(self.h, *args), "ransac_fundamental", points1, points2, distance, self._chk)
 
     def pair_begin_prefiltered(self, bgr1, bgr2, g1, g2, gabor2, nfeatures):
         a = np.ascontiguousarray(bgr1, np.uint8); b = np.ascontiguousarray(bgr2, np.uint8)

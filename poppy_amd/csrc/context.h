@@ -6,7 +6,7 @@
 //   palette_seq.cpp   the PAL8_SEQ / GIF_SEQ sequence (palette_seq.h): store, palette, the two hand-over loops;  writer_ring.cpp: the pinned ring towards the writer (writer_ring.h)
 //   writer_image.cpp  the frames that no slot renders and the stand-alone conversion entry points (writer_image.h);  writer_buffers.h: the grow-only device buffer and the call-scoped holder
 //   pair_begin.cpp    the pair set-up from raw images (pair_begin.h): its schedule and stages, the chain threads (setup_latch.h), the pair_begin entry points
-//   pair_setup.cpp    the stage-by-stage entry points of the once-per-pair half: pre-ORB chain, ORB, matching, auto-align, tables, margins
+//   pair_setup.cpp    the stage-by-stage entry points of the once-per-pair half: pre-ORB chain, ORB, matching, the RANSAC filter (ransac_fundamental.h), auto-align, tables, margins
 //   image_list.cpp    poppy_hip_morph_list
 //   rccl_comm.cpp     the RCCL loader and a context's communicator (rccl_comm.h, comm_guard.h): the two collectives, the abort, the pair state's broadcast, export and import
 //   sharded_setup.cpp the pair set-up spread over ranks, as named stages (shard_protocol.h: roles and the keypoint hand-off; local_hub.h: the in-process transport)
@@ -179,6 +179,10 @@ struct poppy_hip_ctx {
     bool setup_serial = false;                  // pair set-up: the two images' chains one after the other (set by pools of >= 3 contexts per device and by poppy_hip_set_setup_chains)
     hipEvent_t dl_done[kStageRing] = {};
     hipStream_t dl_ring[kStageRing] = {};     // unless POPPY_HIP_DL_EVENTS is set: a stream per pinned ring buffer, carrying nothing but that buffer's copies (no event is recorded behind a copy)
+    // (behind everything else: the frame path's members keep the places they had before the filter came)
+    // what the RANSAC filter of the last poppy_hip_pair_begin_descriptors_ransac found (poppy_hip_pair_fundamental); set_points of any set-up ends its validity
+    struct LastFundamental { bool valid = false; double f[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int n_matches = 0, n_inliers = 0, best = -1; } fundamental;
+    DeviceBuffer ransac_scratch;                    // the filter's points, models and counts on the device (kernels_ransac.hip: ransac_counts_device)
 };
 
 // ---- packed pair state (see poppy_hip_ctx::arena) -------------------------------------------------------------------------

@@ -7,7 +7,11 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
+
+struct DeviceBuffer;                          // writer_buffers.h
+namespace poppy_ransac { struct Problem; }      // ransac_fundamental.h
 
 namespace poppy_hip {
 
@@ -288,5 +292,10 @@ void launch_png_scan(uint8_t* scratch, uint8_t* frame, int w, int h, bool runs, 
 void launch_png_pack(const uint8_t* scratch, uint8_t* frame, int w, int h, bool runs, hipStream_t s);
 void launch_png_crc(uint8_t* scratch, const uint8_t* frame, int w, int h, bool runs, hipStream_t s);
 void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, bool runs, hipStream_t s, hipEvent_t done = nullptr);
+
+// The RANSAC fundamental-matrix filter's 2048 hypotheses (kernels_ransac.hip; the rule: include/poppy_hip.h, poppy_ransac_fundamental): the models of problem P
+// (normalised, 8 .. 65536 pairs) and their inlier counts among the pairs p1 <-> p2 into the host arrays counts (2048) and models (2048 x 9), two launches on s, which
+// is synchronised.  buf: grow-only device scratch.  POPPY_OK, or a status with err set.
+int ransac_counts_device(DeviceBuffer& buf, hipStream_t s, const poppy_ransac::Problem& P, const float* p1, const float* p2, int* counts, double* models, std::string& err);
 
 }  // namespace poppy_hip

@@ -70,6 +70,8 @@ struct PairSetup {                       // one call's state, shared by its two 
     std::vector<OrbKeyPoint> k[2];
     int gabor2_queued = 0;               // times queue_gabor2 did its work (on the calling thread, whichever place): 1 when the set-up is through
     SetupTimes t;
+    double ransac_distance = -1;         // descriptor mode: >= 0 puts the RANSAC fundamental-matrix filter behind the symmetry test, with this distance
+    poppy_hip_ctx::LastFundamental fundamental;      // ... and what it found
 };
 
 struct SetupHook {                       // a pool lets one context per device set a pair up at a time (pool.cpp: the set-up gate)
@@ -185,7 +187,8 @@ int detect_finish_both(PairSetup& p, int nfeatures) {
 
 // Opt-in descriptor mode (the reference only sketched it, src/experiments.hpp:14-144): ORB::compute on both keypoint sets, 2-NN Hamming both
 // ways, ratio test, symmetry test; the surviving pairs, in query order, become the point sets (out-of-image pairs dropped, the four corners appended).
-// No positional re-pairing, no threshold.
+// No positional re-pairing, no threshold.  With p.ransac_distance >= 0 the sketch's third filter, ransacTest, follows drop_out_of_image: pairs that the RANSAC
+// fundamental matrix (ransac_filter) does not keep leave the lists, the others stay in query order; under 8 pairs there is nothing to fit and the filter is skipped.
 int descriptor_points(PairSetup& p) {
     poppy_hip_ctx* c = p.c;
     const int W = p.W, H = p.H, n1 = (int)p.k[0].size(), n2 = (int)p.k[1].size();
@@ -209,6 +212,18 @@ int descriptor_points(PairSetup& p) {
     drop_out_of_image(a, b, W, H);
     c->last_descriptor_matches = (int)a.size();
     if (a.empty()) return fail(c, POPPY_E_NOMATCH, "no symmetric descriptor matches");
+    if (p.ransac_distance >= 0) {
+        auto& f = p.fundamental;
+        f.valid = true; f.n_matches = f.n_inliers = (int)a.size(); f.best = -1;
+        if (a.size() >= (size_t)POPPY_RANSAC_MIN_POINTS) {
+            std::vector<uint8_t> keep(a.size());
+            const int rc = ransac_filter(c, (const float*)a.data(), (const float*)b.data(), (int)a.size(), p.ransac_distance, keep.data(), &f.n_inliers, f.f, &f.best, nullptr, nullptr);
+            if (rc) return rc;
+            size_t m = 0;
+            for (size_t i = 0; i < a.size(); ++i) if (keep[i]) { a[m] = a[i]; b[m] = b[i]; ++m; }
+            a.resize(m); b.resize(m);
+        }
+    }
     c->initial_morph_dist = morph_distance_ref(a, b, W, H);
     add_image_corners(a, b, W, H);
     return set_points(c, (const float*)a.data(), (const float*)b.data(), (int)a.size());
@@ -234,7 +249,9 @@ int align_second_image(PairSetup& p, PointLists& pts) {
 // Pair set-up from the raw images: the pre-ORB filter chain on the GPU, then the same steps as pair_begin_prefiltered.  The two images go through the chain
 // independently: one host thread and one stream each, so that the medians of one image run beside the Gabor bank of the other.
 // next: the set-up of the next pair of the CLI's loop (src/poppy.cpp:326) — image 1 is the resident pair's c2 (bgr1 unused).
-int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint8_t* bgr2, size_t s2, int W, int H, float ratio, bool on_device = false, bool next = false) {
+// ransac_distance >= 0 (descriptor mode only): the RANSAC filter behind the symmetry test.
+int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint8_t* bgr2, size_t s2, int W, int H, float ratio, bool on_device = false, bool next = false,
+                    double ransac_distance = -1) {
     if (!c) return POPPY_E_ARG;
     if (next) {
         if (!c->pair_ready) return fail(c, POPPY_E_STATE, "pair_begin_next: no resident pair");
@@ -245,6 +262,7 @@ int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint
     if (!setup_size_ok(W, H)) return fail(c, POPPY_E_UNSUPPORTED, kSetupSizeMsg);
     HIPCHK(c, hipSetDevice(c->device));
     PairSetup p{c, setup_schedule(c, on_device, next, ratio), W, H, ratio, bgr2, s2};
+    p.ransac_distance = ransac_distance;
     const SetupSchedule& sch = p.sch;
     p.sa = sch.reuse ? c->chain_b : 0; p.sb = 1 - p.sa;
     chain_touch(c);                                               // from here on, nothing is kept until this set-up succeeds
@@ -299,6 +317,7 @@ int pair_begin_impl(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint
         c->kept_gen = c->chain_gen;
     }
     if (sch.timing) p.t.print(W, H, sch);
+    c->fundamental = p.fundamental;                              // (set_points ended the previous one's validity)
     return POPPY_OK;
 }
 
@@ -388,6 +407,11 @@ int poppy_hip_pair_begin_next_device(poppy_hip_ctx* c, const void* d_bgr, int W,
 int poppy_hip_pair_begin_descriptors(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint8_t* bgr2, size_t s2, int W, int H, float ratio) {
     if (!(ratio >= 0.f)) return c ? fail(c, POPPY_E_ARG, "ratio must be >= 0") : POPPY_E_ARG;
     return pair_begin_impl(c, bgr1, s1, bgr2, s2, W, H, ratio);
+}
+int poppy_hip_pair_begin_descriptors_ransac(poppy_hip_ctx* c, const uint8_t* bgr1, size_t s1, const uint8_t* bgr2, size_t s2, int W, int H, float ratio, double distance) {
+    if (!(ratio >= 0.f)) return c ? fail(c, POPPY_E_ARG, "ratio must be >= 0") : POPPY_E_ARG;
+    if (!(distance >= 0.0) || !(distance <= 1.7976931348623157e308)) return c ? fail(c, POPPY_E_ARG, "the distance must be finite and >= 0") : POPPY_E_ARG;
+    return pair_begin_impl(c, bgr1, s1, bgr2, s2, W, H, ratio, false, false, distance);
 }
 int poppy_hip_chain_counts(poppy_hip_ctx* c, unsigned long long* run, unsigned long long* reused) {
     if (!c) return POPPY_E_ARG;

@@ -26,5 +26,10 @@ int prepare_points(poppy_hip_ctx* c, PointLists& pts, int W, int H, Worker* help
 std::vector<float> keypoint_xy(const std::vector<OrbKeyPoint>& k);
 void keypoint_rows7(const std::vector<OrbKeyPoint>& k, float* rows);      // cv::KeyPoint's field order, all as float: x, y, size, angle, response, octave, class_id
 
+// The RANSAC fundamental-matrix filter on the context's GPU (pair_setup.cpp; poppy_hip_ransac_fundamental is this behind hipSetDevice): arguments and result as
+// poppy_ransac_fundamental's.  The set-up with the filter calls it between drop_out_of_image and the corners.
+int ransac_filter(poppy_hip_ctx* c, const float* p1, const float* p2, int n, double distance, uint8_t* inliers, int* n_inliers, double* f3x3, int* best,
+                  int* counts, double* models);
+
 // poppy_match_points with a helper thread for the sums
 int match_points_with(Worker* helper, const float* p1, const float* p2, int n, int W, int H, double tol, float* o1, float* o2, int* n_out, double* imd);

@@ -3,6 +3,7 @@
 // the host-side tables, blur_margin.  The set-up that runs them all from a raw pair is pair_begin.cpp; both share context.h.
 #include "pair_begin.h"
 #include "dft_exact.h"
+#include "ransac_fundamental.h"
 
 // blur_margin's two halves (src/util.cpp:574-602), shared by poppy_hip_blur_margin and poppy_hip_morph_list's device-side padding.
 // taps: exp(-x^2 / 2 sigma^2) / sum in double, to 8 fractional bits with error diffusion, centre = 256 - rest (smooth.dispatch.cpp:224-258)
@@ -113,6 +114,35 @@ int poppy_hip_warp_affine(poppy_hip_ctx* c, const uint8_t* src, size_t ss, int W
     return ok ? POPPY_OK : fail(c, POPPY_E_DEVICE, "warp_affine failed");
 }
 
+}  // extern "C"
+
+// poppy_ransac_fundamental with the 2048 hypotheses on the GPU: the host normalises, the kernels fill counts and models on the set-up stream (own scratch: no
+// resident buffer and no chain slot is touched), the host chooses, masks and refits (ransac_fundamental.cpp) — the same functions before and behind as the
+// host statement runs, so the two differ in who computes counts and models, and in nothing else.
+int ransac_filter(poppy_hip_ctx* c, const float* p1, const float* p2, int n, double distance, uint8_t* inliers, int* n_inliers, double* f3x3, int* best,
+                  int* counts, double* models) {
+    using namespace poppy_ransac;
+    if (!p1 || !p2 || !inliers || !n_inliers || !f3x3 || !best) return fail(c, POPPY_E_ARG, "ransac: a required pointer is null");
+    if (n < kMinPoints || n > kMaxPoints) return fail(c, POPPY_E_ARG, "ransac: takes 8 .. 65536 point pairs");
+    if (!(distance >= 0.0) || !(distance <= 1.7976931348623157e308)) return fail(c, POPPY_E_ARG, "ransac: the distance must be finite and >= 0");
+    std::vector<double> norm((size_t)n * 4), own_models;
+    std::vector<int> own_counts;
+    if (!counts) { own_counts.resize(kHypotheses); counts = own_counts.data(); }
+    if (!models) { own_models.resize((size_t)kHypotheses * 9); models = own_models.data(); }
+    Problem P;
+    P.norm = norm.data();
+    prepare(p1, p2, n, distance, P);
+    if (P.normalised) {
+        std::string err;
+        const int rc = ransac_counts_device(c->ransac_scratch, c->stream, P, p1, p2, counts, models, err);
+        if (rc) return fail(c, rc, err.c_str());
+    } else models_and_counts(P, p1, p2, counts, models);        // no model: every count -1, every model zeros, nothing to launch
+    finish(P, p1, p2, counts, models, inliers, n_inliers, f3x3, best);
+    return POPPY_OK;
+}
+
+extern "C" {
+
 static int align_host_entry(poppy_hip_ctx* c, int which, uint8_t* img, size_t stride, int W, int H, const float* p1, float* p2, int n, double* dist) {
     if (!c) return POPPY_E_ARG;
     if (!img || !p1 || !p2 || W <= 0 || H <= 0 || stride < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad align arguments");
@@ -208,6 +238,21 @@ int poppy_hip_pair_corrected2(poppy_hip_ctx* c, uint8_t* dst, size_t ds) {
 }
 
 // intermediates of the last poppy_hip_pair_begin, for the tolerance tests: nfeatures, the two dft_detail2 values
+int poppy_hip_ransac_fundamental(poppy_hip_ctx* c, const float* p1, const float* p2, int n, double distance, uint8_t* inliers, int* n_inliers, double* f3x3,
+                                 int* best, int* counts, double* models) {
+    if (!c) return POPPY_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return ransac_filter(c, p1, p2, n, distance, inliers, n_inliers, f3x3, best, counts, models);
+}
+int poppy_hip_pair_fundamental(poppy_hip_ctx* c, double* f3x3, int* n_matches, int* n_inliers, int* best) {
+    if (!c) return POPPY_E_ARG;
+    if (!c->pair_ready || !c->fundamental.valid) return fail(c, POPPY_E_STATE, "the resident pair was not set up by poppy_hip_pair_begin_descriptors_ransac");
+    if (f3x3) memcpy(f3x3, c->fundamental.f, sizeof(c->fundamental.f));
+    if (n_matches) *n_matches = c->fundamental.n_matches;
+    if (n_inliers) *n_inliers = c->fundamental.n_inliers;
+    if (best) *best = c->fundamental.best;
+    return POPPY_OK;
+}
 int poppy_hip_pair_begin_info(poppy_hip_ctx* c, int* nfeatures, double* detail2) {
     if (!c) return POPPY_E_ARG;
     if (nfeatures) *nfeatures = c->last_nfeatures;

@@ -133,6 +133,7 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
     if (c->d_comm_scratch) (void)hipFree(c->d_comm_scratch);
     free_context_format(c);
     c->aligner.release();
+    c->ransac_scratch.release();
     (void)hipStreamDestroy(c->copy_stream);
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -279,6 +280,7 @@ int alloc_pair(poppy_hip_ctx* c, int W, int H) {
 
 int set_points(poppy_hip_ctx* c, const float* p1, const float* p2, int n) {
     if (n < 0 || (n > 0 && (!p1 || !p2))) return fail(c, POPPY_E_ARG, "bad point sets");
+    c->fundamental.valid = false;                                  // (the set-up with the RANSAC filter sets it again behind this call)
     c->pts1_0.resize(n); c->pts2.resize(n);
     if (n) { memcpy(c->pts1_0.data(), p1, (size_t)n * 8); memcpy(c->pts2.data(), p2, (size_t)n * 8); }
     c->pts1 = c->pts1_0;
