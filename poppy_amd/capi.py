@@ -247,6 +247,31 @@ def frame_bytes(fmt, w, h):
     return int(lib().poppy_frame_bytes(int(fmt), int(w), int(h)))
 
 
+def _padded_rows(bgr, row_pad):
+    """An HxWx3 BGR frame as it is handed over, (array, stride, w, h): row_pad extra bytes per row, filled with a pattern no pixel may come from."""
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    stride = w * 3 + int(row_pad)
+    if row_pad:
+        buf = np.full((h, stride), 0xA5, np.uint8)
+        buf[:, :w * 3] = a.reshape(h, w * 3)
+        a = buf
+    return a, stride, w, h
+
+
+def _padded_frames(frames, row_pad, frame_pad):
+    """n HxWx3 BGR frames as they are handed over, (array, stride, frame_stride, n, w, h): row_pad extra bytes per row and frame_pad between frames, filled alike."""
+    a = np.ascontiguousarray(frames, np.uint8)
+    n, h, w = a.shape[:3]
+    stride = w * 3 + int(row_pad)
+    frame_stride = stride * h + int(frame_pad)
+    if row_pad or frame_pad:
+        buf = np.full((n, frame_stride), 0xA5, np.uint8)
+        buf[:, :stride * h].reshape(n, h, stride)[:, :, :w * 3] = a.reshape(n, h, w * 3)
+        a = buf
+    return a, stride, frame_stride, n, w, h
+
+
 def bgr_to_i420(bgr):
     """Host-only: the library's I420 of an HxWx3 BGR frame (poppy_bgr_to_i420), as a flat uint8 array of frame_bytes(FRAME_I420, W, H)."""
     a = np.ascontiguousarray(bgr, np.uint8)
@@ -261,13 +286,7 @@ def bgr_to_i420(bgr):
 def bgr_to_pal8(bgr, row_pad=0):
     """Host-only: the library's PAL8 of an HxWx3 BGR frame (poppy_bgr_to_pal8), as a flat uint8 array of frame_bytes(FRAME_PAL8, W, H): W * H
     index bytes, then 256 R, G, B palette entries.  row_pad: the frame is handed over with that many extra bytes per row."""
-    a = np.ascontiguousarray(bgr, np.uint8)
-    h, w = a.shape[:2]
-    stride = w * 3 + int(row_pad)
-    if row_pad:
-        buf = np.full((h, stride), 0xA5, np.uint8)
-        buf[:, :w * 3] = a.reshape(h, w * 3)
-        a = buf
+    a, stride, w, h = _padded_rows(bgr, row_pad)
     out = np.empty(frame_bytes(FRAME_PAL8, w, h), np.uint8)
     rc = lib().poppy_bgr_to_pal8(_p(a), stride, w, h, _p(out))
     if rc:
@@ -279,14 +298,7 @@ def bgr_frames_to_pal8(frames, row_pad=0, frame_pad=0):
     """Host-only: the library's PAL8_SEQ frames of a sequence of n HxWx3 BGR frames (poppy_bgr_frames_to_pal8): an n x frame_bytes(FRAME_PAL8_SEQ, W, H)
     uint8 array, every row W * H index bytes and the sequence's one palette.  row_pad / frame_pad: the frames are handed over with that many extra
     bytes per row / between frames."""
-    a = np.ascontiguousarray(frames, np.uint8)
-    n, h, w = a.shape[:3]
-    stride = w * 3 + int(row_pad)
-    frame_stride = stride * h + int(frame_pad)
-    if row_pad or frame_pad:
-        buf = np.full((n, frame_stride), 0xA5, np.uint8)
-        buf[:, :stride * h].reshape(n, h, stride)[:, :, :w * 3] = a.reshape(n, h, w * 3)
-        a = buf
+    a, stride, frame_stride, n, w, h = _padded_frames(frames, row_pad, frame_pad)
     out = np.empty((n, frame_bytes(FRAME_PAL8_SEQ, w, h)), np.uint8)
     rc = lib().poppy_bgr_frames_to_pal8(_p(a), stride, frame_stride, n, w, h, _p(out))
     if rc:
@@ -294,77 +306,83 @@ def bgr_frames_to_pal8(frames, row_pad=0, frame_pad=0):
     return out
 
 
-def gif_frame_bytes(frame):
-    """Host-only: `total` of a FRAME_GIF frame, its length in bytes (poppy_gif_frame_bytes: the first four bytes, little-endian)."""
+def coded_frame_bytes(frame, coder):
+    """Host-only: `total` of a coded frame, its length in bytes (poppy_<coder>_frame_bytes, coder "gif", "jpeg" or "png": the first four bytes, little-endian)."""
     f = np.ascontiguousarray(frame, np.uint8)
     if f.size < 4:
-        raise PoppyError("gif_frame_bytes: a coded frame has at least four bytes")
-    return int(lib().poppy_gif_frame_bytes(_p(f)))
+        raise PoppyError(f"{coder}_frame_bytes: a coded frame has at least four bytes")
+    return int(getattr(lib(), f"poppy_{coder}_frame_bytes")(_p(f)))
 
 
-def _gif_frame(call, name, w, h):
-    out = np.empty(max(frame_bytes(FRAME_GIF, w, h), 4), np.uint8)
-    rc = call(out)
-    if rc:
-        raise PoppyError(f"{name}: {rc}")
-    return out[:gif_frame_bytes(out)].copy()
+def gif_frame_bytes(frame):
+    """Host-only: `total` of a FRAME_GIF frame, its length in bytes (poppy_gif_frame_bytes: the first four bytes, little-endian)."""
+    return coded_frame_bytes(frame, "gif")
+
+
+def jpeg_frame_bytes(frame):
+    """Host-only: `total` of a FRAME_JPEG frame, its length in bytes (poppy_jpeg_frame_bytes: the first four bytes, little-endian)."""
+    return coded_frame_bytes(frame, "jpeg")
+
+
+def png_frame_bytes(frame):
+    """Host-only: `total` of a FRAME_PNG or FRAME_PNG_RUNS frame, its length in bytes (poppy_png_frame_bytes: the first four bytes, little-endian)."""
+    return coded_frame_bytes(frame, "png")
+
+
+def _coded_frame(call, what, w, h, fmt, chk=None):
+    """A coded frame of format fmt out of call(dst), `what` by name, cut to its `total`.  chk(rc, what): the context's check; without one a status raises as poppy_<what>'s."""
+    out = np.empty(max(frame_bytes(fmt, w, h), 4), np.uint8)
+    rc = call(_p(out))
+    if chk:
+        chk(rc, what)
+    elif rc:
+        raise PoppyError(f"poppy_{what}: {rc}")
+    return out[:coded_frame_bytes(out, "gif" if fmt == FRAME_GIF else "jpeg")].copy()
+
+
+def _pal8_to_gif(call, pal8, w, h, chk=None):
+    a = np.ascontiguousarray(pal8, np.uint8)
+    if a.size != w * h + 768:
+        raise PoppyError("pal8_to_gif_frame: a PAL8 frame has w * h + 768 bytes")
+    return _coded_frame(lambda dst: call(_p(a), int(w), int(h), dst), "pal8_to_gif_frame", w, h, FRAME_GIF, chk)
 
 
 def pal8_to_gif_frame(pal8, w, h):
     """Host-only: the FRAME_GIF frame of a flat PAL8 frame (poppy_pal8_to_gif_frame): `total`, the palette, the LZW-coded indices as GIF image data; a flat
     uint8 array of exactly `total` bytes."""
-    a = np.ascontiguousarray(pal8, np.uint8)
-    if a.size != w * h + 768:
-        raise PoppyError("pal8_to_gif_frame: a PAL8 frame has w * h + 768 bytes")
-    return _gif_frame(lambda out: lib().poppy_pal8_to_gif_frame(_p(a), int(w), int(h), _p(out)), "poppy_pal8_to_gif_frame", w, h)
+    return _pal8_to_gif(lib().poppy_pal8_to_gif_frame, pal8, w, h)
 
 
 def bgr_to_gif_frame(bgr):
     """Host-only: the FRAME_GIF frame of an HxWx3 BGR frame (poppy_bgr_to_gif_frame = bgr_to_pal8, then pal8_to_gif_frame)."""
     a = np.ascontiguousarray(bgr, np.uint8)
     h, w = a.shape[:2]
-    return _gif_frame(lambda out: lib().poppy_bgr_to_gif_frame(_p(a), w * 3, w, h, _p(out)), "poppy_bgr_to_gif_frame", w, h)
+    return _coded_frame(lambda dst: lib().poppy_bgr_to_gif_frame(_p(a), w * 3, w, h, dst), "bgr_to_gif_frame", w, h, FRAME_GIF)
 
 
-def jpeg_frame_bytes(frame):
-    """Host-only: `total` of a FRAME_JPEG frame, its length in bytes (poppy_jpeg_frame_bytes: the first four bytes, little-endian)."""
-    f = np.ascontiguousarray(frame, np.uint8)
-    if f.size < 4:
-        raise PoppyError("jpeg_frame_bytes: a coded frame has at least four bytes")
-    return int(lib().poppy_jpeg_frame_bytes(_p(f)))
-
-
-def _jpeg_frame(call, name, w, h, fmt=FRAME_JPEG):
-    out = np.empty(max(frame_bytes(fmt, w, h), 4), np.uint8)
-    rc = call(out)
-    if rc:
-        raise PoppyError(f"{name}: {rc}")
-    return out[:jpeg_frame_bytes(out)].copy()
+def _planes_to_jpeg(call, fmt, planes, w, h, quality, chk=None):
+    """The body of i420_to_jpeg_frame (fmt FRAME_JPEG) and i444_to_jpeg_frame (FRAME_JPEG444), on the host or a context."""
+    name, size, says = ("i444", 3 * w * h, "3 * w * h") if fmt == FRAME_JPEG444 else ("i420", frame_bytes(FRAME_I420, w, h), "w * h + 2 * cw * ch")
+    a = np.ascontiguousarray(planes, np.uint8).ravel()
+    if w > 0 and h > 0 and a.size != size:
+        raise PoppyError(f"{name}_to_jpeg_frame: an {name.upper()} frame has {says} bytes")
+    return _coded_frame(lambda dst: call(_p(a), int(w), int(h), int(quality), dst), f"{name}_to_jpeg_frame", w, h, fmt, chk)
 
 
 def i420_to_jpeg_frame(i420, w, h, quality=JPEG_QUALITY_DEFAULT):
     """Host-only: the FRAME_JPEG frame of a flat I420 frame (poppy_i420_to_jpeg_frame): `total`, then one baseline JFIF file; a flat uint8 array of its own length."""
-    a = np.ascontiguousarray(i420, np.uint8).ravel()
-    if w > 0 and h > 0 and a.size != frame_bytes(FRAME_I420, w, h):
-        raise PoppyError("i420_to_jpeg_frame: an I420 frame has w * h + 2 * cw * ch bytes")
-    return _jpeg_frame(lambda out: lib().poppy_i420_to_jpeg_frame(_p(a), int(w), int(h), int(quality), _p(out)), "poppy_i420_to_jpeg_frame", w, h)
+    return _planes_to_jpeg(lib().poppy_i420_to_jpeg_frame, FRAME_JPEG, i420, w, h, quality)
 
 
 def bgr_to_jpeg_frame(bgr, quality=JPEG_QUALITY_DEFAULT):
     """Host-only: the FRAME_JPEG frame of an HxWx3 BGR frame (poppy_bgr_to_jpeg_frame = bgr_to_i420, then i420_to_jpeg_frame)."""
     a = np.ascontiguousarray(bgr, np.uint8)
     h, w = a.shape[:2]
-    return _jpeg_frame(lambda out: lib().poppy_bgr_to_jpeg_frame(_p(a), w * 3, w, h, int(quality), _p(out)), "poppy_bgr_to_jpeg_frame", w, h)
+    return _coded_frame(lambda dst: lib().poppy_bgr_to_jpeg_frame(_p(a), w * 3, w, h, int(quality), dst), "bgr_to_jpeg_frame", w, h, FRAME_JPEG)
 
 
 def _i444(call, what, bgr, row_pad, chk=None):
-    a = np.ascontiguousarray(bgr, np.uint8)
-    h, w = a.shape[:2]
-    stride = w * 3 + int(row_pad)
-    if row_pad:
-        buf = np.full((h, stride), 0xA5, np.uint8)
-        buf[:, :w * 3] = a.reshape(h, w * 3)
-        a = buf
+    a, stride, w, h = _padded_rows(bgr, row_pad)
     out = np.empty(3 * w * h, np.uint8)
     rc = call(_p(a), stride, w, h, _p(out))
     if chk:
@@ -383,25 +401,14 @@ def bgr_to_i444(bgr, row_pad=0):
 def i444_to_jpeg_frame(i444, w, h, quality=JPEG_QUALITY_DEFAULT):
     """Host-only: the FRAME_JPEG444 frame of flat I444 planes (poppy_i444_to_jpeg_frame): `total`, then one baseline JFIF file with 4:4:4 sampling; a flat uint8
     array of its own length."""
-    a = np.ascontiguousarray(i444, np.uint8).ravel()
-    if w > 0 and h > 0 and a.size != 3 * w * h:
-        raise PoppyError("i444_to_jpeg_frame: an I444 frame has 3 * w * h bytes")
-    return _jpeg_frame(lambda out: lib().poppy_i444_to_jpeg_frame(_p(a), int(w), int(h), int(quality), _p(out)), "poppy_i444_to_jpeg_frame", w, h, FRAME_JPEG444)
+    return _planes_to_jpeg(lib().poppy_i444_to_jpeg_frame, FRAME_JPEG444, i444, w, h, quality)
 
 
 def bgr_to_jpeg444_frame(bgr, quality=JPEG_QUALITY_DEFAULT):
     """Host-only: the FRAME_JPEG444 frame of an HxWx3 BGR frame (poppy_bgr_to_jpeg444_frame = bgr_to_i444, then i444_to_jpeg_frame)."""
     a = np.ascontiguousarray(bgr, np.uint8)
     h, w = a.shape[:2]
-    return _jpeg_frame(lambda out: lib().poppy_bgr_to_jpeg444_frame(_p(a), w * 3, w, h, int(quality), _p(out)), "poppy_bgr_to_jpeg444_frame", w, h, FRAME_JPEG444)
-
-
-def png_frame_bytes(frame):
-    """Host-only: `total` of a FRAME_PNG or FRAME_PNG_RUNS frame, its length in bytes (poppy_png_frame_bytes: the first four bytes, little-endian)."""
-    f = np.ascontiguousarray(frame, np.uint8)
-    if f.size < 4:
-        raise PoppyError("png_frame_bytes: a coded frame has at least four bytes")
-    return int(lib().poppy_png_frame_bytes(_p(f)))
+    return _coded_frame(lambda dst: lib().poppy_bgr_to_jpeg444_frame(_p(a), w * 3, w, h, int(quality), dst), "bgr_to_jpeg444_frame", w, h, FRAME_JPEG444)
 
 
 def png_table(k):
@@ -432,13 +439,7 @@ PNG_CANARY = 0xA5
 
 
 def _png_frame(call, what, bgr, row_pad, chk=None, whole=False, fmt=FRAME_PNG):
-    a = np.ascontiguousarray(bgr, np.uint8)
-    h, w = a.shape[:2]
-    stride = w * 3 + int(row_pad)
-    if row_pad:
-        buf = np.full((h, stride), 0xA5, np.uint8)
-        buf[:, :w * 3] = a.reshape(h, w * 3)
-        a = buf
+    a, stride, w, h = _padded_rows(bgr, row_pad)
     out = np.full(max(frame_bytes(fmt, w, h), 4) + 64, PNG_CANARY, np.uint8)
     rc = call(_p(a), stride, w, h, _p(out))
     if chk:
@@ -461,27 +462,21 @@ def bgr_to_png_runs_frame(bgr, row_pad=0, whole=False):
     return _png_frame(lib().poppy_bgr_to_png_runs_frame, "bgr_to_png_runs_frame", bgr, row_pad, None, whole, FRAME_PNG_RUNS)
 
 
-def _gif_frames(call, chk, frames, row_pad, frame_pad):
-    a = np.ascontiguousarray(frames, np.uint8)
-    n, h, w = a.shape[:3]
-    stride = w * 3 + int(row_pad)
-    frame_stride = stride * h + int(frame_pad)
-    if row_pad or frame_pad:
-        buf = np.full((n, frame_stride), 0xA5, np.uint8)
-        buf[:, :stride * h].reshape(n, h, stride)[:, :, :w * 3] = a.reshape(n, h, w * 3)
-        a = buf
+def _gif_frames(call, frames, row_pad, frame_pad, chk=None):
+    a, stride, frame_stride, n, w, h = _padded_frames(frames, row_pad, frame_pad)
     out = np.empty((n, max(frame_bytes(FRAME_GIF_SEQ, w, h), 4)), np.uint8)
-    chk(call(_p(a), stride, frame_stride, n, w, h, _p(out)))
+    rc = call(_p(a), stride, frame_stride, n, w, h, _p(out))
+    if chk:
+        chk(rc, "bgr_frames_to_gif_frames")
+    elif rc:
+        raise PoppyError(f"poppy_bgr_frames_to_gif_frames: {rc}")
     return [f[:gif_frame_bytes(f)].copy() for f in out]
 
 
 def bgr_frames_to_gif_frames(frames, row_pad=0, frame_pad=0):
     """Host-only: the library's GIF_SEQ frames of a sequence of n HxWx3 BGR frames (poppy_bgr_frames_to_gif_frames = bgr_frames_to_pal8, then pal8_to_gif_frame
     of every frame): a list of n flat uint8 arrays, each cut to its `total`.  row_pad / frame_pad: as in bgr_frames_to_pal8."""
-    def chk(rc):
-        if rc:
-            raise PoppyError(f"poppy_bgr_frames_to_gif_frames: {rc}")
-    return _gif_frames(lib().poppy_bgr_frames_to_gif_frames, chk, frames, row_pad, frame_pad)
+    return _gif_frames(lib().poppy_bgr_frames_to_gif_frames, frames, row_pad, frame_pad)
 
 
 def frame_scaled_size(w, h, factor):
@@ -497,14 +492,8 @@ def frame_scaled_size(w, h, factor):
 def _scaled_frame(call, what, bgr, size, args, row_pad, dst_pad, chk=None):
     """An HxWx3 BGR frame through one of the four scaling calls, `what` by name: size(w, h) is the result's (ow, oh), args what the call takes between the source's
     size and dst.  chk(rc): the context's check; without one a status raises as poppy_<what>'s."""
-    a = np.ascontiguousarray(bgr, np.uint8)
-    h, w = a.shape[:2]
+    a, stride, w, h = _padded_rows(bgr, row_pad)
     ow, oh = size(w, h)
-    stride = w * 3 + int(row_pad)
-    if row_pad:
-        buf = np.full((h, stride), 0xA5, np.uint8)
-        buf[:, :w * 3] = a.reshape(h, w * 3)
-        a = buf
     out = np.full((max(oh, 1), max(ow, 1) * 3 + int(dst_pad)), 0xA5, np.uint8)
     rc = call(_p(a), stride, w, h, *args, _p(out), ow * 3 + int(dst_pad))
     if chk:
@@ -1101,12 +1090,7 @@ class Context:
     def i420_to_jpeg_frame(self, i420, w, h, quality=JPEG_QUALITY_DEFAULT):
         """The FRAME_JPEG frame of a flat I420 frame, coded on this context's GPU (poppy_hip_i420_to_jpeg_frame: upload, the two kernels, download): the bytes
         of the host's i420_to_jpeg_frame."""
-        a = np.ascontiguousarray(i420, np.uint8).ravel()
-        if w > 0 and h > 0 and a.size != frame_bytes(FRAME_I420, w, h):
-            raise PoppyError("i420_to_jpeg_frame: an I420 frame has w * h + 2 * cw * ch bytes")
-        out = np.empty(max(frame_bytes(FRAME_JPEG, w, h), 4), np.uint8)
-        self._chk(lib().poppy_hip_i420_to_jpeg_frame(self.h, _p(a), int(w), int(h), int(quality), _p(out)), "i420_to_jpeg_frame")
-        return out[:jpeg_frame_bytes(out)].copy()
+        return _planes_to_jpeg(lambda *args: lib().poppy_hip_i420_to_jpeg_frame(self.h, *args), FRAME_JPEG, i420, w, h, quality, self._chk)
 
     def bgr_to_i444(self, bgr, row_pad=0):
         """The I444 planes of an HxWx3 BGR frame, converted on this context's GPU (poppy_hip_bgr_to_i444: upload, the kernel, download): the bytes of the host's
@@ -1126,27 +1110,17 @@ class Context:
     def i444_to_jpeg_frame(self, i444, w, h, quality=JPEG_QUALITY_DEFAULT):
         """The FRAME_JPEG444 frame of flat I444 planes, coded on this context's GPU (poppy_hip_i444_to_jpeg_frame: upload, the two kernels, download): the bytes
         of the host's i444_to_jpeg_frame."""
-        a = np.ascontiguousarray(i444, np.uint8).ravel()
-        if w > 0 and h > 0 and a.size != 3 * w * h:
-            raise PoppyError("i444_to_jpeg_frame: an I444 frame has 3 * w * h bytes")
-        out = np.empty(max(frame_bytes(FRAME_JPEG444, w, h), 4), np.uint8)
-        self._chk(lib().poppy_hip_i444_to_jpeg_frame(self.h, _p(a), int(w), int(h), int(quality), _p(out)), "i444_to_jpeg_frame")
-        return out[:jpeg_frame_bytes(out)].copy()
+        return _planes_to_jpeg(lambda *args: lib().poppy_hip_i444_to_jpeg_frame(self.h, *args), FRAME_JPEG444, i444, w, h, quality, self._chk)
 
     def pal8_to_gif_frame(self, pal8, w, h):
         """The FRAME_GIF frame of a flat PAL8 frame, coded on this context's GPU (poppy_hip_pal8_to_gif_frame: upload, the two kernels, download): the bytes of
         the host's pal8_to_gif_frame."""
-        a = np.ascontiguousarray(pal8, np.uint8)
-        if a.size != w * h + 768:
-            raise PoppyError("pal8_to_gif_frame: a PAL8 frame has w * h + 768 bytes")
-        out = np.empty(max(frame_bytes(FRAME_GIF, w, h), 4), np.uint8)
-        self._chk(lib().poppy_hip_pal8_to_gif_frame(self.h, _p(a), int(w), int(h), _p(out)), "pal8_to_gif_frame")
-        return out[:gif_frame_bytes(out)].copy()
+        return _pal8_to_gif(lambda *args: lib().poppy_hip_pal8_to_gif_frame(self.h, *args), pal8, w, h, self._chk)
 
     def bgr_frames_to_gif_frames(self, frames, row_pad=0, frame_pad=0):
         """The FRAME_GIF_SEQ frames of a sequence of n HxWx3 BGR frames, palette and coding on this context's GPU (poppy_hip_bgr_frames_to_gif_frames: upload, the
         sequence pass per frame, the palette build, the coder and the gather per frame, download): the bytes of the host's bgr_frames_to_gif_frames, as its list."""
-        return _gif_frames(lambda *args: lib().poppy_hip_bgr_frames_to_gif_frames(self.h, *args), lambda rc: self._chk(rc, "bgr_frames_to_gif_frames"), frames, row_pad, frame_pad)
+        return _gif_frames(lambda *args: lib().poppy_hip_bgr_frames_to_gif_frames(self.h, *args), frames, row_pad, frame_pad, self._chk)
 
     def close(self):
         if self.h:
@@ -1551,16 +1525,8 @@ class Context:
         """poppy::morph end to end: returns (status, frames, printed morph distance or None).  status is POPPY_OK (0) or
         POPPY_E_NOMATCH (-5, fallback frames written); anything else raises.  row_pad = (bytes, bytes): the two images are handed over with that many
         extra bytes per row (cv::Mat ROIs, src/poppy.cpp:234-239: step > cols * 3), the padding filled with a pattern no pixel may come from."""
-        a = np.ascontiguousarray(bgr1, np.uint8); b = np.ascontiguousarray(bgr2, np.uint8)
-        h, w = a.shape[:2]
-        strides = [w * 3 + int(row_pad[0]), w * 3 + int(row_pad[1])]
-        if row_pad != (0, 0):
-            padded = []
-            for img, st in zip((a, b), strides):
-                buf = np.full((h, st), 0xA5, np.uint8)
-                buf[:, :w * 3] = img.reshape(h, w * 3)
-                padded.append(buf)
-            a, b = padded
+        a, stride_a, w, h = _padded_rows(bgr1, row_pad[0])
+        b, stride_b = _padded_rows(bgr2, row_pad[1])[:2]
         frames = []
         fmt = self.frame_format
 
@@ -1568,7 +1534,7 @@ class Context:
             frames.append(_frame_view(ptr, ww, hh, stride, fmt).copy())
         fn = WRITE_CB(cb) if collect else None
         d = C.c_double(float("nan"))
-        rc = lib().poppy_hip_morph(self.h, _p(a), strides[0], _p(b), strides[1], w, h, phase, int(distance),
+        rc = lib().poppy_hip_morph(self.h, _p(a), stride_a, _p(b), stride_b, w, h, phase, int(distance),
                                    C.cast(fn, C.c_void_p) if fn else None, None, C.byref(d))
         if rc not in (0, -5):
             self._chk(rc, "morph")

@@ -2,7 +2,7 @@
 //   poppy_hip.cpp     context life cycle, HBM layout, plan blob allocation (plan_blob.h), the pair loaders and the C entry points of the resident-pair API
 //   frame_render.cpp  one frame (frame_render.h): the frame body and the two halves of a frame, prepare_slot and render_slot
 //   frame_sequence.cpp  the multi-frame driver (frame_sequence.h): the planner team's SeqPlans, render_frame, render_sequence and its download pump
-//   frame_format.cpp  the writer's formats and geometry (frame_format.h; frame_limits.h: the bounds shared with the host statements): their facts, slot buffers, conversion launches, the setters
+//   frame_format.cpp  the writer's formats and geometry (frame_format.h; frame_limits.h: one record per format and the bounds shared with the host statements): slot buffers, conversion launches, the setters
 //   palette_seq.cpp   the PAL8_SEQ / GIF_SEQ sequence (palette_seq.h): store, palette, the two hand-over loops;  writer_ring.cpp: the pinned ring towards the writer (writer_ring.h)
 //   writer_image.cpp  the frames that no slot renders and the stand-alone conversion entry points (writer_image.h);  writer_buffers.h: the grow-only device buffer and the call-scoped holder
 //   pair_begin.cpp    the pair set-up from raw images (pair_begin.h): its schedule and stages, the chain threads (setup_latch.h), the pair_begin entry points

@@ -1,4 +1,4 @@
-// frame_format.cpp — the writer's formats and geometry (frame_format.h): their facts, the slots' conversion buffers, the conversion launches and the three setters that
+// frame_format.cpp — the writer's formats and geometry (frame_format.h) over the formats' records (frame_limits.h): the slots' conversion buffers, the conversion launches and the three setters that
 // change this state.  The frame path itself — which stream a frame's conversion runs on, what its completion event rides on, when its copy is issued — is
 // frame_render.cpp's and frame_sequence.cpp's (enqueue_body, render_slot, render_sequence_frames).
 #include "context.h"
@@ -10,22 +10,18 @@ constexpr const char* kJpegSizeMsg = "POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 t
 constexpr const char* kPngSizeMsg = "POPPY_FRAME_PNG and POPPY_FRAME_PNG_RUNS take frames whose capacity stays below 2^31 bytes";
 constexpr const char* kSeqSizeMsg = "POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ take sequences of fewer than 2^32 pixels in all";
 
-bool format_known(int fmt) {
-    return fmt == POPPY_FRAME_BGR || fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ || format_is_jpeg(fmt) || format_is_png(fmt);
-}
-size_t coded_frame_least(int fmt) { return format_is_jpeg(fmt) ? kJpegFrameMinBytes : format_is_png(fmt) ? kPngFrameMinBytes : kGifFrameMinBytes; }
 const char* format_refuses(int fmt, int W, int H) {
-    if ((format_builds_palette(fmt) || format_is_sequence(fmt)) && !pal8_fits(W, H)) return kPal8SizeMsg;
-    if (format_is_jpeg(fmt)) return jpeg_fits(W, H, format_sampling(fmt)) ? nullptr : kJpegSizeMsg;
-    if (format_is_png(fmt)) return png_fits(fmt, W, H) ? nullptr : kPngSizeMsg;
-    if (format_is_coded(fmt) && (W > 65535 || H > 65535)) return kGifSizeMsg;
-    return nullptr;
+    const FormatTraits* t = format_traits(fmt);
+    if (!t) return nullptr;
+    if (t->raster == kRasterPal8 && !pal8_fits(W, H)) return kPal8SizeMsg;
+    if (fits(*t, W, H)) return nullptr;
+    return t->coder == kCoderJpeg ? kJpegSizeMsg : t->coder == kCoderPng ? kPngSizeMsg : kGifSizeMsg;
 }
 const char* sequence_refuses(int fmt, int n, int W, int H) {
     if (const char* why = format_refuses(fmt, W, H)) return why;
     return (unsigned long long)n * (unsigned long long)W * (unsigned long long)H >= POPPY_PAL8_SEQ_MAX_PIXELS ? kSeqSizeMsg : nullptr;
 }
-size_t writer_stride(int fmt, int W) { return format_is_coded(fmt) ? 0 : fmt == POPPY_FRAME_BGR ? (size_t)W * 3 : (size_t)W; }
+size_t writer_stride(int fmt, int W) { return format_stride(*format_traits(fmt), W); }
 constexpr const char* kSizeMsg = "the frame size set with poppy_hip_set_frame_size takes frames at least as large and at most 8 times as large per side";
 WriterGeom scaled_geom(int W, int H, int scale) { return WriterGeom{(W + scale - 1) / scale, (H + scale - 1) / scale, scale, scale > 1 ? kScaleFactor : kScaleNone}; }
 WriterGeom sized_geom(int ow, int oh) { return WriterGeom{ow, oh, 1, kScaleSize}; }
@@ -44,7 +40,7 @@ void launch_writer_scaling(const WriterGeom& g, const uint8_t* src, uint8_t* dst
 }
 const char* scaling_mark(const WriterGeom& g) { return g.kind == kScaleSize ? "frame_resize" : "frame_scale"; }
 int writer_format(const poppy_hip_ctx* c, bool has_writer) { return has_writer ? c->frame_format : POPPY_FRAME_BGR; }
-bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer) { return has_writer && format_is_sequence(c->frame_format); }
+bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer) { return has_writer && format_traits(c->frame_format)->sequence; }
 
 int alloc_zeroed_tables(poppy_hip_ctx* c, uint8_t** tables, size_t bytes) {
     if (*tables) return POPPY_OK;
@@ -88,36 +84,43 @@ static void free_slot_coded(SlotFormat& f) {
     f.coded_for = POPPY_FRAME_BGR;
 }
 
-// PNG, PNG_RUNS: the coded frame, the coder's scratch and the pinned length word.  I420: the slot's I420 buffer.  JPEG: that, the coded frame, the coder's scratch, the pinned length word and the context's tables.  JPEG444: the same with the slot's I444 buffer in the I420 buffer's place.  PAL8: its PAL8 buffer, tables, side stream and event.  GIF: PAL8's (the coder reads the slot's PAL8 frame) and the coded frame, the
-// coder's scratch and the pinned length word.  PAL8_SEQ and GIF_SEQ: the slots' side streams and the context's sequence tables — the store and the index ring depend on the
-// sequence's length and, under GIF_SEQ, the ring of coded frames: palette_seq.cpp's seq_begin, seq_finish.  All of it in the writer's geometry; with a scale above 1 or a size the scaled BGR frame too.
+// the slot's buffer of a raster form (none: none of its own — the BGR frame is the slot's `out` or `scaled`)
+static uint8_t* SlotFormat::* const kRasterBuffer[] = {nullptr, &SlotFormat::i420, &SlotFormat::i444, &SlotFormat::pal8};
+
+size_t coding_scratch_bytes(const FormatTraits& t, int W, int H) {
+    return t.coder == kCoderJpeg ? jpeg_scratch_bytes(W, H, t.sampling()) : t.coder == kCoderPng ? png_scratch_bytes(W, H, t.runs()) : gif_scratch_bytes(W, H);
+}
+
+// What the format's record names, per slot.  A raster step: the buffer of its form, kept until the pair's buffers go, and under PAL8 the conversion's tables.  The
+// palette formats, the sequences too: the side stream and its event.  A coder step: the coded frame, the coder's scratch and the pinned length word, sized for
+// this format, and under JPEG the context's tables.  A sequence format: the context's sequence tables — the store and the index ring depend on the sequence's
+// length and, under GIF_SEQ, the ring of coded frames: palette_seq.cpp's seq_begin, seq_finish.  All of it in the writer's geometry; with a scale above 1 or a
+// size the scaled BGR frame too.
 int alloc_slot_format(poppy_hip_ctx* c) {
     const WriterGeom g = writer_geom(c);
     const int fmt = c->frame_format, W = g.w, H = g.h;
     if (const char* why = writer_refuses(c, fmt, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    const FormatTraits& t = *format_traits(fmt);
+    const FrameRaster raster = t.slot_raster();
     for (FrameSlot& slot : c->slots) {
         SlotFormat& f = slot.fmt;
-        if (g.scaled() && !f.scaled) HIPCHK(c, hipMalloc((void**)&f.scaled, poppy_frame_bytes(POPPY_FRAME_BGR, W, H) + 16));
-        if (format_converts_to_i420(fmt) && !f.i420) HIPCHK(c, hipMalloc((void**)&f.i420, poppy_frame_bytes(POPPY_FRAME_I420, W, H) + 16));
-        if (fmt == POPPY_FRAME_JPEG444 && !f.i444) HIPCHK(c, hipMalloc((void**)&f.i444, (size_t)W * H * 3 + 16));
-        if (format_builds_palette(fmt)) {
-            if (!f.pal8) HIPCHK(c, hipMalloc((void**)&f.pal8, poppy_frame_bytes(POPPY_FRAME_PAL8, W, H) + 16));
-            int rc = alloc_zeroed_tables(c, &f.pal8_tables, kPal8TableBytes); if (rc) return rc;
-        }
-        if (format_builds_palette(fmt) || format_is_sequence(fmt)) { int rc = alloc_slot_side(c, f); if (rc) return rc; }
-        if (!format_codes_per_frame(fmt)) continue;                 // (the slot's coded frame: GIF_SEQ codes from the store into the sequence's ring)
-        if (format_is_jpeg(fmt)) { int rc = ensure_jpeg_tables(c); if (rc) return rc; f.jpeg_tables = c->jpeg_tables; }
+        if (g.scaled() && !f.scaled) HIPCHK(c, hipMalloc((void**)&f.scaled, raster_bytes(kRasterNone, W, H) + 16));
+        if (raster != kRasterNone && !(f.*kRasterBuffer[raster])) HIPCHK(c, hipMalloc((void**)&(f.*kRasterBuffer[raster]), raster_bytes(raster, W, H) + 16));
+        if (raster == kRasterPal8) { int rc = alloc_zeroed_tables(c, &f.pal8_tables, kPal8TableBytes); if (rc) return rc; }
+        if (t.raster == kRasterPal8) { int rc = alloc_slot_side(c, f); if (rc) return rc; }
+        if (t.slot_coder() == kCoderNone) continue;                 // (the slot's coded frame: GIF_SEQ codes from the store into the sequence's ring)
+        if (t.coder == kCoderJpeg) { int rc = ensure_jpeg_tables(c); if (rc) return rc; f.jpeg_tables = c->jpeg_tables; }
         if (f.coded_for != fmt) free_slot_coded(f);                 // (sized for another coded format; the frames are drained and the bodies of that format are captured again)
         f.coded_for = fmt;
-        if (!f.coded) HIPCHK(c, hipMalloc((void**)&f.coded, poppy_frame_bytes(fmt, W, H) + 16));
-        if (!f.coded_scratch) HIPCHK(c, hipMalloc((void**)&f.coded_scratch, format_is_jpeg(fmt) ? jpeg_scratch_bytes(W, H, format_sampling(fmt)) : format_is_png(fmt) ? png_scratch_bytes(W, H, fmt == POPPY_FRAME_PNG_RUNS) : gif_scratch_bytes(W, H)));
+        if (!f.coded) HIPCHK(c, hipMalloc((void**)&f.coded, frame_bytes(t, W, H) + 16));
+        if (!f.coded_scratch) HIPCHK(c, hipMalloc((void**)&f.coded_scratch, coding_scratch_bytes(t, W, H)));
         if (!f.coded_total) {
             HIPCHK(c, hipHostMalloc((void**)&f.coded_total, 64, hipHostMallocMapped));
             HIPCHK(c, hipHostGetDevicePointer(&f.coded_total_dev, f.coded_total, 0));
             *f.coded_total = 0;
         }
     }
-    return format_is_sequence(fmt) ? alloc_zeroed_tables(c, &c->seq.tables, kPal8SeqTableBytes) : POPPY_OK;
+    return t.sequence ? alloc_zeroed_tables(c, &c->seq.tables, kPal8SeqTableBytes) : POPPY_OK;
 }
 
 void free_slot_format_pair(SlotFormat& f) {
@@ -140,38 +143,41 @@ void free_context_format(poppy_hip_ctx* c) {
 
 bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt, const WriterGeom& g) {
     const SlotFormat& f = slot.fmt;
+    const FormatTraits& t = *format_traits(fmt);
+    const FrameRaster raster = t.slot_raster();
     if (g.scaled() && !f.scaled) return false;
-    if (fmt == POPPY_FRAME_I420) return f.i420 != nullptr;
-    if (format_is_jpeg(fmt)) return (fmt == POPPY_FRAME_JPEG444 ? f.i444 : f.i420) && f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt && f.jpeg_tables;
-    if (format_is_sequence(fmt)) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
-    if (format_builds_palette(fmt) && !(f.pal8 && f.pal8_tables && f.fmt_stream && f.bgr_done)) return false;
-    return !format_codes_per_frame(fmt) || (f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt);      // (GIF, PNG, PNG_RUNS)
+    if (t.sequence) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
+    if (raster != kRasterNone && !(f.*kRasterBuffer[raster])) return false;
+    if (raster == kRasterPal8 && !(f.pal8_tables && f.fmt_stream && f.bgr_done)) return false;
+    if (t.coder == kCoderJpeg && !f.jpeg_tables) return false;
+    return !t.coded() || (f.coded && f.coded_scratch && f.coded_total && f.coded_for == fmt);
 }
 const uint8_t* slot_bgr(const FrameSlot& f, const WriterGeom& g) { return g.scaled() ? f.fmt.scaled : f.out; }
 const uint8_t* slot_frame(const FrameSlot& f, int fmt, const WriterGeom& g) {
-    return fmt == POPPY_FRAME_I420 ? f.fmt.i420 : fmt == POPPY_FRAME_PAL8 ? f.fmt.pal8 : format_codes_per_frame(fmt) ? f.fmt.coded : slot_bgr(f, g);
+    const FormatTraits& t = *format_traits(fmt);
+    return t.slot_coder() != kCoderNone ? f.fmt.coded : t.slot_raster() != kRasterNone ? f.fmt.*kRasterBuffer[t.slot_raster()] : slot_bgr(f, g);
 }
 bool slot_frame_length(const FrameSlot& f, int fmt, size_t capacity, size_t* bytes) {
-    *bytes = format_is_coded(fmt) ? *(volatile uint32_t*)f.fmt.coded_total : capacity;
-    return !format_is_coded(fmt) || coded_length_ok(*bytes, capacity, coded_frame_least(fmt));
+    const FormatTraits& t = *format_traits(fmt);
+    *bytes = t.coded() ? *(volatile uint32_t*)f.fmt.coded_total : capacity;
+    return !t.coded() || coded_length_ok(*bytes, capacity, t.least);
 }
 
-void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
+static void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
     launch_gif_lzw(pal8, scratch, W, H, s);
     if (tm) tm->mark("gif_lzw");
     launch_gif_pack(pal8, scratch, frame, (uint32_t*)total_dev, W, H, s, done);
     if (tm) tm->mark("gif_pack");
 }
 
-void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, jpeg::Sampling sm, hipStream_t s, hipEvent_t done, Timer* tm) {
+static void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, jpeg::Sampling sm, hipStream_t s, hipEvent_t done, Timer* tm) {
     launch_jpeg_code(planes, tables, scratch, W, H, sm, s);
     if (tm) tm->mark("jpeg_code");
     launch_jpeg_pack(tables, scratch, frame, (uint32_t*)total_dev, W, H, sm, s, done);
     if (tm) tm->mark("jpeg_pack");
 }
 
-void enqueue_png_coding(int fmt, const uint8_t* bgr, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
-    const bool runs = fmt == POPPY_FRAME_PNG_RUNS;
+static void enqueue_png_coding(bool runs, const uint8_t* bgr, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
     launch_png_filter(bgr, scratch, W, H, runs, s);
     if (tm) tm->mark("png_filter");
     launch_png_cost(scratch, W, H, runs, s);
@@ -186,41 +192,46 @@ void enqueue_png_coding(int fmt, const uint8_t* bgr, uint8_t* scratch, uint8_t* 
     if (tm) tm->mark("png_finish");
 }
 
-void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm) {
-    if (g.scaled()) {                                              // the conversion's first dispatch; what follows reads the scaled frame
-        launch_writer_scaling(g, src_bgr, b.scaled, W, H, s, fmt == POPPY_FRAME_BGR ? done : nullptr);
-        if (tm) tm->mark(scaling_mark(g));
-        src_bgr = b.scaled; W = g.w; H = g.h;
-    }
-    if (format_converts_to_i420(fmt)) {
-        const bool jpeg = fmt == POPPY_FRAME_JPEG;
-        launch_bgr_to_i420(src_bgr, b.i420, W, H, s, jpeg ? nullptr : done);
-        if (tm) tm->mark("frame_format");
-        if (jpeg) enqueue_jpeg_coding(b.i420, b.jpeg_tables, b.coded_scratch, b.coded, b.coded_total_dev, W, H, jpeg::k420, s, done, tm);
-    } else if (fmt == POPPY_FRAME_JPEG444) {                       // JPEG's chain with the I444 kernel in the I420 kernel's place
-        launch_bgr_to_i444(src_bgr, b.i444, W, H, s);
-        if (tm) tm->mark("frame_format");
-        enqueue_jpeg_coding(b.i444, b.jpeg_tables, b.coded_scratch, b.coded, b.coded_total_dev, W, H, jpeg::k444, s, done, tm);
-    } else if (format_is_png(fmt)) {                               // straight from the BGR frame
-        enqueue_png_coding(fmt, src_bgr, b.coded_scratch, b.coded, b.coded_total_dev, W, H, s, done, tm);
-    } else if (format_builds_palette(fmt)) {
+void enqueue_coding(const FormatTraits& t, const uint8_t* src, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
+    if (t.coder == kCoderGif) enqueue_gif_coding(src, scratch, frame, total_dev, W, H, s, done, tm);
+    else if (t.coder == kCoderJpeg) enqueue_jpeg_coding(src, tables, scratch, frame, total_dev, W, H, t.sampling(), s, done, tm);
+    else if (t.coder == kCoderPng) enqueue_png_coding(t.runs(), src, scratch, frame, total_dev, W, H, s, done, tm);
+}
+
+const uint8_t* enqueue_raster(FrameRaster raster, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm) {
+    if (raster == kRasterI420) launch_bgr_to_i420(src_bgr, b.i420, W, H, s, done);
+    else if (raster == kRasterI444) launch_bgr_to_i444(src_bgr, b.i444, W, H, s, done);
+    else {
         // PAL8 is three dispatches, and the palette build in the middle is one workgroup's serial work (about as long as the rest of the frame)
-        const bool gif = fmt == POPPY_FRAME_GIF;
         launch_pal8_hist(src_bgr, b.pal8_tables, W, H, s);
         if (tm) tm->mark("pal8_hist");
         launch_pal8_build(b.pal8_tables, b.pal8, W, H, s);
         if (tm) tm->mark("pal8_build");
-        launch_pal8_remap(src_bgr, b.pal8_tables, b.pal8, W, H, s, gif ? nullptr : done);
-        if (tm) tm->mark("frame_format");                      // (under PAL8 and GIF: the index plane alone)
-        if (gif) enqueue_gif_coding(b.pal8, b.coded_scratch, b.coded, b.coded_total_dev, W, H, s, done, tm);
+        launch_pal8_remap(src_bgr, b.pal8_tables, b.pal8, W, H, s, done);
     }
+    if (tm) tm->mark("frame_format");                              // (under PAL8: the index plane alone)
+    return b.*kRasterBuffer[raster];
+}
+
+void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm) {
+    const FormatTraits& t = *format_traits(fmt);
+    const FrameRaster raster = t.slot_raster();
+    const bool codes = t.slot_coder() != kCoderNone;
+    if (g.scaled()) {                                              // the conversion's first dispatch; what follows reads the scaled frame
+        launch_writer_scaling(g, src_bgr, b.scaled, W, H, s, t.converts() ? nullptr : done);
+        if (tm) tm->mark(scaling_mark(g));
+        src_bgr = b.scaled; W = g.w; H = g.h;
+    }
+    const uint8_t* src = src_bgr;                                  // what the coder reads: the raster form, or (PNG) the BGR frame itself
+    if (raster != kRasterNone) src = enqueue_raster(raster, src_bgr, W, H, b, s, codes ? nullptr : done, tm);
+    if (codes) enqueue_coding(t, src, b.jpeg_tables, b.coded_scratch, b.coded, b.coded_total_dev, W, H, s, done, tm);
 }
 
 extern "C" {
 
 int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
     if (!c) return POPPY_E_ARG;
-    if (!format_known(format)) return fail(c, POPPY_E_ARG, "unknown frame format");
+    if (!format_traits(format)) return fail(c, POPPY_E_ARG, "unknown frame format");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = drain_frames(c); if (rc) return rc; }
     if (c->c1) if (const char* why = writer_refuses(c, format, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);

@@ -8,22 +8,10 @@
 
 struct poppy_hip_ctx; struct FrameSlot; struct Timer;
 
-bool format_known(int fmt);
+// The formats' facts are frame_limits.h's records (format_traits: raster form, coder, sequence, the smallest `total`); a context's format is always a known one
+// (poppy_hip_set_frame_format refuses the others), so the functions below that take `fmt` read its record without asking.
 const char* format_refuses(int fmt, int W, int H);      // why `fmt` refuses a W x H frame, or null: checked on the arguments alone, before anything is allocated or any state changes
-size_t writer_stride(int fmt, int W);      // what the writer is told: 0 for a coded frame (GIF, JPEG, JPEG444, PNG, PNG_RUNS), the width for the planar and palette formats, 3 * width for BGR
-// a palette per frame: the PAL8 triple (histogram, build, index plane) converts it — GIF is PAL8 with the two coding dispatches behind the index plane
-inline bool format_builds_palette(int fmt) { return fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF; }
-// a frame whose length its bytes decide: poppy_frame_bytes is its capacity, the slot's pinned word holds its length (slot_frame_length)
-// (GIF_SEQ: the pinned word is the sequence ring buffer's, seq_finish)
-inline bool format_is_coded(int fmt) { return fmt == POPPY_FRAME_GIF || fmt == POPPY_FRAME_GIF_SEQ || format_is_jpeg(fmt) || format_is_png(fmt); }
-// a coded frame of the slot's own, built by a coder and a pack dispatch behind the conversion: GIF behind the PAL8 triple, JPEG behind the I420 kernel, JPEG444
-// behind the I444 kernel (format_is_jpeg, format_sampling: frame_limits.h), PNG and PNG_RUNS straight from the BGR frame (six dispatches, no raster form in between)
-inline bool format_codes_per_frame(int fmt) { return fmt == POPPY_FRAME_GIF || format_is_jpeg(fmt) || format_is_png(fmt); }
-// the frame in the slot's I420 buffer: the writer's frame itself, or what the JPEG coder reads
-inline bool format_converts_to_i420(int fmt) { return fmt == POPPY_FRAME_I420 || fmt == POPPY_FRAME_JPEG; }
-size_t coded_frame_least(int fmt);      // the smallest `total` a coder of the format gives (coded_length_ok's lower bound)
-// one palette for all the frames a call hands to its writer: they wait in the sequence store until the last is rendered (PaletteSeq); GIF_SEQ is PAL8_SEQ coded
-inline bool format_is_sequence(int fmt) { return fmt == POPPY_FRAME_PAL8_SEQ || fmt == POPPY_FRAME_GIF_SEQ; }
+size_t writer_stride(int fmt, int W);      // what the writer is told (format_stride): 0 for a coded frame, the width for the planar and palette formats, 3 * width for BGR
 // The writer's geometry: what a W x H frame is for the writer of a context — ow x oh.  Under a scale s (poppy_hip_set_frame_scale) ow = (W + s - 1) / s,
 // oh = (H + s - 1) / s (kScaleFactor); under a size (poppy_hip_set_frame_size) ow x oh is that size (kScaleSize); a context has at most one of the two.
 // Everything the writer sees is sized by it: strides, frame bytes, the pinned ring, the conversion buffers, the formats' limits, the sequence store.
@@ -49,16 +37,16 @@ const char* sequence_refuses(int fmt, int n, int W, int H);      // ... and why 
 
 struct SlotFormat {
     uint8_t* scaled = nullptr;            // a scale above 1 or a size: the frame scaled down, tight BGR, ow x oh — what the conversion reads and, under BGR, what the writer gets
-    uint8_t* i420 = nullptr;              // the frame as I420 for the writer (allocated when the format is I420 and a pair is there; kept until the pair's buffers go)
-    uint8_t* i444 = nullptr;              // POPPY_FRAME_JPEG444: the frame's I444 planes, 3 * w * h bytes, which its coder reads (allocated and kept like i420)
-    uint8_t* pal8 = nullptr;              // the frame as PAL8 for the writer, and the conversion's tables (kernels.h: kPal8TableBytes) — the slot's own,
-    uint8_t* pal8_tables = nullptr;       // because the conversions of frames in flight run beside each other (allocated like i420; the stream and event live as long as the context)
-    uint8_t* coded = nullptr;             // POPPY_FRAME_GIF, POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444, POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS: the coded frame for the writer (its capacity: poppy_frame_bytes), the coder's scratch (kernels.h:
-    uint8_t* coded_scratch = nullptr;     // gif_scratch_bytes, jpeg_scratch_bytes, png_scratch_bytes) and a word of mapped pinned memory that the pack kernel stores the frame's length into: the host
-    uint32_t* coded_total = nullptr;      // reads it when `done` has fired and copies that many bytes (the GIF coder reads the slot's pal8, the JPEG coder its i420, the JPEG444 coder its i444, the PNG coder the BGR frame itself); the three
+    uint8_t* i420 = nullptr;              // the frame in the raster form of the format's record (raster_bytes): for the writer, or what the format's coder reads.  Allocated
+    uint8_t* i444 = nullptr;              // when a format with that raster step is set and a pair is there; kept until the pair's buffers go
+    uint8_t* pal8 = nullptr;              // ... and the PAL8 conversion's tables (kernels.h: kPal8TableBytes) — the slot's own, because the conversions of frames in
+    uint8_t* pal8_tables = nullptr;       // flight run beside each other (allocated like the raster buffers; the stream and event live as long as the context)
+    uint8_t* coded = nullptr;             // a format with a coder step: the coded frame for the writer (its capacity: poppy_frame_bytes), the coder's scratch
+    uint8_t* coded_scratch = nullptr;     // (coding_scratch_bytes) and a word of mapped pinned memory that the coder's last kernel stores the frame's length into: the host
+    uint32_t* coded_total = nullptr;      // reads it when `done` has fired and copies that many bytes; the three
     void* coded_total_dev = nullptr;      // are sized by coded_for, the format they were allocated under, and allocated again when the context's coded format is another
     int coded_for = POPPY_FRAME_BGR;
-    const void* jpeg_tables = nullptr;    // POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444: the context's tables for its quality (ensure_jpeg_tables; the context's to free)
+    const void* jpeg_tables = nullptr;    // the JPEG coder: the context's tables for its quality (ensure_jpeg_tables; the context's to free)
     hipStream_t fmt_stream = nullptr;     // chained PAL8 / PAL8_SEQ frames: the conversion's side stream (the chain goes on from the unsharp: enqueue_body)
     hipEvent_t bgr_done = nullptr;        // ... and the event that rides on that unsharp
 };
@@ -71,20 +59,19 @@ const uint8_t* slot_frame(const FrameSlot& f, int fmt, const WriterGeom& g);    
 const uint8_t* slot_bgr(const FrameSlot& f, const WriterGeom& g);       // ... and as BGR in the writer's geometry: the frame itself, or the scaled frame
 bool slot_frame_length(const FrameSlot& f, int fmt, size_t capacity, size_t* bytes);      // the bytes of that frame, once its `done` has fired: `capacity`, or a coded frame's own length from the slot's pinned word; false when that is out of bounds
 
-// src_bgr (W x H) scaled down to g into b.scaled (g.scaled(): the first dispatch) and in format `fmt` into b's buffers on stream s: the I420 kernel, or the PAL8
-// triple and, for GIF, the coding pair behind it.  `done` (optional) rides on the last dispatch; tm (timing mode 1) gets the marks frame_scale or frame_resize,
-// frame_format, pal8_hist, pal8_build, gif_lzw, gif_pack, jpeg_code, jpeg_pack.  JPEG: the I420 kernel and the coding pair behind it, on the context's tables (jpeg_tables);
-// JPEG444: the I444 kernel (its mark is frame_format too) into b.i444 and the same pair behind it.
+// src_bgr (W x H) scaled down to g into b.scaled (g.scaled(): the first dispatch) and in format `fmt` into b's buffers on stream s, in the two steps of the
+// format's record: the raster step (enqueue_raster), then the coder step (enqueue_coding) on what it wrote, on the context's tables (b.jpeg_tables) under JPEG.
+// `done` (optional) rides on the last dispatch; tm (timing mode 1) gets the marks frame_scale or frame_resize and the two steps' own.
 void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm);
-// the GIF half: the PAL8 frame coded into `frame`, its length also into the pinned word behind total_dev (null: none); `done` rides on the second dispatch
-void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm);
-// the JPEG half: the I420 frame (sm == k444: the I444 frame, into a POPPY_FRAME_JPEG444 frame) coded into `frame` at the quality that `tables` (device memory,
-// kernels.h: kJpegTableBytes) name; the rest as for GIF
-void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, poppy_hip::jpeg::Sampling sm, hipStream_t s, hipEvent_t done, Timer* tm);
-// the PNG chain: the BGR frame (tight, any alignment) coded into `frame` by the six dispatches of kernels_frame_png.hip; tm gets the marks png_filter, png_cost,
-// png_scan, png_pack, png_crc, png_finish; the rest as for GIF.  fmt == POPPY_FRAME_PNG_RUNS: the run-aware cost and pack kernels in the places of the two, the
-// same marks (scratch and frame sized for that format)
-void enqueue_png_coding(int fmt, const uint8_t* bgr, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm);
+// the raster step: the I420 kernel into b.i420, the I444 kernel into b.i444 (marks: frame_format), or the PAL8 triple (histogram, build, index plane; marks
+// pal8_hist, pal8_build, frame_format) on b.pal8_tables into b.pal8.  Returns the buffer written, which the coder reads; `done` rides on the last dispatch.
+const uint8_t* enqueue_raster(FrameRaster raster, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm);
+// the coder step: `src` (the record's raster form; PNG: the tight BGR frame, any alignment) coded into `frame`, its length also into the pinned word behind
+// total_dev (null: none); `done` rides on the last dispatch.  GIF: two dispatches (marks gif_lzw, gif_pack).  JPEG: two (jpeg_code, jpeg_pack), in the record's
+// sampling at the quality that `tables` (device memory, kernels.h: kJpegTableBytes) name.  PNG: the six of kernels_frame_png.hip (png_filter, png_cost,
+// png_scan, png_pack, png_crc, png_finish), under PNG_RUNS with the run-aware cost and pack kernels in the places of the two.
+void enqueue_coding(const FormatTraits& t, const uint8_t* src, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm);
+size_t coding_scratch_bytes(const FormatTraits& t, int W, int H);      // ... and what `scratch` holds (kernels.h: gif_scratch_bytes, jpeg_scratch_bytes, png_scratch_bytes)
 // the context's quantisation tables and header for its quality on the device, at an address that stays (captured bodies hold it): allocated and filled when missing
 int ensure_jpeg_tables(poppy_hip_ctx* c);
 // conversion tables, zero before the first frame (the palette builds leave them zero again): PAL8's per slot and for the scratch, the sequence's per context

@@ -1,5 +1,5 @@
-// frame_limits.h — the bounds of a writer's frame that the host statements (frame_resize.cpp, frame_sink.cpp) and the device path (frame_format.cpp, palette_seq.cpp,
-// writer_image.cpp) both check, each stated once.  Host only, nothing of HIP.
+// frame_limits.h — what a writer's frame format is, stated once: one record per POPPY_FRAME_* format (kFormats, format_traits) and the bounds of a frame that the
+// host statements (frame_resize.cpp, frame_sink.cpp) and the device path (frame_format.cpp, palette_seq.cpp, writer_image.cpp) both check.  Host only, nothing of HIP.
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "jpeg_tables.h"
@@ -9,30 +9,99 @@
 inline bool size_admits(int W, int H, int ow, int oh) {
     return ow >= 1 && oh >= 1 && ow <= W && oh <= H && (long long)W <= (long long)POPPY_FRAME_SCALE_MAX * ow && (long long)H <= (long long)POPPY_FRAME_SCALE_MAX * oh;
 }
-// A coded frame (POPPY_FRAME_GIF, POPPY_FRAME_GIF_SEQ) of w x h pixels.  Its capacity (include/poppy_hip.h has the derivation): `total` and the palette, the
-// minimum-code-size byte, every segment's payload at its bound in sub-blocks of 255 bytes behind a length byte each, the terminator ...
+// A GIF-coded frame of w x h pixels.  Its capacity (include/poppy_hip.h has the derivation): `total` and the palette, the minimum-code-size byte, every segment's
+// payload at its bound in sub-blocks of 255 bytes behind a length byte each, the terminator ...
 inline size_t gif_frame_capacity(size_t w, size_t h) {
     const size_t segments = (w * h + POPPY_GIF_SEGMENT_PIXELS - 1) / POPPY_GIF_SEGMENT_PIXELS, payload = segments * POPPY_GIF_SEGMENT_BYTES;
     return 772 + 1 + payload + (payload + 254) / 255 + 1;
 }
 constexpr size_t kGifFrameMinBytes = 776;      // ... and the smallest there is, the same with one byte of payload in one sub-block: 772 + 1 + (1 + 1) + 1
-inline bool coded_length_ok(size_t total, size_t capacity, size_t least = kGifFrameMinBytes) { return total >= least && total <= capacity; }      // a coder's `total`, before that many bytes are copied or read
-// A JPEG-coded frame (POPPY_FRAME_JPEG): `total`, the fixed header, every restart interval at its bound (include/poppy_hip.h has the derivation; jpeg_tables.h) ...
-inline size_t jpeg_frame_capacity(size_t w, size_t h, poppy_hip::jpeg::Sampling s = poppy_hip::jpeg::k420) { return (size_t)poppy_hip::jpeg::frame_capacity(w, h, s); }      // (POPPY_FRAME_JPEG444: k444, twice the blocks)
-constexpr size_t kJpegFrameMinBytes = poppy_hip::jpeg::kFrameMinBytes;      // ... and the smallest: the header, a byte of entropy-coded data, EOI
-// what the format takes: SOF0's 16-bit sides, and a capacity that `total`'s 32 bits hold
+inline bool coded_length_ok(size_t total, size_t capacity, size_t least) { return total >= least && total <= capacity; }      // a coder's `total` between its record's `least` and the capacity, before that many bytes are copied or read
+// A JPEG-coded frame: what the format takes is SOF0's 16-bit sides, and a capacity (jpeg_tables.h; include/poppy_hip.h has the derivation) that `total`'s 32 bits hold
 inline bool jpeg_fits(int W, int H, poppy_hip::jpeg::Sampling s = poppy_hip::jpeg::k420) { return W <= 65535 && H <= 65535 && poppy_hip::jpeg::frame_capacity((size_t)W, (size_t)H, s) <= 0xffffffffull; }
-// the two JPEG formats and the sampling each codes
-inline bool format_is_jpeg(int fmt) { return fmt == POPPY_FRAME_JPEG || fmt == POPPY_FRAME_JPEG444; }
-inline poppy_hip::jpeg::Sampling format_sampling(int fmt) { return fmt == POPPY_FRAME_JPEG444 ? poppy_hip::jpeg::k444 : poppy_hip::jpeg::k420; }
-// A PNG-coded frame (POPPY_FRAME_PNG): `total`, the file's fixed parts and every segment on table 7 at its longest literal (include/poppy_hip.h has the derivation;
-// png_tables.h); what the format takes is a capacity below 2^31 bytes, which IDAT's length field and `total` hold; the smallest frame has one byte of deflate data
+// A PNG-coded frame: what the format takes is a capacity (png_tables.h; with runs coded as matches png_runs_tables.h) below 2^31 bytes, which IDAT's length field and `total` hold
 inline bool png_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
-inline size_t png_frame_capacity(size_t w, size_t h) { return (size_t)poppy_hip::png::frame_capacity(w, h); }
-constexpr size_t kPngFrameMinBytes = poppy_hip::png::kFrameMinBytes;
-// The two PNG formats: POPPY_FRAME_PNG_RUNS is POPPY_FRAME_PNG with runs coded as matches (png_runs_tables.h), the same limits on its own capacity
-inline bool format_is_png(int fmt) { return fmt == POPPY_FRAME_PNG || fmt == POPPY_FRAME_PNG_RUNS; }
 inline bool png_runs_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png_runs::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
-inline size_t png_runs_frame_capacity(size_t w, size_t h) { return (size_t)poppy_hip::png_runs::frame_capacity(w, h); }
-inline bool png_fits(int fmt, int W, int H) { return fmt == POPPY_FRAME_PNG_RUNS ? png_runs_fits(W, H) : png_fits(W, H); }
-inline size_t png_frame_capacity(int fmt, size_t w, size_t h) { return fmt == POPPY_FRAME_PNG_RUNS ? png_runs_frame_capacity(w, h) : png_frame_capacity(w, h); }
+
+// The record of a format.  A frame reaches its writer in up to two steps behind the BGR frame: the raster step (the BGR frame as planes or as palette indices) and
+// the coder step, which reads the raster form (PNG: the BGR frame itself) and gives a frame whose length its own bytes decide.
+enum FrameRaster { kRasterNone = 0, kRasterI420, kRasterI444, kRasterPal8 };      // none: the BGR frame itself
+enum FrameCoder { kCoderNone = 0, kCoderGif, kCoderJpeg, kCoderPng };
+struct FormatTraits {
+    int format;                // the POPPY_FRAME_* constant
+    const char* name;          // for messages: a coded format's is its coder's ("JPEG frame coding: ")
+    FrameRaster raster;
+    FrameCoder coder;
+    int variant;               // the JPEG coder's sampling (jpeg::Sampling), the PNG coder's runs flag
+    bool sequence;             // one palette for all the frames a call hands to its writer: they wait in the sequence store until the last is rendered (palette_seq.h),
+                               // and no slot converts or codes them — the sequence pass and the sequence's coder do
+    size_t least;              // the smallest `total` its coder gives (coded_length_ok's lower bound)
+    // a frame whose length its bytes decide: poppy_frame_bytes is its capacity, the writer is told stride 0, a pinned word holds its length
+    constexpr bool coded() const { return coder != kCoderNone; }
+    // what a slot's own conversion does (enqueue_conversion) and has buffers for: nothing under a sequence format
+    constexpr FrameRaster slot_raster() const { return sequence ? kRasterNone : raster; }
+    constexpr FrameCoder slot_coder() const { return sequence ? kCoderNone : coder; }
+    constexpr bool converts() const { return slot_raster() != kRasterNone || slot_coder() != kCoderNone; }
+    constexpr poppy_hip::jpeg::Sampling sampling() const { return variant ? poppy_hip::jpeg::k444 : poppy_hip::jpeg::k420; }
+    constexpr bool runs() const { return variant != 0; }
+};
+inline constexpr FormatTraits kFormats[] = {
+    {POPPY_FRAME_BGR,      "BGR",  kRasterNone, kCoderNone, 0, false, 0},
+    {POPPY_FRAME_I420,     "I420", kRasterI420, kCoderNone, 0, false, 0},
+    {POPPY_FRAME_PAL8,     "PAL8", kRasterPal8, kCoderNone, 0, false, 0},
+    {POPPY_FRAME_PAL8_SEQ, "PAL8", kRasterPal8, kCoderNone, 0, true,  0},
+    {POPPY_FRAME_GIF,      "GIF",  kRasterPal8, kCoderGif,  0, false, kGifFrameMinBytes},
+    {POPPY_FRAME_GIF_SEQ,  "GIF",  kRasterPal8, kCoderGif,  0, true,  kGifFrameMinBytes},
+    {POPPY_FRAME_JPEG,     "JPEG", kRasterI420, kCoderJpeg, poppy_hip::jpeg::k420, false, poppy_hip::jpeg::kFrameMinBytes},      // the header, a byte of entropy-coded data, EOI
+    {POPPY_FRAME_JPEG444,  "JPEG", kRasterI444, kCoderJpeg, poppy_hip::jpeg::k444, false, poppy_hip::jpeg::kFrameMinBytes},      // (twice the blocks)
+    {POPPY_FRAME_PNG,      "PNG",  kRasterNone, kCoderPng,  0, false, poppy_hip::png::kFrameMinBytes},                            // the file's fixed parts and one byte of deflate data
+    {POPPY_FRAME_PNG_RUNS, "PNG",  kRasterNone, kCoderPng,  1, false, poppy_hip::png::kFrameMinBytes},                            // PNG with runs coded as matches, the same limits on its own capacity
+};
+constexpr const FormatTraits* format_traits(int fmt) {      // null for an unknown format
+    for (const FormatTraits& t : kFormats) if (t.format == fmt) return &t;
+    return nullptr;
+}
+
+// what the writer is told: 0 for a coded frame, the width for the planar and palette formats, 3 * width for BGR
+constexpr size_t format_stride(const FormatTraits& t, int W) { return t.coded() ? 0 : t.raster == kRasterNone ? (size_t)W * 3 : (size_t)W; }
+// the bytes of a w x h frame in a raster form (none: the tight BGR frame)
+constexpr size_t raster_bytes(FrameRaster r, size_t w, size_t h) {
+    return r == kRasterI420 ? w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2) : r == kRasterPal8 ? w * h + 768 : w * h * 3;
+}
+// what the format's coder takes (a format without one: every frame; the palette's own limit is format_refuses')
+inline bool fits(const FormatTraits& t, int W, int H) {
+    return t.coder == kCoderJpeg ? jpeg_fits(W, H, t.sampling()) : t.coder == kCoderPng ? (t.runs() ? png_runs_fits(W, H) : png_fits(W, H)) : t.coder == kCoderGif ? W <= 65535 && H <= 65535 : true;
+}
+// a coded frame's capacity, an upper bound of `total` for any content (include/poppy_hip.h has the derivations)
+inline size_t capacity(const FormatTraits& t, size_t w, size_t h) {
+    return t.coder == kCoderJpeg ? (size_t)poppy_hip::jpeg::frame_capacity(w, h, t.sampling()) :
+           t.coder == kCoderPng ? (size_t)(t.runs() ? poppy_hip::png_runs::frame_capacity(w, h) : poppy_hip::png::frame_capacity(w, h)) : t.coder == kCoderGif ? gif_frame_capacity(w, h) : 0;
+}
+// poppy_frame_bytes of a frame with positive sides: the raster form's bytes, or the capacity (PNG: nothing to size where the format refuses)
+inline size_t frame_bytes(const FormatTraits& t, int W, int H) {
+    if (!t.coded()) return raster_bytes(t.raster, (size_t)W, (size_t)H);
+    return t.coder == kCoderPng && !fits(t, W, H) ? 0 : capacity(t, (size_t)W, (size_t)H);
+}
+
+// every constant of include/poppy_hip.h has exactly one record, and the records hold what the code relies on
+constexpr bool formats_hold() {
+    constexpr int all[] = {POPPY_FRAME_BGR, POPPY_FRAME_I420, POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF, POPPY_FRAME_GIF_SEQ, POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444,
+                           POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS};
+    if (sizeof all / sizeof *all != sizeof kFormats / sizeof *kFormats) return false;
+    for (int fmt : all) {
+        int n = 0;
+        for (const FormatTraits& t : kFormats) n += t.format == fmt;
+        if (n != 1) return false;
+    }
+    for (const FormatTraits& t : kFormats) {
+        if (t.sequence && (t.slot_coder() != kCoderNone || t.slot_raster() != kRasterNone)) return false;      // a sequence format has no per-slot coder (and no raster step)
+        if (t.sequence && (t.raster != kRasterPal8 || (t.coder != kCoderNone && t.coder != kCoderGif))) return false;      // ... and is PAL8 under one palette, bare or GIF-coded (palette_seq.cpp)
+        if ((format_stride(t, 1) == 0) != t.coded()) return false;      // only a coded format reports stride 0
+        if (t.coded() != (t.least > 0)) return false;                   // ... and it alone has a smallest `total`
+        if (t.coder == kCoderGif && t.raster != kRasterPal8) return false;      // the coders read their raster form: GIF PAL8, JPEG the planes of its sampling, PNG the BGR frame
+        if (t.coder == kCoderJpeg && t.raster != (t.sampling() == poppy_hip::jpeg::k444 ? kRasterI444 : kRasterI420)) return false;
+        if (t.coder == kCoderPng && t.raster != kRasterNone) return false;
+    }
+    return true;
+}
+static_assert(formats_hold(), "kFormats: one record per POPPY_FRAME_* constant; a sequence format has no per-slot coder; only a coded format reports stride 0");

@@ -8,7 +8,7 @@ static_assert(kPlanRasterRows == kRasterChunkRows, "the plan's work list and k_r
 
 // the format the frames being submitted are converted to for their writer (their slots' bodies end with the conversion); BGR: none
 // (PAL8_SEQ, GIF_SEQ: none either — the sequence pass is launched behind the body, its destination differs from frame to frame: render_slot)
-static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached && !format_is_sequence(c->frame_format) ? c->frame_format : POPPY_FRAME_BGR; }
+static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached && !format_traits(c->frame_format)->sequence ? c->frame_format : POPPY_FRAME_BGR; }
 // ... and the geometry they are scaled down or resized to in front of it, under every format (the sequence formats' pass reads the scaled frame)
 static WriterGeom frame_wants_geom(const poppy_hip_ctx* c) { return writer_geom(c, c->writer_attached); }
 
@@ -100,8 +100,9 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     // scaled frame); the chain goes on from the full-size frame.
     const int fmt = frame_wants_format(c);
     const WriterGeom geom = frame_wants_geom(c);
-    const bool side = (fmt == POPPY_FRAME_PAL8 || fmt == POPPY_FRAME_GIF || seq_dst) && chained && done && !tm;
-    const bool converts = fmt != POPPY_FRAME_BGR || seq_dst || geom.scaled();
+    const FormatTraits& traits = *format_traits(fmt);
+    const bool side = (traits.slot_raster() == kRasterPal8 || seq_dst) && chained && done && !tm;
+    const bool converts = traits.converts() || seq_dst || geom.scaled();
     launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s,
                    side ? f.fmt.bgr_done : converts ? nullptr : done, c->levels[0].pitch);
     rec(POPPY_PYR_UNSHARP, 0, W < 2 || H < 2);

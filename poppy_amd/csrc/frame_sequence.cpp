@@ -132,7 +132,7 @@ struct FramePump {
         const int r = k % ring.R;
         const auto t0 = clk::now();
         // (GIF: the host waits in every form: k_gif_pack has stored the frame's length into the slot's pinned word by then, and the copy moves that many bytes)
-        hipError_t e = dev_wait && !format_is_coded(fmt) ? hipStreamWaitEvent(c->dl_stream, f.done, 0) : hipEventSynchronize(f.done);
+        hipError_t e = dev_wait && !format_traits(fmt)->coded() ? hipStreamWaitEvent(c->dl_stream, f.done, 0) : hipEventSynchronize(f.done);
         ms_done += lap(t0);
         size_t copy_bytes = frame_bytes;
         if (e == hipSuccess && !slot_frame_length(f, fmt, frame_bytes, &copy_bytes)) { c->err = "the coded frame's length is outside its bounds"; rc = POPPY_E_DEVICE; return false; }
@@ -212,7 +212,7 @@ static int render_sequence_frames(poppy_hip_ctx* c, const double* shape, const d
     double ms_plan = 0, ms_submit = 0;
     const auto t_seq = clk::now();
     const double w0[4] = {c->wait_ms[0], c->wait_ms[1], c->wait_ms[2], c->wait_ms[3]};
-    const int pal8_lag = format_builds_palette(fmt) ? std::max(0, (int)c->slots.size() - 2) : 0;
+    const int pal8_lag = format_traits(fmt)->slot_raster() == kRasterPal8 ? std::max(0, (int)c->slots.size() - 2) : 0;
     // plan, free the slot, submit, prepare ahead, pump
     for (int j = 0; j < n && rc == POPPY_OK; ++j) {
         const auto t_plan = clk::now();

@@ -197,7 +197,7 @@ std::string numbered_name(const poppy_sink* s) {
 bool png_frame(poppy_sink* s, const uint8_t* frame) {
     using namespace poppy_hip::png;
     const size_t total = poppy_png_frame_bytes(frame);
-    if (total < kPngFrameMinBytes || total > std::max(poppy_frame_bytes(POPPY_FRAME_PNG, s->w, s->h), poppy_frame_bytes(POPPY_FRAME_PNG_RUNS, s->w, s->h)) || memcmp(frame + kOffSignature, kSignature, 8) != 0) return false;
+    if (total < kFrameMinBytes || total > std::max(poppy_frame_bytes(POPPY_FRAME_PNG, s->w, s->h), poppy_frame_bytes(POPPY_FRAME_PNG_RUNS, s->w, s->h)) || memcmp(frame + kOffSignature, kSignature, 8) != 0) return false;
     const uint8_t* ihdr = frame + kOffIhdr;
     const uint32_t w = (uint32_t)ihdr[8] << 24 | (uint32_t)ihdr[9] << 16 | (uint32_t)ihdr[10] << 8 | ihdr[11], h = (uint32_t)ihdr[12] << 24 | (uint32_t)ihdr[13] << 16 | (uint32_t)ihdr[14] << 8 | ihdr[15];
     if (memcmp(ihdr + 4, "IHDR", 4) != 0 || w != (uint32_t)s->w || h != (uint32_t)s->h) return false;
@@ -232,15 +232,8 @@ bool avi_close(poppy_sink* s) {
 extern "C" {
 
 size_t poppy_frame_bytes(int format, int width, int height) {
-    if (width <= 0 || height <= 0) return 0;
-    const size_t w = (size_t)width, h = (size_t)height;
-    if (format == POPPY_FRAME_BGR) return w * h * 3;
-    if (format == POPPY_FRAME_I420) return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2);
-    if (format == POPPY_FRAME_PAL8 || format == POPPY_FRAME_PAL8_SEQ) return w * h + 768;
-    if (format == POPPY_FRAME_GIF || format == POPPY_FRAME_GIF_SEQ) return gif_frame_capacity(w, h);      // (frame_limits.h, beside the smallest coded frame)
-    if (format_is_jpeg(format)) return jpeg_frame_capacity(w, h, format_sampling(format));
-    if (format_is_png(format)) return png_fits(format, width, height) ? png_frame_capacity(format, w, h) : 0;      // (nothing to size where the format refuses)
-    return 0;
+    const FormatTraits* t = format_traits(format);                 // (frame_limits.h: the format's record)
+    return t && width > 0 && height > 0 ? frame_bytes(*t, width, height) : 0;
 }
 
 // Y: the C444 branch of poppy_sink_write.  U, V of each 2 x 2 block (n = 1, 2 or 4 pixels at the right and bottom edges, k = log2 n) from

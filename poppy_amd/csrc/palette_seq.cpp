@@ -149,7 +149,7 @@ static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* use
         HIPCHK(c, ring.stream(c, k, &s));
         HIPCHK(c, hipStreamSynchronize(s));                        // the frame is coded, its length is in the pinned word
         const size_t total = *total_word(k);
-        if (!coded_length_ok(total, capacity)) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+        if (!coded_length_ok(total, capacity, kGifFrameMinBytes)) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
         HIPCHK(c, hipMemcpyAsync(ring.buffer(k), d_frame(k), total, hipMemcpyDeviceToHost, s));
         ++ring.issued;
         return POPPY_OK;
@@ -183,7 +183,7 @@ static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
         if (c->timing == 1) tm.mark("pal8_seq_build");
     }
     HIPCHK(c, hipGetLastError());
-    if (!format_is_coded(c->frame_format)) return seq_hand_over_indices(c, write, user);
+    if (!format_traits(c->frame_format)->coded()) return seq_hand_over_indices(c, write, user);
     HIPCHK(c, hipStreamSynchronize(c->stream));                   // the ring's streams read the tables
     return seq_hand_over_coded(c, write, user);
 }
@@ -225,7 +225,7 @@ int poppy_hip_bgr_frames_to_gif_frames(poppy_hip_ctx* c, const uint8_t* bgr, siz
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess && !coded_length_ok(total, capacity)) rc = fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+        if (e == hipSuccess && !coded_length_ok(total, capacity, kGifFrameMinBytes)) rc = fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
         else if (e == hipSuccess) e = hipMemcpy(dst + (size_t)k * capacity, frame, total, hipMemcpyDeviceToHost);
     }
     if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);   // nothing of the call is in flight when its buffers go (`held`, at the return)

@@ -4,6 +4,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <map>
 
 extern "C" {
@@ -301,44 +302,34 @@ int poppy_hip_pool_warp_counts(poppy_hip_pool* p, unsigned long long* fused, uns
     return POPPY_OK;
 }
 
-int poppy_hip_pool_set_frame_format(poppy_hip_pool* p, int format) {
-    if (!p || !format_known(format)) return POPPY_E_ARG;
+// the body of the pool's four writer setters: refused while work is outstanding (the feeders' contexts may be rendering), then `set` on every context
+static int pool_set(poppy_hip_pool* p, const std::function<int(poppy_hip_ctx*)>& set) {
     {
         std::lock_guard<std::mutex> lk(p->q_mu);
-        if (p->unwaited || p->outstanding) return POPPY_E_STATE;                 // the feeders' contexts may be rendering
+        if (p->unwaited || p->outstanding) return POPPY_E_STATE;
     }
-    for (poppy_hip_ctx* c : p->ctx) { const int rc = poppy_hip_set_frame_format(c, format); if (rc) return rc; }
+    for (poppy_hip_ctx* c : p->ctx) { const int rc = set(c); if (rc) return rc; }
     return POPPY_OK;
+}
+
+int poppy_hip_pool_set_frame_format(poppy_hip_pool* p, int format) {
+    if (!p || !format_traits(format)) return POPPY_E_ARG;
+    return pool_set(p, [=](poppy_hip_ctx* c) { return poppy_hip_set_frame_format(c, format); });
 }
 
 int poppy_hip_pool_set_jpeg_quality(poppy_hip_pool* p, int quality) {
     if (!p || quality < 1 || quality > 100) return POPPY_E_ARG;
-    {
-        std::lock_guard<std::mutex> lk(p->q_mu);
-        if (p->unwaited || p->outstanding) return POPPY_E_STATE;                 // the feeders' contexts may be rendering
-    }
-    for (poppy_hip_ctx* c : p->ctx) { const int rc = poppy_hip_set_jpeg_quality(c, quality); if (rc) return rc; }
-    return POPPY_OK;
+    return pool_set(p, [=](poppy_hip_ctx* c) { return poppy_hip_set_jpeg_quality(c, quality); });
 }
 
 int poppy_hip_pool_set_frame_scale(poppy_hip_pool* p, int factor) {
     if (!p || factor < 1 || factor > POPPY_FRAME_SCALE_MAX) return POPPY_E_ARG;
-    {
-        std::lock_guard<std::mutex> lk(p->q_mu);
-        if (p->unwaited || p->outstanding) return POPPY_E_STATE;                 // the feeders' contexts may be rendering
-    }
-    for (poppy_hip_ctx* c : p->ctx) { const int rc = poppy_hip_set_frame_scale(c, factor); if (rc) return rc; }
-    return POPPY_OK;
+    return pool_set(p, [=](poppy_hip_ctx* c) { return poppy_hip_set_frame_scale(c, factor); });
 }
 
 int poppy_hip_pool_set_frame_size(poppy_hip_pool* p, int ow, int oh) {
     if (!p || ow < 0 || oh < 0 || (ow == 0) != (oh == 0)) return POPPY_E_ARG;
-    {
-        std::lock_guard<std::mutex> lk(p->q_mu);
-        if (p->unwaited || p->outstanding) return POPPY_E_STATE;                 // the feeders' contexts may be rendering
-    }
-    for (poppy_hip_ctx* c : p->ctx) { const int rc = poppy_hip_set_frame_size(c, ow, oh); if (rc) return rc; }
-    return POPPY_OK;
+    return pool_set(p, [=](poppy_hip_ctx* c) { return poppy_hip_set_frame_size(c, ow, oh); });
 }
 
 int poppy_hip_pool_mask_rider(poppy_hip_pool* p) {

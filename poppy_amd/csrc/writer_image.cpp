@@ -9,80 +9,38 @@ int scale_into_scratch(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, con
     return POPPY_OK;
 }
 
-// a PAL8 frame in device memory -> its POPPY_FRAME_GIF frame in `host` (exactly `total` bytes), on the context's stream and waited for: the frames that no slot renders,
-// and poppy_hip_pal8_to_gif_frame.  The buffers live for the call.
-static int gif_from_device_pal8(poppy_hip_ctx* c, const uint8_t* d_pal8, int W, int H, std::vector<uint8_t>& host) {
-    const size_t cap = poppy_frame_bytes(POPPY_FRAME_GIF, W, H);
+// what the coder of format `t` reads, in device memory (its raster form; PNG: the tight BGR frame) -> the coded frame in `host` (exactly `total` bytes), on the
+// context's stream and waited for: the frames that no slot renders, and the stand-alone coding entry points.  d_tables: the JPEG coder's.  The buffers live for
+// the call, at t's capacity; nothing of the call is in flight when they go.
+static int coded_from_device(poppy_hip_ctx* c, const FormatTraits& t, const uint8_t* d_src, const void* d_tables, int W, int H, std::vector<uint8_t>& host) {
+    const size_t cap = capacity(t, (size_t)W, (size_t)H);
     CallBuffers held;
     uint8_t *work = nullptr, *frame = nullptr;
-    hipError_t e = held.alloc(&work, gif_scratch_bytes(W, H));
+    hipError_t e = held.alloc(&work, coding_scratch_bytes(t, W, H));
     if (e == hipSuccess) e = held.alloc(&frame, cap + 16);
     uint32_t total = 0;
     if (e == hipSuccess) {
-        enqueue_gif_coding(d_pal8, work, frame, nullptr, W, H, c->stream, nullptr, nullptr);
+        enqueue_coding(t, d_src, d_tables, work, frame, nullptr, W, H, c->stream, nullptr, nullptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && !coded_length_ok(total, cap)) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
-    if (e == hipSuccess) { host.resize(total); e = hipMemcpy(host.data(), frame, total, hipMemcpyDeviceToHost); }
-    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); c->err = std::string("GIF frame coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
-    return POPPY_OK;
-}
-
-// an I420 frame in device memory -> its POPPY_FRAME_JPEG frame in `host` (exactly `total` bytes) at the quality that `d_tables` name, on the context's stream and
-// waited for: the frames that no slot renders, and poppy_hip_i420_to_jpeg_frame.  The buffers live for the call.  sm == k444: an I444 frame -> its
-// POPPY_FRAME_JPEG444 frame (poppy_hip_i444_to_jpeg_frame).
-static int jpeg_from_device_planes(poppy_hip_ctx* c, const uint8_t* d_i420, const void* d_tables, int W, int H, jpeg::Sampling sm, std::vector<uint8_t>& host) {
-    const size_t cap = jpeg_frame_capacity((size_t)W, (size_t)H, sm);
-    CallBuffers held;
-    uint8_t *work = nullptr, *frame = nullptr;
-    hipError_t e = held.alloc(&work, jpeg_scratch_bytes(W, H, sm));
-    if (e == hipSuccess) e = held.alloc(&frame, cap + 16);
-    uint32_t total = 0;
-    if (e == hipSuccess) {
-        enqueue_jpeg_coding(d_i420, d_tables, work, frame, nullptr, W, H, sm, c->stream, nullptr, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = e_sync;
-    if (e == hipSuccess && !coded_length_ok(total, cap, kJpegFrameMinBytes)) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+    if (e == hipSuccess && !coded_length_ok(total, cap, t.least)) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
     if (e == hipSuccess) { host.resize(total); e = hipMemcpy(host.data(), frame, total, hipMemcpyDeviceToHost); }
-    if (e != hipSuccess) { c->err = std::string("JPEG frame coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
-    return POPPY_OK;
-}
-
-// a tight BGR frame in device memory -> its POPPY_FRAME_PNG or POPPY_FRAME_PNG_RUNS frame (fmt) in `host` (exactly `total` bytes), on the context's stream and waited
-// for: the frames that no slot renders, and poppy_hip_bgr_to_png_frame, poppy_hip_bgr_to_png_runs_frame.  The buffers live for the call, at fmt's capacity.
-static int png_from_device_bgr(poppy_hip_ctx* c, int fmt, const uint8_t* d_bgr, int W, int H, std::vector<uint8_t>& host) {
-    const size_t cap = png_frame_capacity(fmt, (size_t)W, (size_t)H);
-    CallBuffers held;
-    uint8_t *work = nullptr, *frame = nullptr;
-    hipError_t e = held.alloc(&work, png_scratch_bytes(W, H, fmt == POPPY_FRAME_PNG_RUNS));
-    if (e == hipSuccess) e = held.alloc(&frame, cap + 16);
-    uint32_t total = 0;
-    if (e == hipSuccess) {
-        enqueue_png_coding(fmt, d_bgr, work, frame, nullptr, W, H, c->stream, nullptr, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go
-    if (e == hipSuccess) e = e_sync;
-    if (e == hipSuccess && !coded_length_ok(total, cap, kPngFrameMinBytes)) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
-    if (e == hipSuccess) { host.resize(total); e = hipMemcpy(host.data(), frame, total, hipMemcpyDeviceToHost); }
-    if (e != hipSuccess) { c->err = std::string("PNG frame coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    if (e != hipSuccess) { c->err = std::string(t.name) + " frame coding: " + hipGetErrorString(e); return POPPY_E_DEVICE; }
     return POPPY_OK;
 }
 
 int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const WriterGeom& g, std::vector<uint8_t>& host, size_t* stride, int n_copies) {
     const int fmt = c->frame_format;
+    const FormatTraits& t = *format_traits(fmt);
     if (const char* why = format_refuses(fmt, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
     if (g.scaled()) {                                              // scaled first, on the device; everything below is in the writer's geometry
         int rc = scale_into_scratch(c, d_bgr, W, H, g); if (rc) return rc;
         d_bgr = c->scale_scratch.p; W = g.w; H = g.h;
     }
-    if (format_is_sequence(fmt)) {                                 // the copies are the sequence: the host statement on the BGR frame
+    if (t.sequence) {                                              // the copies are the sequence: the host statement on the BGR frame
         std::vector<uint8_t> bgr((size_t)W * H * 3);
         HIPCHK(c, hipMemcpyAsync(bgr.data(), d_bgr, bgr.size(), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -92,29 +50,16 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
     }
     *stride = writer_stride(fmt, W);
     const uint8_t* d_frame = d_bgr;
-    if (fmt != POPPY_FRAME_BGR) {                                  // converted into the context's scratch: the slots' launches on other buffers
-        // (a coded format: its raster form into the scratch — PAL8 for GIF, I420 for JPEG, the I444 planes for JPEG444 —, then the coder on buffers that live for the call)
-        if (format_is_png(fmt)) return png_from_device_bgr(c, fmt, d_bgr, W, H, host);      // (no raster form: the coder reads the BGR frame)
-        if (fmt == POPPY_FRAME_JPEG444) {                          // (I444 is no format of its own: the kernel is launched here)
-            { int rc = ensure_jpeg_tables(c); if (rc) return rc; }
-            HIPCHK(c, c->fmt_scratch.reserve((size_t)W * H * 3 + 16, c->stream));
-            launch_bgr_to_i444(d_bgr, c->fmt_scratch.p, W, H, c->stream);
-            HIPCHK(c, hipGetLastError());
-            return jpeg_from_device_planes(c, c->fmt_scratch.p, c->jpeg_tables, W, H, jpeg::k444, host);
-        }
-        const bool gif = fmt == POPPY_FRAME_GIF, jpeg = fmt == POPPY_FRAME_JPEG;
-        const int raster = gif ? POPPY_FRAME_PAL8 : jpeg ? POPPY_FRAME_I420 : fmt;
-        if (format_builds_palette(fmt)) { int rc = alloc_zeroed_tables(c, &c->fmt_scratch_tables, kPal8TableBytes); if (rc) return rc; }
-        if (jpeg) { int rc = ensure_jpeg_tables(c); if (rc) return rc; }
-        HIPCHK(c, c->fmt_scratch.reserve(poppy_frame_bytes(raster, W, H) + 16, c->stream));
+    if (t.coder == kCoderJpeg) { int rc = ensure_jpeg_tables(c); if (rc) return rc; }
+    if (t.raster != kRasterNone) {                                 // the raster step into the context's scratch: the slots' launches on other buffers
+        if (t.raster == kRasterPal8) { int rc = alloc_zeroed_tables(c, &c->fmt_scratch_tables, kPal8TableBytes); if (rc) return rc; }
+        HIPCHK(c, c->fmt_scratch.reserve(raster_bytes(t.raster, W, H) + 16, c->stream));
         SlotFormat scratch;
-        scratch.i420 = scratch.pal8 = c->fmt_scratch.p; scratch.pal8_tables = c->fmt_scratch_tables;
-        enqueue_conversion(raster, WriterGeom{W, H}, d_bgr, W, H, scratch, c->stream, nullptr, nullptr);
+        scratch.i420 = scratch.i444 = scratch.pal8 = c->fmt_scratch.p; scratch.pal8_tables = c->fmt_scratch_tables;
+        d_frame = enqueue_raster(t.raster, d_bgr, W, H, scratch, c->stream, nullptr, nullptr);
         HIPCHK(c, hipGetLastError());
-        if (gif) return gif_from_device_pal8(c, c->fmt_scratch.p, W, H, host);
-        if (jpeg) return jpeg_from_device_planes(c, c->fmt_scratch.p, c->jpeg_tables, W, H, jpeg::k420, host);
-        d_frame = c->fmt_scratch.p;
     }
+    if (t.coded()) return coded_from_device(c, t, d_frame, c->jpeg_tables, W, H, host);      // the coder step, on buffers that live for the call
     host.resize(poppy_frame_bytes(fmt, W, H));
     HIPCHK(c, hipMemcpyAsync(host.data(), d_frame, host.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -123,19 +68,19 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
 
 const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status, int n_copies) {
     const int fmt = c->frame_format;
+    const FormatTraits& t = *format_traits(fmt);
     *out_stride = stride;
     *status = POPPY_OK;
-    if (fmt == POPPY_FRAME_BGR) return bgr;
+    if (t.raster == kRasterNone && !t.coded()) return bgr;
     if (const char* why = format_refuses(fmt, W, H)) { *status = fail(c, POPPY_E_UNSUPPORTED, why); return nullptr; }
     tmp.resize(poppy_frame_bytes(fmt, W, H));
-    std::vector<uint8_t> pal8(format_is_sequence(fmt) && format_is_coded(fmt) ? poppy_frame_bytes(POPPY_FRAME_PAL8_SEQ, W, H) : 0);      // (GIF_SEQ: PAL8_SEQ's frame, then the host coder)
-    int rc = format_is_sequence(fmt) ? pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, pal8.empty() ? tmp.data() : pal8.data()) :
-                   fmt == POPPY_FRAME_GIF ? poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data()) :
-                   fmt == POPPY_FRAME_JPEG ? poppy_bgr_to_jpeg_frame(bgr, stride, W, H, c->jpeg_quality, tmp.data()) :
-                   fmt == POPPY_FRAME_JPEG444 ? poppy_bgr_to_jpeg444_frame(bgr, stride, W, H, c->jpeg_quality, tmp.data()) :
-                   fmt == POPPY_FRAME_PNG ? poppy_bgr_to_png_frame(bgr, stride, W, H, tmp.data()) :
-                   fmt == POPPY_FRAME_PNG_RUNS ? poppy_bgr_to_png_runs_frame(bgr, stride, W, H, tmp.data()) :
-                   fmt == POPPY_FRAME_PAL8 ? poppy_bgr_to_pal8(bgr, stride, W, H, tmp.data()) : poppy_bgr_to_i420(bgr, stride, W, H, tmp.data());
+    std::vector<uint8_t> pal8(t.sequence && t.coded() ? raster_bytes(kRasterPal8, W, H) : 0);      // (GIF_SEQ: PAL8_SEQ's frame, then the host coder)
+    int rc = POPPY_OK;                                             // the host statement of the record's steps
+    if (t.sequence) rc = pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, pal8.empty() ? tmp.data() : pal8.data());
+    else if (t.coder == kCoderGif) rc = poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data());
+    else if (t.coder == kCoderJpeg) rc = (t.sampling() == jpeg::k444 ? poppy_bgr_to_jpeg444_frame : poppy_bgr_to_jpeg_frame)(bgr, stride, W, H, c->jpeg_quality, tmp.data());
+    else if (t.coder == kCoderPng) rc = (t.runs() ? poppy_bgr_to_png_runs_frame : poppy_bgr_to_png_frame)(bgr, stride, W, H, tmp.data());
+    else rc = (t.raster == kRasterPal8 ? poppy_bgr_to_pal8 : poppy_bgr_to_i420)(bgr, stride, W, H, tmp.data());
     if (rc == POPPY_OK && !pal8.empty()) rc = poppy_pal8_to_gif_frame(pal8.data(), W, H, tmp.data());
     if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
     *out_stride = writer_stride(fmt, W);
@@ -174,17 +119,25 @@ int poppy_hip_bgr_resize_area_form(int W, int H, int ow, int oh) {
     return bgr_resize_area_form(W, H, ow, oh);
 }
 
-// the body of the two stand-alone scaling entries: a host frame W x H up, scaled to g on the device, down again, on buffers that live for the call.  The source's
-// place behind a 256-byte boundary is the row pad's low bits (include/poppy_hip.h).
+// a host BGR frame up on the context's stream, tight, into a buffer that lives for the call (`held`).  Its place behind a 256-byte boundary is the row pad's low
+// bits (include/poppy_hip.h): *d_src is that many bytes into the allocation.
+static hipError_t upload_host_bgr(poppy_hip_ctx* c, CallBuffers& held, const uint8_t* bgr, size_t stride, int W, int H, uint8_t** d_src) {
+    const size_t row = (size_t)W * 3, shift = (stride - row) % 16;
+    hipError_t e = held.alloc(d_src, row * H + shift + 16);
+    if (e != hipSuccess) return e;
+    *d_src += shift;
+    return copy_rows_async(*d_src, row, bgr, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream);
+}
+
+// the body of the two stand-alone scaling entries: a host frame W x H up, scaled to g on the device, down again, on buffers that live for the call
 static int scale_host_frame(poppy_hip_ctx* c, const char* what, const uint8_t* bgr, size_t stride, int W, int H, const WriterGeom& g, uint8_t* dst, size_t dst_stride) {
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t row = (size_t)W * 3, shift = (stride - row) % 16, out_row = (size_t)g.w * 3;
+    const size_t out_row = (size_t)g.w * 3;
     CallBuffers held;
     uint8_t *d_src = nullptr, *d_dst = nullptr;
-    hipError_t e = held.alloc(&d_src, row * H + shift + 16);
-    if (e == hipSuccess) e = held.alloc(&d_dst, out_row * g.h + 16);
-    if (e == hipSuccess) e = copy_rows_async(d_src + shift, row, bgr, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) { launch_writer_scaling(g, d_src + shift, d_dst, W, H, c->stream); e = hipGetLastError(); }
+    hipError_t e = held.alloc(&d_dst, out_row * g.h + 16);
+    if (e == hipSuccess) e = upload_host_bgr(c, held, bgr, stride, W, H, &d_src);
+    if (e == hipSuccess) { launch_writer_scaling(g, d_src, d_dst, W, H, c->stream); e = hipGetLastError(); }
     if (e == hipSuccess) e = copy_rows_async(dst, dst_stride, d_dst, out_row, out_row, (size_t)g.h, hipMemcpyDeviceToHost, c->stream);
     const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go (`held`, at the return)
     if (e == hipSuccess) e = e_sync;
@@ -212,12 +165,12 @@ int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* c, const uint8_t* pal8, int W, in
     if (const char* why = format_refuses(POPPY_FRAME_GIF, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = poppy_frame_bytes(POPPY_FRAME_PAL8, W, H);
-    CallBuffers held;                                              // (gif_from_device_pal8 waits for the stream before it returns)
+    CallBuffers held;                                              // (coded_from_device waits for the stream before it returns)
     uint8_t* d_pal8 = nullptr;
     HIPCHK(c, held.alloc(&d_pal8, bytes + 16));
     if (hipMemcpy(d_pal8, pal8, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(c, POPPY_E_DEVICE, "upload of the PAL8 frame failed");
     std::vector<uint8_t> host;
-    const int rc = gif_from_device_pal8(c, d_pal8, W, H, host);
+    const int rc = coded_from_device(c, *format_traits(POPPY_FRAME_GIF), d_pal8, nullptr, W, H, host);
     if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
     return rc;
 }
@@ -228,17 +181,18 @@ static int jpeg_code_host_planes(poppy_hip_ctx* c, int fmt, const uint8_t* i420,
     if (!i420 || !dst || W <= 0 || H <= 0 || quality < 1 || quality > 100) return fail(c, POPPY_E_ARG, "bad arguments");
     if (const char* why = format_refuses(fmt, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bytes = fmt == POPPY_FRAME_JPEG444 ? (size_t)W * H * 3 : poppy_frame_bytes(POPPY_FRAME_I420, W, H);
+    const FormatTraits& traits = *format_traits(fmt);
+    const size_t bytes = raster_bytes(traits.raster, W, H);
     jpeg::QualityTables t;
     jpeg::fill_quality_tables(quality, &t);
-    CallBuffers held;                                              // (jpeg_from_device_planes waits for the stream before it returns)
+    CallBuffers held;                                              // (coded_from_device waits for the stream before it returns)
     uint8_t *d_i420 = nullptr, *d_tables = nullptr;
     HIPCHK(c, held.alloc(&d_i420, bytes + 16));
     HIPCHK(c, held.alloc(&d_tables, kJpegTableBytes));
     if (hipMemcpy(d_i420, i420, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_tables, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess)
         return fail(c, POPPY_E_DEVICE, "upload of the planes failed");
     std::vector<uint8_t> host;
-    const int rc = jpeg_from_device_planes(c, d_i420, d_tables, W, H, format_sampling(fmt), host);
+    const int rc = coded_from_device(c, traits, d_i420, d_tables, W, H, host);
     if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
     return rc;
 }
@@ -251,23 +205,20 @@ int poppy_hip_i444_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i444, int W, i
     return jpeg_code_host_planes(c, POPPY_FRAME_JPEG444, i444, W, H, quality, dst);
 }
 
-// a host frame up, the six PNG kernels, `total` bytes down, on buffers that live for the call; the source's place behind a 256-byte boundary is the row pad's low
-// bits (include/poppy_hip.h), as in scale_host_frame
+// a host frame up (upload_host_bgr), the six PNG kernels, `total` bytes down, on buffers that live for the call
 static int png_code_host_frame(poppy_hip_ctx* c, int fmt, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* dst) {
     if (!c) return POPPY_E_ARG;
     if (!bgr || !dst || W <= 0 || H <= 0 || stride < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad arguments");
     if (const char* why = format_refuses(fmt, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t row = (size_t)W * 3, shift = (stride - row) % 16;
-    CallBuffers held;                                              // (png_from_device_bgr waits for the stream before it returns)
+    CallBuffers held;                                              // (coded_from_device waits for the stream before it returns)
     uint8_t* d_src = nullptr;
-    HIPCHK(c, held.alloc(&d_src, row * H + shift + 16));
-    if (copy_rows_async(d_src + shift, row, bgr, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+    if (upload_host_bgr(c, held, bgr, stride, W, H, &d_src) != hipSuccess) {
         (void)hipStreamSynchronize(c->stream);
         return fail(c, POPPY_E_DEVICE, "upload of the BGR frame failed");
     }
     std::vector<uint8_t> host;
-    const int rc = png_from_device_bgr(c, fmt, d_src + shift, W, H, host);
+    const int rc = coded_from_device(c, *format_traits(fmt), d_src, nullptr, W, H, host);
     if (rc == POPPY_OK) memcpy(dst, host.data(), host.size());
     return rc;
 }
@@ -278,19 +229,17 @@ int poppy_hip_bgr_to_png_runs_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t
     return png_code_host_frame(c, POPPY_FRAME_PNG_RUNS, bgr, stride, W, H, dst);
 }
 
-// a host frame up, the I444 kernel, the planes down, on buffers that live for the call; the source's place behind a 256-byte boundary is the row pad's low bits
-// (include/poppy_hip.h), as in scale_host_frame
+// a host frame up (upload_host_bgr), the I444 kernel, the planes down, on buffers that live for the call
 int poppy_hip_bgr_to_i444(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* dst) {
     if (!c) return POPPY_E_ARG;
     if (!bgr || !dst || W <= 0 || H <= 0 || stride < (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t row = (size_t)W * 3, shift = (stride - row) % 16, bytes = row * H;
+    const size_t bytes = raster_bytes(kRasterI444, W, H);
     CallBuffers held;
     uint8_t *d_src = nullptr, *d_dst = nullptr;
-    hipError_t e = held.alloc(&d_src, bytes + shift + 16);
-    if (e == hipSuccess) e = held.alloc(&d_dst, bytes + 16);
-    if (e == hipSuccess) e = copy_rows_async(d_src + shift, row, bgr, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) { launch_bgr_to_i444(d_src + shift, d_dst, W, H, c->stream); e = hipGetLastError(); }
+    hipError_t e = held.alloc(&d_dst, bytes + 16);
+    if (e == hipSuccess) e = upload_host_bgr(c, held, bgr, stride, W, H, &d_src);
+    if (e == hipSuccess) { launch_bgr_to_i444(d_src, d_dst, W, H, c->stream); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemcpyAsync(dst, d_dst, bytes, hipMemcpyDeviceToHost, c->stream);
     const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go (`held`, at the return)
     if (e == hipSuccess) e = e_sync;

@@ -1,6 +1,7 @@
 // jpeg_host_check.cpp — the host statement of POPPY_FRAME_JPEG (poppy_amd/csrc/frame_jpeg.cpp) alone, on the host, under a sanitizer:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tools/jpeg_host_check.cpp poppy_amd/csrc/frame_jpeg.cpp \
-//       poppy_amd/csrc/frame_sink.cpp poppy_amd/csrc/frame_gif.cpp poppy_amd/csrc/frame_pal8.cpp -o /tmp/jpeg_asan && /tmp/jpeg_asan
+//       poppy_amd/csrc/frame_sink.cpp poppy_amd/csrc/frame_gif.cpp poppy_amd/csrc/frame_pal8.cpp poppy_amd/csrc/frame_i444.cpp poppy_amd/csrc/frame_png.cpp \
+//       -o /tmp/jpeg_asan && /tmp/jpeg_asan
 // Every frame is coded into a heap buffer of EXACTLY poppy_frame_bytes(POPPY_FRAME_JPEG, w, h) bytes from an I420 frame of exactly its own size, so a byte
 // written behind the capacity or read behind a plane is the sanitizer's to report.  The content is what stresses the capacity: noise at quality 100, saturated
 // checkerboards, flat frames and the black / white MCU alternation, at sizes around one MCU and one restart interval.  Returns 0 when every `total` is inside
