@@ -310,6 +310,46 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * poppy_hip_set_jpeg_quality and poppy_hip_pool_set_jpeg_quality serve both formats.  The format applies wherever JPEG applies, under poppy_hip_set_frame_scale
  * and poppy_hip_set_frame_size as the host statement at the writer's geometry, and stays BGR wherever JPEG stays BGR.
  *
+ * POPPY_FRAME_JPEG_OPT (4096) and POPPY_FRAME_JPEG444_OPT (8192): POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 on Huffman tables built from the frame's own symbols
+ * instead of the Annex K examples: the same planes, quality, quantisation, sampling, restart intervals and coefficients, so a file decodes to exactly the pixels of
+ * the JPEG / JPEG444 file of the same frame, in fewer bytes (about 0.8 to 0.95 of them; DESIGN.md section 4, "JPEG optimised-table hand-off").  4095, 4097, 8191
+ * and 8193 stay unknown; there is no sink value: POPPY_SINK_MJPEG takes the frames.  Layout and writer call are JPEG's, poppy_jpeg_frame_bytes reads `total`.  The
+ * rule is the other format's word for word except for the tables, the DHT segment that names them and what follows from their sizes:
+ *   Counts.  Four tables: DC 0, AC 0 (Y), DC 1, AC 1 (Cb and Cr).  count[s] is how often the POPPY_FRAME_JPEG coder emits symbol s from that table for this frame:
+ *      a DC category 0..11, an AC run / size byte, F0 once per ZRL, 00 once per EOB.  Every table of every frame has at least one symbol (every block has a DC
+ *      symbol, and every frame has blocks of both tables' components; a block without an AC symbol ends in coefficient 63, which is an AC symbol).
+ *   Table rule.  poppy_jpeg_optimal_table(counts[256], bits[16], vals[256], &n) is T.81 Annex K.2 as libjpeg's jpeg_gen_optimal_table words it, with every tie
+ *      decided; host only, integers only (sums in 64 bits):
+ *      1. freq[0..255] = counts, freq[256] = 1: the reserved entry, which keeps any real code from being all ones.  Every entry is its own tree.
+ *      2. Repeat: c1 is the index of the smallest non-zero freq, the LARGEST index among equals; c2 the same among the other entries; stop when there is no c2.
+ *         freq[c1] += freq[c2], freq[c2] = 0; every symbol in c1's tree and in c2's tree gets one bit longer; c2's tree joins c1's.
+ *      3. Count the symbols of each length, the reserved entry among them.  A length may reach 256 (257 leaves); the array holds that.
+ *      4. Annex K.3, for i from the longest length down to 17: while bits[i] > 0, set j = i - 2 and step j down until bits[j] > 0; then bits[i] -= 2,
+ *         bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1.
+ *      5. Take one away from the longest non-empty length <= 16: the reserved entry's code.
+ *      6. vals is the symbols that have a count, ordered by their length BEFORE step 4, then by symbol value; n is their number.
+ *      Codes are canonical: in the order of vals, the first code of length 1 is 0, a code is its predecessor plus 1, shifted left by the difference in length.
+ *      POPPY_E_ARG for a null pointer, for counts that are all zero, and for a sum of 2^32 - 1 or more (with the reserved entry the root's count would not fit
+ *      32 bits).  poppy_hip_jpeg_optimal_table runs the device's table build alone on one table's counts and gives the same bits, vals and n.
+ *   Count bound.  A frame the format accepts has a capacity below 2^32 bytes, so fewer than 2^32 / POPPY_JPEG_OPT_SEGMENT_BYTES < 215500 segments of 48 blocks,
+ *      fewer than 10.4 million blocks, each with one DC symbol and at most 63 AC symbols: a table's sum stays below 6.6 * 10^8 < 2^30, far below the limit, and
+ *      the device adds and merges in 32 bits.
+ *   Header.  POPPY_FRAME_JPEG's (JPEG444's) header byte for byte up to the DHT marker at file offset 173; then ONE DHT segment, FF C4, its length
+ *      2 + sum(17 + n), and per table in the order DC 0, AC 0, DC 1, AC 1 the class / id byte (00, 10, 01, 11), bits[16] and the n values; then DRI and SOS as
+ *      before.  The header is 197 + sum(17 + n) bytes — at most 613, since a DC table has at most 12 symbols and an AC table at most 162 — and the
+ *      entropy-coded data begins right behind it, at frame offset 4 + that: no longer a constant.
+ *   Capacity.  A code has at most 16 bits after step 4, and a DC tree has at most 13 leaves (12 categories and the reserved entry), so a DC code has at most 12
+ *      bits where table K.4 stops at 11.  A block is at most 12 + 11 + 63 * (16 + 10) = 1661 bits (ZRL and EOB cost no more than under JPEG: a ZRL is one code of
+ *      at most 16 bits for 16 coefficients), a segment at most ceil(48 * 1661 / 8) bytes, twice that stuffed, and 2 bytes of marker:
+ *      POPPY_JPEG_OPT_SEGMENT_BYTES = 19934.  poppy_frame_bytes = 4 + 613 + segments * POPPY_JPEG_OPT_SEGMENT_BYTES, with JPEG's (JPEG444's) number of segments.
+ *      The smallest frame is the header with four one-symbol tables, one byte of data and EOI: 4 + 197 + 4 * 18 + 1 + 2 = 276 bytes.
+ *   Limits.  JPEG's: a side above 65535 or a capacity of 2^32 bytes or more is POPPY_E_UNSUPPORTED.
+ * poppy_i420_to_jpeg_opt_frame and poppy_i444_to_jpeg_opt_frame are the host statements (two passes over the same coefficients: count, build, code; arguments and
+ * refusals as poppy_i420_to_jpeg_frame's, dst: the capacity), poppy_bgr_to_jpeg_opt_frame and poppy_bgr_to_jpeg444_opt_frame the conversion followed by them.
+ * poppy_hip_i420_to_jpeg_opt_frame and poppy_hip_i444_to_jpeg_opt_frame code host planes on the context's GPU (upload, four kernels — count, table build, code,
+ * gather —, download of `total` bytes): the same bytes.  poppy_hip_set_jpeg_quality serves these formats too, and they apply wherever JPEG applies, under
+ * poppy_hip_set_frame_scale and poppy_hip_set_frame_size as the host statement at the writer's geometry, and stay BGR wherever JPEG stays BGR.
+ *
  * POPPY_FRAME_PNG: the frame coded on the GPU as one PNG file, LOSSLESS: the file decodes to exactly the frame's pixels, at 1.5 - 3 times fewer bytes than BGR on
  * photograph-like frames.  Its value is 1024, and POPPY_SINK_PNG is 1024; 1023 and 1025 stay unknown in both enums.  Layout, little-endian:
  *     bytes 0..3     total: the whole frame's length in bytes, these four included (poppy_png_frame_bytes reads it)
@@ -380,6 +420,7 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
 #define POPPY_JPEG_RESTART_MCUS 8
 #endif
 #define POPPY_JPEG_SEGMENT_BYTES (2 * ((6 * 1660 * POPPY_JPEG_RESTART_MCUS + 7) / 8) + 2)
+#define POPPY_JPEG_OPT_SEGMENT_BYTES (2 * ((6 * 1661 * POPPY_JPEG_RESTART_MCUS + 7) / 8) + 2)
 #define POPPY_JPEG444_RESTART_MCUS 16      /* (3 * 16 blocks = 6 * POPPY_JPEG_RESTART_MCUS: poppy_amd/csrc/jpeg_tables.h asserts it) */
 #define POPPY_JPEG_QUALITY_DEFAULT 90
 #define POPPY_PNG_SEGMENT_BYTES 8192
@@ -387,7 +428,8 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
 #define POPPY_PNG_HEADER_BYTES 236      /* (any header of the form fits: 17 + 19 * 3 + 258 * 7 bits) */
 #define POPPY_PNG_RUN_MIN 8
 enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128, POPPY_FRAME_JPEG = 256,
-       POPPY_FRAME_JPEG444 = 512, POPPY_FRAME_PNG = 1024, POPPY_FRAME_PNG_RUNS = 2048 };
+       POPPY_FRAME_JPEG444 = 512, POPPY_FRAME_PNG = 1024, POPPY_FRAME_PNG_RUNS = 2048, POPPY_FRAME_JPEG_OPT = 4096,
+       POPPY_FRAME_JPEG444_OPT = 8192 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
@@ -409,6 +451,14 @@ int poppy_hip_bgr_to_i444(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride,
 int poppy_i444_to_jpeg_frame(const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
 int poppy_bgr_to_jpeg444_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst);
 int poppy_hip_i444_to_jpeg_frame(poppy_hip_ctx* ctx, const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
+int poppy_jpeg_optimal_table(const uint32_t counts[256], uint8_t bits[16], uint8_t vals[256], int* n_vals);
+int poppy_i420_to_jpeg_opt_frame(const uint8_t* i420, int width, int height, int quality, uint8_t* dst);
+int poppy_i444_to_jpeg_opt_frame(const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
+int poppy_bgr_to_jpeg_opt_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst);
+int poppy_bgr_to_jpeg444_opt_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst);
+int poppy_hip_i420_to_jpeg_opt_frame(poppy_hip_ctx* ctx, const uint8_t* i420, int width, int height, int quality, uint8_t* dst);
+int poppy_hip_i444_to_jpeg_opt_frame(poppy_hip_ctx* ctx, const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
+int poppy_hip_jpeg_optimal_table(poppy_hip_ctx* ctx, const uint32_t counts[256], uint8_t bits[16], uint8_t vals[256], int* n_vals);
 size_t poppy_png_frame_bytes(const uint8_t* frame);
 int poppy_png_table(int k, uint8_t lengths[257], uint8_t* header_bits, int* n_header_bits);
 int poppy_bgr_to_png_frame(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
@@ -922,7 +972,9 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * lengths, the frame counts and the largest chunk's size are patched in at close; no frame at all gives a valid file of no frames.  A frame that would take the
  * file past 4 GiB fails the sink (a plain AVI has 32-bit lengths).  A frame of any other format fails this sink, and a JPEG frame fails every other sink.
  * POPPY_FRAME_JPEG444 frames are taken as well, in any mix with POPPY_FRAME_JPEG frames (the `MJPG` stream does not care): a frame whose SOF0 gives component 1
- * the sampling byte 0x11 is held to POPPY_FRAME_JPEG444's capacity, any other to POPPY_FRAME_JPEG's; nothing else about the sink differs.
+ * the sampling byte 0x11 is held to POPPY_FRAME_JPEG444's capacity, any other to POPPY_FRAME_JPEG's; nothing else about the sink differs.  POPPY_FRAME_JPEG_OPT
+ * and POPPY_FRAME_JPEG444_OPT frames are taken in the same mix: a frame whose DHT segment is not byte for byte the Annex K one is held to the OPT capacity of its
+ * sampling, every other frame as before.
  * PNG: one PNG file per frame from POPPY_FRAME_PNG and POPPY_FRAME_PNG_RUNS frames as they come, in any mix (a PNG file does not say who coded it); `path` follows
  * PPM's %d rule exactly.  The file holds the frame's bytes 4 .. total as they are.  The stride must be 0, bytes 4..11 the PNG signature, IHDR must name the sink's
  * width and height, and `total` must be inside the larger of the two formats' capacities.  A frame

@@ -27,7 +27,8 @@ WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int,
 # formats of the frames handed to writers (poppy_hip_set_frame_format) and the file sinks (poppy_sink_open)
 FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444 = 0, 1, 8, 16, 64, 128, 256, 512
 FRAME_PNG, FRAME_PNG_RUNS = 1024, 2048
-FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444, FRAME_PNG, FRAME_PNG_RUNS)      # a frame whose length its first four bytes hold
+FRAME_JPEG_OPT, FRAME_JPEG444_OPT = 4096, 8192
+FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444, FRAME_PNG, FRAME_PNG_RUNS, FRAME_JPEG_OPT, FRAME_JPEG444_OPT)      # a frame whose length its first four bytes hold
 JPEG_QUALITY_DEFAULT = 90
 SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED, SINK_GIF_GLOBAL_CODED, SINK_MJPEG = 0, 1, 2, 3, 8, 16, 64, 128, 256
 SINK_PNG = 1024
@@ -55,6 +56,8 @@ SYMBOLS = [
     "poppy_bgr_frames_to_gif_frames", "poppy_hip_bgr_frames_to_gif_frames",
     "poppy_jpeg_frame_bytes", "poppy_i420_to_jpeg_frame", "poppy_bgr_to_jpeg_frame", "poppy_hip_i420_to_jpeg_frame", "poppy_hip_set_jpeg_quality", "poppy_hip_pool_set_jpeg_quality",
     "poppy_bgr_to_i444", "poppy_hip_bgr_to_i444", "poppy_i444_to_jpeg_frame", "poppy_bgr_to_jpeg444_frame", "poppy_hip_i444_to_jpeg_frame",
+    "poppy_jpeg_optimal_table", "poppy_i420_to_jpeg_opt_frame", "poppy_i444_to_jpeg_opt_frame", "poppy_bgr_to_jpeg_opt_frame", "poppy_bgr_to_jpeg444_opt_frame",
+    "poppy_hip_i420_to_jpeg_opt_frame", "poppy_hip_i444_to_jpeg_opt_frame", "poppy_hip_jpeg_optimal_table",
     "poppy_png_frame_bytes", "poppy_png_table", "poppy_bgr_to_png_frame", "poppy_hip_bgr_to_png_frame",
     "poppy_png_runs_table", "poppy_bgr_to_png_runs_frame", "poppy_hip_bgr_to_png_runs_frame",
     "poppy_hip_set_frame_scale", "poppy_hip_pool_set_frame_scale", "poppy_frame_scaled_size", "poppy_bgr_downscale", "poppy_hip_bgr_downscale",
@@ -212,6 +215,14 @@ def lib():
         L.poppy_bgr_to_jpeg444_frame.argtypes = [vp, sz, i, i, i, vp]
         L.poppy_hip_i444_to_jpeg_frame.argtypes = [vp, vp, i, i, i, vp]
         L.poppy_hip_pool_set_jpeg_quality.argtypes = [vp, i]
+        L.poppy_jpeg_optimal_table.argtypes = [vp, vp, vp, vp]
+        L.poppy_hip_jpeg_optimal_table.argtypes = [vp, vp, vp, vp, vp]
+        L.poppy_i420_to_jpeg_opt_frame.argtypes = [vp, i, i, i, vp]
+        L.poppy_i444_to_jpeg_opt_frame.argtypes = [vp, i, i, i, vp]
+        L.poppy_bgr_to_jpeg_opt_frame.argtypes = [vp, sz, i, i, i, vp]
+        L.poppy_bgr_to_jpeg444_opt_frame.argtypes = [vp, sz, i, i, i, vp]
+        L.poppy_hip_i420_to_jpeg_opt_frame.argtypes = [vp, vp, i, i, i, vp]
+        L.poppy_hip_i444_to_jpeg_opt_frame.argtypes = [vp, vp, i, i, i, vp]
         L.poppy_png_frame_bytes.restype = sz
         L.poppy_png_frame_bytes.argtypes = [vp]
         L.poppy_png_table.argtypes = [i, vp, vp, vp]
@@ -361,8 +372,8 @@ def bgr_to_gif_frame(bgr):
 
 
 def _planes_to_jpeg(call, fmt, planes, w, h, quality, chk=None):
-    """The body of i420_to_jpeg_frame (fmt FRAME_JPEG) and i444_to_jpeg_frame (FRAME_JPEG444), on the host or a context."""
-    name, size, says = ("i444", 3 * w * h, "3 * w * h") if fmt == FRAME_JPEG444 else ("i420", frame_bytes(FRAME_I420, w, h), "w * h + 2 * cw * ch")
+    """The body of i420_to_jpeg_frame (fmt FRAME_JPEG), i444_to_jpeg_frame (FRAME_JPEG444) and their OPT forms, on the host or a context."""
+    name, size, says = ("i444", 3 * w * h, "3 * w * h") if fmt in (FRAME_JPEG444, FRAME_JPEG444_OPT) else ("i420", frame_bytes(FRAME_I420, w, h), "w * h + 2 * cw * ch")
     a = np.ascontiguousarray(planes, np.uint8).ravel()
     if w > 0 and h > 0 and a.size != size:
         raise PoppyError(f"{name}_to_jpeg_frame: an {name.upper()} frame has {says} bytes")
@@ -409,6 +420,48 @@ def bgr_to_jpeg444_frame(bgr, quality=JPEG_QUALITY_DEFAULT):
     a = np.ascontiguousarray(bgr, np.uint8)
     h, w = a.shape[:2]
     return _coded_frame(lambda dst: lib().poppy_bgr_to_jpeg444_frame(_p(a), w * 3, w, h, int(quality), dst), "bgr_to_jpeg444_frame", w, h, FRAME_JPEG444)
+
+
+def _optimal_table(call, counts, what, chk=None):
+    a = np.ascontiguousarray(counts, np.uint32).ravel()
+    if a.size != 256:
+        raise PoppyError(f"{what}: a table has 256 counts")
+    bits, vals, n = np.zeros(16, np.uint8), np.zeros(256, np.uint8), C.c_int(0)
+    rc = call(_p(a), _p(bits), _p(vals), C.byref(n))
+    if chk:
+        chk(rc, what)
+    elif rc:
+        raise PoppyError(f"poppy_{what}: {rc}")
+    return bits, vals[:n.value].copy()
+
+
+def jpeg_optimal_table(counts):
+    """Host-only: the Huffman table of 256 symbol counts by FRAME_JPEG_OPT's rule (poppy_jpeg_optimal_table): (bits[16], vals[n]) as a DHT segment holds them."""
+    return _optimal_table(lib().poppy_jpeg_optimal_table, counts, "jpeg_optimal_table")
+
+
+def i420_to_jpeg_opt_frame(i420, w, h, quality=JPEG_QUALITY_DEFAULT):
+    """Host-only: the FRAME_JPEG_OPT frame of a flat I420 frame (poppy_i420_to_jpeg_opt_frame): FRAME_JPEG's file on Huffman tables built from the frame's own symbols."""
+    return _planes_to_jpeg(lib().poppy_i420_to_jpeg_opt_frame, FRAME_JPEG_OPT, i420, w, h, quality)
+
+
+def i444_to_jpeg_opt_frame(i444, w, h, quality=JPEG_QUALITY_DEFAULT):
+    """Host-only: the FRAME_JPEG444_OPT frame of flat I444 planes (poppy_i444_to_jpeg_opt_frame)."""
+    return _planes_to_jpeg(lib().poppy_i444_to_jpeg_opt_frame, FRAME_JPEG444_OPT, i444, w, h, quality)
+
+
+def bgr_to_jpeg_opt_frame(bgr, quality=JPEG_QUALITY_DEFAULT):
+    """Host-only: the FRAME_JPEG_OPT frame of an HxWx3 BGR frame (poppy_bgr_to_jpeg_opt_frame = bgr_to_i420, then i420_to_jpeg_opt_frame)."""
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    return _coded_frame(lambda dst: lib().poppy_bgr_to_jpeg_opt_frame(_p(a), w * 3, w, h, int(quality), dst), "bgr_to_jpeg_opt_frame", w, h, FRAME_JPEG_OPT)
+
+
+def bgr_to_jpeg444_opt_frame(bgr, quality=JPEG_QUALITY_DEFAULT):
+    """Host-only: the FRAME_JPEG444_OPT frame of an HxWx3 BGR frame (poppy_bgr_to_jpeg444_opt_frame = bgr_to_i444, then i444_to_jpeg_opt_frame)."""
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    return _coded_frame(lambda dst: lib().poppy_bgr_to_jpeg444_opt_frame(_p(a), w * 3, w, h, int(quality), dst), "bgr_to_jpeg444_opt_frame", w, h, FRAME_JPEG444_OPT)
 
 
 def png_table(k):
@@ -1078,6 +1131,7 @@ class Context:
         FRAME_GIF_SEQ: FRAME_PAL8_SEQ's sequences with every frame coded like FRAME_GIF's, one palette in all frames of a call.
         FRAME_JPEG: every frame one baseline JPEG file, coded on the GPU at set_jpeg_quality's quality; flat arrays of each frame's own length (jpeg_frame_bytes).
         FRAME_JPEG444: the same with full-resolution chroma (4:4:4), coded from the frame's I444 planes.
+        FRAME_JPEG_OPT, FRAME_JPEG444_OPT: the same files on Huffman tables built on the GPU from each frame's own symbols: the same pixels in fewer bytes.
         FRAME_PNG: every frame one PNG file, lossless, coded on the GPU; flat arrays of each frame's own length (png_frame_bytes).
         FRAME_PNG_RUNS: the same with runs of equal bytes coded as matches: several times smaller on frames with flat or smooth regions."""
         self._chk(lib().poppy_hip_set_frame_format(self.h, int(fmt)), "set_frame_format")
@@ -1106,6 +1160,19 @@ class Context:
         """The FRAME_PNG_RUNS frame of an HxWx3 BGR frame, coded on this context's GPU (poppy_hip_bgr_to_png_runs_frame): the bytes of the host's
         bgr_to_png_runs_frame.  row_pad and whole as in bgr_to_png_frame."""
         return _png_frame(lambda *args: lib().poppy_hip_bgr_to_png_runs_frame(self.h, *args), "bgr_to_png_runs_frame", bgr, row_pad, self._chk, whole, FRAME_PNG_RUNS)
+
+    def i420_to_jpeg_opt_frame(self, i420, w, h, quality=JPEG_QUALITY_DEFAULT):
+        """The FRAME_JPEG_OPT frame of a flat I420 frame, coded on this context's GPU (poppy_hip_i420_to_jpeg_opt_frame: upload, the four kernels, download): the
+        bytes of the host's i420_to_jpeg_opt_frame."""
+        return _planes_to_jpeg(lambda *args: lib().poppy_hip_i420_to_jpeg_opt_frame(self.h, *args), FRAME_JPEG_OPT, i420, w, h, quality, self._chk)
+
+    def i444_to_jpeg_opt_frame(self, i444, w, h, quality=JPEG_QUALITY_DEFAULT):
+        """The FRAME_JPEG444_OPT frame of flat I444 planes, coded on this context's GPU (poppy_hip_i444_to_jpeg_opt_frame): the bytes of the host's."""
+        return _planes_to_jpeg(lambda *args: lib().poppy_hip_i444_to_jpeg_opt_frame(self.h, *args), FRAME_JPEG444_OPT, i444, w, h, quality, self._chk)
+
+    def jpeg_optimal_table(self, counts):
+        """The table-build kernel alone on 256 symbol counts (poppy_hip_jpeg_optimal_table): what the host's jpeg_optimal_table gives."""
+        return _optimal_table(lambda *args: lib().poppy_hip_jpeg_optimal_table(self.h, *args), counts, "jpeg_optimal_table", self._chk)
 
     def i444_to_jpeg_frame(self, i444, w, h, quality=JPEG_QUALITY_DEFAULT):
         """The FRAME_JPEG444 frame of flat I444 planes, coded on this context's GPU (poppy_hip_i444_to_jpeg_frame: upload, the two kernels, download): the bytes

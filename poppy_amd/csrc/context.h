@@ -122,7 +122,7 @@ struct poppy_hip_ctx {
     bool writer_attached = false;                   // a multi-frame call with a writer is in progress
     int frame_format = POPPY_FRAME_BGR;             // of the frames handed to writers (poppy_hip_set_frame_format)
     int frame_scale = 1;                            // ... and the whole factor they are scaled down by first (poppy_hip_set_frame_scale; frame_format.h: writer_geom)
-    int jpeg_quality = POPPY_JPEG_QUALITY_DEFAULT;  // ... and the quality of POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames (poppy_hip_set_jpeg_quality)
+    int jpeg_quality = POPPY_JPEG_QUALITY_DEFAULT;  // ... and the quality of the frames of the four JPEG formats (poppy_hip_set_jpeg_quality)
     uint8_t* jpeg_tables = nullptr;                 // ... with its header and quantiser tables on the device (frame_format.h: ensure_jpeg_tables; rewritten in place when the quality changes)
     int frame_ow = 0, frame_oh = 0;                 // ... or the size they are resized to (poppy_hip_set_frame_size; 0, 0: none; never beside a scale above 1)
     DeviceBuffer scale_scratch;                     // the scaled BGR of the copies and fallback frames that no slot renders (writer_image.h: scale_into_scratch)

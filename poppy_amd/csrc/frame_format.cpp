@@ -6,7 +6,7 @@
 static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H <= (unsigned long long)POPPY_PAL8_MAX_PIXELS; }
 constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 2^24 pixels";
 constexpr const char* kGifSizeMsg = "POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 65535 pixels in width and height";
-constexpr const char* kJpegSizeMsg = "POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 take frames of at most 65535 pixels in width and height whose capacity stays below 2^32 bytes";
+constexpr const char* kJpegSizeMsg = "POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444 and their OPT forms take frames of at most 65535 pixels in width and height whose capacity stays below 2^32 bytes";
 constexpr const char* kPngSizeMsg = "POPPY_FRAME_PNG and POPPY_FRAME_PNG_RUNS take frames whose capacity stays below 2^31 bytes";
 constexpr const char* kSeqSizeMsg = "POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ take sequences of fewer than 2^32 pixels in all";
 
@@ -88,7 +88,12 @@ static void free_slot_coded(SlotFormat& f) {
 static uint8_t* SlotFormat::* const kRasterBuffer[] = {nullptr, &SlotFormat::i420, &SlotFormat::i444, &SlotFormat::pal8};
 
 size_t coding_scratch_bytes(const FormatTraits& t, int W, int H) {
-    return t.coder == kCoderJpeg ? jpeg_scratch_bytes(W, H, t.sampling()) : t.coder == kCoderPng ? png_scratch_bytes(W, H, t.runs()) : gif_scratch_bytes(W, H);
+    return t.coder == kCoderJpeg ? jpeg_scratch_bytes(W, H, t.sampling(), t.frame_tables) : t.coder == kCoderPng ? png_scratch_bytes(W, H, t.runs()) : gif_scratch_bytes(W, H);
+}
+
+// what a coder's scratch holds before its first frame: under JPEG on per-frame tables the frame's symbol counts, zero (the table build leaves them zero again)
+hipError_t prepare_coding_scratch(const FormatTraits& t, uint8_t* scratch, int W, int H, hipStream_t s) {
+    return t.coder == kCoderJpeg && t.frame_tables ? launch_jpeg_counts_clear(scratch, W, H, t.sampling(), s) : hipSuccess;
 }
 
 // What the format's record names, per slot.  A raster step: the buffer of its form, kept until the pair's buffers go, and under PAL8 the conversion's tables.  The
@@ -113,7 +118,11 @@ int alloc_slot_format(poppy_hip_ctx* c) {
         if (f.coded_for != fmt) free_slot_coded(f);                 // (sized for another coded format; the frames are drained and the bodies of that format are captured again)
         f.coded_for = fmt;
         if (!f.coded) HIPCHK(c, hipMalloc((void**)&f.coded, frame_bytes(t, W, H) + 16));
-        if (!f.coded_scratch) HIPCHK(c, hipMalloc((void**)&f.coded_scratch, coding_scratch_bytes(t, W, H)));
+        if (!f.coded_scratch) {
+            HIPCHK(c, hipMalloc((void**)&f.coded_scratch, coding_scratch_bytes(t, W, H)));
+            HIPCHK(c, prepare_coding_scratch(t, f.coded_scratch, W, H, nullptr));
+            HIPCHK(c, hipStreamSynchronize(nullptr));      // (the frames that use it run on other streams)
+        }
         if (!f.coded_total) {
             HIPCHK(c, hipHostMalloc((void**)&f.coded_total, 64, hipHostMallocMapped));
             HIPCHK(c, hipHostGetDevicePointer(&f.coded_total_dev, f.coded_total, 0));
@@ -170,10 +179,17 @@ static void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* f
     if (tm) tm->mark("gif_pack");
 }
 
-static void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, jpeg::Sampling sm, hipStream_t s, hipEvent_t done, Timer* tm) {
-    launch_jpeg_code(planes, tables, scratch, W, H, sm, s);
+// (opt: on per-frame tables — the counting pass and the table build in front, both on the coder's scratch, which the slot owns: frames in flight are coded side by side)
+static void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, jpeg::Sampling sm, bool opt, hipStream_t s, hipEvent_t done, Timer* tm) {
+    if (opt) {
+        launch_jpeg_count(planes, tables, scratch, W, H, sm, s);
+        if (tm) tm->mark("jpeg_count");
+        launch_jpeg_tables(scratch, W, H, sm, s);
+        if (tm) tm->mark("jpeg_tables");
+    }
+    launch_jpeg_code(planes, tables, scratch, W, H, sm, opt, s);
     if (tm) tm->mark("jpeg_code");
-    launch_jpeg_pack(tables, scratch, frame, (uint32_t*)total_dev, W, H, sm, s, done);
+    launch_jpeg_pack(tables, scratch, frame, (uint32_t*)total_dev, W, H, sm, opt, s, done);
     if (tm) tm->mark("jpeg_pack");
 }
 
@@ -194,7 +210,7 @@ static void enqueue_png_coding(bool runs, const uint8_t* bgr, uint8_t* scratch, 
 
 void enqueue_coding(const FormatTraits& t, const uint8_t* src, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
     if (t.coder == kCoderGif) enqueue_gif_coding(src, scratch, frame, total_dev, W, H, s, done, tm);
-    else if (t.coder == kCoderJpeg) enqueue_jpeg_coding(src, tables, scratch, frame, total_dev, W, H, t.sampling(), s, done, tm);
+    else if (t.coder == kCoderJpeg) enqueue_jpeg_coding(src, tables, scratch, frame, total_dev, W, H, t.sampling(), t.frame_tables, s, done, tm);
     else if (t.coder == kCoderPng) enqueue_png_coding(t.runs(), src, scratch, frame, total_dev, W, H, s, done, tm);
 }
 

@@ -58,7 +58,7 @@ inline int sample(const uint8_t* plane, int w, int h, int x, int y) {
 }
 
 // the block whose top left sample is (x0, y0): FDCT in two passes and quantisation, the result in zig-zag order
-void code_block_coefficients(const uint8_t* plane, int w, int h, int x0, int y0, const QualityTables& q, int table, int* zz) {
+void code_block_coefficients(const uint8_t* plane, int w, int h, int x0, int y0, const QualityTables& q, int table, int16_t* zz) {
     int t[64], f[64];
     for (int y = 0; y < 8; ++y)
         for (int u = 0; u < 8; ++u) {
@@ -75,31 +75,47 @@ void code_block_coefficients(const uint8_t* plane, int w, int h, int x0, int y0,
     for (int k = 0; k < 64; ++k) {
         const int n = kZigzag[k], a = f[n] < 0 ? -f[n] : f[n];
         const int m = (int)((a + q.bias[table][n]) / (q.bias[table][n] * 2));      // (|F| + 4 Q) / (8 Q)
-        zz[k] = f[n] < 0 ? -m : m;
+        zz[k] = (int16_t)(f[n] < 0 ? -m : m);
     }
 }
 
 inline int category(int v) { int a = v < 0 ? -v : v, c = 0; while (a) { ++c; a >>= 1; } return c; }
-inline void put_value(BitString& b, uint32_t huff, int v, int cat) {
-    b.put(huff >> 8, (int)(huff & 255));
-    if (cat) b.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << cat) - 1), cat);
-}
 
-void code_block(BitString& b, const int* zz, int* pred, int table) {
+// One block as its symbols, the one walk of both passes: sink.dc(table, category, difference), then per AC symbol sink.ac(table, symbol, value, category)
+// (ZRL and EOB: value 0, category 0).
+template <class Sink>
+void code_block(Sink& sink, const int16_t* zz, int* pred, int table) {
     const int diff = zz[0] - *pred;
     *pred = zz[0];
-    const int dc_cat = category(diff);
-    put_value(b, kHuff.dc[table][dc_cat], diff, dc_cat);
+    sink.dc(table, category(diff), diff);
     int run = 0;
     for (int k = 1; k < 64; ++k) {
         if (zz[k] == 0) { ++run; continue; }
-        for (; run >= 16; run -= 16) b.put(kHuff.ac[table][0xF0] >> 8, (int)(kHuff.ac[table][0xF0] & 255));
+        for (; run >= 16; run -= 16) sink.ac(table, 0xF0, 0, 0);
         const int cat = category(zz[k]);
-        put_value(b, kHuff.ac[table][run << 4 | cat], zz[k], cat);
+        sink.ac(table, run << 4 | cat, zz[k], cat);
         run = 0;
     }
-    if (run) b.put(kHuff.ac[table][0] >> 8, (int)(kHuff.ac[table][0] & 255));
+    if (run) sink.ac(table, 0, 0, 0);
 }
+
+// the coding pass: a symbol's code from the tables it is given, then the value's low bits
+struct BitSink {
+    BitString& b;
+    const HuffTables& huff;
+    void put_value(uint32_t code, int v, int cat) {
+        b.put(code >> 8, (int)(code & 255));
+        if (cat) b.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << cat) - 1), cat);
+    }
+    void dc(int table, int cat, int diff) { put_value(huff.dc[table][cat], diff, cat); }
+    void ac(int table, int symbol, int v, int cat) { put_value(huff.ac[table][symbol], v, cat); }
+};
+// the counting pass of the per-frame tables
+struct CountSink {
+    SymbolCounts& n;
+    void dc(int table, int cat, int) { ++n.dc[table][cat]; }
+    void ac(int table, int symbol, int, int) { ++n.ac[table][symbol]; }
+};
 
 }  // namespace
 
@@ -122,45 +138,103 @@ void write_header(int quality, int width, int height, uint8_t* dst) {
 
 namespace {
 
-// the frame of the planes of sampling `s` with restart intervals of `restart` MCUs (the header's DRI names it); returns `total`
-size_t encode(const uint8_t* planes, int w, int h, int quality, Sampling s, int restart, uint8_t* dst) {
-    const int side = mcu_side(s), mw = (w + side - 1) / side, mh = (h + side - 1) / side, n_mcu = mw * mh;
-    const int cw = s == k444 ? w : (w + 1) / 2, ch = s == k444 ? h : (h + 1) / 2;      // the chroma planes
-    const uint8_t *yp = planes, *up = yp + (size_t)w * h, *vp = up + (size_t)cw * ch;
+// The planes of a frame as their blocks in coding order.  Nothing of the frame is kept: a pass computes each block's coefficients as it reaches it, so the
+// two passes of the per-frame tables compute them twice and the frame costs no memory beyond its planes and its bytes.
+struct FrameBlocks {
+    const uint8_t *yp, *up, *vp;
+    int w, h, cw, ch, side, mw, n_mcu;
+    Sampling s;
     QualityTables q;
-    fill_quality_tables(quality, &q);
-    write_header(quality, w, h, dst + 4);
-    dst[4 + kOffSofSampling] = sof_sampling(s);
-    put16(dst + 4 + kOffDri + 4, restart);
-    size_t at = kFrameData;
-    int zz[64];
-    for (int first = 0, seg = 0; first < n_mcu; first += restart, ++seg) {
-        BitString b;
+    FrameBlocks(const uint8_t* planes, int w_, int h_, int quality, Sampling s_) : w(w_), h(h_), s(s_) {
+        side = mcu_side(s); mw = (w + side - 1) / side; n_mcu = mw * ((h + side - 1) / side);
+        cw = s == k444 ? w : (w + 1) / 2; ch = s == k444 ? h : (h + 1) / 2;      // the chroma planes
+        yp = planes; up = yp + (size_t)w * h; vp = up + (size_t)cw * ch;
+        fill_quality_tables(quality, &q);
+    }
+    // block k of MCU m: the luma blocks first (2 x 2 of them in a 16 x 16 MCU, one in an 8 x 8 MCU), then Cb, then Cr
+    void block(int m, int k, int16_t* zz) const {
+        const int mx = m % mw, my = m / mw, luma = mcu_blocks(s) - 2;
+        if (k < luma) code_block_coefficients(yp, w, h, side * mx + 8 * (k & 1), side * my + 8 * (k >> 1), q, 0, zz);
+        else code_block_coefficients(k == luma ? up : vp, cw, ch, 8 * mx, 8 * my, q, 1, zz);
+    }
+};
+
+// segment by segment, every block of the frame through `sink`; begin(segment) in front of a segment's first block, end(segment, last) behind its last
+template <class Sink, class Begin, class End>
+void walk_segments(const FrameBlocks& f, int restart, Sink& sink, Begin begin, End end) {
+    const int blocks = mcu_blocks(f.s), luma = blocks - 2;
+    int16_t zz[64];
+    for (int first = 0, seg = 0; first < f.n_mcu; first += restart, ++seg) {
+        begin(seg);
         int pred[3] = {0, 0, 0};
-        for (int m = first; m < n_mcu && m < first + restart; ++m) {
-            const int mx = m % mw, my = m / mw;
-            for (int k = 0; k < (s == k444 ? 1 : 4); ++k) {       // the luma blocks: 2 x 2 of them in a 16 x 16 MCU, one in an 8 x 8 MCU
-                code_block_coefficients(yp, w, h, side * mx + 8 * (k & 1), side * my + 8 * (k >> 1), q, 0, zz);
-                code_block(b, zz, &pred[0], 0);
+        for (int m = first; m < f.n_mcu && m < first + restart; ++m)
+            for (int k = 0; k < blocks; ++k) {
+                f.block(m, k, zz);
+                code_block(sink, zz, &pred[k < luma ? 0 : k - luma + 1], k >= luma);
             }
-            code_block_coefficients(up, cw, ch, 8 * mx, 8 * my, q, 1, zz);
-            code_block(b, zz, &pred[1], 1);
-            code_block_coefficients(vp, cw, ch, 8 * mx, 8 * my, q, 1, zz);
-            code_block(b, zz, &pred[2], 1);
+        end(seg, first + restart >= f.n_mcu);
+    }
+}
+
+// the OPT header at dst: the fixed header's bytes around one DHT with the four tables given; returns its length
+size_t write_opt_header(int quality, int w, int h, Sampling s, int restart, const uint8_t (*bits)[16], const uint8_t (*vals)[256], const int* n, uint8_t* dst) {
+    uint8_t fixed[kHeaderBytes];
+    write_header(quality, w, h, fixed);
+    fixed[kOffSofSampling] = sof_sampling(s);
+    put16(fixed + kOffDri + 4, restart);
+    memcpy(dst, fixed, kOffDht);
+    uint8_t* p = dst + kOffDht;
+    p[0] = 0xFF; p[1] = 0xC4; put16(p + 2, 2 + 4 * 17 + n[0] + n[1] + n[2] + n[3]);
+    p += 4;
+    for (int k = 0; k < 4; ++k) {                           // DC 0, AC 0, DC 1, AC 1
+        *p++ = (uint8_t)((k & 1) << 4 | k >> 1);
+        memcpy(p, bits[k], 16); memcpy(p + 16, vals[k], (size_t)n[k]); p += 16 + n[k];
+    }
+    memcpy(p, fixed + kOffDri, kHeaderBytes - kOffDri);
+    return (size_t)(p - dst) + (kHeaderBytes - kOffDri);
+}
+
+// the frame of the planes of sampling `s` with restart intervals of `restart` MCUs (the header's DRI names it), on the Annex K tables or (opt) on the tables
+// of the frame's own counts: the counting pass, the table rule, and the same coding pass over the same coefficients on what it gave; returns `total`
+size_t encode(const uint8_t* planes, int w, int h, int quality, Sampling s, int restart, bool opt, uint8_t* dst) {
+    const FrameBlocks frame(planes, w, h, quality, s);
+    HuffTables built{};
+    size_t at = kFrameData;
+    if (opt) {
+        SymbolCounts counts{};
+        CountSink counter{counts};
+        walk_segments(frame, restart, counter, [](int) {}, [](int, bool) {});
+        uint8_t bits[4][16], vals[4][256];
+        int n[4];
+        for (int k = 0; k < 4; ++k) {
+            uint32_t c[256] = {};
+            memcpy(c, table_of(counts, k), sizeof(uint32_t) * table_symbols(k));
+            poppy_jpeg_optimal_table(c, bits[k], vals[k], &n[k]);      // (every table of every frame has a symbol, and a frame the format accepts stays below the sum's limit)
+            huff_fill(bits[k], vals[k], table_of(built, k));
         }
+        at = 4 + write_opt_header(quality, w, h, s, restart, bits, vals, n, dst + 4);
+    } else {
+        write_header(quality, w, h, dst + 4);
+        dst[4 + kOffSofSampling] = sof_sampling(s);
+        put16(dst + 4 + kOffDri + 4, restart);
+    }
+    BitString b;
+    BitSink coder{b, opt ? built : kHuff};
+    walk_segments(frame, restart, coder, [&](int) { b = BitString(); }, [&](int seg, bool last) {
         b.pad();
         for (uint8_t byte : b.bytes) { dst[at++] = byte; if (byte == 0xFF) dst[at++] = 0; }
         dst[at++] = 0xFF;
-        dst[at++] = first + restart < n_mcu ? (uint8_t)(0xD0 + (seg & 7)) : (uint8_t)0xD9;
-    }
+        dst[at++] = last ? (uint8_t)0xD9 : (uint8_t)(0xD0 + (seg & 7));
+    });
     dst[0] = (uint8_t)at; dst[1] = (uint8_t)(at >> 8); dst[2] = (uint8_t)(at >> 16); dst[3] = (uint8_t)(at >> 24);
     return at;
 }
 
 }  // namespace
 
-size_t encode_i420(const uint8_t* i420, int w, int h, int quality, int restart_mcus, uint8_t* dst) { return encode(i420, w, h, quality, k420, restart_mcus, dst); }
-size_t encode_planes(const uint8_t* planes, int w, int h, int quality, Sampling s, uint8_t* dst) { return encode(planes, w, h, quality, s, restart_mcus(s), dst); }
+size_t encode_i420(const uint8_t* i420, int w, int h, int quality, int restart_mcus, uint8_t* dst) { return encode(i420, w, h, quality, k420, restart_mcus, false, dst); }
+size_t encode_planes(const uint8_t* planes, int w, int h, int quality, Sampling s, uint8_t* dst) { return encode(planes, w, h, quality, s, restart_mcus(s), false, dst); }
+size_t encode_planes_opt(const uint8_t* planes, int w, int h, int quality, Sampling s, uint8_t* dst) { return encode(planes, w, h, quality, s, restart_mcus(s), true, dst); }
 
 }  // namespace jpeg
 }  // namespace poppy_hip
@@ -199,6 +273,67 @@ int poppy_bgr_to_jpeg444_frame(const uint8_t* bgr, size_t stride, int width, int
     std::vector<uint8_t> i444((size_t)width * height * 3);
     const int rc = poppy_bgr_to_i444(bgr, stride, width, height, i444.data());
     return rc ? rc : poppy_i444_to_jpeg_frame(i444.data(), width, height, quality, dst);
+}
+
+// The table rule of POPPY_FRAME_JPEG_OPT (include/poppy_hip.h states it step by step): T.81 Annex K.2 with every tie decided, lengths limited by K.3.
+int poppy_jpeg_optimal_table(const uint32_t* counts, uint8_t* bits, uint8_t* vals, int* n_vals) {
+    if (!counts || !bits || !vals || !n_vals) return POPPY_E_ARG;
+    uint64_t freq[257], sum = 0;
+    for (int i = 0; i < 256; ++i) { freq[i] = counts[i]; sum += counts[i]; }
+    if (sum == 0 || sum >= 0xffffffffull) return POPPY_E_ARG;
+    freq[256] = 1;                                          // the reserved entry: no real code is all ones
+    int len[257] = {}, tree[257];                           // a symbol's code length so far, and the root of the tree it is in (the index that holds the tree's count)
+    for (int i = 0; i <= 256; ++i) tree[i] = i;
+    for (;;) {
+        int c1 = -1, c2 = -1;                               // the smallest non-zero count, the largest index among equals; the same among the others
+        for (int i = 0; i <= 256; ++i) if (freq[i] && (c1 < 0 || freq[i] <= freq[c1])) c1 = i;
+        for (int i = 0; i <= 256; ++i) if (freq[i] && i != c1 && (c2 < 0 || freq[i] <= freq[c2])) c2 = i;
+        if (c2 < 0) break;
+        freq[c1] += freq[c2]; freq[c2] = 0;
+        for (int i = 0; i <= 256; ++i) if (tree[i] == c1 || tree[i] == c2) { ++len[i]; tree[i] = c1; }
+    }
+    int of_length[258] = {};                                // lengths up to 256: 257 leaves
+    for (int i = 0; i <= 256; ++i) if (len[i]) ++of_length[len[i]];
+    for (int i = 256; i > 16; --i)                          // Annex K.3
+        while (of_length[i] > 0) {
+            int j = i - 2;
+            while (of_length[j] == 0) --j;
+            of_length[i] -= 2; of_length[i - 1] += 1; of_length[j + 1] += 2; of_length[j] -= 1;
+        }
+    int longest = 16;
+    while (of_length[longest] == 0) --longest;
+    --of_length[longest];                                   // the reserved entry
+    for (int i = 0; i < 16; ++i) bits[i] = (uint8_t)of_length[i + 1];
+    int n = 0;
+    for (int l = 1; l <= 256; ++l)
+        for (int i = 0; i < 256; ++i) if (len[i] == l) vals[n++] = (uint8_t)i;
+    *n_vals = n;
+    return POPPY_OK;
+}
+
+static int planes_to_jpeg_opt(const uint8_t* planes, int width, int height, int quality, poppy_hip::jpeg::Sampling s, uint8_t* dst) {
+    if (!planes || !dst || width <= 0 || height <= 0 || quality < 1 || quality > 100) return POPPY_E_ARG;
+    if (!jpeg_opt_fits(width, height, s)) return POPPY_E_UNSUPPORTED;
+    poppy_hip::jpeg::encode_planes_opt(planes, width, height, quality, s, dst);
+    return POPPY_OK;
+}
+int poppy_i420_to_jpeg_opt_frame(const uint8_t* i420, int width, int height, int quality, uint8_t* dst) { return planes_to_jpeg_opt(i420, width, height, quality, poppy_hip::jpeg::k420, dst); }
+int poppy_i444_to_jpeg_opt_frame(const uint8_t* i444, int width, int height, int quality, uint8_t* dst) { return planes_to_jpeg_opt(i444, width, height, quality, poppy_hip::jpeg::k444, dst); }
+
+int poppy_bgr_to_jpeg_opt_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst) {
+    if (!bgr || !dst || width <= 0 || height <= 0 || stride < (size_t)width * 3 || quality < 1 || quality > 100) return POPPY_E_ARG;
+    if (!jpeg_opt_fits(width, height)) return POPPY_E_UNSUPPORTED;
+    std::vector<uint8_t> i420(poppy_frame_bytes(POPPY_FRAME_I420, width, height));
+    const int rc = poppy_bgr_to_i420(bgr, stride, width, height, i420.data());
+    return rc ? rc : poppy_i420_to_jpeg_opt_frame(i420.data(), width, height, quality, dst);
+}
+
+int poppy_bgr_to_jpeg444_opt_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst) {
+    if (!bgr || !dst || width <= 0 || height <= 0 || stride < (size_t)width * 3 || quality < 1 || quality > 100) return POPPY_E_ARG;
+    if (!jpeg_opt_fits(width, height, poppy_hip::jpeg::k444)) return POPPY_E_UNSUPPORTED;
+    std::vector<uint8_t> i444((size_t)width * height * 3);
+    const int rc = poppy_bgr_to_i444(bgr, stride, width, height, i444.data());
+    return rc ? rc : poppy_i444_to_jpeg_opt_frame(i444.data(), width, height, quality, dst);
 }
 
 }  // extern "C"

@@ -19,6 +19,8 @@ constexpr size_t kGifFrameMinBytes = 776;      // ... and the smallest there is,
 inline bool coded_length_ok(size_t total, size_t capacity, size_t least) { return total >= least && total <= capacity; }      // a coder's `total` between its record's `least` and the capacity, before that many bytes are copied or read
 // A JPEG-coded frame: what the format takes is SOF0's 16-bit sides, and a capacity (jpeg_tables.h; include/poppy_hip.h has the derivation) that `total`'s 32 bits hold
 inline bool jpeg_fits(int W, int H, poppy_hip::jpeg::Sampling s = poppy_hip::jpeg::k420) { return W <= 65535 && H <= 65535 && poppy_hip::jpeg::frame_capacity((size_t)W, (size_t)H, s) <= 0xffffffffull; }
+// ... and the same on per-frame tables (POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT), on their own capacity
+inline bool jpeg_opt_fits(int W, int H, poppy_hip::jpeg::Sampling s = poppy_hip::jpeg::k420) { return W <= 65535 && H <= 65535 && poppy_hip::jpeg::opt_frame_capacity((size_t)W, (size_t)H, s) <= 0xffffffffull; }
 // A PNG-coded frame: what the format takes is a capacity (png_tables.h; with runs coded as matches png_runs_tables.h) below 2^31 bytes, which IDAT's length field and `total` hold
 inline bool png_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
 inline bool png_runs_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png_runs::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
@@ -33,6 +35,7 @@ struct FormatTraits {
     FrameRaster raster;
     FrameCoder coder;
     int variant;               // the JPEG coder's sampling (jpeg::Sampling), the PNG coder's runs flag
+    bool frame_tables;         // the JPEG coder's Huffman tables: the Annex K examples (false), or four tables built from this frame's own symbol counts
     bool sequence;             // one palette for all the frames a call hands to its writer: they wait in the sequence store until the last is rendered (palette_seq.h),
                                // and no slot converts or codes them — the sequence pass and the sequence's coder do
     size_t least;              // the smallest `total` its coder gives (coded_length_ok's lower bound)
@@ -46,16 +49,18 @@ struct FormatTraits {
     constexpr bool runs() const { return variant != 0; }
 };
 inline constexpr FormatTraits kFormats[] = {
-    {POPPY_FRAME_BGR,      "BGR",  kRasterNone, kCoderNone, 0, false, 0},
-    {POPPY_FRAME_I420,     "I420", kRasterI420, kCoderNone, 0, false, 0},
-    {POPPY_FRAME_PAL8,     "PAL8", kRasterPal8, kCoderNone, 0, false, 0},
-    {POPPY_FRAME_PAL8_SEQ, "PAL8", kRasterPal8, kCoderNone, 0, true,  0},
-    {POPPY_FRAME_GIF,      "GIF",  kRasterPal8, kCoderGif,  0, false, kGifFrameMinBytes},
-    {POPPY_FRAME_GIF_SEQ,  "GIF",  kRasterPal8, kCoderGif,  0, true,  kGifFrameMinBytes},
-    {POPPY_FRAME_JPEG,     "JPEG", kRasterI420, kCoderJpeg, poppy_hip::jpeg::k420, false, poppy_hip::jpeg::kFrameMinBytes},      // the header, a byte of entropy-coded data, EOI
-    {POPPY_FRAME_JPEG444,  "JPEG", kRasterI444, kCoderJpeg, poppy_hip::jpeg::k444, false, poppy_hip::jpeg::kFrameMinBytes},      // (twice the blocks)
-    {POPPY_FRAME_PNG,      "PNG",  kRasterNone, kCoderPng,  0, false, poppy_hip::png::kFrameMinBytes},                            // the file's fixed parts and one byte of deflate data
-    {POPPY_FRAME_PNG_RUNS, "PNG",  kRasterNone, kCoderPng,  1, false, poppy_hip::png::kFrameMinBytes},                            // PNG with runs coded as matches, the same limits on its own capacity
+    {POPPY_FRAME_BGR,         "BGR",  kRasterNone, kCoderNone, 0,                     false, false, 0},
+    {POPPY_FRAME_I420,        "I420", kRasterI420, kCoderNone, 0,                     false, false, 0},
+    {POPPY_FRAME_PAL8,        "PAL8", kRasterPal8, kCoderNone, 0,                     false, false, 0},
+    {POPPY_FRAME_PAL8_SEQ,    "PAL8", kRasterPal8, kCoderNone, 0,                     false, true,  0},
+    {POPPY_FRAME_GIF,         "GIF",  kRasterPal8, kCoderGif,  0,                     false, false, kGifFrameMinBytes},
+    {POPPY_FRAME_GIF_SEQ,     "GIF",  kRasterPal8, kCoderGif,  0,                     false, true,  kGifFrameMinBytes},
+    {POPPY_FRAME_JPEG,        "JPEG", kRasterI420, kCoderJpeg, poppy_hip::jpeg::k420, false, false, poppy_hip::jpeg::kFrameMinBytes},      // the header, a byte of entropy-coded data, EOI
+    {POPPY_FRAME_JPEG444,     "JPEG", kRasterI444, kCoderJpeg, poppy_hip::jpeg::k444, false, false, poppy_hip::jpeg::kFrameMinBytes},      // (twice the blocks)
+    {POPPY_FRAME_JPEG_OPT,    "JPEG", kRasterI420, kCoderJpeg, poppy_hip::jpeg::k420, true,  false, poppy_hip::jpeg::kOptFrameMinBytes},   // the header with four one-symbol tables, a byte of data, EOI
+    {POPPY_FRAME_JPEG444_OPT, "JPEG", kRasterI444, kCoderJpeg, poppy_hip::jpeg::k444, true,  false, poppy_hip::jpeg::kOptFrameMinBytes},
+    {POPPY_FRAME_PNG,         "PNG",  kRasterNone, kCoderPng,  0,                     false, false, poppy_hip::png::kFrameMinBytes},       // the file's fixed parts and one byte of deflate data
+    {POPPY_FRAME_PNG_RUNS,    "PNG",  kRasterNone, kCoderPng,  1,                     false, false, poppy_hip::png::kFrameMinBytes},       // PNG with runs coded as matches, the same limits on its own capacity
 };
 constexpr const FormatTraits* format_traits(int fmt) {      // null for an unknown format
     for (const FormatTraits& t : kFormats) if (t.format == fmt) return &t;
@@ -70,11 +75,11 @@ constexpr size_t raster_bytes(FrameRaster r, size_t w, size_t h) {
 }
 // what the format's coder takes (a format without one: every frame; the palette's own limit is format_refuses')
 inline bool fits(const FormatTraits& t, int W, int H) {
-    return t.coder == kCoderJpeg ? jpeg_fits(W, H, t.sampling()) : t.coder == kCoderPng ? (t.runs() ? png_runs_fits(W, H) : png_fits(W, H)) : t.coder == kCoderGif ? W <= 65535 && H <= 65535 : true;
+    return t.coder == kCoderJpeg ? (t.frame_tables ? jpeg_opt_fits(W, H, t.sampling()) : jpeg_fits(W, H, t.sampling())) : t.coder == kCoderPng ? (t.runs() ? png_runs_fits(W, H) : png_fits(W, H)) : t.coder == kCoderGif ? W <= 65535 && H <= 65535 : true;
 }
 // a coded frame's capacity, an upper bound of `total` for any content (include/poppy_hip.h has the derivations)
 inline size_t capacity(const FormatTraits& t, size_t w, size_t h) {
-    return t.coder == kCoderJpeg ? (size_t)poppy_hip::jpeg::frame_capacity(w, h, t.sampling()) :
+    return t.coder == kCoderJpeg ? (size_t)(t.frame_tables ? poppy_hip::jpeg::opt_frame_capacity(w, h, t.sampling()) : poppy_hip::jpeg::frame_capacity(w, h, t.sampling())) :
            t.coder == kCoderPng ? (size_t)(t.runs() ? poppy_hip::png_runs::frame_capacity(w, h) : poppy_hip::png::frame_capacity(w, h)) : t.coder == kCoderGif ? gif_frame_capacity(w, h) : 0;
 }
 // poppy_frame_bytes of a frame with positive sides: the raster form's bytes, or the capacity (PNG: nothing to size where the format refuses)
@@ -86,7 +91,7 @@ inline size_t frame_bytes(const FormatTraits& t, int W, int H) {
 // every constant of include/poppy_hip.h has exactly one record, and the records hold what the code relies on
 constexpr bool formats_hold() {
     constexpr int all[] = {POPPY_FRAME_BGR, POPPY_FRAME_I420, POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF, POPPY_FRAME_GIF_SEQ, POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444,
-                           POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS};
+                           POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT};
     if (sizeof all / sizeof *all != sizeof kFormats / sizeof *kFormats) return false;
     for (int fmt : all) {
         int n = 0;
@@ -101,6 +106,8 @@ constexpr bool formats_hold() {
         if (t.coder == kCoderGif && t.raster != kRasterPal8) return false;      // the coders read their raster form: GIF PAL8, JPEG the planes of its sampling, PNG the BGR frame
         if (t.coder == kCoderJpeg && t.raster != (t.sampling() == poppy_hip::jpeg::k444 ? kRasterI444 : kRasterI420)) return false;
         if (t.coder == kCoderPng && t.raster != kRasterNone) return false;
+        if (t.frame_tables && t.coder != kCoderJpeg) return false;      // per-frame tables are the JPEG coder's, and such a format's smallest frame is the OPT header's
+        if (t.coder == kCoderJpeg && t.least != (t.frame_tables ? poppy_hip::jpeg::kOptFrameMinBytes : poppy_hip::jpeg::kFrameMinBytes)) return false;
     }
     return true;
 }

@@ -10,12 +10,13 @@
 //   POPPY_SINK_GIF_GLOBAL  the same for PAL8_SEQ frames: the first frame's palette as the global colour table, local tables only where a frame's palette differs
 //   POPPY_SINK_GIF_CODED   POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames, whose image data arrives coded (frame_gif.cpp, kernels_frame_gif.hip): nothing is coded here
 //   POPPY_SINK_GIF_GLOBAL_CODED  POPPY_SINK_GIF_GLOBAL's file from coded frames (POPPY_FRAME_GIF_SEQ): the first frame's palette as the global table, local tables only where a palette differs
-//   POPPY_SINK_MJPEG  one RIFF AVI file, a `vids` / `MJPG` stream, from POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames, whose bytes arrive coded (frame_jpeg.cpp, kernels_frame_jpeg.hip)
+//   POPPY_SINK_MJPEG  one RIFF AVI file, a `vids` / `MJPG` stream, from POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames and their OPT forms, whose bytes arrive coded (frame_jpeg.cpp, kernels_frame_jpeg.hip)
 //   POPPY_SINK_PNG   one PNG file per frame from POPPY_FRAME_PNG and POPPY_FRAME_PNG_RUNS frames, whose bytes arrive coded (frame_png.cpp, frame_png_runs.cpp, kernels_frame_png.hip); the path as under PPM
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "frame_limits.h"
 #include "gif_lzw.h"
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -163,16 +164,43 @@ bool jpeg_sof0_size(const uint8_t* jfif, size_t n, int* w, int* h, int* sampling
     return false;
 }
 
+// whether the file's first DHT segment in front of SOS is, byte for byte, the fixed header's with the four Annex K tables (a file without one: yes — it is held
+// as every frame was before there were per-frame tables)
+bool jpeg_dht_is_standard(const uint8_t* jfif, size_t n) {
+    using namespace poppy_hip::jpeg;
+    size_t at = 2;
+    while (at + 4 <= n && jfif[at] == 0xFF) {
+        const int marker = jfif[at + 1];
+        const size_t len = (size_t)jfif[at + 2] << 8 | jfif[at + 3];
+        if (marker == 0xDA || len < 2 || at + 2 + len > n) return true;
+        if (marker == 0xC4) {
+            static const std::array<uint8_t, kOffDri - kOffDht> standard = [] {      // the fixed header's DHT segment with its marker (no quality or size changes it): built once
+                uint8_t fixed[kHeaderBytes];
+                write_header(POPPY_JPEG_QUALITY_DEFAULT, 1, 1, fixed);
+                std::array<uint8_t, kOffDri - kOffDht> dht;
+                memcpy(dht.data(), fixed + kOffDht, dht.size());
+                return dht;
+            }();
+            return 2 + len == standard.size() && memcmp(jfif + at, standard.data(), standard.size()) == 0;
+        }
+        at += 2 + len;
+    }
+    return true;
+}
+
 bool mjpeg_frame(poppy_sink* s, const uint8_t* frame) {
     const size_t total = poppy_jpeg_frame_bytes(frame);
     const size_t cap420 = poppy_frame_bytes(POPPY_FRAME_JPEG, s->w, s->h);
-    if (total < 4 + 4 || total > poppy_frame_bytes(POPPY_FRAME_JPEG444, s->w, s->h)) return false;      // (the larger of the two capacities)
+    if (total < 4 + 4 || total > poppy_frame_bytes(POPPY_FRAME_JPEG444_OPT, s->w, s->h)) return false;      // (the largest of the four capacities)
     const uint8_t* jfif = frame + 4;
     const size_t n = total - 4, pad = n & 1;
     int w = 0, h = 0, sampling = 0;
     // (the header is read inside the smaller capacity, which every frame's buffer has)
     if (jfif[0] != 0xFF || jfif[1] != 0xD8 || !jpeg_sof0_size(jfif, n < cap420 - 4 ? n : cap420 - 4, &w, &h, &sampling) || w != s->w || h != s->h) return false;
-    if (total > poppy_frame_bytes(sampling == 0x11 ? POPPY_FRAME_JPEG444 : POPPY_FRAME_JPEG, s->w, s->h)) return false;      // a 4:4:4 frame is held to its own capacity
+    // a 4:4:4 frame is held to its own capacity, and a frame on tables of its own (POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT) to the OPT capacity of its sampling
+    const bool opt = !jpeg_dht_is_standard(jfif, n < cap420 - 4 ? n : cap420 - 4);
+    const int held_as = sampling == 0x11 ? (opt ? POPPY_FRAME_JPEG444_OPT : POPPY_FRAME_JPEG444) : (opt ? POPPY_FRAME_JPEG_OPT : POPPY_FRAME_JPEG);
+    if (total > poppy_frame_bytes(held_as, s->w, s->h)) return false;
     // the file with this chunk, the index's chunk header and every index entry stays below 4 GiB
     if (s->at + 8 + n + pad + 8 + 16 * (uint64_t)(s->index.size() / 2 + 1) > 0xffffffffull) return false;
     uint8_t head[8] = {'0', '0', 'd', 'c'};

@@ -119,5 +119,31 @@ inline size_t segment_count(size_t w, size_t h, Sampling s = k420) { return (mcu
 inline unsigned long long frame_capacity(size_t w, size_t h, Sampling s = k420) { return kFrameData + (unsigned long long)segment_count(w, h, s) * kSegmentBytesMax; }
 constexpr size_t kFrameMinBytes = kFrameData + 1 + 2;       // the smallest frame: a byte of entropy data and EOI
 
+// ---- POPPY_FRAME_JPEG_OPT and POPPY_FRAME_JPEG444_OPT: the same files on four Huffman tables built from the frame's own symbol counts (include/poppy_hip.h) ----
+// A frame's symbol counts, laid out as the lookup tables are: dc[t][category], ac[t][run << 4 | size].  The DHT's table k = 0..3 is DC 0, AC 0, DC 1, AC 1:
+// class k & 1, id k >> 1.
+using SymbolCounts = HuffTables;
+constexpr int kCountWords = (int)(sizeof(SymbolCounts) / 4);
+constexpr uint32_t* table_of(HuffTables& h, int k) { return k & 1 ? h.ac[k >> 1] : h.dc[k >> 1]; }
+constexpr int table_symbols(int k) { return k & 1 ? 256 : 16; }
+// the header: POPPY_FRAME_JPEG's up to the DHT marker, the DHT's marker and length, per table 17 bytes and its values, DRI and SOS as they were
+constexpr int kOptHeaderFixed = kOffDht + 4 + (kHeaderBytes - kOffDri);
+constexpr int kOptHeaderMax = kOptHeaderFixed + 2 * (17 + 12) + 2 * (17 + 162);      // a DC table has at most 12 symbols, an AC table 16 x 10 run / size pairs, EOB and ZRL
+static_assert(kOptHeaderFixed == 197 && kOptHeaderMax == kHeaderBytes, "the OPT header is 197 + sum(17 + n) bytes, at most the fixed header's 613");
+// What the device's table build leaves for the coder and the gather: the lookup entries, and per DHT table its n and its bytes (class / id, bits, n values)
+struct OptTables {
+    HuffTables huff;
+    uint32_t n[4];
+    uint8_t dht[4][17 + 256 + 3];
+};
+// a code may have 16 bits whatever the table, and a DC tree has at most 13 leaves (12 categories and the reserved entry): a DC code has at most 12 bits
+constexpr size_t kOptBlockBitsMax = 12 + 11 + 63 * (16 + 10);
+constexpr size_t kOptSegmentBytesMax = POPPY_JPEG_OPT_SEGMENT_BYTES;
+static_assert(kOptSegmentBytesMax == 2 * ((6 * kOptBlockBitsMax * kRestartMcus + 7) / 8) + 2, "POPPY_JPEG_OPT_SEGMENT_BYTES is the header's bound");
+inline unsigned long long opt_frame_capacity(size_t w, size_t h, Sampling s = k420) { return 4 + kOptHeaderMax + (unsigned long long)segment_count(w, h, s) * kOptSegmentBytesMax; }
+constexpr size_t kOptFrameMinBytes = 4 + kOptHeaderFixed + 4 * (17 + 1) + 1 + 2;      // four one-symbol tables, a byte of entropy data, EOI
+// the host coder of either sampling on per-frame tables; returns `total`
+size_t encode_planes_opt(const uint8_t* planes, int w, int h, int quality, Sampling s, uint8_t* dst);
+
 }  // namespace jpeg
 }  // namespace poppy_hip

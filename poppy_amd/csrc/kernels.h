@@ -272,9 +272,19 @@ constexpr size_t kJpegSlotBytes = ((size_t)POPPY_JPEG_SEGMENT_BYTES - 2 + 3) & ~
 constexpr size_t kJpegTableBytes = sizeof(jpeg::QualityTables);
 // `sm` (jpeg_tables.h: Sampling): k420 codes an I420 frame into POPPY_FRAME_JPEG, k444 an I444 frame into POPPY_FRAME_JPEG444; a segment of either is 48 blocks, so
 // the slot is one size, and the pack kernel writes the two header bytes in which the formats differ.
-size_t jpeg_scratch_bytes(int w, int h, jpeg::Sampling sm);
-void launch_jpeg_code(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
-void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, jpeg::Sampling sm, hipStream_t s, hipEvent_t done = nullptr);
+// `opt`: the format on per-frame Huffman tables (POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT), four dispatches on one stream: launch_jpeg_count (every workgroup's
+// symbol counts added into the frame's count tables in the scratch), launch_jpeg_tables (one workgroup: the counts -> the four tables by the header's rule, as
+// lookup entries and DHT bytes, in the scratch; the counts are zero again), then the coder on those tables and the gather with the built DHT.  The slots are
+// kJpegOptSlotBytes apart.  Whoever allocates an OPT scratch clears its counts ONCE (launch_jpeg_counts_clear, on a stream ordered in front of the first frame).
+constexpr size_t kJpegOptSlotBytes = ((size_t)POPPY_JPEG_OPT_SEGMENT_BYTES - 2 + 3) & ~(size_t)3;
+size_t jpeg_scratch_bytes(int w, int h, jpeg::Sampling sm, bool opt);
+void launch_jpeg_count(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
+void launch_jpeg_tables(uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
+void launch_jpeg_code(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, jpeg::Sampling sm, bool opt, hipStream_t s);
+void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, jpeg::Sampling sm, bool opt, hipStream_t s, hipEvent_t done = nullptr);
+hipError_t launch_jpeg_counts_clear(uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
+// the table build alone: `counts` is a frame's count tables (jpeg_tables.h: SymbolCounts) in device memory — zero afterwards —, `built` sizeof(jpeg::OptTables) bytes of it
+void launch_jpeg_table_build(uint32_t* counts, void* built, hipStream_t s);
 
 // a frame on the device (tight BGR) -> its I444 planes, 3 * w * h bytes (kernels_frame_i444.hip; poppy_bgr_to_i444 is the host statement): any w, h >= 1; `done`
 // (optional) rides on the dispatch

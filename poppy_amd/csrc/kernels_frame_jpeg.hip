@@ -19,8 +19,25 @@
 //   k_jpeg_pack  every workgroup sums the lengths in front of its group of segments (each with its 2 marker bytes) and all of them for `total`, as k_gif_pack
 //                does, then moves its segments' bytes to their place and writes RST(k mod 8) behind each, EOI behind the last.  Workgroup 0 writes the header —
 //                the context's bytes for the quality, with width and height filled in — and `total`, into the frame and into a word of mapped pinned host memory.
+//
+// POPPY_FRAME_JPEG_OPT and POPPY_FRAME_JPEG444_OPT (the same files on Huffman tables built from the frame's own symbol counts) are four dispatches, no host round trip:
+//   k_jpeg_count   k_jpeg_code's front end (block_front: samples, DCT, quantiser, DC difference) and its walk over the block's symbols (walk_block), adding every
+//                  symbol into the workgroup's count tables in LDS (ds_add).  A workgroup is four waves, a wave takes a segment at a time and every fourth group of
+//                  the grid's; at the end the workgroup adds its non-zero counts into the frame's table with one integer atomic each (at most kCountGroupsMax
+//                  workgroups on 544 words, of which a frame uses 100 to 300).  Integer adds: the counts are exact whatever the schedule.  The frame's table is
+//                  zero in front of the pass: the scratch's owner clears it once (launch_jpeg_counts_clear), k_jpeg_tables clears what it has read.
+//   k_jpeg_tables  one workgroup, a wave per table (DC 0, AC 0, DC 1, AC 1).  The wave reads its table's counts and stores zeros — a lane holds symbols lane + 64 j, lane 0 the
+//                  reserved entry 256 as well — and runs the rule's merges in registers: the two smallest non-zero counts are the minima of a packed key
+//                  (count << 9 | 511 - symbol: the larger symbol wins a tie), taken with ds_min_u64 on two LDS words, and a merge is every lane's update of
+//                  "symbols whose tree is c1 or c2".  Lengths are counted in LDS, lane 0 runs Annex K.3 from the longest length that occurs, a symbol's place in
+//                  the DHT is the number of smaller (length, symbol) keys, and its canonical code follows from its place.  Out come the lookup entries the coder
+//                  reads and each table's DHT bytes (jpeg_tables.h: OptTables).
+//   k_jpeg_code    as above, its Huffman entries read from the frame's built tables in device memory (template parameter OPT), its bit buffer and scratch slot at
+//                  the OPT bound (a DC code may have 12 bits).
+//   k_jpeg_pack    as above; its OPT form puts the header together from the fixed header's bytes around the built DHT, and the data behind it, wherever it ends.
 #include "kernels.h"
 #include <hip/hip_ext.h>
+#include <algorithm>
 #include <utility>
 
 namespace poppy_hip {
@@ -34,6 +51,8 @@ static_assert(kSegLanes <= 64, "a segment's blocks are the lanes of one wave");
 static_assert(mcu_blocks(k444) * kRestartMcus444 == kSegLanes, "... of either sampling: the bit buffer and the scratch slot below are sized for them");
 constexpr int kBitWords = (int)((6 * kBlockBitsMax * kRestartMcus + 31) / 32) + 2;      // the segment's bits at their bound, the word a code may spill into
 static_assert(kJpegSlotBytes >= 2 * ((6 * kBlockBitsMax * kRestartMcus + 7) / 8), "a slot holds a segment with every byte stuffed");
+constexpr int kOptBitWords = (int)((6 * kOptBlockBitsMax * kRestartMcus + 31) / 32) + 2;      // ... on per-frame tables, where a DC code may have 12 bits
+static_assert(kJpegOptSlotBytes >= 2 * ((6 * kOptBlockBitsMax * kRestartMcus + 7) / 8), "an OPT slot holds a segment with every byte stuffed");
 
 __constant__ HuffTables c_huff = make_huff();
 
@@ -61,17 +80,22 @@ constexpr int zigzag_position(int natural) {
     return -1;
 }
 
-struct CoderLds {
+// what the front end of a segment works in (one per wave)
+struct FrontLds {
     int16_t coef[64][64];                                   // [zig-zag position][lane]
-    uint32_t bits[kBitWords];                               // the segment's bit string, most significant bit of word 0 first
+    uint2 q[2][64];                                         // per table and natural index: the bias 4 Q, the reciprocal of 8 Q
+};
+template <int WORDS>
+struct CoderLds {
+    FrontLds f;
+    uint32_t bits[WORDS];                                   // the segment's bit string, most significant bit of word 0 first
     uint32_t ac[2][256];
     uint32_t dc[2][16];
-    uint2 q[2][64];                                         // per table and natural index: the bias 4 Q, the reciprocal of 8 Q
 };
 
 // coefficient N of the lane's block: quantised, into its zig-zag row; returns it
 template <int N>
-__device__ __forceinline__ int quantise_store(CoderLds& L, int F, int table, int lane) {
+__device__ __forceinline__ int quantise_store(FrontLds& L, int F, int table, int lane) {
     constexpr int pos = zigzag_position(N);
     const uint2 q = L.q[table][N];
     const uint32_t a = (uint32_t)(F < 0 ? -F : F);
@@ -81,13 +105,14 @@ __device__ __forceinline__ int quantise_store(CoderLds& L, int F, int table, int
     return v;
 }
 template <int... N>
-__device__ __forceinline__ int quantise_block(CoderLds& L, const int (&f)[64], int table, int lane, std::integer_sequence<int, N...>) {
+__device__ __forceinline__ int quantise_block(FrontLds& L, const int (&f)[64], int table, int lane, std::integer_sequence<int, N...>) {
     int dc = 0;
     ((N == 0 ? (void)(dc = quantise_store<N>(L, f[N], table, lane)) : (void)quantise_store<N>(L, f[N], table, lane)), ...);
     return dc;
 }
 
-// `len` bits (1..26), right-aligned in `value`, at bit position `at` of the segment
+// `len` bits (1..26: an AC code of at most 16 bits with 10 value bits; a DC code with its value is 11 + 11, on per-frame tables 12 + 11), right-aligned in
+// `value`, at bit position `at` of the segment
 __device__ __forceinline__ void emit_bits(uint32_t* bits, uint32_t at, uint32_t value, int len) {
     const uint32_t word = at >> 5, off = at & 31;
     const unsigned long long x = (unsigned long long)value << (64 - (int)off - len);
@@ -97,41 +122,46 @@ __device__ __forceinline__ void emit_bits(uint32_t* bits, uint32_t at, uint32_t 
 
 __device__ __forceinline__ int category(int v) { return 32 - __clz(v < 0 ? -v : v); }      // (__clz(0) is 32)
 
-// The lane's block as Huffman codes: counted (EMIT false) or ORed into the bit buffer from position `at` on.  Returns the block's bits.
-template <bool EMIT>
-__device__ __forceinline__ uint32_t code_block(CoderLds& L, int lane, int table, int diff, uint32_t at) {
-    uint32_t n = 0;
-    auto put = [&](uint32_t huff, int v, int cat) {          // a symbol's code, then the value's low `cat` bits
-        const int len = (int)(huff & 255) + cat;
-        if (EMIT) emit_bits(L.bits, at + n, (huff >> 8) << cat | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << cat) - 1)), len);
-        n += (uint32_t)len;
-    };
-    { const int cat = category(diff); put(L.dc[table][cat], diff, cat); }
+// The lane's block as its symbols, the one walk of the counting and the coding passes: put(is_dc, symbol, value, category) for the DC category, then per AC
+// symbol (ZRL and EOB: value 0, category 0).
+template <class Put>
+__device__ __forceinline__ void walk_block(const FrontLds& L, int lane, int diff, Put put) {
+    { const int cat = category(diff); put(true, cat, diff, cat); }
     int run = 0;
     for (int k = 1; k < 64; ++k) {
         const int v = L.coef[k][lane];
         if (v == 0) { ++run; continue; }
-        for (; run >= 16; run -= 16) put(L.ac[table][0xF0], 0, 0);
+        for (; run >= 16; run -= 16) put(false, 0xF0, 0, 0);
         const int cat = category(v);
-        put(L.ac[table][run << 4 | cat], v, cat);
+        put(false, run << 4 | cat, v, cat);
         run = 0;
     }
-    if (run) put(L.ac[table][0], 0, 0);
+    if (run) put(false, 0, 0, 0);
+}
+
+// The lane's block as Huffman codes: counted (EMIT false) or ORed into the bit buffer from position `at` on.  Returns the block's bits.
+template <bool EMIT, int WORDS>
+__device__ __forceinline__ uint32_t code_block(CoderLds<WORDS>& L, int lane, int table, int diff, uint32_t at) {
+    uint32_t n = 0;
+    walk_block(L.f, lane, diff, [&](bool is_dc, int symbol, int v, int cat) {      // a symbol's code, then the value's low `cat` bits
+        const uint32_t huff = is_dc ? L.dc[table][symbol] : L.ac[table][symbol];
+        const int len = (int)(huff & 255) + cat;
+        if (EMIT) emit_bits(L.bits, at + n, (huff >> 8) << cat | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << cat) - 1)), len);
+        n += (uint32_t)len;
+    });
     return n;
 }
 
-}  // namespace
-
+// A segment's front end, the lane's block of it: samples -> DCT -> quantiser (the coefficients into L.coef) -> DC difference by shuffle.  Every lane of the wave
+// calls it; L.q holds the quantiser.
+struct BlockFront {
+    bool active;                                            // the lane has a block (the frame's last segment may be short)
+    int table;                                              // 0: luma, 1: chroma
+    int diff;                                               // the DC difference
+};
 template <Sampling S>
-__global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i420, const QualityTables* __restrict__ tables, uint8_t* __restrict__ scratch,
-                                                  uint32_t* __restrict__ lengths, int w, int h, int mw, int n_mcu) {
+__device__ __forceinline__ BlockFront block_front(FrontLds& L, const uint8_t* __restrict__ i420, int seg, int lane, int w, int h, int mw, int n_mcu) {
     constexpr int kBlocks = mcu_blocks(S), kMcus = restart_mcus(S);
-    __shared__ CoderLds L;
-    const int lane = threadIdx.x, seg = blockIdx.x;
-    for (int i = lane; i < 512; i += 64) L.ac[i >> 8][i & 255] = c_huff.ac[i >> 8][i & 255];
-    if (lane < 32) L.dc[lane >> 4][lane & 15] = c_huff.dc[lane >> 4][lane & 15];
-    for (int i = lane; i < 128; i += 64) L.q[i >> 6][i & 63] = make_uint2(tables->bias[i >> 6][i & 63], tables->recip[i >> 6][i & 63]);
-    wave_sync();
     const int first = seg * kMcus, mcus = min(kMcus, n_mcu - first);
     const int m_in = lane / kBlocks, b = lane - kBlocks * m_in, table = S == k444 ? b >= 1 : b >= 4;
     const bool active = m_in < mcus;
@@ -174,7 +204,30 @@ __global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i4
     // (4:4:4: the same block of the MCU before, three lanes down)
     const int from = S == k444 ? lane - 3 : b >= 4 ? lane - 6 : b == 0 ? lane - 3 : lane - 1;
     const int before = __shfl(dc, max(from, 0), 64);
-    const int diff = dc - ((S == k444 || b == 0 || b >= 4) && m_in == 0 ? 0 : before);
+    return BlockFront{active, table, dc - ((S == k444 || b == 0 || b >= 4) && m_in == 0 ? 0 : before)};
+}
+
+}  // namespace
+
+// OPT: the Huffman entries are the frame's built tables (`huff`, device memory: k_jpeg_tables wrote them) instead of the Annex K ones, and the bit buffer and the
+// scratch slots are the OPT bound's
+template <Sampling S, bool OPT>
+__global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i420, const QualityTables* __restrict__ tables, const HuffTables* __restrict__ huff,
+                                                  uint8_t* __restrict__ scratch, uint32_t* __restrict__ lengths, int w, int h, int mw, int n_mcu) {
+    __shared__ CoderLds<OPT ? kOptBitWords : kBitWords> L;
+    const int lane = threadIdx.x, seg = blockIdx.x;
+    if constexpr (OPT) {
+        for (int i = lane; i < 512; i += 64) L.ac[i >> 8][i & 255] = huff->ac[i >> 8][i & 255];
+        if (lane < 32) L.dc[lane >> 4][lane & 15] = huff->dc[lane >> 4][lane & 15];
+    } else {
+        for (int i = lane; i < 512; i += 64) L.ac[i >> 8][i & 255] = c_huff.ac[i >> 8][i & 255];
+        if (lane < 32) L.dc[lane >> 4][lane & 15] = c_huff.dc[lane >> 4][lane & 15];
+    }
+    for (int i = lane; i < 128; i += 64) L.f.q[i >> 6][i & 63] = make_uint2(tables->bias[i >> 6][i & 63], tables->recip[i >> 6][i & 63]);
+    wave_sync();
+    const BlockFront front = block_front<S>(L.f, i420, seg, lane, w, h, mw, n_mcu);
+    const bool active = front.active;
+    const int table = front.table, diff = front.diff;
     const uint32_t n_bits = active ? code_block<false>(L, lane, table, diff, 0) : 0;
     uint32_t incl = n_bits;
     #pragma unroll
@@ -188,7 +241,7 @@ __global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i4
     wave_sync();
     // byte stuffing: byte i of the string goes to i + (the FF bytes in front of it), a zero byte behind every FF
     const uint32_t n_bytes = (total_bits + 7) / 8;
-    uint8_t* dst = scratch + (size_t)seg * kJpegSlotBytes;
+    uint8_t* dst = scratch + (size_t)seg * (OPT ? kJpegOptSlotBytes : kJpegSlotBytes);
     uint32_t n_ff = 0;
     for (uint32_t base = 0; base < n_bytes; base += 64) {
         const uint32_t i = base + lane;
@@ -203,11 +256,164 @@ __global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i4
 }
 
 namespace {
+constexpr int kCountWaves = 4;                              // segments a counting workgroup has in flight
+constexpr int kCountGroupsMax = 256;                        // ... and the most workgroups, so the most that add into one word of the frame's counts
+struct CountLds {
+    FrontLds f[kCountWaves];
+    uint32_t n[kCountWords];                                // the workgroup's counts (jpeg_tables.h: SymbolCounts)
+};
+}
+
+template <Sampling S>
+__global__ void __launch_bounds__(64 * kCountWaves) k_jpeg_count(const uint8_t* __restrict__ i420, const QualityTables* __restrict__ tables, uint32_t* __restrict__ counts,
+                                                                int w, int h, int mw, int n_mcu, int n_seg) {
+    __shared__ CountLds L;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    for (int i = t; i < kCountWords; i += 64 * kCountWaves) L.n[i] = 0;
+    FrontLds& F = L.f[wave];
+    for (int i = lane; i < 128; i += 64) F.q[i >> 6][i & 63] = make_uint2(tables->bias[i >> 6][i & 63], tables->recip[i >> 6][i & 63]);
+    __syncthreads();
+    for (int seg = blockIdx.x * kCountWaves + wave; seg < n_seg; seg += gridDim.x * kCountWaves) {      // (wave-uniform: every lane of the wave makes every trip)
+        const BlockFront front = block_front<S>(F, i420, seg, lane, w, h, mw, n_mcu);
+        uint32_t* dc = L.n + 16 * front.table;
+        uint32_t* ac = L.n + 32 + 256 * front.table;
+        if (front.active) walk_block(F, lane, front.diff, [&](bool is_dc, int symbol, int, int) { atomicAdd(is_dc ? &dc[symbol] : &ac[symbol], 1u); });
+        wave_sync();                                        // (the next trip's coefficients go where this trip's were read)
+    }
+    __syncthreads();
+    for (int i = t; i < kCountWords; i += 64 * kCountWaves) if (const uint32_t n = L.n[i]) atomicAdd(&counts[i], n);
+}
+
+namespace {
+struct BuildLds {
+    uint32_t of_length[4][260];                             // per table: the symbols of each length 0..257
+    uint32_t key[4][256];                                   // ... a symbol's (length before limiting) << 8 | symbol, ~0 without a code
+    unsigned long long pick[4][2];                          // ... the two smallest keys of the merge at hand
+    uint32_t first_code[4][17], first_place[4][17], codes[4][17];      // ... per limited length: its first canonical code, the place of its first symbol, its symbols
+};
+constexpr unsigned long long kNoKey = ~0ull;
+}
+
+// The table rule (include/poppy_hip.h) on a frame's counts, a wave per DHT table; `out`: the lookup entries and the DHT bytes.  The counts are zero afterwards.
+__global__ void __launch_bounds__(256) k_jpeg_tables(uint32_t* __restrict__ counts, OptTables* __restrict__ out) {
+    __shared__ BuildLds L;
+    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n_sym = table_symbols(k);
+    uint32_t* src = counts + (k & 1 ? 32 + 256 * (k >> 1) : 16 * (k >> 1));
+    uint32_t freq[5];
+    int tree[5], len[5];
+    #pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int idx = lane + 64 * j;
+        uint32_t f = 0;
+        if (idx < n_sym) { f = src[idx]; src[idx] = 0; }
+        freq[j] = idx == 256 ? 1u : f;                      // the reserved entry
+        tree[j] = idx; len[j] = 0;
+    }
+    for (int i = lane; i < 260; i += 64) L.of_length[k][i] = 0;
+    volatile unsigned long long* pick_read = L.pick[k];
+    unsigned long long* pick = L.pick[k];
+    for (;;) {
+        // the two smallest keys of the wave (keys are unique): the lane's own pair, then two rounds of ds_min_u64 on one LDS word each — the lanes that hold a
+        // live count add theirs, everyone reads the minimum back; the second round leaves the first one's winner out
+        unsigned long long m1 = kNoKey, m2 = kNoKey;
+        #pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const unsigned long long key = freq[j] ? (unsigned long long)freq[j] << 9 | (unsigned long long)(511 - (lane + 64 * j)) : kNoKey;
+            if (key < m1) { m2 = m1; m1 = key; } else if (key < m2) m2 = key;
+        }
+        if (lane == 0) { pick[0] = kNoKey; pick[1] = kNoKey; }
+        wave_sync();
+        if (m1 != kNoKey) atomicMin(&pick[0], m1);
+        wave_sync();
+        const unsigned long long g1 = pick_read[0];
+        { const unsigned long long mine = m1 == g1 ? m2 : m1; if (mine != kNoKey) atomicMin(&pick[1], mine); }
+        wave_sync();
+        m1 = g1; m2 = pick_read[1];
+        wave_sync();                                        // (both are read before lane 0 resets them)
+        if (m2 == kNoKey) break;                            // (wave-uniform)
+        const int c1 = 511 - (int)(m1 & 511), c2 = 511 - (int)(m2 & 511);
+        const uint32_t f2 = (uint32_t)(m2 >> 9);
+        #pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const int idx = lane + 64 * j;
+            if (tree[j] == c1 || tree[j] == c2) { ++len[j]; tree[j] = c1; }
+            if (idx == c1) freq[j] += f2;
+            if (idx == c2) freq[j] = 0;
+        }
+    }
+    wave_sync();
+    int longest = 0;
+    #pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        if (len[j]) atomicAdd(&L.of_length[k][len[j]], 1u);
+        longest = max(longest, len[j]);
+        if (j < 4) L.key[k][lane + 64 * j] = len[j] ? (uint32_t)len[j] << 8 | (uint32_t)(lane + 64 * j) : ~0u;
+    }
+    #pragma unroll
+    for (int d = 1; d < 64; d <<= 1) longest = max(longest, __shfl_xor(longest, d, 64));
+    wave_sync();
+    if (lane == 0) {
+        uint32_t* bits = L.of_length[k];
+        for (int i = longest; i > 16; --i)                  // Annex K.3
+            while (bits[i] > 0) {
+                int j = i - 2;
+                while (j > 0 && bits[j] == 0) --j;
+                bits[i] -= 2; bits[i - 1] += 1; bits[j + 1] += 2; bits[j] -= 1;
+            }
+        int last = 16;
+        while (last > 1 && bits[last] == 0) --last;
+        if (bits[last]) --bits[last];                       // the reserved entry
+        uint32_t code = 0, place = 0;
+        out->dht[k][0] = (uint8_t)((k & 1) << 4 | k >> 1);
+        for (int l = 1; l <= 16; ++l) {
+            L.first_code[k][l] = code; L.first_place[k][l] = place; L.codes[k][l] = bits[l];
+            out->dht[k][l] = (uint8_t)bits[l];
+            code = (code + bits[l]) << 1; place += bits[l];
+        }
+        out->n[k] = place;
+    }
+    wave_sync();
+    // a symbol's place among the DHT's values: the number of smaller keys
+    uint32_t mine[4], place[4] = {0, 0, 0, 0};
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) mine[j] = L.key[k][lane + 64 * j];
+    for (int i = 0; i < 256; ++i) {
+        const uint32_t other = L.key[k][i];
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) place[j] += other < mine[j];
+    }
+    uint32_t* entries = k & 1 ? out->huff.ac[k >> 1] : out->huff.dc[k >> 1];
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int idx = lane + 64 * j;
+        if (idx >= n_sym) continue;
+        uint32_t entry = 0;
+        if (mine[j] != ~0u) {
+            for (int l = 1; l <= 16; ++l)
+                if (place[j] >= L.first_place[k][l] && place[j] - L.first_place[k][l] < L.codes[k][l]) entry = (L.first_code[k][l] + place[j] - L.first_place[k][l]) << 8 | (uint32_t)l;
+            out->dht[k][17 + place[j]] = (uint8_t)idx;
+        }
+        entries[idx] = entry;
+    }
+}
+
+namespace {
 constexpr int kPackGroup = 8;                               // segments per workgroup
 }
 
+// OPT: the header is the fixed one's bytes around the DHT that k_jpeg_tables built (`opt`), 197 + sum(17 + n) bytes, and the data begins behind it
+template <bool OPT>
 __global__ void __launch_bounds__(256) k_jpeg_pack(const uint8_t* __restrict__ scratch, const uint32_t* __restrict__ lengths, const QualityTables* __restrict__ tables,
-                                                   int n_seg, int w, int h, int sof_sampling, int restart, uint8_t* __restrict__ frame, uint32_t* __restrict__ total_host) {
+                                                   const OptTables* __restrict__ opt, int n_seg, int w, int h, int sof_sampling, int restart, uint8_t* __restrict__ frame,
+                                                   uint32_t* __restrict__ total_host) {
+    constexpr size_t kSlot = OPT ? kJpegOptSlotBytes : kJpegSlotBytes;
+    int dht_bytes[4] = {0, 0, 0, 0}, header_bytes = kHeaderBytes;
+    if constexpr (OPT) {
+        header_bytes = kOptHeaderFixed;
+        for (int k = 0; k < 4; ++k) { dht_bytes[k] = 17 + (int)min(opt->n[k], 256u); header_bytes += dht_bytes[k]; }
+    }
+    const size_t data = 4 + (size_t)header_bytes;           // the frame's offset of the entropy-coded data (not OPT: kFrameData)
     __shared__ unsigned long long s_part[2][4];
     __shared__ uint32_t s_off[kPackGroup + 1];
     const int t = threadIdx.x, first = blockIdx.x * kPackGroup;
@@ -217,8 +423,8 @@ __global__ void __launch_bounds__(256) k_jpeg_pack(const uint8_t* __restrict__ s
     for (int d = 32; d >= 1; d >>= 1) { before += __shfl_xor(before, d, 64); all += __shfl_xor(all, d, 64); }
     if ((t & 63) == 0) { s_part[0][t >> 6] = before; s_part[1][t >> 6] = all; }
     __syncthreads();
-    const size_t base = kFrameData + (size_t)(s_part[0][0] + s_part[0][1] + s_part[0][2] + s_part[0][3]);
-    const size_t total = kFrameData + (size_t)(s_part[1][0] + s_part[1][1] + s_part[1][2] + s_part[1][3]);
+    const size_t base = data + (size_t)(s_part[0][0] + s_part[0][1] + s_part[0][2] + s_part[0][3]);
+    const size_t total = data + (size_t)(s_part[1][0] + s_part[1][1] + s_part[1][2] + s_part[1][3]);
     if (t == 0) {
         uint32_t o = 0;
         for (int k = 0; k < kPackGroup; ++k) { s_off[k] = o; if (first + k < n_seg) o += lengths[first + k] + 2; }
@@ -227,16 +433,25 @@ __global__ void __launch_bounds__(256) k_jpeg_pack(const uint8_t* __restrict__ s
     __syncthreads();
     for (int k = 0; k < kPackGroup && first + k < n_seg; ++k) {
         const int seg = first + k;
-        const uint8_t* src = scratch + (size_t)seg * kJpegSlotBytes;
+        const uint8_t* src = scratch + (size_t)seg * kSlot;
         const uint32_t n = s_off[k + 1] - s_off[k] - 2;
         uint8_t* dst = frame + base + s_off[k];
         for (uint32_t j = t; j < n; j += 256) dst[j] = src[j];
         if (t == 0) { dst[n] = 0xFF; dst[n + 1] = seg == n_seg - 1 ? (uint8_t)0xD9 : (uint8_t)(0xD0 + (seg & 7)); }
     }
     if (blockIdx.x == 0) {
-        for (int i = t; i < kHeaderBytes; i += 256) {
+        for (int at = t; at < header_bytes; at += 256) {
+            int i = at;                                     // the fixed header's byte that stands here
+            if constexpr (OPT) if (at >= kOffDht) {
+                int j = at - kOffDht - 4, table = 0;        // inside the DHT: its marker and length, then the tables' bytes; behind it DRI and SOS
+                const int dht_length = 2 + header_bytes - kOptHeaderFixed;
+                if (j < 0) { frame[4 + at] = j == -4 ? (uint8_t)0xFF : j == -3 ? (uint8_t)0xC4 : j == -2 ? (uint8_t)(dht_length >> 8) : (uint8_t)dht_length; continue; }
+                while (table < 4 && j >= dht_bytes[table]) j -= dht_bytes[table++];
+                if (table < 4) { frame[4 + at] = opt->dht[table][j]; continue; }
+                i = kOffDri + j;
+            }
             const int k = i - kOffSofHeight;                // SOF0's height and width, big-endian; the two bytes of the sampling: component 1's factors, DRI's interval
-            frame[4 + i] = k == 0 ? (uint8_t)(h >> 8) : k == 1 ? (uint8_t)h : k == 2 ? (uint8_t)(w >> 8) : k == 3 ? (uint8_t)w :
+            frame[4 + at] = k == 0 ? (uint8_t)(h >> 8) : k == 1 ? (uint8_t)h : k == 2 ? (uint8_t)(w >> 8) : k == 3 ? (uint8_t)w :
                            i == kOffSofSampling ? (uint8_t)sof_sampling : i == kOffDriLow ? (uint8_t)restart : tables->header[i];
         }
         if (t == 0) {
@@ -247,23 +462,55 @@ __global__ void __launch_bounds__(256) k_jpeg_pack(const uint8_t* __restrict__ s
 }
 
 namespace {
-uint32_t* jpeg_lengths(uint8_t* scratch, size_t n_seg) { return (uint32_t*)(scratch + n_seg * kJpegSlotBytes); }
+size_t slot_bytes(bool opt) { return opt ? kJpegOptSlotBytes : kJpegSlotBytes; }
+uint32_t* jpeg_lengths(uint8_t* scratch, size_t n_seg, bool opt) { return (uint32_t*)(scratch + n_seg * slot_bytes(opt)); }
+// the OPT scratch behind the slots and the lengths: the built tables, then the frame's counts
+int count_groups(size_t n_seg) { return (int)std::min<size_t>((n_seg + kCountWaves - 1) / kCountWaves, (size_t)kCountGroupsMax); }
+OptTables* jpeg_opt_tables(uint8_t* scratch, size_t n_seg) { return (OptTables*)(scratch + ((n_seg * (kJpegOptSlotBytes + 4) + 15) & ~(size_t)15)); }
+uint32_t* jpeg_opt_counts(uint8_t* scratch, size_t n_seg) { return (uint32_t*)(jpeg_opt_tables(scratch, n_seg) + 1); }
+static_assert(sizeof(OptTables) % 16 == 0 && kJpegOptSlotBytes % 4 == 0, "the scratch's parts are aligned");
 }
 
-size_t jpeg_scratch_bytes(int w, int h, Sampling sm) { return segment_count((size_t)w, (size_t)h, sm) * (kJpegSlotBytes + 4) + 16; }
+size_t jpeg_scratch_bytes(int w, int h, Sampling sm, bool opt) {
+    const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
+    if (!opt) return n_seg * (kJpegSlotBytes + 4) + 16;
+    return ((n_seg * (kJpegOptSlotBytes + 4) + 15) & ~(size_t)15) + sizeof(OptTables) + sizeof(SymbolCounts) + 16;
+}
 
-void launch_jpeg_code(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
+void launch_jpeg_count(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
     const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
     const int mw = (w + mcu_side(sm) - 1) / mcu_side(sm);
-    hipLaunchKernelGGL(sm == k444 ? k_jpeg_code<k444> : k_jpeg_code<k420>, dim3((unsigned)n_seg), dim3(64), 0, s, planes, (const QualityTables*)tables, scratch,
-                       jpeg_lengths(scratch, n_seg), w, h, mw, (int)mcu_count((size_t)w, (size_t)h, sm));
+    hipLaunchKernelGGL(sm == k444 ? k_jpeg_count<k444> : k_jpeg_count<k420>, dim3((unsigned)count_groups(n_seg)), dim3(64 * kCountWaves), 0, s, planes,
+                       (const QualityTables*)tables, jpeg_opt_counts(scratch, n_seg), w, h, mw, (int)mcu_count((size_t)w, (size_t)h, sm), (int)n_seg);
 }
 
-void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, hipStream_t s, hipEvent_t done) {
+void launch_jpeg_tables(uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
     const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
-    hipExtLaunchKernelGGL(k_jpeg_pack, dim3((unsigned)((n_seg + kPackGroup - 1) / kPackGroup)), dim3(256), 0, s, nullptr, done, 0, scratch,
-                          jpeg_lengths(const_cast<uint8_t*>(scratch), n_seg), (const QualityTables*)tables, (int)n_seg, w, h, (int)sof_sampling(sm), restart_mcus(sm), frame,
-                          total_host);
+    hipLaunchKernelGGL(k_jpeg_tables, dim3(1), dim3(256), 0, s, jpeg_opt_counts(scratch, n_seg), jpeg_opt_tables(scratch, n_seg));
+}
+
+hipError_t launch_jpeg_counts_clear(uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
+    return hipMemsetAsync(jpeg_opt_counts(scratch, segment_count((size_t)w, (size_t)h, sm)), 0, sizeof(SymbolCounts), s);
+}
+
+void launch_jpeg_table_build(uint32_t* counts, void* built, hipStream_t s) {
+    hipLaunchKernelGGL(k_jpeg_tables, dim3(1), dim3(256), 0, s, counts, (OptTables*)built);
+}
+
+void launch_jpeg_code(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, Sampling sm, bool opt, hipStream_t s) {
+    const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
+    const int mw = (w + mcu_side(sm) - 1) / mcu_side(sm);
+    auto kernel = opt ? (sm == k444 ? k_jpeg_code<k444, true> : k_jpeg_code<k420, true>) : (sm == k444 ? k_jpeg_code<k444, false> : k_jpeg_code<k420, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_seg), dim3(64), 0, s, planes, (const QualityTables*)tables, opt ? &jpeg_opt_tables(scratch, n_seg)->huff : (const HuffTables*)nullptr,
+                       scratch, jpeg_lengths(scratch, n_seg, opt), w, h, mw, (int)mcu_count((size_t)w, (size_t)h, sm));
+}
+
+void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, bool opt, hipStream_t s, hipEvent_t done) {
+    const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
+    uint8_t* sc = const_cast<uint8_t*>(scratch);
+    hipExtLaunchKernelGGL(opt ? k_jpeg_pack<true> : k_jpeg_pack<false>, dim3((unsigned)((n_seg + kPackGroup - 1) / kPackGroup)), dim3(256), 0, s, nullptr, done, 0, scratch,
+                          jpeg_lengths(sc, n_seg, opt), (const QualityTables*)tables, opt ? jpeg_opt_tables(sc, n_seg) : (const OptTables*)nullptr, (int)n_seg, w, h,
+                          (int)sof_sampling(sm), restart_mcus(sm), frame, total_host);
 }
 
 }  // namespace poppy_hip

@@ -18,6 +18,7 @@ static int coded_from_device(poppy_hip_ctx* c, const FormatTraits& t, const uint
     uint8_t *work = nullptr, *frame = nullptr;
     hipError_t e = held.alloc(&work, coding_scratch_bytes(t, W, H));
     if (e == hipSuccess) e = held.alloc(&frame, cap + 16);
+    if (e == hipSuccess) e = prepare_coding_scratch(t, work, W, H, c->stream);
     uint32_t total = 0;
     if (e == hipSuccess) {
         enqueue_coding(t, d_src, d_tables, work, frame, nullptr, W, H, c->stream, nullptr, nullptr);
@@ -78,6 +79,7 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
     int rc = POPPY_OK;                                             // the host statement of the record's steps
     if (t.sequence) rc = pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, pal8.empty() ? tmp.data() : pal8.data());
     else if (t.coder == kCoderGif) rc = poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data());
+    else if (t.coder == kCoderJpeg && t.frame_tables) rc = (t.sampling() == jpeg::k444 ? poppy_bgr_to_jpeg444_opt_frame : poppy_bgr_to_jpeg_opt_frame)(bgr, stride, W, H, c->jpeg_quality, tmp.data());
     else if (t.coder == kCoderJpeg) rc = (t.sampling() == jpeg::k444 ? poppy_bgr_to_jpeg444_frame : poppy_bgr_to_jpeg_frame)(bgr, stride, W, H, c->jpeg_quality, tmp.data());
     else if (t.coder == kCoderPng) rc = (t.runs() ? poppy_bgr_to_png_runs_frame : poppy_bgr_to_png_frame)(bgr, stride, W, H, tmp.data());
     else rc = (t.raster == kRasterPal8 ? poppy_bgr_to_pal8 : poppy_bgr_to_i420)(bgr, stride, W, H, tmp.data());
@@ -175,7 +177,7 @@ int poppy_hip_pal8_to_gif_frame(poppy_hip_ctx* c, const uint8_t* pal8, int W, in
     return rc;
 }
 
-// the body of poppy_hip_i420_to_jpeg_frame and poppy_hip_i444_to_jpeg_frame: the planes of format `fmt`'s sampling up, the two kernels, `total` bytes down
+// the body of poppy_hip_i420_to_jpeg_frame, poppy_hip_i444_to_jpeg_frame and their OPT forms: the planes of format `fmt`'s sampling up, its kernels, `total` bytes down
 static int jpeg_code_host_planes(poppy_hip_ctx* c, int fmt, const uint8_t* i420, int W, int H, int quality, uint8_t* dst) {
     if (!c) return POPPY_E_ARG;
     if (!i420 || !dst || W <= 0 || H <= 0 || quality < 1 || quality > 100) return fail(c, POPPY_E_ARG, "bad arguments");
@@ -203,6 +205,43 @@ int poppy_hip_i420_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i420, int W, i
 
 int poppy_hip_i444_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i444, int W, int H, int quality, uint8_t* dst) {
     return jpeg_code_host_planes(c, POPPY_FRAME_JPEG444, i444, W, H, quality, dst);
+}
+
+int poppy_hip_i420_to_jpeg_opt_frame(poppy_hip_ctx* c, const uint8_t* i420, int W, int H, int quality, uint8_t* dst) {
+    return jpeg_code_host_planes(c, POPPY_FRAME_JPEG_OPT, i420, W, H, quality, dst);
+}
+
+int poppy_hip_i444_to_jpeg_opt_frame(poppy_hip_ctx* c, const uint8_t* i444, int W, int H, int quality, uint8_t* dst) {
+    return jpeg_code_host_planes(c, POPPY_FRAME_JPEG444_OPT, i444, W, H, quality, dst);
+}
+
+// the table-build kernel alone on one table's counts (they stand as AC table 0 of a frame's count tables, the other three tables empty): what
+// poppy_jpeg_optimal_table gives, with its refusals
+int poppy_hip_jpeg_optimal_table(poppy_hip_ctx* c, const uint32_t* counts, uint8_t* bits, uint8_t* vals, int* n_vals) {
+    if (!c) return POPPY_E_ARG;
+    if (!counts || !bits || !vals || !n_vals) return fail(c, POPPY_E_ARG, "bad arguments");
+    uint64_t sum = 0;
+    for (int i = 0; i < 256; ++i) sum += counts[i];
+    if (sum == 0 || sum >= 0xffffffffull) return fail(c, POPPY_E_ARG, "the counts are all zero, or their sum is 2^32 - 1 or more");
+    HIPCHK(c, hipSetDevice(c->device));
+    jpeg::SymbolCounts frame_counts{};
+    memcpy(frame_counts.ac[0], counts, sizeof frame_counts.ac[0]);
+    jpeg::OptTables built;
+    CallBuffers held;
+    uint8_t *d_counts = nullptr, *d_built = nullptr;
+    HIPCHK(c, held.alloc(&d_counts, sizeof frame_counts));
+    HIPCHK(c, held.alloc(&d_built, sizeof built));
+    hipError_t e = hipMemcpyAsync(d_counts, &frame_counts, sizeof frame_counts, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { launch_jpeg_table_build((uint32_t*)d_counts, d_built, c->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(&built, d_built, sizeof built, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go (`held`, at the return)
+    if (e == hipSuccess) e = e_sync;
+    if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("JPEG table build: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    if (built.n[1] < 1 || built.n[1] > 256) return fail(c, POPPY_E_DEVICE, "the built table's size is outside its bounds");
+    memcpy(bits, built.dht[1] + 1, 16);
+    memcpy(vals, built.dht[1] + 17, built.n[1]);
+    *n_vals = (int)built.n[1];
+    return POPPY_OK;
 }
 
 // a host frame up (upload_host_bgr), the six PNG kernels, `total` bytes down, on buffers that live for the call

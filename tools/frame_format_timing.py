@@ -14,9 +14,9 @@ PAL8_SEQ: pal8_seq_hist per frame, pal8_seq_build per sequence, frame_format = t
 jpeg_code and jpeg_pack; JPEG444: frame_format = the I444 conversion, then the same two; PNG and PNG_RUNS: png_filter, png_cost, png_scan, png_pack, png_crc, png_finish — under PNG_RUNS png_cost and png_pack are the run-aware kernels), and for the coded formats the median length of the 60 chained frames of the synthetic, of a textured and of a photograph pair (the golden 720 x 405 photographs, tiled; coded_bytes_median, with the coders' times on those frames; JPEG at --jpeg-quality).  Under PAL8_SEQ a pair's (a call's) frames are handed over after its last
 frame.
 
-    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif,jpeg,jpeg444,png,png_runs --scales 1,2 --kernel-scales 2,4
+    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif,jpeg,jpeg444,png,png_runs,jpeg_opt,jpeg444_opt --scales 1,2 --kernel-scales 2,4
                                          --size 1280x720 --size-4k 1920x1080]
---formats leaves formats out (a library older than GIF: bgr,i420,pal8,pal8_seq; older than JPEG: without jpeg; older than JPEG444: without jpeg444; older than PNG: without png; older than PNG_RUNS: without png_runs).  --scales adds every format again per scale above 1 (poppy_hip_set_frame_scale: the
+--formats leaves formats out (a library older than GIF: bgr,i420,pal8,pal8_seq; older than JPEG: without jpeg; older than JPEG444: without jpeg444; older than PNG: without png; older than PNG_RUNS: without png_runs; older than JPEG_OPT: without jpeg_opt,jpeg444_opt — the formats on per-frame Huffman tables, whose marks are jpeg_count, jpeg_tables, jpeg_code, jpeg_pack).  --scales adds every format again per scale above 1 (poppy_hip_set_frame_scale: the
 column "gif@2" is GIF at scale 2), alternated with the others in the same process; --kernel-scales adds k_bgr_downscale's own time (timing mode 1: frame_scale) under BGR
 at 1080p and 4K for those factors.  --size OWxOH adds every format again at that size (poppy_hip_set_frame_size: the column "i420@1280x720"); the 4K rows of such a
 column use --size-4k (default: --size), and its timing mode 1 entry has the resize kernel's time (frame_resize).  GIF's d2h_ceiling entry is its CAPACITY (poppy_frame_bytes); a frame's copy moves its own
@@ -35,7 +35,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poppy_amd import capi, synth  # noqa: E402
 
 ALL_FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420), ("pal8", capi.FRAME_PAL8), ("pal8_seq", capi.FRAME_PAL8_SEQ), ("gif", capi.FRAME_GIF), ("jpeg", capi.FRAME_JPEG),
-            ("jpeg444", capi.FRAME_JPEG444), ("png", getattr(capi, "FRAME_PNG", 1024)), ("png_runs", getattr(capi, "FRAME_PNG_RUNS", 2048)))
+            ("jpeg444", capi.FRAME_JPEG444), ("png", getattr(capi, "FRAME_PNG", 1024)), ("png_runs", getattr(capi, "FRAME_PNG_RUNS", 2048)),
+            ("jpeg_opt", getattr(capi, "FRAME_JPEG_OPT", 4096)), ("jpeg444_opt", getattr(capi, "FRAME_JPEG444_OPT", 8192)))
 
 
 PNG_MARKS = ("png_filter", "png_cost", "png_scan", "png_pack", "png_crc", "png_finish")
@@ -86,7 +87,7 @@ def main():
     ap.add_argument("--steps-4k", type=int, default=3)
     ap.add_argument("--contexts", type=int, default=6)
     ap.add_argument("--rows", default="pool_1080p,pool_4k,job480,chained,chained_frame,d2h_ceiling")
-    ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq,gif,jpeg,jpeg444,png,png_runs")
+    ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq,gif,jpeg,jpeg444,png,png_runs,jpeg_opt,jpeg444_opt")
     ap.add_argument("--jpeg-quality", type=int, default=capi.JPEG_QUALITY_DEFAULT)
     ap.add_argument("--scales", default="1")
     ap.add_argument("--kernel-scales", default="")
@@ -129,7 +130,7 @@ def main():
     pool4 = capi.Pool([0], contexts_per_device=a.contexts, number_of_frames=60) if "pool_4k" in rows else None
     ctx4 = capi.Context(0, number_of_frames=60) if "chained_4k" in rows else None
     ctx = capi.Context(0, number_of_frames=60)
-    if {"jpeg", "jpeg444"} & set(a.formats.split(",")):
+    if {"jpeg", "jpeg444", "jpeg_opt", "jpeg444_opt"} & set(a.formats.split(",")):
         for target in (pool, pool4, ctx4, ctx):
             if target:
                 target.set_jpeg_quality(a.jpeg_quality)
@@ -200,7 +201,7 @@ def main():
             ctx.reset(); ctx.render_many_counted(shapes, chain=True)
             t = {n: (ms, k) for n, ms, k in ctx.timing_summary()}
             ctx.set_timing(0)
-            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_scale", "frame_resize", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build", "gif_lzw", "gif_pack", "jpeg_code", "jpeg_pack") + PNG_MARKS}
+            out["timing_mode1_us"][f"{w}x{h}_{name}"] = {n: round(ms / k * 1e3, 2) for n, (ms, k) in t.items() if n in ("unsharp", "frame_scale", "frame_resize", "frame_format", "pal8_hist", "pal8_build", "pal8_seq_hist", "pal8_seq_build", "gif_lzw", "gif_pack", "jpeg_count", "jpeg_tables", "jpeg_code", "jpeg_pack") + PNG_MARKS}
     # the coded formats' frame lengths: the 60 chained frames of the synthetic pair and of a textured pair, collected
     out["coded_bytes_median"] = {}
     coded = tuple(c for c in FMTS if c[1][0] in capi.FRAMES_CODED and c[1][1] == 1)
@@ -217,7 +218,7 @@ def main():
                 ctx.pair_begin_device(u.data_ptr(), v.data_ptr(), w, h)
                 ctx.set_timing(1)
                 ctx.reset(); ctx.render_many(shapes, chain=True, write=lambda f: sizes.append(int(f.size)))
-                t = {n: round(ms / k * 1e3, 2) for n, ms, k in ctx.timing_summary() if n in ("gif_lzw", "gif_pack", "jpeg_code", "jpeg_pack") + PNG_MARKS}
+                t = {n: round(ms / k * 1e3, 2) for n, ms, k in ctx.timing_summary() if n in ("gif_lzw", "gif_pack", "jpeg_count", "jpeg_tables", "jpeg_code", "jpeg_pack") + PNG_MARKS}
                 ctx.set_timing(0)
                 out["coded_bytes_median"][f"{w}x{h}_{name}_{pair}"] = {"bytes": int(statistics.median(sizes)), "kernels_us": t}
     for p in (pool, pool4, ctx4):
