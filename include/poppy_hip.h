@@ -411,7 +411,41 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * poppy_bgr_to_png_runs_frame is the host statement (dst: the capacity; the refusals are poppy_bgr_to_png_frame's).  poppy_png_runs_table gives table k's 286
  * lengths and its header bit string as poppy_png_table does.  poppy_png_frame_bytes reads `total` of either format.  poppy_hip_bgr_to_png_runs_frame codes a host
  * frame on the context's GPU as poppy_hip_bgr_to_png_frame does: the same bytes as the host statement.  The format applies wherever POPPY_FRAME_PNG applies and
- * stays BGR wherever that stays BGR.  */
+ * stays BGR wherever that stays BGR.
+ *
+ * POPPY_FRAME_PNG_OPT: POPPY_FRAME_PNG_RUNS with a ninth candidate per segment, a code built from the segment's OWN symbol counts, in which a symbol that does
+ * not occur has no code: a run-free segment does not pay for length symbols it never emits, and a flat one does not pay for literals.  Its value is 16384; 16383
+ * and 16385 stay unknown in both enums; there is no sink value of its own: POPPY_SINK_PNG takes the frames and poppy_png_frame_bytes reads `total`.  The format is
+ * POPPY_FRAME_PNG_RUNS word for word — layout and offsets, File, Filtered stream, Segments, Tokens (runs never cross a cut, POPPY_PNG_RUN_MIN), 78 01, blocks that
+ * are not byte-aligned, BFINAL in the last, Adler-32, one IDAT, IEND, Limits — with these changes only:
+ *   Tables.  Per segment, count[s] for s in 0..285 is how often the segment's tokens hold literal or length symbol s, and count[256] = 1, so at least two symbols
+ *      have a count.  The own table's lengths are poppy_png_optimal_lengths(count, 286, 15), the rule below; codes are deflate's canonical codes by (length, symbol).
+ *      The rule, poppy_jpeg_optimal_table's merges without the reserved entry, for n symbols and a limit of 7 or 15:
+ *      1. Every symbol with a count is its own tree.
+ *      2. Until there is no c2: c1 is the smallest non-zero count, the largest index among equals; c2 the same among the rest; count[c1] += count[c2],
+ *         count[c2] = 0; every symbol of both trees gets one bit longer; c2's tree joins c1's.
+ *      3. Count the symbols of each depth.
+ *      4. T.81 Annex K.3 from the longest depth down to limit + 1, with `limit` in the place of 16.
+ *      5. The symbols with a count, ordered by their depth before step 4 and then by symbol value, take the adjusted lengths in ascending order; every other
+ *         symbol gets 0.  A single symbol with a count gets length 1.
+ *      A segment has at most 8193 tokens, so depths above 15 do occur (counts 1, 1, 2, 3, 5, 8, ...: depth 16 from a sum of 4179).
+ *   Block header.  The eight tables keep their committed headers.  An own header is BFINAL, BTYPE = 10, HLIT = max(257, highest symbol with a length + 1) - 257,
+ *      HDIST = 0 with the one distance code of length 1 (even when the block has no match), HCLEN, the code-length code's lengths in RFC 1951's order (16, 17, 18,
+ *      0, 8, 7, ...; trailing zeros trimmed, at least 4), then the HLIT + 258 lengths as ONE sequence, lit/len first and then the distance code's 1, cut into
+ *      maximal runs of equal values.  A run of r zeros: while r >= 11, symbol 18 with min(r, 138); then symbol 17 with r if r >= 3; else r zeros.  A run of r
+ *      equal non-zero lengths: the length once; while the rest is >= 3, symbol 16 with min(rest, 6); what is left as itself.  The code-length code is
+ *      poppy_png_optimal_lengths at limit 7 on the counts of the sequence's entries over the 19 symbols, canonical codes again.  An own header is at most
+ *      17 + 19 * 3 + 287 * 7 = 2083 bits: no entry costs more than 7 bits per length it covers.
+ *   Table choice.  Nine candidates: POPPY_FRAME_PNG_RUNS' tables 0..7 and 8, the own table.  A candidate's cost is its header bits + the tokens' codes + the
+ *      matches' extra and distance bits + its end-of-block code; the smallest wins, ties go to the lowest index.
+ *   Capacity.  Every block is therefore no longer than POPPY_FRAME_PNG_RUNS' block of the same segment: total(PNG_OPT) <= total(PNG_RUNS) for every frame, and
+ *      poppy_frame_bytes(POPPY_FRAME_PNG_OPT, w, h) is POPPY_FRAME_PNG_RUNS' capacity.
+ * poppy_bgr_to_png_opt_frame is the host statement (dst: the capacity; the refusals are poppy_bgr_to_png_frame's).  poppy_png_optimal_lengths is the length rule
+ * alone, host only, integers only: `lengths` receives n_symbols bytes; POPPY_E_ARG for a null pointer, n_symbols outside 1..286, a limit other than 7 or 15,
+ * counts that are all zero, a sum of 2^32 or more, and more symbols with a count than 2^limit (no code of that length holds them).
+ * poppy_hip_bgr_to_png_opt_frame codes a host frame on the context's GPU as poppy_hip_bgr_to_png_runs_frame does, and poppy_hip_png_optimal_lengths runs the
+ * device's length build alone on given counts, as poppy_hip_jpeg_optimal_table does: the same bytes as the host statements, with their refusals.  The format
+ * applies wherever POPPY_FRAME_PNG_RUNS applies and stays BGR wherever that stays BGR.  */
 #define POPPY_PAL8_MAX_PIXELS (1 << 24)
 #define POPPY_PAL8_SEQ_MAX_PIXELS (1ull << 32)
 #define POPPY_GIF_SEGMENT_PIXELS 2048
@@ -429,7 +463,7 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
 #define POPPY_PNG_RUN_MIN 8
 enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128, POPPY_FRAME_JPEG = 256,
        POPPY_FRAME_JPEG444 = 512, POPPY_FRAME_PNG = 1024, POPPY_FRAME_PNG_RUNS = 2048, POPPY_FRAME_JPEG_OPT = 4096,
-       POPPY_FRAME_JPEG444_OPT = 8192 };
+       POPPY_FRAME_JPEG444_OPT = 8192, POPPY_FRAME_PNG_OPT = 16384 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
@@ -466,6 +500,10 @@ int poppy_hip_bgr_to_png_frame(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t st
 int poppy_png_runs_table(int k, uint8_t lengths[286], uint8_t* header_bits, int* n_header_bits);
 int poppy_bgr_to_png_runs_frame(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 int poppy_hip_bgr_to_png_runs_frame(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_png_optimal_lengths(const uint32_t* counts, int n_symbols, int limit, uint8_t* lengths);
+int poppy_bgr_to_png_opt_frame(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_hip_bgr_to_png_opt_frame(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
+int poppy_hip_png_optimal_lengths(poppy_hip_ctx* ctx, const uint32_t* counts, int n_symbols, int limit, uint8_t* lengths);
 /* Scaled hand-off: frames rendered at the pair's resolution and handed to the writer scaled down by a whole factor, on the GPU, in front of the format
  * conversion.  The pair's resolution decides the keypoints, the mesh and the morph; the scale only decides what crosses the link and what the writer gets.
  *   The rule.  A factor s is a whole number from 1 to POPPY_FRAME_SCALE_MAX = 8; 1, the default, is the identity.  A width x height BGR frame becomes
@@ -975,7 +1013,7 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * the sampling byte 0x11 is held to POPPY_FRAME_JPEG444's capacity, any other to POPPY_FRAME_JPEG's; nothing else about the sink differs.  POPPY_FRAME_JPEG_OPT
  * and POPPY_FRAME_JPEG444_OPT frames are taken in the same mix: a frame whose DHT segment is not byte for byte the Annex K one is held to the OPT capacity of its
  * sampling, every other frame as before.
- * PNG: one PNG file per frame from POPPY_FRAME_PNG and POPPY_FRAME_PNG_RUNS frames as they come, in any mix (a PNG file does not say who coded it); `path` follows
+ * PNG: one PNG file per frame from POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS and POPPY_FRAME_PNG_OPT frames as they come, in any mix (a PNG file does not say who coded it); `path` follows
  * PPM's %d rule exactly.  The file holds the frame's bytes 4 .. total as they are.  The stride must be 0, bytes 4..11 the PNG signature, IHDR must name the sink's
  * width and height, and `total` must be inside the larger of the two formats' capacities.  A frame
  * of any other format fails this sink, and a PNG frame fails every other sink.

@@ -28,7 +28,8 @@ WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int,
 FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444 = 0, 1, 8, 16, 64, 128, 256, 512
 FRAME_PNG, FRAME_PNG_RUNS = 1024, 2048
 FRAME_JPEG_OPT, FRAME_JPEG444_OPT = 4096, 8192
-FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444, FRAME_PNG, FRAME_PNG_RUNS, FRAME_JPEG_OPT, FRAME_JPEG444_OPT)      # a frame whose length its first four bytes hold
+FRAME_PNG_OPT = 16384
+FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444, FRAME_PNG, FRAME_PNG_RUNS, FRAME_JPEG_OPT, FRAME_JPEG444_OPT, FRAME_PNG_OPT)      # a frame whose length its first four bytes hold
 JPEG_QUALITY_DEFAULT = 90
 SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED, SINK_GIF_GLOBAL_CODED, SINK_MJPEG = 0, 1, 2, 3, 8, 16, 64, 128, 256
 SINK_PNG = 1024
@@ -60,6 +61,7 @@ SYMBOLS = [
     "poppy_hip_i420_to_jpeg_opt_frame", "poppy_hip_i444_to_jpeg_opt_frame", "poppy_hip_jpeg_optimal_table",
     "poppy_png_frame_bytes", "poppy_png_table", "poppy_bgr_to_png_frame", "poppy_hip_bgr_to_png_frame",
     "poppy_png_runs_table", "poppy_bgr_to_png_runs_frame", "poppy_hip_bgr_to_png_runs_frame",
+    "poppy_png_optimal_lengths", "poppy_bgr_to_png_opt_frame", "poppy_hip_bgr_to_png_opt_frame", "poppy_hip_png_optimal_lengths",
     "poppy_hip_set_frame_scale", "poppy_hip_pool_set_frame_scale", "poppy_frame_scaled_size", "poppy_bgr_downscale", "poppy_hip_bgr_downscale",
     "poppy_hip_set_frame_size", "poppy_hip_pool_set_frame_size", "poppy_frame_fit_size", "poppy_bgr_resize_area", "poppy_hip_bgr_resize_area",
     "poppy_hip_bgr_resize_area_form",
@@ -231,6 +233,10 @@ def lib():
         L.poppy_png_runs_table.argtypes = [i, vp, vp, vp]
         L.poppy_bgr_to_png_runs_frame.argtypes = [vp, sz, i, i, vp]
         L.poppy_hip_bgr_to_png_runs_frame.argtypes = [vp, vp, sz, i, i, vp]
+        L.poppy_png_optimal_lengths.argtypes = [vp, i, i, vp]
+        L.poppy_bgr_to_png_opt_frame.argtypes = [vp, sz, i, i, vp]
+        L.poppy_hip_bgr_to_png_opt_frame.argtypes = [vp, vp, sz, i, i, vp]
+        L.poppy_hip_png_optimal_lengths.argtypes = [vp, vp, i, i, vp]
         L.poppy_hip_set_frame_scale.argtypes = [vp, i]
         L.poppy_hip_pool_set_frame_scale.argtypes = [vp, i]
         L.poppy_frame_scaled_size.argtypes = [i, i, i, vp, vp]
@@ -336,7 +342,7 @@ def jpeg_frame_bytes(frame):
 
 
 def png_frame_bytes(frame):
-    """Host-only: `total` of a FRAME_PNG or FRAME_PNG_RUNS frame, its length in bytes (poppy_png_frame_bytes: the first four bytes, little-endian)."""
+    """Host-only: `total` of a FRAME_PNG, FRAME_PNG_RUNS or FRAME_PNG_OPT frame, its length in bytes (poppy_png_frame_bytes: the first four bytes, little-endian)."""
     return coded_frame_bytes(frame, "png")
 
 
@@ -515,6 +521,29 @@ def bgr_to_png_runs_frame(bgr, row_pad=0, whole=False):
     return _png_frame(lib().poppy_bgr_to_png_runs_frame, "bgr_to_png_runs_frame", bgr, row_pad, None, whole, FRAME_PNG_RUNS)
 
 
+def bgr_to_png_opt_frame(bgr, row_pad=0, whole=False):
+    """Host-only: the FRAME_PNG_OPT frame of an HxWx3 BGR frame (poppy_bgr_to_png_opt_frame): bgr_to_png_runs_frame's file with every segment coded on the table
+    that is shortest for it, the eight fixed ones or one built from its own symbol counts; row_pad and whole as there (the capacity is FRAME_PNG_RUNS's)."""
+    return _png_frame(lib().poppy_bgr_to_png_opt_frame, "bgr_to_png_opt_frame", bgr, row_pad, None, whole, FRAME_PNG_OPT)
+
+
+def _optimal_lengths(call, counts, limit, what, chk=None):
+    a = np.ascontiguousarray(counts, np.uint32).ravel()
+    lengths = np.zeros(max(a.size, 1), np.uint8)
+    rc = call(_p(a), int(a.size), int(limit), _p(lengths))
+    if chk:
+        chk(rc, what)
+    elif rc:
+        raise PoppyError(f"poppy_{what}: {rc}")
+    return lengths[:a.size]
+
+
+def png_optimal_lengths(counts, limit=15):
+    """Host-only: the code lengths of 1..286 symbol counts by FRAME_PNG_OPT's rule (poppy_png_optimal_lengths), none above `limit` (7 or 15); 0 for a symbol
+    without a count."""
+    return _optimal_lengths(lib().poppy_png_optimal_lengths, counts, limit, "png_optimal_lengths")
+
+
 def _gif_frames(call, frames, row_pad, frame_pad, chk=None):
     a, stride, frame_stride, n, w, h = _padded_frames(frames, row_pad, frame_pad)
     out = np.empty((n, max(frame_bytes(FRAME_GIF_SEQ, w, h), 4)), np.uint8)
@@ -604,7 +633,7 @@ def pal8_to_bgr(frame, w, h):
 
 
 def _frame_view(ptr, w, h, stride, fmt):
-    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF, GIF_SEQ, JPEG, JPEG444, PNG and PNG_RUNS.  A view: valid during the callback."""
+    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF, GIF_SEQ, JPEG, JPEG444, PNG, PNG_RUNS and PNG_OPT.  A view: valid during the callback."""
     if fmt in FRAMES_CODED:                                                      # a coded frame: its own length, not the capacity (every coded format keeps it in its first four bytes)
         return np.ctypeslib.as_array(ptr, shape=(int(lib().poppy_gif_frame_bytes(ptr)),))
     if fmt in (FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ):
@@ -1133,7 +1162,8 @@ class Context:
         FRAME_JPEG444: the same with full-resolution chroma (4:4:4), coded from the frame's I444 planes.
         FRAME_JPEG_OPT, FRAME_JPEG444_OPT: the same files on Huffman tables built on the GPU from each frame's own symbols: the same pixels in fewer bytes.
         FRAME_PNG: every frame one PNG file, lossless, coded on the GPU; flat arrays of each frame's own length (png_frame_bytes).
-        FRAME_PNG_RUNS: the same with runs of equal bytes coded as matches: several times smaller on frames with flat or smooth regions."""
+        FRAME_PNG_RUNS: the same with runs of equal bytes coded as matches: several times smaller on frames with flat or smooth regions.
+        FRAME_PNG_OPT: FRAME_PNG_RUNS with every segment on the shortest of the eight tables and one built on the GPU from its own symbols: never larger."""
         self._chk(lib().poppy_hip_set_frame_format(self.h, int(fmt)), "set_frame_format")
         self.frame_format = int(fmt)
 
@@ -1160,6 +1190,15 @@ class Context:
         """The FRAME_PNG_RUNS frame of an HxWx3 BGR frame, coded on this context's GPU (poppy_hip_bgr_to_png_runs_frame): the bytes of the host's
         bgr_to_png_runs_frame.  row_pad and whole as in bgr_to_png_frame."""
         return _png_frame(lambda *args: lib().poppy_hip_bgr_to_png_runs_frame(self.h, *args), "bgr_to_png_runs_frame", bgr, row_pad, self._chk, whole, FRAME_PNG_RUNS)
+
+    def bgr_to_png_opt_frame(self, bgr, row_pad=0, whole=False):
+        """The FRAME_PNG_OPT frame of an HxWx3 BGR frame, coded on this context's GPU (poppy_hip_bgr_to_png_opt_frame): the bytes of the host's
+        bgr_to_png_opt_frame.  row_pad and whole as in bgr_to_png_frame."""
+        return _png_frame(lambda *args: lib().poppy_hip_bgr_to_png_opt_frame(self.h, *args), "bgr_to_png_opt_frame", bgr, row_pad, self._chk, whole, FRAME_PNG_OPT)
+
+    def png_optimal_lengths(self, counts, limit=15):
+        """The length-build routine of the FRAME_PNG_OPT coder alone on 1..286 symbol counts (poppy_hip_png_optimal_lengths): what the host's png_optimal_lengths gives."""
+        return _optimal_lengths(lambda *args: lib().poppy_hip_png_optimal_lengths(self.h, *args), counts, limit, "png_optimal_lengths", self._chk)
 
     def i420_to_jpeg_opt_frame(self, i420, w, h, quality=JPEG_QUALITY_DEFAULT):
         """The FRAME_JPEG_OPT frame of a flat I420 frame, coded on this context's GPU (poppy_hip_i420_to_jpeg_opt_frame: upload, the four kernels, download): the

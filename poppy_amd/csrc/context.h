@@ -11,7 +11,7 @@
 //   rccl_comm.cpp     the RCCL loader and a context's communicator (rccl_comm.h, comm_guard.h): the two collectives, the abort, the pair state's broadcast, export and import
 //   sharded_setup.cpp the pair set-up spread over ranks, as named stages (shard_protocol.h: roles and the keypoint hand-off; local_hub.h: the in-process transport)
 //   morph_sharded.cpp one job over N devices;  pool.cpp: pools of contexts, the set-up gate, batches of pairs
-//   frame_plan.cpp    host-side planning of a frame;  frame_pal8.cpp, frame_gif.cpp, frame_jpeg.cpp (jpeg_tables.h: the tables it shares with kernels_frame_jpeg.hip), frame_png.cpp and frame_png_runs.cpp (frame_png.h; png_tables.h and png_runs_tables.h, shared with kernels_frame_png.hip), frame_i444.cpp, frame_scale.cpp, frame_resize.cpp, frame_sink.cpp: the host side of the writer formats, the scaled and resized hand-off and the file sinks
+//   frame_plan.cpp    host-side planning of a frame;  frame_pal8.cpp, frame_gif.cpp, frame_jpeg.cpp (jpeg_tables.h: the tables it shares with kernels_frame_jpeg.hip), frame_png.cpp, frame_png_runs.cpp and frame_png_opt.cpp (frame_png.h; png_tables.h, png_runs_tables.h and png_opt.h, shared with kernels_frame_png.hip), frame_i444.cpp, frame_scale.cpp, frame_resize.cpp, frame_sink.cpp: the host side of the writer formats, the scaled and resized hand-off and the file sinks
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "foreground.h"

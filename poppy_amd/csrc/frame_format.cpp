@@ -7,7 +7,7 @@ static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned l
 constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 2^24 pixels";
 constexpr const char* kGifSizeMsg = "POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 65535 pixels in width and height";
 constexpr const char* kJpegSizeMsg = "POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444 and their OPT forms take frames of at most 65535 pixels in width and height whose capacity stays below 2^32 bytes";
-constexpr const char* kPngSizeMsg = "POPPY_FRAME_PNG and POPPY_FRAME_PNG_RUNS take frames whose capacity stays below 2^31 bytes";
+constexpr const char* kPngSizeMsg = "POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS and POPPY_FRAME_PNG_OPT take frames whose capacity stays below 2^31 bytes";
 constexpr const char* kSeqSizeMsg = "POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ take sequences of fewer than 2^32 pixels in all";
 
 const char* format_refuses(int fmt, int W, int H) {
@@ -88,7 +88,7 @@ static void free_slot_coded(SlotFormat& f) {
 static uint8_t* SlotFormat::* const kRasterBuffer[] = {nullptr, &SlotFormat::i420, &SlotFormat::i444, &SlotFormat::pal8};
 
 size_t coding_scratch_bytes(const FormatTraits& t, int W, int H) {
-    return t.coder == kCoderJpeg ? jpeg_scratch_bytes(W, H, t.sampling(), t.frame_tables) : t.coder == kCoderPng ? png_scratch_bytes(W, H, t.runs()) : gif_scratch_bytes(W, H);
+    return t.coder == kCoderJpeg ? jpeg_scratch_bytes(W, H, t.sampling(), t.frame_tables) : t.coder == kCoderPng ? png_scratch_bytes(W, H, t.variant) : gif_scratch_bytes(W, H);
 }
 
 // what a coder's scratch holds before its first frame: under JPEG on per-frame tables the frame's symbol counts, zero (the table build leaves them zero again)
@@ -193,25 +193,25 @@ static void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8
     if (tm) tm->mark("jpeg_pack");
 }
 
-static void enqueue_png_coding(bool runs, const uint8_t* bgr, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
-    launch_png_filter(bgr, scratch, W, H, runs, s);
+static void enqueue_png_coding(int variant, const uint8_t* bgr, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
+    launch_png_filter(bgr, scratch, W, H, variant, s);
     if (tm) tm->mark("png_filter");
-    launch_png_cost(scratch, W, H, runs, s);
+    launch_png_cost(scratch, W, H, variant, s);
     if (tm) tm->mark("png_cost");
-    launch_png_scan(scratch, frame, W, H, runs, s);
+    launch_png_scan(scratch, frame, W, H, variant, s);
     if (tm) tm->mark("png_scan");
-    launch_png_pack(scratch, frame, W, H, runs, s);
+    launch_png_pack(scratch, frame, W, H, variant, s);
     if (tm) tm->mark("png_pack");
-    launch_png_crc(scratch, frame, W, H, runs, s);
+    launch_png_crc(scratch, frame, W, H, variant, s);
     if (tm) tm->mark("png_crc");
-    launch_png_finish(scratch, frame, (uint32_t*)total_dev, W, H, runs, s, done);
+    launch_png_finish(scratch, frame, (uint32_t*)total_dev, W, H, variant, s, done);
     if (tm) tm->mark("png_finish");
 }
 
 void enqueue_coding(const FormatTraits& t, const uint8_t* src, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
     if (t.coder == kCoderGif) enqueue_gif_coding(src, scratch, frame, total_dev, W, H, s, done, tm);
     else if (t.coder == kCoderJpeg) enqueue_jpeg_coding(src, tables, scratch, frame, total_dev, W, H, t.sampling(), t.frame_tables, s, done, tm);
-    else if (t.coder == kCoderPng) enqueue_png_coding(t.runs(), src, scratch, frame, total_dev, W, H, s, done, tm);
+    else if (t.coder == kCoderPng) enqueue_png_coding(t.variant, src, scratch, frame, total_dev, W, H, s, done, tm);
 }
 
 const uint8_t* enqueue_raster(FrameRaster raster, const uint8_t* src_bgr, int W, int H, const SlotFormat& b, hipStream_t s, hipEvent_t done, Timer* tm) {

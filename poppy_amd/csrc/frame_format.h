@@ -69,7 +69,7 @@ const uint8_t* enqueue_raster(FrameRaster raster, const uint8_t* src_bgr, int W,
 // the coder step: `src` (the record's raster form; PNG: the tight BGR frame, any alignment) coded into `frame`, its length also into the pinned word behind
 // total_dev (null: none); `done` rides on the last dispatch.  GIF: two dispatches (marks gif_lzw, gif_pack).  JPEG: two (jpeg_code, jpeg_pack), on per-frame tables four (jpeg_count, jpeg_tables in front), in the record's
 // sampling at the quality that `tables` (device memory, kernels.h: kJpegTableBytes) name.  PNG: the six of kernels_frame_png.hip (png_filter, png_cost,
-// png_scan, png_pack, png_crc, png_finish), under PNG_RUNS with the run-aware cost and pack kernels in the places of the two.
+// png_scan, png_pack, png_crc, png_finish), under PNG_RUNS with the run-aware cost and pack kernels in the places of the two, under PNG_OPT with the ones that build and use the segments' own tables.
 void enqueue_coding(const FormatTraits& t, const uint8_t* src, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm);
 hipError_t prepare_coding_scratch(const FormatTraits& t, uint8_t* scratch, int W, int H, hipStream_t s);      // ... once behind its allocation, in front of the first frame coded on it
 size_t coding_scratch_bytes(const FormatTraits& t, int W, int H);      // ... and what `scratch` holds (kernels.h: gif_scratch_bytes, jpeg_scratch_bytes, png_scratch_bytes)

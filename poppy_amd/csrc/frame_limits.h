@@ -3,7 +3,7 @@
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "jpeg_tables.h"
-#include "png_runs_tables.h"
+#include "png_opt.h"
 
 // poppy_hip_set_frame_size's rule (include/poppy_hip.h): ow x oh is no larger than W x H and at most POPPY_FRAME_SCALE_MAX times smaller per side (so W, H >= 1 too)
 inline bool size_admits(int W, int H, int ow, int oh) {
@@ -34,7 +34,7 @@ struct FormatTraits {
     const char* name;          // for messages: a coded format's is its coder's ("JPEG frame coding: ")
     FrameRaster raster;
     FrameCoder coder;
-    int variant;               // the JPEG coder's sampling (jpeg::Sampling), the PNG coder's runs flag
+    int variant;               // the JPEG coder's sampling (jpeg::Sampling); the PNG coder's tokens and tables (png::Variant): literals, runs as matches, or those on the segments' own tables
     bool frame_tables;         // the JPEG coder's Huffman tables: the Annex K examples (false), or four tables built from this frame's own symbol counts
     bool sequence;             // one palette for all the frames a call hands to its writer: they wait in the sequence store until the last is rendered (palette_seq.h),
                                // and no slot converts or codes them — the sequence pass and the sequence's coder do
@@ -46,7 +46,7 @@ struct FormatTraits {
     constexpr FrameCoder slot_coder() const { return sequence ? kCoderNone : coder; }
     constexpr bool converts() const { return slot_raster() != kRasterNone || slot_coder() != kCoderNone; }
     constexpr poppy_hip::jpeg::Sampling sampling() const { return variant ? poppy_hip::jpeg::k444 : poppy_hip::jpeg::k420; }
-    constexpr bool runs() const { return variant != 0; }
+    constexpr bool runs() const { return variant != poppy_hip::png::kLiterals; }      // PNG: runs coded as matches, on POPPY_FRAME_PNG_RUNS' capacity
 };
 inline constexpr FormatTraits kFormats[] = {
     {POPPY_FRAME_BGR,         "BGR",  kRasterNone, kCoderNone, 0,                     false, false, 0},
@@ -60,7 +60,8 @@ inline constexpr FormatTraits kFormats[] = {
     {POPPY_FRAME_JPEG_OPT,    "JPEG", kRasterI420, kCoderJpeg, poppy_hip::jpeg::k420, true,  false, poppy_hip::jpeg::kOptFrameMinBytes},   // the header with four one-symbol tables, a byte of data, EOI
     {POPPY_FRAME_JPEG444_OPT, "JPEG", kRasterI444, kCoderJpeg, poppy_hip::jpeg::k444, true,  false, poppy_hip::jpeg::kOptFrameMinBytes},
     {POPPY_FRAME_PNG,         "PNG",  kRasterNone, kCoderPng,  0,                     false, false, poppy_hip::png::kFrameMinBytes},       // the file's fixed parts and one byte of deflate data
-    {POPPY_FRAME_PNG_RUNS,    "PNG",  kRasterNone, kCoderPng,  1,                     false, false, poppy_hip::png::kFrameMinBytes},       // PNG with runs coded as matches, the same limits on its own capacity
+    {POPPY_FRAME_PNG_RUNS,    "PNG",  kRasterNone, kCoderPng,  poppy_hip::png::kRuns, false, false, poppy_hip::png::kFrameMinBytes},       // PNG with runs coded as matches, the same limits on its own capacity
+    {POPPY_FRAME_PNG_OPT,     "PNG",  kRasterNone, kCoderPng,  poppy_hip::png::kRunsOwn, false, false, poppy_hip::png::kFrameMinBytes},    // PNG_RUNS with a ninth table per segment, built from its counts: PNG_RUNS' limits and capacity
 };
 constexpr const FormatTraits* format_traits(int fmt) {      // null for an unknown format
     for (const FormatTraits& t : kFormats) if (t.format == fmt) return &t;
@@ -91,7 +92,7 @@ inline size_t frame_bytes(const FormatTraits& t, int W, int H) {
 // every constant of include/poppy_hip.h has exactly one record, and the records hold what the code relies on
 constexpr bool formats_hold() {
     constexpr int all[] = {POPPY_FRAME_BGR, POPPY_FRAME_I420, POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF, POPPY_FRAME_GIF_SEQ, POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444,
-                           POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT};
+                           POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT, POPPY_FRAME_PNG_OPT};
     if (sizeof all / sizeof *all != sizeof kFormats / sizeof *kFormats) return false;
     for (int fmt : all) {
         int n = 0;
@@ -106,6 +107,8 @@ constexpr bool formats_hold() {
         if (t.coder == kCoderGif && t.raster != kRasterPal8) return false;      // the coders read their raster form: GIF PAL8, JPEG the planes of its sampling, PNG the BGR frame
         if (t.coder == kCoderJpeg && t.raster != (t.sampling() == poppy_hip::jpeg::k444 ? kRasterI444 : kRasterI420)) return false;
         if (t.coder == kCoderPng && t.raster != kRasterNone) return false;
+        if (t.coder == kCoderPng && t.variant != poppy_hip::png::kLiterals && t.variant != poppy_hip::png::kRuns && t.variant != poppy_hip::png::kRunsOwn) return false;
+        if (t.coder == kCoderPng && t.least != poppy_hip::png::kFrameMinBytes) return false;      // every PNG variant's smallest frame is the fixed parts and a byte of data
         if (t.frame_tables && t.coder != kCoderJpeg) return false;      // per-frame tables are the JPEG coder's, and such a format's smallest frame is the OPT header's
         if (t.coder == kCoderJpeg && t.least != (t.frame_tables ? poppy_hip::jpeg::kOptFrameMinBytes : poppy_hip::jpeg::kFrameMinBytes)) return false;
     }

@@ -1,5 +1,5 @@
-// frame_png.h — what the two PNG host statements share (frame_png.cpp defines it; frame_png_runs.cpp uses it): the filtered stream, the file's fixed parts and
-// the writer of deflate's bits.  POPPY_FRAME_PNG and POPPY_FRAME_PNG_RUNS differ in the deflate blocks only.  Host only.
+// frame_png.h — what the three PNG host statements share (frame_png.cpp defines it; frame_png_runs.cpp and frame_png_opt.cpp use it): the filtered stream, the
+// file's fixed parts and the writer of deflate's bits.  POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS and POPPY_FRAME_PNG_OPT differ in the deflate blocks only.  Host only.
 #pragma once
 #include "frame_limits.h"
 #include <vector>

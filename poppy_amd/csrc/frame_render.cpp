@@ -93,7 +93,7 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     // JPEG is I420 with its two coding dispatches behind the conversion, wherever I420's runs: on the chain's own stream.  Nothing in them is one workgroup's
     // serial work — a wave per restart interval, a thousand of them at 1080p, 46 us in all —, and on the slot's low-priority side stream they were measured
     // slower, not faster: the chained 1080p frame 4.5 - 4.8k frames/s against 5.5k here, a pool of six 4.5 - 4.7k against 6.8 - 6.9k.
-    // PNG (and PNG_RUNS) is six dispatches straight behind the unsharp, on the chain's own stream as JPEG's: the two that are one workgroup's work (scan, finish) are short.
+    // PNG (and PNG_RUNS, PNG_OPT) is six dispatches straight behind the unsharp, on the chain's own stream as JPEG's: the two that are one workgroup's work (scan, finish) are short.
     // PAL8_SEQ (seq_dst: the frame's place in the sequence store, never set in a captured body): the pass takes PAL8's place, on the side stream too — it is short,
     // but the chain needs nothing of it.
     // A scale above 1 or a size: the downscale (the resize) is the conversion's first dispatch wherever that runs, and a conversion of its own under BGR (the writer gets the slot's

@@ -2,7 +2,7 @@
 #pragma once
 #include "../../include/poppy_hip.h"
 #include "jpeg_tables.h"
-#include "png_runs_tables.h"
+#include "png_opt.h"
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
@@ -293,15 +293,19 @@ void launch_bgr_to_i444(const uint8_t* src, uint8_t* dst, int w, int h, hipStrea
 // a frame on the device (tight BGR, any alignment) -> POPPY_FRAME_PNG (kernels_frame_png.hip, which says what each does; the format: include/poppy_hip.h and
 // png_tables.h), six dispatches on one stream in this order.  `scratch`: png_scratch_bytes of device memory (the filtered stream, then the segments' and the CRC
 // pieces' words); `frame`: poppy_frame_bytes(POPPY_FRAME_PNG, w, h) + 16 bytes, 4-byte aligned; total_host (optional): a word of mapped pinned host memory that
-// receives `total` too.  `done` (optional) rides on the last dispatch.  `runs`: POPPY_FRAME_PNG_RUNS (png_runs_tables.h) — scratch and frame at that format's
-// sizes, the run-aware cost and pack kernels; the other four dispatches are the same kernels.
-size_t png_scratch_bytes(int w, int h, bool runs);
-void launch_png_filter(const uint8_t* bgr, uint8_t* scratch, int w, int h, bool runs, hipStream_t s);
-void launch_png_cost(uint8_t* scratch, int w, int h, bool runs, hipStream_t s);
-void launch_png_scan(uint8_t* scratch, uint8_t* frame, int w, int h, bool runs, hipStream_t s);
-void launch_png_pack(const uint8_t* scratch, uint8_t* frame, int w, int h, bool runs, hipStream_t s);
-void launch_png_crc(uint8_t* scratch, const uint8_t* frame, int w, int h, bool runs, hipStream_t s);
-void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, bool runs, hipStream_t s, hipEvent_t done = nullptr);
+// receives `total` too.  `done` (optional) rides on the last dispatch.  `variant` (png_opt.h: png::Variant): kRuns is POPPY_FRAME_PNG_RUNS
+// (png_runs_tables.h) — scratch and frame at that format's sizes, the run-aware cost and pack kernels; the other four dispatches are the same kernels.  kRunsOwn is
+// POPPY_FRAME_PNG_OPT: PNG_RUNS' sizes and a png_opt::OwnTable per segment behind them, k_png_opt_cost and k_png_opt_pack in the places of the two.
+size_t png_scratch_bytes(int w, int h, int variant);
+void launch_png_filter(const uint8_t* bgr, uint8_t* scratch, int w, int h, int variant, hipStream_t s);
+void launch_png_cost(uint8_t* scratch, int w, int h, int variant, hipStream_t s);
+void launch_png_scan(uint8_t* scratch, uint8_t* frame, int w, int h, int variant, hipStream_t s);
+void launch_png_pack(const uint8_t* scratch, uint8_t* frame, int w, int h, int variant, hipStream_t s);
+void launch_png_crc(uint8_t* scratch, const uint8_t* frame, int w, int h, int variant, hipStream_t s);
+void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, int variant, hipStream_t s, hipEvent_t done = nullptr);
+// POPPY_FRAME_PNG_OPT's length build alone (k_png_lengths: the routine k_png_opt_cost runs per segment): `counts` is 286 words of device memory, zeros behind the
+// symbols in use; `lengths` receives 286 words
+void launch_png_length_build(const uint32_t* counts, int limit, uint32_t* lengths, hipStream_t s);
 
 // The RANSAC fundamental-matrix filter's 2048 hypotheses (kernels_ransac.hip; the rule: include/poppy_hip.h, poppy_ransac_fundamental): the models of problem P
 // (normalised, 8 .. 65536 pairs) and their inlier counts among the pairs p1 <-> p2 into the host arrays counts (2048) and models (2048 x 9), two launches on s, which

@@ -32,6 +32,18 @@
 //   k_png_run_pack  the same walk again on the chosen table, first for the thread's bit count, then, behind the workgroup's prefix sum, for the bits: a match is
 //                 its length code and one more field of extra bits + 1 (the distance code's 0 bit on top), 15 + 6 bits at the most, so the 64-bit
 //                 accumulator holds as it does for literals.
+// POPPY_FRAME_PNG_OPT (png_opt.h; poppy_bgr_to_png_opt_frame in frame_png_opt.cpp is its host statement) is POPPY_FRAME_PNG_RUNS with two kernels of its own in
+// the same two places, and a png_opt::OwnTable per segment behind the scratch's other words:
+//   k_png_opt_cost  k_png_run_cost's run bounds and token walk, with the tokens counted into a 286-word LDS histogram (ds_add; end-of-block counts 1): the eight
+//                 fixed costs are the histogram's dot products with the nibble table.  Wave 0 then builds the segment's own table while the others leave
+//                 (build_code, a lane holds symbols lane + 64 j): the rule's merges in registers as k_jpeg_tables runs them — the two smallest packed keys
+//                 (count << 9 | 511 - symbol) by ds_min_u64 —, Annex K.3 on lane 0, a symbol's place by (depth, symbol) and then by (length, symbol) as the
+//                 number of smaller keys, which give its length and its canonical code.  The header's length sequence: the lanes' break flags are five
+//                 ballots, the whole sequence's break mask in every lane, so every place finds its run's start and length by itself and decides what it sends
+//                 (png_opt::entry_at, as token_at does for bytes); the 19 counts, the same build at 7 bits, a prefix sum of the entries' bits, and the header
+//                 ORed into LDS.  Per segment: the choice 0..8 (8: the own table wins outright; ties go to the fixed tables) and, under 8, the own table.
+//   k_png_opt_pack  k_png_run_pack with the codes and the header read from the segment's own table when the choice is 8.  No code is above 15 bits and the block
+//                 is no longer than the best fixed table's, so the accumulator and the LDS image hold as they do there.
 // Plain vector stores and atomics only.
 #include "kernels.h"
 #include <hip/hip_ext.h>
@@ -122,6 +134,13 @@ __constant__ RunNibbleTable c_run_nibbles = make_run_nibbles();
 __constant__ png_runs::Codes c_run_codes = png_runs::make_codes();
 __constant__ RunHeaderWords c_run_header = make_run_header_words();
 __constant__ BlockOver c_run_block = make_run_block_over();
+struct ClOrder { uint8_t e[png_opt::kClSymbols]; };
+constexpr ClOrder make_cl_order() {
+    ClOrder o{};
+    for (int i = 0; i < png_opt::kClSymbols; ++i) o.e[i] = png_opt::kClOrder[i];
+    return o;
+}
+__constant__ ClOrder c_cl_order = make_cl_order();
 __constant__ CrcTable c_crc = make_crc_table();
 __constant__ CrcShifts c_crc_shift = make_crc_shifts();
 __constant__ CrcPowers c_crc_pow = make_crc_powers();
@@ -134,17 +153,20 @@ struct Scratch {
     unsigned long long* start;          // per segment: the frame's bit its block begins at
     uint32_t* crc;                      // per kCrcBlock of the chunk, counted from its end: the raw remainder
     uint32_t* meta;                     // [0] the frame's byte behind the deflate data (Adler-32's place), [1] whether the frame is inside its capacity
+    png_opt::OwnTable* own;             // kRunsOwn only, per segment: its own table where that is its choice
 };
-unsigned long long capacity_of(int w, int h, bool runs) { return runs ? png_runs::frame_capacity((size_t)w, (size_t)h) : frame_capacity((size_t)w, (size_t)h); }
-size_t crc_blocks(int w, int h, bool runs) { return (size_t)((capacity_of(w, h, runs) + kCrcBlock - 1) / kCrcBlock); }
-Scratch scratch_of(uint8_t* p, int w, int h, bool runs) {
+constexpr size_t kMetaWords = 4;
+unsigned long long capacity_of(int w, int h, int variant) { return variant != kLiterals ? png_runs::frame_capacity((size_t)w, (size_t)h) : frame_capacity((size_t)w, (size_t)h); }
+size_t crc_blocks(int w, int h, int variant) { return (size_t)((capacity_of(w, h, variant) + kCrcBlock - 1) / kCrcBlock); }
+Scratch scratch_of(uint8_t* p, int w, int h, int variant) {
     const size_t n_seg = (size_t)segment_count((size_t)w, (size_t)h);
     Scratch s;
     s.stream = p;
     s.seg = (uint4*)(p + n_seg * kSegment);
     s.start = (unsigned long long*)(s.seg + n_seg);
     s.crc = (uint32_t*)(s.start + n_seg);
-    s.meta = s.crc + crc_blocks(w, h, runs);
+    s.meta = s.crc + crc_blocks(w, h, variant);
+    s.own = (png_opt::OwnTable*)(s.meta + kMetaWords);
     return s;
 }
 
@@ -542,9 +564,292 @@ __global__ void __launch_bounds__(kThreads) k_png_run_cost(const uint8_t* __rest
     }
 }
 
-__global__ void __launch_bounds__(kThreads) k_png_run_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const unsigned long long* __restrict__ seg_start,
-                                                           const uint32_t* __restrict__ meta, uint32_t* __restrict__ frame32, uint32_t n_seg, unsigned long long n,
-                                                           unsigned long long capacity) {
+namespace {
+
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+constexpr int kLanes = 64, kPerLane = 5;                    // a lane holds symbols (and places of the header's sequence) lane + 64 j
+static_assert(kLanes * kPerLane >= png_opt::kSequenceMax + 1, "five per lane cover the 286 symbols, and the 287 places of the sequence with the mark behind them");
+struct BuildLds {
+    uint32_t of_depth[png_opt::kSymbols + 2];               // the symbols of each depth 0..286, then of each length
+    uint32_t key[png_opt::kSymbols];                        // a symbol's (depth, then length) << 9 | symbol, ~0 without a code
+    unsigned long long pick[2];                             // the two smallest keys of the merge at hand
+    uint32_t first_code[16], first_place[16];               // per length: its first canonical code, the place of its first symbol
+};
+constexpr unsigned long long kNoKey = ~0ull;
+
+// a symbol's place among the n keys: the number of smaller ones
+__device__ __forceinline__ void places_of(const uint32_t* key, int n, int lane, uint32_t (&place)[kPerLane]) {
+    uint32_t mine[kPerLane];
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) { const int idx = lane + kLanes * j; mine[j] = idx < n ? key[idx] : ~0u; place[j] = 0; }
+    for (int i = 0; i < n; ++i) {
+        const uint32_t other = key[i];
+        #pragma unroll
+        for (int j = 0; j < kPerLane; ++j) place[j] += other < mine[j];
+    }
+}
+
+// poppy_png_optimal_lengths' rule (include/poppy_hip.h) in one wave, every lane of which is here: freq[j] is the count of symbol lane + 64 j (0 from n on, and at
+// least one is not), n <= 286, the used symbols no more than 2^limit.  entry[j]: the symbol's reversed canonical code << 4 | its length, 0 without a code.
+__device__ __forceinline__ void build_code(uint32_t (&freq)[kPerLane], int n, int limit, BuildLds& L, uint32_t (&entry)[kPerLane]) {
+    const int lane = threadIdx.x & (kLanes - 1);
+    int tree[kPerLane], depth[kPerLane];
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) { tree[j] = lane + kLanes * j; depth[j] = 0; }
+    for (int i = lane; i < png_opt::kSymbols + 2; i += kLanes) L.of_depth[i] = 0;
+    volatile unsigned long long* pick_read = L.pick;
+    unsigned long long* pick = L.pick;
+    bool merged = false;
+    unsigned long long m1, m2;
+    for (;;) {
+        // the two smallest keys of the wave (keys are unique), as k_jpeg_tables takes them: the lane's own pair, then two rounds of ds_min_u64
+        m1 = kNoKey; m2 = kNoKey;
+        #pragma unroll
+        for (int j = 0; j < kPerLane; ++j) {
+            const unsigned long long key = freq[j] ? (unsigned long long)freq[j] << 9 | (unsigned long long)(511 - (lane + kLanes * j)) : kNoKey;
+            if (key < m1) { m2 = m1; m1 = key; } else if (key < m2) m2 = key;
+        }
+        if (lane == 0) { pick[0] = kNoKey; pick[1] = kNoKey; }
+        wave_sync();
+        if (m1 != kNoKey) atomicMin(&pick[0], m1);
+        wave_sync();
+        const unsigned long long g1 = pick_read[0];
+        { const unsigned long long mine = m1 == g1 ? m2 : m1; if (mine != kNoKey) atomicMin(&pick[1], mine); }
+        wave_sync();
+        m1 = g1; m2 = pick_read[1];
+        wave_sync();                                        // (both are read before lane 0 resets them)
+        if (m2 == kNoKey) break;                            // (wave-uniform)
+        merged = true;
+        const int c1 = 511 - (int)(m1 & 511), c2 = 511 - (int)(m2 & 511);
+        const uint32_t f2 = (uint32_t)(m2 >> 9);
+        #pragma unroll
+        for (int j = 0; j < kPerLane; ++j) {
+            const int idx = lane + kLanes * j;
+            if (tree[j] == c1 || tree[j] == c2) { ++depth[j]; tree[j] = c1; }
+            if (idx == c1) freq[j] += f2;
+            if (idx == c2) freq[j] = 0;
+        }
+    }
+    int longest = 0;
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) {
+        const int idx = lane + kLanes * j;
+        if (!merged && m1 != kNoKey && idx == 511 - (int)(m1 & 511)) depth[j] = 1;      // a single symbol with a count
+        if (depth[j]) atomicAdd(&L.of_depth[depth[j]], 1u);
+        longest = max(longest, depth[j]);
+        if (idx < n) L.key[idx] = depth[j] ? (uint32_t)depth[j] << 9 | (uint32_t)idx : ~0u;
+    }
+    #pragma unroll
+    for (int d = 1; d < kLanes; d <<= 1) longest = max(longest, __shfl_xor(longest, d, kLanes));
+    wave_sync();
+    if (lane == 0) {
+        uint32_t* bits = L.of_depth;
+        for (int i = longest; i > limit; --i)               // Annex K.3
+            while (bits[i] > 0) {
+                int j = i - 2;
+                while (j > 0 && bits[j] == 0) --j;
+                bits[i] -= 2; bits[i - 1] += 1; bits[j + 1] += 2; bits[j] -= 1;
+            }
+        uint32_t code = 0, place = 0;
+        for (int l = 1; l <= 15; ++l) {
+            L.first_code[l] = code; L.first_place[l] = place;
+            code = (code + bits[l]) << 1; place += bits[l];
+        }
+    }
+    wave_sync();
+    // by depth, then by symbol, the adjusted lengths in ascending order: the length whose places hold the symbol's
+    uint32_t place[kPerLane], length[kPerLane];
+    places_of(L.key, n, lane, place);
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) {
+        length[j] = 0;
+        if (depth[j])
+            for (int l = 1; l <= 15; ++l)
+                if (place[j] >= L.first_place[l] && place[j] - L.first_place[l] < L.of_depth[l]) length[j] = (uint32_t)l;
+    }
+    wave_sync();
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) { const int idx = lane + kLanes * j; if (idx < n) L.key[idx] = length[j] ? length[j] << 9 | (uint32_t)idx : ~0u; }
+    wave_sync();
+    // deflate's canonical code: by length, then by symbol
+    places_of(L.key, n, lane, place);
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) {
+        const uint32_t l = length[j], code = l ? L.first_code[l] + place[j] - L.first_place[l] : 0u;
+        entry[j] = l ? (__brev(code) >> (32 - l)) << 4 | l : 0u;
+    }
+    wave_sync();                                            // (L is free again)
+}
+
+// `width` bits (at most 32) of `value` into a bit string in LDS, at its bit `at`
+__device__ __forceinline__ void or_bits(uint32_t* words, uint32_t at, uint32_t value, uint32_t width) {
+    if (!width) return;
+    const unsigned long long v = (unsigned long long)value << (at & 31);
+    atomicOr(&words[at >> 5], (uint32_t)v);
+    if ((at & 31) + width > 32) atomicOr(&words[(at >> 5) + 1], (uint32_t)(v >> 32));
+}
+
+// What place lane + 64 j of the header's length sequence `seq` (n_seq places) sends: brk holds the sequence's breaks, bit p of the five words together set where place
+// p begins a run, and at p = n_seq.  The run's first place is the last break at or before p (place 0 is one), its end the first break behind p; png_opt::entry_at
+// decides from them.  -1: nothing (a place that an earlier entry covers, or none of the sequence); else symbol | extra bits << 8 | extra value << 16.
+__device__ __forceinline__ int sent_at(const unsigned long long (&brk)[kPerLane], int j, int lane, int n_seq, const uint32_t* seq) {
+    const int p = lane + kLanes * j;
+    int start = 0, stop = n_seq;
+    #pragma unroll
+    for (int w = 0; w < kPerLane; ++w) {
+        const unsigned long long m = w < j ? brk[w] : w == j ? brk[w] & (~0ull >> (63 - lane)) : 0ull;
+        if (m) start = kLanes * w + 63 - __clzll((long long)m);
+    }
+    #pragma unroll
+    for (int w = kPerLane - 1; w >= 0; --w) {
+        const unsigned long long m = w > j ? brk[w] : w == j && lane < 63 ? brk[w] & (~0ull << (lane + 1)) : 0ull;
+        if (m) stop = kLanes * w + __ffsll((long long)m) - 1;
+    }
+    if (p >= n_seq) return -1;
+    const png_opt::Entry e = png_opt::entry_at((int)seq[start], stop - start, p - start);
+    return e.symbol < 0 ? -1 : e.symbol | e.extra_bits << 8 | (int)(e.extra << 16);
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(kThreads) k_png_opt_cost(const uint8_t* __restrict__ stream, uint4* __restrict__ seg_info, png_opt::OwnTable* __restrict__ own, unsigned long long n) {
+    __shared__ uint32_t s_count[kLanes * kPerLane];         // the tokens of each symbol; zeros behind 285
+    __shared__ uint32_t s_seq[kLanes * kPerLane];           // the own header's length sequence
+    __shared__ uint32_t s_cl[32];                           // the code-length symbols' counts, then their entries
+    __shared__ uint32_t s_header[png_opt::kOwnHeaderWords + 1];
+    __shared__ BuildLds s_build;
+    __shared__ unsigned long long s_part[4];
+    __shared__ uint32_t s_bound[8];
+    const int t = threadIdx.x;
+    const size_t first = (size_t)blockIdx.x * kSegment;
+    const uint32_t len = (uint32_t)(n - first < kSegment ? n - first : kSegment);
+    for (int i = t; i < kLanes * kPerLane; i += kThreads) s_count[i] = i == kEob ? 1u : 0u;
+    uint32_t beside = 0, sum = 0, weighted = 0;
+    const uint32_t at = (uint32_t)t * kBytesPerThread;
+    const bool active = at < len;
+    RunBytes r{};
+    if (active) r = load_run_bytes(stream + first, at, len);
+    uint32_t begin = 0, end = 0;
+    group_run_bounds(active ? last_break(r, at) : 0u, active ? first_break(r, at) : 0xFFFFFFFFu, s_bound, &begin, &end);      // (its barrier stands behind s_count's stores too)
+    if (active) {
+        for_each_token(r, at, len, begin, end, [&](uint32_t symbol, uint32_t extra_bits, uint32_t) {
+            atomicAdd(&s_count[symbol], 1u);
+            if (symbol > (uint32_t)kEob) beside += extra_bits + 1u;      // a match's extra bits and its distance code, whatever the table
+        });
+        #pragma unroll
+        for (int i = 0; i < kBytesPerThread; ++i) {
+            const uint32_t d = i < r.valid ? (r.word[i >> 2] >> (8 * (i & 3))) & 255u : 0u;
+            sum += d; weighted += (len - (at + i)) * d;      // (at most 32 * 8192 * 255: no overflow)
+        }
+    }
+    __syncthreads();
+    uint32_t cost[kTables] = {0, 0, 0, 0, 0, 0, 0, 0};      // the fixed tables: the histogram's dot products with their lengths (end-of-block is in it)
+    for (int i = t; i < png_runs::kSymbols; i += kThreads) {
+        const uint32_t c = s_count[i], v = c_run_nibbles.e[i];
+        #pragma unroll
+        for (int k = 0; k < kTables; ++k) cost[k] += c * ((v >> (4 * k)) & 15u);
+    }
+    unsigned long long total[kTables];
+    #pragma unroll
+    for (int k = 0; k < kTables; ++k) total[k] = group_sum(cost[k] + beside, s_part);
+    const unsigned long long a = group_sum(sum, s_part), b = group_sum(weighted % kAdlerMod, s_part), beside_all = group_sum(beside, s_part);
+    if (t >= kLanes) return;                                // wave 0 builds the own table: no workgroup barrier from here on
+    int best = 0; unsigned long long least = 0;
+    for (int k = 0; k < kTables; ++k) {
+        const unsigned long long v = total[k] + c_run_block.header[k];
+        if (k == 0 || v < least) { best = k; least = v; }
+    }
+    const int lane = t;
+    uint32_t freq[kPerLane], count[kPerLane], entry[kPerLane];
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) count[j] = freq[j] = s_count[lane + kLanes * j];
+    build_code(freq, png_opt::kSymbols, png_opt::kLimit, s_build, entry);
+    unsigned long long own_bits = 0;
+    int n_lit = 257;
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) {
+        own_bits += (unsigned long long)count[j] * (entry[j] & 15u);
+        if (entry[j]) n_lit = max(n_lit, lane + kLanes * j + 1);
+    }
+    own_bits = wave_sum(own_bits);
+    #pragma unroll
+    for (int d = 1; d < kLanes; d <<= 1) n_lit = max(n_lit, __shfl_xor(n_lit, d, kLanes));
+    // the length sequence: the lit/len lengths, then the distance code's 1; place n_seq carries the mark that ends the last run
+    const int n_seq = n_lit + 1;
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) { const int p = lane + kLanes * j; s_seq[p] = p < n_lit ? entry[j] & 15u : 1u; }
+    if (lane < 32) s_cl[lane] = 0;
+    for (int i = lane; i < png_opt::kOwnHeaderWords + 1; i += kLanes) s_header[i] = 0;
+    wave_sync();
+    unsigned long long brk[kPerLane];
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) {
+        const int p = lane + kLanes * j;
+        brk[j] = __ballot(p < n_seq ? p == 0 || s_seq[p] != s_seq[p - 1] : p == n_seq);
+    }
+    int sent[kPerLane];                                     // what a place sends: the code-length symbol, its extra bits << 8 and their value << 16; -1 for nothing
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) {
+        sent[j] = sent_at(brk, j, lane, n_seq, s_seq);
+        if (sent[j] >= 0) atomicAdd(&s_cl[sent[j] & 31], 1u);
+    }
+    wave_sync();
+    uint32_t cl_freq[kPerLane] = {lane < png_opt::kClSymbols ? s_cl[lane] : 0u, 0u, 0u, 0u, 0u}, cl_entry[kPerLane];
+    build_code(cl_freq, png_opt::kClSymbols, png_opt::kClLimit, s_build, cl_entry);
+    if (lane < png_opt::kClSymbols) s_cl[lane] = cl_entry[0];
+    wave_sync();
+    // HCLEN: the code-length code's lengths in RFC 1951's order, trailing zeros trimmed, at least 4
+    const uint32_t ordered = lane < png_opt::kClSymbols ? s_cl[c_cl_order.e[lane]] & 15u : 0u;
+    const unsigned long long has = __ballot(ordered != 0);
+    const int n_cl = max(4, has ? 64 - __clzll((long long)has) : 0);
+    uint32_t at_bit = 17u + 3u * (uint32_t)n_cl;
+    if (lane == 0) or_bits(s_header, 0, 4u | (uint32_t)(n_lit - 257) << 3 | (uint32_t)(n_cl - 4) << 13, 17);      // BFINAL 0, BTYPE 10, HLIT, HDIST 0, HCLEN
+    if (lane < n_cl) or_bits(s_header, 17u + 3u * (uint32_t)lane, ordered, 3);
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) {                    // the entries' places in the header: a prefix sum of their bits in the sequence's order
+        const uint32_t e = sent[j] >= 0 ? s_cl[sent[j] & 31] : 0u, code_bits = e & 15u, width = sent[j] >= 0 ? code_bits + ((uint32_t)sent[j] >> 8 & 15u) : 0u;
+        uint32_t incl = width;
+        #pragma unroll
+        for (int d = 1; d < kLanes; d <<= 1) { const uint32_t u = __shfl_up(incl, d, kLanes); if (lane >= d) incl += u; }
+        or_bits(s_header, at_bit + incl - width, e >> 4 | ((uint32_t)sent[j] >> 16) << code_bits, width);      // the code, then the extra bits: 7 + 7 at the most
+        at_bit += __shfl(incl, kLanes - 1, kLanes);
+    }
+    wave_sync();
+    const unsigned long long own_cost = (unsigned long long)at_bit + own_bits + beside_all;
+    const bool owned = own_cost < least;                    // (ties go to the lowest index: a fixed table)
+    if (lane == 0) seg_info[blockIdx.x] = make_uint4(owned ? (uint32_t)png_opt::kOwn : (uint32_t)best, (uint32_t)(owned ? own_cost : least), (uint32_t)a, (uint32_t)(b % kAdlerMod));
+    if (!owned) return;
+    own += blockIdx.x;
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) { const int idx = lane + kLanes * j; if (idx < png_opt::kSymbols) own->code[idx] = entry[j]; }
+    if (lane == 0) own->header_bits = at_bit;
+    for (int i = lane; i < png_opt::kOwnHeaderWords + 1; i += kLanes) own->header[i] = s_header[i];
+}
+
+// the length build alone, one wave: counts[286] (zeros behind the symbols in use) -> lengths[286]
+__global__ void __launch_bounds__(64) k_png_lengths(const uint32_t* __restrict__ counts, int limit, uint32_t* __restrict__ lengths) {
+    __shared__ BuildLds s_build;
+    const int lane = threadIdx.x;
+    uint32_t freq[kPerLane], entry[kPerLane];
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) { const int idx = lane + kLanes * j; freq[j] = idx < png_opt::kSymbols ? counts[idx] : 0u; }
+    build_code(freq, png_opt::kSymbols, limit, s_build, entry);
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) { const int idx = lane + kLanes * j; if (idx < png_opt::kSymbols) lengths[idx] = entry[j] & 15u; }
+}
+
+namespace {
+
+// k_png_run_pack's body.  OWN (k_png_opt_pack): a segment whose choice is png_opt::kOwn takes its codes, its header and the header's length from `own`, its table
+// in the scratch; every other segment, and every segment without OWN, from table 0..7's constants.
+template <bool OWN>
+__device__ __forceinline__ void run_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const png_opt::OwnTable* __restrict__ own,
+                                         const unsigned long long* __restrict__ seg_start, const uint32_t* __restrict__ meta, uint32_t* __restrict__ frame32, uint32_t n_seg,
+                                         unsigned long long n, unsigned long long capacity) {
     __shared__ uint32_t s_image[kRunImageWords];
     __shared__ uint32_t s_code[png_runs::kSymbols];
     __shared__ uint32_t s_part[4];
@@ -552,18 +857,20 @@ __global__ void __launch_bounds__(kThreads) k_png_run_pack(const uint8_t* __rest
     const int t = threadIdx.x;
     const uint32_t seg = blockIdx.x;
     const uint4 info = seg_info[seg];
+    const bool owned = OWN && info.x == (uint32_t)png_opt::kOwn;
     const uint32_t table = info.x & (kTables - 1), bits = info.y;
+    if (OWN) own += seg;
     if (!meta[1] || bits > png_runs::kSegmentBitsMax) return;      // (never: the scan found the frame inside its capacity, and table 7 bounds every block)
     const unsigned long long start = seg_start[seg];
     const size_t first = (size_t)seg * kSegment;
     const uint32_t len = (uint32_t)(n - first < kSegment ? n - first : kSegment);
     const uint32_t off = (uint32_t)start & 31u, n_words = (off + bits + 31) >> 5;
     for (uint32_t i = t; i < n_words; i += kThreads) s_image[i] = 0;
-    for (int i = t; i < png_runs::kSymbols; i += kThreads) s_code[i] = c_run_codes.e[table][i];
+    for (int i = t; i < png_runs::kSymbols; i += kThreads) s_code[i] = owned ? own->code[i] : c_run_codes.e[table][i];
     __syncthreads();
-    const uint32_t header_bits = c_run_block.header[table];
+    const uint32_t header_bits = owned ? min(own->header_bits, (uint32_t)png_opt::kOwnHeaderBitsMax) : c_run_block.header[table];
     for (uint32_t i = t; 32 * i < header_bits; i += kThreads) {      // the header, a word per thread (the bits behind H_k are zeros in the table)
-        const uint32_t v = c_run_header.e[table][i] | (i == 0 && seg == n_seg - 1 ? 1u : 0u), p = off + 32 * i;
+        const uint32_t v = (owned ? own->header[i] : c_run_header.e[table][i]) | (i == 0 && seg == n_seg - 1 ? 1u : 0u), p = off + 32 * i;
         atomicOr(&s_image[p >> 5], v << (p & 31));
         if ((p & 31) && (v >> (32 - (p & 31)))) atomicOr(&s_image[(p >> 5) + 1], v >> (32 - (p & 31)));
     }
@@ -604,6 +911,20 @@ __global__ void __launch_bounds__(kThreads) k_png_run_pack(const uint8_t* __rest
         if (fw >= cap_words) continue;
         if (fw == word0 || fw == word_end) atomicOr(&frame32[fw], s_image[i]); else frame32[fw] = s_image[i];
     }
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(kThreads) k_png_run_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const unsigned long long* __restrict__ seg_start,
+                                                           const uint32_t* __restrict__ meta, uint32_t* __restrict__ frame32, uint32_t n_seg, unsigned long long n,
+                                                           unsigned long long capacity) {
+    run_pack<false>(stream, seg_info, nullptr, seg_start, meta, frame32, n_seg, n, capacity);
+}
+
+__global__ void __launch_bounds__(kThreads) k_png_opt_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const png_opt::OwnTable* __restrict__ own,
+                                                           const unsigned long long* __restrict__ seg_start, const uint32_t* __restrict__ meta, uint32_t* __restrict__ frame32,
+                                                           uint32_t n_seg, unsigned long long n, unsigned long long capacity) {
+    run_pack<true>(stream, seg_info, own, seg_start, meta, frame32, n_seg, n, capacity);
 }
 
 __global__ void __launch_bounds__(kThreads) k_png_crc(const uint8_t* __restrict__ frame, const uint32_t* __restrict__ meta, uint32_t* __restrict__ pieces) {
@@ -654,42 +975,52 @@ __global__ void __launch_bounds__(kThreads) k_png_finish(const uint32_t* __restr
     if (total_host) { *total_host = total; __threadfence_system(); }
 }
 
-size_t png_scratch_bytes(int w, int h, bool runs) {
+size_t png_scratch_bytes(int w, int h, int variant) {
     const size_t n_seg = (size_t)segment_count((size_t)w, (size_t)h);
-    return n_seg * (kSegment + sizeof(uint4) + 8) + crc_blocks(w, h, runs) * 4 + 16 + 16;
+    return n_seg * (kSegment + sizeof(uint4) + 8) + crc_blocks(w, h, variant) * 4 + 4 * kMetaWords + 16 + (variant == kRunsOwn ? n_seg * sizeof(png_opt::OwnTable) : 0);
 }
 
-void launch_png_filter(const uint8_t* bgr, uint8_t* scratch, int w, int h, bool runs, hipStream_t s) {
+void launch_png_filter(const uint8_t* bgr, uint8_t* scratch, int w, int h, int variant, hipStream_t s) {
     const bool wide = w % 4 == 0 && (uintptr_t)bgr % 4 == 0;
-    hipLaunchKernelGGL(wide ? k_png_filter<true> : k_png_filter<false>, dim3((unsigned)h), dim3(kThreads), 0, s, bgr, scratch_of(scratch, w, h, runs).stream, w);
+    hipLaunchKernelGGL(wide ? k_png_filter<true> : k_png_filter<false>, dim3((unsigned)h), dim3(kThreads), 0, s, bgr, scratch_of(scratch, w, h, variant).stream, w);
 }
-void launch_png_cost(uint8_t* scratch, int w, int h, bool runs, hipStream_t s) {
-    const Scratch m = scratch_of(scratch, w, h, runs);
-    hipLaunchKernelGGL(runs ? k_png_run_cost : k_png_cost, dim3((unsigned)segment_count((size_t)w, (size_t)h)), dim3(kThreads), 0, s, (const uint8_t*)m.stream, m.seg, stream_bytes((size_t)w, (size_t)h));
+void launch_png_cost(uint8_t* scratch, int w, int h, int variant, hipStream_t s) {
+    const Scratch m = scratch_of(scratch, w, h, variant);
+    const dim3 grid((unsigned)segment_count((size_t)w, (size_t)h));
+    if (variant == kRunsOwn) hipLaunchKernelGGL(k_png_opt_cost, grid, dim3(kThreads), 0, s, (const uint8_t*)m.stream, m.seg, m.own, stream_bytes((size_t)w, (size_t)h));
+    else hipLaunchKernelGGL(variant == kRuns ? k_png_run_cost : k_png_cost, grid, dim3(kThreads), 0, s, (const uint8_t*)m.stream, m.seg, stream_bytes((size_t)w, (size_t)h));
 }
-void launch_png_scan(uint8_t* scratch, uint8_t* frame, int w, int h, bool runs, hipStream_t s) {
-    const Scratch m = scratch_of(scratch, w, h, runs);
+void launch_png_scan(uint8_t* scratch, uint8_t* frame, int w, int h, int variant, hipStream_t s) {
+    const Scratch m = scratch_of(scratch, w, h, variant);
     constexpr CrcTable table = make_crc_table();
     const uint8_t ihdr[17] = {'I', 'H', 'D', 'R', (uint8_t)(w >> 24), (uint8_t)(w >> 16), (uint8_t)(w >> 8), (uint8_t)w,
                               (uint8_t)(h >> 24), (uint8_t)(h >> 16), (uint8_t)(h >> 8), (uint8_t)h, 8, 2, 0, 0, 0};
     uint32_t c = 0xFFFFFFFFu;
     for (uint8_t byte : ihdr) c = table.e[(c ^ byte) & 255u] ^ (c >> 8);
     hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(kThreads), 0, s, (const uint4*)m.seg, m.start, m.meta, (uint32_t*)frame, (uint32_t)segment_count((size_t)w, (size_t)h),
-                       stream_bytes((size_t)w, (size_t)h), (uint32_t)w, (uint32_t)h, c ^ 0xFFFFFFFFu, capacity_of(w, h, runs));
+                       stream_bytes((size_t)w, (size_t)h), (uint32_t)w, (uint32_t)h, c ^ 0xFFFFFFFFu, capacity_of(w, h, variant));
 }
-void launch_png_pack(const uint8_t* scratch, uint8_t* frame, int w, int h, bool runs, hipStream_t s) {
-    const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h, runs);
+void launch_png_pack(const uint8_t* scratch, uint8_t* frame, int w, int h, int variant, hipStream_t s) {
+    const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h, variant);
     const uint32_t n_seg = (uint32_t)segment_count((size_t)w, (size_t)h);
-    hipLaunchKernelGGL(runs ? k_png_run_pack : k_png_pack, dim3(n_seg), dim3(kThreads), 0, s, (const uint8_t*)m.stream, (const uint4*)m.seg, (const unsigned long long*)m.start, (const uint32_t*)m.meta,
-                       (uint32_t*)frame, n_seg, stream_bytes((size_t)w, (size_t)h), capacity_of(w, h, runs));
+    if (variant == kRunsOwn)
+        hipLaunchKernelGGL(k_png_opt_pack, dim3(n_seg), dim3(kThreads), 0, s, (const uint8_t*)m.stream, (const uint4*)m.seg, (const png_opt::OwnTable*)m.own, (const unsigned long long*)m.start,
+                           (const uint32_t*)m.meta, (uint32_t*)frame, n_seg, stream_bytes((size_t)w, (size_t)h), capacity_of(w, h, variant));
+    else
+        hipLaunchKernelGGL(variant == kRuns ? k_png_run_pack : k_png_pack, dim3(n_seg), dim3(kThreads), 0, s, (const uint8_t*)m.stream, (const uint4*)m.seg, (const unsigned long long*)m.start,
+                           (const uint32_t*)m.meta, (uint32_t*)frame, n_seg, stream_bytes((size_t)w, (size_t)h), capacity_of(w, h, variant));
 }
-void launch_png_crc(uint8_t* scratch, const uint8_t* frame, int w, int h, bool runs, hipStream_t s) {
-    const Scratch m = scratch_of(scratch, w, h, runs);
-    hipLaunchKernelGGL(k_png_crc, dim3((unsigned)crc_blocks(w, h, runs)), dim3(kThreads), 0, s, frame, (const uint32_t*)m.meta, m.crc);
+void launch_png_crc(uint8_t* scratch, const uint8_t* frame, int w, int h, int variant, hipStream_t s) {
+    const Scratch m = scratch_of(scratch, w, h, variant);
+    hipLaunchKernelGGL(k_png_crc, dim3((unsigned)crc_blocks(w, h, variant)), dim3(kThreads), 0, s, frame, (const uint32_t*)m.meta, m.crc);
 }
-void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, bool runs, hipStream_t s, hipEvent_t done) {
-    const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h, runs);
+void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, int variant, hipStream_t s, hipEvent_t done) {
+    const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h, variant);
     hipExtLaunchKernelGGL(k_png_finish, dim3(1), dim3(kThreads), 0, s, nullptr, done, 0, (const uint32_t*)m.meta, (const uint32_t*)m.crc, frame, total_host);
+}
+
+void launch_png_length_build(const uint32_t* counts, int limit, uint32_t* lengths, hipStream_t s) {
+    hipLaunchKernelGGL(k_png_lengths, dim3(1), dim3(64), 0, s, counts, limit, lengths);
 }
 
 }  // namespace poppy_hip

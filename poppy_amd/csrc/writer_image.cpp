@@ -81,7 +81,7 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
     else if (t.coder == kCoderGif) rc = poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data());
     else if (t.coder == kCoderJpeg && t.frame_tables) rc = (t.sampling() == jpeg::k444 ? poppy_bgr_to_jpeg444_opt_frame : poppy_bgr_to_jpeg_opt_frame)(bgr, stride, W, H, c->jpeg_quality, tmp.data());
     else if (t.coder == kCoderJpeg) rc = (t.sampling() == jpeg::k444 ? poppy_bgr_to_jpeg444_frame : poppy_bgr_to_jpeg_frame)(bgr, stride, W, H, c->jpeg_quality, tmp.data());
-    else if (t.coder == kCoderPng) rc = (t.runs() ? poppy_bgr_to_png_runs_frame : poppy_bgr_to_png_frame)(bgr, stride, W, H, tmp.data());
+    else if (t.coder == kCoderPng) rc = (t.variant == png::kRunsOwn ? poppy_bgr_to_png_opt_frame : t.runs() ? poppy_bgr_to_png_runs_frame : poppy_bgr_to_png_frame)(bgr, stride, W, H, tmp.data());
     else rc = (t.raster == kRasterPal8 ? poppy_bgr_to_pal8 : poppy_bgr_to_i420)(bgr, stride, W, H, tmp.data());
     if (rc == POPPY_OK && !pal8.empty()) rc = poppy_pal8_to_gif_frame(pal8.data(), W, H, tmp.data());
     if (rc) { *status = fail(c, rc, "the frame format refuses this frame"); return nullptr; }
@@ -266,6 +266,35 @@ int poppy_hip_bgr_to_png_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stri
 }
 int poppy_hip_bgr_to_png_runs_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* dst) {
     return png_code_host_frame(c, POPPY_FRAME_PNG_RUNS, bgr, stride, W, H, dst);
+}
+int poppy_hip_bgr_to_png_opt_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, uint8_t* dst) {
+    return png_code_host_frame(c, POPPY_FRAME_PNG_OPT, bgr, stride, W, H, dst);
+}
+
+// the length-build routine of k_png_opt_cost alone on given counts: what poppy_png_optimal_lengths gives, with its refusals
+int poppy_hip_png_optimal_lengths(poppy_hip_ctx* c, const uint32_t* counts, int n_symbols, int limit, uint8_t* lengths) {
+    if (!c) return POPPY_E_ARG;
+    uint8_t host[png_opt::kSymbols];
+    if (poppy_png_optimal_lengths(counts, n_symbols, limit, lengths ? host : nullptr) != POPPY_OK)      // (the refusals are the host statement's; its lengths are not used)
+        return fail(c, POPPY_E_ARG, "bad arguments: a null pointer, n_symbols outside 1..286, a limit other than 7 or 15, counts that are all zero, whose sum is 2^32 or more, or more of them than 2^limit");
+    HIPCHK(c, hipSetDevice(c->device));
+    uint32_t padded[png_opt::kSymbols] = {}, built[png_opt::kSymbols];
+    memcpy(padded, counts, sizeof(uint32_t) * (size_t)n_symbols);
+    CallBuffers held;
+    uint8_t *d_counts = nullptr, *d_built = nullptr;
+    HIPCHK(c, held.alloc(&d_counts, sizeof padded));
+    HIPCHK(c, held.alloc(&d_built, sizeof built));
+    hipError_t e = hipMemcpyAsync(d_counts, padded, sizeof padded, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { launch_png_length_build((const uint32_t*)d_counts, limit, (uint32_t*)d_built, c->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(built, d_built, sizeof built, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go (`held`, at the return)
+    if (e == hipSuccess) e = e_sync;
+    if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("PNG length build: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    for (int i = 0; i < n_symbols; ++i) {
+        if (built[i] > (uint32_t)limit) return fail(c, POPPY_E_DEVICE, "a built length is outside its bounds");
+        lengths[i] = (uint8_t)built[i];
+    }
+    return POPPY_OK;
 }
 
 // a host frame up (upload_host_bgr), the I444 kernel, the planes down, on buffers that live for the call

@@ -1,4 +1,4 @@
-"""BGR against I420 against PAL8 against PAL8_SEQ against GIF against JPEG against JPEG444 against PNG against PNG_RUNS frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run
+"""BGR against I420 against PAL8 against PAL8_SEQ against GIF against JPEG against JPEG444 against PNG against PNG_RUNS against PNG_OPT frame hand-off (poppy_hip_set_frame_format), alternated in ONE process: processes differ by up to +-10 %, so every run
 times each row once per format, one format right after the other, and the rows report min / median / max over --runs runs.
 
   pool_1080p    bench.py's `value` set-up: a pool of --contexts contexts, --steps queued batches of six 1080p pairs from device images, 60 chained
@@ -11,12 +11,12 @@ times each row once per format, one format right after the other, and the rows r
   d2h_ceiling   pinned device-to-host copies of one frame's bytes, back to back on one stream (BGR, I420 and PAL8 sizes at 1080p and 4K)
 and, at the end, the conversion kernels' own times in timing mode 1 at 1080p and 4K (I420: frame_format; PAL8: pal8_hist, pal8_build, frame_format = the index plane;
 PAL8_SEQ: pal8_seq_hist per frame, pal8_seq_build per sequence, frame_format = the index plane; GIF: PAL8's three, then gif_lzw and gif_pack; JPEG: I420's frame_format, then
-jpeg_code and jpeg_pack; JPEG444: frame_format = the I444 conversion, then the same two; PNG and PNG_RUNS: png_filter, png_cost, png_scan, png_pack, png_crc, png_finish — under PNG_RUNS png_cost and png_pack are the run-aware kernels), and for the coded formats the median length of the 60 chained frames of the synthetic, of a textured and of a photograph pair (the golden 720 x 405 photographs, tiled; coded_bytes_median, with the coders' times on those frames; JPEG at --jpeg-quality).  Under PAL8_SEQ a pair's (a call's) frames are handed over after its last
+jpeg_code and jpeg_pack; JPEG444: frame_format = the I444 conversion, then the same two; PNG, PNG_RUNS and PNG_OPT: png_filter, png_cost, png_scan, png_pack, png_crc, png_finish — under PNG_RUNS png_cost and png_pack are the run-aware kernels, under PNG_OPT the ones that build and use the segments' own tables), and for the coded formats the median length of the 60 chained frames of the synthetic, of a textured and of a photograph pair (the golden 720 x 405 photographs, tiled; coded_bytes_median, with the coders' times on those frames; JPEG at --jpeg-quality).  Under PAL8_SEQ a pair's (a call's) frames are handed over after its last
 frame.
 
-    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif,jpeg,jpeg444,png,png_runs,jpeg_opt,jpeg444_opt --scales 1,2 --kernel-scales 2,4
+    python tools/frame_format_timing.py [--runs 3 --steps 8 --steps-4k 3 --contexts 6 --formats bgr,i420,pal8,pal8_seq,gif,jpeg,jpeg444,png,png_runs,jpeg_opt,jpeg444_opt,png_opt --scales 1,2 --kernel-scales 2,4
                                          --size 1280x720 --size-4k 1920x1080]
---formats leaves formats out (a library older than GIF: bgr,i420,pal8,pal8_seq; older than JPEG: without jpeg; older than JPEG444: without jpeg444; older than PNG: without png; older than PNG_RUNS: without png_runs; older than JPEG_OPT: without jpeg_opt,jpeg444_opt — the formats on per-frame Huffman tables, whose marks are jpeg_count, jpeg_tables, jpeg_code, jpeg_pack).  --scales adds every format again per scale above 1 (poppy_hip_set_frame_scale: the
+--formats leaves formats out (a library older than GIF: bgr,i420,pal8,pal8_seq; older than JPEG: without jpeg; older than JPEG444: without jpeg444; older than PNG: without png; older than PNG_RUNS: without png_runs; older than PNG_OPT: without png_opt; older than JPEG_OPT: without jpeg_opt,jpeg444_opt — the formats on per-frame Huffman tables, whose marks are jpeg_count, jpeg_tables, jpeg_code, jpeg_pack).  --scales adds every format again per scale above 1 (poppy_hip_set_frame_scale: the
 column "gif@2" is GIF at scale 2), alternated with the others in the same process; --kernel-scales adds k_bgr_downscale's own time (timing mode 1: frame_scale) under BGR
 at 1080p and 4K for those factors.  --size OWxOH adds every format again at that size (poppy_hip_set_frame_size: the column "i420@1280x720"); the 4K rows of such a
 column use --size-4k (default: --size), and its timing mode 1 entry has the resize kernel's time (frame_resize).  GIF's d2h_ceiling entry is its CAPACITY (poppy_frame_bytes); a frame's copy moves its own
@@ -36,7 +36,7 @@ from poppy_amd import capi, synth  # noqa: E402
 
 ALL_FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420), ("pal8", capi.FRAME_PAL8), ("pal8_seq", capi.FRAME_PAL8_SEQ), ("gif", capi.FRAME_GIF), ("jpeg", capi.FRAME_JPEG),
             ("jpeg444", capi.FRAME_JPEG444), ("png", getattr(capi, "FRAME_PNG", 1024)), ("png_runs", getattr(capi, "FRAME_PNG_RUNS", 2048)),
-            ("jpeg_opt", getattr(capi, "FRAME_JPEG_OPT", 4096)), ("jpeg444_opt", getattr(capi, "FRAME_JPEG444_OPT", 8192)))
+            ("jpeg_opt", getattr(capi, "FRAME_JPEG_OPT", 4096)), ("jpeg444_opt", getattr(capi, "FRAME_JPEG444_OPT", 8192)), ("png_opt", getattr(capi, "FRAME_PNG_OPT", 16384)))
 
 
 PNG_MARKS = ("png_filter", "png_cost", "png_scan", "png_pack", "png_crc", "png_finish")
@@ -87,7 +87,7 @@ def main():
     ap.add_argument("--steps-4k", type=int, default=3)
     ap.add_argument("--contexts", type=int, default=6)
     ap.add_argument("--rows", default="pool_1080p,pool_4k,job480,chained,chained_frame,d2h_ceiling")
-    ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq,gif,jpeg,jpeg444,png,png_runs,jpeg_opt,jpeg444_opt")
+    ap.add_argument("--formats", default="bgr,i420,pal8,pal8_seq,gif,jpeg,jpeg444,png,png_runs,jpeg_opt,jpeg444_opt,png_opt")
     ap.add_argument("--jpeg-quality", type=int, default=capi.JPEG_QUALITY_DEFAULT)
     ap.add_argument("--scales", default="1")
     ap.add_argument("--kernel-scales", default="")

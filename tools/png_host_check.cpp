@@ -1,7 +1,7 @@
-// png_host_check.cpp — the host statements of POPPY_FRAME_PNG (poppy_amd/csrc/frame_png.cpp) and POPPY_FRAME_PNG_RUNS (frame_png_runs.cpp) alone, on the
-// host, under a sanitizer:
+// png_host_check.cpp — the host statements of POPPY_FRAME_PNG (poppy_amd/csrc/frame_png.cpp), POPPY_FRAME_PNG_RUNS (frame_png_runs.cpp) and POPPY_FRAME_PNG_OPT
+// (frame_png_opt.cpp) alone, on the host, under a sanitizer:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tools/png_host_check.cpp poppy_amd/csrc/frame_png.cpp \
-//       poppy_amd/csrc/frame_png_runs.cpp poppy_amd/csrc/frame_sink.cpp poppy_amd/csrc/frame_jpeg.cpp poppy_amd/csrc/frame_i444.cpp poppy_amd/csrc/frame_gif.cpp poppy_amd/csrc/frame_pal8.cpp \
+//       poppy_amd/csrc/frame_png_runs.cpp poppy_amd/csrc/frame_png_opt.cpp poppy_amd/csrc/frame_sink.cpp poppy_amd/csrc/frame_jpeg.cpp poppy_amd/csrc/frame_i444.cpp poppy_amd/csrc/frame_gif.cpp poppy_amd/csrc/frame_pal8.cpp \
 //       -o /tmp/png_asan && /tmp/png_asan
 // Every frame is coded from a BGR buffer of exactly its own size into a heap buffer of EXACTLY poppy_frame_bytes(POPPY_FRAME_PNG, w, h) bytes, so a byte written
 // behind the capacity or read outside the frame is the sanitizer's to report; a second run into a canary-filled buffer checks that nothing behind `total` is
@@ -10,7 +10,9 @@
 // frame's own bytes: IDAT's CRC-32 from raw remainders of 32-byte pieces counted from the chunk's end, multiplied into place modulo the generator, and Adler-32
 // from per-segment sums.  POPPY_FRAME_PNG_RUNS: the same frames (and black ones, which are all matches) through poppy_bgr_to_png_runs_frame into a buffer of
 // exactly THAT format's capacity, the canary run, the same CRC check, and the frame decoded by a plain inflate of its blocks (literals, and matches at distance
-// 1 only) back to POPPY_FRAME_PNG's filtered stream.  Returns 0 when everything holds.
+// 1 only) back to POPPY_FRAME_PNG's filtered stream.  POPPY_FRAME_PNG_OPT: the same through poppy_bgr_to_png_opt_frame into a buffer of exactly PNG_RUNS' capacity,
+// never longer than the PNG_RUNS frame, decoded by an inflate that reads every block's header (the own ones are run-coded).  poppy_png_optimal_lengths: count
+// families — deep trees, ties, one symbol, as many as the limit holds — into buffers of exactly n_symbols bytes, the Kraft sum exactly 1.  Returns 0 when everything holds.
 #include "../include/poppy_hip.h"
 #include "../poppy_amd/csrc/png_runs_tables.h"
 #include <cstdint>
@@ -137,6 +139,80 @@ static bool decode_runs_stream(const uint8_t* frame, size_t end, size_t n, std::
     return out->size() == n && (bit + 7) / 8 == end;
 }
 
+// the same for a POPPY_FRAME_PNG_OPT frame: every block's code is read from its header (RFC 1951, 3.2.7), the fixed tables' and the own ones alike
+static bool decode_opt_stream(const uint8_t* frame, size_t end, size_t n, std::vector<uint8_t>* out) {
+    namespace R = poppy_hip::png_runs;
+    static const int base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+    static const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    size_t bit = 8 * kStreamByte;
+    bool short_of_bits = false;
+    auto take = [&](int count) {
+        uint32_t v = 0;
+        for (int i = 0; i < count; ++i, ++bit) { if ((bit >> 3) >= end) { short_of_bits = true; return 0u; } v |= (uint32_t)(frame[bit >> 3] >> (bit & 7) & 1u) << i; }
+        return v;
+    };
+    // a symbol of the canonical code of `lengths` (n_sym of them), read bit by bit, most significant bit first
+    auto symbol = [&](const int* lengths, int n_sym) {
+        int code = 0, first = 0;
+        for (int len = 1; len <= 15; ++len) {
+            code |= (int)take(1);
+            int count = 0;
+            for (int v = 0; v < n_sym; ++v) count += lengths[v] == len;
+            if (code - count < first) {
+                int k = code - first;
+                for (int v = 0; v < n_sym; ++v) if (lengths[v] == len && k-- == 0) return v;
+            }
+            first += count; first <<= 1; code <<= 1;
+        }
+        return -1;
+    };
+    out->clear();
+    for (bool last = false; !last;) {
+        last = take(1) != 0;
+        if (take(2) != 2) return false;
+        const int hlit = (int)take(5) + 257, hdist = (int)take(5) + 1, hclen = (int)take(4) + 4;
+        if (hlit > R::kSymbols || hdist != 1) return false;
+        int cl[19] = {}, lengths[R::kSymbols + 1] = {};
+        for (int i = 0; i < hclen; ++i) cl[order[i]] = (int)take(3);
+        for (int i = 0; i < hlit + 1;) {
+            const int s = symbol(cl, 19);
+            if (s < 0 || short_of_bits) return false;
+            if (s < 16) { lengths[i++] = s; continue; }
+            const int repeat = s == 16 ? 3 + (int)take(2) : s == 17 ? 3 + (int)take(3) : 11 + (int)take(7), value = s == 16 ? (i ? lengths[i - 1] : -1) : 0;
+            if (value < 0 || i + repeat > hlit + 1) return false;
+            for (int k = 0; k < repeat; ++k) lengths[i++] = value;
+        }
+        if (lengths[hlit] != 1 || lengths[R::kEob] == 0) return false;      // the one distance code
+        for (size_t in_block = 0;;) {
+            const int s = symbol(lengths, hlit);
+            if (s < 0 || short_of_bits) return false;
+            if (s == R::kEob) break;
+            if (s < 256) { out->push_back((uint8_t)s); ++in_block; continue; }
+            const int length = base[s - 257] + (int)take(R::extra_bits_of_symbol(s));
+            if (take(1) != 0 || in_block == 0) return false;      // distance 1, never into the block before
+            out->insert(out->end(), (size_t)length, out->back());
+            in_block += (size_t)length;
+        }
+    }
+    return !short_of_bits && out->size() == n && (bit + 7) / 8 == end;
+}
+
+// poppy_png_optimal_lengths on n counts c(i) into a heap buffer of exactly n bytes: no length above the limit, zeros where the counts are, the Kraft sum exactly 1
+template <typename F>
+static bool lengths_hold(int n, int limit, F&& c) {
+    std::vector<uint32_t> counts((size_t)n);
+    std::vector<uint8_t> lengths((size_t)n);
+    int used = 0;
+    for (int i = 0; i < n; ++i) { counts[(size_t)i] = c(i); used += counts[(size_t)i] != 0; }
+    if (poppy_png_optimal_lengths(counts.data(), n, limit, lengths.data()) != POPPY_OK) return false;
+    unsigned long long kraft = 0;
+    for (int i = 0; i < n; ++i) {
+        if ((lengths[(size_t)i] != 0) != (counts[(size_t)i] != 0) || lengths[(size_t)i] > limit) return false;
+        if (lengths[(size_t)i]) kraft += 1ull << (limit - lengths[(size_t)i]);
+    }
+    return used == 1 ? kraft == 1ull << (limit - 1) : kraft == 1ull << limit;
+}
+
 int main() {
     const int sizes[][2] = {{1, 1}, {1, 5}, {5, 1}, {63, 3}, {64, 3}, {65, 3}, {682, 4}, {683, 4}, {341, 8}, {341, 128}, {21, 130}, {333, 97}, {40, 137}};
     int failures = 0, frames = 0;
@@ -177,8 +253,35 @@ int main() {
             }
             if (!runs_ok) { fprintf(stderr, "%d x %d, content %d, runs: rc %d, total %zu of %zu\n", w, h, content, runs_rc, runs_total, runs_cap); ++failures; }
             if (runs_total * fullest_cap > fullest * runs_cap) { fullest = runs_total; fullest_cap = runs_cap; }
+            // the own-table format into a buffer of exactly the run format's capacity: never longer than the run format's frame, and the same stream
+            std::vector<uint8_t> opt(runs_cap), opt_again(runs_cap + 64, 0xA5), opt_stream;
+            const int opt_rc = poppy_bgr_to_png_opt_frame(bgr.data(), (size_t)w * 3, w, h, opt.data());
+            const size_t opt_total = poppy_png_frame_bytes(opt.data());
+            ++frames;
+            bool opt_ok = runs_ok && opt_rc == POPPY_OK && poppy_frame_bytes(POPPY_FRAME_PNG_OPT, w, h) == runs_cap && opt_total >= kFrameMinBytes && opt_total <= runs_total;
+            if (opt_ok) {
+                const size_t end = opt_total - kTailBytes;
+                opt_ok = poppy_bgr_to_png_opt_frame(bgr.data(), (size_t)w * 3, w, h, opt_again.data()) == POPPY_OK;
+                for (size_t i = 0; i < opt_again.size() && opt_ok; ++i) opt_ok = opt_again[i] == (i < opt_total ? opt[i] : 0xA5);
+                opt_ok = opt_ok && be32(opt.data() + kOffIdat) == end + 4 - (kOffIdatType + 4) && crc_in_pieces(opt.data(), end) == be32(opt.data() + end + 4);
+                opt_ok = opt_ok && decode_opt_stream(opt.data(), end, n, &opt_stream) && opt_stream == stream && adler_in_segments(opt_stream) == be32(opt.data() + end);
+            }
+            if (!opt_ok) { fprintf(stderr, "%d x %d, content %d, own tables: rc %d, total %zu, the run format's %zu\n", w, h, content, opt_rc, opt_total, runs_total); ++failures; }
         }
     }
+    // the length rule alone: Fibonacci counts (depth n - 1), equal counts (every merge a tie), one symbol, a ramp, as many symbols as 7 bits hold
+    uint32_t fib[47] = {1, 1};
+    for (int i = 2; i < 47; ++i) fib[i] = fib[i - 1] + fib[i - 2];
+    int rules = 0;
+    for (int n : {2, 9, 17, 18, 40, 45}) for (int limit : {7, 15}) { ++rules; if (!lengths_hold(n, limit, [&](int i) { return fib[i]; })) { fprintf(stderr, "lengths: %d Fibonacci counts at %d\n", n, limit); ++failures; } }
+    for (int n : {1, 2, 3, 19, 127, 128, 286}) { ++rules; if (!lengths_hold(n, n > 128 ? 15 : 7, [](int) { return 5u; })) { fprintf(stderr, "lengths: %d equal counts\n", n); ++failures; } }
+    for (int n : {1, 5, 286}) { ++rules; if (!lengths_hold(n, 15, [&](int i) { return i == n - 1 ? 9u : 0u; })) { fprintf(stderr, "lengths: one symbol of %d\n", n); ++failures; } }
+    ++rules; if (!lengths_hold(286, 15, [](int i) { return (uint32_t)(i % 7 ? i + 1 : 0); })) { fprintf(stderr, "lengths: a ramp with holes\n"); ++failures; }
+    { uint8_t one[1]; const uint32_t zero[2] = {0, 0}, big[2] = {1u << 31, 1u << 31}; std::vector<uint32_t> many(129, 1u); std::vector<uint8_t> out(129);
+      ++rules;
+      if (poppy_png_optimal_lengths(zero, 2, 15, one) != POPPY_E_ARG || poppy_png_optimal_lengths(big, 2, 15, one) != POPPY_E_ARG || poppy_png_optimal_lengths(zero, 0, 15, one) != POPPY_E_ARG ||
+          poppy_png_optimal_lengths(many.data(), 129, 7, out.data()) != POPPY_E_ARG || poppy_png_optimal_lengths(many.data(), 19, 8, out.data()) != POPPY_E_ARG) { fprintf(stderr, "lengths: a refusal is missing\n"); ++failures; } }
+    printf("%d count families through the length rule\n", rules);
     printf("%d frames coded into buffers of exactly the capacity, %d failures; the fullest used %zu of %zu bytes\n", frames, failures, fullest, fullest_cap);
     return failures ? 1 : 0;
 }
