@@ -350,6 +350,38 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * gather —, download of `total` bytes): the same bytes.  poppy_hip_set_jpeg_quality serves these formats too, and they apply wherever JPEG applies, under
  * poppy_hip_set_frame_scale and poppy_hip_set_frame_size as the host statement at the writer's geometry, and stay BGR wherever JPEG stays BGR.
  *
+ * POPPY_FRAME_JPEG_SEQ (32768) and POPPY_FRAME_JPEG444_SEQ (65536): POPPY_FRAME_JPEG_OPT and POPPY_FRAME_JPEG444_OPT on ONE set of four Huffman tables for all
+ * the frames a call hands to its writer, as POPPY_FRAME_PAL8_SEQ is PAL8 on one palette: one table build per sequence instead of one per frame.  32767, 32769,
+ * 65535 and 65537 stay unknown in both enums; there is no sink value of their own: POPPY_SINK_MJPEG takes the frames.  Layout and writer call are JPEG_OPT's,
+ * poppy_jpeg_frame_bytes reads `total`.  The rule is POPPY_FRAME_JPEG_OPT (JPEG444_OPT) word for word, except:
+ *   Counts.  The four count tables (DC 0, AC 0, DC 1, AC 1) are the element-wise sums, over all frames of the sequence, of the counts POPPY_FRAME_JPEG_OPT
+ *      defines for each frame.  One call of the unchanged table rule (poppy_jpeg_optimal_table) per table gives the sequence's tables.  A symbol that some
+ *      frame never emits still has a code, because another frame gave it a count; a symbol no frame emits has none.
+ *   Frames.  Every frame is a complete baseline JFIF file in JPEG_OPT's layout — `total`, the header with ONE DHT segment naming the four tables, DRI, SOS, the
+ *      restart intervals, EOI — and stands alone, so that MJPEG players open it.  All frames of a sequence carry the same header bytes: width, height, quality,
+ *      DHT and so the data's offset are identical.  A sequence of one frame is byte for byte that frame's POPPY_FRAME_JPEG_OPT (JPEG444_OPT) frame, and every
+ *      frame decodes to exactly the pixels of its POPPY_FRAME_JPEG (JPEG444) frame.
+ *   Capacity, least, stride.  JPEG_OPT's: the derivation uses only "a code has at most 16 bits, a DC code at most 12", which holds for any counts.
+ *      poppy_frame_bytes(POPPY_FRAME_JPEG_SEQ, w, h) = poppy_frame_bytes(POPPY_FRAME_JPEG_OPT, w, h), the smallest frame has 276 bytes, the writer is told stride 0.
+ *   Limits.  Checked on the arguments alone, before any state changes, and refused with POPPY_E_UNSUPPORTED: JPEG_OPT's per frame; and for the sequence, with B
+ *      the number of 8 x 8 blocks of a frame over all components in the format's sampling (MCUs x 6 in 4:2:0, MCUs x 3 in 4:4:4), n_frames * B * 64 <=
+ *      POPPY_JPEG_SEQ_MAX_SYMBOLS = 2^32 - 2.  A block has at most 64 symbols, so every table's sum then stays below the table rule's own refusal and the device
+ *      keeps adding and merging in 32 bits.  That allows 1370 frames at 1080p in 4:2:0.
+ *   A sequence is exactly what it is under POPPY_FRAME_PAL8_SEQ: all frames one call hands to its writer — one pair's frames in poppy_hip_morph_list and in the
+ *      pool; the t = 0 / t = 1 copies of poppy_hip_render_phases and the phase-0 / phase-1 short-circuits (N copies of one image: its counts N times) count
+ *      among them.  The writer is first called after the last frame is rendered, and gets the frames in order.
+ * poppy_i420_frames_to_jpeg_seq_frames and poppy_i444_frames_to_jpeg_seq_frames are the host statements: n_frames frames of planes, frame k at planes +
+ * k * frame_stride, in three passes over the same coefficients — every frame counted into the sums, one build, every frame coded; frame k goes to dst +
+ * k * poppy_frame_bytes(format, width, height).  poppy_bgr_frames_to_jpeg_seq_frames and poppy_bgr_frames_to_jpeg444_seq_frames take poppy_bgr_frames_to_pal8's
+ * arguments and the quality, and are the conversion of every frame followed by them.  POPPY_E_ARG for a null pointer, n_frames < 1, an empty frame, a row stride
+ * below 3 * width, a frame_stride shorter than a frame (the planes' bytes; stride * (height - 1) + 3 * width) and a quality outside 1..100; POPPY_E_UNSUPPORTED
+ * for the limits; both before a byte is read.  poppy_hip_bgr_frames_to_jpeg_seq_frames and poppy_hip_bgr_frames_to_jpeg444_seq_frames do the same on the
+ * context's GPU, on a sequence that lives for the call (per frame: upload, raster kernel, counting kernel; one table build; per frame: coder, gather, download of
+ * `total` bytes): the same bytes; they need no resident pair and disturb neither one nor the context's own sequence.  poppy_hip_set_jpeg_quality serves these
+ * formats, poppy_hip_pool_set_frame_format takes them, and they apply wherever POPPY_FRAME_JPEG applies, under poppy_hip_set_frame_scale and
+ * poppy_hip_set_frame_size as the host statement at the writer's geometry (the tables are taken over the SCALED frames), and stay BGR wherever JPEG stays BGR
+ * (poppy_hip_morph_sharded, poppy_hip_morph_pairs).
+ *
  * POPPY_FRAME_PNG: the frame coded on the GPU as one PNG file, LOSSLESS: the file decodes to exactly the frame's pixels, at 1.5 - 3 times fewer bytes than BGR on
  * photograph-like frames.  Its value is 1024, and POPPY_SINK_PNG is 1024; 1023 and 1025 stay unknown in both enums.  Layout, little-endian:
  *     bytes 0..3     total: the whole frame's length in bytes, these four included (poppy_png_frame_bytes reads it)
@@ -455,6 +487,7 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
 #endif
 #define POPPY_JPEG_SEGMENT_BYTES (2 * ((6 * 1660 * POPPY_JPEG_RESTART_MCUS + 7) / 8) + 2)
 #define POPPY_JPEG_OPT_SEGMENT_BYTES (2 * ((6 * 1661 * POPPY_JPEG_RESTART_MCUS + 7) / 8) + 2)
+#define POPPY_JPEG_SEQ_MAX_SYMBOLS 0xfffffffeull      /* (n_frames * blocks of a frame * 64 at the most: POPPY_FRAME_JPEG_SEQ, Limits) */
 #define POPPY_JPEG444_RESTART_MCUS 16      /* (3 * 16 blocks = 6 * POPPY_JPEG_RESTART_MCUS: poppy_amd/csrc/jpeg_tables.h asserts it) */
 #define POPPY_JPEG_QUALITY_DEFAULT 90
 #define POPPY_PNG_SEGMENT_BYTES 8192
@@ -463,7 +496,7 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
 #define POPPY_PNG_RUN_MIN 8
 enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128, POPPY_FRAME_JPEG = 256,
        POPPY_FRAME_JPEG444 = 512, POPPY_FRAME_PNG = 1024, POPPY_FRAME_PNG_RUNS = 2048, POPPY_FRAME_JPEG_OPT = 4096,
-       POPPY_FRAME_JPEG444_OPT = 8192, POPPY_FRAME_PNG_OPT = 16384 };
+       POPPY_FRAME_JPEG444_OPT = 8192, POPPY_FRAME_PNG_OPT = 16384, POPPY_FRAME_JPEG_SEQ = 32768, POPPY_FRAME_JPEG444_SEQ = 65536 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
@@ -493,6 +526,12 @@ int poppy_bgr_to_jpeg444_opt_frame(const uint8_t* bgr, size_t stride, int width,
 int poppy_hip_i420_to_jpeg_opt_frame(poppy_hip_ctx* ctx, const uint8_t* i420, int width, int height, int quality, uint8_t* dst);
 int poppy_hip_i444_to_jpeg_opt_frame(poppy_hip_ctx* ctx, const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
 int poppy_hip_jpeg_optimal_table(poppy_hip_ctx* ctx, const uint32_t counts[256], uint8_t bits[16], uint8_t vals[256], int* n_vals);
+int poppy_i420_frames_to_jpeg_seq_frames(const uint8_t* i420, size_t frame_stride, int n_frames, int width, int height, int quality, uint8_t* dst);
+int poppy_i444_frames_to_jpeg_seq_frames(const uint8_t* i444, size_t frame_stride, int n_frames, int width, int height, int quality, uint8_t* dst);
+int poppy_bgr_frames_to_jpeg_seq_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality, uint8_t* dst);
+int poppy_bgr_frames_to_jpeg444_seq_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality, uint8_t* dst);
+int poppy_hip_bgr_frames_to_jpeg_seq_frames(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality, uint8_t* dst);
+int poppy_hip_bgr_frames_to_jpeg444_seq_frames(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality, uint8_t* dst);
 size_t poppy_png_frame_bytes(const uint8_t* frame);
 int poppy_png_table(int k, uint8_t lengths[257], uint8_t* header_bits, int* n_header_bits);
 int poppy_bgr_to_png_frame(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);

@@ -28,8 +28,9 @@ WRITE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int,
 FRAME_BGR, FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ, FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444 = 0, 1, 8, 16, 64, 128, 256, 512
 FRAME_PNG, FRAME_PNG_RUNS = 1024, 2048
 FRAME_JPEG_OPT, FRAME_JPEG444_OPT = 4096, 8192
+FRAME_JPEG_SEQ, FRAME_JPEG444_SEQ = 32768, 65536      # JPEG_OPT's frames on one Huffman table set for all the frames a call hands to its writer
 FRAME_PNG_OPT = 16384
-FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444, FRAME_PNG, FRAME_PNG_RUNS, FRAME_JPEG_OPT, FRAME_JPEG444_OPT, FRAME_PNG_OPT)      # a frame whose length its first four bytes hold
+FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444, FRAME_PNG, FRAME_PNG_RUNS, FRAME_JPEG_OPT, FRAME_JPEG444_OPT, FRAME_PNG_OPT, FRAME_JPEG_SEQ, FRAME_JPEG444_SEQ)      # a frame whose length its first four bytes hold
 JPEG_QUALITY_DEFAULT = 90
 SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED, SINK_GIF_GLOBAL_CODED, SINK_MJPEG = 0, 1, 2, 3, 8, 16, 64, 128, 256
 SINK_PNG = 1024
@@ -59,6 +60,8 @@ SYMBOLS = [
     "poppy_bgr_to_i444", "poppy_hip_bgr_to_i444", "poppy_i444_to_jpeg_frame", "poppy_bgr_to_jpeg444_frame", "poppy_hip_i444_to_jpeg_frame",
     "poppy_jpeg_optimal_table", "poppy_i420_to_jpeg_opt_frame", "poppy_i444_to_jpeg_opt_frame", "poppy_bgr_to_jpeg_opt_frame", "poppy_bgr_to_jpeg444_opt_frame",
     "poppy_hip_i420_to_jpeg_opt_frame", "poppy_hip_i444_to_jpeg_opt_frame", "poppy_hip_jpeg_optimal_table",
+    "poppy_i420_frames_to_jpeg_seq_frames", "poppy_i444_frames_to_jpeg_seq_frames", "poppy_bgr_frames_to_jpeg_seq_frames", "poppy_bgr_frames_to_jpeg444_seq_frames",
+    "poppy_hip_bgr_frames_to_jpeg_seq_frames", "poppy_hip_bgr_frames_to_jpeg444_seq_frames",
     "poppy_png_frame_bytes", "poppy_png_table", "poppy_bgr_to_png_frame", "poppy_hip_bgr_to_png_frame",
     "poppy_png_runs_table", "poppy_bgr_to_png_runs_frame", "poppy_hip_bgr_to_png_runs_frame",
     "poppy_png_optimal_lengths", "poppy_bgr_to_png_opt_frame", "poppy_hip_bgr_to_png_opt_frame", "poppy_hip_png_optimal_lengths",
@@ -225,6 +228,12 @@ def lib():
         L.poppy_bgr_to_jpeg444_opt_frame.argtypes = [vp, sz, i, i, i, vp]
         L.poppy_hip_i420_to_jpeg_opt_frame.argtypes = [vp, vp, i, i, i, vp]
         L.poppy_hip_i444_to_jpeg_opt_frame.argtypes = [vp, vp, i, i, i, vp]
+        L.poppy_i420_frames_to_jpeg_seq_frames.argtypes = [vp, sz, i, i, i, i, vp]
+        L.poppy_i444_frames_to_jpeg_seq_frames.argtypes = [vp, sz, i, i, i, i, vp]
+        L.poppy_bgr_frames_to_jpeg_seq_frames.argtypes = [vp, sz, sz, i, i, i, i, vp]
+        L.poppy_bgr_frames_to_jpeg444_seq_frames.argtypes = [vp, sz, sz, i, i, i, i, vp]
+        L.poppy_hip_bgr_frames_to_jpeg_seq_frames.argtypes = [vp, vp, sz, sz, i, i, i, i, vp]
+        L.poppy_hip_bgr_frames_to_jpeg444_seq_frames.argtypes = [vp, vp, sz, sz, i, i, i, i, vp]
         L.poppy_png_frame_bytes.restype = sz
         L.poppy_png_frame_bytes.argtypes = [vp]
         L.poppy_png_table.argtypes = [i, vp, vp, vp]
@@ -559,6 +568,44 @@ def bgr_frames_to_gif_frames(frames, row_pad=0, frame_pad=0):
     """Host-only: the library's GIF_SEQ frames of a sequence of n HxWx3 BGR frames (poppy_bgr_frames_to_gif_frames = bgr_frames_to_pal8, then pal8_to_gif_frame
     of every frame): a list of n flat uint8 arrays, each cut to its `total`.  row_pad / frame_pad: as in bgr_frames_to_pal8."""
     return _gif_frames(lib().poppy_bgr_frames_to_gif_frames, frames, row_pad, frame_pad)
+
+
+def _jpeg_seq_frames(call, what, fmt, n, w, h, chk=None):
+    """The frames of a JPEG sequence of format fmt out of call(dst), a list of n flat uint8 arrays, each cut to its `total`; chk: as in _coded_frame."""
+    if fmt not in (FRAME_JPEG_SEQ, FRAME_JPEG444_SEQ):
+        raise PoppyError(f"{what}: fmt is FRAME_JPEG_SEQ or FRAME_JPEG444_SEQ")
+    out = np.empty((max(n, 1), max(frame_bytes(fmt, w, h), 4)), np.uint8)
+    rc = call(_p(out))
+    if chk:
+        chk(rc, what)
+    elif rc:
+        raise PoppyError(f"poppy_{what}: {rc}")
+    return [f[:jpeg_frame_bytes(f)].copy() for f in out]
+
+
+def bgr_frames_to_jpeg_seq_frames(frames, quality=JPEG_QUALITY_DEFAULT, fmt=FRAME_JPEG_SEQ, row_pad=0, frame_pad=0):
+    """Host-only: the FRAME_JPEG_SEQ (fmt FRAME_JPEG444_SEQ: 4:4:4) frames of a sequence of n HxWx3 BGR frames (poppy_bgr_frames_to_jpeg_seq_frames,
+    poppy_bgr_frames_to_jpeg444_seq_frames): every frame's symbol counts summed, one Huffman table set, every frame a complete JFIF file on it.  A list of n flat
+    uint8 arrays, each cut to its `total`.  row_pad / frame_pad: as in bgr_frames_to_pal8."""
+    a, stride, frame_stride, n, w, h = _padded_frames(frames, row_pad, frame_pad)
+    call = lib().poppy_bgr_frames_to_jpeg444_seq_frames if fmt == FRAME_JPEG444_SEQ else lib().poppy_bgr_frames_to_jpeg_seq_frames
+    return _jpeg_seq_frames(lambda dst: call(_p(a), stride, frame_stride, n, w, h, int(quality), dst), "bgr_frames_to_jpeg_seq_frames", fmt, n, w, h)
+
+
+def planes_to_jpeg_seq_frames(planes, w, h, quality=JPEG_QUALITY_DEFAULT, fmt=FRAME_JPEG_SEQ, frame_pad=0):
+    """Host-only: the same from the planes (poppy_i420_frames_to_jpeg_seq_frames; fmt FRAME_JPEG444_SEQ: poppy_i444_frames_to_jpeg_seq_frames): `planes` is n flat
+    I420 (I444) frames, an n x bytes array; frame_pad: that many extra bytes between frames."""
+    a = np.ascontiguousarray(planes, np.uint8)
+    n, size = a.shape
+    want = 3 * w * h if fmt == FRAME_JPEG444_SEQ else frame_bytes(FRAME_I420, w, h)
+    if w > 0 and h > 0 and size != want:
+        raise PoppyError(f"planes_to_jpeg_seq_frames: a frame of planes has {want} bytes")
+    if frame_pad:
+        buf = np.full((n, size + int(frame_pad)), 0xA5, np.uint8)
+        buf[:, :size] = a
+        a = buf
+    call = lib().poppy_i444_frames_to_jpeg_seq_frames if fmt == FRAME_JPEG444_SEQ else lib().poppy_i420_frames_to_jpeg_seq_frames
+    return _jpeg_seq_frames(lambda dst: call(_p(a), a.shape[1], n, int(w), int(h), int(quality), dst), "planes_to_jpeg_seq_frames", fmt, n, w, h)
 
 
 def frame_scaled_size(w, h, factor):
@@ -1161,6 +1208,8 @@ class Context:
         FRAME_JPEG: every frame one baseline JPEG file, coded on the GPU at set_jpeg_quality's quality; flat arrays of each frame's own length (jpeg_frame_bytes).
         FRAME_JPEG444: the same with full-resolution chroma (4:4:4), coded from the frame's I444 planes.
         FRAME_JPEG_OPT, FRAME_JPEG444_OPT: the same files on Huffman tables built on the GPU from each frame's own symbols: the same pixels in fewer bytes.
+        FRAME_JPEG_SEQ, FRAME_JPEG444_SEQ: FRAME_JPEG_OPT's files on ONE table set for all the frames a call hands to its writer, built from their summed symbol
+        counts; the writer is first called after the last frame is rendered.
         FRAME_PNG: every frame one PNG file, lossless, coded on the GPU; flat arrays of each frame's own length (png_frame_bytes).
         FRAME_PNG_RUNS: the same with runs of equal bytes coded as matches: several times smaller on frames with flat or smooth regions.
         FRAME_PNG_OPT: FRAME_PNG_RUNS with every segment on the shortest of the eight tables and one built on the GPU from its own symbols: never larger."""
@@ -1222,6 +1271,14 @@ class Context:
         """The FRAME_GIF frame of a flat PAL8 frame, coded on this context's GPU (poppy_hip_pal8_to_gif_frame: upload, the two kernels, download): the bytes of
         the host's pal8_to_gif_frame."""
         return _pal8_to_gif(lambda *args: lib().poppy_hip_pal8_to_gif_frame(self.h, *args), pal8, w, h, self._chk)
+
+    def bgr_frames_to_jpeg_seq_frames(self, frames, quality=JPEG_QUALITY_DEFAULT, fmt=FRAME_JPEG_SEQ, row_pad=0, frame_pad=0):
+        """The FRAME_JPEG_SEQ (FRAME_JPEG444_SEQ) frames of a sequence of n HxWx3 BGR frames, coded on this context's GPU on a sequence that lives for the call
+        (poppy_hip_bgr_frames_to_jpeg_seq_frames: per frame upload, raster and counting kernels; one table build; per frame coder, gather and download): the bytes of
+        the host's bgr_frames_to_jpeg_seq_frames, as its list."""
+        a, stride, frame_stride, n, w, h = _padded_frames(frames, row_pad, frame_pad)
+        call = lib().poppy_hip_bgr_frames_to_jpeg444_seq_frames if fmt == FRAME_JPEG444_SEQ else lib().poppy_hip_bgr_frames_to_jpeg_seq_frames
+        return _jpeg_seq_frames(lambda dst: call(self.h, _p(a), stride, frame_stride, n, w, h, int(quality), dst), "bgr_frames_to_jpeg_seq_frames", fmt, n, w, h, self._chk)
 
     def bgr_frames_to_gif_frames(self, frames, row_pad=0, frame_pad=0):
         """The FRAME_GIF_SEQ frames of a sequence of n HxWx3 BGR frames, palette and coding on this context's GPU (poppy_hip_bgr_frames_to_gif_frames: upload, the

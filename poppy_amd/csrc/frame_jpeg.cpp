@@ -194,32 +194,29 @@ size_t write_opt_header(int quality, int w, int h, Sampling s, int restart, cons
     return (size_t)(p - dst) + (kHeaderBytes - kOffDri);
 }
 
-// the frame of the planes of sampling `s` with restart intervals of `restart` MCUs (the header's DRI names it), on the Annex K tables or (opt) on the tables
-// of the frame's own counts: the counting pass, the table rule, and the same coding pass over the same coefficients on what it gave; returns `total`
-size_t encode(const uint8_t* planes, int w, int h, int quality, Sampling s, int restart, bool opt, uint8_t* dst) {
-    const FrameBlocks frame(planes, w, h, quality, s);
-    HuffTables built{};
-    size_t at = kFrameData;
-    if (opt) {
-        SymbolCounts counts{};
-        CountSink counter{counts};
-        walk_segments(frame, restart, counter, [](int) {}, [](int, bool) {});
-        uint8_t bits[4][16], vals[4][256];
-        int n[4];
-        for (int k = 0; k < 4; ++k) {
-            uint32_t c[256] = {};
-            memcpy(c, table_of(counts, k), sizeof(uint32_t) * table_symbols(k));
-            poppy_jpeg_optimal_table(c, bits[k], vals[k], &n[k]);      // (every table of every frame has a symbol, and a frame the format accepts stays below the sum's limit)
-            huff_fill(bits[k], vals[k], table_of(built, k));
-        }
-        at = 4 + write_opt_header(quality, w, h, s, restart, bits, vals, n, dst + 4);
-    } else {
-        write_header(quality, w, h, dst + 4);
-        dst[4 + kOffSofSampling] = sof_sampling(s);
-        put16(dst + 4 + kOffDri + 4, restart);
+// the counting pass of one frame: every symbol the coder emits for it, added into `counts`
+void count_frame(const FrameBlocks& frame, int restart, SymbolCounts& counts) {
+    CountSink counter{counts};
+    walk_segments(frame, restart, counter, [](int) {}, [](int, bool) {});
+}
+
+// the four tables of the rule on `counts`, as the coder looks them up (`built`), and the OPT header that names them at dst; returns its length
+size_t build_opt_tables(SymbolCounts& counts, int quality, int w, int h, Sampling s, int restart, HuffTables* built, uint8_t* dst) {
+    uint8_t bits[4][16], vals[4][256];
+    int n[4];
+    for (int k = 0; k < 4; ++k) {
+        uint32_t c[256] = {};
+        memcpy(c, table_of(counts, k), sizeof(uint32_t) * table_symbols(k));
+        poppy_jpeg_optimal_table(c, bits[k], vals[k], &n[k]);      // (every table of every frame has a symbol, and a frame or sequence the format accepts stays below the sum's limit)
+        huff_fill(bits[k], vals[k], table_of(*built, k));
     }
+    return write_opt_header(quality, w, h, s, restart, bits, vals, n, dst);
+}
+
+// the coding pass of one frame on `huff`: its segments from dst + at on (the header stands in front), then `total` into dst's first four bytes; returns it
+size_t code_frame(const FrameBlocks& frame, int restart, const HuffTables& huff, size_t at, uint8_t* dst) {
     BitString b;
-    BitSink coder{b, opt ? built : kHuff};
+    BitSink coder{b, huff};
     walk_segments(frame, restart, coder, [&](int) { b = BitString(); }, [&](int seg, bool last) {
         b.pad();
         for (uint8_t byte : b.bytes) { dst[at++] = byte; if (byte == 0xFF) dst[at++] = 0; }
@@ -230,11 +227,51 @@ size_t encode(const uint8_t* planes, int w, int h, int quality, Sampling s, int 
     return at;
 }
 
+// the frame of the planes of sampling `s` with restart intervals of `restart` MCUs (the header's DRI names it), on the Annex K tables or (opt) on the tables
+// of the frame's own counts: the counting pass, the table rule, and the same coding pass over the same coefficients on what it gave; returns `total`
+size_t encode(const uint8_t* planes, int w, int h, int quality, Sampling s, int restart, bool opt, uint8_t* dst) {
+    const FrameBlocks frame(planes, w, h, quality, s);
+    if (opt) {
+        SymbolCounts counts{};
+        HuffTables built{};
+        count_frame(frame, restart, counts);
+        const size_t header = build_opt_tables(counts, quality, w, h, s, restart, &built, dst + 4);
+        return code_frame(frame, restart, built, 4 + header, dst);
+    }
+    write_header(quality, w, h, dst + 4);
+    dst[4 + kOffSofSampling] = sof_sampling(s);
+    put16(dst + 4 + kOffDri + 4, restart);
+    return code_frame(frame, restart, kHuff, kFrameData, dst);
+}
+
 }  // namespace
 
 size_t encode_i420(const uint8_t* i420, int w, int h, int quality, int restart_mcus, uint8_t* dst) { return encode(i420, w, h, quality, k420, restart_mcus, false, dst); }
 size_t encode_planes(const uint8_t* planes, int w, int h, int quality, Sampling s, uint8_t* dst) { return encode(planes, w, h, quality, s, restart_mcus(s), false, dst); }
 size_t encode_planes_opt(const uint8_t* planes, int w, int h, int quality, Sampling s, uint8_t* dst) { return encode(planes, w, h, quality, s, restart_mcus(s), true, dst); }
+
+// POPPY_FRAME_JPEG_SEQ / JPEG444_SEQ: three passes over the same coefficients — every frame counted into the sequence's sums (`copies` times), one table build,
+// every frame coded on what it gave behind the one header
+void encode_planes_seq(const uint8_t* planes, size_t frame_stride, int n, int copies, int w, int h, int quality, Sampling s, uint8_t* dst, size_t dst_stride) {
+    const int restart = restart_mcus(s);
+    std::vector<FrameBlocks> frames;
+    for (int k = 0; k < n; ++k) frames.emplace_back(planes + (size_t)k * frame_stride, w, h, quality, s);
+    SymbolCounts sums{};
+    for (int k = 0; k < n; ++k) {
+        SymbolCounts one{};
+        count_frame(frames[k], restart, one);
+        for (int t = 0; t < 4; ++t)
+            for (int i = 0; i < table_symbols(t); ++i) table_of(sums, t)[i] += table_of(one, t)[i] * (uint32_t)copies;
+    }
+    HuffTables built{};
+    uint8_t header[kHeaderBytes];
+    const size_t header_bytes = build_opt_tables(sums, quality, w, h, s, restart, &built, header);
+    for (int k = 0; k < n; ++k) {
+        uint8_t* frame = dst + (size_t)k * dst_stride;
+        memcpy(frame + 4, header, header_bytes);
+        code_frame(frames[k], restart, built, 4 + header_bytes, frame);
+    }
+}
 
 }  // namespace jpeg
 }  // namespace poppy_hip
@@ -336,4 +373,51 @@ int poppy_bgr_to_jpeg444_opt_frame(const uint8_t* bgr, size_t stride, int width,
     return rc ? rc : poppy_i444_to_jpeg_opt_frame(i444.data(), width, height, quality, dst);
 }
 
+// POPPY_FRAME_JPEG_SEQ and POPPY_FRAME_JPEG444_SEQ (include/poppy_hip.h): the refusals, all from the arguments alone
+static int jpeg_seq_refuses(const void* src, const void* dst, size_t frame_stride, size_t frame_bytes, int n_frames, int width, int height, int quality, poppy_hip::jpeg::Sampling s) {
+    if (!src || !dst || n_frames < 1 || width <= 0 || height <= 0 || frame_stride < frame_bytes || quality < 1 || quality > 100) return POPPY_E_ARG;
+    return jpeg_opt_fits(width, height, s) && jpeg_seq_fits(n_frames, width, height, s) ? POPPY_OK : POPPY_E_UNSUPPORTED;
+}
+static int planes_to_jpeg_seq(const uint8_t* planes, size_t frame_stride, int n_frames, int width, int height, int quality, poppy_hip::jpeg::Sampling s, uint8_t* dst) {
+    const bool is444 = s == poppy_hip::jpeg::k444;
+    if (width <= 0 || height <= 0) return POPPY_E_ARG;
+    if (const int rc = jpeg_seq_refuses(planes, dst, frame_stride, raster_bytes(is444 ? kRasterI444 : kRasterI420, (size_t)width, (size_t)height), n_frames, width, height, quality, s)) return rc;
+    poppy_hip::jpeg::encode_planes_seq(planes, frame_stride, n_frames, 1, width, height, quality, s, dst, (size_t)poppy_hip::jpeg::opt_frame_capacity((size_t)width, (size_t)height, s));
+    return POPPY_OK;
+}
+int poppy_i420_frames_to_jpeg_seq_frames(const uint8_t* i420, size_t frame_stride, int n_frames, int width, int height, int quality, uint8_t* dst) {
+    return planes_to_jpeg_seq(i420, frame_stride, n_frames, width, height, quality, poppy_hip::jpeg::k420, dst);
+}
+int poppy_i444_frames_to_jpeg_seq_frames(const uint8_t* i444, size_t frame_stride, int n_frames, int width, int height, int quality, uint8_t* dst) {
+    return planes_to_jpeg_seq(i444, frame_stride, n_frames, width, height, quality, poppy_hip::jpeg::k444, dst);
+}
+
+static int bgr_frames_to_jpeg_seq(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality, poppy_hip::jpeg::Sampling s, uint8_t* dst) {
+    if (width <= 0 || height <= 0 || stride < (size_t)width * 3) return POPPY_E_ARG;
+    if (const int rc = jpeg_seq_refuses(bgr, dst, frame_stride, stride * ((size_t)height - 1) + (size_t)width * 3, n_frames, width, height, quality, s)) return rc;
+    const bool is444 = s == poppy_hip::jpeg::k444;
+    const size_t place = raster_bytes(is444 ? kRasterI444 : kRasterI420, (size_t)width, (size_t)height);
+    std::vector<uint8_t> planes(place * (size_t)n_frames);
+    for (int k = 0; k < n_frames; ++k)
+        if (const int rc = (is444 ? poppy_bgr_to_i444 : poppy_bgr_to_i420)(bgr + (size_t)k * frame_stride, stride, width, height, planes.data() + (size_t)k * place)) return rc;
+    return planes_to_jpeg_seq(planes.data(), place, n_frames, width, height, quality, s, dst);
+}
+int poppy_bgr_frames_to_jpeg_seq_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality, uint8_t* dst) {
+    return bgr_frames_to_jpeg_seq(bgr, stride, frame_stride, n_frames, width, height, quality, poppy_hip::jpeg::k420, dst);
+}
+int poppy_bgr_frames_to_jpeg444_seq_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality, uint8_t* dst) {
+    return bgr_frames_to_jpeg_seq(bgr, stride, frame_stride, n_frames, width, height, quality, poppy_hip::jpeg::k444, dst);
+}
+
 }  // extern "C"
+
+// writer_image.h: a sequence that is n_copies times the same frame; that frame once in dst
+int jpeg_seq_of_copies(const uint8_t* bgr, size_t stride, int n_copies, int width, int height, int quality, int format, uint8_t* dst) {
+    const poppy_hip::jpeg::Sampling s = format == POPPY_FRAME_JPEG444_SEQ ? poppy_hip::jpeg::k444 : poppy_hip::jpeg::k420;
+    if (width <= 0 || height <= 0 || stride < (size_t)width * 3) return POPPY_E_ARG;
+    if (const int rc = jpeg_seq_refuses(bgr, dst, 0, 0, n_copies, width, height, quality, s)) return rc;
+    std::vector<uint8_t> planes(raster_bytes(s == poppy_hip::jpeg::k444 ? kRasterI444 : kRasterI420, (size_t)width, (size_t)height));
+    if (const int rc = (s == poppy_hip::jpeg::k444 ? poppy_bgr_to_i444 : poppy_bgr_to_i420)(bgr, stride, width, height, planes.data())) return rc;
+    poppy_hip::jpeg::encode_planes_seq(planes.data(), 0, 1, n_copies, width, height, quality, s, dst, 0);
+    return POPPY_OK;
+}

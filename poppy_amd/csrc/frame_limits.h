@@ -21,6 +21,13 @@ inline bool coded_length_ok(size_t total, size_t capacity, size_t least) { retur
 inline bool jpeg_fits(int W, int H, poppy_hip::jpeg::Sampling s = poppy_hip::jpeg::k420) { return W <= 65535 && H <= 65535 && poppy_hip::jpeg::frame_capacity((size_t)W, (size_t)H, s) <= 0xffffffffull; }
 // ... and the same on per-frame tables (POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT), on their own capacity
 inline bool jpeg_opt_fits(int W, int H, poppy_hip::jpeg::Sampling s = poppy_hip::jpeg::k420) { return W <= 65535 && H <= 65535 && poppy_hip::jpeg::opt_frame_capacity((size_t)W, (size_t)H, s) <= 0xffffffffull; }
+// ... and a sequence of n such frames on one table set (POPPY_FRAME_JPEG_SEQ, POPPY_FRAME_JPEG444_SEQ): with B the blocks of a frame over all components, n * B * 64
+// symbols at the most, so that every summed table stays below the table rule's refusal and the device adds and merges in 32 bits (include/poppy_hip.h: Limits)
+inline bool jpeg_seq_fits(int n, int W, int H, poppy_hip::jpeg::Sampling s = poppy_hip::jpeg::k420) {
+    if (n < 1 || !jpeg_opt_fits(W, H, s)) return false;
+    const unsigned long long per_frame = (unsigned long long)poppy_hip::jpeg::mcu_count((size_t)W, (size_t)H, s) * poppy_hip::jpeg::mcu_blocks(s) * 64ull;      // (< 2^30: the count bound)
+    return (unsigned long long)n <= POPPY_JPEG_SEQ_MAX_SYMBOLS / per_frame;
+}
 // A PNG-coded frame: what the format takes is a capacity (png_tables.h; with runs coded as matches png_runs_tables.h) below 2^31 bytes, which IDAT's length field and `total` hold
 inline bool png_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
 inline bool png_runs_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png_runs::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
@@ -35,9 +42,9 @@ struct FormatTraits {
     FrameRaster raster;
     FrameCoder coder;
     int variant;               // the JPEG coder's sampling (jpeg::Sampling); the PNG coder's tokens and tables (png::Variant): literals, runs as matches, or those on the segments' own tables
-    bool frame_tables;         // the JPEG coder's Huffman tables: the Annex K examples (false), or four tables built from this frame's own symbol counts
-    bool sequence;             // one palette for all the frames a call hands to its writer: they wait in the sequence store until the last is rendered (palette_seq.h),
-                               // and no slot converts or codes them — the sequence pass and the sequence's coder do
+    bool frame_tables;         // the JPEG coder's Huffman tables: the Annex K examples (false), or four tables built from symbol counts — this frame's own, or (sequence) the sequence's sums
+    bool sequence;             // one palette (PAL8) or one Huffman table set (JPEG) for all the frames a call hands to its writer: they wait in the sequence store until the last
+                               // is rendered (palette_seq.h), and no slot converts or codes them — the sequence pass and the sequence's coder do
     size_t least;              // the smallest `total` its coder gives (coded_length_ok's lower bound)
     // a frame whose length its bytes decide: poppy_frame_bytes is its capacity, the writer is told stride 0, a pinned word holds its length
     constexpr bool coded() const { return coder != kCoderNone; }
@@ -59,6 +66,8 @@ inline constexpr FormatTraits kFormats[] = {
     {POPPY_FRAME_JPEG444,     "JPEG", kRasterI444, kCoderJpeg, poppy_hip::jpeg::k444, false, false, poppy_hip::jpeg::kFrameMinBytes},      // (twice the blocks)
     {POPPY_FRAME_JPEG_OPT,    "JPEG", kRasterI420, kCoderJpeg, poppy_hip::jpeg::k420, true,  false, poppy_hip::jpeg::kOptFrameMinBytes},   // the header with four one-symbol tables, a byte of data, EOI
     {POPPY_FRAME_JPEG444_OPT, "JPEG", kRasterI444, kCoderJpeg, poppy_hip::jpeg::k444, true,  false, poppy_hip::jpeg::kOptFrameMinBytes},
+    {POPPY_FRAME_JPEG_SEQ,    "JPEG", kRasterI420, kCoderJpeg, poppy_hip::jpeg::k420, true,  true,  poppy_hip::jpeg::kOptFrameMinBytes},   // JPEG_OPT's frames on one table set per sequence
+    {POPPY_FRAME_JPEG444_SEQ, "JPEG", kRasterI444, kCoderJpeg, poppy_hip::jpeg::k444, true,  true,  poppy_hip::jpeg::kOptFrameMinBytes},
     {POPPY_FRAME_PNG,         "PNG",  kRasterNone, kCoderPng,  0,                     false, false, poppy_hip::png::kFrameMinBytes},       // the file's fixed parts and one byte of deflate data
     {POPPY_FRAME_PNG_RUNS,    "PNG",  kRasterNone, kCoderPng,  poppy_hip::png::kRuns, false, false, poppy_hip::png::kFrameMinBytes},       // PNG with runs coded as matches, the same limits on its own capacity
     {POPPY_FRAME_PNG_OPT,     "PNG",  kRasterNone, kCoderPng,  poppy_hip::png::kRunsOwn, false, false, poppy_hip::png::kFrameMinBytes},    // PNG_RUNS with a ninth table per segment, built from its counts: PNG_RUNS' limits and capacity
@@ -92,7 +101,7 @@ inline size_t frame_bytes(const FormatTraits& t, int W, int H) {
 // every constant of include/poppy_hip.h has exactly one record, and the records hold what the code relies on
 constexpr bool formats_hold() {
     constexpr int all[] = {POPPY_FRAME_BGR, POPPY_FRAME_I420, POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF, POPPY_FRAME_GIF_SEQ, POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444,
-                           POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT, POPPY_FRAME_PNG_OPT};
+                           POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT, POPPY_FRAME_PNG_OPT, POPPY_FRAME_JPEG_SEQ, POPPY_FRAME_JPEG444_SEQ};
     if (sizeof all / sizeof *all != sizeof kFormats / sizeof *kFormats) return false;
     for (int fmt : all) {
         int n = 0;
@@ -101,7 +110,8 @@ constexpr bool formats_hold() {
     }
     for (const FormatTraits& t : kFormats) {
         if (t.sequence && (t.slot_coder() != kCoderNone || t.slot_raster() != kRasterNone)) return false;      // a sequence format has no per-slot coder (and no raster step)
-        if (t.sequence && (t.raster != kRasterPal8 || (t.coder != kCoderNone && t.coder != kCoderGif))) return false;      // ... and is PAL8 under one palette, bare or GIF-coded (palette_seq.cpp)
+        const bool palette_seq = t.raster == kRasterPal8 && (t.coder == kCoderNone || t.coder == kCoderGif), table_seq = t.coder == kCoderJpeg && t.frame_tables;
+        if (t.sequence && !palette_seq && !table_seq) return false;      // ... and is PAL8 under one palette, bare or GIF-coded, or JPEG under one table set (palette_seq.cpp)
         if ((format_stride(t, 1) == 0) != t.coded()) return false;      // only a coded format reports stride 0
         if (t.coded() != (t.least > 0)) return false;                   // ... and it alone has a smallest `total`
         if (t.coder == kCoderGif && t.raster != kRasterPal8) return false;      // the coders read their raster form: GIF PAL8, JPEG the planes of its sampling, PNG the BGR frame

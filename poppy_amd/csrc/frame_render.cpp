@@ -96,12 +96,15 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     // PNG (and PNG_RUNS, PNG_OPT) is six dispatches straight behind the unsharp, on the chain's own stream as JPEG's: the two that are one workgroup's work (scan, finish) are short.
     // PAL8_SEQ (seq_dst: the frame's place in the sequence store, never set in a captured body): the pass takes PAL8's place, on the side stream too — it is short,
     // but the chain needs nothing of it.
+    // JPEG_SEQ and JPEG444_SEQ: the pass is the raster kernel into the store and the counting kernel on it, 27 - 38 us at 1080p and nothing of it one workgroup's serial
+    // work, so it stays on the chain's own stream as JPEG's coder does.  On the side stream it was measured at 2.8k chained frames/s against 5.0k here: `done` rides on the
+    // pass, the low-priority queue runs it late, and the slot's reuse waits for it ("JPEG sequence-table hand-off").
     // A scale above 1 or a size: the downscale (the resize) is the conversion's first dispatch wherever that runs, and a conversion of its own under BGR (the writer gets the slot's
     // scaled frame); the chain goes on from the full-size frame.
     const int fmt = frame_wants_format(c);
     const WriterGeom geom = frame_wants_geom(c);
     const FormatTraits& traits = *format_traits(fmt);
-    const bool side = (traits.slot_raster() == kRasterPal8 || seq_dst) && chained && done && !tm;
+    const bool side = (traits.slot_raster() == kRasterPal8 || (seq_dst && traits.raster == kRasterPal8)) && chained && done && !tm;
     const bool converts = traits.converts() || seq_dst || geom.scaled();
     launch_unsharp(f.pyrB, f.tmp, f.diff, f.out, debug ? f.unsharpF : nullptr, W, H, amount, (const float*)f.d_blob, (float)0.3, s,
                    side ? f.fmt.bgr_done : converts ? nullptr : done, c->levels[0].pitch);
@@ -113,7 +116,7 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     if (!seq_dst) { enqueue_conversion(fmt, geom, f.out, W, H, f.fmt, fs, done, tm); return POPPY_OK; }
     if (geom.scaled()) enqueue_conversion(POPPY_FRAME_BGR, geom, f.out, W, H, f.fmt, fs, nullptr, tm);
     { int rc = seq_pass(c, slot_bgr(f, geom), seq_dst, fs, done); if (rc) return rc; }
-    if (tm) tm->mark("pal8_seq_hist");
+    if (tm) tm->mark(seq_pass_mark(c));
     return POPPY_OK;
 }
 

@@ -144,6 +144,9 @@ inline unsigned long long opt_frame_capacity(size_t w, size_t h, Sampling s = k4
 constexpr size_t kOptFrameMinBytes = 4 + kOptHeaderFixed + 4 * (17 + 1) + 1 + 2;      // four one-symbol tables, a byte of entropy data, EOI
 // the host coder of either sampling on per-frame tables; returns `total`
 size_t encode_planes_opt(const uint8_t* planes, int w, int h, int quality, Sampling s, uint8_t* dst);
+// ... and on one table set per sequence (POPPY_FRAME_JPEG_SEQ, POPPY_FRAME_JPEG444_SEQ): n frames of planes frame_stride bytes apart, every frame standing for
+// `copies` of itself in the sums (the phase 0 / 1 copies; otherwise 1); frame k goes to dst + k * dst_stride
+void encode_planes_seq(const uint8_t* planes, size_t frame_stride, int n, int copies, int w, int h, int quality, Sampling s, uint8_t* dst, size_t dst_stride);
 
 }  // namespace jpeg
 }  // namespace poppy_hip

@@ -285,6 +285,13 @@ void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame
 hipError_t launch_jpeg_counts_clear(uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
 // the table build alone: `counts` is a frame's count tables (jpeg_tables.h: SymbolCounts) in device memory — zero afterwards —, `built` sizeof(jpeg::OptTables) bytes of it
 void launch_jpeg_table_build(uint32_t* counts, void* built, hipStream_t s);
+// The same kernels on tables that are not a scratch's own (POPPY_FRAME_JPEG_SEQ, POPPY_FRAME_JPEG444_SEQ: one table set per sequence).  launch_jpeg_count_into adds a
+// frame's symbols into `counts` (kJpegSeqTableBytes: a SymbolCounts, zero in front of the sequence's first frame; `done`, optional, rides on it), launch_jpeg_table_build
+// makes `built` from them, and the OPT coder and gather of every frame read `built` (never null here) beside the frame's own scratch (jpeg_scratch_bytes, opt).
+constexpr size_t kJpegSeqTableBytes = sizeof(jpeg::SymbolCounts) + sizeof(jpeg::OptTables);      // the sequence's counts, then its built tables
+void launch_jpeg_count_into(const uint8_t* planes, const void* tables, uint32_t* counts, int w, int h, jpeg::Sampling sm, hipStream_t s, hipEvent_t done = nullptr);
+void launch_jpeg_code_on(const uint8_t* planes, const void* tables, const void* built, uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
+void launch_jpeg_pack_on(const void* tables, const void* built, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, jpeg::Sampling sm, hipStream_t s, hipEvent_t done = nullptr);
 
 // a frame on the device (tight BGR) -> its I444 planes, 3 * w * h bytes (kernels_frame_i444.hip; poppy_bgr_to_i444 is the host statement): any w, h >= 1; `done`
 // (optional) rides on the dispatch

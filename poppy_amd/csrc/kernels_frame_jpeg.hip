@@ -477,40 +477,53 @@ size_t jpeg_scratch_bytes(int w, int h, Sampling sm, bool opt) {
     return ((n_seg * (kJpegOptSlotBytes + 4) + 15) & ~(size_t)15) + sizeof(OptTables) + sizeof(SymbolCounts) + 16;
 }
 
-void launch_jpeg_count(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
+void launch_jpeg_count_into(const uint8_t* planes, const void* tables, uint32_t* counts, int w, int h, Sampling sm, hipStream_t s, hipEvent_t done) {
     const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
     const int mw = (w + mcu_side(sm) - 1) / mcu_side(sm);
-    hipLaunchKernelGGL(sm == k444 ? k_jpeg_count<k444> : k_jpeg_count<k420>, dim3((unsigned)count_groups(n_seg)), dim3(64 * kCountWaves), 0, s, planes,
-                       (const QualityTables*)tables, jpeg_opt_counts(scratch, n_seg), w, h, mw, (int)mcu_count((size_t)w, (size_t)h, sm), (int)n_seg);
+    auto kernel = sm == k444 ? k_jpeg_count<k444> : k_jpeg_count<k420>;
+    const dim3 grid((unsigned)count_groups(n_seg)), block(64 * kCountWaves);
+    const int n_mcu = (int)mcu_count((size_t)w, (size_t)h, sm);
+    if (done) hipExtLaunchKernelGGL(kernel, grid, block, 0, s, nullptr, done, 0, planes, (const QualityTables*)tables, counts, w, h, mw, n_mcu, (int)n_seg);
+    else hipLaunchKernelGGL(kernel, grid, block, 0, s, planes, (const QualityTables*)tables, counts, w, h, mw, n_mcu, (int)n_seg);
+}
+void launch_jpeg_count(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
+    launch_jpeg_count_into(planes, tables, jpeg_opt_counts(scratch, segment_count((size_t)w, (size_t)h, sm)), w, h, sm, s, nullptr);
 }
 
+void launch_jpeg_table_build(uint32_t* counts, void* built, hipStream_t s) {
+    hipLaunchKernelGGL(k_jpeg_tables, dim3(1), dim3(256), 0, s, counts, (OptTables*)built);
+}
 void launch_jpeg_tables(uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
     const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
-    hipLaunchKernelGGL(k_jpeg_tables, dim3(1), dim3(256), 0, s, jpeg_opt_counts(scratch, n_seg), jpeg_opt_tables(scratch, n_seg));
+    launch_jpeg_table_build(jpeg_opt_counts(scratch, n_seg), jpeg_opt_tables(scratch, n_seg), s);
 }
 
 hipError_t launch_jpeg_counts_clear(uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
     return hipMemsetAsync(jpeg_opt_counts(scratch, segment_count((size_t)w, (size_t)h, sm)), 0, sizeof(SymbolCounts), s);
 }
 
-void launch_jpeg_table_build(uint32_t* counts, void* built, hipStream_t s) {
-    hipLaunchKernelGGL(k_jpeg_tables, dim3(1), dim3(256), 0, s, counts, (OptTables*)built);
-}
-
-void launch_jpeg_code(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, Sampling sm, bool opt, hipStream_t s) {
+// built: null for the Annex K tables, or the OptTables that a table build left — the scratch's own (launch_jpeg_code) or a sequence's (launch_jpeg_code_on)
+void launch_jpeg_code_on(const uint8_t* planes, const void* tables, const void* built, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
     const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
     const int mw = (w + mcu_side(sm) - 1) / mcu_side(sm);
+    const bool opt = built != nullptr;
     auto kernel = opt ? (sm == k444 ? k_jpeg_code<k444, true> : k_jpeg_code<k420, true>) : (sm == k444 ? k_jpeg_code<k444, false> : k_jpeg_code<k420, false>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)n_seg), dim3(64), 0, s, planes, (const QualityTables*)tables, opt ? &jpeg_opt_tables(scratch, n_seg)->huff : (const HuffTables*)nullptr,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_seg), dim3(64), 0, s, planes, (const QualityTables*)tables, opt ? &((const OptTables*)built)->huff : (const HuffTables*)nullptr,
                        scratch, jpeg_lengths(scratch, n_seg, opt), w, h, mw, (int)mcu_count((size_t)w, (size_t)h, sm));
 }
+void launch_jpeg_code(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, Sampling sm, bool opt, hipStream_t s) {
+    launch_jpeg_code_on(planes, tables, opt ? jpeg_opt_tables(scratch, segment_count((size_t)w, (size_t)h, sm)) : nullptr, scratch, w, h, sm, s);
+}
 
-void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, bool opt, hipStream_t s, hipEvent_t done) {
+void launch_jpeg_pack_on(const void* tables, const void* built, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, hipStream_t s, hipEvent_t done) {
     const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
-    uint8_t* sc = const_cast<uint8_t*>(scratch);
+    const bool opt = built != nullptr;
     hipExtLaunchKernelGGL(opt ? k_jpeg_pack<true> : k_jpeg_pack<false>, dim3((unsigned)((n_seg + kPackGroup - 1) / kPackGroup)), dim3(256), 0, s, nullptr, done, 0, scratch,
-                          jpeg_lengths(sc, n_seg, opt), (const QualityTables*)tables, opt ? jpeg_opt_tables(sc, n_seg) : (const OptTables*)nullptr, (int)n_seg, w, h,
+                          jpeg_lengths(const_cast<uint8_t*>(scratch), n_seg, opt), (const QualityTables*)tables, (const OptTables*)built, (int)n_seg, w, h,
                           (int)sof_sampling(sm), restart_mcus(sm), frame, total_host);
+}
+void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, bool opt, hipStream_t s, hipEvent_t done) {
+    launch_jpeg_pack_on(tables, opt ? jpeg_opt_tables(const_cast<uint8_t*>(scratch), segment_count((size_t)w, (size_t)h, sm)) : nullptr, scratch, frame, total_host, w, h, sm, s, done);
 }
 
 }  // namespace poppy_hip

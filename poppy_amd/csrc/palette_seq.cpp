@@ -1,6 +1,14 @@
-// palette_seq.cpp — the POPPY_FRAME_PAL8_SEQ / POPPY_FRAME_GIF_SEQ sequence (palette_seq.h): collecting a call's frames in the store, the palette, the two hand-over
-// loops through the writer ring, and the call-scoped sequence of poppy_hip_bgr_frames_to_gif_frames.
+// palette_seq.cpp — the sequence formats (palette_seq.h: POPPY_FRAME_PAL8_SEQ / GIF_SEQ on one palette, POPPY_FRAME_JPEG_SEQ / JPEG444_SEQ on one table set):
+// collecting a call's frames in the store, the palette or the tables, the two hand-over loops through the writer ring, and the call-scoped sequences of
+// poppy_hip_bgr_frames_to_gif_frames and poppy_hip_bgr_frames_to_jpeg_seq_frames.
 #include "context.h"
+
+// the context's sequence under a JPEG format: its record's sampling, its counts and its built tables (PaletteSeq::jpeg)
+static bool seq_is_jpeg(const poppy_hip_ctx* c) { return format_traits(c->frame_format)->coder == kCoderJpeg; }
+static uint32_t* seq_jpeg_counts(const PaletteSeq& q) { return (uint32_t*)q.jpeg; }
+static const void* seq_jpeg_built(const PaletteSeq& q) { return q.jpeg + sizeof(jpeg::SymbolCounts); }
+// what waits in the store: the planes that a JPEG sequence's coder reads, the BGR frame under a palette sequence
+static FrameRaster seq_held_raster(const FormatTraits& t) { return t.coder == kCoderJpeg ? t.raster : kRasterNone; }
 
 int seq_begin(poppy_hip_ctx* c, int n) {
     const WriterGeom g = writer_geom(c);
@@ -9,8 +17,8 @@ int seq_begin(poppy_hip_ctx* c, int n) {
     if (q.open) { int rc = seq_abort(c); if (rc) return rc; }      // (a sequence that a device error left open: its frames and sums are dropped, not mixed into this one)
     if (const char* why = sequence_refuses(c->frame_format, n, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);      // (a sequence format: writer_wants_sequence)
     { int rc = alloc_slot_format(c); if (rc) return rc; }
-    const size_t stride = ((size_t)W * H * 3 + 15) & ~(size_t)15, need = stride * (size_t)n;      // (every frame's place begins on a 16-byte boundary)
-    if (q.store.reserve(need) != hipSuccess) { (void)hipGetLastError(); return fail(c, POPPY_E_DEVICE, "no device memory for the sequence's frames (3 * width * height bytes each)"); }
+    const size_t stride = (raster_bytes(seq_held_raster(*format_traits(c->frame_format)), (size_t)W, (size_t)H) + 15) & ~(size_t)15, need = stride * (size_t)n;      // (every frame's place begins on a 16-byte boundary)
+    if (q.store.reserve(need) != hipSuccess) { (void)hipGetLastError(); return fail(c, POPPY_E_DEVICE, "no device memory for the sequence's frames (3 * width * height bytes each, half of that as I420 planes)"); }
     q.stride = stride; q.n = n; q.count = 0; q.open = true;
     return POPPY_OK;
 }
@@ -18,10 +26,17 @@ int seq_begin(poppy_hip_ctx* c, int n) {
 bool seq_wanted(const poppy_hip_ctx* c) { return c->seq.open && writer_wants_sequence(c, c->writer_attached); }
 int seq_pass(poppy_hip_ctx* c, const uint8_t* d_bgr, uint8_t* dst, hipStream_t s, hipEvent_t done) {
     const WriterGeom g = writer_geom(c);
-    launch_pal8_seq_pass(d_bgr, dst, c->seq.tables, g.w, g.h, s, done);
+    const FormatTraits& t = *format_traits(c->frame_format);
+    if (t.coder == kCoderJpeg) {                                   // the planes straight into the frame's place, then their symbols into the sequence's counts
+        Timer tm(c, s);
+        (t.raster == kRasterI444 ? launch_bgr_to_i444 : launch_bgr_to_i420)(d_bgr, dst, g.w, g.h, s, nullptr);
+        if (c->timing == 1) tm.mark("frame_format");
+        launch_jpeg_count_into(dst, c->jpeg_tables, seq_jpeg_counts(c->seq), g.w, g.h, t.sampling(), s, done);
+    } else launch_pal8_seq_pass(d_bgr, dst, c->seq.tables, g.w, g.h, s, done);
     HIPCHK(c, hipGetLastError());
     return POPPY_OK;
 }
+const char* seq_pass_mark(const poppy_hip_ctx* c) { return seq_is_jpeg(c) ? "jpeg_count" : "pal8_seq_hist"; }
 uint8_t* seq_next_place(poppy_hip_ctx* c) { return c->seq.count < c->seq.n ? c->seq.store.p + (size_t)c->seq.count++ * c->seq.stride : nullptr; }
 
 int seq_add_image(poppy_hip_ctx* c, const uint8_t* d_bgr) {
@@ -36,7 +51,7 @@ int seq_add_image(poppy_hip_ctx* c, const uint8_t* d_bgr) {
         d_bgr = c->scale_scratch.p;
     }
     { int rc = seq_pass(c, d_bgr, dst, c->stream, nullptr); if (rc) return rc; }
-    if (c->timing == 1) tm.mark("pal8_seq_hist");
+    if (c->timing == 1) tm.mark(seq_pass_mark(c));
     return POPPY_OK;
 }
 
@@ -44,6 +59,7 @@ int seq_abort(poppy_hip_ctx* c) {
     c->seq.open = false;
     int rc = drain_frames(c);
     if (c->seq.tables && hipMemset(c->seq.tables, 0, kPal8SeqTableOffset) != hipSuccess && rc == POPPY_OK) rc = fail(c, POPPY_E_DEVICE, "could not clear the sequence tables");
+    if (c->seq.jpeg && hipMemset(c->seq.jpeg, 0, sizeof(jpeg::SymbolCounts)) != hipSuccess && rc == POPPY_OK) rc = fail(c, POPPY_E_DEVICE, "could not clear the sequence's symbol counts");
     return rc;
 }
 void seq_abort_keep_error(poppy_hip_ctx* c) { const std::string why = c->err; (void)seq_abort(c); c->err = why; }
@@ -93,9 +109,17 @@ static void enqueue_seq_gif_coding(const uint8_t* bgr, const uint8_t* seq_tables
     launch_gif_pack_seq(seq_tables, scratch, frame, (uint32_t*)total_dev, W, H, s);
     if (tm) tm->mark("gif_pack");
 }
+// ... and of one frame of a JPEG sequence: from its planes (its place in a sequence store) on the sequence's built tables, the OPT forms of the coder and the gather
+static void enqueue_seq_jpeg_coding(const uint8_t* planes, const void* tables, const void* built, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, jpeg::Sampling sm, hipStream_t s, Timer* tm) {
+    launch_jpeg_code_on(planes, tables, built, scratch, W, H, sm, s);
+    if (tm) tm->mark("jpeg_code");
+    launch_jpeg_pack_on(tables, built, scratch, frame, (uint32_t*)total_dev, W, H, sm, s);
+    if (tm) tm->mark("jpeg_pack");
+}
 
-// Every frame as GIF_SEQ: coded from its place in the store (k_gif_lzw_bgr: no index plane) into one of R device buffers, each followed by the coder's scratch, on the
-// ring buffer's own stream; k_gif_pack stores the frame's length into the ring buffer's pinned word.  The host waits for that stream, reads the word, bounds-checks it
+// Every frame of a coded sequence: coded from its place in the store (GIF_SEQ: k_gif_lzw_bgr, no index plane; the JPEG sequences: k_jpeg_code and k_jpeg_pack in their
+// OPT forms on the sequence's tables) into one of R device buffers, each followed by the coder's scratch, on the ring buffer's own stream; the coder's last kernel
+// stores the frame's length into the ring buffer's pinned word.  The host waits for that stream, reads the word, bounds-checks it
 // as slot_frame_length does and queues the copy of exactly that many bytes on the same stream — no event behind a copy.  Frame k + 1 is being coded (on the next ring
 // buffer's stream) while the host waits for frame k's length, its copy runs and the writer has the frames before it; the writer gets the frames in order.
 static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
@@ -103,21 +127,22 @@ static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* use
     const WriterGeom g = writer_geom(c);
     const int n = q.count, W = g.w, H = g.h;
     const bool marks = c->timing == 1;
-    const size_t capacity = poppy_frame_bytes(POPPY_FRAME_GIF_SEQ, W, H), frame_part = (capacity + 16 + 255) & ~(size_t)255;
-    const size_t each = frame_part + ((gif_scratch_bytes(W, H) + 255) & ~(size_t)255);
+    const FormatTraits& t = *format_traits(c->frame_format);
+    const size_t capacity = poppy_frame_bytes(t.format, W, H), frame_part = (capacity + 16 + 255) & ~(size_t)255;
+    const size_t each = frame_part + ((coding_scratch_bytes(t, W, H) + 255) & ~(size_t)255);
     WriterRing ring;
     { int rc = ring.open(c, capacity, false); if (rc) return rc; }
-    HIPCHK(c, q.gif.reserve(each * ring.R));
-    if (!q.gif_total) {
-        HIPCHK(c, hipHostMalloc((void**)&q.gif_total, 64 * poppy_hip_ctx::kStageRing, hipHostMallocMapped));
-        HIPCHK(c, hipHostGetDevicePointer((void**)&q.gif_total_dev, q.gif_total, 0));
+    HIPCHK(c, q.coded.reserve(each * ring.R));
+    if (!q.coded_total) {
+        HIPCHK(c, hipHostMalloc((void**)&q.coded_total, 64 * poppy_hip_ctx::kStageRing, hipHostMallocMapped));
+        HIPCHK(c, hipHostGetDevicePointer((void**)&q.coded_total_dev, q.coded_total, 0));
     }
-    auto d_frame = [&](int k) { return q.gif.p + (size_t)(k % ring.R) * each; };
-    auto total_word = [&](int k) { return (volatile uint32_t*)((uint8_t*)q.gif_total + 64 * (size_t)(k % ring.R)); };
+    auto d_frame = [&](int k) { return q.coded.p + (size_t)(k % ring.R) * each; };
+    auto total_word = [&](int k) { return (volatile uint32_t*)((uint8_t*)q.coded_total + 64 * (size_t)(k % ring.R)); };
 #ifdef POPPY_EXPERIMENTS
     const size_t plane = ((size_t)W * H + 255) & ~(size_t)255;
     HIPCHK(c, q.idx.reserve(plane * ring.R));
-    const bool two_dispatch = getenv("POPPY_GIF_SEQ_TWO_DISPATCH") != nullptr;      // timing experiment, read per sequence so that one process alternates: the index plane through HBM (k_pal8_remap, then k_gif_lzw); the same bytes
+    const bool two_dispatch = t.coder == kCoderGif && getenv("POPPY_GIF_SEQ_TWO_DISPATCH") != nullptr;      // timing experiment, read per sequence so that one process alternates: the index plane through HBM (k_pal8_remap, then k_gif_lzw); the same bytes
 #endif
     int coded = 0;                                                 // frames 0 .. coded - 1: their coding is queued; ring.issued: their copies are
     auto code_next = [&]() -> int {
@@ -134,11 +159,12 @@ static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* use
             if (marks) tm.mark("frame_format");
             launch_gif_lzw(d_idx, d_frame(k) + frame_part, W, H, s);
             if (marks) tm.mark("gif_lzw");
-            launch_gif_pack_seq(q.tables, d_frame(k) + frame_part, d_frame(k), (uint32_t*)(q.gif_total_dev + 64 * (size_t)(k % ring.R)), W, H, s);
+            launch_gif_pack_seq(q.tables, d_frame(k) + frame_part, d_frame(k), (uint32_t*)(q.coded_total_dev + 64 * (size_t)(k % ring.R)), W, H, s);
             if (marks) tm.mark("gif_pack");
         } else
 #endif
-        enqueue_seq_gif_coding(q.store.p + (size_t)k * q.stride, q.tables, d_frame(k) + frame_part, d_frame(k), q.gif_total_dev + 64 * (size_t)(k % ring.R), W, H, s, marks ? &tm : nullptr);
+        if (t.coder == kCoderJpeg) enqueue_seq_jpeg_coding(q.store.p + (size_t)k * q.stride, c->jpeg_tables, seq_jpeg_built(q), d_frame(k) + frame_part, d_frame(k), q.coded_total_dev + 64 * (size_t)(k % ring.R), W, H, t.sampling(), s, marks ? &tm : nullptr);
+        else enqueue_seq_gif_coding(q.store.p + (size_t)k * q.stride, q.tables, d_frame(k) + frame_part, d_frame(k), q.coded_total_dev + 64 * (size_t)(k % ring.R), W, H, s, marks ? &tm : nullptr);
         HIPCHK(c, hipGetLastError());
         ++coded;
         return POPPY_OK;
@@ -149,7 +175,7 @@ static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* use
         HIPCHK(c, ring.stream(c, k, &s));
         HIPCHK(c, hipStreamSynchronize(s));                        // the frame is coded, its length is in the pinned word
         const size_t total = *total_word(k);
-        if (!coded_length_ok(total, capacity, kGifFrameMinBytes)) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+        if (!coded_length_ok(total, capacity, t.least)) return fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
         HIPCHK(c, hipMemcpyAsync(ring.buffer(k), d_frame(k), total, hipMemcpyDeviceToHost, s));
         ++ring.issued;
         return POPPY_OK;
@@ -158,7 +184,7 @@ static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* use
         if (ring.issued == ring.written) { int rc = copy_next(); if (rc) return rc; }
         uint8_t* frame = nullptr;
         HIPCHK(c, ring.deliver_next(c, false, &frame));
-        write(user, frame, W, H, writer_stride(POPPY_FRAME_GIF_SEQ, W));
+        write(user, frame, W, H, writer_stride(t.format, W));
         return POPPY_OK;
     };
     int rc = POPPY_OK;
@@ -179,8 +205,9 @@ static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
     {
         Timer tm(c, c->stream);
         if (c->timing == 1) tm.mark(nullptr);
-        launch_pal8_seq_build(q.tables, c->stream);
-        if (c->timing == 1) tm.mark("pal8_seq_build");
+        if (seq_is_jpeg(c)) launch_jpeg_table_build(seq_jpeg_counts(q), const_cast<void*>(seq_jpeg_built(q)), c->stream);      // once, on the sums: the counts are zero behind it
+        else launch_pal8_seq_build(q.tables, c->stream);
+        if (c->timing == 1) tm.mark(seq_is_jpeg(c) ? "jpeg_tables" : "pal8_seq_build");
     }
     HIPCHK(c, hipGetLastError());
     if (!format_traits(c->frame_format)->coded()) return seq_hand_over_indices(c, write, user);
@@ -231,6 +258,60 @@ int poppy_hip_bgr_frames_to_gif_frames(poppy_hip_ctx* c, const uint8_t* bgr, siz
     if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);   // nothing of the call is in flight when its buffers go (`held`, at the return)
     if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("GIF sequence coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
     return rc;
+}
+
+// the body of poppy_hip_bgr_frames_to_jpeg_seq_frames and its 4:4:4 twin: host BGR frames up one by one, each through the pass of a JPEG sequence (raster kernel,
+// counting kernel) into a store of planes, one table build, every frame coded and `total` bytes of it down — all on buffers and tables that live for the call
+static int jpeg_seq_code_host_frames(poppy_hip_ctx* c, int fmt, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int W, int H, int quality, uint8_t* dst) {
+    if (!c) return POPPY_E_ARG;
+    if (!bgr || !dst || W <= 0 || H <= 0 || stride < (size_t)W * 3 || n_frames < 1 || quality < 1 || quality > 100) return fail(c, POPPY_E_ARG, "bad arguments");
+    if (frame_stride < stride * ((size_t)H - 1) + (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad arguments: the frames overlap");
+    if (const char* why = sequence_refuses(fmt, n_frames, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    HIPCHK(c, hipSetDevice(c->device));
+    // everything lives for the call: the context's own sequence tables, store and rings, and its quality's tables, are not touched
+    const FormatTraits& t = *format_traits(fmt);
+    const jpeg::Sampling sm = t.sampling();
+    const size_t row = (size_t)W * 3, place = (raster_bytes(t.raster, (size_t)W, (size_t)H) + 15) & ~(size_t)15, capacity = poppy_frame_bytes(fmt, W, H);
+    jpeg::QualityTables qt;
+    jpeg::fill_quality_tables(quality, &qt);
+    CallBuffers held;
+    uint8_t *d_bgr = nullptr, *store = nullptr, *seq = nullptr, *d_tables = nullptr, *work = nullptr, *frame = nullptr;
+    hipError_t e = held.alloc(&d_bgr, row * H + 16);
+    if (e == hipSuccess) e = held.alloc(&store, place * (size_t)n_frames);
+    if (e == hipSuccess) e = held.alloc(&seq, kJpegSeqTableBytes);
+    if (e == hipSuccess) e = held.alloc(&d_tables, kJpegTableBytes);
+    if (e == hipSuccess) e = held.alloc(&work, jpeg_scratch_bytes(W, H, sm, true));
+    if (e == hipSuccess) e = held.alloc(&frame, capacity + 16);
+    if (e == hipSuccess) e = hipMemsetAsync(seq, 0, kJpegSeqTableBytes, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tables, &qt, sizeof qt, hipMemcpyHostToDevice, c->stream);
+    for (int k = 0; k < n_frames && e == hipSuccess; ++k) {      // (the one BGR buffer: the upload is ordered behind the raster kernel that read the frame before)
+        e = copy_rows_async(d_bgr, row, bgr + (size_t)k * frame_stride, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) break;
+        (sm == jpeg::k444 ? launch_bgr_to_i444 : launch_bgr_to_i420)(d_bgr, store + (size_t)k * place, W, H, c->stream, nullptr);
+        launch_jpeg_count_into(store + (size_t)k * place, d_tables, (uint32_t*)seq, W, H, sm, c->stream);
+        e = hipGetLastError();
+    }
+    const void* built = seq + sizeof(jpeg::SymbolCounts);
+    if (e == hipSuccess) { launch_jpeg_table_build((uint32_t*)seq, const_cast<void*>(built), c->stream); e = hipGetLastError(); }
+    int rc = POPPY_OK;
+    for (int k = 0; k < n_frames && e == hipSuccess && rc == POPPY_OK; ++k) {
+        uint32_t total = 0;
+        enqueue_seq_jpeg_coding(store + (size_t)k * place, d_tables, built, work, frame, nullptr, W, H, sm, c->stream, nullptr);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess && !coded_length_ok(total, capacity, t.least)) rc = fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+        else if (e == hipSuccess) e = hipMemcpy(dst + (size_t)k * capacity, frame, total, hipMemcpyDeviceToHost);
+    }
+    (void)hipStreamSynchronize(c->stream);                         // nothing of the call is in flight when its buffers and `qt` go (`held`, at the return)
+    if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("JPEG sequence coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    return rc;
+}
+int poppy_hip_bgr_frames_to_jpeg_seq_frames(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int W, int H, int quality, uint8_t* dst) {
+    return jpeg_seq_code_host_frames(c, POPPY_FRAME_JPEG_SEQ, bgr, stride, frame_stride, n_frames, W, H, quality, dst);
+}
+int poppy_hip_bgr_frames_to_jpeg444_seq_frames(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int W, int H, int quality, uint8_t* dst) {
+    return jpeg_seq_code_host_frames(c, POPPY_FRAME_JPEG444_SEQ, bgr, stride, frame_stride, n_frames, W, H, quality, dst);
 }
 
 }  // extern "C"
