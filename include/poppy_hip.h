@@ -878,8 +878,13 @@ int poppy_radial_mask(int width, int height, float* out);
  * poppy_gabor_tables: the 16 kernels of a Gabor bank as cv::getGaborKernel returns them (which = 31: src/extractor.cpp:63-64, 13:
  * src/util.hpp:95; 16 * which^2 floats) and their paired, conjugated 64 x 64 spectra (8 * 4096 complex doubles) for the FFT form;
  * poppy_pyr_tail_plan: the tap table of the pyramid tail kernel for a frame geometry (info: first tail level, multi-pixel level
- * steps, single-pixel reductions, descriptors, LDS bytes, usable; desc: 4 words per descriptor). */
+ * steps, single-pixel reductions, descriptors, LDS bytes, usable; desc: 4 words per descriptor);
+ * poppy_gabor_rounding_in_doubt: the FFT form's doubt rule on one plane value v (the function the kernel calls, run on the host):
+ * 0 not in doubt, 1 within band of zero, 2 within band of the midpoint between two floats;
+ * poppy_gabor_band_unit: the band the kernels use, per unit of max(1, the largest magnitude in the tile's 64 x 64 patch). */
 int poppy_gabor_tables(int which, float* bank, double* spectra);
+int poppy_gabor_rounding_in_doubt(double v, double band);
+double poppy_gabor_band_unit(void);
 int poppy_pyr_tail_plan(int width, int height, int pyramid_levels, int tail_px, int* info, unsigned* desc);
 /* Host only: the plan of the length-n transform dft_detail2's kernels run (pass order, load permutation, float twiddles; see
  * poppy_amd/csrc/dft_exact.cpp).  factors needs room for 34 ints, itab for n ints, wave for 2n floats.  For the test suite. */

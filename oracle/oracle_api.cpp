@@ -175,6 +175,11 @@ void orc_gabor_filter_direct(const float* src, int w, int h, int c, int ks, cons
     std::vector<float> b(bank, bank + (size_t)16 * ks * ks); ImageF o;
     gabor_filter_direct(wrap_f(src, w, h, c), ks, b, o); put_img(dst, o);
 }
+// planes: w * h * c * 16 doubles, [y][x][channel][orientation]: gabor_filter_direct's sums before the cast to float
+void orc_gabor_planes(const float* src, int w, int h, int c, int ks, const float* bank, double* planes) {
+    std::vector<float> b(bank, bank + (size_t)16 * ks * ks); std::vector<double> p;
+    gabor_planes(wrap_f(src, w, h, c), ks, b, 0, h, p); memcpy(planes, p.data(), p.size() * 8);
+}
 
 double orc_dft_detail2(const uint8_t* gray, int w, int h) { return dft_detail2(wrap_u8(gray, w, h, 1)); }
 void orc_radial_gradient(int w, int h, float* out) { ImageF o; radial_gradient(w, h, o); put_img(out, o); }

@@ -327,15 +327,14 @@ void gabor_bank(int ks, double sigma, double lambd, double gamma, double psi, st
     }
 }
 
-// mean over the bank of clamp(correlate(src, kernel), 0, 1).  The reference evaluates the correlation through OpenCV's DFT-based
-// filter2D; this is the direct sum in double, rounded once: the comparator for tolerance checks, not a bit-exact restatement.
-void gabor_filter_direct(const ImageF& src, int ks, const std::vector<float>& bank, ImageF& dst) {
-    dst = ImageF(src.w, src.h, src.c);
+// The 16 correlation sums of every pixel and channel of rows [y0, y1) in double, before the cast to float:
+// planes[(((y - y0) * w + x) * cn + ch) * 16 + a].  Taps in row-major order, one multiply and one add per tap.
+void gabor_planes(const ImageF& src, int ks, const std::vector<float>& bank, int y0, int y1, std::vector<double>& planes) {
     const int m = ks / 2, w = src.w, h = src.h, cn = src.c;
-    for (int y = 0; y < h; ++y)
+    planes.resize((size_t)(y1 - y0) * w * cn * 16);
+    for (int y = y0; y < y1; ++y)
         for (int x = 0; x < w; ++x)
-            for (int ch = 0; ch < cn; ++ch) {
-                float sum = 0.f;
+            for (int ch = 0; ch < cn; ++ch)
                 for (int a = 0; a < 16; ++a) {
                     double acc = 0;
                     const float* k = &bank[(size_t)a * ks * ks];
@@ -343,12 +342,28 @@ void gabor_filter_direct(const ImageF& src, int ks, const std::vector<float>& ba
                         const float* row = src.row(border_reflect101(y + dy - m, h));
                         for (int dx = 0; dx < ks; ++dx) acc += (double)k[dy * ks + dx] * row[(size_t)border_reflect101(x + dx - m, w) * cn + ch];
                     }
-                    float p = (float)acc;
-                    p = p > 1.f ? 1.f : p; p = p < 0.f ? 0.f : p;
-                    sum += p;
+                    planes[((((size_t)(y - y0)) * w + x) * cn + ch) * 16 + a] = acc;
                 }
-                dst.d[((size_t)y * w + x) * cn + ch] = sum * 0.0625f;
+}
+
+// mean over the bank of clamp(correlate(src, kernel), 0, 1).  The reference evaluates the correlation through OpenCV's DFT-based
+// filter2D; this is the direct sum in double (gabor_planes), rounded once: the comparator for tolerance checks, not a bit-exact restatement.
+void gabor_filter_direct(const ImageF& src, int ks, const std::vector<float>& bank, ImageF& dst) {
+    dst = ImageF(src.w, src.h, src.c);
+    const int w = src.w, h = src.h, cn = src.c;
+    std::vector<double> planes;
+    for (int y = 0; y < h; ++y) {
+        gabor_planes(src, ks, bank, y, y + 1, planes);
+        for (int i = 0; i < w * cn; ++i) {
+            float sum = 0.f;
+            for (int a = 0; a < 16; ++a) {
+                float p = (float)planes[(size_t)i * 16 + a];
+                p = p > 1.f ? 1.f : p; p = p < 0.f ? 0.f : p;
+                sum += p;
             }
+            dst.d[(size_t)y * w * cn + i] = sum * 0.0625f;
+        }
+    }
 }
 
 // us = grey(unsharp_mask(triple(gf / 255), 2, 6, 0.1)): exact

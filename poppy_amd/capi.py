@@ -50,7 +50,7 @@ SYMBOLS = [
     "poppy_sink_open", "poppy_sink_write", "poppy_sink_close", "poppy_hip_render_phases", "poppy_hip_pool_set_timing", "poppy_hip_pool_timing_summary", "poppy_hip_pool_warp_counts", "poppy_hip_pool_create", "poppy_hip_pool_create_tuned", "poppy_hip_pool_destroy", "poppy_hip_pool_morph_pairs", "poppy_hip_pool_submit_pairs", "poppy_hip_pool_wait", "poppy_count_pair_frames_cb", "poppy_hip_warp_counts", "poppy_hip_time_last_warp", "poppy_hip_mask_rider", "poppy_hip_pool_mask_rider", "poppy_hip_comm_id", "poppy_hip_comm_init", "poppy_hip_comm_free", "poppy_hip_comm_info", "poppy_hip_pair_broadcast", "poppy_hip_comm_max",
     "poppy_hip_pair_begin_sharded", "poppy_hip_sharded_setups", "poppy_hip_pair_begin_sharded_local", "poppy_hip_pair_state_bytes", "poppy_hip_pair_export_device", "poppy_hip_pair_import_device", "poppy_hip_morph_sharded", "poppy_hip_morph_pairs",
     "poppy_dft_plan", "poppy_hip_pair_begin_device", "poppy_count_frames_cb", "poppy_hip_morph", "poppy_hip_pair_distance", "poppy_printed_morph_distance", "poppy_hypotf_selfcheck",
-    "poppy_hip_orb_detect", "poppy_hip_foreground", "poppy_hip_median_blur", "poppy_match_points", "poppy_hip_pair_begin_prefiltered", "poppy_hip_pair_begin", "poppy_hip_pair_begin_info", "poppy_hip_orb_input", "poppy_hip_gabor_field", "poppy_hip_set_gabor_direct", "poppy_hip_set_setup_chains", "poppy_hip_gabor_doubt", "poppy_radial_gradient", "poppy_radial_mask", "poppy_gabor_tables", "poppy_pyr_tail_plan", "poppy_hip_blur_margin", "poppy_hip_pair_points",
+    "poppy_hip_orb_detect", "poppy_hip_foreground", "poppy_hip_median_blur", "poppy_match_points", "poppy_hip_pair_begin_prefiltered", "poppy_hip_pair_begin", "poppy_hip_pair_begin_info", "poppy_hip_orb_input", "poppy_hip_gabor_field", "poppy_hip_set_gabor_direct", "poppy_hip_set_setup_chains", "poppy_hip_gabor_doubt", "poppy_radial_gradient", "poppy_radial_mask", "poppy_gabor_tables", "poppy_gabor_rounding_in_doubt", "poppy_gabor_band_unit", "poppy_pyr_tail_plan", "poppy_hip_blur_margin", "poppy_hip_pair_points",
     "poppy_hip_pair_begin_next", "poppy_hip_pair_begin_next_device", "poppy_hip_chain_counts", "poppy_hip_morph_list",
     "poppy_hip_last_pyramid_forms",
     "poppy_hip_set_frame_format", "poppy_hip_pool_set_frame_format", "poppy_frame_bytes", "poppy_bgr_to_i420", "poppy_bgr_to_pal8", "poppy_bgr_frames_to_pal8",
@@ -145,6 +145,9 @@ def lib():
         L.poppy_radial_gradient.argtypes = [i, i, vp]
         L.poppy_radial_mask.argtypes = [i, i, vp]
         L.poppy_gabor_tables.argtypes = [i, vp, vp]
+        L.poppy_gabor_rounding_in_doubt.argtypes = [C.c_double, C.c_double]
+        L.poppy_gabor_band_unit.argtypes = []
+        L.poppy_gabor_band_unit.restype = C.c_double
         L.poppy_pyr_tail_plan.argtypes = [i, i, i, i, vp, vp]
         L.poppy_hip_blur_margin.argtypes = [vp, vp, sz, i, i, i, i, vp, sz]
         L.poppy_hip_orb_describe.argtypes = [vp, vp, sz, i, i, vp, i, vp]
@@ -844,6 +847,16 @@ def gabor_tables(which):
     if rc:
         raise PoppyError(f"poppy_gabor_tables: {rc}")
     return bank, spec[..., 0] + 1j * spec[..., 1]
+
+
+def gabor_rounding_in_doubt(v, band):
+    """The doubt rule of the FFT form of the Gabor banks on one plane value (host only): 0 no, 1 near zero, 2 near a float midpoint."""
+    return int(lib().poppy_gabor_rounding_in_doubt(float(v), float(band)))
+
+
+def gabor_band_unit():
+    """The doubt band of the FFT form per unit of max(1, the largest magnitude in the tile's 64 x 64 patch) (host only)."""
+    return float(lib().poppy_gabor_band_unit())
 
 
 def pyr_tail_plan(w, h, levels=64, tail_px=600):

@@ -27,6 +27,7 @@
 // fixtures) or of zero (the borders of all-black regions).  Those values are detected (rounding_in_doubt) and formed as the direct
 // kernel forms them (k_gabor_redo): the two forms give the same bits; tests/test_gpu_prefilter2.py compares them.
 #include "kernels_prefilter.h"
+#include "gabor_doubt.h"
 #include "pyramid_device.h"
 #include <cmath>
 #include <cstdlib>
@@ -106,7 +107,11 @@ __device__ __forceinline__ void fft_pass(cd* __restrict__ L, int tid) { cd v[8];
 // as the direct sum unless it lies within that distance of the midpoint between two floats, or of zero (the clamp's corner: the noise
 // around an exact zero at the border of a black region would survive it).  `band` is 1e-13 x max(1, the patch's largest magnitude): ten
 // times the measured worst case — an empirical margin (the transform's error follows the patch's and the kernel's norms), so "the two forms
-// agree in every bit" means: on everything tested, with that margin; POPPY_GABOR_BAND=1e30 re-forms every pixel for a check without it.
+// agree in every bit" means: with that margin, on the content it has been held against — photographs, textures, flat shapes and noise at up to
+// 1080p, and plane values constructed to lie 1.0 to 1.5 bands from a midpoint, where nothing but the transform's accuracy keeps the forms
+// equal: 96 two-pixel windows on black, 576 inside saturated 0 / 255 noise at 256 x 192 (patches of close to the largest norm a byte image
+// has) and 8 two-dot images of the 31-tap bank with |us| up to 5.4 (tests/test_gpu_gabor_ties.py, from tests/gabor_ties_util.py).  None
+// flipped on an MI355X, so the margin stands unchanged.  POPPY_GABOR_BAND=1e30 re-forms every pixel for a check without it.
 // Not in doubt: v below -band or above 1 + band (clamped either way) and the planes of a window that holds only zeros (exact zeros in
 // the direct sums; the kernel knows such windows from ballots taken while it loads the patch and adds nothing for them).  A pixel
 // with a value in doubt — 1 value in ~1e4, most of them small: a float's neighbours are 2^-24 of its size apart — goes on a list, and
@@ -114,18 +119,7 @@ __device__ __forceinline__ void fft_pass(cd* __restrict__ L, int tid) { cd v[8];
 // pixel, one orientation's chain each.  (Re-forming a value inside the transform kernel holds its whole tile at a barrier for the
 // length of a 961-step chain: 0.27 -> 1.1 ms at 1080p; all listed pixels of an image side by side take ~20 us.)
 __device__ unsigned long long g_doubt[3];                     // since the last read: values near zero, near a midpoint; pixels re-formed (poppy_hip_gabor_doubt)
-__device__ __forceinline__ int rounding_in_doubt(double v, double band) {      // 0: no, 1: near zero, 2: near a midpoint
-    if (v < -band || v > 1.0 + band) return 0;
-    if (v < band) return 1;
-    // v = f + d with f the nearest float; the midpoints lie half a spacing away: 2^(e - 24) above f and below it, except below a power of two
-    // (2^(e - 25)).  In doubt when d comes within `band` of one of them.
-    const float f = (float)v;
-    const double d = v - (double)f;
-    const int fb = __float_as_int(f);
-    float h = __int_as_float((fb & 0x7f800000) - (24 << 23));
-    if ((fb & 0x007fffff) == 0 && d < 0.0) h *= 0.5f;
-    return fabs(d) > (double)h - band ? 2 : 0;
-}
+// rounding_in_doubt(v, band): gabor_doubt.h, shared with the host (poppy_gabor_rounding_in_doubt) — 0: no, 1: near zero, 2: near a midpoint
 
 // list[0]: entries, list[2 + e]: (y * W + x) * CN + ch.  A group of 16 lanes takes an entry; lane o of the group runs orientation o's chain.
 // A chain is KS * KS dependent steps, so everything it reads is staged where a step costs an LDS read: the 16 windows of a workgroup's
@@ -345,7 +339,7 @@ static bool gabor_redo_on() { static const bool on = poppy_experiment_env("POPPY
 // The width of the doubt band in units of max(1, the patch's largest magnitude): 1e-13 = ten times the largest distance between the two forms
 // measured on ~1e5 plane values (1.1e-14).  The equality of the forms rests on that measurement, not on a proof: POPPY_GABOR_BAND widens the
 // band for checks (1e30: every pixel is re-formed as direct sums — a fuzz run under it and one without must agree in every bit).
-static double gabor_band_unit() { static const double v = poppy_experiment_env("POPPY_GABOR_BAND") ? atof(poppy_experiment_env("POPPY_GABOR_BAND")) : 1e-13; return v; }
+double gabor_band_unit() { static const double v = poppy_experiment_env("POPPY_GABOR_BAND") ? atof(poppy_experiment_env("POPPY_GABOR_BAND")) : kGaborBandUnit; return v; }
 
 // list: 2 + w * h * channels words, device (this launch resets and fills it; k_gabor_redo reads it)
 void launch_gabor_fft31(const float* src, const double* d_tables, const double* d_bank, unsigned* d_list, float* dst, int w, int h, hipStream_t s) {

@@ -92,6 +92,7 @@ std::vector<double> gabor_fft_tables(const std::vector<float>& bank, int ks);
 // launch re-forms them as the direct sums (d_bank: the direct kernels' table), so both forms give the same bits.
 bool gabor_fft_prepare();
 bool gabor_fft_doubt(unsigned long long out[3]);
+double gabor_band_unit();                                      // the doubt band per unit of max(1, the patch's largest magnitude) the launches below pass to the kernel
 void launch_gabor_fft31(const float* src, const double* d_tables, const double* d_bank, unsigned* d_list, float* dst, int w, int h, hipStream_t s);
 void launch_gabor_fft13_c3(const float* src, const double* d_tables, const double* d_bank, unsigned* d_list, float* dst, int w, int h, hipStream_t s);
 void launch_u8_to_f32(const uint8_t* src, float* dst, int n, hipStream_t s);

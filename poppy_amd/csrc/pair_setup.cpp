@@ -4,6 +4,7 @@
 #include "pair_begin.h"
 #include "dft_exact.h"
 #include "ransac_fundamental.h"
+#include "gabor_doubt.h"
 
 // blur_margin's two halves (src/util.cpp:574-602), shared by poppy_hip_blur_margin and poppy_hip_morph_list's device-side padding.
 // taps: exp(-x^2 / 2 sigma^2) / sum in double, to 8 fractional bits with error diffusion, centre = 256 - rest (smooth.dispatch.cpp:224-258)
@@ -360,6 +361,8 @@ int poppy_gabor_tables(int which, float* bank, double* spectra) {
     if (spectra) { const std::vector<double> t = gabor_fft_tables(b, which); memcpy(spectra, t.data(), t.size() * 8); }
     return POPPY_OK;
 }
+int poppy_gabor_rounding_in_doubt(double v, double band) { return rounding_in_doubt(v, band); }
+double poppy_gabor_band_unit(void) { return gabor_band_unit(); }
 // The tap table of the pyramid tail (kernels.h: PyrTailPlan) of a width x height frame: info[0..5] = first level of the tail, multi-pixel
 // level steps, single-pixel reductions (-1: none), descriptors, LDS bytes, usable (0 / 1); desc (optional, room for info[3] * 4 words).
 int poppy_pyr_tail_plan(int width, int height, int pyramid_levels, int tail_px, int* info, unsigned* desc) {

@@ -430,6 +430,14 @@ def align_step(which, img, p1, p2):
 
 
 # ---- round 2: the rest of the pre-ORB chain, the whole pair set-up and poppy::morph in the oracle ---------------------
+def gabor_planes(src, ks, bank):
+    """The 16 double sums behind every float of gabor_filter_direct, before the cast to float: (h, w, 16) or (h, w, c, 16) float64."""
+    a = _f(src); c = 1 if a.ndim == 2 else a.shape[2]
+    o = np.zeros(a.shape + (16,), np.float64); b = _f(bank)
+    lib().orc_gabor_planes(_vp(a), a.shape[1], a.shape[0], c, ks, _vp(b), _vp(o))
+    return o
+
+
 def dft_detail2(gray):
     g = np.ascontiguousarray(gray, np.uint8)
     L = lib(); L.orc_dft_detail2.restype = C.c_double
