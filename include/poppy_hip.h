@@ -891,9 +891,29 @@ int poppy_pyr_tail_plan(int width, int height, int pyramid_levels, int tail_px, 
 int poppy_dft_plan(int n, int* factors, int* n_factors, int* itab, float* wave);
 
 /* blur_margin (src/util.cpp:574-602), the CLI's padding step before poppy::morph (src/poppy.cpp:233-240,293-308): the image
- * centred in a union_width x union_height canvas, the four margin strips Gaussian-blurred (127x127, sigma 6).  Bit-exact.   */
+ * centred in a union_width x union_height canvas, the four margin strips Gaussian-blurred (127x127, sigma 6).  Bit-exact.
+ * POPPY_E_ARG: a null pointer, a non-positive size, a canvas smaller than the image, a stride shorter than its row.
+ * POPPY_E_UNSUPPORTED, before anything is allocated or launched and with dst untouched: sizes whose margin strips leave the canvas
+ * (poppy_blur_margin_rects below), and a canvas of more rows than the device's grid takes in y (poppy_hip_blur_margin_max_rows).
+ * The context stays usable after either.                                                                                       */
 int poppy_hip_blur_margin(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height,
                           int union_width, int union_height, uint8_t* dst, size_t dst_stride);
+/* Host only: the one statement of blur_margin's geometry.  With margin = (width + height) / 100.0 and, per axis,
+ * d = |size - union| / 2, then d = (d == 0 ? 1.3 : d + margin):
+ *   rects  = left {0, 0, (int)dx, UH}, right {(int)(UW - dx), 0, (int)dx, UH}, top {0, 0, UW, (int)dy}, bottom {0, (int)(UH - dy), UW, (int)dy}
+ *            as 16 ints (x, y, width, height), blurred from the unblurred canvas and written in this order (later strips win);
+ *   origin = the image's top-left pixel in the canvas, ((int)(|W - UW| / 2), (int)(|H - UH| / 2)).
+ * Either pointer may be NULL.  POPPY_E_ARG: a non-positive size or a canvas smaller than the image (nothing written).
+ * POPPY_E_UNSUPPORTED (both still written): a strip leaves the canvas, (int)dx > UW or (int)dy > UH — images more than about 99
+ * times as high as wide, or as wide as high (8 x 1000 in 10 x 1000).  The reference throws there (Mat(Rect) asserts the rectangle
+ * lies inside the matrix); poppy_hip_blur_margin and poppy_hip_morph_list refuse such sizes.
+ * A rectangle of width or height 0 (a size difference of 1 with width + height < 100: 3 x 3 in 4 x 4) means "strip skipped".
+ * That is this library's rule: the reference's GaussianBlur is never asked about an empty strip by its own CLI.              */
+int poppy_blur_margin_rects(int width, int height, int union_width, int union_height, int rects[16], int origin[2]);
+/* Host only: blur_margin's 127 fixed-point (8.8) taps, as the strip kernels get them (they sum to 256). */
+int poppy_blur_margin_taps(int taps[127]);
+/* The most canvas rows poppy_hip_blur_margin and poppy_hip_morph_list's canvas take on this context's device (its maxGridSize[1]). */
+int poppy_hip_blur_margin_max_rows(poppy_hip_ctx* ctx, int* rows);
 /* copies of the resident point sets after pair_begin / pair_load (n x 2 floats each); n via *n_points */
 int poppy_hip_pair_points(poppy_hip_ctx* ctx, float* points1, float* points2, int max_points, int* n_points);
 
@@ -1007,6 +1027,8 @@ int poppy_hip_pool_mask_rider(poppy_hip_pool* pool);
  *   canvas          canvas_width = canvas_height = 0: every image must have image 0's size (poppy::morph takes one size,
  *                   src/poppy.cpp:313-316), else POPPY_E_ARG.  Otherwise every image (at most the canvas in each side) is placed into
  *                   the canvas by blur_margin's rule on the device, the bytes poppy_hip_blur_margin(img, canvas) returns (src/util.cpp:574-602).
+ *                   An image whose margin strips would leave the canvas (poppy_blur_margin_rects), or a canvas of more rows than
+ *                   poppy_hip_blur_margin_max_rows: POPPY_E_UNSUPPORTED when that image arrives, before it is padded; the context stays usable.
  *   phase           < 0: default chained mode; 0 < phase < 1: one phase-mode frame per pair.  0 or 1 with more than two images:
  *                   POPPY_E_UNSUPPORTED (poppy::morph returns before it sets corrected2, :54-70); with two images as poppy_hip_morph.
  *   write           (pair, frame) in order, on the calling thread; NULL keeps the frames on the device.

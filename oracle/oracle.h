@@ -176,6 +176,6 @@ void orb_input_image(const ImageU8& good_features, ImageU8& g);              // 
 void gaussian_taps_fx(int n, double sigma, std::vector<int>& taps);          // 8.8 fixed-point taps of the 8-bit GaussianBlur (sigma <= 0: OpenCV's defaults)
 void convex_hull_points(const std::vector<Pt>& pts, std::vector<Pt>& hull);  // cv::convexHull(points, hull): counter-clockwise, points returned
 void dissolve_u8(const ImageU8& img1, const ImageU8& img2, double phase, ImageU8& out);   // img2*phase + img1*(1-phase), src/poppy.hpp:129   // GaussianBlur on 8 bit, fixed-point path
-void blur_margin(const ImageU8& src, int union_w, int union_h, ImageU8& dst);            // src/util.cpp:574-602
+bool blur_margin(const ImageU8& src, int union_w, int union_h, ImageU8& dst);            // src/util.cpp:574-602; false where the reference throws (a strip leaves the canvas)
 
 }  // namespace oracle

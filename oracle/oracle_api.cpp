@@ -203,7 +203,13 @@ int orc_convex_hull(const float* pts, int n, float* hull) {
     memcpy(hull, h.data(), h.size() * sizeof(Pt));
     return (int)h.size();
 }
-void orc_blur_margin(const uint8_t* src, int w, int h, int uw, int uh, uint8_t* dst) { ImageU8 o; blur_margin(wrap_u8(src, w, h, 3), uw, uh, o); put_img(dst, o); }
+int orc_blur_margin(const uint8_t* src, int w, int h, int uw, int uh, uint8_t* dst) {      // -1, dst untouched: sizes the reference throws on
+    if (w <= 0 || h <= 0 || uw < w || uh < h) return -1;
+    ImageU8 o;
+    if (!blur_margin(wrap_u8(src, w, h, 3), uw, uh, o)) return -1;
+    put_img(dst, o);
+    return 0;
+}
 
 // ---- auto-align ----------------------------------------------------------------------------------------------
 void orc_warp_affine(const uint8_t* src, int w, int h, int c, const double* M6, uint8_t* dst) {

@@ -443,22 +443,28 @@ void gaussian_blur_fx_u8(const ImageU8& src, int ksize, double sigma, ImageU8& d
             }
 }
 
-void blur_margin(const ImageU8& src, int uw, int uh, ImageU8& dst) {
-    ImageU8 U(uw, uh, 3);
+// false, and dst untouched: a non-positive size, a canvas smaller than the image, or a strip that leaves the canvas — (int)dx > uw or
+// (int)dy > uh, images more than about 99 times as high as wide or as wide as high — where the reference's Mat(Rect) throws
+bool blur_margin(const ImageU8& src, int uw, int uh, ImageU8& dst) {
+    if (src.w <= 0 || src.h <= 0 || uw < src.w || uh < src.h) return false;
     const double margin = (src.w + src.h) / 100.0;
     double dx = std::fabs((double)(src.w - uw)) / 2.0, dy = std::fabs((double)(src.h - uh)) / 2.0;
     const int rx = (int)dx, ry = (int)dy;
-    for (int y = 0; y < src.h; ++y) memcpy(&U.d[((size_t)(ry + y) * uw + rx) * 3], src.row(y), (size_t)src.w * 3);
     dx = (dx == 0 ? 1.3 : dx + margin);
     dy = (dy == 0 ? 1.3 : dy + margin);
+    if ((int)dx > uw || (int)dy > uh) return false;
+    ImageU8 U(uw, uh, 3);
+    for (int y = 0; y < src.h; ++y) memcpy(&U.d[((size_t)(ry + y) * uw + rx) * 3], src.row(y), (size_t)src.w * 3);
     const int rects[4][4] = {{0, 0, (int)dx, uh}, {(int)(uw - dx), 0, (int)dx, uh}, {0, 0, uw, (int)dy}, {0, (int)(uh - dy), uw, (int)dy}};
     dst = U;
     for (const auto& r : rects) {                       // all four strips are cut from the unblurred canvas; written in this order
+        if (r[2] <= 0 || r[3] <= 0) continue;           // a strip of width or height 0 is skipped: no 0-wide image is ever built
         ImageU8 strip(r[2], r[3], 3), blurred;
         for (int y = 0; y < r[3]; ++y) memcpy(strip.row(y), &U.d[((size_t)(r[1] + y) * uw + r[0]) * 3], (size_t)r[2] * 3);
         gaussian_blur_fx_u8(strip, 127, 6, blurred);
         for (int y = 0; y < r[3]; ++y) memcpy(&dst.d[((size_t)(r[1] + y) * uw + r[0]) * 3], blurred.row(y), (size_t)r[2] * 3);
     }
+    return true;
 }
 
 }  // namespace oracle

@@ -70,6 +70,7 @@ SYMBOLS = [
     "poppy_hip_bgr_resize_area_form",
     "poppy_hip_unsharp_frame", "poppy_hip_align_scores",
     "poppy_ransac_fundamental", "poppy_hip_ransac_fundamental", "poppy_hip_pair_begin_descriptors_ransac", "poppy_hip_pair_fundamental",
+    "poppy_blur_margin_rects", "poppy_blur_margin_taps", "poppy_hip_blur_margin_max_rows",
 ]
 
 
@@ -150,6 +151,9 @@ def lib():
         L.poppy_gabor_band_unit.restype = C.c_double
         L.poppy_pyr_tail_plan.argtypes = [i, i, i, i, vp, vp]
         L.poppy_hip_blur_margin.argtypes = [vp, vp, sz, i, i, i, i, vp, sz]
+        L.poppy_blur_margin_rects.argtypes = [i, i, i, i, vp, vp]
+        L.poppy_blur_margin_taps.argtypes = [vp]
+        L.poppy_hip_blur_margin_max_rows.argtypes = [vp, vp]
         L.poppy_hip_orb_describe.argtypes = [vp, vp, sz, i, i, vp, i, vp]
         L.poppy_hip_hamming_match.argtypes = [vp, vp, i, vp, i, vp, vp]
         L.poppy_match_points.argtypes = [vp, vp, i, i, i, d, vp, vp, vp, vp]
@@ -1142,6 +1146,26 @@ class Pool:
         return n
 
 
+def blur_margin_rects(w, h, union_w, union_h):
+    """Host-only: (status, rects [4, 4] int32 = left, right, top, bottom as (x, y, width, height), origin (x, y)) of blur_margin's geometry.
+    status is POPPY_OK, or POPPY_E_UNSUPPORTED (-6) where a strip leaves the canvas (the reference throws; the entry points refuse);
+    bad sizes raise."""
+    rects = np.zeros((4, 4), np.int32); origin = np.zeros(2, np.int32)
+    rc = lib().poppy_blur_margin_rects(int(w), int(h), int(union_w), int(union_h), _p(rects), _p(origin))
+    if rc not in (0, -6):
+        raise PoppyError(f"poppy_blur_margin_rects: {rc}")
+    return rc, rects, (int(origin[0]), int(origin[1]))
+
+
+def blur_margin_taps():
+    """Host-only: blur_margin's 127 fixed-point (8.8) taps."""
+    taps = np.zeros(127, np.int32)
+    rc = lib().poppy_blur_margin_taps(_p(taps))
+    if rc:
+        raise PoppyError(f"poppy_blur_margin_taps: {rc}")
+    return taps
+
+
 def dft_plan(n):
     """Host-only: (factors, itab, wave) of the length-n transform plan."""
     f = np.zeros(34, np.int32); nf = C.c_int(0); itab = np.zeros(n, np.int32); wave = np.zeros((n, 2), np.float32)
@@ -1568,12 +1592,27 @@ class Context:
         self._chk(lib().poppy_hip_orb_input(self.h, _p(gf), w, h, _p(g), _p(us), _p(gb), C.byref(d)), "orb_input")
         return dict(g=g, us=us, gb=gb, detail=d.value)
 
-    def blur_margin(self, bgr, union_w, union_h):
-        a = np.ascontiguousarray(bgr, np.uint8)
+    def blur_margin(self, bgr, union_w, union_h, src_pad=0, dst_pad=0):
+        """blur_margin's padded image.  bgr: HxWx3 uint8 whose rows may be strided (pixels contiguous), read in place; src_pad > 0 copies it
+        into rows src_pad bytes longer first.  dst_pad: the destination's rows are that many bytes longer (the pad bytes must come back untouched)."""
+        a = np.asarray(bgr, np.uint8)
         h, w = a.shape[:2]
-        out = np.zeros((union_h, union_w, 3), np.uint8)
-        self._chk(lib().poppy_hip_blur_margin(self.h, _p(a), w * 3, w, h, union_w, union_h, _p(out), union_w * 3), "blur_margin")
-        return out
+        if a.strides[1:] != (3, 1) or a.strides[0] < w * 3 or src_pad:
+            buf = np.full((h, w * 3 + src_pad), 0x5A, np.uint8)
+            buf[:, :w * 3] = a.reshape(h, w * 3)
+            a = buf[:, :w * 3].reshape(h, w, 3)
+        stride = a.strides[0]
+        full = np.full((union_h, union_w * 3 + dst_pad), 0xA5, np.uint8)
+        self._chk(lib().poppy_hip_blur_margin(self.h, a.ctypes.data, stride, w, h, union_w, union_h, _p(full), union_w * 3 + dst_pad), "blur_margin")
+        if dst_pad and not (full[:, union_w * 3:] == 0xA5).all():
+            raise PoppyError("blur_margin wrote into the destination's row padding")
+        return np.ascontiguousarray(full[:, :union_w * 3]).reshape(union_h, union_w, 3)
+
+    def blur_margin_max_rows(self):
+        """The most canvas rows blur_margin takes on this context's device."""
+        n = C.c_int(0)
+        self._chk(lib().poppy_hip_blur_margin_max_rows(self.h, C.byref(n)), "blur_margin_max_rows")
+        return n.value
 
     def time_last_warp(self, reps=50):
         """Average milliseconds per launch of the last frame's fused raster + warp kernel, relaunched back to back, nothing else running."""

@@ -183,6 +183,7 @@ struct poppy_hip_ctx {
     // what the RANSAC filter of the last poppy_hip_pair_begin_descriptors_ransac found (poppy_hip_pair_fundamental); set_points of any set-up ends its validity
     struct LastFundamental { bool valid = false; double f[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int n_matches = 0, n_inliers = 0, best = -1; } fundamental;
     DeviceBuffer ransac_scratch;                    // the filter's points, models and counts on the device (kernels_ransac.hip: ransac_counts_device)
+    int max_grid_y = 65535;                         // the device's maxGridSize[1]: the rows one launch_strip_blur takes (blur_margin_rows_fit)
 };
 
 // ---- packed pair state (see poppy_hip_ctx::arena) -------------------------------------------------------------------------
@@ -255,6 +256,9 @@ struct Timer {
 constexpr int kBlurMarginTaps = 127;
 std::vector<int> blur_margin_taps();
 void blur_margin_origin(int W, int H, int UW, int UH, int* x0, int* y0);
+bool blur_margin_rows_fit(const poppy_hip_ctx* c, int UH);
+constexpr const char* kBlurMarginOffCanvasMsg = "blur_margin: a margin strip leaves the canvas (an image about 99 times as high as wide, or as wide as high; the reference throws there)";
+constexpr const char* kBlurMarginRowsMsg = "blur_margin: the canvas has more rows than the device's grid takes in y";
 hipError_t blur_margin_strips(const uint8_t* canvas, uint8_t* out, uint32_t* tmp, const int* d_taps, int W, int H, int UW, int UH, hipStream_t s);
 
 inline ForegroundFilter& chain_fg(poppy_hip_ctx* c, int slot) { return slot ? c->foreground_b : c->foreground; }

@@ -69,6 +69,8 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
         if (inputs_on_device) stride = (size_t)w * 3;
         if (!p || w <= 0 || h <= 0 || stride < (size_t)w * 3) return fail(c, POPPY_E_ARG, "morph_list: bad image from the source");
         if (canvas && (w > UW || h > UH)) return fail(c, POPPY_E_ARG, "morph_list: an image is larger than the canvas");
+        if (canvas && poppy_blur_margin_rects(w, h, UW, UH, nullptr, nullptr) != POPPY_OK) return fail(c, POPPY_E_UNSUPPORTED, kBlurMarginOffCanvasMsg);
+        if (canvas && !blur_margin_rows_fit(c, UH)) return fail(c, POPPY_E_UNSUPPORTED, kBlurMarginRowsMsg);
         if (!canvas) {
             if (k == 0) { W = w; H = h; }
             else if (w != W || h != H) return fail(c, POPPY_E_ARG, "morph_list: images of different sizes and no canvas (poppy::morph takes one size)");

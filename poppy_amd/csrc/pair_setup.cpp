@@ -18,21 +18,25 @@ std::vector<int> blur_margin_taps() {
       taps[n / 2] = 256 - 2 * tot; }
     return taps;
 }
-// where a W x H image goes in the UW x UH canvas (its top-left pixel)
+// where a W x H image goes in the UW x UH canvas (its top-left pixel); the caller has checked the sizes
 void blur_margin_origin(int W, int H, int UW, int UH, int* x0, int* y0) {
-    *x0 = (int)(std::fabs((double)(W - UW)) / 2.0);
-    *y0 = (int)(std::fabs((double)(H - UH)) / 2.0);
+    int origin[2] = {0, 0};
+    (void)poppy_blur_margin_rects(W, H, UW, UH, nullptr, origin);
+    *x0 = origin[0]; *y0 = origin[1];
 }
-// canvas (the image already placed, zeros around it) -> out: the canvas, then the four margin strips blurred from it
+// the device's grid.y bound holds a strip's rows (launch_strip_blur: one grid row per strip row; the side strips are UH high)
+bool blur_margin_rows_fit(const poppy_hip_ctx* c, int UH) { return UH <= c->max_grid_y; }
+// canvas (the image already placed, zeros around it) -> out: the canvas, then the four margin strips blurred from it.
+// Only for sizes poppy_blur_margin_rects admits: the entry points refuse the others before they come here, and so does this.
 hipError_t blur_margin_strips(const uint8_t* canvas, uint8_t* out, uint32_t* tmp, const int* d_taps, int W, int H, int UW, int UH, hipStream_t s) {
+    int rects[16];
+    if (poppy_blur_margin_rects(W, H, UW, UH, rects, nullptr) != POPPY_OK) return hipErrorInvalidValue;
     hipError_t e = hipMemcpyAsync(out, canvas, (size_t)UW * UH * 3, hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return e;
-    const double margin = (W + H) / 100.0;
-    double dx = std::fabs((double)(W - UW)) / 2.0, dy = std::fabs((double)(H - UH)) / 2.0;
-    dx = (dx == 0 ? 1.3 : dx + margin);
-    dy = (dy == 0 ? 1.3 : dy + margin);
-    const int rects[4][4] = {{0, 0, (int)dx, UH}, {(int)(UW - dx), 0, (int)dx, UH}, {0, 0, UW, (int)dy}, {0, (int)(UH - dy), UW, (int)dy}};
-    for (const auto& r : rects) launch_strip_blur(canvas, out, UW, tmp, d_taps, kBlurMarginTaps, r[0], r[1], r[2], r[3], s);   // left, right, top, bottom: later strips win
+    for (int k = 0; k < 4; ++k) {                      // left, right, top, bottom: later strips win; a strip of width or height 0 is skipped
+        const int* r = rects + 4 * k;
+        launch_strip_blur(canvas, out, UW, tmp, d_taps, kBlurMarginTaps, r[0], r[1], r[2], r[3], s);
+    }
     return hipGetLastError();
 }
 
@@ -315,6 +319,8 @@ int poppy_hip_gabor_field(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
 int poppy_hip_blur_margin(poppy_hip_ctx* c, const uint8_t* src, size_t stride, int W, int H, int UW, int UH, uint8_t* dst, size_t dst_stride) {
     if (!c) return POPPY_E_ARG;
     if (!src || !dst || W <= 0 || H <= 0 || UW < W || UH < H || stride < (size_t)W * 3 || dst_stride < (size_t)UW * 3) return fail(c, POPPY_E_ARG, "bad arguments");
+    if (poppy_blur_margin_rects(W, H, UW, UH, nullptr, nullptr) != POPPY_OK) return fail(c, POPPY_E_UNSUPPORTED, kBlurMarginOffCanvasMsg);
+    if (!blur_margin_rows_fit(c, UH)) return fail(c, POPPY_E_UNSUPPORTED, kBlurMarginRowsMsg);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t UB = (size_t)UW * UH * 3;
     uint8_t *canvas = nullptr, *out = nullptr; uint32_t* tmp = nullptr; int* d_taps = nullptr;
@@ -336,6 +342,33 @@ int poppy_hip_blur_margin(poppy_hip_ctx* c, const uint8_t* src, size_t stride, i
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     cleanup();
     if (e != hipSuccess) { c->err = std::string("blur_margin: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    return POPPY_OK;
+}
+
+// The one statement of blur_margin's geometry (src/util.cpp:580-595): rects = left, right, top, bottom as (x, y, width, height), origin = the
+// image's top-left pixel in the canvas.  Either may be NULL.  Both are filled whenever the sizes are valid, also with POPPY_E_UNSUPPORTED.
+int poppy_blur_margin_rects(int W, int H, int UW, int UH, int* rects, int* origin) {
+    if (W <= 0 || H <= 0 || UW < W || UH < H) return POPPY_E_ARG;
+    const double margin = ((double)W + (double)H) / 100.0;
+    double dx = std::fabs((double)W - (double)UW) / 2.0, dy = std::fabs((double)H - (double)UH) / 2.0;
+    if (origin) { origin[0] = (int)dx; origin[1] = (int)dy; }
+    dx = (dx == 0 ? 1.3 : dx + margin);
+    dy = (dy == 0 ? 1.3 : dy + margin);
+    if (rects) {
+        const int r[16] = {0, 0, (int)dx, UH,  (int)(UW - dx), 0, (int)dx, UH,  0, 0, UW, (int)dy,  0, (int)(UH - dy), UW, (int)dy};
+        memcpy(rects, r, sizeof r);
+    }
+    return (int)dx > UW || (int)dy > UH ? POPPY_E_UNSUPPORTED : POPPY_OK;      // a strip leaves the canvas: the reference's Mat(Rect) throws
+}
+int poppy_blur_margin_taps(int* taps) {
+    if (!taps) return POPPY_E_ARG;
+    const std::vector<int> t = blur_margin_taps();
+    memcpy(taps, t.data(), sizeof(int) * t.size());
+    return POPPY_OK;
+}
+int poppy_hip_blur_margin_max_rows(poppy_hip_ctx* c, int* rows) {
+    if (!c || !rows) return POPPY_E_ARG;
+    *rows = c->max_grid_y;
     return POPPY_OK;
 }
 

@@ -377,7 +377,8 @@ def gabor_filter_direct(src, ks, bank):
 
 def blur_margin(img, uw, uh):
     a = np.ascontiguousarray(img, np.uint8); o = np.zeros((uh, uw, 3), np.uint8)
-    lib().orc_blur_margin(_vp(a), a.shape[1], a.shape[0], uw, uh, _vp(o))
+    if lib().orc_blur_margin(_vp(a), a.shape[1], a.shape[0], uw, uh, _vp(o)):
+        raise ValueError("blur_margin: %dx%d in %dx%d: a margin strip leaves the canvas (the reference throws)" % (a.shape[1], a.shape[0], uw, uh))
     return o
 
 
