@@ -477,7 +477,40 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * counts that are all zero, a sum of 2^32 or more, and more symbols with a count than 2^limit (no code of that length holds them).
  * poppy_hip_bgr_to_png_opt_frame codes a host frame on the context's GPU as poppy_hip_bgr_to_png_runs_frame does, and poppy_hip_png_optimal_lengths runs the
  * device's length build alone on given counts, as poppy_hip_jpeg_optimal_table does: the same bytes as the host statements, with their refusals.  The format
- * applies wherever POPPY_FRAME_PNG_RUNS applies and stays BGR wherever that stays BGR.  */
+ * applies wherever POPPY_FRAME_PNG_RUNS applies and stays BGR wherever that stays BGR.
+ *
+ * POPPY_FRAME_PNG_SEQ: POPPY_FRAME_PNG_OPT with ONE ninth table for all the frames a call hands to its writer, built from the summed symbol counts of the whole
+ * sequence: the build runs once per sequence, not once per segment, and its 900-bit header is paid only by the segments that choose it.  Its value is 131072;
+ * 131071 and 131073 stay unknown in both enums; there is no sink value of its own: POPPY_SINK_PNG takes the frames and poppy_png_frame_bytes reads `total`.  The
+ * format is POPPY_FRAME_PNG_OPT word for word — layout and offsets, File, Filtered stream, Segments of POPPY_PNG_SEGMENT_BYTES, Tokens with POPPY_PNG_RUN_MIN,
+ * 78 01, blocks that are not byte-aligned, BFINAL in a frame's last block, Adler-32, one IDAT, IEND — with these changes only:
+ *   Counts.  For s in 0..285, count[s] is how often the tokens of all segments of all frames of the sequence hold literal or length symbol s; count[256] is the
+ *      number of segments of the sequence, one end-of-block per block.  A frame that stands in the sequence N times counts N times.
+ *   Table.  poppy_png_optimal_lengths(count, 286, 15), the unchanged rule, once per sequence; codes are the canonical codes by (length, symbol).  A symbol that
+ *      some segment never emits still has a code, because another segment gave it a count; a symbol no segment emits has none.
+ *   Block header.  POPPY_FRAME_PNG_OPT's own-header rule applied to the sequence's lengths: HLIT from the highest symbol with a length, HDIST = 0, the run-coded
+ *      length sequence on its own 7-bit code-length code.  It is one bit string per sequence, of at most 2083 bits; BFINAL, bit 0, is set in a frame's last
+ *      block only.
+ *   Table choice.  Nine candidates per segment: POPPY_FRAME_PNG_RUNS' tables 0..7, and 8, the sequence's table.  A candidate's cost is its header bits + the
+ *      tokens' codes + the matches' extra and distance bits + its end-of-block code; the smallest wins, ties go to the lowest index: table 8 wins only outright.
+ *   Consequences.  Every block is no longer than POPPY_FRAME_PNG_RUNS' block of the same segment: total(PNG_SEQ) <= total(PNG_RUNS) for every frame of every
+ *      sequence, and poppy_frame_bytes(POPPY_FRAME_PNG_SEQ, w, h) is POPPY_FRAME_PNG_RUNS' capacity.  A sequence of one frame of one segment is byte for byte
+ *      that frame's POPPY_FRAME_PNG_OPT frame.  Every frame decodes to exactly its pixels.  The order of the frames changes no table.
+ *   Limits, checked on the arguments alone before any state changes, refused with POPPY_E_UNSUPPORTED.  Per frame: POPPY_FRAME_PNG_RUNS'.  Per sequence: with
+ *      n = h (1 + 3 w) and S = ceil(n / 8192), n_frames * (n + S) <= POPPY_PNG_SEQ_MAX_SYMBOLS = 2^32 - 1.  A segment of s bytes has at most s tokens and one
+ *      end-of-block, so the sum of the counts stays under the length rule's own refusal and the device adds in 32 bits.  That allows 690 frames at 1080p.
+ *   Sequence.  Exactly what it is under POPPY_FRAME_JPEG_SEQ: all the frames one call hands to its writer; in poppy_hip_morph_list and in the pool one pair's
+ *      frames.  The t = 0 / t = 1 copies of poppy_hip_render_phases, the phase-0 / phase-1 short-circuits and the POPPY_E_NOMATCH linear-blend frames count as
+ *      POPPY_FRAME_JPEG_SEQ counts them.  The frames wait on the device as filtered streams; the writer is first called after the last frame is rendered and gets
+ *      the frames in order, as (frame, width, height, stride = 0).
+ * poppy_bgr_frames_to_png_seq_frames is the host statement: poppy_bgr_frames_to_jpeg_seq_frames' arguments without the quality, frame k into dst +
+ * k * poppy_frame_bytes(POPPY_FRAME_PNG_SEQ, width, height); POPPY_E_ARG for a null pointer, n_frames < 1, an empty frame, a stride shorter than a row or a
+ * frame_stride shorter than a frame, POPPY_E_UNSUPPORTED for the limits; both before a byte is read.  poppy_png_seq_table gives the table and its header bit
+ * string (BFINAL 0; header_bits: POPPY_PNG_SEQ_HEADER_BYTES bytes, bit i of the string is bit i mod 8 of byte i / 8; either output may be null) from given counts:
+ * poppy_png_optimal_lengths' refusals, and POPPY_E_ARG too where count[256] is 0.  poppy_hip_bgr_frames_to_png_seq_frames does the same on the context's GPU, in a
+ * sequence that lives for the call and disturbs neither a resident pair nor the context's own sequence, and poppy_hip_png_seq_table runs the device's table build
+ * alone on given counts: the same bytes as the host statements, with their refusals.  The format applies wherever POPPY_FRAME_PNG_RUNS applies and stays BGR
+ * wherever that stays BGR.  */
 #define POPPY_PAL8_MAX_PIXELS (1 << 24)
 #define POPPY_PAL8_SEQ_MAX_PIXELS (1ull << 32)
 #define POPPY_GIF_SEGMENT_PIXELS 2048
@@ -494,9 +527,12 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
 #define POPPY_PNG_TABLES 8
 #define POPPY_PNG_HEADER_BYTES 236      /* (any header of the form fits: 17 + 19 * 3 + 258 * 7 bits) */
 #define POPPY_PNG_RUN_MIN 8
+#define POPPY_PNG_SEQ_MAX_SYMBOLS 0xffffffffull      /* (n_frames * (stream bytes + segments of a frame) at the most: POPPY_FRAME_PNG_SEQ, Limits) */
+#define POPPY_PNG_SEQ_HEADER_BYTES 261      /* (the sequence's header fits: 17 + 19 * 3 + 287 * 7 = 2083 bits) */
 enum { POPPY_FRAME_BGR = 0, POPPY_FRAME_I420 = 1, POPPY_FRAME_PAL8 = 8, POPPY_FRAME_PAL8_SEQ = 16, POPPY_FRAME_GIF = 64, POPPY_FRAME_GIF_SEQ = 128, POPPY_FRAME_JPEG = 256,
        POPPY_FRAME_JPEG444 = 512, POPPY_FRAME_PNG = 1024, POPPY_FRAME_PNG_RUNS = 2048, POPPY_FRAME_JPEG_OPT = 4096,
-       POPPY_FRAME_JPEG444_OPT = 8192, POPPY_FRAME_PNG_OPT = 16384, POPPY_FRAME_JPEG_SEQ = 32768, POPPY_FRAME_JPEG444_SEQ = 65536 };
+       POPPY_FRAME_JPEG444_OPT = 8192, POPPY_FRAME_PNG_OPT = 16384, POPPY_FRAME_JPEG_SEQ = 32768, POPPY_FRAME_JPEG444_SEQ = 65536,
+       POPPY_FRAME_PNG_SEQ = 131072 };
 int poppy_hip_set_frame_format(poppy_hip_ctx* ctx, int format);
 size_t poppy_frame_bytes(int format, int width, int height);
 int poppy_bgr_to_i420(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
@@ -543,6 +579,10 @@ int poppy_png_optimal_lengths(const uint32_t* counts, int n_symbols, int limit, 
 int poppy_bgr_to_png_opt_frame(const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 int poppy_hip_bgr_to_png_opt_frame(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, uint8_t* dst);
 int poppy_hip_png_optimal_lengths(poppy_hip_ctx* ctx, const uint32_t* counts, int n_symbols, int limit, uint8_t* lengths);
+int poppy_png_seq_table(const uint32_t counts[286], uint8_t lengths[286], uint8_t* header_bits, int* n_header_bits);
+int poppy_bgr_frames_to_png_seq_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst);
+int poppy_hip_bgr_frames_to_png_seq_frames(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, uint8_t* dst);
+int poppy_hip_png_seq_table(poppy_hip_ctx* ctx, const uint32_t counts[286], uint8_t lengths[286], uint8_t* header_bits, int* n_header_bits);
 /* Scaled hand-off: frames rendered at the pair's resolution and handed to the writer scaled down by a whole factor, on the GPU, in front of the format
  * conversion.  The pair's resolution decides the keypoints, the mesh and the morph; the scale only decides what crosses the link and what the writer gets.
  *   The rule.  A factor s is a whole number from 1 to POPPY_FRAME_SCALE_MAX = 8; 1, the default, is the identity.  A width x height BGR frame becomes
@@ -1079,7 +1119,7 @@ int poppy_hip_morph_pairs(const int* devices, int n_devices, int contexts_per_de
  * the sampling byte 0x11 is held to POPPY_FRAME_JPEG444's capacity, any other to POPPY_FRAME_JPEG's; nothing else about the sink differs.  POPPY_FRAME_JPEG_OPT
  * and POPPY_FRAME_JPEG444_OPT frames are taken in the same mix: a frame whose DHT segment is not byte for byte the Annex K one is held to the OPT capacity of its
  * sampling, every other frame as before.
- * PNG: one PNG file per frame from POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS and POPPY_FRAME_PNG_OPT frames as they come, in any mix (a PNG file does not say who coded it); `path` follows
+ * PNG: one PNG file per frame from POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_PNG_OPT and POPPY_FRAME_PNG_SEQ frames as they come, in any mix (a PNG file does not say who coded it); `path` follows
  * PPM's %d rule exactly.  The file holds the frame's bytes 4 .. total as they are.  The stride must be 0, bytes 4..11 the PNG signature, IHDR must name the sink's
  * width and height, and `total` must be inside the larger of the two formats' capacities.  A frame
  * of any other format fails this sink, and a PNG frame fails every other sink.

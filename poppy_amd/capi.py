@@ -30,12 +30,14 @@ FRAME_PNG, FRAME_PNG_RUNS = 1024, 2048
 FRAME_JPEG_OPT, FRAME_JPEG444_OPT = 4096, 8192
 FRAME_JPEG_SEQ, FRAME_JPEG444_SEQ = 32768, 65536      # JPEG_OPT's frames on one Huffman table set for all the frames a call hands to its writer
 FRAME_PNG_OPT = 16384
-FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444, FRAME_PNG, FRAME_PNG_RUNS, FRAME_JPEG_OPT, FRAME_JPEG444_OPT, FRAME_PNG_OPT, FRAME_JPEG_SEQ, FRAME_JPEG444_SEQ)      # a frame whose length its first four bytes hold
+FRAME_PNG_SEQ = 131072      # PNG_OPT's frames on one ninth table for all the frames a call hands to its writer
+FRAMES_CODED = (FRAME_GIF, FRAME_GIF_SEQ, FRAME_JPEG, FRAME_JPEG444, FRAME_PNG, FRAME_PNG_RUNS, FRAME_JPEG_OPT, FRAME_JPEG444_OPT, FRAME_PNG_OPT, FRAME_JPEG_SEQ, FRAME_JPEG444_SEQ, FRAME_PNG_SEQ)      # a frame whose length its first four bytes hold
 JPEG_QUALITY_DEFAULT = 90
 SINK_RAW, SINK_PPM, SINK_Y4M, SINK_Y4M420, SINK_GIF, SINK_GIF_GLOBAL, SINK_GIF_CODED, SINK_GIF_GLOBAL_CODED, SINK_MJPEG = 0, 1, 2, 3, 8, 16, 64, 128, 256
 SINK_PNG = 1024
 PNG_SEGMENT_BYTES, PNG_TABLES, PNG_HEADER_BYTES = 8192, 8, 236
 PNG_RUN_MIN, PNG_RUNS_SYMBOLS = 8, 286
+PNG_SEQ_MAX_SYMBOLS, PNG_SEQ_HEADER_BYTES = (1 << 32) - 1, 261
 
 # every symbol include/poppy_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -65,6 +67,7 @@ SYMBOLS = [
     "poppy_png_frame_bytes", "poppy_png_table", "poppy_bgr_to_png_frame", "poppy_hip_bgr_to_png_frame",
     "poppy_png_runs_table", "poppy_bgr_to_png_runs_frame", "poppy_hip_bgr_to_png_runs_frame",
     "poppy_png_optimal_lengths", "poppy_bgr_to_png_opt_frame", "poppy_hip_bgr_to_png_opt_frame", "poppy_hip_png_optimal_lengths",
+    "poppy_png_seq_table", "poppy_bgr_frames_to_png_seq_frames", "poppy_hip_bgr_frames_to_png_seq_frames", "poppy_hip_png_seq_table",
     "poppy_hip_set_frame_scale", "poppy_hip_pool_set_frame_scale", "poppy_frame_scaled_size", "poppy_bgr_downscale", "poppy_hip_bgr_downscale",
     "poppy_hip_set_frame_size", "poppy_hip_pool_set_frame_size", "poppy_frame_fit_size", "poppy_bgr_resize_area", "poppy_hip_bgr_resize_area",
     "poppy_hip_bgr_resize_area_form",
@@ -253,6 +256,10 @@ def lib():
         L.poppy_bgr_to_png_opt_frame.argtypes = [vp, sz, i, i, vp]
         L.poppy_hip_bgr_to_png_opt_frame.argtypes = [vp, vp, sz, i, i, vp]
         L.poppy_hip_png_optimal_lengths.argtypes = [vp, vp, i, i, vp]
+        L.poppy_png_seq_table.argtypes = [vp, vp, vp, vp]
+        L.poppy_bgr_frames_to_png_seq_frames.argtypes = [vp, sz, sz, i, i, i, vp]
+        L.poppy_hip_bgr_frames_to_png_seq_frames.argtypes = [vp, vp, sz, sz, i, i, i, vp]
+        L.poppy_hip_png_seq_table.argtypes = [vp, vp, vp, vp, vp]
         L.poppy_hip_set_frame_scale.argtypes = [vp, i]
         L.poppy_hip_pool_set_frame_scale.argtypes = [vp, i]
         L.poppy_frame_scaled_size.argtypes = [i, i, i, vp, vp]
@@ -358,7 +365,7 @@ def jpeg_frame_bytes(frame):
 
 
 def png_frame_bytes(frame):
-    """Host-only: `total` of a FRAME_PNG, FRAME_PNG_RUNS or FRAME_PNG_OPT frame, its length in bytes (poppy_png_frame_bytes: the first four bytes, little-endian)."""
+    """Host-only: `total` of a FRAME_PNG, FRAME_PNG_RUNS, FRAME_PNG_OPT or FRAME_PNG_SEQ frame, its length in bytes (poppy_png_frame_bytes: the first four bytes, little-endian)."""
     return coded_frame_bytes(frame, "png")
 
 
@@ -560,6 +567,45 @@ def png_optimal_lengths(counts, limit=15):
     return _optimal_lengths(lib().poppy_png_optimal_lengths, counts, limit, "png_optimal_lengths")
 
 
+def _png_seq_frames(call, what, frames, row_pad, frame_pad, chk=None):
+    a, stride, frame_stride, n, w, h = _padded_frames(frames, row_pad, frame_pad)
+    out = np.empty((max(n, 1), max(frame_bytes(FRAME_PNG_SEQ, w, h), 4)), np.uint8)
+    rc = call(_p(a), stride, frame_stride, n, w, h, _p(out))
+    if chk:
+        chk(rc, what)
+    elif rc:
+        raise PoppyError(f"poppy_{what}: {rc}")
+    return [f[:png_frame_bytes(f)].copy() for f in out]
+
+
+def bgr_frames_to_png_seq_frames(frames, row_pad=0, frame_pad=0):
+    """Host-only: the FRAME_PNG_SEQ frames of a sequence of n HxWx3 BGR frames (poppy_bgr_frames_to_png_seq_frames): every frame's token counts summed, one table
+    built from the sums, every frame a complete PNG file whose segments choose among FRAME_PNG_RUNS' eight tables and that one.  A list of n flat uint8 arrays,
+    each cut to its `total`.  row_pad / frame_pad: as in bgr_frames_to_pal8."""
+    return _png_seq_frames(lib().poppy_bgr_frames_to_png_seq_frames, "bgr_frames_to_png_seq_frames", frames, row_pad, frame_pad)
+
+
+def _png_seq_table(call, counts, what, chk=None):
+    a = np.ascontiguousarray(counts, np.uint32).ravel()
+    if a.size != PNG_RUNS_SYMBOLS:
+        raise PoppyError(f"{what}: counts has {PNG_RUNS_SYMBOLS} entries")
+    lengths = np.zeros(PNG_RUNS_SYMBOLS, np.uint8)
+    header = np.zeros(PNG_SEQ_HEADER_BYTES, np.uint8)
+    n = C.c_int(0)
+    rc = call(_p(a), _p(lengths), _p(header), C.byref(n))
+    if chk:
+        chk(rc, what)
+    elif rc:
+        raise PoppyError(f"poppy_{what}: {rc}")
+    return lengths, np.unpackbits(header, bitorder="little")[:n.value].copy()
+
+
+def png_seq_table(counts):
+    """Host-only: the one table of a FRAME_PNG_SEQ sequence from its 286 summed counts (poppy_png_seq_table): the code lengths as a uint8 array, and the table's
+    block header as an array of bits in stream order (bit 0 is BFINAL, left 0)."""
+    return _png_seq_table(lib().poppy_png_seq_table, counts, "png_seq_table")
+
+
 def _gif_frames(call, frames, row_pad, frame_pad, chk=None):
     a, stride, frame_stride, n, w, h = _padded_frames(frames, row_pad, frame_pad)
     out = np.empty((n, max(frame_bytes(FRAME_GIF_SEQ, w, h), 4)), np.uint8)
@@ -687,7 +733,7 @@ def pal8_to_bgr(frame, w, h):
 
 
 def _frame_view(ptr, w, h, stride, fmt):
-    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF, GIF_SEQ, JPEG, JPEG444, PNG, PNG_RUNS and PNG_OPT.  A view: valid during the callback."""
+    """A writer's frame as numpy: HxWx3 for BGR, the flat bytes (frame_bytes long) for I420, PAL8 and PAL8_SEQ, the flat `total` bytes for GIF, GIF_SEQ, JPEG, JPEG444, PNG, PNG_RUNS, PNG_OPT and PNG_SEQ.  A view: valid during the callback."""
     if fmt in FRAMES_CODED:                                                      # a coded frame: its own length, not the capacity (every coded format keeps it in its first four bytes)
         return np.ctypeslib.as_array(ptr, shape=(int(lib().poppy_gif_frame_bytes(ptr)),))
     if fmt in (FRAME_I420, FRAME_PAL8, FRAME_PAL8_SEQ):
@@ -1249,7 +1295,9 @@ class Context:
         counts; the writer is first called after the last frame is rendered.
         FRAME_PNG: every frame one PNG file, lossless, coded on the GPU; flat arrays of each frame's own length (png_frame_bytes).
         FRAME_PNG_RUNS: the same with runs of equal bytes coded as matches: several times smaller on frames with flat or smooth regions.
-        FRAME_PNG_OPT: FRAME_PNG_RUNS with every segment on the shortest of the eight tables and one built on the GPU from its own symbols: never larger."""
+        FRAME_PNG_OPT: FRAME_PNG_RUNS with every segment on the shortest of the eight tables and one built on the GPU from its own symbols: never larger.
+        FRAME_PNG_SEQ: FRAME_PNG_OPT's files on ONE ninth table for all the frames a call hands to its writer, built once from their summed token counts; the
+        frames wait on the GPU as filtered streams and reach the writer after the last is rendered.  Never larger than FRAME_PNG_RUNS."""
         self._chk(lib().poppy_hip_set_frame_format(self.h, int(fmt)), "set_frame_format")
         self.frame_format = int(fmt)
 
@@ -1308,6 +1356,16 @@ class Context:
         """The FRAME_GIF frame of a flat PAL8 frame, coded on this context's GPU (poppy_hip_pal8_to_gif_frame: upload, the two kernels, download): the bytes of
         the host's pal8_to_gif_frame."""
         return _pal8_to_gif(lambda *args: lib().poppy_hip_pal8_to_gif_frame(self.h, *args), pal8, w, h, self._chk)
+
+    def bgr_frames_to_png_seq_frames(self, frames, row_pad=0, frame_pad=0):
+        """The FRAME_PNG_SEQ frames of a sequence of n HxWx3 BGR frames, coded on this context's GPU on a sequence that lives for the call
+        (poppy_hip_bgr_frames_to_png_seq_frames: per frame upload, filter and counting kernel; one table build; per frame choice, pack and download): the bytes of
+        the host's bgr_frames_to_png_seq_frames, as its list."""
+        return _png_seq_frames(lambda *args: lib().poppy_hip_bgr_frames_to_png_seq_frames(self.h, *args), "bgr_frames_to_png_seq_frames", frames, row_pad, frame_pad, self._chk)
+
+    def png_seq_table(self, counts):
+        """The table-build kernel of the FRAME_PNG_SEQ coder alone on 286 summed counts (poppy_hip_png_seq_table): what the host's png_seq_table gives."""
+        return _png_seq_table(lambda *args: lib().poppy_hip_png_seq_table(self.h, *args), counts, "png_seq_table", self._chk)
 
     def bgr_frames_to_jpeg_seq_frames(self, frames, quality=JPEG_QUALITY_DEFAULT, fmt=FRAME_JPEG_SEQ, row_pad=0, frame_pad=0):
         """The FRAME_JPEG_SEQ (FRAME_JPEG444_SEQ) frames of a sequence of n HxWx3 BGR frames, coded on this context's GPU on a sequence that lives for the call

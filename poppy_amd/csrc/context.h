@@ -128,7 +128,7 @@ struct poppy_hip_ctx {
     DeviceBuffer scale_scratch;                     // the scaled BGR of the copies and fallback frames that no slot renders (writer_image.h: scale_into_scratch)
     DeviceBuffer fmt_scratch;                       // I420 / I444 / PAL8 of the copies and fallback frames that no slot renders (download_frame)
     uint8_t* fmt_scratch_tables = nullptr;          // ... and the PAL8 conversion's tables for them
-    PaletteSeq seq;                                 // the sequence formats (PAL8_SEQ, GIF_SEQ, JPEG_SEQ, JPEG444_SEQ): the sequence being collected (palette_seq.h: seq_begin .. seq_finish)
+    PaletteSeq seq;                                 // the sequence formats (PAL8_SEQ, GIF_SEQ, JPEG_SEQ, JPEG444_SEQ, PNG_SEQ): the sequence being collected (palette_seq.h: seq_begin .. seq_finish)
     double wait_ms[4] = {0, 0, 0, 0};               // host waits inside submit_frame since the context was made (POPPY_SEQ_TIMING prints the per-sequence share)
     ForegroundFilter foreground, foreground_b;      // two instances: the images of a pair are filtered side by side
     // The two chain slots (slot 0 = foreground + orb, slot 1 = foreground_b + orb_b; chain_fg / chain_orb below).  After a set-up from raw images the slot

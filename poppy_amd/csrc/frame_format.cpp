@@ -7,9 +7,10 @@ static bool pal8_fits(int W, int H) { return (unsigned long long)W * (unsigned l
 constexpr const char* kPal8SizeMsg = "POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 2^24 pixels";
 constexpr const char* kGifSizeMsg = "POPPY_FRAME_GIF and POPPY_FRAME_GIF_SEQ take frames of at most 65535 pixels in width and height";
 constexpr const char* kJpegSizeMsg = "POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444 and their OPT and SEQ forms take frames of at most 65535 pixels in width and height whose capacity stays below 2^32 bytes";
-constexpr const char* kPngSizeMsg = "POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS and POPPY_FRAME_PNG_OPT take frames whose capacity stays below 2^31 bytes";
+constexpr const char* kPngSizeMsg = "POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_PNG_OPT and POPPY_FRAME_PNG_SEQ take frames whose capacity stays below 2^31 bytes";
 constexpr const char* kSeqSizeMsg = "POPPY_FRAME_PAL8_SEQ and POPPY_FRAME_GIF_SEQ take sequences of fewer than 2^32 pixels in all";
 constexpr const char* kJpegSeqSizeMsg = "POPPY_FRAME_JPEG_SEQ and POPPY_FRAME_JPEG444_SEQ take sequences of at most POPPY_JPEG_SEQ_MAX_SYMBOLS / 64 blocks of 8 x 8 samples in all";
+constexpr const char* kPngSeqSizeMsg = "POPPY_FRAME_PNG_SEQ takes sequences of at most POPPY_PNG_SEQ_MAX_SYMBOLS filtered bytes and segments in all";
 
 const char* format_refuses(int fmt, int W, int H) {
     const FormatTraits* t = format_traits(fmt);
@@ -21,6 +22,7 @@ const char* format_refuses(int fmt, int W, int H) {
 const char* sequence_refuses(int fmt, int n, int W, int H) {
     if (const char* why = format_refuses(fmt, W, H)) return why;
     if (const FormatTraits* t = format_traits(fmt)) if (t->coder == kCoderJpeg) return jpeg_seq_fits(n, W, H, t->sampling()) ? nullptr : kJpegSeqSizeMsg;      // the symbol bound; the pixel bound is the palette sequences'
+    if (const FormatTraits* t = format_traits(fmt)) if (t->coder == kCoderPng) return png_seq_fits(n, W, H) ? nullptr : kPngSeqSizeMsg;
     return (unsigned long long)n * (unsigned long long)W * (unsigned long long)H >= POPPY_PAL8_SEQ_MAX_PIXELS ? kSeqSizeMsg : nullptr;
 }
 size_t writer_stride(int fmt, int W) { return format_stride(*format_traits(fmt), W); }
@@ -132,6 +134,12 @@ int alloc_slot_format(poppy_hip_ctx* c) {
         }
     }
     if (!t.sequence) return POPPY_OK;
+    if (t.coder == kCoderPng) {                                    // a PNG sequence: its summed counts (zero) and its built table
+        if (c->seq.png) return POPPY_OK;
+        HIPCHK(c, hipMalloc((void**)&c->seq.png, kPngSeqTableBytes));
+        HIPCHK(c, hipMemset(c->seq.png, 0, kPngSeqTableBytes));
+        return POPPY_OK;
+    }
     if (t.coder != kCoderJpeg) return alloc_zeroed_tables(c, &c->seq.tables, kPal8SeqTableBytes);
     { int rc = ensure_jpeg_tables(c); if (rc) return rc; }         // a JPEG sequence: the quality's tables, and the sequence's counts (zero) and built tables
     if (c->seq.jpeg) return POPPY_OK;
@@ -151,7 +159,7 @@ void free_slot_format_ctx(SlotFormat& f) {
 }
 void free_context_format(poppy_hip_ctx* c) {
     for (DeviceBuffer* b : {&c->scale_scratch, &c->fmt_scratch, &c->seq.store, &c->seq.idx, &c->seq.coded}) b->release();
-    for (uint8_t* b : {c->fmt_scratch_tables, c->seq.tables, c->seq.jpeg, c->jpeg_tables}) if (b) (void)hipFree(b);
+    for (uint8_t* b : {c->fmt_scratch_tables, c->seq.tables, c->seq.jpeg, c->seq.png, c->jpeg_tables}) if (b) (void)hipFree(b);
     c->jpeg_tables = nullptr;
     if (c->seq.coded_total) (void)hipHostFree(c->seq.coded_total);
     c->fmt_scratch_tables = nullptr;
@@ -164,6 +172,7 @@ bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt, c
     const FrameRaster raster = t.slot_raster();
     if (g.scaled() && !f.scaled) return false;
     if (t.sequence && t.coder == kCoderJpeg) return c->seq.open && c->seq.jpeg && c->jpeg_tables;      // (its pass runs on the frame's own stream: enqueue_body)
+    if (t.sequence && t.coder == kCoderPng) return c->seq.open && c->seq.png;      // (the same)
     if (t.sequence) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
     if (raster != kRasterNone && !(f.*kRasterBuffer[raster])) return false;
     if (raster == kRasterPal8 && !(f.pal8_tables && f.fmt_stream && f.bgr_done)) return false;

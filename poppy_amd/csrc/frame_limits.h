@@ -31,6 +31,17 @@ inline bool jpeg_seq_fits(int n, int W, int H, poppy_hip::jpeg::Sampling s = pop
 // A PNG-coded frame: what the format takes is a capacity (png_tables.h; with runs coded as matches png_runs_tables.h) below 2^31 bytes, which IDAT's length field and `total` hold
 inline bool png_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
 inline bool png_runs_fits(int W, int H) { return (unsigned long long)W * (unsigned long long)H < (1ull << 31) && poppy_hip::png_runs::frame_capacity((size_t)W, (size_t)H) < (1ull << 31); }
+// ... and a sequence of n such frames on one table (POPPY_FRAME_PNG_SEQ): a segment of s bytes has at most s tokens and one end-of-block, so with n_bytes the stream's
+// bytes and S its segments, n * (n_bytes + S) bounds the sum of the sequence's counts; at most POPPY_PNG_SEQ_MAX_SYMBOLS keeps it below the length rule's refusal
+// and lets the device add in 32 bits (include/poppy_hip.h: Limits)
+constexpr bool png_seq_symbols_fit(unsigned long long n, unsigned long long w, unsigned long long h) {
+    const unsigned long long n_bytes = h * (1 + 3 * w), segments = (n_bytes + POPPY_PNG_SEGMENT_BYTES - 1) / POPPY_PNG_SEGMENT_BYTES;
+    return n >= 1 && n <= POPPY_PNG_SEQ_MAX_SYMBOLS / (n_bytes + segments);
+}
+static_assert(png_seq_symbols_fit(858993459, 1, 1) && !png_seq_symbols_fit(858993460, 1, 1), "1 x 1: 4 bytes and a segment, 5 * 858993459 = 2^32 - 1 is the last sequence admitted");
+static_assert(png_seq_symbols_fit((1u << 29) - 1, 2, 1) && !png_seq_symbols_fit(1u << 29, 2, 1), "2 x 1: 7 bytes and a segment, 8 * 2^29 = 2^32 is refused");
+static_assert(png_seq_symbols_fit(690, 1920, 1080) && !png_seq_symbols_fit(691, 1920, 1080), "include/poppy_hip.h states 690 frames at 1080p");
+inline bool png_seq_fits(int n, int W, int H) { return n >= 1 && W >= 1 && H >= 1 && png_runs_fits(W, H) && png_seq_symbols_fit((unsigned long long)n, (unsigned long long)W, (unsigned long long)H); }
 
 // The record of a format.  A frame reaches its writer in up to two steps behind the BGR frame: the raster step (the BGR frame as planes or as palette indices) and
 // the coder step, which reads the raster form (PNG: the BGR frame itself) and gives a frame whose length its own bytes decide.
@@ -41,9 +52,9 @@ struct FormatTraits {
     const char* name;          // for messages: a coded format's is its coder's ("JPEG frame coding: ")
     FrameRaster raster;
     FrameCoder coder;
-    int variant;               // the JPEG coder's sampling (jpeg::Sampling); the PNG coder's tokens and tables (png::Variant): literals, runs as matches, or those on the segments' own tables
+    int variant;               // the JPEG coder's sampling (jpeg::Sampling); the PNG coder's tokens and tables (png::Variant): literals, runs as matches, those on the segments' own tables, or on the sequence's one table
     bool frame_tables;         // the JPEG coder's Huffman tables: the Annex K examples (false), or four tables built from symbol counts — this frame's own, or (sequence) the sequence's sums
-    bool sequence;             // one palette (PAL8) or one Huffman table set (JPEG) for all the frames a call hands to its writer: they wait in the sequence store until the last
+    bool sequence;             // one palette (PAL8), one Huffman table set (JPEG) or one ninth table (PNG) for all the frames a call hands to its writer: they wait in the sequence store until the last
                                // is rendered (palette_seq.h), and no slot converts or codes them — the sequence pass and the sequence's coder do
     size_t least;              // the smallest `total` its coder gives (coded_length_ok's lower bound)
     // a frame whose length its bytes decide: poppy_frame_bytes is its capacity, the writer is told stride 0, a pinned word holds its length
@@ -71,6 +82,7 @@ inline constexpr FormatTraits kFormats[] = {
     {POPPY_FRAME_PNG,         "PNG",  kRasterNone, kCoderPng,  0,                     false, false, poppy_hip::png::kFrameMinBytes},       // the file's fixed parts and one byte of deflate data
     {POPPY_FRAME_PNG_RUNS,    "PNG",  kRasterNone, kCoderPng,  poppy_hip::png::kRuns, false, false, poppy_hip::png::kFrameMinBytes},       // PNG with runs coded as matches, the same limits on its own capacity
     {POPPY_FRAME_PNG_OPT,     "PNG",  kRasterNone, kCoderPng,  poppy_hip::png::kRunsOwn, false, false, poppy_hip::png::kFrameMinBytes},    // PNG_RUNS with a ninth table per segment, built from its counts: PNG_RUNS' limits and capacity
+    {POPPY_FRAME_PNG_SEQ,     "PNG",  kRasterNone, kCoderPng,  poppy_hip::png::kRunsSeq, false, true,  poppy_hip::png::kFrameMinBytes},    // PNG_OPT's frames on one ninth table per sequence, built from the sequence's summed counts
 };
 constexpr const FormatTraits* format_traits(int fmt) {      // null for an unknown format
     for (const FormatTraits& t : kFormats) if (t.format == fmt) return &t;
@@ -101,7 +113,8 @@ inline size_t frame_bytes(const FormatTraits& t, int W, int H) {
 // every constant of include/poppy_hip.h has exactly one record, and the records hold what the code relies on
 constexpr bool formats_hold() {
     constexpr int all[] = {POPPY_FRAME_BGR, POPPY_FRAME_I420, POPPY_FRAME_PAL8, POPPY_FRAME_PAL8_SEQ, POPPY_FRAME_GIF, POPPY_FRAME_GIF_SEQ, POPPY_FRAME_JPEG, POPPY_FRAME_JPEG444,
-                           POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT, POPPY_FRAME_PNG_OPT, POPPY_FRAME_JPEG_SEQ, POPPY_FRAME_JPEG444_SEQ};
+                           POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_JPEG_OPT, POPPY_FRAME_JPEG444_OPT, POPPY_FRAME_PNG_OPT, POPPY_FRAME_JPEG_SEQ, POPPY_FRAME_JPEG444_SEQ,
+                           POPPY_FRAME_PNG_SEQ};
     if (sizeof all / sizeof *all != sizeof kFormats / sizeof *kFormats) return false;
     for (int fmt : all) {
         int n = 0;
@@ -111,13 +124,15 @@ constexpr bool formats_hold() {
     for (const FormatTraits& t : kFormats) {
         if (t.sequence && (t.slot_coder() != kCoderNone || t.slot_raster() != kRasterNone)) return false;      // a sequence format has no per-slot coder (and no raster step)
         const bool palette_seq = t.raster == kRasterPal8 && (t.coder == kCoderNone || t.coder == kCoderGif), table_seq = t.coder == kCoderJpeg && t.frame_tables;
-        if (t.sequence && !palette_seq && !table_seq) return false;      // ... and is PAL8 under one palette, bare or GIF-coded, or JPEG under one table set (palette_seq.cpp)
+        const bool png_seq = t.coder == kCoderPng && t.variant == poppy_hip::png::kRunsSeq;
+        if (t.sequence && !palette_seq && !table_seq && !png_seq) return false;      // ... and is PAL8 under one palette, bare or GIF-coded, JPEG under one table set, or PNG under one ninth table (palette_seq.cpp)
+        if (png_seq && !t.sequence) return false;                       // ... which only a sequence has
         if ((format_stride(t, 1) == 0) != t.coded()) return false;      // only a coded format reports stride 0
         if (t.coded() != (t.least > 0)) return false;                   // ... and it alone has a smallest `total`
         if (t.coder == kCoderGif && t.raster != kRasterPal8) return false;      // the coders read their raster form: GIF PAL8, JPEG the planes of its sampling, PNG the BGR frame
         if (t.coder == kCoderJpeg && t.raster != (t.sampling() == poppy_hip::jpeg::k444 ? kRasterI444 : kRasterI420)) return false;
         if (t.coder == kCoderPng && t.raster != kRasterNone) return false;
-        if (t.coder == kCoderPng && t.variant != poppy_hip::png::kLiterals && t.variant != poppy_hip::png::kRuns && t.variant != poppy_hip::png::kRunsOwn) return false;
+        if (t.coder == kCoderPng && t.variant != poppy_hip::png::kLiterals && t.variant != poppy_hip::png::kRuns && t.variant != poppy_hip::png::kRunsOwn && t.variant != poppy_hip::png::kRunsSeq) return false;
         if (t.coder == kCoderPng && t.least != poppy_hip::png::kFrameMinBytes) return false;      // every PNG variant's smallest frame is the fixed parts and a byte of data
         if (t.frame_tables && t.coder != kCoderJpeg) return false;      // per-frame tables are the JPEG coder's, and such a format's smallest frame is the OPT header's
         if (t.coder == kCoderJpeg && t.least != (t.frame_tables ? poppy_hip::jpeg::kOptFrameMinBytes : poppy_hip::jpeg::kFrameMinBytes)) return false;

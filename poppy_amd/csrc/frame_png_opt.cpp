@@ -13,8 +13,11 @@ namespace png_opt {
 namespace {
 
 constexpr png_runs::Codes kFixedCodes = png_runs::make_codes();
+using png_runs::for_each_token;
 
-// deflate's canonical codes by (length, symbol), bit-reversed: entry = reversed code << 4 | length, 0 for a symbol without a code
+}  // namespace
+
+// (frame_png.h says what these three are; POPPY_FRAME_PNG_SEQ's statement, frame_png_seq.cpp, runs them too)
 void canonical_codes(const uint8_t* lengths, int n, uint32_t* entries) {
     uint32_t code = 0;
     for (int i = 0; i < n; ++i) entries[i] = 0;
@@ -30,24 +33,6 @@ void canonical_codes(const uint8_t* lengths, int n, uint32_t* entries) {
     }
 }
 
-// a segment's tokens in order, as frame_png_runs.cpp's: f(symbol, extra_bits, extra)
-template <typename F>
-void for_each_token(const uint8_t* seg, size_t len, F&& f) {
-    for (size_t s = 0; s < len;) {
-        size_t e = s + 1;
-        while (e < len && seg[e] == seg[s]) ++e;
-        for (size_t p = s; p < e;) {
-            const int t = png_runs::token_at((int)(e - s), (int)(p - s));
-            if (t == 0) { f((int)seg[p], 0, 0u); ++p; }
-            else { const png_runs::Match m = png_runs::match_of(t); f(m.symbol, m.extra_bits, m.extra); p += (size_t)t; }
-        }
-        s = e;
-    }
-}
-
-struct Field { uint32_t value; int bits; };
-
-// the own header of a table (include/poppy_hip.h: Block header), BFINAL 0, as fields in order; returns its bits
 int own_header(const uint8_t* lengths, std::vector<Field>& out) {
     int n_lit = 257;
     for (int v = 257; v < kSymbols; ++v) if (lengths[v]) n_lit = v + 1;
@@ -94,16 +79,14 @@ int own_header(const uint8_t* lengths, std::vector<Field>& out) {
     return bits;
 }
 
-}  // namespace
-
-size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst) {
+// every segment's nine costs, its choice and its block; the ninth candidate is the segment's own table, or `shared`
+size_t encode_stream(const std::vector<uint8_t>& stream, int w, int h, const SharedTable* shared, uint8_t* dst) {
     using png::kAdlerMod; using png::kSegment; using png::kStreamByte;
-    const std::vector<uint8_t> stream = png::filter_frame(bgr, stride, w, h);
     const size_t n = stream.size();
     png::frame_head(dst, w, h);
     png::BitWriter bits{dst + kStreamByte};
     uint32_t adler_a = 1, adler_b = 0;
-    std::vector<Field> header;
+    std::vector<Field> own_fields;
     for (size_t first = 0; first < n; first += kSegment) {
         const size_t len = n - first < kSegment ? n - first : kSegment;
         const uint8_t* seg = stream.data() + first;
@@ -112,23 +95,25 @@ size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst)
         for_each_token(seg, len, [&](int symbol, int extra_bits, uint32_t) { ++counts[symbol]; if (symbol > kEob) beside += (unsigned long long)extra_bits + 1; });
         counts[kEob] = 1;
         uint8_t own_len[kSymbols];
-        poppy_png_optimal_lengths(counts, kSymbols, kLimit, own_len);
+        const uint8_t* ninth_len = shared ? shared->lengths : own_len;
+        if (!shared) poppy_png_optimal_lengths(counts, kSymbols, kLimit, own_len);
         unsigned long long cost[kTables + 1];
         for (int k = 0; k < kTables; ++k) {
             cost[k] = (unsigned long long)png_runs::kHeaderBits[k] + beside;
             for (int v = 0; v < kSymbols; ++v) cost[k] += (unsigned long long)counts[v] * png_runs::kLen[k][v];
         }
-        cost[kOwn] = (unsigned long long)own_header(own_len, header) + beside;
-        for (int v = 0; v < kSymbols; ++v) cost[kOwn] += (unsigned long long)counts[v] * own_len[v];
+        cost[kOwn] = (unsigned long long)(shared ? shared->header_bits : own_header(own_len, own_fields)) + beside;
+        for (int v = 0; v < kSymbols; ++v) cost[kOwn] += (unsigned long long)counts[v] * ninth_len[v];
         int choice = 0;
         for (int k = 1; k <= kTables; ++k) if (cost[k] < cost[choice]) choice = k;
         const bool last = first + len == n;
         uint32_t own_code[kSymbols];
-        const uint32_t* code = own_code;
+        const uint32_t* code = shared ? shared->code : own_code;
         if (choice == kOwn) {
-            canonical_codes(own_len, kSymbols, own_code);
-            header[0].value = last;                         // BFINAL in the last block
-            for (const Field& f : header) bits.put(f.value, f.bits);
+            if (!shared) canonical_codes(own_len, kSymbols, own_code);
+            const std::vector<Field>& header = shared ? shared->header : own_fields;
+            bits.put(last, header[0].bits);                 // BFINAL in the last block
+            for (size_t i = 1; i < header.size(); ++i) bits.put(header[i].value, header[i].bits);
         } else {
             code = kFixedCodes.e[choice];
             for (int i = 0; i < png_runs::kHeaderBits[choice]; i += 32) {
@@ -146,6 +131,8 @@ size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst)
     bits.pad();
     return png::frame_tail(dst, bits.at, adler_b << 16 | adler_a);
 }
+
+size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst) { return encode_stream(png::filter_frame(bgr, stride, w, h), w, h, nullptr, dst); }
 
 }  // namespace png_opt
 }  // namespace poppy_hip

@@ -12,21 +12,6 @@ namespace {
 
 constexpr Codes kCodes = make_codes();
 
-// a segment's tokens in order: f(symbol, extra_bits, extra) — a literal is its byte with no extra bits, a match its length symbol; every match is at distance 1
-template <typename F>
-void for_each_token(const uint8_t* seg, size_t len, F&& f) {
-    for (size_t s = 0; s < len;) {
-        size_t e = s + 1;
-        while (e < len && seg[e] == seg[s]) ++e;            // the maximal run [s, e): it ends with the segment at the latest
-        for (size_t p = s; p < e;) {
-            const int t = token_at((int)(e - s), (int)(p - s));      // (never negative: p moves from token to token)
-            if (t == 0) { f((int)seg[p], 0, 0u); ++p; }
-            else { const Match m = match_of(t); f(m.symbol, m.extra_bits, m.extra); p += (size_t)t; }
-        }
-        s = e;
-    }
-}
-
 }  // namespace
 
 size_t encode_bgr(const uint8_t* bgr, size_t stride, int w, int h, uint8_t* dst) {

@@ -99,6 +99,8 @@ static int enqueue_body(poppy_hip_ctx* c, FrameSlot& f, hipStream_t s, Timer* tm
     // JPEG_SEQ and JPEG444_SEQ: the pass is the raster kernel into the store and the counting kernel on it, 27 - 38 us at 1080p and nothing of it one workgroup's serial
     // work, so it stays on the chain's own stream as JPEG's coder does.  On the side stream it was measured at 2.8k chained frames/s against 5.0k here: `done` rides on the
     // pass, the low-priority queue runs it late, and the slot's reuse waits for it ("JPEG sequence-table hand-off").
+    // PNG_SEQ: the pass is PNG's filter into the frame's place in the store and the counting kernel on it, a workgroup per row and per segment and nothing serial, so
+    // it stays on the chain's own stream for JPEG_SEQ's reason; everything else of the coder runs behind the sequence's build, in the hand-over loop.
     // A scale above 1 or a size: the downscale (the resize) is the conversion's first dispatch wherever that runs, and a conversion of its own under BGR (the writer gets the slot's
     // scaled frame); the chain goes on from the full-size frame.
     const int fmt = frame_wants_format(c);

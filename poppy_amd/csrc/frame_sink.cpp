@@ -11,7 +11,7 @@
 //   POPPY_SINK_GIF_CODED   POPPY_SINK_GIF's file from POPPY_FRAME_GIF frames, whose image data arrives coded (frame_gif.cpp, kernels_frame_gif.hip): nothing is coded here
 //   POPPY_SINK_GIF_GLOBAL_CODED  POPPY_SINK_GIF_GLOBAL's file from coded frames (POPPY_FRAME_GIF_SEQ): the first frame's palette as the global table, local tables only where a palette differs
 //   POPPY_SINK_MJPEG  one RIFF AVI file, a `vids` / `MJPG` stream, from POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames and their OPT forms, whose bytes arrive coded (frame_jpeg.cpp, kernels_frame_jpeg.hip)
-//   POPPY_SINK_PNG   one PNG file per frame from POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS and POPPY_FRAME_PNG_OPT frames, whose bytes arrive coded (frame_png.cpp, frame_png_runs.cpp, frame_png_opt.cpp, kernels_frame_png.hip); the path as under PPM
+//   POPPY_SINK_PNG   one PNG file per frame from POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_PNG_OPT and POPPY_FRAME_PNG_SEQ frames, whose bytes arrive coded (frame_png.cpp, frame_png_runs.cpp, frame_png_opt.cpp, frame_png_seq.cpp, kernels_frame_png.hip); the path as under PPM
 // and the library's definition of the I420 hand-off format: poppy_bgr_to_i420 (kernels_frame_format.hip computes the same bytes on the device).
 #include "frame_limits.h"
 #include "gif_lzw.h"
@@ -220,7 +220,7 @@ std::string numbered_name(const poppy_sink* s) {
     return s->path + num + s->tail;
 }
 
-// a POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS or POPPY_FRAME_PNG_OPT frame (the file does not say which: `total` is held to the larger capacity; PNG_OPT's is PNG_RUNS'): its bytes 4 .. total as one file, once
+// a POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_PNG_OPT or POPPY_FRAME_PNG_SEQ frame (the file does not say which: `total` is held to the larger capacity; PNG_OPT's and PNG_SEQ's are PNG_RUNS'): its bytes 4 .. total as one file, once
 // the signature, IHDR's size and `total` are what the sink's size allows
 bool png_frame(poppy_sink* s, const uint8_t* frame) {
     using namespace poppy_hip::png;

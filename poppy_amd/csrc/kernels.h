@@ -313,6 +313,17 @@ void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_h
 // POPPY_FRAME_PNG_OPT's length build alone (k_png_lengths: the routine k_png_opt_cost runs per segment): `counts` is 286 words of device memory, zeros behind the
 // symbols in use; `lengths` receives 286 words
 void launch_png_length_build(const uint32_t* counts, int limit, uint32_t* lengths, hipStream_t s);
+// POPPY_FRAME_PNG_SEQ (png::kRunsSeq): one ninth table per sequence.  `place` is a frame's place in the sequence store, png_scratch_bytes(w, h, kRunsSeq) bytes laid
+// out as a PNG_RUNS scratch.  Per frame as it is rendered: launch_png_filter into the place, then launch_png_seq_count, which adds the frame's token counts into
+// `sums` (kPngSeqTableBytes: kPngSeqSumWords words, zero in front of the sequence's first frame, then the built png_opt::OwnTable; `done`, optional, rides on it).
+// Once per sequence launch_png_seq_table builds `table` from the sums and leaves them zero.  Per frame behind it: launch_png_seq_cost (the choice among nine),
+// launch_png_scan, launch_png_seq_pack, launch_png_crc, launch_png_finish, all on the place.
+constexpr size_t kPngSeqSumWords = 288;
+constexpr size_t kPngSeqTableBytes = kPngSeqSumWords * 4 + sizeof(png_opt::OwnTable);
+void launch_png_seq_count(const uint8_t* place, uint32_t* sums, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
+void launch_png_seq_table(uint32_t* sums, void* table, hipStream_t s);
+void launch_png_seq_cost(uint8_t* place, const void* table, int w, int h, hipStream_t s);
+void launch_png_seq_pack(const uint8_t* place, const void* table, uint8_t* frame, int w, int h, hipStream_t s);
 
 // The RANSAC fundamental-matrix filter's 2048 hypotheses (kernels_ransac.hip; the rule: include/poppy_hip.h, poppy_ransac_fundamental): the models of problem P
 // (normalised, 8 .. 65536 pairs) and their inlier counts among the pairs p1 <-> p2 into the host arrays counts (2048) and models (2048 x 9), two launches on s, which

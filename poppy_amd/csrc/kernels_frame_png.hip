@@ -37,13 +37,20 @@
 //   k_png_opt_cost  k_png_run_cost's run bounds and token walk, with the tokens counted into a 286-word LDS histogram (ds_add; end-of-block counts 1): the eight
 //                 fixed costs are the histogram's dot products with the nibble table.  Wave 0 then builds the segment's own table while the others leave
 //                 (build_code, a lane holds symbols lane + 64 j): the rule's merges in registers as k_jpeg_tables runs them — the two smallest packed keys
-//                 (count << 9 | 511 - symbol) by ds_min_u64 —, Annex K.3 on lane 0, a symbol's place by (depth, symbol) and then by (length, symbol) as the
+//                 (count << 9 | 511 - symbol) by a butterfly of shuffles —, Annex K.3 on lane 0, a symbol's place by (depth, symbol) and then by (length, symbol) as the
 //                 number of smaller keys, which give its length and its canonical code.  The header's length sequence: the lanes' break flags are five
 //                 ballots, the whole sequence's break mask in every lane, so every place finds its run's start and length by itself and decides what it sends
 //                 (png_opt::entry_at, as token_at does for bytes); the 19 counts, the same build at 7 bits, a prefix sum of the entries' bits, and the header
 //                 ORed into LDS.  Per segment: the choice 0..8 (8: the own table wins outright; ties go to the fixed tables) and, under 8, the own table.
 //   k_png_opt_pack  k_png_run_pack with the codes and the header read from the segment's own table when the choice is 8.  No code is above 15 bits and the block
 //                 is no longer than the best fixed table's, so the accumulator and the LDS image hold as they do there.
+// POPPY_FRAME_PNG_SEQ (poppy_bgr_frames_to_png_seq_frames in frame_png_seq.cpp is its host statement) is POPPY_FRAME_PNG_OPT with one ninth table per sequence.  A
+// frame's place in the sequence store is a POPPY_FRAME_PNG_RUNS scratch; the filter writes the stream there as the frame is rendered, and
+//   k_png_seq_count  k_png_opt_cost's histogram of a segment, its non-zero words added (global atomicAdd) to the sequence's 286 sums.
+//   k_png_seq_table  once per sequence, one wave: build_code at 15 bits on the sums and the own header, k_png_opt_cost's two routines, into one OwnTable record.
+//   k_png_seq_cost   per frame behind the build: k_png_run_cost's walk again with the record's lengths as a ninth column in LDS; the choice 0..8.
+//   k_png_seq_pack   k_png_opt_pack with every segment's `own` the sequence's record.
+// The scan, the CRC and the finish are the kernels above, on the frame's place.  No launch of these is capped or grid-strided: a workgroup per segment throughout.
 // Plain vector stores and atomics only.
 #include "kernels.h"
 #include <hip/hip_ext.h>
@@ -522,15 +529,21 @@ __global__ void __launch_bounds__(kThreads) k_png_pack(const uint8_t* __restrict
     }
 }
 
-__global__ void __launch_bounds__(kThreads) k_png_run_cost(const uint8_t* __restrict__ stream, uint4* __restrict__ seg_info, unsigned long long n) {
+namespace {
+
+// k_png_run_cost's body.  SEQ (k_png_seq_cost): a ninth candidate, the sequence's table, whose lengths (its entries' low nibbles) stand in LDS beside the eight
+// fixed tables' nibbles; its cost is its header, the tokens' codes, the same extra and distance bits and its end-of-block code.  Ties go to the fixed tables.
+template <bool SEQ>
+__device__ __forceinline__ void run_cost(const uint8_t* __restrict__ stream, uint4* __restrict__ seg_info, const png_opt::OwnTable* __restrict__ shared, unsigned long long n) {
     __shared__ uint32_t s_nib[png_runs::kSymbols];
+    __shared__ uint32_t s_ninth[SEQ ? png_runs::kSymbols : 1];
     __shared__ unsigned long long s_part[4];
     __shared__ uint32_t s_bound[8];
     const int t = threadIdx.x;
     const size_t first = (size_t)blockIdx.x * kSegment;
     const uint32_t len = (uint32_t)(n - first < kSegment ? n - first : kSegment);
-    for (int i = t; i < png_runs::kSymbols; i += kThreads) s_nib[i] = c_run_nibbles.e[i];
-    uint32_t cost[kTables] = {0, 0, 0, 0, 0, 0, 0, 0}, beside = 0, sum = 0, weighted = 0;
+    for (int i = t; i < png_runs::kSymbols; i += kThreads) { s_nib[i] = c_run_nibbles.e[i]; if (SEQ) s_ninth[i] = shared->code[i] & 15u; }
+    uint32_t cost[kTables] = {0, 0, 0, 0, 0, 0, 0, 0}, ninth = 0, beside = 0, sum = 0, weighted = 0;
     const uint32_t at = (uint32_t)t * kBytesPerThread;
     const bool active = at < len;
     RunBytes r{};
@@ -542,6 +555,7 @@ __global__ void __launch_bounds__(kThreads) k_png_run_cost(const uint8_t* __rest
             const uint32_t v = s_nib[symbol];
             #pragma unroll
             for (int k = 0; k < kTables; ++k) cost[k] += (v >> (4 * k)) & 15u;
+            if (SEQ) ninth += s_ninth[symbol];
             if (symbol > (uint32_t)kEob) beside += extra_bits + 1u;      // a match's extra bits and its distance code, whatever the table
         });
         #pragma unroll
@@ -554,14 +568,30 @@ __global__ void __launch_bounds__(kThreads) k_png_run_cost(const uint8_t* __rest
     #pragma unroll
     for (int k = 0; k < kTables; ++k) total[k] = group_sum(cost[k] + beside, s_part);
     const unsigned long long a = group_sum(sum, s_part), b = group_sum(weighted % kAdlerMod, s_part);
+    const unsigned long long ninth_all = SEQ ? group_sum(ninth + beside, s_part) : 0ull;
     if (t == 0) {
         int best = 0; unsigned long long least = 0;
         for (int k = 0; k < kTables; ++k) {
             const unsigned long long v = total[k] + c_run_block.over[k];
             if (k == 0 || v < least) { best = k; least = v; }
         }
+        if (SEQ) {
+            const unsigned long long v = ninth_all + shared->header_bits + s_ninth[kEob];
+            if (v < least) { best = png_opt::kOwn; least = v; }
+        }
         seg_info[blockIdx.x] = make_uint4((uint32_t)best, (uint32_t)least, (uint32_t)a, (uint32_t)(b % kAdlerMod));
     }
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(kThreads) k_png_run_cost(const uint8_t* __restrict__ stream, uint4* __restrict__ seg_info, unsigned long long n) {
+    run_cost<false>(stream, seg_info, nullptr, n);
+}
+
+// POPPY_FRAME_PNG_SEQ's choice, behind the sequence's build: k_png_run_cost with the sequence's table as the ninth candidate
+__global__ void __launch_bounds__(kThreads) k_png_seq_cost(const uint8_t* __restrict__ stream, uint4* __restrict__ seg_info, const png_opt::OwnTable* __restrict__ shared, unsigned long long n) {
+    run_cost<true>(stream, seg_info, shared, n);
 }
 
 namespace {
@@ -576,7 +606,6 @@ static_assert(kLanes * kPerLane >= png_opt::kSequenceMax + 1, "five per lane cov
 struct BuildLds {
     uint32_t of_depth[png_opt::kSymbols + 2];               // the symbols of each depth 0..286, then of each length
     uint32_t key[png_opt::kSymbols];                        // a symbol's (depth, then length) << 9 | symbol, ~0 without a code
-    unsigned long long pick[2];                             // the two smallest keys of the merge at hand
     uint32_t first_code[16], first_place[16];               // per length: its first canonical code, the place of its first symbol
 };
 constexpr unsigned long long kNoKey = ~0ull;
@@ -593,6 +622,18 @@ __device__ __forceinline__ void places_of(const uint32_t* key, int n, int lane, 
     }
 }
 
+// The two smallest of the wave's keys (unique, or kNoKey) in every lane, from every lane's own two smallest: a butterfly over the lanes in which the pairs (a1, a2)
+// and (b1, b2) merge into (min(a1, b1), min(max(a1, b1), min(a2, b2))).  Twelve 64-bit shuffles and no LDS word: written as atomicMin on an LDS word, the
+// compiler makes each of the two minima a scalar loop over the active lanes, and reading the word back is a flat load — 5 us per merge where this takes a tenth.
+__device__ __forceinline__ void wave_two_smallest(unsigned long long& m1, unsigned long long& m2) {
+    #pragma unroll
+    for (int d = 1; d < kLanes; d <<= 1) {
+        const unsigned long long o1 = __shfl_xor(m1, d, kLanes), o2 = __shfl_xor(m2, d, kLanes);
+        const unsigned long long lo = m1 < o1 ? m1 : o1, hi = m1 < o1 ? o1 : m1, rest = m2 < o2 ? m2 : o2;
+        m1 = lo; m2 = hi < rest ? hi : rest;
+    }
+}
+
 // poppy_png_optimal_lengths' rule (include/poppy_hip.h) in one wave, every lane of which is here: freq[j] is the count of symbol lane + 64 j (0 from n on, and at
 // least one is not), n <= 286, the used symbols no more than 2^limit.  entry[j]: the symbol's reversed canonical code << 4 | its length, 0 without a code.
 __device__ __forceinline__ void build_code(uint32_t (&freq)[kPerLane], int n, int limit, BuildLds& L, uint32_t (&entry)[kPerLane]) {
@@ -601,28 +642,18 @@ __device__ __forceinline__ void build_code(uint32_t (&freq)[kPerLane], int n, in
     #pragma unroll
     for (int j = 0; j < kPerLane; ++j) { tree[j] = lane + kLanes * j; depth[j] = 0; }
     for (int i = lane; i < png_opt::kSymbols + 2; i += kLanes) L.of_depth[i] = 0;
-    volatile unsigned long long* pick_read = L.pick;
-    unsigned long long* pick = L.pick;
     bool merged = false;
     unsigned long long m1, m2;
     for (;;) {
-        // the two smallest keys of the wave (keys are unique), as k_jpeg_tables takes them: the lane's own pair, then two rounds of ds_min_u64
+        // the two smallest keys of the wave (keys are unique): the lane's own pair, then the butterfly
         m1 = kNoKey; m2 = kNoKey;
         #pragma unroll
         for (int j = 0; j < kPerLane; ++j) {
             const unsigned long long key = freq[j] ? (unsigned long long)freq[j] << 9 | (unsigned long long)(511 - (lane + kLanes * j)) : kNoKey;
             if (key < m1) { m2 = m1; m1 = key; } else if (key < m2) m2 = key;
         }
-        if (lane == 0) { pick[0] = kNoKey; pick[1] = kNoKey; }
-        wave_sync();
-        if (m1 != kNoKey) atomicMin(&pick[0], m1);
-        wave_sync();
-        const unsigned long long g1 = pick_read[0];
-        { const unsigned long long mine = m1 == g1 ? m2 : m1; if (mine != kNoKey) atomicMin(&pick[1], mine); }
-        wave_sync();
-        m1 = g1; m2 = pick_read[1];
-        wave_sync();                                        // (both are read before lane 0 resets them)
-        if (m2 == kNoKey) break;                            // (wave-uniform)
+        wave_two_smallest(m1, m2);
+        if (m2 == kNoKey) break;                            // (wave-uniform: every lane holds the same pair)
         merged = true;
         const int c1 = 511 - (int)(m1 & 511), c2 = 511 - (int)(m2 & 511);
         const uint32_t f2 = (uint32_t)(m2 >> 9);
@@ -634,6 +665,7 @@ __device__ __forceinline__ void build_code(uint32_t (&freq)[kPerLane], int n, in
             if (idx == c2) freq[j] = 0;
         }
     }
+    wave_sync();                                            // (of_depth's zeros stand before other lanes count into them)
     int longest = 0;
     #pragma unroll
     for (int j = 0; j < kPerLane; ++j) {
@@ -714,68 +746,18 @@ __device__ __forceinline__ int sent_at(const unsigned long long (&brk)[kPerLane]
     return e.symbol < 0 ? -1 : e.symbol | e.extra_bits << 8 | (int)(e.extra << 16);
 }
 
-}  // namespace
+// What the own header of a table needs in LDS: the length sequence, the code-length symbols' counts and then their entries, the header's bits
+struct HeaderLds { uint32_t seq[kLanes * kPerLane], cl[32], header[png_opt::kOwnHeaderWords + 1]; };
 
-__global__ void __launch_bounds__(kThreads) k_png_opt_cost(const uint8_t* __restrict__ stream, uint4* __restrict__ seg_info, png_opt::OwnTable* __restrict__ own, unsigned long long n) {
-    __shared__ uint32_t s_count[kLanes * kPerLane];         // the tokens of each symbol; zeros behind 285
-    __shared__ uint32_t s_seq[kLanes * kPerLane];           // the own header's length sequence
-    __shared__ uint32_t s_cl[32];                           // the code-length symbols' counts, then their entries
-    __shared__ uint32_t s_header[png_opt::kOwnHeaderWords + 1];
-    __shared__ BuildLds s_build;
-    __shared__ unsigned long long s_part[4];
-    __shared__ uint32_t s_bound[8];
-    const int t = threadIdx.x;
-    const size_t first = (size_t)blockIdx.x * kSegment;
-    const uint32_t len = (uint32_t)(n - first < kSegment ? n - first : kSegment);
-    for (int i = t; i < kLanes * kPerLane; i += kThreads) s_count[i] = i == kEob ? 1u : 0u;
-    uint32_t beside = 0, sum = 0, weighted = 0;
-    const uint32_t at = (uint32_t)t * kBytesPerThread;
-    const bool active = at < len;
-    RunBytes r{};
-    if (active) r = load_run_bytes(stream + first, at, len);
-    uint32_t begin = 0, end = 0;
-    group_run_bounds(active ? last_break(r, at) : 0u, active ? first_break(r, at) : 0xFFFFFFFFu, s_bound, &begin, &end);      // (its barrier stands behind s_count's stores too)
-    if (active) {
-        for_each_token(r, at, len, begin, end, [&](uint32_t symbol, uint32_t extra_bits, uint32_t) {
-            atomicAdd(&s_count[symbol], 1u);
-            if (symbol > (uint32_t)kEob) beside += extra_bits + 1u;      // a match's extra bits and its distance code, whatever the table
-        });
-        #pragma unroll
-        for (int i = 0; i < kBytesPerThread; ++i) {
-            const uint32_t d = i < r.valid ? (r.word[i >> 2] >> (8 * (i & 3))) & 255u : 0u;
-            sum += d; weighted += (len - (at + i)) * d;      // (at most 32 * 8192 * 255: no overflow)
-        }
-    }
-    __syncthreads();
-    uint32_t cost[kTables] = {0, 0, 0, 0, 0, 0, 0, 0};      // the fixed tables: the histogram's dot products with their lengths (end-of-block is in it)
-    for (int i = t; i < png_runs::kSymbols; i += kThreads) {
-        const uint32_t c = s_count[i], v = c_run_nibbles.e[i];
-        #pragma unroll
-        for (int k = 0; k < kTables; ++k) cost[k] += c * ((v >> (4 * k)) & 15u);
-    }
-    unsigned long long total[kTables];
-    #pragma unroll
-    for (int k = 0; k < kTables; ++k) total[k] = group_sum(cost[k] + beside, s_part);
-    const unsigned long long a = group_sum(sum, s_part), b = group_sum(weighted % kAdlerMod, s_part), beside_all = group_sum(beside, s_part);
-    if (t >= kLanes) return;                                // wave 0 builds the own table: no workgroup barrier from here on
-    int best = 0; unsigned long long least = 0;
-    for (int k = 0; k < kTables; ++k) {
-        const unsigned long long v = total[k] + c_run_block.header[k];
-        if (k == 0 || v < least) { best = k; least = v; }
-    }
-    const int lane = t;
-    uint32_t freq[kPerLane], count[kPerLane], entry[kPerLane];
-    #pragma unroll
-    for (int j = 0; j < kPerLane; ++j) count[j] = freq[j] = s_count[lane + kLanes * j];
-    build_code(freq, png_opt::kSymbols, png_opt::kLimit, s_build, entry);
-    unsigned long long own_bits = 0;
+// The own header of a table (include/poppy_hip.h: Block header) in one wave, every lane of which is here: entry[j] is build_code's of symbol lane + 64 j.  The
+// lanes' break flags are five ballots, so every place of the length sequence finds its run by itself (sent_at); the 19 counts, the same build at 7 bits, a prefix
+// sum of the entries' bits, and the header ORed into H.header, BFINAL 0, zeros behind it.  Returns the header's bits.
+__device__ __forceinline__ uint32_t own_header(const uint32_t (&entry)[kPerLane], HeaderLds& H, BuildLds& L) {
+    const int lane = threadIdx.x & (kLanes - 1);
+    uint32_t* const s_seq = H.seq; uint32_t* const s_cl = H.cl; uint32_t* const s_header = H.header;
     int n_lit = 257;
     #pragma unroll
-    for (int j = 0; j < kPerLane; ++j) {
-        own_bits += (unsigned long long)count[j] * (entry[j] & 15u);
-        if (entry[j]) n_lit = max(n_lit, lane + kLanes * j + 1);
-    }
-    own_bits = wave_sum(own_bits);
+    for (int j = 0; j < kPerLane; ++j) if (entry[j]) n_lit = max(n_lit, lane + kLanes * j + 1);
     #pragma unroll
     for (int d = 1; d < kLanes; d <<= 1) n_lit = max(n_lit, __shfl_xor(n_lit, d, kLanes));
     // the length sequence: the lit/len lengths, then the distance code's 1; place n_seq carries the mark that ends the last run
@@ -799,7 +781,7 @@ __global__ void __launch_bounds__(kThreads) k_png_opt_cost(const uint8_t* __rest
     }
     wave_sync();
     uint32_t cl_freq[kPerLane] = {lane < png_opt::kClSymbols ? s_cl[lane] : 0u, 0u, 0u, 0u, 0u}, cl_entry[kPerLane];
-    build_code(cl_freq, png_opt::kClSymbols, png_opt::kClLimit, s_build, cl_entry);
+    build_code(cl_freq, png_opt::kClSymbols, png_opt::kClLimit, L, cl_entry);
     if (lane < png_opt::kClSymbols) s_cl[lane] = cl_entry[0];
     wave_sync();
     // HCLEN: the code-length code's lengths in RFC 1951's order, trailing zeros trimmed, at least 4
@@ -819,15 +801,121 @@ __global__ void __launch_bounds__(kThreads) k_png_opt_cost(const uint8_t* __rest
         at_bit += __shfl(incl, kLanes - 1, kLanes);
     }
     wave_sync();
+    return at_bit;
+}
+
+// A segment of `len` bytes by its workgroup: its tokens counted into the histogram s_count (kLanes * kPerLane words; end-of-block counts 1, zeros behind 285), with a
+// barrier behind the last ds_add.  The thread's own share of what no table changes comes back: the extra and distance bits of the matches that begin in its
+// bytes, and its bytes' sums for the Adler pair.  (s_bound: group_run_bounds' 8 words)
+struct SegmentSums { uint32_t beside, sum, weighted; };
+__device__ __forceinline__ SegmentSums count_tokens(const uint8_t* __restrict__ seg, uint32_t len, uint32_t* s_count, uint32_t* s_bound) {
+    const int t = threadIdx.x;
+    for (int i = t; i < kLanes * kPerLane; i += kThreads) s_count[i] = i == kEob ? 1u : 0u;
+    uint32_t beside = 0, sum = 0, weighted = 0;
+    const uint32_t at = (uint32_t)t * kBytesPerThread;
+    const bool active = at < len;
+    RunBytes r{};
+    if (active) r = load_run_bytes(seg, at, len);
+    uint32_t begin = 0, end = 0;
+    group_run_bounds(active ? last_break(r, at) : 0u, active ? first_break(r, at) : 0xFFFFFFFFu, s_bound, &begin, &end);      // (its barrier stands behind s_count's stores too)
+    if (active) {
+        for_each_token(r, at, len, begin, end, [&](uint32_t symbol, uint32_t extra_bits, uint32_t) {
+            atomicAdd(&s_count[symbol], 1u);
+            if (symbol > (uint32_t)kEob) beside += extra_bits + 1u;      // a match's extra bits and its distance code, whatever the table
+        });
+        #pragma unroll
+        for (int i = 0; i < kBytesPerThread; ++i) {
+            const uint32_t d = i < r.valid ? (r.word[i >> 2] >> (8 * (i & 3))) & 255u : 0u;
+            sum += d; weighted += (len - (at + i)) * d;      // (at most 32 * 8192 * 255: no overflow)
+        }
+    }
+    __syncthreads();
+    return SegmentSums{beside, sum, weighted};
+}
+
+// a built table into its record: the symbols' entries, the header's bits and their number (one wave)
+__device__ __forceinline__ void store_table(png_opt::OwnTable* __restrict__ own, const uint32_t (&entry)[kPerLane], uint32_t at_bit, const HeaderLds& H) {
+    const int lane = threadIdx.x & (kLanes - 1);
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) { const int idx = lane + kLanes * j; if (idx < png_opt::kSymbols) own->code[idx] = entry[j]; }
+    if (lane == 0) own->header_bits = at_bit;
+    for (int i = lane; i < png_opt::kOwnHeaderWords + 1; i += kLanes) own->header[i] = H.header[i];
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(kThreads) k_png_opt_cost(const uint8_t* __restrict__ stream, uint4* __restrict__ seg_info, png_opt::OwnTable* __restrict__ own, unsigned long long n) {
+    __shared__ uint32_t s_count[kLanes * kPerLane];         // the tokens of each symbol; zeros behind 285
+    __shared__ HeaderLds s_head;                            // the own header in the making
+    __shared__ BuildLds s_build;
+    __shared__ unsigned long long s_part[4];
+    __shared__ uint32_t s_bound[8];
+    const int t = threadIdx.x;
+    const size_t first = (size_t)blockIdx.x * kSegment;
+    const uint32_t len = (uint32_t)(n - first < kSegment ? n - first : kSegment);
+    const SegmentSums mine = count_tokens(stream + first, len, s_count, s_bound);
+    const uint32_t beside = mine.beside, sum = mine.sum, weighted = mine.weighted;
+    uint32_t cost[kTables] = {0, 0, 0, 0, 0, 0, 0, 0};      // the fixed tables: the histogram's dot products with their lengths (end-of-block is in it)
+    for (int i = t; i < png_runs::kSymbols; i += kThreads) {
+        const uint32_t c = s_count[i], v = c_run_nibbles.e[i];
+        #pragma unroll
+        for (int k = 0; k < kTables; ++k) cost[k] += c * ((v >> (4 * k)) & 15u);
+    }
+    unsigned long long total[kTables];
+    #pragma unroll
+    for (int k = 0; k < kTables; ++k) total[k] = group_sum(cost[k] + beside, s_part);
+    const unsigned long long a = group_sum(sum, s_part), b = group_sum(weighted % kAdlerMod, s_part), beside_all = group_sum(beside, s_part);
+    if (t >= kLanes) return;                                // wave 0 builds the own table: no workgroup barrier from here on
+    int best = 0; unsigned long long least = 0;
+    for (int k = 0; k < kTables; ++k) {
+        const unsigned long long v = total[k] + c_run_block.header[k];
+        if (k == 0 || v < least) { best = k; least = v; }
+    }
+    const int lane = t;
+    uint32_t freq[kPerLane], count[kPerLane], entry[kPerLane];
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) count[j] = freq[j] = s_count[lane + kLanes * j];
+    build_code(freq, png_opt::kSymbols, png_opt::kLimit, s_build, entry);
+    unsigned long long own_bits = 0;
+    #pragma unroll
+    for (int j = 0; j < kPerLane; ++j) own_bits += (unsigned long long)count[j] * (entry[j] & 15u);
+    own_bits = wave_sum(own_bits);
+    const uint32_t at_bit = own_header(entry, s_head, s_build);
     const unsigned long long own_cost = (unsigned long long)at_bit + own_bits + beside_all;
     const bool owned = own_cost < least;                    // (ties go to the lowest index: a fixed table)
     if (lane == 0) seg_info[blockIdx.x] = make_uint4(owned ? (uint32_t)png_opt::kOwn : (uint32_t)best, (uint32_t)(owned ? own_cost : least), (uint32_t)a, (uint32_t)(b % kAdlerMod));
     if (!owned) return;
-    own += blockIdx.x;
+    store_table(own + blockIdx.x, entry, at_bit, s_head);
+}
+
+// POPPY_FRAME_PNG_SEQ's counting pass, a workgroup per segment of a frame that has just been filtered into its place in the sequence store: k_png_opt_cost's
+// histogram, then its non-zero words added to the sequence's 286 sums (end-of-block: 1 per segment).  No sum passes 2^32 - 1: png_seq_fits.
+__global__ void __launch_bounds__(kThreads) k_png_seq_count(const uint8_t* __restrict__ stream, uint32_t* __restrict__ sums, unsigned long long n) {
+    __shared__ uint32_t s_count[kLanes * kPerLane];
+    __shared__ uint32_t s_bound[8];
+    const size_t first = (size_t)blockIdx.x * kSegment;
+    const uint32_t len = (uint32_t)(n - first < kSegment ? n - first : kSegment);
+    (void)count_tokens(stream + first, len, s_count, s_bound);
+    for (int i = threadIdx.x; i < png_runs::kSymbols; i += kThreads) if (s_count[i]) atomicAdd(&sums[i], s_count[i]);
+}
+
+// POPPY_FRAME_PNG_SEQ's one build per sequence, one wave: the sums (zero again behind it) -> the sequence's table, as k_png_opt_cost's wave 0 builds a segment's:
+// build_code at 15 bits, then the own header.  The counts here are a whole sequence's, up to 2^32 - 1 in all: build_code's keys are count << 9 | 511 - symbol in
+// 64 bits, a merged count is a sum of counts and so below 2^32 too, the depths are counted per symbol (286 at the most), and nothing here multiplies a count.
+__global__ void __launch_bounds__(kLanes) k_png_seq_table(uint32_t* __restrict__ sums, png_opt::OwnTable* __restrict__ table) {
+    __shared__ HeaderLds s_head;
+    __shared__ BuildLds s_build;
+    const int lane = threadIdx.x;
+    uint32_t freq[kPerLane], entry[kPerLane];
     #pragma unroll
-    for (int j = 0; j < kPerLane; ++j) { const int idx = lane + kLanes * j; if (idx < png_opt::kSymbols) own->code[idx] = entry[j]; }
-    if (lane == 0) own->header_bits = at_bit;
-    for (int i = lane; i < png_opt::kOwnHeaderWords + 1; i += kLanes) own->header[i] = s_header[i];
+    for (int j = 0; j < kPerLane; ++j) {
+        const int idx = lane + kLanes * j;
+        freq[j] = idx < png_opt::kSymbols ? sums[idx] : 0u;
+        if (idx < png_opt::kSymbols) sums[idx] = 0;
+    }
+    build_code(freq, png_opt::kSymbols, png_opt::kLimit, s_build, entry);
+    const uint32_t at_bit = own_header(entry, s_head, s_build);
+    store_table(table, entry, at_bit, s_head);
 }
 
 // the length build alone, one wave: counts[286] (zeros behind the symbols in use) -> lengths[286]
@@ -845,9 +933,10 @@ __global__ void __launch_bounds__(64) k_png_lengths(const uint32_t* __restrict__
 namespace {
 
 // k_png_run_pack's body.  OWN (k_png_opt_pack): a segment whose choice is png_opt::kOwn takes its codes, its header and the header's length from `own`, its table
-// in the scratch; every other segment, and every segment without OWN, from table 0..7's constants.
+// in the scratch (own_stride 1), or from the one table of its sequence (k_png_seq_pack: own_stride 0); every other segment, and every segment without OWN, from
+// table 0..7's constants.
 template <bool OWN>
-__device__ __forceinline__ void run_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const png_opt::OwnTable* __restrict__ own,
+__device__ __forceinline__ void run_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const png_opt::OwnTable* __restrict__ own, uint32_t own_stride,
                                          const unsigned long long* __restrict__ seg_start, const uint32_t* __restrict__ meta, uint32_t* __restrict__ frame32, uint32_t n_seg,
                                          unsigned long long n, unsigned long long capacity) {
     __shared__ uint32_t s_image[kRunImageWords];
@@ -859,7 +948,7 @@ __device__ __forceinline__ void run_pack(const uint8_t* __restrict__ stream, con
     const uint4 info = seg_info[seg];
     const bool owned = OWN && info.x == (uint32_t)png_opt::kOwn;
     const uint32_t table = info.x & (kTables - 1), bits = info.y;
-    if (OWN) own += seg;
+    if (OWN) own += (size_t)seg * own_stride;
     if (!meta[1] || bits > png_runs::kSegmentBitsMax) return;      // (never: the scan found the frame inside its capacity, and table 7 bounds every block)
     const unsigned long long start = seg_start[seg];
     const size_t first = (size_t)seg * kSegment;
@@ -918,13 +1007,20 @@ __device__ __forceinline__ void run_pack(const uint8_t* __restrict__ stream, con
 __global__ void __launch_bounds__(kThreads) k_png_run_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const unsigned long long* __restrict__ seg_start,
                                                            const uint32_t* __restrict__ meta, uint32_t* __restrict__ frame32, uint32_t n_seg, unsigned long long n,
                                                            unsigned long long capacity) {
-    run_pack<false>(stream, seg_info, nullptr, seg_start, meta, frame32, n_seg, n, capacity);
+    run_pack<false>(stream, seg_info, nullptr, 0, seg_start, meta, frame32, n_seg, n, capacity);
 }
 
 __global__ void __launch_bounds__(kThreads) k_png_opt_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const png_opt::OwnTable* __restrict__ own,
                                                            const unsigned long long* __restrict__ seg_start, const uint32_t* __restrict__ meta, uint32_t* __restrict__ frame32,
                                                            uint32_t n_seg, unsigned long long n, unsigned long long capacity) {
-    run_pack<true>(stream, seg_info, own, seg_start, meta, frame32, n_seg, n, capacity);
+    run_pack<true>(stream, seg_info, own, 1, seg_start, meta, frame32, n_seg, n, capacity);
+}
+
+// POPPY_FRAME_PNG_SEQ's pack: k_png_opt_pack reading the sequence's one table wherever the choice is 8
+__global__ void __launch_bounds__(kThreads) k_png_seq_pack(const uint8_t* __restrict__ stream, const uint4* __restrict__ seg_info, const png_opt::OwnTable* __restrict__ shared,
+                                                           const unsigned long long* __restrict__ seg_start, const uint32_t* __restrict__ meta, uint32_t* __restrict__ frame32,
+                                                           uint32_t n_seg, unsigned long long n, unsigned long long capacity) {
+    run_pack<true>(stream, seg_info, shared, 0, seg_start, meta, frame32, n_seg, n, capacity);
 }
 
 __global__ void __launch_bounds__(kThreads) k_png_crc(const uint8_t* __restrict__ frame, const uint32_t* __restrict__ meta, uint32_t* __restrict__ pieces) {
@@ -1017,6 +1113,24 @@ void launch_png_crc(uint8_t* scratch, const uint8_t* frame, int w, int h, int va
 void launch_png_finish(const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, int variant, hipStream_t s, hipEvent_t done) {
     const Scratch m = scratch_of(const_cast<uint8_t*>(scratch), w, h, variant);
     hipExtLaunchKernelGGL(k_png_finish, dim3(1), dim3(kThreads), 0, s, nullptr, done, 0, (const uint32_t*)m.meta, (const uint32_t*)m.crc, frame, total_host);
+}
+
+void launch_png_seq_count(const uint8_t* place, uint32_t* sums, int w, int h, hipStream_t s, hipEvent_t done) {
+    const Scratch m = scratch_of(const_cast<uint8_t*>(place), w, h, kRunsSeq);
+    hipExtLaunchKernelGGL(k_png_seq_count, dim3((unsigned)segment_count((size_t)w, (size_t)h)), dim3(kThreads), 0, s, nullptr, done, 0, (const uint8_t*)m.stream, sums, stream_bytes((size_t)w, (size_t)h));
+}
+void launch_png_seq_table(uint32_t* sums, void* table, hipStream_t s) {
+    hipLaunchKernelGGL(k_png_seq_table, dim3(1), dim3(kLanes), 0, s, sums, (png_opt::OwnTable*)table);
+}
+void launch_png_seq_cost(uint8_t* place, const void* table, int w, int h, hipStream_t s) {
+    const Scratch m = scratch_of(place, w, h, kRunsSeq);
+    hipLaunchKernelGGL(k_png_seq_cost, dim3((unsigned)segment_count((size_t)w, (size_t)h)), dim3(kThreads), 0, s, (const uint8_t*)m.stream, m.seg, (const png_opt::OwnTable*)table, stream_bytes((size_t)w, (size_t)h));
+}
+void launch_png_seq_pack(const uint8_t* place, const void* table, uint8_t* frame, int w, int h, hipStream_t s) {
+    const Scratch m = scratch_of(const_cast<uint8_t*>(place), w, h, kRunsSeq);
+    const uint32_t n_seg = (uint32_t)segment_count((size_t)w, (size_t)h);
+    hipLaunchKernelGGL(k_png_seq_pack, dim3(n_seg), dim3(kThreads), 0, s, (const uint8_t*)m.stream, (const uint4*)m.seg, (const png_opt::OwnTable*)table, (const unsigned long long*)m.start,
+                       (const uint32_t*)m.meta, (uint32_t*)frame, n_seg, stream_bytes((size_t)w, (size_t)h), capacity_of(w, h, kRunsSeq));
 }
 
 void launch_png_length_build(const uint32_t* counts, int limit, uint32_t* lengths, hipStream_t s) {

@@ -1,14 +1,21 @@
-// palette_seq.cpp — the sequence formats (palette_seq.h: POPPY_FRAME_PAL8_SEQ / GIF_SEQ on one palette, POPPY_FRAME_JPEG_SEQ / JPEG444_SEQ on one table set):
+// palette_seq.cpp — the sequence formats (palette_seq.h: POPPY_FRAME_PAL8_SEQ / GIF_SEQ on one palette, POPPY_FRAME_JPEG_SEQ / JPEG444_SEQ on one table set,
+// POPPY_FRAME_PNG_SEQ on one ninth table):
 // collecting a call's frames in the store, the palette or the tables, the two hand-over loops through the writer ring, and the call-scoped sequences of
-// poppy_hip_bgr_frames_to_gif_frames and poppy_hip_bgr_frames_to_jpeg_seq_frames.
+// poppy_hip_bgr_frames_to_gif_frames, poppy_hip_bgr_frames_to_jpeg_seq_frames and poppy_hip_bgr_frames_to_png_seq_frames.
 #include "context.h"
 
 // the context's sequence under a JPEG format: its record's sampling, its counts and its built tables (PaletteSeq::jpeg)
 static bool seq_is_jpeg(const poppy_hip_ctx* c) { return format_traits(c->frame_format)->coder == kCoderJpeg; }
 static uint32_t* seq_jpeg_counts(const PaletteSeq& q) { return (uint32_t*)q.jpeg; }
 static const void* seq_jpeg_built(const PaletteSeq& q) { return q.jpeg + sizeof(jpeg::SymbolCounts); }
-// what waits in the store: the planes that a JPEG sequence's coder reads, the BGR frame under a palette sequence
-static FrameRaster seq_held_raster(const FormatTraits& t) { return t.coder == kCoderJpeg ? t.raster : kRasterNone; }
+// ... under PNG: its sums and its built table (PaletteSeq::png)
+static bool seq_is_png(const poppy_hip_ctx* c) { return format_traits(c->frame_format)->coder == kCoderPng; }
+static uint32_t* seq_png_sums(const PaletteSeq& q) { return (uint32_t*)q.png; }
+static void* seq_png_table(const PaletteSeq& q) { return q.png + kPngSeqSumWords * 4; }
+// what waits in the store: the planes that a JPEG sequence's coder reads, the filtered stream in its coder's scratch under PNG, the BGR frame under a palette sequence
+static size_t seq_held_bytes(const FormatTraits& t, int W, int H) {
+    return t.coder == kCoderPng ? png_scratch_bytes(W, H, t.variant) : raster_bytes(t.coder == kCoderJpeg ? t.raster : kRasterNone, (size_t)W, (size_t)H);
+}
 
 int seq_begin(poppy_hip_ctx* c, int n) {
     const WriterGeom g = writer_geom(c);
@@ -17,8 +24,8 @@ int seq_begin(poppy_hip_ctx* c, int n) {
     if (q.open) { int rc = seq_abort(c); if (rc) return rc; }      // (a sequence that a device error left open: its frames and sums are dropped, not mixed into this one)
     if (const char* why = sequence_refuses(c->frame_format, n, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);      // (a sequence format: writer_wants_sequence)
     { int rc = alloc_slot_format(c); if (rc) return rc; }
-    const size_t stride = (raster_bytes(seq_held_raster(*format_traits(c->frame_format)), (size_t)W, (size_t)H) + 15) & ~(size_t)15, need = stride * (size_t)n;      // (every frame's place begins on a 16-byte boundary)
-    if (q.store.reserve(need) != hipSuccess) { (void)hipGetLastError(); return fail(c, POPPY_E_DEVICE, "no device memory for the sequence's frames (3 * width * height bytes each, half of that as I420 planes)"); }
+    const size_t stride = (seq_held_bytes(*format_traits(c->frame_format), W, H) + 15) & ~(size_t)15, need = stride * (size_t)n;      // (every frame's place begins on a 16-byte boundary)
+    if (q.store.reserve(need) != hipSuccess) { (void)hipGetLastError(); return fail(c, POPPY_E_DEVICE, "no device memory for the sequence's frames (3 * width * height bytes each, half of that as I420 planes, height more as PNG's filtered stream)"); }
     q.stride = stride; q.n = n; q.count = 0; q.open = true;
     return POPPY_OK;
 }
@@ -32,11 +39,16 @@ int seq_pass(poppy_hip_ctx* c, const uint8_t* d_bgr, uint8_t* dst, hipStream_t s
         (t.raster == kRasterI444 ? launch_bgr_to_i444 : launch_bgr_to_i420)(d_bgr, dst, g.w, g.h, s, nullptr);
         if (c->timing == 1) tm.mark("frame_format");
         launch_jpeg_count_into(dst, c->jpeg_tables, seq_jpeg_counts(c->seq), g.w, g.h, t.sampling(), s, done);
+    } else if (t.coder == kCoderPng) {                             // the filtered stream straight into the frame's place, then its tokens into the sequence's sums
+        Timer tm(c, s);
+        launch_png_filter(d_bgr, dst, g.w, g.h, t.variant, s);
+        if (c->timing == 1) tm.mark("png_filter");
+        launch_png_seq_count(dst, seq_png_sums(c->seq), g.w, g.h, s, done);
     } else launch_pal8_seq_pass(d_bgr, dst, c->seq.tables, g.w, g.h, s, done);
     HIPCHK(c, hipGetLastError());
     return POPPY_OK;
 }
-const char* seq_pass_mark(const poppy_hip_ctx* c) { return seq_is_jpeg(c) ? "jpeg_count" : "pal8_seq_hist"; }
+const char* seq_pass_mark(const poppy_hip_ctx* c) { return seq_is_jpeg(c) ? "jpeg_count" : seq_is_png(c) ? "png_seq_count" : "pal8_seq_hist"; }
 uint8_t* seq_next_place(poppy_hip_ctx* c) { return c->seq.count < c->seq.n ? c->seq.store.p + (size_t)c->seq.count++ * c->seq.stride : nullptr; }
 
 int seq_add_image(poppy_hip_ctx* c, const uint8_t* d_bgr) {
@@ -60,6 +72,7 @@ int seq_abort(poppy_hip_ctx* c) {
     int rc = drain_frames(c);
     if (c->seq.tables && hipMemset(c->seq.tables, 0, kPal8SeqTableOffset) != hipSuccess && rc == POPPY_OK) rc = fail(c, POPPY_E_DEVICE, "could not clear the sequence tables");
     if (c->seq.jpeg && hipMemset(c->seq.jpeg, 0, sizeof(jpeg::SymbolCounts)) != hipSuccess && rc == POPPY_OK) rc = fail(c, POPPY_E_DEVICE, "could not clear the sequence's symbol counts");
+    if (c->seq.png && hipMemset(c->seq.png, 0, kPngSeqSumWords * 4) != hipSuccess && rc == POPPY_OK) rc = fail(c, POPPY_E_DEVICE, "could not clear the sequence's token counts");
     return rc;
 }
 void seq_abort_keep_error(poppy_hip_ctx* c) { const std::string why = c->err; (void)seq_abort(c); c->err = why; }
@@ -117,6 +130,21 @@ static void enqueue_seq_jpeg_coding(const uint8_t* planes, const void* tables, c
     if (tm) tm->mark("jpeg_pack");
 }
 
+// ... and of one frame of a PNG sequence: the choice among nine, then PNG_RUNS' scan, the pack on the sequence's table, the CRC and the finish, all on the frame's place
+// in the store, which is its coder's scratch and holds its filtered stream
+static void enqueue_seq_png_coding(uint8_t* place, const void* table, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, Timer* tm) {
+    launch_png_seq_cost(place, table, W, H, s);
+    if (tm) tm->mark("png_seq_cost");
+    launch_png_scan(place, frame, W, H, png::kRunsSeq, s);
+    if (tm) tm->mark("png_scan");
+    launch_png_seq_pack(place, table, frame, W, H, s);
+    if (tm) tm->mark("png_seq_pack");
+    launch_png_crc(place, frame, W, H, png::kRunsSeq, s);
+    if (tm) tm->mark("png_crc");
+    launch_png_finish(place, frame, (uint32_t*)total_dev, W, H, png::kRunsSeq, s);
+    if (tm) tm->mark("png_finish");
+}
+
 // Every frame of a coded sequence: coded from its place in the store (GIF_SEQ: k_gif_lzw_bgr, no index plane; the JPEG sequences: k_jpeg_code and k_jpeg_pack in their
 // OPT forms on the sequence's tables) into one of R device buffers, each followed by the coder's scratch, on the ring buffer's own stream; the coder's last kernel
 // stores the frame's length into the ring buffer's pinned word.  The host waits for that stream, reads the word, bounds-checks it
@@ -129,7 +157,7 @@ static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* use
     const bool marks = c->timing == 1;
     const FormatTraits& t = *format_traits(c->frame_format);
     const size_t capacity = poppy_frame_bytes(t.format, W, H), frame_part = (capacity + 16 + 255) & ~(size_t)255;
-    const size_t each = frame_part + ((coding_scratch_bytes(t, W, H) + 255) & ~(size_t)255);
+    const size_t each = frame_part + (t.coder == kCoderPng ? 0 : (coding_scratch_bytes(t, W, H) + 255) & ~(size_t)255);      // (a PNG frame's scratch is its place in the store)
     WriterRing ring;
     { int rc = ring.open(c, capacity, false); if (rc) return rc; }
     HIPCHK(c, q.coded.reserve(each * ring.R));
@@ -163,7 +191,8 @@ static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* use
             if (marks) tm.mark("gif_pack");
         } else
 #endif
-        if (t.coder == kCoderJpeg) enqueue_seq_jpeg_coding(q.store.p + (size_t)k * q.stride, c->jpeg_tables, seq_jpeg_built(q), d_frame(k) + frame_part, d_frame(k), q.coded_total_dev + 64 * (size_t)(k % ring.R), W, H, t.sampling(), s, marks ? &tm : nullptr);
+        if (t.coder == kCoderPng) enqueue_seq_png_coding(q.store.p + (size_t)k * q.stride, seq_png_table(q), d_frame(k), q.coded_total_dev + 64 * (size_t)(k % ring.R), W, H, s, marks ? &tm : nullptr);
+        else if (t.coder == kCoderJpeg) enqueue_seq_jpeg_coding(q.store.p + (size_t)k * q.stride, c->jpeg_tables, seq_jpeg_built(q), d_frame(k) + frame_part, d_frame(k), q.coded_total_dev + 64 * (size_t)(k % ring.R), W, H, t.sampling(), s, marks ? &tm : nullptr);
         else enqueue_seq_gif_coding(q.store.p + (size_t)k * q.stride, q.tables, d_frame(k) + frame_part, d_frame(k), q.coded_total_dev + 64 * (size_t)(k % ring.R), W, H, s, marks ? &tm : nullptr);
         HIPCHK(c, hipGetLastError());
         ++coded;
@@ -205,9 +234,10 @@ static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
     {
         Timer tm(c, c->stream);
         if (c->timing == 1) tm.mark(nullptr);
-        if (seq_is_jpeg(c)) launch_jpeg_table_build(seq_jpeg_counts(q), const_cast<void*>(seq_jpeg_built(q)), c->stream);      // once, on the sums: the counts are zero behind it
+        if (seq_is_png(c)) launch_png_seq_table(seq_png_sums(q), seq_png_table(q), c->stream);      // once, on the sums: they are zero behind it
+        else if (seq_is_jpeg(c)) launch_jpeg_table_build(seq_jpeg_counts(q), const_cast<void*>(seq_jpeg_built(q)), c->stream);      // once, on the sums: the counts are zero behind it
         else launch_pal8_seq_build(q.tables, c->stream);
-        if (c->timing == 1) tm.mark(seq_is_jpeg(c) ? "jpeg_tables" : "pal8_seq_build");
+        if (c->timing == 1) tm.mark(seq_is_png(c) ? "png_seq_table" : seq_is_jpeg(c) ? "jpeg_tables" : "pal8_seq_build");
     }
     HIPCHK(c, hipGetLastError());
     if (!format_traits(c->frame_format)->coded()) return seq_hand_over_indices(c, write, user);
@@ -312,6 +342,76 @@ int poppy_hip_bgr_frames_to_jpeg_seq_frames(poppy_hip_ctx* c, const uint8_t* bgr
 }
 int poppy_hip_bgr_frames_to_jpeg444_seq_frames(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int W, int H, int quality, uint8_t* dst) {
     return jpeg_seq_code_host_frames(c, POPPY_FRAME_JPEG444_SEQ, bgr, stride, frame_stride, n_frames, W, H, quality, dst);
+}
+
+// host BGR frames up one by one, each through the pass of a PNG sequence (filter, counting kernel) into a store of places, one table build, every frame coded on its
+// place and `total` bytes of it down — all on buffers and sums that live for the call: the context's own sequence, store and rings are not touched
+int poppy_hip_bgr_frames_to_png_seq_frames(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int W, int H, uint8_t* dst) {
+    if (!c) return POPPY_E_ARG;
+    if (!bgr || !dst || W <= 0 || H <= 0 || stride < (size_t)W * 3 || n_frames < 1) return fail(c, POPPY_E_ARG, "bad arguments");
+    if (frame_stride < stride * ((size_t)H - 1) + (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad arguments: the frames overlap");
+    if (const char* why = sequence_refuses(POPPY_FRAME_PNG_SEQ, n_frames, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const FormatTraits& t = *format_traits(POPPY_FRAME_PNG_SEQ);
+    const size_t row = (size_t)W * 3, place = (png_scratch_bytes(W, H, t.variant) + 15) & ~(size_t)15, capacity = poppy_frame_bytes(POPPY_FRAME_PNG_SEQ, W, H);
+    CallBuffers held;
+    uint8_t *d_bgr = nullptr, *store = nullptr, *seq = nullptr, *frame = nullptr;
+    hipError_t e = held.alloc(&d_bgr, row * H + 16);
+    if (e == hipSuccess) e = held.alloc(&store, place * (size_t)n_frames);
+    if (e == hipSuccess) e = held.alloc(&seq, kPngSeqTableBytes);
+    if (e == hipSuccess) e = held.alloc(&frame, capacity + 16);
+    if (e == hipSuccess) e = hipMemsetAsync(seq, 0, kPngSeqTableBytes, c->stream);
+    for (int k = 0; k < n_frames && e == hipSuccess; ++k) {      // (the one BGR buffer: the upload is ordered behind the filter that read the frame before)
+        e = copy_rows_async(d_bgr, row, bgr + (size_t)k * frame_stride, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) break;
+        launch_png_filter(d_bgr, store + (size_t)k * place, W, H, t.variant, c->stream);
+        launch_png_seq_count(store + (size_t)k * place, (uint32_t*)seq, W, H, c->stream);
+        e = hipGetLastError();
+    }
+    void* table = seq + kPngSeqSumWords * 4;
+    if (e == hipSuccess) { launch_png_seq_table((uint32_t*)seq, table, c->stream); e = hipGetLastError(); }
+    int rc = POPPY_OK;
+    for (int k = 0; k < n_frames && e == hipSuccess && rc == POPPY_OK; ++k) {
+        uint32_t total = 0;
+        enqueue_seq_png_coding(store + (size_t)k * place, table, frame, nullptr, W, H, c->stream, nullptr);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess && !coded_length_ok(total, capacity, t.least)) rc = fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+        else if (e == hipSuccess) e = hipMemcpy(dst + (size_t)k * capacity, frame, total, hipMemcpyDeviceToHost);
+    }
+    (void)hipStreamSynchronize(c->stream);                         // nothing of the call is in flight when its buffers go (`held`, at the return)
+    if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("PNG sequence coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    return rc;
+}
+
+// k_png_seq_table alone on given counts: what poppy_png_seq_table gives, with its refusals
+int poppy_hip_png_seq_table(poppy_hip_ctx* c, const uint32_t* counts, uint8_t* lengths, uint8_t* header_bits, int* n_header_bits) {
+    if (!c) return POPPY_E_ARG;
+    if (poppy_png_seq_table(counts, nullptr, nullptr, nullptr) != POPPY_OK)      // (the refusals are the host statement's; its outputs are not used)
+        return fail(c, POPPY_E_ARG, "bad arguments: a null pointer, counts that are all zero, whose sum is 2^32 or more, or no count for symbol 256");
+    HIPCHK(c, hipSetDevice(c->device));
+    uint32_t padded[kPngSeqSumWords] = {};
+    memcpy(padded, counts, sizeof(uint32_t) * png_opt::kSymbols);
+    png_opt::OwnTable built;
+    CallBuffers held;
+    uint8_t* seq = nullptr;
+    HIPCHK(c, held.alloc(&seq, kPngSeqTableBytes));
+    uint8_t* table = seq + kPngSeqSumWords * 4;
+    hipError_t e = hipMemcpyAsync(seq, padded, sizeof padded, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { launch_png_seq_table((uint32_t*)seq, table, c->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(&built, table, sizeof built, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);     // nothing of the call is in flight when its buffers go (`held`, at the return)
+    if (e == hipSuccess) e = e_sync;
+    if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("PNG sequence table build: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    if (built.header_bits < 17 || built.header_bits > (uint32_t)png_opt::kOwnHeaderBitsMax) return fail(c, POPPY_E_DEVICE, "the built header's length is outside its bounds");
+    if (lengths) for (int i = 0; i < png_opt::kSymbols; ++i) lengths[i] = (uint8_t)(built.code[i] & 15u);
+    if (header_bits) {
+        memset(header_bits, 0, POPPY_PNG_SEQ_HEADER_BYTES);
+        for (uint32_t i = 0; 8 * i < built.header_bits; ++i) header_bits[i] = (uint8_t)(built.header[i / 4] >> (8 * (i & 3)));
+    }
+    if (n_header_bits) *n_header_bits = (int)built.header_bits;
+    return POPPY_OK;
 }
 
 }  // extern "C"

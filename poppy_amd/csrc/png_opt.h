@@ -1,5 +1,5 @@
 // png_opt.h — the constants of the POPPY_FRAME_PNG_OPT hand-off format (include/poppy_hip.h has the rule) that the host statement (frame_png_opt.cpp) and the
-// device coder (kernels_frame_png.hip) share: the ninth candidate of a segment, its own table; the bounds of an own header; the code-length code's order; what a
+// device coder (kernels_frame_png.hip) share: the ninth candidate of a segment, its own table (under POPPY_FRAME_PNG_SEQ, frame_png_seq.cpp: its sequence's one table, in the same record); the bounds of an own header; the code-length code's order; what a
 // place of the header's length sequence sends.  Everything else is POPPY_FRAME_PNG_RUNS': png_runs_tables.h.  Host and device, nothing of HIP.
 #pragma once
 #include "png_runs_tables.h"
@@ -7,7 +7,7 @@
 namespace poppy_hip {
 namespace png {
 // what the PNG coder's two format-specific steps are (frame_limits.h: FormatTraits::variant; kernels.h: launch_png_*)
-enum Variant { kLiterals = 0, kRuns = 1, kRunsOwn = 2 };      // POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_PNG_OPT
+enum Variant { kLiterals = 0, kRuns = 1, kRunsOwn = 2, kRunsSeq = 3 };      // POPPY_FRAME_PNG, POPPY_FRAME_PNG_RUNS, POPPY_FRAME_PNG_OPT, POPPY_FRAME_PNG_SEQ
 }
 namespace png_opt {
 
@@ -44,7 +44,7 @@ static_assert(entry_at(0, 149, 0).extra == 127 && entry_at(0, 149, 138).symbol =
 static_assert(entry_at(5, 3, 1).symbol == 5 && entry_at(5, 4, 1).symbol == 16 && entry_at(5, 4, 1).extra == 0 && entry_at(5, 7, 1).extra == 3 && entry_at(5, 8, 7).symbol == 5 &&
               entry_at(5, 10, 7).symbol == 16 && entry_at(5, 10, 7).extra == 0 && entry_at(5, 10, 8).symbol < 0, "runs of a length: itself, then 16 while 3 or more are left");
 
-// The table a segment's own candidate leaves in the coder's scratch: a symbol's entry as png_runs::Codes' (reversed code << 4 | length, 0 without a code), and
+// The table a segment's own candidate leaves in the coder's scratch, and the one table of a POPPY_FRAME_PNG_SEQ sequence: a symbol's entry as png_runs::Codes' (reversed code << 4 | length, 0 without a code), and
 // the header's bits, least significant bit of word 0 first, BFINAL 0, zeros behind `header_bits`.
 struct OwnTable { uint32_t code[kSymbols], header_bits, header[kOwnHeaderWords + 1]; };      // (+ 1: the word a 64-bit flush may touch behind the last)
 

@@ -78,6 +78,7 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
     std::vector<uint8_t> pal8(t.sequence && t.coder == kCoderGif ? raster_bytes(kRasterPal8, W, H) : 0);      // (GIF_SEQ: PAL8_SEQ's frame, then the host coder)
     int rc = POPPY_OK;                                             // the host statement of the record's steps
     if (t.sequence && t.coder == kCoderJpeg) rc = jpeg_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, c->jpeg_quality, fmt, tmp.data());
+    else if (t.sequence && t.coder == kCoderPng) rc = png_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, tmp.data());
     else if (t.sequence) rc = pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, pal8.empty() ? tmp.data() : pal8.data());
     else if (t.coder == kCoderGif) rc = poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data());
     else if (t.coder == kCoderJpeg && t.frame_tables) rc = (t.sampling() == jpeg::k444 ? poppy_bgr_to_jpeg444_opt_frame : poppy_bgr_to_jpeg_opt_frame)(bgr, stride, W, H, c->jpeg_quality, tmp.data());

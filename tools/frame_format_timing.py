@@ -20,7 +20,8 @@ frame.
 column "gif@2" is GIF at scale 2), alternated with the others in the same process; --kernel-scales adds k_bgr_downscale's own time (timing mode 1: frame_scale) under BGR
 at 1080p and 4K for those factors.  --size OWxOH adds every format again at that size (poppy_hip_set_frame_size: the column "i420@1280x720"); the 4K rows of such a
 column use --size-4k (default: --size), and its timing mode 1 entry has the resize kernel's time (frame_resize).  GIF's d2h_ceiling entry is its CAPACITY (poppy_frame_bytes); a frame's copy moves its own
-length, which depends on the content.  jpeg_seq and jpeg444_seq (POPPY_FRAME_JPEG_SEQ, POPPY_FRAME_JPEG444_SEQ: one table set per sequence) are columns only when --formats names them:
+length, which depends on the content.  jpeg_seq and jpeg444_seq (POPPY_FRAME_JPEG_SEQ, POPPY_FRAME_JPEG444_SEQ: one table set per sequence) and png_seq (POPPY_FRAME_PNG_SEQ: one ninth deflate
+table per sequence; its marks are png_filter, png_seq_count, png_seq_table, png_seq_cost, png_scan, png_seq_pack, png_crc, png_finish) are columns only when --formats names them:
 under them a row's call hands its writer nothing before its last frame is rendered, and job480 is one sequence of 480 frames.  One JSON line at the end.
 """
 import argparse
@@ -38,10 +39,11 @@ from poppy_amd import capi, synth  # noqa: E402
 ALL_FMTS = (("bgr", capi.FRAME_BGR), ("i420", capi.FRAME_I420), ("pal8", capi.FRAME_PAL8), ("pal8_seq", capi.FRAME_PAL8_SEQ), ("gif", capi.FRAME_GIF), ("jpeg", capi.FRAME_JPEG),
             ("jpeg444", capi.FRAME_JPEG444), ("png", getattr(capi, "FRAME_PNG", 1024)), ("png_runs", getattr(capi, "FRAME_PNG_RUNS", 2048)),
             ("jpeg_opt", getattr(capi, "FRAME_JPEG_OPT", 4096)), ("jpeg444_opt", getattr(capi, "FRAME_JPEG444_OPT", 8192)), ("png_opt", getattr(capi, "FRAME_PNG_OPT", 16384)),
-            ("jpeg_seq", getattr(capi, "FRAME_JPEG_SEQ", 32768)), ("jpeg444_seq", getattr(capi, "FRAME_JPEG444_SEQ", 65536)))      # (not among the default --formats)
+            ("jpeg_seq", getattr(capi, "FRAME_JPEG_SEQ", 32768)), ("jpeg444_seq", getattr(capi, "FRAME_JPEG444_SEQ", 65536)),
+            ("png_seq", getattr(capi, "FRAME_PNG_SEQ", 131072)))      # (the sequence formats of JPEG and PNG are not among the default --formats)
 
 
-PNG_MARKS = ("png_filter", "png_cost", "png_scan", "png_pack", "png_crc", "png_finish")
+PNG_MARKS = ("png_filter", "png_cost", "png_scan", "png_pack", "png_crc", "png_finish", "png_seq_count", "png_seq_table", "png_seq_cost", "png_seq_pack")
 PHOTOS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "photo_pair_720x405.npz")
 
 

@@ -1,7 +1,7 @@
 // png_host_check.cpp — the host statements of POPPY_FRAME_PNG (poppy_amd/csrc/frame_png.cpp), POPPY_FRAME_PNG_RUNS (frame_png_runs.cpp) and POPPY_FRAME_PNG_OPT
 // (frame_png_opt.cpp) alone, on the host, under a sanitizer:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tools/png_host_check.cpp poppy_amd/csrc/frame_png.cpp \
-//       poppy_amd/csrc/frame_png_runs.cpp poppy_amd/csrc/frame_png_opt.cpp poppy_amd/csrc/frame_sink.cpp poppy_amd/csrc/frame_jpeg.cpp poppy_amd/csrc/frame_i444.cpp poppy_amd/csrc/frame_gif.cpp poppy_amd/csrc/frame_pal8.cpp \
+//       poppy_amd/csrc/frame_png_runs.cpp poppy_amd/csrc/frame_png_opt.cpp poppy_amd/csrc/frame_png_seq.cpp poppy_amd/csrc/frame_sink.cpp poppy_amd/csrc/frame_jpeg.cpp poppy_amd/csrc/frame_i444.cpp poppy_amd/csrc/frame_gif.cpp poppy_amd/csrc/frame_pal8.cpp \
 //       -o /tmp/png_asan && /tmp/png_asan
 // Every frame is coded from a BGR buffer of exactly its own size into a heap buffer of EXACTLY poppy_frame_bytes(POPPY_FRAME_PNG, w, h) bytes, so a byte written
 // behind the capacity or read outside the frame is the sanitizer's to report; a second run into a canary-filled buffer checks that nothing behind `total` is
@@ -12,7 +12,10 @@
 // exactly THAT format's capacity, the canary run, the same CRC check, and the frame decoded by a plain inflate of its blocks (literals, and matches at distance
 // 1 only) back to POPPY_FRAME_PNG's filtered stream.  POPPY_FRAME_PNG_OPT: the same through poppy_bgr_to_png_opt_frame into a buffer of exactly PNG_RUNS' capacity,
 // never longer than the PNG_RUNS frame, decoded by an inflate that reads every block's header (the own ones are run-coded).  poppy_png_optimal_lengths: count
-// families — deep trees, ties, one symbol, as many as the limit holds — into buffers of exactly n_symbols bytes, the Kraft sum exactly 1.  Returns 0 when everything holds.
+// families — deep trees, ties, one symbol, as many as the limit holds — into buffers of exactly n_symbols bytes, the Kraft sum exactly 1.  POPPY_FRAME_PNG_SEQ
+// (frame_png_seq.cpp, added to the command line above): the four contents of a size as ONE sequence through poppy_bgr_frames_to_png_seq_frames, from a buffer of
+// exactly four frames into one of exactly four capacities, the canary run, no frame longer than its PNG_RUNS frame, every frame decoded by the same inflate;
+// poppy_png_seq_table on the sequence-sized count families into buffers of exactly 286 and POPPY_PNG_SEQ_HEADER_BYTES bytes.  Returns 0 when everything holds.
 #include "../include/poppy_hip.h"
 #include "../poppy_amd/csrc/png_runs_tables.h"
 #include <cstdint>
@@ -221,9 +224,13 @@ int main() {
         const int w = wh[0], h = wh[1];
         const size_t cap = poppy_frame_bytes(POPPY_FRAME_PNG, w, h), n = (size_t)h * (1 + 3 * (size_t)w);
         const size_t runs_cap = poppy_frame_bytes(POPPY_FRAME_PNG_RUNS, w, h);
+        std::vector<uint8_t> seq_bgr;                        // the four contents, one behind the other: the size's sequence
+        std::vector<std::vector<uint8_t>> seq_streams;
+        size_t seq_runs_total[4] = {};
         for (int content = 0; content < 4; ++content) {
             std::vector<uint8_t> bgr((size_t)w * h * 3);
             for (size_t i = 0; i < bgr.size(); ++i) bgr[i] = content == 0 ? noise() : content == 1 ? 200 : content == 2 ? (uint8_t)(i * 7 / 3) : 0;
+            seq_bgr.insert(seq_bgr.end(), bgr.begin(), bgr.end());
             std::vector<uint8_t> frame(cap), again(cap + 64, 0xA5), stream;
             const int rc = poppy_bgr_to_png_frame(bgr.data(), (size_t)w * 3, w, h, frame.data());
             const size_t total = poppy_png_frame_bytes(frame.data());
@@ -267,6 +274,26 @@ int main() {
                 opt_ok = opt_ok && decode_opt_stream(opt.data(), end, n, &opt_stream) && opt_stream == stream && adler_in_segments(opt_stream) == be32(opt.data() + end);
             }
             if (!opt_ok) { fprintf(stderr, "%d x %d, content %d, own tables: rc %d, total %zu, the run format's %zu\n", w, h, content, opt_rc, opt_total, runs_total); ++failures; }
+            seq_streams.push_back(stream); seq_runs_total[content] = runs_total;
+        }
+        // the sequence format: the four frames on one table, into a buffer of exactly four capacities; every frame no longer than its run-format frame, the same stream
+        {
+            const size_t frame_bytes = (size_t)w * h * 3;
+            std::vector<uint8_t> seq(4 * runs_cap), seq_again(4 * runs_cap + 64, 0xA5), seq_stream;
+            const int seq_rc = poppy_bgr_frames_to_png_seq_frames(seq_bgr.data(), (size_t)w * 3, frame_bytes, 4, w, h, seq.data());
+            bool seq_ok = seq_rc == POPPY_OK && poppy_frame_bytes(POPPY_FRAME_PNG_SEQ, w, h) == runs_cap &&
+                          poppy_bgr_frames_to_png_seq_frames(seq_bgr.data(), (size_t)w * 3, frame_bytes, 4, w, h, seq_again.data()) == POPPY_OK;
+            for (int k = 0; k < 4 && seq_ok; ++k) {
+                const uint8_t* f = seq.data() + (size_t)k * runs_cap;
+                const size_t total = poppy_png_frame_bytes(f), end = total - kTailBytes;
+                ++frames;
+                seq_ok = total >= kFrameMinBytes && total <= seq_runs_total[k];
+                for (size_t i = 0; i < total && seq_ok; ++i) seq_ok = seq_again[(size_t)k * runs_cap + i] == f[i];
+                seq_ok = seq_ok && be32(f + kOffIdat) == end + 4 - (kOffIdatType + 4) && crc_in_pieces(f, end) == be32(f + end + 4);
+                seq_ok = seq_ok && decode_opt_stream(f, end, n, &seq_stream) && seq_stream == seq_streams[(size_t)k] && adler_in_segments(seq_stream) == be32(f + end);
+            }
+            for (size_t i = 4 * runs_cap; i < seq_again.size() && seq_ok; ++i) seq_ok = seq_again[i] == 0xA5;
+            if (!seq_ok) { fprintf(stderr, "%d x %d, the sequence of four: rc %d\n", w, h, seq_rc); ++failures; }
         }
     }
     // the length rule alone: Fibonacci counts (depth n - 1), equal counts (every merge a tie), one symbol, a ramp, as many symbols as 7 bits hold
@@ -281,7 +308,34 @@ int main() {
       ++rules;
       if (poppy_png_optimal_lengths(zero, 2, 15, one) != POPPY_E_ARG || poppy_png_optimal_lengths(big, 2, 15, one) != POPPY_E_ARG || poppy_png_optimal_lengths(zero, 0, 15, one) != POPPY_E_ARG ||
           poppy_png_optimal_lengths(many.data(), 129, 7, out.data()) != POPPY_E_ARG || poppy_png_optimal_lengths(many.data(), 19, 8, out.data()) != POPPY_E_ARG) { fprintf(stderr, "lengths: a refusal is missing\n"); ++failures; } }
-    printf("%d count families through the length rule\n", rules);
+    // the sequence's table alone, into buffers of exactly its outputs' sizes: sums no segment reaches, and the refusals
+    {
+        std::vector<uint32_t> counts(286);
+        std::vector<uint8_t> lengths(286), header(POPPY_PNG_SEQ_HEADER_BYTES);
+        int bits = 0;
+        auto table_holds = [&]() {
+            if (poppy_png_seq_table(counts.data(), lengths.data(), header.data(), &bits) != POPPY_OK || bits < 17 || bits > 2083) return false;
+            unsigned long long kraft = 0; int used = 0;
+            for (int i = 0; i < 286; ++i) { if ((lengths[(size_t)i] != 0) != (counts[(size_t)i] != 0) || lengths[(size_t)i] > 15) return false; if (lengths[(size_t)i]) { kraft += 1ull << (15 - lengths[(size_t)i]); ++used; } }
+            for (int i = bits; i < 8 * POPPY_PNG_SEQ_HEADER_BYTES; ++i) if (header[(size_t)i >> 3] >> (i & 7) & 1) return false;      // zeros behind the header
+            return (header[0] & 7) == 4 && (used == 1 ? kraft == 1ull << 14 : kraft == 1ull << 15);
+        };
+        for (int i = 0; i < 286; ++i) counts[(size_t)i] = 7; ++rules; if (!table_holds()) { fprintf(stderr, "sequence table: 286 equal counts\n"); ++failures; }
+        for (int i = 0; i < 286; ++i) counts[(size_t)i] = (uint32_t)i + 1; ++rules; if (!table_holds()) { fprintf(stderr, "sequence table: a ramp\n"); ++failures; }
+        for (int i = 0; i < 286; ++i) counts[(size_t)i] = i >= 217 && i <= 256 ? fib[256 - i] : 0; ++rules; if (!table_holds()) { fprintf(stderr, "sequence table: 40 Fibonacci counts\n"); ++failures; }
+        for (int i = 0; i < 286; ++i) counts[(size_t)i] = i == 0 ? 0xFFFFFFFFu - 285u : 1u; ++rules; if (!table_holds()) { fprintf(stderr, "sequence table: a sum of 2^32 - 1\n"); ++failures; }
+        for (int i = 0; i < 286; ++i) counts[(size_t)i] = i == 256 ? 3u : 0u; ++rules; if (!table_holds()) { fprintf(stderr, "sequence table: end-of-block alone\n"); ++failures; }
+        ++rules;
+        if (poppy_png_seq_table(counts.data(), nullptr, nullptr, nullptr) != POPPY_OK || poppy_png_seq_table(nullptr, lengths.data(), header.data(), &bits) != POPPY_E_ARG) { fprintf(stderr, "sequence table: null pointers\n"); ++failures; }
+        counts[256] = 0; counts[0] = 5;
+        if (poppy_png_seq_table(counts.data(), lengths.data(), header.data(), &bits) != POPPY_E_ARG) { fprintf(stderr, "sequence table: no end-of-block is not refused\n"); ++failures; }
+        counts[256] = 1u << 31; counts[0] = 1u << 31;
+        if (poppy_png_seq_table(counts.data(), lengths.data(), header.data(), &bits) != POPPY_E_ARG) { fprintf(stderr, "sequence table: a sum of 2^32 is not refused\n"); ++failures; }
+        const uint8_t* wild = (const uint8_t*)8;
+        if (poppy_bgr_frames_to_png_seq_frames(wild, 3, 3, 858993460, 1, 1, header.data()) != POPPY_E_UNSUPPORTED || poppy_bgr_frames_to_png_seq_frames(wild, 6, 6, 1 << 29, 2, 1, header.data()) != POPPY_E_UNSUPPORTED ||
+            poppy_bgr_frames_to_png_seq_frames(wild, 6, 11, 2, 2, 2, header.data()) != POPPY_E_ARG || poppy_bgr_frames_to_png_seq_frames(wild, 6, 12, 0, 2, 2, header.data()) != POPPY_E_ARG) { fprintf(stderr, "sequence: a refusal is missing\n"); ++failures; }
+    }
+    printf("%d count families through the length rule and the sequence's table\n", rules);
     printf("%d frames coded into buffers of exactly the capacity, %d failures; the fullest used %zu of %zu bytes\n", frames, failures, fullest, fullest_cap);
     return failures ? 1 : 0;
 }
