@@ -816,6 +816,21 @@ int poppy_hip_foreground(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, 
  * by windows, 6 / 7 = as 5 with the first window at the top / bottom of the ranks (the windows beside it do the work).  All forms return
  * the same bytes.                                                                                                                     */
 int poppy_hip_median_blur(poppy_hip_ctx* ctx, const uint8_t* src, int width, int height, int ksize, int form, uint8_t* dst);
+/* What tests of those medians need to state what they reach; host only, no result depends on them.
+ * poppy_median_cols_geom: how k_median_cols cuts a width x height image: tiles_x x tiles_y tiles of tile_cols columns by rows rows (the last
+ * ones cut by the image; POPPY_MED_COLS_ROWS, read once per process, sets rows).  Each pointer may be NULL.
+ * poppy_median_cols_hint: the choice between the two median kernels that the set-up makes from a sparse sample of a host BGR image: 1 = its
+ * tiles hold few values (the chain takes k_median_cols), 0 = not, or an image under 256 x 64 (k_median_u8).  POPPY_E_ARG (negative) on bad
+ * arguments.
+ * poppy_hip_foreground_median_links: of the last chain that the context's image slot `which` (0: poppy_hip_foreground and a pair's first
+ * image, 1: a pair's second image; a chained next pair swaps them) ran: cols_mask bit i = the median of ksize 8 i + 1 went through
+ * k_median_cols (bit 0 never: eleven real links, 0xffe), decided_by = POPPY_MEDIAN_BY_* below, 0 before any chain.                         */
+#define POPPY_MEDIAN_BY_HINT 1      /* the host sample (poppy_median_cols_hint) */
+#define POPPY_MEDIAN_BY_DEVICE 2    /* the device's count of tiles of at most 24 values: nine tenths of the tiles -> k_median_cols */
+#define POPPY_MEDIAN_BY_ENV 3       /* POPPY_MED_COLS_FORCE, or POPPY_MED_COLS_MIN above 89 */
+int poppy_median_cols_geom(int width, int height, int* tiles_x, int* tiles_y, int* rows, int* tile_cols);
+int poppy_median_cols_hint(const uint8_t* bgr, size_t stride, int width, int height);
+int poppy_hip_foreground_median_links(poppy_hip_ctx* ctx, int which, unsigned* cols_mask, int* decided_by);
 
 /* The last stage of every frame on its own: unsharp_mask(src, 1, amount, 0.3) + convertTo(CV_8U, 255) (src/util.cpp:113-148,
  * src/algo.cpp:263-265) on a host float image of width x height BGR pixels, `pitch` pixels per row (>= width; the padding pixels are

@@ -52,7 +52,7 @@ SYMBOLS = [
     "poppy_sink_open", "poppy_sink_write", "poppy_sink_close", "poppy_hip_render_phases", "poppy_hip_pool_set_timing", "poppy_hip_pool_timing_summary", "poppy_hip_pool_warp_counts", "poppy_hip_pool_create", "poppy_hip_pool_create_tuned", "poppy_hip_pool_destroy", "poppy_hip_pool_morph_pairs", "poppy_hip_pool_submit_pairs", "poppy_hip_pool_wait", "poppy_count_pair_frames_cb", "poppy_hip_warp_counts", "poppy_hip_time_last_warp", "poppy_hip_mask_rider", "poppy_hip_pool_mask_rider", "poppy_hip_comm_id", "poppy_hip_comm_init", "poppy_hip_comm_free", "poppy_hip_comm_info", "poppy_hip_pair_broadcast", "poppy_hip_comm_max",
     "poppy_hip_pair_begin_sharded", "poppy_hip_sharded_setups", "poppy_hip_pair_begin_sharded_local", "poppy_hip_pair_state_bytes", "poppy_hip_pair_export_device", "poppy_hip_pair_import_device", "poppy_hip_morph_sharded", "poppy_hip_morph_pairs",
     "poppy_dft_plan", "poppy_hip_pair_begin_device", "poppy_count_frames_cb", "poppy_hip_morph", "poppy_hip_pair_distance", "poppy_printed_morph_distance", "poppy_hypotf_selfcheck",
-    "poppy_hip_orb_detect", "poppy_hip_foreground", "poppy_hip_median_blur", "poppy_match_points", "poppy_hip_pair_begin_prefiltered", "poppy_hip_pair_begin", "poppy_hip_pair_begin_info", "poppy_hip_orb_input", "poppy_hip_gabor_field", "poppy_hip_set_gabor_direct", "poppy_hip_set_setup_chains", "poppy_hip_gabor_doubt", "poppy_radial_gradient", "poppy_radial_mask", "poppy_gabor_tables", "poppy_gabor_rounding_in_doubt", "poppy_gabor_band_unit", "poppy_pyr_tail_plan", "poppy_hip_blur_margin", "poppy_hip_pair_points",
+    "poppy_hip_orb_detect", "poppy_hip_foreground", "poppy_hip_median_blur", "poppy_median_cols_geom", "poppy_median_cols_hint", "poppy_hip_foreground_median_links", "poppy_match_points", "poppy_hip_pair_begin_prefiltered", "poppy_hip_pair_begin", "poppy_hip_pair_begin_info", "poppy_hip_orb_input", "poppy_hip_gabor_field", "poppy_hip_set_gabor_direct", "poppy_hip_set_setup_chains", "poppy_hip_gabor_doubt", "poppy_radial_gradient", "poppy_radial_mask", "poppy_gabor_tables", "poppy_gabor_rounding_in_doubt", "poppy_gabor_band_unit", "poppy_pyr_tail_plan", "poppy_hip_blur_margin", "poppy_hip_pair_points",
     "poppy_hip_pair_begin_next", "poppy_hip_pair_begin_next_device", "poppy_hip_chain_counts", "poppy_hip_morph_list",
     "poppy_hip_last_pyramid_forms",
     "poppy_hip_set_frame_format", "poppy_hip_pool_set_frame_format", "poppy_frame_bytes", "poppy_bgr_to_i420", "poppy_bgr_to_pal8", "poppy_bgr_frames_to_pal8",
@@ -138,6 +138,9 @@ def lib():
         L.poppy_hip_orb_detect.argtypes = [vp, vp, sz, i, i, i, vp, i, vp]
         L.poppy_hip_foreground.argtypes = [vp, vp, sz, i, i, vp, vp]
         L.poppy_hip_median_blur.argtypes = [vp, vp, i, i, i, i, vp]
+        L.poppy_median_cols_geom.argtypes = [i, i, vp, vp, vp, vp]
+        L.poppy_median_cols_hint.argtypes = [vp, sz, i, i]
+        L.poppy_hip_foreground_median_links.argtypes = [vp, i, vp, vp]
         L.poppy_hip_unsharp_frame.argtypes = [vp, vp, i, i, i, C.c_float, i, i, vp, vp]
         L.poppy_hip_comm_info.argtypes = [vp, vp, vp, vp, vp]
         L.poppy_hip_pair_begin.argtypes = [vp, vp, sz, vp, sz, i, i]
@@ -279,6 +282,27 @@ def lib():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+MEDIAN_BY_HINT, MEDIAN_BY_DEVICE, MEDIAN_BY_ENV = 1, 2, 3      # decided_by of Context.foreground_median_links (include/poppy_hip.h)
+
+
+def median_cols_geom(w, h):
+    """(tiles_x, tiles_y, rows, tile_cols): how k_median_cols cuts a w x h image (host only)."""
+    v = [C.c_int(0) for _ in range(4)]
+    if lib().poppy_median_cols_geom(int(w), int(h), *[C.byref(x) for x in v]) != 0:
+        raise ValueError("median_cols_geom: bad size")
+    return tuple(x.value for x in v)
+
+
+def median_cols_hint(bgr):
+    """1: the set-up's sparse sample of this host BGR image says "few values per tile" (its chain of medians takes k_median_cols), 0: not (host only)."""
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    r = lib().poppy_median_cols_hint(_p(a), w * 3, w, h)
+    if r < 0:
+        raise ValueError("median_cols_hint: bad image")
+    return r
 
 
 def frame_bytes(fmt, w, h):
@@ -1447,6 +1471,13 @@ class Context:
         out = np.zeros((h, w), np.uint8)
         self._chk(lib().poppy_hip_median_blur(self.h, _p(a), w, h, int(ksize), int(form), _p(out)), "median_blur")
         return out
+
+    def foreground_median_links(self, which=0):
+        """(cols_mask, decided_by) of the last chain of medians that image slot `which` ran: bit i of cols_mask = the link of ksize 8 i + 1 went
+        through k_median_cols (0xffe: all eleven real links); decided_by: MEDIAN_BY_HINT / _DEVICE / _ENV, 0 before any chain."""
+        m, d = C.c_uint(0), C.c_int(0)
+        self._chk(lib().poppy_hip_foreground_median_links(self.h, int(which), C.byref(m), C.byref(d)), "foreground_median_links")
+        return m.value, d.value
 
     def unsharp_frame(self, src, amount, form=0, pitch=None, amount_on_device=False, want_float=False):
         """The frame path's last stage on a float image (h, w, 3): unsharp_mask(src, 1, amount, 0.3) + convertTo(CV_8U, 255) -> u8 (h, w, 3), with

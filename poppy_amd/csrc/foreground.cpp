@@ -92,6 +92,8 @@ const uint8_t* ForegroundFilter::run_device(const uint8_t* bgr, size_t stride, i
     static const int forced_cols = getenv("POPPY_MED_COLS_FORCE") ? atoi(getenv("POPPY_MED_COLS_FORCE")) : -1;
     int use_cols = forced_cols >= 0 ? forced_cols : median_cols_hint;
     median_cols_hint = -1;
+    last_cols_decided_by = forced_cols >= 0 || median_cols_min_ksize() > 89 ? 3 : use_cols >= 0 ? 1 : 2;
+    last_cols_mask = 0;
     if (median_cols_min_ksize() > 89) use_cols = 0;
     // images with many values per tile (photographs): the lane-per-column kernel's time grows with the window, the column histograms' does not — they take over later
     const int cols_from_hard = forced_cols == 0 || median_cols_min_ksize() > 89 ? 999 : median_cols_min_ksize_hard();
@@ -128,6 +130,7 @@ const uint8_t* ForegroundFilter::run_device(const uint8_t* bgr, size_t stride, i
             if (!pres_valid) { launch_median_presence(inputs[i], pres[pp], w, h, nullptr, s); pres_valid = true; }
             launch_median_cols(pad[pc], med, i < 11 ? pad[pc ^ 1] : nullptr, w, h, ksize, pres[pp], pres[pp ^ 1], 0, s);
             pc ^= 1; pp ^= 1;
+            last_cols_mask |= 1u << i;
         } else {                                              // every median writes its result twice: tight (MOG2's input) and padded (the next median's)
             launch_median_padded(pad[pc], med, i < 11 ? pad[pc ^ 1] : nullptr, w, h, ksize, s);
             pc ^= 1; pres_valid = false;

@@ -49,6 +49,11 @@ public:
     // column, -1 = ask the device (a presence pass over the grey image and a 4-byte read-back).  Set per image by the caller that holds host pixels
     // (median_cols_hint_from_host); reset to -1 by run_device.  POPPY_MED_COLS_FORCE = 0 / 1 overrides.  Every choice gives the same bytes.
     int median_cols_hint = -1;
+    // What the last run_device's chain of medians took (poppy_hip_foreground_median_links): bit i of 12 set = the link of ksize 8 i + 1 went through
+    // launch_median_cols (bit 0, the copy of ksize 1, never is: eleven real links, 0xffe); who chose between the kernels: 1 = the caller's hint, 2 = the device's count of easy tiles, 3 = an environment override
+    // (POPPY_MED_COLS_FORCE, or POPPY_MED_COLS_MIN above 89); 0 = no chain has run.  Plain member writes: read them once the run has returned.
+    unsigned last_cols_mask = 0;
+    int last_cols_decided_by = 0;
     bool radial_mask_on = false;         // Settings::enable_radial_mask (src/extractor.cpp:178-197): set before the first run of a geometry or any time after
     bool gabor_direct = false;           // run the Gabor banks as direct double sums even when the FFT spectra exist (tests compare the two)
 private:

@@ -401,7 +401,8 @@ __global__ void __launch_bounds__(256) k_median_presence(const uint8_t* __restri
 MedianColsGeom median_cols_geom(int w, int h) {
     MedianColsGeom g{};
     g.run = kMcRun;                                                  // (compiled in: the run's loop is unrolled)
-    g.tiles_x = (w + kMcWaves * kMcRun - 1) / (kMcWaves * kMcRun);
+    g.cols = kMcWaves * kMcRun;
+    g.tiles_x = (w + g.cols - 1) / g.cols;
     // rows per tile: about three tiles per compute unit for the whole image (a tile pays 2r rows of column warm-up; four workgroups fit a compute unit
     // and a pair's two images run side by side), at least 16.  Measured at 1080p / 4K: tools/experiments/median_rows_ab.sh.
     static const int forced_rows = getenv("POPPY_MED_COLS_ROWS") ? atoi(getenv("POPPY_MED_COLS_ROWS")) : 0;

@@ -45,7 +45,7 @@ void launch_median_padded(const uint8_t* padded_src, uint8_t* dst, uint8_t* padd
 // of a pixel does not depend on ksize.  The image is cut into tiles of median_cols_geom(); pres_in (may be null) = the 256-bit presence map of every
 // tile of the SOURCE (median_presence_words() dwords: launch_median_presence, or the pres_out of the median that made the source): tiles whose
 // footprint holds at most 64 different values are filtered on the values' ranks, at a third of the cost.  pres_out (may be null): the map of dst.
-struct MedianColsGeom { int run, rows, tiles_x, tiles_y; };
+struct MedianColsGeom { int run, rows, tiles_x, tiles_y, cols; };      // cols: a tile's width (its chains' runs side by side)
 MedianColsGeom median_cols_geom(int w, int h);
 size_t median_presence_words(int w, int h);
 // easy_or_null: a device counter (zeroed by the caller) of the tiles that hold few different values: nine tenths of an image's tiles -> the column-histogram form pays

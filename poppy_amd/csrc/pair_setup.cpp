@@ -232,6 +232,27 @@ int poppy_hip_median_blur(poppy_hip_ctx* c, const uint8_t* src, int W, int H, in
     return POPPY_OK;
 }
 
+int poppy_median_cols_geom(int W, int H, int* tiles_x, int* tiles_y, int* rows, int* tile_cols) {
+    if (W <= 0 || H <= 0) return POPPY_E_ARG;
+    const MedianColsGeom g = median_cols_geom(W, H);
+    if (tiles_x) *tiles_x = g.tiles_x;
+    if (tiles_y) *tiles_y = g.tiles_y;
+    if (rows) *rows = g.rows;
+    if (tile_cols) *tile_cols = g.cols;
+    return POPPY_OK;
+}
+int poppy_median_cols_hint(const uint8_t* bgr, size_t stride, int W, int H) {
+    if (!bgr || W <= 0 || H <= 0 || stride < (size_t)W * 3) return POPPY_E_ARG;
+    return median_cols_hint_from_host(bgr, stride, W, H);
+}
+int poppy_hip_foreground_median_links(poppy_hip_ctx* c, int which, unsigned* cols_mask, int* decided_by) {
+    if (!c || which < 0 || which > 1) return POPPY_E_ARG;
+    const ForegroundFilter& fg = chain_fg(c, which);
+    if (cols_mask) *cols_mask = fg.last_cols_mask;
+    if (decided_by) *decided_by = fg.last_cols_decided_by;
+    return POPPY_OK;
+}
+
 int poppy_hip_pair_corrected2(poppy_hip_ctx* c, uint8_t* dst, size_t ds) {
     if (!c || !dst) return POPPY_E_ARG;
     if (!c->pair_ready) return fail(c, POPPY_E_STATE, "no resident pair");
