@@ -969,6 +969,67 @@ int poppy_blur_margin_rects(int width, int height, int union_width, int union_he
 int poppy_blur_margin_taps(int taps[127]);
 /* The most canvas rows poppy_hip_blur_margin and poppy_hip_morph_list's canvas take on this context's device (its maxGridSize[1]). */
 int poppy_hip_blur_margin_max_rows(poppy_hip_ctx* ctx, int* rows);
+
+/* --denoise: the CLI's optional fastNlMeansDenoising of every image as it is read (src/poppy.cpp:172), in front of the union size and blur_margin.
+ * Non-local means on an 8-bit BGR image with ONE strength hs, in the direct integer form of OpenCV 4.6's fastNlMeansDenoising.  PINNED BY RESTATEMENT
+ * ONLY: neither the reference nor OpenCV was at hand, so the rule is DEFINED by the host statement poppy_bgr_denoise below, and poppy_hip_denoise returns
+ * the same bytes.  What a fixture from the reference would have to confirm: the constants (fixed_point_mult from 2^32 - 1, the table length, the 0.001
+ * cut-off), float evaluation of hs * hs * 3, the border (reflect-101), the rounding of the table and of the final quotient — and the arguments the CLI
+ * passes at :172, which SURVEY.md does not record: hs and both windows are arguments here.
+ *
+ * The rule.  src is width x height; template window tw and search window sw are odd; th = tw / 2, sh = sw / 2, b = th + sh.
+ *   1. e = src extended by b on every side with reflect-101, folded as often as needed (a side of 1 maps every index to 0): blur_margin's fold.
+ *   2. fpm = min(floor((2^32 - 1) / (sw * sw * 255)), 2^31 - 1); shift = the smallest s with 2^s >= tw * tw; mult = 2^shift / (tw * tw) as a double;
+ *      the table has n = (int)(195075 / mult) + 1 entries.
+ *   3. den = (hs * hs) * 3 evaluated in FLOAT, then widened to double.  For a = 0 .. n - 1: wd = exp(-(a * mult) / den) in double (the host's libm),
+ *      t[a] = round-half-even(fpm * wd), set to 0 where it is below 0.001 * fpm.  The table does not increase; L = the index behind its last non-zero
+ *      entry.
+ *   4. For pixel (x, y) and every offset (dx, dy) in [-sh, sh]^2:  D = the sum over (i, j) in [-th, th]^2 and the three channels of
+ *      (e(x + i, y + j) - e(x + dx + i, y + dy + j))^2.
+ *   5. a = D >> shift, wgt = a < L ? t[a] : 0;  est[c] += wgt * e(x + dx, y + dy)[c], ws += wgt, in unsigned 32-bit arithmetic (est <= 255 ws < 2^32 by the
+ *      choice of fpm).
+ *   6. dst[c] = (est[c] + ws / 2) / ws, where ws / 2 is the integer half and the SUM is not reduced modulo 2^32: at sw = 21 an all-255 image has
+ *      est = 4 294 881 360, 85 936 under 2^32, and est + ws / 2 above it; the result is 255.  ws >= t[0] = fpm > 0: the centre offset has D = 0.
+ * With tw = 7, sw = 21: fpm = 38192, shift = 6, n = 149355, and L = 143 at hs = 3, 1585 at 10, 6340 at 20, 25357 at 40, the whole table at 100.
+ *
+ * Refusals, the same in every entry point below, before a byte is read, anything is allocated or launched, and with dst untouched:
+ *   POPPY_E_ARG          a null pointer, a non-positive size, a stride shorter than its row, hs not finite or <= 0, an even or non-positive window
+ *                        (poppy_hip_denoise_device: also d_src == d_dst);
+ *   POPPY_E_UNSUPPORTED  tw outside 3 .. POPPY_DENOISE_MAX_TEMPLATE or sw outside 3 .. POPPY_DENOISE_MAX_SEARCH.  These limits are the kernel's; the host
+ *                        statement shares them, so the two agree on what exists.
+ * Left out: the per-channel h form (a vector of strengths), fastNlMeansDenoisingColored, grey and 16-bit images, larger windows.                          */
+#define POPPY_DENOISE_MAX_TEMPLATE 7
+#define POPPY_DENOISE_MAX_SEARCH 21
+#define POPPY_DENOISE_TILE_W 58        /* poppy_denoise_tile */
+#define POPPY_DENOISE_TILE_H 64
+#define POPPY_DENOISE_TABLE_LDS 8192   /* poppy_denoise_table_bound */
+/* Host only: the ONE place the weight table and its constants are formed (steps 2 and 3); the GPU path uploads this table and never evaluates exp.
+ * table (may be NULL with capacity 0: the constants alone) takes n entries; a capacity below n: POPPY_E_ARG with *n set.  Every output may be NULL. */
+int poppy_denoise_weights(float hs, int template_window, int search_window, uint32_t* table, int capacity,
+                          int* n, int* L, uint32_t* fixed_point_mult, int* shift);
+/* Host only: the rule, from per-offset squared-difference images and their integrals (every D exactly). */
+int poppy_bgr_denoise(const uint8_t* bgr, size_t stride, int width, int height, float hs, int template_window, int search_window,
+                      uint8_t* dst, size_t dst_stride);
+/* Host only: the output tile of the kernel's workgroups, and the longest table prefix L the kernel stages in LDS (a longer one is read from global
+ * memory) — for tests, which take their sizes and strengths from here. */
+int poppy_denoise_tile(int* tile_width, int* tile_height);
+int poppy_denoise_table_bound(int* entries);
+/* The same bytes from the GPU.  Host image in, host image out, synchronous; needs no resident pair and disturbs none.  The table of the last
+ * (hs, tw, sw) and a staging image are kept by the context. */
+int poppy_hip_denoise(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, int width, int height, float hs, int template_window, int search_window,
+                      uint8_t* dst, size_t dst_stride);
+/* Device image in, device image out, tight rows, d_src != d_dst, queued on poppy_hip_stream(ctx).  (A change of hs or of a window since the last call
+ * waits for that stream once, while the table is replaced.) */
+int poppy_hip_denoise_device(poppy_hip_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int width, int height, float hs, int template_window, int search_window);
+/* The CLI's --denoise for poppy_hip_morph_list.  hs = 0 (the default; the windows are ignored): off.  Otherwise the list call denoises EVERY image its
+ * source hands it, as it arrives — host or device images, with or without a canvas — at the image's OWN size and in front of the canvas padding
+ * (:172 before :239), into buffers of the context: the source's buffer is never written.  The result is the list of the images poppy_bgr_denoise returns
+ * with the setting off; each image's filter chain still runs once (poppy_hip_chain_counts does not change).  Bad arguments: refused here, as above, and
+ * the setting stays as it was.  The setting is read when a list call starts.
+ * Where it does not apply: poppy_hip_morph, the pair loaders (poppy_hip_pair_begin and the rest), the pools and the multi-GPU entry points take their
+ * images as they are — the reference's morph never denoises, its run loop does. */
+int poppy_hip_set_denoise(poppy_hip_ctx* ctx, float hs, int template_window, int search_window);
+int poppy_hip_get_denoise(poppy_hip_ctx* ctx, float* hs, int* template_window, int* search_window);
 /* copies of the resident point sets after pair_begin / pair_load (n x 2 floats each); n via *n_points */
 int poppy_hip_pair_points(poppy_hip_ctx* ctx, float* points1, float* points2, int max_points, int* n_points);
 
@@ -1084,6 +1145,8 @@ int poppy_hip_pool_mask_rider(poppy_hip_pool* pool);
  *                   the canvas by blur_margin's rule on the device, the bytes poppy_hip_blur_margin(img, canvas) returns (src/util.cpp:574-602).
  *                   An image whose margin strips would leave the canvas (poppy_blur_margin_rects), or a canvas of more rows than
  *                   poppy_hip_blur_margin_max_rows: POPPY_E_UNSUPPORTED when that image arrives, before it is padded; the context stays usable.
+ *   denoise         poppy_hip_set_denoise with hs > 0 beforehand (the CLI's --denoise, :172): every image is denoised on the device as it arrives, at
+ *                   its own size and in front of the canvas padding, into the context's buffers; the setting is read when the call starts.
  *   phase           < 0: default chained mode; 0 < phase < 1: one phase-mode frame per pair.  0 or 1 with more than two images:
  *                   POPPY_E_UNSUPPORTED (poppy::morph returns before it sets corrected2, :54-70); with two images as poppy_hip_morph.
  *   write           (pair, frame) in order, on the calling thread; NULL keeps the frames on the device.

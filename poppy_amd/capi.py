@@ -74,6 +74,8 @@ SYMBOLS = [
     "poppy_hip_unsharp_frame", "poppy_hip_align_scores",
     "poppy_ransac_fundamental", "poppy_hip_ransac_fundamental", "poppy_hip_pair_begin_descriptors_ransac", "poppy_hip_pair_fundamental",
     "poppy_blur_margin_rects", "poppy_blur_margin_taps", "poppy_hip_blur_margin_max_rows",
+    "poppy_denoise_weights", "poppy_bgr_denoise", "poppy_denoise_tile", "poppy_denoise_table_bound",
+    "poppy_hip_denoise", "poppy_hip_denoise_device", "poppy_hip_set_denoise", "poppy_hip_get_denoise",
 ]
 
 
@@ -160,6 +162,14 @@ def lib():
         L.poppy_blur_margin_rects.argtypes = [i, i, i, i, vp, vp]
         L.poppy_blur_margin_taps.argtypes = [vp]
         L.poppy_hip_blur_margin_max_rows.argtypes = [vp, vp]
+        L.poppy_denoise_weights.argtypes = [C.c_float, i, i, vp, i, vp, vp, vp, vp]
+        L.poppy_bgr_denoise.argtypes = [vp, sz, i, i, C.c_float, i, i, vp, sz]
+        L.poppy_denoise_tile.argtypes = [vp, vp]
+        L.poppy_denoise_table_bound.argtypes = [vp]
+        L.poppy_hip_denoise.argtypes = [vp, vp, sz, i, i, C.c_float, i, i, vp, sz]
+        L.poppy_hip_denoise_device.argtypes = [vp, vp, vp, i, i, C.c_float, i, i]
+        L.poppy_hip_set_denoise.argtypes = [vp, C.c_float, i, i]
+        L.poppy_hip_get_denoise.argtypes = [vp, vp, vp, vp]
         L.poppy_hip_orb_describe.argtypes = [vp, vp, sz, i, i, vp, i, vp]
         L.poppy_hip_hamming_match.argtypes = [vp, vp, i, vp, i, vp, vp]
         L.poppy_match_points.argtypes = [vp, vp, i, i, i, d, vp, vp, vp, vp]
@@ -1236,6 +1246,46 @@ def blur_margin_taps():
     return taps
 
 
+DENOISE_MAX_TABLE = 3 * 255 * 255 + 1      # no weight table is longer
+
+
+def denoise_weights(hs, tw=7, sw=21):
+    """Host-only: the weight table of the non-local-means denoise and its constants (poppy_denoise_weights, the one place they are formed):
+    dict(table uint32 [n], n, L, fpm, shift).  A refusal raises PoppyError with the status."""
+    t = np.zeros(DENOISE_MAX_TABLE, np.uint32)
+    n, last, shift, fpm = C.c_int(0), C.c_int(0), C.c_int(0), C.c_uint32(0)
+    rc = lib().poppy_denoise_weights(float(hs), int(tw), int(sw), _p(t), len(t), C.byref(n), C.byref(last), C.byref(fpm), C.byref(shift))
+    if rc:
+        raise PoppyError(f"poppy_denoise_weights: {rc}")
+    return dict(table=t[:n.value].copy(), n=n.value, L=last.value, fpm=fpm.value, shift=shift.value)
+
+
+def _denoise(call, bgr, hs, tw, sw, row_pad, dst_pad, chk=None):
+    return _scaled_frame(call, "bgr_denoise", bgr, lambda w, h: (w, h), (float(hs), int(tw), int(sw)), row_pad, dst_pad, chk)
+
+
+def bgr_denoise(bgr, hs, tw=7, sw=21, row_pad=0, dst_pad=0):
+    """Host-only: an HxWx3 BGR image denoised by non-local means (poppy_bgr_denoise, the host statement that defines Context.denoise's rule).  row_pad /
+    dst_pad: the image is handed over / taken back with that many extra bytes per row."""
+    return _denoise(lib().poppy_bgr_denoise, bgr, hs, tw, sw, row_pad, dst_pad)
+
+
+def denoise_tile():
+    """Host-only: (width, height) of the output tile of the denoise kernel's workgroups."""
+    w, h = C.c_int(0), C.c_int(0)
+    if lib().poppy_denoise_tile(C.byref(w), C.byref(h)):
+        raise PoppyError("poppy_denoise_tile")
+    return w.value, h.value
+
+
+def denoise_table_bound():
+    """Host-only: the longest non-zero table prefix L the denoise kernel stages in LDS; a longer one is read from global memory."""
+    n = C.c_int(0)
+    if lib().poppy_denoise_table_bound(C.byref(n)):
+        raise PoppyError("poppy_denoise_table_bound")
+    return n.value
+
+
 def dft_plan(n):
     """Host-only: (factors, itab, wave) of the length-n transform plan."""
     f = np.zeros(34, np.int32); nf = C.c_int(0); itab = np.zeros(n, np.int32); wave = np.zeros((n, 2), np.float32)
@@ -1696,6 +1746,25 @@ class Context:
         if dst_pad and not (full[:, union_w * 3:] == 0xA5).all():
             raise PoppyError("blur_margin wrote into the destination's row padding")
         return np.ascontiguousarray(full[:, :union_w * 3]).reshape(union_h, union_w, 3)
+
+    def denoise(self, bgr, hs, tw=7, sw=21, row_pad=0, dst_pad=0):
+        """capi.bgr_denoise on this context's GPU (poppy_hip_denoise: upload, the kernel, download): the same bytes."""
+        return _denoise(lambda *args: lib().poppy_hip_denoise(self.h, *args), bgr, hs, tw, sw, row_pad, dst_pad, self._chk)
+
+    def denoise_device(self, d_src, d_dst, w, h, hs, tw=7, sw=21):
+        """Device image (pointer, tight rows) -> device image, queued on the context's stream (poppy_hip_denoise_device); sync() before reading d_dst."""
+        self._chk(lib().poppy_hip_denoise_device(self.h, d_src, d_dst, int(w), int(h), float(hs), int(tw), int(sw)), "denoise_device")
+
+    def set_denoise(self, hs, tw=7, sw=21):
+        """The CLI's --denoise for morph_list (poppy_hip_set_denoise): every image of a list is denoised on the GPU as it arrives, at its own size and in
+        front of the canvas padding.  hs = 0 (the default): off.  morph, the pair loaders, pools and the multi-GPU entry points are not affected."""
+        self._chk(lib().poppy_hip_set_denoise(self.h, float(hs), int(tw), int(sw)), "set_denoise")
+
+    def get_denoise(self):
+        """(hs, tw, sw) of set_denoise; hs 0.0: off."""
+        hs, tw, sw = C.c_float(0), C.c_int(0), C.c_int(0)
+        self._chk(lib().poppy_hip_get_denoise(self.h, C.byref(hs), C.byref(tw), C.byref(sw)), "get_denoise")
+        return hs.value, tw.value, sw.value
 
     def blur_margin_max_rows(self):
         """The most canvas rows blur_margin takes on this context's device."""

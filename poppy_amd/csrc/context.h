@@ -7,7 +7,7 @@
 //   writer_image.cpp  the frames that no slot renders and the stand-alone conversion entry points (writer_image.h);  writer_buffers.h: the grow-only device buffer and the call-scoped holder
 //   pair_begin.cpp    the pair set-up from raw images (pair_begin.h): its schedule and stages, the chain threads (setup_latch.h), the pair_begin entry points
 //   pair_setup.cpp    the stage-by-stage entry points of the once-per-pair half: pre-ORB chain, ORB, matching, the RANSAC filter (ransac_fundamental.h), auto-align, tables, margins
-//   image_list.cpp    poppy_hip_morph_list
+//   image_list.cpp    poppy_hip_morph_list;  denoise_hip.cpp: the non-local-means denoise on a context (denoise.h, denoise.cpp: its host statement and weight table)
 //   rccl_comm.cpp     the RCCL loader and a context's communicator (rccl_comm.h, comm_guard.h): the two collectives, the abort, the pair state's broadcast, export and import
 //   sharded_setup.cpp the pair set-up spread over ranks, as named stages (shard_protocol.h: roles and the keypoint hand-off; local_hub.h: the in-process transport)
 //   morph_sharded.cpp one job over N devices;  pool.cpp: pools of contexts, the set-up gate, batches of pairs
@@ -184,6 +184,13 @@ struct poppy_hip_ctx {
     struct LastFundamental { bool valid = false; double f[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int n_matches = 0, n_inliers = 0, best = -1; } fundamental;
     DeviceBuffer ransac_scratch;                    // the filter's points, models and counts on the device (kernels_ransac.hip: ransac_counts_device)
     int max_grid_y = 65535;                         // the device's maxGridSize[1]: the rows one launch_strip_blur takes (blur_margin_rows_fit)
+    // the non-local-means denoise (denoise_hip.cpp): the weight table's non-zero prefix on the device with the parameters it was formed for, the staging
+    // images of the host-facing entry point and of the list's host images, the list's two denoised images, and poppy_hip_set_denoise's setting (hs 0: off)
+    struct Denoise {
+        DeviceBuffer table, stage, list_img[2];
+        float table_hs = 0; int table_tw = 0, table_sw = 0, L = 0, shift = 0;
+        float hs = 0; int tw = 0, sw = 0;
+    } denoise;
 };
 
 // ---- packed pair state (see poppy_hip_ctx::arena) -------------------------------------------------------------------------
@@ -260,6 +267,9 @@ bool blur_margin_rows_fit(const poppy_hip_ctx* c, int UH);
 constexpr const char* kBlurMarginOffCanvasMsg = "blur_margin: a margin strip leaves the canvas (an image about 99 times as high as wide, or as wide as high; the reference throws there)";
 constexpr const char* kBlurMarginRowsMsg = "blur_margin: the canvas has more rows than the device's grid takes in y";
 hipError_t blur_margin_strips(const uint8_t* canvas, uint8_t* out, uint32_t* tmp, const int* d_taps, int W, int H, int UW, int UH, hipStream_t s);
+
+// the denoise (denoise_hip.cpp): d_src (rows of `stride` bytes) -> d_dst (tight), queued on the context's stream; the refusals are the caller's
+int denoise_queue(poppy_hip_ctx* c, const uint8_t* d_src, size_t stride, uint8_t* d_dst, int w, int h, float hs, int tw, int sw);
 
 inline ForegroundFilter& chain_fg(poppy_hip_ctx* c, int slot) { return slot ? c->foreground_b : c->foreground; }
 inline OrbDetector& chain_orb(poppy_hip_ctx* c, int slot) { return slot ? c->orb_b : c->orb; }

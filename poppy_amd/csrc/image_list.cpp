@@ -1,7 +1,8 @@
 // image_list.cpp — poppy_hip_morph_list: the reference CLI's loop over an image list (src/poppy.cpp:266-328) in one call.  Pair k is
 // (image k, image k + 1), where image k is what poppy::morph handed back as corrected2 for pair k - 1 (:326).  Pair 0 is set up with
 // pair_begin, every later pair with pair_begin_next: the second image's filter chain of one pair is the first image's of the next, and
-// it runs once.  Optional canvas: every image is padded on the device by blur_margin's rule (src/util.cpp:574-602) before its pair.
+// it runs once.  Optional canvas: every image is padded on the device by blur_margin's rule (src/util.cpp:574-602) before its pair.  Optional denoise
+// (poppy_hip_set_denoise, the CLI's --denoise at :172): every image goes through the non-local-means kernel first, at its own size.
 #include "context.h"
 
 namespace {
@@ -47,6 +48,20 @@ int list_pad(poppy_hip_ctx* c, const ListImage& img, int UW, int UH, uint8_t* ou
     return POPPY_OK;
 }
 
+// img -> out (its own size, tight rows, device): the bytes poppy_hip_denoise(img) returns, queued on the context's stream.  A host image goes through the
+// context's staging image; a device image is read where it is and never written.
+int list_denoise(poppy_hip_ctx* c, const ListImage& img, float hs, int tw, int sw, DeviceBuffer& out) {
+    const size_t B = (size_t)img.w * img.h * 3;
+    HIPCHK(c, out.reserve(B + 16, c->stream));
+    const uint8_t* d_src = img.p; size_t stride = img.stride;
+    if (!img.dev) {
+        HIPCHK(c, c->denoise.stage.reserve(B, c->stream));
+        HIPCHK(c, copy_rows_async(c->denoise.stage.p, (size_t)img.w * 3, img.p, img.stride, (size_t)img.w * 3, img.h, hipMemcpyHostToDevice, c->stream));
+        d_src = c->denoise.stage.p; stride = (size_t)img.w * 3;
+    }
+    return denoise_queue(c, d_src, stride, out.p, img.w, img.h, hs, tw, sw);
+}
+
 }  // namespace
 
 extern "C" {
@@ -63,6 +78,7 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
     const bool canvas = UW > 0;
     const int N = c->cfg.number_of_frames;
     int W = UW, H = UH;
+    struct { float hs; int tw, sw; } const dn{c->denoise.hs, c->denoise.tw, c->denoise.sw};      // poppy_hip_set_denoise, as it stands when the call starts
     auto fetch = [&](int k, ListImage& img) -> int {            // image k from the source, checked against the list's geometry
         const uint8_t* p = nullptr; size_t stride = 0; int w = 0, h = 0;
         if (source(user, k, &p, &stride, &w, &h) != 0) return fail(c, POPPY_E_ARG, "morph_list: the image source failed");
@@ -76,7 +92,11 @@ int poppy_hip_morph_list(poppy_hip_ctx* c, int n, int UW, int UH, double phase, 
             else if (w != W || h != H) return fail(c, POPPY_E_ARG, "morph_list: images of different sizes and no canvas (poppy::morph takes one size)");
         }
         img = ListImage{p, stride, w, h, inputs_on_device != 0};
-        if (canvas) {                                          // padded into the context's image buffer k mod 2
+        if (dn.hs != 0) {                                      // denoised at its own size, in front of the padding (src/poppy.cpp:172 before :239)
+            const int rc = list_denoise(c, img, dn.hs, dn.tw, dn.sw, c->denoise.list_img[k & 1]); if (rc) return rc;
+            img = ListImage{c->denoise.list_img[k & 1].p, (size_t)w * 3, w, h, true};
+        }
+        if (canvas) {                                         // padded into the context's image buffer k mod 2
             int rc = list_scratch(c, UW, UH); if (rc) return rc;
             rc = list_pad(c, img, UW, UH, c->list_img[k & 1]); if (rc) return rc;
             img = ListImage{c->list_img[k & 1], (size_t)UW * 3, UW, UH, true};

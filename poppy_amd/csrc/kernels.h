@@ -215,6 +215,10 @@ void launch_unsharp_stream(const float* src, uint8_t* out_u8, float* out_f32_or_
 // u8 cross-dissolve fallback (src/poppy.hpp:129)
 void launch_dissolve(const uint8_t* a, const uint8_t* b, uint8_t* dst, size_t n, float wa, float wb, hipStream_t s);
 
+// non-local-means denoise (kernels_denoise.hip; the rule: include/poppy_hip.h, poppy_bgr_denoise): src (rows of `stride` bytes) -> dst (tight rows), both on
+// the device, with the first L entries of the weight table poppy_denoise_weights formed for (hs, tw, sw) at d_table and that table's shift
+hipError_t launch_denoise(const uint8_t* src, size_t stride, uint8_t* dst, int w, int h, int tw, int sw, int shift, int L, const uint32_t* d_table, hipStream_t s);
+
 // tight u8x3 BGR -> I420 (kernels_frame_format.hip; the format: include/poppy_hip.h, POPPY_FRAME_I420).  `done` (optional) rides on the last dispatch.
 void launch_bgr_to_i420(const uint8_t* src, uint8_t* dst, int w, int h, hipStream_t s, hipEvent_t done = nullptr);
 

@@ -135,6 +135,7 @@ void poppy_hip_destroy(poppy_hip_ctx* c) {
     free_context_format(c);
     c->aligner.release();
     c->ransac_scratch.release();
+    for (DeviceBuffer* b : {&c->denoise.table, &c->denoise.stage, &c->denoise.list_img[0], &c->denoise.list_img[1]}) b->release();
     (void)hipStreamDestroy(c->copy_stream);
     (void)hipStreamDestroy(c->stream);
     delete c;
