@@ -382,6 +382,42 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * poppy_hip_set_frame_size as the host statement at the writer's geometry (the tables are taken over the SCALED frames), and stay BGR wherever JPEG stays BGR
  * (poppy_hip_morph_sharded, poppy_hip_morph_pairs).
  *
+ * JPEG byte budget: POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames of at most B bytes each, for a stream with a bitrate cap, a slot in a ring or a file that must
+ * stay under a size.  poppy_hip_set_jpeg_budget(ctx, B) sets it, 0 (the default) is off and leaves every frame, byte and launch as it is without; with B > 0 the
+ * context's quality (poppy_hip_set_jpeg_quality) is the HIGHEST quality a frame may have, and every frame is coded at the quality this rule picks for it:
+ *   Size.  size(q) is the length of the JFIF file of the frame's POPPY_FRAME_JPEG (JPEG444) frame at quality q: `total` - 4, the bytes POPPY_SINK_MJPEG writes.
+ *   Search.  With qmax the context's quality:
+ *         if size(qmax) <= B: the quality is qmax
+ *         lo = 0; hi = qmax                  (hi is known not to fit; lo = 0: nothing known to fit)
+ *         while hi - lo > 1:  mid = (lo + hi) >> 1;  if size(mid) <= B: lo = mid, else: hi = mid
+ *         the quality is max(lo, 1)
+ *      At most 1 + ceil(log2(qmax)) qualities are asked about, 8 at qmax = 100.  The search IS the rule, not "the highest quality that fits": size is not monotone
+ *      in q on small frames (an 8 x 8 frame of noise has qualities whose file is shorter than the quality below's), the two disagree there, and a rule that needs
+ *      all 100 sizes costs 100 measurements where this one costs 8.  On frames of 40 x 24 pixels of noise and more, and on a morph's frames, they coincide.
+ *      poppy_jpeg_budget_pick(sizes, qmax, B) is the search alone on a table sizes[1..qmax] (entry 0 is not read): the quality, or POPPY_E_ARG for a null table,
+ *      qmax outside 1..100 or B = 0.
+ *   Output.  The frame is byte for byte the POPPY_FRAME_JPEG (JPEG444) frame of the same planes at the picked quality: the header with that quality's DQT, the
+ *      layout, the capacity, the smallest frame and stride 0 are the format's.  poppy_jpeg_frame_quality(frame) reads the quality back: the largest q in 1..100
+ *      whose two tables are the frame's DQT entries, 0 if none is or the frame is not one of this library's JPEG frames (bytes 4, 5 not FF D8, no DQT at the fixed
+ *      offset); it serves all six JPEG formats.
+ *   No memory between frames.  A frame is a pure function of (planes, qmax, B).
+ *   When nothing fits.  If not even quality 1 fits, the frame is the quality-1 frame and exceeds the budget: a frame is always produced, and the caller sees the
+ *      overshoot from `total`.
+ * poppy_i420_to_jpeg_budget_frame and poppy_i444_to_jpeg_budget_frame are the host statements, poppy_bgr_to_jpeg_budget_frame and
+ * poppy_bgr_to_jpeg444_budget_frame the conversion followed by them: the fixed-quality functions' arguments with quality_max and budget in the quality's place, and
+ * quality_used (may be null), which receives the picked quality.  They refuse what the fixed-quality functions refuse, and a budget of 0 or above 2^32 - 1 with
+ * POPPY_E_ARG.  poppy_hip_i420_to_jpeg_budget_frame and poppy_hip_i444_to_jpeg_budget_frame run the search and the coder on the context's GPU on host planes
+ * (upload, the measuring and picking kernels, the two coding kernels, download of `total` bytes): the same bytes and quality; they need no resident pair, disturb
+ * none, and neither read nor change the context's own budget and quality.
+ * poppy_hip_set_jpeg_budget follows poppy_hip_set_jpeg_quality's contract: POPPY_E_ARG above 2^32 - 1, POPPY_E_STATE while a sequence is open, the context's
+ * frames are drained first, and on a refusal the setting stays as it was.  poppy_hip_get_jpeg_budget reads it.  The budget is applied by POPPY_FRAME_JPEG and
+ * POPPY_FRAME_JPEG444 only — wherever they apply: poppy_hip_morph, poppy_hip_morph_frames, poppy_hip_render_many, poppy_hip_render_phases,
+ * poppy_hip_morph_list and pools, the phase 0 / 1 and t == 0 / 1 copies and the POPPY_E_NOMATCH frames included, under poppy_hip_set_frame_scale and
+ * poppy_hip_set_frame_size on the frame at the writer's geometry.  The four formats on built tables (_OPT, _SEQ) have no budget form: a positive budget together
+ * with one of them is refused with POPPY_E_UNSUPPORTED by whichever of poppy_hip_set_frame_format and poppy_hip_set_jpeg_budget comes second, and the earlier
+ * setting stays.  The other formats ignore the budget as they ignore the quality.  poppy_hip_pool_set_jpeg_budget sets every context of a pool (POPPY_E_STATE
+ * with work submitted).  POPPY_SINK_MJPEG takes the frames as they are: every frame is a complete file, and the sink does not read DQT.
+ *
  * POPPY_FRAME_PNG: the frame coded on the GPU as one PNG file, LOSSLESS: the file decodes to exactly the frame's pixels, at 1.5 - 3 times fewer bytes than BGR on
  * photograph-like frames.  Its value is 1024, and POPPY_SINK_PNG is 1024; 1023 and 1025 stay unknown in both enums.  Layout, little-endian:
  *     bytes 0..3     total: the whole frame's length in bytes, these four included (poppy_png_frame_bytes reads it)
@@ -554,6 +590,16 @@ int poppy_hip_bgr_to_i444(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride,
 int poppy_i444_to_jpeg_frame(const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
 int poppy_bgr_to_jpeg444_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality, uint8_t* dst);
 int poppy_hip_i444_to_jpeg_frame(poppy_hip_ctx* ctx, const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
+int poppy_jpeg_budget_pick(const uint32_t* sizes, int quality_max, size_t budget);
+int poppy_jpeg_frame_quality(const uint8_t* frame);
+int poppy_i420_to_jpeg_budget_frame(const uint8_t* i420, int width, int height, int quality_max, size_t budget, uint8_t* dst, int* quality_used);
+int poppy_i444_to_jpeg_budget_frame(const uint8_t* i444, int width, int height, int quality_max, size_t budget, uint8_t* dst, int* quality_used);
+int poppy_bgr_to_jpeg_budget_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality_max, size_t budget, uint8_t* dst, int* quality_used);
+int poppy_bgr_to_jpeg444_budget_frame(const uint8_t* bgr, size_t stride, int width, int height, int quality_max, size_t budget, uint8_t* dst, int* quality_used);
+int poppy_hip_i420_to_jpeg_budget_frame(poppy_hip_ctx* ctx, const uint8_t* i420, int width, int height, int quality_max, size_t budget, uint8_t* dst, int* quality_used);
+int poppy_hip_i444_to_jpeg_budget_frame(poppy_hip_ctx* ctx, const uint8_t* i444, int width, int height, int quality_max, size_t budget, uint8_t* dst, int* quality_used);
+int poppy_hip_set_jpeg_budget(poppy_hip_ctx* ctx, size_t max_frame_bytes);
+int poppy_hip_get_jpeg_budget(poppy_hip_ctx* ctx, size_t* max_frame_bytes);
 int poppy_jpeg_optimal_table(const uint32_t counts[256], uint8_t bits[16], uint8_t vals[256], int* n_vals);
 int poppy_i420_to_jpeg_opt_frame(const uint8_t* i420, int width, int height, int quality, uint8_t* dst);
 int poppy_i444_to_jpeg_opt_frame(const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
@@ -1130,6 +1176,8 @@ int poppy_hip_pool_set_frame_scale(poppy_hip_pool* pool, int factor);
 int poppy_hip_pool_set_frame_size(poppy_hip_pool* pool, int ow, int oh);
 /* poppy_hip_set_jpeg_quality on every context of the pool; POPPY_E_ARG outside 1..100, POPPY_E_STATE as for the format. */
 int poppy_hip_pool_set_jpeg_quality(poppy_hip_pool* pool, int quality);
+/* poppy_hip_set_jpeg_budget on every context of the pool; POPPY_E_ARG above 2^32 - 1, POPPY_E_STATE as for the format. */
+int poppy_hip_pool_set_jpeg_budget(poppy_hip_pool* pool, size_t max_frame_bytes);
 /* poppy_hip_mask_rider of the pool's contexts (they share settings and geometry) */
 int poppy_hip_pool_mask_rider(poppy_hip_pool* pool);
 /* The CLI's loop over an image list (src/poppy.cpp:266-328) on ONE context: pair k = (image k, image k + 1), where image k of pair k > 0 is

@@ -59,6 +59,9 @@ SYMBOLS = [
     "poppy_gif_frame_bytes", "poppy_pal8_to_gif_frame", "poppy_bgr_to_gif_frame", "poppy_hip_pal8_to_gif_frame",
     "poppy_bgr_frames_to_gif_frames", "poppy_hip_bgr_frames_to_gif_frames",
     "poppy_jpeg_frame_bytes", "poppy_i420_to_jpeg_frame", "poppy_bgr_to_jpeg_frame", "poppy_hip_i420_to_jpeg_frame", "poppy_hip_set_jpeg_quality", "poppy_hip_pool_set_jpeg_quality",
+    "poppy_jpeg_budget_pick", "poppy_jpeg_frame_quality", "poppy_i420_to_jpeg_budget_frame", "poppy_i444_to_jpeg_budget_frame", "poppy_bgr_to_jpeg_budget_frame",
+    "poppy_bgr_to_jpeg444_budget_frame", "poppy_hip_i420_to_jpeg_budget_frame", "poppy_hip_i444_to_jpeg_budget_frame", "poppy_hip_set_jpeg_budget",
+    "poppy_hip_get_jpeg_budget", "poppy_hip_pool_set_jpeg_budget",
     "poppy_bgr_to_i444", "poppy_hip_bgr_to_i444", "poppy_i444_to_jpeg_frame", "poppy_bgr_to_jpeg444_frame", "poppy_hip_i444_to_jpeg_frame",
     "poppy_jpeg_optimal_table", "poppy_i420_to_jpeg_opt_frame", "poppy_i444_to_jpeg_opt_frame", "poppy_bgr_to_jpeg_opt_frame", "poppy_bgr_to_jpeg444_opt_frame",
     "poppy_hip_i420_to_jpeg_opt_frame", "poppy_hip_i444_to_jpeg_opt_frame", "poppy_hip_jpeg_optimal_table",
@@ -243,6 +246,17 @@ def lib():
         L.poppy_bgr_to_jpeg444_frame.argtypes = [vp, sz, i, i, i, vp]
         L.poppy_hip_i444_to_jpeg_frame.argtypes = [vp, vp, i, i, i, vp]
         L.poppy_hip_pool_set_jpeg_quality.argtypes = [vp, i]
+        L.poppy_jpeg_budget_pick.argtypes = [vp, i, sz]
+        L.poppy_jpeg_frame_quality.argtypes = [vp]
+        L.poppy_i420_to_jpeg_budget_frame.argtypes = [vp, i, i, i, sz, vp, vp]
+        L.poppy_i444_to_jpeg_budget_frame.argtypes = [vp, i, i, i, sz, vp, vp]
+        L.poppy_bgr_to_jpeg_budget_frame.argtypes = [vp, sz, i, i, i, sz, vp, vp]
+        L.poppy_bgr_to_jpeg444_budget_frame.argtypes = [vp, sz, i, i, i, sz, vp, vp]
+        L.poppy_hip_i420_to_jpeg_budget_frame.argtypes = [vp, vp, i, i, i, sz, vp, vp]
+        L.poppy_hip_i444_to_jpeg_budget_frame.argtypes = [vp, vp, i, i, i, sz, vp, vp]
+        L.poppy_hip_set_jpeg_budget.argtypes = [vp, sz]
+        L.poppy_hip_get_jpeg_budget.argtypes = [vp, vp]
+        L.poppy_hip_pool_set_jpeg_budget.argtypes = [vp, sz]
         L.poppy_jpeg_optimal_table.argtypes = [vp, vp, vp, vp]
         L.poppy_hip_jpeg_optimal_table.argtypes = [vp, vp, vp, vp, vp]
         L.poppy_i420_to_jpeg_opt_frame.argtypes = [vp, i, i, i, vp]
@@ -446,6 +460,60 @@ def _planes_to_jpeg(call, fmt, planes, w, h, quality, chk=None):
 def i420_to_jpeg_frame(i420, w, h, quality=JPEG_QUALITY_DEFAULT):
     """Host-only: the FRAME_JPEG frame of a flat I420 frame (poppy_i420_to_jpeg_frame): `total`, then one baseline JFIF file; a flat uint8 array of its own length."""
     return _planes_to_jpeg(lib().poppy_i420_to_jpeg_frame, FRAME_JPEG, i420, w, h, quality)
+
+
+def jpeg_budget_pick(sizes, quality_max, budget):
+    """Host-only: the quality the byte budget's search picks on a table of file sizes, sizes[q] for q = 1..quality_max (entry 0 is not read)
+    (poppy_jpeg_budget_pick); PoppyError with the status on a refusal."""
+    a = None if sizes is None else np.ascontiguousarray(sizes, np.uint32)
+    if a is not None and a.size <= int(quality_max) and 1 <= int(quality_max) <= 100:
+        raise PoppyError("jpeg_budget_pick: the table has quality_max + 1 entries")
+    rc = lib().poppy_jpeg_budget_pick(None if a is None else _p(a), int(quality_max), int(budget))
+    if rc < 0:
+        raise PoppyError(f"poppy_jpeg_budget_pick: {rc}")
+    return rc
+
+
+def jpeg_frame_quality(frame):
+    """Host-only: the quality whose tables a JPEG frame of any of the six formats carries in its DQT, the largest of equals (poppy_jpeg_frame_quality); 0 if none
+    does or the frame is no such frame."""
+    a = np.ascontiguousarray(frame, np.uint8).ravel()
+    if a.size < 4 or a.size < coded_frame_bytes(a, "jpeg"):
+        return 0
+    return lib().poppy_jpeg_frame_quality(_p(a))
+
+
+def _planes_to_jpeg_budget(call, fmt, planes, w, h, quality_max, budget, chk=None):
+    """The body of i420_to_jpeg_budget_frame (fmt FRAME_JPEG) and i444_to_jpeg_budget_frame (FRAME_JPEG444), on the host or a context: (frame, quality used)."""
+    name, size, says = ("i444", 3 * w * h, "3 * w * h") if fmt == FRAME_JPEG444 else ("i420", frame_bytes(FRAME_I420, w, h), "w * h + 2 * cw * ch")
+    a = np.ascontiguousarray(planes, np.uint8).ravel()
+    if w > 0 and h > 0 and a.size != size:
+        raise PoppyError(f"{name}_to_jpeg_budget_frame: an {name.upper()} frame has {says} bytes")
+    used = C.c_int(0)
+    frame = _coded_frame(lambda dst: call(_p(a), int(w), int(h), int(quality_max), int(budget), dst, C.byref(used)), f"{name}_to_jpeg_budget_frame", w, h, fmt, chk)
+    return frame, used.value
+
+
+def i420_to_jpeg_budget_frame(i420, w, h, quality_max, budget):
+    """Host-only: (the FRAME_JPEG frame of a flat I420 frame at the quality the byte budget's search picks at or below quality_max, that quality)
+    (poppy_i420_to_jpeg_budget_frame)."""
+    return _planes_to_jpeg_budget(lib().poppy_i420_to_jpeg_budget_frame, FRAME_JPEG, i420, w, h, quality_max, budget)
+
+
+def i444_to_jpeg_budget_frame(i444, w, h, quality_max, budget):
+    """Host-only: the same for FRAME_JPEG444 on flat I444 planes (poppy_i444_to_jpeg_budget_frame)."""
+    return _planes_to_jpeg_budget(lib().poppy_i444_to_jpeg_budget_frame, FRAME_JPEG444, i444, w, h, quality_max, budget)
+
+
+def bgr_to_jpeg_budget_frame(bgr, quality_max, budget, fmt=FRAME_JPEG):
+    """Host-only: (frame, quality used) of an HxWx3 BGR frame under a byte budget, fmt FRAME_JPEG (poppy_bgr_to_jpeg_budget_frame) or FRAME_JPEG444
+    (poppy_bgr_to_jpeg444_budget_frame)."""
+    a = np.ascontiguousarray(bgr, np.uint8)
+    h, w = a.shape[:2]
+    call = lib().poppy_bgr_to_jpeg444_budget_frame if fmt == FRAME_JPEG444 else lib().poppy_bgr_to_jpeg_budget_frame
+    used = C.c_int(0)
+    frame = _coded_frame(lambda dst: call(_p(a), w * 3, w, h, int(quality_max), int(budget), dst, C.byref(used)), "bgr_to_jpeg_budget_frame", w, h, fmt)
+    return frame, used.value
 
 
 def bgr_to_jpeg_frame(bgr, quality=JPEG_QUALITY_DEFAULT):
@@ -1131,6 +1199,13 @@ class Pool:
         if rc:
             raise PoppyError(f"poppy_hip_pool_set_jpeg_quality: {rc}")
 
+    def set_jpeg_budget(self, max_frame_bytes):
+        """The byte budget of the FRAME_JPEG and FRAME_JPEG444 frames of every context of the pool, 0 for none (poppy_hip_pool_set_jpeg_budget); PoppyError with
+        the status on a refusal or while submitted batches have not been waited for."""
+        rc = lib().poppy_hip_pool_set_jpeg_budget(self.h, int(max_frame_bytes))
+        if rc:
+            raise PoppyError(f"poppy_hip_pool_set_jpeg_budget: {rc}")
+
     def close(self):
         if self.h:
             lib().poppy_hip_pool_destroy(self.h)
@@ -1378,6 +1453,26 @@ class Context:
     def set_jpeg_quality(self, quality):
         """The quality, 1..100 (default JPEG_QUALITY_DEFAULT), of the FRAME_JPEG frames this context hands to writers (poppy_hip_set_jpeg_quality)."""
         self._chk(lib().poppy_hip_set_jpeg_quality(self.h, int(quality)), "set_jpeg_quality")
+
+    def set_jpeg_budget(self, max_frame_bytes):
+        """The most bytes a FRAME_JPEG or FRAME_JPEG444 frame's file may have, 0 (the default) for none (poppy_hip_set_jpeg_budget): every frame is coded at the
+        quality the budget's search picks at or below set_jpeg_quality's."""
+        self._chk(lib().poppy_hip_set_jpeg_budget(self.h, int(max_frame_bytes)), "set_jpeg_budget")
+
+    def get_jpeg_budget(self):
+        """The context's byte budget (poppy_hip_get_jpeg_budget); 0: none."""
+        v = C.c_size_t(0)
+        self._chk(lib().poppy_hip_get_jpeg_budget(self.h, C.byref(v)), "get_jpeg_budget")
+        return v.value
+
+    def i420_to_jpeg_budget_frame(self, i420, w, h, quality_max, budget):
+        """(frame, quality used) of a flat I420 frame under a byte budget, searched and coded on this context's GPU (poppy_hip_i420_to_jpeg_budget_frame): what the
+        host's i420_to_jpeg_budget_frame gives."""
+        return _planes_to_jpeg_budget(lambda *args: lib().poppy_hip_i420_to_jpeg_budget_frame(self.h, *args), FRAME_JPEG, i420, w, h, quality_max, budget, self._chk)
+
+    def i444_to_jpeg_budget_frame(self, i444, w, h, quality_max, budget):
+        """The same for FRAME_JPEG444 on flat I444 planes (poppy_hip_i444_to_jpeg_budget_frame)."""
+        return _planes_to_jpeg_budget(lambda *args: lib().poppy_hip_i444_to_jpeg_budget_frame(self.h, *args), FRAME_JPEG444, i444, w, h, quality_max, budget, self._chk)
 
     def i420_to_jpeg_frame(self, i420, w, h, quality=JPEG_QUALITY_DEFAULT):
         """The FRAME_JPEG frame of a flat I420 frame, coded on this context's GPU (poppy_hip_i420_to_jpeg_frame: upload, the two kernels, download): the bytes

@@ -63,6 +63,7 @@ struct FrameSlot {
     hipEvent_t uploaded = nullptr;                  // the device copy is complete
     hipGraphExec_t body = nullptr;                  // pyrdown .. unsharp of this slot, captured once per pair geometry
     int body_format = POPPY_FRAME_BGR;              // ... with this format's conversion behind the unsharp (re-captured when that changes)
+    bool body_budget = false;                       // ... with the JPEG byte budget's search in front of the coder (poppy_hip_set_jpeg_budget: on and off differ in the launches)
     WriterGeom body_geom;                           // ... and this geometry's downscale or resize in front of it (frame_format.h: WriterGeom)
     SlotFormat fmt;                                 // the frame in the writer's format: buffers, side stream and event (frame_format.h)
     hipEvent_t downloaded = nullptr;                // completes when the last download of this slot's `out` towards the writer has read it
@@ -123,6 +124,8 @@ struct poppy_hip_ctx {
     int frame_format = POPPY_FRAME_BGR;             // of the frames handed to writers (poppy_hip_set_frame_format)
     int frame_scale = 1;                            // ... and the whole factor they are scaled down by first (poppy_hip_set_frame_scale; frame_format.h: writer_geom)
     int jpeg_quality = POPPY_JPEG_QUALITY_DEFAULT;  // ... and the quality of the frames of the four JPEG formats (poppy_hip_set_jpeg_quality)
+    size_t jpeg_budget = 0;                         // ... the most bytes a POPPY_FRAME_JPEG / JPEG444 frame's file may have (poppy_hip_set_jpeg_budget; 0: off), and what its search reads on
+    uint8_t* jpeg_budget_tables = nullptr;          // the device (frame_format.h: context_jpeg_budget)
     uint8_t* jpeg_tables = nullptr;                 // ... with its header and quantiser tables on the device (frame_format.h: ensure_jpeg_tables; rewritten in place when the quality changes)
     int frame_ow = 0, frame_oh = 0;                 // ... or the size they are resized to (poppy_hip_set_frame_size; 0, 0: none; never beside a scale above 1)
     DeviceBuffer scale_scratch;                     // the scaled BGR of the copies and fallback frames that no slot renders (writer_image.h: scale_into_scratch)

@@ -79,6 +79,31 @@ int ensure_jpeg_tables(poppy_hip_ctx* c) {
     return POPPY_OK;
 }
 
+bool budget_applies(const FormatTraits& t) { return t.coder == kCoderJpeg && !t.frame_tables; }
+constexpr const char* kBudgetFormatMsg = "a JPEG byte budget is set, and the OPT and SEQ forms of the JPEG formats have no budget form: poppy_hip_set_jpeg_budget(ctx, 0) or another format first";
+
+static int write_budget_params(poppy_hip_ctx* c, size_t budget, int quality) {
+    const JpegBudgetParams p{(uint32_t)budget, (uint32_t)quality};
+    HIPCHK(c, hipMemcpy(c->jpeg_budget_tables + kJpegBudgetTableBytes, &p, sizeof p, hipMemcpyHostToDevice));
+    return POPPY_OK;
+}
+int ensure_jpeg_budget_tables(poppy_hip_ctx* c) {
+    if (c->jpeg_budget_tables) return POPPY_OK;
+    std::vector<jpeg::QualityTables> all(100);
+    for (int q = 1; q <= 100; ++q) jpeg::fill_quality_tables(q, &all[(size_t)q - 1]);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMalloc((void**)&c->jpeg_budget_tables, kJpegBudgetTableBytes + 16));
+    HIPCHK(c, hipMemcpy(c->jpeg_budget_tables, all.data(), kJpegBudgetTableBytes, hipMemcpyHostToDevice));
+    return write_budget_params(c, c->jpeg_budget, c->jpeg_quality);
+}
+int context_jpeg_budget(poppy_hip_ctx* c, const FormatTraits& t, JpegBudget* out) {
+    *out = JpegBudget();
+    if (!c->jpeg_budget || !budget_applies(t)) return POPPY_OK;
+    { int rc = ensure_jpeg_budget_tables(c); if (rc) return rc; }
+    out->tables = c->jpeg_budget_tables; out->params = c->jpeg_budget_tables + kJpegBudgetTableBytes;
+    return POPPY_OK;
+}
+
 // the coded frame, the coder's scratch and the pinned length word of a slot: gone (the format they were sized for is another, or the pair's buffers go)
 static void free_slot_coded(SlotFormat& f) {
     for (uint8_t* b : {f.coded, f.coded_scratch}) if (b) (void)hipFree(b);
@@ -119,6 +144,7 @@ int alloc_slot_format(poppy_hip_ctx* c) {
         if (t.raster == kRasterPal8) { int rc = alloc_slot_side(c, f); if (rc) return rc; }
         if (t.slot_coder() == kCoderNone) continue;                 // (the slot's coded frame: GIF_SEQ codes from the store into the sequence's ring)
         if (t.coder == kCoderJpeg) { int rc = ensure_jpeg_tables(c); if (rc) return rc; f.jpeg_tables = c->jpeg_tables; }
+        { int rc = context_jpeg_budget(c, t, &f.jpeg_budget); if (rc) return rc; }
         if (f.coded_for != fmt) free_slot_coded(f);                 // (sized for another coded format; the frames are drained and the bodies of that format are captured again)
         f.coded_for = fmt;
         if (!f.coded) HIPCHK(c, hipMalloc((void**)&f.coded, frame_bytes(t, W, H) + 16));
@@ -159,8 +185,8 @@ void free_slot_format_ctx(SlotFormat& f) {
 }
 void free_context_format(poppy_hip_ctx* c) {
     for (DeviceBuffer* b : {&c->scale_scratch, &c->fmt_scratch, &c->seq.store, &c->seq.idx, &c->seq.coded}) b->release();
-    for (uint8_t* b : {c->fmt_scratch_tables, c->seq.tables, c->seq.jpeg, c->seq.png, c->jpeg_tables}) if (b) (void)hipFree(b);
-    c->jpeg_tables = nullptr;
+    for (uint8_t* b : {c->fmt_scratch_tables, c->seq.tables, c->seq.jpeg, c->seq.png, c->jpeg_tables, c->jpeg_budget_tables}) if (b) (void)hipFree(b);
+    c->jpeg_tables = c->jpeg_budget_tables = nullptr;
     if (c->seq.coded_total) (void)hipHostFree(c->seq.coded_total);
     c->fmt_scratch_tables = nullptr;
     c->seq = PaletteSeq();
@@ -198,7 +224,22 @@ static void enqueue_gif_coding(const uint8_t* pal8, uint8_t* scratch, uint8_t* f
 }
 
 // (opt: on per-frame tables — the counting pass and the table build in front, both on the coder's scratch, which the slot owns: frames in flight are coded side by side)
-static void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, jpeg::Sampling sm, bool opt, hipStream_t s, hipEvent_t done, Timer* tm) {
+// (budget: the search's steps in front, a fixed sequence of dispatches whatever the search finds, then the coder and the gather on the tables it picked)
+static void enqueue_jpeg_coding(const uint8_t* planes, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, jpeg::Sampling sm, bool opt, hipStream_t s, hipEvent_t done, Timer* tm,
+                                const JpegBudget& budget) {
+    if (budget) {
+        for (int step = 0; step < kJpegBudgetSteps; ++step) {
+            launch_jpeg_measure(planes, budget, scratch, step, W, H, sm, s);
+            if (tm) tm->mark("jpeg_measure");
+            launch_jpeg_pick(budget, scratch, step, W, H, sm, s);
+            if (tm) tm->mark("jpeg_pick");
+        }
+        launch_jpeg_code_picked(planes, budget, scratch, W, H, sm, s);
+        if (tm) tm->mark("jpeg_code");
+        launch_jpeg_pack_picked(budget, scratch, frame, (uint32_t*)total_dev, W, H, sm, s, done);
+        if (tm) tm->mark("jpeg_pack");
+        return;
+    }
     if (opt) {
         launch_jpeg_count(planes, tables, scratch, W, H, sm, s);
         if (tm) tm->mark("jpeg_count");
@@ -226,9 +267,10 @@ static void enqueue_png_coding(int variant, const uint8_t* bgr, uint8_t* scratch
     if (tm) tm->mark("png_finish");
 }
 
-void enqueue_coding(const FormatTraits& t, const uint8_t* src, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm) {
+void enqueue_coding(const FormatTraits& t, const uint8_t* src, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm,
+                    const JpegBudget& budget) {
     if (t.coder == kCoderGif) enqueue_gif_coding(src, scratch, frame, total_dev, W, H, s, done, tm);
-    else if (t.coder == kCoderJpeg) enqueue_jpeg_coding(src, tables, scratch, frame, total_dev, W, H, t.sampling(), t.frame_tables, s, done, tm);
+    else if (t.coder == kCoderJpeg) enqueue_jpeg_coding(src, tables, scratch, frame, total_dev, W, H, t.sampling(), t.frame_tables, s, done, tm, budget_applies(t) ? budget : JpegBudget());
     else if (t.coder == kCoderPng) enqueue_png_coding(t.variant, src, scratch, frame, total_dev, W, H, s, done, tm);
 }
 
@@ -258,7 +300,7 @@ void enqueue_conversion(int fmt, const WriterGeom& g, const uint8_t* src_bgr, in
     }
     const uint8_t* src = src_bgr;                                  // what the coder reads: the raster form, or (PNG) the BGR frame itself
     if (raster != kRasterNone) src = enqueue_raster(raster, src_bgr, W, H, b, s, codes ? nullptr : done, tm);
-    if (codes) enqueue_coding(t, src, b.jpeg_tables, b.coded_scratch, b.coded, b.coded_total_dev, W, H, s, done, tm);
+    if (codes) enqueue_coding(t, src, b.jpeg_tables, b.coded_scratch, b.coded, b.coded_total_dev, W, H, s, done, tm, b.jpeg_budget);
 }
 
 extern "C" {
@@ -269,6 +311,7 @@ int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = drain_frames(c); if (rc) return rc; }
     if (c->c1) if (const char* why = writer_refuses(c, format, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    if (c->jpeg_budget && format_traits(format)->coder == kCoderJpeg && !budget_applies(*format_traits(format))) return fail(c, POPPY_E_UNSUPPORTED, kBudgetFormatMsg);
     c->frame_format = format;
     return c->c1 ? alloc_slot_format(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
 }
@@ -287,7 +330,35 @@ int poppy_hip_set_jpeg_quality(poppy_hip_ctx* c, int quality) {
         jpeg::fill_quality_tables(quality, &t);
         HIPCHK(c, hipMemcpy(c->jpeg_tables, &t, sizeof t, hipMemcpyHostToDevice));
     }
+    if (c->jpeg_budget_tables) { int rc = write_budget_params(c, c->jpeg_budget, quality); if (rc) return rc; }      // (the search's highest quality)
     c->jpeg_quality = quality;
+    return POPPY_OK;
+}
+
+// The budget is two words that the search's kernels read, at an address that stays: rewritten once nothing reads them.  On and off differ in the dispatches of a
+// frame; a slot's captured body records which of the two it holds (FrameSlot::body_budget) and is captured again when the next frame wants the other, whatever
+// happened to the format in between (frame_render.cpp: prepare_slot).  Between two positive budgets the bodies stay.
+int poppy_hip_set_jpeg_budget(poppy_hip_ctx* c, size_t max_frame_bytes) {
+    if (!c) return POPPY_E_ARG;
+    if (max_frame_bytes > 0xffffffffull) return fail(c, POPPY_E_ARG, "the JPEG byte budget is at most 2^32 - 1 bytes, or 0 for none");
+    if (c->seq.open) return fail(c, POPPY_E_STATE, "a sequence is open on this context");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = drain_frames(c); if (rc) return rc; }
+    const FormatTraits& t = *format_traits(c->frame_format);
+    if (max_frame_bytes && t.coder == kCoderJpeg && !budget_applies(t)) return fail(c, POPPY_E_UNSUPPORTED, kBudgetFormatMsg);
+    if (max_frame_bytes == c->jpeg_budget) return POPPY_OK;
+    if (c->jpeg_budget_tables) { int rc = write_budget_params(c, max_frame_bytes, c->jpeg_quality); if (rc) return rc; }
+    c->jpeg_budget = max_frame_bytes;
+    for (FrameSlot& f : c->slots) {
+        int rc = context_jpeg_budget(c, t, &f.fmt.jpeg_budget); if (rc) return rc;
+    }
+    return POPPY_OK;
+}
+
+int poppy_hip_get_jpeg_budget(poppy_hip_ctx* c, size_t* max_frame_bytes) {
+    if (!c) return POPPY_E_ARG;
+    if (!max_frame_bytes) return fail(c, POPPY_E_ARG, "bad arguments");
+    *max_frame_bytes = c->jpeg_budget;
     return POPPY_OK;
 }
 

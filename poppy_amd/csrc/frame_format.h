@@ -5,6 +5,7 @@
 #include "../../include/poppy_hip.h"
 #include <hip/hip_runtime.h>
 #include "frame_limits.h"
+#include "kernels.h"
 
 struct poppy_hip_ctx; struct FrameSlot; struct Timer;
 
@@ -47,6 +48,7 @@ struct SlotFormat {
     void* coded_total_dev = nullptr;      // are sized by coded_for, the format they were allocated under, and allocated again when the context's coded format is another
     int coded_for = POPPY_FRAME_BGR;
     const void* jpeg_tables = nullptr;    // the JPEG coder: the context's tables for its quality (ensure_jpeg_tables; the context's to free)
+    poppy_hip::JpegBudget jpeg_budget;    // ... and, with a byte budget set (poppy_hip_set_jpeg_budget), the context's tables of all qualities and the budget's words (context_jpeg_budget); empty: off
     hipStream_t fmt_stream = nullptr;     // chained PAL8 / PAL8_SEQ frames: the conversion's side stream (the chain goes on from the unsharp: enqueue_body)
     hipEvent_t bgr_done = nullptr;        // ... and the event that rides on that unsharp
 };
@@ -70,10 +72,19 @@ const uint8_t* enqueue_raster(FrameRaster raster, const uint8_t* src_bgr, int W,
 // total_dev (null: none); `done` rides on the last dispatch.  GIF: two dispatches (marks gif_lzw, gif_pack).  JPEG: two (jpeg_code, jpeg_pack), on per-frame tables four (jpeg_count, jpeg_tables in front), in the record's
 // sampling at the quality that `tables` (device memory, kernels.h: kJpegTableBytes) name.  PNG: the six of kernels_frame_png.hip (png_filter, png_cost,
 // png_scan, png_pack, png_crc, png_finish), under PNG_RUNS with the run-aware cost and pack kernels in the places of the two, under PNG_OPT with the ones that build and use the segments' own tables.
-void enqueue_coding(const FormatTraits& t, const uint8_t* src, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm);
+// JPEG under a byte budget (`budget` not empty; POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 only): kJpegBudgetSteps pairs of dispatches in front (marks jpeg_measure, jpeg_pick),
+// then the same two on the picked quality's tables.
+void enqueue_coding(const FormatTraits& t, const uint8_t* src, const void* tables, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, hipStream_t s, hipEvent_t done, Timer* tm,
+                    const poppy_hip::JpegBudget& budget = poppy_hip::JpegBudget());
 hipError_t prepare_coding_scratch(const FormatTraits& t, uint8_t* scratch, int W, int H, hipStream_t s);      // ... once behind its allocation, in front of the first frame coded on it
 size_t coding_scratch_bytes(const FormatTraits& t, int W, int H);      // ... and what `scratch` holds (kernels.h: gif_scratch_bytes, jpeg_scratch_bytes, png_scratch_bytes)
 // the context's quantisation tables and header for its quality on the device, at an address that stays (captured bodies hold it): allocated and filled when missing
 int ensure_jpeg_tables(poppy_hip_ctx* c);
+// the byte budget of the context's JPEG frames as the kernels read it: the tables of all 100 qualities and the words (budget, highest quality) behind them, one
+// allocation at an address that stays, filled on first use and the words rewritten by the setters once the frames are drained.  *out stays empty with the budget off
+// or for a format the budget does not apply to.
+int context_jpeg_budget(poppy_hip_ctx* c, const FormatTraits& t, poppy_hip::JpegBudget* out);
+int ensure_jpeg_budget_tables(poppy_hip_ctx* c);      // ... the allocation alone (c->jpeg_budget_tables), for a call that brings its own words
+bool budget_applies(const FormatTraits& t);      // POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444; (the four formats on built tables refuse a budget: poppy_hip_set_frame_format and poppy_hip_set_jpeg_budget, whichever comes second)
 // conversion tables, zero before the first frame (the palette builds leave them zero again): PAL8's per slot and for the scratch, the sequence's per context
 int alloc_zeroed_tables(poppy_hip_ctx* c, uint8_t** tables, size_t bytes);

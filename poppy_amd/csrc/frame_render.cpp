@@ -10,6 +10,8 @@ static_assert(kPlanRasterRows == kRasterChunkRows, "the plan's work list and k_r
 // (PAL8_SEQ, GIF_SEQ: none either — the sequence pass is launched behind the body, its destination differs from frame to frame: render_slot)
 static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached && !format_traits(c->frame_format)->sequence ? c->frame_format : POPPY_FRAME_BGR; }
 // ... and the geometry they are scaled down or resized to in front of it, under every format (the sequence formats' pass reads the scaled frame)
+// ... and whether its conversion runs the JPEG byte budget's search (what enqueue_conversion reads: the slot's budget, under a format that applies it)
+static bool frame_wants_budget(const poppy_hip_ctx* c, const FrameSlot& f) { return budget_applies(*format_traits(frame_wants_format(c))) && (bool)f.fmt.jpeg_budget; }
 static WriterGeom frame_wants_geom(const poppy_hip_ctx* c) { return writer_geom(c, c->writer_attached); }
 
 // pyrdown .. unsharp of one slot.  Every argument is fixed for the life of the pair (the per-frame unsharp amount is
@@ -126,7 +128,7 @@ static int capture_body(poppy_hip_ctx* c, FrameSlot& f) {
     hipGraph_t g = nullptr;
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     (void)enqueue_body(c, f, c->stream, nullptr, 0.f, false);
-    f.body_format = frame_wants_format(c); f.body_geom = frame_wants_geom(c);
+    f.body_format = frame_wants_format(c); f.body_geom = frame_wants_geom(c); f.body_budget = frame_wants_budget(c, f);
     HIPCHK(c, hipStreamEndCapture(c->stream, &g));
     hipError_t e = hipGraphInstantiate(&f.body, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
@@ -246,7 +248,7 @@ static int prepare_slot(poppy_hip_ctx* c, const FramePlan& plan, double mask, bo
     // bottleneck.  On the chained critical path a graph launch leaves the GPU idle ~8 us longer than the same kernels
     // launched one by one (4600 vs 4785 frames/s, profiles/r01_e_streams.md), and the host keeps up easily.
     const bool use_graph = !no_graph && !chained && !c->debug && !all_marks && W > 1 && H > 1;
-    if (use_graph && f.body && (f.body_format != frame_wants_format(c) || f.body_geom != frame_wants_geom(c))) {      // the body has (not) the downscale and conversion the frame needs: captured again
+    if (use_graph && f.body && (f.body_format != frame_wants_format(c) || f.body_geom != frame_wants_geom(c) || f.body_budget != frame_wants_budget(c, f))) {      // the body has (not) the downscale, the conversion and the budget's search the frame needs: captured again
         HIPCHK(c, hipEventSynchronize(f.done));                                // (the slot's last frame may still run it)
         (void)hipGraphExecDestroy(f.body); f.body = nullptr;
     }

@@ -118,6 +118,8 @@ bool gif_coded_frame(poppy_sink* s, const uint8_t* frame) {
 }
 
 // ---- POPPY_SINK_MJPEG: a RIFF AVI with one Motion-JPEG video stream (include/poppy_hip.h names every chunk) ----
+// Frames under a byte budget (poppy_hip_set_jpeg_budget) need nothing of their own here: every frame is a complete file with its own DQT, the sink reads SOF0 and
+// `total` and never DQT, so frames of differing qualities stand side by side in one stream (tests/test_host_jpeg_budget.py writes such a file).
 constexpr long kAviMovi = 220;                              // the file offset of the `movi` fourcc; the first chunk follows it
 constexpr long kAviRiffSize = 4, kAviTotalFrames = 48, kAviBuffer = 60, kAviLength = 140, kAviStreamBuffer = 144, kAviMoviSize = 216;
 

@@ -296,6 +296,30 @@ constexpr size_t kJpegSeqTableBytes = sizeof(jpeg::SymbolCounts) + sizeof(jpeg::
 void launch_jpeg_count_into(const uint8_t* planes, const void* tables, uint32_t* counts, int w, int h, jpeg::Sampling sm, hipStream_t s, hipEvent_t done = nullptr);
 void launch_jpeg_code_on(const uint8_t* planes, const void* tables, const void* built, uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
 void launch_jpeg_pack_on(const void* tables, const void* built, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, jpeg::Sampling sm, hipStream_t s, hipEvent_t done = nullptr);
+// POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 under a byte budget (include/poppy_hip.h, "JPEG byte budget"): the search over the qualities runs on the device, in
+// kJpegBudgetSteps steps of two dispatches each — launch_jpeg_measure (the coder without its stores at the step's qualities: every segment's byte length at each)
+// and launch_jpeg_pick (one workgroup: the sizes, the search advanced by kJpegBudgetLevels levels; steps behind the search's end return at once) —, then the coder
+// and the gather run once on the tables of the picked quality (launch_jpeg_code_picked, launch_jpeg_pack_picked).  The search's state and the measured lengths live in
+// the frame's scratch (jpeg_scratch_bytes, not opt); the budget and the highest quality are read from `params` and the tables from `tables` (the tables of the
+// qualities 1..100 in order, kJpegBudgetTableBytes), both device memory: no kernel argument names a setting, so a captured body follows the setters.
+struct JpegBudgetParams { uint32_t budget, quality_max; };
+struct JpegBudget {
+    const void* tables = nullptr;
+    const void* params = nullptr;
+    explicit operator bool() const { return tables != nullptr; }
+};
+#ifndef POPPY_JPEG_BUDGET_LEVELS
+#define POPPY_JPEG_BUDGET_LEVELS 1                          // the plain schedule, one level of the search per step.  2 (a build with -DPOPPY_JPEG_BUDGET_LEVELS=2): two levels per step
+                                                            // measured speculatively, 13 qualities in 4 steps instead of 8 in 7 — measured 6 to 8 % slower per chained 1080p frame
+#endif
+constexpr int kJpegBudgetLevels = POPPY_JPEG_BUDGET_LEVELS;
+constexpr int kJpegBudgetListMax = 1 << kJpegBudgetLevels;   // a step's qualities at most: the levels' full tree, and the highest quality at step 0
+constexpr int kJpegBudgetSteps = (7 + kJpegBudgetLevels - 1) / kJpegBudgetLevels;      // the search from (0, 100) has ceil(log2(100)) = 7 levels
+constexpr size_t kJpegBudgetTableBytes = 100 * kJpegTableBytes;
+void launch_jpeg_measure(const uint8_t* planes, const JpegBudget& budget, uint8_t* scratch, int step, int w, int h, jpeg::Sampling sm, hipStream_t s);
+void launch_jpeg_pick(const JpegBudget& budget, uint8_t* scratch, int step, int w, int h, jpeg::Sampling sm, hipStream_t s);
+void launch_jpeg_code_picked(const uint8_t* planes, const JpegBudget& budget, uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
+void launch_jpeg_pack_picked(const JpegBudget& budget, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, jpeg::Sampling sm, hipStream_t s, hipEvent_t done = nullptr);
 
 // a frame on the device (tight BGR) -> its I444 planes, 3 * w * h bytes (kernels_frame_i444.hip; poppy_bgr_to_i444 is the host statement): any w, h >= 1; `done`
 // (optional) rides on the dispatch

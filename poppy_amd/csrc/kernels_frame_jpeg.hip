@@ -35,6 +35,14 @@
 //   k_jpeg_code    as above, its Huffman entries read from the frame's built tables in device memory (template parameter OPT), its bit buffer and scratch slot at
 //                  the OPT bound (a DC code may have 12 bits).
 //   k_jpeg_pack    as above; its OPT form puts the header together from the fixed header's bytes around the built DHT, and the data behind it, wherever it ends.
+//
+// POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 under a byte budget (poppy_hip_set_jpeg_budget; frame_jpeg_budget.cpp is the host statement) put kJpegBudgetSteps pairs of
+// dispatches in front of the two, no host round trip:
+//   k_jpeg_measure k_jpeg_code without its stores, at the qualities of one step of the search: the samples and the DCT once (block_dct), the 64 coefficients in front of
+//                  the quantiser kept in the lane's registers, and per quality the quantiser (block_quantise), the bit string in LDS (segment_bits) and the count of its
+//                  FF bytes: every segment's exact byte length at that quality.  The tables of all 100 qualities, the budget and the highest quality are device memory.
+//   k_jpeg_pick    one workgroup: the file's size at each measured quality, the search's interval advanced by the rule; at its end the picked quality, in the scratch.
+//   k_jpeg_code, k_jpeg_pack   once, on the picked quality's entry of the 100 tables (an index read from the scratch).
 #include "kernels.h"
 #include <hip/hip_ext.h>
 #include <algorithm>
@@ -159,13 +167,19 @@ struct BlockFront {
     int table;                                              // 0: luma, 1: chroma
     int diff;                                               // the DC difference
 };
+// ... in its parts (k_jpeg_measure runs the first once and the other two per quality).  block_dct: which block the lane has, and its 64 coefficients in front of
+// the quantiser, natural order, in f (registers)
+struct BlockPlace {
+    bool active;
+    int table;
+    int b, m_in;                                            // the block's number in its MCU, the MCU's in the segment
+};
 template <Sampling S>
-__device__ __forceinline__ BlockFront block_front(FrontLds& L, const uint8_t* __restrict__ i420, int seg, int lane, int w, int h, int mw, int n_mcu) {
+__device__ __forceinline__ BlockPlace block_dct(int (&f)[64], const uint8_t* __restrict__ i420, int seg, int lane, int w, int h, int mw, int n_mcu) {
     constexpr int kBlocks = mcu_blocks(S), kMcus = restart_mcus(S);
     const int first = seg * kMcus, mcus = min(kMcus, n_mcu - first);
     const int m_in = lane / kBlocks, b = lane - kBlocks * m_in, table = S == k444 ? b >= 1 : b >= 4;
     const bool active = m_in < mcus;
-    int dc = 0;
     if (active) {
         const int m = first + m_in, my = m / mw, mx = m - my * mw;
         // the block's plane, that plane's size and the block's origin in it.  4:4:4: (the I444 planes) every plane w x h, every block at (8 mx, 8 my)
@@ -173,7 +187,6 @@ __device__ __forceinline__ BlockFront block_front(FrontLds& L, const uint8_t* __
         const int pw = table ? cw : w, ph = table ? ch : h;
         const int x0 = table || S == k444 ? 8 * mx : 16 * mx + 8 * (b & 1), y0 = table || S == k444 ? 8 * my : 16 * my + 8 * (b >> 1);
         const uint8_t* plane = i420 + (!table ? (size_t)0 : (size_t)w * h + (b == kBlocks - 1 ? (size_t)cw * ch : (size_t)0));
-        int f[64];
         #pragma unroll
         for (int y = 0; y < 8; ++y) {
             const uint8_t* row = plane + (size_t)min(y0 + y, ph - 1) * pw;
@@ -198,36 +211,31 @@ __device__ __forceinline__ BlockFront block_front(FrontLds& L, const uint8_t* __
             #pragma unroll
             for (int y = 0; y < 8; ++y) f[y * 8 + u] = v[y];
         }
-        dc = quantise_block(L, f, table, lane, std::make_integer_sequence<int, 64>());
     }
+    return BlockPlace{active, table, b, m_in};
+}
+// the quantiser in L.q on f (the coefficients into L.coef) and the DC difference by shuffle; every lane of the wave calls it
+template <Sampling S>
+__device__ __forceinline__ int block_quantise(FrontLds& L, const int (&f)[64], const BlockPlace& p, int lane) {
+    const int b = p.b;
+    const int dc = p.active ? quantise_block(L, f, p.table, lane, std::make_integer_sequence<int, 64>()) : 0;
     // the previous block of the same component: the luma block before, Y11 of the MCU before for Y00, the same chroma block of the MCU before; the segment's first: 0
     // (4:4:4: the same block of the MCU before, three lanes down)
     const int from = S == k444 ? lane - 3 : b >= 4 ? lane - 6 : b == 0 ? lane - 3 : lane - 1;
     const int before = __shfl(dc, max(from, 0), 64);
-    return BlockFront{active, table, dc - ((S == k444 || b == 0 || b >= 4) && m_in == 0 ? 0 : before)};
+    return dc - ((S == k444 || b == 0 || b >= 4) && p.m_in == 0 ? 0 : before);
+}
+template <Sampling S>
+__device__ __forceinline__ BlockFront block_front(FrontLds& L, const uint8_t* __restrict__ i420, int seg, int lane, int w, int h, int mw, int n_mcu) {
+    int f[64];
+    const BlockPlace p = block_dct<S>(f, i420, seg, lane, w, h, mw, n_mcu);
+    return BlockFront{p.active, p.table, block_quantise<S>(L, f, p, lane)};
 }
 
-}  // namespace
-
-// OPT: the Huffman entries are the frame's built tables (`huff`, device memory: k_jpeg_tables wrote them) instead of the Annex K ones, and the bit buffer and the
-// scratch slots are the OPT bound's
-template <Sampling S, bool OPT>
-__global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i420, const QualityTables* __restrict__ tables, const HuffTables* __restrict__ huff,
-                                                  uint8_t* __restrict__ scratch, uint32_t* __restrict__ lengths, int w, int h, int mw, int n_mcu) {
-    __shared__ CoderLds<OPT ? kOptBitWords : kBitWords> L;
-    const int lane = threadIdx.x, seg = blockIdx.x;
-    if constexpr (OPT) {
-        for (int i = lane; i < 512; i += 64) L.ac[i >> 8][i & 255] = huff->ac[i >> 8][i & 255];
-        if (lane < 32) L.dc[lane >> 4][lane & 15] = huff->dc[lane >> 4][lane & 15];
-    } else {
-        for (int i = lane; i < 512; i += 64) L.ac[i >> 8][i & 255] = c_huff.ac[i >> 8][i & 255];
-        if (lane < 32) L.dc[lane >> 4][lane & 15] = c_huff.dc[lane >> 4][lane & 15];
-    }
-    for (int i = lane; i < 128; i += 64) L.f.q[i >> 6][i & 63] = make_uint2(tables->bias[i >> 6][i & 63], tables->recip[i >> 6][i & 63]);
-    wave_sync();
-    const BlockFront front = block_front<S>(L.f, i420, seg, lane, w, h, mw, n_mcu);
-    const bool active = front.active;
-    const int table = front.table, diff = front.diff;
+// A segment's bit string from its front end: every block counted, placed by a wave prefix sum and ORed into L.bits, the padding 1-bits behind; returns the
+// string's length in bits.  Every lane of the wave calls it.
+template <int WORDS>
+__device__ __forceinline__ uint32_t segment_bits(CoderLds<WORDS>& L, int lane, bool active, int table, int diff) {
     const uint32_t n_bits = active ? code_block<false>(L, lane, table, diff, 0) : 0;
     uint32_t incl = n_bits;
     #pragma unroll
@@ -239,6 +247,68 @@ __global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i4
     const int pad = (int)((8 - (total_bits & 7)) & 7);
     if (lane == 0 && pad) emit_bits(L.bits, total_bits, (1u << pad) - 1, pad);
     wave_sync();
+    return total_bits;
+}
+
+// ---- the byte budget (include/poppy_hip.h, "JPEG byte budget"): the search's state, in the frame's scratch.  Nothing of it is a kernel argument that a captured
+// body could keep: the budget and the highest quality are read from JpegBudgetParams in device memory, the state from here. ----
+struct BudgetSearch {
+    uint32_t lo, hi;                                        // hi is known not to fit; lo = 0: nothing known to fit
+    uint32_t picked;                                        // 0 while the search runs, then the frame's quality
+    uint32_t pad;
+};
+// the quality that k_jpeg_code and k_jpeg_pack index the tables by (whatever the word holds, the index stays inside the 100 tables)
+__device__ __forceinline__ int picked_quality(const BudgetSearch* s) { return (int)min(max(s->picked, 1u), 100u); }
+
+// The qualities a step measures: the first kJpegBudgetLevels levels of the search tree below (lo, hi) in breadth-first order, and at step 0, where
+// (lo, hi) = (0, quality_max), quality_max in front.  fits(q) is a pure function of the frame, so measuring a level whose question the level above has not
+// answered yet changes no result.  k_jpeg_measure and k_jpeg_pick derive the same list from the same state.
+constexpr int kBudgetListMax = kJpegBudgetListMax;
+static_assert(kJpegBudgetLevels == 1 || kJpegBudgetLevels == 2, "probe_list writes out one or two levels");
+static_assert(kBudgetListMax == (1 << kJpegBudgetLevels), "a full tree of the step's levels, and quality_max at step 0");
+__device__ __forceinline__ int probe_list(int lo, int hi, bool first, int (&q)[kBudgetListMax]) {
+    int n = 0;
+    if (first) q[n++] = hi;
+    if (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        q[n++] = mid;
+        if (kJpegBudgetLevels > 1) {
+            if (mid - lo > 1) q[n++] = (lo + mid) >> 1;
+            if (hi - mid > 1) q[n++] = (mid + hi) >> 1;
+        }
+    }
+    return n;
+}
+// the state a step starts from: step 0 from the context's highest quality (clamped: whatever the words hold, every table index stays inside the 100), later steps
+// from what the pick before left.  False: the search is over.
+__device__ __forceinline__ bool search_state(const JpegBudgetParams* params, const BudgetSearch* search, bool first, int* lo, int* hi) {
+    if (first) { *lo = 0; *hi = (int)min(max(params->quality_max, 1u), 100u); return true; }
+    if (search->picked) return false;
+    *lo = (int)min(search->lo, 99u); *hi = (int)min(max(search->hi, (uint32_t)*lo + 1), 100u);
+    return true;
+}
+
+}  // namespace
+
+// OPT: the Huffman entries are the frame's built tables (`huff`, device memory: k_jpeg_tables wrote them) instead of the Annex K ones, and the bit buffer and the
+// scratch slots are the OPT bound's
+template <Sampling S, bool OPT>
+__global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i420, const QualityTables* __restrict__ tables, const HuffTables* __restrict__ huff,
+                                                  uint8_t* __restrict__ scratch, uint32_t* __restrict__ lengths, int w, int h, int mw, int n_mcu, const BudgetSearch* __restrict__ search) {
+    __shared__ CoderLds<OPT ? kOptBitWords : kBitWords> L;
+    const int lane = threadIdx.x, seg = blockIdx.x;
+    if (search) tables += picked_quality(search) - 1;      // under a byte budget `tables` are all 100 qualities' and k_jpeg_pick chose one
+    if constexpr (OPT) {
+        for (int i = lane; i < 512; i += 64) L.ac[i >> 8][i & 255] = huff->ac[i >> 8][i & 255];
+        if (lane < 32) L.dc[lane >> 4][lane & 15] = huff->dc[lane >> 4][lane & 15];
+    } else {
+        for (int i = lane; i < 512; i += 64) L.ac[i >> 8][i & 255] = c_huff.ac[i >> 8][i & 255];
+        if (lane < 32) L.dc[lane >> 4][lane & 15] = c_huff.dc[lane >> 4][lane & 15];
+    }
+    for (int i = lane; i < 128; i += 64) L.f.q[i >> 6][i & 63] = make_uint2(tables->bias[i >> 6][i & 63], tables->recip[i >> 6][i & 63]);
+    wave_sync();
+    const BlockFront front = block_front<S>(L.f, i420, seg, lane, w, h, mw, n_mcu);
+    const uint32_t total_bits = segment_bits(L, lane, front.active, front.table, front.diff);
     // byte stuffing: byte i of the string goes to i + (the FF bytes in front of it), a zero byte behind every FF
     const uint32_t n_bytes = (total_bits + 7) / 8;
     uint8_t* dst = scratch + (size_t)seg * (OPT ? kJpegOptSlotBytes : kJpegSlotBytes);
@@ -253,6 +323,75 @@ __global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i4
         n_ff += (uint32_t)__popcll(ff);
     }
     if (lane == 0) lengths[seg] = n_bytes + n_ff;
+}
+
+// The coder without its stores, at the qualities of one step of the budget's search (probe_list): a segment per wave and a block per lane as in k_jpeg_code, the
+// samples and the DCT once, the 64 coefficients in front of the quantiser kept in the lane's registers, and per quality the quantiser, the bit string in LDS and
+// the count of its FF bytes — the segment's exact byte length, into measured[k * n_seg + seg].  `tables`: all 100 qualities'.
+template <Sampling S>
+__global__ void __launch_bounds__(64) k_jpeg_measure(const uint8_t* __restrict__ i420, const QualityTables* __restrict__ tables, const JpegBudgetParams* __restrict__ params,
+                                                     const BudgetSearch* __restrict__ search, uint32_t* __restrict__ measured, int first, int w, int h, int mw, int n_mcu, int n_seg) {
+    __shared__ CoderLds<kBitWords> L;
+    const int lane = threadIdx.x, seg = blockIdx.x;
+    int lo, hi, list[kBudgetListMax];
+    if (!search_state(params, search, first != 0, &lo, &hi)) return;      // (uniform: the search is over)
+    const int n = probe_list(lo, hi, first != 0, list);
+    if (n == 0) return;
+    for (int i = lane; i < 512; i += 64) L.ac[i >> 8][i & 255] = c_huff.ac[i >> 8][i & 255];
+    if (lane < 32) L.dc[lane >> 4][lane & 15] = c_huff.dc[lane >> 4][lane & 15];
+    int f[64];
+    const BlockPlace place = block_dct<S>(f, i420, seg, lane, w, h, mw, n_mcu);
+    for (int k = 0; k < n; ++k) {
+        const QualityTables* t = tables + (list[k] - 1);
+        for (int i = lane; i < 128; i += 64) L.f.q[i >> 6][i & 63] = make_uint2(t->bias[i >> 6][i & 63], t->recip[i >> 6][i & 63]);
+        wave_sync();
+        const int diff = block_quantise<S>(L.f, f, place, lane);
+        const uint32_t total_bits = segment_bits(L, lane, place.active, place.table, diff);
+        const uint32_t n_bytes = (total_bits + 7) / 8;
+        uint32_t n_ff = 0;
+        for (uint32_t base = 0; base < n_bytes; base += 64) {
+            const uint32_t i = base + lane;
+            const uint32_t byte = i < n_bytes ? (L.bits[i >> 2] >> (24 - 8 * (i & 3))) & 255u : 0u;
+            n_ff += (uint32_t)__popcll(__ballot(byte == 255u));
+        }
+        if (lane == 0) measured[(size_t)k * n_seg + seg] = n_bytes + n_ff;
+        wave_sync();                                        // (the next quality's quantiser, coefficients and bits go where this one's were read)
+    }
+}
+
+// One workgroup: size(q) of every quality the step measured — the header, the segments' lengths with their two marker bytes each; the file, not `total` — and
+// the search advanced by the rule over the step's levels.  Leaves the next step's (lo, hi), or the frame's quality in `picked`.
+__global__ void __launch_bounds__(256) k_jpeg_pick(const JpegBudgetParams* __restrict__ params, BudgetSearch* __restrict__ search, const uint32_t* __restrict__ measured,
+                                                   int first, int n_seg) {
+    __shared__ unsigned long long s_part[kBudgetListMax][4];
+    int lo, hi, list[kBudgetListMax];
+    if (!search_state(params, search, first != 0, &lo, &hi)) return;
+    const int n = probe_list(lo, hi, first != 0, list);
+    const int t = threadIdx.x;
+    for (int k = 0; k < n; ++k) {
+        unsigned long long sum = 0;
+        for (int i = t; i < n_seg; i += 256) sum += measured[(size_t)k * n_seg + i] + 2;
+        #pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+        if ((t & 63) == 0) s_part[k][t >> 6] = sum;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    const unsigned long long budget = params->budget;
+    auto fits = [&](int q) {                                // (q is in the list: the list is the tree's levels that the walk below takes)
+        for (int k = 0; k < n; ++k) if (list[k] == q) return (unsigned long long)kHeaderBytes + s_part[k][0] + s_part[k][1] + s_part[k][2] + s_part[k][3] <= budget;
+        return false;
+    };
+    uint32_t picked = 0;
+    if (first && fits(hi)) picked = (uint32_t)hi;
+    else {
+        for (int level = 0; level < kJpegBudgetLevels && hi - lo > 1; ++level) {
+            const int mid = (lo + hi) >> 1;
+            if (fits(mid)) lo = mid; else hi = mid;
+        }
+        if (hi - lo <= 1) picked = (uint32_t)max(lo, 1);
+    }
+    search->lo = (uint32_t)lo; search->hi = (uint32_t)hi; search->picked = picked;
 }
 
 namespace {
@@ -406,8 +545,9 @@ constexpr int kPackGroup = 8;                               // segments per work
 template <bool OPT>
 __global__ void __launch_bounds__(256) k_jpeg_pack(const uint8_t* __restrict__ scratch, const uint32_t* __restrict__ lengths, const QualityTables* __restrict__ tables,
                                                    const OptTables* __restrict__ opt, int n_seg, int w, int h, int sof_sampling, int restart, uint8_t* __restrict__ frame,
-                                                   uint32_t* __restrict__ total_host) {
+                                                   uint32_t* __restrict__ total_host, const BudgetSearch* __restrict__ search) {
     constexpr size_t kSlot = OPT ? kJpegOptSlotBytes : kJpegSlotBytes;
+    if (search) tables += picked_quality(search) - 1;      // (as in k_jpeg_code: the header's bytes are the picked quality's)
     int dht_bytes[4] = {0, 0, 0, 0}, header_bytes = kHeaderBytes;
     if constexpr (OPT) {
         header_bytes = kOptHeaderFixed;
@@ -469,11 +609,16 @@ int count_groups(size_t n_seg) { return (int)std::min<size_t>((n_seg + kCountWav
 OptTables* jpeg_opt_tables(uint8_t* scratch, size_t n_seg) { return (OptTables*)(scratch + ((n_seg * (kJpegOptSlotBytes + 4) + 15) & ~(size_t)15)); }
 uint32_t* jpeg_opt_counts(uint8_t* scratch, size_t n_seg) { return (uint32_t*)(jpeg_opt_tables(scratch, n_seg) + 1); }
 static_assert(sizeof(OptTables) % 16 == 0 && kJpegOptSlotBytes % 4 == 0, "the scratch's parts are aligned");
+
+// the scratch of the formats on the Annex K tables, behind the slots and the lengths: the budget's search state, then the lengths it measures
+BudgetSearch* jpeg_budget_search(uint8_t* scratch, size_t n_seg) { return (BudgetSearch*)(scratch + ((n_seg * (kJpegSlotBytes + 4) + 15) & ~(size_t)15)); }
+uint32_t* jpeg_budget_measured(uint8_t* scratch, size_t n_seg) { return (uint32_t*)(jpeg_budget_search(scratch, n_seg) + 1); }
+static_assert(sizeof(BudgetSearch) == 16 && sizeof(QualityTables) % 4 == 0, "the scratch's parts and the 100 tables are aligned");
 }
 
 size_t jpeg_scratch_bytes(int w, int h, Sampling sm, bool opt) {
     const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
-    if (!opt) return n_seg * (kJpegSlotBytes + 4) + 16;
+    if (!opt) return ((n_seg * (kJpegSlotBytes + 4) + 15) & ~(size_t)15) + sizeof(BudgetSearch) + n_seg * 4 * kBudgetListMax + 16;
     return ((n_seg * (kJpegOptSlotBytes + 4) + 15) & ~(size_t)15) + sizeof(OptTables) + sizeof(SymbolCounts) + 16;
 }
 
@@ -503,27 +648,53 @@ hipError_t launch_jpeg_counts_clear(uint8_t* scratch, int w, int h, Sampling sm,
 }
 
 // built: null for the Annex K tables, or the OptTables that a table build left — the scratch's own (launch_jpeg_code) or a sequence's (launch_jpeg_code_on)
-void launch_jpeg_code_on(const uint8_t* planes, const void* tables, const void* built, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
+static void launch_jpeg_code_with(const uint8_t* planes, const void* tables, const void* built, const BudgetSearch* search, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
     const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
     const int mw = (w + mcu_side(sm) - 1) / mcu_side(sm);
     const bool opt = built != nullptr;
     auto kernel = opt ? (sm == k444 ? k_jpeg_code<k444, true> : k_jpeg_code<k420, true>) : (sm == k444 ? k_jpeg_code<k444, false> : k_jpeg_code<k420, false>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)n_seg), dim3(64), 0, s, planes, (const QualityTables*)tables, opt ? &((const OptTables*)built)->huff : (const HuffTables*)nullptr,
-                       scratch, jpeg_lengths(scratch, n_seg, opt), w, h, mw, (int)mcu_count((size_t)w, (size_t)h, sm));
+                       scratch, jpeg_lengths(scratch, n_seg, opt), w, h, mw, (int)mcu_count((size_t)w, (size_t)h, sm), search);
+}
+void launch_jpeg_code_on(const uint8_t* planes, const void* tables, const void* built, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
+    launch_jpeg_code_with(planes, tables, built, nullptr, scratch, w, h, sm, s);
 }
 void launch_jpeg_code(const uint8_t* planes, const void* tables, uint8_t* scratch, int w, int h, Sampling sm, bool opt, hipStream_t s) {
     launch_jpeg_code_on(planes, tables, opt ? jpeg_opt_tables(scratch, segment_count((size_t)w, (size_t)h, sm)) : nullptr, scratch, w, h, sm, s);
 }
 
-void launch_jpeg_pack_on(const void* tables, const void* built, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, hipStream_t s, hipEvent_t done) {
+static void launch_jpeg_pack_with(const void* tables, const void* built, const BudgetSearch* search, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, hipStream_t s, hipEvent_t done) {
     const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
     const bool opt = built != nullptr;
     hipExtLaunchKernelGGL(opt ? k_jpeg_pack<true> : k_jpeg_pack<false>, dim3((unsigned)((n_seg + kPackGroup - 1) / kPackGroup)), dim3(256), 0, s, nullptr, done, 0, scratch,
                           jpeg_lengths(const_cast<uint8_t*>(scratch), n_seg, opt), (const QualityTables*)tables, (const OptTables*)built, (int)n_seg, w, h,
-                          (int)sof_sampling(sm), restart_mcus(sm), frame, total_host);
+                          (int)sof_sampling(sm), restart_mcus(sm), frame, total_host, search);
+}
+void launch_jpeg_pack_on(const void* tables, const void* built, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, hipStream_t s, hipEvent_t done) {
+    launch_jpeg_pack_with(tables, built, nullptr, scratch, frame, total_host, w, h, sm, s, done);
 }
 void launch_jpeg_pack(const void* tables, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, bool opt, hipStream_t s, hipEvent_t done) {
     launch_jpeg_pack_on(tables, opt ? jpeg_opt_tables(const_cast<uint8_t*>(scratch), segment_count((size_t)w, (size_t)h, sm)) : nullptr, scratch, frame, total_host, w, h, sm, s, done);
+}
+
+// ---- the byte budget: steps of one measuring and one picking dispatch each, then the coder and the gather on the picked quality's tables ----
+void launch_jpeg_measure(const uint8_t* planes, const JpegBudget& budget, uint8_t* scratch, int step, int w, int h, Sampling sm, hipStream_t s) {
+    const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
+    const int mw = (w + mcu_side(sm) - 1) / mcu_side(sm);
+    hipLaunchKernelGGL(sm == k444 ? k_jpeg_measure<k444> : k_jpeg_measure<k420>, dim3((unsigned)n_seg), dim3(64), 0, s, planes, (const QualityTables*)budget.tables,
+                       (const JpegBudgetParams*)budget.params, (const BudgetSearch*)jpeg_budget_search(scratch, n_seg), jpeg_budget_measured(scratch, n_seg), (int)(step == 0), w, h, mw,
+                       (int)mcu_count((size_t)w, (size_t)h, sm), (int)n_seg);
+}
+void launch_jpeg_pick(const JpegBudget& budget, uint8_t* scratch, int step, int w, int h, Sampling sm, hipStream_t s) {
+    const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
+    hipLaunchKernelGGL(k_jpeg_pick, dim3(1), dim3(256), 0, s, (const JpegBudgetParams*)budget.params, jpeg_budget_search(scratch, n_seg), (const uint32_t*)jpeg_budget_measured(scratch, n_seg),
+                       (int)(step == 0), (int)n_seg);
+}
+void launch_jpeg_code_picked(const uint8_t* planes, const JpegBudget& budget, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
+    launch_jpeg_code_with(planes, budget.tables, nullptr, jpeg_budget_search(scratch, segment_count((size_t)w, (size_t)h, sm)), scratch, w, h, sm, s);
+}
+void launch_jpeg_pack_picked(const JpegBudget& budget, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, hipStream_t s, hipEvent_t done) {
+    launch_jpeg_pack_with(budget.tables, nullptr, jpeg_budget_search(const_cast<uint8_t*>(scratch), segment_count((size_t)w, (size_t)h, sm)), scratch, frame, total_host, w, h, sm, s, done);
 }
 
 }  // namespace poppy_hip

@@ -11,8 +11,8 @@ int scale_into_scratch(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, con
 
 // what the coder of format `t` reads, in device memory (its raster form; PNG: the tight BGR frame) -> the coded frame in `host` (exactly `total` bytes), on the
 // context's stream and waited for: the frames that no slot renders, and the stand-alone coding entry points.  d_tables: the JPEG coder's.  The buffers live for
-// the call, at t's capacity; nothing of the call is in flight when they go.
-static int coded_from_device(poppy_hip_ctx* c, const FormatTraits& t, const uint8_t* d_src, const void* d_tables, int W, int H, std::vector<uint8_t>& host) {
+// the call, at t's capacity; nothing of the call is in flight when they go.  budget (not empty: JPEG under a byte budget): the tables of all qualities and the budget's words.
+static int coded_from_device(poppy_hip_ctx* c, const FormatTraits& t, const uint8_t* d_src, const void* d_tables, int W, int H, std::vector<uint8_t>& host, const JpegBudget& budget = JpegBudget()) {
     const size_t cap = capacity(t, (size_t)W, (size_t)H);
     CallBuffers held;
     uint8_t *work = nullptr, *frame = nullptr;
@@ -21,7 +21,7 @@ static int coded_from_device(poppy_hip_ctx* c, const FormatTraits& t, const uint
     if (e == hipSuccess) e = prepare_coding_scratch(t, work, W, H, c->stream);
     uint32_t total = 0;
     if (e == hipSuccess) {
-        enqueue_coding(t, d_src, d_tables, work, frame, nullptr, W, H, c->stream, nullptr, nullptr);
+        enqueue_coding(t, d_src, d_tables, work, frame, nullptr, W, H, c->stream, nullptr, nullptr, budget);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
@@ -51,7 +51,8 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
     }
     *stride = writer_stride(fmt, W);
     const uint8_t* d_frame = d_bgr;
-    if (t.coder == kCoderJpeg) { int rc = ensure_jpeg_tables(c); if (rc) return rc; }
+    JpegBudget budget;
+    if (t.coder == kCoderJpeg) { int rc = ensure_jpeg_tables(c); if (rc) return rc; rc = context_jpeg_budget(c, t, &budget); if (rc) return rc; }
     if (t.raster != kRasterNone) {                                 // the raster step into the context's scratch: the slots' launches on other buffers
         if (t.raster == kRasterPal8) { int rc = alloc_zeroed_tables(c, &c->fmt_scratch_tables, kPal8TableBytes); if (rc) return rc; }
         HIPCHK(c, c->fmt_scratch.reserve(raster_bytes(t.raster, W, H) + 16, c->stream));
@@ -60,7 +61,7 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
         d_frame = enqueue_raster(t.raster, d_bgr, W, H, scratch, c->stream, nullptr, nullptr);
         HIPCHK(c, hipGetLastError());
     }
-    if (t.coded()) return coded_from_device(c, t, d_frame, c->jpeg_tables, W, H, host);      // the coder step, on buffers that live for the call
+    if (t.coded()) return coded_from_device(c, t, d_frame, c->jpeg_tables, W, H, host, budget);      // the coder step, on buffers that live for the call
     host.resize(poppy_frame_bytes(fmt, W, H));
     HIPCHK(c, hipMemcpyAsync(host.data(), d_frame, host.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -82,6 +83,7 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
     else if (t.sequence) rc = pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, pal8.empty() ? tmp.data() : pal8.data());
     else if (t.coder == kCoderGif) rc = poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data());
     else if (t.coder == kCoderJpeg && t.frame_tables) rc = (t.sampling() == jpeg::k444 ? poppy_bgr_to_jpeg444_opt_frame : poppy_bgr_to_jpeg_opt_frame)(bgr, stride, W, H, c->jpeg_quality, tmp.data());
+    else if (t.coder == kCoderJpeg && c->jpeg_budget) rc = (t.sampling() == jpeg::k444 ? poppy_bgr_to_jpeg444_budget_frame : poppy_bgr_to_jpeg_budget_frame)(bgr, stride, W, H, c->jpeg_quality, c->jpeg_budget, tmp.data(), nullptr);
     else if (t.coder == kCoderJpeg) rc = (t.sampling() == jpeg::k444 ? poppy_bgr_to_jpeg444_frame : poppy_bgr_to_jpeg_frame)(bgr, stride, W, H, c->jpeg_quality, tmp.data());
     else if (t.coder == kCoderPng) rc = (t.variant == png::kRunsOwn ? poppy_bgr_to_png_opt_frame : t.runs() ? poppy_bgr_to_png_runs_frame : poppy_bgr_to_png_frame)(bgr, stride, W, H, tmp.data());
     else rc = (t.raster == kRasterPal8 ? poppy_bgr_to_pal8 : poppy_bgr_to_i420)(bgr, stride, W, H, tmp.data());
@@ -203,6 +205,40 @@ static int jpeg_code_host_planes(poppy_hip_ctx* c, int fmt, const uint8_t* i420,
 
 int poppy_hip_i420_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i420, int W, int H, int quality, uint8_t* dst) {
     return jpeg_code_host_planes(c, POPPY_FRAME_JPEG, i420, W, H, quality, dst);
+}
+
+// the body of poppy_hip_i420_to_jpeg_budget_frame and its I444 twin: the planes and the call's own budget words up, the search and the two coding kernels on the
+// context's tables of all qualities, `total` bytes down; the quality is read back from the frame's DQT
+static int jpeg_budget_code_host_planes(poppy_hip_ctx* c, int fmt, const uint8_t* planes, int W, int H, int quality_max, size_t budget, uint8_t* dst, int* quality_used) {
+    if (!c) return POPPY_E_ARG;
+    if (!planes || !dst || W <= 0 || H <= 0 || quality_max < 1 || quality_max > 100 || budget == 0 || budget > 0xffffffffull) return fail(c, POPPY_E_ARG, "bad arguments");
+    if (const char* why = format_refuses(fmt, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const FormatTraits& traits = *format_traits(fmt);
+    const size_t bytes = raster_bytes(traits.raster, W, H);
+    { int rc = ensure_jpeg_budget_tables(c); if (rc) return rc; }      // (the context's tables of all qualities; its own budget is neither read nor touched)
+    JpegBudget of_call;
+    of_call.tables = c->jpeg_budget_tables;
+    const JpegBudgetParams p{(uint32_t)budget, (uint32_t)quality_max};
+    CallBuffers held;                                              // (coded_from_device waits for the stream before it returns)
+    uint8_t *d_planes = nullptr, *d_params = nullptr;
+    HIPCHK(c, held.alloc(&d_planes, bytes + 16));
+    HIPCHK(c, held.alloc(&d_params, sizeof p));
+    if (hipMemcpy(d_planes, planes, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_params, &p, sizeof p, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(c, POPPY_E_DEVICE, "upload of the planes failed");
+    of_call.params = d_params;
+    std::vector<uint8_t> host;
+    const int rc = coded_from_device(c, traits, d_planes, nullptr, W, H, host, of_call);
+    if (rc != POPPY_OK) return rc;
+    memcpy(dst, host.data(), host.size());
+    if (quality_used) *quality_used = poppy_jpeg_frame_quality(dst);
+    return POPPY_OK;
+}
+int poppy_hip_i420_to_jpeg_budget_frame(poppy_hip_ctx* c, const uint8_t* i420, int W, int H, int quality_max, size_t budget, uint8_t* dst, int* quality_used) {
+    return jpeg_budget_code_host_planes(c, POPPY_FRAME_JPEG, i420, W, H, quality_max, budget, dst, quality_used);
+}
+int poppy_hip_i444_to_jpeg_budget_frame(poppy_hip_ctx* c, const uint8_t* i444, int W, int H, int quality_max, size_t budget, uint8_t* dst, int* quality_used) {
+    return jpeg_budget_code_host_planes(c, POPPY_FRAME_JPEG444, i444, W, H, quality_max, budget, dst, quality_used);
 }
 
 int poppy_hip_i444_to_jpeg_frame(poppy_hip_ctx* c, const uint8_t* i444, int W, int H, int quality, uint8_t* dst) {
