@@ -418,6 +418,39 @@ int poppy_hip_morph_frames(poppy_hip_ctx* ctx, double phase, poppy_write_cb writ
  * setting stays.  The other formats ignore the budget as they ignore the quality.  poppy_hip_pool_set_jpeg_budget sets every context of a pool (POPPY_E_STATE
  * with work submitted).  POPPY_SINK_MJPEG takes the frames as they are: every frame is a complete file, and the sink does not read DQT.
  *
+ * JPEG sequence budget: POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames whose files TOGETHER have at most B bytes, all coded at ONE quality — "this morph must come
+ * out under B bytes as a file", without the pumping of per-frame qualities and without the easy frames leaving their share unused.
+ * poppy_hip_set_jpeg_sequence_budget(ctx, B) sets it; 0 (the default) is off and leaves every frame, byte, launch and timing mark as it is without.
+ *   Sequence.  Exactly what it is under POPPY_FRAME_JPEG_SEQ: all frames one call hands to its writer; one pair's frames in poppy_hip_morph_list and in the
+ *      pools; the t == 0 / 1 copies of poppy_hip_render_phases and the phase 0 / 1 short-circuits count among them, N copies of one frame being its size N times.
+ *      The frames wait on the GPU as the planes of their sampling; the writer is first called after the last frame is rendered, and gets the frames in order.
+ *   Size.  size_k(q) is the per-frame budget's size: the JFIF file of frame k at quality q, `total` - 4, the bytes POPPY_SINK_MJPEG writes for it.  size(q) is the
+ *      sum of size_k(q) over the sequence's frames, in 64 bits.  A container's own bytes are NOT counted — the AVI's index and chunk headers are a constant per
+ *      frame, and a caller with a file-size target subtracts them from B itself: the rule is about the frames.
+ *   Search.  The per-frame budget's search, word for word, on size(q), with qmax the context's quality: qmax if size(qmax) <= B, otherwise the bisection from
+ *      (lo, hi) = (0, qmax), the result max(lo, 1).  The search is the rule, not "the highest quality that fits"; poppy_jpeg_budget_pick on the table of the sums
+ *      is its host statement, and B has no 32-bit limit.  At most 1 + ceil(log2(qmax)) qualities are asked about.
+ *   Output.  Every frame is byte for byte its POPPY_FRAME_JPEG (JPEG444) frame at the picked quality; the layout, the capacity, the smallest frame and stride 0 are
+ *      the format's.  poppy_jpeg_frame_quality reads the quality back from any of the frames.
+ *   A sequence of one frame is byte for byte that frame's per-frame-budget frame for the same B.
+ *   When nothing fits.  If not even quality 1 fits, the frames are the quality-1 frames, and the caller sees the overshoot from the `total`s.
+ * poppy_i420_frames_to_jpeg_seq_budget_frames and poppy_i444_frames_to_jpeg_seq_budget_frames are the host statements, poppy_bgr_frames_to_jpeg_seq_budget_frames
+ * and poppy_bgr_frames_to_jpeg444_seq_budget_frames the conversion followed by them: the arguments of poppy_i420_frames_to_jpeg_seq_frames /
+ * poppy_bgr_frames_to_jpeg_seq_frames with quality_max and budget in the quality's place; frame k goes to dst + k * poppy_frame_bytes(POPPY_FRAME_JPEG or
+ * POPPY_FRAME_JPEG444, width, height); quality_used (may be null) receives the one quality.  Refusals, all from the arguments alone: POPPY_E_ARG for what the
+ * _seq_frames functions refuse with it, quality_max outside 1..100 and budget 0; POPPY_E_UNSUPPORTED for JPEG's per-frame limits.  There is no limit on the
+ * sequence: a frame's capacity is below 2^32 and the frame count is an int, so the worst case always fits the 64-bit sums.
+ * poppy_hip_bgr_frames_to_jpeg_seq_budget_frames and poppy_hip_bgr_frames_to_jpeg444_seq_budget_frames give the same bytes and quality from the context's GPU, on
+ * a sequence that lives for the call (upload, raster kernel per frame, the search's steps of one measuring launch over all frames and one pick, the two coding
+ * kernels per frame, download of `total` bytes): no resident pair needed, none disturbed, the context's own settings neither read nor changed.
+ * poppy_hip_set_jpeg_sequence_budget follows poppy_hip_set_jpeg_budget's contract: POPPY_E_STATE while a sequence is open, the context's frames are drained first,
+ * and on a refusal the setting stays as it was; poppy_hip_get_jpeg_sequence_budget reads it.  A context has one of the two budgets: a positive sequence budget
+ * together with a positive per-frame budget, or with one of the four formats on built tables (_OPT, _SEQ), is refused with POPPY_E_UNSUPPORTED by whichever of
+ * poppy_hip_set_jpeg_sequence_budget, poppy_hip_set_jpeg_budget and poppy_hip_set_frame_format comes second, and the earlier setting stays.  It applies wherever
+ * POPPY_FRAME_JPEG_SEQ applies, under poppy_hip_set_frame_scale and poppy_hip_set_frame_size on the frames at the writer's geometry; every other format ignores
+ * it, and poppy_hip_morph_sharded and poppy_hip_morph_pairs stay BGR.  poppy_hip_pool_set_jpeg_sequence_budget sets every context of a pool (POPPY_E_STATE with
+ * work submitted).  POPPY_SINK_MJPEG takes the frames as they are.
+ *
  * POPPY_FRAME_PNG: the frame coded on the GPU as one PNG file, LOSSLESS: the file decodes to exactly the frame's pixels, at 1.5 - 3 times fewer bytes than BGR on
  * photograph-like frames.  Its value is 1024, and POPPY_SINK_PNG is 1024; 1023 and 1025 stay unknown in both enums.  Layout, little-endian:
  *     bytes 0..3     total: the whole frame's length in bytes, these four included (poppy_png_frame_bytes reads it)
@@ -600,6 +633,15 @@ int poppy_hip_i420_to_jpeg_budget_frame(poppy_hip_ctx* ctx, const uint8_t* i420,
 int poppy_hip_i444_to_jpeg_budget_frame(poppy_hip_ctx* ctx, const uint8_t* i444, int width, int height, int quality_max, size_t budget, uint8_t* dst, int* quality_used);
 int poppy_hip_set_jpeg_budget(poppy_hip_ctx* ctx, size_t max_frame_bytes);
 int poppy_hip_get_jpeg_budget(poppy_hip_ctx* ctx, size_t* max_frame_bytes);
+/* JPEG sequence budget (above): the host statements, the same from the context's GPU, and the setting; 0 (the default): off */
+int poppy_i420_frames_to_jpeg_seq_budget_frames(const uint8_t* i420, size_t frame_stride, int n_frames, int width, int height, int quality_max, uint64_t budget, uint8_t* dst, int* quality_used);
+int poppy_i444_frames_to_jpeg_seq_budget_frames(const uint8_t* i444, size_t frame_stride, int n_frames, int width, int height, int quality_max, uint64_t budget, uint8_t* dst, int* quality_used);
+int poppy_bgr_frames_to_jpeg_seq_budget_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality_max, uint64_t budget, uint8_t* dst, int* quality_used);
+int poppy_bgr_frames_to_jpeg444_seq_budget_frames(const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality_max, uint64_t budget, uint8_t* dst, int* quality_used);
+int poppy_hip_bgr_frames_to_jpeg_seq_budget_frames(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality_max, uint64_t budget, uint8_t* dst, int* quality_used);
+int poppy_hip_bgr_frames_to_jpeg444_seq_budget_frames(poppy_hip_ctx* ctx, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int width, int height, int quality_max, uint64_t budget, uint8_t* dst, int* quality_used);
+int poppy_hip_set_jpeg_sequence_budget(poppy_hip_ctx* ctx, uint64_t max_sequence_bytes);
+int poppy_hip_get_jpeg_sequence_budget(poppy_hip_ctx* ctx, uint64_t* max_sequence_bytes);
 int poppy_jpeg_optimal_table(const uint32_t counts[256], uint8_t bits[16], uint8_t vals[256], int* n_vals);
 int poppy_i420_to_jpeg_opt_frame(const uint8_t* i420, int width, int height, int quality, uint8_t* dst);
 int poppy_i444_to_jpeg_opt_frame(const uint8_t* i444, int width, int height, int quality, uint8_t* dst);
@@ -1178,6 +1220,8 @@ int poppy_hip_pool_set_frame_size(poppy_hip_pool* pool, int ow, int oh);
 int poppy_hip_pool_set_jpeg_quality(poppy_hip_pool* pool, int quality);
 /* poppy_hip_set_jpeg_budget on every context of the pool; POPPY_E_ARG above 2^32 - 1, POPPY_E_STATE as for the format. */
 int poppy_hip_pool_set_jpeg_budget(poppy_hip_pool* pool, size_t max_frame_bytes);
+/* poppy_hip_set_jpeg_sequence_budget on every context of the pool; POPPY_E_STATE as for the format. */
+int poppy_hip_pool_set_jpeg_sequence_budget(poppy_hip_pool* pool, uint64_t max_sequence_bytes);
 /* poppy_hip_mask_rider of the pool's contexts (they share settings and geometry) */
 int poppy_hip_pool_mask_rider(poppy_hip_pool* pool);
 /* The CLI's loop over an image list (src/poppy.cpp:266-328) on ONE context: pair k = (image k, image k + 1), where image k of pair k > 0 is

@@ -62,6 +62,9 @@ SYMBOLS = [
     "poppy_jpeg_budget_pick", "poppy_jpeg_frame_quality", "poppy_i420_to_jpeg_budget_frame", "poppy_i444_to_jpeg_budget_frame", "poppy_bgr_to_jpeg_budget_frame",
     "poppy_bgr_to_jpeg444_budget_frame", "poppy_hip_i420_to_jpeg_budget_frame", "poppy_hip_i444_to_jpeg_budget_frame", "poppy_hip_set_jpeg_budget",
     "poppy_hip_get_jpeg_budget", "poppy_hip_pool_set_jpeg_budget",
+    "poppy_i420_frames_to_jpeg_seq_budget_frames", "poppy_i444_frames_to_jpeg_seq_budget_frames", "poppy_bgr_frames_to_jpeg_seq_budget_frames",
+    "poppy_bgr_frames_to_jpeg444_seq_budget_frames", "poppy_hip_bgr_frames_to_jpeg_seq_budget_frames", "poppy_hip_bgr_frames_to_jpeg444_seq_budget_frames",
+    "poppy_hip_set_jpeg_sequence_budget", "poppy_hip_get_jpeg_sequence_budget", "poppy_hip_pool_set_jpeg_sequence_budget",
     "poppy_bgr_to_i444", "poppy_hip_bgr_to_i444", "poppy_i444_to_jpeg_frame", "poppy_bgr_to_jpeg444_frame", "poppy_hip_i444_to_jpeg_frame",
     "poppy_jpeg_optimal_table", "poppy_i420_to_jpeg_opt_frame", "poppy_i444_to_jpeg_opt_frame", "poppy_bgr_to_jpeg_opt_frame", "poppy_bgr_to_jpeg444_opt_frame",
     "poppy_hip_i420_to_jpeg_opt_frame", "poppy_hip_i444_to_jpeg_opt_frame", "poppy_hip_jpeg_optimal_table",
@@ -257,6 +260,16 @@ def lib():
         L.poppy_hip_set_jpeg_budget.argtypes = [vp, sz]
         L.poppy_hip_get_jpeg_budget.argtypes = [vp, vp]
         L.poppy_hip_pool_set_jpeg_budget.argtypes = [vp, sz]
+        u64 = C.c_uint64
+        L.poppy_i420_frames_to_jpeg_seq_budget_frames.argtypes = [vp, sz, i, i, i, i, u64, vp, vp]
+        L.poppy_i444_frames_to_jpeg_seq_budget_frames.argtypes = [vp, sz, i, i, i, i, u64, vp, vp]
+        L.poppy_bgr_frames_to_jpeg_seq_budget_frames.argtypes = [vp, sz, sz, i, i, i, i, u64, vp, vp]
+        L.poppy_bgr_frames_to_jpeg444_seq_budget_frames.argtypes = [vp, sz, sz, i, i, i, i, u64, vp, vp]
+        L.poppy_hip_bgr_frames_to_jpeg_seq_budget_frames.argtypes = [vp, vp, sz, sz, i, i, i, i, u64, vp, vp]
+        L.poppy_hip_bgr_frames_to_jpeg444_seq_budget_frames.argtypes = [vp, vp, sz, sz, i, i, i, i, u64, vp, vp]
+        L.poppy_hip_set_jpeg_sequence_budget.argtypes = [vp, u64]
+        L.poppy_hip_get_jpeg_sequence_budget.argtypes = [vp, vp]
+        L.poppy_hip_pool_set_jpeg_sequence_budget.argtypes = [vp, u64]
         L.poppy_jpeg_optimal_table.argtypes = [vp, vp, vp, vp]
         L.poppy_hip_jpeg_optimal_table.argtypes = [vp, vp, vp, vp, vp]
         L.poppy_i420_to_jpeg_opt_frame.argtypes = [vp, i, i, i, vp]
@@ -747,6 +760,48 @@ def bgr_frames_to_jpeg_seq_frames(frames, quality=JPEG_QUALITY_DEFAULT, fmt=FRAM
     return _jpeg_seq_frames(lambda dst: call(_p(a), stride, frame_stride, n, w, h, int(quality), dst), "bgr_frames_to_jpeg_seq_frames", fmt, n, w, h)
 
 
+def _jpeg_seq_budget_frames(call, what, fmt, n, w, h, chk=None):
+    """The frames of a JPEG sequence under a sequence budget out of call(dst, quality_used): (a list of n flat uint8 arrays, each cut to its `total`, the one
+    quality); fmt FRAME_JPEG or FRAME_JPEG444; chk: as in _coded_frame."""
+    if fmt not in (FRAME_JPEG, FRAME_JPEG444):
+        raise PoppyError(f"{what}: fmt is FRAME_JPEG or FRAME_JPEG444")
+    out = np.empty((max(n, 1), max(frame_bytes(fmt, w, h), 4)), np.uint8)
+    used = C.c_int(0)
+    rc = call(_p(out), C.byref(used))
+    if chk:
+        chk(rc, what)
+    elif rc:
+        raise PoppyError(f"poppy_{what}: {rc}")
+    return [f[:jpeg_frame_bytes(f)].copy() for f in out], used.value
+
+
+def bgr_frames_to_jpeg_seq_budget_frames(frames, quality_max, budget, fmt=FRAME_JPEG, row_pad=0, frame_pad=0):
+    """Host-only: (frames, quality used) of a sequence of n HxWx3 BGR frames whose FRAME_JPEG (fmt FRAME_JPEG444: 4:4:4) files together have at most `budget`
+    bytes, all at the one quality the budget's search picks at or below quality_max (poppy_bgr_frames_to_jpeg_seq_budget_frames,
+    poppy_bgr_frames_to_jpeg444_seq_budget_frames).  row_pad / frame_pad: as in bgr_frames_to_pal8."""
+    a, stride, frame_stride, n, w, h = _padded_frames(frames, row_pad, frame_pad)
+    call = lib().poppy_bgr_frames_to_jpeg444_seq_budget_frames if fmt == FRAME_JPEG444 else lib().poppy_bgr_frames_to_jpeg_seq_budget_frames
+    return _jpeg_seq_budget_frames(lambda dst, used: call(_p(a), stride, frame_stride, n, w, h, int(quality_max), int(budget), dst, used),
+                                   "bgr_frames_to_jpeg_seq_budget_frames", fmt, n, w, h)
+
+
+def planes_to_jpeg_seq_budget_frames(planes, w, h, quality_max, budget, fmt=FRAME_JPEG, frame_pad=0):
+    """Host-only: the same from the planes (poppy_i420_frames_to_jpeg_seq_budget_frames; fmt FRAME_JPEG444: poppy_i444_frames_to_jpeg_seq_budget_frames):
+    `planes` is n flat I420 (I444) frames, an n x bytes array; frame_pad: that many extra bytes between frames."""
+    a = np.ascontiguousarray(planes, np.uint8)
+    n, size = a.shape
+    want = 3 * w * h if fmt == FRAME_JPEG444 else frame_bytes(FRAME_I420, w, h)
+    if w > 0 and h > 0 and size != want:
+        raise PoppyError(f"planes_to_jpeg_seq_budget_frames: a frame of planes has {want} bytes")
+    if frame_pad:
+        buf = np.full((n, size + int(frame_pad)), 0xA5, np.uint8)
+        buf[:, :size] = a
+        a = buf
+    call = lib().poppy_i444_frames_to_jpeg_seq_budget_frames if fmt == FRAME_JPEG444 else lib().poppy_i420_frames_to_jpeg_seq_budget_frames
+    return _jpeg_seq_budget_frames(lambda dst, used: call(_p(a), a.shape[1], n, int(w), int(h), int(quality_max), int(budget), dst, used),
+                                   "planes_to_jpeg_seq_budget_frames", fmt, n, w, h)
+
+
 def planes_to_jpeg_seq_frames(planes, w, h, quality=JPEG_QUALITY_DEFAULT, fmt=FRAME_JPEG_SEQ, frame_pad=0):
     """Host-only: the same from the planes (poppy_i420_frames_to_jpeg_seq_frames; fmt FRAME_JPEG444_SEQ: poppy_i444_frames_to_jpeg_seq_frames): `planes` is n flat
     I420 (I444) frames, an n x bytes array; frame_pad: that many extra bytes between frames."""
@@ -1206,6 +1261,13 @@ class Pool:
         if rc:
             raise PoppyError(f"poppy_hip_pool_set_jpeg_budget: {rc}")
 
+    def set_jpeg_sequence_budget(self, max_sequence_bytes):
+        """The sequence budget of the FRAME_JPEG and FRAME_JPEG444 frames of every context of the pool, 0 for none (poppy_hip_pool_set_jpeg_sequence_budget);
+        PoppyError with the status on a refusal or while submitted batches have not been waited for."""
+        rc = lib().poppy_hip_pool_set_jpeg_sequence_budget(self.h, int(max_sequence_bytes))
+        if rc:
+            raise PoppyError(f"poppy_hip_pool_set_jpeg_sequence_budget: {rc}")
+
     def close(self):
         if self.h:
             lib().poppy_hip_pool_destroy(self.h)
@@ -1464,6 +1526,26 @@ class Context:
         v = C.c_size_t(0)
         self._chk(lib().poppy_hip_get_jpeg_budget(self.h, C.byref(v)), "get_jpeg_budget")
         return v.value
+
+    def set_jpeg_sequence_budget(self, max_sequence_bytes):
+        """The most bytes the files of all FRAME_JPEG or FRAME_JPEG444 frames of one sequence (a call's frames, a pair's) may have together, 0 (the default) for
+        none (poppy_hip_set_jpeg_sequence_budget): the frames wait on the GPU and are all coded at the one quality the search picks at or below set_jpeg_quality's."""
+        self._chk(lib().poppy_hip_set_jpeg_sequence_budget(self.h, int(max_sequence_bytes)), "set_jpeg_sequence_budget")
+
+    def get_jpeg_sequence_budget(self):
+        """The context's sequence budget (poppy_hip_get_jpeg_sequence_budget); 0: none."""
+        v = C.c_uint64(0)
+        self._chk(lib().poppy_hip_get_jpeg_sequence_budget(self.h, C.byref(v)), "get_jpeg_sequence_budget")
+        return v.value
+
+    def bgr_frames_to_jpeg_seq_budget_frames(self, frames, quality_max, budget, fmt=FRAME_JPEG, row_pad=0, frame_pad=0):
+        """(frames, quality used) of a sequence of HxWx3 BGR frames under a sequence budget, searched and coded on this context's GPU on a sequence that lives for
+        the call (poppy_hip_bgr_frames_to_jpeg_seq_budget_frames, poppy_hip_bgr_frames_to_jpeg444_seq_budget_frames): what the host's
+        bgr_frames_to_jpeg_seq_budget_frames gives."""
+        a, stride, frame_stride, n, w, h = _padded_frames(frames, row_pad, frame_pad)
+        call = lib().poppy_hip_bgr_frames_to_jpeg444_seq_budget_frames if fmt == FRAME_JPEG444 else lib().poppy_hip_bgr_frames_to_jpeg_seq_budget_frames
+        return _jpeg_seq_budget_frames(lambda dst, used: call(self.h, _p(a), stride, frame_stride, n, w, h, int(quality_max), int(budget), dst, used),
+                                       "bgr_frames_to_jpeg_seq_budget_frames", fmt, n, w, h, self._chk)
 
     def i420_to_jpeg_budget_frame(self, i420, w, h, quality_max, budget):
         """(frame, quality used) of a flat I420 frame under a byte budget, searched and coded on this context's GPU (poppy_hip_i420_to_jpeg_budget_frame): what the

@@ -126,6 +126,7 @@ struct poppy_hip_ctx {
     int jpeg_quality = POPPY_JPEG_QUALITY_DEFAULT;  // ... and the quality of the frames of the four JPEG formats (poppy_hip_set_jpeg_quality)
     size_t jpeg_budget = 0;                         // ... the most bytes a POPPY_FRAME_JPEG / JPEG444 frame's file may have (poppy_hip_set_jpeg_budget; 0: off), and what its search reads on
     uint8_t* jpeg_budget_tables = nullptr;          // the device (frame_format.h: context_jpeg_budget)
+    uint64_t jpeg_seq_budget = 0;                   // ... or the most bytes the files of a whole sequence of them may have together, at one quality (poppy_hip_set_jpeg_sequence_budget; 0: off; never beside jpeg_budget)
     uint8_t* jpeg_tables = nullptr;                 // ... with its header and quantiser tables on the device (frame_format.h: ensure_jpeg_tables; rewritten in place when the quality changes)
     int frame_ow = 0, frame_oh = 0;                 // ... or the size they are resized to (poppy_hip_set_frame_size; 0, 0: none; never beside a scale above 1)
     DeviceBuffer scale_scratch;                     // the scaled BGR of the copies and fallback frames that no slot renders (writer_image.h: scale_into_scratch)

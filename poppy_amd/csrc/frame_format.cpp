@@ -21,6 +21,7 @@ const char* format_refuses(int fmt, int W, int H) {
 }
 const char* sequence_refuses(int fmt, int n, int W, int H) {
     if (const char* why = format_refuses(fmt, W, H)) return why;
+    if (const FormatTraits* t = format_traits(fmt)) if (budget_applies(*t)) return nullptr;      // (POPPY_FRAME_JPEG / JPEG444 held back under a sequence budget: 64-bit sums, no limit beyond the frames' own)
     if (const FormatTraits* t = format_traits(fmt)) if (t->coder == kCoderJpeg) return jpeg_seq_fits(n, W, H, t->sampling()) ? nullptr : kJpegSeqSizeMsg;      // the symbol bound; the pixel bound is the palette sequences'
     if (const FormatTraits* t = format_traits(fmt)) if (t->coder == kCoderPng) return png_seq_fits(n, W, H) ? nullptr : kPngSeqSizeMsg;
     return (unsigned long long)n * (unsigned long long)W * (unsigned long long)H >= POPPY_PAL8_SEQ_MAX_PIXELS ? kSeqSizeMsg : nullptr;
@@ -44,7 +45,16 @@ void launch_writer_scaling(const WriterGeom& g, const uint8_t* src, uint8_t* dst
 }
 const char* scaling_mark(const WriterGeom& g) { return g.kind == kScaleSize ? "frame_resize" : "frame_scale"; }
 int writer_format(const poppy_hip_ctx* c, bool has_writer) { return has_writer ? c->frame_format : POPPY_FRAME_BGR; }
-bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer) { return has_writer && format_traits(c->frame_format)->sequence; }
+bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer) { return has_writer && writer_traits(c, c->frame_format).sequence; }
+// POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 under a sequence budget: their own records, held back as a sequence
+static constexpr FormatTraits kJpegBudgetSeq[2] = {
+    {POPPY_FRAME_JPEG,    "JPEG", kRasterI420, kCoderJpeg, poppy_hip::jpeg::k420, false, true, poppy_hip::jpeg::kFrameMinBytes},
+    {POPPY_FRAME_JPEG444, "JPEG", kRasterI444, kCoderJpeg, poppy_hip::jpeg::k444, false, true, poppy_hip::jpeg::kFrameMinBytes},
+};
+const FormatTraits& writer_traits(const poppy_hip_ctx* c, int fmt) {
+    const FormatTraits& t = *format_traits(fmt);
+    return c->jpeg_seq_budget && budget_applies(t) ? kJpegBudgetSeq[t.sampling() == poppy_hip::jpeg::k444] : t;
+}
 
 int alloc_zeroed_tables(poppy_hip_ctx* c, uint8_t** tables, size_t bytes) {
     if (*tables) return POPPY_OK;
@@ -81,9 +91,14 @@ int ensure_jpeg_tables(poppy_hip_ctx* c) {
 
 bool budget_applies(const FormatTraits& t) { return t.coder == kCoderJpeg && !t.frame_tables; }
 constexpr const char* kBudgetFormatMsg = "a JPEG byte budget is set, and the OPT and SEQ forms of the JPEG formats have no budget form: poppy_hip_set_jpeg_budget(ctx, 0) or another format first";
+constexpr const char* kSeqBudgetFormatMsg = "a JPEG sequence budget is set, and the OPT and SEQ forms of the JPEG formats have no budget form: poppy_hip_set_jpeg_sequence_budget(ctx, 0) or another format first";
+constexpr const char* kTwoBudgetsMsg = "a context has the JPEG byte budget per frame or per sequence, not both: set the other one to 0 first";
 
-static int write_budget_params(poppy_hip_ctx* c, size_t budget, int quality) {
-    const JpegBudgetParams p{(uint32_t)budget, (uint32_t)quality};
+// the words behind the 100 tables: the per-frame budget's, then (16 bytes on) the sequence budget's
+struct BudgetWords { JpegBudgetParams frame; uint32_t pad[2]; JpegSeqBudgetParams seq; };
+static_assert(offsetof(BudgetWords, seq) == 16 && sizeof(BudgetWords) == 32, "the two sets of words, each at an address that stays");
+static int write_budget_params(poppy_hip_ctx* c, size_t budget, uint64_t seq_budget, int quality) {
+    const BudgetWords p{{(uint32_t)budget, (uint32_t)quality}, {0, 0}, {(uint32_t)seq_budget, (uint32_t)quality, (uint32_t)(seq_budget >> 32), 0}};
     HIPCHK(c, hipMemcpy(c->jpeg_budget_tables + kJpegBudgetTableBytes, &p, sizeof p, hipMemcpyHostToDevice));
     return POPPY_OK;
 }
@@ -92,9 +107,15 @@ int ensure_jpeg_budget_tables(poppy_hip_ctx* c) {
     std::vector<jpeg::QualityTables> all(100);
     for (int q = 1; q <= 100; ++q) jpeg::fill_quality_tables(q, &all[(size_t)q - 1]);
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMalloc((void**)&c->jpeg_budget_tables, kJpegBudgetTableBytes + 16));
+    HIPCHK(c, hipMalloc((void**)&c->jpeg_budget_tables, kJpegBudgetTableBytes + sizeof(BudgetWords)));
     HIPCHK(c, hipMemcpy(c->jpeg_budget_tables, all.data(), kJpegBudgetTableBytes, hipMemcpyHostToDevice));
-    return write_budget_params(c, c->jpeg_budget, c->jpeg_quality);
+    return write_budget_params(c, c->jpeg_budget, c->jpeg_seq_budget, c->jpeg_quality);
+}
+int context_jpeg_seq_budget(poppy_hip_ctx* c, JpegBudget* out) {
+    *out = JpegBudget();
+    { int rc = ensure_jpeg_budget_tables(c); if (rc) return rc; }
+    out->tables = c->jpeg_budget_tables; out->params = c->jpeg_budget_tables + kJpegBudgetTableBytes + offsetof(BudgetWords, seq);
+    return POPPY_OK;
 }
 int context_jpeg_budget(poppy_hip_ctx* c, const FormatTraits& t, JpegBudget* out) {
     *out = JpegBudget();
@@ -134,7 +155,7 @@ int alloc_slot_format(poppy_hip_ctx* c) {
     const WriterGeom g = writer_geom(c);
     const int fmt = c->frame_format, W = g.w, H = g.h;
     if (const char* why = writer_refuses(c, fmt, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
-    const FormatTraits& t = *format_traits(fmt);
+    const FormatTraits& t = writer_traits(c, fmt);
     const FrameRaster raster = t.slot_raster();
     for (FrameSlot& slot : c->slots) {
         SlotFormat& f = slot.fmt;
@@ -167,6 +188,7 @@ int alloc_slot_format(poppy_hip_ctx* c) {
         return POPPY_OK;
     }
     if (t.coder != kCoderJpeg) return alloc_zeroed_tables(c, &c->seq.tables, kPal8SeqTableBytes);
+    if (!t.frame_tables) return ensure_jpeg_budget_tables(c);      // JPEG under a sequence budget: the tables of all qualities and the budget's words (the search's state and lengths: seq_begin)
     { int rc = ensure_jpeg_tables(c); if (rc) return rc; }         // a JPEG sequence: the quality's tables, and the sequence's counts (zero) and built tables
     if (c->seq.jpeg) return POPPY_OK;
     HIPCHK(c, hipMalloc((void**)&c->seq.jpeg, kJpegSeqTableBytes));
@@ -184,7 +206,7 @@ void free_slot_format_ctx(SlotFormat& f) {
     if (f.bgr_done) (void)hipEventDestroy(f.bgr_done);
 }
 void free_context_format(poppy_hip_ctx* c) {
-    for (DeviceBuffer* b : {&c->scale_scratch, &c->fmt_scratch, &c->seq.store, &c->seq.idx, &c->seq.coded}) b->release();
+    for (DeviceBuffer* b : {&c->scale_scratch, &c->fmt_scratch, &c->seq.store, &c->seq.idx, &c->seq.coded, &c->seq.budget}) b->release();
     for (uint8_t* b : {c->fmt_scratch_tables, c->seq.tables, c->seq.jpeg, c->seq.png, c->jpeg_tables, c->jpeg_budget_tables}) if (b) (void)hipFree(b);
     c->jpeg_tables = c->jpeg_budget_tables = nullptr;
     if (c->seq.coded_total) (void)hipHostFree(c->seq.coded_total);
@@ -194,9 +216,10 @@ void free_context_format(poppy_hip_ctx* c) {
 
 bool slot_format_ready(const poppy_hip_ctx* c, const FrameSlot& slot, int fmt, const WriterGeom& g) {
     const SlotFormat& f = slot.fmt;
-    const FormatTraits& t = *format_traits(fmt);
+    const FormatTraits& t = writer_traits(c, fmt);
     const FrameRaster raster = t.slot_raster();
     if (g.scaled() && !f.scaled) return false;
+    if (t.sequence && t.coder == kCoderJpeg && !t.frame_tables) return c->seq.open && c->jpeg_budget_tables && c->seq.budget.p;      // (under a sequence budget: the same)
     if (t.sequence && t.coder == kCoderJpeg) return c->seq.open && c->seq.jpeg && c->jpeg_tables;      // (its pass runs on the frame's own stream: enqueue_body)
     if (t.sequence && t.coder == kCoderPng) return c->seq.open && c->seq.png;      // (the same)
     if (t.sequence) return c->seq.open && c->seq.tables && f.fmt_stream && f.bgr_done;
@@ -312,6 +335,7 @@ int poppy_hip_set_frame_format(poppy_hip_ctx* c, int format) {
     { int rc = drain_frames(c); if (rc) return rc; }
     if (c->c1) if (const char* why = writer_refuses(c, format, c->W, c->H)) return fail(c, POPPY_E_UNSUPPORTED, why);
     if (c->jpeg_budget && format_traits(format)->coder == kCoderJpeg && !budget_applies(*format_traits(format))) return fail(c, POPPY_E_UNSUPPORTED, kBudgetFormatMsg);
+    if (c->jpeg_seq_budget && format_traits(format)->coder == kCoderJpeg && !budget_applies(*format_traits(format))) return fail(c, POPPY_E_UNSUPPORTED, kSeqBudgetFormatMsg);
     c->frame_format = format;
     return c->c1 ? alloc_slot_format(c) : POPPY_OK;      // (a pair allocated later gets them in alloc_pair)
 }
@@ -330,7 +354,7 @@ int poppy_hip_set_jpeg_quality(poppy_hip_ctx* c, int quality) {
         jpeg::fill_quality_tables(quality, &t);
         HIPCHK(c, hipMemcpy(c->jpeg_tables, &t, sizeof t, hipMemcpyHostToDevice));
     }
-    if (c->jpeg_budget_tables) { int rc = write_budget_params(c, c->jpeg_budget, quality); if (rc) return rc; }      // (the search's highest quality)
+    if (c->jpeg_budget_tables) { int rc = write_budget_params(c, c->jpeg_budget, c->jpeg_seq_budget, quality); if (rc) return rc; }      // (the search's highest quality)
     c->jpeg_quality = quality;
     return POPPY_OK;
 }
@@ -346,8 +370,9 @@ int poppy_hip_set_jpeg_budget(poppy_hip_ctx* c, size_t max_frame_bytes) {
     { int rc = drain_frames(c); if (rc) return rc; }
     const FormatTraits& t = *format_traits(c->frame_format);
     if (max_frame_bytes && t.coder == kCoderJpeg && !budget_applies(t)) return fail(c, POPPY_E_UNSUPPORTED, kBudgetFormatMsg);
+    if (max_frame_bytes && c->jpeg_seq_budget) return fail(c, POPPY_E_UNSUPPORTED, kTwoBudgetsMsg);
     if (max_frame_bytes == c->jpeg_budget) return POPPY_OK;
-    if (c->jpeg_budget_tables) { int rc = write_budget_params(c, max_frame_bytes, c->jpeg_quality); if (rc) return rc; }
+    if (c->jpeg_budget_tables) { int rc = write_budget_params(c, max_frame_bytes, c->jpeg_seq_budget, c->jpeg_quality); if (rc) return rc; }
     c->jpeg_budget = max_frame_bytes;
     for (FrameSlot& f : c->slots) {
         int rc = context_jpeg_budget(c, t, &f.fmt.jpeg_budget); if (rc) return rc;
@@ -359,6 +384,30 @@ int poppy_hip_get_jpeg_budget(poppy_hip_ctx* c, size_t* max_frame_bytes) {
     if (!c) return POPPY_E_ARG;
     if (!max_frame_bytes) return fail(c, POPPY_E_ARG, "bad arguments");
     *max_frame_bytes = c->jpeg_budget;
+    return POPPY_OK;
+}
+
+// The sequence budget is the 64-bit word of JpegSeqBudgetParams that the sequence's pick reads, at an address that stays: rewritten once nothing reads it.  On and
+// off differ in who converts a frame — the sequence pass into the store, or the slot's own conversion —: the slots' buffers are allocated for the new state, and a
+// slot's captured body, which records the format it converts to (BGR under a sequence), is captured again by the next frame that wants the other.
+int poppy_hip_set_jpeg_sequence_budget(poppy_hip_ctx* c, uint64_t max_sequence_bytes) {
+    if (!c) return POPPY_E_ARG;
+    if (c->seq.open) return fail(c, POPPY_E_STATE, "a sequence is open on this context");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = drain_frames(c); if (rc) return rc; }
+    const FormatTraits& t = *format_traits(c->frame_format);
+    if (max_sequence_bytes && t.coder == kCoderJpeg && !budget_applies(t)) return fail(c, POPPY_E_UNSUPPORTED, kSeqBudgetFormatMsg);
+    if (max_sequence_bytes && c->jpeg_budget) return fail(c, POPPY_E_UNSUPPORTED, kTwoBudgetsMsg);
+    if (max_sequence_bytes == c->jpeg_seq_budget) return POPPY_OK;
+    if (c->jpeg_budget_tables) { int rc = write_budget_params(c, c->jpeg_budget, max_sequence_bytes, c->jpeg_quality); if (rc) return rc; }
+    c->jpeg_seq_budget = max_sequence_bytes;
+    return c->c1 ? alloc_slot_format(c) : POPPY_OK;      // (a pair allocated later gets its buffers in alloc_pair)
+}
+
+int poppy_hip_get_jpeg_sequence_budget(poppy_hip_ctx* c, uint64_t* max_sequence_bytes) {
+    if (!c) return POPPY_E_ARG;
+    if (!max_sequence_bytes) return fail(c, POPPY_E_ARG, "bad arguments");
+    *max_sequence_bytes = c->jpeg_seq_budget;
     return POPPY_OK;
 }
 

@@ -34,6 +34,10 @@ void launch_writer_scaling(const WriterGeom& g, const uint8_t* src, uint8_t* dst
 const char* scaling_mark(const WriterGeom& g);      // its name in timing mode 1: frame_scale or frame_resize
 int writer_format(const poppy_hip_ctx* c, bool has_writer);      // the format of the frames a call hands to its writer (none: they stay BGR in HBM), and whether they are collected into one palette sequence first
 bool writer_wants_sequence(const poppy_hip_ctx* c, bool has_writer);
+// The record of format `fmt` as the context's writer gets it: the format's own, except that under a sequence budget (poppy_hip_set_jpeg_sequence_budget) POPPY_FRAME_JPEG
+// and POPPY_FRAME_JPEG444 are held back as a sequence — the same frames, capacity and smallest frame on the Annex K tables, `sequence` set: no slot converts or
+// codes them, the sequence pass stores their planes and the sequence's search and coder do the rest (palette_seq.h).
+const FormatTraits& writer_traits(const poppy_hip_ctx* c, int fmt);
 const char* sequence_refuses(int fmt, int n, int W, int H);      // ... and why a sequence of n such frames is refused, or null
 
 struct SlotFormat {
@@ -85,6 +89,9 @@ int ensure_jpeg_tables(poppy_hip_ctx* c);
 // or for a format the budget does not apply to.
 int context_jpeg_budget(poppy_hip_ctx* c, const FormatTraits& t, poppy_hip::JpegBudget* out);
 int ensure_jpeg_budget_tables(poppy_hip_ctx* c);      // ... the allocation alone (c->jpeg_budget_tables), for a call that brings its own words
+// ... and the sequence budget's: the same tables, and the words (JpegSeqBudgetParams: the 64-bit budget, the highest quality) that stand behind the per-frame budget's
+// in the same allocation, rewritten by the setters once the frames are drained
+int context_jpeg_seq_budget(poppy_hip_ctx* c, poppy_hip::JpegBudget* out);
 bool budget_applies(const FormatTraits& t);      // POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444; (the four formats on built tables refuse a budget: poppy_hip_set_frame_format and poppy_hip_set_jpeg_budget, whichever comes second)
 // conversion tables, zero before the first frame (the palette builds leave them zero again): PAL8's per slot and for the scratch, the sequence's per context
 int alloc_zeroed_tables(poppy_hip_ctx* c, uint8_t** tables, size_t bytes);

@@ -1,5 +1,5 @@
 // frame_jpeg_budget.cpp — POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 frames that fit a byte budget (include/poppy_hip.h, "JPEG byte budget", has the rule) in plain
-// C++: the search over the qualities, written once (budget_search), the four host statements on top of frame_jpeg.cpp's coder, and poppy_jpeg_frame_quality,
+// C++: the search over the qualities on a table (the search itself is written once, jpeg_tables.h: budget_search), the four host statements on top of frame_jpeg.cpp's coder, and poppy_jpeg_frame_quality,
 // which reads a frame's quality back from its DQT.  kernels_frame_jpeg.hip (k_jpeg_measure, k_jpeg_pick) runs the same search on the device; the bytes are equal.
 // Host only, integer arithmetic only.
 #include "frame_limits.h"
@@ -10,18 +10,7 @@ namespace jpeg {
 
 namespace {
 
-// The rule.  size(q): the JFIF file's length at quality q, asked about at most 1 + ceil(log2(quality_max)) times.
-template <class Size>
-int budget_search(Size size, int quality_max, size_t budget) {
-    if (size(quality_max) <= budget) return quality_max;
-    int lo = 0, hi = quality_max;                           // hi is known not to fit; lo = 0: nothing known to fit
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (size(mid) <= budget) lo = mid; else hi = mid;
-    }
-    return lo > 1 ? lo : 1;
-}
-
+// (the rule itself is jpeg_tables.h's budget_search; size(q) here: the JFIF file's length at quality q)
 int planes_to_budget_frame(const uint8_t* planes, int width, int height, int quality_max, size_t budget, Sampling s, uint8_t* dst, int* quality_used) {
     if (!planes || !dst || width <= 0 || height <= 0 || quality_max < 1 || quality_max > 100 || budget == 0 || budget > 0xffffffffull) return POPPY_E_ARG;
     if (!jpeg_fits(width, height, s)) return POPPY_E_UNSUPPORTED;

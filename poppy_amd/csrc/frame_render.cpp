@@ -8,7 +8,7 @@ static_assert(kPlanRasterRows == kRasterChunkRows, "the plan's work list and k_r
 
 // the format the frames being submitted are converted to for their writer (their slots' bodies end with the conversion); BGR: none
 // (PAL8_SEQ, GIF_SEQ: none either — the sequence pass is launched behind the body, its destination differs from frame to frame: render_slot)
-static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached && !format_traits(c->frame_format)->sequence ? c->frame_format : POPPY_FRAME_BGR; }
+static int frame_wants_format(const poppy_hip_ctx* c) { return c->writer_attached && !writer_traits(c, c->frame_format).sequence ? c->frame_format : POPPY_FRAME_BGR; }
 // ... and the geometry they are scaled down or resized to in front of it, under every format (the sequence formats' pass reads the scaled frame)
 // ... and whether its conversion runs the JPEG byte budget's search (what enqueue_conversion reads: the slot's budget, under a format that applies it)
 static bool frame_wants_budget(const poppy_hip_ctx* c, const FrameSlot& f) { return budget_applies(*format_traits(frame_wants_format(c))) && (bool)f.fmt.jpeg_budget; }

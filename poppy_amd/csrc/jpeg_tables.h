@@ -148,5 +148,18 @@ size_t encode_planes_opt(const uint8_t* planes, int w, int h, int quality, Sampl
 // `copies` of itself in the sums (the phase 0 / 1 copies; otherwise 1); frame k goes to dst + k * dst_stride
 void encode_planes_seq(const uint8_t* planes, size_t frame_stride, int n, int copies, int w, int h, int quality, Sampling s, uint8_t* dst, size_t dst_stride);
 
+// ---- the byte budgets (include/poppy_hip.h, "JPEG byte budget" and "JPEG sequence budget"): the rule, written once.  size(q): the length in bytes of what the
+// budget is about at quality q — a frame's file, or the sum of a sequence's files —, asked about at most 1 + ceil(log2(quality_max)) times. ----
+template <class Size>
+int budget_search(Size size, int quality_max, unsigned long long budget) {
+    if (size(quality_max) <= budget) return quality_max;
+    int lo = 0, hi = quality_max;                           // hi is known not to fit; lo = 0: nothing known to fit
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (size(mid) <= budget) lo = mid; else hi = mid;
+    }
+    return lo > 1 ? lo : 1;
+}
+
 }  // namespace jpeg
 }  // namespace poppy_hip

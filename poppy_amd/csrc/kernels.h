@@ -320,6 +320,18 @@ void launch_jpeg_measure(const uint8_t* planes, const JpegBudget& budget, uint8_
 void launch_jpeg_pick(const JpegBudget& budget, uint8_t* scratch, int step, int w, int h, jpeg::Sampling sm, hipStream_t s);
 void launch_jpeg_code_picked(const uint8_t* planes, const JpegBudget& budget, uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
 void launch_jpeg_pack_picked(const JpegBudget& budget, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, jpeg::Sampling sm, hipStream_t s, hipEvent_t done = nullptr);
+// The same two formats under a sequence budget (include/poppy_hip.h, "JPEG sequence budget"): ONE search for the n_frames frames that wait as planes in a store,
+// frame_stride bytes apart.  Per step launch_jpeg_seq_measure (the measuring kernel over segments x frames: one launch, several only beyond 32768 frames; lengths at
+// measured[(k * n_frames + frame) * n_seg + seg]) and launch_jpeg_seq_pick (one workgroup: every frame's lengths, markers and header summed per quality in 64 bits,
+// compared with the 64-bit budget, the one search advanced).  `state` (jpeg_seq_budget_bytes: the search's state, then the measured lengths) is the sequence's;
+// budget.params points at a JpegSeqBudgetParams in device memory.  Every frame is then coded by launch_jpeg_code_picked_by / launch_jpeg_pack_picked_by on its own scratch
+// (jpeg_scratch_bytes, not opt), the picked quality read from `state`.  No kernel argument names a setting here either.
+struct JpegSeqBudgetParams { uint32_t budget_low, quality_max, budget_high, pad; };      // (the first two words where JpegBudgetParams has them)
+size_t jpeg_seq_budget_bytes(int n_frames, int w, int h, jpeg::Sampling sm);
+void launch_jpeg_seq_measure(const uint8_t* store, size_t frame_stride, int n_frames, const JpegBudget& budget, uint8_t* state, int step, int w, int h, jpeg::Sampling sm, hipStream_t s);
+void launch_jpeg_seq_pick(const JpegBudget& budget, uint8_t* state, int n_frames, int step, int w, int h, jpeg::Sampling sm, hipStream_t s);
+void launch_jpeg_code_picked_by(const uint8_t* planes, const JpegBudget& budget, const uint8_t* state, uint8_t* scratch, int w, int h, jpeg::Sampling sm, hipStream_t s);
+void launch_jpeg_pack_picked_by(const JpegBudget& budget, const uint8_t* state, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, jpeg::Sampling sm, hipStream_t s, hipEvent_t done = nullptr);
 
 // a frame on the device (tight BGR) -> its I444 planes, 3 * w * h bytes (kernels_frame_i444.hip; poppy_bgr_to_i444 is the host statement): any w, h >= 1; `done`
 // (optional) rides on the dispatch

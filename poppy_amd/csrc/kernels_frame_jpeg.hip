@@ -43,6 +43,11 @@
 //                  FF bytes: every segment's exact byte length at that quality.  The tables of all 100 qualities, the budget and the highest quality are device memory.
 //   k_jpeg_pick    one workgroup: the file's size at each measured quality, the search's interval advanced by the rule; at its end the picked quality, in the scratch.
 //   k_jpeg_code, k_jpeg_pack   once, on the picked quality's entry of the 100 tables (an index read from the scratch).
+//
+// The same two formats under a SEQUENCE budget (poppy_hip_set_jpeg_sequence_budget; frame_jpeg_seq_budget.cpp is the host statement) run ONE search for all the
+// frames of a sequence, which wait as planes in a store: per step one k_jpeg_measure over segments x frames (blockIdx.y: the frame) and one k_jpeg_pick that sums
+// every frame's lengths per quality in 64 bits against the 64-bit budget of JpegSeqBudgetParams; the search's state is the sequence's, not a frame's scratch, and
+// every frame's k_jpeg_code and k_jpeg_pack then read the picked quality from there.
 #include "kernels.h"
 #include <hip/hip_ext.h>
 #include <algorithm>
@@ -327,12 +332,16 @@ __global__ void __launch_bounds__(64) k_jpeg_code(const uint8_t* __restrict__ i4
 
 // The coder without its stores, at the qualities of one step of the budget's search (probe_list): a segment per wave and a block per lane as in k_jpeg_code, the
 // samples and the DCT once, the 64 coefficients in front of the quantiser kept in the lane's registers, and per quality the quantiser, the bit string in LDS and
-// the count of its FF bytes — the segment's exact byte length, into measured[k * n_seg + seg].  `tables`: all 100 qualities'.
+// the count of its FF bytes — the segment's exact byte length, into measured[(k * n_frames + frame) * n_seg + seg].  `tables`: all 100 qualities'.
+// A frame alone: n_frames 1 on a grid of n_seg.  A sequence's store: the grid is n_seg x frames, frame frame0 + blockIdx.y has its planes frame_stride bytes
+// behind the frame before it.
 template <Sampling S>
 __global__ void __launch_bounds__(64) k_jpeg_measure(const uint8_t* __restrict__ i420, const QualityTables* __restrict__ tables, const JpegBudgetParams* __restrict__ params,
-                                                     const BudgetSearch* __restrict__ search, uint32_t* __restrict__ measured, int first, int w, int h, int mw, int n_mcu, int n_seg) {
+                                                     const BudgetSearch* __restrict__ search, uint32_t* __restrict__ measured, int first, int w, int h, int mw, int n_mcu, int n_seg,
+                                                     size_t frame_stride, int frame0, int n_frames) {
     __shared__ CoderLds<kBitWords> L;
-    const int lane = threadIdx.x, seg = blockIdx.x;
+    const int lane = threadIdx.x, seg = blockIdx.x, frame = frame0 + (int)blockIdx.y;
+    i420 += (size_t)frame * frame_stride;
     int lo, hi, list[kBudgetListMax];
     if (!search_state(params, search, first != 0, &lo, &hi)) return;      // (uniform: the search is over)
     const int n = probe_list(lo, hi, first != 0, list);
@@ -354,15 +363,18 @@ __global__ void __launch_bounds__(64) k_jpeg_measure(const uint8_t* __restrict__
             const uint32_t byte = i < n_bytes ? (L.bits[i >> 2] >> (24 - 8 * (i & 3))) & 255u : 0u;
             n_ff += (uint32_t)__popcll(__ballot(byte == 255u));
         }
-        if (lane == 0) measured[(size_t)k * n_seg + seg] = n_bytes + n_ff;
+        if (lane == 0) measured[((size_t)k * n_frames + frame) * n_seg + seg] = n_bytes + n_ff;
         wave_sync();                                        // (the next quality's quantiser, coefficients and bits go where this one's were read)
     }
 }
 
 // One workgroup: size(q) of every quality the step measured — the header, the segments' lengths with their two marker bytes each; the file, not `total` — and
 // the search advanced by the rule over the step's levels.  Leaves the next step's (lo, hi), or the frame's quality in `picked`.
+// SEQ: size(q) is the sum over the n_frames frames of a sequence (n_frames headers, n_frames x n_seg lengths per quality, integers: no order changes the sum) and the
+// budget is the 64 bits of JpegSeqBudgetParams, whose first two words are laid out as JpegBudgetParams' (search_state reads the highest quality from either).
+template <bool SEQ>
 __global__ void __launch_bounds__(256) k_jpeg_pick(const JpegBudgetParams* __restrict__ params, BudgetSearch* __restrict__ search, const uint32_t* __restrict__ measured,
-                                                   int first, int n_seg) {
+                                                   int first, int n_seg, int n_frames) {
     __shared__ unsigned long long s_part[kBudgetListMax][4];
     int lo, hi, list[kBudgetListMax];
     if (!search_state(params, search, first != 0, &lo, &hi)) return;
@@ -370,16 +382,22 @@ __global__ void __launch_bounds__(256) k_jpeg_pick(const JpegBudgetParams* __res
     const int t = threadIdx.x;
     for (int k = 0; k < n; ++k) {
         unsigned long long sum = 0;
-        for (int i = t; i < n_seg; i += 256) sum += measured[(size_t)k * n_seg + i] + 2;
+        const size_t n_len = (size_t)(SEQ ? n_frames : 1) * (size_t)n_seg;
+        for (size_t i = t; i < n_len; i += 256) sum += measured[(size_t)k * n_len + i] + 2;
         #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
         if ((t & 63) == 0) s_part[k][t >> 6] = sum;
     }
     __syncthreads();
     if (t != 0) return;
-    const unsigned long long budget = params->budget;
+    unsigned long long budget = params->budget, headers = kHeaderBytes;
+    if constexpr (SEQ) {
+        const JpegSeqBudgetParams* sp = (const JpegSeqBudgetParams*)params;
+        budget = (unsigned long long)sp->budget_low | (unsigned long long)sp->budget_high << 32;
+        headers = (unsigned long long)kHeaderBytes * (unsigned long long)n_frames;
+    }
     auto fits = [&](int q) {                                // (q is in the list: the list is the tree's levels that the walk below takes)
-        for (int k = 0; k < n; ++k) if (list[k] == q) return (unsigned long long)kHeaderBytes + s_part[k][0] + s_part[k][1] + s_part[k][2] + s_part[k][3] <= budget;
+        for (int k = 0; k < n; ++k) if (list[k] == q) return headers + s_part[k][0] + s_part[k][1] + s_part[k][2] + s_part[k][3] <= budget;
         return false;
     };
     uint32_t picked = 0;
@@ -683,18 +701,46 @@ void launch_jpeg_measure(const uint8_t* planes, const JpegBudget& budget, uint8_
     const int mw = (w + mcu_side(sm) - 1) / mcu_side(sm);
     hipLaunchKernelGGL(sm == k444 ? k_jpeg_measure<k444> : k_jpeg_measure<k420>, dim3((unsigned)n_seg), dim3(64), 0, s, planes, (const QualityTables*)budget.tables,
                        (const JpegBudgetParams*)budget.params, (const BudgetSearch*)jpeg_budget_search(scratch, n_seg), jpeg_budget_measured(scratch, n_seg), (int)(step == 0), w, h, mw,
-                       (int)mcu_count((size_t)w, (size_t)h, sm), (int)n_seg);
+                       (int)mcu_count((size_t)w, (size_t)h, sm), (int)n_seg, (size_t)0, 0, 1);
 }
 void launch_jpeg_pick(const JpegBudget& budget, uint8_t* scratch, int step, int w, int h, Sampling sm, hipStream_t s) {
     const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
-    hipLaunchKernelGGL(k_jpeg_pick, dim3(1), dim3(256), 0, s, (const JpegBudgetParams*)budget.params, jpeg_budget_search(scratch, n_seg), (const uint32_t*)jpeg_budget_measured(scratch, n_seg),
-                       (int)(step == 0), (int)n_seg);
+    hipLaunchKernelGGL(k_jpeg_pick<false>, dim3(1), dim3(256), 0, s, (const JpegBudgetParams*)budget.params, jpeg_budget_search(scratch, n_seg), (const uint32_t*)jpeg_budget_measured(scratch, n_seg),
+                       (int)(step == 0), (int)n_seg, 1);
+}
+// (the picked quality is read from `state`: the frame's own search state in its scratch, or a sequence's)
+void launch_jpeg_code_picked_by(const uint8_t* planes, const JpegBudget& budget, const uint8_t* state, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
+    launch_jpeg_code_with(planes, budget.tables, nullptr, (const BudgetSearch*)state, scratch, w, h, sm, s);
+}
+void launch_jpeg_pack_picked_by(const JpegBudget& budget, const uint8_t* state, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, hipStream_t s, hipEvent_t done) {
+    launch_jpeg_pack_with(budget.tables, nullptr, (const BudgetSearch*)state, scratch, frame, total_host, w, h, sm, s, done);
 }
 void launch_jpeg_code_picked(const uint8_t* planes, const JpegBudget& budget, uint8_t* scratch, int w, int h, Sampling sm, hipStream_t s) {
-    launch_jpeg_code_with(planes, budget.tables, nullptr, jpeg_budget_search(scratch, segment_count((size_t)w, (size_t)h, sm)), scratch, w, h, sm, s);
+    launch_jpeg_code_picked_by(planes, budget, (const uint8_t*)jpeg_budget_search(scratch, segment_count((size_t)w, (size_t)h, sm)), scratch, w, h, sm, s);
 }
 void launch_jpeg_pack_picked(const JpegBudget& budget, const uint8_t* scratch, uint8_t* frame, uint32_t* total_host, int w, int h, Sampling sm, hipStream_t s, hipEvent_t done) {
-    launch_jpeg_pack_with(budget.tables, nullptr, jpeg_budget_search(const_cast<uint8_t*>(scratch), segment_count((size_t)w, (size_t)h, sm)), scratch, frame, total_host, w, h, sm, s, done);
+    launch_jpeg_pack_picked_by(budget, (const uint8_t*)jpeg_budget_search(const_cast<uint8_t*>(scratch), segment_count((size_t)w, (size_t)h, sm)), scratch, frame, total_host, w, h, sm, s, done);
+}
+
+// ---- the sequence budget: the same steps once for all the frames of a store, the search's state and the measured lengths in `state` (jpeg_seq_budget_bytes) ----
+static_assert(offsetof(JpegSeqBudgetParams, quality_max) == offsetof(JpegBudgetParams, quality_max) && sizeof(JpegSeqBudgetParams) == 16, "search_state reads the highest quality from either");
+namespace {
+constexpr int kSeqMeasureFrames = 32768;                    // frames of one measuring launch (a grid's second dimension ends at 65535): a longer sequence takes several per step
+}
+size_t jpeg_seq_budget_bytes(int n_frames, int w, int h, Sampling sm) {
+    return sizeof(BudgetSearch) + (size_t)n_frames * segment_count((size_t)w, (size_t)h, sm) * 4 * kBudgetListMax + 16;
+}
+void launch_jpeg_seq_measure(const uint8_t* store, size_t frame_stride, int n_frames, const JpegBudget& budget, uint8_t* state, int step, int w, int h, Sampling sm, hipStream_t s) {
+    const size_t n_seg = segment_count((size_t)w, (size_t)h, sm);
+    const int mw = (w + mcu_side(sm) - 1) / mcu_side(sm);
+    for (int frame0 = 0; frame0 < n_frames; frame0 += kSeqMeasureFrames)
+        hipLaunchKernelGGL(sm == k444 ? k_jpeg_measure<k444> : k_jpeg_measure<k420>, dim3((unsigned)n_seg, (unsigned)std::min(kSeqMeasureFrames, n_frames - frame0)), dim3(64), 0, s, store,
+                           (const QualityTables*)budget.tables, (const JpegBudgetParams*)budget.params, (const BudgetSearch*)state, (uint32_t*)(state + sizeof(BudgetSearch)), (int)(step == 0), w, h, mw,
+                           (int)mcu_count((size_t)w, (size_t)h, sm), (int)n_seg, frame_stride, frame0, n_frames);
+}
+void launch_jpeg_seq_pick(const JpegBudget& budget, uint8_t* state, int n_frames, int step, int w, int h, Sampling sm, hipStream_t s) {
+    hipLaunchKernelGGL(k_jpeg_pick<true>, dim3(1), dim3(256), 0, s, (const JpegBudgetParams*)budget.params, (BudgetSearch*)state, (const uint32_t*)(state + sizeof(BudgetSearch)),
+                       (int)(step == 0), (int)segment_count((size_t)w, (size_t)h, sm), n_frames);
 }
 
 }  // namespace poppy_hip

@@ -6,6 +6,8 @@
 
 // the context's sequence under a JPEG format: its record's sampling, its counts and its built tables (PaletteSeq::jpeg)
 static bool seq_is_jpeg(const poppy_hip_ctx* c) { return format_traits(c->frame_format)->coder == kCoderJpeg; }
+// ... under POPPY_FRAME_JPEG / JPEG444 with a sequence budget: no counts and no built tables, the sequence's search instead (PaletteSeq::budget)
+static bool seq_is_budget(const poppy_hip_ctx* c) { const FormatTraits& t = writer_traits(c, c->frame_format); return t.coder == kCoderJpeg && !t.frame_tables; }
 static uint32_t* seq_jpeg_counts(const PaletteSeq& q) { return (uint32_t*)q.jpeg; }
 static const void* seq_jpeg_built(const PaletteSeq& q) { return q.jpeg + sizeof(jpeg::SymbolCounts); }
 // ... under PNG: its sums and its built table (PaletteSeq::png)
@@ -24,7 +26,9 @@ int seq_begin(poppy_hip_ctx* c, int n) {
     if (q.open) { int rc = seq_abort(c); if (rc) return rc; }      // (a sequence that a device error left open: its frames and sums are dropped, not mixed into this one)
     if (const char* why = sequence_refuses(c->frame_format, n, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);      // (a sequence format: writer_wants_sequence)
     { int rc = alloc_slot_format(c); if (rc) return rc; }
-    const size_t stride = (seq_held_bytes(*format_traits(c->frame_format), W, H) + 15) & ~(size_t)15, need = stride * (size_t)n;      // (every frame's place begins on a 16-byte boundary)
+    const FormatTraits& t = writer_traits(c, c->frame_format);
+    const size_t stride = (seq_held_bytes(t, W, H) + 15) & ~(size_t)15, need = stride * (size_t)n;      // (every frame's place begins on a 16-byte boundary)
+    if (seq_is_budget(c) && q.budget.reserve(jpeg_seq_budget_bytes(n, W, H, t.sampling())) != hipSuccess) { (void)hipGetLastError(); return fail(c, POPPY_E_DEVICE, "no device memory for the sequence budget's measured lengths (8 bytes per segment and frame)"); }
     if (q.store.reserve(need) != hipSuccess) { (void)hipGetLastError(); return fail(c, POPPY_E_DEVICE, "no device memory for the sequence's frames (3 * width * height bytes each, half of that as I420 planes, height more as PNG's filtered stream)"); }
     q.stride = stride; q.n = n; q.count = 0; q.open = true;
     return POPPY_OK;
@@ -33,8 +37,10 @@ int seq_begin(poppy_hip_ctx* c, int n) {
 bool seq_wanted(const poppy_hip_ctx* c) { return c->seq.open && writer_wants_sequence(c, c->writer_attached); }
 int seq_pass(poppy_hip_ctx* c, const uint8_t* d_bgr, uint8_t* dst, hipStream_t s, hipEvent_t done) {
     const WriterGeom g = writer_geom(c);
-    const FormatTraits& t = *format_traits(c->frame_format);
-    if (t.coder == kCoderJpeg) {                                   // the planes straight into the frame's place, then their symbols into the sequence's counts
+    const FormatTraits& t = writer_traits(c, c->frame_format);
+    if (t.coder == kCoderJpeg && !t.frame_tables)                  // under a sequence budget: the planes straight into the frame's place, nothing else (the mark behind it is frame_format)
+        (t.raster == kRasterI444 ? launch_bgr_to_i444 : launch_bgr_to_i420)(d_bgr, dst, g.w, g.h, s, done);
+    else if (t.coder == kCoderJpeg) {                              // the planes straight into the frame's place, then their symbols into the sequence's counts
         Timer tm(c, s);
         (t.raster == kRasterI444 ? launch_bgr_to_i444 : launch_bgr_to_i420)(d_bgr, dst, g.w, g.h, s, nullptr);
         if (c->timing == 1) tm.mark("frame_format");
@@ -48,7 +54,7 @@ int seq_pass(poppy_hip_ctx* c, const uint8_t* d_bgr, uint8_t* dst, hipStream_t s
     HIPCHK(c, hipGetLastError());
     return POPPY_OK;
 }
-const char* seq_pass_mark(const poppy_hip_ctx* c) { return seq_is_jpeg(c) ? "jpeg_count" : seq_is_png(c) ? "png_seq_count" : "pal8_seq_hist"; }
+const char* seq_pass_mark(const poppy_hip_ctx* c) { return seq_is_budget(c) ? "frame_format" : seq_is_jpeg(c) ? "jpeg_count" : seq_is_png(c) ? "png_seq_count" : "pal8_seq_hist"; }
 uint8_t* seq_next_place(poppy_hip_ctx* c) { return c->seq.count < c->seq.n ? c->seq.store.p + (size_t)c->seq.count++ * c->seq.stride : nullptr; }
 
 int seq_add_image(poppy_hip_ctx* c, const uint8_t* d_bgr) {
@@ -145,6 +151,24 @@ static void enqueue_seq_png_coding(uint8_t* place, const void* table, uint8_t* f
     if (tm) tm->mark("png_finish");
 }
 
+// ... and of one frame of a sequence under a sequence budget: from its planes on the tables of all qualities, the picked quality read from the sequence's search state
+static void enqueue_seq_jpeg_budget_coding(const uint8_t* planes, const JpegBudget& budget, const uint8_t* state, uint8_t* scratch, uint8_t* frame, void* total_dev, int W, int H, jpeg::Sampling sm, hipStream_t s, Timer* tm) {
+    launch_jpeg_code_picked_by(planes, budget, state, scratch, W, H, sm, s);
+    if (tm) tm->mark("jpeg_code");
+    launch_jpeg_pack_picked_by(budget, state, scratch, frame, (uint32_t*)total_dev, W, H, sm, s);
+    if (tm) tm->mark("jpeg_pack");
+}
+// the sequence budget's search over a store of n frames of planes: kJpegBudgetSteps steps of one measuring launch over segments x frames and one pick, a fixed
+// sequence of dispatches whatever the search finds; behind it `state` holds the one quality
+static void enqueue_seq_jpeg_budget_search(const uint8_t* store, size_t stride, int n, const JpegBudget& budget, uint8_t* state, int W, int H, jpeg::Sampling sm, hipStream_t s, Timer* tm) {
+    for (int step = 0; step < kJpegBudgetSteps; ++step) {
+        launch_jpeg_seq_measure(store, stride, n, budget, state, step, W, H, sm, s);
+        if (tm) tm->mark("jpeg_measure");
+        launch_jpeg_seq_pick(budget, state, n, step, W, H, sm, s);
+        if (tm) tm->mark("jpeg_pick");
+    }
+}
+
 // Every frame of a coded sequence: coded from its place in the store (GIF_SEQ: k_gif_lzw_bgr, no index plane; the JPEG sequences: k_jpeg_code and k_jpeg_pack in their
 // OPT forms on the sequence's tables) into one of R device buffers, each followed by the coder's scratch, on the ring buffer's own stream; the coder's last kernel
 // stores the frame's length into the ring buffer's pinned word.  The host waits for that stream, reads the word, bounds-checks it
@@ -155,7 +179,9 @@ static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* use
     const WriterGeom g = writer_geom(c);
     const int n = q.count, W = g.w, H = g.h;
     const bool marks = c->timing == 1;
-    const FormatTraits& t = *format_traits(c->frame_format);
+    const FormatTraits& t = writer_traits(c, c->frame_format);
+    JpegBudget seq_budget;
+    if (seq_is_budget(c)) { int rc = context_jpeg_seq_budget(c, &seq_budget); if (rc) return rc; }
     const size_t capacity = poppy_frame_bytes(t.format, W, H), frame_part = (capacity + 16 + 255) & ~(size_t)255;
     const size_t each = frame_part + (t.coder == kCoderPng ? 0 : (coding_scratch_bytes(t, W, H) + 255) & ~(size_t)255);      // (a PNG frame's scratch is its place in the store)
     WriterRing ring;
@@ -192,6 +218,7 @@ static int seq_hand_over_coded(poppy_hip_ctx* c, poppy_write_cb write, void* use
         } else
 #endif
         if (t.coder == kCoderPng) enqueue_seq_png_coding(q.store.p + (size_t)k * q.stride, seq_png_table(q), d_frame(k), q.coded_total_dev + 64 * (size_t)(k % ring.R), W, H, s, marks ? &tm : nullptr);
+        else if (seq_budget) enqueue_seq_jpeg_budget_coding(q.store.p + (size_t)k * q.stride, seq_budget, q.budget.p, d_frame(k) + frame_part, d_frame(k), q.coded_total_dev + 64 * (size_t)(k % ring.R), W, H, t.sampling(), s, marks ? &tm : nullptr);
         else if (t.coder == kCoderJpeg) enqueue_seq_jpeg_coding(q.store.p + (size_t)k * q.stride, c->jpeg_tables, seq_jpeg_built(q), d_frame(k) + frame_part, d_frame(k), q.coded_total_dev + 64 * (size_t)(k % ring.R), W, H, t.sampling(), s, marks ? &tm : nullptr);
         else enqueue_seq_gif_coding(q.store.p + (size_t)k * q.stride, q.tables, d_frame(k) + frame_part, d_frame(k), q.coded_total_dev + 64 * (size_t)(k % ring.R), W, H, s, marks ? &tm : nullptr);
         HIPCHK(c, hipGetLastError());
@@ -231,7 +258,14 @@ static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
     PaletteSeq& q = c->seq;
     q.open = false;
     { int rc = drain_frames(c); if (rc) return rc; }              // every pass has added its frame (they ran on the slots' streams)
-    {
+    if (seq_is_budget(c)) {                                        // the one search over the store, in place of a build
+        const WriterGeom g = writer_geom(c);
+        JpegBudget budget;
+        { int rc = context_jpeg_seq_budget(c, &budget); if (rc) return rc; }
+        Timer tm(c, c->stream);
+        if (c->timing == 1) tm.mark(nullptr);
+        enqueue_seq_jpeg_budget_search(q.store.p, q.stride, q.count, budget, q.budget.p, g.w, g.h, writer_traits(c, c->frame_format).sampling(), c->stream, c->timing == 1 ? &tm : nullptr);
+    } else {
         Timer tm(c, c->stream);
         if (c->timing == 1) tm.mark(nullptr);
         if (seq_is_png(c)) launch_png_seq_table(seq_png_sums(q), seq_png_table(q), c->stream);      // once, on the sums: they are zero behind it
@@ -240,7 +274,7 @@ static int seq_hand_over(poppy_hip_ctx* c, poppy_write_cb write, void* user) {
         if (c->timing == 1) tm.mark(seq_is_png(c) ? "png_seq_table" : seq_is_jpeg(c) ? "jpeg_tables" : "pal8_seq_build");
     }
     HIPCHK(c, hipGetLastError());
-    if (!format_traits(c->frame_format)->coded()) return seq_hand_over_indices(c, write, user);
+    if (!writer_traits(c, c->frame_format).coded()) return seq_hand_over_indices(c, write, user);
     HIPCHK(c, hipStreamSynchronize(c->stream));                   // the ring's streams read the tables
     return seq_hand_over_coded(c, write, user);
 }
@@ -342,6 +376,60 @@ int poppy_hip_bgr_frames_to_jpeg_seq_frames(poppy_hip_ctx* c, const uint8_t* bgr
 }
 int poppy_hip_bgr_frames_to_jpeg444_seq_frames(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int W, int H, int quality, uint8_t* dst) {
     return jpeg_seq_code_host_frames(c, POPPY_FRAME_JPEG444_SEQ, bgr, stride, frame_stride, n_frames, W, H, quality, dst);
+}
+
+// the body of poppy_hip_bgr_frames_to_jpeg_seq_budget_frames and its 4:4:4 twin: host BGR frames up one by one, each through the raster kernel into a store of
+// planes, the sequence budget's search once over the store on the call's own words, every frame coded at the picked quality and `total` bytes of it down — all on
+// buffers that live for the call; of the context only its tables of all qualities are used, and its own budgets and quality are neither read nor touched
+static int jpeg_seq_budget_code_host_frames(poppy_hip_ctx* c, int fmt, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int W, int H, int quality_max, uint64_t budget, uint8_t* dst, int* quality_used) {
+    if (!c) return POPPY_E_ARG;
+    if (!bgr || !dst || W <= 0 || H <= 0 || stride < (size_t)W * 3 || n_frames < 1 || quality_max < 1 || quality_max > 100 || budget == 0) return fail(c, POPPY_E_ARG, "bad arguments");
+    if (frame_stride < stride * ((size_t)H - 1) + (size_t)W * 3) return fail(c, POPPY_E_ARG, "bad arguments: the frames overlap");
+    if (const char* why = format_refuses(fmt, W, H)) return fail(c, POPPY_E_UNSUPPORTED, why);
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = ensure_jpeg_budget_tables(c); if (rc) return rc; }
+    const FormatTraits& t = *format_traits(fmt);
+    const jpeg::Sampling sm = t.sampling();
+    const size_t row = (size_t)W * 3, place = (raster_bytes(t.raster, (size_t)W, (size_t)H) + 15) & ~(size_t)15, capacity = poppy_frame_bytes(fmt, W, H);
+    const JpegSeqBudgetParams p{(uint32_t)budget, (uint32_t)quality_max, (uint32_t)(budget >> 32), 0};
+    CallBuffers held;
+    uint8_t *d_bgr = nullptr, *store = nullptr, *state = nullptr, *d_params = nullptr, *work = nullptr, *frame = nullptr;
+    hipError_t e = held.alloc(&d_bgr, row * H + 16);
+    if (e == hipSuccess) e = held.alloc(&store, place * (size_t)n_frames);
+    if (e == hipSuccess) e = held.alloc(&state, jpeg_seq_budget_bytes(n_frames, W, H, sm));
+    if (e == hipSuccess) e = held.alloc(&d_params, sizeof p);
+    if (e == hipSuccess) e = held.alloc(&work, jpeg_scratch_bytes(W, H, sm, false));
+    if (e == hipSuccess) e = held.alloc(&frame, capacity + 16);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_params, &p, sizeof p, hipMemcpyHostToDevice, c->stream);
+    JpegBudget of_call;
+    of_call.tables = c->jpeg_budget_tables; of_call.params = d_params;
+    for (int k = 0; k < n_frames && e == hipSuccess; ++k) {      // (the one BGR buffer: the upload is ordered behind the raster kernel that read the frame before)
+        e = copy_rows_async(d_bgr, row, bgr + (size_t)k * frame_stride, stride, row, (size_t)H, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) break;
+        (sm == jpeg::k444 ? launch_bgr_to_i444 : launch_bgr_to_i420)(d_bgr, store + (size_t)k * place, W, H, c->stream, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) { enqueue_seq_jpeg_budget_search(store, place, n_frames, of_call, state, W, H, sm, c->stream, nullptr); e = hipGetLastError(); }
+    int rc = POPPY_OK;
+    for (int k = 0; k < n_frames && e == hipSuccess && rc == POPPY_OK; ++k) {
+        uint32_t total = 0;
+        enqueue_seq_jpeg_budget_coding(store + (size_t)k * place, of_call, state, work, frame, nullptr, W, H, sm, c->stream, nullptr);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&total, frame, 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess && !coded_length_ok(total, capacity, t.least)) rc = fail(c, POPPY_E_DEVICE, "the coded frame's length is outside its bounds");
+        else if (e == hipSuccess) e = hipMemcpy(dst + (size_t)k * capacity, frame, total, hipMemcpyDeviceToHost);
+    }
+    (void)hipStreamSynchronize(c->stream);                         // nothing of the call is in flight when its buffers and `p` go (`held`, at the return)
+    if (e != hipSuccess) { (void)hipGetLastError(); c->err = std::string("JPEG sequence budget coding: ") + hipGetErrorString(e); return POPPY_E_DEVICE; }
+    if (rc == POPPY_OK && quality_used) *quality_used = poppy_jpeg_frame_quality(dst);
+    return rc;
+}
+int poppy_hip_bgr_frames_to_jpeg_seq_budget_frames(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int W, int H, int quality_max, uint64_t budget, uint8_t* dst, int* quality_used) {
+    return jpeg_seq_budget_code_host_frames(c, POPPY_FRAME_JPEG, bgr, stride, frame_stride, n_frames, W, H, quality_max, budget, dst, quality_used);
+}
+int poppy_hip_bgr_frames_to_jpeg444_seq_budget_frames(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, size_t frame_stride, int n_frames, int W, int H, int quality_max, uint64_t budget, uint8_t* dst, int* quality_used) {
+    return jpeg_seq_budget_code_host_frames(c, POPPY_FRAME_JPEG444, bgr, stride, frame_stride, n_frames, W, H, quality_max, budget, dst, quality_used);
 }
 
 // host BGR frames up one by one, each through the pass of a PNG sequence (filter, counting kernel) into a store of places, one table build, every frame coded on its

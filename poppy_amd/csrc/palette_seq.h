@@ -16,12 +16,17 @@
 // stream padded to whole segments, h (1 + 3 w) bytes and under 0.5 % on top at 1080p, 6.2 MB a frame, 374 MB for 60), so that the frame's coder later runs on its
 // place and the ring buffers carry no scratch.  The store is kept between sequences and grown when needed, like the others'; it goes with the context.  Every frame's
 // tokens are added into `png` (kernels.h: kPngSeqTableBytes — the 286 sums, zero between sequences, then the one table built from them).
+// POPPY_FRAME_JPEG and POPPY_FRAME_JPEG444 under a sequence budget (poppy_hip_set_jpeg_sequence_budget; frame_format.h: writer_traits) are held back as the JPEG
+// sequences are, as planes, but nothing is counted and no table built: the pass is the raster kernel alone, and seq_finish runs the budget's search ONCE over the
+// store — kJpegBudgetSteps steps of one measuring launch over segments x frames and one pick on `budget` — and then codes every frame at the one picked quality
+// through the ring of coded frames.  Nothing of it needs clearing between sequences: the first step starts the search from the context's words.
 struct PaletteSeq {
     uint8_t* tables = nullptr;
     uint8_t* jpeg = nullptr;
     uint8_t* png = nullptr;
     DeviceBuffer store; size_t stride = 0;
     DeviceBuffer idx, coded;
+    DeviceBuffer budget;                  // POPPY_FRAME_JPEG / JPEG444 under a sequence budget: the sequence's one search state, then the lengths its steps measure (kernels.h: jpeg_seq_budget_bytes)
     uint32_t* coded_total = nullptr; uint8_t* coded_total_dev = nullptr;      // kStageRing words, 64 bytes apart
     bool open = false;                    // a sequence is being collected: frames for the writer go through the pass into the store
     int n = 0, count = 0;                 // its frames, and how many of them have been queued

@@ -327,6 +327,11 @@ int poppy_hip_pool_set_jpeg_budget(poppy_hip_pool* p, size_t max_frame_bytes) {
     return pool_set(p, [=](poppy_hip_ctx* c) { return poppy_hip_set_jpeg_budget(c, max_frame_bytes); });
 }
 
+int poppy_hip_pool_set_jpeg_sequence_budget(poppy_hip_pool* p, uint64_t max_sequence_bytes) {
+    if (!p) return POPPY_E_ARG;
+    return pool_set(p, [=](poppy_hip_ctx* c) { return poppy_hip_set_jpeg_sequence_budget(c, max_sequence_bytes); });
+}
+
 int poppy_hip_pool_set_frame_scale(poppy_hip_pool* p, int factor) {
     if (!p || factor < 1 || factor > POPPY_FRAME_SCALE_MAX) return POPPY_E_ARG;
     return pool_set(p, [=](poppy_hip_ctx* c) { return poppy_hip_set_frame_scale(c, factor); });

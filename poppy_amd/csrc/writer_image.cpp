@@ -35,7 +35,7 @@ static int coded_from_device(poppy_hip_ctx* c, const FormatTraits& t, const uint
 
 int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const WriterGeom& g, std::vector<uint8_t>& host, size_t* stride, int n_copies) {
     const int fmt = c->frame_format;
-    const FormatTraits& t = *format_traits(fmt);
+    const FormatTraits& t = writer_traits(c, fmt);
     if (const char* why = format_refuses(fmt, g.w, g.h)) return fail(c, POPPY_E_UNSUPPORTED, why);
     if (g.scaled()) {                                              // scaled first, on the device; everything below is in the writer's geometry
         int rc = scale_into_scratch(c, d_bgr, W, H, g); if (rc) return rc;
@@ -70,7 +70,7 @@ int download_frame(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, const W
 
 const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, std::vector<uint8_t>& tmp, size_t* out_stride, int* status, int n_copies) {
     const int fmt = c->frame_format;
-    const FormatTraits& t = *format_traits(fmt);
+    const FormatTraits& t = writer_traits(c, fmt);
     *out_stride = stride;
     *status = POPPY_OK;
     if (t.raster == kRasterNone && !t.coded()) return bgr;
@@ -78,7 +78,8 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
     tmp.resize(poppy_frame_bytes(fmt, W, H));
     std::vector<uint8_t> pal8(t.sequence && t.coder == kCoderGif ? raster_bytes(kRasterPal8, W, H) : 0);      // (GIF_SEQ: PAL8_SEQ's frame, then the host coder)
     int rc = POPPY_OK;                                             // the host statement of the record's steps
-    if (t.sequence && t.coder == kCoderJpeg) rc = jpeg_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, c->jpeg_quality, fmt, tmp.data());
+    if (t.sequence && t.coder == kCoderJpeg && !t.frame_tables) rc = jpeg_seq_budget_of_copies(bgr, stride, std::max(1, n_copies), W, H, c->jpeg_quality, c->jpeg_seq_budget, fmt, tmp.data());
+    else if (t.sequence && t.coder == kCoderJpeg) rc = jpeg_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, c->jpeg_quality, fmt, tmp.data());
     else if (t.sequence && t.coder == kCoderPng) rc = png_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, tmp.data());
     else if (t.sequence) rc = pal8_seq_of_copies(bgr, stride, std::max(1, n_copies), W, H, pal8.empty() ? tmp.data() : pal8.data());
     else if (t.coder == kCoderGif) rc = poppy_bgr_to_gif_frame(bgr, stride, W, H, tmp.data());

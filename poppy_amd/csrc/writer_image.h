@@ -15,5 +15,6 @@ const uint8_t* host_frame(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, i
 int write_device_image(poppy_hip_ctx* c, const uint8_t* d_bgr, int W, int H, int n_copies, poppy_write_cb write, void* user);      // a device image / a host image to the writer, n_copies times, in the writer's format (the phase 0 / 1 and t = 0 / 1 copies, the linear-blend fallback frames)
 int write_host_image(poppy_hip_ctx* c, const uint8_t* bgr, size_t stride, int W, int H, int n_copies, poppy_write_cb write, void* user);
 int jpeg_seq_of_copies(const uint8_t* bgr, size_t stride, int n_copies, int width, int height, int quality, int format, uint8_t* dst);      // frame_jpeg.cpp: the POPPY_FRAME_JPEG_SEQ / JPEG444_SEQ (`format`) frame of a sequence that is n_copies times the same BGR frame: its counts n_copies times in the sums, one frame out
+int jpeg_seq_budget_of_copies(const uint8_t* bgr, size_t stride, int n_copies, int width, int height, int quality_max, uint64_t budget, int format, uint8_t* dst);      // frame_jpeg_seq_budget.cpp: the POPPY_FRAME_JPEG / JPEG444 (`format`) frame of a sequence under a sequence budget that is n_copies times the same BGR frame: its size n_copies times in the sums, one frame out
 int png_seq_of_copies(const uint8_t* bgr, size_t stride, int n_copies, int width, int height, uint8_t* dst);      // frame_png_seq.cpp: the POPPY_FRAME_PNG_SEQ frame of a sequence that is n_copies times the same BGR frame: its counts n_copies times in the sums, one frame out
 int pal8_seq_of_copies(const uint8_t* bgr, size_t stride, int n_copies, int width, int height, uint8_t* dst);      // frame_pal8.cpp: the POPPY_FRAME_PAL8_SEQ frame of a sequence that is n_copies times the same BGR frame (poppy_bgr_frames_to_pal8 with frame_stride 0, one frame out)
